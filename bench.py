@@ -25,6 +25,9 @@ Timing: W warm-up steps, then exactly K steps bracketed by barrier + torch.cuda.
 region is run three times and the MEDIAN is reported (`timing` says so).  Rank 0 prints ONE JSON line.
 `roofline` comes from a second pass over the same K steps with per-kernel HIP events (gnx_profile_*); `cpu_baseline` from
 the oracle's C restatement (test infrastructure) on the host cores.
+`--dump-outputs DIR` (one GPU): after the timed region, the outputs of its last step (ef / nf / gf; --model c4: the model's) go to
+DIR/<name>.npy as float32, at most 64 MB in all (a fixed, seeded sample of the rows beyond that).  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 The default N = 1 invocation also carries `"secondary"`: the other BASELINE configs measured by the same script in the same run —
 core dims on C2, C3 (configs[2]), C5 on one GPU (configs[4]'s batch), C4 (configs[3]) and README ex.3 at its own widths — each with
 ms_per_step, roofline (traffic + provenance), cpu_baseline and, for the hetero batches, the cost of `batch()` itself.  They run as
@@ -322,6 +325,8 @@ def bench_c4(args, gn, torch, dev, c_abi=None):
         torch.cuda.synchronize(dev)
         reps.append((time.perf_counter() - t0) / K)
     dt = float(np.median(reps))
+    if args.dump_outputs is not None:  # the model's outputs as the last replay left them (the captured output buffers, [D][T][R] views)
+        dump_outputs(args.dump_outputs, {k: None if getattr(graphed._out, k) is None else getattr(graphed._out, k).permute(2, 1, 0) for k in ("ef", "nf", "gf")})
     E, N = g.n_edges, g.n_nodes
     if core == (128, 64, 32):
         aflops = 699.2e9  # whole-model algorithmic FLOPs at 1M edges
@@ -592,6 +597,40 @@ def emit(line, args, tag):
     if sec:
         print("bench-secondary (not the result line): " + json.dumps(secondary_summary(sec)), flush=True)
     print(json.dumps(compact_line(line, rel)), flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: cap on the bytes written in all
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs DIR: what the timed path's last step computed, as DIR/<name>.npy (float32, the packed [R][T][D] layout of the outputs).
+    `arrays` maps names to tensors / arrays of that layout (None: an output of width 0, not written).  When the whole set is larger than
+    `max_bytes`, every array keeps one row plus the same fraction of its other rows, a seeded sample that depends only on the array's name and
+    shape (sorted row indices), so two builds run with the same arguments write the same rows.  Returns {name: (shape written, rows of the full
+    output)}."""
+    import zlib
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    nbytes = {k: int(np.prod(tuple(v.shape))) * 4 for k, v in arrays.items()}
+    row_bytes = sum(n // max(int(arrays[k].shape[1]), 1) for k, n in nbytes.items())
+    total, budget = sum(nbytes.values()), max_bytes - 1024 * len(arrays)  # (1 KB per file for its .npy header)
+    frac = 1.0 if total <= budget else (budget - row_bytes) / total  # (1 + frac * (T - 1) rows of each: at most the budget in all)
+    assert frac > 0, "--dump-outputs: one row of every output is already above the cap"
+    import torch  # (the arrays are device tensors; numpy arrays in the CPU tests)
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        T = int(a.shape[1])
+        keep = T if frac >= 1.0 else min(T, 1 + int((T - 1) * frac))
+        if keep < T:
+            rows = np.sort(np.random.default_rng(zlib.crc32(f"{name}:{tuple(a.shape)}".encode())).choice(T, keep, replace=False))
+            if isinstance(a, torch.Tensor):  # only the sampled rows leave the GPU
+                a = a.index_select(1, torch.from_numpy(rows).to(a.device))
+            else:
+                a = np.asarray(a)[:, rows]
+        host = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
+        np.save(os.path.join(path, name + ".npy"), host)
+        written[name] = (tuple(host.shape), T)
+    return written
 
 
 SECONDARY = [  # (key, extra argv, BASELINE config it stands for)
@@ -1153,9 +1192,14 @@ def main():
     ap.add_argument("--core-dims", type=str, default="128,64,32", help="core widths for --model c4 (README ex.3 uses 10,5,3)")
     ap.add_argument("--model", choices=["block", "c4"], default="block",
                     help="c4: BASELINE configs[3] — encoder -> 2 x GNCore(128,64,32) -> decoder on the C2 graph (extra; not the headline line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path's last step computed (ef / nf / gf, float32, packed [R][T][D]) as DIR/<name>.npy, "
+                         "at most 64 MB in all (a fixed, seeded sample of the rows of a larger output); one GPU only")
     args = ap.parse_args()
     if args.steps < 1 or args.steps > 5000 or args.warmup < 0:  # (K steps are captured into ONE hipGraph: six-figure node counts crash the runtime's capture)
         ap.error("--steps must be in 1..5000 and --warmup >= 0")
+    if args.dump_outputs is not None and (args.gpus != 1 or args.force_dist or args.dist_backend != "torch" or "RANK" in os.environ):
+        ap.error("--dump-outputs is for one GPU (the single-GPU block and --model c4 paths)")
 
     if args.dist_backend == "gnx":
         return bench_dist_gnx(args)
@@ -1367,6 +1411,8 @@ def main():
     spin_up(torch, dev, cold.replay)
     reps = sorted(timed(cold.replay) for _ in range(3))
     dt = reps[1]
+    if args.dump_outputs is not None:  # the timed region's last step wrote the outputs of buffer set (K - 1) mod nsets
+        dump_outputs(args.dump_outputs, dict(zip(("ef", "nf", "gf"), sets[(K - 1) % nsets]["out"])))
     if steps_form:
         sep = capture(K, True)
         sep.replay(); torch.cuda.synchronize(dev)

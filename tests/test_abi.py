@@ -117,9 +117,12 @@ def test_c_language_binding_compiles_links_and_validates():
 
 def test_host_shim_under_address_sanitizer():
     """libgnx's host translation units built with g++ -fsanitize=address,undefined and driven through adjacency /
-    CSC validation, tile construction, failed handle creation, model validation, the run-time specialiser and the profiler."""
+    CSC validation, tile construction, failed handle creation, model validation, the run-time specialiser and the profiler.  The driver
+    runs as on a machine without a GPU wherever it runs: the devices are hidden from it, and leaks inside the ROCm runtime's own
+    initialisation are suppressed (tests/c/lsan_rocm.supp)."""
     import subprocess
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
+               LSAN_OPTIONS="suppressions=" + os.path.join(ROOT, "tests", "c", "lsan_rocm.supp") + ":print_suppressions=0", ROCR_VISIBLE_DEVICES="-1")
     out = subprocess.run([os.path.join(_make_c_tests(), "host_asan_driver")], capture_output=True, text=True, env=env)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     assert "host_asan_driver: ok" in out.stdout

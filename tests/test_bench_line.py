@@ -116,6 +116,7 @@ def test_live_traffic_falls_back_without_a_gpu_and_the_compact_line_says_where_t
     no GPU (here), a pass that overruns — the call returns None with the reason and the committed profile's figure stays; the compact line names
     the origin either way and stays under its cap."""
     import bench
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")  # the profiled child sees no GPU on any machine (it inherits this environment)
     got, rec = bench.live_traffic("k_block_wave", ["--gpus", "1", "--steps", "2", "--warmup", "1"], timeout_s=120)
     assert got is None and rec["live"] is False and rec["why"]
     monkeypatch.setattr(__import__("shutil"), "which", lambda name: None)
