@@ -1354,7 +1354,7 @@ class BlockPlan:
     def steps(self, sets, stream=None):
         """`gnx_block_forward_steps`: a LOOP over batches as one call — `sets` is a sequence of dicts / tuples (ef, nf, gf, eo, no, go, ws), one per
         step, in order.  Exactly `len(sets)` forwards (bit-identical outputs); where the two-launch narrow form runs, step i's graph update rides at
-        the front of step i + 1's launch and the last one is flushed inside the call: every output is complete when the enqueued work is.
+        the front of a later launch (step i + 2's: neighbouring steps run on two streams) and the last ones are flushed inside the call: every output is complete when the enqueued work is.
         Consecutive steps must use different workspaces and gf outputs to be chained (else the step simply runs unchained)."""
         s = torch.cuda.current_stream(self.g.device).cuda_stream if stream is None else stream
         arr = (_lib.BlockStep * max(len(sets), 1))()

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "gnx_device.h"
+#include "gnx_step_hazard.h"
 
 namespace gnx {
 
@@ -30,6 +31,7 @@ void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p);
 bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
 bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1, int act2);
 bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a);
+bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
 int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
 static_assert(GNX_ACT_IDENTITY == 0 && GNX_ACT_RELU == 1 && GNX_ACT_TANH == 2 && GNX_ACT_SIGMOID == 3 && GNX_ACT_GELU == 4,
               "act_apply (gnx_device.h) hard-codes the activation codes");
@@ -196,6 +198,8 @@ extern "C" int32_t gnx_ensure_collapse(const gnx_graphs* h);
 
 using namespace gnx;
 
+static void ensure_aux(const gnx_graphs* h);
+
 extern "C" {
 
 size_t gnx_block_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
@@ -204,6 +208,7 @@ size_t gnx_block_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p,
     warm_block_narrow(h, p);        // run-time specialisation happens here, not in a capture
     warm_block_wide(h, p, false);   // ... and so does the build of the matrix-core tables when these widths take that path
   }
+  ensure_aux(h);  // the side streams of gnx_block_forward_steps' two-stream schedule (created outside any capture)
   return block_ws(h, p, R).total;
 }
 
@@ -241,34 +246,124 @@ int32_t gnx_block_forward_chained(const gnx_graphs* h, const gnx_block_params* p
   return block_forward_impl(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream, 3);
 }
 
+// the bytes a step reads and writes (gnx_step_hazard.h); the workspace is the part the block's kernels use
+static StepSpans step_spans(const gnx_graphs* h, const gnx_block_params* p, int64_t R, const gnx_block_step& st) {
+  const size_t f = sizeof(float) * (size_t)R;
+  StepSpans sp;
+  sp.rd[0] = byte_span(st.ef, f * h->E * p->de);
+  sp.rd[1] = byte_span(st.nf, f * h->N * p->dn);
+  sp.rd[2] = byte_span(st.gf, f * h->G * p->dg);
+  sp.wr[0] = byte_span(st.ef_out, f * h->E * p->oe);
+  sp.wr[1] = byte_span(st.nf_out, f * h->N * p->on);
+  sp.wr[2] = byte_span(st.gf_out, f * h->G * p->og);
+  sp.wr[3] = byte_span(st.workspace, std::min(st.workspace_bytes, block_ws(h, p, R).total));
+  return sp;
+}
+
+// Can the steps of this call run on two streams?  The fused narrow kernel (plain, chained, pack form, run-time specialised) only: the
+// matrix-core widths keep one stream (concurrent matrix kernels: DeviceTurn's history), and so do the generic kernels.
+static bool steps_overlap_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R, uint32_t flags, hipStream_t s) {
+  if (!h || !p || matrix_core_widths(*p) || (flags & GNX_FLAG_FORCE_GENERIC) || form(GNX_FLAG_NO_FORK) || profile_enabled()) return false;
+  if (check_block(h, p, R) != GNX_OK) return false;  // (the one-stream loop reports it)
+  BlockArgs a{};
+  a.de = p->de; a.dn = p->dn; a.dg = p->dg; a.oe = p->oe; a.on = p->on; a.og = p->og;
+  a.n_wtiles = (int)h->n_wtiles(); a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G;
+  return block_narrow_takes(h, a, s);
+}
+
 int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step* steps, int64_t n_steps, int64_t R, uint32_t flags,
                                 void* stream) {
   if (n_steps < 0 || (n_steps > 0 && !steps)) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps: steps is NULL / n_steps is negative");
   if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps finishes every step's graph update itself");
   DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));  // (one turn for the whole loop; the calls below nest inside it)
-  gnx_pending_update pend{};
-  auto flush = [&]() -> int32_t {
-    if (!pend.workspace) return GNX_OK;
-    const int32_t rc = gnx_block_graph_update(h, p, pend.gf, R, pend.gf_out, const_cast<void*>(pend.workspace), pend.workspace_bytes, flags, stream);
-    pend = gnx_pending_update{};
+  FormScope forms(flags);
+  // Two streams: even steps on the caller's, odd steps on a side stream of the handle's pool (taken as gnx_core_forward takes it), so that
+  // step i + 1's launch fills the slots that step i's ramp and drain leave idle and the per-launch cost of one hides under the other.
+  // Every set taken, GNX_FLAG_NO_FORK, the per-kernel profiler on, or not the fused narrow kernel: one stream, the loop as before.
+  std::unique_lock<std::mutex> aux_lk;
+  const gnx_graphs::AuxSet* aux = nullptr;
+  if (n_steps > 1 && steps_overlap_applies(h, p, R, flags, (hipStream_t)stream))
+    for (auto& ax : h->aux) {
+      if (!ax.stream || !ax.step[3]) break;
+      std::unique_lock<std::mutex> lk(ax.mu, std::try_to_lock);
+      if (lk.owns_lock()) { aux_lk = std::move(lk); aux = &ax; break; }
+    }
+  hipStream_t str[2] = {(hipStream_t)stream, aux ? aux->stream : nullptr};
+  // the pending graph update of each stream: step i's rides at the front of the next launch on ITS stream (step i + 1's on
+  // one stream, step i + 2's on two)
+  gnx_pending_update pend[2]{};
+  auto flush = [&](int k) -> int32_t {
+    if (!pend[k].workspace) return GNX_OK;
+    const int32_t rc = gnx_block_graph_update(h, p, pend[k].gf, R, pend[k].gf_out, const_cast<void*>(pend[k].workspace), pend[k].workspace_bytes, flags, str[k]);
+    pend[k] = gnx_pending_update{};
     return rc;
   };
-  for (int64_t i = 0; i < n_steps; ++i) {
+  if (!aux) {
+    StepSpans prev;
+    const bool valid = h && p && check_block(h, p, R) == GNX_OK;  // (else the first step reports the error)
+    for (int64_t i = 0; i < n_steps; ++i) {
+      const gnx_block_step& st = steps[i];
+      // a step whose buffers overlap its predecessor's (a shared workspace / gf_out, or gf' read as the next step's input) cannot start
+      // before that one's graph update has run
+      const StepSpans cur = valid ? step_spans(h, p, R, st) : StepSpans{};
+      if (pend[0].workspace && (pend[0].workspace == st.workspace || (p && p->og > 0 && pend[0].gf_out == st.gf_out) || steps_conflict(cur, prev))) {
+        if (int32_t rc = flush(0)) return rc;
+      }
+      prev = cur;
+      gnx_pending_update next{};
+      if (int32_t rc = gnx_block_forward_chained(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[0],
+                                                 pend[0].workspace ? &pend[0] : nullptr, &next)) {
+        // (an argument error of step i: what is pending belongs to step i - 1, whose arguments were valid — finish it, report the error)
+        (void)flush(0);
+        return rc;
+      }
+      pend[0] = next;
+    }
+    return flush(0);
+  }
+  // The schedule and its hazard rule: gnx_step_hazard.h (step_order).  Step i waits for step i - 3's launch (the ring of events aux->step),
+  // so that only steps up to three apart can be in flight together; conflicts among those are ordered as step_order says.
+  GNX_HIP(hipEventRecord(aux->fork, str[0]));
+  GNX_HIP(hipStreamWaitEvent(str[1], aux->fork, 0));
+  StepSpans recent[3];  // steps i - 1, i - 2, i - 3
+  int32_t rc = GNX_OK;
+  for (int64_t i = 0; i < n_steps && rc == GNX_OK; ++i) {
     const gnx_block_step& st = steps[i];
-    // a step that shares its predecessor's workspace / gf_out cannot start before that one's graph update has run
-    if (pend.workspace && (pend.workspace == st.workspace || (p && p->og > 0 && pend.gf_out == st.gf_out))) {
-      if (int32_t rc = flush()) return rc;
+    const int k = (int)(i & 1), o = k ^ 1;
+    const StepSpans cur = step_spans(h, p, R, st);
+    const StepOrder ord = step_order(cur, recent, i);
+    if (ord.flush_own && (rc = flush(k))) break;
+    if (i >= 3) {
+      const hipError_t e = hipStreamWaitEvent(str[k], aux->step[(i - 3) & 3], 0);
+      if (e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: ordering a step behind the step three before it"); break; }
+    }
+    if (ord.after_other) {
+      if ((rc = flush(o))) break;
+      hipEvent_t ev = o == 1 ? aux->join : aux->fork;
+      hipError_t e = hipEventRecord(ev, str[o]);
+      if (e == hipSuccess) e = hipStreamWaitEvent(str[k], ev, 0);
+      if (e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: ordering a step behind the other stream"); break; }
     }
     gnx_pending_update next{};
-    if (int32_t rc = gnx_block_forward_chained(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, stream,
-                                               pend.workspace ? &pend : nullptr, &next)) {
-      // (an argument error of step i: what is pending belongs to step i - 1, whose arguments were valid — finish it, report the error)
-      (void)flush();
-      return rc;
-    }
-    pend = next;
+    rc = gnx_block_forward_chained(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[k],
+                                   pend[k].workspace ? &pend[k] : nullptr, &next);
+    if (rc != GNX_OK) break;
+    pend[k] = next;
+    // (step[i & 3] was last recorded for step i - 4, and the wait on that record — step i - 1's — is already enqueued)
+    if (const hipError_t e = hipEventRecord(aux->step[i & 3], str[k]); e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: step event"); break; }
+    recent[2] = recent[1]; recent[1] = recent[0]; recent[0] = cur;
   }
-  return flush();
+  // the last two steps' graph updates (one per stream), then the join — on every path, so that a capture never ends with the side stream
+  // un-joined and an error leaves everything issued so far complete when the caller's stream is
+  const int32_t rf0 = flush(0), rf1 = flush(1);
+  const hipError_t e1 = hipEventRecord(aux->join, str[1]);
+  const hipError_t e2 = hipStreamWaitEvent(str[0], aux->join, 0);
+  if (rc) return rc;
+  if (rf0) return rf0;
+  if (rf1) return rf1;
+  GNX_HIP(e1);
+  GNX_HIP(e2);
+  return GNX_OK;
 }
 
 int32_t gnx_block_graph_update(const gnx_graphs* h, const gnx_block_params* p, const float* gf, int64_t R, float* gf_out, void* ws,
@@ -306,10 +401,16 @@ static void ensure_aux(const gnx_graphs* h) {
     for (auto& ax : h->aux) {
       hipStream_t st = nullptr;
       hipEvent_t e1 = nullptr, e2 = nullptr;
-      if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess &&
-          hipEventCreateWithFlags(&e2, hipEventDisableTiming) == hipSuccess) {
+      hipEvent_t es[4] = {};
+      bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess &&
+                hipEventCreateWithFlags(&e2, hipEventDisableTiming) == hipSuccess;
+      for (auto& e : es) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+      if (ok) {
         ax.stream = st; ax.fork = e1; ax.join = e2;
+        for (int j = 0; j < 4; ++j) ax.step[j] = es[j];
       } else {
+        for (hipEvent_t e : es)
+          if (e) (void)hipEventDestroy(e);
         if (e1) (void)hipEventDestroy(e1);
         if (e2) (void)hipEventDestroy(e2);
         if (st) (void)hipStreamDestroy(st);

@@ -690,6 +690,8 @@ int32_t gnx_graphs_destroy(gnx_graphs* h) {
   for (auto& ax : h->aux) {
     if (ax.fork) (void)hipEventDestroy(ax.fork);
     if (ax.join) (void)hipEventDestroy(ax.join);
+    for (hipEvent_t e : ax.step)
+      if (e) (void)hipEventDestroy(e);
     if (ax.stream) (void)hipStreamDestroy(ax.stream);
   }
   delete h;

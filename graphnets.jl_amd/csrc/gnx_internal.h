@@ -121,7 +121,8 @@ struct gnx_graphs {
   // record that precedes it), so concurrent forwards on one handle — distinct buffers, distinct streams — each get their side stream; a caller
   // that finds every set taken runs on its own stream alone.  Apart from the lazily built tables (mutex-guarded) a handle is immutable.
   static constexpr int kAuxSets = 4;
-  struct AuxSet { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; std::mutex mu; };
+  // step[]: gnx_block_forward_steps' ring of per-step events (step i waits for step i - 3's end: gnx_forward.hip)
+  struct AuxSet { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; hipEvent_t step[4] = {}; std::mutex mu; };
   mutable std::once_flag aux_once;
   mutable AuxSet aux[kAuxSets];
   int64_t n_tiles() const { return n_tiles_; }

@@ -24,8 +24,7 @@ static int partial_rows(const gnx_graphs* h) { return (int)(h->G == 1 ? (h->n_wt
 // Threads of the graph update: one wavefront per graph while a graph has <= 256 partial rows (the usual heterogeneous batch:
 // C3 has ~16 rows per graph, C5 ~3), else 256, and 1024 from 1024 rows on (C2: 2032 rows, two per thread in flight at once).
 static int graph_update_threads(const gnx_graphs* h) {
-  const int64_t rows = h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->max_wtiles_per_graph;
-  return rows <= 256 ? 64 : (rows >= 1024 ? 1024 : 256);
+  return graph_update_threads_for_rows(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->max_wtiles_per_graph);
 }
 
 template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool FFE = false, bool CHAIN = false>
@@ -198,7 +197,7 @@ bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a) {
   const int C = a.oe + a.on;
   if (C <= 0) return false;
   const int wsl = wave_slice_floats(a.oe, 2);
-  if (h->G == 1) { if (graph_update_lds_floats(C, a.dg, a.og, kThreads) > 4 * wsl) return false; }
+  if (h->G == 1) { if (graph_update_lds_floats(C, a.dg, a.og, graph_update_threads(h)) > 4 * wsl) return false; }
   else if (h->max_wtiles_per_graph > 256 || graph_update_lds_floats(C, a.dg, a.og, 64) > wsl) return false;
 #define GNX_CASE(DE, DN, DG, OE, ON) \
   if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return true;
@@ -229,6 +228,31 @@ bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1,
          !form(GNX_FLAG_NO_FFE);  // (max_in_degree: every wave tile is ONE chunk of edges — the kernel runs the FeedForward once, at its end)
 }
 
+// Which fused kernel launch_block_narrow runs for a call without LayerNorm on load: the run-time specialised kernel first under GNX_JIT_ALL,
+// an ahead-of-time width set at a wave-tile size it has, else the specialised kernel (never compiled while `s` is being captured); none:
+// the caller goes on to the matrix-core / generic kernels.  The ONE place this is decided: launch_block_narrow dispatches on it and
+// block_narrow_takes (gnx_block_forward_steps: two streams only on this path) asks it.
+enum NarrowRoute { NR_NONE, NR_AOT, NR_JIT };
+static NarrowRoute narrow_route(const gnx_graphs* h, const BlockArgs& a, hipStream_t s) {
+  if (a.n_wtiles == 0 || a.E == 0 || wants_ln(a)) return NR_NONE;
+  auto jit_ok = [&]() {
+    const int ept = h->wtile_e_cap / 64;
+    if (ept * 64 != h->wtile_e_cap || (ept != 1 && ept != 2 && ept != 4)) return false;
+    hipFunction_t fb, fg;
+    return jit_get(a, ept, s, &fb, &fg) == GNX_OK;
+  };
+  static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // testing: run-time specialise even the listed width sets
+  if (jit_all && jit_ok()) return NR_JIT;
+#define GNX_CASE(DE, DN, DG, OE, ON)                                                                                              \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON)                                                          \
+    return h->wtile_e_cap == 64 || h->wtile_e_cap == 128 || (h->wtile_e_cap == 256 && (DE + DN) * 4 <= 64) ? NR_AOT : NR_NONE;  // (launch_fused's EPT)
+  GNX_NARROW_DIMS(GNX_CASE)
+#undef GNX_CASE
+  return jit_ok() ? NR_JIT : NR_NONE;
+}
+
+bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s) { return narrow_route(h, a, s) != NR_NONE; }
+
 int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
   if (a.n_wtiles == 0 || a.E == 0) return 1;
   if (wants_ln(a)) {  // only reached after block_narrow_ready(): a miss here would silently drop the LayerNorm
@@ -240,14 +264,15 @@ int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, 
     const int32_t rc = launch_wave_jit(h, a, R, s, phase);
     return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: LayerNorm-on-load requested but the fused kernel is not available") : rc;
   }
-  static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // testing: run-time specialise even the listed width sets
-  if (jit_all && launch_wave_jit(h, a, R, s, phase) == GNX_OK) return GNX_OK;
+  const NarrowRoute route = narrow_route(h, a, s);
+  if (route == NR_NONE) return 1;
+  if (route == NR_JIT) return launch_wave_jit(h, a, R, s, phase);  // compiled on first use (gnx_block_workspace_bytes)
   // 16-B vector copies assume fp32-aligned buffers (always true for fp32 arrays); nothing else is required
 #define GNX_CASE(DE, DN, DG, OE, ON) \
   if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return launch_fused<DE, DN, DG, OE, ON>(h, a, R, s, phase);
   GNX_NARROW_DIMS(GNX_CASE)
 #undef GNX_CASE
-  return launch_wave_jit(h, a, R, s, phase);  // any other narrow width set: compiled on first use (1 if not eligible)
+  return fail(GNX_ERR_INVALID_ARG, "internal: ahead-of-time route for a width set without that kernel");
 }
 
 }  // namespace gnx

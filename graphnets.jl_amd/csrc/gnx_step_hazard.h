@@ -1,0 +1,56 @@
+// Host-side hazard rule of gnx_block_forward_steps' two-stream schedule (gnx_forward.hip): may two steps of the loop run at the same time?
+// Conservative and by address range only: step i's writes (ef_out, nf_out, gf_out, workspace) must not overlap anything step j reads or
+// writes (ef, nf, gf, ef_out, nf_out, gf_out, workspace), and the same the other way round.  The weights are read by every step and
+// written by none.  Plain C++ (no HIP): tests/test_steps_hazard_cpu.py compiles it on its own.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace gnx {
+
+struct ByteSpan {  // [lo, hi); empty when lo == hi
+  uintptr_t lo = 0, hi = 0;
+};
+
+inline ByteSpan byte_span(const void* p, size_t bytes) {
+  ByteSpan s;
+  if (p && bytes) { s.lo = reinterpret_cast<uintptr_t>(p); s.hi = s.lo + bytes; }
+  return s;
+}
+
+inline bool spans_overlap(ByteSpan a, ByteSpan b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
+
+struct StepSpans {
+  ByteSpan rd[3];  // ef, nf, gf
+  ByteSpan wr[4];  // ef_out, nf_out, gf_out, workspace
+};
+
+// true: the two steps must not be in flight together
+inline bool steps_conflict(const StepSpans& x, const StepSpans& y) {
+  for (const ByteSpan& w : x.wr) {
+    for (const ByteSpan& r : y.rd) if (spans_overlap(w, r)) return true;
+    for (const ByteSpan& v : y.wr) if (spans_overlap(w, v)) return true;
+  }
+  for (const ByteSpan& w : y.wr)
+    for (const ByteSpan& r : x.rd) if (spans_overlap(w, r)) return true;
+  return false;
+}
+
+// The two-stream schedule of gnx_block_forward_steps: step i runs on stream i & 1 (even steps on the caller's stream, odd steps on the side
+// stream); the chained graph update of step i rides at the front of step i + 2's launch (the next on its stream); and step i's launch waits
+// for step i - 3's launch to end (an event per step).  That wait is what bounds the streams' skew: launches i and j can then run together
+// only when |i - j| == 1, so step i (its launch and, two launches later, its graph update) is in flight together with steps i +- 1 and
+// i +- 3 only, whatever the order in which the two streams (or a captured graph's two branches) make progress.  The rest is this:
+struct StepOrder {
+  bool flush_own = false;    // step i - 2's pending graph update runs as its own launch before step i's (it must not ride in step i's)
+  bool after_other = false;  // step i waits for everything issued on the other stream, step i - 1's pending graph update flushed first
+};
+// recent[d - 1]: the spans of step i - d, for d = 1 .. min(i, 3)
+inline StepOrder step_order(const StepSpans& cur, const StepSpans* recent, long long i) {
+  StepOrder o;
+  o.flush_own = i >= 2 && steps_conflict(cur, recent[1]);
+  o.after_other = (i >= 1 && steps_conflict(cur, recent[0])) || (i >= 3 && steps_conflict(cur, recent[2]));
+  return o;
+}
+
+}  // namespace gnx

@@ -447,12 +447,16 @@ __device__ __forceinline__ void store_partial_row(float mine, float* row, int la
   }
 }
 
+// vthr (a multiple of 64; 0: nthr): the sums come out as a launch of vthr threads would form them — the bits k_graph_t gives with that many
+// threads.  Thread tid plays the threads tid, tid + nthr, ... below vthr in turn (none, one or several; the same count across a wavefront).
 template <int C, bool WAVE, int F4_IN_FLIGHT>
-__device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const float* __restrict__ base, int g, size_t r, int t0, int t1, int tid, int nthr, float* s_g) {
+__device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const float* __restrict__ base, int g, size_t r, int t0, int t1, int tid, int nthr, float* s_g,
+                                                  int vthr = 0) {
   constexpr int Q = (C + 3) / 4, CP = 4 * Q;
   constexpr int RIF = Q >= F4_IN_FLIGHT ? 1 : F4_IN_FLIGHT / Q;  // rows in flight per thread; the per-thread accumulation order (rows ascending) does not depend on it
   const int K = C + a.dg, og = a.og;
-  const int nrow16 = nthr >> 4;
+  if (vthr <= 0) vthr = nthr;
+  const int nrow16 = vthr >> 4;
   float* s_x = s_g + (size_t)nrow16 * C;  // [K]   graph-function input
   float* s_w = s_x + K + 4;               // [K*og] weights, [og] bias
 
@@ -467,25 +471,34 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
   float gf_reg = 0.f;
   if (tid < a.dg) gf_reg = a.gf[(r * (size_t)a.G + g) * a.dg + tid];
 
-  float acc[Q][4];
+  const int lane = tid & 63;
+  for (int v = tid; v < vthr; v += nthr) {
+    float acc[Q][4];
 #pragma unroll
-  for (int q = 0; q < Q; ++q) acc[q][0] = acc[q][1] = acc[q][2] = acc[q][3] = 0.f;
-  for (int row0 = t0 + tid; row0 < t1; row0 += RIF * nthr) {
-    float4 val[RIF][Q];
+    for (int q = 0; q < Q; ++q) acc[q][0] = acc[q][1] = acc[q][2] = acc[q][3] = 0.f;
+    for (int row0 = t0 + v; row0 < t1; row0 += RIF * vthr) {
+      float4 val[RIF][Q];
 #pragma unroll
-    for (int u = 0; u < RIF; ++u) {
-      const int row = row0 + u * nthr;
-      if (row < t1) {
+      for (int u = 0; u < RIF; ++u) {
+        const int row = row0 + u * vthr;
+        if (row < t1) {
 #pragma unroll
-        for (int q = 0; q < Q; ++q) val[u][q] = *reinterpret_cast<const float4*>(base + (size_t)row * CP + 4 * q);
+          for (int q = 0; q < Q; ++q) val[u][q] = *reinterpret_cast<const float4*>(base + (size_t)row * CP + 4 * q);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < RIF; ++u) {
+        if (row0 + u * vthr < t1) {
+#pragma unroll
+          for (int q = 0; q < Q; ++q) { acc[q][0] += val[u][q].x; acc[q][1] += val[u][q].y; acc[q][2] += val[u][q].z; acc[q][3] += val[u][q].w; }
+        }
       }
     }
+    const int row16 = v >> 4;
 #pragma unroll
-    for (int u = 0; u < RIF; ++u) {
-      if (row0 + u * nthr < t1) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) { acc[q][0] += val[u][q].x; acc[q][1] += val[u][q].y; acc[q][2] += val[u][q].z; acc[q][3] += val[u][q].w; }
-      }
+    for (int c = 0; c < C; ++c) {
+      const float x = row16_sum(acc[c >> 2][c & 3]);
+      if ((lane & 15) == 0) s_g[row16 * C + c] = x;
     }
   }
   // weights to LDS (loads have long since landed)
@@ -508,12 +521,6 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
   } else {
     if (tid < a.dg) s_x[C + tid] = gf_reg;
     for (int k = tid + nthr; k < a.dg; k += nthr) s_x[C + k] = a.gf[(r * (size_t)a.G + g) * a.dg + k];
-  }
-  const int lane = tid & 63, row16 = tid >> 4;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const float x = row16_sum(acc[c >> 2][c & 3]);
-    if ((lane & 15) == 0) s_g[row16 * C + c] = x;
   }
   if constexpr (WAVE) __builtin_amdgcn_wave_barrier(); else __syncthreads();
   // second stage: wave 0 sums the <= 64 row sums of every column (fixed order: DPP tree + 4 readlanes)
@@ -581,6 +588,9 @@ __device__ __forceinline__ void graph_update_wave(const BlockArgs& a, float xsum
   }
 }
 
+// threads of k_graph_t for a graph of `rows` partial rows (gnx_narrow.hip: graph_update_threads) — and the thread count whose summation
+// order the CHAIN front of k_block_wave reproduces (its graph update is bit-identical to k_graph_t's)
+__host__ __device__ constexpr int graph_update_threads_for_rows(long long rows) { return rows <= 256 ? 64 : (rows >= 1024 ? 1024 : 256); }
 // LDS floats graph_update_rows needs with nthr threads
 __host__ __device__ constexpr int graph_update_lds_floats(int C, int dg, int og, int nthr) {
   return (nthr / 16) * C + (C + dg + 4) + (C + dg + 1) * og + 8;
@@ -677,7 +687,9 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
         a.gf = a.prev_gf; a.gf_out = a.prev_gf_out;  // (this workgroup returns below: the kernel's own copy of the arguments is its to change)
         const float* pbase = a.prev_partials + blockIdx.y * (size_t)n_rows * CPc;
         if constexpr (ONEG) {
-          graph_update_rows<C, false, 4>(a, pbase, 0, blockIdx.y, 0, (a.n_wtiles + 3) / 4, (int)threadIdx.x, kThreads, s_mem);
+          // summed as k_graph_t sums them at the thread count its launcher picks for these rows (graph_update_threads): the same bits
+          const int rows = (a.n_wtiles + 3) / 4;
+          graph_update_rows<C, false, 4>(a, pbase, 0, blockIdx.y, 0, rows, (int)threadIdx.x, kThreads, s_mem, graph_update_threads_for_rows(rows));
         } else {
           const int g = (int)blockIdx.x * WAVES + wv;  // one wavefront per graph (the launcher chains only while a graph has <= 256 rows)
           if (g < a.G) graph_update_rows<C, true, 4>(a, pbase, g, blockIdx.y, a.wtile_off[g], a.wtile_off[g + 1], lane, 64, s_mem + wv * WSL);

@@ -97,6 +97,7 @@ extern "C" {
 #define GNX_FLAG_LN_STATS_PASS 0x400u    /* wide GNCore: row statistics of ef by the statistics pass instead of in the six-term kernels    */
 #define GNX_FLAG_CORE_EDGE_SPLIT 0x800u  /* wide GNCore: edge update and edge FeedForward as two launches                                  */
 #define GNX_FLAG_NO_FORK 0x1000u         /* wide GNCore: everything on the caller's stream (no side stream for the graph level)            */
+                                         /* ... and gnx_block_forward_steps: every step on the caller's stream (no two-stream schedule)    */
 #define GNX_FLAG_NO_PACK 0x2000u         /* narrow block on small graphs: graph update as its own launch (k_graph_t)                       */
 #define GNX_FLAG_NO_FFE 0x4000u          /* narrow GNCore: edge FeedForward in k_core_post3 instead of the block kernel's edge lanes       */
 #define GNX_FLAG_NO_JIT 0x8000u          /* never specialise a kernel at run time (generic kernels instead); env GNX_JIT=0 / GNX_NO_JIT=1   */
@@ -289,7 +290,15 @@ GNX_API int32_t gnx_block_forward_chained(const gnx_graphs* h, const gnx_block_p
  * us/step on BASELINE configs[1]).  Every output of every step is complete once the work this call enqueued is complete.  Consecutive
  * steps must not share a workspace or a gf_out (step i + 1 starts while step i's graph update is pending): a step that does share them with
  * its predecessor is simply run unchained.  Other paths (matrix-core / generic kernels, batches of small graphs): n_steps plain forwards.
- * Capture-safe like gnx_block_forward (bench.py captures K steps into one hipGraph). */
+ * Capture-safe like gnx_block_forward (bench.py captures K steps into one hipGraph).
+ * TWO STREAMS: where the fused narrow kernel runs (plain, chained, pack form, run-time specialised widths) even steps go to the caller's
+ * stream and odd steps to a side stream of the handle's pool (gnx_block_workspace_bytes creates it, outside any capture), forked from and
+ * joined back into `stream` inside the call (on error paths too), so neighbouring steps overlap; the chained graph update of step i then
+ * rides at the front of step i + 2's launch (its stream's next), and two pending updates are flushed at the end.  Steps whose buffers
+ * overlap (one step writes a byte range — ef_out, nf_out, gf_out, workspace — that another reads or writes, up to three steps apart) are
+ * ordered by an event wait instead, and every step's launch waits for the end of the launch three steps before it (the streams never
+ * drift further apart).  Outputs are bit-identical in either schedule.  One stream: GNX_FLAG_NO_FORK, matrix-core / generic
+ * kernels, the per-kernel profiler on (gnx_profile_enable), or every side stream of the handle taken by other host threads. */
 typedef struct gnx_block_step {
   const float* ef;
   const float* nf;

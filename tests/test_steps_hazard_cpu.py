@@ -1,0 +1,200 @@
+"""The host-side hazard rule of gnx_block_forward_steps' two-stream schedule (graphnets.jl_amd/csrc/gnx_step_hazard.h), compiled on its
+own with g++: two steps may be in flight together only if no byte range one writes overlaps a range the other reads or writes; and the
+two-stream schedule built on it (step_order + the wait of step i for step i - 3), checked by simulating the order it enforces."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+DRIVER = r"""
+#include <cstdio>
+#include "gnx_step_hazard.h"
+using namespace gnx;
+static char buf[1 << 16];
+static int fails = 0;
+#define EXPECT(c) do { if (!(c)) { std::printf("FAIL line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
+// a step: inputs at in[0..2], outputs at out[0..2], workspace at ws; each 256 bytes
+static StepSpans step(int in0, int in1, int in2, int o0, int o1, int o2, int ws, size_t n = 256) {
+  StepSpans s;
+  const int in[3] = {in0, in1, in2}, out[4] = {o0, o1, o2, ws};
+  for (int t = 0; t < 3; ++t) s.rd[t] = in[t] < 0 ? ByteSpan{} : byte_span(buf + in[t], n);
+  for (int t = 0; t < 4; ++t) s.wr[t] = out[t] < 0 ? ByteSpan{} : byte_span(buf + out[t], n);
+  return s;
+}
+int main() {
+  // the spans themselves: half-open, empty for NULL or zero bytes
+  EXPECT(spans_overlap(byte_span(buf, 16), byte_span(buf + 15, 16)));
+  EXPECT(!spans_overlap(byte_span(buf, 16), byte_span(buf + 16, 16)));
+  EXPECT(!spans_overlap(byte_span(buf + 16, 16), byte_span(buf, 16)));
+  EXPECT(spans_overlap(byte_span(buf, 64), byte_span(buf + 8, 8)));
+  EXPECT(!spans_overlap(byte_span(buf, 0), byte_span(buf, 16)));
+  EXPECT(!spans_overlap(byte_span(nullptr, 16), byte_span(nullptr, 16)));
+  // two disjoint buffer sets: independent
+  const StepSpans a = step(0, 256, 512, 1024, 1280, 1536, 2048);
+  const StepSpans b = step(4096, 4352, 4608, 5120, 5376, 5632, 6144);
+  EXPECT(!steps_conflict(a, b) && !steps_conflict(b, a));
+  // the same set twice: every pair aliases
+  EXPECT(steps_conflict(a, a));
+  // both READ the same inputs: still independent
+  const StepSpans c = step(0, 256, 512, 5120, 5376, 5632, 6144);
+  EXPECT(!steps_conflict(a, c) && !steps_conflict(c, a));
+  // dims -> dims: the next step reads this step's outputs (each output alone is enough), in either argument order
+  EXPECT(steps_conflict(a, step(1024, 4352, 4608, 5120, 5376, 5632, 6144)));
+  EXPECT(steps_conflict(step(4096, 1280, 4608, 5120, 5376, 5632, 6144), a));
+  EXPECT(steps_conflict(a, step(4096, 4352, 1536, 5120, 5376, 5632, 6144)));
+  // one shared workspace, or one shared output
+  EXPECT(steps_conflict(a, step(4096, 4352, 4608, 5120, 5376, 5632, 2048)));
+  EXPECT(steps_conflict(a, step(4096, 4352, 4608, 5120, 5376, 1536, 6144)));
+  // a step that WRITES what the other reads, the other way round
+  EXPECT(steps_conflict(a, step(4096, 4352, 4608, 0, 5376, 5632, 6144)));
+  EXPECT(steps_conflict(step(4096, 4352, 4608, 5120, 5376, 5632, 200), a));
+  // partial overlap of one byte at a range's end; touching ranges do not overlap
+  EXPECT(steps_conflict(a, step(4096, 4352, 4608, 5120, 5376, 5632, 2048 + 255)));
+  EXPECT(!steps_conflict(a, step(4096, 4352, 4608, 5120, 5376, 5632, 2048 + 256)));
+  // widths of 0 (`nothing`): absent ranges never conflict
+  EXPECT(!steps_conflict(step(-1, 256, -1, -1, 1280, -1, 2048), step(-1, 4352, -1, -1, 5376, -1, 6144)));
+  if (fails) return 1;
+  std::printf("hazard rule ok\n");
+  return 0;
+}
+"""
+
+
+def test_step_hazard_rule(tmp_path):
+    src = tmp_path / "hazard.cpp"
+    src.write_text(DRIVER)
+    exe = tmp_path / "hazard"
+    cxx = os.environ.get("CXX", "g++")
+    subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "graphnets.jl_amd", "csrc"), str(src), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "hazard rule ok" in out.stdout
+
+
+SCHEDULE = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#include "gnx_step_hazard.h"
+using namespace gnx;
+// Simulation of gnx_block_forward_steps' two-stream schedule (gnx_forward.hip) as a happens-before relation: launches are nodes on two
+// streams (stream order), plus the waits the schedule adds.  An activity is a step's edge + node update (its launch) or its graph update
+// (chained into the launch two later on its stream, or a flush launch).  Every two activities of different steps whose buffers conflict
+// must be ordered, whatever the streams' relative progress.
+struct Node { int stream; std::vector<int> steps; };
+struct Sim {
+  std::vector<Node> nodes;
+  std::vector<std::vector<int>> deps;  // explicit edges into a node
+  int last[2] = {-1, -1};
+  int add(int stream, std::vector<int> steps, std::vector<int> extra) {
+    nodes.push_back({stream, steps});
+    if (last[stream] >= 0) extra.push_back(last[stream]);
+    deps.push_back(extra);
+    return last[stream] = (int)nodes.size() - 1;
+  }
+};
+static char mem[1 << 20];
+// a buffer set: seven 64-byte ranges at base
+static StepSpans spans_of(int in_set, int out_set, int ws_set) {
+  StepSpans s;
+  for (int t = 0; t < 3; ++t) s.rd[t] = byte_span(mem + in_set * 1024 + t * 64, 64);
+  for (int t = 0; t < 3; ++t) s.wr[t] = byte_span(mem + out_set * 1024 + 512 + t * 64, 64);
+  s.wr[3] = byte_span(mem + 200 * 1024 + ws_set * 64, 64);
+  return s;
+}
+// dims -> dims: the inputs of a step are the outputs of out_set
+static StepSpans spans_chain(int src_out_set, int out_set, int ws_set) {
+  StepSpans s = spans_of(0, out_set, ws_set);
+  for (int t = 0; t < 3; ++t) s.rd[t] = byte_span(mem + src_out_set * 1024 + 512 + t * 64, 64);
+  return s;
+}
+// returns the number of unordered conflicting pairs
+static int check(const std::vector<StepSpans>& sp, bool chain, bool wait3) {
+  const long long K = (long long)sp.size();
+  Sim sim;
+  int pend[2] = {-1, -1};
+  std::vector<int> launch(K, -1);
+  StepSpans recent[3];
+  for (long long i = 0; i < K; ++i) {
+    const int k = (int)(i & 1), o = k ^ 1;
+    const StepOrder ord = step_order(sp[i], recent, i);
+    if (ord.flush_own && pend[k] >= 0) { sim.add(k, {pend[k]}, {}); pend[k] = -1; }
+    std::vector<int> extra;
+    if (wait3 && i >= 3) extra.push_back(launch[i - 3]);
+    if (ord.after_other) {
+      if (pend[o] >= 0) { sim.add(o, {pend[o]}, {}); pend[o] = -1; }
+      if (sim.last[o] >= 0) extra.push_back(sim.last[o]);
+    }
+    std::vector<int> acts = {(int)i};
+    if (pend[k] >= 0) acts.push_back(pend[k]);  // the chained graph update of step i - 2 at the front of this launch
+    launch[i] = sim.add(k, acts, extra);
+    pend[k] = chain ? (int)i : -1;  // (not chained: the step's graph update is inside its own launch)
+    recent[2] = recent[1]; recent[1] = recent[0]; recent[0] = sp[i];
+  }
+  for (int k = 0; k < 2; ++k)
+    if (pend[k] >= 0) sim.add(k, {pend[k]}, {});
+  const int n = (int)sim.nodes.size();
+  std::vector<std::vector<char>> r(n, std::vector<char>(n, 0));  // r[a][b]: a ends before b starts
+  for (int b = 0; b < n; ++b)
+    for (int a : sim.deps[b]) {
+      r[a][b] = 1;
+      for (int x = 0; x < n; ++x) if (r[x][a]) r[x][b] = 1;
+    }
+  int bad = 0;
+  for (int a = 0; a < n; ++a)
+    for (int b = a; b < n; ++b) {
+      if (a != b && (r[a][b] || r[b][a])) continue;
+      for (int s : sim.nodes[a].steps)
+        for (int t : sim.nodes[b].steps)
+          if (s != t && steps_conflict(sp[s], sp[t])) ++bad;
+    }
+  return bad;
+}
+int main() {
+  int fails = 0;
+  for (int chain = 0; chain < 2; ++chain) {
+    // rotating buffer sets: every count, every length
+    for (int nsets = 1; nsets <= 9; ++nsets)
+      for (int K = 1; K <= 24; ++K) {
+        std::vector<StepSpans> sp;
+        for (int i = 0; i < K; ++i) sp.push_back(spans_of(i % nsets, i % nsets, i % nsets));
+        if (int b = check(sp, chain, true)) { std::printf("FAIL rotating nsets=%d K=%d chain=%d: %d\n", nsets, K, chain, b); ++fails; }
+      }
+    // one shared workspace; dims -> dims
+    for (int K = 1; K <= 12; ++K) {
+      std::vector<StepSpans> a, b;
+      for (int i = 0; i < K; ++i) { a.push_back(spans_of(i, i, 0)); b.push_back(spans_chain(i == 0 ? 99 : i - 1, i, i)); }
+      if (check(a, chain, true) || check(b, chain, true)) { std::printf("FAIL shared / chain K=%d\n", K); ++fails; }
+    }
+    // random reuse of inputs, outputs and workspaces from small pools
+    unsigned x = 12345u;
+    auto rnd = [&](int m) { x = x * 1664525u + 1013904223u; return (int)((x >> 8) % (unsigned)m); };
+    for (int trial = 0; trial < 3000; ++trial) {
+      const int K = 1 + rnd(20), m = 1 + rnd(7);
+      std::vector<StepSpans> sp;
+      for (int i = 0; i < K; ++i) sp.push_back(rnd(4) == 0 && i > 0 ? spans_chain(rnd(m), rnd(m), rnd(m)) : spans_of(rnd(m), rnd(m), rnd(m)));
+      if (int b = check(sp, chain, true)) { std::printf("FAIL random trial %d chain=%d: %d\n", trial, chain, b); ++fails; break; }
+    }
+  }
+  // the checker sees the race the wait for step i - 3 prevents: five rotating sets without it
+  {
+    std::vector<StepSpans> sp;
+    for (int i = 0; i < 12; ++i) sp.push_back(spans_of(i % 5, i % 5, i % 5));
+    if (!check(sp, true, false)) { std::printf("FAIL: five rotating sets without the step i - 3 wait were not flagged\n"); ++fails; }
+  }
+  if (fails) return 1;
+  std::printf("schedule ok\n");
+  return 0;
+}
+"""
+
+
+def test_two_stream_schedule_orders_every_conflicting_pair(tmp_path):
+    src = tmp_path / "schedule.cpp"
+    src.write_text(SCHEDULE)
+    exe = tmp_path / "schedule"
+    cxx = os.environ.get("CXX", "g++")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "graphnets.jl_amd", "csrc"), str(src), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "schedule ok" in out.stdout
