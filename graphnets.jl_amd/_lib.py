@@ -17,6 +17,7 @@ ERR_INVALID_ARG, ERR_NO_GRAPHS, ERR_ADJ_SHAPE, ERR_ADJ_VALUE, ERR_ALL_NOTHING = 
 ERR_DIMS, ERR_CSC, ERR_WORKSPACE, ERR_TOO_LARGE, ERR_COUNT_MISMATCH = -6, -7, -8, -9, -10
 ACT = dict(identity=0, relu=1, tanh=2, sigmoid=3, gelu=4)
 ELEM_U8, ELEM_I32, ELEM_I64, ELEM_F32, ELEM_F64 = 0, 1, 2, 3, 4
+ELEM_BF16 = 5  # feature tensors only (gnx_block_forward_typed)
 FLAG_FORCE_GENERIC, FLAG_NO_MFMA, FLAG_DEFER_GRAPH_UPDATE, FLAG_NO_GRAPH, FLAG_DIST_NO_GATHER = 0x1, 0x2, 0x4, 0x8, 0x10
 # forms of the forward selected per call (include/gnx.h); the environment variables of the same names (GNX_FFN_FP32=1 ...) are the process-wide
 # defaults, read once by the library
@@ -136,6 +137,8 @@ SIGNATURES = {
     "gnx_graphs_get_table": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
     "gnx_block_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(BlockParams), C.c_int64]),
     "gnx_block_forward": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams)] + _FWD[2:]),
+    "gnx_block_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(BlockParams), C.c_int64, C.c_int32, C.c_uint32]),
+    "gnx_block_forward_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32] + _FWD[2:]),
     "gnx_chain_block_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
     "gnx_chain_block_forward": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams)] + _FWD[2:]),
     "gnx_chain_block_backward_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
@@ -185,6 +188,7 @@ SIGNATURES = {
     "gnx_dist_block_forward": (C.c_int32, [C.c_void_p] + [_pp] * 10 + [C.POINTER(C.c_size_t), C.c_uint32, _pp]),
     "gnx_dist_block_forward_steps": (C.c_int32, [C.c_void_p, C.c_int32] + [_pp] * 9 + [C.POINTER(C.c_size_t), C.c_uint32, _pp]),
     "gnx_jit_precompile": (C.c_int32, [C.POINTER(BlockParams), C.c_int32, C.POINTER(C.c_size_t)]),
+    "gnx_jit_precompile_typed": (C.c_int32, [C.POINTER(BlockParams), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "gnx_jit_precompile_core_post": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "gnx_jit_stats": (C.c_int32, [_i64p]),
     "gnx_profile_enable": (C.c_int32, [C.c_int32]),

@@ -305,6 +305,33 @@ def _dev_f32(a, device):
     return t.to(device=device, dtype=torch.float32)
 
 
+def _dev_feat(a, device, dtype):
+    """batch()'s feature conversion: float32 as always (dtype None / float32), or bfloat16 — uploaded as it is and converted once on the device."""
+    if dtype is None or dtype == torch.float32:
+        return _dev_f32(a, device)
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(_np(a), dtype=np.float32))
+    return t.to(device=device).to(dtype)
+
+
+def _no_bf16(what, *tensors):
+    """The fp32-only entry points: a bfloat16 feature tensor is refused instead of having its bytes read as floats."""
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16:
+            raise TypeError(f"{what}: bfloat16 features are supported by GNBlock only (gnx_block_forward_typed); convert with .float()")
+
+
+def _feature_dtype(ef, nf, gf):
+    """torch.bfloat16 when every present feature tensor is bf16, else None (the fp32 path, other dtypes as before); mixed bf16 / other: TypeError."""
+    present = [a for a in (ef, nf, gf) if isinstance(a, torch.Tensor)]
+    n = sum(a.dtype == torch.bfloat16 for a in present)
+    if n == 0:
+        return None
+    if n != len(present):
+        raise TypeError("GNBlock: the features mix bfloat16 and " + ", ".join(sorted({str(a.dtype) for a in present if a.dtype != torch.bfloat16})) +
+                        " tensors; batch them with one dtype (batch(..., dtype=...))")
+    return torch.bfloat16
+
+
 def _ndim(a):
     return a.dim() if isinstance(a, torch.Tensor) else np.ndim(a)
 
@@ -361,9 +388,12 @@ def _is_matrix(g):
     return isinstance(g, (np.ndarray, torch.Tensor)) and g.ndim == 2
 
 
-def batch(t, device=None):
+def batch(t, device=None, dtype=None):
     """`batch(t::NamedTuple)` (batch.jl:53-64).  `graphs` is one adjacency matrix (shared by the whole data batch),
-    a vector of adjacency matrices, or an existing GNGraphBatch (e.g. from_csc)."""
+    a vector of adjacency matrices, or an existing GNGraphBatch (e.g. from_csc).  The features are stored as float32 (dtype None, the
+    default) or, with dtype=torch.bfloat16, as bfloat16 (converted once on the device; GNBlock then computes on them natively)."""
+    if dtype is not None and dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"batch: dtype must be None, torch.float32 or torch.bfloat16, not {dtype}")
     if isinstance(t, dict):
         assert set(t.keys()) == set(_KEYS), "keys must be (graphs, ef, nf, gf)"
     t = _as_nt(t)
@@ -384,17 +414,17 @@ def batch(t, device=None):
         _checks_vector(graphs, ef, nf, gf)
         g = GNGraphBatch(graphs, device=dev)
     if shared:
-        bef = None if ef is None else _jl(_packed(_dev_f32(ef, dev)))
-        bnf = None if nf is None else _jl(_packed(_dev_f32(nf, dev)))
-        bgf = None if gf is None else _jl(_dev_f32(gf, dev).t().contiguous()[:, None, :])  # (DG,B) → [B][1][DG]
+        bef = None if ef is None else _jl(_packed(_dev_feat(ef, dev, dtype)))
+        bnf = None if nf is None else _jl(_packed(_dev_feat(nf, dev, dtype)))
+        bgf = None if gf is None else _jl(_dev_feat(gf, dev, dtype).t().contiguous()[:, None, :])  # (DG,B) → [B][1][DG]
         for name, a, T in (("ef", bef, g.n_edges), ("nf", bnf, g.n_nodes)):
             if a is not None:
                 assert a.shape[1] == T, f"size({name}, 2) = {a.shape[1]} != {T} (checks.jl:41-46)"
     else:
-        cat = lambda items: torch.cat([_dev_f32(x, dev).t() for x in items], dim=0).contiguous()[None]  # [1][ΣT][D]
+        cat = lambda items: torch.cat([_dev_feat(x, dev, dtype).t() for x in items], dim=0).contiguous()[None]  # [1][ΣT][D]
         bef = None if ef is None else _jl(cat(ef))
         bnf = None if nf is None else _jl(cat(nf))
-        bgf = None if gf is None else _jl(torch.stack([_dev_f32(x, dev) for x in gf]).contiguous()[None])  # [1][G][DG]
+        bgf = None if gf is None else _jl(torch.stack([_dev_feat(x, dev, dtype) for x in gf]).contiguous()[None])  # [1][G][DG]
         for name, a, T in (("ef", bef, g.n_edges), ("nf", bnf, g.n_nodes), ("gf", bgf, g.n_graphs)):
             if a is not None:
                 assert a.shape[1] == T, f"{name}: {a.shape[1]} columns != {T} (checks.jl:41-46)"
@@ -477,6 +507,7 @@ def padded(t):
     """The reference's padded batched arrays — ef (DE, PN², B), nf (DN, PN, B), gf (DG, 1, B) — with zeros in the
     pads (the reference leaves act(bias) junk there; SURVEY §8b 'raw padded arrays')."""
     t = _as_nt(t)
+    _no_bf16("padded", t.ef, t.nf, t.gf)
     g = t.graphs
     lib = _lib.load()
     stream = torch.cuda.current_stream(g.device).cuda_stream
@@ -505,6 +536,7 @@ def unpadded(graphs, ef=None, nf=None, gf=None):
     returns).  Whatever the pads hold is dropped."""
     g = graphs
     assert isinstance(g, GNGraphBatch), "graphs must be a GNGraphBatch (batch(...).graphs)"
+    _no_bf16("unpadded", ef, nf, gf)
     lib = _lib.load()
     stream = torch.cuda.current_stream(g.device).cuda_stream
     out = {}
@@ -533,6 +565,7 @@ def _collapse(t):
     t = _as_nt(t)
     g, ef = t.graphs, t.ef
     assert ef is not None, "collapsing needs edge features"
+    _no_bf16("unpaddedcollapsedef", ef)
     lib = _lib.load()
     off = np.zeros(g.n_graphs + 1, dtype=np.int64)
     with torch.cuda.device(g.device):
@@ -551,6 +584,7 @@ def collapsef(t):
     t = _as_nt(t)
     g, ef = t.graphs, t.ef
     assert ef is not None, "collapsing needs edge features"
+    _no_bf16("collapsef", ef)
     lib = _lib.load()
     with torch.cuda.device(g.device):
         c = _packed(ef)
@@ -608,6 +642,7 @@ def logitcrossentropy(yhat, y):
     """`Flux.logitcrossentropy(ŷ, y)` on (d, cols) arrays such as `flatunpaddednf(ŷ)` (examples/sort/sort.jl:69-81):
     mean over columns of -sum(y .* logsoftmax(ŷ; dims=1); dims=1).  Returns a 0-d device tensor; differentiable w.r.t. ŷ."""
     assert yhat.dim() == 2 and tuple(yhat.shape) == tuple(y.shape), "ŷ and y must be (d, cols) arrays of the same size"
+    _no_bf16("logitcrossentropy", yhat, y)
     a = yhat.t().contiguous().float()   # [cols][d] rows = the bytes of a column-major (d, cols) array
     b = y.to(yhat.device).t().contiguous().float()
     return _XentFn.apply(a, b)
@@ -618,6 +653,7 @@ def _fn_input(kind, graphs, ef, nf, gf):
     assert isinstance(g, GNGraphBatch), "graphs must be the GNGraphBatch of a batched tuple"
     present = [a for a in (ef, nf, gf) if a is not None]
     assert present, "ef, nf and gf are all nothing"
+    _no_bf16(("getedgefninput", "getnodefninput", "getgraphfninput")[kind], ef, nf, gf)
     R = present[0].shape[2]
     c = [_packed(a) for a in (ef, nf, gf)]
     d = [0 if a is None else a.shape[2] for a in c]
@@ -817,9 +853,11 @@ def _pair(in_dims, out_dims):
     return tuple(int(d) for d in in_dims), tuple(int(d) for d in out_dims)
 
 
-def _forward_common(x, in_dims):
+def _forward_common(x, in_dims, what="GNCore"):
     x = _as_nt(x)
     g, ef, nf, gf = x
+    if what is not None:  # (GNBlock's own bf16 path passes None)
+        _no_bf16(what, ef, nf, gf)
     assert isinstance(g, GNGraphBatch), "x must come from batch()"
     present = [a for a in (ef, nf, gf) if a is not None]
     assert present, "ef, nf and gf are all nothing"
@@ -931,7 +969,7 @@ class GNBlock:
 
     def _call_chains(self, x, flags):
         """Update functions that are multi-layer Chains: gnx_chain_block_forward; differentiable through gnx_chain_block_backward."""
-        g, ef, nf, gf, R = _forward_common(x, self.in_dims)
+        g, ef, nf, gf, R = _forward_common(x, self.in_dims, "GNBlock")
         flags = self.flags if flags is None else flags
         chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
         params = [t for ch in chains for l in ch.layers for t in (l.weight, l.bias)]
@@ -946,14 +984,19 @@ class GNBlock:
         return NT(g, _jl(eo), _jl(no), _jl(go))
 
     def __call__(self, x, flags=None):
-        if any(isinstance(f, Chain) and (len(f) != 1 or isinstance(f.layers[0], LayerNorm)) for f in (self.edgefn, self.nodefn, self.graphfn)):
-            return self._call_chains(x, flags)
-        if any(isinstance(f, Chain) and f.dropout_p > 0 for f in (self.edgefn, self.nodefn, self.graphfn)):
+        fns = (self.edgefn, self.nodefn, self.graphfn)
+        chained = any(isinstance(f, Chain) and (len(f) != 1 or isinstance(f.layers[0], LayerNorm) or f.dropout_p > 0) for f in fns)
+        xt = _as_nt(x)
+        if _feature_dtype(xt.ef, xt.nf, xt.gf) == torch.bfloat16:  # (mixed bf16 / other features: TypeError, before any library call)
+            if chained:
+                raise NotImplementedError("GNBlock: Chain update functions on bfloat16 features are not supported; convert the features with .float()")
+            return self._call_bf16(x, flags)
+        if chained:
             return self._call_chains(x, flags)
         if any(isinstance(f, Chain) for f in (self.edgefn, self.nodefn, self.graphfn)):  # one-layer chains are plain Dense layers
             self.edgefn, self.nodefn, self.graphfn = (f.layers[0] if isinstance(f, Chain) else f for f in (self.edgefn, self.nodefn, self.graphfn))
         self._sync_dims()
-        g, ef, nf, gf, R = _forward_common(x, self.in_dims)
+        g, ef, nf, gf, R = _forward_common(x, self.in_dims, "GNBlock")
         if self._trainable((ef, nf, gf)):  # differentiable call: gnx_block_backward is the pullback
             outs = iter(_BlockFn.apply(self, g, R, self.flags if flags is None else flags, ef, nf, gf, self.edgefn.weight, self.edgefn.bias,
                                        self.nodefn.weight, self.nodefn.bias, self.graphfn.weight, self.graphfn.bias))
@@ -972,6 +1015,33 @@ class GNBlock:
                                         ws.data_ptr(), ws.numel(), (self.flags if flags is None else flags),
                                         torch.cuda.current_stream(dev).cuda_stream))
         return NT(g, _jl(eo), _jl(no), _jl(go))  # zero-width outputs are None (gnblock.jl:71-78)
+
+
+    def _call_bf16(self, x, flags):
+        """bfloat16 features (batch(..., dtype=torch.bfloat16)): gnx_block_forward_typed, bf16 outputs — bit for bit the fp32 forward of the
+        widened inputs, rounded once to bf16.  Forward only: a differentiable call raises NotImplementedError."""
+        if any(isinstance(f, Chain) for f in (self.edgefn, self.nodefn, self.graphfn)):  # one-layer chains are plain Dense layers
+            self.edgefn, self.nodefn, self.graphfn = (f.layers[0] if isinstance(f, Chain) else f for f in (self.edgefn, self.nodefn, self.graphfn))
+        self._sync_dims()
+        g, ef, nf, gf, R = _forward_common(x, self.in_dims, None)
+        if self._trainable((ef, nf, gf)):
+            raise NotImplementedError("GNBlock: the backward of a bfloat16 forward is not implemented; call it under torch.no_grad() or with float32 features")
+        # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
+        ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+        lib = _lib.load()
+        keep = []
+        p = self._c(keep)
+        oe, on, og = self.out_dims
+        dev = g.device
+        flags = self.flags if flags is None else flags
+        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.bfloat16, device=dev) if d > 0 else None
+        eo, no, go = mk(g.n_edges, oe), mk(g.n_nodes, on), mk(g.n_graphs, og)
+        with torch.cuda.device(dev):
+            nbytes = lib.gnx_block_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, flags)
+            ws = g.workspace(nbytes, ("block_bf16", self.in_dims, self.out_dims, R, flags))
+            check(lib.gnx_block_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
+                                              ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
+        return NT(g, _jl(eo), _jl(no), _jl(go))
 
 
 class _BlockFn(torch.autograd.Function):

@@ -27,11 +27,12 @@ int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, 
 // returns 1 when the path does not apply to these dims (caller falls through to the next path)
 // phase bit 1: edge + node update (leaves per-tile partial sums in the workspace); bit 2: graph update from them
 int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
-void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p);
+void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p, bool bf16 = false);
 bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
 bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1, int act2);
 bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a);
-bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
+bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16 = false);
+int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);  // 1: no fused bf16 kernel for these widths
 int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
 static_assert(GNX_ACT_IDENTITY == 0 && GNX_ACT_RELU == 1 && GNX_ACT_TANH == 2 && GNX_ACT_SIGMOID == 3 && GNX_ACT_GELU == 4,
               "act_apply (gnx_device.h) hard-codes the activation codes");
@@ -106,7 +107,7 @@ static int32_t block_forward_impl(const gnx_graphs* h, const gnx_block_params* p
                                   float ln_eps = 0.f, int ln_mode = 0, bool* fused_ln = nullptr, const float* const* wide_ln_stats = nullptr,
                                   BlockArgs* args_out = nullptr, const gnx_ffn* ffe = nullptr, const gnx_layernorm* ffe_ln2 = nullptr, bool* ffe_took = nullptr,
                                   const gnx_pending_update* chain_prev = nullptr, bool* chain_took = nullptr, bool* edge_x6_out = nullptr, bool ln_inline_e = false,
-                                  void* ffe_scratch = nullptr) {
+                                  void* ffe_scratch = nullptr, bool bf16 = false) {
   FormScope forms(flags);  // the forms this call selected (gnx.h: GNX_FLAG_FFN_FP32 ...) for every dispatch predicate below
   PreparedScope prepared(p ? p->prepared : nullptr);  // the layer's prepared weight planes, if the caller made them (a core passes its own through its block)
   int32_t rc = check_block(h, p, R);
@@ -181,6 +182,10 @@ static int32_t block_forward_impl(const gnx_graphs* h, const gnx_block_params* p
     }
     return launch_block_narrow_chained(h, a, R, s);
   }
+  if (bf16) {  // gnx_block_forward_typed: the six feature pointers are bf16; only the fused kernels read them natively (the caller checked)
+    rc = launch_block_narrow_bf16(h, a, R, s);
+    return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: no fused bf16 kernel for these widths") : rc;
+  }
   if (!(flags & GNX_FLAG_FORCE_GENERIC)) {
     rc = launch_block_narrow(h, a, R, s, phase);  // fused wave-per-tile kernel: ahead-of-time width sets, else specialised at run time
     if (rc != 1) return rc;
@@ -218,6 +223,97 @@ int32_t gnx_block_forward(const gnx_graphs* h, const gnx_block_params* p, const 
   DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
   return block_forward_impl(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream,
                             (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) ? 1 : 3);
+}
+
+}  // extern "C"
+
+// ---- bfloat16 features (gnx_block_forward_typed) ----
+namespace gnx {
+int32_t launch_bf16_widen(const void* src, size_t n, float* dst, hipStream_t s);  // gnx_bf16.hip
+int32_t launch_bf16_round(const float* src, size_t n, void* dst, hipStream_t s);
+
+// Does a fused kernel read and write bf16 rows for these widths under the call's forms (FormScope open)?  A run-time specialisation counts
+// once it is loaded (gnx_block_typed_workspace_bytes loads it; never inside a capture).
+static bool typed_native(const gnx_graphs* h, const gnx_block_params* p, uint32_t flags, hipStream_t s) {
+  if (flags & GNX_FLAG_FORCE_GENERIC) return false;
+  BlockArgs a{};
+  a.de = p->de; a.dn = p->dn; a.dg = p->dg; a.oe = p->oe; a.on = p->on; a.og = p->og;
+  a.n_wtiles = (int)h->n_wtiles(); a.E = (int)h->E; a.G = (int)h->G;
+  return block_narrow_takes(h, a, s, true);
+}
+
+// workspace of a bf16 call: gnx_block_forward's, then (fallback only) fp32 staging of the six tensors, each carve 256-B aligned
+struct TypedWs {
+  size_t base, off[6], n[6], total;
+};
+static TypedWs typed_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R, bool native) {
+  TypedWs w{};
+  w.base = block_ws(h, p, R).total;
+  const int64_t rows[3] = {h->E, h->N, h->G};
+  const int d[6] = {p->de, p->dn, p->dg, p->oe, p->on, p->og};
+  size_t o = align_up(w.base, 256);
+  for (int i = 0; i < 6; ++i) {
+    w.n[i] = native ? 0 : (size_t)R * (size_t)rows[i % 3] * (size_t)d[i];
+    w.off[i] = o;
+    o += align_up(sizeof(float) * w.n[i], 256);
+  }
+  w.total = native ? w.base : o;
+  return w;
+}
+}  // namespace gnx
+
+extern "C" {
+
+size_t gnx_block_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem, uint32_t flags) {
+  if (elem == GNX_ELEM_F32) return gnx_block_workspace_bytes(h, p, R);
+  if (elem != GNX_ELEM_BF16 || !h || !p || R <= 0 || (flags & GNX_FLAG_DEFER_GRAPH_UPDATE)) return 0;
+  FormScope forms(flags);
+  if (check_block(h, p, R) != GNX_OK) return 0;
+  warm_block_narrow(h, p, true);  // the bf16 specialisation of these widths, if they need one
+  const bool native = typed_native(h, p, flags, nullptr);
+  if (!native) (void)gnx_block_workspace_bytes(h, p, R);  // warms the fp32 path the fallback runs
+  return typed_ws(h, p, R, native).total;
+}
+
+int32_t gnx_block_forward_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf, int64_t R,
+                                void* ef_out, void* nf_out, void* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  if (elem == GNX_ELEM_F32)
+    return gnx_block_forward(h, p, static_cast<const float*>(ef), static_cast<const float*>(nf), static_cast<const float*>(gf), R, static_cast<float*>(ef_out),
+                             static_cast<float*>(nf_out), static_cast<float*>(gf_out), ws, ws_bytes, flags, stream);
+  if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "GNX_FLAG_DEFER_GRAPH_UPDATE is not supported with bf16 features");
+  const hipStream_t s = (hipStream_t)stream;
+  FormScope forms(flags);
+  int32_t rc = check_block(h, p, R);
+  if (rc) return rc;
+  if ((p->de > 0 && !ef && h->E > 0) || (p->dn > 0 && !nf) || (p->dg > 0 && !gf))
+    return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL (width 0 <=> nothing)");
+  if ((p->oe > 0 && !ef_out && h->E > 0) || (p->on > 0 && !nf_out) || (p->og > 0 && !gf_out))
+    return fail(GNX_ERR_INVALID_ARG, "an output with non-zero width is NULL");
+  const void* bufs[6] = {ef, nf, gf, ef_out, nf_out, gf_out};
+  for (const void* b : bufs)
+    if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  const bool native = typed_native(h, p, flags, s);
+  const TypedWs w = typed_ws(h, p, R, native);
+  if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_typed_workspace_bytes()");
+  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  if (native) {
+    DeviceTurn turn(s, false);  // (narrow widths: no matrix instruction)
+    return block_forward_impl(h, p, static_cast<const float*>(ef), static_cast<const float*>(nf), static_cast<const float*>(gf), R, static_cast<float*>(ef_out),
+                              static_cast<float*>(nf_out), static_cast<float*>(gf_out), ws, w.base, flags, s, 3, nullptr, 0.f, 0, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, true);
+  }
+  // every other path: widen into the workspace, the fp32 forward (its own dispatch, DeviceTurn included), round the outputs
+  float* st[6];
+  for (int i = 0; i < 6; ++i) st[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + w.off[i]);
+  for (int i = 0; i < 3; ++i)
+    if (w.n[i] > 0 && (rc = launch_bf16_widen(bufs[i], w.n[i], st[i], s)) != GNX_OK) return rc;
+  rc = gnx_block_forward(h, p, p->de ? st[0] : nullptr, p->dn ? st[1] : nullptr, p->dg ? st[2] : nullptr, R, p->oe ? st[3] : nullptr, p->on ? st[4] : nullptr,
+                         p->og ? st[5] : nullptr, ws, w.base, flags, stream);
+  if (rc) return rc;
+  for (int i = 3; i < 6; ++i)
+    if (w.n[i] > 0 && (rc = launch_bf16_round(st[i], w.n[i], const_cast<void*>(bufs[i]), s)) != GNX_OK) return rc;
+  return GNX_OK;
 }
 
 int32_t gnx_block_forward_chained(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R, float* ef_out,

@@ -14,97 +14,10 @@
 #include <cstdlib>
 
 #include "gnx_device.h"
+#include "gnx_narrow_launch.h"
 #include "gnx_wave_kernel.h"
 
 namespace gnx {
-
-// Rows of the partial-sum table per replica: one per workgroup (one graph) or one per wave tile (several graphs).
-static int partial_rows(const gnx_graphs* h) { return (int)(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->n_wtiles()); }
-
-// Threads of the graph update: one wavefront per graph while a graph has <= 256 partial rows (the usual heterogeneous batch:
-// C3 has ~16 rows per graph, C5 ~3), else 256, and 1024 from 1024 rows on (C2: 2032 rows, two per thread in flight at once).
-static int graph_update_threads(const gnx_graphs* h) {
-  return graph_update_threads_for_rows(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->max_wtiles_per_graph);
-}
-
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool FFE = false, bool CHAIN = false>
-static int32_t launch_wave_g(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
-  constexpr int C = OE + ON;
-  const int n_rows = partial_rows(h);
-  const unsigned grid = (unsigned)((a.n_wtiles + 3) / 4) + (CHAIN ? (unsigned)a.prev_blocks : 0u);
-  if (phase & 1) {
-    ProfScope ps("k_block_wave", s);
-#ifdef GNX_WAVE_STAMPS_BUILD  // diagnostic build: GNX_WAVE_STAMPS_DUMP=<file> writes [wave tile][8] shader-clock stamps of every (eager) launch
-    static unsigned long long* d_dbg = nullptr;
-    static size_t dbg_cap = 0;
-    const char* dump = getenv("GNX_WAVE_STAMPS_DUMP");
-    if (dump) {
-      if (dbg_cap < (size_t)a.n_wtiles) { if (d_dbg) (void)hipFree(d_dbg); dbg_cap = (size_t)a.n_wtiles; (void)hipMalloc((void**)&d_dbg, dbg_cap * 64); }
-      (void)hipMemsetAsync(d_dbg, 0, (size_t)a.n_wtiles * 64, s);
-      (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_wave_dbg), &d_dbg, sizeof(d_dbg), 0, hipMemcpyHostToDevice, s);
-    }
-#endif
-    if constexpr (FFE) GNX_LAUNCH((k_block_wave_ffe<DE, DN, DG, OE, ON, EPT, ONEG>), dim3(grid, (unsigned)R), dim3(kThreads), 0, s, a, n_rows);
-    else GNX_LAUNCH((k_block_wave<DE, DN, DG, OE, ON, EPT, LN, ONEG, false, false, CHAIN>), dim3(grid, (unsigned)R), dim3(kThreads), 0, s, a, n_rows);
-    GNX_HIP(hipGetLastError());
-#ifdef GNX_WAVE_STAMPS_BUILD
-    if (dump) {
-      (void)hipStreamSynchronize(s);
-      std::vector<unsigned long long> hs((size_t)a.n_wtiles * 8);
-      (void)hipMemcpy(hs.data(), d_dbg, hs.size() * 8, hipMemcpyDeviceToHost);
-      if (FILE* f = fopen(dump, "wb")) { fwrite(hs.data(), 8, hs.size(), f); fclose(f); }
-    }
-#endif
-  }
-  if ((phase & 2) && a.og > 0) {
-    if constexpr (C > 0) {
-      const int threads = graph_update_threads(h);
-      const size_t lds = sizeof(float) * (size_t)graph_update_lds_floats(C, a.dg, a.og, threads);
-      ProfScope ps("k_graph_t", s);
-      GNX_LAUNCH((k_graph_t<C, ONEG>), dim3((unsigned)a.G, (unsigned)R), dim3(threads), lds, s, a, n_rows);
-      GNX_HIP(hipGetLastError());
-    }
-  }
-  return GNX_OK;
-}
-
-// Batches of small graphs (every graph <= 8 wave tiles: the handle has a pack table): ONE launch — 512-thread workgroups that own whole
-// graphs run the graph update themselves (k_block_wave<..., PACK>).  Only for the whole block in one call (phase 3): a caller that
-// splits off the graph update, or a narrow GNCore that runs it inside its FeedForward launch, reads the partial rows of the two-launch form.
-// GNX_FLAG_NO_PACK keeps the two launches.
-template <int DE, int DN, int DG, int OE, int ON, int EPT>
-static bool launch_wave_pack(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, int32_t* rc) {
-  constexpr int C = OE + ON;
-  if constexpr (EPT != 2 || C == 0) return false;
-  else {
-    if (h->G <= 1 || h->n_packs <= 0 || !a.packs || phase != 3 || a.og <= 0 || form(GNX_FLAG_NO_PACK)) return false;
-    ProfScope ps("k_block_wave", s);
-    GNX_LAUNCH((k_block_wave<DE, DN, DG, OE, ON, EPT, false, false, true>), dim3((unsigned)h->n_packs, (unsigned)R), dim3(kPackThreads), 0, s, a, 0);
-    const hipError_t e = hipGetLastError();
-    *rc = e == hipSuccess ? GNX_OK : hip_fail(e, "k_block_wave<PACK>");
-    return true;
-  }
-}
-
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN = false>
-static int32_t launch_wave_t(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
-  if constexpr (!LN) {
-    int32_t rc = GNX_OK;
-    if (launch_wave_pack<DE, DN, DG, OE, ON, EPT>(h, a, R, s, phase, &rc)) return rc;
-  }
-  return h->G == 1 ? launch_wave_g<DE, DN, DG, OE, ON, EPT, LN, true>(h, a, R, s, phase) : launch_wave_g<DE, DN, DG, OE, ON, EPT, LN, false>(h, a, R, s, phase);
-}
-
-template <int DE, int DN, int DG, int OE, int ON>
-static int32_t launch_fused(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
-  // the kernel's EPT must match the handle's wave-tile edge cap (GNX_WTILE_E at handle creation: 64, 128 or 256)
-  if (h->wtile_e_cap == 64) return launch_wave_t<DE, DN, DG, OE, ON, 1>(h, a, R, s, phase);
-  if (h->wtile_e_cap == 128) return launch_wave_t<DE, DN, DG, OE, ON, 2>(h, a, R, s, phase);
-  if (h->wtile_e_cap == 256) {
-    if constexpr ((DE + DN) * 4 <= 64) return launch_wave_t<DE, DN, DG, OE, ON, 4>(h, a, R, s, phase);
-  }
-  return 1;
-}
 
 // Instantiated width sets.  (de, dn, dg) => (oe, on); og is free (the graph update is its own small kernel).
 #define GNX_NARROW_DIMS(X) \
@@ -117,16 +30,19 @@ static int32_t launch_fused(const gnx_graphs* h, const BlockArgs& a, int64_t R, 
   X(8, 8, 8, 16, 8)        \
   X(10, 5, 3, 10, 5)       \
   X(10, 5, 0, 10, 5)
+// ... with bfloat16 features: gnx_narrow_bf16.hip
+bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a);
+int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
 
 bool jit_eligible(const BlockArgs& a, int ept);
-int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph);
+int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph, bool bf16 = false);
 
 // Same launch geometry as launch_wave_t, kernels specialised at run time (gnx_jit.cpp) for this width set.
-static int32_t launch_wave_jit(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+static int32_t launch_wave_jit(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, bool bf16 = false) {
   const int ept = h->wtile_e_cap / 64;
   if (ept * 64 != h->wtile_e_cap || (ept != 1 && ept != 2 && ept != 4)) return 1;
   hipFunction_t fb = nullptr, fg = nullptr;
-  const int32_t rc = jit_get(a, ept, s, &fb, &fg);
+  const int32_t rc = jit_get(a, ept, s, &fb, &fg, bf16);
   if (rc) return rc;
   const int C = a.oe + a.on;
   BlockArgs aa = a;
@@ -147,18 +63,20 @@ static int32_t launch_wave_jit(const gnx_graphs* h, const BlockArgs& a, int64_t 
 
 // compiles + loads the run-time specialised kernels of this width set ahead of the first forward (called from
 // gnx_block_workspace_bytes, which every caller runs before a forward and never inside a stream capture)
-void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p) {
+void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p, bool bf16) {
   BlockArgs a{};
   a.de = p->de; a.dn = p->dn; a.dg = p->dg; a.oe = p->oe; a.on = p->on; a.og = p->og;
   a.G = (int)h->G;  // selects the one-graph / several-graphs variant of the kernel
 #define GNX_CASE(DE, DN, DG, OE, ON) \
   if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return;
   static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // (diagnostic: specialise even the ahead-of-time width sets; read once)
-  if (!jit_all) { GNX_NARROW_DIMS(GNX_CASE) }
+  if (!jit_all) {
+    if (bf16) { if (narrow_bf16_aot(h, a)) return; } else { GNX_NARROW_DIMS(GNX_CASE) }
+  }
 #undef GNX_CASE
   if (h->n_wtiles() == 0 || h->E == 0) return;
   hipFunction_t fb, fg;
-  (void)jit_get(a, h->wtile_e_cap / 64, nullptr, &fb, &fg);
+  (void)jit_get(a, h->wtile_e_cap / 64, nullptr, &fb, &fg, bf16);
 }
 
 static bool wants_ln(const BlockArgs& a) { return a.ln_g[0] || a.ln_g[1] || a.ln_g[2]; }
@@ -233,25 +151,39 @@ bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1,
 // the caller goes on to the matrix-core / generic kernels.  The ONE place this is decided: launch_block_narrow dispatches on it and
 // block_narrow_takes (gnx_block_forward_steps: two streams only on this path) asks it.
 enum NarrowRoute { NR_NONE, NR_AOT, NR_JIT };
-static NarrowRoute narrow_route(const gnx_graphs* h, const BlockArgs& a, hipStream_t s) {
+static NarrowRoute narrow_route(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16 = false) {
   if (a.n_wtiles == 0 || a.E == 0 || wants_ln(a)) return NR_NONE;
   auto jit_ok = [&]() {
     const int ept = h->wtile_e_cap / 64;
     if (ept * 64 != h->wtile_e_cap || (ept != 1 && ept != 2 && ept != 4)) return false;
     hipFunction_t fb, fg;
-    return jit_get(a, ept, s, &fb, &fg) == GNX_OK;
+    return jit_get(a, ept, s, &fb, &fg, bf16) == GNX_OK;
   };
   static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // testing: run-time specialise even the listed width sets
   if (jit_all && jit_ok()) return NR_JIT;
 #define GNX_CASE(DE, DN, DG, OE, ON)                                                                                              \
   if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON)                                                          \
     return h->wtile_e_cap == 64 || h->wtile_e_cap == 128 || (h->wtile_e_cap == 256 && (DE + DN) * 4 <= 64) ? NR_AOT : NR_NONE;  // (launch_fused's EPT)
-  GNX_NARROW_DIMS(GNX_CASE)
+  if (bf16) {
+    if (narrow_bf16_aot(h, a)) return NR_AOT;
+  } else {
+    GNX_NARROW_DIMS(GNX_CASE)
+  }
 #undef GNX_CASE
   return jit_ok() ? NR_JIT : NR_NONE;
 }
 
-bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s) { return narrow_route(h, a, s) != NR_NONE; }
+bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16) { return narrow_route(h, a, s, bf16) != NR_NONE; }
+
+// bf16 features (gnx_block_forward_typed): the native kernels, or 1 when no fused kernel takes these widths (the caller converts around
+// the fp32 forward).  No LayerNorm on load, no chained / deferred forms.
+int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s) {
+  const NarrowRoute route = narrow_route(h, a, s, true);
+  if (route == NR_NONE) return 1;
+  if (route == NR_JIT) return launch_wave_jit(h, a, R, s, 3, true);
+  const int32_t rc = launch_fused_bf16(h, a, R, s);
+  return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: ahead-of-time bf16 route for a width set without that kernel") : rc;
+}
 
 int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
   if (a.n_wtiles == 0 || a.E == 0) return 1;

@@ -1,0 +1,35 @@
+// The fused narrow kernels with bfloat16 feature rows (k_block_wave<..., BF16 = true>, k_graph_t<C, ONEG, true>) for the ahead-of-time
+// width sets; gnx_narrow.hip routes gnx_block_forward_typed here, every other narrow width set is specialised at run time (gnx_jit.cpp).
+// A translation unit of its own because build.py compiles it without the SLP vectoriser (-fno-slp-vectorize; gnx_jit.cpp passes the same
+// option for a bf16 key): with it, every widened value feeds a v_pk_fma_f32 as the low half of a register pair of its own, and the README
+// ex.1 kernel needs 70 instead of 58 VGPRs — 7 instead of 8 waves per SIMD.  Scalar FMAs compute the same bits.
+#include "gnx_device.h"
+#include "gnx_narrow_launch.h"
+#include "gnx_wave_kernel.h"
+
+namespace gnx {
+
+// README ex.1 / the headline batch (BASELINE configs[1])
+#define GNX_NARROW_DIMS_BF16(X) \
+  X(10, 5, 0, 3, 4)
+
+// an ahead-of-time bf16 kernel exists for these widths at the handle's wave-tile size (launch_fused's EPT)
+bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a) {
+#define GNX_CASE(DE, DN, DG, OE, ON)                                     \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) \
+    return h->wtile_e_cap == 64 || h->wtile_e_cap == 128 || (h->wtile_e_cap == 256 && (DE + DN) * 4 <= 64);
+  GNX_NARROW_DIMS_BF16(GNX_CASE)
+#undef GNX_CASE
+  return false;
+}
+
+// the whole block (phase 3) on bf16 rows; 1: no ahead-of-time kernel for these widths
+int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s) {
+#define GNX_CASE(DE, DN, DG, OE, ON) \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return launch_fused<DE, DN, DG, OE, ON, true>(h, a, R, s, 3);
+  GNX_NARROW_DIMS_BF16(GNX_CASE)
+#undef GNX_CASE
+  return 1;
+}
+
+}  // namespace gnx

@@ -1,0 +1,100 @@
+// Launchers of the fused narrow kernels (gnx_wave_kernel.h) for a width set known at compile time: shared by gnx_narrow.hip (fp32 features)
+// and gnx_narrow_bf16.hip (bfloat16 features, a translation unit of its own: see there).
+#pragma once
+#include <cstdlib>
+
+#include "gnx_device.h"
+#include "gnx_wave_kernel.h"
+
+namespace gnx {
+
+// Rows of the partial-sum table per replica: one per workgroup (one graph) or one per wave tile (several graphs).
+static int partial_rows(const gnx_graphs* h) { return (int)(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->n_wtiles()); }
+
+// Threads of the graph update: one wavefront per graph while a graph has <= 256 partial rows (the usual heterogeneous batch:
+// C3 has ~16 rows per graph, C5 ~3), else 256, and 1024 from 1024 rows on (C2: 2032 rows, two per thread in flight at once).
+static int graph_update_threads(const gnx_graphs* h) {
+  return graph_update_threads_for_rows(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->max_wtiles_per_graph);
+}
+
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool FFE = false, bool CHAIN = false, bool BF16 = false>
+static int32_t launch_wave_g(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+  constexpr int C = OE + ON;
+  const int n_rows = partial_rows(h);
+  const unsigned grid = (unsigned)((a.n_wtiles + 3) / 4) + (CHAIN ? (unsigned)a.prev_blocks : 0u);
+  if (phase & 1) {
+    ProfScope ps("k_block_wave", s);
+#ifdef GNX_WAVE_STAMPS_BUILD  // diagnostic build: GNX_WAVE_STAMPS_DUMP=<file> writes [wave tile][8] shader-clock stamps of every (eager) launch
+    static unsigned long long* d_dbg = nullptr;
+    static size_t dbg_cap = 0;
+    const char* dump = getenv("GNX_WAVE_STAMPS_DUMP");
+    if (dump) {
+      if (dbg_cap < (size_t)a.n_wtiles) { if (d_dbg) (void)hipFree(d_dbg); dbg_cap = (size_t)a.n_wtiles; (void)hipMalloc((void**)&d_dbg, dbg_cap * 64); }
+      (void)hipMemsetAsync(d_dbg, 0, (size_t)a.n_wtiles * 64, s);
+      (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_wave_dbg), &d_dbg, sizeof(d_dbg), 0, hipMemcpyHostToDevice, s);
+    }
+#endif
+    if constexpr (FFE) GNX_LAUNCH((k_block_wave_ffe<DE, DN, DG, OE, ON, EPT, ONEG>), dim3(grid, (unsigned)R), dim3(kThreads), 0, s, a, n_rows);
+    else GNX_LAUNCH((k_block_wave<DE, DN, DG, OE, ON, EPT, LN, ONEG, false, false, CHAIN, BF16>), dim3(grid, (unsigned)R), dim3(kThreads), 0, s, a, n_rows);
+    GNX_HIP(hipGetLastError());
+#ifdef GNX_WAVE_STAMPS_BUILD
+    if (dump) {
+      (void)hipStreamSynchronize(s);
+      std::vector<unsigned long long> hs((size_t)a.n_wtiles * 8);
+      (void)hipMemcpy(hs.data(), d_dbg, hs.size() * 8, hipMemcpyDeviceToHost);
+      if (FILE* f = fopen(dump, "wb")) { fwrite(hs.data(), 8, hs.size(), f); fclose(f); }
+    }
+#endif
+  }
+  if ((phase & 2) && a.og > 0) {
+    if constexpr (C > 0) {
+      const int threads = graph_update_threads(h);
+      const size_t lds = sizeof(float) * (size_t)graph_update_lds_floats(C, a.dg, a.og, threads);
+      ProfScope ps("k_graph_t", s);
+      GNX_LAUNCH((k_graph_t<C, ONEG, BF16>), dim3((unsigned)a.G, (unsigned)R), dim3(threads), lds, s, a, n_rows);
+      GNX_HIP(hipGetLastError());
+    }
+  }
+  return GNX_OK;
+}
+
+// Batches of small graphs (every graph <= 8 wave tiles: the handle has a pack table): ONE launch — 512-thread workgroups that own whole
+// graphs run the graph update themselves (k_block_wave<..., PACK>).  Only for the whole block in one call (phase 3): a caller that
+// splits off the graph update, or a narrow GNCore that runs it inside its FeedForward launch, reads the partial rows of the two-launch form.
+// GNX_FLAG_NO_PACK keeps the two launches.
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool BF16 = false>
+static bool launch_wave_pack(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, int32_t* rc) {
+  constexpr int C = OE + ON;
+  if constexpr (EPT != 2 || C == 0) return false;
+  else {
+    if (h->G <= 1 || h->n_packs <= 0 || !a.packs || phase != 3 || a.og <= 0 || form(GNX_FLAG_NO_PACK)) return false;
+    ProfScope ps("k_block_wave", s);
+    GNX_LAUNCH((k_block_wave<DE, DN, DG, OE, ON, EPT, false, false, true, false, false, BF16>), dim3((unsigned)h->n_packs, (unsigned)R), dim3(kPackThreads), 0, s, a, 0);
+    const hipError_t e = hipGetLastError();
+    *rc = e == hipSuccess ? GNX_OK : hip_fail(e, "k_block_wave<PACK>");
+    return true;
+  }
+}
+
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN = false, bool BF16 = false>
+static int32_t launch_wave_t(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+  if constexpr (!LN) {
+    int32_t rc = GNX_OK;
+    if (launch_wave_pack<DE, DN, DG, OE, ON, EPT, BF16>(h, a, R, s, phase, &rc)) return rc;
+  }
+  return h->G == 1 ? launch_wave_g<DE, DN, DG, OE, ON, EPT, LN, true, false, false, BF16>(h, a, R, s, phase)
+                   : launch_wave_g<DE, DN, DG, OE, ON, EPT, LN, false, false, false, BF16>(h, a, R, s, phase);
+}
+
+template <int DE, int DN, int DG, int OE, int ON, bool BF16 = false>
+static int32_t launch_fused(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+  // the kernel's EPT must match the handle's wave-tile edge cap (GNX_WTILE_E at handle creation: 64, 128 or 256)
+  if (h->wtile_e_cap == 64) return launch_wave_t<DE, DN, DG, OE, ON, 1, false, BF16>(h, a, R, s, phase);
+  if (h->wtile_e_cap == 128) return launch_wave_t<DE, DN, DG, OE, ON, 2, false, BF16>(h, a, R, s, phase);
+  if (h->wtile_e_cap == 256) {
+    if constexpr ((DE + DN) * 4 <= 64) return launch_wave_t<DE, DN, DG, OE, ON, 4, false, BF16>(h, a, R, s, phase);
+  }
+  return 1;
+}
+
+}  // namespace gnx

@@ -60,6 +60,128 @@ __device__ __forceinline__ void store_row(float* __restrict__ p, const float (&x
   }
 }
 
+// ---- bfloat16 feature rows (gnx_block_forward_typed, GNX_ELEM_BF16) ----
+// Values are widened exactly on load (bf16 -> fp32 is a 16-bit shift) and rounded to nearest even only where an output is stored
+// (v_cvt_pk_bf16_f32); all arithmetic in between is the fp32 arithmetic above.  Buffers are 4-B aligned (the entry point checks), a row of D
+// elements starts at byte 2 * row * D: rows of even width are dword-aligned, rows of odd width only 2-B aligned.  Loads then read the
+// enclosing aligned dwords — every one of them holds a byte of the row, so none lies past the buffer — and funnel-shift them; stores write
+// the aligned interior pairs as dwords and the one boundary element as a 16-bit store: the other half of that dword is another lane's row.
+typedef unsigned short bf16_t;
+template <bool BF16> struct ElemOf { typedef float T; };
+template <> struct ElemOf<true> { typedef bf16_t T; };
+struct __attribute__((packed, aligned(4))) U4u { unsigned x, y, z, w; };
+struct __attribute__((packed, aligned(4))) U3u { unsigned x, y, z; };
+struct __attribute__((packed, aligned(4))) U2u { unsigned x, y; };
+typedef float f2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f2_t){lo, hi}, bf2_t));
+}
+__device__ __forceinline__ bf16_t to_bf16(float x) { return __builtin_bit_cast(bf16_t, (__bf16)x); }
+
+template <int N>
+__device__ __forceinline__ void load_dwords(const unsigned* __restrict__ p, unsigned (&w)[N]) {
+  constexpr int Q = N / 4, R = N % 4;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const U4u v = *reinterpret_cast<const U4u*>(p + 4 * q);
+    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+  }
+  if constexpr (R == 3) {
+    const U3u v = *reinterpret_cast<const U3u*>(p + 4 * Q);
+    w[4 * Q] = v.x; w[4 * Q + 1] = v.y; w[4 * Q + 2] = v.z;
+  } else if constexpr (R == 2) {
+    const U2u v = *reinterpret_cast<const U2u*>(p + 4 * Q);
+    w[4 * Q] = v.x; w[4 * Q + 1] = v.y;
+  } else if constexpr (R == 1) {
+    w[4 * Q] = p[4 * Q];
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void store_dwords(unsigned* __restrict__ p, const unsigned (&w)[N]) {
+  constexpr int Q = N / 4, R = N % 4;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    U4u v; v.x = w[4 * q]; v.y = w[4 * q + 1]; v.z = w[4 * q + 2]; v.w = w[4 * q + 3];
+    *reinterpret_cast<U4u*>(p + 4 * q) = v;
+  }
+  if constexpr (R == 3) {
+    U3u v; v.x = w[4 * Q]; v.y = w[4 * Q + 1]; v.z = w[4 * Q + 2];
+    *reinterpret_cast<U3u*>(p + 4 * Q) = v;
+  } else if constexpr (R == 2) {
+    U2u v; v.x = w[4 * Q]; v.y = w[4 * Q + 1];
+    *reinterpret_cast<U2u*>(p + 4 * Q) = v;
+  } else if constexpr (R == 1) {
+    p[4 * Q] = w[4 * Q];
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void load_row(const bf16_t* __restrict__ p, float (&x)[D > 0 ? D : 1]) {
+  if constexpr (D % 2 == 0) {
+    unsigned w[D / 2];
+    load_dwords<D / 2>(reinterpret_cast<const unsigned*>(p), w);
+#pragma unroll
+    for (int j = 0; j < D / 2; ++j) { x[2 * j] = bf16_lo(w[j]); x[2 * j + 1] = bf16_hi(w[j]); }
+  } else {
+    // (D + 1) / 2 dwords from the one holding element 0; a row that starts in a dword's high half is shifted down by 16 bits
+    constexpr int N = (D + 1) / 2;
+    const size_t a = reinterpret_cast<size_t>(p);
+    unsigned w[N];
+    load_dwords<N>(reinterpret_cast<const unsigned*>(a & ~(size_t)3), w);
+    const unsigned sh = (unsigned)(a & 2) << 3;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const unsigned v = __builtin_amdgcn_alignbit(j + 1 < N ? w[j + 1] : 0u, w[j], sh);
+      x[2 * j] = bf16_lo(v);
+      if (2 * j + 1 < D) x[2 * j + 1] = bf16_hi(v);
+    }
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void store_row(bf16_t* __restrict__ p, const float (&x)[D > 0 ? D : 1]) {
+  if constexpr (D % 2 == 0) {
+    unsigned w[D / 2];
+#pragma unroll
+    for (int j = 0; j < D / 2; ++j) w[j] = pack_bf16(x[2 * j], x[2 * j + 1]);
+    store_dwords<D / 2>(reinterpret_cast<unsigned*>(p), w);
+  } else {
+    // row starting in a dword's low half: pairs (0,1), (2,3), ... and element D-1 alone; in the high half: element 0 alone, pairs (1,2), ...
+    constexpr int M = (D - 1) / 2;
+    const size_t a = reinterpret_cast<size_t>(p);
+    const bool hi = (a & 2) != 0;
+    if constexpr (M > 0) {
+      unsigned w[M];
+#pragma unroll
+      for (int j = 0; j < M; ++j) w[j] = pack_bf16(hi ? x[2 * j + 1] : x[2 * j], hi ? x[2 * j + 2] : x[2 * j + 1]);
+      store_dwords<M>(reinterpret_cast<unsigned*>(a + (hi ? 2 : 0)), w);
+    }
+    *reinterpret_cast<bf16_t*>(a + (hi ? 0 : 2 * (D - 1))) = to_bf16(hi ? x[0] : x[D - 1]);
+  }
+}
+
+// one element of a feature buffer (graph rows: a few values per graph)
+template <bool BF16>
+__device__ __forceinline__ float ld_feat(const float* base, size_t i) {
+  if constexpr (BF16) return bf16_lo(reinterpret_cast<const bf16_t*>(base)[i]);
+  else return base[i];
+}
+template <bool BF16>
+__device__ __forceinline__ void st_feat(float* base, size_t i, float v) {
+  if constexpr (BF16) reinterpret_cast<bf16_t*>(base)[i] = to_bf16(v);
+  else base[i] = v;
+}
+// a feature pointer of BlockArgs (declared float) as the element type of the launch
+template <bool BF16>
+__device__ __forceinline__ const typename ElemOf<BF16>::T* feat(const float* p) { return reinterpret_cast<const typename ElemOf<BF16>::T*>(p); }
+template <bool BF16>
+__device__ __forceinline__ typename ElemOf<BF16>::T* feat(float* p) { return reinterpret_cast<typename ElemOf<BF16>::T*>(p); }
+
 // activation of a whole register row: ONE (wave-uniform) switch, the loop inside each case
 template <int N>
 __device__ __forceinline__ void act_row(float (&v)[N], int act) {
@@ -449,7 +571,7 @@ __device__ __forceinline__ void store_partial_row(float mine, float* row, int la
 
 // vthr (a multiple of 64; 0: nthr): the sums come out as a launch of vthr threads would form them — the bits k_graph_t gives with that many
 // threads.  Thread tid plays the threads tid, tid + nthr, ... below vthr in turn (none, one or several; the same count across a wavefront).
-template <int C, bool WAVE, int F4_IN_FLIGHT>
+template <int C, bool WAVE, int F4_IN_FLIGHT, bool BF16 = false>
 __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const float* __restrict__ base, int g, size_t r, int t0, int t1, int tid, int nthr, float* s_g,
                                                   int vthr = 0) {
   constexpr int Q = (C + 3) / 4, CP = 4 * Q;
@@ -469,7 +591,7 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
     w_reg[i] = idx < nw ? a.Wg[idx] : (idx < nw + og ? (a.bg ? a.bg[idx - nw] : 0.f) : 0.f);
   }
   float gf_reg = 0.f;
-  if (tid < a.dg) gf_reg = a.gf[(r * (size_t)a.G + g) * a.dg + tid];
+  if (tid < a.dg) gf_reg = ld_feat<BF16>(a.gf, (r * (size_t)a.G + g) * a.dg + tid);
 
   const int lane = tid & 63;
   for (int v = tid; v < vthr; v += nthr) {
@@ -509,18 +631,18 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
   }
   for (int idx = tid + 4 * nthr; idx < nw + og; idx += nthr) s_w[idx] = idx < nw ? a.Wg[idx] : (a.bg ? a.bg[idx - nw] : 0.f);
   if (a.ln_g[2] && a.dg > 0) {  // GNCore: the graph function sees gn1(gf); a few values, every thread computes the statistics
-    const float* gp = a.gf + (r * (size_t)a.G + g) * a.dg;
+    const size_t gp = (r * (size_t)a.G + g) * a.dg;
     float mu = 0.f;
-    for (int k = 0; k < a.dg; ++k) mu += gp[k];
+    for (int k = 0; k < a.dg; ++k) mu += ld_feat<BF16>(a.gf, gp + k);
     mu /= (float)a.dg;
     float var = 0.f;
-    for (int k = 0; k < a.dg; ++k) { const float c = gp[k] - mu; var = fmaf(c, c, var); }
+    for (int k = 0; k < a.dg; ++k) { const float c = ld_feat<BF16>(a.gf, gp + k) - mu; var = fmaf(c, c, var); }
     var /= (float)a.dg;
     const float rstd = a.ln_mode == 0 ? 1.f / (sqrtf(var) + a.ln_eps) : 1.f / sqrtf(var + a.ln_eps);
-    for (int k = tid; k < a.dg; k += nthr) s_x[C + k] = fmaf(a.ln_g[2][k], (gp[k] - mu) * rstd, a.ln_b[2][k]);
+    for (int k = tid; k < a.dg; k += nthr) s_x[C + k] = fmaf(a.ln_g[2][k], (ld_feat<BF16>(a.gf, gp + k) - mu) * rstd, a.ln_b[2][k]);
   } else {
     if (tid < a.dg) s_x[C + tid] = gf_reg;
-    for (int k = tid + nthr; k < a.dg; k += nthr) s_x[C + k] = a.gf[(r * (size_t)a.G + g) * a.dg + k];
+    for (int k = tid + nthr; k < a.dg; k += nthr) s_x[C + k] = ld_feat<BF16>(a.gf, (r * (size_t)a.G + g) * a.dg + k);
   }
   if constexpr (WAVE) __builtin_amdgcn_wave_barrier(); else __syncthreads();
   // second stage: wave 0 sums the <= 64 row sums of every column (fixed order: DPP tree + 4 readlanes)
@@ -532,11 +654,11 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
     }
   }
   if constexpr (WAVE) __builtin_amdgcn_wave_barrier(); else __syncthreads();
-  float* out = a.gf_out + (r * (size_t)a.G + g) * og;
+  const size_t out = (r * (size_t)a.G + g) * og;
   for (int j = tid; j < og; j += nthr) {
     float y = s_w[nw + j];
     for (int k = 0; k < K; ++k) y = fmaf(s_w[k * og + j], s_x[k], y);
-    out[j] = act_apply(y, a.act_g);
+    st_feat<BF16>(a.gf_out, out + j, act_apply(y, a.act_g));
   }
 }
 
@@ -554,37 +676,37 @@ __device__ __forceinline__ void graph_wave_prefetch(const BlockArgs& a, int lane
 #pragma unroll
   for (int u = 0; u < kGraphWavePrefetch; ++u) gr.w[u] = a.Wg[(size_t)(u < K ? u : K - 1) * og + j];
 }
-template <int C>
+template <int C, bool BF16 = false>
 __device__ __forceinline__ void graph_update_wave(const BlockArgs& a, float xsum, int g, size_t r, int lane, float* s_x, const GraphWaveRegs& gr) {
   const int K = C + a.dg, og = a.og;
   if (lane < C) s_x[lane] = xsum;
-  const float* gp = a.dg > 0 ? a.gf + (r * (size_t)a.G + g) * a.dg : nullptr;
+  const size_t gp = (r * (size_t)a.G + g) * a.dg;
   if (a.ln_g[2] && a.dg > 0) {
     float mu = 0.f;
-    for (int k = 0; k < a.dg; ++k) mu += gp[k];
+    for (int k = 0; k < a.dg; ++k) mu += ld_feat<BF16>(a.gf, gp + k);
     mu /= (float)a.dg;
     float var = 0.f;
-    for (int k = 0; k < a.dg; ++k) { const float c = gp[k] - mu; var = fmaf(c, c, var); }
+    for (int k = 0; k < a.dg; ++k) { const float c = ld_feat<BF16>(a.gf, gp + k) - mu; var = fmaf(c, c, var); }
     var /= (float)a.dg;
     const float rstd = a.ln_mode == 0 ? 1.f / (sqrtf(var) + a.ln_eps) : 1.f / sqrtf(var + a.ln_eps);
-    for (int k = lane; k < a.dg; k += 64) s_x[C + k] = fmaf(a.ln_g[2][k], (gp[k] - mu) * rstd, a.ln_b[2][k]);
+    for (int k = lane; k < a.dg; k += 64) s_x[C + k] = fmaf(a.ln_g[2][k], (ld_feat<BF16>(a.gf, gp + k) - mu) * rstd, a.ln_b[2][k]);
   } else {
-    for (int k = lane; k < a.dg; k += 64) s_x[C + k] = gp[k];
+    for (int k = lane; k < a.dg; k += 64) s_x[C + k] = ld_feat<BF16>(a.gf, gp + k);
   }
   __builtin_amdgcn_wave_barrier();
-  float* out = a.gf_out + (r * (size_t)a.G + g) * og;
+  const size_t out = (r * (size_t)a.G + g) * og;
   if (lane < og) {  // FMAs in the order k = 0, 1, 2, ... (the order of graph_update_rows)
     float y = gr.bias;
 #pragma unroll
     for (int u = 0; u < kGraphWavePrefetch; ++u)
       if (u < K) y = fmaf(gr.w[u], s_x[u], y);
     for (int k = kGraphWavePrefetch; k < K; ++k) y = fmaf(a.Wg[(size_t)k * og + lane], s_x[k], y);
-    out[lane] = act_apply(y, a.act_g);
+    st_feat<BF16>(a.gf_out, out + lane, act_apply(y, a.act_g));
   }
   for (int j = lane + 64; j < og; j += 64) {  // (graph functions wider than a wavefront: plain loop)
     float y = a.bg ? a.bg[j] : 0.f;
     for (int k = 0; k < K; ++k) y = fmaf(a.Wg[(size_t)k * og + j], s_x[k], y);
-    out[j] = act_apply(y, a.act_g);
+    st_feat<BF16>(a.gf_out, out + j, act_apply(y, a.act_g));
   }
 }
 
@@ -663,9 +785,10 @@ __device__ __forceinline__ auto phase_args(const BlockArgs& a) {
   }
 }
 
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK, bool FFE, bool CHAIN>
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK, bool FFE, bool CHAIN, bool BF16 = false>
 __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   static_assert(!(PACK && ONEG), "packs are for batches of several graphs");
+  static_assert(!BF16 || (!FFE && !CHAIN && !LN), "bf16 features: the plain block forward");
   static_assert(!CHAIN || (!PACK && !FFE && !LN && OE + ON > 0), "CHAIN: the two-launch form of a plain block");
   static_assert(!FFE || (LN && DE == OE && DE > 0 && EPT == 2 && (DE + DN) * OE > 96 && ((DE + DN) * OE) % 2 == 0 && GNX_WAVE_PK && !PACK),
                 "FFE: a core's block (dims => dims) with LayerNorm on load, two edges per lane, streamed weights");
@@ -748,9 +871,9 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   GNX_WSTAMP(1);  // (the stamp's own s_waitcnt lgkmcnt(0) makes this "tile record arrived")
 
   const size_t r = blockIdx.y;
-  const float* __restrict__ ef = DE > 0 ? A0->ef + r * (size_t)A0->E * DE : nullptr;
-  const float* __restrict__ nf = DN > 0 ? A0->nf + r * (size_t)A0->N * DN : nullptr;
-  const cfloatp gf = DG > 0 ? as_const(A0->gf + (r * (size_t)A0->G + g) * DG) : nullptr;
+  const auto* __restrict__ ef = DE > 0 ? feat<BF16>(A0->ef) + r * (size_t)A0->E * DE : nullptr;  // (float or bf16_t rows)
+  const auto* __restrict__ nf = DN > 0 ? feat<BF16>(A0->nf) + r * (size_t)A0->N * DN : nullptr;
+  const cfloatp gf = DG > 0 && !BF16 ? as_const(A0->gf + (r * (size_t)A0->G + g) * DG) : nullptr;
 
   // ---- issue every load up front, branch-free (indices clamped into the tile; results of clamped lanes unused) ----
   const bool is_node = lane < nn;
@@ -785,8 +908,12 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
     for (int i = 0; i < EPT; ++i) load_row<DN>(nf + (size_t)src[i] * DN, xs[i]);
   }
   float gfr[1][DG1];
+  if constexpr (BF16) {
+    if constexpr (DG > 0) load_row<DG>(feat<true>(A0->gf) + (r * (size_t)A0->G + g) * DG, gfr[0]);
+  } else {
 #pragma unroll
-  for (int k = 0; k < DG; ++k) gfr[0][k] = gf[k];
+    for (int k = 0; k < DG; ++k) gfr[0][k] = gf[k];
+  }
   if constexpr (LN) {  // gn1(x) applied in registers: rows are normalised as they arrive (gathered rows once per edge)
     ln_row<DN>(xn[0], A0->ln_g[1], A0->ln_b[1], A0->ln_eps, A0->ln_mode);
     ln_row<DG>(gfr[0], A0->ln_g[2], A0->ln_b[2], A0->ln_eps, A0->ln_mode);
@@ -919,7 +1046,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
           act_row<OE1>(acc[i], A1->act_e);
         }
         if (valid[i]) {
-          if constexpr (!FFE) store_row<OE>(A1->ef_out + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc[i]);
+          if constexpr (!FFE) store_row<OE>(feat<BF16>(A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc[i]);
           if (nn > 1 || FFE) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) s_out[el * OE + j] = acc[i][j];
@@ -954,7 +1081,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) acc[j] = fmaf(We[(DE + k) * OE + j], xs[i][k], acc[j]);
           act_row<OE1>(acc, A1->act_e);
-          store_row<OE>(A1->ef_out + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc);
+          store_row<OE>(feat<BF16>(A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc);
           if (nn > 1) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) s_out[el * OE + j] = acc[j];
@@ -1006,7 +1133,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
       act_row<ON1>(acc, A2->act_n);
 #pragma unroll
       for (int j = 0; j < ON; ++j) v[OE + j] = acc[j];
-      store_row<ON>(A2->nf_out + (r * (size_t)A2->N + n0 + lane) * ON, acc);
+      store_row<ON>(feat<BF16>(A2->nf_out) + (r * (size_t)A2->N + n0 + lane) * ON, acc);
     }
   }
 
@@ -1063,7 +1190,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) rr[k] = (k < tile_cnt && wv + k < WAVES && lane < C) ? 0.f + s_rows[(wv + k) < WAVES ? wv + k : 0][lane < C ? lane : 0] : 0.f;
           const float xs = ((rr[0] + rr[1]) + (rr[2] + rr[3])) + ((rr[4] + rr[5]) + (rr[6] + rr[7]));
-          graph_update_wave<C>(a, xs, tile_g, r, lane, s_mem + wv * WSL, gr);
+          graph_update_wave<C, BF16>(a, xs, tile_g, r, lane, s_mem + wv * WSL, gr);
         }
       } else if constexpr (ONEG) {
         __shared__ float s_blk[WAVES][C1];
@@ -1128,10 +1255,12 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   }
 }
 
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN = false, bool ONEG = false, bool PACK = false, bool FFE = false, bool CHAIN = false>
+// BF16: the six feature tensors are bfloat16 (gnx_block_forward_typed): rows widened on load, outputs rounded on store, fp32 in between
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN = false, bool ONEG = false, bool PACK = false, bool FFE = false, bool CHAIN = false,
+          bool BF16 = false>
 __global__ __launch_bounds__(PACK ? kPackThreads : kThreads) __attribute__((amdgpu_num_sgpr(GNX_WAVE_SGPRS))) void k_block_wave(BlockArgs a, int n_rows) {
   static_assert(!FFE, "the FFE form is k_block_wave_ffe");
-  block_wave_body<DE, DN, DG, OE, ON, EPT, LN, ONEG, PACK, false, CHAIN>(a, n_rows);
+  block_wave_body<DE, DN, DG, OE, ON, EPT, LN, ONEG, PACK, false, CHAIN, BF16>(a, n_rows);
 }
 template <int DE, int DN, int DG, int OE, int ON, int EPT, bool ONEG>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_block_wave_ffe(BlockArgs a, int n_rows) {
@@ -1139,7 +1268,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 }
 
 // Graph update for the wave path: one workgroup per graph (one wavefront when the graph has <= 256 partial rows).
-template <int C, bool ONEG = false>
+template <int C, bool ONEG = false, bool BF16 = false>
 __global__ void k_graph_t(BlockArgs a, int n_rows) {
   extern __shared__ float s_g[];
   constexpr int CP = (C + 3) / 4 * 4;
@@ -1147,8 +1276,8 @@ __global__ void k_graph_t(BlockArgs a, int n_rows) {
   // one graph: k_block_wave stored one row per WORKGROUP (4 wave tiles); several graphs: one row per wave tile
   const int t0 = ONEG ? 0 : a.wtile_off[g], t1 = ONEG ? (a.n_wtiles + 3) / 4 : a.wtile_off[g + 1];
   const float* base = a.partials + blockIdx.y * (size_t)n_rows * CP;
-  if (blockDim.x == 64) graph_update_rows<C, true, 16>(a, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, 64, s_g);
-  else graph_update_rows<C, false, 16>(a, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
+  if (blockDim.x == 64) graph_update_rows<C, true, 16, BF16>(a, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, 64, s_g);
+  else graph_update_rows<C, false, 16, BF16>(a, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
 }
 
 }  // namespace gnx

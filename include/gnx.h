@@ -76,6 +76,8 @@ extern "C" {
 #define GNX_ELEM_I64 2
 #define GNX_ELEM_F32 3
 #define GNX_ELEM_F64 4
+/* bfloat16: FEATURE tensors only (gnx_block_forward_typed); the adjacency constructors reject it like any other unknown kind */
+#define GNX_ELEM_BF16 5
 
 /* forward flags */
 #define GNX_FLAG_FORCE_GENERIC 0x1u /* use the dimension-generic kernels even when a specialised path exists */
@@ -252,6 +254,22 @@ GNX_API size_t gnx_block_workspace_bytes(const gnx_graphs* h, const gnx_block_pa
 GNX_API int32_t gnx_block_forward(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf,
                           const float* gf, int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out,
                           void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
+
+/* The same forward on bfloat16 feature tensors.  `elem` (GNX_ELEM_F32 or GNX_ELEM_BF16) applies to all six tensors; GNX_ELEM_F32 is exactly
+ * gnx_block_forward.  Contract, for finite data: the bf16 result is bit for bit to_bf16(gnx_block_forward(widen(ef), widen(nf), widen(gf)))
+ * under the same flags — inputs are widened exactly, every intermediate (edge->node sums, graph-update partial sums, workspace) stays fp32,
+ * and only the three outputs are rounded, to nearest even.  bf16 buffers must be 4-byte aligned (rows of odd width are then 2-byte aligned:
+ * the kernels never assume more).  Paths: the fused narrow kernel reads and writes bf16 rows itself (ahead of time for README ex.1's widths,
+ * run-time specialised for every other narrow width set); every other path — matrix-core / generic widths, GNX_FLAG_FORCE_GENERIC,
+ * GNX_FLAG_NO_JIT, a failed specialisation — widens the inputs into fp32 staging buffers of the workspace, runs gnx_block_forward on them
+ * and rounds the outputs.  gnx_block_typed_workspace_bytes sizes the workspace for the path these flags take (the staging only when it is
+ * needed; the process-wide default forms are ORed in as everywhere) and compiles / loads a run-time specialisation, so call it outside any
+ * capture; it returns 0 for an unknown `elem` or GNX_FLAG_DEFER_GRAPH_UPDATE with bf16, which gnx_block_forward_typed rejects
+ * (GNX_ERR_INVALID_ARG) before any GPU work.  No allocation, no synchronisation: capture-safe like gnx_block_forward. */
+GNX_API size_t gnx_block_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas, int32_t elem, uint32_t flags);
+GNX_API int32_t gnx_block_forward_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                        int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace, size_t workspace_bytes,
+                                        uint32_t flags, void* stream);
 
 /* Second phase of a deferred block forward: gf'[g] = graphfn([sum_e ef' ; sum_n nf' ; gf_g]) (src/gnblock.jl:67,
  * src/graphfninput.jl:1-13) from the partial sums a gnx_block_forward(..., GNX_FLAG_DEFER_GRAPH_UPDATE, ...) call left
@@ -608,6 +626,8 @@ GNX_API int32_t gnx_dist_block_forward_steps(gnx_dist* d, int32_t n_steps, const
 GNX_API int32_t gnx_jit_precompile(const gnx_block_params* p, int32_t wtile_e_cap, size_t* code_bytes);
 /* the same check for the one-launch FeedForward + residual kernel of a narrow GNCore (widths 1..16), which is specialised at run time for
  * width triples other than README ex.3's (10,5,3) */
+/* gnx_jit_precompile for the kernel of another element type of the feature tensors (GNX_ELEM_F32: gnx_jit_precompile; GNX_ELEM_BF16) */
+GNX_API int32_t gnx_jit_precompile_typed(const gnx_block_params* p, int32_t wtile_e_cap, int32_t elem, size_t* code_bytes);
 GNX_API int32_t gnx_jit_precompile_core_post(int32_t de, int32_t dn, int32_t dg, size_t* code_bytes);
 GNX_API int32_t gnx_jit_stats(int64_t out[4]);
 
