@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — edges updated/sec of the GNBlock forward on a 1M-edge batch (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dims readme|core] [--workload c2|hetero]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dims readme|core] [--workload c2|hetero] [--full]
 
 A "step" is one GNBlock forward (edge + node + graph update) over one resident batch.
+A plain run measures the headline figure and nothing else: it builds the batch, warms up, times the K steps, writes `--dump-outputs`
+and prints the result line.  `--full` adds everything below that is not that figure: the secondary configs, the C program's leg,
+`cpu_baseline`, `roofline` (its per-kernel pass and the live traffic counters), `batch_ms`, the other forms of the same steps
+(`two_launch_form`, `warm_ms_per_step`, `pipelined_two_streams`, `chained_graph_update`, `kernel_us_one_forward`), and at N > 1
+`single_gpu_same_workload`, `without_allgather` and C5w.  Without `--full` those keys are absent or null.
   N = 1 : BASELINE configs[1] — one shared Erdős–Rényi graph, 100k nodes / 1M edges, batch_size 1.  The K timed steps
           are ONE gnx_block_forward_steps call (the library's loop over batches: K forwards in order, step i's graph update at the
           front of step i + 1's launch, the last one flushed inside the call) captured into ONE hipGraph (the step is ~20 µs
@@ -28,7 +33,7 @@ the oracle's C restatement (test infrastructure) on the host cores.
 `--dump-outputs DIR` (one GPU): after the timed region, the outputs of its last step (ef / nf / gf; --model c4: the model's) go to
 DIR/<name>.npy as float32, at most 64 MB in all (a fixed, seeded sample of the rows beyond that).  The inputs are seeded, so two builds
 run with the same arguments can be compared output for output.
-The default N = 1 invocation also carries `"secondary"`: the other BASELINE configs measured by the same script in the same run —
+With `--full`, the default N = 1 invocation also carries `"secondary"`: the other BASELINE configs measured by the same script in the same run —
 core dims on C2, C3 (configs[2]), C5 on one GPU (configs[4]'s batch), C4 (configs[3]) and README ex.3 at its own widths — each with
 ms_per_step, roofline (traffic + provenance), cpu_baseline and, for the hetero batches, the cost of `batch()` itself.  They run as
 child processes BEFORE this process touches the GPU, one at a time (`--no-secondary` skips them).
@@ -285,21 +290,23 @@ def bench_c4(args, gn, torch, dev, c_abi=None):
     for _ in range(max(args.warmup, 1)):
         fwd()
     torch.cuda.synchronize(dev)
-    spin_up(torch, dev, fwd)  # (the per-kernel figures below are steady-state figures too)
-    gn.profile_reset(); gn.profile_enable(True)
-    for _ in range(3):
-        fwd()
-    gn.profile_calibrate(20, torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
-    gn.profile_enable(False)
-    praw = gn.profile_read(); gn.profile_reset()
-    kern = calibrated_kernel_us(praw, per=3)
     K = args.steps
-    t0 = time.perf_counter()
-    for _ in range(K):
-        fwd()
-    torch.cuda.synchronize(dev)
-    dt_eager = (time.perf_counter() - t0) / K
+    kern = dt_eager = None
+    if args.full:  # the per-kernel pass and the eager figure
+        spin_up(torch, dev, fwd)  # (the per-kernel figures below are steady-state figures too)
+        gn.profile_reset(); gn.profile_enable(True)
+        for _ in range(3):
+            fwd()
+        gn.profile_calibrate(20, torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize(dev)
+        gn.profile_enable(False)
+        praw = gn.profile_read(); gn.profile_reset()
+        kern = calibrated_kernel_us(praw, per=3)
+        t0 = time.perf_counter()
+        for _ in range(K):
+            fwd()
+        torch.cuda.synchronize(dev)
+        dt_eager = (time.perf_counter() - t0) / K
     # the timed region: ONE forward captured into a hipGraph, replayed K times (at narrow widths an eager forward is ten ~20-us launches
     # and costs the host about as much as the GPU: the eager figure then measures the Python mirror, not the kernels); median of 3 regions
     def model_fn(t):
@@ -365,7 +372,7 @@ def bench_c4(args, gn, torch, dev, c_abi=None):
             "config": {"workload": "C4: Encoder -> 2 x GNCore(%s) -> Decoder on the C2 graph (100k nodes / 1M edges); one step = the whole model forward" % ",".join(map(str, core)),
                        "launch": "one forward captured into a hipGraph, replayed %d times" % K,
                        "timing": "median of 3 regions (%s ms/step)" % [round(r * 1e3, 4) for r in reps],
-                       "eager_ms_per_step": round(dt_eager * 1e3, 4),
+                       "eager_ms_per_step": None if dt_eager is None else round(dt_eager * 1e3, 4),
                        # (for tools/summarize_prof.py --model-traffic: bytes of a profiled run / forwards = bytes per forward)
                        "forwards_executed": n_fw[0]}}
     if max(core) < 32:  # narrow widths run on the vector units, not the matrix cores: the model is priced against HBM like a narrow block
@@ -380,7 +387,7 @@ def bench_c4(args, gn, torch, dev, c_abi=None):
         line["c_abi"] = ({"vs_torch_captured": round(c_abi["model_us_per_step"] * 1e-3 / (dt * 1e3), 4), "what": c_abi.get("model_what"), "reps_us": c_abi.get("model_reps_us"),
                           "event_us_per_step": c_abi.get("model_event_us_per_step"), "batch_ms": c_abi.get("batch_ms"), "program": "tests/c/abi_bench.c --mode c4"}
                          if "model_us_per_step" in c_abi else c_abi)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = c4_cpu_baseline(ps)
     line.update({"n_gpus": 1, "warmup": args.warmup, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic"})
     emit(line, args, "c4" if core == (128, 64, 32) else "c4_" + "-".join(map(str, core)))
@@ -391,7 +398,7 @@ def measure_dist_gnx(args, gn, torch, n, din, dout, Gtot, Etot, seed, K, W):
     device 0 first (single_gpu_same_workload); then the K-step region with and without the grouped all-gather, median of three each."""
     from graphnets_jl_amd.dist import DistBlockRunner, partition_graphs
     single = None
-    if not args.no_single_gpu_leg:
+    if args.full and not args.no_single_gpu_leg:
         torch.cuda.set_device(0)
         single = single_gpu_same_workload(gn, torch, torch.device("cuda", 0), seed, Gtot, Etot, din, dout, K, W, args.flags)
     n_all, e_all = hetero_spec(seed, Gtot, Etot)
@@ -423,14 +430,17 @@ def measure_dist_gnx(args, gn, torch, n, din, dout, Gtot, Etot, seed, K, W):
     while (time.perf_counter() - t_w) * 1e3 < CLOCK_WARMUP_MS:  # the same untimed load as spin_up
         region(); run.synchronize()
     reps = timed(0)
-    reps_wo = timed(gn._lib.FLAG_DIST_NO_GATHER)
-    # the eager form of the same entry point (no per-device hipGraph): what the replay form saves
-    t0 = time.perf_counter()
-    region(gn._lib.FLAG_NO_GRAPH)
-    run.synchronize()
-    dt_eager = time.perf_counter() - t0
-    res = {"E_job": run.edges, "G_job": Gtot, "seed": seed, "M": M, "nsets": nsets, "dt": reps[1], "dt_without": reps_wo[1], "reps": reps, "reps_without": reps_wo,
-           "per_rank": [[g.n_edges, g.n_nodes, g.n_graphs] for g in run.handles], "single": single, "eager_ms_per_step": round(dt_eager / K * 1e3, 6)}
+    reps_wo = dt_eager = None
+    if args.full:
+        reps_wo = timed(gn._lib.FLAG_DIST_NO_GATHER)
+        # the eager form of the same entry point (no per-device hipGraph): what the replay form saves
+        t0 = time.perf_counter()
+        region(gn._lib.FLAG_NO_GRAPH)
+        run.synchronize()
+        dt_eager = time.perf_counter() - t0
+    res = {"E_job": run.edges, "G_job": Gtot, "seed": seed, "M": M, "nsets": nsets, "dt": reps[1], "dt_without": None if reps_wo is None else reps_wo[1], "reps": reps, "reps_without": reps_wo,
+           "per_rank": [[g.n_edges, g.n_nodes, g.n_graphs] for g in run.handles], "single": single,
+           "eager_ms_per_step": None if dt_eager is None else round(dt_eager / K * 1e3, 6)}
     run.close()
     del run
     torch.cuda.empty_cache()
@@ -470,7 +480,7 @@ def bench_dist_gnx(args):
                          "counts": "algorithmic bytes of every device's shard / whole-step time / (n_gpus x 8 TB/s)", "algorithmic_bytes": abytes}}
     if "speedup_vs_single_gpu_same_workload" in e:
         line["speedup_vs_single_gpu_same_workload"] = e["speedup_vs_single_gpu_same_workload"]
-    if strong and (Gtot, Etot) == (4096, 1_000_000) and not args.no_secondary:
+    if args.full and strong and (Gtot, Etot) == (4096, 1_000_000) and not args.no_secondary:
         c5w = measure_dist_gnx(args, gn, torch, n, din, dout, 4096, 8_000_000, 5, K, W)
         ew = sharded_entry(c5w, K, n)
         ew["what"] = "C5w (SURVEY 8e): the same 4096 graphs at configs[2]'s density — 8M edges — sharded over the same devices"
@@ -658,7 +668,7 @@ def collect_secondary(args):
     for key, extra, what, *env_extra in SECONDARY:
         steps = {"c4": max(3, min(args.steps, 5)), "c4_fp32_mfma": max(3, min(args.steps, 5)), "core_c2": max(5, min(args.steps, 10))}.get(key, max(10, min(args.steps, 20)))
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(max(2, min(args.warmup, 5))),
-               "--no-secondary", "--full-line", "--cpu-budget", "3.0"] + extra
+               "--full", "--no-secondary", "--full-line", "--cpu-budget", "3.0"] + extra
         t0 = time.perf_counter()
         line = err = None
         for attempt in (0, 1):  # (a child that dies within seconds — a communicator's start-up now and then does — is started once more; a slow failure is not)
@@ -781,7 +791,7 @@ def live_traffic(kernel, bench_args, timeout_s=75.0):
     for counter in ("FETCH_SIZE", "WRITE_SIZE", None):  # (None: a third pass with the kernel trace alone — the profiler's own average duration of the kernel)
         out = tempfile.mkdtemp(prefix="gnx_pmc_", dir="/tmp")
         cmd = [exe] + (["--pmc", counter] if counter else []) + ["--kernel-trace", "--output-format", "csv", "-d", out, "--", py, os.path.join(ROOT, "bench.py")] + \
-              list(bench_args) + ["--no-secondary", "--no-cpu-baseline", "--no-c-abi", "--full-line", "--no-live-traffic"]
+              list(bench_args) + ["--full", "--no-secondary", "--no-cpu-baseline", "--no-c-abi", "--full-line", "--no-live-traffic"]
         try:
             pr = subprocess.Popen(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
@@ -980,7 +990,7 @@ def measure_sharded(gn, torch, dist, dev, rank, world, args, din, dout, Gtot, Et
     from graphnets_jl_amd.dist import GfGather, partition_graphs
     (de, dn, dg), (oe, on, og) = din, dout
     single = None
-    if rank == 0 and not args.no_single_gpu_leg:
+    if rank == 0 and args.full and not args.no_single_gpu_leg:
         single = single_gpu_same_workload(gn, torch, dev, seed, Gtot, Etot, din, dout, K, W, args.flags)
     n_all, e_all = hetero_spec(seed, Gtot, Etot)
     shards = partition_graphs(e_all, world)
@@ -1057,11 +1067,14 @@ def measure_sharded(gn, torch, dist, dev, rank, world, args, din, dout, Gtot, Et
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             if float(t.item()) * 1e3 >= CLOCK_WARMUP_MS:
                 return
-    settle(run_without)
-    reps_wo = sorted(timed(run_without) for _ in range(3))
+    reps_wo = dt_wo = None
+    if args.full:
+        settle(run_without)
+        reps_wo = sorted(timed(run_without) for _ in range(3))
+        dt_wo = reps_wo[1]
     settle(run_with)
     reps = sorted(timed(run_with) for _ in range(3))
-    dt, dt_wo = reps[1], reps_wo[1]
+    dt = reps[1]
     gf_all = gather.finish() if gather._ready is not None else gather.result()
     assert tuple(gf_all.reshape(M, -1, og).shape) == (M, gather.G, og) and torch.equal(gf_all.reshape(-1, og), gf_result)
     # every rank's rows of the gathered table are the rows it computed (original graph order restored)
@@ -1085,12 +1098,14 @@ def measure_sharded(gn, torch, dist, dev, rank, world, args, din, dout, Gtot, Et
 
 def sharded_entry(res, K, world):
     """The fields of one sharded measurement as they appear in the line (headline of an N > 1 run, and `secondary.c5w`)."""
-    dt, dtw, E = res["dt"] / K, res["dt_without"] / K, res["E_job"]
+    dt, E = res["dt"] / K, res["E_job"]
     out = {"value": round(E / dt, 1), "unit": "edges/s", "ms_per_step": round(dt * 1e3, 6), "edges_whole_job": E, "graphs_whole_job": res["G_job"],
            "with_allgather": {"ms_per_step": round(dt * 1e3, 6), "value": round(E / dt, 1), "reps_us_per_step": [round(r / K * 1e6, 2) for r in res["reps"]]},
-           "without_allgather": {"ms_per_step": round(dtw * 1e3, 6), "value": round(E / dtw, 1), "reps_us_per_step": [round(r / K * 1e6, 2) for r in res["reps_without"]],
-                                 "what": "the same hipGraph replays without the RCCL all-gather of gf' (every rank keeps only its own graphs' rows)"},
-           "per_rank_edges_nodes_graphs": res["per_rank"], "single_gpu_same_workload": res["single"]}
+           "without_allgather": None, "per_rank_edges_nodes_graphs": res["per_rank"], "single_gpu_same_workload": res["single"]}
+    if res["dt_without"] is not None:  # (--full)
+        dtw = res["dt_without"] / K
+        out["without_allgather"] = {"ms_per_step": round(dtw * 1e3, 6), "value": round(E / dtw, 1), "reps_us_per_step": [round(r / K * 1e6, 2) for r in res["reps_without"]],
+                                    "what": "the same hipGraph replays without the RCCL all-gather of gf' (every rank keeps only its own graphs' rows)"}
     if res["single"]:
         out["speedup_vs_single_gpu_same_workload"] = round(res["single"]["ms_per_step"] / (dt * 1e3), 4)
     return out
@@ -1136,9 +1151,9 @@ def bench_sharded(args, gn, torch, dist, dev, rank, world, din, dout):
     and the region with and without the all-gather."""
     K, W = args.steps, args.warmup
     Gtot, Etot, seed = sharded_workload(args, world)
-    res = measure_sharded(gn, torch, dist, dev, rank, world, args, din, dout, Gtot, Etot, seed, K, W)
+    res = measure_sharded(gn, torch, dist, dev, rank, world, args, din, dout, Gtot, Etot, seed, K, W, want_roofline=args.full)
     c5w = None
-    strong_default = args.scaling == "strong" and (Gtot, Etot) == (4096, 1_000_000) and not args.no_secondary
+    strong_default = args.full and args.scaling == "strong" and (Gtot, Etot) == (4096, 1_000_000) and not args.no_secondary
     if strong_default:
         torch.cuda.empty_cache()
         c5w = measure_sharded(gn, torch, dist, dev, rank, world, args, din, dout, 4096, 8_000_000, 5, K, W)
@@ -1149,6 +1164,79 @@ def bench_sharded(args, gn, torch, dist, dev, rank, world, din, dout):
     if rank == 0:
         time.sleep(0.5)  # the other ranks' (already flushed) output reaches the launcher's pipe first
         emit(line, args, f"sharded_n{world}")
+
+
+def batch_construction(gn, torch, dev, colptrs, rowvals, nn, workload):
+    """`--full`: GNGraphBatch construction timed in every input form (`batch_ms`).  Returns (the batch of the timed steps, batch_ms, the
+    packed colptr / rowval arrays)."""
+    # once per process, not per batch: library load, context, and the device builder's own first use (its kernels' code objects, its stream and
+    # scratch buffer) on a graph large enough to take that path; reported as batch_ms.one_time_init
+    t0 = time.perf_counter()
+    gn.GNGraphBatch.from_csc(*make_c2(seed=1, N=8_000, E=80_000), device=dev)
+    torch.cuda.synchronize(dev)
+    init_ms = (time.perf_counter() - t0) * 1e3
+    tb = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        g = gn.GNGraphBatch.from_csc(colptrs, rowvals, nn, device=dev)
+        torch.cuda.synchronize(dev)
+        tb.append((time.perf_counter() - t0) * 1e3)
+    # the packed input form (the graphs' colptr / rowval arrays one after the other, as a data loader holds them): no per-graph Python work
+    cpc, rvc = np.concatenate(colptrs), np.concatenate(rowvals)
+    tp = []
+    for _ in range(4):
+        t0 = time.perf_counter()
+        gp = gn.GNGraphBatch.from_csc_packed(cpc, rvc, nn, device=dev)
+        torch.cuda.synchronize(dev)
+        tp.append((time.perf_counter() - t0) * 1e3)
+        del gp
+    cp32, rv32 = cpc.astype(np.int32), rvc.astype(np.int32)
+    t32 = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        gp = gn.GNGraphBatch.from_csc_packed(cp32, rv32, nn, device=dev)
+        torch.cuda.synchronize(dev)
+        t32.append((time.perf_counter() - t0) * 1e3)
+        del gp
+    batch_ms = {"from_csc": round(min(tb), 3), "from_csc_first_call": round(tb[0], 3),
+                "from_csc_packed": round(min(tp), 3), "from_csc_packed_first_call": round(tp[0], 3), "from_csc_packed_int32": round(min(t32), 3),
+                "one_time_init": round(init_ms, 3),
+                "what": "GNGraphBatch construction from Python, end to end: best of the calls, and the first call of this batch (one_time_init = the first build of the PROCESS, on an 80k-edge graph: library load, context, the builder's code objects and scratch).  from_csc = a LIST of per-graph arrays (numpy "
+                        "concatenates them: ~2.4 ms for 4096 graphs); from_csc_packed = the concatenated arrays as they are (int64; _int32: int32 indices).  "
+                        "from_dense_uint8 = the reference's own input form, a LIST of dense 0/1 matrices (per-matrix Python work: ~1.5 us each); from_dense_packed = the same matrices as ONE uint8 buffer "
+                        "(pageable numpy memory through the library's pinned staging pair; _pinned: one DMA — dense_bytes over PCIe bound it; _device: a device tensor, read where it is).  "
+                        "Validation, device-format arrays and both tile tables are built by kernels (csrc/gnx_build_csc.hip); the matrix-core path's tables by its workspace query"}
+    E, N = g.n_edges, g.n_nodes
+    if workload == "hetero" and sum(int(n) * int(n) for n in nn) <= 2e8:  # the reference's own input form: dense 0/1 matrices
+        adjs = []
+        for cp, rv, n in zip(colptrs, rowvals, nn):
+            a = np.zeros((n, n), dtype=np.uint8)
+            a[rv, np.repeat(np.arange(n), np.diff(cp))] = 1  # A[i, j] = 1 <=> edge i -> j (src = row, dst = column)
+            adjs.append(a)
+        td = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            gd = gn.GNGraphBatch(adjs, device=dev)
+            torch.cuda.synchronize(dev)
+            td.append((time.perf_counter() - t0) * 1e3)
+        batch_ms["from_dense_uint8"] = round(min(td), 3)
+        batch_ms["from_dense_uint8_first_call"] = round(td[0], 3)  # (includes the one-off allocation of the 64 MB pinned staging buffers)
+        assert gd.n_edges == E and gd.n_nodes == N
+        # the same matrices as ONE buffer (from_dense_packed): pageable numpy memory, a pinned tensor (one DMA), a device tensor (no copy)
+        cat = np.concatenate([a.reshape(-1) for a in adjs])
+        for form, buf in (("from_dense_packed", cat), ("from_dense_packed_pinned", torch.from_numpy(cat).pin_memory()), ("from_dense_packed_device", torch.from_numpy(cat).to(dev))):
+            tpk = []
+            for _ in range(4):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                gd = gn.GNGraphBatch.from_dense_packed(buf, nn, device=dev)
+                torch.cuda.synchronize(dev)
+                tpk.append((time.perf_counter() - t0) * 1e3)
+            batch_ms[form] = round(min(tpk), 3)
+            assert gd.n_edges == E and gd.n_nodes == N
+        batch_ms["dense_bytes"] = int(cat.nbytes)
+        del gd, adjs, cat, buf
+    return g, batch_ms, cpc, rvc
 
 
 def main():
@@ -1168,6 +1256,10 @@ def main():
     ap.add_argument("--no-prepare", action="store_true", help="--model c4: leave the layers' parameters unprepared (every forward then runs the *_prep launches, as before round 5)")
     ap.add_argument("--no-single-gpu-leg", action="store_true", help="N > 1: skip rank 0's run of the whole batch on one GPU (single_gpu_same_workload)")
     ap.add_argument("--c2-scale", type=float, default=1.0, help="scale C2's nodes and edges by this factor (size sweeps; 1 = BASELINE configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure (secondary configs, C program, CPU baseline, roofline and per-kernel "
+                         "passes, batch construction, the other forms of the same steps, N > 1: the single-GPU leg, the region without the "
+                         "all-gather and C5w); a plain run only times the K steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configs of the default N = 1 line")
     ap.add_argument("--no-c-abi", action="store_true", help="skip the torch-free C program's leg (c_abi_ms_per_step)")
@@ -1208,10 +1300,11 @@ def main():
     # the default single-GPU line carries the other configs: child processes, one at a time, BEFORE this process touches the GPU
     headline = (args.gpus == 1 and "RANK" not in os.environ and args.dims == "readme" and args.workload in (None, "c2") and args.model == "block"
                 and not args.force_dist and args.c2_scale == 1.0 and args.flags == 0 and not args.overlap)
-    secondary = collect_secondary(args) if headline and not args.no_secondary else None
+    secondary = collect_secondary(args) if headline and args.full and not args.no_secondary else None
     # the same workload through the C boundary WITHOUT Python / torch (tests/c/abi_bench.c), as a child process before this one touches the GPU
     c_abi = None
-    if args.gpus == 1 and "RANK" not in os.environ and not args.no_c_abi and not args.force_dist and args.c2_scale == 1.0 and args.flags == 0 and not args.overlap:
+    if (args.full and args.gpus == 1 and "RANK" not in os.environ and not args.no_c_abi and not args.force_dist and args.c2_scale == 1.0
+            and args.flags == 0 and not args.overlap):
         if args.model == "c4":
             c_abi = c_abi_bench("c4", max(3, min(args.steps, 10)), 2, ["--core-dims", args.core_dims])
         elif args.dims == "readme" and args.workload in (None, "c2"):
@@ -1266,77 +1359,15 @@ def main():
         wl_name = (f"ONE heterogeneous batch of {Gtot} random graphs (32-256 nodes, {Etot / 1e6:g}M edges, seed {seed}) on one GPU "
                    f"(BASELINE configs[{2 if Gtot == 512 else 4}] law)")
     torch.cuda.synchronize(dev)
-    # once per process, not per batch: library load, context, and the device builder's own first use (its kernels' code objects, its stream and
-    # scratch buffer) on a graph large enough to take that path; reported as batch_ms.one_time_init
-    t0 = time.perf_counter()
-    gn.GNGraphBatch.from_csc(*make_c2(seed=1, N=8_000, E=80_000), device=dev)
-    torch.cuda.synchronize(dev)
-    init_ms = (time.perf_counter() - t0) * 1e3
-    tb = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        g = gn.GNGraphBatch.from_csc(colptrs, rowvals, nn, device=dev)
-        torch.cuda.synchronize(dev)
-        tb.append((time.perf_counter() - t0) * 1e3)
-    # the packed input form (the graphs' colptr / rowval arrays one after the other, as a data loader holds them): no per-graph Python work
-    cpc, rvc = np.concatenate(colptrs), np.concatenate(rowvals)
-    tp = []
-    for _ in range(4):
-        t0 = time.perf_counter()
-        gp = gn.GNGraphBatch.from_csc_packed(cpc, rvc, nn, device=dev)
-        torch.cuda.synchronize(dev)
-        tp.append((time.perf_counter() - t0) * 1e3)
-        del gp
-    cp32, rv32 = cpc.astype(np.int32), rvc.astype(np.int32)
-    t32 = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        gp = gn.GNGraphBatch.from_csc_packed(cp32, rv32, nn, device=dev)
-        torch.cuda.synchronize(dev)
-        t32.append((time.perf_counter() - t0) * 1e3)
-        del gp
-    batch_ms = {"from_csc": round(min(tb), 3), "from_csc_first_call": round(tb[0], 3),
-                "from_csc_packed": round(min(tp), 3), "from_csc_packed_first_call": round(tp[0], 3), "from_csc_packed_int32": round(min(t32), 3),
-                "one_time_init": round(init_ms, 3),
-                "what": "GNGraphBatch construction from Python, end to end: best of the calls, and the first call of this batch (one_time_init = the first build of the PROCESS, on an 80k-edge graph: library load, context, the builder's code objects and scratch).  from_csc = a LIST of per-graph arrays (numpy "
-                        "concatenates them: ~2.4 ms for 4096 graphs); from_csc_packed = the concatenated arrays as they are (int64; _int32: int32 indices).  "
-                        "from_dense_uint8 = the reference's own input form, a LIST of dense 0/1 matrices (per-matrix Python work: ~1.5 us each); from_dense_packed = the same matrices as ONE uint8 buffer "
-                        "(pageable numpy memory through the library's pinned staging pair; _pinned: one DMA — dense_bytes over PCIe bound it; _device: a device tensor, read where it is).  "
-                        "Validation, device-format arrays and both tile tables are built by kernels (csrc/gnx_build_csc.hip); the matrix-core path's tables by its workspace query"}
+    if args.full:
+        g, batch_ms, cpc, rvc = batch_construction(gn, torch, dev, colptrs, rowvals, nn, workload)
+    else:
+        g, batch_ms = gn.GNGraphBatch.from_csc(colptrs, rowvals, nn, device=dev), None
     E, N, G = g.n_edges, g.n_nodes, g.n_graphs
-    if workload == "hetero" and sum(int(n) * int(n) for n in nn) <= 2e8:  # the reference's own input form: dense 0/1 matrices
-        adjs = []
-        for cp, rv, n in zip(colptrs, rowvals, nn):
-            a = np.zeros((n, n), dtype=np.uint8)
-            a[rv, np.repeat(np.arange(n), np.diff(cp))] = 1  # A[i, j] = 1 <=> edge i -> j (src = row, dst = column)
-            adjs.append(a)
-        td = []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            gd = gn.GNGraphBatch(adjs, device=dev)
-            torch.cuda.synchronize(dev)
-            td.append((time.perf_counter() - t0) * 1e3)
-        batch_ms["from_dense_uint8"] = round(min(td), 3)
-        batch_ms["from_dense_uint8_first_call"] = round(td[0], 3)  # (includes the one-off allocation of the 64 MB pinned staging buffers)
-        assert gd.n_edges == E and gd.n_nodes == N
-        # the same matrices as ONE buffer (from_dense_packed): pageable numpy memory, a pinned tensor (one DMA), a device tensor (no copy)
-        cat = np.concatenate([a.reshape(-1) for a in adjs])
-        for form, buf in (("from_dense_packed", cat), ("from_dense_packed_pinned", torch.from_numpy(cat).pin_memory()), ("from_dense_packed_device", torch.from_numpy(cat).to(dev))):
-            tpk = []
-            for _ in range(4):
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                gd = gn.GNGraphBatch.from_dense_packed(buf, nn, device=dev)
-                torch.cuda.synchronize(dev)
-                tpk.append((time.perf_counter() - t0) * 1e3)
-            batch_ms[form] = round(min(tpk), 3)
-            assert gd.n_edges == E and gd.n_nodes == N
-        batch_ms["dense_bytes"] = int(cat.nbytes)
-        del gd, adjs, cat, buf
     blk = bench_weights(gn, din, dout, dev)
     (de, dn, dg), (oe, on, og) = din, dout
     plan = gn.BlockPlan(blk, g, R=1, flags=args.flags)
-    if max(din + dout) >= 32:
+    if args.full and max(din + dout) >= 32:
         # widths that take the matrix-core path: the first workspace query on a NEW handle also builds that path's tables (128-row tiles, the
         # destination of every edge, the aggregation chunks: kernels over the handle's device arrays) — what a loop that rebuilds its batch pays per batch
         tw = []
@@ -1397,7 +1428,7 @@ def main():
     # The headline form (round 6): the K steps as ONE gnx_block_forward_steps call — the library's own loop over batches: K forwards in order,
     # bit-identical outputs (tests/test_gpu_block.py), and because it knows the next step exists, step i's graph update rides at the front of
     # step i + 1's launch (one launch per step + one flush INSIDE the call, i.e. inside the timed region).  K separate gnx_block_forward calls
-    # (two launches per step) are timed beside it: `two_launch_form`.
+    # (two launches per step) are timed beside it with --full: `two_launch_form`.
     steps_form = not args.overlap and not args.separate_calls
 
     def capture_steps(nsteps, rotate):
@@ -1413,7 +1444,7 @@ def main():
     dt = reps[1]
     if args.dump_outputs is not None:  # the timed region's last step wrote the outputs of buffer set (K - 1) mod nsets
         dump_outputs(args.dump_outputs, dict(zip(("ef", "nf", "gf"), sets[(K - 1) % nsets]["out"])))
-    if steps_form:
+    if args.full and steps_form:
         sep = capture(K, True)
         sep.replay(); torch.cuda.synchronize(dev)
         spin_up(torch, dev, sep.replay, 50.0)
@@ -1422,10 +1453,11 @@ def main():
                       "reps_us_per_step": [round(r / K * 1e6, 2) for r in reps_sep],
                       "what": f"the same {K} steps as {K} separate gnx_block_forward calls in one hipGraph (two launches per step: block kernel + graph update); rounds 1-5's headline form"}
         del sep
-    warm = capture_steps(K, False) if steps_form else capture(K, False)
-    warm.replay(); torch.cuda.synchronize(dev)
-    spin_up(torch, dev, warm.replay, 50.0)
-    extra["warm_ms_per_step"] = round(sorted(timed(warm.replay) for _ in range(3))[1] / K * 1e3, 6)
+    if args.full:
+        warm = capture_steps(K, False) if steps_form else capture(K, False)
+        warm.replay(); torch.cuda.synchronize(dev)
+        spin_up(torch, dev, warm.replay, 50.0)
+        extra["warm_ms_per_step"] = round(sorted(timed(warm.replay) for _ in range(3))[1] / K * 1e3, 6)
     extra["launch"] = ((f"gnx_block_forward_steps: {K} steps in one call, one launch per step (step i's graph update at the front of step i+1's launch) + one flush, captured in one hipGraph; "
                         if steps_form else f"hipGraph of {K} gnx_block_forward calls; ") + f"{nsets} rotating buffer sets (cache-cold); " +
                        ("single stream" if not args.overlap else "graph update of step i on a 2nd stream, overlapping step i+1 (joined inside the timed region)"))
@@ -1433,7 +1465,7 @@ def main():
     # (different buffer sets), so a serving loop would pipeline them: step i's graph-update launch (~4 us of latency on 83 KB) runs under
     # step i+1's block kernel, and one kernel's ramp / drain under its neighbour.  Same results bit for bit (tools/experiments/
     # two_stream_pipeline.py); `value` above stays the single-stream figure, where every step waits for the one before it.
-    if K >= 4 and not args.overlap:
+    if args.full and K >= 4 and not args.overlap:
         Kp = max(K, 80)  # (two short graphs would measure their own replay overhead: at least 40 steps per stream)
 
         def capture_half(par):
@@ -1458,7 +1490,7 @@ def main():
     # NOT the headline either: the chained form (gnx_block_forward_chained) — step i's launch carries step i - 1's graph update in
     # workgroups at its front, so a loop over batches is ONE launch per step (opt-in: gf' of a step is complete one call later or after
     # the flush).  Bit-identical outputs (tests/test_gpu_block.py::test_chained_forward...).
-    if not args.overlap and og > 0 and not steps_form:
+    if args.full and not args.overlap and og > 0 and not steps_form:
         def capture_chained():
             cgc = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cgc, capture_error_mode="thread_local"):
@@ -1481,9 +1513,9 @@ def main():
     E_job = E
     value = E_job / (dt / K)
 
-    # ---- roofline: the same K steps again with per-kernel dispatch timestamps (block_roofline) ----
+    # ---- --full: roofline, the same K steps again with per-kernel dispatch timestamps (block_roofline) ----
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         dims_key = args.dims.replace(":", "_").replace(",", "-") + ("" if workload == "c2" else f"_hetero{G}")
         if workload != "c2" and args.hetero_edges != 1_000_000:
             dims_key += f"_{args.hetero_edges}"  # the committed PMC profiles are of the 1M-edge batches: no traffic figure for another size
@@ -1508,9 +1540,9 @@ def main():
             else:
                 roof["traffic_live"] = lrec  # (why not; `traffic` is then the committed profile's, as before)
 
-    # ---- CPU baseline: the oracle's C restatement ("port") on the host cores, rank 0, N = 1 only ----
+    # ---- --full: CPU baseline, the oracle's C restatement ("port") on the host cores, rank 0, N = 1 only ----
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import c_port
         p = dict(in_dims=din, out_dims=dout, We=blk.edgefn.weight.cpu().numpy(), be=np.zeros(oe, np.float32),
                  Wn=blk.nodefn.weight.cpu().numpy(), bn=np.zeros(on, np.float32), Wg=blk.graphfn.weight.cpu().numpy(),

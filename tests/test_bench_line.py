@@ -132,3 +132,49 @@ def test_live_traffic_falls_back_without_a_gpu_and_the_compact_line_says_where_t
     assert c["roofline"]["traffic"] == 79676633.1 and c["roofline"]["traffic_measured"].startswith("this run")
     line["roofline"]["traffic_source"] = {"file": "profiles/traffic_readme.json", "commit": None}
     assert bench.compact_line(line)["roofline"]["traffic_measured"].startswith("profiles/")
+
+
+class _TouchedTheGpu(Exception):
+    pass
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_a_plain_run_starts_no_other_measurement_before_its_steps(full, monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` measures the headline alone: the secondary configs and the C program's leg (child processes that
+    run before this process touches the GPU) only come with --full.  Stopped where the process would first touch the GPU."""
+    import sys
+    import torch
+    calls = []
+    monkeypatch.setattr(bench, "collect_secondary", lambda args: calls.append("secondary") or {})
+    monkeypatch.setattr(bench, "c_abi_bench", lambda *a, **k: calls.append("c_abi") or {})
+    monkeypatch.setattr(bench.subprocess, "run", lambda *a, **k: calls.append("child"))
+    monkeypatch.setattr(bench.subprocess, "call", lambda *a, **k: calls.append("child"))
+
+    def touch(*a, **k):
+        raise _TouchedTheGpu
+    monkeypatch.setattr(torch.cuda, "set_device", touch)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"] + (["--full"] if full else []))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    with pytest.raises(_TouchedTheGpu):
+        bench.main()
+    assert calls == (["secondary", "c_abi"] if full else [])
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_alone():
+    """The plain run's result line: the headline figure of the K timed steps (C2, README dims) and nothing that takes a run of its own —
+    no secondary line, no roofline, no CPU baseline, no other form of the steps."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert not any(l.startswith("bench-secondary") for l in lines)
+    c = json.loads(lines[-1])
+    assert c["metric"] == "edges updated/sec, GNBlock fwd, 1M-edge batch" and c["unit"] == "edges/s" and c["higher_is_better"] is True
+    assert c["dtype"] == "f32" and c["steps"] == 20 and c["warmup"] == 5 and c["n_gpus"] == 1
+    assert c["ms_per_step"] > 0 and abs(c["value"] - 1_000_000 / (c["ms_per_step"] * 1e-3)) <= 1e-3 * c["value"]
+    assert c["roofline"] is None and c["cpu_baseline"] is None
+    assert not set(c) & {"two_launch_ms", "chained_ms", "pipelined_two_streams_ms", "c_abi_ms_per_step"}

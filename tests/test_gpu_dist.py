@@ -142,12 +142,12 @@ def _check_strong_line(line, backend):
 def test_bench_sharded_prints_the_compact_line_last(backend):
     """What the driver's 8-GPU SCALE run will parse: `bench.py --gpus 1 --force-dist` (the N > 1 branch: configs[4]'s fixed 4096-graph batch sharded
     by the product's partitioner, hipGraphs of stacked steps, RCCL all-gather on a side stream, one rank) and `--dist-backend gnx` (one process
-    driving the devices through gnx_dist_block_forward_steps; its without_allgather leg is GNX_FLAG_DIST_NO_GATHER), started as the driver starts
-    them (no --full-line).  The LAST stdout line is the compact headline — the contract's keys, roofline, the with / without-gather pair, the same
+    driving the devices through gnx_dist_block_forward_steps; its without_allgather leg is GNX_FLAG_DIST_NO_GATHER), with --full and without
+    --full-line.  The LAST stdout line is the compact headline — the contract's keys, roofline, the with / without-gather pair, the same
     batch on one GPU and C5w as numbers, below 3 KB; the secondary line is prefixed; the whole line is in gpurun_out/bench_detail_*.json and names
     configs[4]'s workload, the same batch on one GPU, the region with and without the collective, and C5w beside it."""
     from tests.test_bench_line import check_compact
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "2", "--full"]
     cmd += ["--force-dist", "--no-cpu-baseline"] if backend == "torch" else ["--dist-backend", "gnx"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1100)
     assert out.returncode == 0, out.stderr[-2000:]

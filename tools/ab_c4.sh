@@ -4,7 +4,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 for spec in "$@"; do
   set -- $spec; name=$1; shift
   for rep in 1 2; do
-    env "$@" python3 $REPO/bench.py --model c4 --steps 10 --warmup 3 2>/dev/null | tail -1 | python3 -c "
+    env "$@" python3 $REPO/bench.py --full --model c4 --steps 10 --warmup 3 2>/dev/null | tail -1 | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 k=d['kernel_us_one_forward']

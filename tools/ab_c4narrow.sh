@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/ab_c4narrow; mkdir -p $OUT; : > $OUT/summary.txt
 variants=("X=1" "$@")
 for rep in 1 2; do
   for v in "${variants[@]}"; do
-    line=$(env $v python3 $REPO/bench.py --model c4 --core-dims 10,5,3 --steps 50 --no-cpu-baseline 2> $OUT/err.log | tail -1)
+    line=$(env $v python3 $REPO/bench.py --full --model c4 --core-dims 10,5,3 --steps 50 --no-cpu-baseline 2> $OUT/err.log | tail -1)
     echo "$v rep$rep $(echo "$line" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('us/step', round(d['ms_per_step']*1e3,1), d.get('kernel_us_one_forward'))" 2>&1)" | tee -a $OUT/summary.txt
   done
 done

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for i in 1 2 3; do
   for v in 0 1; do
     if [ $v = 1 ]; then export GNX_NO_FFE=1; else unset GNX_NO_FFE; fi
-    python bench.py --model c4 --core-dims 10,5,3 --steps 50 --warmup 5 --no-cpu-baseline --no-c-abi 2>/dev/null | python -c "
+    python bench.py --full --model c4 --core-dims 10,5,3 --steps 50 --warmup 5 --no-cpu-baseline --no-c-abi 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('NO_FFE=$v', 'ms/step', d['ms_per_step'], 'kernels', d['kernel_us_one_forward'])"

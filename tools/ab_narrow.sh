@@ -8,7 +8,7 @@ run() {  # name, env..., -- args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
   for rep in 1 2; do
-    line=$(env "${envs[@]}" python3 $REPO/bench.py --no-cpu-baseline --steps 200 "$@" 2>/dev/null | tail -1)
+    line=$(env "${envs[@]}" python3 $REPO/bench.py --full --no-cpu-baseline --steps 200 "$@" 2>/dev/null | tail -1)
     echo "$name rep$rep $(echo "$line" | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"]; print("us/step", round(d["ms_per_step"]*1e3,2), "warm", round(d["config"].get("warm_ms_per_step",0)*1e3,2), "kernels", r["all_kernels_us"], "frac", r["frac"], "whole", r["frac_whole_step"])' 2>&1)" | tee -a $LOG
   done
 }

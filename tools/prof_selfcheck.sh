@@ -8,5 +8,5 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/selfcheck_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d "$OUT/kt" -- python3 $REPO/bench.py --no-cpu-baseline --no-secondary --no-c-abi "$@" > "$OUT/kt.log" 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$OUT/kt" -- python3 $REPO/bench.py --full --no-cpu-baseline --no-secondary --no-c-abi "$@" > "$OUT/kt.log" 2>&1
 python3 $REPO/tools/prof_selfcheck.py "$OUT" | tee $REPO/gpurun_out/selfcheck_$TAG.txt
