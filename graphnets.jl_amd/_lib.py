@@ -146,6 +146,8 @@ SIGNATURES = {
                                  [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_block_forward_chained": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams)] + _FWD[2:] + [C.POINTER(PendingUpdate), C.POINTER(PendingUpdate)]),
     "gnx_block_forward_steps": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.POINTER(BlockStep), C.c_int64, C.c_int64, C.c_uint32, C.c_void_p]),
+    "gnx_block_forward_steps_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32, C.POINTER(BlockStep), C.c_int64, C.c_int64, C.c_uint32,
+                                                  C.c_void_p]),
     "gnx_row_stats": (C.c_int32, [_fp, C.c_int64, C.c_int32, C.c_float, C.c_int32, _fp, C.c_void_p]),
     "gnx_block_graph_update": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), _fp, C.c_int64, _fp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "gnx_block_backward_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(BlockParams), C.c_int64]),

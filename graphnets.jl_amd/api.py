@@ -1384,29 +1384,58 @@ class GNCoreList:
 
 class BlockPlan:
     """A pre-bound `gnx_block_forward` call: parameter struct, workspace and handle are fixed, so one step is ONE
-    ctypes call on packed [R][T][D] tensors — what hipGraph capture and the bench loop want.  No allocation here."""
+    ctypes call on packed [R][T][D] tensors — what hipGraph capture and the bench loop want.  No allocation here.
+    `dtype=torch.bfloat16`: bf16 feature tensors — the workspace sized by gnx_block_typed_workspace_bytes, `outputs()` in bf16, a call is
+    `gnx_block_forward_typed` and `steps` is `gnx_block_forward_steps_typed`; the chained / deferred forms are fp32-only (TypeError)."""
 
-    def __init__(self, block, g, R=1, flags=None):
+    def __init__(self, block, g, R=1, flags=None, dtype=None):
+        if dtype not in (None, torch.float32, torch.bfloat16):
+            raise TypeError(f"BlockPlan: dtype must be None, torch.float32 or torch.bfloat16, not {dtype}")
         self.block, self.g, self.R = block, g, int(R)
+        self.bf16 = dtype == torch.bfloat16
         self.flags = block.flags if flags is None else flags
         self._keep = []
         self.p = block._c(self._keep)
         self.lib = _lib.load()
         with torch.cuda.device(g.device):
-            nbytes = self.lib.gnx_block_workspace_bytes(g._h, C.byref(self.p), self.R)
+            if self.bf16:
+                nbytes = self.lib.gnx_block_typed_workspace_bytes(g._h, C.byref(self.p), self.R, _lib.ELEM_BF16, self.flags)
+                if not nbytes:
+                    raise GnxError(_lib.ERR_INVALID_ARG, "gnx_block_typed_workspace_bytes: " + (self.lib.gnx_last_error() or b"").decode())
+            else:
+                nbytes = self.lib.gnx_block_workspace_bytes(g._h, C.byref(self.p), self.R)
         self.ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=g.device)
 
     def outputs(self):
         oe, on, og = self.block.out_dims
         g, R = self.g, self.R
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.float32, device=g.device) if d > 0 else None
+        dt = torch.bfloat16 if self.bf16 else torch.float32
+        mk = lambda T, d: torch.empty((R, T, d), dtype=dt, device=g.device) if d > 0 else None
         return mk(g.n_edges, oe), mk(g.n_nodes, on), mk(g.n_graphs, og)
+
+    def _fp32_only(self, what):
+        if self.bf16:
+            raise TypeError(f"BlockPlan.{what}: not a bfloat16 form (gnx_block_forward_steps_typed runs the chained graph updates itself)")
+
+    @staticmethod
+    def _check_bf16(ts, what):
+        for t in ts:
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16):
+                raise TypeError(f"BlockPlan.{what}: a bfloat16 plan takes bfloat16 feature tensors, not {getattr(t, 'dtype', type(t).__name__)}")
 
     def __call__(self, ef, nf, gf, eo, no, go, stream=None, ws=None, defer_graph_update=False):
         """`defer_graph_update`: stop after the edge + node update (GNX_FLAG_DEFER_GRAPH_UPDATE); finish with
         `graph_update` — typically on a second stream so that it overlaps the next batch."""
+        if self.bf16:
+            if defer_graph_update:
+                self._fp32_only("__call__(defer_graph_update=True)")
+            self._check_bf16((ef, nf, gf, eo, no, go), "__call__")
         s = torch.cuda.current_stream(self.g.device).cuda_stream if stream is None else stream
         ws = self.ws if ws is None else ws
+        if self.bf16:
+            check(self.lib.gnx_block_forward_typed(self.g._h, C.byref(self.p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), self.R, _ptr(eo), _ptr(no),
+                                                   _ptr(go), ws.data_ptr(), ws.numel(), self.flags, s))
+            return
         flags = self.flags | (_lib.FLAG_DEFER_GRAPH_UPDATE if defer_graph_update else 0)
         check(self.lib.gnx_block_forward(self.g._h, C.byref(self.p), _ptr(ef), _ptr(nf), _ptr(gf), self.R, _ptr(eo), _ptr(no),
                                          _ptr(go), ws.data_ptr(), ws.numel(), flags, s))
@@ -1415,6 +1444,7 @@ class BlockPlan:
         """`gnx_block_forward_chained`: this call's edge + node update with the graph update of the PREVIOUS chained call (`prev`: the
         record that call returned, or None) at the front of the same launch.  Returns this call's pending record; `go` is valid after
         the next chained call on the stream or `flush(pending)`.  `ws` / `go` must differ from the pending call's."""
+        self._fp32_only("chained")
         s = torch.cuda.current_stream(self.g.device).cuda_stream if stream is None else stream
         pending = _lib.PendingUpdate()
         check(self.lib.gnx_block_forward_chained(self.g._h, C.byref(self.p), _ptr(ef), _ptr(nf), _ptr(gf), self.R, _ptr(eo), _ptr(no), _ptr(go),
@@ -1425,16 +1455,24 @@ class BlockPlan:
         """`gnx_block_forward_steps`: a LOOP over batches as one call — `sets` is a sequence of dicts / tuples (ef, nf, gf, eo, no, go, ws), one per
         step, in order.  Exactly `len(sets)` forwards (bit-identical outputs); where the two-launch narrow form runs, step i's graph update rides at
         the front of a later launch (step i + 2's: neighbouring steps run on two streams) and the last ones are flushed inside the call: every output is complete when the enqueued work is.
-        Consecutive steps must use different workspaces and gf outputs to be chained (else the step simply runs unchained)."""
+        Consecutive steps must use different workspaces and gf outputs to be chained (else the step simply runs unchained).
+        A bfloat16 plan: `gnx_block_forward_steps_typed` (every feature tensor of every step bf16, checked before the call)."""
+        steps = [(b["ef"], b["nf"], b["gf"], *b["out"], b["ws"]) if isinstance(b, dict) else tuple(b) for b in sets]
+        if self.bf16:
+            for st in steps:
+                self._check_bf16(st[:6], "steps")
         s = torch.cuda.current_stream(self.g.device).cuda_stream if stream is None else stream
-        arr = (_lib.BlockStep * max(len(sets), 1))()
-        for i, b in enumerate(sets):
-            ef, nf, gf, eo, no, go, ws = (b["ef"], b["nf"], b["gf"], *b["out"], b["ws"]) if isinstance(b, dict) else b
+        arr = (_lib.BlockStep * max(len(steps), 1))()
+        for i, (ef, nf, gf, eo, no, go, ws) in enumerate(steps):
             arr[i] = _lib.BlockStep(_ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), ws.data_ptr(), ws.numel())
-        check(self.lib.gnx_block_forward_steps(self.g._h, C.byref(self.p), arr, len(sets), self.R, self.flags, s))
+        if self.bf16:
+            check(self.lib.gnx_block_forward_steps_typed(self.g._h, C.byref(self.p), _lib.ELEM_BF16, arr, len(steps), self.R, self.flags, s))
+        else:
+            check(self.lib.gnx_block_forward_steps(self.g._h, C.byref(self.p), arr, len(steps), self.R, self.flags, s))
 
     def flush(self, pending, stream=None):
         """finishes a pending graph update (one plain `gnx_block_graph_update` launch); no-op when nothing is pending"""
+        self._fp32_only("flush")
         if pending is None or not pending.workspace:
             return
         s = torch.cuda.current_stream(self.g.device).cuda_stream if stream is None else stream
@@ -1446,6 +1484,7 @@ class BlockPlan:
         return torch.empty_like(self.ws)
 
     def graph_update(self, gf, go, stream=None, ws=None):
+        self._fp32_only("graph_update")
         s = torch.cuda.current_stream(self.g.device).cuda_stream if stream is None else stream
         ws = self.ws if ws is None else ws
         check(self.lib.gnx_block_graph_update(self.g._h, C.byref(self.p), _ptr(gf), self.R, _ptr(go), ws.data_ptr(), ws.numel(),

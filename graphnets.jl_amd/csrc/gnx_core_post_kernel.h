@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void k_core_post3(PostJob e, PostJob n, PostJo
     const size_t r = gb / (unsigned)a.G;
     const bool oneg = a.G == 1;  // one row per workgroup of k_block_wave, else one per wave tile (gnx_narrow.hip: partial_rows)
     const int t0 = oneg ? 0 : a.wtile_off[gi], t1 = oneg ? (a.n_wtiles + 3) / 4 : a.wtile_off[gi + 1];
-    graph_update_rows<C, false, 16>(a, a.partials + r * (size_t)n_rows * CP, gi, r, t0, t1, (int)threadIdx.x, 256, s_g);
+    graph_update_rows<C, false, 16>(a, a.gf, a.gf_out, a.partials + r * (size_t)n_rows * CP, gi, r, t0, t1, (int)threadIdx.x, 256, s_g);
     __syncthreads();  // gf' of this graph is in memory (written by this workgroup): the FeedForward below reads it as the block's output
     const size_t row = r * (size_t)a.G + gi;
     core_post_lds_body<D2, 1>(g.x + row * D2, 1, g.gamma, g.beta, g.fc1, g.fc2, eps, eps_mode, g.out + row * D2, 0, 1);

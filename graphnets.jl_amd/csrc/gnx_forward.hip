@@ -30,10 +30,11 @@ int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, 
 void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p, bool bf16 = false);
 bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
 bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1, int act2);
-bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a);
+bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16 = false);
 bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16 = false);
-int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);  // 1: no fused bf16 kernel for these widths
+int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);  // 1: no fused bf16 kernel for these widths
 int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
+int32_t launch_block_narrow_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
 static_assert(GNX_ACT_IDENTITY == 0 && GNX_ACT_RELU == 1 && GNX_ACT_TANH == 2 && GNX_ACT_SIGMOID == 3 && GNX_ACT_GELU == 4,
               "act_apply (gnx_device.h) hard-codes the activation codes");
 int32_t launch_block_wide(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
@@ -173,17 +174,18 @@ static int32_t block_forward_impl(const gnx_graphs* h, const gnx_block_params* p
     if (args_out) *args_out = a;
     return launch_block_narrow(h, a, R, s, phase);
   }
-  if (chain_took) {  // gnx_block_forward_chained: this call's edge + node update with the previous call's graph update at the front of the launch
-    *chain_took = !(flags & (GNX_FLAG_FORCE_GENERIC)) && block_narrow_chain_applies(h, a);
+  if (chain_took) {  // gnx_block_forward_chained (bf16: a step of gnx_block_forward_steps_typed): this call's edge + node update with the previous
+                     // call's graph update at the front of the launch
+    *chain_took = !(flags & (GNX_FLAG_FORCE_GENERIC)) && block_narrow_chain_applies(h, a, bf16);
     if (!*chain_took) return GNX_OK;  // nothing launched: the caller runs the plain form
     if (chain_prev && chain_prev->workspace) {
       a.prev_partials = reinterpret_cast<const float*>(static_cast<const char*>(chain_prev->workspace) + w.part_off);
       a.prev_gf = chain_prev->gf; a.prev_gf_out = chain_prev->gf_out;
     }
-    return launch_block_narrow_chained(h, a, R, s);
+    return bf16 ? launch_block_narrow_chained_bf16(h, a, R, s) : launch_block_narrow_chained(h, a, R, s);
   }
   if (bf16) {  // gnx_block_forward_typed: the six feature pointers are bf16; only the fused kernels read them natively (the caller checked)
-    rc = launch_block_narrow_bf16(h, a, R, s);
+    rc = launch_block_narrow_bf16(h, a, R, s, phase);
     return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: no fused bf16 kernel for these widths") : rc;
   }
   if (!(flags & GNX_FLAG_FORCE_GENERIC)) {
@@ -267,6 +269,7 @@ extern "C" {
 size_t gnx_block_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem, uint32_t flags) {
   if (elem == GNX_ELEM_F32) return gnx_block_workspace_bytes(h, p, R);
   if (elem != GNX_ELEM_BF16 || !h || !p || R <= 0 || (flags & GNX_FLAG_DEFER_GRAPH_UPDATE)) return 0;
+  ensure_aux(h);  // the side streams of gnx_block_forward_steps_typed's two-stream schedule (the native path never reaches the fp32 query)
   FormScope forms(flags);
   if (check_block(h, p, R) != GNX_OK) return 0;
   warm_block_narrow(h, p, true);  // the bf16 specialisation of these widths, if they need one
@@ -342,18 +345,13 @@ int32_t gnx_block_forward_chained(const gnx_graphs* h, const gnx_block_params* p
   return block_forward_impl(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream, 3);
 }
 
-// the bytes a step reads and writes (gnx_step_hazard.h); the workspace is the part the block's kernels use
-static StepSpans step_spans(const gnx_graphs* h, const gnx_block_params* p, int64_t R, const gnx_block_step& st) {
-  const size_t f = sizeof(float) * (size_t)R;
-  StepSpans sp;
-  sp.rd[0] = byte_span(st.ef, f * h->E * p->de);
-  sp.rd[1] = byte_span(st.nf, f * h->N * p->dn);
-  sp.rd[2] = byte_span(st.gf, f * h->G * p->dg);
-  sp.wr[0] = byte_span(st.ef_out, f * h->E * p->oe);
-  sp.wr[1] = byte_span(st.nf_out, f * h->N * p->on);
-  sp.wr[2] = byte_span(st.gf_out, f * h->G * p->og);
-  sp.wr[3] = byte_span(st.workspace, std::min(st.workspace_bytes, block_ws(h, p, R).total));
-  return sp;
+// the bytes a step reads and writes (gnx_step_hazard.h: elem bytes per feature); the workspace is the part the block's kernels use (ws_extent)
+static StepSpans step_spans(const gnx_graphs* h, const gnx_block_params* p, int64_t R, const gnx_block_step& st, size_t elem, size_t ws_extent) {
+  const void* const in[3] = {st.ef, st.nf, st.gf};
+  const void* const out[3] = {st.ef_out, st.nf_out, st.gf_out};
+  const long long rows[3] = {(long long)h->E, (long long)h->N, (long long)h->G};
+  const int in_w[3] = {p->de, p->dn, p->dg}, out_w[3] = {p->oe, p->on, p->og};
+  return step_spans_of(in, out, st.workspace, st.workspace_bytes, rows, in_w, out_w, R, elem, ws_extent);
 }
 
 // Can the steps of this call run on two streams?  The fused narrow kernel (plain, chained, pack form, run-time specialised) only: the
@@ -367,18 +365,51 @@ static bool steps_overlap_applies(const gnx_graphs* h, const gnx_block_params* p
   return block_narrow_takes(h, a, s);
 }
 
-int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step* steps, int64_t n_steps, int64_t R, uint32_t flags,
-                                void* stream) {
-  if (n_steps < 0 || (n_steps > 0 && !steps)) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps: steps is NULL / n_steps is negative");
-  if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps finishes every step's graph update itself");
-  DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));  // (one turn for the whole loop; the calls below nest inside it)
-  FormScope forms(flags);
+// ---- bf16 steps (gnx_block_forward_steps_typed): typed, internal forms of gnx_block_forward_chained and gnx_block_graph_update ----
+// (the exported pending-update record has float* fields and no element type: these two stay inside the loop)
+static int32_t typed_graph_update(const gnx_graphs* h, const gnx_block_params* p, const float* gf, int64_t R, float* gf_out, void* ws, size_t ws_bytes,
+                                  uint32_t flags, hipStream_t s) {
+  return block_forward_impl(h, p, nullptr, nullptr, gf, R, nullptr, nullptr, gf_out, ws, ws_bytes, flags, s, 2, nullptr, 0.f, 0, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, true);
+}
+// One bf16 step on the native path: chained where the fp32 rule would chain (bf16 ahead-of-time widths), else `prev` flushed and the step run
+// whole by gnx_block_forward_typed (run-time specialised widths, the pack form), nothing left pending.
+static int32_t typed_chained(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step& st, int64_t R, uint32_t flags, hipStream_t s,
+                             const gnx_pending_update* prev, gnx_pending_update* pending) {
+  int32_t rc = check_block(h, p, R);
+  if (rc) return rc;
+  if ((p->de > 0 && !st.ef && h->E > 0) || (p->dn > 0 && !st.nf) || (p->dg > 0 && !st.gf))
+    return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL (width 0 <=> nothing)");
+  if ((p->oe > 0 && !st.ef_out && h->E > 0) || (p->on > 0 && !st.nf_out) || (p->og > 0 && !st.gf_out))
+    return fail(GNX_ERR_INVALID_ARG, "an output with non-zero width is NULL");
+  if (prev && prev->workspace && (prev->workspace == st.workspace || (p->og > 0 && prev->gf_out == st.gf_out)))
+    return fail(GNX_ERR_INVALID_ARG, "internal: the pending step's workspace / gf_out is this step's");
+  bool took = false;
+  rc = block_forward_impl(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, s, 1, nullptr, 0.f, 0,
+                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, prev, &took, nullptr, false, nullptr, true);
+  if (rc) return rc;
+  if (took) {
+    pending->workspace = st.workspace; pending->workspace_bytes = st.workspace_bytes; pending->gf = st.gf; pending->gf_out = st.gf_out;
+    return GNX_OK;
+  }
+  if (prev && prev->workspace) {
+    rc = typed_graph_update(h, p, prev->gf, R, prev->gf_out, const_cast<void*>(prev->workspace), prev->workspace_bytes, flags, s);
+    if (rc) return rc;
+  }
+  *pending = gnx_pending_update{};
+  return gnx_block_forward_typed(h, p, GNX_ELEM_BF16, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, s);
+}
+
+// The loop of gnx_block_forward_steps (bf16: gnx_block_forward_steps_typed on the native path), on one stream or — `overlap` — on two.  The
+// caller holds the DeviceTurn and the FormScope.
+static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step* steps, int64_t n_steps, int64_t R, uint32_t flags,
+                              void* stream, bool bf16, bool overlap) {
   // Two streams: even steps on the caller's, odd steps on a side stream of the handle's pool (taken as gnx_core_forward takes it), so that
   // step i + 1's launch fills the slots that step i's ramp and drain leave idle and the per-launch cost of one hides under the other.
   // Every set taken, GNX_FLAG_NO_FORK, the per-kernel profiler on, or not the fused narrow kernel: one stream, the loop as before.
   std::unique_lock<std::mutex> aux_lk;
   const gnx_graphs::AuxSet* aux = nullptr;
-  if (n_steps > 1 && steps_overlap_applies(h, p, R, flags, (hipStream_t)stream))
+  if (overlap)
     for (auto& ax : h->aux) {
       if (!ax.stream || !ax.step[3]) break;
       std::unique_lock<std::mutex> lk(ax.mu, std::try_to_lock);
@@ -390,25 +421,34 @@ int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, 
   gnx_pending_update pend[2]{};
   auto flush = [&](int k) -> int32_t {
     if (!pend[k].workspace) return GNX_OK;
-    const int32_t rc = gnx_block_graph_update(h, p, pend[k].gf, R, pend[k].gf_out, const_cast<void*>(pend[k].workspace), pend[k].workspace_bytes, flags, str[k]);
+    const int32_t rc = bf16 ? typed_graph_update(h, p, pend[k].gf, R, pend[k].gf_out, const_cast<void*>(pend[k].workspace), pend[k].workspace_bytes, flags, str[k])
+                            : gnx_block_graph_update(h, p, pend[k].gf, R, pend[k].gf_out, const_cast<void*>(pend[k].workspace), pend[k].workspace_bytes, flags, str[k]);
     pend[k] = gnx_pending_update{};
     return rc;
   };
+  auto run = [&](const gnx_block_step& st, int k, gnx_pending_update* next) -> int32_t {
+    const gnx_pending_update* prev = pend[k].workspace ? &pend[k] : nullptr;
+    return bf16 ? typed_chained(h, p, st, R, flags, str[k], prev, next)
+                : gnx_block_forward_chained(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[k],
+                                            prev, next);
+  };
+  const bool valid = h && p && check_block(h, p, R) == GNX_OK;  // (else the first step reports the error)
+  // per feature: 4 or 2 bytes; the workspace extent is the workspace query's (bf16 on this path: the native kernels, no staging)
+  const size_t elem = bf16 ? 2 : sizeof(float);
+  const size_t ws_extent = !valid ? 0 : bf16 ? typed_ws(h, p, R, true).total : block_ws(h, p, R).total;
   if (!aux) {
     StepSpans prev;
-    const bool valid = h && p && check_block(h, p, R) == GNX_OK;  // (else the first step reports the error)
     for (int64_t i = 0; i < n_steps; ++i) {
       const gnx_block_step& st = steps[i];
       // a step whose buffers overlap its predecessor's (a shared workspace / gf_out, or gf' read as the next step's input) cannot start
       // before that one's graph update has run
-      const StepSpans cur = valid ? step_spans(h, p, R, st) : StepSpans{};
+      const StepSpans cur = valid ? step_spans(h, p, R, st, elem, ws_extent) : StepSpans{};
       if (pend[0].workspace && (pend[0].workspace == st.workspace || (p && p->og > 0 && pend[0].gf_out == st.gf_out) || steps_conflict(cur, prev))) {
         if (int32_t rc = flush(0)) return rc;
       }
       prev = cur;
       gnx_pending_update next{};
-      if (int32_t rc = gnx_block_forward_chained(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[0],
-                                                 pend[0].workspace ? &pend[0] : nullptr, &next)) {
+      if (int32_t rc = run(st, 0, &next)) {
         // (an argument error of step i: what is pending belongs to step i - 1, whose arguments were valid — finish it, report the error)
         (void)flush(0);
         return rc;
@@ -426,7 +466,7 @@ int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, 
   for (int64_t i = 0; i < n_steps && rc == GNX_OK; ++i) {
     const gnx_block_step& st = steps[i];
     const int k = (int)(i & 1), o = k ^ 1;
-    const StepSpans cur = step_spans(h, p, R, st);
+    const StepSpans cur = step_spans(h, p, R, st, elem, ws_extent);
     const StepOrder ord = step_order(cur, recent, i);
     if (ord.flush_own && (rc = flush(k))) break;
     if (i >= 3) {
@@ -441,8 +481,7 @@ int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, 
       if (e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: ordering a step behind the other stream"); break; }
     }
     gnx_pending_update next{};
-    rc = gnx_block_forward_chained(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[k],
-                                   pend[k].workspace ? &pend[k] : nullptr, &next);
+    rc = run(st, k, &next);
     if (rc != GNX_OK) break;
     pend[k] = next;
     // (step[i & 3] was last recorded for step i - 4, and the wait on that record — step i - 1's — is already enqueued)
@@ -460,6 +499,46 @@ int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, 
   GNX_HIP(e1);
   GNX_HIP(e2);
   return GNX_OK;
+}
+
+int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step* steps, int64_t n_steps, int64_t R, uint32_t flags,
+                                void* stream) {
+  if (n_steps < 0 || (n_steps > 0 && !steps)) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps: steps is NULL / n_steps is negative");
+  if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps finishes every step's graph update itself");
+  DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));  // (one turn for the whole loop; the calls below nest inside it)
+  FormScope forms(flags);
+  return steps_schedule(h, p, steps, n_steps, R, flags, stream, false, n_steps > 1 && steps_overlap_applies(h, p, R, flags, (hipStream_t)stream));
+}
+
+int32_t gnx_block_forward_steps_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_block_step* steps, int64_t n_steps, int64_t R,
+                                      uint32_t flags, void* stream) {
+  if (elem == GNX_ELEM_F32) return gnx_block_forward_steps(h, p, steps, n_steps, R, flags, stream);
+  // every argument error below is found before the first launch (the fp32 loop reports a step's error once the steps before it are issued)
+  if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps_typed finishes every step's graph update itself");
+  if (n_steps < 0 || (n_steps > 0 && !steps)) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps_typed: steps is NULL / n_steps is negative");
+  for (int64_t i = 0; i < n_steps; ++i) {
+    const gnx_block_step& st = steps[i];
+    const void* bufs[6] = {st.ef, st.nf, st.gf, st.ef_out, st.nf_out, st.gf_out};
+    for (const void* b : bufs)
+      if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned (in every step)");
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  DeviceTurn turn(s, p && matrix_core_widths(*p));  // (one turn for the whole loop; the calls below nest inside it)
+  FormScope forms(flags);
+  if (!h || !p || check_block(h, p, R) != GNX_OK || !typed_native(h, p, flags, s)) {
+    // matrix-core / generic widths, GNX_FLAG_FORCE_GENERIC, GNX_FLAG_NO_JIT, a failed specialisation: n typed forwards in order on the caller's
+    // stream, each converting around the fp32 forward inside its own workspace (and the first invalid step reporting its error)
+    for (int64_t i = 0; i < n_steps; ++i) {
+      const gnx_block_step& st = steps[i];
+      if (int32_t rc = gnx_block_forward_typed(h, p, GNX_ELEM_BF16, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes,
+                                               flags, stream))
+        return rc;
+    }
+    return GNX_OK;
+  }
+  // a native bf16 kernel takes these widths (ahead of time, run-time specialised, pack form): the fp32 loop's schedule on bf16 rows
+  return steps_schedule(h, p, steps, n_steps, R, flags, stream, true, n_steps > 1 && !form(GNX_FLAG_NO_FORK) && !profile_enabled());
 }
 
 int32_t gnx_block_graph_update(const gnx_graphs* h, const gnx_block_params* p, const float* gf, int64_t R, float* gf_out, void* ws,

@@ -32,7 +32,8 @@ namespace gnx {
   X(10, 5, 0, 10, 5)
 // ... with bfloat16 features: gnx_narrow_bf16.hip
 bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a);
-int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
+int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
+int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
 
 bool jit_eligible(const BlockArgs& a, int ept);
 int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph, bool bf16 = false);
@@ -109,19 +110,21 @@ bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s) 
 // gnx_block_forward_chained: can the previous call's graph update ride at the front of this call's block kernel?  The two-launch form of
 // an ahead-of-time width set at the default wave-tile size, graph function small enough for the kernel's LDS, <= 256 partial rows per
 // graph (one wavefront per graph) or one graph.  (Batches that take the pack form run their graph update inside the kernel already.)
+// bf16 features: the same rule, restricted to the bf16 ahead-of-time list (gnx_narrow_bf16.hip).
 static bool pack_form(const gnx_graphs* h, const BlockArgs& a) { return h->G > 1 && h->n_packs > 0 && a.packs && a.og > 0 && !getenv("GNX_NO_PACK"); }
-bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a) {
+bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16) {
   if (a.n_wtiles == 0 || a.E == 0 || a.og <= 0 || h->wtile_e_cap != 128 || wants_ln(a) || a.ffe_w1 || pack_form(h, a)) return false;
   const int C = a.oe + a.on;
   if (C <= 0) return false;
   const int wsl = wave_slice_floats(a.oe, 2);
   if (h->G == 1) { if (graph_update_lds_floats(C, a.dg, a.og, graph_update_threads(h)) > 4 * wsl) return false; }
   else if (h->max_wtiles_per_graph > 256 || graph_update_lds_floats(C, a.dg, a.og, 64) > wsl) return false;
+  bool listed = false;
 #define GNX_CASE(DE, DN, DG, OE, ON) \
-  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return true;
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) listed = true;
   GNX_NARROW_DIMS(GNX_CASE)
 #undef GNX_CASE
-  return false;
+  return listed && (!bf16 || narrow_bf16_aot(h, a));
 }
 // the edge + node update of THIS call with a.prev_* (the previous call's pending graph update) at the front of the same launch
 int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a0, int64_t R, hipStream_t s) {
@@ -137,6 +140,13 @@ int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a0, in
   GNX_NARROW_DIMS(GNX_CASE)
 #undef GNX_CASE
   return fail(GNX_ERR_INVALID_ARG, "internal: chained launch for a width set without that kernel");
+}
+// ... on bf16 rows (gnx_block_forward_steps_typed)
+int32_t launch_block_narrow_chained_bf16(const gnx_graphs* h, const BlockArgs& a0, int64_t R, hipStream_t s) {
+  BlockArgs a = a0;
+  a.prev_blocks = a.prev_partials ? (h->G == 1 ? 1 : (int)((h->G + 3) / 4)) : 0;
+  const int32_t rc = launch_chained_bf16(h, a, R, s);
+  return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: chained bf16 launch for a width set without that kernel") : rc;
 }
 
 // the edge FeedForward + residual of a narrow GNCore inside the block kernel (k_block_wave<..., FFE>): ahead-of-time widths, identity / relu
@@ -176,12 +186,12 @@ static NarrowRoute narrow_route(const gnx_graphs* h, const BlockArgs& a, hipStre
 bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16) { return narrow_route(h, a, s, bf16) != NR_NONE; }
 
 // bf16 features (gnx_block_forward_typed): the native kernels, or 1 when no fused kernel takes these widths (the caller converts around
-// the fp32 forward).  No LayerNorm on load, no chained / deferred forms.
-int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s) {
+// the fp32 forward).  No LayerNorm on load, no deferred form; phase 2 alone is the flush of a chained bf16 step (ahead-of-time widths only).
+int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
   const NarrowRoute route = narrow_route(h, a, s, true);
   if (route == NR_NONE) return 1;
-  if (route == NR_JIT) return launch_wave_jit(h, a, R, s, 3, true);
-  const int32_t rc = launch_fused_bf16(h, a, R, s);
+  if (route == NR_JIT) return launch_wave_jit(h, a, R, s, phase, true);
+  const int32_t rc = launch_fused_bf16(h, a, R, s, phase);
   return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: ahead-of-time bf16 route for a width set without that kernel") : rc;
 }
 

@@ -1,5 +1,6 @@
-// The fused narrow kernels with bfloat16 feature rows (k_block_wave<..., BF16 = true>, k_graph_t<C, ONEG, true>) for the ahead-of-time
-// width sets; gnx_narrow.hip routes gnx_block_forward_typed here, every other narrow width set is specialised at run time (gnx_jit.cpp).
+// The fused narrow kernels with bfloat16 feature rows (k_block_wave<..., BF16 = true>, its chained form k_block_wave<..., CHAIN, BF16>,
+// k_graph_t<C, ONEG, true>) for the ahead-of-time width sets; gnx_narrow.hip routes gnx_block_forward_typed and the bf16 steps of
+// gnx_block_forward_steps_typed here, every other narrow width set is specialised at run time (gnx_jit.cpp).
 // A translation unit of its own because build.py compiles it without the SLP vectoriser (-fno-slp-vectorize; gnx_jit.cpp passes the same
 // option for a bf16 key): with it, every widened value feeds a v_pk_fma_f32 as the low half of a register pair of its own, and the README
 // ex.1 kernel needs 70 instead of 58 VGPRs — 7 instead of 8 waves per SIMD.  Scalar FMAs compute the same bits.
@@ -9,9 +10,11 @@
 
 namespace gnx {
 
-// README ex.1 / the headline batch (BASELINE configs[1])
+// README ex.1 / the headline batch (BASELINE configs[1]); README ex.1's outputs (3,4,5) => (3,4,5): a set with dg > 0 (the chained graph
+// update reads a bf16 gf) that also maps dims to dims (the recurrent loop x_{i+1} = block(x_i))
 #define GNX_NARROW_DIMS_BF16(X) \
-  X(10, 5, 0, 3, 4)
+  X(10, 5, 0, 3, 4)             \
+  X(3, 4, 5, 3, 4)
 
 // an ahead-of-time bf16 kernel exists for these widths at the handle's wave-tile size (launch_fused's EPT)
 bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a) {
@@ -23,10 +26,26 @@ bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a) {
   return false;
 }
 
-// the whole block (phase 3) on bf16 rows; 1: no ahead-of-time kernel for these widths
-int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s) {
+// the block on bf16 rows — whole (phase 3), or only the graph update from partial rows a chained launch left (phase 2: a flush of
+// gnx_block_forward_steps_typed); 1: no ahead-of-time kernel for these widths
+int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
 #define GNX_CASE(DE, DN, DG, OE, ON) \
-  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return launch_fused<DE, DN, DG, OE, ON, true>(h, a, R, s, 3);
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return launch_fused<DE, DN, DG, OE, ON, true>(h, a, R, s, phase);
+  GNX_NARROW_DIMS_BF16(GNX_CASE)
+#undef GNX_CASE
+  return 1;
+}
+
+// the chained form (gnx_narrow.hip: launch_block_narrow_chained) on bf16 rows: this call's edge + node update with the previous call's
+// graph update at the front of the launch; 1: no ahead-of-time kernel for these widths
+int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s) {
+#define GNX_CASE(DE, DN, DG, OE, ON)                                                                                               \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) {                                                         \
+    if constexpr (OE + ON > 0) {                                                                                                   \
+      return h->G == 1 ? launch_wave_g<DE, DN, DG, OE, ON, 2, false, true, false, true, true>(h, a, R, s, 1)                        \
+                       : launch_wave_g<DE, DN, DG, OE, ON, 2, false, false, false, true, true>(h, a, R, s, 1);                      \
+    }                                                                                                                              \
+  }
   GNX_NARROW_DIMS_BF16(GNX_CASE)
 #undef GNX_CASE
   return 1;

@@ -25,6 +25,20 @@ struct StepSpans {
   ByteSpan wr[4];  // ef_out, nf_out, gf_out, workspace
 };
 
+// The spans of one step of R replicas: rows[t] rows (E, N, G) of the inputs in_w[t] wide and of the outputs out_w[t] wide, elem bytes per
+// feature (4: fp32, 2: bf16), and the part of the workspace the block's kernels use (ws_extent: the workspace query's figure for this call).
+inline StepSpans step_spans_of(const void* const in[3], const void* const out[3], const void* ws, size_t ws_bytes, const long long rows[3],
+                               const int in_w[3], const int out_w[3], long long R, size_t elem, size_t ws_extent) {
+  const size_t f = elem * (size_t)R;
+  StepSpans sp;
+  for (int t = 0; t < 3; ++t) {
+    sp.rd[t] = byte_span(in[t], f * (size_t)rows[t] * (size_t)in_w[t]);
+    sp.wr[t] = byte_span(out[t], f * (size_t)rows[t] * (size_t)out_w[t]);
+  }
+  sp.wr[3] = byte_span(ws, ws_bytes < ws_extent ? ws_bytes : ws_extent);
+  return sp;
+}
+
 // true: the two steps must not be in flight together
 inline bool steps_conflict(const StepSpans& x, const StepSpans& y) {
   for (const ByteSpan& w : x.wr) {

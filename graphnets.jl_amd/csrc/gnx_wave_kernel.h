@@ -569,11 +569,12 @@ __device__ __forceinline__ void store_partial_row(float mine, float* row, int la
   }
 }
 
+// gf / gf_out: the graph rows this update reads and writes (a.gf / a.gf_out; the CHAIN front passes the previous call's a.prev_gf / a.prev_gf_out).
 // vthr (a multiple of 64; 0: nthr): the sums come out as a launch of vthr threads would form them — the bits k_graph_t gives with that many
 // threads.  Thread tid plays the threads tid, tid + nthr, ... below vthr in turn (none, one or several; the same count across a wavefront).
 template <int C, bool WAVE, int F4_IN_FLIGHT, bool BF16 = false>
-__device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const float* __restrict__ base, int g, size_t r, int t0, int t1, int tid, int nthr, float* s_g,
-                                                  int vthr = 0) {
+__device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const float* gf, float* gf_out, const float* __restrict__ base, int g, size_t r, int t0,
+                                                  int t1, int tid, int nthr, float* s_g, int vthr = 0) {
   constexpr int Q = (C + 3) / 4, CP = 4 * Q;
   constexpr int RIF = Q >= F4_IN_FLIGHT ? 1 : F4_IN_FLIGHT / Q;  // rows in flight per thread; the per-thread accumulation order (rows ascending) does not depend on it
   const int K = C + a.dg, og = a.og;
@@ -591,7 +592,7 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
     w_reg[i] = idx < nw ? a.Wg[idx] : (idx < nw + og ? (a.bg ? a.bg[idx - nw] : 0.f) : 0.f);
   }
   float gf_reg = 0.f;
-  if (tid < a.dg) gf_reg = ld_feat<BF16>(a.gf, (r * (size_t)a.G + g) * a.dg + tid);
+  if (tid < a.dg) gf_reg = ld_feat<BF16>(gf, (r * (size_t)a.G + g) * a.dg + tid);
 
   const int lane = tid & 63;
   for (int v = tid; v < vthr; v += nthr) {
@@ -633,16 +634,16 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
   if (a.ln_g[2] && a.dg > 0) {  // GNCore: the graph function sees gn1(gf); a few values, every thread computes the statistics
     const size_t gp = (r * (size_t)a.G + g) * a.dg;
     float mu = 0.f;
-    for (int k = 0; k < a.dg; ++k) mu += ld_feat<BF16>(a.gf, gp + k);
+    for (int k = 0; k < a.dg; ++k) mu += ld_feat<BF16>(gf, gp + k);
     mu /= (float)a.dg;
     float var = 0.f;
-    for (int k = 0; k < a.dg; ++k) { const float c = ld_feat<BF16>(a.gf, gp + k) - mu; var = fmaf(c, c, var); }
+    for (int k = 0; k < a.dg; ++k) { const float c = ld_feat<BF16>(gf, gp + k) - mu; var = fmaf(c, c, var); }
     var /= (float)a.dg;
     const float rstd = a.ln_mode == 0 ? 1.f / (sqrtf(var) + a.ln_eps) : 1.f / sqrtf(var + a.ln_eps);
-    for (int k = tid; k < a.dg; k += nthr) s_x[C + k] = fmaf(a.ln_g[2][k], (ld_feat<BF16>(a.gf, gp + k) - mu) * rstd, a.ln_b[2][k]);
+    for (int k = tid; k < a.dg; k += nthr) s_x[C + k] = fmaf(a.ln_g[2][k], (ld_feat<BF16>(gf, gp + k) - mu) * rstd, a.ln_b[2][k]);
   } else {
     if (tid < a.dg) s_x[C + tid] = gf_reg;
-    for (int k = tid + nthr; k < a.dg; k += nthr) s_x[C + k] = ld_feat<BF16>(a.gf, (r * (size_t)a.G + g) * a.dg + k);
+    for (int k = tid + nthr; k < a.dg; k += nthr) s_x[C + k] = ld_feat<BF16>(gf, (r * (size_t)a.G + g) * a.dg + k);
   }
   if constexpr (WAVE) __builtin_amdgcn_wave_barrier(); else __syncthreads();
   // second stage: wave 0 sums the <= 64 row sums of every column (fixed order: DPP tree + 4 readlanes)
@@ -658,7 +659,7 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
   for (int j = tid; j < og; j += nthr) {
     float y = s_w[nw + j];
     for (int k = 0; k < K; ++k) y = fmaf(s_w[k * og + j], s_x[k], y);
-    st_feat<BF16>(a.gf_out, out + j, act_apply(y, a.act_g));
+    st_feat<BF16>(gf_out, out + j, act_apply(y, a.act_g));
   }
 }
 
@@ -765,7 +766,8 @@ constexpr int kPackThreads = 512;
 // CHAIN (gnx_block_forward_chained): the first a.prev_blocks workgroups of the launch — dispatched first, so they run beside the tiles — finish
 // the graph update of the PREVIOUS call (graph_update_rows over ITS partial rows: one workgroup for a one-graph batch, one wavefront per
 // graph otherwise), the rest are this call's tiles.  In a loop over batches the second launch of every step disappears (an empty launch is
-// ~4 us of a ~25-us step).  A template parameter: the plain kernel keeps its registers (58 at README widths) and has no barrier.
+// ~4 us of a ~25-us step).  A template parameter: the plain kernel keeps its registers (58 at README widths) and has no barrier.  With BF16 the
+// previous call's partial rows are fp32 as always, its gf is read as bf16 and its gf_out rounded on store — k_graph_t<C, ONEG, true>'s bits.
 // (The body is a device function so that the kernel can exist under two resource limits: k_block_wave with the 80-SGPR cap that buys the eighth
 // workgroup per CU, k_block_wave_ffe without it — at its 120+ vector registers a CU holds four workgroups whatever the scalar count, and under
 // the cap that form kept ~70 scalars in lanes of a vector register: a v_readlane_b32, often with an s_nop behind it, per use.)
@@ -788,7 +790,7 @@ __device__ __forceinline__ auto phase_args(const BlockArgs& a) {
 template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK, bool FFE, bool CHAIN, bool BF16 = false>
 __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   static_assert(!(PACK && ONEG), "packs are for batches of several graphs");
-  static_assert(!BF16 || (!FFE && !CHAIN && !LN), "bf16 features: the plain block forward");
+  static_assert(!BF16 || (!FFE && !LN), "bf16 features: the plain block forward and its chained form");
   static_assert(!CHAIN || (!PACK && !FFE && !LN && OE + ON > 0), "CHAIN: the two-launch form of a plain block");
   static_assert(!FFE || (LN && DE == OE && DE > 0 && EPT == 2 && (DE + DN) * OE > 96 && ((DE + DN) * OE) % 2 == 0 && GNX_WAVE_PK && !PACK),
                 "FFE: a core's block (dims => dims) with LayerNorm on load, two edges per lane, streamed weights");
@@ -797,6 +799,9 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   constexpr int C = OE + ON, C1 = C > 0 ? C : 1;
   constexpr int WAVES = (PACK ? kPackThreads : kThreads) / 64;
   constexpr int WSL = wave_slice_floats(OE, EPT);
+  // the phases read their arguments afresh (phase_args) in the FFE form, and in the chained bf16 form of several graphs: held from the top,
+  // they took that kernel past its 80 scalar registers (4 spilled, 36 B of scratch per lane)
+  constexpr bool FRESH = FFE || (CHAIN && BF16 && !ONEG);
   __shared__ __attribute__((aligned(16))) float s_mem[WAVES * WSL];  // one slice per wave
 
   const int lane = threadIdx.x & 63;
@@ -807,15 +812,14 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
     if ((int)blockIdx.x < a.prev_blocks) {
       if (a.og > 0) {
         constexpr int CPc = (C + 3) / 4 * 4;
-        a.gf = a.prev_gf; a.gf_out = a.prev_gf_out;  // (this workgroup returns below: the kernel's own copy of the arguments is its to change)
         const float* pbase = a.prev_partials + blockIdx.y * (size_t)n_rows * CPc;
         if constexpr (ONEG) {
           // summed as k_graph_t sums them at the thread count its launcher picks for these rows (graph_update_threads): the same bits
           const int rows = (a.n_wtiles + 3) / 4;
-          graph_update_rows<C, false, 4>(a, pbase, 0, blockIdx.y, 0, rows, (int)threadIdx.x, kThreads, s_mem, graph_update_threads_for_rows(rows));
+          graph_update_rows<C, false, 4, BF16>(a, a.prev_gf, a.prev_gf_out, pbase, 0, blockIdx.y, 0, rows, (int)threadIdx.x, kThreads, s_mem, graph_update_threads_for_rows(rows));
         } else {
           const int g = (int)blockIdx.x * WAVES + wv;  // one wavefront per graph (the launcher chains only while a graph has <= 256 rows)
-          if (g < a.G) graph_update_rows<C, true, 4>(a, pbase, g, blockIdx.y, a.wtile_off[g], a.wtile_off[g + 1], lane, 64, s_mem + wv * WSL);
+          if (g < a.G) graph_update_rows<C, true, 4, BF16>(a, a.prev_gf, a.prev_gf_out, pbase, g, blockIdx.y, a.wtile_off[g], a.wtile_off[g + 1], lane, 64, s_mem + wv * WSL);
         }
       }
       return;
@@ -854,7 +858,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   for (int i = 0; i < EPT; ++i) ffv[i] = false;
   do {
   if constexpr (ONEG || PACK) { if (!active) break; }
-  const auto A0 = phase_args<FFE>(a);  // tile record, loads, LayerNorm of the node-side rows
+  const auto A0 = phase_args<FRESH>(a);  // tile record, loads, LayerNorm of the node-side rows
   float* s_out = s_mem + wv * WSL;                                        // ef' of the wave's tile
   float* s_pd = s_out + (TEW * OE + 4);                                   // per node: bias' + We[:, dst-seg]*nf[n]
   unsigned char* s_dst = reinterpret_cast<unsigned char*>(s_pd + (64 * OE + 4));  // tile-local destination of each edge
@@ -919,7 +923,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
     ln_row<DG>(gfr[0], A0->ln_g[2], A0->ln_b[2], A0->ln_eps, A0->ln_mode);
   }  // (the edge rows and the gathered rows are normalised at the start of the edge phase: their loads are still in flight)
   GNX_WSTAMP(2);  // every load issued
-  const auto A1 = phase_args<FFE>(a);  // node-side preparation + edge phase
+  const auto A1 = phase_args<FRESH>(a);  // node-side preparation + edge phase
   const cfloatp We = as_const(A1->We);
   const cfloatp be = as_const(A1->be ? A1->be : k_zero_bias);
   // ---- lanes as nodes: destination index of each in-edge, per-node part of the edge update ----
@@ -1096,7 +1100,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   }
   __builtin_amdgcn_wave_barrier();
   GNX_WSTAMP(4);  // edge phase done (needed ef rows, rowval, gathered rows; ef' stores issued)
-  const auto A2 = phase_args<FFE>(a);  // node phase
+  const auto A2 = phase_args<FRESH>(a);  // node phase
   const cfloatp Wn = as_const(A2->Wn);
   const cfloatp bn = as_const(A2->bn ? A2->bn : k_zero_bias);
 
@@ -1173,7 +1177,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
     o[7] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | __builtin_amdgcn_s_getreg((31 << 11) | 4);  // XCC_ID, HW_ID
   }
 #endif
-  const auto A3 = phase_args<FFE>(a);
+  const auto A3 = phase_args<FRESH>(a);
   if (A3->og > 0) {
     if constexpr (C > 0) {
       const size_t r = blockIdx.y;
@@ -1276,8 +1280,8 @@ __global__ void k_graph_t(BlockArgs a, int n_rows) {
   // one graph: k_block_wave stored one row per WORKGROUP (4 wave tiles); several graphs: one row per wave tile
   const int t0 = ONEG ? 0 : a.wtile_off[g], t1 = ONEG ? (a.n_wtiles + 3) / 4 : a.wtile_off[g + 1];
   const float* base = a.partials + blockIdx.y * (size_t)n_rows * CP;
-  if (blockDim.x == 64) graph_update_rows<C, true, 16, BF16>(a, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, 64, s_g);
-  else graph_update_rows<C, false, 16, BF16>(a, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
+  if (blockDim.x == 64) graph_update_rows<C, true, 16, BF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, 64, s_g);
+  else graph_update_rows<C, false, 16, BF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
 }
 
 }  // namespace gnx

@@ -330,6 +330,24 @@ typedef struct gnx_block_step {
 GNX_API int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step* steps, int64_t n_steps,
                                 int64_t n_replicas, uint32_t flags, void* stream);
 
+/* The same loop on bfloat16 feature tensors.  GNX_ELEM_F32 is exactly gnx_block_forward_steps.  With GNX_ELEM_BF16 the six feature pointers
+ * of every step point to bf16 storage (they keep their float* type in gnx_block_step) and each step's workspace_bytes is at least
+ * gnx_block_typed_workspace_bytes(h, p, n_replicas, GNX_ELEM_BF16, flags) — the query that also creates the side streams, outside any capture.
+ * Contract, for finite data: each step's outputs are bit for bit those of gnx_block_forward_typed on that step alone, the steps run in order —
+ * in every schedule (one stream, two streams, chained, replayed from a captured graph).  Where a native bf16 kernel takes the widths (the
+ * ahead-of-time sets, run-time specialised widths, the pack form) the loop runs the schedule above on bf16 rows: two streams, and step i's
+ * graph update at the front of a later launch at the bf16 ahead-of-time widths (the chained graph update reads the previous step's fp32
+ * partial rows and its bf16 gf, and rounds its gf_out as k_graph_t does); one stream under GNX_FLAG_NO_FORK, the profiler or an exhausted
+ * pool, still chained.  Every other path (matrix-core / generic widths, GNX_FLAG_FORCE_GENERIC, GNX_FLAG_NO_JIT, a failed specialisation):
+ * n_steps gnx_block_forward_typed calls in order on `stream`, each converting around the fp32 forward inside its own workspace.
+ * Refused with GNX_ERR_INVALID_ARG BEFORE ANY GPU WORK: an `elem` other than these two, GNX_FLAG_DEFER_GRAPH_UPDATE, a negative n_steps or
+ * steps == NULL with n_steps > 0, and a feature buffer of ANY step that is not 4-byte aligned.  (Unlike gnx_block_forward_steps, which reports a
+ * step's error once the steps before it have been issued.)  An error found only inside the loop (a workspace too small, a NULL input) is
+ * reported once the steps before it are issued, with the side stream joined into `stream` as in the fp32 loop.  There is no typed
+ * gnx_block_forward_chained or gnx_block_graph_update: the pending graph updates stay inside this call. */
+GNX_API int32_t gnx_block_forward_steps_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_block_step* steps,
+                                              int64_t n_steps, int64_t n_replicas, uint32_t flags, void* stream);
+
 /* ---- GNBlock with Flux `Chain`s of Dense layers as update functions (src/gnblock.jl:1-6: edgefn / nodefn / graphfn are
  * arbitrary Chains; the constructor's default is Chain(Dense), which is what gnx_block_forward fuses).  widths[i] = output
  * width of layer i; the input width of layer 0 is fixed by the block (de+2dn+dg / oe+dn+dg / oe+on+dg with oe, on = the LAST
