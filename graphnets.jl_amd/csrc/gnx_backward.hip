@@ -13,36 +13,9 @@
 // duality of nf[src] is resolved with a CSR view (out-edges per node) instead of atomics; every sum has a fixed order.
 #include <algorithm>
 
-#include "gnx_device.h"
-
-extern "C" int32_t gnx_ensure_csr(const gnx_graphs* h);
-extern "C" size_t gnx_chain_block_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R);
+#include "gnx_launchers.h"
 
 namespace gnx {
-
-// matrix-core primitives (gnx_backward_wide.hip)
-bool bw_use_mfma(size_t rows, int J, int K);     // dX
-bool bw_use_mfma_dw(size_t rows, int J, int K);  // dW
-size_t dw_mfma_partial_floats(size_t rows, int J, int K);
-int32_t dw_mfma(const float* delta, const float* X, size_t rows, int J, int K, float* dW, float* partial, hipStream_t s);
-int32_t dx_mfma(const gnx_graphs* h, int entity, const float* delta, const float* W, int J, int K, int ka, int kb, float* out, int64_t R,
-                float* WT, bool fill, hipStream_t s, const char* name, const float* gmul = nullptr, int gmul_act = 0,
-                float* tile_colsum = nullptr, int* n_tiles_out = nullptr);
-int32_t transpose_w(const float* W, int K, int J, float* WT, hipStream_t s);
-int32_t rows_times_wt(const gnx_graphs* h, int entity, const float* A, int J, const float* WT, int K, int ka, int kb, float* out, const float* add1,
-                      int64_t R, hipStream_t s, const char* name);
-int32_t segsum_rows(const float* src, const int* ptr, const int* idx, int N, int E, int D, int64_t R, float* out, hipStream_t s, const char* name);
-int32_t add_cols(const float* in, int ld, int off, size_t rows, int d, float* out, int accumulate, hipStream_t s);
-int32_t launch_dense_rows(const gnx_graphs* h, int entity, const float* A, int K, const gnx_dense& d, int OUT, const float* add1,
-                          const float* add2, float* out, int64_t R, hipStream_t s, const char* name);
-
-// csrc/gnx_dropout.hip
-bool dropout_active(const gnx_dropout* d);
-int32_t check_dropout(const gnx_dropout* d);
-int32_t launch_dropout(const gnx_dropout& d, int entity, size_t n, const float* in, float* out, int mode, hipStream_t s);
-
-int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, const float* nf, int dn, const float* gf, int dg,
-                        int64_t R, float* out, hipStream_t s);
 
 // delta[m][j] = (G[m][j] + extra1[i1(m)][o1 + j] + extra2[i2(m)][o2 + j]) * act'(out[m][j]);  one thread per element.
 // kind 0: rows = graphs (no extras); 1: rows = nodes (extra1 = dXg rows by graph); 2: rows = edges (extra1 = dXg by graph,
@@ -509,9 +482,6 @@ __global__ __launch_bounds__(256) void k_ln_backward_v4(const float* __restrict_
     }
   }
 }
-
-int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps, int eps_mode,
-                          float* y1, float* y2, hipStream_t s);
 
 // stage 2 for many slices: out[c] = sum_s partial[s][c]; 64 columns per workgroup, 4 slice groups, fixed order
 __global__ __launch_bounds__(256) void k_bw_colsum_final(const float* __restrict__ partial, int d, int S, float* __restrict__ out, int ld = 0) {

@@ -4,15 +4,12 @@
 // Both are exact fp32 (v_mfma_f32_32x32x2_f32) with a fixed summation order, like the forward.
 #include <algorithm>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_x6_mma.h"
 
 namespace gnx {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-int32_t launch_rows_matmul(const gnx_graphs* h, int entity, const float* A, int K, const float* B, int ldw, int OUT, float* out, int64_t R,
-                           hipStream_t s, const char* name, const float* gmul, int gmul_act, float* tile_colsum, int* n_tiles_out, const float* add1);
 
 // WT[j*K + k] = W[k*J + j]   (W = [K][J] row-major, i.e. the (J x K) column-major Dense weight)
 __global__ void k_transpose_w(const float* __restrict__ W, int K, int J, float* __restrict__ WT) {

@@ -2,7 +2,7 @@
 // (matrix-core / generic widths, GNX_FLAG_FORCE_GENERIC, GNX_FLAG_NO_JIT, a failed run-time specialisation): the inputs are widened into
 // fp32 staging buffers of the workspace, gnx_block_forward runs on them, the outputs are rounded to bf16 (nearest even).  Widening is exact,
 // and the rounding is the one the fused kernels apply on store (pack_bf16 / to_bf16 of gnx_wave_kernel.h): every path gives the same bits.
-#include "gnx_internal.h"
+#include "gnx_launchers.h"
 #include "gnx_wave_kernel.h"
 
 namespace gnx {

@@ -10,7 +10,7 @@
 #include <mutex>
 #include <thread>
 
-#include "gnx_internal.h"
+#include "gnx_launchers.h"
 
 namespace gnx {
 

@@ -13,14 +13,7 @@
 // Semantics are exactly (m::GNBlock)(x) of src/gnblock.jl:63-69 with Chain update functions; zero-width outputs -> `nothing`.
 #include <algorithm>
 
-#include "gnx_internal.h"
-
-namespace gnx {
-int32_t launch_dense_rows(const gnx_graphs* h, int entity, const float* A, int K, const gnx_dense& d, int OUT, const float* add1,
-                          const float* add2, float* out, int64_t R, hipStream_t s, const char* name);
-int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, const float* nf, int dn, const float* gf, int dg,
-                        int64_t R, float* out, hipStream_t s);
-}  // namespace gnx
+#include "gnx_launchers.h"
 
 using namespace gnx;
 

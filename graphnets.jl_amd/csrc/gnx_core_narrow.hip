@@ -6,7 +6,7 @@
 //                    hand-streamed scalar operands of packed FMAs (k_core_post_s; two rows per thread).
 // At d = 10 a wave-per-row kernel keeps 54 of 64 lanes idle and the hidden tile bounced through LDS; here a row is
 // D registers of one lane and the kernel is a pure stream: x in, (block_out in,) out.
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_wave_kernel.h"  // load_row / store_row / fma_rows / act_row
 #include "gnx_core_post_kernel.h"  // k_core_post / k_core_post_s / k_core_post3 (also compiled at run time for other width triples)
 
@@ -81,8 +81,6 @@ int32_t launch_core_post(const float* x, size_t rows, int d, const gnx_layernorm
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
-
-int32_t jit_get_core_post3(int d0, int d1, int d2, hipStream_t s, hipFunction_t* fn);  // gnx_jit.cpp
 
 // One launch for the three entities of a core: the edge and node levels have rows to spare (two rows per thread), the activations are
 // identity / relu and the combined kernel exists for the width triple — ahead of time for README ex.3's (10,5,3), specialised at run

@@ -16,13 +16,9 @@
 // the same intermediates anyway, and the inference kernels stay free of a mask operand.
 #include <algorithm>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 
 namespace gnx {
-int32_t launch_dense_rows(const gnx_graphs* h, int entity, const float* A, int K, const gnx_dense& d, int OUT, const float* add1,
-                          const float* add2, float* out, int64_t R, hipStream_t s, const char* name);
-int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps, int eps_mode,
-                          float* y1, float* y2, hipStream_t s);
 
 namespace {
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {

@@ -13,7 +13,7 @@
 // run boundaries are a scalar bit mask, and the tile's column sums are the sums of the run sums.  No LDS staging, no barrier per slice
 // (round 4's form: two LDS passes and two workgroup barriers per 32-output slice — 39 % of a core tile's clocks for 11 % of its matrix work).
 #pragma once
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 
 namespace gnx {
 

@@ -16,7 +16,7 @@
 // 256 threads = 4 waves = one 128-edge tile of the handle's edge-tile table; 72 KB of LDS: two workgroups per CU.
 #include <cstdio>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_x6_stats.h"
 
 namespace gnx {

@@ -17,7 +17,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_x6_mma.h"
 
 #ifndef GNX_LN_GUARD  // see the LayerNorm branch of store_step (and csrc/gnx_wide.hip)
@@ -353,10 +353,6 @@ bool ffn_fused_applies(const float* z, int d, const gnx_ffn& ff, const float* ad
   const uintptr_t al = (uintptr_t)z | (uintptr_t)ff.fc1.weight | (uintptr_t)ff.fc2.weight | (uintptr_t)ff.fc2.bias | (uintptr_t)add1 | (uintptr_t)add2 | (uintptr_t)out;
   return (al & 15) == 0;
 }
-
-bool ffn_x6_applies(const float* z, int d, const gnx_ffn& ff, const float* add1, const float* add2, const float* out, size_t scratch_bytes);  // gnx_ffn_x6.hip
-int32_t launch_ffn_x6(const float* z, size_t nrows, int d, const gnx_ffn& ff, const float* add1, const float* add2, float* out, int64_t R, hipStream_t s,
-                      const float* ln_stats, const gnx_layernorm* ln, void* scratch, bool ln_inline, float ln_eps, int ln_mode);
 
 // scratch (optional; scratch_bytes of device memory the caller does not need until this launch has run): lets the edge FeedForward at d = 128 run
 // as k_ffn_x6 — the fp32 products carried by six bf16 matrix-core terms (gnx_ffn_x6.hip) — instead of the fp32-MFMA kernel below

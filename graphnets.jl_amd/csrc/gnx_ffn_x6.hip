@@ -25,7 +25,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_x6_stats.h"
 
 namespace gnx {
@@ -898,8 +898,6 @@ __global__ __launch_bounds__(64 * XW) __attribute__((amdgpu_waves_per_eu(2, D ==
 
 size_t ffn_x6_scratch_bytes(int d) { return (size_t)3 * d * 4 * d * sizeof(__bf16) * 2; }
 
-int32_t launch_fold_beta(const float* W, int ldw, int K, int n_out, const float* beta, const float* bias, float* out, hipStream_t s);  // gnx_edge_x6.hip
-
 // the folded form's scratch: the planes with (gamma . W1), then the 4 d floats of b1 + W1^T beta
 size_t ffn_x6_fold_scratch_bytes(int d) { return ffn_x6_scratch_bytes(d) + (size_t)4 * d * sizeof(float); }
 
@@ -957,9 +955,6 @@ int32_t launch_ffn_x6(const float* z, size_t nrows, int d, const gnx_ffn& ff, co
 #endif
   return GNX_OK;
 }
-
-int32_t launch_edge_x6_prep(const float* We, int ldw, void* scratch, hipStream_t s, int n_out, const float* ln_gamma, const float* ln_beta);  // gnx_edge_x6.hip
-size_t edge_x6_scratch_bytes();
 
 // A GNCore's edge rows in ONE launch (EDGE form of k_ffn_x6): out = x + ef' + FF(gn2(x)), ef' = act(We^T gn1(x) + Ps[src] + Pd[dst]) with its per-destination
 // sums (agg_out) and column sums (colsum) as k_edge_x6 writes them; ef' itself is never written.  Row statistics of x in the kernel.

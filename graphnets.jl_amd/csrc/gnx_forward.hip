@@ -4,62 +4,13 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_step_hazard.h"
 
 namespace gnx {
 
-// implemented in gnx_generic.hip / gnx_narrow.hip / gnx_wide.hip
-int32_t launch_block_generic(const BlockArgs& a, int64_t R, int tile_n_cap, hipStream_t s, int phase);
-int32_t launch_graph(const BlockArgs& a, int64_t R, hipStream_t s);
-int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps,
-                          int eps_mode, float* y1, float* y2, hipStream_t s);
-int32_t launch_ffn_residual(const float* z, const float* x, size_t rows, int d, const gnx_ffn& ff, float* out, hipStream_t s);
-int32_t launch_pad(const gnx_graphs* h, int kind, bool pad, const float* src, int d, int64_t R, float* dst, hipStream_t s);
-int32_t launch_calibration(int n, hipStream_t s);
-int xent_blocks(int64_t cols);
-int32_t launch_xent_backward(const float* logits, const float* targets, int d, int64_t cols, const float* upstream, float* dl, hipStream_t s);
-int32_t launch_xent(const float* logits, const float* targets, int d, int64_t cols, float* out, float* ws, hipStream_t s);
-int32_t launch_collapse(const gnx_graphs* h, const float* ef, int d, int64_t R, float* out, hipStream_t s);
-int32_t launch_collapse_padded(const gnx_graphs* h, const float* ef, int d, int64_t R, float* out, hipStream_t s);
-int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, const float* nf, int dn, const float* gf, int dg,
-                        int64_t R, float* out, hipStream_t s);
-// returns 1 when the path does not apply to these dims (caller falls through to the next path)
-// phase bit 1: edge + node update (leaves per-tile partial sums in the workspace); bit 2: graph update from them
-int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
-void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p, bool bf16 = false);
-bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
-bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1, int act2);
-bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16 = false);
-bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16 = false);
-int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);  // 1: no fused bf16 kernel for these widths
-int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
-int32_t launch_block_narrow_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
 static_assert(GNX_ACT_IDENTITY == 0 && GNX_ACT_RELU == 1 && GNX_ACT_TANH == 2 && GNX_ACT_SIGMOID == 3 && GNX_ACT_GELU == 4,
               "act_apply (gnx_device.h) hard-codes the activation codes");
-int32_t launch_block_wide(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
-size_t wide_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R);
-void warm_block_wide(const gnx_graphs* h, const gnx_block_params* p, bool rows_gemm);
-// narrow-width GNCore kernels (gnx_core_narrow.hip)
-bool core_narrow_width(int d);
-int32_t launch_ln1_rows(const float* x, size_t rows, int d, const gnx_layernorm& l1, float eps, int eps_mode, float* y, hipStream_t s);
-int32_t launch_ffn_fused(const gnx_graphs* h, int entity, const float* z, int d, const gnx_ffn& ff, const float* add1, const float* add2, float* out,
-                         int64_t R, hipStream_t s, const float* ln_stats = nullptr, const gnx_layernorm* ln = nullptr, void* scratch = nullptr, size_t scratch_bytes = 0,
-                         bool ln_inline = false, float ln_eps = 0.f, int ln_mode = 0);
-bool ffn_x6_applies(const float* z, int d, const gnx_ffn& ff, const float* add1, const float* add2, const float* out, size_t scratch_bytes);  // gnx_ffn_x6.hip
-bool block_wide_edge_x6_applies(const gnx_graphs* h, const BlockArgs& a);  // gnx_wide.hip
-bool edge_n_enabled();  // gnx_edge_n.hip
-bool ffn_fused_applies(const float* z, int d, const gnx_ffn& ff, const float* add1, const float* add2, const float* out);
-bool block_wide_ln_applies(const gnx_graphs* h, const BlockArgs& a);
-bool ln_stats_applies(const float* x, int d);
-int32_t launch_ln_stats(const float* x, size_t rows, int d, float eps, int eps_mode, float* stats, hipStream_t s);
-bool core_post3_applies(const size_t rows[3], const int d[3], const gnx_ffn ff[3], bool deferred, hipStream_t s);
-int32_t launch_core_post3(const float* const x[3], const size_t rows[3], const int d[3], const gnx_layernorm l2[3], const gnx_ffn ff[3], float eps,
-                          int eps_mode, float* const out[3], hipStream_t s, const BlockArgs* blk, int n_rows, bool skip_edges = false);
-int32_t launch_core_post(const float* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode,
-                         float* out, hipStream_t s);
-int32_t launch_dense_rows(const gnx_graphs* h, int entity, const float* A, int K, const gnx_dense& d, int OUT, const float* add1,
-                          const float* add2, float* out, int64_t R, hipStream_t s, const char* name);
 
 static int32_t check_block(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
   if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
@@ -100,148 +51,183 @@ static BlockWs block_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t 
   return w;
 }
 
-// ln1 (optional, 3 entries): LayerNorm applied to the inputs on load — only together with *fused_ln: the caller passes a bool
-// that is set when the fused narrow kernel took the call; otherwise nothing was launched and the caller must normalise itself.
-static int32_t block_forward_impl(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf,
-                                  const float* gf, int64_t R, float* ef_out, float* nf_out, float* gf_out, void* ws,
-                                  size_t ws_bytes, uint32_t flags, hipStream_t s, int phase = 3, const gnx_layernorm* ln1 = nullptr,
-                                  float ln_eps = 0.f, int ln_mode = 0, bool* fused_ln = nullptr, const float* const* wide_ln_stats = nullptr,
-                                  BlockArgs* args_out = nullptr, const gnx_ffn* ffe = nullptr, const gnx_layernorm* ffe_ln2 = nullptr, bool* ffe_took = nullptr,
-                                  const gnx_pending_update* chain_prev = nullptr, bool* chain_took = nullptr, bool* edge_x6_out = nullptr, bool ln_inline_e = false,
-                                  void* ffe_scratch = nullptr, bool bf16 = false) {
-  FormScope forms(flags);  // the forms this call selected (gnx.h: GNX_FLAG_FFN_FP32 ...) for every dispatch predicate below
-  PreparedScope prepared(p ? p->prepared : nullptr);  // the layer's prepared weight planes, if the caller made them (a core passes its own through its block)
-  int32_t rc = check_block(h, p, R);
-  if (rc) return rc;
-  if (phase & 1) {
+// ---- one block forward: the call record, its validation, and one function per FORM of the forward ----
+// What an entry point asks of the block kernels.  Every form below takes the record plus only what that form needs.
+struct BlockCall {
+  const gnx_graphs* h;
+  const gnx_block_params* p;
+  int32_t elem;  // GNX_ELEM_F32 / GNX_ELEM_BF16: what the six feature pointers point to
+  const void *ef, *nf, *gf;
+  int64_t R;
+  void *ef_out, *nf_out, *gf_out;
+  void* ws;
+  size_t ws_bytes;
+  uint32_t flags;
+  hipStream_t s;
+  int phase;  // GNX_PHASE_* (gnx_internal.h)
+  // the same call on another stream and phase / on other inputs
+  BlockCall on(hipStream_t stream, int ph) const { BlockCall c = *this; c.s = stream; c.phase = ph; return c; }
+  BlockCall with(const void* e, const void* n, const void* g) const { BlockCall c = *this; c.ef = e; c.nf = n; c.gf = g; return c; }
+};
+
+// check_block, then the buffers the call's phases read and write
+static int32_t check_call(const BlockCall& c) {
+  if (const int32_t rc = check_block(c.h, c.p, c.R)) return rc;
+  const gnx_graphs* h = c.h;
+  const gnx_block_params* p = c.p;
+  if (c.phase & GNX_PHASE_EDGE_NODE) {
     // a batch without a single edge has (DE, 0) edge features: its (empty) buffers may be NULL
-    if ((p->de > 0 && !ef && h->E > 0) || (p->dn > 0 && !nf) || (p->dg > 0 && !gf))
+    if ((p->de > 0 && !c.ef && h->E > 0) || (p->dn > 0 && !c.nf) || (p->dg > 0 && !c.gf))
       return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL (width 0 <=> nothing)");
-    if ((p->oe > 0 && !ef_out && h->E > 0) || (p->on > 0 && !nf_out))
+    // (a whole bf16 call counts gf_out among the outputs: the wording of the bf16 entry points, which refuse everything before a launch)
+    const bool typed_whole = c.elem == GNX_ELEM_BF16 && (c.phase & GNX_PHASE_GRAPH);
+    if ((p->oe > 0 && !c.ef_out && h->E > 0) || (p->on > 0 && !c.nf_out) || (typed_whole && p->og > 0 && !c.gf_out))
       return fail(GNX_ERR_INVALID_ARG, "an output with non-zero width is NULL");
   }
-  if (phase & 2) {
-    if ((p->dg > 0 && !gf) || (p->og > 0 && !gf_out)) return fail(GNX_ERR_INVALID_ARG, "gf / gf_out is NULL");
-  }
-  const BlockWs w = block_ws(h, p, R);
-  if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_workspace_bytes()");
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  if ((c.phase & GNX_PHASE_GRAPH) && ((p->dg > 0 && !c.gf) || (p->og > 0 && !c.gf_out))) return fail(GNX_ERR_INVALID_ARG, "gf / gf_out is NULL");
+  return GNX_OK;
+}
 
-  BlockArgs a{};
-  a.de = p->de; a.dn = p->dn; a.dg = p->dg;
-  a.oe = p->oe; a.on = p->on; a.og = p->og;
-  a.We = p->edgefn.weight; a.be = p->edgefn.bias; a.act_e = p->edgefn.act;
-  a.Wn = p->nodefn.weight; a.bn = p->nodefn.bias; a.act_n = p->nodefn.act;
-  a.Wg = p->graphfn.weight; a.bg = p->graphfn.bias; a.act_g = p->graphfn.act;
-  a.ef = p->de ? ef : nullptr; a.nf = p->dn ? nf : nullptr; a.gf = p->dg ? gf : nullptr;
-  a.ef_out = ef_out; a.nf_out = nf_out; a.gf_out = gf_out;
-  a.agg = reinterpret_cast<float*>(static_cast<char*>(ws) + w.agg_off);
-  a.partials = reinterpret_cast<float*>(static_cast<char*>(ws) + w.part_off);
-  a.colptr = h->d_colptr; a.rowval = h->d_rowval; a.node_off = h->d_node_off; a.edge_off = h->d_edge_off;
-  a.tile_off = h->d_tile_off; a.tiles = h->d_tiles;
-  a.wtile_off = h->d_wtile_off; a.wtiles = h->d_wtiles; a.n_wtiles = (int)h->n_wtiles();
-  a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G; a.n_tiles = (int)h->n_tiles();
-  a.packs = h->d_packs; a.n_packs = h->n_packs;
+// A validated call — the ONE place that validates a call and fills the kernels' argument block: the scopes every form opens first (the forms
+// this call selected, gnx.h: GNX_FLAG_FFN_FP32 ..., for every dispatch predicate; the layer's prepared weight planes, if the caller made them —
+// a core passes its own through its block), then rc == GNX_OK and the arguments + workspace carve, or the error.
+struct Prepared {
+  FormScope forms;
+  PreparedScope planes;
+  BlockArgs a;
+  BlockWs w;
+  int32_t rc;
+  explicit Prepared(const BlockCall& c) : forms(c.flags), planes(c.p ? c.p->prepared : nullptr), rc(fill(c)) {}
+  int32_t fill(const BlockCall& c) {
+    const gnx_graphs* h = c.h;
+    const gnx_block_params* p = c.p;
+    if (const int32_t bad = check_call(c)) return bad;
+    w = block_ws(h, p, c.R);
+    if (!c.ws || c.ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_workspace_bytes()");
+    if (((uintptr_t)c.ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    a = block_probe(h, p);
+    a.We = p->edgefn.weight; a.be = p->edgefn.bias; a.act_e = p->edgefn.act;
+    a.Wn = p->nodefn.weight; a.bn = p->nodefn.bias; a.act_n = p->nodefn.act;
+    a.Wg = p->graphfn.weight; a.bg = p->graphfn.bias; a.act_g = p->graphfn.act;
+    // (bf16 rows travel in the float* fields: only the native bf16 kernels read them, as what they are)
+    a.ef = p->de ? static_cast<const float*>(c.ef) : nullptr; a.nf = p->dn ? static_cast<const float*>(c.nf) : nullptr; a.gf = p->dg ? static_cast<const float*>(c.gf) : nullptr;
+    a.ef_out = static_cast<float*>(c.ef_out); a.nf_out = static_cast<float*>(c.nf_out); a.gf_out = static_cast<float*>(c.gf_out);
+    a.agg = reinterpret_cast<float*>(static_cast<char*>(c.ws) + w.agg_off);
+    a.partials = reinterpret_cast<float*>(static_cast<char*>(c.ws) + w.part_off);
+    a.colptr = h->d_colptr; a.rowval = h->d_rowval; a.node_off = h->d_node_off; a.edge_off = h->d_edge_off;
+    a.tile_off = h->d_tile_off; a.tiles = h->d_tiles;
+    a.wtile_off = h->d_wtile_off; a.wtiles = h->d_wtiles; a.n_tiles = (int)h->n_tiles();
+    a.packs = h->d_packs; a.n_packs = h->n_packs;
+    return GNX_OK;
+  }
+};
 
-  if (ln1 && wide_ln_stats) {
-    // matrix-core path with ef / nf normalised on load from their row statistics (gf arrives normalised).  wide_ln_stats[0] == nullptr:
-    // only ASK whether this block takes that form (nothing is launched)
-    for (int t = 0; t < 2; ++t) { a.ln_g[t] = ln1[t].gamma; a.ln_b[t] = ln1[t].beta; }
-    *fused_ln = !(flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA)) && block_wide_ln_applies(h, a);
-    if (edge_x6_out) *edge_x6_out = *fused_ln && block_wide_edge_x6_applies(h, a);  // (the caller may then leave the edge rows' statistics to that kernel)
-    if (!*fused_ln || !wide_ln_stats[0]) return GNX_OK;
-    a.ln_stats[0] = wide_ln_stats[0]; a.ln_stats[1] = wide_ln_stats[1];
-    if (ln_inline_e) { a.ln_stats[0] = nullptr; a.ln_inline_e = 1; a.ln_eps = ln_eps; a.ln_mode = ln_mode; }  // no table for the edges: k_edge_x6 computes them in registers
-    if (ln_inline_e && ffe && ffe_ln2 && ffe_scratch && (phase & 1)) {  // ... and the edge FeedForward + residuals run in that launch too: ef_out receives the CORE's edge output
-      a.ffe_w1 = ffe->fc1.weight; a.ffe_b1 = ffe->fc1.bias; a.ffe_w2 = ffe->fc2.weight; a.ffe_b2 = ffe->fc2.bias;
-      a.ffe_g2 = ffe_ln2->gamma; a.ffe_be2 = ffe_ln2->beta; a.ffe_act1 = ffe->fc1.act; a.ffe_act2 = ffe->fc2.act; a.ffe_scratch = ffe_scratch;
-    }
-    return launch_block_wide(h, a, R, s, phase);
-  }
-  if (ln1) {
-    *fused_ln = false;
-    if (flags & GNX_FLAG_FORCE_GENERIC) return GNX_OK;
-    for (int t = 0; t < 3; ++t) { a.ln_g[t] = ln1[t].gamma; a.ln_b[t] = ln1[t].beta; }
-    a.ln_eps = ln_eps; a.ln_mode = ln_mode;
-    if (!block_narrow_ready(h, a, s)) return GNX_OK;  // nothing launched: the caller runs gn1 as its own kernels
-    *fused_ln = true;
-    if (ffe && ffe_ln2 && ffe_took && (phase & 1) && block_narrow_ffe_applies(h, a, ffe->fc1.act, ffe->fc2.act)) {
-      // narrow core: the edge FeedForward and both residual terms run in the block kernel's edge lanes — ef_out receives the CORE's output
-      a.ffe_w1 = ffe->fc1.weight; a.ffe_b1 = ffe->fc1.bias; a.ffe_w2 = ffe->fc2.weight; a.ffe_b2 = ffe->fc2.bias;
-      a.ffe_g2 = ffe_ln2->gamma; a.ffe_be2 = ffe_ln2->beta; a.ffe_act1 = ffe->fc1.act; a.ffe_act2 = ffe->fc2.act;
-      *ffe_took = true;
-    }
-    if (args_out) *args_out = a;
-    return launch_block_narrow(h, a, R, s, phase);
-  }
-  if (chain_took) {  // gnx_block_forward_chained (bf16: a step of gnx_block_forward_steps_typed): this call's edge + node update with the previous
-                     // call's graph update at the front of the launch
-    *chain_took = !(flags & (GNX_FLAG_FORCE_GENERIC)) && block_narrow_chain_applies(h, a, bf16);
-    if (!*chain_took) return GNX_OK;  // nothing launched: the caller runs the plain form
-    if (chain_prev && chain_prev->workspace) {
-      a.prev_partials = reinterpret_cast<const float*>(static_cast<const char*>(chain_prev->workspace) + w.part_off);
-      a.prev_gf = chain_prev->gf; a.prev_gf_out = chain_prev->gf_out;
-    }
-    return bf16 ? launch_block_narrow_chained_bf16(h, a, R, s) : launch_block_narrow_chained(h, a, R, s);
-  }
-  if (bf16) {  // gnx_block_forward_typed: the six feature pointers are bf16; only the fused kernels read them natively (the caller checked)
-    rc = launch_block_narrow_bf16(h, a, R, s, phase);
+// The plain GNBlock.  fp32 rows: the fused narrow kernel, else the matrix-core kernels, else the generic ones.  bf16 rows: only the fused
+// kernels read them natively (the caller checked that one takes these widths: typed_native).
+static int32_t block_plain(const BlockCall& c) {
+  Prepared q(c);
+  if (q.rc) return q.rc;
+  if (c.elem == GNX_ELEM_BF16) {
+    const int32_t rc = launch_block_narrow(c.h, q.a, c.R, c.s, c.phase, true);
     return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: no fused bf16 kernel for these widths") : rc;
   }
-  if (!(flags & GNX_FLAG_FORCE_GENERIC)) {
-    rc = launch_block_narrow(h, a, R, s, phase);  // fused wave-per-tile kernel: ahead-of-time width sets, else specialised at run time
+  if (!(c.flags & GNX_FLAG_FORCE_GENERIC)) {
+    int32_t rc = launch_block_narrow(c.h, q.a, c.R, c.s, c.phase);  // fused wave-per-tile kernel: ahead-of-time width sets, else specialised at run time
     if (rc != 1) return rc;
-    if (!(flags & GNX_FLAG_NO_MFMA)) {
-      rc = launch_block_wide(h, a, R, s, phase);  // fp32 MFMA gathered-row GEMMs
+    if (!(c.flags & GNX_FLAG_NO_MFMA)) {
+      rc = launch_block_wide(c.h, q.a, c.R, c.s, c.phase);  // fp32 MFMA gathered-row GEMMs
       if (rc != 1) return rc;
     }
   }
-  return launch_block_generic(a, R, h->tile_n_cap, s, phase);
+  return launch_block_generic(q.a, c.R, c.h->tile_n_cap, c.s, c.phase);
 }
 
-}  // namespace gnx
-
-extern "C" int32_t gnx_ensure_collapse(const gnx_graphs* h);
-
-using namespace gnx;
-
-static void ensure_aux(const gnx_graphs* h);
-
-extern "C" {
-
-size_t gnx_block_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  if (!h || !p || R <= 0) return 0;
-  if (check_block(h, p, R) == GNX_OK) {
-    warm_block_narrow(h, p);        // run-time specialisation happens here, not in a capture
-    warm_block_wide(h, p, false);   // ... and so does the build of the matrix-core tables when these widths take that path
+// The chained step: this call's edge + node update with the previous call's graph update (`prev`, may be NULL) at the front of the launch.
+// took == false: these widths do not chain and nothing was launched — the caller runs the plain form.
+static int32_t block_chained(const BlockCall& c, const gnx_pending_update* prev, bool& took) {
+  took = false;
+  Prepared q(c);
+  if (q.rc) return q.rc;
+  const bool bf16 = c.elem == GNX_ELEM_BF16;
+  took = !(c.flags & GNX_FLAG_FORCE_GENERIC) && block_narrow_chain_applies(c.h, q.a, bf16);
+  if (!took) return GNX_OK;
+  if (prev && prev->workspace) {
+    q.a.prev_partials = reinterpret_cast<const float*>(static_cast<const char*>(prev->workspace) + q.w.part_off);
+    q.a.prev_gf = prev->gf; q.a.prev_gf_out = prev->gf_out;
   }
-  ensure_aux(h);  // the side streams of gnx_block_forward_steps' two-stream schedule (created outside any capture)
-  return block_ws(h, p, R).total;
+  return launch_block_narrow_chained(c.h, q.a, c.R, c.s, bf16);
 }
 
-int32_t gnx_block_forward(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
-                          int64_t R, float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags,
-                          void* stream) {
-  DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
-  return block_forward_impl(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream,
-                            (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) ? 1 : 3);
+// the edge FeedForward of a GNCore inside the block's edge launch: ef_out then receives the CORE's edge output
+static void set_edge_ffn(BlockArgs& a, const gnx_ffn& ff, const gnx_layernorm& ln2) {
+  a.ffe_w1 = ff.fc1.weight; a.ffe_b1 = ff.fc1.bias; a.ffe_w2 = ff.fc2.weight; a.ffe_b2 = ff.fc2.bias;
+  a.ffe_g2 = ln2.gamma; a.ffe_be2 = ln2.beta; a.ffe_act1 = ff.fc1.act; a.ffe_act2 = ff.fc2.act;
 }
 
-}  // extern "C"
+// Narrow GNCore: the fused narrow kernel applies LayerNorm ln1 (3 entries) to its inputs as it loads them.  took == false: that kernel is not
+// available for these widths, nothing was launched and the caller normalises itself.  `ffe` (may be NULL: not offered) + ffe_ln2: the edge
+// FeedForward and both residual terms run in the block kernel's edge lanes when they can (ffe_took).
+struct NarrowLnResult {
+  bool took = false, ffe_took = false;
+  BlockArgs args{};  // took: the block's arguments as launched (k_core_post3 finishes a deferred graph update from them)
+};
+static int32_t block_narrow_ln(const BlockCall& c, const gnx_layernorm* ln1, float ln_eps, int ln_mode, const gnx_ffn* ffe, const gnx_layernorm& ffe_ln2,
+                               NarrowLnResult& r) {
+  r.took = r.ffe_took = false;
+  Prepared q(c);
+  if (q.rc || (c.flags & GNX_FLAG_FORCE_GENERIC)) return q.rc;
+  BlockArgs& a = q.a;
+  for (int t = 0; t < 3; ++t) { a.ln_g[t] = ln1[t].gamma; a.ln_b[t] = ln1[t].beta; }
+  a.ln_eps = ln_eps; a.ln_mode = ln_mode;
+  if (!block_narrow_ready(c.h, a, c.s)) return GNX_OK;  // nothing launched: the caller runs gn1 as its own kernels
+  r.took = true;
+  r.ffe_took = ffe && (c.phase & GNX_PHASE_EDGE_NODE) && block_narrow_ffe_applies(c.h, a, ffe->fc1.act, ffe->fc2.act);
+  if (r.ffe_took) set_edge_ffn(a, *ffe, ffe_ln2);
+  r.args = a;
+  return launch_block_narrow(c.h, a, c.R, c.s, c.phase);
+}
+
+// Matrix-core GNCore: ef / nf normalised on load from their row statistics (gf arrives normalised).  Two functions: ASK whether this block
+// takes that form (launches nothing), and RUN a phase of it.  Both decide with gamma / beta of ef and nf in the arguments:
+static bool wide_ln_applies(const BlockCall& c, const gnx_layernorm* ln1, BlockArgs& a) {
+  for (int t = 0; t < 2; ++t) { a.ln_g[t] = ln1[t].gamma; a.ln_b[t] = ln1[t].beta; }
+  return !(c.flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA)) && block_wide_ln_applies(c.h, a);
+}
+// edge_x6: ... and its edge update is k_edge_x6 (the caller may then leave the edge rows' statistics to that kernel)
+static int32_t block_wide_ln_ask(const BlockCall& c, const gnx_layernorm* ln1, bool& applies, bool& edge_x6) {
+  applies = edge_x6 = false;
+  Prepared q(c);
+  if (q.rc) return q.rc;
+  applies = wide_ln_applies(c, ln1, q.a);
+  edge_x6 = applies && block_wide_edge_x6_applies(c.h, q.a);
+  return GNX_OK;
+}
+// how a run treats the edge rows
+struct WideLnEdges {
+  bool inline_stats = false;  // no statistics table for the edges: k_edge_x6 computes them in registers
+  // ... and then (all three set, a phase with GNX_PHASE_EDGE_NODE) the edge FeedForward + residuals run in that launch too
+  const gnx_ffn* ffe = nullptr;
+  const gnx_layernorm* ffe_ln2 = nullptr;
+  void* ffe_scratch = nullptr;
+};
+// stats: the row statistics of ef and nf (an entry may be NULL: that input is used as it is).  took == false: the block declined, nothing launched.
+static int32_t block_wide_ln_run(const BlockCall& c, const gnx_layernorm* ln1, float ln_eps, int ln_mode, const float* const stats[2], const WideLnEdges& e,
+                                 bool& took) {
+  took = false;
+  Prepared q(c);
+  if (q.rc || !(took = wide_ln_applies(c, ln1, q.a))) return q.rc;
+  BlockArgs& a = q.a;
+  a.ln_stats[0] = stats[0]; a.ln_stats[1] = stats[1];
+  if (e.inline_stats) { a.ln_stats[0] = nullptr; a.ln_inline_e = 1; a.ln_eps = ln_eps; a.ln_mode = ln_mode; }
+  if (e.inline_stats && e.ffe && e.ffe_ln2 && e.ffe_scratch && (c.phase & GNX_PHASE_EDGE_NODE)) { set_edge_ffn(a, *e.ffe, *e.ffe_ln2); a.ffe_scratch = e.ffe_scratch; }
+  return launch_block_wide(c.h, a, c.R, c.s, c.phase);
+}
 
 // ---- bfloat16 features (gnx_block_forward_typed) ----
-namespace gnx {
-int32_t launch_bf16_widen(const void* src, size_t n, float* dst, hipStream_t s);  // gnx_bf16.hip
-int32_t launch_bf16_round(const float* src, size_t n, void* dst, hipStream_t s);
-
 // Does a fused kernel read and write bf16 rows for these widths under the call's forms (FormScope open)?  A run-time specialisation counts
 // once it is loaded (gnx_block_typed_workspace_bytes loads it; never inside a capture).
 static bool typed_native(const gnx_graphs* h, const gnx_block_params* p, uint32_t flags, hipStream_t s) {
-  if (flags & GNX_FLAG_FORCE_GENERIC) return false;
-  BlockArgs a{};
-  a.de = p->de; a.dn = p->dn; a.dg = p->dg; a.oe = p->oe; a.on = p->on; a.og = p->og;
-  a.n_wtiles = (int)h->n_wtiles(); a.E = (int)h->E; a.G = (int)h->G;
-  return block_narrow_takes(h, a, s, true);
+  return !(flags & GNX_FLAG_FORCE_GENERIC) && block_narrow_takes(h, block_probe(h, p), s, true);
 }
 
 // workspace of a bf16 call: gnx_block_forward's, then (fallback only) fp32 staging of the six tensors, each carve 256-B aligned
@@ -262,9 +248,78 @@ static TypedWs typed_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t 
   w.total = native ? w.base : o;
   return w;
 }
+
+// side stream + fork / join events of the handle (see gnx_internal.h); failure just leaves the core on one stream
+static void ensure_aux(const gnx_graphs* h) {
+  std::call_once(h->aux_once, [h]() {
+    // the streams and their events belong to the HANDLE's device, whatever device is current in the querying thread
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev != h->device ? prev : -1};
+    if (prev != h->device && hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return; }
+    for (auto& ax : h->aux) {
+      hipStream_t st = nullptr;
+      hipEvent_t e1 = nullptr, e2 = nullptr;
+      hipEvent_t es[4] = {};
+      bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess &&
+                hipEventCreateWithFlags(&e2, hipEventDisableTiming) == hipSuccess;
+      for (auto& e : es) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+      if (ok) {
+        ax.stream = st; ax.fork = e1; ax.join = e2;
+        for (int j = 0; j < 4; ++j) ax.step[j] = es[j];
+      } else {
+        for (hipEvent_t e : es)
+          if (e) (void)hipEventDestroy(e);
+        if (e1) (void)hipEventDestroy(e1);
+        if (e2) (void)hipEventDestroy(e2);
+        if (st) (void)hipStreamDestroy(st);
+        (void)hipGetLastError();
+        break;
+      }
+    }
+  });
+}
+
+// A free side-stream set of the handle's pool (gnx_internal.h: AuxSet), held while the caller enqueues its work: a second host thread in that
+// section — same handle, another stream, other buffers — takes the next set; set == NULL (every set taken, or none created): the caller runs
+// everything on its own stream.  need_step_events: only a set that has the ring of per-step events.
+struct AuxHold {
+  std::unique_lock<std::mutex> lock;
+  const gnx_graphs::AuxSet* set = nullptr;
+};
+static AuxHold take_aux(const gnx_graphs* h, bool need_step_events) {
+  AuxHold hold;
+  for (auto& ax : h->aux) {
+    if (!ax.stream || (need_step_events && !ax.step[3])) break;
+    std::unique_lock<std::mutex> lk(ax.mu, std::try_to_lock);
+    if (lk.owns_lock()) { hold.lock = std::move(lk); hold.set = &ax; break; }
+  }
+  return hold;
+}
+
 }  // namespace gnx
 
+using namespace gnx;
+
 extern "C" {
+
+size_t gnx_block_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  if (!h || !p || R <= 0) return 0;
+  if (check_block(h, p, R) == GNX_OK) {
+    warm_block_narrow(h, p);        // run-time specialisation happens here, not in a capture
+    warm_block_wide(h, p, false);   // ... and so does the build of the matrix-core tables when these widths take that path
+  }
+  ensure_aux(h);  // the side streams of gnx_block_forward_steps' two-stream schedule (created outside any capture)
+  return block_ws(h, p, R).total;
+}
+
+int32_t gnx_block_forward(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
+                          int64_t R, float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags,
+                          void* stream) {
+  DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
+  return block_plain(BlockCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream,
+                               (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL});
+}
 
 size_t gnx_block_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem, uint32_t flags) {
   if (elem == GNX_ELEM_F32) return gnx_block_workspace_bytes(h, p, R);
@@ -287,12 +342,9 @@ int32_t gnx_block_forward_typed(const gnx_graphs* h, const gnx_block_params* p, 
   if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "GNX_FLAG_DEFER_GRAPH_UPDATE is not supported with bf16 features");
   const hipStream_t s = (hipStream_t)stream;
   FormScope forms(flags);
-  int32_t rc = check_block(h, p, R);
+  BlockCall call{h, p, GNX_ELEM_BF16, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, s, GNX_PHASE_ALL};
+  int32_t rc = check_call(call);
   if (rc) return rc;
-  if ((p->de > 0 && !ef && h->E > 0) || (p->dn > 0 && !nf) || (p->dg > 0 && !gf))
-    return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL (width 0 <=> nothing)");
-  if ((p->oe > 0 && !ef_out && h->E > 0) || (p->on > 0 && !nf_out) || (p->og > 0 && !gf_out))
-    return fail(GNX_ERR_INVALID_ARG, "an output with non-zero width is NULL");
   const void* bufs[6] = {ef, nf, gf, ef_out, nf_out, gf_out};
   for (const void* b : bufs)
     if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
@@ -302,9 +354,8 @@ int32_t gnx_block_forward_typed(const gnx_graphs* h, const gnx_block_params* p, 
   if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   if (native) {
     DeviceTurn turn(s, false);  // (narrow widths: no matrix instruction)
-    return block_forward_impl(h, p, static_cast<const float*>(ef), static_cast<const float*>(nf), static_cast<const float*>(gf), R, static_cast<float*>(ef_out),
-                              static_cast<float*>(nf_out), static_cast<float*>(gf_out), ws, w.base, flags, s, 3, nullptr, 0.f, 0, nullptr, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, true);
+    call.ws_bytes = w.base;
+    return block_plain(call);
   }
   // every other path: widen into the workspace, the fp32 forward (its own dispatch, DeviceTurn included), round the outputs
   float* st[6];
@@ -319,30 +370,47 @@ int32_t gnx_block_forward_typed(const gnx_graphs* h, const gnx_block_params* p, 
   return GNX_OK;
 }
 
+// the graph update a call left pending (gnx_block_graph_update; a flush of the loops below): the kernels of this phase read only gf, the graph
+// function's parameters and the workspace
+static int32_t graph_update(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_pending_update& u, int64_t R, uint32_t flags, hipStream_t s) {
+  return block_plain(BlockCall{h, p, elem, nullptr, nullptr, u.gf, R, nullptr, nullptr, u.gf_out, const_cast<void*>(u.workspace), u.workspace_bytes, flags, s,
+                               GNX_PHASE_GRAPH});
+}
+
+// One step of a chain of calls (gnx_block_forward_chained; a step of the loops below), `c` the whole step: chained where these widths chain —
+// prev's graph update rides in this launch, this step's is left in *pending — else prev finished the plain way, the step run whole, nothing
+// pending (matrix-core / generic kernels, run-time specialised widths, batches of small graphs whose graph update already runs inside the
+// block kernel).  The exported pending-update record has float* fields and no element type: a bf16 step exists inside the loop only, validates
+// before any launch, and its whole-step form is gnx_block_forward_typed.
+static int32_t chained_step(const BlockCall& c, const gnx_pending_update* prev, gnx_pending_update* pending) {
+  const bool bf16 = c.elem == GNX_ELEM_BF16;
+  int32_t rc = bf16 ? check_call(c) : GNX_OK;
+  if (rc) return rc;
+  if (prev && prev->workspace && (prev->workspace == c.ws || (c.p && c.p->og > 0 && prev->gf_out == c.gf_out)))
+    return fail(GNX_ERR_INVALID_ARG, bf16 ? "internal: the pending step's workspace / gf_out is this step's"
+                                          : "the pending call's workspace / gf_out must not be this call's (its graph update has not run yet)");
+  bool took = false;
+  rc = block_chained(c.on(c.s, GNX_PHASE_EDGE_NODE), prev, took);
+  if (rc) return rc;
+  if (took) {
+    *pending = gnx_pending_update{c.ws, c.ws_bytes, static_cast<const float*>(c.gf), static_cast<float*>(c.gf_out)};
+    return GNX_OK;
+  }
+  if (prev && prev->workspace) {
+    rc = graph_update(c.h, c.p, c.elem, *prev, c.R, c.flags, c.s);
+    if (rc) return rc;
+  }
+  *pending = gnx_pending_update{};
+  return bf16 ? gnx_block_forward_typed(c.h, c.p, GNX_ELEM_BF16, c.ef, c.nf, c.gf, c.R, c.ef_out, c.nf_out, c.gf_out, c.ws, c.ws_bytes, c.flags, c.s) : block_plain(c);
+}
+
 int32_t gnx_block_forward_chained(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R, float* ef_out,
                                   float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream, const gnx_pending_update* prev,
                                   gnx_pending_update* pending) {
   if (!pending) return fail(GNX_ERR_INVALID_ARG, "pending is NULL");
   DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));
   if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_chained defers the graph update itself");
-  if (prev && prev->workspace && (prev->workspace == ws || (p && p->og > 0 && prev->gf_out == gf_out)))
-    return fail(GNX_ERR_INVALID_ARG, "the pending call's workspace / gf_out must not be this call's (its graph update has not run yet)");
-  bool took = false;
-  int32_t rc = block_forward_impl(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream, 1, nullptr, 0.f, 0, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, prev, &took);
-  if (rc) return rc;
-  if (took) {  // prev's graph update rode in this launch; this call's is pending
-    pending->workspace = ws; pending->workspace_bytes = ws_bytes; pending->gf = gf; pending->gf_out = gf_out;
-    return GNX_OK;
-  }
-  // not the two-launch narrow form (matrix-core / generic kernels, run-time specialised widths, batches of small graphs whose graph update
-  // already runs inside the block kernel): finish the previous call the plain way, run this call whole, nothing stays pending
-  if (prev && prev->workspace) {
-    rc = gnx_block_graph_update(h, p, prev->gf, R, prev->gf_out, const_cast<void*>(prev->workspace), prev->workspace_bytes, flags, stream);
-    if (rc) return rc;
-  }
-  pending->workspace = nullptr; pending->workspace_bytes = 0; pending->gf = nullptr; pending->gf_out = nullptr;
-  return block_forward_impl(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream, 3);
+  return chained_step(BlockCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, (hipStream_t)stream, GNX_PHASE_ALL}, prev, pending);
 }
 
 // the bytes a step reads and writes (gnx_step_hazard.h: elem bytes per feature); the workspace is the part the block's kernels use (ws_extent)
@@ -359,82 +427,37 @@ static StepSpans step_spans(const gnx_graphs* h, const gnx_block_params* p, int6
 static bool steps_overlap_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R, uint32_t flags, hipStream_t s) {
   if (!h || !p || matrix_core_widths(*p) || (flags & GNX_FLAG_FORCE_GENERIC) || form(GNX_FLAG_NO_FORK) || profile_enabled()) return false;
   if (check_block(h, p, R) != GNX_OK) return false;  // (the one-stream loop reports it)
-  BlockArgs a{};
-  a.de = p->de; a.dn = p->dn; a.dg = p->dg; a.oe = p->oe; a.on = p->on; a.og = p->og;
-  a.n_wtiles = (int)h->n_wtiles(); a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G;
-  return block_narrow_takes(h, a, s);
+  return block_narrow_takes(h, block_probe(h, p), s);
 }
 
-// ---- bf16 steps (gnx_block_forward_steps_typed): typed, internal forms of gnx_block_forward_chained and gnx_block_graph_update ----
-// (the exported pending-update record has float* fields and no element type: these two stay inside the loop)
-static int32_t typed_graph_update(const gnx_graphs* h, const gnx_block_params* p, const float* gf, int64_t R, float* gf_out, void* ws, size_t ws_bytes,
-                                  uint32_t flags, hipStream_t s) {
-  return block_forward_impl(h, p, nullptr, nullptr, gf, R, nullptr, nullptr, gf_out, ws, ws_bytes, flags, s, 2, nullptr, 0.f, 0, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, true);
-}
-// One bf16 step on the native path: chained where the fp32 rule would chain (bf16 ahead-of-time widths), else `prev` flushed and the step run
-// whole by gnx_block_forward_typed (run-time specialised widths, the pack form), nothing left pending.
-static int32_t typed_chained(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step& st, int64_t R, uint32_t flags, hipStream_t s,
-                             const gnx_pending_update* prev, gnx_pending_update* pending) {
-  int32_t rc = check_block(h, p, R);
-  if (rc) return rc;
-  if ((p->de > 0 && !st.ef && h->E > 0) || (p->dn > 0 && !st.nf) || (p->dg > 0 && !st.gf))
-    return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL (width 0 <=> nothing)");
-  if ((p->oe > 0 && !st.ef_out && h->E > 0) || (p->on > 0 && !st.nf_out) || (p->og > 0 && !st.gf_out))
-    return fail(GNX_ERR_INVALID_ARG, "an output with non-zero width is NULL");
-  if (prev && prev->workspace && (prev->workspace == st.workspace || (p->og > 0 && prev->gf_out == st.gf_out)))
-    return fail(GNX_ERR_INVALID_ARG, "internal: the pending step's workspace / gf_out is this step's");
-  bool took = false;
-  rc = block_forward_impl(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, s, 1, nullptr, 0.f, 0,
-                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, prev, &took, nullptr, false, nullptr, true);
-  if (rc) return rc;
-  if (took) {
-    pending->workspace = st.workspace; pending->workspace_bytes = st.workspace_bytes; pending->gf = st.gf; pending->gf_out = st.gf_out;
-    return GNX_OK;
-  }
-  if (prev && prev->workspace) {
-    rc = typed_graph_update(h, p, prev->gf, R, prev->gf_out, const_cast<void*>(prev->workspace), prev->workspace_bytes, flags, s);
-    if (rc) return rc;
-  }
-  *pending = gnx_pending_update{};
-  return gnx_block_forward_typed(h, p, GNX_ELEM_BF16, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, s);
-}
-
-// The loop of gnx_block_forward_steps (bf16: gnx_block_forward_steps_typed on the native path), on one stream or — `overlap` — on two.  The
+// The loop of gnx_block_forward_steps (bf16 rows: gnx_block_forward_steps_typed on the native path), on one stream or — `overlap` — on two.  The
 // caller holds the DeviceTurn and the FormScope.
-static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step* steps, int64_t n_steps, int64_t R, uint32_t flags,
-                              void* stream, bool bf16, bool overlap) {
+static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_block_step* steps, int64_t n_steps, int64_t R,
+                              uint32_t flags, void* stream, bool overlap) {
   // Two streams: even steps on the caller's, odd steps on a side stream of the handle's pool (taken as gnx_core_forward takes it), so that
   // step i + 1's launch fills the slots that step i's ramp and drain leave idle and the per-launch cost of one hides under the other.
   // Every set taken, GNX_FLAG_NO_FORK, the per-kernel profiler on, or not the fused narrow kernel: one stream, the loop as before.
-  std::unique_lock<std::mutex> aux_lk;
-  const gnx_graphs::AuxSet* aux = nullptr;
-  if (overlap)
-    for (auto& ax : h->aux) {
-      if (!ax.stream || !ax.step[3]) break;
-      std::unique_lock<std::mutex> lk(ax.mu, std::try_to_lock);
-      if (lk.owns_lock()) { aux_lk = std::move(lk); aux = &ax; break; }
-    }
+  const AuxHold hold = overlap ? take_aux(h, true) : AuxHold{};
+  const gnx_graphs::AuxSet* aux = hold.set;
   hipStream_t str[2] = {(hipStream_t)stream, aux ? aux->stream : nullptr};
   // the pending graph update of each stream: step i's rides at the front of the next launch on ITS stream (step i + 1's on
   // one stream, step i + 2's on two)
   gnx_pending_update pend[2]{};
   auto flush = [&](int k) -> int32_t {
     if (!pend[k].workspace) return GNX_OK;
-    const int32_t rc = bf16 ? typed_graph_update(h, p, pend[k].gf, R, pend[k].gf_out, const_cast<void*>(pend[k].workspace), pend[k].workspace_bytes, flags, str[k])
-                            : gnx_block_graph_update(h, p, pend[k].gf, R, pend[k].gf_out, const_cast<void*>(pend[k].workspace), pend[k].workspace_bytes, flags, str[k]);
+    const int32_t rc = graph_update(h, p, elem, pend[k], R, flags, str[k]);
     pend[k] = gnx_pending_update{};
     return rc;
   };
   auto run = [&](const gnx_block_step& st, int k, gnx_pending_update* next) -> int32_t {
     const gnx_pending_update* prev = pend[k].workspace ? &pend[k] : nullptr;
-    return bf16 ? typed_chained(h, p, st, R, flags, str[k], prev, next)
-                : gnx_block_forward_chained(h, p, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[k],
-                                            prev, next);
+    return chained_step(BlockCall{h, p, elem, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[k], GNX_PHASE_ALL},
+                        prev, next);
   };
+  const bool bf16 = elem == GNX_ELEM_BF16;
   const bool valid = h && p && check_block(h, p, R) == GNX_OK;  // (else the first step reports the error)
   // per feature: 4 or 2 bytes; the workspace extent is the workspace query's (bf16 on this path: the native kernels, no staging)
-  const size_t elem = bf16 ? 2 : sizeof(float);
+  const size_t elem_bytes = bf16 ? 2 : sizeof(float);
   const size_t ws_extent = !valid ? 0 : bf16 ? typed_ws(h, p, R, true).total : block_ws(h, p, R).total;
   if (!aux) {
     StepSpans prev;
@@ -442,7 +465,7 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, co
       const gnx_block_step& st = steps[i];
       // a step whose buffers overlap its predecessor's (a shared workspace / gf_out, or gf' read as the next step's input) cannot start
       // before that one's graph update has run
-      const StepSpans cur = valid ? step_spans(h, p, R, st, elem, ws_extent) : StepSpans{};
+      const StepSpans cur = valid ? step_spans(h, p, R, st, elem_bytes, ws_extent) : StepSpans{};
       if (pend[0].workspace && (pend[0].workspace == st.workspace || (p && p->og > 0 && pend[0].gf_out == st.gf_out) || steps_conflict(cur, prev))) {
         if (int32_t rc = flush(0)) return rc;
       }
@@ -466,7 +489,7 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, co
   for (int64_t i = 0; i < n_steps && rc == GNX_OK; ++i) {
     const gnx_block_step& st = steps[i];
     const int k = (int)(i & 1), o = k ^ 1;
-    const StepSpans cur = step_spans(h, p, R, st, elem, ws_extent);
+    const StepSpans cur = step_spans(h, p, R, st, elem_bytes, ws_extent);
     const StepOrder ord = step_order(cur, recent, i);
     if (ord.flush_own && (rc = flush(k))) break;
     if (i >= 3) {
@@ -507,7 +530,7 @@ int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, 
   if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "gnx_block_forward_steps finishes every step's graph update itself");
   DeviceTurn turn((hipStream_t)stream, p && matrix_core_widths(*p));  // (one turn for the whole loop; the calls below nest inside it)
   FormScope forms(flags);
-  return steps_schedule(h, p, steps, n_steps, R, flags, stream, false, n_steps > 1 && steps_overlap_applies(h, p, R, flags, (hipStream_t)stream));
+  return steps_schedule(h, p, GNX_ELEM_F32, steps, n_steps, R, flags, stream, n_steps > 1 && steps_overlap_applies(h, p, R, flags, (hipStream_t)stream));
 }
 
 int32_t gnx_block_forward_steps_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_block_step* steps, int64_t n_steps, int64_t R,
@@ -538,13 +561,12 @@ int32_t gnx_block_forward_steps_typed(const gnx_graphs* h, const gnx_block_param
     return GNX_OK;
   }
   // a native bf16 kernel takes these widths (ahead of time, run-time specialised, pack form): the fp32 loop's schedule on bf16 rows
-  return steps_schedule(h, p, steps, n_steps, R, flags, stream, true, n_steps > 1 && !form(GNX_FLAG_NO_FORK) && !profile_enabled());
+  return steps_schedule(h, p, GNX_ELEM_BF16, steps, n_steps, R, flags, stream, n_steps > 1 && !form(GNX_FLAG_NO_FORK) && !profile_enabled());
 }
 
 int32_t gnx_block_graph_update(const gnx_graphs* h, const gnx_block_params* p, const float* gf, int64_t R, float* gf_out, void* ws,
                                size_t ws_bytes, uint32_t flags, void* stream) {
-  // the kernels of this phase read only gf, the graph function's parameters and the workspace
-  return block_forward_impl(h, p, nullptr, nullptr, gf, R, nullptr, nullptr, gf_out, ws, ws_bytes, flags, (hipStream_t)stream, 2);
+  return graph_update(h, p, GNX_ELEM_F32, gnx_pending_update{ws, ws_bytes, gf, gf_out}, R, flags, (hipStream_t)stream);
 }
 
 // FeedForward width from which the two Dense layers run on the matrix cores (hidden activations staged in HBM)
@@ -563,37 +585,6 @@ static void core_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, si
   off[6] = o; o += align_up(hidden, 256);
   off[7] = o;
   *total = o + block_ws(h, &p->block, R).total;
-}
-
-// side stream + fork / join events of the handle (see gnx_internal.h); failure just leaves the core on one stream
-static void ensure_aux(const gnx_graphs* h) {
-  std::call_once(h->aux_once, [h]() {
-    // the streams and their events belong to the HANDLE's device, whatever device is current in the querying thread
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev != h->device ? prev : -1};
-    if (prev != h->device && hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return; }
-    for (auto& ax : h->aux) {
-      hipStream_t st = nullptr;
-      hipEvent_t e1 = nullptr, e2 = nullptr;
-      hipEvent_t es[4] = {};
-      bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&e2, hipEventDisableTiming) == hipSuccess;
-      for (auto& e : es) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-      if (ok) {
-        ax.stream = st; ax.fork = e1; ax.join = e2;
-        for (int j = 0; j < 4; ++j) ax.step[j] = es[j];
-      } else {
-        for (hipEvent_t e : es)
-          if (e) (void)hipEventDestroy(e);
-        if (e1) (void)hipEventDestroy(e1);
-        if (e2) (void)hipEventDestroy(e2);
-        if (st) (void)hipStreamDestroy(st);
-        (void)hipGetLastError();
-        break;
-      }
-    }
-  });
 }
 
 size_t gnx_core_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
@@ -658,7 +649,9 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
   // All three widths narrow: the fused block kernel normalises its inputs as it loads them (gn1 never materialised) when it
   // is available for this width set; gn2 is recomputed inside k_core_post either way.
   bool fused_ln = false, defer_gu = false, edge_ff_done = false;
-  BlockArgs blk_args{};
+  NarrowLnResult narrow;
+  // the core's block as the forms see it; every call below is this one on its own inputs, stream and phase
+  const BlockCall blk{h, &b, GNX_ELEM_F32, ef, nf, gf, R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, s, GNX_PHASE_ALL};
   const bool all_narrow = core_narrow_width(d[0]) && core_narrow_width(d[1]) && core_narrow_width(d[2]) && !(flags & GNX_FLAG_FORCE_GENERIC);
   if (all_narrow) {
     // (the graph level of a NARROW core on the handle's side stream — graph update + the G-row / N-row k_core_post launches behind the
@@ -667,9 +660,9 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
     // without its k_graph_t
     defer_gu = h->E > 0 && !(flags & GNX_FLAG_DEFER_GRAPH_UPDATE) && core_post3_applies(rows, d, p->ff, true, s);
     // (the FeedForward moves into the block kernel only together with the one-launch post kernel, which then skips the edge rows)
-    rc = block_forward_impl(h, &b, ef, nf, gf, R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, s, defer_gu ? 1 : 3, p->ln1, p->eps,
-                            p->eps_mode, &fused_ln, nullptr, &blk_args, defer_gu ? &p->ff[0] : nullptr, &p->ln2[0], &edge_ff_done);
+    rc = block_narrow_ln(blk.on(s, defer_gu ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL), p->ln1, p->eps, p->eps_mode, defer_gu ? &p->ff[0] : nullptr, p->ln2[0], narrow);
     if (rc) return rc;
+    fused_ln = narrow.took; edge_ff_done = narrow.ffe_took;
     defer_gu = defer_gu && fused_ln;
   }
   // Wide edges and nodes: the matrix-core kernels normalise x as they load it (block: gn1, fused FeedForward: gn2) from one pass of
@@ -677,15 +670,14 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
   // and both FeedForwards are the fused kernel's; gf (G rows) is normalised by the ordinary kernel.
   const bool no_ln_fuse = form(GNX_FLAG_NO_LN_FUSE);
   bool wide_ln = false, edge_x6 = false;
+  BlockCall wide = blk.with(x[0], x[1], l1[2]);  // the matrix-core form reads ef and nf raw (normalised on load) and gf normalised
   if (!fused_ln && !all_narrow && !no_ln_fuse && !(flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA)) && h->E > 0) {
-    const float* ask[2] = {nullptr, nullptr};
     bool ok = true;
     for (int t = 0; t < 2; ++t)
       ok = ok && ln_stats_applies(x[t], d[t]) && ffn_fused_applies(x[t], d[t], p->ff[t], out[t], x[t], out[t]) &&
            (((uintptr_t)p->ln2[t].gamma | (uintptr_t)p->ln2[t].beta) & 15) == 0;
     if (ok) {
-      rc = block_forward_impl(h, &b, x[0], x[1], l1[2], R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, s, 3, p->ln1, p->eps, p->eps_mode, &wide_ln, ask,
-                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &edge_x6);
+      rc = block_wide_ln_ask(wide, p->ln1, wide_ln, edge_x6);
       if (rc) return rc;
     }
   }
@@ -707,7 +699,7 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
   const bool node_mat = wide_ln && !ln_on_load && !node_x6_forms;  // edges by the six-term kernels (statistics in registers), node LayerNorms materialised
   if (wide_ln) {
     const float* stats[2] = {l1[0], node_mat ? nullptr : l1[1]};  // the (unused) gn1 buffers hold the statistics: 2 floats per row
-    const float* node_in = node_mat ? l1[1] : x[1];              // node_mat: gn1(nf) itself (and l2[1] = gn2(nf) for the FeedForward)
+    wide.nf = node_mat ? l1[1] : x[1];                           // node_mat: gn1(nf) itself (and l2[1] = gn2(nf) for the FeedForward)
     auto node_ln = [&](hipStream_t st) -> int32_t {
       return node_mat ? launch_layernorm2(x[1], rows[1], d[1], p->ln1[1], p->ln2[1], p->eps, p->eps_mode, l1[1], l2[1], st)
                       : launch_ln_stats(x[1], rows[1], d[1], p->eps, p->eps_mode, l1[1], st);
@@ -719,14 +711,8 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
     const bool no_fork0 = form(GNX_FLAG_NO_FORK);
     // A side stream and its pair of events from the handle's pool, held while this call enqueues its work (a second host thread in this section —
     // same handle, another stream, other buffers — takes the next set; with every set taken a caller runs everything on its own stream).
-    std::unique_lock<std::mutex> aux_lk;
-    const gnx_graphs::AuxSet* aux = nullptr;
-    if (!no_fork0 && !profile_enabled())
-      for (auto& ax : h->aux) {
-        if (!ax.stream) break;
-        std::unique_lock<std::mutex> lk(ax.mu, std::try_to_lock);
-        if (lk.owns_lock()) { aux_lk = std::move(lk); aux = &ax; break; }
-      }
+    const AuxHold hold = !no_fork0 && !profile_enabled() ? take_aux(h, false) : AuxHold{};
+    const gnx_graphs::AuxSet* aux = hold.set;
     const bool fork0 = aux != nullptr;
     if ((rc = launch_layernorm2(x[2], rows[2], d[2], p->ln1[2], p->ln2[2], p->eps, p->eps_mode, l1[2], l2[2], s))) return rc;
     if (fork0) {
@@ -736,7 +722,7 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
       GNX_HIP(hipEventRecord(aux->fork, s));
       GNX_HIP(hipStreamWaitEvent(ax, aux->fork, 0));
       rc = node_ln(ax);
-      if (rc == GNX_OK) rc = block_forward_impl(h, &b, x[0], node_in, l1[2], R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, ax, 4, p->ln1, p->eps, p->eps_mode, &took0, stats);
+      if (rc == GNX_OK) rc = block_wide_ln_run(wide.on(ax, GNX_PHASE_WIDE_PROJ_ONLY), p->ln1, p->eps, p->eps_mode, stats, WideLnEdges{}, took0);
       const hipError_t e1 = hipEventRecord(aux->join, ax);
       const int32_t rc2 = inline_e ? GNX_OK : launch_ln_stats(x[0], rows[0], d[0], p->eps, p->eps_mode, l1[0], s);
       const hipError_t e2 = hipStreamWaitEvent(s, aux->join, 0);
@@ -754,15 +740,15 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
     const bool no_fork = no_fork0;
     const bool fork = !no_fork && aux != nullptr;
     bool took = false;
-    rc = block_forward_impl(h, &b, x[0], node_in, l1[2], R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, s, (fork ? 1 : 3) | (fork0 ? 8 : 0), p->ln1, p->eps, p->eps_mode, &took, stats,
-                            nullptr, fuse_e ? &p->ff[0] : nullptr, fuse_e ? &p->ln2[0] : nullptr, nullptr, nullptr, nullptr, nullptr, inline_e, fuse_e ? l2[0] : nullptr);
+    const WideLnEdges edges{inline_e, fuse_e ? &p->ff[0] : nullptr, fuse_e ? &p->ln2[0] : nullptr, fuse_e ? l2[0] : nullptr};
+    rc = block_wide_ln_run(wide.on(s, (fork ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL) | (fork0 ? GNX_PHASE_WIDE_PROJ_DONE : 0)), p->ln1, p->eps, p->eps_mode, stats, edges, took);
     if (rc) return rc;
     if (!took) return fail(GNX_ERR_INVALID_ARG, "gnx_core_forward: the block declined the form it had accepted");
     if (fork) {
       hipStream_t ax = aux->stream;
       GNX_HIP(hipEventRecord(aux->fork, s));
       GNX_HIP(hipStreamWaitEvent(ax, aux->fork, 0));
-      rc = block_forward_impl(h, &b, x[0], node_in, l1[2], R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, ax, 2, p->ln1, p->eps, p->eps_mode, &took, stats);
+      rc = block_wide_ln_run(wide.on(ax, GNX_PHASE_GRAPH), p->ln1, p->eps, p->eps_mode, stats, WideLnEdges{}, took);
       if (rc == GNX_OK) {  // the G-row FeedForward: out = gf' + gf + FF(gn2(gf)); the hidden buffer is its alone (the wide FeedForwards are the fused kernel)
         float* hidden2 = reinterpret_cast<float*>(base + off[6]);
         rc = launch_ffn_fused(h, 2, l2[2], d[2], p->ff[2], out[2], x[2], out[2], R, ax);
@@ -803,13 +789,13 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
       else rc = launch_layernorm2(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, l1[t], l2[t], s);
       if (rc) return rc;
     }
-    rc = block_forward_impl(h, &b, l1[0], l1[1], l1[2], R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, s);
+    rc = block_plain(blk.with(l1[0], l1[1], l1[2]));  // everything materialised: the plain block on gn1(x)
     if (rc) return rc;
   }
   float* hidden = reinterpret_cast<float*>(base + off[6]);
   if (all_narrow) {  // the three entities' FeedForward + residual in one launch when the width triple has the combined kernel
     const int n_rows = (int)(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->n_wtiles());  // partial-sum rows of the fused narrow block (gnx_narrow.hip)
-    rc = launch_core_post3(x, rows, d, p->ln2, p->ff, p->eps, p->eps_mode, out, s, defer_gu ? &blk_args : nullptr, n_rows, edge_ff_done);
+    rc = launch_core_post3(x, rows, d, p->ln2, p->ff, p->eps, p->eps_mode, out, s, defer_gu ? &narrow.args : nullptr, n_rows, edge_ff_done);
     if (rc != 1) return rc;
     if (edge_ff_done) return fail(GNX_ERR_INVALID_ARG, "internal: the edge FeedForward ran in the block kernel but the one-launch post kernel declined");
   }

@@ -6,7 +6,7 @@
 // src/gnblock.jl:63-69, src/gngraphnorm.jl:19-26, src/gnfeedforward.jl:27-40, src/gncore.jl:56-68.
 #include <algorithm>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 
 namespace gnx {
 

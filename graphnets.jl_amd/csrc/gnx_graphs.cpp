@@ -8,7 +8,7 @@
 #include <cstring>
 #include <thread>
 
-#include "gnx_internal.h"
+#include "gnx_launchers.h"
 
 namespace gnx {
 
@@ -307,14 +307,7 @@ static int32_t build_wide_tables(const gnx_graphs* h) {
 
 }  // namespace gnx
 
-namespace gnx {
-int32_t build_csc_on_device(const void* const* adj, const void* packed, int packed_on_device, const int64_t* n_nodes, int64_t G, int32_t elem_kind, int32_t row_major,
-                            gnx::vec_i64& h_colptr, gnx::vec_i64& h_rowval, const std::vector<int64_t>& h_node_off, DenseCscOnDevice* keep);
-}
-
 using namespace gnx;
-
-extern "C" int32_t gnx_graphs_destroy(gnx_graphs* h);
 
 // Shared body of the two CSC constructors: graph g's arrays through two accessors.  Two passes: sizes (so that every array is allocated
 // once), then validation fused with the copy — int64 host copies (accessors, collapse / CSR builders) and the int32 device-format arrays

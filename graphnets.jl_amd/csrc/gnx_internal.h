@@ -274,6 +274,27 @@ bool profile_enabled();  // per-kernel timing is on: callers keep everything on 
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// The `int phase` of the block launchers: which parts of a GNBlock a launch sequence runs.
+enum : int {
+  GNX_PHASE_EDGE_NODE = 1,  // edge + node update (leaves per-tile partial sums in the workspace)
+  GNX_PHASE_GRAPH = 2,      // graph update from those partial sums
+  GNX_PHASE_ALL = GNX_PHASE_EDGE_NODE | GNX_PHASE_GRAPH,
+  // launch_block_wide only (a GNCore that forks): the gf fold + node projections may run as a call of their own, on the side stream
+  GNX_PHASE_WIDE_PROJ_ONLY = 4,  // ... that call: nothing but them
+  GNX_PHASE_WIDE_PROJ_DONE = 8,  // ... with GNX_PHASE_EDGE_NODE: they were run by such a call, do not repeat them
+};
+
+// The widths and counts of a block on a handle, nothing else set: what the "which kernel takes these widths" predicates read (jit_eligible,
+// narrow_route / block_narrow_takes, narrow_bf16_aot, wide_applies) and the start of every full BlockArgs.  h == NULL (a width set asked
+// about without a batch: gnx_jit_precompile) leaves the counts 0.
+inline BlockArgs block_probe(const gnx_graphs* h, const gnx_block_params* p) {
+  BlockArgs a{};
+  a.de = p->de; a.dn = p->dn; a.dg = p->dg;
+  a.oe = p->oe; a.on = p->on; a.og = p->og;
+  if (h) { a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G; a.n_wtiles = (int)h->n_wtiles(); }
+  return a;
+}
+
 // graph-aligned packs of wave tiles from h->h_wtile_off (gnx_graphs.cpp; both builders): fills `packs` ([n_packs][8]) and h->n_packs
 void build_packs(gnx_graphs* h, std::vector<int32_t>& packs);
 // released handle arenas (gnx_build_csc.hip)
@@ -294,7 +315,6 @@ int32_t build_handle_from_csc_on_device(gnx_graphs* h, const void* colptr_cat, c
 extern "C" int32_t gnx_ensure_wide_tables(const gnx_graphs* h, void* stream = nullptr);
 // int64 host copies of colptr / rowval of a handle that was built on the device (no-op otherwise)
 extern "C" int32_t gnx_ensure_host_csc(const gnx_graphs* h);
-namespace gnx {
-
-
-}  // namespace gnx
+// the CSR view (backward pass) / the edge-collapsing tables of a handle, built on first use (gnx_graphs.cpp)
+extern "C" int32_t gnx_ensure_csr(const gnx_graphs* h);
+extern "C" int32_t gnx_ensure_collapse(const gnx_graphs* h);

@@ -1,0 +1,135 @@
+// Functions that one translation unit of libgnx.so defines and another calls: launchers, their "does this form apply" predicates and
+// their scratch-size queries.  The ONE declaration of each (the defining unit includes this header too, so a signature that drifts is
+// a compile error, not a link error), and the one place their default arguments are written.  Not part of the ABI.
+#pragma once
+#include "gnx_internal.h"
+
+namespace gnx {
+
+// ---- gnx_generic.hip: dimension-generic kernels ----
+int32_t launch_block_generic(const BlockArgs& a, int64_t R, int tile_n_cap, hipStream_t s, int phase);
+int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps, int eps_mode, float* y1, float* y2, hipStream_t s);
+int32_t launch_ffn_residual(const float* z, const float* x, size_t rows, int d, const gnx_ffn& ff, float* out, hipStream_t s);
+int32_t launch_pad(const gnx_graphs* h, int kind, bool pad, const float* src, int d, int64_t R, float* dst, hipStream_t s);
+int32_t launch_calibration(int n, hipStream_t s);
+int xent_blocks(int64_t cols);
+int32_t launch_xent_backward(const float* logits, const float* targets, int d, int64_t cols, const float* upstream, float* dl, hipStream_t s);
+int32_t launch_xent(const float* logits, const float* targets, int d, int64_t cols, float* out, float* ws, hipStream_t s);
+int32_t launch_collapse(const gnx_graphs* h, const float* ef, int d, int64_t R, float* out, hipStream_t s);
+int32_t launch_collapse_padded(const gnx_graphs* h, const float* ef, int d, int64_t R, float* out, hipStream_t s);
+int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, const float* nf, int dn, const float* gf, int dg, int64_t R, float* out, hipStream_t s);
+
+// ---- gnx_narrow.hip / gnx_narrow_bf16.hip / gnx_jit.cpp: the fused narrow block ----
+// launch_*: 1 when the path does not apply to these dims (the caller falls through to the next path); phase: GNX_PHASE_* (gnx_internal.h)
+int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, bool bf16 = false);
+void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p, bool bf16 = false);
+bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
+bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1, int act2);
+bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16 = false);
+bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16 = false);
+int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, bool bf16);
+bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a);
+int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
+int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
+bool jit_eligible(const BlockArgs& a, int ept);
+int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph, bool bf16 = false);
+int32_t jit_get_core_post3(int d0, int d1, int d2, hipStream_t s, hipFunction_t* fn);
+
+// ---- gnx_core_narrow.hip: narrow-width GNCore kernels ----
+bool core_narrow_width(int d);
+int32_t launch_ln1_rows(const float* x, size_t rows, int d, const gnx_layernorm& l1, float eps, int eps_mode, float* y, hipStream_t s);
+bool core_post3_applies(const size_t rows[3], const int d[3], const gnx_ffn ff[3], bool deferred, hipStream_t s);
+int32_t launch_core_post3(const float* const x[3], const size_t rows[3], const int d[3], const gnx_layernorm l2[3], const gnx_ffn ff[3], float eps,
+                          int eps_mode, float* const out[3], hipStream_t s, const BlockArgs* blk, int n_rows, bool skip_edges = false);
+int32_t launch_core_post(const float* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode, float* out, hipStream_t s);
+
+// ---- gnx_wide.hip: the matrix-core block and row-wise Dense ----
+int32_t launch_block_wide(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
+size_t wide_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R);
+void warm_block_wide(const gnx_graphs* h, const gnx_block_params* p, bool rows_gemm);
+bool block_wide_ln_applies(const gnx_graphs* h, const BlockArgs& a);
+bool block_wide_edge_x6_applies(const gnx_graphs* h, const BlockArgs& a);
+int32_t launch_dense_rows(const gnx_graphs* h, int entity, const float* A, int K, const gnx_dense& d, int OUT, const float* add1,
+                          const float* add2, float* out, int64_t R, hipStream_t s, const char* name);
+int32_t launch_rows_matmul(const gnx_graphs* h, int entity, const float* A, int K, const float* B, int ldw, int OUT, float* out, int64_t R,
+                           hipStream_t s, const char* name, const float* gmul, int gmul_act, float* tile_colsum, int* n_tiles_out, const float* add1);
+
+// ---- gnx_ffn_fused.hip / gnx_ffn_x6.hip: FeedForward + residual on the matrix cores, row statistics ----
+int32_t launch_ffn_fused(const gnx_graphs* h, int entity, const float* z, int d, const gnx_ffn& ff, const float* add1, const float* add2, float* out,
+                         int64_t R, hipStream_t s, const float* ln_stats = nullptr, const gnx_layernorm* ln = nullptr, void* scratch = nullptr, size_t scratch_bytes = 0,
+                         bool ln_inline = false, float ln_eps = 0.f, int ln_mode = 0);
+bool ffn_fused_applies(const float* z, int d, const gnx_ffn& ff, const float* add1, const float* add2, const float* out);
+bool ln_stats_applies(const float* x, int d);
+int32_t launch_ln_stats(const float* x, size_t rows, int d, float eps, int eps_mode, float* stats, hipStream_t s);
+bool ffn_x6_applies(const float* z, int d, const gnx_ffn& ff, const float* add1, const float* add2, const float* out, size_t scratch_bytes);
+int32_t launch_ffn_x6(const float* z, size_t nrows, int d, const gnx_ffn& ff, const float* add1, const float* add2, float* out, int64_t R, hipStream_t s,
+                      const float* ln_stats, const gnx_layernorm* ln, void* scratch, bool ln_inline, float ln_eps, int ln_mode);
+int32_t launch_ffn_x6_prep(const float* W1, const float* W2, int d, void* scratch, hipStream_t s, const float* ln_gamma, const float* ln_beta, const float* b1);
+size_t ffn_x6_scratch_bytes(int d);
+size_t ffn_x6_fold_scratch_bytes(int d);
+int32_t launch_core_edge_x6(const Tile* tiles, size_t n_tiles, const float* x, size_t E, const gnx_layernorm* ln1, float ln_eps, int ln_mode, const float* We, int ldw,
+                            const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* colsum, float* agg_out, size_t n_agg_rows,
+                            const int* chunk_row0, const gnx_ffn& ff, const gnx_layernorm* ln2, float* out, int64_t R, void* scratch_e, void* scratch_f, hipStream_t s);
+
+// ---- gnx_edge_x6.hip: the six-term edge / projection / node kernels of the matrix-core block ----
+int32_t launch_edge_x6(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
+                       const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out,
+                       size_t n_agg_rows, const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline = false, float ln_eps = 0.f,
+                       int ln_mode = 0, int oe = 128);
+int32_t launch_edge_x6_prep(const float* We, int ldw, void* scratch, hipStream_t s, int n_out, const float* ln_gamma, const float* ln_beta);
+size_t edge_x6_scratch_bytes();
+size_t edge_x6_fold_scratch_bytes();
+int32_t launch_fold_beta(const float* W, int ldw, int K, int n_out, const float* beta, const float* bias, float* out, hipStream_t s);
+bool proj_x6_applies(int dn, int oe, const float* nf, const float* W, const float* out, size_t N);
+int32_t launch_proj_x6(const Tile* tiles, size_t n_tiles, const float* nf, size_t N, const float* ln_stats, const float* ln_g, const float* ln_b, const float* Ws, const float* Wd,
+                       int ldw, const float* bias, const float* bias_g, int G, float* out_s, float* out_d, int64_t R, void* scratch, hipStream_t s, bool only_d = false,
+                       float* zn_out = nullptr);
+int32_t launch_proj_x6_prep(const float* Ws, const float* Wd, int ldw, void* scratch, hipStream_t s);
+size_t proj_x6_scratch_bytes();
+// the encoder form of k_edge_x6 ((10, 5, .) => 128 unprojected)
+int32_t launch_edge_enc(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* nf, size_t N, const float* We, int ldw, const float* bias, const float* bias_g,
+                        int G, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows, const int* chunk_row0, int64_t R,
+                        void* scratch, hipStream_t s);
+int32_t launch_edge_enc_prep(const float* We, int ldw, void* scratch, hipStream_t s);
+size_t edge_enc_scratch_bytes();
+bool node_x6_applies(int oe, int dn, int on, int act, const float* nf, const float* Wn, const float* out, size_t N);
+int32_t launch_node_x6(const Tile* tiles, size_t n_tiles, const float* nf, size_t N, const float* ln_stats, const float* ln_g, const float* ln_b, const float* agg,
+                       size_t n_agg_rows, const int* agg_row, const int* agg_parts, const int* agg_chunk, const int* chunk_row0, const float* Wn, int ldw, const float* bias,
+                       const float* bias_g, int G, int act, float* out, float* colsum, int64_t R, void* scratch, hipStream_t s);
+int32_t launch_node_x6_prep(const float* Wn, int ldw, void* scratch, hipStream_t s);
+size_t node_x6_scratch_bytes();
+
+// ---- gnx_edge_n.hip: the edge update with the source side gathered raw (K = 128 + 64) and a register epilogue ----
+bool edge_n_enabled();
+size_t edge_n_scratch_bytes();
+int32_t launch_edge_n(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
+                      const float* zsrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows,
+                      const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline, float ln_eps, int ln_mode);
+
+// ---- gnx_bf16.hip: bf16 <-> fp32 conversion of whole tensors ----
+int32_t launch_bf16_widen(const void* src, size_t n, float* dst, hipStream_t s);
+int32_t launch_bf16_round(const float* src, size_t n, void* dst, hipStream_t s);
+
+// ---- gnx_backward_wide.hip: matrix-core primitives of the backward pass ----
+bool bw_use_mfma(size_t rows, int J, int K);     // dX
+bool bw_use_mfma_dw(size_t rows, int J, int K);  // dW
+size_t dw_mfma_partial_floats(size_t rows, int J, int K);
+int32_t dw_mfma(const float* delta, const float* X, size_t rows, int J, int K, float* dW, float* partial, hipStream_t s);
+int32_t dx_mfma(const gnx_graphs* h, int entity, const float* delta, const float* W, int J, int K, int ka, int kb, float* out, int64_t R,
+                float* WT, bool fill, hipStream_t s, const char* name, const float* gmul = nullptr, int gmul_act = 0, float* tile_colsum = nullptr, int* n_tiles_out = nullptr);
+int32_t transpose_w(const float* W, int K, int J, float* WT, hipStream_t s);
+int32_t rows_times_wt(const gnx_graphs* h, int entity, const float* A, int J, const float* WT, int K, int ka, int kb, float* out, const float* add1,
+                      int64_t R, hipStream_t s, const char* name);
+int32_t segsum_rows(const float* src, const int* ptr, const int* idx, int N, int E, int D, int64_t R, float* out, hipStream_t s, const char* name);
+int32_t add_cols(const float* in, int ld, int off, size_t rows, int d, float* out, int accumulate, hipStream_t s);
+
+// ---- gnx_dropout.hip ----
+bool dropout_active(const gnx_dropout* d);
+int32_t check_dropout(const gnx_dropout* d);
+int32_t launch_dropout(const gnx_dropout& d, int entity, size_t n, const float* in, float* out, int mode, hipStream_t s);
+
+// ---- gnx_build_device.hip: the CSC of a dense batch built on the device ----
+int32_t build_csc_on_device(const void* const* adj, const void* packed, int packed_on_device, const int64_t* n_nodes, int64_t G, int32_t elem_kind, int32_t row_major,
+                            gnx::vec_i64& h_colptr, gnx::vec_i64& h_rowval, const std::vector<int64_t>& h_node_off, DenseCscOnDevice* keep);
+
+}  // namespace gnx

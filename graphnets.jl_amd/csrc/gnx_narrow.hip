@@ -13,7 +13,7 @@
 // dims on first use.  1 ("not applicable") sends the caller on to the MFMA / generic kernels.
 #include <cstdlib>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_narrow_launch.h"
 #include "gnx_wave_kernel.h"
 
@@ -30,18 +30,25 @@ namespace gnx {
   X(8, 8, 8, 16, 8)        \
   X(10, 5, 3, 10, 5)       \
   X(10, 5, 0, 10, 5)
-// ... with bfloat16 features: gnx_narrow_bf16.hip
-bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a);
-int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
-int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
+// (with bfloat16 features: the list in gnx_narrow_bf16.hip, narrow_bf16_aot)
+static bool narrow_aot_listed(const BlockArgs& a) {
+#define GNX_CASE(DE, DN, DG, OE, ON) \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return true;
+  GNX_NARROW_DIMS(GNX_CASE)
+#undef GNX_CASE
+  return false;
+}
 
-bool jit_eligible(const BlockArgs& a, int ept);
-int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph, bool bf16 = false);
+// edges per lane of the run-time specialised kernel at the handle's wave-tile size (1, 2 or 4); 0: no such kernel for that size
+static int jit_ept(const gnx_graphs* h) {
+  const int ept = h->wtile_e_cap / 64;
+  return ept * 64 == h->wtile_e_cap && (ept == 1 || ept == 2 || ept == 4) ? ept : 0;
+}
 
 // Same launch geometry as launch_wave_t, kernels specialised at run time (gnx_jit.cpp) for this width set.
 static int32_t launch_wave_jit(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, bool bf16 = false) {
-  const int ept = h->wtile_e_cap / 64;
-  if (ept * 64 != h->wtile_e_cap || (ept != 1 && ept != 2 && ept != 4)) return 1;
+  const int ept = jit_ept(h);
+  if (!ept) return 1;
   hipFunction_t fb = nullptr, fg = nullptr;
   const int32_t rc = jit_get(a, ept, s, &fb, &fg, bf16);
   if (rc) return rc;
@@ -65,16 +72,9 @@ static int32_t launch_wave_jit(const gnx_graphs* h, const BlockArgs& a, int64_t 
 // compiles + loads the run-time specialised kernels of this width set ahead of the first forward (called from
 // gnx_block_workspace_bytes, which every caller runs before a forward and never inside a stream capture)
 void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p, bool bf16) {
-  BlockArgs a{};
-  a.de = p->de; a.dn = p->dn; a.dg = p->dg; a.oe = p->oe; a.on = p->on; a.og = p->og;
-  a.G = (int)h->G;  // selects the one-graph / several-graphs variant of the kernel
-#define GNX_CASE(DE, DN, DG, OE, ON) \
-  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return;
+  const BlockArgs a = block_probe(h, p);  // (a.G selects the one-graph / several-graphs variant of the kernel)
   static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // (diagnostic: specialise even the ahead-of-time width sets; read once)
-  if (!jit_all) {
-    if (bf16) { if (narrow_bf16_aot(h, a)) return; } else { GNX_NARROW_DIMS(GNX_CASE) }
-  }
-#undef GNX_CASE
+  if (!jit_all && (bf16 ? narrow_bf16_aot(h, a) : narrow_aot_listed(a))) return;
   if (h->n_wtiles() == 0 || h->E == 0) return;
   hipFunction_t fb, fg;
   (void)jit_get(a, h->wtile_e_cap / 64, nullptr, &fb, &fg, bf16);
@@ -95,16 +95,12 @@ bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s) 
   if (a.n_wtiles == 0 || a.E == 0) return false;
   if (wants_ln(a)) {
     if (ln_aot(h, a)) return true;
-  } else {
-#define GNX_CASE(DE, DN, DG, OE, ON) \
-    if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return h->wtile_e_cap == 64 || h->wtile_e_cap == 128 || h->wtile_e_cap == 256;
-    GNX_NARROW_DIMS(GNX_CASE)
-#undef GNX_CASE
+  } else if (narrow_aot_listed(a)) {
+    return h->wtile_e_cap == 64 || h->wtile_e_cap == 128 || h->wtile_e_cap == 256;
   }
-  const int ept = h->wtile_e_cap / 64;
-  if (ept * 64 != h->wtile_e_cap || (ept != 1 && ept != 2 && ept != 4)) return false;
+  const int ept = jit_ept(h);
   hipFunction_t fb, fg;
-  return jit_get(a, ept, s, &fb, &fg) == GNX_OK;
+  return ept && jit_get(a, ept, s, &fb, &fg) == GNX_OK;
 }
 
 // gnx_block_forward_chained: can the previous call's graph update ride at the front of this call's block kernel?  The two-launch form of
@@ -119,17 +115,16 @@ bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a, bool bf
   const int wsl = wave_slice_floats(a.oe, 2);
   if (h->G == 1) { if (graph_update_lds_floats(C, a.dg, a.og, graph_update_threads(h)) > 4 * wsl) return false; }
   else if (h->max_wtiles_per_graph > 256 || graph_update_lds_floats(C, a.dg, a.og, 64) > wsl) return false;
-  bool listed = false;
-#define GNX_CASE(DE, DN, DG, OE, ON) \
-  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) listed = true;
-  GNX_NARROW_DIMS(GNX_CASE)
-#undef GNX_CASE
-  return listed && (!bf16 || narrow_bf16_aot(h, a));
+  return narrow_aot_listed(a) && (!bf16 || narrow_bf16_aot(h, a));
 }
 // the edge + node update of THIS call with a.prev_* (the previous call's pending graph update) at the front of the same launch
-int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a0, int64_t R, hipStream_t s) {
+int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a0, int64_t R, hipStream_t s, bool bf16) {
   BlockArgs a = a0;
   a.prev_blocks = a.prev_partials ? (h->G == 1 ? 1 : (int)((h->G + 3) / 4)) : 0;
+  if (bf16) {  // ... on bf16 rows (gnx_block_forward_steps_typed): gnx_narrow_bf16.hip
+    const int32_t rc = launch_chained_bf16(h, a, R, s);
+    return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: chained bf16 launch for a width set without that kernel") : rc;
+  }
 #define GNX_CASE(DE, DN, DG, OE, ON)                                                                                               \
   if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) {                                                         \
     if constexpr (OE + ON > 0) {                                                                                                   \
@@ -140,13 +135,6 @@ int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a0, in
   GNX_NARROW_DIMS(GNX_CASE)
 #undef GNX_CASE
   return fail(GNX_ERR_INVALID_ARG, "internal: chained launch for a width set without that kernel");
-}
-// ... on bf16 rows (gnx_block_forward_steps_typed)
-int32_t launch_block_narrow_chained_bf16(const gnx_graphs* h, const BlockArgs& a0, int64_t R, hipStream_t s) {
-  BlockArgs a = a0;
-  a.prev_blocks = a.prev_partials ? (h->G == 1 ? 1 : (int)((h->G + 3) / 4)) : 0;
-  const int32_t rc = launch_chained_bf16(h, a, R, s);
-  return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: chained bf16 launch for a width set without that kernel") : rc;
 }
 
 // the edge FeedForward + residual of a narrow GNCore inside the block kernel (k_block_wave<..., FFE>): ahead-of-time widths, identity / relu
@@ -164,38 +152,25 @@ enum NarrowRoute { NR_NONE, NR_AOT, NR_JIT };
 static NarrowRoute narrow_route(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16 = false) {
   if (a.n_wtiles == 0 || a.E == 0 || wants_ln(a)) return NR_NONE;
   auto jit_ok = [&]() {
-    const int ept = h->wtile_e_cap / 64;
-    if (ept * 64 != h->wtile_e_cap || (ept != 1 && ept != 2 && ept != 4)) return false;
+    const int ept = jit_ept(h);
     hipFunction_t fb, fg;
-    return jit_get(a, ept, s, &fb, &fg, bf16) == GNX_OK;
+    return ept && jit_get(a, ept, s, &fb, &fg, bf16) == GNX_OK;
   };
   static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // testing: run-time specialise even the listed width sets
   if (jit_all && jit_ok()) return NR_JIT;
-#define GNX_CASE(DE, DN, DG, OE, ON)                                                                                              \
-  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON)                                                          \
-    return h->wtile_e_cap == 64 || h->wtile_e_cap == 128 || (h->wtile_e_cap == 256 && (DE + DN) * 4 <= 64) ? NR_AOT : NR_NONE;  // (launch_fused's EPT)
   if (bf16) {
     if (narrow_bf16_aot(h, a)) return NR_AOT;
-  } else {
-    GNX_NARROW_DIMS(GNX_CASE)
+  } else if (narrow_aot_listed(a)) {
+    return h->wtile_e_cap == 64 || h->wtile_e_cap == 128 || (h->wtile_e_cap == 256 && (a.de + a.dn) * 4 <= 64) ? NR_AOT : NR_NONE;  // (launch_fused's EPT)
   }
-#undef GNX_CASE
   return jit_ok() ? NR_JIT : NR_NONE;
 }
 
 bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16) { return narrow_route(h, a, s, bf16) != NR_NONE; }
 
-// bf16 features (gnx_block_forward_typed): the native kernels, or 1 when no fused kernel takes these widths (the caller converts around
-// the fp32 forward).  No LayerNorm on load, no deferred form; phase 2 alone is the flush of a chained bf16 step (ahead-of-time widths only).
-int32_t launch_block_narrow_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
-  const NarrowRoute route = narrow_route(h, a, s, true);
-  if (route == NR_NONE) return 1;
-  if (route == NR_JIT) return launch_wave_jit(h, a, R, s, phase, true);
-  const int32_t rc = launch_fused_bf16(h, a, R, s, phase);
-  return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: ahead-of-time bf16 route for a width set without that kernel") : rc;
-}
-
-int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+// 1: no fused kernel takes these widths.  bf16 features (gnx_block_forward_typed): the native kernels (on 1 the caller converts around the
+// fp32 forward); no LayerNorm on load, no deferred form; phase 2 alone is the flush of a chained bf16 step (ahead-of-time widths only).
+int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, bool bf16) {
   if (a.n_wtiles == 0 || a.E == 0) return 1;
   if (wants_ln(a)) {  // only reached after block_narrow_ready(): a miss here would silently drop the LayerNorm
     if (a.ffe_w1) {   // (set by gnx_core_forward only after block_narrow_ffe_applies())
@@ -206,9 +181,13 @@ int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, 
     const int32_t rc = launch_wave_jit(h, a, R, s, phase);
     return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: LayerNorm-on-load requested but the fused kernel is not available") : rc;
   }
-  const NarrowRoute route = narrow_route(h, a, s);
+  const NarrowRoute route = narrow_route(h, a, s, bf16);
   if (route == NR_NONE) return 1;
-  if (route == NR_JIT) return launch_wave_jit(h, a, R, s, phase);  // compiled on first use (gnx_block_workspace_bytes)
+  if (route == NR_JIT) return launch_wave_jit(h, a, R, s, phase, bf16);  // compiled on first use (gnx_block_workspace_bytes)
+  if (bf16) {
+    const int32_t rc = launch_fused_bf16(h, a, R, s, phase);
+    return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: ahead-of-time bf16 route for a width set without that kernel") : rc;
+  }
   // 16-B vector copies assume fp32-aligned buffers (always true for fp32 arrays); nothing else is required
 #define GNX_CASE(DE, DN, DG, OE, ON) \
   if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return launch_fused<DE, DN, DG, OE, ON>(h, a, R, s, phase);

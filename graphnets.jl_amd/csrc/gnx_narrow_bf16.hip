@@ -4,7 +4,7 @@
 // A translation unit of its own because build.py compiles it without the SLP vectoriser (-fno-slp-vectorize; gnx_jit.cpp passes the same
 // option for a bf16 key): with it, every widened value feeds a v_pk_fma_f32 as the low half of a register pair of its own, and the README
 // ex.1 kernel needs 70 instead of 58 VGPRs — 7 instead of 8 waves per SIMD.  Scalar FMAs compute the same bits.
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_narrow_launch.h"
 #include "gnx_wave_kernel.h"
 

@@ -8,22 +8,7 @@
 #include <mutex>
 #include <vector>
 
-#include "gnx_internal.h"
-
-namespace gnx {
-int32_t launch_edge_x6_prep(const float* We, int ldw, void* scratch, hipStream_t s, int n_out, const float* ln_gamma, const float* ln_beta);  // gnx_edge_x6.hip
-size_t edge_x6_fold_scratch_bytes();
-int32_t launch_proj_x6_prep(const float* Ws, const float* Wd, int ldw, void* scratch, hipStream_t s);  // gnx_edge_x6.hip
-size_t proj_x6_scratch_bytes();
-int32_t launch_ffn_x6_prep(const float* W1, const float* W2, int d, void* scratch, hipStream_t s, const float* ln_gamma, const float* ln_beta,
-                           const float* b1);  // gnx_ffn_x6.hip
-size_t ffn_x6_fold_scratch_bytes(int d);
-int32_t launch_edge_enc_prep(const float* We, int ldw, void* scratch, hipStream_t s);                  // gnx_edge_x6.hip
-int32_t launch_node_x6_prep(const float* Wn, int ldw, void* scratch, hipStream_t s);                   // gnx_edge_x6.hip
-size_t node_x6_scratch_bytes();
-size_t edge_enc_scratch_bytes();
-size_t ffn_x6_scratch_bytes(int d);
-}  // namespace gnx
+#include "gnx_launchers.h"
 
 struct gnx_prepared {
   struct Entry {

@@ -19,7 +19,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "gnx_device.h"
+#include "gnx_launchers.h"
 #include "gnx_x6_mma.h"
 
 #ifndef GNX_LN_GUARD  // see store_chunk's LayerNorm branch
@@ -27,36 +27,6 @@
 #endif
 
 namespace gnx {
-
-int32_t launch_edge_x6(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
-                       const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out,
-                       size_t n_agg_rows, const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline = false, float ln_eps = 0.f,
-                       int ln_mode = 0, int oe = 128);  // gnx_edge_x6.hip
-size_t proj_x6_scratch_bytes();  // gnx_edge_x6.hip
-bool proj_x6_applies(int dn, int oe, const float* nf, const float* W, const float* out, size_t N);
-int32_t launch_proj_x6(const Tile* tiles, size_t n_tiles, const float* nf, size_t N, const float* ln_stats, const float* ln_g, const float* ln_b, const float* Ws, const float* Wd,
-                       int ldw, const float* bias, const float* bias_g, int G, float* out_s, float* out_d, int64_t R, void* scratch, hipStream_t s, bool only_d = false,
-                       float* zn_out = nullptr);
-// the encoder form of k_edge_x6 ((10, 5, .) => 128 unprojected; gnx_edge_x6.hip)
-size_t edge_enc_scratch_bytes();
-int32_t launch_edge_enc(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* nf, size_t N, const float* We, int ldw, const float* bias, const float* bias_g,
-                        int G, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows, const int* chunk_row0, int64_t R,
-                        void* scratch, hipStream_t s);
-// gnx_edge_n.hip: the edge update with the source side gathered raw (K = 128 + 64) and a register epilogue
-size_t edge_n_scratch_bytes();
-size_t edge_x6_fold_scratch_bytes();  // gnx_edge_x6.hip
-bool node_x6_applies(int oe, int dn, int on, int act, const float* nf, const float* Wn, const float* out, size_t N);  // gnx_edge_x6.hip
-size_t node_x6_scratch_bytes();
-int32_t launch_node_x6(const Tile* tiles, size_t n_tiles, const float* nf, size_t N, const float* ln_stats, const float* ln_g, const float* ln_b, const float* agg,
-                       size_t n_agg_rows, const int* agg_row, const int* agg_parts, const int* agg_chunk, const int* chunk_row0, const float* Wn, int ldw, const float* bias,
-                       const float* bias_g, int G, int act, float* out, float* colsum, int64_t R, void* scratch, hipStream_t s);
-bool edge_n_enabled();
-int32_t launch_edge_n(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
-                      const float* zsrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows,
-                      const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline, float ln_eps, int ln_mode);
-int32_t launch_core_edge_x6(const Tile* tiles, size_t n_tiles, const float* x, size_t E, const gnx_layernorm* ln1, float ln_eps, int ln_mode, const float* We, int ldw,
-                            const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* colsum, float* agg_out, size_t n_agg_rows,
-                            const int* chunk_row0, const gnx_ffn& ff, const gnx_layernorm* ln2, float* out, int64_t R, void* scratch_e, void* scratch_f, hipStream_t s);  // gnx_ffn_x6.hip
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -1437,11 +1407,8 @@ static bool wide_applies(const gnx_graphs* h, const BlockArgs& a, bool* project_
 void warm_block_wide(const gnx_graphs* h, const gnx_block_params* p, bool rows_gemm) {
   bool need = rows_gemm;
   if (!need && p) {
-    BlockArgs a{};
-    a.de = p->de; a.dn = p->dn; a.dg = p->dg; a.oe = p->oe; a.on = p->on; a.og = p->og;
-    a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G;
     bool project = false;
-    need = wide_applies(h, a, &project);
+    need = wide_applies(h, block_probe(h, p), &project);
   }
   if (need) (void)gnx_ensure_wide_tables(h);  // a failure is not latched: the forward reports it
 }
@@ -1500,10 +1467,10 @@ int32_t launch_block_wide(const gnx_graphs* h, const BlockArgs& a, int64_t R, hi
   // (needs quad outputs, and — with the projections' epilogue operands — an ef whose rows are quads: see launch_gemm's instantiations)
   const bool edge_out_vec = a.oe % 4 == 0 && al16(a.We) && al16(a.ef_out) && ((size_t)a.E * a.oe) % 4 == 0 && ((size_t)a.N * a.oe) % 4 == 0;
   const bool ef_vec = a.de % 4 == 0 && al16(a.ef) && ((size_t)a.E * a.de) % 4 == 0;
-  const bool agg_fuse = !no_agg_fuse && (phase & 5) && a.oe > 0 && a.on > 0 && edge_out_vec && (!project || ef_vec) && h->n_agg_rows > 0 &&
+  const bool agg_fuse = !no_agg_fuse && (phase & (GNX_PHASE_EDGE_NODE | GNX_PHASE_WIDE_PROJ_ONLY)) && a.oe > 0 && a.on > 0 && edge_out_vec && (!project || ef_vec) && h->n_agg_rows > 0 &&
                         (size_t)h->n_agg_rows * a.oe * sizeof(float) < (1ull << 32);
   int32_t rc = GNX_OK;
-  const bool prep = (phase & 4) || ((phase & 1) && !(phase & 8));  // gf fold + node projections
+  const bool prep = (phase & GNX_PHASE_WIDE_PROJ_ONLY) || ((phase & GNX_PHASE_EDGE_NODE) && !(phase & GNX_PHASE_WIDE_PROJ_DONE));  // gf fold + node projections
   if (prep && a.dg > 0) {  // fold gf into per-graph biases (one tiny launch per update function)
     ProfScope ps("k_fold_bias", s);
     if (skinny_ok(R * a.G, a.dg, std::max(a.oe, a.on))) {  // a few graphs, wide layers: one round-trip-lean GEMV kernel per function
@@ -1521,7 +1488,7 @@ int32_t launch_block_wide(const gnx_graphs* h, const BlockArgs& a, int64_t R, hi
   const bool proj6 = project && proj_x6_applies(a.dn, a.oe, a.nf, a.We, proj_s, (size_t)a.N) && (!a.ln_stats[1] || (al16(a.ln_g[1]) && al16(a.ln_b[1]))) && al16(a.be);
   // k_edge_n's form (gnx_edge_n.hip): the source side multiplied per edge from the raw 64-wide row — the projection launch then produces the
   // destination table and, under a LayerNorm, the normalised rows the edges gather (in the source table's place).  One predicate for both launches
-  // (they may run in different calls: phase 4 on the side stream, phase 1 on the caller's): it depends on the block, never on the phase.
+  // (they may run in different calls: GNX_PHASE_WIDE_PROJ_ONLY on the side stream, GNX_PHASE_EDGE_NODE on the caller's): it depends on the block, never on the phase.
   const bool edge_n = proj6 && block_wide_edge_n_applies(h, a);
   if (prep && proj6) {
     // 64 -> 2 x 128 from 4096 nodes on: both tables in one launch of k_proj_x6 (six bf16 matrix-core terms per fp32 product; gnx_edge_x6.hip)
