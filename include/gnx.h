@@ -30,6 +30,17 @@
  *   - The library uses the calling thread's current HIP device; a handle lives on the device it was created on.
  *   - Output buffers must not overlap input buffers or the workspace (the kernels read inputs while they write outputs; the training forward
  *     re-reads x after the outputs exist).  The reference's layers are out-of-place as well (every update allocates its result).
+ *   - Sizes are exact: a feature / gradient buffer is R * T * D * sizeof(element) bytes, a workspace the value of its gnx_*_workspace_bytes
+ *     query; a call writes nothing outside its output, gradient and workspace buffers, leaves its inputs (features, weights, upstream
+ *     gradients) untouched, and its result does not depend on what the workspace held before — except between the phases of the forms that
+ *     say so (GNX_FLAG_DEFER_GRAPH_UPDATE -> gnx_block_graph_update, gnx_block_forward_chained, the steps of gnx_block_forward_steps).
+ *     tests/test_gpu_memory_contract.py holds every dispatch form to this.
+ *   - Alignment of fp32 buffers: 4 bytes (a float) is all the narrow and generic kernels assume (their row accesses are dword-aligned vector
+ *     loads).  The matrix-core launchers (any width above 32: csrc/gnx_wide.hip, gnx_edge_x6.hip, gnx_ffn_*.hip, gnx_backward_wide.hip) TEST
+ *     16-byte alignment of the feature, weight and output pointers they are handed and take an element-wise or another kernel form when it
+ *     does not hold; the six-term kernels refuse a bias or LayerNorm gamma / beta vector that is not 16-byte aligned with GNX_ERR_INVALID_ARG
+ *     instead.  A workspace must be 16-byte aligned (GNX_ERR_WORKSPACE otherwise).  Every device allocator returns 256-byte aligned memory and
+ *     the tests run with nothing less: fp32 buffers at other alignments (a view into the middle of a tensor) are untested.
  */
 #ifndef GNX_H
 #define GNX_H
