@@ -328,27 +328,25 @@ int32_t launch_edge_n_prep(const float* We, int ldw, void* scratch, hipStream_t 
   return GNX_OK;
 }
 
-int32_t launch_edge_n(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
-                      const float* zsrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows,
-                      const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline, float ln_eps, int ln_mode) {
-  if (n_tiles == 0) return GNX_OK;
-  if (!tiles || !ef || !We || !zsrc || !pdst || !src || !dst || !out || !scratch) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: NULL operand");
-  if ((((uintptr_t)ef | (uintptr_t)zsrc | (uintptr_t)scratch | (uintptr_t)ln_g | (uintptr_t)ln_b) & 15) || ((uintptr_t)ln_stats & 7))
+int32_t launch_edge_n(const EdgeLaunch& e) {
+  if (e.n_tiles == 0) return GNX_OK;
+  if (!e.tiles || !e.ef || !e.We || !e.psrc || !e.pdst || !e.src || !e.dst || !e.out || !e.scratch) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: NULL operand");
+  if ((((uintptr_t)e.ef | (uintptr_t)e.psrc | (uintptr_t)e.scratch | (uintptr_t)e.ln.g | (uintptr_t)e.ln.b) & 15) || ((uintptr_t)e.ln.stats & 7))
     return fail(GNX_ERR_INVALID_ARG, "k_edge_n: operand not 16-byte aligned");
-  if (agg_out && !chunk_row0) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: per-destination sums need the chunk table");
-  if (const int32_t rc = launch_edge_n_prep(We, ldw, scratch, s)) return rc;
+  if (e.agg_out && !e.chunk_row0) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: per-destination sums need the chunk table");
+  if (const int32_t rc = launch_edge_n_prep(e.We, e.ldw, e.scratch, e.stream)) return rc;
   EdgeNArgs a{};
-  a.tiles = tiles; a.ef = ef; a.E = E; a.ln_stats = ln_stats; a.ln_g = ln_g; a.ln_b = ln_b;
-  if (ln_inline) {
-    if (ln_stats || !ln_g || !ln_b) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: statistics in the kernel exclude a statistics table and need gamma / beta");
-    a.ln_inline = 1; a.ln_eps = ln_eps; a.ln_mode = ln_mode;
-  } else if (ln_stats && (!ln_g || !ln_b)) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: LayerNorm parameters missing");
-  a.Wp = static_cast<const __bf16*>(scratch);
-  a.zsrc = zsrc; a.pdst = pdst; a.N = N; a.src = src; a.dst = dst; a.act = act; a.out = out; a.colsum = colsum; a.n_tiles = n_tiles;
-  a.agg_out = agg_out; a.n_agg_rows = n_agg_rows; a.chunk_row0 = chunk_row0;
-  ProfScope ps("k_rows_gemm_edge", s);  // (the name the edge update has in every profile and bench line)
-  if (act > GNX_ACT_RELU) GNX_LAUNCH(k_edge_n<true>, dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * NW), 0, s, a);
-  else GNX_LAUNCH(k_edge_n<false>, dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * NW), 0, s, a);
+  a.tiles = e.tiles; a.ef = e.ef; a.E = e.E; a.ln_stats = e.ln.stats; a.ln_g = e.ln.g; a.ln_b = e.ln.b;
+  if (e.ln.inline_stats) {
+    if (e.ln.stats || !e.ln.g || !e.ln.b) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: statistics in the kernel exclude a statistics table and need gamma / beta");
+    a.ln_inline = 1; a.ln_eps = e.ln.eps; a.ln_mode = e.ln.mode;
+  } else if (e.ln.stats && (!e.ln.g || !e.ln.b)) return fail(GNX_ERR_INVALID_ARG, "k_edge_n: LayerNorm parameters missing");
+  a.Wp = static_cast<const __bf16*>(e.scratch);
+  a.zsrc = e.psrc; a.pdst = e.pdst; a.N = e.N; a.src = e.src; a.dst = e.dst; a.act = e.act; a.out = e.out; a.colsum = e.colsum; a.n_tiles = e.n_tiles;
+  a.agg_out = e.agg_out; a.n_agg_rows = e.n_agg_rows; a.chunk_row0 = e.chunk_row0;
+  ProfScope ps("k_rows_gemm_edge", e.stream);  // (the name the edge update has in every profile and bench line)
+  if (e.act > GNX_ACT_RELU) GNX_LAUNCH(k_edge_n<true>, dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * NW), 0, e.stream, a);
+  else GNX_LAUNCH(k_edge_n<false>, dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * NW), 0, e.stream, a);
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }

@@ -862,24 +862,23 @@ int32_t launch_edge_enc_prep(const float* We, int ldw, void* scratch, hipStream_
 }
 
 // ef' = act(We^T [ef ; nf[src] ; nf[dst]] + bias) at (10, 5, .) => 128 with the per-destination sums and column sums of k_edge_x6; bias_g: per-graph bias (gf fold)
-int32_t launch_edge_enc(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* nf, size_t N, const float* We, int ldw, const float* bias, const float* bias_g,
-                        int G, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows, const int* chunk_row0, int64_t R,
-                        void* scratch, hipStream_t s) {
-  if (n_tiles == 0) return GNX_OK;
-  if (!tiles || !ef || !nf || !We || !src || !dst || !out || !scratch || (((uintptr_t)scratch | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)bias_g | (uintptr_t)agg_out) & 15))
+int32_t launch_edge_enc(const EdgeLaunch& e, const float* bias, const float* bias_g, int G) {
+  if (e.n_tiles == 0) return GNX_OK;
+  if (!e.tiles || !e.ef || !e.psrc || !e.We || !e.src || !e.dst || !e.out || !e.scratch ||
+      (((uintptr_t)e.scratch | (uintptr_t)e.out | (uintptr_t)bias | (uintptr_t)bias_g | (uintptr_t)e.agg_out) & 15))
     return fail(GNX_ERR_INVALID_ARG, "k_edge_x6 (encoder form): NULL or misaligned operand");
-  if (agg_out && !chunk_row0) return fail(GNX_ERR_INVALID_ARG, "k_edge_x6 (encoder form): per-destination sums need the chunk table");
-  const __bf16* Wp = static_cast<const __bf16*>(prepared_planes(PREP_ENC, We, nullptr, ldw));
+  if (e.agg_out && !e.chunk_row0) return fail(GNX_ERR_INVALID_ARG, "k_edge_x6 (encoder form): per-destination sums need the chunk table");
+  const __bf16* Wp = static_cast<const __bf16*>(prepared_planes(PREP_ENC, e.We, nullptr, e.ldw));
   if (!Wp) {
-    if (const int32_t rc = launch_edge_enc_prep(We, ldw, scratch, s)) return rc;
-    Wp = static_cast<const __bf16*>(scratch);
+    if (const int32_t rc = launch_edge_enc_prep(e.We, e.ldw, e.scratch, e.stream)) return rc;
+    Wp = static_cast<const __bf16*>(e.scratch);
   }
   EdgeX6Args a{};
-  a.tiles = tiles; a.ef = ef; a.E = E; a.Wp = Wp; a.N = N; a.src = src; a.dst = dst; a.act = act; a.out = out; a.colsum = colsum; a.n_tiles = n_tiles;
-  a.agg_out = agg_out; a.n_agg_rows = n_agg_rows; a.chunk_row0 = chunk_row0; a.oe = EOUT; a.nf = nf; a.bias = bias; a.bias_g = bias_g; a.G = G;
-  ProfScope ps("k_rows_gemm_edge", s);  // (the name the edge update has in every profile and bench line)
-  if (act > GNX_ACT_RELU) GNX_LAUNCH((k_edge_x6<false, 2, true>), dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * EW), 0, s, a);
-  else GNX_LAUNCH((k_edge_x6<false, 2, false>), dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * EW), 0, s, a);
+  a.tiles = e.tiles; a.ef = e.ef; a.E = e.E; a.Wp = Wp; a.N = e.N; a.src = e.src; a.dst = e.dst; a.act = e.act; a.out = e.out; a.colsum = e.colsum; a.n_tiles = e.n_tiles;
+  a.agg_out = e.agg_out; a.n_agg_rows = e.n_agg_rows; a.chunk_row0 = e.chunk_row0; a.oe = EOUT; a.nf = e.psrc; a.bias = bias; a.bias_g = bias_g; a.G = G;
+  ProfScope ps("k_rows_gemm_edge", e.stream);  // (the name the edge update has in every profile and bench line)
+  if (e.act > GNX_ACT_RELU) GNX_LAUNCH((k_edge_x6<false, 2, true>), dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * EW), 0, e.stream, a);
+  else GNX_LAUNCH((k_edge_x6<false, 2, false>), dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * EW), 0, e.stream, a);
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
@@ -915,25 +914,23 @@ int32_t launch_edge_x6_prep(const float* We, int ldw, void* scratch, hipStream_t
   return GNX_OK;
 }
 
-int32_t launch_edge_x6(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
-                       const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out,
-                       size_t n_agg_rows, const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline, float ln_eps, int ln_mode, int oe) {
-  if (n_tiles == 0) return GNX_OK;
-  if (oe != EOUT && (oe < 1 || oe > 32 || agg_out)) return fail(GNX_ERR_INVALID_ARG, "k_edge_x6: output width 128, or 1..32 without per-destination sums");
-  const __bf16* Wp = static_cast<const __bf16*>(prepared_planes(PREP_EDGE, We, nullptr, oe));  // made once with the layer (gnx_*_prepare) ...
-  if (!Wp) {                                                                                        // ... or by a launch in front of this forward
-    if (const int32_t rc = launch_edge_x6_prep(We, ldw, scratch, s, oe, nullptr, nullptr)) return rc;
-    Wp = static_cast<const __bf16*>(scratch);
+int32_t launch_edge_x6(const EdgeLaunch& e, int oe) {
+  if (e.n_tiles == 0) return GNX_OK;
+  if (oe != EOUT && (oe < 1 || oe > 32 || e.agg_out)) return fail(GNX_ERR_INVALID_ARG, "k_edge_x6: output width 128, or 1..32 without per-destination sums");
+  const __bf16* Wp = static_cast<const __bf16*>(prepared_planes(PREP_EDGE, e.We, nullptr, oe));  // made once with the layer (gnx_*_prepare) ...
+  if (!Wp) {                                                                                          // ... or by a launch in front of this forward
+    if (const int32_t rc = launch_edge_x6_prep(e.We, e.ldw, e.scratch, e.stream, oe, nullptr, nullptr)) return rc;
+    Wp = static_cast<const __bf16*>(e.scratch);
   }
   EdgeX6Args a{};
-  a.tiles = tiles; a.ef = ef; a.E = E; a.ln_stats = ln_stats; a.ln_g = ln_g; a.ln_b = ln_b; a.Wp = Wp; a.psrc = psrc; a.pdst = pdst; a.N = N;
-  a.src = src; a.dst = dst; a.act = act; a.out = out; a.colsum = colsum; a.n_tiles = n_tiles; a.agg_out = agg_out; a.n_agg_rows = n_agg_rows; a.chunk_row0 = chunk_row0;
-  if (ln_inline) { if (ln_stats || !ln_g || !ln_b) return fail(GNX_ERR_INVALID_ARG, "k_edge_x6: statistics in the kernel exclude a statistics table and need gamma / beta"); a.ln_inline = 1; a.ln_eps = ln_eps; a.ln_mode = ln_mode; }
+  a.tiles = e.tiles; a.ef = e.ef; a.E = e.E; a.ln_stats = e.ln.stats; a.ln_g = e.ln.g; a.ln_b = e.ln.b; a.Wp = Wp; a.psrc = e.psrc; a.pdst = e.pdst; a.N = e.N;
+  a.src = e.src; a.dst = e.dst; a.act = e.act; a.out = e.out; a.colsum = e.colsum; a.n_tiles = e.n_tiles; a.agg_out = e.agg_out; a.n_agg_rows = e.n_agg_rows; a.chunk_row0 = e.chunk_row0;
+  if (e.ln.inline_stats) { if (e.ln.stats || !e.ln.g || !e.ln.b) return fail(GNX_ERR_INVALID_ARG, "k_edge_x6: statistics in the kernel exclude a statistics table and need gamma / beta"); a.ln_inline = 1; a.ln_eps = e.ln.eps; a.ln_mode = e.ln.mode; }
   a.oe = oe;
-  ProfScope ps("k_rows_gemm_edge", s);  // (the name the edge update has in every profile and bench line)
-  const bool trans = act > GNX_ACT_RELU;
-  if (oe == EOUT) { if (trans) GNX_LAUNCH((k_edge_x6<false, EKS, true>), dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * EW), 0, s, a); else GNX_LAUNCH((k_edge_x6<false, EKS, false>), dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * EW), 0, s, a); }
-  else { if (trans) GNX_LAUNCH((k_edge_x6<true, EKS, true>), dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * EW), 0, s, a); else GNX_LAUNCH((k_edge_x6<true, EKS, false>), dim3((unsigned)n_tiles, (unsigned)R), dim3(64 * EW), 0, s, a); }
+  ProfScope ps("k_rows_gemm_edge", e.stream);  // (the name the edge update has in every profile and bench line)
+  const bool trans = e.act > GNX_ACT_RELU;
+  if (oe == EOUT) { if (trans) GNX_LAUNCH((k_edge_x6<false, EKS, true>), dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * EW), 0, e.stream, a); else GNX_LAUNCH((k_edge_x6<false, EKS, false>), dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * EW), 0, e.stream, a); }
+  else { if (trans) GNX_LAUNCH((k_edge_x6<true, EKS, true>), dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * EW), 0, e.stream, a); else GNX_LAUNCH((k_edge_x6<true, EKS, false>), dim3((unsigned)e.n_tiles, (unsigned)e.R), dim3(64 * EW), 0, e.stream, a); }
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }

@@ -959,25 +959,24 @@ int32_t launch_ffn_x6(const float* z, size_t nrows, int d, const gnx_ffn& ff, co
 // A GNCore's edge rows in ONE launch (EDGE form of k_ffn_x6): out = x + ef' + FF(gn2(x)), ef' = act(We^T gn1(x) + Ps[src] + Pd[dst]) with its per-destination
 // sums (agg_out) and column sums (colsum) as k_edge_x6 writes them; ef' itself is never written.  Row statistics of x in the kernel.
 // Both LayerNorms are folded into the weight planes (see FfnX6Edge): prepared with the layer (gnx_core_prepare), or here, per call.
-// scratch_e: edge_x6_fold_scratch_bytes(), scratch_f: ffn_x6_fold_scratch_bytes(128); both 16-byte aligned and free until the launch has run.
-int32_t launch_core_edge_x6(const Tile* tiles, size_t n_tiles, const float* x, size_t E, const gnx_layernorm* ln1, float ln_eps, int ln_mode, const float* We, int ldw,
-                            const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* colsum, float* agg_out, size_t n_agg_rows,
-                            const int* chunk_row0, const gnx_ffn& ff, const gnx_layernorm* ln2, float* out, int64_t R, void* scratch_e, void* scratch_f, hipStream_t s) {
-  if (n_tiles == 0) return GNX_OK;
-  if (!scratch_e || !scratch_f || (((uintptr_t)scratch_e | (uintptr_t)scratch_f) & 15)) return fail(GNX_ERR_INVALID_ARG, "k_ffn_x6 (edge form): scratch missing or misaligned");
-  if (!tiles || !x || !We || !psrc || !pdst || !src || !dst || !ff.fc1.weight || !ff.fc2.weight || !out) return fail(GNX_ERR_INVALID_ARG, "k_ffn_x6 (edge form): NULL operand");
-  if (!ln1 || !ln2 || !ln1->gamma || !ln1->beta || !ln2->gamma || !ln2->beta ||
-      (((uintptr_t)ln1->gamma | (uintptr_t)ln1->beta | (uintptr_t)ln2->gamma | (uintptr_t)ln2->beta | (uintptr_t)x | (uintptr_t)out | (uintptr_t)psrc | (uintptr_t)pdst | (uintptr_t)ff.fc2.bias |
-        (uintptr_t)agg_out) & 15))
+// e.scratch: edge_x6_fold_scratch_bytes(), scratch_f: ffn_x6_fold_scratch_bytes(128); both 16-byte aligned and free until the launch has run.
+int32_t launch_core_edge_x6(const EdgeLaunch& e, const gnx_ffn& ff, const gnx_layernorm* ln2, void* scratch_f) {
+  if (e.n_tiles == 0) return GNX_OK;
+  const hipStream_t s = e.stream;
+  if (!e.scratch || !scratch_f || (((uintptr_t)e.scratch | (uintptr_t)scratch_f) & 15)) return fail(GNX_ERR_INVALID_ARG, "k_ffn_x6 (edge form): scratch missing or misaligned");
+  if (!e.tiles || !e.ef || !e.We || !e.psrc || !e.pdst || !e.src || !e.dst || !ff.fc1.weight || !ff.fc2.weight || !e.out) return fail(GNX_ERR_INVALID_ARG, "k_ffn_x6 (edge form): NULL operand");
+  if (!ln2 || !e.ln.g || !e.ln.b || !ln2->gamma || !ln2->beta ||
+      (((uintptr_t)e.ln.g | (uintptr_t)e.ln.b | (uintptr_t)ln2->gamma | (uintptr_t)ln2->beta | (uintptr_t)e.ef | (uintptr_t)e.out | (uintptr_t)e.psrc | (uintptr_t)e.pdst | (uintptr_t)ff.fc2.bias |
+        (uintptr_t)e.agg_out) & 15))
     return fail(GNX_ERR_INVALID_ARG, "k_ffn_x6 (edge form): LayerNorm parameters missing, or an operand not 16-byte aligned");
   if (ff.fc2.act != GNX_ACT_IDENTITY) return fail(GNX_ERR_INVALID_ARG, "k_ffn_x6 (edge form): fc2 with an activation");
   // both weight blocks with their LayerNorm folded in (planes, then the constant vector): made once with the layer (gnx_core_prepare: looked up
   // by the weight and the gamma pointer), or by launches in front of this forward
   int32_t rc = GNX_OK;
-  const char* Wpe = static_cast<const char*>(prepared_planes(PREP_EDGE, We, ln1->gamma, 128));
+  const char* Wpe = static_cast<const char*>(prepared_planes(PREP_EDGE, e.We, e.ln.g, 128));
   if (!Wpe) {
-    if ((rc = launch_edge_x6_prep(We, ldw, scratch_e, s, 128, ln1->gamma, ln1->beta))) return rc;
-    Wpe = static_cast<const char*>(scratch_e);
+    if ((rc = launch_edge_x6_prep(e.We, e.ldw, e.scratch, s, 128, e.ln.g, e.ln.b))) return rc;
+    Wpe = static_cast<const char*>(e.scratch);
   }
   const char* Wp = static_cast<const char*>(prepared_planes(PREP_FFN, ff.fc1.weight, ln2->gamma, 128));
   if (!Wp) {
@@ -985,27 +984,27 @@ int32_t launch_core_edge_x6(const Tile* tiles, size_t n_tiles, const float* x, s
     Wp = static_cast<const char*>(scratch_f);
   }
   FfnX6Args a{};
-  a.z = x; a.Wp = reinterpret_cast<const __bf16*>(Wp); a.b1 = reinterpret_cast<const float*>(Wp + ffn_x6_scratch_bytes(128));  // b1 + W1^T beta2
-  a.b2 = ff.fc2.bias; a.add1 = x; a.add2 = nullptr; a.out = out; a.rows = E; a.act1 = ff.fc1.act;
-  a.ln_g = ln2->gamma; a.ln_b = ln2->beta; a.ln_eps = ln_eps; a.ln_mode = ln_mode;
-  a.e.tiles = tiles; a.e.c1 = reinterpret_cast<const float*>(Wpe + edge_x6_scratch_bytes()); a.e.Wpe = reinterpret_cast<const __bf16*>(Wpe); a.e.psrc = psrc; a.e.pdst = pdst; a.e.N = N; a.e.src = src; a.e.dst = dst;
-  a.e.act = act; a.e.colsum = colsum; a.e.n_tiles = n_tiles; a.e.agg_out = agg_out; a.e.n_agg_rows = n_agg_rows; a.e.chunk_row0 = chunk_row0;
+  a.z = e.ef; a.Wp = reinterpret_cast<const __bf16*>(Wp); a.b1 = reinterpret_cast<const float*>(Wp + ffn_x6_scratch_bytes(128));  // b1 + W1^T beta2
+  a.b2 = ff.fc2.bias; a.add1 = e.ef; a.add2 = nullptr; a.out = e.out; a.rows = e.E; a.act1 = ff.fc1.act;
+  a.ln_g = ln2->gamma; a.ln_b = ln2->beta; a.ln_eps = e.ln.eps; a.ln_mode = e.ln.mode;
+  a.e.tiles = e.tiles; a.e.c1 = reinterpret_cast<const float*>(Wpe + edge_x6_scratch_bytes()); a.e.Wpe = reinterpret_cast<const __bf16*>(Wpe); a.e.psrc = e.psrc; a.e.pdst = e.pdst; a.e.N = e.N; a.e.src = e.src; a.e.dst = e.dst;
+  a.e.act = e.act; a.e.colsum = e.colsum; a.e.n_tiles = e.n_tiles; a.e.agg_out = e.agg_out; a.e.n_agg_rows = e.n_agg_rows; a.e.chunk_row0 = e.chunk_row0;
   ProfScope ps("k_core_edge_x6", s);
-  const dim3 grid((unsigned)n_tiles, (unsigned)R);
+  const dim3 grid((unsigned)e.n_tiles, (unsigned)e.R);
 #ifdef GNX_X6_STAMPS_BUILD
-  const unsigned long long* d_dbg = x6_stamps_begin(n_tiles, s);
+  const unsigned long long* d_dbg = x6_stamps_begin(e.n_tiles, s);
   const unsigned dyn_lds = getenv("GNX_X6_ONE_WG") ? 8192u : 0u;  // (diagnostic: 8 KB of unused dynamic LDS leave room for ONE workgroup per CU — a wave's phases without a partner)
 #else
   constexpr unsigned dyn_lds = 0;
 #endif
-  if (ff.fc1.act > GNX_ACT_RELU || act > GNX_ACT_RELU) GNX_LAUNCH((k_ffn_x6<128, true, true>), grid, dim3(64 * XW), dyn_lds, s, a);
+  if (ff.fc1.act > GNX_ACT_RELU || e.act > GNX_ACT_RELU) GNX_LAUNCH((k_ffn_x6<128, true, true>), grid, dim3(64 * XW), dyn_lds, s, a);
   else GNX_LAUNCH((k_ffn_x6<128, false, true>), grid, dim3(64 * XW), dyn_lds, s, a);
   GNX_HIP(hipGetLastError());
 #ifdef GNX_X6_STAMPS_BUILD
   static const char* const names[XNST] = {nullptr, "prologue", "FeedForward", "transition",
     "s0:mfma", "s0:addends", "s0:epilogue", "s0:barrier1", "s0:sums", "s0:barrier2", "s1:mfma", "s1:addends", "s1:epilogue", "s1:barrier1", "s1:sums", "s1:barrier2",
     "s2:mfma", "s2:addends", "s2:epilogue", "s2:barrier1", "s2:sums", "s2:barrier2", "s3:mfma", "s3:addends", "s3:epilogue", "s3:barrier1", "s3:sums", "s3:barrier2", "drain"};
-  x6_stamps_end(d_dbg, n_tiles, "k_core_edge_x6", names, s);
+  x6_stamps_end(d_dbg, e.n_tiles, "k_core_edge_x6", names, s);
 #endif
   return GNX_OK;
 }

@@ -94,7 +94,7 @@ struct gnx_graphs {
   mutable int32_t* d_node_agg_chunk = nullptr;   // [N] its first chunk
   mutable int64_t n_agg_rows = 0;
   // edge tiles whose destinations span more than gnx::kPdRowsCap consecutive nodes (the edge GEMM stages a tile's destination
-  // projections in LDS when they fit: launch_block_wide picks that kernel when nearly every tile qualifies)
+  // projections in LDS when they fit: the wide block's k_rows_gemm edge update picks that kernel when every tile qualifies)
   mutable int64_t n_etiles_wide_span = 0;
   gnx::Tile* d_wtiles = nullptr;  // [n_wtiles]
   // graph-aligned packs of wave tiles (batches whose graphs all have <= 8 wave tiles): [n_packs][8] tile ids, -1 = empty slot; a graph's
@@ -279,13 +279,14 @@ enum : int {
   GNX_PHASE_EDGE_NODE = 1,  // edge + node update (leaves per-tile partial sums in the workspace)
   GNX_PHASE_GRAPH = 2,      // graph update from those partial sums
   GNX_PHASE_ALL = GNX_PHASE_EDGE_NODE | GNX_PHASE_GRAPH,
-  // launch_block_wide only (a GNCore that forks): the gf fold + node projections may run as a call of their own, on the side stream
+  // launch_block_wide only (a GNCore that forks): the gf fold + node projections may run as a call of their own, on the side stream.  Its plan
+  // (gnx_wide.hip: WidePlan) never reads the phase — both calls decide alike; the phase only picks which of the planned steps a call runs
   GNX_PHASE_WIDE_PROJ_ONLY = 4,  // ... that call: nothing but them
   GNX_PHASE_WIDE_PROJ_DONE = 8,  // ... with GNX_PHASE_EDGE_NODE: they were run by such a call, do not repeat them
 };
 
 // The widths and counts of a block on a handle, nothing else set: what the "which kernel takes these widths" predicates read (jit_eligible,
-// narrow_route / block_narrow_takes, narrow_bf16_aot, wide_applies) and the start of every full BlockArgs.  h == NULL (a width set asked
+// narrow_route / block_narrow_takes, narrow_bf16_aot, wide_plan) and the start of every full BlockArgs.  h == NULL (a width set asked
 // about without a batch: gnx_jit_precompile) leaves the counts 0.
 inline BlockArgs block_probe(const gnx_graphs* h, const gnx_block_params* p) {
   BlockArgs a{};

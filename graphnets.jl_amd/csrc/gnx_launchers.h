@@ -6,6 +6,20 @@
 
 namespace gnx {
 
+// What the edge launchers of the matrix-core block share (launch_edge_x6, launch_edge_enc, launch_edge_n, launch_core_edge_x6): filled once per edge
+// update by launch_block_wide (gnx_wide.hip), by name — each launcher takes it plus only what is its own.
+struct EdgeLaunch {
+  const Tile* tiles; size_t n_tiles; const float* ef; size_t E;  // the edge rows, in 128-row tiles
+  struct { const float* stats; const float* g; const float* b; bool inline_stats; float eps; int mode; } ln;  // gn1 of the edge rows: from a statistics table, or (inline_stats) in the kernel
+  const float* We; int ldw;
+  const float* psrc;  // the source-side table [R][N][.]: projected rows Ps (k_edge_n: the 64-wide rows themselves; encoder: nf, both sides)
+  const float* pdst;  // projected rows Pd (bias and gf fold included)
+  size_t N; const int* src; const int* dst; int act;
+  float* out; float* colsum;  // ef' (the core form: x + ef' + FF) / its per-tile column sums or nullptr
+  float* agg_out; size_t n_agg_rows; const int* chunk_row0;  // per-destination partial sums or nullptr
+  int64_t R; void* scratch; hipStream_t stream;  // scratch: for the prepared weight planes when the layer brings none
+};
+
 // ---- gnx_generic.hip: dimension-generic kernels ----
 int32_t launch_block_generic(const BlockArgs& a, int64_t R, int tile_n_cap, hipStream_t s, int phase);
 int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps, int eps_mode, float* y1, float* y2, hipStream_t s);
@@ -67,15 +81,10 @@ int32_t launch_ffn_x6(const float* z, size_t nrows, int d, const gnx_ffn& ff, co
 int32_t launch_ffn_x6_prep(const float* W1, const float* W2, int d, void* scratch, hipStream_t s, const float* ln_gamma, const float* ln_beta, const float* b1);
 size_t ffn_x6_scratch_bytes(int d);
 size_t ffn_x6_fold_scratch_bytes(int d);
-int32_t launch_core_edge_x6(const Tile* tiles, size_t n_tiles, const float* x, size_t E, const gnx_layernorm* ln1, float ln_eps, int ln_mode, const float* We, int ldw,
-                            const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* colsum, float* agg_out, size_t n_agg_rows,
-                            const int* chunk_row0, const gnx_ffn& ff, const gnx_layernorm* ln2, float* out, int64_t R, void* scratch_e, void* scratch_f, hipStream_t s);
+int32_t launch_core_edge_x6(const EdgeLaunch& e, const gnx_ffn& ff, const gnx_layernorm* ln2, void* scratch_f);  // (e.ln: gn1, folded into the planes; e.out: the CORE's edge output)
 
 // ---- gnx_edge_x6.hip: the six-term edge / projection / node kernels of the matrix-core block ----
-int32_t launch_edge_x6(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
-                       const float* psrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out,
-                       size_t n_agg_rows, const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline = false, float ln_eps = 0.f,
-                       int ln_mode = 0, int oe = 128);
+int32_t launch_edge_x6(const EdgeLaunch& e, int oe);  // oe: 128, or 1..32 (the narrow form: one zero-padded slice, no per-destination sums)
 int32_t launch_edge_x6_prep(const float* We, int ldw, void* scratch, hipStream_t s, int n_out, const float* ln_gamma, const float* ln_beta);
 size_t edge_x6_scratch_bytes();
 size_t edge_x6_fold_scratch_bytes();
@@ -86,10 +95,8 @@ int32_t launch_proj_x6(const Tile* tiles, size_t n_tiles, const float* nf, size_
                        float* zn_out = nullptr);
 int32_t launch_proj_x6_prep(const float* Ws, const float* Wd, int ldw, void* scratch, hipStream_t s);
 size_t proj_x6_scratch_bytes();
-// the encoder form of k_edge_x6 ((10, 5, .) => 128 unprojected)
-int32_t launch_edge_enc(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* nf, size_t N, const float* We, int ldw, const float* bias, const float* bias_g,
-                        int G, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows, const int* chunk_row0, int64_t R,
-                        void* scratch, hipStream_t s);
+// the encoder form of k_edge_x6 ((10, 5, .) => 128 unprojected; e.psrc: nf, e.pdst and e.ln unused)
+int32_t launch_edge_enc(const EdgeLaunch& e, const float* bias, const float* bias_g, int G);
 int32_t launch_edge_enc_prep(const float* We, int ldw, void* scratch, hipStream_t s);
 size_t edge_enc_scratch_bytes();
 bool node_x6_applies(int oe, int dn, int on, int act, const float* nf, const float* Wn, const float* out, size_t N);
@@ -102,9 +109,7 @@ size_t node_x6_scratch_bytes();
 // ---- gnx_edge_n.hip: the edge update with the source side gathered raw (K = 128 + 64) and a register epilogue ----
 bool edge_n_enabled();
 size_t edge_n_scratch_bytes();
-int32_t launch_edge_n(const Tile* tiles, size_t n_tiles, const float* ef, size_t E, const float* ln_stats, const float* ln_g, const float* ln_b, const float* We, int ldw,
-                      const float* zsrc, const float* pdst, size_t N, const int* src, const int* dst, int act, float* out, float* colsum, float* agg_out, size_t n_agg_rows,
-                      const int* chunk_row0, int64_t R, void* scratch, hipStream_t s, bool ln_inline, float ln_eps, int ln_mode);
+int32_t launch_edge_n(const EdgeLaunch& e);  // (e.psrc: the 64-wide source rows, raw or normalised)
 
 // ---- gnx_bf16.hip: bf16 <-> fp32 conversion of whole tensors ----
 int32_t launch_bf16_widen(const void* src, size_t n, float* dst, hipStream_t s);

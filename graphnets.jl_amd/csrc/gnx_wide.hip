@@ -105,7 +105,7 @@ struct WideArgs {
   int ln_width;                // (set by launch_gemm)
   WSeg pk[3];                  // mode 5: the packed segments (modes 0-2), their W rows consecutive from seg[0].w_row0
   int npk;
-  int pd_lds;                  // gathered addends: every tile's destination rows fit the LDS table of the NL = 3 kernel (set by launch_block_wide from the handle's tile statistics)
+  int pd_lds;                  // gathered addends: every tile's destination rows fit the LDS table of the NL = 3 kernel (set by the wide block's edge update from the handle's tile statistics)
   int stagger;                 // start delay per residency slot (units of 64*127 clocks), 0 = none (set by launch_gemm)
   int fp32;                    // 1: the products on v_mfma_f32_32x32x2f32 — only where the CALL's flags ask (GNX_FLAG_EDGE_FP32 / _PROJ_FP32 / _EDGE_NARROW_FP32 /
                                // _FFN_FP32: set by the callers from form()); 0, the default: six bf16 matrix-core terms per product (gnx_x6_mma.h)
@@ -1141,10 +1141,6 @@ static int32_t launch_skinny2(const SkinnyJob& j0, const SkinnyJob& j1, hipStrea
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
-static int32_t launch_skinny(const float* x, int ldx, int M, int K, const float* W, int w_row0, int ldw, const float* bias, int N, int act, float* y,
-                             int ldy, hipStream_t s) {
-  return launch_skinny2(SkinnyJob{x, ldx, M, K, W, w_row0, ldw, bias, N, act, y, ldy}, SkinnyJob{}, s);
-}
 
 // Xg[r*G + g][:] = [sum_e ef' ; sum_n nf' ; gf_g] from the stage-1 slices (the input of the graph function)
 __global__ __launch_bounds__(256) void k_graph_x(const float* pe2, const float* pn2, int S, BlockArgs a, float* __restrict__ xg) {
@@ -1185,17 +1181,35 @@ static size_t x6_tab_bytes(int de, int oe) {
   return (de == 128 && oe == 128) ? std::max(edge_x6_fold_scratch_bytes(), edge_n_scratch_bytes()) : x6;  // (the core's one-launch form: + We^T beta)
 }
 
-size_t wide_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  const size_t per_tile = sizeof(float) * (size_t)R * ((size_t)h->n_etiles * p->oe + (size_t)h->n_ntiles * p->on);
-  const size_t stage2 = sizeof(float) * (size_t)R * h->G * wide_slices(h) * (size_t)(p->oe + p->on);
-  const size_t bias_g = sizeof(float) * (size_t)R * h->G * (size_t)(p->oe + p->on);
-  const size_t proj = sizeof(float) * 2 * (size_t)R * h->N * (size_t)p->oe;  // node projections Ps, Pd
-  const size_t xg = sizeof(float) * (size_t)R * h->G * (size_t)(p->oe + p->on + p->dg);  // graph-function input (small batches)
-  const size_t agg = sizeof(float) * (size_t)R * (size_t)h->agg_rows_bound * (size_t)p->oe;  // per-destination partial sums of the edge GEMM (rows: an upper bound known without the tables)
-  const size_t x6 = x6_tab_bytes(p->de, p->oe);
-  const size_t x6p = proj_x6_scratch_bytes();  // the node projections' two weight blocks likewise (k_proj_x6_prep)
-  return align_up(per_tile, 256) + align_up(stage2, 256) + align_up(bias_g, 256) + align_up(proj, 256) + align_up(xg, 256) + align_up(agg, 256) + align_up(x6, 256) + align_up(x6p, 256) + 512;
+// The wide block's workspace (a.partials), written ONCE: the byte offset of every region and the total.  Eight 256-byte aligned regions in this order
+// (pe | pe2 | bias_e | proj_s | xg | agg | x6 | x6p); pn, pn2, bias_n and proj_d start where their partner's rows end.
+struct WideLayout {
+  int S;                  // slices per graph of the graph level's stage 1 (wide_slices)
+  size_t pe, pn;          // per-tile column sums of ef' / nf'
+  size_t pe2, pn2;        // ... summed per (graph, slice)
+  size_t bias_e, bias_n;  // gf folded into per-graph biases
+  size_t proj_s, proj_d;  // node projections Ps, Pd
+  size_t xg;              // graph-function input (small batches)
+  size_t agg;             // per-destination partial sums of the edge GEMM
+  size_t x6, x6p, total;  // prepared weight planes of the edge update / of the node projections (k_proj_x6_prep; the node update's after them)
+};
+static WideLayout wide_layout(const gnx_graphs* h, int de, int dg, int oe, int on, int64_t R) {
+  const size_t f = sizeof(float), r = (size_t)R, G = (size_t)h->G, N = (size_t)h->N, n_et = (size_t)h->n_etiles, n_nt = (size_t)h->n_ntiles;
+  WideLayout L{};
+  L.S = wide_slices(h);
+  L.pn = f * r * n_et * oe;  // (pe = 0)
+  L.pe2 = align_up(f * r * (n_et * oe + n_nt * on), 256);                   L.pn2 = L.pe2 + f * r * G * L.S * oe;
+  L.bias_e = L.pe2 + align_up(f * r * G * L.S * (size_t)(oe + on), 256);    L.bias_n = L.bias_e + f * r * G * oe;
+  L.proj_s = L.bias_e + align_up(f * r * G * (size_t)(oe + on), 256);       L.proj_d = L.proj_s + f * r * N * oe;
+  L.xg = L.proj_s + align_up(f * 2 * r * N * oe, 256);
+  L.agg = L.xg + align_up(f * r * G * (size_t)(oe + on + dg), 256);
+  L.x6 = L.agg + align_up(f * r * (size_t)h->agg_rows_bound * oe, 256);  // (rows: the upper bound known without the tables — never n_agg_rows: the size is asked before they exist)
+  L.x6p = L.x6 + align_up(x6_tab_bytes(de, oe), 256);
+  L.total = L.x6p + align_up(proj_x6_scratch_bytes(), 256) + 512;
+  return L;
 }
+static float* wide_at(const BlockArgs& a, size_t off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(a.partials) + off); }
+size_t wide_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) { return wide_layout(h, p->de, p->dg, p->oe, p->on, R).total; }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -1384,254 +1398,240 @@ int32_t launch_rows_matmul(const gnx_graphs* h, int entity, const float* A, int 
   return launch_gemm_any(w, n_tiles, R, s, name);
 }
 
-// does launch_block_wide take this block (else 1 = "not applicable": the caller's next path), and in which form
-static bool wide_applies(const gnx_graphs* h, const BlockArgs& a, bool* project_out) {
+// The forms a block takes on the wide path, decided ONCE from the block and the call's forms (form(): read inside the open FormScope) — never from the
+// phase: the projection launch and the edge launch of one block may run in different calls on different streams (GNX_PHASE_WIDE_PROJ_ONLY on the side
+// stream, GNX_PHASE_EDGE_NODE on the caller's) and must agree, on edge_n above all.  launch_block_wide applies the phase afterwards: which planned steps this call runs.
+enum class WideEdge { none, x6, x6_narrow, enc, core, edge_n, rows_gemm };  // core: a GNCore's edge update + edge FeedForward + residuals in one launch (the edge form of k_ffn_x6)
+enum class WideNode { none, x6, rows_gemm };
+struct WidePlan {
+  bool applies, project;      // launch_block_wide takes this block (else: the caller's next path) / in the node-projection form
+  bool ln_on_load;            // ef and nf can be normalised as they are loaded (BlockArgs::ln_stats)
+  bool edge_out_vec, ef_vec;  // ef' (with We and both tables of projected rows) / ef can be accessed as 16-B quads
+  bool agg_fuse;              // edge -> node sums inside the edge update's epilogue (the node update then reads ~N rows instead of all E rows of ef')
+  bool proj6, edge_n;         // the projections run as k_proj_x6 / ... in the form k_edge_n reads (destination table only; normalised rows in the source table's place)
+  WideEdge edge; WideNode node;
+  // the edge update is k_edge_x6 in one of its 128 -> 128 forms (a caller may then leave the edge rows' statistics to that kernel)
+  bool edge_x6() const { return edge == WideEdge::x6 || edge == WideEdge::core || edge == WideEdge::edge_n; }
+};
+static WidePlan wide_plan(const gnx_graphs* h, const BlockArgs& a) {
+  WidePlan p{};
   static const bool off = getenv("GNX_NO_WIDE") != nullptr;
-  if (off) return false;
+  if (off) return p;
   const int ke = a.de + 2 * a.dn + a.dg, kn = a.oe + a.dn + a.dg;
   // the matrix-core path pays when the update is a real GEMM; tiny widths stay on the other paths
-  if (std::max(std::max(ke, a.oe), std::max(kn, a.on)) < 32) return false;
-  if (a.E == 0 && a.oe > 0) return false;
+  if (std::max(std::max(ke, a.oe), std::max(kn, a.on)) < 32) return p;
+  if (a.E == 0 && a.oe > 0) return p;
   // gathered tables (node features, node projections, partial sums) are addressed with 32-bit element offsets
-  if ((size_t)h->N * (size_t)std::max(std::max(a.oe, a.dn), 1) * sizeof(float) >= (1ull << 32)) return false;
+  if ((size_t)h->N * (size_t)std::max(std::max(a.oe, a.dn), 1) * sizeof(float) >= (1ull << 32)) return p;
+  p.applies = true;
   // Node-projection form (edgefninput.jl:2-7 regrouped): W*[ef; nf_s; nf_d; gf] = We_e*ef + (We_s*nf)[src] + (We_d*nf + b')[dst].
   // The 2*dn columns of nf are multiplied once per NODE (two small GEMMs) instead of once per EDGE; the edge GEMM keeps
   // K = de and gathers two projected rows in its epilogue.  Same mathematics, different (still fixed) summation order.
   static const bool no_project = getenv("GNX_NO_PROJECT") != nullptr;
-  *project_out = !no_project && a.oe > 0 && a.dn >= 16 && a.E >= 2 * (int64_t)a.N;
-  return true;
+  const bool project = p.project = !no_project && a.oe > 0 && a.dn >= 16 && a.E >= 2 * (int64_t)a.N, big = (size_t)h->E >= 4096;
+  // LayerNorm on load: every launch that reads ef / nf is then a quad-row, quad-output GEMM with the features as mode-0 segments — the projected form, widths multiples of 4
+  p.ln_on_load = project && a.de % 4 == 0 && a.dn % 4 == 0 && a.oe % 4 == 0 && a.on % 4 == 0 && a.de <= 256 && a.dn <= 256 && a.on > 0 && al16(a.ef) && al16(a.nf) &&
+                 al16(a.We) && al16(a.Wn) && al16(a.ef_out) && al16(a.nf_out) && al16(a.ln_g[0]) && al16(a.ln_b[0]) && al16(a.ln_g[1]) && al16(a.ln_b[1]);
+  p.edge_out_vec = a.oe % 4 == 0 && al16(a.We) && al16(a.ef_out) && ((size_t)a.E * a.oe) % 4 == 0 && ((size_t)a.N * a.oe) % 4 == 0;
+  p.ef_vec = a.de % 4 == 0 && al16(a.ef) && ((size_t)a.E * a.de) % 4 == 0;
+  // agg_fuse needs quad outputs, with the projections' epilogue operands an ef whose rows are quads (launch_gemm's instantiations), and a table within 32-bit
+  // offsets.  TWO row counts: what is launched goes by n_agg_rows, the table's real size; whether the edge update is k_edge_x6 goes by agg_rows_bound, because
+  // block_wide_ln_ask asks that before the tables — and with them n_agg_rows — need exist, and the launcher must answer alike.
+  static const bool no_agg_fuse = getenv("GNX_NO_AGG_FUSE") != nullptr;
+  const auto agg_fuse = [&](int64_t rows) { return !no_agg_fuse && a.oe > 0 && a.on > 0 && p.edge_out_vec && (!project || p.ef_vec) && rows > 0 && (size_t)rows * a.oe * sizeof(float) < (1ull << 32); };
+  p.agg_fuse = agg_fuse(h->n_agg_rows);
+  const bool ln_n_al = !a.ln_stats[1] || (al16(a.ln_g[1]) && al16(a.ln_b[1]));
+  // 64 -> 2 x 128 from 4096 nodes on: both tables in one launch of k_proj_x6 (six bf16 matrix-core terms per fp32 product; gnx_edge_x6.hip).  (The tables lie a multiple of 256 bytes behind a.partials: its alignment is theirs.)
+  p.proj6 = project && proj_x6_applies(a.dn, a.oe, a.nf, a.We, a.partials, (size_t)a.N) && ln_n_al && al16(a.be);
+  // the projected edge update at 128 -> 128 on the six-term scheme (gnx_edge_x6.hip; GNX_FLAG_EDGE_FP32: k_rows_gemm on the fp32 matrix instruction instead)
+  const bool x6 = project && a.de == 128 && a.oe == 128 && a.dn > 0 && p.edge_out_vec && p.ef_vec && al16(a.ln_g[0]) && al16(a.ln_b[0]) && (agg_fuse(h->agg_rows_bound) || a.on == 0) &&
+                  !form(GNX_FLAG_EDGE_FP32) && big;
+  // ... as k_edge_n (gnx_edge_n.hip: the source side per edge from the raw 64-wide row): needs the six-term projection launch, which then makes the destination table and, under a LayerNorm, the normalised rows the edges gather
+  p.edge_n = p.proj6 && edge_n_enabled() && a.dn == 64 && x6 && al16(a.nf);
+  // ... at 128 -> at most 32 outputs without fused per-destination sums (config 4's decoder: 128 -> 3) its narrow form: one zero-padded slice (GNX_FLAG_EDGE_NARROW_FP32: this form alone back on k_rows_gemm)
+  const bool x6n = !x6 && project && a.de == 128 && a.oe >= 1 && a.oe <= 32 && a.dn > 0 && p.ef_vec && !p.agg_fuse && (!a.ln_stats[0] || (al16(a.ln_g[0]) && al16(a.ln_b[0]))) &&
+                   !form(GNX_FLAG_EDGE_FP32) && !form(GNX_FLAG_EDGE_NARROW_FP32) && big;
+  // the ENCODER form: (10, 5, .) => 128 unprojected (README ex.3's / config 4's encoder) on the six-term scheme with the row's 20 inputs assembled in registers
+  // (k_rows_gemm's packed element loader: 209 us at 1M edges against ~110 us of traffic; GNX_FLAG_EDGE_FP32 keeps it)
+  const bool enc = !project && a.de == 10 && a.dn == 5 && a.oe == 128 && !a.ln_stats[0] && !a.ln_inline_e && !a.ffe_w1 && p.edge_out_vec && (p.agg_fuse || a.on == 0) && al16(a.be) &&
+                   !form(GNX_FLAG_EDGE_FP32) && big && a.ef && a.nf;
+  p.edge = x6 ? (a.ffe_w1 ? WideEdge::core : (p.edge_n ? WideEdge::edge_n : WideEdge::x6)) : (x6n ? WideEdge::x6_narrow : (enc ? WideEdge::enc : (a.oe > 0 ? WideEdge::rows_gemm : WideEdge::none)));
+  // the node update at core widths on the six-term scheme (k_node_x6: the summed in-edge rows from the edge kernel's per-destination partial sums);
+  // its weight planes: the layer's prepared ones, or made in the projections' scratch (their planes were consumed by the projection launch)
+  const bool node_x6 = a.on > 0 && p.agg_fuse && node_x6_applies(a.oe, a.dn, a.on, a.act_n, a.nf, a.Wn, a.nf_out, (size_t)a.N) && ln_n_al && al16(a.bn) && node_x6_scratch_bytes() <= proj_x6_scratch_bytes();
+  p.node = node_x6 ? WideNode::x6 : (a.on > 0 ? WideNode::rows_gemm : WideNode::none);
+  return p;
 }
 
 // Workspace queries (outside any capture) build the handle's matrix-core tables when a forward with these widths can read them: the wide
 // block itself, or a row-wise Dense on the matrix cores (a core's FeedForward from width 32, a Chain's further layers: `rows_gemm`).
 void warm_block_wide(const gnx_graphs* h, const gnx_block_params* p, bool rows_gemm) {
-  bool need = rows_gemm;
-  if (!need && p) {
-    bool project = false;
-    need = wide_applies(h, block_probe(h, p), &project);
+  if (rows_gemm || (p && wide_plan(h, block_probe(h, p)).applies)) (void)gnx_ensure_wide_tables(h);  // a failure is not latched: the forward reports it
+}
+// one answer for the launcher and for the callers that ask before they launch (gnx_forward.hip: block_wide_ln_ask)
+bool block_wide_ln_applies(const gnx_graphs* h, const BlockArgs& a) { return wide_plan(h, a).ln_on_load; }
+bool block_wide_edge_x6_applies(const gnx_graphs* h, const BlockArgs& a) { return wide_plan(h, a).edge_x6(); }
+
+// ---- the steps of launch_block_wide: each takes (h, a, layout, plan, R, s), or the part of that it reads ----
+// fold gf into per-graph biases (one tiny launch per update function)
+static int32_t wide_fold_gf(const BlockArgs& a, const WideLayout& L, int64_t R, hipStream_t s) {
+  float *bias_e = wide_at(a, L.bias_e), *bias_n = wide_at(a, L.bias_n);
+  ProfScope ps("k_fold_bias", s);
+  if (skinny_ok(R * a.G, a.dg, std::max(a.oe, a.on))) {  // a few graphs, wide layers: one round-trip-lean GEMV kernel, both gf folds in one launch
+    const SkinnyJob je{a.gf, a.dg, (int)(R * a.G), a.dg, a.We, a.de + 2 * a.dn, a.oe, a.be, a.oe, GNX_ACT_IDENTITY, bias_e, a.oe};
+    const SkinnyJob jn{a.gf, a.dg, (int)(R * a.G), a.dg, a.Wn, a.oe + a.dn, a.on, a.bn, a.on, GNX_ACT_IDENTITY, bias_n, a.on};
+    return (a.oe > 0 || a.on > 0) ? launch_skinny2(a.oe > 0 ? je : jn, a.oe > 0 && a.on > 0 ? jn : SkinnyJob{}, s) : GNX_OK;
   }
-  if (need) (void)gnx_ensure_wide_tables(h);  // a failure is not latched: the forward reports it
+  if (a.oe > 0) GNX_LAUNCH(k_fold_bias, dim3((unsigned)a.G, (unsigned)R), dim3(128), 0, s, a.We, a.be, a.gf, a.dg, a.de + 2 * a.dn, a.oe, a.G, bias_e);
+  if (a.on > 0) GNX_LAUNCH(k_fold_bias, dim3((unsigned)a.G, (unsigned)R), dim3(128), 0, s, a.Wn, a.bn, a.gf, a.dg, a.oe + a.dn, a.on, a.G, bias_n);
+  GNX_HIP(hipGetLastError());
+  return GNX_OK;
 }
 
-// The wide path can normalise ef and nf as it loads them (BlockArgs::ln_stats): every launch that reads them is then a quad-row,
-// quad-output GEMM with the features as mode-0 segments — the projected form with widths that are multiples of 4.
-bool block_wide_ln_applies(const gnx_graphs* h, const BlockArgs& a) {
-  bool project = false;
-  if (!wide_applies(h, a, &project) || !project) return false;
-  return a.de % 4 == 0 && a.dn % 4 == 0 && a.oe % 4 == 0 && a.on % 4 == 0 && a.de <= 256 && a.dn <= 256 && a.on > 0 && al16(a.ef) && al16(a.nf) &&
-         al16(a.We) && al16(a.Wn) && al16(a.ef_out) && al16(a.nf_out) && al16(a.ln_g[0]) && al16(a.ln_b[0]) && al16(a.ln_g[1]) && al16(a.ln_b[1]);
+// the node projections Ps = We_s nf, Pd = We_d nf + b' (bias and gf fold ride on Pd), both in ONE launch: nf is read once
+static int32_t wide_project(const gnx_graphs* h, const BlockArgs& a, const WideLayout& L, const WidePlan& plan, int64_t R, hipStream_t s) {
+  float *proj_s = wide_at(a, L.proj_s), *proj_d = wide_at(a, L.proj_d);
+  const float *Ws = a.We + (size_t)a.de * a.oe, *Wd = a.We + (size_t)(a.de + a.dn) * a.oe;  // rows of the src / of the dst segment
+  const float* bias_g = a.dg > 0 ? wide_at(a, L.bias_e) : nullptr;
+  if (plan.proj6)
+    return launch_proj_x6(h->d_ntiles, (size_t)h->n_ntiles, a.nf, (size_t)a.N, a.ln_stats[1], a.ln_g[1], a.ln_b[1], Ws, Wd, a.oe, a.be, bias_g, a.G, proj_s, proj_d, R, wide_at(a, L.x6p), s,
+                          plan.edge_n, plan.edge_n && a.ln_stats[1] ? proj_s : nullptr);
+  WideArgs w{};  // (the second weight block of k_rows_gemm)
+  w.tiles = h->d_ntiles; w.row_kind = 1;
+  w.seg[0] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 0, 0};
+  w.nseg = 1;
+  if (a.ln_stats[1]) { w.seg[0].ln = 1; w.ln_stats = a.ln_stats[1]; w.ln_rep_stride = 2 * (size_t)a.N; w.ln_g = a.ln_g[1]; w.ln_b = a.ln_b[1]; }
+  w.W = Ws; w.W2 = Wd; w.OUT = a.oe; w.act = GNX_ACT_IDENTITY;
+  w.bias2 = a.be; w.bias_g2 = bias_g; w.n_graphs = a.G;  // bias (+ gf fold) rides on the dst projection
+  w.out = proj_s; w.out2 = proj_d; w.out_rep_stride = (size_t)a.N * a.oe;
+  w.fp32 = form(GNX_FLAG_EDGE_FP32 | GNX_FLAG_PROJ_FP32);
+  return launch_gemm_any(w, (unsigned)h->n_ntiles, R, s, "k_rows_gemm_proj");
 }
 
-// does the block's edge update run as k_edge_x6 (gnx_edge_x6.hip)?  One predicate for the launcher and for callers that then leave the edge rows' statistics to that kernel
-bool block_wide_edge_x6_applies(const gnx_graphs* h, const BlockArgs& a) {
-  bool project = false;
-  if (!wide_applies(h, a, &project) || !project) return false;
-  static const bool no_agg_fuse = getenv("GNX_NO_AGG_FUSE") != nullptr;
-  const bool edge_out_vec = a.oe % 4 == 0 && al16(a.We) && al16(a.ef_out) && ((size_t)a.E * a.oe) % 4 == 0 && ((size_t)a.N * a.oe) % 4 == 0;
-  const bool ef_vec = a.de % 4 == 0 && al16(a.ef) && ((size_t)a.E * a.de) % 4 == 0;
-  const bool agg_fuse = !no_agg_fuse && a.oe > 0 && a.on > 0 && edge_out_vec && ef_vec && h->agg_rows_bound > 0 && (size_t)h->agg_rows_bound * a.oe * sizeof(float) < (1ull << 32);
-  return a.de == 128 && a.oe == 128 && a.dn > 0 && edge_out_vec && ef_vec && al16(a.ln_g[0]) && al16(a.ln_b[0]) && (agg_fuse || a.on == 0) && !form(GNX_FLAG_EDGE_FP32) &&
-         (size_t)h->E >= 4096;
+// the edge update on k_rows_gemm: any widths, projected (two gathered addends in the epilogue) or with the node rows as gathered segments
+static int32_t wide_edge_rows_gemm(const gnx_graphs* h, const BlockArgs& a, const WideLayout& L, const WidePlan& plan, int64_t R, hipStream_t s) {
+  const bool project = plan.project;
+  WideArgs w{};
+  w.tiles = h->d_etiles; w.row_kind = 0;
+  int ns = 0;
+  if (a.de) {
+    w.seg[ns++] = WSeg{a.ef, (size_t)a.E * a.de, a.de, 0, 0};
+    if (a.ln_stats[0]) { w.seg[ns - 1].ln = 1; w.ln_stats = a.ln_stats[0]; w.ln_rep_stride = 2 * (size_t)a.E; w.ln_g = a.ln_g[0]; w.ln_b = a.ln_b[0]; }
+  }
+  if (a.dn && !project) {
+    w.seg[ns++] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 1, a.de};
+    w.seg[ns++] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 2, a.de + a.dn};
+  }
+  w.nseg = ns;
+  if (project) {
+    w.gadd_a = wide_at(a, L.proj_s); w.gadd_b = wide_at(a, L.proj_d); w.gadd_rep_stride = (size_t)a.N * a.oe;
+    w.pd_lds = h->n_etiles_wide_span == 0;  // every edge tile's destinations fit the kernel's LDS table
+  }
+  w.idx_a = a.rowval; w.idx_b = h->d_edge_dst; w.cp = a.colptr;
+  w.W = a.We; w.bias = project ? nullptr : a.be; w.OUT = a.oe; w.act = a.act_e;
+  w.bias_g = (!project && a.dg > 0) ? wide_at(a, L.bias_e) : nullptr; w.n_graphs = a.G;
+  w.out = a.ef_out; w.out_rep_stride = (size_t)a.E * a.oe;
+  w.colsum = a.og > 0 ? wide_at(a, L.pe) : nullptr; w.colsum_rep_stride = (size_t)h->n_etiles * (size_t)a.oe;
+  if (plan.agg_fuse) { w.agg_out = wide_at(a, L.agg); w.agg_rep_stride = (size_t)h->n_agg_rows * a.oe; w.chunk_row0 = h->d_chunk_row0; }
+  w.fp32 = form(GNX_FLAG_EDGE_FP32) || (a.oe <= 32 && form(GNX_FLAG_EDGE_NARROW_FP32));
+  return launch_gemm_any(w, (unsigned)h->n_etiles, R, s, "k_rows_gemm_edge");
 }
 
-// ... and as k_edge_n (gnx_edge_n.hip: source rows gathered raw, register epilogue)?  Needs the six-term projection launch (64-wide nodes, from 4096
-// nodes on) — launch_block_wide checks that part; a core whose edge FeedForward rides in the edge launch keeps round 4's form until that kernel is ported
-bool block_wide_edge_n_applies(const gnx_graphs* h, const BlockArgs& a) {
-  return edge_n_enabled() && a.dn == 64 && block_wide_edge_x6_applies(h, a) && al16(a.nf);
+static int32_t wide_edge_update(const gnx_graphs* h, const BlockArgs& a, const WideLayout& L, const WidePlan& plan, int64_t R, hipStream_t s) {
+  if (a.ln_inline_e && !plan.edge_x6()) return fail(GNX_ERR_INVALID_ARG, "internal: edge statistics in the kernel asked of a block that does not run k_edge_x6");
+  if (a.ffe_w1 && !(plan.edge_x6() && a.ln_inline_e)) return fail(GNX_ERR_INVALID_ARG, "internal: the edge FeedForward inside the edge update asked of a block that does not run k_edge_x6 with its own statistics");
+  EdgeLaunch e{};  // as k_edge_x6's 128 -> 128 form takes it; the other forms change what differs
+  e.tiles = h->d_etiles; e.n_tiles = (size_t)h->n_etiles; e.ef = a.ef; e.E = (size_t)a.E;
+  e.ln.stats = a.ln_stats[0]; e.ln.g = a.ln_g[0]; e.ln.b = a.ln_b[0]; e.ln.inline_stats = a.ln_inline_e != 0; e.ln.eps = a.ln_eps; e.ln.mode = a.ln_mode;
+  e.We = a.We; e.ldw = a.oe; e.psrc = wide_at(a, L.proj_s); e.pdst = wide_at(a, L.proj_d);
+  e.N = (size_t)a.N; e.src = a.rowval; e.dst = h->d_edge_dst; e.act = a.act_e; e.out = a.ef_out; e.colsum = a.og > 0 ? wide_at(a, L.pe) : nullptr;
+  e.agg_out = plan.agg_fuse ? wide_at(a, L.agg) : nullptr; e.n_agg_rows = (size_t)h->n_agg_rows; e.chunk_row0 = h->d_chunk_row0;
+  e.R = R; e.scratch = wide_at(a, L.x6); e.stream = s;
+  switch (plan.edge) {
+    case WideEdge::none: break;
+    case WideEdge::rows_gemm: return wide_edge_rows_gemm(h, a, L, plan, R, s);
+    case WideEdge::x6: case WideEdge::x6_narrow: return launch_edge_x6(e, a.oe);  // (narrow: never with per-destination sums or statistics of its own — the plan saw to both)
+    case WideEdge::enc: e.psrc = a.nf; return launch_edge_enc(e, a.be, a.dg > 0 ? wide_at(a, L.bias_e) : nullptr, a.G);  // unprojected: the raw node rows, both sides
+    case WideEdge::edge_n: if (!a.ln_stats[1]) e.psrc = a.nf; return launch_edge_n(e);  // the source rows raw, or as the projection launch normalised them (in Ps' place)
+    case WideEdge::core: {  // ef_out receives the CORE's edge output
+      if (plan.edge_n) return fail(GNX_ERR_INVALID_ARG, "internal: the one-launch core form was asked of a block whose projections are k_edge_n's");
+      gnx_ffn ff{};
+      ff.fc1.weight = a.ffe_w1; ff.fc1.bias = a.ffe_b1; ff.fc1.act = a.ffe_act1; ff.fc2.weight = a.ffe_w2; ff.fc2.bias = a.ffe_b2; ff.fc2.act = a.ffe_act2;
+      const gnx_layernorm ln2{a.ffe_g2, a.ffe_be2};
+      return launch_core_edge_x6(e, ff, &ln2, a.ffe_scratch);
+    }
+  }
+  return GNX_OK;
 }
 
+static int32_t wide_node_update(const gnx_graphs* h, const BlockArgs& a, const WideLayout& L, const WidePlan& plan, int64_t R, hipStream_t s) {
+  if (plan.node == WideNode::none) return GNX_OK;
+  float *agg_tab = wide_at(a, L.agg), *colsum = a.og > 0 ? wide_at(a, L.pn) : nullptr;
+  const float* bias_g = a.dg > 0 ? wide_at(a, L.bias_n) : nullptr;
+  const size_t n_nt = (size_t)h->n_ntiles;
+  if (plan.node == WideNode::x6)
+    return launch_node_x6(h->d_ntiles, n_nt, a.nf, (size_t)a.N, a.ln_stats[1], a.ln_g[1], a.ln_b[1], agg_tab, (size_t)h->n_agg_rows, h->d_node_agg_row, h->d_node_agg_parts,
+                          h->d_node_agg_chunk, h->d_chunk_row0, a.Wn, a.on, a.bn, bias_g, a.G, a.act_n, a.nf_out, colsum, R, wide_at(a, L.x6p), s);
+  WideArgs w{};
+  w.tiles = h->d_ntiles; w.row_kind = 1;
+  int ns = 0;
+  if (a.oe && plan.agg_fuse) {
+    w.seg[ns++] = WSeg{agg_tab, (size_t)h->n_agg_rows * a.oe, a.oe, 4, 0};
+    w.node_agg_row = h->d_node_agg_row; w.node_agg_parts = h->d_node_agg_parts; w.node_agg_chunk = h->d_node_agg_chunk; w.chunk_row0 = h->d_chunk_row0;
+  } else if (a.oe) {
+    w.seg[ns++] = WSeg{a.ef_out, (size_t)a.E * a.oe, a.oe, 3, 0};
+  }
+  if (a.dn) {
+    w.seg[ns++] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 0, a.oe};
+    if (a.ln_stats[1]) { w.seg[ns - 1].ln = 1; w.ln_stats = a.ln_stats[1]; w.ln_rep_stride = 2 * (size_t)a.N; w.ln_g = a.ln_g[1]; w.ln_b = a.ln_b[1]; }
+  }
+  w.nseg = ns;
+  w.idx_a = nullptr; w.idx_b = nullptr; w.cp = a.colptr;
+  w.W = a.Wn; w.bias = a.bn; w.bias_g = bias_g; w.n_graphs = a.G; w.OUT = a.on; w.act = a.act_n;
+  w.out = a.nf_out; w.out_rep_stride = (size_t)a.N * a.on;
+  w.colsum = colsum; w.colsum_rep_stride = n_nt * (size_t)a.on;
+  w.fp32 = form(GNX_FLAG_EDGE_FP32 | GNX_FLAG_PROJ_FP32);
+  return launch_gemm_any(w, (unsigned)n_nt, R, s, "k_rows_gemm_node");
+}
+
+static int32_t wide_graph_update(const gnx_graphs* h, const BlockArgs& a, const WideLayout& L, int64_t R, hipStream_t s) {
+  float *pe2 = wide_at(a, L.pe2), *pn2 = wide_at(a, L.pn2);
+  const int S = L.S, Kg = a.oe + a.on + a.dg;
+  ProfScope ps("k_graph_wide", s);
+  if (a.oe > 0 || a.on > 0) {
+    const ColsumJob je{a.oe > 0 ? wide_at(a, L.pe) : nullptr, (size_t)h->n_etiles * (size_t)a.oe, h->d_etile_off, a.oe, pe2};
+    const ColsumJob jn{a.on > 0 ? wide_at(a, L.pn) : nullptr, (size_t)h->n_ntiles * (size_t)a.on, h->d_ntile_off, a.on, pn2};
+    GNX_LAUNCH(k_colsum_slices, dim3(2u * (unsigned)a.G, (unsigned)S, (unsigned)R), dim3(128), 0, s, je, jn, S, a.G);
+  }
+  if (skinny_ok(R * a.G, Kg, a.og)) {  // small batch, wide layers: assemble Xg, then the round-trip-lean GEMV kernel
+    float* xg = wide_at(a, L.xg);
+    GNX_LAUNCH(k_graph_x, dim3((unsigned)a.G, (unsigned)R), dim3(256), 0, s, pe2, pn2, S, a, xg);
+    if (int32_t rc = launch_skinny2(SkinnyJob{xg, Kg, (int)(R * a.G), Kg, a.Wg, 0, a.og, a.bg, a.og, a.act_g, a.gf_out, a.og}, SkinnyJob{}, s)) return rc;
+  } else {
+    const size_t lds = sizeof(float) * ((size_t)(a.oe + a.on + a.dg + 4) + 256 * 33 + 4);
+    GNX_LAUNCH(k_graph_final, dim3((unsigned)a.G, (unsigned)R), dim3(256), lds, s, pe2, pn2, S, a);
+  }
+  GNX_HIP(hipGetLastError());
+  return GNX_OK;
+}
+
+// plan -> layout -> gf fold -> projections -> edge update -> node update -> graph phase; 1 = "not applicable": the caller's next path
 int32_t launch_block_wide(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
-  bool project = false;
-  if (!wide_applies(h, a, &project)) return 1;
-  if ((a.ln_stats[0] || a.ln_stats[1]) && !block_wide_ln_applies(h, a)) return fail(GNX_ERR_INVALID_ARG, "launch_block_wide: LayerNorm on load is not applicable to this block");
-  if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw;
-  const size_t n_et = (size_t)h->n_etiles, n_nt = (size_t)h->n_ntiles;
-  // workspace layout inside a.partials (sized by gnx_block_workspace_bytes >= wide_workspace_bytes)
-  float* pe = a.partials;
-  float* pn = pe + (size_t)R * n_et * a.oe;
-  const int S = wide_slices(h);
-  float* stage2 = reinterpret_cast<float*>(reinterpret_cast<char*>(a.partials) +
-                                           align_up(sizeof(float) * (size_t)R * (n_et * a.oe + n_nt * a.on), 256));
-  float* pe2 = stage2;
-  float* pn2 = pe2 + (size_t)R * h->G * S * a.oe;
-  float* bias_e = reinterpret_cast<float*>(reinterpret_cast<char*>(stage2) + align_up(sizeof(float) * (size_t)R * h->G * S * (a.oe + a.on), 256));
-  float* bias_n = bias_e + (size_t)R * h->G * a.oe;
-  float* proj_s = reinterpret_cast<float*>(reinterpret_cast<char*>(bias_e) + align_up(sizeof(float) * (size_t)R * h->G * (a.oe + a.on), 256));
-  float* proj_d = proj_s + (size_t)R * h->N * a.oe;
-  float* agg_tab = reinterpret_cast<float*>(reinterpret_cast<char*>(proj_s) + align_up(sizeof(float) * 2 * (size_t)R * h->N * a.oe, 256) +
-                                            align_up(sizeof(float) * (size_t)R * h->G * (size_t)(a.oe + a.on + a.dg), 256));
-  void* x6_tab = reinterpret_cast<char*>(agg_tab) + align_up(sizeof(float) * (size_t)R * (size_t)h->agg_rows_bound * (size_t)a.oe, 256);
-  void* x6p_tab = reinterpret_cast<char*>(x6_tab) + align_up(x6_tab_bytes(a.de, a.oe), 256);
-  // edge -> node sums inside the edge GEMM's epilogue (the node GEMM then reads ~N rows instead of all E rows of ef')
-  static const bool no_agg_fuse = getenv("GNX_NO_AGG_FUSE") != nullptr;
-  // (needs quad outputs, and — with the projections' epilogue operands — an ef whose rows are quads: see launch_gemm's instantiations)
-  const bool edge_out_vec = a.oe % 4 == 0 && al16(a.We) && al16(a.ef_out) && ((size_t)a.E * a.oe) % 4 == 0 && ((size_t)a.N * a.oe) % 4 == 0;
-  const bool ef_vec = a.de % 4 == 0 && al16(a.ef) && ((size_t)a.E * a.de) % 4 == 0;
-  const bool agg_fuse = !no_agg_fuse && (phase & (GNX_PHASE_EDGE_NODE | GNX_PHASE_WIDE_PROJ_ONLY)) && a.oe > 0 && a.on > 0 && edge_out_vec && (!project || ef_vec) && h->n_agg_rows > 0 &&
-                        (size_t)h->n_agg_rows * a.oe * sizeof(float) < (1ull << 32);
+  const bool warm = h->wide_built.load(std::memory_order_acquire);  // (read before the plan: n_agg_rows, which the plan reads, exists only once the tables do)
+  WidePlan plan = wide_plan(h, a);
+  if (!plan.applies) return 1;
+  if ((a.ln_stats[0] || a.ln_stats[1]) && !plan.ln_on_load) return fail(GNX_ERR_INVALID_ARG, "launch_block_wide: LayerNorm on load is not applicable to this block");
+  if (!warm) {  // a handle no workspace query warmed: the tables are built here (not for a block this path declines), then the plan is made again
+    if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw;
+    plan = wide_plan(h, a);
+  }
+  const WideLayout L = wide_layout(h, a.de, a.dg, a.oe, a.on, R);  // inside a.partials (sized by gnx_block_workspace_bytes >= wide_workspace_bytes)
   int32_t rc = GNX_OK;
-  const bool prep = (phase & GNX_PHASE_WIDE_PROJ_ONLY) || ((phase & GNX_PHASE_EDGE_NODE) && !(phase & GNX_PHASE_WIDE_PROJ_DONE));  // gf fold + node projections
-  if (prep && a.dg > 0) {  // fold gf into per-graph biases (one tiny launch per update function)
-    ProfScope ps("k_fold_bias", s);
-    if (skinny_ok(R * a.G, a.dg, std::max(a.oe, a.on))) {  // a few graphs, wide layers: one round-trip-lean GEMV kernel per function
-      const SkinnyJob je{a.gf, a.dg, (int)(R * a.G), a.dg, a.We, a.de + 2 * a.dn, a.oe, a.be, a.oe, GNX_ACT_IDENTITY, bias_e, a.oe};
-      const SkinnyJob jn{a.gf, a.dg, (int)(R * a.G), a.dg, a.Wn, a.oe + a.dn, a.on, a.bn, a.on, GNX_ACT_IDENTITY, bias_n, a.on};
-      if (a.oe > 0 && a.on > 0) { if ((rc = launch_skinny2(je, jn, s))) return rc; }  // both gf folds in one launch
-      else if (a.oe > 0) { if ((rc = launch_skinny2(je, SkinnyJob{}, s))) return rc; }
-      else if (a.on > 0) { if ((rc = launch_skinny2(jn, SkinnyJob{}, s))) return rc; }
-    } else {
-    if (a.oe > 0) GNX_LAUNCH(k_fold_bias, dim3((unsigned)a.G, (unsigned)R), dim3(128), 0, s, a.We, a.be, a.gf, a.dg, a.de + 2 * a.dn, a.oe, a.G, bias_e);
-    if (a.on > 0) GNX_LAUNCH(k_fold_bias, dim3((unsigned)a.G, (unsigned)R), dim3(128), 0, s, a.Wn, a.bn, a.gf, a.dg, a.oe + a.dn, a.on, a.G, bias_n);
-    }
-    GNX_HIP(hipGetLastError());
-  }
-  const bool proj6 = project && proj_x6_applies(a.dn, a.oe, a.nf, a.We, proj_s, (size_t)a.N) && (!a.ln_stats[1] || (al16(a.ln_g[1]) && al16(a.ln_b[1]))) && al16(a.be);
-  // k_edge_n's form (gnx_edge_n.hip): the source side multiplied per edge from the raw 64-wide row — the projection launch then produces the
-  // destination table and, under a LayerNorm, the normalised rows the edges gather (in the source table's place).  One predicate for both launches
-  // (they may run in different calls: GNX_PHASE_WIDE_PROJ_ONLY on the side stream, GNX_PHASE_EDGE_NODE on the caller's): it depends on the block, never on the phase.
-  const bool edge_n = proj6 && block_wide_edge_n_applies(h, a);
-  if (prep && proj6) {
-    // 64 -> 2 x 128 from 4096 nodes on: both tables in one launch of k_proj_x6 (six bf16 matrix-core terms per fp32 product; gnx_edge_x6.hip)
-    if ((rc = launch_proj_x6(h->d_ntiles, n_nt, a.nf, (size_t)a.N, a.ln_stats[1], a.ln_g[1], a.ln_b[1], a.We + (size_t)a.de * a.oe, a.We + (size_t)(a.de + a.dn) * a.oe, a.oe, a.be,
-                             a.dg > 0 ? bias_e : nullptr, a.G, proj_s, proj_d, R, x6p_tab, s, edge_n, edge_n && a.ln_stats[1] ? proj_s : nullptr)))
-      return rc;
-  } else
-  if (prep && project) {  // both projections in ONE launch (the second weight block of k_rows_gemm): nf is read once
-    WideArgs w{};
-    w.tiles = h->d_ntiles; w.row_kind = 1;
-    w.seg[0] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 0, 0};
-    w.nseg = 1;
-    if (a.ln_stats[1]) { w.seg[0].ln = 1; w.ln_stats = a.ln_stats[1]; w.ln_rep_stride = 2 * (size_t)a.N; w.ln_g = a.ln_g[1]; w.ln_b = a.ln_b[1]; }
-    w.W = a.We + (size_t)a.de * a.oe;              // rows of the src segment
-    w.W2 = a.We + (size_t)(a.de + a.dn) * a.oe;    // rows of the dst segment: bias (+ gf fold) rides on the dst projection
-    w.bias2 = a.be; w.bias_g2 = a.dg > 0 ? bias_e : nullptr; w.n_graphs = a.G;
-    w.OUT = a.oe; w.act = GNX_ACT_IDENTITY;
-    w.out = proj_s; w.out2 = proj_d; w.out_rep_stride = (size_t)a.N * a.oe;
-    w.fp32 = form(GNX_FLAG_EDGE_FP32 | GNX_FLAG_PROJ_FP32);
-    if ((rc = launch_gemm_any(w, (unsigned)n_nt, R, s, "k_rows_gemm_proj"))) return rc;
-  }
-  // the projected edge update at 128 -> 128 as six bf16 matrix-core terms per fp32 product (gnx_edge_x6.hip)
-  // (GNX_FLAG_EDGE_FP32: k_rows_gemm on the fp32 matrix instruction instead)
-  const bool edge_x6 = (phase & 1) && block_wide_edge_x6_applies(h, a);
-  if (a.ln_inline_e && (phase & 1) && !edge_x6) return fail(GNX_ERR_INVALID_ARG, "internal: edge statistics in the kernel asked of a block that does not run k_edge_x6");
-  if (a.ffe_w1 && (phase & 1) && !(edge_x6 && a.ln_inline_e)) return fail(GNX_ERR_INVALID_ARG, "internal: the edge FeedForward inside the edge update asked of a block that does not run k_edge_x6 with its own statistics");
-  // ... and at 128 -> at most 32 outputs without fused per-destination sums (config 4's decoder: 128 -> 3) its narrow form: one zero-padded slice
-  const bool edge_x6n = (phase & 1) && !edge_x6 && project && a.de == 128 && a.oe >= 1 && a.oe <= 32 && a.dn > 0 && ef_vec && !agg_fuse &&
-                        (!a.ln_stats[0] || (al16(a.ln_g[0]) && al16(a.ln_b[0]))) && !form(GNX_FLAG_EDGE_FP32) && !form(GNX_FLAG_EDGE_NARROW_FP32) &&
-                        (size_t)h->E >= 4096;  // (GNX_FLAG_EDGE_NARROW_FP32: this form alone back on k_rows_gemm)
-  // the ENCODER form: (10, 5, .) => 128 unprojected (README ex.3's / config 4's encoder) on the six-term scheme with the row's 20 inputs assembled in registers
-  // (k_rows_gemm's packed element loader: 209 us at 1M edges against ~110 us of traffic; GNX_FLAG_EDGE_FP32 keeps it)
-  const bool edge_enc = (phase & 1) && !project && a.de == 10 && a.dn == 5 && a.oe == 128 && !a.ln_stats[0] && !a.ln_inline_e && !a.ffe_w1 && edge_out_vec && (agg_fuse || a.on == 0) &&
-                        al16(a.be) && !form(GNX_FLAG_EDGE_FP32) && (size_t)h->E >= 4096 && a.ef && a.nf;
-  if (edge_x6n) {
-    if ((rc = launch_edge_x6(h->d_etiles, n_et, a.ef, (size_t)a.E, a.ln_stats[0], a.ln_g[0], a.ln_b[0], a.We, a.oe, proj_s, proj_d, (size_t)a.N, a.rowval, h->d_edge_dst, a.act_e,
-                             a.ef_out, a.og > 0 ? pe : nullptr, nullptr, 0, nullptr, R, x6_tab, s, false, 0.f, 0, a.oe)))
-      return rc;
-  } else
-  if (edge_enc) {
-    if ((rc = launch_edge_enc(h->d_etiles, n_et, a.ef, (size_t)a.E, a.nf, (size_t)a.N, a.We, a.oe, a.be, a.dg > 0 ? bias_e : nullptr, a.G, a.rowval, h->d_edge_dst, a.act_e, a.ef_out,
-                              a.og > 0 ? pe : nullptr, agg_fuse ? agg_tab : nullptr, (size_t)h->n_agg_rows, h->d_chunk_row0, R, x6_tab, s)))
-      return rc;
-  } else
-  if (edge_x6 && a.ffe_w1 && edge_n) {
-    return fail(GNX_ERR_INVALID_ARG, "internal: the one-launch core form was asked of a block whose projections are k_edge_n's");
-  } else
-  if (edge_x6 && a.ffe_w1) {  // GNCore: edge update + edge FeedForward + residuals in one launch (edge form of k_ffn_x6); ef_out receives the CORE's edge output
-    gnx_ffn ff{};
-    ff.fc1.weight = a.ffe_w1; ff.fc1.bias = a.ffe_b1; ff.fc1.act = a.ffe_act1; ff.fc2.weight = a.ffe_w2; ff.fc2.bias = a.ffe_b2; ff.fc2.act = a.ffe_act2;
-    const gnx_layernorm ln1{a.ln_g[0], a.ln_b[0]}, ln2{a.ffe_g2, a.ffe_be2};
-    if ((rc = launch_core_edge_x6(h->d_etiles, n_et, a.ef, (size_t)a.E, &ln1, a.ln_eps, a.ln_mode, a.We, a.oe, proj_s, proj_d, (size_t)a.N, a.rowval, h->d_edge_dst, a.act_e,
-                                  a.og > 0 ? pe : nullptr, agg_fuse ? agg_tab : nullptr, (size_t)h->n_agg_rows, h->d_chunk_row0, ff, &ln2, a.ef_out, R, x6_tab, a.ffe_scratch, s)))
-      return rc;
-  } else
-  if (edge_x6 && edge_n) {
-    if ((rc = launch_edge_n(h->d_etiles, n_et, a.ef, (size_t)a.E, a.ln_stats[0], a.ln_g[0], a.ln_b[0], a.We, a.oe, a.ln_stats[1] ? proj_s : a.nf, proj_d, (size_t)a.N, a.rowval,
-                            h->d_edge_dst, a.act_e, a.ef_out, a.og > 0 ? pe : nullptr, agg_fuse ? agg_tab : nullptr, (size_t)h->n_agg_rows, h->d_chunk_row0, R, x6_tab, s,
-                            a.ln_inline_e != 0, a.ln_eps, a.ln_mode)))
-      return rc;
-  } else
-  if (edge_x6) {
-    if ((rc = launch_edge_x6(h->d_etiles, n_et, a.ef, (size_t)a.E, a.ln_stats[0], a.ln_g[0], a.ln_b[0], a.We, a.oe, proj_s, proj_d, (size_t)a.N, a.rowval, h->d_edge_dst, a.act_e,
-                             a.ef_out, a.og > 0 ? pe : nullptr, agg_fuse ? agg_tab : nullptr, (size_t)h->n_agg_rows, h->d_chunk_row0, R, x6_tab, s, a.ln_inline_e != 0, a.ln_eps,
-                             a.ln_mode)))
-      return rc;
-  } else
-  if ((phase & 1) && a.oe > 0) {
-    WideArgs w{};
-    w.tiles = h->d_etiles; w.row_kind = 0;
-    int ns = 0;
-    if (a.de) {
-      w.seg[ns++] = WSeg{a.ef, (size_t)a.E * a.de, a.de, 0, 0};
-      if (a.ln_stats[0]) { w.seg[ns - 1].ln = 1; w.ln_stats = a.ln_stats[0]; w.ln_rep_stride = 2 * (size_t)a.E; w.ln_g = a.ln_g[0]; w.ln_b = a.ln_b[0]; }
-    }
-    if (a.dn && !project) {
-      w.seg[ns++] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 1, a.de};
-      w.seg[ns++] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 2, a.de + a.dn};
-    }
-    w.nseg = ns;
-    if (project) {
-      w.gadd_a = proj_s; w.gadd_b = proj_d; w.gadd_rep_stride = (size_t)a.N * a.oe;
-      w.pd_lds = h->n_etiles_wide_span == 0;  // every edge tile's destinations fit the kernel's LDS table
-    }
-    w.idx_a = a.rowval; w.idx_b = h->d_edge_dst; w.cp = a.colptr;
-    w.W = a.We; w.bias = project ? nullptr : a.be; w.OUT = a.oe; w.act = a.act_e;
-    w.bias_g = (!project && a.dg > 0) ? bias_e : nullptr; w.n_graphs = a.G;
-    w.out = a.ef_out; w.out_rep_stride = (size_t)a.E * a.oe;
-    w.colsum = a.og > 0 ? pe : nullptr; w.colsum_rep_stride = n_et * (size_t)a.oe;
-    if (agg_fuse) { w.agg_out = agg_tab; w.agg_rep_stride = (size_t)h->n_agg_rows * a.oe; w.chunk_row0 = h->d_chunk_row0; }
-    w.fp32 = form(GNX_FLAG_EDGE_FP32) || (a.oe <= 32 && form(GNX_FLAG_EDGE_NARROW_FP32));
-    if ((rc = launch_gemm_any(w, (unsigned)n_et, R, s, "k_rows_gemm_edge"))) return rc;
-  }
-  // the node update at core widths on the six-term scheme (k_node_x6: the summed in-edge rows from the edge kernel's per-destination partial sums);
-  // its weight planes: the layer's prepared ones, or made here in the projections' scratch (their planes were consumed by the projection launch)
-  const bool node_x6 = (phase & 1) && a.on > 0 && agg_fuse && node_x6_applies(a.oe, a.dn, a.on, a.act_n, a.nf, a.Wn, a.nf_out, (size_t)a.N) &&
-                       (!a.ln_stats[1] || (al16(a.ln_g[1]) && al16(a.ln_b[1]))) && al16(a.bn) && node_x6_scratch_bytes() <= proj_x6_scratch_bytes();
-  if (node_x6) {
-    if ((rc = launch_node_x6(h->d_ntiles, n_nt, a.nf, (size_t)a.N, a.ln_stats[1], a.ln_g[1], a.ln_b[1], agg_tab, (size_t)h->n_agg_rows, h->d_node_agg_row, h->d_node_agg_parts,
-                             h->d_node_agg_chunk, h->d_chunk_row0, a.Wn, a.on, a.bn, a.dg > 0 ? bias_n : nullptr, a.G, a.act_n, a.nf_out, a.og > 0 ? pn : nullptr, R, x6p_tab, s)))
-      return rc;
-  } else
-  if ((phase & 1) && a.on > 0) {
-    WideArgs w{};
-    w.tiles = h->d_ntiles; w.row_kind = 1;
-    int ns = 0;
-    if (a.oe && agg_fuse) {
-      w.seg[ns++] = WSeg{agg_tab, (size_t)h->n_agg_rows * a.oe, a.oe, 4, 0};
-      w.node_agg_row = h->d_node_agg_row; w.node_agg_parts = h->d_node_agg_parts; w.node_agg_chunk = h->d_node_agg_chunk; w.chunk_row0 = h->d_chunk_row0;
-    } else if (a.oe) {
-      w.seg[ns++] = WSeg{a.ef_out, (size_t)a.E * a.oe, a.oe, 3, 0};
-    }
-    if (a.dn) {
-      w.seg[ns++] = WSeg{a.nf, (size_t)a.N * a.dn, a.dn, 0, a.oe};
-      if (a.ln_stats[1]) { w.seg[ns - 1].ln = 1; w.ln_stats = a.ln_stats[1]; w.ln_rep_stride = 2 * (size_t)a.N; w.ln_g = a.ln_g[1]; w.ln_b = a.ln_b[1]; }
-    }
-    w.nseg = ns;
-    w.idx_a = nullptr; w.idx_b = nullptr; w.cp = a.colptr;
-    w.W = a.Wn; w.bias = a.bn; w.OUT = a.on; w.act = a.act_n;
-    w.bias_g = a.dg > 0 ? bias_n : nullptr; w.n_graphs = a.G;
-    w.out = a.nf_out; w.out_rep_stride = (size_t)a.N * a.on;
-    w.colsum = a.og > 0 ? pn : nullptr; w.colsum_rep_stride = n_nt * (size_t)a.on;
-    w.fp32 = form(GNX_FLAG_EDGE_FP32 | GNX_FLAG_PROJ_FP32);
-    if ((rc = launch_gemm_any(w, (unsigned)n_nt, R, s, "k_rows_gemm_node"))) return rc;
-  }
-  if ((phase & 2) && a.og > 0) {
-    ProfScope ps("k_graph_wide", s);
-    if (a.oe > 0 || a.on > 0) {
-      const ColsumJob je{a.oe > 0 ? pe : nullptr, n_et * (size_t)a.oe, h->d_etile_off, a.oe, pe2};
-      const ColsumJob jn{a.on > 0 ? pn : nullptr, n_nt * (size_t)a.on, h->d_ntile_off, a.on, pn2};
-      GNX_LAUNCH(k_colsum_slices, dim3(2u * (unsigned)a.G, (unsigned)S, (unsigned)R), dim3(128), 0, s, je, jn, S, a.G);
-    }
-    const int Kg = a.oe + a.on + a.dg;
-    if (skinny_ok(R * a.G, Kg, a.og)) {  // small batch, wide layers: assemble Xg, then the round-trip-lean GEMV kernel
-      float* xg = reinterpret_cast<float*>(reinterpret_cast<char*>(proj_s) + align_up(sizeof(float) * 2 * (size_t)R * h->N * a.oe, 256));
-      GNX_LAUNCH(k_graph_x, dim3((unsigned)a.G, (unsigned)R), dim3(256), 0, s, pe2, pn2, S, a, xg);
-      if ((rc = launch_skinny(xg, Kg, (int)(R * a.G), Kg, a.Wg, 0, a.og, a.bg, a.og, a.act_g, a.gf_out, a.og, s))) return rc;
-    } else {
-      const size_t lds = sizeof(float) * ((size_t)(a.oe + a.on + a.dg + 4) + 256 * 33 + 4);
-      GNX_LAUNCH(k_graph_final, dim3((unsigned)a.G, (unsigned)R), dim3(256), lds, s, pe2, pn2, S, a);
-    }
-    GNX_HIP(hipGetLastError());
-  }
+  const bool prep = (phase & GNX_PHASE_WIDE_PROJ_ONLY) || ((phase & GNX_PHASE_EDGE_NODE) && !(phase & GNX_PHASE_WIDE_PROJ_DONE));  // gf fold + node projections: this call's, unless a GNX_PHASE_WIDE_PROJ_ONLY call ran them
+  if (prep && a.dg > 0 && (rc = wide_fold_gf(a, L, R, s))) return rc;
+  if (prep && plan.project && (rc = wide_project(h, a, L, plan, R, s))) return rc;
+  if ((phase & GNX_PHASE_EDGE_NODE) && ((rc = wide_edge_update(h, a, L, plan, R, s)) || (rc = wide_node_update(h, a, L, plan, R, s)))) return rc;
+  if ((phase & GNX_PHASE_GRAPH) && a.og > 0) return wide_graph_update(h, a, L, R, s);
   return GNX_OK;
 }
 
