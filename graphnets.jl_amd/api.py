@@ -1456,6 +1456,7 @@ class BlockPlan:
         step, in order.  Exactly `len(sets)` forwards (bit-identical outputs); where the two-launch narrow form runs, step i's graph update rides at
         the front of a later launch (step i + 2's: neighbouring steps run on two streams) and the last ones are flushed inside the call: every output is complete when the enqueued work is.
         Consecutive steps must use different workspaces and gf outputs to be chained (else the step simply runs unchained).
+        Eight neighbouring steps whose buffers do not overlap share one launch (GNX_STEPS_RUN_MAX; same bits): rotate over at least eight buffer sets.
         A bfloat16 plan: `gnx_block_forward_steps_typed` (every feature tensor of every step bf16, checked before the call)."""
         steps = [(b["ef"], b["nf"], b["gf"], *b["out"], b["ws"]) if isinstance(b, dict) else tuple(b) for b in sets]
         if self.bf16:

@@ -73,6 +73,21 @@ struct BlockArgs {
   int prev_blocks;
 };
 
+// A run of gnx_block_forward_steps (k_block_wave_run, k_graph_run): Z neighbouring steps whose buffers do not overlap share one launch,
+// gridDim.y = Z.  The graph, the weights and the widths are the launch's BlockArgs; what differs per step is one RunSlot, and the table
+// travels BY VALUE as the second kernel argument (a captured launch keeps its contents, not a pointer to them).
+struct RunSlot {
+  const float *ef, *nf, *gf;
+  float *ef_out, *nf_out, *gf_out;
+  float* partials;
+};
+constexpr int kRunSlots = 8;
+struct RunTable {
+  RunSlot slot[kRunSlots];
+};
+// the table's place in the kernel-argument segment of (BlockArgs, RunTable, ...)
+constexpr unsigned kRunTableOffset = (unsigned)((sizeof(BlockArgs) + 7) / 8 * 8);
+
 // relu as ONE v_max_f32.  fmaxf(x, 0.f) compiles to two under the default IEEE mode: a canonicalising v_max_f32 x, x, x in front of the
 // maximum whenever the compiler cannot see that x is the result of an arithmetic instruction (the packed FMAs of the streamed products are
 // inline asm) — 125 of the 3 700 vector instructions of the narrow core kernel.  (NaN: v_max_f32 returns the other operand, as fmaxf does.)

@@ -430,18 +430,38 @@ static bool steps_overlap_applies(const gnx_graphs* h, const gnx_block_params* p
   return block_narrow_takes(h, block_probe(h, p), s);
 }
 
+// The most steps the loop below puts into one launch: GNX_STEPS_RUN_MAX (read once; 1: one launch per step, the schedule before runs),
+// clamped to the table's slots.  The default is the measured best of 2, 4 and 8 on the 1M-edge graph (profiles/steps_runs_c2.md): what a run
+// gains grows with its length, and two shorter runs side by side on two streams gain nothing over one.
+constexpr int kStepsRunDefault = 8;
+static_assert(kRunMax == kRunSlots, "gnx_step_hazard.h groups what gnx_device.h's table holds");
+static int steps_run_max() {
+  static const int v = [] {
+    const char* e = getenv("GNX_STEPS_RUN_MAX");
+    const int n = e && *e ? atoi(e) : kStepsRunDefault;
+    return n < 1 ? 1 : (n > kRunMax ? kRunMax : n);
+  }();
+  return v;
+}
+
 // The loop of gnx_block_forward_steps (bf16 rows: gnx_block_forward_steps_typed on the native path), on one stream or — `overlap` — on two.  The
 // caller holds the DeviceTurn and the FormScope.
 static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_block_step* steps, int64_t n_steps, int64_t R,
                               uint32_t flags, void* stream, bool overlap) {
-  // Two streams: even steps on the caller's, odd steps on a side stream of the handle's pool (taken as gnx_core_forward takes it), so that
-  // step i + 1's launch fills the slots that step i's ramp and drain leave idle and the per-launch cost of one hides under the other.
-  // Every set taken, GNX_FLAG_NO_FORK, the per-kernel profiler on, or not the fused narrow kernel: one stream, the loop as before.
+  // The unit of the schedule is the RUN (gnx_step_hazard.h): steps_run_max() neighbouring steps no two of which conflict — or the last four
+  // or more of the loop — issued as ONE block launch with a slot per step and one launch for their graph updates: a ramp, a drain and a
+  // dispatch per run instead of per step.  Where the next steps are not such a window (a conflict among them, an invalid step, R > 1,
+  // widths without a run kernel, the off-switch) the step is a run of its own: a chained step as before, its graph update pending until the
+  // next launch on its stream.
+  // Two streams: even runs on the caller's, odd runs on a side stream of the handle's pool (taken as gnx_core_forward takes it), so that
+  // run j + 1's launch fills the slots that run j's ramp and drain leave idle and the per-launch cost of one hides under the other.
+  // Every set taken, GNX_FLAG_NO_FORK, the per-kernel profiler on, or not the fused narrow kernel: one stream, the runs in order.
   const AuxHold hold = overlap ? take_aux(h, true) : AuxHold{};
   const gnx_graphs::AuxSet* aux = hold.set;
+  const bool two = aux != nullptr;
   hipStream_t str[2] = {(hipStream_t)stream, aux ? aux->stream : nullptr};
-  // the pending graph update of each stream: step i's rides at the front of the next launch on ITS stream (step i + 1's on
-  // one stream, step i + 2's on two)
+  // the pending graph update of each stream: a one-step run's rides at the front of the next ONE-STEP launch on ITS stream (run j + 1's on
+  // one stream, run j + 2's on two); a launch of several steps has no such front and the update is flushed ahead of it
   gnx_pending_update pend[2]{};
   auto flush = [&](int k) -> int32_t {
     if (!pend[k].workspace) return GNX_OK;
@@ -459,41 +479,61 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
   // per feature: 4 or 2 bytes; the workspace extent is the workspace query's (bf16 on this path: the native kernels, no staging)
   const size_t elem_bytes = bf16 ? 2 : sizeof(float);
   const size_t ws_extent = !valid ? 0 : bf16 ? typed_ws(h, p, R, true).total : block_ws(h, p, R).total;
-  if (!aux) {
-    StepSpans prev;
-    for (int64_t i = 0; i < n_steps; ++i) {
-      const gnx_block_step& st = steps[i];
-      // a step whose buffers overlap its predecessor's (a shared workspace / gf_out, or gf' read as the next step's input) cannot start
-      // before that one's graph update has run
-      const StepSpans cur = valid ? step_spans(h, p, R, st, elem_bytes, ws_extent) : StepSpans{};
-      if (pend[0].workspace && (pend[0].workspace == st.workspace || (p && p->og > 0 && pend[0].gf_out == st.gf_out) || steps_conflict(cur, prev))) {
-        if (int32_t rc = flush(0)) return rc;
-      }
-      prev = cur;
-      gnx_pending_update next{};
-      if (int32_t rc = run(st, 0, &next)) {
-        // (an argument error of step i: what is pending belongs to step i - 1, whose arguments were valid — finish it, report the error)
-        (void)flush(0);
-        return rc;
-      }
-      pend[0] = next;
+  // several steps per launch: replicas use blockIdx.y themselves; the widths and the batch must be ones with a run kernel (asked at the first candidate)
+  // (the per-kernel profiler attributes time launch by launch, one step each: with it on every run is one step)
+  bool can_fuse = valid && R == 1 && !(flags & GNX_FLAG_FORCE_GENERIC) && steps_run_max() > 1 && !profile_enabled();
+  // a step joins a run only VALIDATED (the whole step's arguments and workspace): an invalid one starts a run of its own, whose chained
+  // step reports the error once everything before it has been issued.  run_args: the launch's shared arguments, from the run's first step.
+  auto slot_of = [&](const gnx_block_step& st, RunSlot& sl, BlockArgs* run_args) -> bool {
+    Prepared q(BlockCall{h, p, elem, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[0], GNX_PHASE_ALL});
+    if (q.rc) return false;
+    if (run_args) {
+      if (!block_narrow_run_applies(h, q.a, bf16)) return can_fuse = false;
+      *run_args = q.a;
     }
-    return flush(0);
+    sl = RunSlot{q.a.ef, q.a.nf, q.a.gf, q.a.ef_out, q.a.nf_out, q.a.gf_out, q.a.partials};
+    return true;
+  };
+  // The schedule and its hazard rule: gnx_step_hazard.h (run_order).  Run j waits for run j - 3's launches (the ring of events aux->step),
+  // so that only runs up to three apart can be in flight together; conflicts among those are ordered as run_order says.
+  if (two) {
+    GNX_HIP(hipEventRecord(aux->fork, str[0]));
+    GNX_HIP(hipStreamWaitEvent(str[1], aux->fork, 0));
   }
-  // The schedule and its hazard rule: gnx_step_hazard.h (step_order).  Step i waits for step i - 3's launch (the ring of events aux->step),
-  // so that only steps up to three apart can be in flight together; conflicts among those are ordered as step_order says.
-  GNX_HIP(hipEventRecord(aux->fork, str[0]));
-  GNX_HIP(hipStreamWaitEvent(str[1], aux->fork, 0));
-  StepSpans recent[3];  // steps i - 1, i - 2, i - 3
+  RunSpans recent[3];  // runs j - 1, j - 2, j - 3
   int32_t rc = GNX_OK;
-  for (int64_t i = 0; i < n_steps && rc == GNX_OK; ++i) {
+  int64_t i = 0;  // the run's first step
+  for (int64_t j = 0; i < n_steps && rc == GNX_OK; ++j) {
     const gnx_block_step& st = steps[i];
-    const int k = (int)(i & 1), o = k ^ 1;
-    const StepSpans cur = step_spans(h, p, R, st, elem_bytes, ws_extent);
-    const StepOrder ord = step_order(cur, recent, i);
-    if (ord.flush_own && (rc = flush(k))) break;
-    if (i >= 3) {
-      const hipError_t e = hipStreamWaitEvent(str[k], aux->step[(i - 3) & 3], 0);
+    RunSpans cur;
+    RunTable tab{};
+    BlockArgs run_args{};
+    cur.step[0] = valid ? step_spans(h, p, R, st, elem_bytes, ws_extent) : StepSpans{};
+    cur.n = 1;
+    if (can_fuse && n_steps - i >= 2) {
+      // a run or one step (gnx_step_hazard.h: group_run): the window by address ranges first, then every step of it validated
+      RunSpans win = cur;
+      while (i + win.n < n_steps) {
+        const StepSpans sp = step_spans(h, p, R, steps[i + win.n], elem_bytes, ws_extent);
+        if (!run_takes(win, sp, steps_run_max())) break;
+        win.step[win.n++] = sp;
+      }
+      bool ok = window_is_run(win.n, i, n_steps, steps_run_max());
+      for (int z = 0; ok && z < win.n; ++z) ok = slot_of(steps[i + z], tab.slot[z], z == 0 ? &run_args : nullptr);
+      if (ok) cur = win;
+    }
+    const int k = two ? (int)(j & 1) : 0, o = k ^ 1;
+    StepOrder ord;
+    if (two) {
+      ord = run_order(cur, recent, j);
+    } else {
+      // one stream: a run whose buffers overlap its predecessor's (a shared workspace / gf_out, or gf' read as the next step's input) cannot
+      // start before that one's graph update has run
+      ord.flush_own = pend[0].workspace && (pend[0].workspace == st.workspace || (p && p->og > 0 && pend[0].gf_out == st.gf_out) || runs_conflict(cur, recent[0]));
+    }
+    if ((ord.flush_own || cur.n > 1) && (rc = flush(k))) break;
+    if (two && j >= 3) {
+      const hipError_t e = hipStreamWaitEvent(str[k], aux->step[(j - 3) & 3], 0);
       if (e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: ordering a step behind the step three before it"); break; }
     }
     if (ord.after_other) {
@@ -503,19 +543,31 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
       if (e == hipSuccess) e = hipStreamWaitEvent(str[k], ev, 0);
       if (e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: ordering a step behind the other stream"); break; }
     }
-    gnx_pending_update next{};
-    rc = run(st, k, &next);
+    if (cur.n > 1) {
+      // (validated above: a failure here is a launch failure; nothing of this run is pending afterwards)
+      rc = launch_block_narrow_run(h, run_args, tab, cur.n, str[k], bf16);
+    } else {
+      gnx_pending_update next{};
+      rc = run(st, k, &next);
+      // (an argument error of step i: what is pending belongs to earlier steps, whose arguments were valid — finished below, then the error)
+      if (rc == GNX_OK) pend[k] = next;
+    }
     if (rc != GNX_OK) break;
-    pend[k] = next;
-    // (step[i & 3] was last recorded for step i - 4, and the wait on that record — step i - 1's — is already enqueued)
-    if (const hipError_t e = hipEventRecord(aux->step[i & 3], str[k]); e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: step event"); break; }
+    if (two) {
+      // (step[j & 3] was last recorded for run j - 4, and the wait on that record — run j - 1's — is already enqueued)
+      if (const hipError_t e = hipEventRecord(aux->step[j & 3], str[k]); e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: step event"); break; }
+    }
     recent[2] = recent[1]; recent[1] = recent[0]; recent[0] = cur;
+    i += cur.n;
   }
-  // the last two steps' graph updates (one per stream), then the join — on every path, so that a capture never ends with the side stream
+  // the last one-step runs' graph updates (one per stream), then the join — on every path, so that a capture never ends with the side stream
   // un-joined and an error leaves everything issued so far complete when the caller's stream is
-  const int32_t rf0 = flush(0), rf1 = flush(1);
-  const hipError_t e1 = hipEventRecord(aux->join, str[1]);
-  const hipError_t e2 = hipStreamWaitEvent(str[0], aux->join, 0);
+  const int32_t rf0 = flush(0), rf1 = two ? flush(1) : GNX_OK;
+  hipError_t e1 = hipSuccess, e2 = hipSuccess;
+  if (two) {
+    e1 = hipEventRecord(aux->join, str[1]);
+    e2 = hipStreamWaitEvent(str[0], aux->join, 0);
+  }
   if (rc) return rc;
   if (rf0) return rf0;
   if (rf1) return rf1;

@@ -45,6 +45,10 @@ int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int
 bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a);
 int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
 int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
+bool block_narrow_run_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16);
+bool narrow_bf16_run(const gnx_graphs* h, const BlockArgs& a);
+int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16);
+int32_t launch_run_bf16(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s);
 bool jit_eligible(const BlockArgs& a, int ept);
 int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph, bool bf16 = false);
 int32_t jit_get_core_post3(int d0, int d1, int d2, hipStream_t s, hipFunction_t* fn);

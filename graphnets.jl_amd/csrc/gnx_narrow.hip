@@ -137,6 +137,44 @@ int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a0, in
   return fail(GNX_ERR_INVALID_ARG, "internal: chained launch for a width set without that kernel");
 }
 
+// A run of Z >= 2 neighbouring, hazard-free steps of gnx_block_forward_steps in one launch (k_block_wave_run) plus one for their graph
+// updates: the batches that chain (block_narrow_chain_applies), whose steps would otherwise be Z chained launches, at the width sets whose
+// run kernel keeps the limits that make the form worth having — at most 80 scalar registers (the eighth workgroup per CU), no scratch, no
+// more vector registers than the chained kernel of the set (tests/test_steps_runs_cpu.py).  The three wide sets of GNX_NARROW_DIMS
+// ((8,8,8)=>(16,8), (10,5,3)=>(10,5), (10,5,0)=>(10,5)) are over 100 scalar and vector registers in every form — three or four workgroups per
+// CU whatever the schedule — and keep one launch per step.
+#define GNX_NARROW_RUN_DIMS(X) \
+  X(10, 5, 0, 3, 4)            \
+  X(3, 4, 5, 3, 4)             \
+  X(10, 5, 3, 3, 4)            \
+  X(0, 2, 0, 2, 2)             \
+  X(2, 2, 2, 2, 2)             \
+  X(4, 3, 2, 3, 4)
+bool block_narrow_run_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16) {
+  if (!block_narrow_chain_applies(h, a, bf16)) return false;
+  if (bf16) return narrow_bf16_run(h, a);
+#define GNX_CASE(DE, DN, DG, OE, ON) \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return true;
+  GNX_NARROW_RUN_DIMS(GNX_CASE)
+#undef GNX_CASE
+  return false;
+}
+int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16) {
+  if (bf16) {  // ... on bf16 rows: gnx_narrow_bf16.hip
+    const int32_t rc = launch_run_bf16(h, a, t, Z, s);
+    return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: bf16 run launch for a width set without that kernel") : rc;
+  }
+#define GNX_CASE(DE, DN, DG, OE, ON)                                                                                               \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) {                                                         \
+    if constexpr (OE + ON > 0) {                                                                                                   \
+      return h->G == 1 ? launch_wave_run<DE, DN, DG, OE, ON, true>(h, a, t, Z, s) : launch_wave_run<DE, DN, DG, OE, ON, false>(h, a, t, Z, s); \
+    }                                                                                                                              \
+  }
+  GNX_NARROW_RUN_DIMS(GNX_CASE)
+#undef GNX_CASE
+  return fail(GNX_ERR_INVALID_ARG, "internal: run launch for a width set without that kernel");
+}
+
 // the edge FeedForward + residual of a narrow GNCore inside the block kernel (k_block_wave<..., FFE>): ahead-of-time widths, identity / relu
 // activations.  GNX_FLAG_NO_FFE keeps the FeedForward in k_core_post3.
 bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1, int act2) {

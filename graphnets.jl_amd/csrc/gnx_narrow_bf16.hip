@@ -1,5 +1,5 @@
 // The fused narrow kernels with bfloat16 feature rows (k_block_wave<..., BF16 = true>, its chained form k_block_wave<..., CHAIN, BF16>,
-// k_graph_t<C, ONEG, true>) for the ahead-of-time width sets; gnx_narrow.hip routes gnx_block_forward_typed and the bf16 steps of
+// k_graph_t<C, ONEG, true>, the run form k_block_wave_run / k_graph_run of several steps in one launch) for the ahead-of-time width sets; gnx_narrow.hip routes gnx_block_forward_typed and the bf16 steps of
 // gnx_block_forward_steps_typed here, every other narrow width set is specialised at run time (gnx_jit.cpp).
 // A translation unit of its own because build.py compiles it without the SLP vectoriser (-fno-slp-vectorize; gnx_jit.cpp passes the same
 // option for a bf16 key): with it, every widened value feeds a v_pk_fma_f32 as the low half of a register pair of its own, and the README
@@ -47,6 +47,32 @@ int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, 
     }                                                                                                                              \
   }
   GNX_NARROW_DIMS_BF16(GNX_CASE)
+#undef GNX_CASE
+  return 1;
+}
+
+// A run of steps in one launch (gnx_narrow.hip: launch_block_narrow_run) on bf16 rows.  (DE, DN, DG, OE, ON, SEVERAL): SEVERAL — the set
+// has a run kernel for batches of several graphs too.  (10,5,0)=>(3,4,5) has not: that kernel needs 54 vector registers, as the plain bf16
+// kernel does, against the 52 of the set's chained kernel — the limit a run kernel keeps (tests/test_steps_runs_cpu.py); such a batch keeps
+// one chained launch per step.
+#define GNX_NARROW_RUN_DIMS_BF16(X) \
+  X(10, 5, 0, 3, 4, false)          \
+  X(3, 4, 5, 3, 4, true)
+bool narrow_bf16_run(const gnx_graphs* h, const BlockArgs& a) {
+#define GNX_CASE(DE, DN, DG, OE, ON, SEVERAL) \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return h->G == 1 || SEVERAL;
+  GNX_NARROW_RUN_DIMS_BF16(GNX_CASE)
+#undef GNX_CASE
+  return false;
+}
+// 1: no run kernel for these widths and this batch
+int32_t launch_run_bf16(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s) {
+#define GNX_CASE(DE, DN, DG, OE, ON, SEVERAL)                                                                \
+  if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) {                                   \
+    if (h->G == 1) return launch_wave_run<DE, DN, DG, OE, ON, true, true>(h, a, t, Z, s);                     \
+    if constexpr (SEVERAL) return launch_wave_run<DE, DN, DG, OE, ON, false, true>(h, a, t, Z, s);            \
+  }
+  GNX_NARROW_RUN_DIMS_BF16(GNX_CASE)
 #undef GNX_CASE
   return 1;
 }

@@ -58,6 +58,28 @@ static int32_t launch_wave_g(const gnx_graphs* h, const BlockArgs& a, int64_t R,
   return GNX_OK;
 }
 
+// A run of Z steps of gnx_block_forward_steps (a.ef ... a.partials unused: the slots of `t`): every slot's edge + node update in one launch
+// (k_block_wave_run, slot-major: x fastest), then every slot's graph update in a second one right behind it, with k_graph_t's thread count.
+template <int DE, int DN, int DG, int OE, int ON, bool ONEG, bool BF16 = false>
+static int32_t launch_wave_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s) {
+  constexpr int C = OE + ON;
+  if (Z < 1 || Z > kRunSlots) return fail(GNX_ERR_INVALID_ARG, "internal: a run of more steps than the table has slots");
+  const int n_rows = partial_rows(h);
+  {
+    ProfScope ps("k_block_wave", s);
+    GNX_LAUNCH((k_block_wave_run<DE, DN, DG, OE, ON, 2, ONEG, BF16>), dim3((unsigned)((a.n_wtiles + 3) / 4), (unsigned)Z), dim3(kThreads), 0, s, a, t, n_rows);
+    GNX_HIP(hipGetLastError());
+  }
+  if (a.og > 0) {
+    const int threads = graph_update_threads(h);
+    const size_t lds = sizeof(float) * (size_t)graph_update_lds_floats(C, a.dg, a.og, threads);
+    ProfScope ps("k_graph_t", s);
+    GNX_LAUNCH((k_graph_run<C, ONEG, BF16>), dim3((unsigned)a.G, (unsigned)Z), dim3(threads), lds, s, a, t, n_rows);
+    GNX_HIP(hipGetLastError());
+  }
+  return GNX_OK;
+}
+
 // Batches of small graphs (every graph <= 8 wave tiles: the handle has a pack table): ONE launch — 512-thread workgroups that own whole
 // graphs run the graph update themselves (k_block_wave<..., PACK>).  Only for the whole block in one call (phase 3): a caller that
 // splits off the graph update, or a narrow GNCore that runs it inside its FeedForward launch, reads the partial rows of the two-launch form.

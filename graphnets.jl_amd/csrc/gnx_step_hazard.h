@@ -67,4 +67,63 @@ inline StepOrder step_order(const StepSpans& cur, const StepSpans* recent, long 
   return o;
 }
 
+// ---- runs: neighbouring steps that share ONE launch (k_block_wave_run: gridDim.y = the run's steps) ----
+// A run is consecutive steps no two of which conflict: inside a launch nothing orders one slot's workgroups against another's.  The window
+// grows greedily from the run's first step; it becomes a run if it is FULL — run_max steps (<= kRunMax) — or if the end of the loop cut it
+// and it still has kRunTailMin steps.  Else the step is a run of its own: what a shared launch gains grows with its length
+// (profiles/steps_runs_c2.md: eight steps per launch gain 6 % on the 1M-edge graph, four nothing, two lose 5 % against single steps on two
+// streams), so a window that a CONFLICT cuts short (fewer buffer sets in rotation than run_max, a shared workspace, dims -> dims) keeps the
+// schedule of single steps, which overlaps them on the two streams, and so does a short rest of the loop.
+// The unit of the two-stream schedule above is the run: read "step" as "run" throughout — run j on stream j & 1, behind run j - 3's event,
+// ordered against runs j - 1, j - 2, j - 3 by run_order.  A run of ONE step is issued exactly as a step was (chained, its graph update pending
+// until the next launch on its stream); a run of several is two launches, its graph updates right behind its block launch, nothing pending.
+constexpr int kRunMax = 8;      // slots of the kernel-argument table
+constexpr int kRunTailMin = 4;  // the shortest run that is not full: the last steps of a loop
+
+struct RunSpans {
+  int n = 0;
+  StepSpans step[kRunMax];
+};
+
+inline bool run_conflicts_step(const RunSpans& r, const StepSpans& s) {
+  for (int a = 0; a < r.n; ++a)
+    if (steps_conflict(r.step[a], s)) return true;
+  return false;
+}
+
+// two runs conflict if any pair of their steps does
+inline bool runs_conflict(const RunSpans& x, const RunSpans& y) {
+  for (int b = 0; b < y.n; ++b)
+    if (run_conflicts_step(x, y.step[b])) return true;
+  return false;
+}
+
+// Greedy growth of the window: does the next step join?  (The caller also asks that the step is valid and that the run form takes the call.)
+inline bool run_takes(const RunSpans& run, const StepSpans& next, int run_max) {
+  return run.n >= 1 && run.n < run_max && run.n < kRunMax && !run_conflicts_step(run, next);
+}
+
+// a window of n steps that begins at step `first` of n_steps: is it a run?
+inline bool window_is_run(int n, long long first, long long n_steps, int run_max) {
+  return n >= 2 && (n == run_max || (first + n == n_steps && n >= kRunTailMin));
+}
+
+// the run that starts at step `first` of spans[0 .. n_steps)
+inline RunSpans group_run(const StepSpans* spans, long long n_steps, long long first, int run_max) {
+  RunSpans run;
+  if (first >= n_steps) return run;
+  run.step[run.n++] = spans[first];
+  while (first + run.n < n_steps && run_takes(run, spans[first + run.n], run_max)) { run.step[run.n] = spans[first + run.n]; ++run.n; }
+  if (!window_is_run(run.n, first, n_steps, run_max)) run.n = 1;
+  return run;
+}
+
+// step_order on runs.  recent[d - 1]: run j - d, for d = 1 .. min(j, 3).  With runs of one step these are step_order's decisions.
+inline StepOrder run_order(const RunSpans& cur, const RunSpans* recent, long long j) {
+  StepOrder o;
+  o.flush_own = j >= 2 && runs_conflict(cur, recent[1]);
+  o.after_other = (j >= 1 && runs_conflict(cur, recent[0])) || (j >= 3 && runs_conflict(cur, recent[2]));
+  return o;
+}
+
 }  // namespace gnx

@@ -787,8 +787,21 @@ __device__ __forceinline__ auto phase_args(const BlockArgs& a) {
   }
 }
 
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK, bool FFE, bool CHAIN, bool BF16 = false>
+// RUN (gnx_block_forward_steps: k_block_wave_run): blockIdx.y is a SLOT of a run of steps, not a replica — the slot's feature pointers and
+// its partial rows come from the RunTable behind BlockArgs in the kernel-argument segment, read afresh at the top of the phase that uses
+// them (scalar loads at an offset that depends on blockIdx.y; held from the top of the kernel they would cost scalar registers of the 80),
+// and the replica terms drop out.  Slot z's tile t is the wave-level program of a plain launch of step z: the same bits.
+typedef const RunSlot __attribute__((address_space(4))) * cslotp;
+__device__ __forceinline__ cslotp run_slot() {
+  typedef const char __attribute__((address_space(4))) * ccharp;
+  cslotp p = (cslotp)((ccharp)__builtin_amdgcn_kernarg_segment_ptr() + kRunTableOffset) + blockIdx.y;
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK, bool FFE, bool CHAIN, bool BF16 = false, bool RUN = false>
 __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
+  static_assert(!RUN || (!PACK && !FFE && !LN && !CHAIN && OE + ON > 0), "RUN: the two-launch form of a plain block, one slot per step");
   static_assert(!(PACK && ONEG), "packs are for batches of several graphs");
   static_assert(!BF16 || (!FFE && !LN), "bf16 features: the plain block forward and its chained form");
   static_assert(!CHAIN || (!PACK && !FFE && !LN && OE + ON > 0), "CHAIN: the two-launch form of a plain block");
@@ -874,10 +887,17 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   const int nn = n1 - n0, ne = e1 - e0;
   GNX_WSTAMP(1);  // (the stamp's own s_waitcnt lgkmcnt(0) makes this "tile record arrived")
 
-  const size_t r = blockIdx.y;
-  const auto* __restrict__ ef = DE > 0 ? feat<BF16>(A0->ef) + r * (size_t)A0->E * DE : nullptr;  // (float or bf16_t rows)
-  const auto* __restrict__ nf = DN > 0 ? feat<BF16>(A0->nf) + r * (size_t)A0->N * DN : nullptr;
-  const cfloatp gf = DG > 0 && !BF16 ? as_const(A0->gf + (r * (size_t)A0->G + g) * DG) : nullptr;
+  const size_t r = RUN ? 0 : blockIdx.y;
+  const float *ef_in = nullptr, *nf_in = nullptr, *gf_in = nullptr;
+  if constexpr (RUN) {
+    const cslotp S0 = run_slot();
+    ef_in = S0->ef; nf_in = S0->nf; gf_in = S0->gf;
+  } else {
+    ef_in = A0->ef; nf_in = A0->nf; gf_in = A0->gf;
+  }
+  const auto* __restrict__ ef = DE > 0 ? feat<BF16>(ef_in) + r * (size_t)A0->E * DE : nullptr;  // (float or bf16_t rows)
+  const auto* __restrict__ nf = DN > 0 ? feat<BF16>(nf_in) + r * (size_t)A0->N * DN : nullptr;
+  const cfloatp gf = DG > 0 && !BF16 ? as_const(gf_in + (r * (size_t)A0->G + g) * DG) : nullptr;
 
   // ---- issue every load up front, branch-free (indices clamped into the tile; results of clamped lanes unused) ----
   const bool is_node = lane < nn;
@@ -913,7 +933,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   }
   float gfr[1][DG1];
   if constexpr (BF16) {
-    if constexpr (DG > 0) load_row<DG>(feat<true>(A0->gf) + (r * (size_t)A0->G + g) * DG, gfr[0]);
+    if constexpr (DG > 0) load_row<DG>(feat<true>(gf_in) + (r * (size_t)A0->G + g) * DG, gfr[0]);
   } else {
 #pragma unroll
     for (int k = 0; k < DG; ++k) gfr[0][k] = gf[k];
@@ -926,6 +946,8 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   const auto A1 = phase_args<FRESH>(a);  // node-side preparation + edge phase
   const cfloatp We = as_const(A1->We);
   const cfloatp be = as_const(A1->be ? A1->be : k_zero_bias);
+  [[maybe_unused]] float* run_ef_out = nullptr;  // RUN: the slot's ef', read at the top of the phase (read at the store: two more vector registers)
+  if constexpr (RUN) run_ef_out = run_slot()->ef_out;
   // ---- lanes as nodes: destination index of each in-edge, per-node part of the edge update ----
   //   pd[n] = be + We[:, gf-seg] * gf[g] + We[:, dst-seg] * nf[n]      (edgefninput.jl:5-6 hoisted out of the edge loop)
   if (is_node) {
@@ -1050,7 +1072,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
           act_row<OE1>(acc[i], A1->act_e);
         }
         if (valid[i]) {
-          if constexpr (!FFE) store_row<OE>(feat<BF16>(A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc[i]);
+          if constexpr (!FFE) store_row<OE>(feat<BF16>(RUN ? run_ef_out : A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc[i]);
           if (nn > 1 || FFE) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) s_out[el * OE + j] = acc[i][j];
@@ -1085,7 +1107,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) acc[j] = fmaf(We[(DE + k) * OE + j], xs[i][k], acc[j]);
           act_row<OE1>(acc, A1->act_e);
-          store_row<OE>(feat<BF16>(A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc);
+          store_row<OE>(feat<BF16>(RUN ? run_ef_out : A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc);
           if (nn > 1) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) s_out[el * OE + j] = acc[j];
@@ -1103,6 +1125,8 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   const auto A2 = phase_args<FRESH>(a);  // node phase
   const cfloatp Wn = as_const(A2->Wn);
   const cfloatp bn = as_const(A2->bn ? A2->bn : k_zero_bias);
+  [[maybe_unused]] float* run_nf_out = nullptr;
+  if constexpr (RUN) run_nf_out = run_slot()->nf_out;
 
   // ---- lanes as nodes: edge->node sum (nodefninput.jl:3), node update ----
   float v[C1];  // per-lane contribution to the tile's graph-level partial sums: [agg ; nf']
@@ -1137,7 +1161,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
       act_row<ON1>(acc, A2->act_n);
 #pragma unroll
       for (int j = 0; j < ON; ++j) v[OE + j] = acc[j];
-      store_row<ON>(feat<BF16>(A2->nf_out) + (r * (size_t)A2->N + n0 + lane) * ON, acc);
+      store_row<ON>(feat<BF16>(RUN ? run_nf_out : A2->nf_out) + (r * (size_t)A2->N + n0 + lane) * ON, acc);
     }
   }
 
@@ -1180,9 +1204,11 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   const auto A3 = phase_args<FRESH>(a);
   if (A3->og > 0) {
     if constexpr (C > 0) {
-      const size_t r = blockIdx.y;
+      const size_t r = RUN ? 0 : blockIdx.y;
       constexpr int CP = (C + 3) / 4 * 4;
-      float* __restrict__ pbase = A3->partials + r * (size_t)n_rows * CP;
+      float* part;
+      if constexpr (RUN) part = run_slot()->partials; else part = A3->partials;
+      float* __restrict__ pbase = part + r * (size_t)n_rows * CP;
       if constexpr (PACK) {
         __shared__ float s_rows[WAVES][C1];
         if (lane < C) s_rows[wv][lane] = active ? mine : 0.f;
@@ -1271,6 +1297,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
   block_wave_body<DE, DN, DG, OE, ON, EPT, true, ONEG, false, true, false>(a, n_rows);
 }
 
+// A run of steps in one launch (RUN above): gridDim.y = the run's steps, blockIdx.y the slot.  A kernel of its own, so that k_block_wave keeps
+// its argument list and its name; the same resource limits.
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool ONEG, bool BF16 = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(GNX_WAVE_SGPRS))) void k_block_wave_run(BlockArgs a, RunTable t, int n_rows) {
+  block_wave_body<DE, DN, DG, OE, ON, EPT, false, ONEG, false, false, false, BF16, true>(a, n_rows);
+}
+
 // Graph update for the wave path: one workgroup per graph (one wavefront when the graph has <= 256 partial rows).
 template <int C, bool ONEG = false, bool BF16 = false>
 __global__ void k_graph_t(BlockArgs a, int n_rows) {
@@ -1282,6 +1315,21 @@ __global__ void k_graph_t(BlockArgs a, int n_rows) {
   const float* base = a.partials + blockIdx.y * (size_t)n_rows * CP;
   if (blockDim.x == 64) graph_update_rows<C, true, 16, BF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, 64, s_g);
   else graph_update_rows<C, false, 16, BF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
+}
+
+// ... of a run: slot blockIdx.y's partial rows, gf and gf_out from the table, summed as k_graph_t sums them (the launcher gives it k_graph_t's
+// thread count for these rows): the same bits.
+template <int C, bool ONEG = false, bool BF16 = false>
+__global__ void k_graph_run(BlockArgs a, RunTable t, int n_rows) {
+  extern __shared__ float s_g[];
+  const int g = blockIdx.x;
+  const int t0 = ONEG ? 0 : a.wtile_off[g], t1 = ONEG ? (a.n_wtiles + 3) / 4 : a.wtile_off[g + 1];
+  const cslotp S = run_slot();
+  const float* const base = S->partials;
+  const float* const gf = S->gf;
+  float* const gf_out = S->gf_out;
+  if (blockDim.x == 64) graph_update_rows<C, true, 16, BF16>(a, gf, gf_out, base, g, 0, t0, t1, (int)threadIdx.x, 64, s_g);
+  else graph_update_rows<C, false, 16, BF16>(a, gf, gf_out, base, g, 0, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
 }
 
 }  // namespace gnx

@@ -327,7 +327,17 @@ GNX_API int32_t gnx_block_forward_chained(const gnx_graphs* h, const gnx_block_p
  * overlap (one step writes a byte range — ef_out, nf_out, gf_out, workspace — that another reads or writes, up to three steps apart) are
  * ordered by an event wait instead, and every step's launch waits for the end of the launch three steps before it (the streams never
  * drift further apart).  Outputs are bit-identical in either schedule.  One stream: GNX_FLAG_NO_FORK, matrix-core / generic
- * kernels, the per-kernel profiler on (gnx_profile_enable), or every side stream of the handle taken by other host threads. */
+ * kernels, the per-kernel profiler on (gnx_profile_enable), or every side stream of the handle taken by other host threads.
+ * RUNS: neighbouring steps whose buffers do not overlap may SHARE A LAUNCH.  Where the chained form would run and the width set has a
+ * run kernel (the narrow ahead-of-time sets, fp32 and bf16, n_replicas == 1) the library groups consecutive steps, by the same
+ * address-range rule, into runs of GNX_STEPS_RUN_MAX steps (environment, read once; default 8, at most 8; 1: every step its own launch):
+ * a run is ONE block launch with a slot per step plus one launch for their graph updates, and "step" in the two-stream schedule above
+ * reads "run".  Only a full run, or the last four or more steps of the loop, share a launch (shorter ones measured no gain): where a
+ * conflict cuts the window short (a shared workspace or gf_out, dims -> dims feedback, fewer buffer sets in rotation than that)
+ * the step is a run of its own — the chained step above.  Unchanged: the order of the results, their bits (each slot is
+ * the program of a launch of its own), and that every output is complete, and the side stream joined, when the call returns its work to
+ * `stream` — on error paths too; a step's argument error is reported once everything before it has been issued, and an invalid step
+ * never joins a run.  With the per-kernel profiler on every run is one step (its figures are per step). */
 typedef struct gnx_block_step {
   const float* ef;
   const float* nf;
