@@ -876,9 +876,12 @@ def _ptr(t):
 
 
 class GNBlock:
-    """`GNBlock(in => out; dropout=0)` (gnblock.jl:47-61).  `block(x)` = gnblock.jl:63-69 via gnx_block_forward."""
+    """`GNBlock(in => out; dropout=0)` (gnblock.jl:47-61).  `block(x)` = gnblock.jl:63-69 via gnx_block_forward.
 
-    def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3):
+    `bf16_backward` (also a plain attribute): lets a differentiable call on bfloat16 features run — gnx_block_backward_typed is its pullback,
+    the input gradients come back rounded to bfloat16, the weight / bias gradients in float32.  Off (the default) such a call raises."""
+
+    def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -890,6 +893,7 @@ class GNBlock:
         self.graphfn = Dense(on + oe + dg, og, act[2], device, generator)     # gnblock.jl:54,58
         self.dropout = dropout  # stored, never applied by the forward (gnblock.jl:63-69)
         self.flags = 0
+        self.bf16_backward = bool(bf16_backward)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1019,13 +1023,21 @@ class GNBlock:
 
     def _call_bf16(self, x, flags):
         """bfloat16 features (batch(..., dtype=torch.bfloat16)): gnx_block_forward_typed, bf16 outputs — bit for bit the fp32 forward of the
-        widened inputs, rounded once to bf16.  Forward only: a differentiable call raises NotImplementedError."""
+        widened inputs, rounded once to bf16.  A differentiable call needs `bf16_backward` (gnx_block_backward_typed is then the pullback);
+        without it it raises NotImplementedError."""
         if any(isinstance(f, Chain) for f in (self.edgefn, self.nodefn, self.graphfn)):  # one-layer chains are plain Dense layers
             self.edgefn, self.nodefn, self.graphfn = (f.layers[0] if isinstance(f, Chain) else f for f in (self.edgefn, self.nodefn, self.graphfn))
         self._sync_dims()
         g, ef, nf, gf, R = _forward_common(x, self.in_dims, None)
         if self._trainable((ef, nf, gf)):
-            raise NotImplementedError("GNBlock: the backward of a bfloat16 forward is not implemented; call it under torch.no_grad() or with float32 features")
+            if not getattr(self, "bf16_backward", False):
+                raise NotImplementedError("GNBlock: the backward of a bfloat16 forward is not implemented unless the block's bf16_backward switch is on "
+                                          "(GNBlock(..., bf16_backward=True) or blk.bf16_backward = True): its input gradients are rounded to bfloat16; "
+                                          "or call it under torch.no_grad() or with float32 features")
+            outs = iter(_BlockBf16Fn.apply(self, g, R, self.flags if flags is None else flags, ef, nf, gf, self.edgefn.weight, self.edgefn.bias,
+                                           self.nodefn.weight, self.nodefn.bias, self.graphfn.weight, self.graphfn.bias))
+            eo, no, go = (next(outs) if d > 0 else None for d in self.out_dims)
+            return NT(g, _jl(eo), _jl(no), _jl(go))
         # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
         ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
         lib = _lib.load()
@@ -1099,6 +1111,72 @@ class _BlockFn(torch.autograd.Function):
             check(lib.gnx_block_backward(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_),
                                          _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
                                          torch.cuda.current_stream(dev).cuda_stream))
+        gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
+        return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
+
+
+class _BlockBf16Fn(torch.autograd.Function):
+    """_BlockFn on bfloat16 features (GNBlock.bf16_backward): forward = gnx_block_forward_typed, backward = gnx_block_backward_typed.  The six
+    saved tensors are bf16; the input gradients come back in bf16 (rounded once from the fp32 pullback at the rounded saved outputs), the
+    weight / bias gradients in fp32 in _BlockFn's layout."""
+
+    @staticmethod
+    def forward(ctx, block, g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg):
+        lib = _lib.load()
+        keep = []
+        p = block._c(keep)
+        oe, on, og = block.out_dims
+        dev = g.device
+        # the typed entries need 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
+        ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.bfloat16, device=dev) if d > 0 else None
+        eo, no, go = mk(g.n_edges, oe), mk(g.n_nodes, on), mk(g.n_graphs, og)
+        with torch.cuda.device(dev):
+            nbytes = lib.gnx_block_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, flags)
+            ws = g.workspace(nbytes, ("block_bf16", block.in_dims, block.out_dims, R, flags))
+            check(lib.gnx_block_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
+                                              ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
+        ctx.block, ctx.g, ctx.R = block, g, R
+        six = (ef, nf, gf, eo, no, go)
+        ctx.slots = tuple(t is not None for t in six)
+        ctx.save_for_backward(*[t for t in six if t is not None])
+        ctx.present = tuple(o is not None for o in (eo, no, go))
+        return tuple(o for o in (eo, no, go) if o is not None)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        lib = _lib.load()
+        block, g, R = ctx.block, ctx.g, ctx.R
+        sv = iter(ctx.saved_tensors)
+        ef, nf, gf, eo, no, go = (next(sv) if present else None for present in ctx.slots)
+        it = iter(gouts)
+        ge, gn_, gg = (next(it) if pr else None for pr in ctx.present)
+
+        def cot(t):  # contiguous and 4-byte aligned (a cotangent has the bf16 dtype of its output)
+            if t is None:
+                return None
+            t = t.contiguous()
+            return t if t.data_ptr() % 4 == 0 else t.clone()
+
+        ge, gn_, gg = cot(ge), cot(gn_), cot(gg)
+        keep = []
+        p = block._c(keep)
+        dev = g.device
+        need = ctx.needs_input_grad[1:]  # (g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg) -> ef is need[3]
+        d_ef = torch.empty_like(ef) if ef is not None and need[3] else None
+        d_nf = torch.empty_like(nf) if nf is not None and need[4] else None
+        d_gf = torch.empty_like(gf) if gf is not None and need[5] else None
+        layers = (block.edgefn, block.nodefn, block.graphfn)
+        gW = [torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev) if need[6 + 2 * i] else None for i, l in enumerate(layers)]
+        gb = [torch.empty_like(l.bias) if (l.bias is not None and need[7 + 2 * i]) else None for i, l in enumerate(layers)]
+        grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None)
+                                  for w, b in zip(gW, gb)])
+        with torch.cuda.device(dev):
+            nb = lib.gnx_block_backward_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16)
+            ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
+            check(lib.gnx_block_backward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge),
+                                               _ptr(gn_), _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
+                                               torch.cuda.current_stream(dev).cuda_stream))
         gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
         return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
 

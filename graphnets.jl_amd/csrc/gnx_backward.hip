@@ -14,8 +14,23 @@
 #include <algorithm>
 
 #include "gnx_launchers.h"
+#include "gnx_wave_kernel.h"  // ld_feat / st_feat: a bf16 or fp32 element of a feature buffer
 
 namespace gnx {
+
+// bfloat16 feature tensors (gnx_block_backward_typed, GNX_ELEM_BF16): the kernels below that read or write one of the twelve feature-shaped
+// tensors take the element type as a template parameter.  A bf16 element is widened on load (exact) and rounded to nearest even on store
+// (to_bf16), one 16-bit access per element — a thread never touches the other half of a dword, so odd element counts and rows that start
+// in the middle of a dword need no special case; everything between load and store is the fp32 code, instruction for instruction.
+
+// four consecutive bf16 elements from element i of a feature buffer (i % 4 == 0, base 8-B aligned), widened
+__device__ __forceinline__ float4 ld_bf16x4(const float* base, size_t i) {
+  const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(base) + i);
+  return make_float4(bf16_lo(w.x), bf16_hi(w.x), bf16_lo(w.y), bf16_hi(w.y));
+}
+// one element through a typed row pointer
+__device__ __forceinline__ float ld_elem(const float* p) { return *p; }
+__device__ __forceinline__ float ld_elem(const bf16_t* p) { return bf16_lo(*p); }
 
 // delta[m][j] = (G[m][j] + extra1[i1(m)][o1 + j] + extra2[i2(m)][o2 + j]) * act'(out[m][j]);  one thread per element.
 // kind 0: rows = graphs (no extras); 1: rows = nodes (extra1 = dXg rows by graph); 2: rows = edges (extra1 = dXg by graph,
@@ -38,18 +53,22 @@ struct DeltaArgs {
   const int* edge_dst;
   int J, rows, n_seg, act, kind;
 };
+// EL: bit 0 — G is bfloat16; bit 1 — out is bfloat16 (a gelu level's `out` is the fp32 pre-activation whatever the features are)
+template <int EL>
 __global__ void k_bw_delta(DeltaArgs a, size_t ex1_rep, size_t ex2_rep) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t r = blockIdx.y;
   if (idx >= (size_t)a.rows * a.J) return;
   const int m = (int)(idx / a.J), j = (int)(idx % a.J);
   const size_t o = r * (size_t)a.rows * a.J + idx;
-  float g = a.G ? a.G[o] : 0.f;
+  float g = a.G ? ld_feat<(EL & 1) != 0>(a.G, o) : 0.f;
   if (a.kind >= 1 && a.ex1) g += a.ex1[r * ex1_rep + (size_t)segment_of(a.seg_off, a.n_seg, m) * a.ex1_stride + a.ex1_off + j];
   if (a.kind == 2 && a.ex2) g += a.ex2[r * ex2_rep + (size_t)a.edge_dst[m] * a.ex2_stride + a.ex2_off + j];
-  a.delta[o] = g * act_grad_bw(a.out[o], a.act);
+  a.delta[o] = g * act_grad_bw(ld_feat<(EL & 2) != 0>(a.out, o), a.act);
 }
-// the same, four columns per thread with 16-B accesses (J % 4 == 0, every base / stride / offset a multiple of 4 floats)
+// the same, four columns per thread with 16-B accesses (J % 4 == 0, every base / stride / offset a multiple of 4 floats; a bf16 G / out
+// is read as four elements = 8 B, its base 8-B aligned)
+template <int EL>
 __global__ void k_bw_delta_v4(DeltaArgs a, size_t ex1_rep, size_t ex2_rep) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t r = blockIdx.y;
@@ -57,8 +76,11 @@ __global__ void k_bw_delta_v4(DeltaArgs a, size_t ex1_rep, size_t ex2_rep) {
   if (idx >= (size_t)a.rows * J4) return;
   const int m = (int)(idx / J4), j = 4 * (int)(idx % J4);
   const size_t o = r * (size_t)a.rows * a.J + (size_t)m * a.J + j;
-  float4 g = a.G ? *reinterpret_cast<const float4*>(a.G + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float4 y = *reinterpret_cast<const float4*>(a.out + o);
+  float4 g, y;
+  if constexpr ((EL & 1) != 0) g = a.G ? ld_bf16x4(a.G, o) : make_float4(0.f, 0.f, 0.f, 0.f);
+  else g = a.G ? *reinterpret_cast<const float4*>(a.G + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr ((EL & 2) != 0) y = ld_bf16x4(a.out, o);
+  else y = *reinterpret_cast<const float4*>(a.out + o);
   if (a.kind >= 1 && a.ex1) {
     const float4 u = *reinterpret_cast<const float4*>(a.ex1 + r * ex1_rep + (size_t)segment_of(a.seg_off, a.n_seg, m) * a.ex1_stride + a.ex1_off + j);
     g.x += u.x; g.y += u.y; g.z += u.z; g.w += u.w;
@@ -70,15 +92,27 @@ __global__ void k_bw_delta_v4(DeltaArgs a, size_t ex1_rep, size_t ex2_rep) {
   g.x *= act_grad_bw(y.x, a.act); g.y *= act_grad_bw(y.y, a.act); g.z *= act_grad_bw(y.z, a.act); g.w *= act_grad_bw(y.w, a.act);
   *reinterpret_cast<float4*>(a.delta + o) = g;
 }
-static void launch_delta(const DeltaArgs& a, size_t ex1_rep, size_t ex2_rep, unsigned Ru, hipStream_t s) {
-  const bool al = (((uintptr_t)a.G | (uintptr_t)a.out | (uintptr_t)a.delta | (uintptr_t)a.ex1 | (uintptr_t)a.ex2) & 15) == 0;
+// el: the EL of the kernels (0: fp32 features; 1: bf16 G, fp32 out; 3: both bf16)
+static void launch_delta_scalar(const DeltaArgs& a, size_t ex1_rep, size_t ex2_rep, unsigned Ru, hipStream_t s, int el = 0) {
+  const dim3 grid((unsigned)(((size_t)a.rows * a.J + 255) / 256), Ru);
+  if (el == 0) GNX_LAUNCH(k_bw_delta<0>, grid, dim3(256), 0, s, a, ex1_rep, ex2_rep);
+  else if (el == 1) GNX_LAUNCH(k_bw_delta<1>, grid, dim3(256), 0, s, a, ex1_rep, ex2_rep);
+  else GNX_LAUNCH(k_bw_delta<3>, grid, dim3(256), 0, s, a, ex1_rep, ex2_rep);
+}
+static void launch_delta(const DeltaArgs& a, size_t ex1_rep, size_t ex2_rep, unsigned Ru, hipStream_t s, int el = 0) {
+  const bool al = ((((uintptr_t)a.delta | (uintptr_t)a.ex1 | (uintptr_t)a.ex2) & 15) | ((uintptr_t)a.G & ((el & 1) ? 7 : 15)) |
+                   ((uintptr_t)a.out & ((el & 2) ? 7 : 15))) == 0;
   const bool v4 = al && a.J % 4 == 0 && a.ex1_stride % 4 == 0 && a.ex1_off % 4 == 0 && a.ex2_stride % 4 == 0 && a.ex2_off % 4 == 0 && ex1_rep % 4 == 0 &&
                   ex2_rep % 4 == 0;
-  if (v4) GNX_LAUNCH(k_bw_delta_v4, dim3((unsigned)(((size_t)a.rows * (a.J / 4) + 255) / 256), Ru), dim3(256), 0, s, a, ex1_rep, ex2_rep);
-  else GNX_LAUNCH(k_bw_delta, dim3((unsigned)(((size_t)a.rows * a.J + 255) / 256), Ru), dim3(256), 0, s, a, ex1_rep, ex2_rep);
+  if (!v4) return launch_delta_scalar(a, ex1_rep, ex2_rep, Ru, s, el);
+  const dim3 grid((unsigned)(((size_t)a.rows * (a.J / 4) + 255) / 256), Ru);
+  if (el == 0) GNX_LAUNCH(k_bw_delta_v4<0>, grid, dim3(256), 0, s, a, ex1_rep, ex2_rep);
+  else if (el == 1) GNX_LAUNCH(k_bw_delta_v4<1>, grid, dim3(256), 0, s, a, ex1_rep, ex2_rep);
+  else GNX_LAUNCH(k_bw_delta_v4<3>, grid, dim3(256), 0, s, a, ex1_rep, ex2_rep);
 }
 
-// dX[m][k] = sum_j W[k*J + j] * delta[m][j]   (W is (J x K) column-major); one thread per (m, k)
+// dX[m][k] = sum_j W[k*J + j] * delta[m][j]   (W is (J x K) column-major); one thread per (m, k).  BF16: `direct` is bfloat16 (dX stays fp32)
+template <bool BF16>
 __global__ void k_bw_dx(const float* __restrict__ delta, const float* __restrict__ W, int rows, int J, int K, float* __restrict__ dX,
                         int k0, int k1, float* __restrict__ direct, int direct_w) {
   // columns [k0, k1) additionally go to `direct` (row stride direct_w) — e.g. the ef segment of dXe is d_ef itself
@@ -90,10 +124,11 @@ __global__ void k_bw_dx(const float* __restrict__ delta, const float* __restrict
   float acc = 0.f;
   for (int j = 0; j < J; ++j) acc = fmaf(W[(size_t)k * J + j], d[j], acc);
   dX[r * (size_t)rows * K + idx] = acc;
-  if (direct && k >= k0 && k < k1) direct[(r * rows + m) * (size_t)direct_w + (k - k0)] = acc;
+  if (direct && k >= k0 && k < k1) st_feat<BF16>(direct, (r * rows + m) * (size_t)direct_w + (k - k0), acc);
 }
 
-// d_nf[n][k] = dXn[n][a_off+k] + sum_{in-edges} dXe[e][dst_off+k] + sum_{out-edges} dXe[e][src_off+k]
+// d_nf[n][k] = dXn[n][a_off+k] + sum_{in-edges} dXe[e][dst_off+k] + sum_{out-edges} dXe[e][src_off+k].  BF16: d_nf is bfloat16
+template <bool BF16>
 __global__ void k_bw_dnf(const float* dXn, int Kn, int n_off, const float* dXe, int Ke, int src_off, int dst_off, const int* colptr,
                          const int* csr_ptr, const int* csr_eid, int N, int E, int dn, float* d_nf) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,11 +141,12 @@ __global__ void k_bw_dnf(const float* dXn, int Kn, int n_off, const float* dXe, 
     for (int e = colptr[n]; e < colptr[n + 1]; ++e) acc += base[(size_t)e * Ke + dst_off + k];
     for (int i = csr_ptr[n]; i < csr_ptr[n + 1]; ++i) acc += base[(size_t)csr_eid[i] * Ke + src_off + k];
   }
-  d_nf[r * (size_t)N * dn + idx] = acc;
+  st_feat<BF16>(d_nf, r * (size_t)N * dn + idx, acc);
 }
 
 // per-graph column sums of a row tensor (sum_e ef', sum_n nf' for Xg), two stages, fixed order:
-// stage 1: workgroup (slice s of graph g): thread (grp, c) strides over the slice's rows for column c -> partial[g][s][c]
+// stage 1: workgroup (slice s of graph g): thread (grp, c) strides over the slice's rows for column c -> partial[g][s][c].  BF16: `in` is bfloat16
+template <bool BF16>
 __global__ __launch_bounds__(256) void k_bw_colsum1(const float* __restrict__ in, int d, int rows_total, const int* __restrict__ off, int S,
                                                     int G, float* __restrict__ partial, int ld, int coff) {  // ld: row length of `in`, coff: first column
   __shared__ float s_red[256];
@@ -119,7 +155,7 @@ __global__ __launch_bounds__(256) void k_bw_colsum1(const float* __restrict__ in
   const int t0 = off[g], t1 = off[g + 1];
   const int per = (t1 - t0 + S - 1) / S;
   const int a0 = t0 + sl * per, a1 = min(a0 + per, t1);
-  const float* base = in + r * (size_t)rows_total * ld + coff;
+  const auto* base = feat<BF16>(in) + r * (size_t)rows_total * ld + coff;  // (float or bf16_t rows)
   for (int c0 = 0; c0 < d; c0 += 256) {
     const int dc = min(d - c0, 256);         // columns handled in this pass
     const int groups = 256 / dc;             // row groups working in parallel
@@ -129,7 +165,7 @@ __global__ __launch_bounds__(256) void k_bw_colsum1(const float* __restrict__ in
       for (int m = a0 + grp; m < a1; m += 8 * groups) {
         float v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = base[(size_t)min(m + u * groups, a1 - 1) * ld + c0 + c];
+        for (int u = 0; u < 8; ++u) v[u] = ld_elem(&base[(size_t)min(m + u * groups, a1 - 1) * ld + c0 + c]);
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc += m + u * groups < a1 ? v[u] : 0.f;
       }
@@ -162,10 +198,11 @@ __global__ void k_bw_dgf_init(const float* __restrict__ dXg, int Kg, int g_off, 
   if (idx >= GR * dg) return;
   d_gf[idx] = dXg ? dXg[(size_t)(idx / dg) * Kg + g_off + idx % dg] : 0.f;
 }
+template <bool BF16>  // gf is bfloat16
 __global__ void k_bw_copy_gf(const float* __restrict__ gf, int dg, int GR, float* __restrict__ out, int out_stride, int out_off) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= GR * dg) return;
-  out[(size_t)(idx / dg) * out_stride + out_off + idx % dg] = gf[idx];
+  out[(size_t)(idx / dg) * out_stride + out_off + idx % dg] = ld_feat<BF16>(gf, idx);
 }
 
 // weight / bias gradients: dW[k*J + j] = sum_m delta[m][j] * X[m][k], db[j] = sum_m delta[m][j]  over ALL rows (and replicas).
@@ -252,10 +289,11 @@ __global__ void k_bw_dw_small(const float* __restrict__ delta, const float* __re
 
 // generic dX launch with a profiling scope
 static void launch_bw_dx(dim3 grid, hipStream_t s, const float* delta, const float* W, int rows, int J, int K, float* dX, int k0, int k1, float* direct,
-                         int direct_w) {
+                         int direct_w, bool direct_bf16 = false) {
   if (grid.x == 0 || grid.y == 0) return;  // a function without inputs (K = 0: e.g. a node function when oe = dn = dg = 0) has no dX
   ProfScope ps("bw_dx_generic", s);
-  GNX_LAUNCH(k_bw_dx, grid, dim3(256), 0, s, delta, W, rows, J, K, dX, k0, k1, direct, direct_w);
+  if (direct_bf16) GNX_LAUNCH(k_bw_dx<true>, grid, dim3(256), 0, s, delta, W, rows, J, K, dX, k0, k1, direct, direct_w);
+  else GNX_LAUNCH(k_bw_dx<false>, grid, dim3(256), 0, s, delta, W, rows, J, K, dX, k0, k1, direct, direct_w);
 }
 
 struct BwLayout {
@@ -511,7 +549,7 @@ static int32_t colsum_all(const float* in, size_t rows, int d, float* out, float
   if (rows == 0) { GNX_HIP(hipMemsetAsync(out, 0, sizeof(float) * d, s)); return GNX_OK; }
   ProfScope ps("bw_colsum_all", s);
   const int S = (int)std::min<size_t>(std::max<size_t>(rows / 512, 1), 2048);
-  GNX_LAUNCH(k_bw_colsum1, dim3((unsigned)S, 1, 1), dim3(256), 0, s, in, d, (int)rows, d_off2, S, 1, part, d, 0);
+  GNX_LAUNCH(k_bw_colsum1<false>, dim3((unsigned)S, 1, 1), dim3(256), 0, s, in, d, (int)rows, d_off2, S, 1, part, d, 0);
   GNX_LAUNCH(k_bw_colsum_final, dim3((unsigned)((d + 63) / 64)), dim3(256), 0, s, part, d, S, out, 0);
   GNX_HIP(hipGetLastError());
   return GNX_OK;
@@ -525,26 +563,9 @@ __global__ void k_act_inplace(float* __restrict__ x, size_t n, int act) {
   if (idx < n) x[idx] = act_apply(x[idx], act);
 }
 
-}  // namespace gnx
-
-using namespace gnx;
-
-extern "C" {
-
-size_t gnx_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  if (!h || !p || R <= 0) return 0;
-  (void)gnx_ensure_wide_tables(h);  // what the backward reads is built here, outside any capture (a failure resurfaces in the backward)
-  (void)gnx_ensure_csr(h);
-  return bw_layout(h, p, R).total;
-}
-
-int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
-                           const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
-                           const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
-                           void* ws, size_t ws_bytes, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  DeviceTurn turn(s, matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
+// what gnx_block_backward checks of its arguments before anything else (h, p non-NULL)
+static int32_t bw_check(const gnx_graphs* h, const gnx_block_params* p, const void* ef, const void* nf, const void* gf, const void* ef_out, const void* nf_out,
+                        const void* gf_out, int64_t R) {
   if (R <= 0 || (R > 1 && h->G != 1) || R > 65535) return fail(GNX_ERR_INVALID_ARG, "bad n_replicas");
   const int de = p->de, dn = p->dn, dg = p->dg, oe = p->oe, on = p->on, og = p->og;
   if (de < 0 || dn < 0 || dg < 0 || oe < 0 || on < 0 || og < 0 || de + dn + dg == 0 || oe + on + og == 0) return fail(GNX_ERR_DIMS, "bad widths");
@@ -553,9 +574,37 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
   const int acts[3] = {p->edgefn.act, p->nodefn.act, p->graphfn.act};
   for (int a : acts)
     if (a < 0 || a > GNX_ACT_GELU) return fail(GNX_ERR_INVALID_ARG, "unknown activation code");
+  return GNX_OK;
+}
+
+// Do the edge level / the node level of this backward go to the matrix cores?  (The graph level never does.)
+static bool bw_mfma_edge(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  return p->oe > 0 && h->E > 0 && p->edgefn.act != GNX_ACT_GELU && bw_use_mfma((size_t)R * h->E, p->oe, p->de + 2 * p->dn + p->dg);
+}
+static bool bw_mfma_node(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  return p->on > 0 && bw_use_mfma((size_t)R * h->N, p->on, p->oe + p->dn + p->dg);
+}
+
+// gnx_block_backward.  BF16 (gnx_block_backward_typed on its native path: neither level on the matrix cores): the nine feature-shaped inputs and
+// d_ef / d_nf point to bfloat16 — declared float like the feature pointers of BlockArgs, the kernels read them as the element type of the
+// launch — and d_gf, which several launches accumulate, is built in `dgf_acc` (R * G * dg floats) and rounded once at the end.
+template <bool BF16>
+static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
+                                const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
+                                const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
+                                void* ws, size_t ws_bytes, void* stream, float* dgf_acc) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  DeviceTurn turn(s, matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
+  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
+  if (rc) return rc;
+  const int de = p->de, dn = p->dn, dg = p->dg, oe = p->oe, on = p->on, og = p->og;
+  const int acts[3] = {p->edgefn.act, p->nodefn.act, p->graphfn.act};
+  if (BF16 && (bw_mfma_edge(h, p, R) || bw_mfma_node(h, p, R))) return fail(GNX_ERR_INVALID_ARG, "bf16 backward: matrix-core widths take the staging path");
+  constexpr size_t kElem = BF16 ? 2 : sizeof(float);  // bytes of a feature element
   const BwLayout L = bw_layout(h, p, R);
   if (!ws || ws_bytes < L.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_backward_workspace_bytes()");
-  int32_t rc = gnx_ensure_wide_tables(h, stream);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
+  rc = gnx_ensure_wide_tables(h, stream);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
   if (rc) return rc;
   rc = gnx_ensure_csr(h);
   if (rc) return rc;
@@ -577,16 +626,19 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
   int64_t me = 1, mn = 1;
   for (int64_t g = 0; g < h->G; ++g) { me = std::max(me, h->h_edge_off[g + 1] - h->h_edge_off[g]); mn = std::max(mn, h->h_node_off[g + 1] - h->h_node_off[g]); }
   auto colsum = [&](const float* in, int d, int ld, int coff, int rows_total, const int* off, int64_t max_rows, float* out, int out_stride, int out_off,
-                    int accumulate) {
+                    int accumulate, bool in_bf16 = false) {
     if (d == 0) return;
     const int S = (int)std::min<int64_t>(std::max<int64_t>(max_rows / 2048, 1), 256);
-    GNX_LAUNCH(k_bw_colsum1, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, in, d, rows_total, off, S, G, part, ld, coff);
+    if (in_bf16) GNX_LAUNCH(k_bw_colsum1<true>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, in, d, rows_total, off, S, G, part, ld, coff);
+    else GNX_LAUNCH(k_bw_colsum1<false>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, in, d, rows_total, off, S, G, part, ld, coff);
     GNX_LAUNCH(k_bw_colsum2, dim3((unsigned)G, Ru), dim3(64), 0, s, part, d, S, G, out, out_stride, out_off, accumulate);
   };
   // Edge level on the matrix cores: regrouped (see below) — the edge function's input Xe is never materialised.
   // (a gelu edge function needs its pre-activation, hence the materialised Xe of the generic form)
-  const bool mfma_e = oe > 0 && E > 0 && acts[0] != GNX_ACT_GELU && bw_use_mfma((size_t)R * E, oe, Ke);
+  const bool mfma_e = bw_mfma_edge(h, p, R);
   // gelu: the level's pre-activation z = W x + b, recomputed into its delta buffer; the delta kernel then reads it in place
+  // the element types the delta kernels of a level read (their EL): a bf16 call has bf16 G, and bf16 `out` unless the level is gelu
+  auto el = [&](int level) { return !BF16 ? 0 : acts[level] == GNX_ACT_GELU ? 1 : 3; };
   auto preact = [&](int level, const float* X, const gnx_dense& d, size_t rows, int K, int J, float* z) {
     if (acts[level] != GNX_ACT_GELU || rows == 0 || J == 0) return;
     ProfScope ps("bw_gelu_preact", s);
@@ -594,12 +646,12 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
   };
   // function inputs, exactly as the forward's building blocks define them
   { ProfScope ps("bw_fn_inputs", s);
-  if (oe && E && !mfma_e && (rc = launch_fn_input(h, 0, ef, de, nf, dn, gf, dg, R, Xe, s))) return rc;
-  if (on && (rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s))) return rc; }
+  if (oe && E && !mfma_e && (rc = launch_fn_input(h, 0, ef, de, nf, dn, gf, dg, R, Xe, s, BF16))) return rc;
+  if (on && (rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s, BF16))) return rc; }
   if (og) {  // Xg = [sum_e ef' ; sum_n nf' ; gf] with parallel two-stage column sums (one workgroup per graph would walk 1M rows)
-    colsum(ef_out, oe, oe, 0, E, h->d_edge_off, me, Xg, Kg, 0, 0);
-    colsum(nf_out, on, on, 0, N, h->d_node_off, mn, Xg, Kg, oe, 0);
-    if (dg) GNX_LAUNCH(k_bw_copy_gf, blocks((size_t)R * G * dg), dim3(256), 0, s, gf, dg, (int)(R * G), Xg, Kg, oe + on);
+    colsum(ef_out, oe, oe, 0, E, h->d_edge_off, me, Xg, Kg, 0, 0, BF16);
+    colsum(nf_out, on, on, 0, N, h->d_node_off, mn, Xg, Kg, oe, 0, BF16);
+    if (dg) GNX_LAUNCH(k_bw_copy_gf<BF16>, blocks((size_t)R * G * dg), dim3(256), 0, s, gf, dg, (int)(R * G), Xg, Kg, oe + on);
     GNX_HIP(hipGetLastError());
   }
 
@@ -608,7 +660,7 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
   if (have_g) {
     preact(2, Xg, p->graphfn, (size_t)R * G, Kg, og, dlt_g);
     DeltaArgs a{g_gf_out, acts[2] == GNX_ACT_GELU ? dlt_g : gf_out, dlt_g, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, og, G, G, acts[2], 0};
-    GNX_LAUNCH(k_bw_delta, dim3(blocks((size_t)G * og).x, Ru), dim3(256), 0, s, a, (size_t)0, (size_t)0);
+    launch_delta_scalar(a, (size_t)0, (size_t)0, Ru, s, el(2));
     launch_bw_dx(dim3(blocks((size_t)G * Kg).x, Ru), s, dlt_g, p->graphfn.weight, G, og, Kg, dXg, 0, 0, (float*)nullptr, 0);
     if ((rc = dw_reduce(dlt_g, Xg, (size_t)R * G, og, Kg, gr.graphfn, part, s))) return rc;
   }
@@ -617,8 +669,8 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
   if (have_n) {
     preact(1, Xn, p->nodefn, (size_t)R * N, Kn, on, dlt_n);
     DeltaArgs a{g_nf_out, acts[1] == GNX_ACT_GELU ? dlt_n : nf_out, dlt_n, have_g ? dXg : nullptr, Kg, oe, nullptr, 0, 0, h->d_node_off, nullptr, on, N, G, acts[1], 1};
-    launch_delta(a, (size_t)G * Kg, (size_t)0, Ru, s);
-    if (bw_use_mfma((size_t)R * N, on, Kn)) {  // matrix cores: dXn = dn Wn^T, dWn = Xn^T dn, dbn = column sums
+    launch_delta(a, (size_t)G * Kg, (size_t)0, Ru, s, el(1));
+    if (bw_mfma_node(h, p, R)) {  // matrix cores: dXn = dn Wn^T, dWn = Xn^T dn, dbn = column sums
       if ((rc = dx_mfma(h, 1, dlt_n, p->nodefn.weight, on, Kn, 0, Kn, dXn, R, wt, true, s, "bw_dx_node"))) return rc;
       if ((rc = dw_auto(dlt_n, Xn, (size_t)R * N, on, Kn, gr.nodefn, part, off2, s))) return rc;
     } else {
@@ -632,7 +684,7 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
     preact(0, Xe, p->edgefn, (size_t)R * E, Ke, oe, dlt_e);
     DeltaArgs a{g_ef_out, acts[0] == GNX_ACT_GELU ? dlt_e : ef_out, dlt_e, have_g ? dXg : nullptr, Kg, 0, have_n ? dXn : nullptr, Kn, 0, h->d_edge_off, h->d_edge_dst, oe, E, G, acts[0], 2};
     { ProfScope ps("bw_delta_edge", s);
-    launch_delta(a, (size_t)G * Kg, (size_t)N * Kn, Ru, s); }
+    launch_delta(a, (size_t)G * Kg, (size_t)N * Kn, Ru, s, el(0)); }
     if (mfma_e) {
       // Matrix cores, regrouped so that only the ef block is a per-edge product.  With de = delta of the edges and
       //   S_dst[n] = sum_{e: dst = n} de[e]  (contiguous CSC segments)   S_src[n] = sum_{e: src = n} de[e]  (CSR view)   S_g = sum_{n in g} S_dst[n]
@@ -672,11 +724,11 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
       GNX_LAUNCH(k_set_off2, dim3(1), dim3(1), 0, s, off2, (int)(R * E));
       if ((rc = colsum_all(dlt_e, (size_t)R * E, oe, gr.edgefn.bias, part, off2, s))) return rc;
     } else {
-      launch_bw_dx(dim3(blocks((size_t)E * Ke).x, Ru), s, dlt_e, p->edgefn.weight, E, oe, Ke, dXe, 0, de, d_ef, de);
+      launch_bw_dx(dim3(blocks((size_t)E * Ke).x, Ru), s, dlt_e, p->edgefn.weight, E, oe, Ke, dXe, 0, de, d_ef, de, BF16);
       if ((rc = dw_reduce(dlt_e, Xe, (size_t)R * E, oe, Ke, gr.edgefn, part, s))) return rc;
     }
   } else {
-    if (d_ef && de && E) GNX_HIP(hipMemsetAsync(d_ef, 0, sizeof(float) * (size_t)R * E * de, s));
+    if (d_ef && de && E) GNX_HIP(hipMemsetAsync(d_ef, 0, kElem * (size_t)R * E * de, s));
     if (gr.edgefn.weight && oe) GNX_HIP(hipMemsetAsync(gr.edgefn.weight, 0, sizeof(float) * (size_t)oe * Ke, s));
     if (gr.edgefn.bias && oe) GNX_HIP(hipMemsetAsync(gr.edgefn.bias, 0, sizeof(float) * (size_t)oe, s));
   }
@@ -687,17 +739,115 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
   // input gradients that need sums
   if (d_nf && dn && !mfma_e) {
     ProfScope ps("bw_dnf", s);
-    GNX_LAUNCH(k_bw_dnf, dim3(blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, have_n ? dXn : nullptr, Kn, oe, have_e ? dXe : nullptr, dxe_stride,
+    GNX_LAUNCH(k_bw_dnf<BF16>, dim3(blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, have_n ? dXn : nullptr, Kn, oe, have_e ? dXe : nullptr, dxe_stride,
                        de - dxe_col0, de + dn - dxe_col0, h->d_colptr, h->d_csr_ptr, h->d_csr_eid, N, E, dn, d_nf);
   }
   if (d_gf && dg) {  // d_gf[g] = dXg[g][gf cols] + sum_{n in g} dXn[n][gf cols] + sum_{e in g} dXe[e][gf cols]
-    ProfScope ps("bw_dgf", s);
-    GNX_LAUNCH(k_bw_dgf_init, blocks((size_t)R * G * dg), dim3(256), 0, s, have_g ? dXg : nullptr, Kg, oe + on, (int)(R * G), dg, d_gf);
-    if (have_n) colsum(dXn, dg, Kn, oe + dn, N, h->d_node_off, mn, d_gf, dg, 0, 1);
-    if (have_e && mfma_e) { if ((rc = add_cols(dXe, Ke, de + 2 * dn, (size_t)R * G, dg, d_gf, 1, s))) return rc; }  // dXe holds S_g We^T here
-    else if (have_e) colsum(dXe, dg, dxe_stride, de + 2 * dn - dxe_col0, E, h->d_edge_off, me, d_gf, dg, 0, 1);
+    float* const acc = BF16 ? dgf_acc : d_gf;  // (bf16: the fp32 sum, rounded once below)
+    { ProfScope ps("bw_dgf", s);
+    GNX_LAUNCH(k_bw_dgf_init, blocks((size_t)R * G * dg), dim3(256), 0, s, have_g ? dXg : nullptr, Kg, oe + on, (int)(R * G), dg, acc);
+    if (have_n) colsum(dXn, dg, Kn, oe + dn, N, h->d_node_off, mn, acc, dg, 0, 1);
+    if (have_e && mfma_e) { if ((rc = add_cols(dXe, Ke, de + 2 * dn, (size_t)R * G, dg, acc, 1, s))) return rc; }  // dXe holds S_g We^T here
+    else if (have_e) colsum(dXe, dg, dxe_stride, de + 2 * dn - dxe_col0, E, h->d_edge_off, me, acc, dg, 0, 1); }
+    if (BF16 && (rc = launch_bf16_round(acc, (size_t)R * G * dg, d_gf, s))) return rc;
   }
   GNX_HIP(hipGetLastError());
+  return GNX_OK;
+}
+
+// workspace of a bf16 backward: gnx_block_backward's, then — native path — the fp32 sum of d_gf, or — staging path — fp32 copies of the nine
+// feature-shaped inputs and the three input gradients; every carve 256-B aligned
+struct TypedBwWs {
+  size_t base, dgf, off[12], n[12], total;
+  bool native;
+};
+static TypedBwWs typed_bw_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  TypedBwWs w{};
+  w.native = !bw_mfma_edge(h, p, R) && !bw_mfma_node(h, p, R);
+  w.base = bw_layout(h, p, R).total;
+  size_t o = align_up(w.base, 256);
+  if (w.native) {
+    w.dgf = o;
+    w.total = o + align_up(sizeof(float) * (size_t)R * (size_t)h->G * (size_t)std::max(p->dg, 0), 256);
+    return w;
+  }
+  const int64_t rows[3] = {h->E, h->N, h->G};
+  const int d[12] = {p->de, p->dn, p->dg, p->oe, p->on, p->og, p->oe, p->on, p->og, p->de, p->dn, p->dg};
+  for (int i = 0; i < 12; ++i) {
+    w.n[i] = (size_t)R * (size_t)rows[i % 3] * (size_t)std::max(d[i], 0);
+    w.off[i] = o;
+    o += align_up(sizeof(float) * w.n[i], 256);
+  }
+  w.total = o;
+  return w;
+}
+
+}  // namespace gnx
+
+using namespace gnx;
+
+extern "C" {
+
+size_t gnx_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  if (!h || !p || R <= 0) return 0;
+  (void)gnx_ensure_wide_tables(h);  // what the backward reads is built here, outside any capture (a failure resurfaces in the backward)
+  (void)gnx_ensure_csr(h);
+  return bw_layout(h, p, R).total;
+}
+
+int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
+                           const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
+                           const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
+                           void* ws, size_t ws_bytes, void* stream) {
+  return block_backward_t<false>(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr);
+}
+
+size_t gnx_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
+  if (elem == GNX_ELEM_F32) return gnx_block_backward_workspace_bytes(h, p, R);
+  if (elem != GNX_ELEM_BF16 || !h || !p || R <= 0) return 0;
+  (void)gnx_ensure_wide_tables(h);  // (as the fp32 query: outside any capture)
+  (void)gnx_ensure_csr(h);
+  return typed_bw_ws(h, p, R).total;
+}
+
+int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                 const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
+                                 const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  auto cf = [](const void* q) { return static_cast<const float*>(q); };
+  auto mf = [](void* q) { return static_cast<float*>(q); };
+  if (elem == GNX_ELEM_F32)
+    return gnx_block_backward(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf),
+                              mf(d_gf), grads, ws, ws_bytes, stream);
+  if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
+  if (rc) return rc;
+  const void* in[9] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out};
+  void* out[3] = {d_ef, d_nf, d_gf};
+  for (const void* b : in)
+    if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  for (const void* b : out)
+    if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  const TypedBwWs w = typed_bw_ws(h, p, R);
+  if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_backward_typed_workspace_bytes()");
+  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  char* base = static_cast<char*>(ws);
+  if (w.native)  // the kernels read and write bf16 themselves (declared float, like the feature pointers of BlockArgs)
+    return block_backward_t<true>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
+                                  mf(d_nf), mf(d_gf), grads, ws, w.base, stream, reinterpret_cast<float*>(base + w.dgf));
+  // matrix-core widths: widen into the workspace, the fp32 backward (its own DeviceTurn), round the input gradients
+  const hipStream_t s = (hipStream_t)stream;
+  float* st[12];
+  for (int i = 0; i < 12; ++i) st[i] = reinterpret_cast<float*>(base + w.off[i]);
+  for (int i = 0; i < 9; ++i)
+    if (in[i] && w.n[i] > 0 && (rc = launch_bf16_widen(in[i], w.n[i], st[i], s)) != GNX_OK) return rc;
+  auto src = [&](int i) -> const float* { return in[i] && w.n[i] > 0 ? st[i] : nullptr; };
+  auto dst = [&](int i) -> float* { return out[i] && w.n[9 + i] > 0 ? st[9 + i] : nullptr; };
+  rc = gnx_block_backward(h, p, src(0), src(1), src(2), src(3), src(4), src(5), src(6), src(7), src(8), R, dst(0), dst(1), dst(2), grads, ws, w.base, stream);
+  if (rc) return rc;
+  for (int i = 0; i < 3; ++i)
+    if (out[i] && w.n[9 + i] > 0 && (rc = launch_bf16_round(st[9 + i], w.n[9 + i], out[i], s)) != GNX_OK) return rc;
   return GNX_OK;
 }
 
@@ -857,7 +1007,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
       if ((rc = dw_reduce(gff, hbuf, rows[t], D, H, gr.ff[t].fc2, part, s))) return rc;
     } else {
       DeltaArgs a{dh, hbuf, dh, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, H, (int)rows[t], 1, act1, 0};  // delta1 = dh * act1'(h), in place
-      GNX_LAUNCH(k_bw_delta, dim3(blocks(rows[t] * H).x, 1), dim3(256), 0, s, a, (size_t)0, (size_t)0);
+      GNX_LAUNCH(k_bw_delta<0>, dim3(blocks(rows[t] * H).x, 1), dim3(256), 0, s, a, (size_t)0, (size_t)0);
     }
     if ((rc = dw_reduce(dh, F(L.l2[t]), rows[t], H, D, gr.ff[t].fc1, part, s))) return rc;                      // dW1 = delta1^T z
     launch_bw_dx(dim3(blocks(rows[t] * D).x, 1), s, dh, p->ff[t].fc1.weight, (int)rows[t], H, D, dz2, 0, 0, (float*)nullptr, 0);
@@ -1162,7 +1312,7 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
       int64_t mn = 1;
       for (int64_t g = 0; g < h->G; ++g) mn = std::max(mn, h->h_node_off[g + 1] - h->h_node_off[g]);
       const int S = (int)std::min<int64_t>(std::max<int64_t>(mn / 2048, 1), 256);
-      GNX_LAUNCH(k_bw_colsum1, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, dXn, dg, N, h->d_node_off, S, G, part, Kn, oe + dn);
+      GNX_LAUNCH(k_bw_colsum1<false>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, dXn, dg, N, h->d_node_off, S, G, part, Kn, oe + dn);
       GNX_LAUNCH(k_bw_colsum2, dim3((unsigned)G, Ru), dim3(64), 0, s, part, dg, S, G, d_gf, dg, 0, 1);
     }
     if (og > 0 && (rc = add_cols(dXg, Kg, oe + on, rows[2], dg, d_gf, 1, s))) return rc;

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "gnx_launchers.h"
+#include "gnx_wave_kernel.h"  // ld_feat: a bf16 or fp32 element of a feature buffer
 
 namespace gnx {
 
@@ -414,7 +415,9 @@ struct FnInArgs {
   float* out;
 };
 
-// one thread per output element; lanes run along the concatenated feature dim (coalesced row writes)
+// one thread per output element; lanes run along the concatenated feature dim (coalesced row writes).
+// BF16 (gnx_block_backward_typed): ef / nf / gf are bfloat16, widened on the gather (one 16-bit load per element); `out` is fp32 either way.
+template <bool BF16>
 __global__ void k_fn_input_edge(FnInArgs a) {
   const int K = a.de + 2 * a.dn + a.dg;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -422,13 +425,14 @@ __global__ void k_fn_input_edge(FnInArgs a) {
   if (idx >= (size_t)a.E * K) return;
   const int e = (int)(idx / K), k = (int)(idx % K);
   float v;
-  if (k < a.de) v = a.ef[(r * a.E + e) * a.de + k];
-  else if (k < a.de + a.dn) v = a.nf[(r * a.N + a.rowval[e]) * a.dn + (k - a.de)];
-  else if (k < a.de + 2 * a.dn) v = a.nf[(r * a.N + a.edge_dst[e]) * a.dn + (k - a.de - a.dn)];
-  else v = a.gf[(r * a.G + segment_of(a.edge_off, a.G, e)) * a.dg + (k - a.de - 2 * a.dn)];
+  if (k < a.de) v = ld_feat<BF16>(a.ef, (r * a.E + e) * a.de + k);
+  else if (k < a.de + a.dn) v = ld_feat<BF16>(a.nf, (r * a.N + a.rowval[e]) * a.dn + (k - a.de));
+  else if (k < a.de + 2 * a.dn) v = ld_feat<BF16>(a.nf, (r * a.N + a.edge_dst[e]) * a.dn + (k - a.de - a.dn));
+  else v = ld_feat<BF16>(a.gf, (r * a.G + segment_of(a.edge_off, a.G, e)) * a.dg + (k - a.de - 2 * a.dn));
   a.out[r * (size_t)a.E * K + idx] = v;
 }
 
+template <bool BF16>
 __global__ void k_fn_input_node(FnInArgs a) {
   const int K = a.de + a.dn + a.dg;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -437,11 +441,11 @@ __global__ void k_fn_input_node(FnInArgs a) {
   const int n = (int)(idx / K), k = (int)(idx % K);
   float v = 0.f;
   if (k < a.de) {
-    for (int e = a.colptr[n]; e < a.colptr[n + 1]; ++e) v += a.ef[(r * a.E + e) * a.de + k];  // CSC order
+    for (int e = a.colptr[n]; e < a.colptr[n + 1]; ++e) v += ld_feat<BF16>(a.ef, (r * a.E + e) * a.de + k);  // CSC order
   } else if (k < a.de + a.dn) {
-    v = a.nf[(r * a.N + n) * a.dn + (k - a.de)];
+    v = ld_feat<BF16>(a.nf, (r * a.N + n) * a.dn + (k - a.de));
   } else {
-    v = a.gf[(r * a.G + segment_of(a.node_off, a.G, n)) * a.dg + (k - a.de - a.dn)];
+    v = ld_feat<BF16>(a.gf, (r * a.G + segment_of(a.node_off, a.G, n)) * a.dg + (k - a.de - a.dn));
   }
   a.out[r * (size_t)a.N * K + idx] = v;
 }
@@ -471,16 +475,20 @@ __global__ __launch_bounds__(256) void k_fn_input_graph(FnInArgs a) {
   for (int k = tid; k < a.dg; k += 256) out[a.de + a.dn + k] = a.gf[(r * a.G + g) * a.dg + k];
 }
 
+// bf16: ef / nf / gf point to bfloat16 rows (kinds 0 and 1; the graph form has no bf16 caller)
 int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, const float* nf, int dn, const float* gf, int dg,
-                        int64_t R, float* out, hipStream_t s) {
+                        int64_t R, float* out, hipStream_t s, bool bf16) {
+  if (bf16 && kind == 2) return fail(GNX_ERR_INVALID_ARG, "launch_fn_input: the graph function's input has no bf16 form");
   if (kind == 0) { if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw; }  // (the edge form reads the destination of every edge)
   FnInArgs a{ef, nf, gf, de, dn, dg, (int)h->N, (int)h->E, (int)h->G, h->d_colptr, h->d_rowval, h->d_edge_dst, h->d_node_off, h->d_edge_off, out};
   if (kind == 0) {
     const size_t total = (size_t)h->E * (de + 2 * dn + dg);
-    if (total) GNX_LAUNCH(k_fn_input_edge, dim3((unsigned)((total + 255) / 256), (unsigned)R), dim3(256), 0, s, a);
+    if (total && bf16) GNX_LAUNCH(k_fn_input_edge<true>, dim3((unsigned)((total + 255) / 256), (unsigned)R), dim3(256), 0, s, a);
+    else if (total) GNX_LAUNCH(k_fn_input_edge<false>, dim3((unsigned)((total + 255) / 256), (unsigned)R), dim3(256), 0, s, a);
   } else if (kind == 1) {
     const size_t total = (size_t)h->N * (de + dn + dg);
-    if (total) GNX_LAUNCH(k_fn_input_node, dim3((unsigned)((total + 255) / 256), (unsigned)R), dim3(256), 0, s, a);
+    if (total && bf16) GNX_LAUNCH(k_fn_input_node<true>, dim3((unsigned)((total + 255) / 256), (unsigned)R), dim3(256), 0, s, a);
+    else if (total) GNX_LAUNCH(k_fn_input_node<false>, dim3((unsigned)((total + 255) / 256), (unsigned)R), dim3(256), 0, s, a);
   } else {
     GNX_LAUNCH(k_fn_input_graph, dim3((unsigned)h->G, (unsigned)R), dim3(256), 0, s, a);
   }

@@ -31,7 +31,8 @@ int32_t launch_xent_backward(const float* logits, const float* targets, int d, i
 int32_t launch_xent(const float* logits, const float* targets, int d, int64_t cols, float* out, float* ws, hipStream_t s);
 int32_t launch_collapse(const gnx_graphs* h, const float* ef, int d, int64_t R, float* out, hipStream_t s);
 int32_t launch_collapse_padded(const gnx_graphs* h, const float* ef, int d, int64_t R, float* out, hipStream_t s);
-int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, const float* nf, int dn, const float* gf, int dg, int64_t R, float* out, hipStream_t s);
+int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, const float* nf, int dn, const float* gf, int dg, int64_t R, float* out, hipStream_t s,
+                        bool bf16 = false);
 
 // ---- gnx_narrow.hip / gnx_narrow_bf16.hip / gnx_jit.cpp: the fused narrow block ----
 // launch_*: 1 when the path does not apply to these dims (the caller falls through to the next path); phase: GNX_PHASE_* (gnx_internal.h)

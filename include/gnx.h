@@ -416,6 +416,30 @@ GNX_API int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* 
                            const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef, float* d_nf,
                            float* d_gf, const gnx_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same backward on bfloat16 feature tensors: the pullback of gnx_block_forward_typed.  `elem` (GNX_ELEM_F32 or GNX_ELEM_BF16) applies to the
+ * twelve feature-shaped tensors — the nine inputs and d_ef / d_nf / d_gf; the parameter gradients (gnx_block_grads) stay fp32, as the weights
+ * do.  GNX_ELEM_F32 is exactly gnx_block_backward (same validation, same workspace size, same bits); any other `elem` is GNX_ERR_INVALID_ARG
+ * before any GPU work, and the workspace query returns 0 for it.  NULL rules, optional outputs, n_replicas rules and status codes are
+ * gnx_block_backward's.
+ * Contract, for finite data with GNX_ELEM_BF16: with ref = gnx_block_backward on the exactly widened nine inputs, d_ef / d_nf / d_gf are bit for
+ * bit to_bf16(ref's) (round to nearest even, once) and every parameter gradient is bit for bit ref's: every intermediate stays fp32 and all
+ * sums keep the fp32 backward's fixed orders.
+ * This is the fp32 pullback evaluated AT THE ROUNDED SAVED OUTPUTS: ef_out enters the node function's input and act' is taken from the stored
+ * (bf16) outputs, not from the unrounded values the forward held in registers.  It is this ABI's convention — the caller supplies the outputs —
+ * not a further approximation; a gelu level recomputes its pre-activation in fp32 from the (bf16) inputs.
+ * Paths, chosen as gnx_block_backward chooses for the same handle and widths: where neither the edge nor the node level goes to the matrix
+ * cores (any widths below 64 rows; README ex.1's widths at every size) the kernels read and write bf16 themselves — no conversion pass, and
+ * d_gf, which several launches accumulate, is summed in fp32 in the workspace and rounded once.  Matrix-core widths widen the nine inputs into
+ * fp32 regions of the workspace, run gnx_block_backward on them and round the three input gradients.  The workspace is
+ * gnx_block_backward_workspace_bytes plus, on the first path, 256-B aligned room for R * G * dg floats, on the second, the twelve fp32
+ * copies; the query builds the CSR view and the wide tables, so call it outside any capture.  bf16 buffers must be 4-byte aligned (rows of
+ * odd width are then 2-byte aligned: the kernels never assume more) and the workspace 16-byte aligned.  No allocation, no synchronisation. */
+GNX_API size_t gnx_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                         const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
+                                         const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the Chain block: takes the forward's INPUTS and the upstream gradients (NULL = zero); every layer's output is recomputed
  * into the workspace.  Gradients w.r.t. the inputs (optional) and, per chain, one gnx_dense_grad per layer (host arrays of n_layers
  * entries, or NULL; entries' pointers optional), all OVERWRITTEN.  The tail layers and the node / graph chains are row-wise Dense
