@@ -604,6 +604,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   constexpr size_t kElem = BF16 ? 2 : sizeof(float);  // bytes of a feature element
   const BwLayout L = bw_layout(h, p, R);
   if (!ws || ws_bytes < L.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_backward_workspace_bytes()");
+  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   rc = gnx_ensure_wide_tables(h, stream);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
   if (rc) return rc;
   rc = gnx_ensure_csr(h);
@@ -921,6 +922,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
   }
   const CoreBwLayout L = core_bw_layout(h, p, R);
   if (!ws || ws_bytes < L.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_core_backward_workspace_bytes()");
+  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
   char* base = static_cast<char*>(ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };

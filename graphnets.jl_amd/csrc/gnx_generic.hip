@@ -268,17 +268,27 @@ __global__ __launch_bounds__(256) void k_layernorm2_v4(const float* __restrict__
 // Row statistics only — stats[row] = (mean, 1/(sigma + eps) or 1/sqrt(var + eps)) with exactly the arithmetic of k_layernorm2_v4: the
 // matrix-core kernels of a wide GNCore normalise x as they LOAD it ((x - mean) * inv, then fma(gamma, ., beta): bit-identical to the
 // materialised gn1(x) / gn2(x)), so neither LayerNorm output is written to or read back from HBM (gncore.jl:56-59).
-template <int Q>
+// AL: x 16-byte and stats 8-byte aligned (the forms inside the library); !AL: both 4-byte aligned only (gnx_row_stats on a caller's view) —
+// the same values in the same order through dword-aligned loads and two stores: the same bits.
+template <int Q, bool AL = true>
 __global__ __launch_bounds__(256) void k_ln_stats_v4(const float* __restrict__ x, size_t rows, float eps, int eps_mode, float2* __restrict__ stats) {
   constexpr int D = 64 * Q;
   const int sub = threadIdx.x & 15;
   size_t row = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   const bool live = row < rows;
   row = live ? row : rows - 1;  // clamped: every lane takes part in the DPP reductions
-  const float4* xr = reinterpret_cast<const float4*>(x + row * D);
+  typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+  const float* xr = x + row * D;
   float4 v[Q];
 #pragma unroll
-  for (int q = 0; q < Q; ++q) v[q] = xr[sub + 16 * q];
+  for (int q = 0; q < Q; ++q) {
+    if constexpr (AL) {
+      v[q] = reinterpret_cast<const float4*>(xr)[sub + 16 * q];
+    } else {
+      const f32x4u u = *reinterpret_cast<const f32x4u*>(xr + 4 * (sub + 16 * q));
+      v[q] = make_float4(u.x, u.y, u.z, u.w);
+    }
+  }
   float s = 0.f;
 #pragma unroll
   for (int q = 0; q < Q; ++q) s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
@@ -291,19 +301,26 @@ __global__ __launch_bounds__(256) void k_ln_stats_v4(const float* __restrict__ x
   }
   var = row16_sum_g(var) * (1.f / (float)D);
   const float inv = eps_mode == 0 ? 1.f / (sqrtf(var) + eps) : 1.f / sqrtf(var + eps);
+  if constexpr (!AL) {
+    if (live && sub == 0) { reinterpret_cast<float*>(stats)[2 * row] = mu; reinterpret_cast<float*>(stats)[2 * row + 1] = inv; }
+    return;
+  }
   if (live && sub == 0) stats[row] = make_float2(mu, inv);  // (written whole, through lanes 0..3 or behind a fence: no difference to what round 6 chased — profiles/r06_overlap_hazard.log)
 }
 
-// 1: this width / alignment is not covered (the caller materialises the LayerNorm outputs instead)
+// false: this width / alignment is not covered by the kernels that normalise on load from a statistics table (the caller materialises the
+// LayerNorm outputs instead).  (The statistics pass itself takes any 4-byte aligned x: launch_ln_stats.)
 bool ln_stats_applies(const float* x, int d) { return ((uintptr_t)x & 15) == 0 && d % 64 == 0 && d <= 512; }
 
 int32_t launch_ln_stats(const float* x, size_t rows, int d, float eps, int eps_mode, float* stats, hipStream_t s) {
   if (rows == 0) return GNX_OK;
-  if (!ln_stats_applies(x, d) || ((uintptr_t)stats & 7)) return fail(GNX_ERR_INVALID_ARG, "launch_ln_stats: width / alignment not covered");
+  if (d <= 0 || d % 64 != 0 || d > 512) return fail(GNX_ERR_INVALID_ARG, "launch_ln_stats: width not covered (a multiple of 64 up to 512)");
+  const bool al = ((uintptr_t)x & 15) == 0 && ((uintptr_t)stats & 7) == 0;
   ProfScope ps("k_ln_stats", s);
   const dim3 grid((unsigned)((rows + 15) / 16));
   switch (d / 64) {
-#define GNX_LN_CASE(Q) case Q: GNX_LAUNCH((k_ln_stats_v4<Q>), grid, dim3(256), 0, s, x, rows, eps, eps_mode, reinterpret_cast<float2*>(stats)); break;
+#define GNX_LN_CASE(Q) case Q: if (al) GNX_LAUNCH((k_ln_stats_v4<Q, true>), grid, dim3(256), 0, s, x, rows, eps, eps_mode, reinterpret_cast<float2*>(stats)); \
+                               else GNX_LAUNCH((k_ln_stats_v4<Q, false>), grid, dim3(256), 0, s, x, rows, eps, eps_mode, reinterpret_cast<float2*>(stats)); break;
     GNX_LN_CASE(1) GNX_LN_CASE(2) GNX_LN_CASE(3) GNX_LN_CASE(4) GNX_LN_CASE(5) GNX_LN_CASE(6) GNX_LN_CASE(7) GNX_LN_CASE(8)
 #undef GNX_LN_CASE
   }

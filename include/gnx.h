@@ -35,12 +35,18 @@
  *     gradients) untouched, and its result does not depend on what the workspace held before — except between the phases of the forms that
  *     say so (GNX_FLAG_DEFER_GRAPH_UPDATE -> gnx_block_graph_update, gnx_block_forward_chained, the steps of gnx_block_forward_steps).
  *     tests/test_gpu_memory_contract.py holds every dispatch form to this.
- *   - Alignment of fp32 buffers: 4 bytes (a float) is all the narrow and generic kernels assume (their row accesses are dword-aligned vector
- *     loads).  The matrix-core launchers (any width above 32: csrc/gnx_wide.hip, gnx_edge_x6.hip, gnx_ffn_*.hip, gnx_backward_wide.hip) TEST
- *     16-byte alignment of the feature, weight and output pointers they are handed and take an element-wise or another kernel form when it
- *     does not hold; the six-term kernels refuse a bias or LayerNorm gamma / beta vector that is not 16-byte aligned with GNX_ERR_INVALID_ARG
- *     instead.  A workspace must be 16-byte aligned (GNX_ERR_WORKSPACE otherwise).  Every device allocator returns 256-byte aligned memory and
- *     the tests run with nothing less: fp32 buffers at other alignments (a view into the middle of a tensor) are untested.
+ *   - Alignment: every public entry point accepts fp32 and bf16 buffers (features, weights, biases, LayerNorm gamma / beta, upstream and
+ *     input gradients, parameter gradients) that are 4-byte aligned (a bf16 buffer too: GNX_ERR_INVALID_ARG below that; its rows of odd width
+ *     are then 2-byte aligned); only the workspace needs 16 bytes (GNX_ERR_WORKSPACE otherwise, before anything is written).  The narrow and
+ *     generic kernels assume no more than the 4 bytes.  The matrix-core launchers (any width above 32: csrc/gnx_wide.hip, gnx_edge_x6.hip,
+ *     gnx_ffn_*.hip, gnx_backward_wide.hip) TEST 16-byte alignment of the pointers they are handed — and of the replica strides R > 1 adds to
+ *     them — and take an element-wise or another kernel form when it does not hold; the six-term kernels need their bias and LayerNorm gamma /
+ *     beta vectors 16-byte aligned, and the plans (wide_plan, the core's form decision) take another form when they are not: a launcher's own
+ *     refusal of such a vector is an internal defence no public call reaches.  Results at another alignment meet the same bounds; where no
+ *     summation order depends on an address (narrow, generic and bf16 kernels) they are the same bits.  Tested: tests/test_gpu_alignment.py
+ *     runs every case of the memory-contract table with its buffers at 256 k + 4, + 8 and + 12 bytes — all of them at once, features only,
+ *     parameters only, and one operand group at a time —, replica strides that are no multiple of 16 bytes, and the Python mirror on views
+ *     into the middle of a tensor; tests/test_arena_cpu.py counts the pointer-alignment tests of csrc/ so that a new one comes with its case.
  */
 #ifndef GNX_H
 #define GNX_H
@@ -543,7 +549,8 @@ GNX_API int32_t gnx_core_backward_train(const gnx_graphs* h, const gnx_core_para
 /* ---- row statistics of a packed [rows][d] tensor: stats[row] = (mean, 1 / (sigma + eps)) (eps_mode 0, Flux 0.14 `normalise`) or
  * (mean, 1 / sqrt(sigma^2 + eps)) (eps_mode 1), uncorrected sigma — the one pass over x from which the wide kernels apply GNGraphNorm's
  * LayerNorms (src/gngraphnorm.jl:19-26) as they load their rows; exported as the building block it is (and so that it can be exercised
- * on its own: tests/overlap_probe.py).  d must be a multiple of 64 up to 512, x 16-byte aligned, stats [rows][2] 8-byte aligned. */
+ * on its own: tests/overlap_probe.py).  d must be a multiple of 64 up to 512; x and stats [rows][2] 4-byte aligned as every fp32 buffer (the
+ * same bits at any alignment). */
 GNX_API int32_t gnx_row_stats(const float* x, int64_t rows, int32_t d, float eps, int32_t eps_mode, float* stats, void* stream);
 
 /* ---- materialised update-function inputs: the reference's exported building blocks getedgefninput /

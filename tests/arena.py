@@ -12,12 +12,15 @@ outside a buffer the call may write lands on a byte a test looks at.
 
 Layout: every carve starts ALIGN-byte aligned and has exactly the byte size it was declared with (a carve of 0 bytes is allowed: it has an
 address and guards, and nothing may be written at it); at least GUARD sentinel bytes lie before the first carve, between two carves and
-behind the last one.  Plain torch: the same code checks CPU tensors (tests/test_arena_cpu.py proves that the checker can fail)."""
+behind the last one.  `Arena(device, skew=f)` moves the start of carve c to its aligned start + f(c) bytes (even, below ALIGN, a multiple of
+the carve's element size): the same buffers at addresses that are 256 k + 4, + 8, ... — a view into the middle of a tensor — with the same
+guards (tests/test_gpu_alignment.py).  Plain torch: the same code checks CPU tensors (tests/test_arena_cpu.py proves that the checker can fail)."""
 import numpy as np
 import torch
 
 GUARD = 64 * 1024  # a condition, not a measurement: a stray row or a whole stray tile still lands inside the arena
-ALIGN = 256        # what torch's allocator gives every tensor; the ABI states no alignment for fp32 feature buffers
+ALIGN = 256        # what torch's allocator gives every tensor, and where a carve starts without a skew; the ABI asks 4 bytes of fp32 and bf16
+                   # buffers and 16 of a workspace (include/gnx.h), which Arena(skew=...) places a carve at
 SENTINEL = 0xA5
 UNWRITTEN = 0xFF   # fp32 0xFFFFFFFF and bf16 0xFFFF are NaNs
 
@@ -41,9 +44,10 @@ def _bytes_of(data):
 
 
 class Arena:
-    def __init__(self, device="cpu", guard=GUARD):
-        self.device, self.guard = torch.device(device), int(guard)
-        self.carves, self.by_name, self.buf, self.snap = [], {}, None, None
+    def __init__(self, device="cpu", guard=GUARD, skew=None):
+        """`skew`: None, or a callable (Carve) -> bytes by which the carve starts behind its ALIGN-aligned start"""
+        self.device, self.guard, self.skew = torch.device(device), int(guard), skew
+        self.carves, self.by_name, self.buf, self.snap, self.queries = [], {}, None, None, []
 
     # ---- declaration ----
     def _add(self, c):
@@ -73,12 +77,19 @@ class Arena:
             return self._add(c)
         return self._add(Carve(name, WORKSPACE, nbytes, None, torch.uint8, (int(nbytes),)))
 
+    def _skew_of(self, c):
+        if self.skew is None:
+            return 0
+        k = int(self.skew(c))
+        assert 0 <= k < ALIGN and k % 2 == 0, (c.name, k)
+        assert k % torch.empty(0, dtype=c.dtype).element_size() == 0, (c.name, k, c.dtype)
+        return k
+
     # ---- build / refill ----
     def build(self, ws_fill=0x00):
         late = [c for c in self.carves if c.kind == WORKSPACE and callable(c.data)]
         if late:
-            queries = [(c, c.data) for c in late]
-            kept = [(c, c.data) for c in self.carves if c.kind == INPUT]
+            queries = self.queries = [(c, c.data) for c in late]
             for c in late:
                 c.data = None
             self.build(ws_fill)  # provisional: the late workspaces have no bytes yet
@@ -86,12 +97,10 @@ class Arena:
                 c.nbytes = int(q())
                 assert c.nbytes >= 0
                 c.shape = (c.nbytes,)
-            for c, d in kept:
-                c.data = d if d is not None and c.nbytes == 0 else self.raw(c.name).cpu()
             self.buf = self.snap = None
         off = 0
         for c in self.carves:
-            off = (off + self.guard + ALIGN - 1) // ALIGN * ALIGN
+            off = (off + self.guard + ALIGN - 1) // ALIGN * ALIGN + self._skew_of(c)
             c.off = off
             off += c.nbytes
         total = off + self.guard
@@ -101,11 +110,20 @@ class Arena:
         assert self.buf.data_ptr() % ALIGN == 0
         for c in self.carves:
             if c.kind == INPUT and c.nbytes:
-                self.buf[c.off:c.off + c.nbytes] = c.data.to(self.device)
-                c.data = None
+                self.buf[c.off:c.off + c.nbytes] = c.data.to(self.device)  # (the declared bytes stay in c.data: every layout starts from them)
         self.refill(ws_fill)
         self.snap = self.buf.clone()
         return self
+
+    def relayout(self, skew, ws_fill=0x00):
+        """the same carves laid out again under another skew (None: aligned): what build() would have given had the arena been declared with
+        it.  The inputs are filled from the bytes they were DECLARED with, not from the previous layout — a call that corrupted an input there is
+        reported there and nowhere else.  The workspace queries run again, at the new addresses."""
+        assert self.buf is not None
+        for c, q in self.queries:
+            c.data, c.nbytes, c.shape = q, 0, (0,)
+        self.skew, self.buf, self.snap = skew, None, None
+        return self.build(ws_fill)
 
     def refill(self, ws_fill):
         """outputs back to 0xFF bytes, every workspace to `ws_fill` — the state before a call (inputs and guards are left as they are: a call

@@ -1,6 +1,9 @@
 """The arena checker of tests/arena.py on CPU tensors: the proof that tests/test_gpu_memory_contract.py can fail.  Every situation the checker
 exists for is produced by writing the byte directly — no GPU and no broken kernel — and must be reported, with the carve, the side and the
 offsets named; a call that stays inside its output and workspace carves must not be."""
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -186,3 +189,187 @@ def test_a_workspace_sized_by_a_query_that_needs_addresses():
     assert a.violations() == []
     a.buf[a.by_name["ws"].off + 777] = 0
     assert "AFTER workspace 'ws' (777 bytes)" in a.violations()[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# skewed carves: the same buffers at 256 k + 4 / + 8 / + 12 (+ 2 for a bf16 carve), tests/test_gpu_alignment.py
+# ---------------------------------------------------------------------------------------------------------------------------------------
+SKEWS = {"x": 4, "y": 8, "ws": 0, "empty": 12, "z": 2}
+
+
+def _skewed(ws_fill=0x00):
+    a = AR.Arena("cpu", skew=lambda c: SKEWS[c.name])
+    a.input("x", np.arange(35, dtype=np.float32).reshape(1, 7, 5))
+    a.output("y", (1, 7, 3), torch.float32)
+    a.workspace("ws", 1000)
+    a.input("empty", np.zeros((1, 0, 4), dtype=np.float32))
+    a.output("z", (3, 5), torch.bfloat16)
+    return a.build(ws_fill=ws_fill)
+
+
+def test_a_skewed_layout_is_exact_skewed_and_guarded():
+    a = _skewed()
+    sizes = {"x": 140, "y": 84, "ws": 1000, "empty": 0, "z": 30}
+    prev_end = 0
+    for c in a.carves:
+        assert c.nbytes == sizes[c.name] and a.raw(c.name).numel() == sizes[c.name]
+        assert c.off % AR.ALIGN == SKEWS[c.name] and a.ptr(c.name) % AR.ALIGN == SKEWS[c.name]
+        assert c.off - prev_end >= AR.GUARD
+        prev_end = c.off + c.nbytes
+    assert a.buf.numel() - prev_end == AR.GUARD
+    assert np.array_equal(a.numpy("x"), np.arange(35, dtype=np.float32).reshape(1, 7, 5))
+    assert bool((a.raw("ws") == 0).all()) and bool(torch.isnan(a.view("y")).all()) and bool(torch.isnan(a.view("z").float()).all())
+    mask = torch.ones_like(a.buf, dtype=torch.bool)
+    for c in a.carves:
+        mask[c.off:c.off + c.nbytes] = False
+    assert bool((a.buf[mask] == AR.SENTINEL).all())
+    _write_all_outputs(a)
+    assert a.violations() == []
+    # skew=None and a skew of 0 everywhere are the unskewed layout, byte for byte
+    b, z = _arena(), AR.Arena("cpu", skew=lambda c: 0)
+    z.input("x", np.arange(35, dtype=np.float32).reshape(1, 7, 5)); z.output("y", (1, 7, 3), torch.float32); z.workspace("ws", 1000)
+    z.input("empty", np.zeros((1, 0, 4), dtype=np.float32)); z.output("z", (3, 5), torch.bfloat16)
+    z.build()
+    assert [c.off for c in b.carves] == [c.off for c in z.carves] and torch.equal(b.buf, z.buf)
+
+
+@pytest.mark.parametrize("bad", [3, 256, -4, 6])
+def test_a_skew_outside_the_rule_is_refused(bad):
+    """odd, >= ALIGN, negative, or (6 on an fp32 carve) no multiple of the element size"""
+    a = AR.Arena("cpu", skew=lambda c: bad)
+    a.output("y", (4,), torch.float32)
+    with pytest.raises(AssertionError):
+        a.build()
+
+
+@pytest.mark.parametrize("carve", ["x", "y", "z"])
+def test_a_byte_just_before_a_skewed_carve_is_reported(carve):
+    a = _skewed()
+    _write_all_outputs(a)
+    a.buf[a.by_name[carve].off - 1] = 0   # (inside the ALIGN-aligned start .. start + skew: still a guard byte)
+    found = a.violations()
+    assert len(found) == 1 and "BEFORE" in found[0] and f"'{carve}'" in found[0] and "first at -1 and last at -1" in found[0], found
+    b = _skewed()
+    _write_all_outputs(b)
+    c = b.by_name[carve]
+    b.buf[c.off - SKEWS[carve]] = 0       # the aligned address a vector store rounded down to would hit
+    found = b.violations()
+    assert len(found) == 1 and f"BEFORE {c.kind} '{carve}'" in found[0] and f"first at {-SKEWS[carve]:+d}" in found[0], found
+
+
+@pytest.mark.parametrize("carve", ["x", "y", "z", "empty"])
+def test_a_byte_just_after_a_skewed_carve_is_reported(carve):
+    a = _skewed()
+    _write_all_outputs(a)
+    c = a.by_name[carve]
+    a.buf[c.off + c.nbytes] = 0
+    a.buf[c.off + c.nbytes + 11] = 0
+    found = a.violations()
+    assert len(found) == 1 and "AFTER" in found[0] and f"'{carve}'" in found[0] and "2 bytes, first at +0 and last at +11" in found[0], found
+
+
+def test_a_late_workspace_in_a_skewed_arena_is_laid_out_twice():
+    sk = {"w": 12, "ws": 0, "y": 4, "h": 2}
+    a = AR.Arena("cpu", skew=lambda c: sk[c.name])
+    w = np.arange(12, dtype=np.float32)
+    a.input("w", w)
+    seen = []
+
+    def query():
+        seen.append(a.ptr("w"))
+        assert a.ptr("w") % AR.ALIGN == 12 and np.array_equal(a.numpy("w"), w)
+        return 777
+    a.workspace("ws", query)
+    a.output("y", (5,), torch.float32)
+    a.input("h", torch.arange(7, dtype=torch.float32).to(torch.bfloat16))
+    a.build(ws_fill=0xFF)
+    assert len(seen) == 1 and a.nbytes("ws") == 777 and bool((a.raw("ws") == 0xFF).all())
+    for n, k in sk.items():
+        assert a.ptr(n) % AR.ALIGN == k, n
+    assert np.array_equal(a.numpy("w"), w) and np.array_equal(a.numpy("h"), np.arange(7, dtype=np.float32))
+    assert a.by_name["y"].off - (a.by_name["ws"].off + 777) >= AR.GUARD
+    a.view("y")[:] = 0.0
+    assert a.violations() == []
+    a.buf[a.by_name["y"].off - 1] = 0
+    assert "BEFORE output 'y'" in a.violations()[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# completeness of tests/test_gpu_alignment.py: every host-side pointer-alignment test of csrc/
+# ---------------------------------------------------------------------------------------------------------------------------------------
+ALIGNMENT_TEST = re.compile(r"\bal16\(|(?:\(uintptr_t\)|\(al\b)[^;{}]*?&\s*(?:15|7|3)\b")  # (`al`: the OR of a predicate's pointers, *_applies)
+
+# file -> number of source lines holding a pointer-alignment test.  Each of them picks a kernel form (or refuses a call) by the address of a
+# caller's buffer; tests/test_gpu_alignment.py runs both sides of them.
+ALIGNMENT_SITES = {
+    "gnx_backward.hip": 8,       # launch_delta's `al`; the typed entry's bf16 checks; four workspace checks; the core backward's al16
+    "gnx_backward_wide.hip": 2,  # k_dw_gemm's and the segmented sums' v4
+    "gnx_chain.cpp": 1,          # workspace
+    "gnx_dropout.hip": 2,        # the quad / scalar mask kernel; workspace
+    "gnx_edge_n.hip": 1,
+    "gnx_edge_x6.hip": 10,       # proj_x6_applies, node_x6_applies and the launchers' refusals
+    "gnx_ffn_fused.hip": 2,      # ffn_fused_applies; the LayerNorm-on-load refusal
+    "gnx_ffn_x6.hip": 5,         # ffn_x6_applies and the launchers' refusals
+    "gnx_forward.hip": 6,        # workspace and bf16 checks of the entry points; the core's wide_ln decision
+    "gnx_generic.hip": 3,        # ln_stats_applies, launch_ln_stats, launch_layernorm2's al16
+    "gnx_wide.hip": 17,          # al16 itself, out_vec, launch_gemm's g.vec and refusals, wide_plan
+}
+
+
+def alignment_sites():
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "graphnets.jl_amd", "csrc")
+    out = {}
+    for f in sorted(os.listdir(src)):
+        if f.endswith((".hip", ".cpp", ".h")):
+            n = sum(1 for line in open(os.path.join(src, f), encoding="utf-8") if ALIGNMENT_TEST.search(line))
+            if n:
+                out[f] = n
+    return out
+
+
+def test_every_pointer_alignment_branch_is_counted():
+    found = alignment_sites()
+    assert found == ALIGNMENT_SITES, (
+        "the pointer-alignment tests of csrc/ changed: " +
+        ", ".join(f"{f}: {ALIGNMENT_SITES.get(f, 0)} -> {found.get(f, 0)}" for f in sorted(set(found) | set(ALIGNMENT_SITES)) if found.get(f) != ALIGNMENT_SITES.get(f)) +
+        ".  A new alignment branch needs a one(...) group or an anchor case in tests/test_gpu_alignment.py that takes both of its sides BEFORE "
+        "the count here is updated.")
+
+
+def test_relayout_moves_the_carves_and_keeps_their_bytes():
+    a = AR.Arena("cpu")
+    w = np.arange(12, dtype=np.float32)
+    a.input("w", w)
+    calls = []
+    a.workspace("ws", lambda: calls.append(a.ptr("w") % AR.ALIGN) or 777)
+    a.output("y", (5,), torch.float32)
+    a.build(ws_fill=0xFF)
+    a.view("y")[:] = 3.0
+    a.relayout(lambda c: {"w": 8, "ws": 0, "y": 12}[c.name], ws_fill=0x11)
+    assert calls == [0, 8] and a.nbytes("ws") == 777 and bool((a.raw("ws") == 0x11).all())
+    assert a.ptr("w") % AR.ALIGN == 8 and a.ptr("y") % AR.ALIGN == 12 and a.ptr("ws") % AR.ALIGN == 0
+    assert np.array_equal(a.numpy("w"), w) and bool(torch.isnan(a.view("y")).all())
+    found = a.violations()
+    assert len(found) == 1 and "5 of 5 elements never written" in found[0], found
+    a.relayout(None)
+    b = AR.Arena("cpu")
+    b.input("w", w); b.workspace("ws", 777); b.output("y", (5,), torch.float32)
+    b.build()
+    assert [c.off for c in a.carves] == [c.off for c in b.carves] and torch.equal(a.buf, b.buf)
+
+
+def test_relayout_fills_the_inputs_from_their_declared_bytes():
+    """an input a call corrupted under one layout is reported there; the next layout of the same arena starts from the declared bytes again"""
+    a = AR.Arena("cpu")
+    w = np.arange(12, dtype=np.float32)
+    a.input("w", w)
+    a.workspace("ws", lambda: 64)
+    a.output("y", (5,), torch.float32)
+    a.build()
+    a.view("w")[3] = -1.0
+    a.view("y")[:] = 0.0
+    assert any("input 'w' was modified" in f for f in a.violations())
+    a.relayout(lambda c: 0 if c.kind == AR.WORKSPACE else 4)
+    assert np.array_equal(a.numpy("w"), w) and a.ptr("w") % AR.ALIGN == 4
+    a.view("y")[:] = 0.0
+    assert a.violations() == []

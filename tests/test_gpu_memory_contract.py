@@ -2,7 +2,7 @@
 
 The rest of the suite checks values; this module checks where a call writes.  Every case calls the ABI through `gn._lib.load()` directly with ALL
 its buffers — features, weights, gradients, workspaces — carved out of one sentinel-filled arena (tests/arena.py: exact byte sizes, 256-byte
-aligned starts, 64 KiB of sentinel on both sides of every carve) and asserts, in this order:
+aligned starts — tests/test_gpu_alignment.py runs the same table at 4-byte aligned ones —, 64 KiB of sentinel on both sides of every carve) and asserts, in this order:
 
   1. the call returns 0;
   2. every byte of the arena outside an output or workspace carve is unchanged (guards intact, inputs bit-identical) and no output element still
@@ -414,39 +414,42 @@ def _dense_grad(gn, a, name):
     return _L(gn).DenseGrad(a.ptr(name + ".dW"), a.ptr(name + ".db"))
 
 
-def block_backward_case(graph, in_dims, out_dims, act=(2, 3, 0), seed=0):
+def block_backward_case(graph, in_dims, out_dims, act=(2, 3, 0), seed=0, R=1):
     """gnx_block_backward: forward inputs, forward outputs (the float64 forward rounded to fp32) and cotangents are inputs; d_ef / d_nf / d_gf
-    and all six parameter gradients are outputs.  One replica, as the torch restatement."""
+    and all six parameter gradients are outputs.  The torch restatement runs replica by replica on the same parameter leaves (R > 1: one graph,
+    the parameter gradients are sums over the replicas)."""
     def setup(gn, a):
         lib = _L(gn).load()
         g, csc = graph(gn)
         rng = np.random.default_rng(3000 + seed)
         p = O.make_block_params(rng, in_dims, out_dims, act=act)
         _decl_block(a, p)
-        x = U.packed_inputs(rng, 1, g.n_edges, g.n_nodes, g.n_graphs, in_dims)
+        x = U.packed_inputs(rng, R, g.n_edges, g.n_nodes, g.n_graphs, in_dims)
         W = {k: torch.tensor(p[k], dtype=torch.float64, requires_grad=True) for k in ("We", "be", "Wn", "bn", "Wg", "bg")}
-        xs = [None if v is None else torch.tensor(v[0], dtype=torch.float64, requires_grad=True) for v in x]
-        outs_r = _torch_block(p, csc, *xs, W)
-        cot = [rng.standard_normal(tuple(o.shape)) for o in outs_r]
-        sum((o * torch.from_numpy(c)).sum() for o, c in zip(outs_r, cot) if o.shape[1] > 0).backward()
+        xs = [[None if v is None else torch.tensor(v[r], dtype=torch.float64, requires_grad=True) for v in x] for r in range(R)]
+        outs_r = [_torch_block(p, csc, *xs[r], W) for r in range(R)]
+        cot = [[rng.standard_normal(tuple(o.shape)) for o in outs_r[r]] for r in range(R)]
+        sum((o * torch.from_numpy(c)).sum() for r in range(R) for o, c in zip(outs_r[r], cot[r]) if o.shape[1] > 0).backward()
+        stack = lambda per_rep, k: np.stack([np.asarray(per_rep[r][k].detach() if isinstance(per_rep[r][k], torch.Tensor) else per_rep[r][k]) for r in range(R)]).astype(np.float32)
         ins = [_decl(a, n, v) for n, v in zip(("ef", "nf", "gf"), x)]
-        fw = [_decl(a, n, o.detach().numpy().astype(np.float32)[None]) if d > 0 else None for n, o, d in zip(("ef_out", "nf_out", "gf_out"), outs_r, out_dims)]
-        gs = [_decl(a, n, c.astype(np.float32)[None]) if d > 0 else None for n, c, d in zip(("g_ef_out", "g_nf_out", "g_gf_out"), cot, out_dims)]
+        fw = [_decl(a, n, stack(outs_r, k)) if d > 0 else None for k, (n, d) in enumerate(zip(("ef_out", "nf_out", "gf_out"), out_dims))]
+        gs = [_decl(a, n, stack(cot, k)) if d > 0 else None for k, (n, d) in enumerate(zip(("g_ef_out", "g_nf_out", "g_gf_out"), out_dims))]
         dx = [a.output(n, v.shape) if v is not None else None for n, v in zip(("d_ef", "d_nf", "d_gf"), x)]
         for fn, w, b in (("edgefn", "We", "be"), ("nodefn", "Wn", "bn"), ("graphfn", "Wg", "bg")):
             _decl_dense_grad(a, f"grad.{fn}", p[w], p[b])
-        ws = a.workspace("ws", lambda: lib.gnx_block_backward_workspace_bytes(g._h, C.byref(_block_params(gn, a, p)), 1))
+        ws = a.workspace("ws", lambda: lib.gnx_block_backward_workspace_bytes(g._h, C.byref(_block_params(gn, a, p)), R))
 
         def run(a):
             P = a.ptr
             gr = _L(gn).BlockGrads(*[_dense_grad(gn, a, f"grad.{fn}") for fn in ("edgefn", "nodefn", "graphfn")])
-            return lib.gnx_block_backward(g._h, C.byref(_block_params(gn, a, p)), *map(P, ins), *map(P, fw), *map(P, gs), 1, *map(P, dx), C.byref(gr),
+            return lib.gnx_block_backward(g._h, C.byref(_block_params(gn, a, p)), *map(P, ins), *map(P, fw), *map(P, gs), R, *map(P, dx), C.byref(gr),
                                           P(ws), a.nbytes(ws), _stream())
 
         def verify(a, what):
-            for n, t in zip(dx, xs):
+            for k, n in enumerate(dx):
                 if n is not None:
-                    _grad_close(a.numpy(n)[0], t.grad, f"{what} {n}", 2e-4)
+                    for r in range(R):
+                        _grad_close(a.numpy(n)[r], xs[r][k].grad, f"{what} {n}[{r}]", 2e-4)
             for fn, w, b in (("edgefn", "We", "be"), ("nodefn", "Wn", "bn"), ("graphfn", "Wg", "bg")):
                 _grad_close(a.numpy(f"grad.{fn}.dW").T, W[w].grad, f"{what} dW {fn}", 2e-4)
                 _grad_close(a.numpy(f"grad.{fn}.db"), W[b].grad, f"{what} db {fn}", 2e-4)
@@ -894,6 +897,9 @@ CASES = {
     "block/encoder(10,5,0)=>(128,64,32)": block_case(BIG1, (10, 5, 0), (128, 64, 32), seed=57, act=(1, 1, 0)),
     "block/encoder(10,5,3)=>(128,64,32)/R3": block_case(g_hub(1001, 7001, 333), (10, 5, 3), (128, 64, 32), R=3, seed=58, act=(1, 1, 0)),
     "block/wide/small-graphs": block_case(g_medium(seed=30), *WIDE, seed=30, act=(1, 1, 0)),
+    # every replica stride (4097 . 33, 601 . 17, 4097 . 40, ... floats) is odd or 2 mod 4: replicas 1 and 2 start 4-byte aligned only, inside
+    # an aligned buffer (tests/test_gpu_alignment.py)
+    "block/wide-odd(33,17,5)=>(40,35,7)/R3": block_case(g_er(601, 4097), (33, 17, 5), (40, 35, 7), R=3, seed=59, act=(1, 1, 0)),
     # ---- deferred, chained, steps ----
     "block/deferred/readme": block_case(BIG1, *README, seed=31, entry="deferred"),
     "block/deferred/wide": block_case(WIDE_G, *WIDE, seed=32, act=(1, 1, 0), entry="deferred"),
@@ -966,6 +972,7 @@ CASES = {
     "block-backward/small/width-0-nodefn": block_backward_case(g_small(seed=112), (6, 5, 0), (4, 0, 3), seed=112),
     "block-backward/small/no-edges": block_backward_case(g_no_edges, (4, 3, 2), (2, 3, 2), seed=113),
     "block-backward/big/odd(37,22,5)": block_backward_case(g_big3(seed=114), (37, 22, 5), (35, 19, 7), seed=114),
+    "block-backward/big/odd(37,22,5)/R3": block_backward_case(g_er(4099, 12007), (37, 22, 5), (35, 19, 7), seed=121, R=3),
     "block-backward/big/wide": block_backward_case(g_big3(seed=115), *WIDE, seed=115),
     "block-backward/big/gelu": block_backward_case(g_big3(seed=116), (40, 24, 8), (36, 20, 12), act=(4, 4, 4), seed=116),
     "core-backward/small(10,5,3)": core_backward_case(g_small(seed=117), (10, 5, 3), seed=117),
@@ -1023,6 +1030,7 @@ EXPECT = {
     "block/wide/128=>(3,4,5)/R3/EDGE_NARROW_FP32": ({"k_rows_gemm_edge"}, _X6),
     "block/wide/128=>(3,4,5)/4095-edges": ({"k_rows_gemm_edge"}, _X6),
     "block/encoder(10,5,0)=>(128,64,32)": ({"k_edge_x6_prep"}, {"k_rows_gemm_proj"}),
+    "block/wide-odd(33,17,5)=>(40,35,7)/R3": ({"k_rows_gemm_proj", "k_rows_gemm_edge", "k_rows_gemm_node", "k_graph_wide"}, _GENERIC | _X6 | {"k_block_wave"}),
     "block/chained/one-graph": ({"k_block_wave", "k_graph_t"}, set()),
     "block/steps/mid-widths": ({"k_rows_gemm_edge"}, {"k_block_wave"}),
     "bf16/readme/one-graph/R3": ({"k_block_wave"}, _BF16),
@@ -1055,6 +1063,8 @@ EXPECT = {
     "chain/backward/big": ({"k_dw_gemm", "bw_dx_chain", "bw_layernorm"}, set()),
     "block-backward/small/readme": ({"bw_dx_generic", "bw_dw_generic", "bw_dnf"}, {"k_dw_gemm", "bw_dx_node"}),
     "block-backward/small/gelu+gf": ({"bw_gelu_preact", "bw_dgf"}, {"k_dw_gemm"}),
+    "block-backward/big/odd(37,22,5)/R3": ({"k_dw_gemm", "bw_dx_node", "bw_dx_edge_ef", "bw_segsum_src", "bw_segsum_dst", "bw_dx_nf_src", "bw_dx_nf_dst"},
+                                           set()),
     "block-backward/big/wide": ({"k_dw_gemm", "k_dw_final2", "bw_dx_node", "bw_dx_edge_ef", "bw_segsum_src", "bw_segsum_dst"}, set()),
     "block-backward/big/gelu": ({"k_dw_gemm", "bw_gelu_preact", "bw_dx_node"}, set()),
     "core-backward/small/gelu/eps1": ({"bw_gelu_hidden", "bw_layernorm"}, {"k_dw_gemm"}),
