@@ -317,17 +317,21 @@ def _no_bf16(what, *tensors):
     """The fp32-only entry points: a bfloat16 feature tensor is refused instead of having its bytes read as floats."""
     for t in tensors:
         if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16:
-            raise TypeError(f"{what}: bfloat16 features are supported by GNBlock only (gnx_block_forward_typed); convert with .float()")
+            if what == "GNCore":
+                raise TypeError("GNCore: bfloat16 features need the core's bf16 switch (GNCore(dims, bf16=True) or core.bf16 = True: "
+                                "gnx_core_forward_typed, no gradient); or convert with .float()")
+            raise TypeError(f"{what}: bfloat16 features are supported by GNBlock and GNCore(bf16=True) only (gnx_block_forward_typed, "
+                            "gnx_core_forward_typed); convert with .float()")
 
 
-def _feature_dtype(ef, nf, gf):
+def _feature_dtype(ef, nf, gf, what="GNBlock"):
     """torch.bfloat16 when every present feature tensor is bf16, else None (the fp32 path, other dtypes as before); mixed bf16 / other: TypeError."""
     present = [a for a in (ef, nf, gf) if isinstance(a, torch.Tensor)]
     n = sum(a.dtype == torch.bfloat16 for a in present)
     if n == 0:
         return None
     if n != len(present):
-        raise TypeError("GNBlock: the features mix bfloat16 and " + ", ".join(sorted({str(a.dtype) for a in present if a.dtype != torch.bfloat16})) +
+        raise TypeError(what + ": the features mix bfloat16 and " + ", ".join(sorted({str(a.dtype) for a in present if a.dtype != torch.bfloat16})) +
                         " tensors; batch them with one dtype (batch(..., dtype=...))")
     return torch.bfloat16
 
@@ -1260,9 +1264,12 @@ class GNCore:
     via gnx_core_forward.  `dropout = p`: the Dropout(p) ending each FeedForward (gnfeedforward.jl:27-31) is active inside a gradient call
     (gnx_core_forward_train / gnx_core_backward_train, a fresh seed per call) and the identity otherwise — Flux's automatic mode;
     `testmode(core)` / `trainmode(core)` force it as `Flux.testmode!` / `trainmode!` do.
-    `eps_mode` 0 = Flux 0.14 `normalise` (x-μ)/(σ+ε); 1 = (x-μ)/sqrt(σ²+ε)."""
+    `eps_mode` 0 = Flux 0.14 `normalise` (x-μ)/(σ+ε); 1 = (x-μ)/sqrt(σ²+ε).
+    `bf16` (also a plain attribute): lets a call on bfloat16 features (batch(..., dtype=torch.bfloat16)) run through gnx_core_forward_typed —
+    bf16 outputs, bit for bit the fp32 core on the widened inputs rounded once.  The test-mode forward only: a differentiable call or one
+    with Dropout active raises NotImplementedError.  Off (the default) a bfloat16 tensor raises TypeError; float32 features never notice it."""
 
-    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0):
+    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False):
         dims = tuple(int(d) for d in dims)
         assert any(d > 0 for d in dims)  # gncore.jl:47
         self.dims = dims
@@ -1272,6 +1279,7 @@ class GNCore:
         self.gn2 = GNGraphNorm(dims, device)
         self.eps, self.eps_mode = eps, eps_mode
         self.flags = 0
+        self.bf16 = bool(bf16)
 
     def _c(self, keep):
         p = _lib.CoreParams()
@@ -1338,6 +1346,8 @@ class GNCore:
         # and skips in test mode: gnx_core_forward_train / gnx_core_backward_train with a per-call seed, gnx_core_forward otherwise.
         x = _as_nt(x)
         assert x.ef is not None and x.nf is not None and x.gf is not None, "GNCore needs ef, nf and gf (gncore.jl:61-68)"
+        if getattr(self, "bf16", False) and _feature_dtype(x.ef, x.nf, x.gf, "GNCore") == torch.bfloat16:  # (mixed bf16 / other: TypeError)
+            return self._call_bf16(x, flags)
         g, ef, nf, gf, R = _forward_common(x, self.dims)
         plist = self._param_list()
         grad_call = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [ef, nf, gf] + plist)
@@ -1346,6 +1356,32 @@ class GNCore:
             eo, no, go = _CoreFn.apply(self, g, R, self.flags if flags is None else flags, drop, ef, nf, gf, *plist)
             return NT(g, _jl(eo), _jl(no), _jl(go))
         eo, no, go = _core_forward(self, g, R, self.flags if flags is None else flags, drop, ef, nf, gf)
+        return NT(g, _jl(eo), _jl(no), _jl(go))
+
+
+    def _call_bf16(self, x, flags):
+        """bfloat16 features with the `bf16` switch on: gnx_core_forward_typed, bf16 outputs.  Everything that is not this test-mode forward is
+        refused before any library call."""
+        if self._training((x.ef, x.nf, x.gf)):
+            raise NotImplementedError("GNCore: the backward of a bfloat16 core (a typed gnx_core_backward) is not implemented; call it under "
+                                      "torch.no_grad() with parameters that need no gradient, or with float32 features")
+        if float(self.ffwd.dropout or 0) > 0 and getattr(self, "_dropout_mode", None):
+            raise NotImplementedError("GNCore: Dropout in training mode on bfloat16 features (a typed gnx_core_forward_train) is not implemented; "
+                                      "use testmode(core) or float32 features")
+        g, ef, nf, gf, R = _forward_common(x, self.dims, None)
+        # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
+        ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+        lib = _lib.load()
+        keep = []
+        p = self._c(keep)
+        dev = g.device
+        flags = self.flags if flags is None else flags
+        eo, no, go = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
+        with torch.cuda.device(dev):
+            nbytes = lib.gnx_core_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, flags)
+            ws = g.workspace(nbytes, ("core_bf16", self.dims, R, flags))
+            check(lib.gnx_core_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(), no.data_ptr(),
+                                             go.data_ptr(), ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
         return NT(g, _jl(eo), _jl(no), _jl(go))
 
 

@@ -55,8 +55,9 @@ int32_t launch_ln1_rows(const float* x, size_t rows, int d, const gnx_layernorm&
 // rows per workgroup of the streamed two-rows-per-thread body
 static size_t core_post_s_rows_per_block() { return (size_t)512 * GNX_CORE_POST_UNITS; }
 
+// block_out: bf16 rows (x, out) with the block's output in this fp32 buffer — README ex.3's widths only (gnx_core_forward_typed's native path)
 int32_t launch_core_post(const float* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode,
-                         float* out, hipStream_t s) {
+                         float* out, hipStream_t s, const float* block_out) {
   if (rows == 0) return GNX_OK;
   ProfScope ps("k_core_post", s);
   static const int rows_env = getenv("GNX_CORE_POST_ROWS") ? atoi(getenv("GNX_CORE_POST_ROWS")) : 2;  // (A/B switch, read once)
@@ -66,18 +67,30 @@ int32_t launch_core_post(const float* x, size_t rows, int d, const gnx_layernorm
   const bool streamed = !lds_weights && M == 2;
   const size_t per_block = streamed ? core_post_s_rows_per_block() : 256 * (size_t)M;
   const dim3 grid((unsigned)((rows + per_block - 1) / per_block));
-  switch (d) {
-#define GNX_CASE(D)                                                                                                                                  \
+#define GNX_POST_CASE(D, BF)                                                                                                                           \
   case D:                                                                                                                                            \
-    if (!lds_weights && M == 2 && trans) GNX_LAUNCH((k_core_post_s<D, true>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out); \
-    else if (!lds_weights && M == 2) GNX_LAUNCH((k_core_post_s<D, false>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out); \
-    else if (M == 2) GNX_LAUNCH((k_core_post<D, 2>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out); \
-    else GNX_LAUNCH((k_core_post<D, 1>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out);             \
+    if (!lds_weights && M == 2 && trans) GNX_LAUNCH((k_core_post_s<D, true, BF>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out, bsrc); \
+    else if (!lds_weights && M == 2) GNX_LAUNCH((k_core_post_s<D, false, BF>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out, bsrc); \
+    else if (M == 2) GNX_LAUNCH((k_core_post<D, 2, BF>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out, bsrc); \
+    else GNX_LAUNCH((k_core_post<D, 1, BF>), grid, dim3(256), 0, s, x, rows, l2.gamma, l2.beta, ff.fc1, ff.fc2, eps, eps_mode, out, bsrc);             \
     break;
-    GNX_CORE_WIDTHS(GNX_CASE)
+  const float* const bsrc = block_out ? block_out : out;
+  if (block_out) {
+    switch (d) {
+      GNX_POST_CASE(3, true)
+      GNX_POST_CASE(5, true)
+      GNX_POST_CASE(10, true)
+      default: return fail(GNX_ERR_DIMS, "launch_core_post: width not instantiated for bf16 rows");
+    }
+  } else {
+    switch (d) {
+#define GNX_CASE(D) GNX_POST_CASE(D, false)
+      GNX_CORE_WIDTHS(GNX_CASE)
 #undef GNX_CASE
-    default: return fail(GNX_ERR_DIMS, "launch_core_post: width not instantiated");
+      default: return fail(GNX_ERR_DIMS, "launch_core_post: width not instantiated");
+    }
   }
+#undef GNX_POST_CASE
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
@@ -101,18 +114,21 @@ bool core_post3_applies(const size_t rows[3], const int d[3], const gnx_ffn ff[3
 // 1 = not applicable (three launches).
 // skip_edges: the edge rows are final already (k_block_wave<..., FFE> ran their FeedForward and residual): the edge job gets no workgroups
 int32_t launch_core_post3(const float* const x[3], const size_t rows[3], const int d[3], const gnx_layernorm l2[3], const gnx_ffn ff[3], float eps,
-                          int eps_mode, float* const out[3], hipStream_t s, const BlockArgs* blk, int n_rows, bool skip_edges) {
+                          int eps_mode, float* const out[3], hipStream_t s, const BlockArgs* blk, int n_rows, bool skip_edges, const float* const block_out[3]) {
   if (!core_post3_applies(rows, d, ff, blk != nullptr, s)) return blk ? fail(GNX_ERR_INVALID_ARG, "internal: deferred graph update without the combined kernel") : 1;
   PostJob j[3];
   for (int t = 0; t < 3; ++t) {
     const size_t per = t < 2 ? core_post_s_rows_per_block() : 256;
-    j[t] = PostJob{x[t], rows[t], l2[t].gamma, l2[t].beta, ff[t].fc1, ff[t].fc2, out[t], (unsigned)((rows[t] + per - 1) / per)};
+    j[t] = PostJob{x[t], rows[t], l2[t].gamma, l2[t].beta, ff[t].fc1, ff[t].fc2, out[t], (unsigned)((rows[t] + per - 1) / per), block_out ? block_out[t] : out[t]};
   }
   if (blk) j[2].blocks = (unsigned)rows[2];  // one workgroup per graph (and replica)
   if (skip_edges) j[0].blocks = 0;
   const dim3 grid(j[0].blocks + j[1].blocks + j[2].blocks);
   ProfScope ps("k_core_post", s);
-  if (d[0] == 10 && d[1] == 5 && d[2] == 3) {
+  if (block_out) {  // bf16 rows: the ahead-of-time triple with the graph update inside, the only form the native bf16 core launches
+    if (!blk || d[0] != 10 || d[1] != 5 || d[2] != 3) return fail(GNX_ERR_INVALID_ARG, "internal: no combined kernel on bf16 rows for this form");
+    GNX_LAUNCH((k_core_post3<10, 5, 3, true, true>), grid, dim3(256), 0, s, j[0], j[1], j[2], eps, eps_mode, *blk, n_rows);
+  } else if (d[0] == 10 && d[1] == 5 && d[2] == 3) {
     if (blk) GNX_LAUNCH((k_core_post3<10, 5, 3, true>), grid, dim3(256), 0, s, j[0], j[1], j[2], eps, eps_mode, *blk, n_rows);
     else GNX_LAUNCH((k_core_post3<10, 5, 3, false>), grid, dim3(256), 0, s, j[0], j[1], j[2], eps, eps_mode, BlockArgs{}, 0);
   } else {

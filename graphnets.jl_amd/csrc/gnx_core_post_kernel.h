@@ -11,14 +11,25 @@ struct gnx_dense { const float* weight; const float* bias; int act; int reserved
 
 namespace gnx {
 
+// BF16 (every body and kernel below; gnx_core_forward_typed's native path): x and out are bfloat16 rows — widened exactly on load, rounded
+// to nearest even once on store — and the block's output, an INTERMEDIATE of the core, is read as fp32 from `bsrc`, a buffer of its own
+// (the staging the block kernel wrote).  fp32 rows: the block wrote its output into `out` and it is read from there, as always (bsrc == out).
+// The pointers travel as float* (as in BlockArgs) and are read as what the launch says they are.
+template <bool BF16>
+__device__ __forceinline__ const float* feat_at(const float* p, size_t i) { return reinterpret_cast<const float*>(feat<BF16>(p) + i); }
+template <bool BF16>
+__device__ __forceinline__ float* feat_at(float* p, size_t i) { return reinterpret_cast<float*>(feat<BF16>(p) + i); }
+
 // The FeedForward's 8 D^2 weights (800 at D = 10) do not fit the ~100 scalar registers: as SGPR operands they are streamed in
 // groups, and hipcc's scheduler hoists the scalar loads until it spills (k_core_post<10> with scalar weights: 237 spilled SGPRs,
 // i.e. a v_readlane in front of most FMAs, 126 VGPRs).  Here the workgroup stages the weights in LDS once and every lane reads
 // them with UNIFORM addresses (ds_read_b128 of one address is a broadcast: no bank conflict) into a few VGPRs; M = 2 rows per
 // thread share each read, which keeps the LDS at ~half its rate (D + 4*ceil(D/4)/... reads per 8 D M FMAs).
-template <int D, int M>
-__device__ __forceinline__ void core_post_lds_body(const float* __restrict__ x, size_t rows, const float* gamma2, const float* beta2, gnx_dense fc1,
-                                                   gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out, unsigned blk, unsigned nblk) {
+template <int D, int M, bool BF16 = false>
+__device__ __forceinline__ void core_post_lds_body(const float* __restrict__ x_, size_t rows, const float* gamma2, const float* beta2, gnx_dense fc1,
+                                                   gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out_, const float* bsrc, unsigned blk, unsigned nblk) {
+  const auto* __restrict__ x = feat<BF16>(x_);
+  auto* __restrict__ out = feat<BF16>(out_);
   constexpr int H = 4 * D;
   constexpr int DP = (D + 3) / 4 * 4;  // padded row of W2 in LDS (16-B reads)
   __shared__ __attribute__((aligned(16))) float s_w1[D * H];   // W1 (4D x D column-major): element (j, k) at k*H + j
@@ -42,7 +53,8 @@ __device__ __forceinline__ void core_post_lds_body(const float* __restrict__ x, 
     row[m] = rm < rows ? rm : row0;  // clamped: a lane without an m-th row recomputes its first one (its store is skipped)
     float blk[D];
     load_row<D>(x + row[m] * D, z[m]);
-    load_row<D>(out + row[m] * D, blk);  // block(gn1(x)) written by the block forward
+    if constexpr (BF16) load_row<D>(bsrc + row[m] * D, blk);  // block(gn1(x)) written by the block forward: fp32 staging
+    else load_row<D>(out + row[m] * D, blk);                  // ... into out
 #pragma unroll
     for (int k = 0; k < D; ++k) rs[m][k] = z[m][k] + blk[k];  // the two residual terms (gncore.jl:56-59)
     normalise<D>(z[m], eps, eps_mode);
@@ -98,10 +110,10 @@ __device__ __forceinline__ void core_post_lds_body(const float* __restrict__ x, 
 }
 
 
-template <int D, int M>
+template <int D, int M, bool BF16 = false>
 __global__ __launch_bounds__(256) void k_core_post(const float* __restrict__ x, size_t rows, const float* gamma2, const float* beta2,
-                                                   gnx_dense fc1, gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out) {
-  core_post_lds_body<D, M>(x, rows, gamma2, beta2, fc1, fc2, eps, eps_mode, out, blockIdx.x, gridDim.x);
+                                                   gnx_dense fc1, gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out, const float* bsrc) {
+  core_post_lds_body<D, M, BF16>(x, rows, gamma2, beta2, fc1, fc2, eps, eps_mode, out, bsrc, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -114,9 +126,11 @@ __global__ __launch_bounds__(256) void k_core_post(const float* __restrict__ x, 
 // take the weight as their SGPR operand.  No LDS, no workgroup barrier, 4*D live weight registers.
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (CorePostStream — the streamed FeedForward of two rows held as register pairs — lives in gnx_wave_kernel.h: k_block_wave<..., FFE> runs it in its edge lanes too)
-template <int D, bool TRANS>
-__device__ __forceinline__ void core_post_s_body(const float* __restrict__ x, size_t rows, const float* gamma2, const float* beta2, gnx_dense fc1,
-                                                 gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out, unsigned blk, unsigned nblk) {
+template <int D, bool TRANS, bool BF16 = false>
+__device__ __forceinline__ void core_post_s_body(const float* __restrict__ x_, size_t rows, const float* gamma2, const float* beta2, gnx_dense fc1,
+                                                 gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out_, const float* bsrc, unsigned blk, unsigned nblk) {
+  const auto* __restrict__ x = feat<BF16>(x_);
+  auto* __restrict__ out = feat<BF16>(out_);
   // A thread walks GNX_CORE_POST_UNITS units of two rows (rows row0 + m*stride, m = 2u, 2u+1).  With more than one unit, while a unit's FMAs
   // run the lines of the thread's NEXT unit are pulled into the L2 by one dword load per row and array whose destination is never read
   // (kept reserved until the next unit's own loads have returned: loads complete in order), so that the next unit starts from the L2
@@ -143,7 +157,8 @@ __device__ __forceinline__ void core_post_s_body(const float* __restrict__ x, si
       const size_t rm = rbase + m * stride;
       row[m] = rm < rows ? rm : rbase;  // clamped: a lane without a second row recomputes its first one (its store is skipped)
       load_row<D>(x + row[m] * D, zr[m]);
-      load_row<D>(out + row[m] * D, blkr[m]);  // block(gn1(x)) written by the block forward
+      if constexpr (BF16) load_row<D>(bsrc + row[m] * D, blkr[m]);  // block(gn1(x)) written by the block forward: fp32 staging
+      else load_row<D>(out + row[m] * D, blkr[m]);                  // ... into out
     }
 #pragma unroll
     for (int m = 0; m < M; ++m) {
@@ -166,7 +181,7 @@ __device__ __forceinline__ void core_post_s_body(const float* __restrict__ x, si
         const size_t rn = rbase + (size_t)(M + m) * stride;
         if (rn < rows) {
           asm volatile("global_load_dword %0, %1, off" : "+v"(touched) : "v"(x + rn * D));
-          asm volatile("global_load_dword %0, %1, off" : "+v"(touched) : "v"(out + rn * D));
+          asm volatile("global_load_dword %0, %1, off" : "+v"(touched) : "v"(BF16 ? bsrc + rn * D : reinterpret_cast<const float*>(out + rn * D)));
         }
       }
     }
@@ -188,10 +203,10 @@ __device__ __forceinline__ void core_post_s_body(const float* __restrict__ x, si
   }
   if constexpr (U > 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(touched));  // the touch loads' destination stays reserved until they have landed
 }
-template <int D, bool TRANS>
+template <int D, bool TRANS, bool BF16 = false>
 __global__ __launch_bounds__(256) void k_core_post_s(const float* __restrict__ x, size_t rows, const float* gamma2, const float* beta2,
-                                                     gnx_dense fc1, gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out) {
-  core_post_s_body<D, TRANS>(x, rows, gamma2, beta2, fc1, fc2, eps, eps_mode, out, blockIdx.x, gridDim.x);
+                                                     gnx_dense fc1, gnx_dense fc2, float eps, int eps_mode, float* __restrict__ out, const float* bsrc) {
+  core_post_s_body<D, TRANS, BF16>(x, rows, gamma2, beta2, fc1, fc2, eps, eps_mode, out, bsrc, blockIdx.x, gridDim.x);
 }
 
 // The three entities of a core in ONE launch (workgroup ranges: edges | nodes | graphs): the node and graph rows ride in the shadow of
@@ -199,18 +214,20 @@ __global__ __launch_bounds__(256) void k_core_post_s(const float* __restrict__ x
 // nodes: the streamed two-rows-per-thread body; graphs (few rows): the LDS body, one row per thread.
 struct PostJob {
   const float* x; size_t rows; const float* gamma; const float* beta; gnx_dense fc1, fc2; float* out; unsigned blocks;
+  const float* bsrc;  // the block's output rows of this entity: out itself for fp32 rows, the fp32 staging for bf16 rows
 };
 // GU: the block's graph update (graph_update_rows over the partial-sum rows k_block_wave left) runs HERE, in the graph job's workgroups
 // (one per graph), followed by that graph's FeedForward + residual — the block is launched without its k_graph_t, whose 6.5 us then
-// hide behind the edge rows.
-template <int D0, int D1, int D2, bool GU>
+// hide behind the edge rows.  With BF16 the update reads gf as bf16 and writes gf' as fp32 into the staging (a.gf_out == g.bsrc there), the
+// FeedForward reads it back from the staging and stores the core's graph row as bf16.
+template <int D0, int D1, int D2, bool GU, bool BF16 = false>
 __global__ __launch_bounds__(256) void k_core_post3(PostJob e, PostJob n, PostJob g, float eps, int eps_mode, BlockArgs a, int n_rows) {
   // workgroup ranges: graphs | edges | nodes — the graph job (a serial chain of a few microseconds) is dispatched FIRST, so that it runs
   // beside the edge rows instead of behind them
   const unsigned b = blockIdx.x;
-  if (b >= g.blocks && b < g.blocks + e.blocks) core_post_s_body<D0, false>(e.x, e.rows, e.gamma, e.beta, e.fc1, e.fc2, eps, eps_mode, e.out, b - g.blocks, e.blocks);
-  else if (b >= g.blocks) core_post_s_body<D1, false>(n.x, n.rows, n.gamma, n.beta, n.fc1, n.fc2, eps, eps_mode, n.out, b - g.blocks - e.blocks, n.blocks);
-  else if constexpr (!GU) core_post_lds_body<D2, 1>(g.x, g.rows, g.gamma, g.beta, g.fc1, g.fc2, eps, eps_mode, g.out, b, g.blocks);
+  if (b >= g.blocks && b < g.blocks + e.blocks) core_post_s_body<D0, false, BF16>(e.x, e.rows, e.gamma, e.beta, e.fc1, e.fc2, eps, eps_mode, e.out, e.bsrc, b - g.blocks, e.blocks);
+  else if (b >= g.blocks) core_post_s_body<D1, false, BF16>(n.x, n.rows, n.gamma, n.beta, n.fc1, n.fc2, eps, eps_mode, n.out, n.bsrc, b - g.blocks - e.blocks, n.blocks);
+  else if constexpr (!GU) core_post_lds_body<D2, 1, BF16>(g.x, g.rows, g.gamma, g.beta, g.fc1, g.fc2, eps, eps_mode, g.out, g.bsrc, b, g.blocks);
   else {
     constexpr int C = D0 + D1, CP = (C + 3) / 4 * 4;
     __shared__ float s_g[graph_update_lds_floats(C, D2, D2, 256)];
@@ -219,10 +236,10 @@ __global__ __launch_bounds__(256) void k_core_post3(PostJob e, PostJob n, PostJo
     const size_t r = gb / (unsigned)a.G;
     const bool oneg = a.G == 1;  // one row per workgroup of k_block_wave, else one per wave tile (gnx_narrow.hip: partial_rows)
     const int t0 = oneg ? 0 : a.wtile_off[gi], t1 = oneg ? (a.n_wtiles + 3) / 4 : a.wtile_off[gi + 1];
-    graph_update_rows<C, false, 16>(a, a.gf, a.gf_out, a.partials + r * (size_t)n_rows * CP, gi, r, t0, t1, (int)threadIdx.x, 256, s_g);
+    graph_update_rows<C, false, 16, BF16, false>(a, a.gf, a.gf_out, a.partials + r * (size_t)n_rows * CP, gi, r, t0, t1, (int)threadIdx.x, 256, s_g);
     __syncthreads();  // gf' of this graph is in memory (written by this workgroup): the FeedForward below reads it as the block's output
     const size_t row = r * (size_t)a.G + gi;
-    core_post_lds_body<D2, 1>(g.x + row * D2, 1, g.gamma, g.beta, g.fc1, g.fc2, eps, eps_mode, g.out + row * D2, 0, 1);
+    core_post_lds_body<D2, 1, BF16>(feat_at<BF16>(g.x, row * D2), 1, g.gamma, g.beta, g.fc1, g.fc2, eps, eps_mode, feat_at<BF16>(g.out, row * D2), g.bsrc + row * D2, 0, 1);
   }
 }
 

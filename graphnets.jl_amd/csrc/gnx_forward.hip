@@ -249,6 +249,14 @@ static TypedWs typed_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t 
   return w;
 }
 
+// the six feature buffers of a bf16 call (gnx_block_forward_typed, gnx_core_forward_typed): rows of odd width are then 2-byte aligned, which
+// is all the kernels assume
+static int32_t check_bf16_aligned(const void* const bufs[6]) {
+  for (int i = 0; i < 6; ++i)
+    if (((uintptr_t)bufs[i] & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  return GNX_OK;
+}
+
 // side stream + fork / join events of the handle (see gnx_internal.h); failure just leaves the core on one stream
 static void ensure_aux(const gnx_graphs* h) {
   std::call_once(h->aux_once, [h]() {
@@ -346,8 +354,7 @@ int32_t gnx_block_forward_typed(const gnx_graphs* h, const gnx_block_params* p, 
   int32_t rc = check_call(call);
   if (rc) return rc;
   const void* bufs[6] = {ef, nf, gf, ef_out, nf_out, gf_out};
-  for (const void* b : bufs)
-    if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  if ((rc = check_bf16_aligned(bufs))) return rc;
   const bool native = typed_native(h, p, flags, s);
   const TypedWs w = typed_ws(h, p, R, native);
   if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_typed_workspace_bytes()");
@@ -621,6 +628,9 @@ int32_t gnx_block_graph_update(const gnx_graphs* h, const gnx_block_params* p, c
   return graph_update(h, p, GNX_ELEM_F32, gnx_pending_update{ws, ws_bytes, gf, gf_out}, R, flags, (hipStream_t)stream);
 }
 
+// partial-sum rows per replica of the fused narrow block (gnx_narrow_launch.h: partial_rows)
+static int partial_rows_of(const gnx_graphs* h) { return (int)(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->n_wtiles()); }
+
 // FeedForward width from which the two Dense layers run on the matrix cores (hidden activations staged in HBM)
 static bool ffn_on_mfma(int d) { return d >= 32; }
 
@@ -637,6 +647,42 @@ static void core_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, si
   off[6] = o; o += align_up(hidden, 256);
   off[7] = o;
   *total = o + block_ws(h, &p->block, R).total;
+}
+
+// ---- validation of a core forward (gnx_core_forward, gnx_core_forward_typed), in the order the fp32 entry has always reported it ----
+// GNFeedForward / GNGraphNorm need all three widths > 0 and graphnetadd needs all three present
+// (gnfeedforward.jl:18, gngraphnorm.jl:10, gncore.jl:61-68); the block maps dims => dims (gncore.jl:49).
+static int32_t check_core_dims(const gnx_block_params& b) {
+  if (b.de <= 0 || b.dn <= 0 || b.dg <= 0) return fail(GNX_ERR_DIMS, "GNCore needs all(dims .> 0) (gnfeedforward.jl:18)");
+  if (b.oe != b.de || b.on != b.dn || b.og != b.dg) return fail(GNX_ERR_DIMS, "GNCore's block must map dims => dims (gncore.jl:49)");
+  return GNX_OK;
+}
+// b: the core's block (p->block with the core's prepared planes)
+static int32_t check_core(const gnx_graphs* h, const gnx_core_params* p, const gnx_block_params& b, int64_t R, const void* ef, const void* nf, const void* gf,
+                          const void* ef_out, const void* nf_out, const void* gf_out, uint32_t flags) {
+  int32_t rc = check_core_dims(b);
+  if (rc) return rc;
+  rc = check_block(h, &b, R);
+  if (rc) return rc;
+  if (((!ef || !ef_out) && h->E > 0) || !nf || !gf || !nf_out || !gf_out) return fail(GNX_ERR_INVALID_ARG, "GNCore needs ef, nf, gf and all outputs");
+  for (int t = 0; t < 3; ++t) {
+    if (!p->ln1[t].gamma || !p->ln1[t].beta || !p->ln2[t].gamma || !p->ln2[t].beta) return fail(GNX_ERR_INVALID_ARG, "LayerNorm parameter is NULL");
+    if (!p->ff[t].fc1.weight || !p->ff[t].fc2.weight) return fail(GNX_ERR_INVALID_ARG, "FeedForward weight is NULL");
+  }
+  if (p->eps_mode != 0 && p->eps_mode != 1) return fail(GNX_ERR_INVALID_ARG, "eps_mode must be 0 or 1");
+  const int dd[3] = {b.de, b.dn, b.dg};
+  for (int t = 0; t < 3; ++t) {
+    const bool generic = !ffn_on_mfma(dd[t]) || (flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA));
+    if (generic && (size_t)dd[t] * 5 * 4 * sizeof(float) > 64 * 1024)
+      return fail(GNX_ERR_DIMS, "GNCore width too large for the generic FFN kernel (80*d bytes of LDS)");
+  }
+  return GNX_OK;
+}
+// the workspace of a core call against `total`, the size its query (`query`: the name for the message) returns
+static int32_t check_core_ws(const void* ws, size_t ws_bytes, size_t total, const char* query) {
+  if (!ws || ws_bytes < total) return fail(GNX_ERR_WORKSPACE, query);
+  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  return GNX_OK;
 }
 
 size_t gnx_core_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
@@ -663,30 +709,11 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
   gnx_block_params b = p->block;
   b.prepared = p->prepared;  // (the core's object holds its block's planes too; block.prepared is ignored)
   PreparedScope prepared(p->prepared);
-  // GNFeedForward / GNGraphNorm need all three widths > 0 and graphnetadd needs all three present
-  // (gnfeedforward.jl:18, gngraphnorm.jl:10, gncore.jl:61-68); the block maps dims => dims (gncore.jl:49).
-  if (b.de <= 0 || b.dn <= 0 || b.dg <= 0) return fail(GNX_ERR_DIMS, "GNCore needs all(dims .> 0) (gnfeedforward.jl:18)");
-  if (b.oe != b.de || b.on != b.dn || b.og != b.dg) return fail(GNX_ERR_DIMS, "GNCore's block must map dims => dims (gncore.jl:49)");
-  int32_t rc = check_block(h, &b, R);
+  int32_t rc = check_core(h, p, b, R, ef, nf, gf, ef_out, nf_out, gf_out, flags);
   if (rc) return rc;
-  if (((!ef || !ef_out) && h->E > 0) || !nf || !gf || !nf_out || !gf_out) return fail(GNX_ERR_INVALID_ARG, "GNCore needs ef, nf, gf and all outputs");
-  for (int t = 0; t < 3; ++t) {
-    if (!p->ln1[t].gamma || !p->ln1[t].beta || !p->ln2[t].gamma || !p->ln2[t].beta) return fail(GNX_ERR_INVALID_ARG, "LayerNorm parameter is NULL");
-    if (!p->ff[t].fc1.weight || !p->ff[t].fc2.weight) return fail(GNX_ERR_INVALID_ARG, "FeedForward weight is NULL");
-  }
-  if (p->eps_mode != 0 && p->eps_mode != 1) return fail(GNX_ERR_INVALID_ARG, "eps_mode must be 0 or 1");
-  {
-    const int dd[3] = {b.de, b.dn, b.dg};
-    for (int t = 0; t < 3; ++t) {
-      const bool generic = !ffn_on_mfma(dd[t]) || (flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA));
-      if (generic && (size_t)dd[t] * 5 * 4 * sizeof(float) > 64 * 1024)
-        return fail(GNX_ERR_DIMS, "GNCore width too large for the generic FFN kernel (80*d bytes of LDS)");
-    }
-  }
   size_t off[8], total;
   core_ws(h, p, R, off, &total);
-  if (!ws || ws_bytes < total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_core_workspace_bytes()");
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  if ((rc = check_core_ws(ws, ws_bytes, total, "workspace missing or smaller than gnx_core_workspace_bytes()"))) return rc;
   char* base = static_cast<char*>(ws);
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
   const int d[3] = {b.de, b.dn, b.dg};
@@ -846,7 +873,7 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
   }
   float* hidden = reinterpret_cast<float*>(base + off[6]);
   if (all_narrow) {  // the three entities' FeedForward + residual in one launch when the width triple has the combined kernel
-    const int n_rows = (int)(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->n_wtiles());  // partial-sum rows of the fused narrow block (gnx_narrow.hip)
+    const int n_rows = partial_rows_of(h);
     rc = launch_core_post3(x, rows, d, p->ln2, p->ff, p->eps, p->eps_mode, out, s, defer_gu ? &narrow.args : nullptr, n_rows, edge_ff_done);
     if (rc != 1) return rc;
     if (edge_ff_done) return fail(GNX_ERR_INVALID_ARG, "internal: the edge FeedForward ran in the block kernel but the one-launch post kernel declined");
@@ -879,6 +906,75 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
   return GNX_OK;
 }
 
+// ---- bfloat16 features (gnx_core_forward_typed) ----
+// Does the core run natively on bf16 rows under the call's forms (FormScope open)?  Where the fp32 core takes the fused LayerNorm-on-load
+// block kernel of the ahead-of-time set: README ex.3's widths at the default wave-tile size, a batch with edges.  Everything else — the
+// matrix-core widths, other narrow triples (run-time specialised ones too), GNX_FLAG_FORCE_GENERIC, GNX_FLAG_NO_JIT — converts around
+// gnx_core_forward.
+static bool core_typed_native(const gnx_graphs* h, const gnx_core_params* p, uint32_t flags) {
+  if ((flags & GNX_FLAG_FORCE_GENERIC) || form(GNX_FLAG_NO_JIT)) return false;
+  return p->block.og == 3 && narrow_bf16_ln_aot(h, block_probe(h, &p->block));
+}
+
+// workspace of a bf16 core call: gnx_core_forward's, then (fallback only) fp32 copies of the six tensors, each carve 256-B aligned.  The native
+// path stages the block's three outputs in fp32 too, but in the gn1 regions of the fp32 layout (core_ws: off[0], off[2], off[4] — exactly
+// the three tensors' sizes), which the LayerNorm-on-load form never writes: no byte beyond the fp32 core's workspace.
+struct CoreTypedWs {
+  size_t base, off[6], n[6], total;
+};
+static CoreTypedWs core_typed_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool native) {
+  CoreTypedWs w{};
+  size_t o8[8];
+  core_ws(h, p, R, o8, &w.base);
+  const int64_t rows[3] = {h->E, h->N, h->G};
+  const int d[3] = {p->block.de, p->block.dn, p->block.dg};
+  size_t o = align_up(w.base, 256);
+  for (int i = 0; i < 6; ++i) {
+    w.n[i] = native ? 0 : (size_t)R * (size_t)rows[i % 3] * (size_t)d[i % 3];
+    w.off[i] = o;
+    o += align_up(sizeof(float) * w.n[i], 256);
+  }
+  w.total = native ? w.base : o;
+  return w;
+}
+
+// The native path (validated call, core_typed_native): the fp32 narrow core's launches on bf16 rows.  The block normalises the bf16 rows as it
+// loads them and hands ef' / nf' / gf' on in fp32 (st[]: intermediates of the core never pass through bf16); the post kernels read x as bf16,
+// the block's rows from st[], and store the core's rows rounded once.  One-launch form (core_post3_applies): the block without its graph
+// update — with the edge FeedForward in its edge lanes where block_narrow_ffe_applies, which then stores the core's edge rows itself and
+// no edge-sized staging is written — then k_core_post3 with the graph update inside; else the block whole, then k_core_post per entity.
+static int32_t core_forward_bf16_native(const gnx_graphs* h, const gnx_core_params* p, const gnx_block_params& b, const void* const x[3], int64_t R, void* const out[3],
+                                        void* ws, size_t ws_bytes, uint32_t flags, hipStream_t s) {
+  size_t off[8], total;
+  core_ws(h, p, R, off, &total);
+  char* base = static_cast<char*>(ws);
+  float* st[3];
+  for (int t = 0; t < 3; ++t) st[t] = reinterpret_cast<float*>(base + off[2 * t]);
+  const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
+  const int d[3] = {b.de, b.dn, b.dg};
+  const bool post3 = core_post3_applies(rows, d, p->ff, true, s);
+  const int phase = post3 ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL;
+  Prepared q(BlockCall{h, &b, GNX_ELEM_BF16, x[0], x[1], x[2], R, st[0], st[1], st[2], base + off[7], ws_bytes - off[7], flags, s, phase});
+  if (q.rc) return q.rc;
+  BlockArgs& a = q.a;
+  for (int t = 0; t < 3; ++t) { a.ln_g[t] = p->ln1[t].gamma; a.ln_b[t] = p->ln1[t].beta; }
+  a.ln_eps = p->eps; a.ln_mode = p->eps_mode;
+  const bool ffe = post3 && block_narrow_ffe_applies(h, a, p->ff[0].fc1.act, p->ff[0].fc2.act);
+  if (ffe) {
+    set_edge_ffn(a, p->ff[0], p->ln2[0]);
+    a.ef_out = static_cast<float*>(out[0]);  // (bf16 rows in a float* field, as the inputs: the edge lanes store the core's edge rows)
+  }
+  int32_t rc = launch_block_narrow(h, a, R, s, phase, true);
+  if (rc) return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: the bf16 core's block declined the form it had accepted") : rc;
+  const float* xf[3];
+  float* of[3];
+  for (int t = 0; t < 3; ++t) { xf[t] = static_cast<const float*>(x[t]); of[t] = static_cast<float*>(out[t]); }
+  if (post3) return launch_core_post3(xf, rows, d, p->ln2, p->ff, p->eps, p->eps_mode, of, s, &a, partial_rows_of(h), ffe, st);
+  for (int t = 0; t < 3; ++t)
+    if ((rc = launch_core_post(xf[t], rows[t], d[t], p->ln2[t], p->ff[t], p->eps, p->eps_mode, of[t], s, st[t]))) return rc;
+  return GNX_OK;
+}
+
 static int32_t pad_impl(const gnx_graphs* h, int32_t kind, bool pad, const float* src, int32_t d, int64_t R, float* dst, void* stream) {
   if (!h) return fail(GNX_ERR_INVALID_ARG, "NULL argument");
   if (kind != 0 && kind != 1) return fail(GNX_ERR_INVALID_ARG, "kind must be 0 (edges) or 1 (nodes)");
@@ -888,6 +984,59 @@ static int32_t pad_impl(const gnx_graphs* h, int32_t kind, bool pad, const float
   if (d <= 0 || R <= 0) return fail(GNX_ERR_INVALID_ARG, "d and n_replicas must be >= 1");
   if (R > 1 && h->G != 1) return fail(GNX_ERR_INVALID_ARG, "n_replicas > 1 needs a single-graph handle");
   return launch_pad(h, kind, pad, src, d, R, dst, (hipStream_t)stream);
+}
+
+size_t gnx_core_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem, uint32_t flags) {
+  if (elem == GNX_ELEM_F32) return gnx_core_workspace_bytes(h, p, R);
+  if (elem != GNX_ELEM_BF16 || !h || !p || R <= 0 || (flags & GNX_FLAG_DEFER_GRAPH_UPDATE)) return 0;
+  const size_t base = gnx_core_workspace_bytes(h, p, R);  // side streams, the matrix-core tables, the run-time specialisations of the fp32 core the fallback runs
+  FormScope forms(flags);
+  if (check_core_dims(p->block) != GNX_OK || check_block(h, &p->block, R) != GNX_OK) return base;  // (the forward reports it)
+  const bool native = core_typed_native(h, p, flags);
+  if (!native) (void)gnx_block_workspace_bytes(h, &p->block, R);  // ... and of its block
+  return core_typed_ws(h, p, R, native).total;
+}
+
+int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf, int64_t R,
+                               void* ef_out, void* nf_out, void* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  if (elem == GNX_ELEM_F32)
+    return gnx_core_forward(h, p, static_cast<const float*>(ef), static_cast<const float*>(nf), static_cast<const float*>(gf), R, static_cast<float*>(ef_out),
+                            static_cast<float*>(nf_out), static_cast<float*>(gf_out), ws, ws_bytes, flags, stream);
+  if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (flags & GNX_FLAG_DEFER_GRAPH_UPDATE) return fail(GNX_ERR_INVALID_ARG, "GNX_FLAG_DEFER_GRAPH_UPDATE is not supported with bf16 features");
+  // what needs no handle comes first: every refusal below happens before any GPU work
+  if (!p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  const void* bufs[6] = {ef, nf, gf, ef_out, nf_out, gf_out};
+  int32_t rc = check_bf16_aligned(bufs);
+  if (rc) return rc;
+  if ((rc = check_core_dims(p->block))) return rc;
+  if (!h) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  const hipStream_t s = (hipStream_t)stream;
+  FormScope forms(flags);
+  gnx_block_params b = p->block;
+  b.prepared = p->prepared;
+  if ((rc = check_core(h, p, b, R, ef, nf, gf, ef_out, nf_out, gf_out, flags))) return rc;
+  const bool native = core_typed_native(h, p, flags);
+  const CoreTypedWs w = core_typed_ws(h, p, R, native);
+  if ((rc = check_core_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_core_typed_workspace_bytes()"))) return rc;
+  if (native) {
+    DeviceTurn turn(s, false);  // (narrow widths: no matrix instruction)
+    PreparedScope prepared(p->prepared);
+    const void* const x[3] = {ef, nf, gf};
+    void* const out[3] = {ef_out, nf_out, gf_out};
+    return core_forward_bf16_native(h, p, b, x, R, out, ws, w.base, flags, s);
+  }
+  // every other path: widen into the workspace, the fp32 core (its own dispatch, DeviceTurn included), round the outputs
+  float* st[6];
+  for (int i = 0; i < 6; ++i) st[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + w.off[i]);
+  for (int i = 0; i < 3; ++i)
+    if (w.n[i] > 0 && (rc = launch_bf16_widen(bufs[i], w.n[i], st[i], s)) != GNX_OK) return rc;
+  // (a batch without edges: its empty edge buffers may be NULL, for the fp32 core too)
+  rc = gnx_core_forward(h, p, w.n[0] ? st[0] : nullptr, st[1], st[2], R, w.n[3] ? st[3] : nullptr, st[4], st[5], ws, w.base, flags, stream);
+  if (rc) return rc;
+  for (int i = 3; i < 6; ++i)
+    if (w.n[i] > 0 && (rc = launch_bf16_round(st[i], w.n[i], const_cast<void*>(bufs[i]), s)) != GNX_OK) return rc;
+  return GNX_OK;
 }
 
 int32_t gnx_row_stats(const float* x, int64_t rows, int32_t d, float eps, int32_t eps_mode, float* stats, void* stream) {

@@ -46,6 +46,8 @@ int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int
 bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a);
 int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
 int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
+bool narrow_bf16_ln_aot(const gnx_graphs* h, const BlockArgs& a);
+int32_t launch_ln_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
 bool block_narrow_run_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16);
 bool narrow_bf16_run(const gnx_graphs* h, const BlockArgs& a);
 int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16);
@@ -58,9 +60,12 @@ int32_t jit_get_core_post3(int d0, int d1, int d2, hipStream_t s, hipFunction_t*
 bool core_narrow_width(int d);
 int32_t launch_ln1_rows(const float* x, size_t rows, int d, const gnx_layernorm& l1, float eps, int eps_mode, float* y, hipStream_t s);
 bool core_post3_applies(const size_t rows[3], const int d[3], const gnx_ffn ff[3], bool deferred, hipStream_t s);
+// block_out (bf16 rows only; else nullptr): x and out are bf16 rows and the block's outputs are read from these fp32 buffers instead of from out
 int32_t launch_core_post3(const float* const x[3], const size_t rows[3], const int d[3], const gnx_layernorm l2[3], const gnx_ffn ff[3], float eps,
-                          int eps_mode, float* const out[3], hipStream_t s, const BlockArgs* blk, int n_rows, bool skip_edges = false);
-int32_t launch_core_post(const float* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode, float* out, hipStream_t s);
+                          int eps_mode, float* const out[3], hipStream_t s, const BlockArgs* blk, int n_rows, bool skip_edges = false,
+                          const float* const block_out[3] = nullptr);
+int32_t launch_core_post(const float* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode, float* out, hipStream_t s,
+                         const float* block_out = nullptr);
 
 // ---- gnx_wide.hip: the matrix-core block and row-wise Dense ----
 int32_t launch_block_wide(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);

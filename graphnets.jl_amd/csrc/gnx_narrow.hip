@@ -207,10 +207,15 @@ static NarrowRoute narrow_route(const gnx_graphs* h, const BlockArgs& a, hipStre
 bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16) { return narrow_route(h, a, s, bf16) != NR_NONE; }
 
 // 1: no fused kernel takes these widths.  bf16 features (gnx_block_forward_typed): the native kernels (on 1 the caller converts around the
-// fp32 forward); no LayerNorm on load, no deferred form; phase 2 alone is the flush of a chained bf16 step (ahead-of-time widths only).
+// fp32 forward); LayerNorm on load only as the block of a bf16 core (launch_ln_bf16: bf16 rows in, fp32 out); phase 2 alone is the flush of
+// a chained bf16 step (ahead-of-time widths only).
 int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, bool bf16) {
   if (a.n_wtiles == 0 || a.E == 0) return 1;
   if (wants_ln(a)) {  // only reached after block_narrow_ready(): a miss here would silently drop the LayerNorm
+    if (bf16) {       // the block of a bf16 core (gnx_core_forward_typed's native path: ahead-of-time widths only): gnx_narrow_bf16.hip
+      const int32_t rc = launch_ln_bf16(h, a, R, s, phase);
+      return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: LayerNorm-on-load on bf16 rows for a width set without that kernel") : rc;
+    }
     if (a.ffe_w1) {   // (set by gnx_core_forward only after block_narrow_ffe_applies())
       if (!ln_aot(h, a)) return fail(GNX_ERR_INVALID_ARG, "internal: FeedForward-in-the-edge-lanes requested for a width set without that kernel");
       return h->G == 1 ? launch_wave_g<10, 5, 3, 10, 5, 2, true, true, true>(h, a, R, s, phase) : launch_wave_g<10, 5, 3, 10, 5, 2, true, false, true>(h, a, R, s, phase);

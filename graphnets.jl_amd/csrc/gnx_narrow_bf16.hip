@@ -1,6 +1,7 @@
 // The fused narrow kernels with bfloat16 feature rows (k_block_wave<..., BF16 = true>, its chained form k_block_wave<..., CHAIN, BF16>,
 // k_graph_t<C, ONEG, true>, the run form k_block_wave_run / k_graph_run of several steps in one launch) for the ahead-of-time width sets; gnx_narrow.hip routes gnx_block_forward_typed and the bf16 steps of
-// gnx_block_forward_steps_typed here, every other narrow width set is specialised at run time (gnx_jit.cpp).
+// gnx_block_forward_steps_typed here, every other narrow width set is specialised at run time (gnx_jit.cpp).  Also the block of a bf16
+// GNCore at README ex.3's widths (k_block_wave<..., LN, ..., BF16>, k_block_wave_ffe<..., BF16>: bf16 rows in, fp32 intermediates out).
 // A translation unit of its own because build.py compiles it without the SLP vectoriser (-fno-slp-vectorize; gnx_jit.cpp passes the same
 // option for a bf16 key): with it, every widened value feeds a v_pk_fma_f32 as the low half of a register pair of its own, and the README
 // ex.1 kernel needs 70 instead of 58 VGPRs — 7 instead of 8 waves per SIMD.  Scalar FMAs compute the same bits.
@@ -49,6 +50,22 @@ int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, 
   GNX_NARROW_DIMS_BF16(GNX_CASE)
 #undef GNX_CASE
   return 1;
+}
+
+// ---- the block of a bf16 GNCore (gnx_core_forward_typed): LayerNorm on load of bf16 rows, fp32 out ----
+// README ex.3's core widths at the default wave-tile size: the set gnx_narrow.hip's ln_aot has ahead of time for fp32 rows.
+bool narrow_bf16_ln_aot(const gnx_graphs* h, const BlockArgs& a) {
+  return a.n_wtiles > 0 && a.E > 0 && a.de == 10 && a.dn == 5 && a.dg == 3 && a.oe == 10 && a.on == 5 && h->wtile_e_cap == 128;
+}
+// gn1 applied to the bf16 rows as they are loaded; the block's outputs are the core's intermediates and leave as fp32 (a.nf_out, a.gf_out and —
+// without the FeedForward in the edge lanes — a.ef_out are fp32 staging).  a.ffe_w1 set: the edge lanes finish the core's edge rows and
+// store them, rounded once, as bf16 (a.ef_out is then the caller's).  1: not these widths.
+int32_t launch_ln_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+  if (!narrow_bf16_ln_aot(h, a)) return 1;
+  if (a.ffe_w1)
+    return h->G == 1 ? launch_wave_g<10, 5, 3, 10, 5, 2, true, true, true, false, true>(h, a, R, s, phase)
+                     : launch_wave_g<10, 5, 3, 10, 5, 2, true, false, true, false, true>(h, a, R, s, phase);
+  return launch_wave_t<10, 5, 3, 10, 5, 2, true, true>(h, a, R, s, phase);
 }
 
 // A run of steps in one launch (gnx_narrow.hip: launch_block_narrow_run) on bf16 rows.  (DE, DN, DG, OE, ON, SEVERAL): SEVERAL — the set

@@ -17,6 +17,7 @@ static int graph_update_threads(const gnx_graphs* h) {
   return graph_update_threads_for_rows(h->G == 1 ? (h->n_wtiles() + 3) / 4 : h->max_wtiles_per_graph);
 }
 
+// LN with BF16 (gnx_wave_kernel.h: OUT32): bf16 rows in, the block's own outputs — ef' / nf' / gf' — out as fp32 (the block of a bf16 core)
 template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool FFE = false, bool CHAIN = false, bool BF16 = false>
 static int32_t launch_wave_g(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
   constexpr int C = OE + ON;
@@ -34,7 +35,7 @@ static int32_t launch_wave_g(const gnx_graphs* h, const BlockArgs& a, int64_t R,
       (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_wave_dbg), &d_dbg, sizeof(d_dbg), 0, hipMemcpyHostToDevice, s);
     }
 #endif
-    if constexpr (FFE) GNX_LAUNCH((k_block_wave_ffe<DE, DN, DG, OE, ON, EPT, ONEG>), dim3(grid, (unsigned)R), dim3(kThreads), 0, s, a, n_rows);
+    if constexpr (FFE) GNX_LAUNCH((k_block_wave_ffe<DE, DN, DG, OE, ON, EPT, ONEG, BF16>), dim3(grid, (unsigned)R), dim3(kThreads), 0, s, a, n_rows);
     else GNX_LAUNCH((k_block_wave<DE, DN, DG, OE, ON, EPT, LN, ONEG, false, false, CHAIN, BF16>), dim3(grid, (unsigned)R), dim3(kThreads), 0, s, a, n_rows);
     GNX_HIP(hipGetLastError());
 #ifdef GNX_WAVE_STAMPS_BUILD
@@ -51,7 +52,7 @@ static int32_t launch_wave_g(const gnx_graphs* h, const BlockArgs& a, int64_t R,
       const int threads = graph_update_threads(h);
       const size_t lds = sizeof(float) * (size_t)graph_update_lds_floats(C, a.dg, a.og, threads);
       ProfScope ps("k_graph_t", s);
-      GNX_LAUNCH((k_graph_t<C, ONEG, BF16>), dim3((unsigned)a.G, (unsigned)R), dim3(threads), lds, s, a, n_rows);
+      GNX_LAUNCH((k_graph_t<C, ONEG, BF16, BF16 && !LN>), dim3((unsigned)a.G, (unsigned)R), dim3(threads), lds, s, a, n_rows);
       GNX_HIP(hipGetLastError());
     }
   }

@@ -572,7 +572,8 @@ __device__ __forceinline__ void store_partial_row(float mine, float* row, int la
 // gf / gf_out: the graph rows this update reads and writes (a.gf / a.gf_out; the CHAIN front passes the previous call's a.prev_gf / a.prev_gf_out).
 // vthr (a multiple of 64; 0: nthr): the sums come out as a launch of vthr threads would form them — the bits k_graph_t gives with that many
 // threads.  Thread tid plays the threads tid, tid + nthr, ... below vthr in turn (none, one or several; the same count across a wavefront).
-template <int C, bool WAVE, int F4_IN_FLIGHT, bool BF16 = false>
+// BF16: gf is bfloat16; OBF16: gf_out is (a narrow bf16 core hands gf' on in fp32: bf16 in, fp32 out).
+template <int C, bool WAVE, int F4_IN_FLIGHT, bool BF16 = false, bool OBF16 = BF16>
 __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const float* gf, float* gf_out, const float* __restrict__ base, int g, size_t r, int t0,
                                                   int t1, int tid, int nthr, float* s_g, int vthr = 0) {
   constexpr int Q = (C + 3) / 4, CP = 4 * Q;
@@ -659,7 +660,7 @@ __device__ __forceinline__ void graph_update_rows(const BlockArgs& a, const floa
   for (int j = tid; j < og; j += nthr) {
     float y = s_w[nw + j];
     for (int k = 0; k < K; ++k) y = fmaf(s_w[k * og + j], s_x[k], y);
-    st_feat<BF16>(gf_out, out + j, act_apply(y, a.act_g));
+    st_feat<OBF16>(gf_out, out + j, act_apply(y, a.act_g));
   }
 }
 
@@ -799,11 +800,16 @@ __device__ __forceinline__ cslotp run_slot() {
   return p;
 }
 
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK, bool FFE, bool CHAIN, bool BF16 = false, bool RUN = false>
+// OUT32 (with BF16; the block of a narrow bf16 GNCore, gnx_core_forward_typed): the INPUT rows are bf16, the block's own outputs — nf', and ef'
+// without FFE — are stored as fp32 (they are intermediates of the core: the post kernels add the residual terms to them unrounded); with FFE
+// the edge lanes store the CORE's edge row, rounded once, as bf16.
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK, bool FFE, bool CHAIN, bool BF16 = false, bool RUN = false, bool OUT32 = false>
 __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
+  static_assert(!OUT32 || (BF16 && LN), "OUT32: bf16 rows in, fp32 rows out — the LayerNorm-on-load block of a bf16 core");
+  constexpr bool OBF16 = BF16 && !OUT32;  // element type of the ef' / nf' rows this kernel stores
   static_assert(!RUN || (!PACK && !FFE && !LN && !CHAIN && OE + ON > 0), "RUN: the two-launch form of a plain block, one slot per step");
   static_assert(!(PACK && ONEG), "packs are for batches of several graphs");
-  static_assert(!BF16 || (!FFE && !LN), "bf16 features: the plain block forward and its chained form");
+  static_assert(!BF16 || OUT32 || (!FFE && !LN), "bf16 features: the plain block forward and its chained form; a core's block hands on fp32");
   static_assert(!CHAIN || (!PACK && !FFE && !LN && OE + ON > 0), "CHAIN: the two-launch form of a plain block");
   static_assert(!FFE || (LN && DE == OE && DE > 0 && EPT == 2 && (DE + DN) * OE > 96 && ((DE + DN) * OE) % 2 == 0 && GNX_WAVE_PK && !PACK),
                 "FFE: a core's block (dims => dims) with LayerNorm on load, two edges per lane, streamed weights");
@@ -1072,7 +1078,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
           act_row<OE1>(acc[i], A1->act_e);
         }
         if (valid[i]) {
-          if constexpr (!FFE) store_row<OE>(feat<BF16>(RUN ? run_ef_out : A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc[i]);
+          if constexpr (!FFE) store_row<OE>(feat<OBF16>(RUN ? run_ef_out : A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc[i]);
           if (nn > 1 || FFE) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) s_out[el * OE + j] = acc[i][j];
@@ -1107,7 +1113,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) acc[j] = fmaf(We[(DE + k) * OE + j], xs[i][k], acc[j]);
           act_row<OE1>(acc, A1->act_e);
-          store_row<OE>(feat<BF16>(RUN ? run_ef_out : A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc);
+          store_row<OE>(feat<OBF16>(RUN ? run_ef_out : A1->ef_out) + (r * (size_t)A1->E + e0 + c0 + el) * OE, acc);
           if (nn > 1) {
 #pragma unroll
             for (int j = 0; j < OE; ++j) s_out[el * OE + j] = acc[j];
@@ -1161,7 +1167,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
       act_row<ON1>(acc, A2->act_n);
 #pragma unroll
       for (int j = 0; j < ON; ++j) v[OE + j] = acc[j];
-      store_row<ON>(feat<BF16>(RUN ? run_nf_out : A2->nf_out) + (r * (size_t)A2->N + n0 + lane) * ON, acc);
+      store_row<ON>(feat<OBF16>(RUN ? run_nf_out : A2->nf_out) + (r * (size_t)A2->N + n0 + lane) * ON, acc);
     }
   }
 
@@ -1279,22 +1285,24 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
         }
 #pragma unroll
         for (int k = 0; k < DE; ++k) o[k] = rs[m][k] + o[k];
-        if (ffv[m]) store_row<OE>(ef_out_t + (ff_row0 + 64 * m) * OE, o);
+        if (ffv[m]) store_row<OE>(feat<BF16>(ef_out_t) + (ff_row0 + 64 * m) * OE, o);  // (the core's edge row: the element type of the call)
       }
     }
   }
 }
 
-// BF16: the six feature tensors are bfloat16 (gnx_block_forward_typed): rows widened on load, outputs rounded on store, fp32 in between
+// BF16: the six feature tensors are bfloat16 (gnx_block_forward_typed): rows widened on load, outputs rounded on store, fp32 in between.
+// LN with BF16 is the block of a bf16 core and nothing else: bf16 rows in, fp32 rows out (OUT32 above; the kernel keeps its parameter list).
 template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN = false, bool ONEG = false, bool PACK = false, bool FFE = false, bool CHAIN = false,
           bool BF16 = false>
 __global__ __launch_bounds__(PACK ? kPackThreads : kThreads) __attribute__((amdgpu_num_sgpr(GNX_WAVE_SGPRS))) void k_block_wave(BlockArgs a, int n_rows) {
   static_assert(!FFE, "the FFE form is k_block_wave_ffe");
-  block_wave_body<DE, DN, DG, OE, ON, EPT, LN, ONEG, PACK, false, CHAIN, BF16>(a, n_rows);
+  block_wave_body<DE, DN, DG, OE, ON, EPT, LN, ONEG, PACK, false, CHAIN, BF16, false, LN && BF16>(a, n_rows);
 }
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool ONEG>
+// (BF16: a bf16 core — bf16 rows in, nf' out as fp32, the core's edge rows out as bf16)
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool ONEG, bool BF16 = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_block_wave_ffe(BlockArgs a, int n_rows) {
-  block_wave_body<DE, DN, DG, OE, ON, EPT, true, ONEG, false, true, false>(a, n_rows);
+  block_wave_body<DE, DN, DG, OE, ON, EPT, true, ONEG, false, true, false, BF16, false, BF16>(a, n_rows);
 }
 
 // A run of steps in one launch (RUN above): gridDim.y = the run's steps, blockIdx.y the slot.  A kernel of its own, so that k_block_wave keeps
@@ -1305,7 +1313,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(GNX_WAVE_S
 }
 
 // Graph update for the wave path: one workgroup per graph (one wavefront when the graph has <= 256 partial rows).
-template <int C, bool ONEG = false, bool BF16 = false>
+template <int C, bool ONEG = false, bool BF16 = false, bool OBF16 = BF16>
 __global__ void k_graph_t(BlockArgs a, int n_rows) {
   extern __shared__ float s_g[];
   constexpr int CP = (C + 3) / 4 * 4;
@@ -1313,8 +1321,8 @@ __global__ void k_graph_t(BlockArgs a, int n_rows) {
   // one graph: k_block_wave stored one row per WORKGROUP (4 wave tiles); several graphs: one row per wave tile
   const int t0 = ONEG ? 0 : a.wtile_off[g], t1 = ONEG ? (a.n_wtiles + 3) / 4 : a.wtile_off[g + 1];
   const float* base = a.partials + blockIdx.y * (size_t)n_rows * CP;
-  if (blockDim.x == 64) graph_update_rows<C, true, 16, BF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, 64, s_g);
-  else graph_update_rows<C, false, 16, BF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
+  if (blockDim.x == 64) graph_update_rows<C, true, 16, BF16, OBF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, 64, s_g);
+  else graph_update_rows<C, false, 16, BF16, OBF16>(a, a.gf, a.gf_out, base, g, blockIdx.y, t0, t1, (int)threadIdx.x, (int)blockDim.x, s_g);
 }
 
 // ... of a run: slot blockIdx.y's partial rows, gf and gf_out from the table, summed as k_graph_t sums them (the launcher gives it k_graph_t's

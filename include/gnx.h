@@ -519,6 +519,31 @@ GNX_API int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, 
                          const float* gf, int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out,
                          void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
 
+/* The same (test-mode) forward on bfloat16 feature tensors.  `elem` (GNX_ELEM_F32 or GNX_ELEM_BF16) applies to all six tensors; GNX_ELEM_F32
+ * is exactly gnx_core_forward (same validation, same workspace size, same bits).  Contract, for finite data with GNX_ELEM_BF16: the three
+ * outputs are bit for bit to_bf16(gnx_core_forward(widen(ef), widen(nf), widen(gf))) under the same flags — inputs are widened exactly, every
+ * intermediate (gn1 / gn2 rows, the block's three outputs, edge->node sums, graph partial rows, FeedForward hidden units) stays fp32, and
+ * only the core's three outputs are rounded, once, to nearest even.  bf16 buffers must be 4-byte aligned (rows of odd width are then 2-byte
+ * aligned: the kernels never assume more), else GNX_ERR_INVALID_ARG; the workspace 16-byte aligned, else GNX_ERR_WORKSPACE.
+ * Paths.  NATIVE, where the fp32 core runs the fused LayerNorm-on-load block kernel of the ahead-of-time set (README ex.3's widths (10,5,3) at
+ * the default wave-tile size, a batch with edges): the same launches as the fp32 core, no conversion pass — the block kernel reads bf16 rows,
+ * normalises them on load and hands ef' / nf' / gf' on as fp32 in the workspace (the gn1 regions of the fp32 layout, unused in this form; with
+ * the edge FeedForward in the block's edge lanes no edge-sized intermediate exists at all and the core's edge rows are stored as bf16 from
+ * there), and k_core_post3 / k_core_post read x as bf16, the block's rows as fp32, and store the core's rows as bf16.  The workspace is
+ * gnx_core_workspace_bytes.  FALLBACK, everything else — the matrix-core widths, other narrow triples (run-time specialised ones too),
+ * GNX_FLAG_FORCE_GENERIC, GNX_FLAG_NO_JIT, another wave-tile size, a batch without edges: the inputs are widened into fp32 copies behind
+ * the fp32 core's workspace, gnx_core_forward runs on them, the outputs are rounded (six fp32 tensors more in the query's size).
+ * gnx_core_typed_workspace_bytes sizes the workspace for the path these flags take and warms whatever the call will need (side streams,
+ * tables, run-time specialisations), so call it outside any capture; it returns 0 for an unknown `elem` or GNX_FLAG_DEFER_GRAPH_UPDATE with
+ * bf16, both of which gnx_core_forward_typed rejects (GNX_ERR_INVALID_ARG) before any GPU work — as it does a misaligned bf16 buffer and
+ * (GNX_ERR_DIMS) dims that the block does not map to themselves, each of them even on a NULL handle.  Every other rule is gnx_core_forward's:
+ * NULL rules, status codes, no allocation, no synchronisation, capture-safe.  Not typed (fp32 only): gnx_core_forward_train,
+ * gnx_core_backward, gnx_model. */
+GNX_API size_t gnx_core_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem, uint32_t flags);
+GNX_API int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                       int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace, size_t workspace_bytes,
+                                       uint32_t flags, void* stream);
+
 /* ---- GNCore in TRAINING mode: the Dropout(p) that ends each FeedForward chain (src/gnfeedforward.jl:27-31), applied by Flux inside a
  * gradient call and skipped in test mode (= gnx_core_forward).  y = x + block(gn1(x)) + m .* ffwd(gn2(x)) with m = u > p ? 1/(1-p) : 0,
  * u uniform on [0,1), independent per element (Flux._dropout_kernel).  (GNBlock's own `dropout` field is never applied by its forward:
