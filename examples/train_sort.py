@@ -3,7 +3,9 @@
 (/root/reference/examples/sort/sort.jl:31-81,116-134): every graph is a fully connected set of N random numbers, the
 model (GNBlock -> GNCoreList -> GNBlock) learns, per node, whether the node holds the minimum, and per edge i->j whether
 x_j is the successor of x_i in sorted order; loss = logitcrossentropy on flatunpaddednf + flatunpaddedef.
-    python examples/train_sort.py [--iters 300] [--graphs 64] [--n 8] [--width 16]
+    python examples/train_sort.py [--iters 300] [--graphs 64] [--n 8] [--width 16] [--bf16]
+--bf16: the features are batched as bfloat16 and stay bfloat16 from layer to layer — forward and backward of every block and core run on them
+(gnx_block_backward_typed, gnx_core_backward_typed); weights, their gradients and the loss stay float32.
 """
 import argparse
 import os
@@ -16,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import graphnets_jl_amd as gn  # noqa: E402
 
 
-def make_batch(rng, n_graphs, n, device, vocab=0):
+def make_batch(rng, n_graphs, n, device, vocab=0, dtype=None):
     """vocab = 0: n random reals per graph as a 1-wide node feature; vocab > 0: the reference's setup — 2..n random integers in
     1..vocab per graph, one-hot node features of width vocab (sort.jl:13-26)."""
     adjs, nfs, tn, te = [], [], [], []
@@ -36,7 +38,7 @@ def make_batch(rng, n_graphs, n, device, vocab=0):
         succ = (rank[None, :] == rank[:, None] + 1)                                        # succ[i, j]: x_j follows x_i
         flat = succ.flatten(order="F")                                                     # edge order = column-major ones
         te.append(np.stack([flat, ~flat]).astype(np.float32))                              # (2, n*n)
-    x = gn.batch(dict(graphs=adjs, ef=None, nf=nfs, gf=None), device=device)
+    x = gn.batch(dict(graphs=adjs, ef=None, nf=nfs, gf=None), device=device, dtype=dtype)
     return x, torch.from_numpy(np.concatenate(tn, axis=1)).to(device), torch.from_numpy(np.concatenate(te, axis=1)).to(device)
 
 
@@ -52,15 +54,19 @@ def main():
     ap.add_argument("--vocab", type=int, default=0, help="one-hot integer inputs like the reference (sort.jl uses 100)")
     ap.add_argument("--reference-config", action="store_true",
                     help="the reference's sizes: vocab 100, 2..10 nodes, core width 384, batch 4, 2 cores (sort.jl:11-16,86-89,116)")
+    ap.add_argument("--bf16", action="store_true", help="bfloat16 features through every layer, forward and backward (weights and the loss stay float32)")
     args = ap.parse_args()
+    if args.bf16 and args.dropout > 0:
+        sys.exit("--bf16 with --dropout > 0: Dropout in training mode on bfloat16 features is not implemented (the training-mode core is fp32 only)")
     if args.reference_config:
         args.vocab, args.n, args.width, args.graphs = 100, 10, 384, 4
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     w = args.width
-    enc = gn.GNBlock((0, args.vocab or 1, 0), (w, w, w), device=dev, act=("relu", "relu", "relu"))
-    cores = gn.GNCoreList([gn.GNCore((w, w, w), dropout=args.dropout, device=dev) for _ in range(2)])
-    dec = gn.GNBlock((w, w, w), (2, 2, 0), device=dev)
+    b16 = bool(args.bf16)
+    enc = gn.GNBlock((0, args.vocab or 1, 0), (w, w, w), device=dev, act=("relu", "relu", "relu"), bf16_backward=b16)
+    cores = gn.GNCoreList([gn.GNCore((w, w, w), dropout=args.dropout, device=dev, bf16=b16, bf16_backward=b16) for _ in range(2)])
+    dec = gn.GNBlock((w, w, w), (2, 2, 0), device=dev, bf16_backward=b16)
     params = []
     for blk in (enc, dec):
         for l in (blk.edgefn, blk.nodefn, blk.graphfn):
@@ -78,10 +84,12 @@ def main():
     for it in range(args.iters):
         if it == min(10, args.iters - 1):
             torch.cuda.synchronize(); t_start = (time.perf_counter(), it)
-        x, tn, te = make_batch(rng, args.graphs, args.n, dev, args.vocab)
+        x, tn, te = make_batch(rng, args.graphs, args.n, dev, args.vocab, torch.bfloat16 if b16 else None)
         if args.profile and it == args.iters - 1:
             torch.cuda.synchronize(); gn._lib.profile_enable(True); gn._lib.profile_reset()
         y = dec(cores(enc(x)))
+        if b16:  # the loss is computed in float32
+            y = gn.NT(y.graphs, y.ef.float(), y.nf.float(), None)
         loss = gn.logitcrossentropy(gn.flatunpaddednf(y), tn) + gn.logitcrossentropy(gn.flatunpaddedef(y), te)
         opt.zero_grad()
         loss.backward()

@@ -1266,10 +1266,14 @@ class GNCore:
     `testmode(core)` / `trainmode(core)` force it as `Flux.testmode!` / `trainmode!` do.
     `eps_mode` 0 = Flux 0.14 `normalise` (x-μ)/(σ+ε); 1 = (x-μ)/sqrt(σ²+ε).
     `bf16` (also a plain attribute): lets a call on bfloat16 features (batch(..., dtype=torch.bfloat16)) run through gnx_core_forward_typed —
-    bf16 outputs, bit for bit the fp32 core on the widened inputs rounded once.  The test-mode forward only: a differentiable call or one
-    with Dropout active raises NotImplementedError.  Off (the default) a bfloat16 tensor raises TypeError; float32 features never notice it."""
+    bf16 outputs, bit for bit the fp32 core on the widened inputs rounded once.  Off (the default) a bfloat16 tensor raises TypeError; float32
+    features never notice it.
+    `bf16_backward` (also a plain attribute, as GNBlock's): lets a differentiable call on bfloat16 features run — gnx_core_backward_typed is its
+    pullback, the three saved inputs stay bf16, input gradients come back in bf16 and parameter gradients in fp32.  Off (the default) such a
+    call raises NotImplementedError.  Dropout active on bfloat16 features (forced by `trainmode`, or p > 0 inside a gradient call) raises
+    NotImplementedError either way: the training-mode pair is fp32 only."""
 
-    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False):
+    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False, bf16_backward=False):
         dims = tuple(int(d) for d in dims)
         assert any(d > 0 for d in dims)  # gncore.jl:47
         self.dims = dims
@@ -1280,6 +1284,7 @@ class GNCore:
         self.eps, self.eps_mode = eps, eps_mode
         self.flags = 0
         self.bf16 = bool(bf16)
+        self.bf16_backward = bool(bf16_backward)
 
     def _c(self, keep):
         p = _lib.CoreParams()
@@ -1360,15 +1365,27 @@ class GNCore:
 
 
     def _call_bf16(self, x, flags):
-        """bfloat16 features with the `bf16` switch on: gnx_core_forward_typed, bf16 outputs.  Everything that is not this test-mode forward is
-        refused before any library call."""
-        if self._training((x.ef, x.nf, x.gf)):
-            raise NotImplementedError("GNCore: the backward of a bfloat16 core (a typed gnx_core_backward) is not implemented; call it under "
-                                      "torch.no_grad() with parameters that need no gradient, or with float32 features")
-        if float(self.ffwd.dropout or 0) > 0 and getattr(self, "_dropout_mode", None):
-            raise NotImplementedError("GNCore: Dropout in training mode on bfloat16 features (a typed gnx_core_forward_train) is not implemented; "
-                                      "use testmode(core) or float32 features")
-        g, ef, nf, gf, R = _forward_common(x, self.dims, None)
+        """bfloat16 features with the `bf16` switch on: gnx_core_forward_typed, bf16 outputs; a differentiable call needs `bf16_backward`
+        (gnx_core_backward_typed is then the pullback).  Everything else is refused before any library call."""
+        grad_call = self._training((x.ef, x.nf, x.gf))
+        if grad_call and not getattr(self, "bf16_backward", False):
+            raise NotImplementedError("GNCore: the backward of a bfloat16 core is off; construct the core with bf16_backward=True (or set "
+                                      "core.bf16_backward = True) to differentiate through gnx_core_backward_typed, call it under torch.no_grad() "
+                                      "with parameters that need no gradient, or use float32 features")
+        forced = getattr(self, "_dropout_mode", None)
+        if float(self.ffwd.dropout or 0) > 0 and (grad_call if forced is None else forced):
+            raise NotImplementedError("GNCore: Dropout in training mode on bfloat16 features (a typed gnx_core_forward_train / "
+                                      "gnx_core_backward_train) is not implemented; use testmode(core), dropout=0 or float32 features")
+        if grad_call:
+            g, ef, nf, gf, R = _forward_common(x, self.dims, None)
+            eo, no, go = _CoreBf16Fn.apply(self, g, R, self.flags if flags is None else flags, ef, nf, gf, *self._param_list())
+            return NT(g, _jl(eo), _jl(no), _jl(go))
+        eo, no, go, g = self._forward_bf16(x, flags)
+        return NT(g, _jl(eo), _jl(no), _jl(go))
+
+    def _forward_bf16(self, x, flags):
+        """gnx_core_forward_typed on the features of x (or on packed tensors with their handle: x = (g, ef, nf, gf, R))."""
+        g, ef, nf, gf, R = x if isinstance(x, tuple) and len(x) == 5 else _forward_common(x, self.dims, None)
         # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
         ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
         lib = _lib.load()
@@ -1382,7 +1399,7 @@ class GNCore:
             ws = g.workspace(nbytes, ("core_bf16", self.dims, R, flags))
             check(lib.gnx_core_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(), no.data_ptr(),
                                              go.data_ptr(), ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
-        return NT(g, _jl(eo), _jl(no), _jl(go))
+        return eo, no, go, g
 
 
 def _core_forward(core, g, R, flags, drop, ef, nf, gf):
@@ -1458,17 +1475,7 @@ class _CoreFn(torch.autograd.Function):
         p = core._c(keep)
         plist = core._param_list()
         out = [torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=dev).t() if q.dim() == 2 else torch.empty_like(q) for q in plist]
-        gr = _lib.CoreGrads()
-        wptr = lambda t: t.t().data_ptr() if t.dim() == 2 else t.data_ptr()  # the (in, out)-contiguous storage under the (out, in) view
-        it = iter(out)
-        for dst in (gr.block.edgefn, gr.block.nodefn, gr.block.graphfn):
-            dst.weight, dst.bias = wptr(next(it)), wptr(next(it))
-        for arr in (gr.ln1, gr.ln2):
-            for i in range(3):
-                arr[i].gamma, arr[i].beta = wptr(next(it)), wptr(next(it))
-        for i in range(3):
-            gr.ff[i].fc1.weight, gr.ff[i].fc1.bias = wptr(next(it)), wptr(next(it))
-            gr.ff[i].fc2.weight, gr.ff[i].fc2.bias = wptr(next(it)), wptr(next(it))
+        gr = _core_grads(core, out)
         d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
         with torch.cuda.device(dev):
             nb = lib.gnx_core_backward_workspace_bytes(g._h, C.byref(p), R)
@@ -1482,6 +1489,66 @@ class _CoreFn(torch.autograd.Function):
                                                   _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(), d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(),
                                                   torch.cuda.current_stream(dev).cuda_stream))
         return (None, None, None, None, None, d_ef, d_nf, d_gf, *out)
+
+
+def _core_grads(core, out):
+    """gnx_core_grads over `out`, one fp32 tensor per entry of core._param_list() in its order (weights as (out, in) views of (in, out)-contiguous
+    storage, like the parameters)."""
+    gr = _lib.CoreGrads()
+    wptr = lambda t: t.t().data_ptr() if t.dim() == 2 else t.data_ptr()  # the (in, out)-contiguous storage under the (out, in) view
+    it = iter(out)
+    for dst in (gr.block.edgefn, gr.block.nodefn, gr.block.graphfn):
+        dst.weight, dst.bias = wptr(next(it)), wptr(next(it))
+    for arr in (gr.ln1, gr.ln2):
+        for i in range(3):
+            arr[i].gamma, arr[i].beta = wptr(next(it)), wptr(next(it))
+    for i in range(3):
+        gr.ff[i].fc1.weight, gr.ff[i].fc1.bias = wptr(next(it)), wptr(next(it))
+        gr.ff[i].fc2.weight, gr.ff[i].fc2.bias = wptr(next(it)), wptr(next(it))
+    return gr
+
+
+class _CoreBf16Fn(torch.autograd.Function):
+    """_CoreFn on bfloat16 features (GNCore.bf16 with GNCore.bf16_backward, test mode): forward = gnx_core_forward_typed, backward =
+    gnx_core_backward_typed.  The three saved inputs are bf16 — the backward recomputes every intermediate from them in fp32; the input
+    gradients come back in bf16 (rounded once from the fp32 pullback), the parameter gradients in fp32 in _CoreFn's layout."""
+
+    @staticmethod
+    def forward(ctx, core, g, R, flags, ef, nf, gf, *params):
+        # the typed entries need 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
+        ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+        eo, no, go, _ = core._forward_bf16((g, ef, nf, gf, R), flags)
+        ctx.core, ctx.g, ctx.R = core, g, R
+        ctx.save_for_backward(ef, nf, gf)
+        return eo, no, go
+
+    @staticmethod
+    def backward(ctx, ge, gn_, gg):
+        lib = _lib.load()
+        core, g, R = ctx.core, ctx.g, ctx.R
+        ef, nf, gf = ctx.saved_tensors
+        dev = g.device
+
+        def cot(t):  # contiguous and 4-byte aligned (a cotangent has the bf16 dtype of its output); a missing one is passed as NULL
+            if t is None:
+                return None
+            t = t.contiguous()
+            return t if t.data_ptr() % 4 == 0 else t.clone()
+
+        ge, gn_, gg = cot(ge), cot(gn_), cot(gg)
+        keep = []
+        p = core._c(keep)
+        plist = core._param_list()
+        out = [torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=dev).t() if q.dim() == 2 else torch.empty_like(q) for q in plist]
+        gr = _core_grads(core, out)
+        d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
+        with torch.cuda.device(dev):
+            nb = lib.gnx_core_backward_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16)
+            ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
+            check(lib.gnx_core_backward_typed(g._h, C.byref(p), _lib.ELEM_BF16, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg),
+                                              R, d_ef.data_ptr(), d_nf.data_ptr(), d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(),
+                                              torch.cuda.current_stream(dev).cuda_stream))
+        return (None, None, None, None, d_ef, d_nf, d_gf, *out)
 
 
 class GNCoreList:

@@ -15,6 +15,7 @@
 
 #include "gnx_launchers.h"
 #include "gnx_wave_kernel.h"  // ld_feat / st_feat: a bf16 or fp32 element of a feature buffer
+#include "gnx_feat4.h"        // ld_bf16x4, ld_feat4 / st_feat4: four of them
 
 namespace gnx {
 
@@ -23,11 +24,6 @@ namespace gnx {
 // (to_bf16), one 16-bit access per element — a thread never touches the other half of a dword, so odd element counts and rows that start
 // in the middle of a dword need no special case; everything between load and store is the fp32 code, instruction for instruction.
 
-// four consecutive bf16 elements from element i of a feature buffer (i % 4 == 0, base 8-B aligned), widened
-__device__ __forceinline__ float4 ld_bf16x4(const float* base, size_t i) {
-  const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(base) + i);
-  return make_float4(bf16_lo(w.x), bf16_hi(w.x), bf16_lo(w.y), bf16_hi(w.y));
-}
 // one element through a typed row pointer
 __device__ __forceinline__ float ld_elem(const float* p) { return *p; }
 __device__ __forceinline__ float ld_elem(const bf16_t* p) { return bf16_lo(*p); }
@@ -373,6 +369,8 @@ __global__ void k_fw_dense(const float* __restrict__ x, const float* __restrict_
 //   xhat = (x - mu) / s,  s = sigma + eps (mode 0) or sqrt(sigma^2 + eps) (mode 1);  y_i = gamma_i xhat + beta_i
 //   dxhat = dy1*gamma1 + dy2*gamma2;  dx = (dxhat - mean(dxhat)) / s - c * sum(dxhat*c) / (D * q),  c = x - mu,
 //   q = sigma*s^2 (mode 0) or s^3 (mode 1);  dx_out = resid + dx.   t1 = dy1*xhat, t2 = dy2*xhat feed the gamma gradients.
+// BF16: x and dx hold bfloat16 elements (gnx_core_backward_typed) — x widened on load, dx rounded on store; everything else is fp32.
+template <bool BF16>
 __global__ __launch_bounds__(256) void k_ln_backward(const float* __restrict__ x, size_t rows, int d, const float* g1, const float* g2,
                                                      const float* __restrict__ dy1, const float* __restrict__ dy2,
                                                      const float* __restrict__ resid, float eps, int eps_mode, float* __restrict__ dx,
@@ -380,13 +378,13 @@ __global__ __launch_bounds__(256) void k_ln_backward(const float* __restrict__ x
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float* xr = x + row * d;
+  const typename ElemOf<BF16>::T* xr = feat<BF16>(x) + row * d;
   float s = 0.f;
-  for (int k = lane; k < d; k += 64) s += xr[k];
+  for (int k = lane; k < d; k += 64) s += ld_elem(xr + k);
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   const float mu = s / (float)d;
   float v = 0.f;
-  for (int k = lane; k < d; k += 64) { const float c = xr[k] - mu; v = fmaf(c, c, v); }
+  for (int k = lane; k < d; k += 64) { const float c = ld_elem(xr + k) - mu; v = fmaf(c, c, v); }
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   v /= (float)d;
   const float sigma = sqrtf(v);
@@ -394,7 +392,7 @@ __global__ __launch_bounds__(256) void k_ln_backward(const float* __restrict__ x
   const float q = eps_mode == 0 ? sigma * sden * sden : sden * sden * sden;
   float sum_dxh = 0.f, sum_dxh_c = 0.f;
   for (int k = lane; k < d; k += 64) {
-    const float c = xr[k] - mu;
+    const float c = ld_elem(xr + k) - mu;
     const float a1 = dy1 ? dy1[row * d + k] : 0.f, a2 = dy2 ? dy2[row * d + k] : 0.f;
     const float dxh = a1 * g1[k] + a2 * g2[k];
     sum_dxh += dxh;
@@ -408,10 +406,10 @@ __global__ __launch_bounds__(256) void k_ln_backward(const float* __restrict__ x
   const float coef = q > 0.f ? sum_dxh_c / ((float)d * q) : 0.f;
   if (dx) {
     for (int k = lane; k < d; k += 64) {
-      const float c = xr[k] - mu;
+      const float c = ld_elem(xr + k) - mu;
       const float a1 = dy1 ? dy1[row * d + k] : 0.f, a2 = dy2 ? dy2[row * d + k] : 0.f;
       const float dxh = a1 * g1[k] + a2 * g2[k];
-      dx[row * d + k] = (resid ? resid[row * d + k] : 0.f) + (dxh - mean_dxh) / sden - c * coef;
+      st_feat<BF16>(dx, row * d + k, (resid ? resid[row * d + k] : 0.f) + (dxh - mean_dxh) / sden - c * coef);
     }
   }
 }
@@ -428,7 +426,8 @@ __device__ __forceinline__ float row16_sum_b(float v) {
   return v;
 }
 constexpr int LNB_ROWS = 128;  // rows per workgroup
-template <int Q>
+// BF16: x and dx hold bfloat16 elements — a lane's four columns are one 8-byte access instead of one 16-byte access.
+template <int Q, bool BF16>
 __global__ __launch_bounds__(256) void k_ln_backward_v4(const float* __restrict__ x, size_t rows, const float* __restrict__ g1, const float* __restrict__ g2,
                                                         const float* __restrict__ dy1, const float* __restrict__ dy2, const float* __restrict__ resid,
                                                         float eps, int eps_mode, float* __restrict__ dx, float* __restrict__ cpart) {
@@ -449,7 +448,7 @@ __global__ __launch_bounds__(256) void k_ln_backward_v4(const float* __restrict_
     float4 c[Q], a1[Q], a2[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      c[q] = reinterpret_cast<const float4*>(x + row * D)[sub + 16 * q];
+      c[q] = ld_feat4<BF16>(x, row * D, sub + 16 * q);
       a1[q] = reinterpret_cast<const float4*>(dy1 + row * D)[sub + 16 * q];
       a2[q] = reinterpret_cast<const float4*>(dy2 + row * D)[sub + 16 * q];
     }
@@ -496,7 +495,7 @@ __global__ __launch_bounds__(256) void k_ln_backward_v4(const float* __restrict_
           o.y = rr.y + (dxh[q].y - mean_dxh) * inv - c[q].y * coef;
           o.z = rr.z + (dxh[q].z - mean_dxh) * inv - c[q].z * coef;
           o.w = rr.w + (dxh[q].w - mean_dxh) * inv - c[q].w * coef;
-          reinterpret_cast<float4*>(dx + row * D)[sub + 16 * q] = o;
+          st_feat4<BF16>(dx, row * D, sub + 16 * q, o);
         }
       }
     }
@@ -783,6 +782,16 @@ static TypedBwWs typed_bw_ws(const gnx_graphs* h, const gnx_block_params* p, int
   return w;
 }
 
+// the feature buffers of a bf16 backward call (gnx_block_backward_typed, gnx_core_backward_typed): n_in inputs and the three input gradients
+// (NULL passes).  Rows of odd width are then 2-byte aligned, which is all the kernels assume.
+static int32_t check_bf16_aligned(const void* const* in, int n_in, void* const out[3]) {
+  for (int i = 0; i < n_in; ++i)
+    if (((uintptr_t)in[i] & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  for (int i = 0; i < 3; ++i)
+    if (((uintptr_t)out[i] & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  return GNX_OK;
+}
+
 }  // namespace gnx
 
 using namespace gnx;
@@ -826,10 +835,7 @@ int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_params* p,
   if (rc) return rc;
   const void* in[9] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out};
   void* out[3] = {d_ef, d_nf, d_gf};
-  for (const void* b : in)
-    if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
-  for (const void* b : out)
-    if (((uintptr_t)b & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  if ((rc = check_bf16_aligned(in, 9, out))) return rc;
   const TypedBwWs w = typed_bw_ws(h, p, R);
   if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_backward_typed_workspace_bytes()");
   if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
@@ -893,6 +899,25 @@ CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64
   L.total = o + 256;
   return L;
 }
+// gnx_core_backward_typed, GNX_ELEM_BF16: the fp32 layout, then an fp32 copy of each upstream gradient, every carve 256-B aligned.  (x and d_x
+// need none: the LayerNorm kernels read and write bf16 themselves.)
+struct TypedCoreBwWs {
+  size_t base, off[3], n[3], total;
+};
+TypedCoreBwWs typed_core_bw_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
+  TypedCoreBwWs w{};
+  w.base = core_bw_layout(h, p, R).total;
+  const int64_t rows[3] = {h->E, h->N, h->G};
+  const int d[3] = {p->block.de, p->block.dn, p->block.dg};
+  size_t o = align_up(w.base, 256);
+  for (int t = 0; t < 3; ++t) {
+    w.n[t] = (size_t)R * (size_t)rows[t] * (size_t)std::max(d[t], 0);
+    w.off[t] = o;
+    o += align_up(sizeof(float) * w.n[t], 256);
+  }
+  w.total = o;
+  return w;
+}
 }  // namespace
 
 size_t gnx_core_backward_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
@@ -907,6 +932,10 @@ size_t gnx_core_backward_workspace_bytes(const gnx_graphs* h, const gnx_core_par
 // `dr` (gnx_core_backward_train): the FeedForwards' outputs were multiplied by the Dropout masks of *dr in the forward
 // (gnx_core_forward_train, csrc/gnx_dropout.hip), so the upstream gradient of every FeedForward branch is g_out .* mask — the mask
 // regenerated from (seed, entity, element); the block branch and the residual see g_out as it is.
+// BF16 (gnx_core_backward_typed): the nine feature-shaped tensors hold bfloat16 elements (declared float, like the feature pointers of BlockArgs).
+// Only the LayerNorm kernels touch x and d_x — steps 1 and 4 — and they take the element type; the upstream gradients are widened once into
+// fp32 copies behind the fp32 layout, which every consumer below reads; the kernel forms are chosen from the CALLER's addresses as before.
+template <bool BF16>
 static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p, const gnx_dropout* dr, const float* ef, const float* nf, const float* gf,
                                   const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                                   float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
@@ -920,27 +949,44 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
   for (int t = 0; t < 3; ++t) {
     if (p->ff[t].fc2.act != GNX_ACT_IDENTITY) return fail(GNX_ERR_INVALID_ARG, "core backward: fc2 must be identity");
   }
+  const float* x[3] = {ef, nf, gf};
+  const float* gout[3] = {g_ef_out, g_nf_out, g_gf_out};  // what the consumers read (BF16: the fp32 copies, set below)
+  const float* const gcaller[3] = {g_ef_out, g_nf_out, g_gf_out};
+  float* dxo[3] = {d_ef, d_nf, d_gf};
+  int32_t rc;
+  if constexpr (BF16) {
+    const void* in[6] = {ef, nf, gf, g_ef_out, g_nf_out, g_gf_out};
+    void* out[3] = {d_ef, d_nf, d_gf};
+    if ((rc = check_bf16_aligned(in, 6, out))) return rc;
+  }
   const CoreBwLayout L = core_bw_layout(h, p, R);
-  if (!ws || ws_bytes < L.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_core_backward_workspace_bytes()");
+  const TypedCoreBwWs tw = BF16 ? typed_core_bw_ws(h, p, R) : TypedCoreBwWs{};
+  if (!ws || ws_bytes < (BF16 ? tw.total : L.total))
+    return fail(GNX_ERR_WORKSPACE, BF16 ? "workspace missing or smaller than gnx_core_backward_typed_workspace_bytes()"
+                                        : "workspace missing or smaller than gnx_core_backward_workspace_bytes()");
   if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
   char* base = static_cast<char*>(ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
   const int d[3] = {b.de, b.dn, b.dg};
-  const float* x[3] = {ef, nf, gf};
-  const float* gout[3] = {g_ef_out, g_nf_out, g_gf_out};
-  float* dxo[3] = {d_ef, d_nf, d_gf};
   const gnx_core_grads none{};
   const gnx_core_grads& gr = grads ? *grads : none;
-  int32_t rc;
+  if constexpr (BF16) {  // a NULL upstream gradient stays NULL; one without rows is never read
+    for (int t = 0; t < 3; ++t) {
+      if (!gcaller[t] || tw.n[t] == 0) continue;
+      if ((rc = launch_bf16_widen(gcaller[t], tw.n[t], F(tw.off[t]), s))) return rc;
+      gout[t] = F(tw.off[t]);
+    }
+  }
   auto blocks = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
   int* off2 = reinterpret_cast<int*>(base + L.off2);
   float* part = F(L.part);
 
   // 1. recompute gn1(x), gn2(x) and the block's outputs
   for (int t = 0; t < 3; ++t)
-    if ((rc = launch_layernorm2(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, F(L.l1[t]), F(L.l2[t]), s))) return rc;
+    if ((rc = BF16 ? launch_layernorm2_bf16(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, F(L.l1[t]), F(L.l2[t]), s)
+                   : launch_layernorm2(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, F(L.l1[t]), F(L.l2[t]), s))) return rc;
   if ((rc = gnx_block_forward(h, &b, F(L.l1[0]), F(L.l1[1]), F(L.l1[2]), R, F(L.bout[0]), F(L.bout[1]), F(L.bout[2]), base + L.blk_fw,
                               gnx_block_workspace_bytes(h, &b, R), 0, stream))) return rc;
   // 2. FeedForward pullback per entity: f = W2 h + b2, h = act1(W1 z + b1), z = gn2(x); upstream of f is g_out
@@ -1016,7 +1062,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
     GNX_HIP(hipGetLastError());
   }
   // 3. block pullback: inputs gn1(x), outputs recomputed above, upstream g_out -> gradients w.r.t. gn1(x)
-  if ((rc = gnx_block_backward(h, &b, F(L.l1[0]), F(L.l1[1]), F(L.l1[2]), F(L.bout[0]), F(L.bout[1]), F(L.bout[2]), g_ef_out, g_nf_out, g_gf_out, R,
+  if ((rc = gnx_block_backward(h, &b, F(L.l1[0]), F(L.l1[1]), F(L.l1[2]), F(L.bout[0]), F(L.bout[1]), F(L.bout[2]), gout[0], gout[1], gout[2], R,
                                F(L.dl1[0]), F(L.dl1[1]), F(L.dl1[2]), &gr.block, base + L.blk_bw, gnx_block_backward_workspace_bytes(h, &b, R), stream))) return rc;
   // 4. LayerNorm pullbacks (both norms at once) + residual; gamma/beta gradients as column sums over all rows
   for (int t = 0; t < 3; ++t) {
@@ -1026,7 +1072,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
       continue;
     }
     float* t1 = F(L.t1); float* t2 = F(L.t2);
-    const bool al16 = (((uintptr_t)x[t] | (uintptr_t)F(L.dl1[t]) | (uintptr_t)F(L.dz2[t]) | (uintptr_t)gout[t] | (uintptr_t)dxo[t] | (uintptr_t)p->ln1[t].gamma |
+    const bool al16 = (((uintptr_t)x[t] | (uintptr_t)F(L.dl1[t]) | (uintptr_t)F(L.dz2[t]) | (uintptr_t)gcaller[t] | (uintptr_t)dxo[t] | (uintptr_t)p->ln1[t].gamma |
                         (uintptr_t)p->ln2[t].gamma) & 15) == 0;
     if (al16 && d[t] % 64 == 0 && d[t] <= 512 && rows[t] >= 1024) {
       const unsigned nb = (unsigned)((rows[t] + LNB_ROWS - 1) / LNB_ROWS);
@@ -1034,7 +1080,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
       {
         ProfScope ps("bw_layernorm", s);
         switch (d[t] / 64) {
-#define GNX_LNB_CASE(Q) case Q: GNX_LAUNCH((k_ln_backward_v4<Q>), dim3(nb), dim3(256), 0, s, x[t], rows[t], p->ln1[t].gamma, p->ln2[t].gamma, \
+#define GNX_LNB_CASE(Q) case Q: GNX_LAUNCH((k_ln_backward_v4<Q, BF16>), dim3(nb), dim3(256), 0, s, x[t], rows[t], p->ln1[t].gamma, p->ln2[t].gamma, \
                                                    F(L.dl1[t]), F(L.dz2[t]), gout[t], p->eps, p->eps_mode, dxo[t], cpart); break;
           GNX_LNB_CASE(1) GNX_LNB_CASE(2) GNX_LNB_CASE(3) GNX_LNB_CASE(4) GNX_LNB_CASE(5) GNX_LNB_CASE(6) GNX_LNB_CASE(7) GNX_LNB_CASE(8)
 #undef GNX_LNB_CASE
@@ -1048,7 +1094,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
       continue;
     }
     { ProfScope ps("bw_layernorm", s);
-    GNX_LAUNCH(k_ln_backward, dim3((unsigned)((rows[t] + 3) / 4)), dim3(256), 0, s, x[t], rows[t], d[t], p->ln1[t].gamma, p->ln2[t].gamma, F(L.dl1[t]),
+    GNX_LAUNCH(k_ln_backward<BF16>, dim3((unsigned)((rows[t] + 3) / 4)), dim3(256), 0, s, x[t], rows[t], d[t], p->ln1[t].gamma, p->ln2[t].gamma, F(L.dl1[t]),
                        F(L.dz2[t]), gout[t], p->eps, p->eps_mode, dxo[t], t1, t2); }
     GNX_LAUNCH(k_set_off2, dim3(1), dim3(1), 0, s, off2, (int)rows[t]);
     if ((rc = colsum_all(t1, rows[t], d[t], gr.ln1[t].gamma, part, off2, s))) return rc;
@@ -1064,13 +1110,29 @@ extern "C" {
 int32_t gnx_core_backward(const gnx_graphs* h, const gnx_core_params* p, const float* ef, const float* nf, const float* gf,
                           const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                           float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  return core_backward_impl(h, p, nullptr, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
+  return core_backward_impl<false>(h, p, nullptr, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
 }
 int32_t gnx_core_backward_train(const gnx_graphs* h, const gnx_core_params* p, const gnx_dropout* dropout, const float* ef, const float* nf,
                                 const float* gf, const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef,
                                 float* d_nf, float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   if (int32_t rc = check_dropout(dropout)) return rc;
-  return core_backward_impl(h, p, dropout, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
+  return core_backward_impl<false>(h, p, dropout, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
+}
+size_t gnx_core_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) {
+  if (elem == GNX_ELEM_F32) return gnx_core_backward_workspace_bytes(h, p, R);
+  if (elem != GNX_ELEM_BF16 || gnx_core_backward_workspace_bytes(h, p, R) == 0) return 0;  // (the fp32 query builds the tables, outside any capture)
+  return typed_core_bw_ws(h, p, R).total;
+}
+int32_t gnx_core_backward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf,
+                                const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  auto cf = [](const void* q) { return static_cast<const float*>(q); };
+  auto mf = [](void* q) { return static_cast<float*>(q); };
+  if (elem == GNX_ELEM_F32)
+    return gnx_core_backward(h, p, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream);
+  if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  return core_backward_impl<true>(h, p, nullptr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws,
+                                  ws_bytes, stream);
 }
 }  // extern "C"
 
@@ -1240,7 +1302,7 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
         // a LayerNorm layer value: dx through the normalisation (k_ln_backward with one norm), dgamma = column sums of dy . xhat, dbeta = of dy
         float* t1 = gb[2];  // (free here: the gelu pre-activation buffer of delta_rows / last_delta is consumed inside those calls)
         { ProfScope ps("bw_layernorm", s);
-          GNX_LAUNCH(k_ln_backward, dim3((unsigned)((rows[t] + 3) / 4)), dim3(256), 0, s, Ain, rows[t], J, d.weight, d.weight, cur, (const float*)nullptr, (const float*)nullptr,
+          GNX_LAUNCH(k_ln_backward<false>, dim3((unsigned)((rows[t] + 3) / 4)), dim3(256), 0, s, Ain, rows[t], J, d.weight, d.weight, cur, (const float*)nullptr, (const float*)nullptr,
                      kChainLnEps, chain_layer_ln_mode(d), gin, t1, (float*)nullptr); }
         GNX_LAUNCH(k_set_off2, dim3(1), dim3(1), 0, s, off2, (int)rows[t]);
         if ((r2 = colsum_all(t1, rows[t], J, grad_of(t, i).weight, part, off2, s))) return r2;

@@ -8,6 +8,7 @@
 
 #include "gnx_launchers.h"
 #include "gnx_wave_kernel.h"  // ld_feat: a bf16 or fp32 element of a feature buffer
+#include "gnx_feat4.h"        // ld_bf16x4: four of them
 
 namespace gnx {
 
@@ -190,24 +191,26 @@ int32_t launch_block_generic(const BlockArgs& a, int64_t R, int tile_n_cap, hipS
 // GNCore pieces (generic): two LayerNorms sharing statistics, and FFN + residual
 // ---------------------------------------------------------------------------------------------------------
 // One wave per row.  y1 = g1*xhat+b1, y2 = g2*xhat+b2 (gn1 and gn2 normalise the same x, gncore.jl:56-59).
+// BF16: x holds bfloat16 elements (gnx_core_backward_typed), widened as they are loaded; y1 / y2 are fp32 either way.
+template <bool BF16>
 __global__ __launch_bounds__(256) void k_layernorm2(const float* __restrict__ x, size_t rows, int d, const float* g1,
                                                     const float* b1, const float* g2, const float* b2, float eps,
                                                     int eps_mode, float* __restrict__ y1, float* __restrict__ y2) {
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float* xr = x + row * d;
+  const size_t xr = row * d;
   float s = 0.f;
-  for (int k = lane; k < d; k += 64) s += xr[k];
+  for (int k = lane; k < d; k += 64) s += ld_feat<BF16>(x, xr + k);
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   const float mu = s / (float)d;
   float v = 0.f;
-  for (int k = lane; k < d; k += 64) { const float c = xr[k] - mu; v = fmaf(c, c, v); }
+  for (int k = lane; k < d; k += 64) { const float c = ld_feat<BF16>(x, xr + k) - mu; v = fmaf(c, c, v); }
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   v /= (float)d;
   const float inv = eps_mode == 0 ? 1.f / (sqrtf(v) + eps) : 1.f / sqrtf(v + eps);
   for (int k = lane; k < d; k += 64) {
-    const float xh = (xr[k] - mu) * inv;
+    const float xh = (ld_feat<BF16>(x, xr + k) - mu) * inv;
     y1[row * d + k] = fmaf(g1[k], xh, b1[k]);
     y2[row * d + k] = fmaf(g2[k], xh, b2[k]);
   }
@@ -225,7 +228,8 @@ __device__ __forceinline__ float row16_sum_g(float v) {
 // Widths that are multiples of 64 (GNCore at 128/64, the sort example's 384): 16 lanes per row, every lane keeps its
 // Q = d/64 float4 of the row in registers (x is read ONCE, 16-B accesses), statistics by DPP row reductions (a DPP row
 // is exactly the 16 lanes of one LayerNorm row), both outputs written from registers.  4 rows per wave, 16 per block.
-template <int Q>
+// BF16: a lane's four columns are one 8-byte load of bfloat16 elements, widened.
+template <int Q, bool BF16>
 __global__ __launch_bounds__(256) void k_layernorm2_v4(const float* __restrict__ x, size_t rows, const float* __restrict__ g1,
                                                        const float* __restrict__ b1, const float* __restrict__ g2,
                                                        const float* __restrict__ b2, float eps, int eps_mode,
@@ -235,10 +239,15 @@ __global__ __launch_bounds__(256) void k_layernorm2_v4(const float* __restrict__
   size_t row = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   const bool live = row < rows;
   row = live ? row : rows - 1;  // clamped: every lane takes part in the DPP reductions
-  const float4* xr = reinterpret_cast<const float4*>(x + row * D);
   float4 v[Q];
+  if constexpr (BF16) {
 #pragma unroll
-  for (int q = 0; q < Q; ++q) v[q] = xr[sub + 16 * q];
+    for (int q = 0; q < Q; ++q) v[q] = ld_bf16x4(x, row * D + 4 * (sub + 16 * q));
+  } else {
+    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) v[q] = xr[sub + 16 * q];
+  }
   float s = 0.f;
 #pragma unroll
   for (int q = 0; q < Q; ++q) s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
@@ -354,25 +363,36 @@ __global__ __launch_bounds__(256) void k_ffn_residual(const float* __restrict__ 
   }
 }
 
-int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps,
-                          int eps_mode, float* y1, float* y2, hipStream_t s) {
+// BF16: x holds bfloat16 elements.  The forms are chosen as for an fp32 x at the same address (an x that is not 16-byte aligned takes the
+// one-wave-per-row kernel), so a bf16 call runs the kernel form of the fp32 call it is compared with.
+template <bool BF16>
+static int32_t launch_layernorm2_t(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps,
+                                   int eps_mode, float* y1, float* y2, hipStream_t s) {
   if (rows == 0 || d == 0) return GNX_OK;
   ProfScope ps("k_layernorm2", s);
   const bool al16 = (((uintptr_t)x | (uintptr_t)y1 | (uintptr_t)y2 | (uintptr_t)l1.gamma | (uintptr_t)l1.beta | (uintptr_t)l2.gamma | (uintptr_t)l2.beta) & 15) == 0;
   if (al16 && d % 64 == 0 && d <= 512) {
     const dim3 grid((unsigned)((rows + 15) / 16));
     switch (d / 64) {
-#define GNX_LN_CASE(Q) case Q: GNX_LAUNCH((k_layernorm2_v4<Q>), grid, dim3(256), 0, s, x, rows, l1.gamma, l1.beta, l2.gamma, l2.beta, eps, eps_mode, y1, y2); break;
+#define GNX_LN_CASE(Q) case Q: GNX_LAUNCH((k_layernorm2_v4<Q, BF16>), grid, dim3(256), 0, s, x, rows, l1.gamma, l1.beta, l2.gamma, l2.beta, eps, eps_mode, y1, y2); break;
       GNX_LN_CASE(1) GNX_LN_CASE(2) GNX_LN_CASE(3) GNX_LN_CASE(4) GNX_LN_CASE(5) GNX_LN_CASE(6) GNX_LN_CASE(7) GNX_LN_CASE(8)
 #undef GNX_LN_CASE
     }
     GNX_HIP(hipGetLastError());
     return GNX_OK;
   }
-  GNX_LAUNCH(k_layernorm2, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, d, l1.gamma, l1.beta, l2.gamma,
+  GNX_LAUNCH(k_layernorm2<BF16>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, d, l1.gamma, l1.beta, l2.gamma,
                      l2.beta, eps, eps_mode, y1, y2);
   GNX_HIP(hipGetLastError());
   return GNX_OK;
+}
+int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps,
+                          int eps_mode, float* y1, float* y2, hipStream_t s) {
+  return launch_layernorm2_t<false>(x, rows, d, l1, l2, eps, eps_mode, y1, y2, s);
+}
+int32_t launch_layernorm2_bf16(const void* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps,
+                               int eps_mode, float* y1, float* y2, hipStream_t s) {
+  return launch_layernorm2_t<true>(static_cast<const float*>(x), rows, d, l1, l2, eps, eps_mode, y1, y2, s);
 }
 
 int32_t launch_ffn_residual(const float* z, const float* x, size_t rows, int d, const gnx_ffn& ff, float* out, hipStream_t s) {

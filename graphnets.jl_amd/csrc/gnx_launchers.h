@@ -23,6 +23,8 @@ struct EdgeLaunch {
 // ---- gnx_generic.hip: dimension-generic kernels ----
 int32_t launch_block_generic(const BlockArgs& a, int64_t R, int tile_n_cap, hipStream_t s, int phase);
 int32_t launch_layernorm2(const float* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps, int eps_mode, float* y1, float* y2, hipStream_t s);
+// the same on an x of bfloat16 elements (y1 / y2 fp32); the kernel form is chosen as for an fp32 x at that address
+int32_t launch_layernorm2_bf16(const void* x, size_t rows, int d, const gnx_layernorm& l1, const gnx_layernorm& l2, float eps, int eps_mode, float* y1, float* y2, hipStream_t s);
 int32_t launch_ffn_residual(const float* z, const float* x, size_t rows, int d, const gnx_ffn& ff, float* out, hipStream_t s);
 int32_t launch_pad(const gnx_graphs* h, int kind, bool pad, const float* src, int d, int64_t R, float* dst, hipStream_t s);
 int32_t launch_calibration(int n, hipStream_t s);

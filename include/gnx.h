@@ -483,6 +483,30 @@ GNX_API int32_t gnx_core_backward(const gnx_graphs* h, const gnx_core_params* p,
                           const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
                           float* d_nf, float* d_gf, const gnx_core_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same backward on bfloat16 feature tensors: the pullback of gnx_core_forward_typed.  `elem` (GNX_ELEM_F32 or GNX_ELEM_BF16) applies to the
+ * nine feature-shaped tensors — the three inputs, the three upstream gradients and d_ef / d_nf / d_gf; the parameter gradients (gnx_core_grads)
+ * stay fp32, as the weights do.  GNX_ELEM_F32 is exactly gnx_core_backward (same validation, same workspace size, same bits); any other `elem`
+ * is GNX_ERR_INVALID_ARG before any GPU work, and the workspace query returns 0 for it.  NULL rules, optional outputs, n_replicas rules and
+ * status codes are gnx_core_backward's.
+ * Contract, for finite data with GNX_ELEM_BF16: with ref = gnx_core_backward on the exactly widened six inputs, every buffer at the same byte
+ * offset modulo 16 as in the typed call, d_ef / d_nf / d_gf are bit for bit to_bf16(ref's) (round to nearest even, once) and every parameter
+ * gradient is bit for bit ref's.  Nothing is approximate: widening is exact, every intermediate stays fp32 and all sums keep the fp32
+ * backward's fixed orders.
+ * One path at all widths.  The caller's x is read only by the two LayerNorm kernels that recompute gn1(x) / gn2(x) and by the LayerNorm
+ * pullback, which is also the only writer of d_ef / d_nf / d_gf: these kernels take the element type, widen x as they load it and round dx as
+ * they store it, so neither x nor an input gradient ever exists as an fp32 tensor.  Each non-NULL upstream gradient is widened once into an
+ * fp32 copy behind the fp32 layout of the workspace, which the dW2 sums, the dX products, gnx_block_backward and the pullback's residual read
+ * (a NULL one stays NULL).  The kernel forms are chosen as gnx_core_backward chooses them from the caller's addresses: a bf16 x, upstream
+ * gradient or d_x that is not 16-byte aligned takes the one-wave-per-row LayerNorm kernels, as a 4-byte aligned fp32 one does.  The workspace
+ * is gnx_core_backward_workspace_bytes plus the three 256-B aligned fp32 copies; the query builds the CSR view and the wide tables, so call it
+ * outside any capture.  bf16 buffers must be 4-byte aligned (rows of odd width are then 2-byte aligned: the kernels never assume more), else
+ * GNX_ERR_INVALID_ARG; the workspace 16-byte aligned, else GNX_ERR_WORKSPACE; both before anything is written or launched.  No allocation, no
+ * synchronisation.  Not typed (fp32 only): the training-mode pair gnx_core_forward_train / gnx_core_backward_train. */
+GNX_API size_t gnx_core_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem);
+GNX_API int32_t gnx_core_backward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                        const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf,
+                                        void* d_gf, const gnx_core_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- forward: replaces (m::GNCore)(x) (src/gncore.jl:56-68); GNCoreList = caller-side fold (gncorelist.jl:43-45) ----
  * Wide cores (block in the matrix cores' projected form, FeedForward widths 64 / 128): gn1 / gn2 of ef and nf are applied by the
  * kernels as they load x (one pass of row statistics; GNX_FLAG_NO_LN_FUSE materialises the LayerNorms: bit-identical for the node rows and
@@ -537,8 +561,8 @@ GNX_API int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, 
  * tables, run-time specialisations), so call it outside any capture; it returns 0 for an unknown `elem` or GNX_FLAG_DEFER_GRAPH_UPDATE with
  * bf16, both of which gnx_core_forward_typed rejects (GNX_ERR_INVALID_ARG) before any GPU work — as it does a misaligned bf16 buffer and
  * (GNX_ERR_DIMS) dims that the block does not map to themselves, each of them even on a NULL handle.  Every other rule is gnx_core_forward's:
- * NULL rules, status codes, no allocation, no synchronisation, capture-safe.  Not typed (fp32 only): gnx_core_forward_train,
- * gnx_core_backward, gnx_model. */
+ * NULL rules, status codes, no allocation, no synchronisation, capture-safe.  The pullback is gnx_core_backward_typed.  Not typed (fp32 only):
+ * gnx_core_forward_train / gnx_core_backward_train, gnx_model. */
 GNX_API size_t gnx_core_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem, uint32_t flags);
 GNX_API int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                        int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace, size_t workspace_bytes,
