@@ -17,9 +17,11 @@ def gn():
     return gn
 
 
-def _torch_block(p, csc, ef, nf, gf, W, pre=None):
+def _torch_block(p, csc, ef, nf, gf, W, pre=None, acts=None):
     """float64 torch restatement of SURVEY Appendix A (one replica); W = dict of leaf tensors.  `pre` (a list) receives the
-    three pre-activations."""
+    three pre-activations.  (Float32 leaves and inputs give the same restatement in float32, and `acts` — three callables — stands in for
+    the activations of `p`: the yardstick of tests/test_gpu_backward_replicas.py.)"""
+    act_e, act_n, act_g = acts if acts is not None else (ACT[p["act_e"]], ACT[p["act_n"]], ACT[p["act_g"]])
     colptr, rowval, node_off, edge_off = (torch.from_numpy(np.asarray(a)) for a in csc)
     N, G = len(colptr) - 1, len(node_off) - 1
     dst = torch.repeat_interleave(torch.arange(N), colptr[1:] - colptr[:-1])
@@ -28,14 +30,14 @@ def _torch_block(p, csc, ef, nf, gf, W, pre=None):
     cat = lambda parts: torch.cat([q for q in parts if q is not None], dim=1)
     Xe = cat([ef, None if nf is None else nf[rowval], None if nf is None else nf[dst], None if gf is None else gf[eg]])
     ze = Xe @ W["We"].T + W["be"]
-    he = ACT[p["act_e"]](ze)
-    agg = torch.zeros((N, he.shape[1]), dtype=torch.float64).index_add(0, dst, he)
+    he = act_e(ze)
+    agg = torch.zeros((N, he.shape[1]), dtype=he.dtype).index_add(0, dst, he)
     zn = cat([agg, nf, None if gf is None else gf[ng]]) @ W["Wn"].T + W["bn"]
-    hn = ACT[p["act_n"]](zn)
-    se = torch.zeros((G, he.shape[1]), dtype=torch.float64).index_add(0, eg, he)
-    sn = torch.zeros((G, hn.shape[1]), dtype=torch.float64).index_add(0, ng, hn)
+    hn = act_n(zn)
+    se = torch.zeros((G, he.shape[1]), dtype=he.dtype).index_add(0, eg, he)
+    sn = torch.zeros((G, hn.shape[1]), dtype=hn.dtype).index_add(0, ng, hn)
     zg = cat([se, sn, gf]) @ W["Wg"].T + W["bg"]
-    hg = ACT[p["act_g"]](zg)
+    hg = act_g(zg)
     if pre is not None:
         pre.extend([ze, zn, zg])
     return he, hn, hg

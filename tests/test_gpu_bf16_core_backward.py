@@ -216,7 +216,8 @@ def _case(batch, dims, act, seed=0):
     return Case(gn, batch, dims, act, _seed(batch, dims, act, seed))
 
 
-CASES = [(b, d) for b in BATCHES for d in NARROW] + [("one", d) for d in WIDE]
+# one-R3 at width 64: the typed _v4 LayerNorm kernels and k_bf16_widen with replicas (9003 edge rows of three replicas)
+CASES = [(b, d) for b in BATCHES for d in NARROW] + [("one", d) for d in WIDE] + [("one-R3", (64, 64, 64))]
 
 
 @pytest.mark.parametrize("act", ACTS)

@@ -330,8 +330,8 @@ def _torch_core(p, csc, xs, W, Wb, hidden_fn, masks=None):
     return outs
 
 
-def _core_leaves(p):
-    T = lambda v: torch.tensor(v, dtype=torch.float64, requires_grad=True)
+def _core_leaves(p, dtype=torch.float64):
+    T = lambda v: torch.tensor(v, dtype=dtype, requires_grad=True)
     return {k: T(v) for k, v in p.items() if isinstance(v, np.ndarray)}, {k: T(p["block"][k]) for k in ("We", "be", "Wn", "bn", "Wg", "bg")}
 
 

@@ -53,6 +53,42 @@ def packed_inputs(rng, R, E, N, G, dims):
     return ef, nf, gf
 
 
+KINK_MARGIN = 10.0  # in units of RTOL . S: an fp32 evaluation stays within 1 of the float64 value (the forward bound), so within 10 it keeps its sign
+
+
+def relu_kink_rows(p, t, x):
+    """rows of the packed [R][T][d] features `x` of entity t ('e', 'n', 'g') of a GNCore with parameters `p` on which some hidden pre-activation of
+    the FeedForward, z1 = W1 . gn2(x_row) + b1 (float64), lies within KINK_MARGIN . RTOL . S of the relu kink: a boolean [R][T].
+    S = |gn2(x)| . |W1|^T + |b1|, the error scale of a Dense the forward parity tests use (oracle `_scale_rows`), here in float64: an fp32
+    recomputation of z1 within RTOL . S of the float64 value has its sign on every other row."""
+    g2, b2 = p[f"ln2_{t}_gamma"], p[f"ln2_{t}_beta"]
+    W1, b1 = np.asarray(p[f"ff_{t}_W1"], dtype=np.float64), np.asarray(p[f"ff_{t}_b1"], dtype=np.float64)
+    z = O.layernorm(np.asarray(x, dtype=np.float64), g2, b2, p["eps"], p["eps_mode"], axis=-1)
+    return (np.abs(z @ W1.T + b1) <= KINK_MARGIN * RTOL * (np.abs(z) @ np.abs(W1).T + np.abs(b1))).any(axis=-1)
+
+
+def kinkfree_core_inputs(rng, p, R, E, N, G, max_rounds=20):
+    """packed_inputs for a GNCore whose FeedForwards use relu, without a row near a kink.  The core's block has identity activations, so the three
+    hidden pre-activations are the only kinks, and each depends on ONE row of x: draw x as fp32, then redraw (as fp32) every row relu_kink_rows
+    reports until none is left.  Returns ((ef, nf, gf), rounds of redrawing, share of rows redrawn in the first round); AssertionError when rows
+    are left after `max_rounds` rounds.  No case is dropped and no seed is swapped: the condition is asserted by the callers on what is returned."""
+    xs = list(packed_inputs(rng, R, E, N, G, p["dims"]))
+    rounds, first, total = 0, 0, 0
+    for t, x in zip("eng", xs):
+        bad = relu_kink_rows(p, t, x)
+        first, total, k = first + int(bad.sum()), total + bad.size, 0
+        while bad.any():
+            k += 1
+            assert k <= max_rounds, f"entity {t}: {int(bad.sum())} rows still within the kink margin after {max_rounds} rounds"
+            x[bad] = rng.random((int(bad.sum()), x.shape[-1]), dtype=np.float32)
+            again = relu_kink_rows(p, t, x[bad][None])[0]
+            idx = np.argwhere(bad)
+            bad[:] = False
+            bad[tuple(idx[again].T)] = True
+        rounds = max(rounds, k)
+    return tuple(xs), rounds, first / max(total, 1)
+
+
 def to_nt(gn, g, ef, nf, gf):
     """packed numpy [R][T][D] → the batched tuple the layers take (Julia-shaped views of device tensors)."""
     import torch
