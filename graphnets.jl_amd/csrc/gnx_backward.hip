@@ -13,7 +13,7 @@
 // duality of nf[src] is resolved with a CSR view (out-edges per node) instead of atomics; every sum has a fixed order.
 #include <algorithm>
 
-#include "gnx_launchers.h"
+#include "gnx_staging.h"
 #include "gnx_wave_kernel.h"  // ld_feat / st_feat: a bf16 or fp32 element of a feature buffer
 #include "gnx_feat4.h"        // ld_bf16x4, ld_feat4 / st_feat4: four of them
 
@@ -602,8 +602,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   if (BF16 && (bw_mfma_edge(h, p, R) || bw_mfma_node(h, p, R))) return fail(GNX_ERR_INVALID_ARG, "bf16 backward: matrix-core widths take the staging path");
   constexpr size_t kElem = BF16 ? 2 : sizeof(float);  // bytes of a feature element
   const BwLayout L = bw_layout(h, p, R);
-  if (!ws || ws_bytes < L.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_backward_workspace_bytes()");
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  if ((rc = check_ws(ws, ws_bytes, L.total, "workspace missing or smaller than gnx_block_backward_workspace_bytes()"))) return rc;
   rc = gnx_ensure_wide_tables(h, stream);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
   if (rc) return rc;
   rc = gnx_ensure_csr(h);
@@ -756,41 +755,21 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
 }
 
 // workspace of a bf16 backward: gnx_block_backward's, then — native path — the fp32 sum of d_gf, or — staging path — fp32 copies of the nine
-// feature-shaped inputs and the three input gradients; every carve 256-B aligned
+// feature-shaped inputs and the three input gradients (gnx_staging.h); every carve 256-B aligned
 struct TypedBwWs {
-  size_t base, dgf, off[12], n[12], total;
+  Staging st;  // native: copy 0 is the fp32 sum of d_gf; staging: copies 0..8 the inputs, 9..11 the input gradients
   bool native;
 };
 static TypedBwWs typed_bw_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  TypedBwWs w{};
-  w.native = !bw_mfma_edge(h, p, R) && !bw_mfma_node(h, p, R);
-  w.base = bw_layout(h, p, R).total;
-  size_t o = align_up(w.base, 256);
-  if (w.native) {
-    w.dgf = o;
-    w.total = o + align_up(sizeof(float) * (size_t)R * (size_t)h->G * (size_t)std::max(p->dg, 0), 256);
-    return w;
-  }
-  const int64_t rows[3] = {h->E, h->N, h->G};
+  const bool native = !bw_mfma_edge(h, p, R) && !bw_mfma_node(h, p, R);
+  const size_t base = bw_layout(h, p, R).total, dgf = (size_t)R * (size_t)h->G * (size_t)std::max(p->dg, 0);
   const int d[12] = {p->de, p->dn, p->dg, p->oe, p->on, p->og, p->oe, p->on, p->og, p->de, p->dn, p->dg};
-  for (int i = 0; i < 12; ++i) {
-    w.n[i] = (size_t)R * (size_t)rows[i % 3] * (size_t)std::max(d[i], 0);
-    w.off[i] = o;
-    o += align_up(sizeof(float) * w.n[i], 256);
-  }
-  w.total = o;
-  return w;
+  return TypedBwWs{native ? stage_layout(base, &dgf, 1) : stage_features(base, h, R, d, 12), native};
 }
 
-// the feature buffers of a bf16 backward call (gnx_block_backward_typed, gnx_core_backward_typed): n_in inputs and the three input gradients
-// (NULL passes).  Rows of odd width are then 2-byte aligned, which is all the kernels assume.
-static int32_t check_bf16_aligned(const void* const* in, int n_in, void* const out[3]) {
-  for (int i = 0; i < n_in; ++i)
-    if (((uintptr_t)in[i] & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
-  for (int i = 0; i < 3; ++i)
-    if (((uintptr_t)out[i] & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
-  return GNX_OK;
-}
+// the typed entry points' feature pointers as the float* the kernels' arguments are declared with
+static const float* cf(const void* q) { return static_cast<const float*>(q); }
+static float* mf(void* q) { return static_cast<float*>(q); }
 
 }  // namespace gnx
 
@@ -817,15 +796,13 @@ size_t gnx_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_b
   if (elem != GNX_ELEM_BF16 || !h || !p || R <= 0) return 0;
   (void)gnx_ensure_wide_tables(h);  // (as the fp32 query: outside any capture)
   (void)gnx_ensure_csr(h);
-  return typed_bw_ws(h, p, R).total;
+  return typed_bw_ws(h, p, R).st.total;
 }
 
 int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                  const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
                                  const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws,
                                  size_t ws_bytes, void* stream) {
-  auto cf = [](const void* q) { return static_cast<const float*>(q); };
-  auto mf = [](void* q) { return static_cast<float*>(q); };
   if (elem == GNX_ELEM_F32)
     return gnx_block_backward(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf),
                               mf(d_gf), grads, ws, ws_bytes, stream);
@@ -833,29 +810,20 @@ int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_params* p,
   if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
   int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
   if (rc) return rc;
-  const void* in[9] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out};
-  void* out[3] = {d_ef, d_nf, d_gf};
-  if ((rc = check_bf16_aligned(in, 9, out))) return rc;
-  const TypedBwWs w = typed_bw_ws(h, p, R);
-  if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_backward_typed_workspace_bytes()");
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
-  char* base = static_cast<char*>(ws);
-  if (w.native)  // the kernels read and write bf16 themselves (declared float, like the feature pointers of BlockArgs)
+  const void* const bufs[12] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
+  if ((rc = check_bf16_aligned(bufs, 12))) return rc;
+  const TypedBwWs tw = typed_bw_ws(h, p, R);
+  const Staging& w = tw.st;
+  if ((rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_block_backward_typed_workspace_bytes()"))) return rc;
+  if (tw.native)  // the kernels read and write bf16 themselves (declared float, like the feature pointers of BlockArgs)
     return block_backward_t<true>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
-                                  mf(d_nf), mf(d_gf), grads, ws, w.base, stream, reinterpret_cast<float*>(base + w.dgf));
+                                  mf(d_nf), mf(d_gf), grads, ws, w.base, stream, w.at(ws, 0));
   // matrix-core widths: widen into the workspace, the fp32 backward (its own DeviceTurn), round the input gradients
   const hipStream_t s = (hipStream_t)stream;
-  float* st[12];
-  for (int i = 0; i < 12; ++i) st[i] = reinterpret_cast<float*>(base + w.off[i]);
-  for (int i = 0; i < 9; ++i)
-    if (in[i] && w.n[i] > 0 && (rc = launch_bf16_widen(in[i], w.n[i], st[i], s)) != GNX_OK) return rc;
-  auto src = [&](int i) -> const float* { return in[i] && w.n[i] > 0 ? st[i] : nullptr; };
-  auto dst = [&](int i) -> float* { return out[i] && w.n[9 + i] > 0 ? st[9 + i] : nullptr; };
-  rc = gnx_block_backward(h, p, src(0), src(1), src(2), src(3), src(4), src(5), src(6), src(7), src(8), R, dst(0), dst(1), dst(2), grads, ws, w.base, stream);
-  if (rc) return rc;
-  for (int i = 0; i < 3; ++i)
-    if (out[i] && w.n[9 + i] > 0 && (rc = launch_bf16_round(st[9 + i], w.n[9 + i], out[i], s)) != GNX_OK) return rc;
-  return GNX_OK;
+  if ((rc = stage_widen(w, ws, bufs, 0, 9, s))) return rc;
+  auto st = [&](int i) -> float* { return bufs[i] && w.n[i] > 0 ? w.at(ws, i) : nullptr; };  // the copy of a tensor the caller passed
+  rc = gnx_block_backward(h, p, st(0), st(1), st(2), st(3), st(4), st(5), st(6), st(7), st(8), R, st(9), st(10), st(11), grads, ws, w.base, stream);
+  return rc ? rc : stage_round(w, ws, bufs, 9, 12, s);
 }
 
 
@@ -901,22 +869,9 @@ CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64
 }
 // gnx_core_backward_typed, GNX_ELEM_BF16: the fp32 layout, then an fp32 copy of each upstream gradient, every carve 256-B aligned.  (x and d_x
 // need none: the LayerNorm kernels read and write bf16 themselves.)
-struct TypedCoreBwWs {
-  size_t base, off[3], n[3], total;
-};
-TypedCoreBwWs typed_core_bw_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
-  TypedCoreBwWs w{};
-  w.base = core_bw_layout(h, p, R).total;
-  const int64_t rows[3] = {h->E, h->N, h->G};
+Staging typed_core_bw_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
   const int d[3] = {p->block.de, p->block.dn, p->block.dg};
-  size_t o = align_up(w.base, 256);
-  for (int t = 0; t < 3; ++t) {
-    w.n[t] = (size_t)R * (size_t)rows[t] * (size_t)std::max(d[t], 0);
-    w.off[t] = o;
-    o += align_up(sizeof(float) * w.n[t], 256);
-  }
-  w.total = o;
-  return w;
+  return stage_features(core_bw_layout(h, p, R).total, h, R, d, 3);
 }
 }  // namespace
 
@@ -955,16 +910,13 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
   float* dxo[3] = {d_ef, d_nf, d_gf};
   int32_t rc;
   if constexpr (BF16) {
-    const void* in[6] = {ef, nf, gf, g_ef_out, g_nf_out, g_gf_out};
-    void* out[3] = {d_ef, d_nf, d_gf};
-    if ((rc = check_bf16_aligned(in, 6, out))) return rc;
+    const void* const bufs[9] = {ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
+    if ((rc = check_bf16_aligned(bufs, 9))) return rc;
   }
   const CoreBwLayout L = core_bw_layout(h, p, R);
-  const TypedCoreBwWs tw = BF16 ? typed_core_bw_ws(h, p, R) : TypedCoreBwWs{};
-  if (!ws || ws_bytes < (BF16 ? tw.total : L.total))
-    return fail(GNX_ERR_WORKSPACE, BF16 ? "workspace missing or smaller than gnx_core_backward_typed_workspace_bytes()"
-                                        : "workspace missing or smaller than gnx_core_backward_workspace_bytes()");
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  const Staging tw = BF16 ? typed_core_bw_ws(h, p, R) : Staging{};
+  if ((rc = check_ws(ws, ws_bytes, BF16 ? tw.total : L.total, BF16 ? "workspace missing or smaller than gnx_core_backward_typed_workspace_bytes()"
+                                                                   : "workspace missing or smaller than gnx_core_backward_workspace_bytes()"))) return rc;
   if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
   char* base = static_cast<char*>(ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -1126,8 +1078,6 @@ size_t gnx_core_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_co
 int32_t gnx_core_backward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                 const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf,
                                 const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  auto cf = [](const void* q) { return static_cast<const float*>(q); };
-  auto mf = [](void* q) { return static_cast<float*>(q); };
   if (elem == GNX_ELEM_F32)
     return gnx_core_backward(h, p, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream);
   if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
@@ -1219,9 +1169,8 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
   if ((de > 0 && !ef && h->E > 0) || (dn > 0 && !nf) || (dg > 0 && !gf)) return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL");
   if (oe == 0) return fail(GNX_ERR_DIMS, "chain backward: not implemented for an edge function without output (the forward takes it; train such a block with one-layer update functions)");
   const ChainBwLayout L = chain_bw_layout(h, p, R, lnf.ident_floats());
-  if (!ws || ws_bytes < L.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_chain_block_backward_workspace_bytes()");
+  if (int32_t rcc = check_ws(ws, ws_bytes, L.total, "workspace missing or smaller than gnx_chain_block_backward_workspace_bytes()")) return rcc;
   if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   char* base = static_cast<char*>(ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   if (lnf.on) {

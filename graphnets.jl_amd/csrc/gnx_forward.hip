@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "gnx_launchers.h"
+#include "gnx_staging.h"
 #include "gnx_step_hazard.h"
 
 namespace gnx {
@@ -103,8 +103,7 @@ struct Prepared {
     const gnx_block_params* p = c.p;
     if (const int32_t bad = check_call(c)) return bad;
     w = block_ws(h, p, c.R);
-    if (!c.ws || c.ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_workspace_bytes()");
-    if (((uintptr_t)c.ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    if (const int32_t bad = check_ws(c.ws, c.ws_bytes, w.total, "workspace missing or smaller than gnx_block_workspace_bytes()")) return bad;
     a = block_probe(h, p);
     a.We = p->edgefn.weight; a.be = p->edgefn.bias; a.act_e = p->edgefn.act;
     a.Wn = p->nodefn.weight; a.bn = p->nodefn.bias; a.act_n = p->nodefn.act;
@@ -230,31 +229,10 @@ static bool typed_native(const gnx_graphs* h, const gnx_block_params* p, uint32_
   return !(flags & GNX_FLAG_FORCE_GENERIC) && block_narrow_takes(h, block_probe(h, p), s, true);
 }
 
-// workspace of a bf16 call: gnx_block_forward's, then (fallback only) fp32 staging of the six tensors, each carve 256-B aligned
-struct TypedWs {
-  size_t base, off[6], n[6], total;
-};
-static TypedWs typed_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R, bool native) {
-  TypedWs w{};
-  w.base = block_ws(h, p, R).total;
-  const int64_t rows[3] = {h->E, h->N, h->G};
+// workspace of a bf16 call: gnx_block_forward's, then (fallback only) fp32 staging of the six tensors (gnx_staging.h)
+static Staging typed_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R, bool native) {
   const int d[6] = {p->de, p->dn, p->dg, p->oe, p->on, p->og};
-  size_t o = align_up(w.base, 256);
-  for (int i = 0; i < 6; ++i) {
-    w.n[i] = native ? 0 : (size_t)R * (size_t)rows[i % 3] * (size_t)d[i];
-    w.off[i] = o;
-    o += align_up(sizeof(float) * w.n[i], 256);
-  }
-  w.total = native ? w.base : o;
-  return w;
-}
-
-// the six feature buffers of a bf16 call (gnx_block_forward_typed, gnx_core_forward_typed): rows of odd width are then 2-byte aligned, which
-// is all the kernels assume
-static int32_t check_bf16_aligned(const void* const bufs[6]) {
-  for (int i = 0; i < 6; ++i)
-    if (((uintptr_t)bufs[i] & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
-  return GNX_OK;
+  return stage_features(block_ws(h, p, R).total, h, R, d, native ? 0 : 6);
 }
 
 // side stream + fork / join events of the handle (see gnx_internal.h); failure just leaves the core on one stream
@@ -303,6 +281,23 @@ static AuxHold take_aux(const gnx_graphs* h, bool need_step_events) {
     if (lk.owns_lock()) { hold.lock = std::move(lk); hold.set = &ax; break; }
   }
   return hold;
+}
+
+// `side` on the set's stream beside `main` on the caller's stream s.  The join event is recorded even after a failed launch — a capture must not
+// end with the side stream un-joined — and every status is looked at only once both streams have their work.
+template <class Side, class Main>
+static int32_t fork_join(const gnx_graphs::AuxSet* aux, hipStream_t s, Side side, Main main) {
+  GNX_HIP(hipEventRecord(aux->fork, s));
+  GNX_HIP(hipStreamWaitEvent(aux->stream, aux->fork, 0));
+  const int32_t rc = side(aux->stream);
+  const hipError_t e1 = hipEventRecord(aux->join, aux->stream);
+  const int32_t rc2 = main();
+  const hipError_t e2 = hipStreamWaitEvent(s, aux->join, 0);
+  if (rc) return rc;
+  if (rc2) return rc2;
+  GNX_HIP(e1);
+  GNX_HIP(e2);
+  return GNX_OK;
 }
 
 }  // namespace gnx
@@ -354,27 +349,20 @@ int32_t gnx_block_forward_typed(const gnx_graphs* h, const gnx_block_params* p, 
   int32_t rc = check_call(call);
   if (rc) return rc;
   const void* bufs[6] = {ef, nf, gf, ef_out, nf_out, gf_out};
-  if ((rc = check_bf16_aligned(bufs))) return rc;
+  if ((rc = check_bf16_aligned(bufs, 6))) return rc;
   const bool native = typed_native(h, p, flags, s);
-  const TypedWs w = typed_ws(h, p, R, native);
-  if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_block_typed_workspace_bytes()");
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  const Staging w = typed_ws(h, p, R, native);
+  if ((rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_block_typed_workspace_bytes()"))) return rc;
   if (native) {
     DeviceTurn turn(s, false);  // (narrow widths: no matrix instruction)
     call.ws_bytes = w.base;
     return block_plain(call);
   }
   // every other path: widen into the workspace, the fp32 forward (its own dispatch, DeviceTurn included), round the outputs
-  float* st[6];
-  for (int i = 0; i < 6; ++i) st[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + w.off[i]);
-  for (int i = 0; i < 3; ++i)
-    if (w.n[i] > 0 && (rc = launch_bf16_widen(bufs[i], w.n[i], st[i], s)) != GNX_OK) return rc;
-  rc = gnx_block_forward(h, p, p->de ? st[0] : nullptr, p->dn ? st[1] : nullptr, p->dg ? st[2] : nullptr, R, p->oe ? st[3] : nullptr, p->on ? st[4] : nullptr,
-                         p->og ? st[5] : nullptr, ws, w.base, flags, stream);
-  if (rc) return rc;
-  for (int i = 3; i < 6; ++i)
-    if (w.n[i] > 0 && (rc = launch_bf16_round(st[i], w.n[i], const_cast<void*>(bufs[i]), s)) != GNX_OK) return rc;
-  return GNX_OK;
+  if ((rc = stage_widen(w, ws, bufs, 0, 3, s))) return rc;
+  rc = gnx_block_forward(h, p, p->de ? w.at(ws, 0) : nullptr, p->dn ? w.at(ws, 1) : nullptr, p->dg ? w.at(ws, 2) : nullptr, R, p->oe ? w.at(ws, 3) : nullptr,
+                         p->on ? w.at(ws, 4) : nullptr, p->og ? w.at(ws, 5) : nullptr, ws, w.base, flags, stream);
+  return rc ? rc : stage_round(w, ws, bufs, 3, 6, s);
 }
 
 // the graph update a call left pending (gnx_block_graph_update; a flush of the loops below): the kernels of this phase read only gf, the graph
@@ -634,19 +622,35 @@ static int partial_rows_of(const gnx_graphs* h) { return (int)(h->G == 1 ? (h->n
 // FeedForward width from which the two Dense layers run on the matrix cores (hidden activations staged in HBM)
 static bool ffn_on_mfma(int d) { return d >= 32; }
 
-// workspace of a core: LN1 and LN2 outputs for edges, nodes, graphs, the FFN hidden buffer, then the block workspace
-static void core_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, size_t off[8], size_t* total) {
+// Workspace of a core: per entity (edges, nodes, graphs) the outputs of LayerNorm ln1 and ln2, each the size of the entity's rows; the
+// FeedForward's hidden buffer (the two-GEMM form; else scratch of the launch that holds it); then the block's workspace.  A form that never
+// materialises a LayerNorm output uses that region for something else — the named accessors below are every such use:
+struct CoreLayout {
+  size_t ln1[3], ln2[3], hidden, block, total;
+  float* at(void* ws, size_t off) const { return reinterpret_cast<float*>(static_cast<char*>(ws) + off); }
+  float* gn1(void* ws, int t) const { return at(ws, ln1[t]); }
+  float* gn2(void* ws, int t) const { return at(ws, ln2[t]); }
+  // t = 0, 1: the row statistics of ef / nf (2 floats per row) that the matrix-core kernels normalise from on load
+  float* stats(void* ws, int t) const { return gn1(ws, t); }
+  // t = 0, 1: the split weight planes of k_ffn_x6 when that FeedForward normalises on load (gn2 of ef / nf is never written then)
+  float* x6_planes(void* ws, int t) const { return gn2(ws, t); }
+  // the bf16 core: the block's outputs in fp32, exactly the three tensors' sizes (its LayerNorm-on-load block never writes gn1)
+  float* block_out(void* ws, int t) const { return gn1(ws, t); }
+};
+static CoreLayout core_layout(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
   const int d[3] = {p->block.de, p->block.dn, p->block.dg};
+  CoreLayout L{};
   size_t o = 0, hidden = 0;
   for (int t = 0; t < 3; ++t) {
-    off[2 * t] = o; o += align_up(sizeof(float) * rows[t] * d[t], 256);
-    off[2 * t + 1] = o; o += align_up(sizeof(float) * rows[t] * d[t], 256);
+    L.ln1[t] = o; o += align_up(sizeof(float) * rows[t] * d[t], 256);
+    L.ln2[t] = o; o += align_up(sizeof(float) * rows[t] * d[t], 256);
     if (ffn_on_mfma(d[t])) hidden = std::max(hidden, sizeof(float) * rows[t] * 4 * (size_t)d[t]);
   }
-  off[6] = o; o += align_up(hidden, 256);
-  off[7] = o;
-  *total = o + block_ws(h, &p->block, R).total;
+  L.hidden = o; o += align_up(hidden, 256);
+  L.block = o;
+  L.total = o + block_ws(h, &p->block, R).total;
+  return L;
 }
 
 // ---- validation of a core forward (gnx_core_forward, gnx_core_forward_typed), in the order the fp32 entry has always reported it ----
@@ -678,25 +682,123 @@ static int32_t check_core(const gnx_graphs* h, const gnx_core_params* p, const g
   }
   return GNX_OK;
 }
-// the workspace of a core call against `total`, the size its query (`query`: the name for the message) returns
-static int32_t check_core_ws(const void* ws, size_t ws_bytes, size_t total, const char* query) {
-  if (!ws || ws_bytes < total) return fail(GNX_ERR_WORKSPACE, query);
-  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+
+// ---- the GNCore forward: a validated call (CoreRun), what it does (CorePlan: decided before the first launch), the FeedForward step ----
+// The form of an entity's FeedForward + residual: out = block(gn1 x) + x + fc2(act1(fc1(gn2 x)))   (gncore.jl:56-68, gnfeedforward.jl:27-31)
+enum FfForm {
+  FF_DONE,          // the block's edge launch was the edge form of k_ffn_x6: out[0] is final
+  FF_LN_ON_LOAD,    // launch_ffn_fused normalises x as it loads it: from the statistics table, or (edges, inline_e) with the statistics in registers
+  FF_MATERIALISED,  // launch_ffn_fused on gn2(x) in HBM, no scratch (node_mat's node rows)
+  FF_HIDDEN,        // launch_ffn_fused on gn2(x), the hidden buffer its scratch; where it declines, two launch_dense_rows through the hidden buffer
+  FF_POST,          // a narrow width: k_core_post (recomputes gn2)
+  FF_RESIDUAL       // the generic kernel on gn2(x)
+};
+// Every decision of a core forward that its arguments alone determine.  What a LAUNCHER answers — whether the narrow block took the
+// LayerNorm-on-load form and the edge FeedForward, whether k_core_post3 / launch_ffn_fused declined — is consumed where it is returned.
+struct CorePlan {
+  bool all_narrow = false;  // three narrow widths: the fused narrow block is asked to normalise on load; FeedForwards by k_core_post3 / k_core_post
+  bool post3 = false;       // ... and the one-launch post kernel applies: the block is asked to leave its graph update (and take the edge FeedForward)
+  bool wide_ln = false;     // the matrix-core block and FeedForwards normalise ef / nf on load: neither LayerNorm output of them exists in HBM
+  bool inline_e = false, fuse_e = false, ln_on_load = false, node_x6_forms = false, node_mat = false;  // (core_plan)
+  bool may_fork = false;    // the call may take a side stream of the handle
+  FfForm ff[3] = {};
+};
+struct CoreRun {
+  const gnx_graphs* h; const gnx_core_params* p; int64_t R; uint32_t flags;
+  size_t rows[3]; int d[3];            // per entity: rows (all replicas), width
+  const float* x[3]; float* out[3];    // the caller's tensors
+  float *l1[3], *l2[3], *stats[2], *planes[2], *hidden;  // regions of the workspace (CoreLayout)
+  CorePlan plan;
+  int32_t make_plan(const BlockCall& wide, hipStream_t s);
+  int32_t ffn(int t, hipStream_t st) const;
+};
+
+// wide: the core's block as the matrix-core form reads it (asked here, launched by gnx_core_forward)
+int32_t CoreRun::make_plan(const BlockCall& wide, hipStream_t s) {
+  CorePlan& pl = plan;
+  // All three widths narrow: the fused block kernel normalises its inputs as it loads them (gn1 never materialised) when it
+  // is available for this width set; gn2 is recomputed inside k_core_post either way.
+  pl.all_narrow = core_narrow_width(d[0]) && core_narrow_width(d[1]) && core_narrow_width(d[2]) && !(flags & GNX_FLAG_FORCE_GENERIC);
+  // (the graph level of a NARROW core on the handle's side stream — graph update + the G-row / N-row k_core_post launches behind the
+  // edges' k_core_post — was measured: README ex.3 model 298 vs 271 us; two fork/join pairs cost more than the ~20 us they hide)
+  // when the three FeedForwards go out as ONE launch (k_core_post3), the block's graph update runs inside it: the block is launched
+  // without its k_graph_t
+  pl.post3 = pl.all_narrow && h->E > 0 && !(flags & GNX_FLAG_DEFER_GRAPH_UPDATE) && core_post3_applies(rows, d, p->ff, true, s);
+  // Wide edges and nodes: the matrix-core kernels normalise x as they load it (block: gn1, fused FeedForward: gn2) from one pass of
+  // row statistics — neither LayerNorm output of ef / nf exists in HBM.  Taken when the block runs in the projected quad-row form
+  // and both FeedForwards are the fused kernel's; gf (G rows) is normalised by the ordinary kernel.
+  bool edge_x6 = false;
+  if (!pl.all_narrow && !form(GNX_FLAG_NO_LN_FUSE) && !(flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA)) && h->E > 0) {
+    bool ok = true;
+    for (int t = 0; t < 2; ++t)
+      ok = ok && ln_stats_applies(x[t], d[t]) && ffn_fused_applies(x[t], d[t], p->ff[t], out[t], x[t], out[t]) &&
+           (((uintptr_t)p->ln2[t].gamma | (uintptr_t)p->ln2[t].beta) & 15) == 0;
+    if (ok)
+      if (const int32_t rc = block_wide_ln_ask(wide, p->ln1, pl.wide_ln, edge_x6)) return rc;
+  }
+  // Both consumers of the edge rows' statistics hold whole rows in registers when they are the six-term kernels (k_edge_x6: gn1, k_ffn_x6: gn2) and
+  // compute them there, bit-identical to k_ln_stats_v4 (gnx_x6_stats.h): the statistics pass over ef — 512 MB at 1M edges — is not launched.
+  pl.inline_e = pl.wide_ln && edge_x6 && d[0] == 128 && rows[0] >= 4096 && !form(GNX_FLAG_LN_STATS_PASS) &&
+                ffn_x6_applies(x[0], d[0], p->ff[0], out[0], x[0], out[0], sizeof(float) * rows[0] * d[0]);
+  // ... and then ONE launch does both (the edge form of k_ffn_x6: ef' stays in the accumulator — never written, never read back; GNX_CORE_EDGE_SPLIT=1: two launches)
+  pl.fuse_e = pl.inline_e && !form(GNX_FLAG_CORE_EDGE_SPLIT) && !(edge_n_enabled() && d[1] == 64);  // (the opt-in k_edge_n gathers RAW source rows: its projection tables are not the one-launch form's)
+  // Round 6 (profiles/r06_overlap_hazard.log): the GENERAL kernels (k_rows_gemm, k_ffn_fused) came out wrong now and then beside another queue's
+  // matrix kernel, but only in launches that normalise on load from a statistics table; the site was found later in the round (their LayerNorm
+  // branch consumed an LDS read too early on a shared CU) and is guarded (GNX_LN_GUARD).  This rule predates the guard and stays as a second,
+  // independent protection of the path small batches take: a statistics table is consumed by six-term kernels only — an entity whose rows a general
+  // kernel would normalise on load gets its LayerNorms MATERIALISED instead (k_layernorm2, one more pass over rows that are few whenever this
+  // happens: below 4096, or widths without a six-term kernel).  GNX_FLAG_LN_ON_LOAD restores the statistics-table forms (exact too since the guard).
+  pl.ln_on_load = form(GNX_FLAG_LN_ON_LOAD) || form(GNX_FLAG_FP32_MFMA | GNX_FLAG_PROJ_FP32 | GNX_FLAG_LN_STATS_PASS | GNX_FLAG_CORE_EDGE_SPLIT);  // (the diagnostic forms keep their tables)
+  if (pl.wide_ln && !pl.ln_on_load && !pl.inline_e) pl.wide_ln = false;  // the edge rows' table would feed k_rows_gemm / k_ffn_fused: everything materialised
+  pl.node_x6_forms = d[0] == 128 && d[1] == 64 && h->N >= 4096 && p->block.nodefn.act <= GNX_ACT_RELU;  // k_proj_x6, k_node_x6, k_ffn_x6<64> take the node rows
+  pl.node_mat = pl.wide_ln && !pl.ln_on_load && !pl.node_x6_forms;  // edges by the six-term kernels (statistics in registers), node LayerNorms materialised
+  // A side stream is for the matrix-core form alone (the narrow core's measurement above).  GNX_NO_FORK=1, or the per-kernel profiler on:
+  // everything on the caller's stream.
+  pl.may_fork = pl.wide_ln && !form(GNX_FLAG_NO_FORK) && !profile_enabled();
+  for (int t = 0; t < 3; ++t) {
+    if (ffn_on_mfma(d[t]) && !(flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA)))
+      pl.ff[t] = !(pl.wide_ln && t < 2) ? FF_HIDDEN : (t == 0 && pl.fuse_e) ? FF_DONE : (t == 1 && pl.node_mat) ? FF_MATERIALISED : FF_LN_ON_LOAD;
+    else
+      pl.ff[t] = core_narrow_width(d[t]) && !(flags & GNX_FLAG_FORCE_GENERIC) ? FF_POST : FF_RESIDUAL;
+  }
   return GNX_OK;
+}
+
+// The FeedForward + residual of entity t on stream st, in the form the plan names: the one copy of this dispatch.
+int32_t CoreRun::ffn(int t, hipStream_t st) const {
+  const gnx_ffn& ff = p->ff[t];
+  switch (plan.ff[t]) {
+    case FF_DONE: return GNX_OK;
+    case FF_LN_ON_LOAD: {  // (the entity's gn2 region is unused in this form: room for the split weight planes of k_ffn_x6)
+      const bool inl = t == 0 && plan.inline_e;
+      return launch_ffn_fused(h, t, x[t], d[t], ff, out[t], x[t], out[t], R, st, inl ? nullptr : stats[t], &p->ln2[t], planes[t], sizeof(float) * rows[t] * d[t], inl, p->eps,
+                              p->eps_mode);
+    }
+    case FF_MATERIALISED: return launch_ffn_fused(h, t, l2[t], d[t], ff, out[t], x[t], out[t], R, st);
+    case FF_HIDDEN: {
+      // hidden layer never leaves the chip (d = 64, 128); the edges' and nodes' launch may use the hidden buffer of the two-GEMM form as its scratch.
+      // Not the G rows': their FeedForward may be the side stream's, where the hidden buffer belongs to its two-GEMM form alone.
+      int32_t rc = launch_ffn_fused(h, t, l2[t], d[t], ff, out[t], x[t], out[t], R, st, nullptr, nullptr, t < 2 ? hidden : nullptr, sizeof(float) * rows[t] * 4 * (size_t)d[t]);
+      if (rc != 1) return rc;
+      if ((rc = launch_dense_rows(h, t, l2[t], d[t], ff.fc1, 4 * d[t], nullptr, nullptr, hidden, R, st, "k_rows_gemm_ff1"))) return rc;
+      return launch_dense_rows(h, t, hidden, 4 * d[t], ff.fc2, d[t], out[t], x[t], out[t], R, st, "k_rows_gemm_ff2");
+    }
+    case FF_POST: return launch_core_post(x[t], rows[t], d[t], p->ln2[t], ff, p->eps, p->eps_mode, out[t], st);
+    case FF_RESIDUAL: break;
+  }
+  return launch_ffn_residual(l2[t], x[t], rows[t], d[t], ff, out[t], st);
 }
 
 size_t gnx_core_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
   if (!h || !p || R <= 0) return 0;
   ensure_aux(h);
   warm_block_wide(h, &p->block, ffn_on_mfma(p->block.de) || ffn_on_mfma(p->block.dn) || ffn_on_mfma(p->block.dg));
-  size_t off[8], total;
-  core_ws(h, p, R, off, &total);
   {  // run-time specialisation of a narrow core's combined FeedForward launch happens here (as for the block: never in a capture)
     const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
     const int d[3] = {p->block.de, p->block.dn, p->block.dg};
     if (h->E > 0 && core_narrow_width(d[0]) && core_narrow_width(d[1]) && core_narrow_width(d[2])) (void)core_post3_applies(rows, d, p->ff, true, nullptr);
   }
-  return total;
+  return core_layout(h, p, R).total;
 }
 
 int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const float* ef, const float* nf, const float* gf,
@@ -711,199 +813,99 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
   PreparedScope prepared(p->prepared);
   int32_t rc = check_core(h, p, b, R, ef, nf, gf, ef_out, nf_out, gf_out, flags);
   if (rc) return rc;
-  size_t off[8], total;
-  core_ws(h, p, R, off, &total);
-  if ((rc = check_core_ws(ws, ws_bytes, total, "workspace missing or smaller than gnx_core_workspace_bytes()"))) return rc;
-  char* base = static_cast<char*>(ws);
-  const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
-  const int d[3] = {b.de, b.dn, b.dg};
-  const float* x[3] = {ef, nf, gf};
-  float* out[3] = {ef_out, nf_out, gf_out};
-  float* l1[3];
-  float* l2[3];
-  for (int t = 0; t < 3; ++t) {
-    l1[t] = reinterpret_cast<float*>(base + off[2 * t]);
-    l2[t] = reinterpret_cast<float*>(base + off[2 * t + 1]);
-  }
-  // All three widths narrow: the fused block kernel normalises its inputs as it loads them (gn1 never materialised) when it
-  // is available for this width set; gn2 is recomputed inside k_core_post either way.
-  bool fused_ln = false, defer_gu = false, edge_ff_done = false;
-  NarrowLnResult narrow;
+  const CoreLayout L = core_layout(h, p, R);
+  if ((rc = check_ws(ws, ws_bytes, L.total, "workspace missing or smaller than gnx_core_workspace_bytes()"))) return rc;
+  CoreRun c{h, p, R, flags, {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G}, {b.de, b.dn, b.dg}, {ef, nf, gf}, {ef_out, nf_out, gf_out}};
+  for (int t = 0; t < 3; ++t) { c.l1[t] = L.gn1(ws, t); c.l2[t] = L.gn2(ws, t); }
+  for (int t = 0; t < 2; ++t) { c.stats[t] = L.stats(ws, t); c.planes[t] = L.x6_planes(ws, t); }
+  c.hidden = L.at(ws, L.hidden);
+  const size_t* rows = c.rows;
+  const int* d = c.d;
+  const float* const* x = c.x;
   // the core's block as the forms see it; every call below is this one on its own inputs, stream and phase
-  const BlockCall blk{h, &b, GNX_ELEM_F32, ef, nf, gf, R, out[0], out[1], out[2], base + off[7], ws_bytes - off[7], flags, s, GNX_PHASE_ALL};
-  const bool all_narrow = core_narrow_width(d[0]) && core_narrow_width(d[1]) && core_narrow_width(d[2]) && !(flags & GNX_FLAG_FORCE_GENERIC);
-  if (all_narrow) {
-    // (the graph level of a NARROW core on the handle's side stream — graph update + the G-row / N-row k_core_post launches behind the
-    // edges' k_core_post — was measured: README ex.3 model 298 vs 271 us; two fork/join pairs cost more than the ~20 us they hide)
-    // when the three FeedForwards go out as ONE launch (k_core_post3), the block's graph update runs inside it: the block is launched
-    // without its k_graph_t
-    defer_gu = h->E > 0 && !(flags & GNX_FLAG_DEFER_GRAPH_UPDATE) && core_post3_applies(rows, d, p->ff, true, s);
+  const BlockCall blk{h, &b, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, static_cast<char*>(ws) + L.block, ws_bytes - L.block, flags, s, GNX_PHASE_ALL};
+  BlockCall wide = blk.with(ef, nf, c.l1[2]);  // the matrix-core form reads ef and nf raw (normalised on load) and gf normalised
+  if ((rc = c.make_plan(wide, s))) return rc;
+  const CorePlan& pl = c.plan;
+
+  // ---- LayerNorms / statistics, then the block ----
+  NarrowLnResult narrow;  // the narrow block's answers: it normalised on load (took); the edge FeedForward ran in its edge lanes (ffe_took)
+  // A side stream and its pair of events from the handle's pool, held while this call enqueues its work (a second host thread in this section —
+  // same handle, another stream, other buffers — takes the next set; with every set taken a caller runs everything on its own stream).
+  const AuxHold hold = pl.may_fork ? take_aux(h, false) : AuxHold{};
+  const gnx_graphs::AuxSet* aux = hold.set;
+  if (pl.all_narrow) {
     // (the FeedForward moves into the block kernel only together with the one-launch post kernel, which then skips the edge rows)
-    rc = block_narrow_ln(blk.on(s, defer_gu ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL), p->ln1, p->eps, p->eps_mode, defer_gu ? &p->ff[0] : nullptr, p->ln2[0], narrow);
+    rc = block_narrow_ln(blk.on(s, pl.post3 ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL), p->ln1, p->eps, p->eps_mode, pl.post3 ? &p->ff[0] : nullptr, p->ln2[0], narrow);
     if (rc) return rc;
-    fused_ln = narrow.took; edge_ff_done = narrow.ffe_took;
-    defer_gu = defer_gu && fused_ln;
   }
-  // Wide edges and nodes: the matrix-core kernels normalise x as they load it (block: gn1, fused FeedForward: gn2) from one pass of
-  // row statistics — neither LayerNorm output of ef / nf exists in HBM.  Taken when the block runs in the projected quad-row form
-  // and both FeedForwards are the fused kernel's; gf (G rows) is normalised by the ordinary kernel.
-  const bool no_ln_fuse = form(GNX_FLAG_NO_LN_FUSE);
-  bool wide_ln = false, edge_x6 = false;
-  BlockCall wide = blk.with(x[0], x[1], l1[2]);  // the matrix-core form reads ef and nf raw (normalised on load) and gf normalised
-  if (!fused_ln && !all_narrow && !no_ln_fuse && !(flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA)) && h->E > 0) {
-    bool ok = true;
-    for (int t = 0; t < 2; ++t)
-      ok = ok && ln_stats_applies(x[t], d[t]) && ffn_fused_applies(x[t], d[t], p->ff[t], out[t], x[t], out[t]) &&
-           (((uintptr_t)p->ln2[t].gamma | (uintptr_t)p->ln2[t].beta) & 15) == 0;
-    if (ok) {
-      rc = block_wide_ln_ask(wide, p->ln1, wide_ln, edge_x6);
-      if (rc) return rc;
-    }
-  }
-  // Both consumers of the edge rows' statistics hold whole rows in registers when they are the six-term kernels (k_edge_x6: gn1, k_ffn_x6: gn2) and
-  // compute them there, bit-identical to k_ln_stats_v4 (gnx_x6_stats.h): the statistics pass over ef — 512 MB at 1M edges — is not launched.
-  const bool inline_e = wide_ln && edge_x6 && d[0] == 128 && rows[0] >= 4096 && !form(GNX_FLAG_LN_STATS_PASS) &&
-                        ffn_x6_applies(x[0], d[0], p->ff[0], out[0], x[0], out[0], sizeof(float) * rows[0] * d[0]);
-  // ... and then ONE launch does both (the edge form of k_ffn_x6: ef' stays in the accumulator — never written, never read back; GNX_CORE_EDGE_SPLIT=1: two launches)
-  const bool fuse_e = inline_e && !form(GNX_FLAG_CORE_EDGE_SPLIT) && !(edge_n_enabled() && d[1] == 64);  // (the opt-in k_edge_n gathers RAW source rows: its projection tables are not the one-launch form's)
-  // Round 6 (profiles/r06_overlap_hazard.log): the GENERAL kernels (k_rows_gemm, k_ffn_fused) came out wrong now and then beside another queue's
-  // matrix kernel, but only in launches that normalise on load from a statistics table; the site was found later in the round (their LayerNorm
-  // branch consumed an LDS read too early on a shared CU) and is guarded (GNX_LN_GUARD).  This rule predates the guard and stays as a second,
-  // independent protection of the path small batches take: a statistics table is consumed by six-term kernels only — an entity whose rows a general
-  // kernel would normalise on load gets its LayerNorms MATERIALISED instead (k_layernorm2, one more pass over rows that are few whenever this
-  // happens: below 4096, or widths without a six-term kernel).  GNX_FLAG_LN_ON_LOAD restores the statistics-table forms (exact too since the guard).
-  const bool ln_on_load = form(GNX_FLAG_LN_ON_LOAD) || form(GNX_FLAG_FP32_MFMA | GNX_FLAG_PROJ_FP32 | GNX_FLAG_LN_STATS_PASS | GNX_FLAG_CORE_EDGE_SPLIT);  // (the diagnostic forms keep their tables)
-  if (wide_ln && !ln_on_load && !inline_e) wide_ln = false;  // the edge rows' table would feed k_rows_gemm / k_ffn_fused: everything materialised (the branch below)
-  const bool node_x6_forms = d[0] == 128 && d[1] == 64 && h->N >= 4096 && p->block.nodefn.act <= GNX_ACT_RELU;  // k_proj_x6, k_node_x6, k_ffn_x6<64> take the node rows
-  const bool node_mat = wide_ln && !ln_on_load && !node_x6_forms;  // edges by the six-term kernels (statistics in registers), node LayerNorms materialised
-  if (wide_ln) {
-    const float* stats[2] = {l1[0], node_mat ? nullptr : l1[1]};  // the (unused) gn1 buffers hold the statistics: 2 floats per row
-    wide.nf = node_mat ? l1[1] : x[1];                           // node_mat: gn1(nf) itself (and l2[1] = gn2(nf) for the FeedForward)
+  const float* const stats[2] = {c.stats[0], pl.node_mat ? nullptr : c.stats[1]};  // what the matrix-core block normalises ef / nf from (NULL: used as it is)
+  if (pl.wide_ln) {
+    wide.nf = pl.node_mat ? c.l1[1] : x[1];  // node_mat: gn1(nf) itself (and l2[1] = gn2(nf) for the FeedForward)
     auto node_ln = [&](hipStream_t st) -> int32_t {
-      return node_mat ? launch_layernorm2(x[1], rows[1], d[1], p->ln1[1], p->ln2[1], p->eps, p->eps_mode, l1[1], l2[1], st)
-                      : launch_ln_stats(x[1], rows[1], d[1], p->eps, p->eps_mode, l1[1], st);
+      return pl.node_mat ? launch_layernorm2(x[1], rows[1], d[1], p->ln1[1], p->ln2[1], p->eps, p->eps_mode, c.l1[1], c.l2[1], st)
+                         : launch_ln_stats(x[1], rows[1], d[1], p->eps, p->eps_mode, c.stats[1], st);
     };
-    auto node_ffn = [&](hipStream_t st) -> int32_t {  // out[1] = nf' + nf + FF(gn2(nf))
-      return node_mat ? launch_ffn_fused(h, 1, l2[1], d[1], p->ff[1], out[1], x[1], out[1], R, st)
-                      : launch_ffn_fused(h, 1, x[1], d[1], p->ff[1], out[1], x[1], out[1], R, st, l1[1], &p->ln2[1], l2[1], sizeof(float) * rows[1] * d[1]);
-    };
-    const bool no_fork0 = form(GNX_FLAG_NO_FORK);
-    // A side stream and its pair of events from the handle's pool, held while this call enqueues its work (a second host thread in this section —
-    // same handle, another stream, other buffers — takes the next set; with every set taken a caller runs everything on its own stream).
-    const AuxHold hold = !no_fork0 && !profile_enabled() ? take_aux(h, false) : AuxHold{};
-    const gnx_graphs::AuxSet* aux = hold.set;
-    const bool fork0 = aux != nullptr;
-    if ((rc = launch_layernorm2(x[2], rows[2], d[2], p->ln1[2], p->ln2[2], p->eps, p->eps_mode, l1[2], l2[2], s))) return rc;
-    if (fork0) {
+    auto edge_stats = [&]() -> int32_t { return pl.inline_e ? GNX_OK : launch_ln_stats(x[0], rows[0], d[0], p->eps, p->eps_mode, c.stats[0], s); };
+    if ((rc = launch_layernorm2(x[2], rows[2], d[2], p->ln1[2], p->ln2[2], p->eps, p->eps_mode, c.l1[2], c.l2[2], s))) return rc;
+    if (aux) {
       // side stream: node statistics, gf fold, node projections (latency / matrix-core work) beside the edge statistics pass (HBM-bound)
-      hipStream_t ax = aux->stream;
-      bool took0 = false;
-      GNX_HIP(hipEventRecord(aux->fork, s));
-      GNX_HIP(hipStreamWaitEvent(ax, aux->fork, 0));
-      rc = node_ln(ax);
-      if (rc == GNX_OK) rc = block_wide_ln_run(wide.on(ax, GNX_PHASE_WIDE_PROJ_ONLY), p->ln1, p->eps, p->eps_mode, stats, WideLnEdges{}, took0);
-      const hipError_t e1 = hipEventRecord(aux->join, ax);
-      const int32_t rc2 = inline_e ? GNX_OK : launch_ln_stats(x[0], rows[0], d[0], p->eps, p->eps_mode, l1[0], s);
-      const hipError_t e2 = hipStreamWaitEvent(s, aux->join, 0);
-      if (rc) return rc;
-      if (rc2) return rc2;
-      GNX_HIP(e1);
-      GNX_HIP(e2);
+      auto node_side = [&](hipStream_t ax) -> int32_t {
+        bool took0 = false;
+        const int32_t r = node_ln(ax);
+        return r ? r : block_wide_ln_run(wide.on(ax, GNX_PHASE_WIDE_PROJ_ONLY), p->ln1, p->eps, p->eps_mode, stats, WideLnEdges{}, took0);
+      };
+      if ((rc = fork_join(aux, s, node_side, edge_stats))) return rc;
     } else {
-      if (!inline_e && (rc = launch_ln_stats(x[0], rows[0], d[0], p->eps, p->eps_mode, l1[0], s))) return rc;
+      if ((rc = edge_stats())) return rc;
       if ((rc = node_ln(s))) return rc;
     }
-    // The graph level of the core — the block's graph update (four 5-us launches) and the G-row FeedForward — is independent of the edge /
-    // node FeedForwards that follow the block: it runs on the handle's side stream behind them (fork after the node update, join
-    // before returning; inside a capture the side stream joins the captured graph).  GNX_NO_FORK=1: everything on the caller's stream.
-    const bool no_fork = no_fork0;
-    const bool fork = !no_fork && aux != nullptr;
+    // (two streams: the block's graph update is left to the side stream, below; the node projections are done)
     bool took = false;
-    const WideLnEdges edges{inline_e, fuse_e ? &p->ff[0] : nullptr, fuse_e ? &p->ln2[0] : nullptr, fuse_e ? l2[0] : nullptr};
-    rc = block_wide_ln_run(wide.on(s, (fork ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL) | (fork0 ? GNX_PHASE_WIDE_PROJ_DONE : 0)), p->ln1, p->eps, p->eps_mode, stats, edges, took);
+    const WideLnEdges edges{pl.inline_e, pl.fuse_e ? &p->ff[0] : nullptr, pl.fuse_e ? &p->ln2[0] : nullptr, pl.fuse_e ? c.planes[0] : nullptr};
+    rc = block_wide_ln_run(wide.on(s, aux ? GNX_PHASE_EDGE_NODE | GNX_PHASE_WIDE_PROJ_DONE : GNX_PHASE_ALL), p->ln1, p->eps, p->eps_mode, stats, edges, took);
     if (rc) return rc;
     if (!took) return fail(GNX_ERR_INVALID_ARG, "gnx_core_forward: the block declined the form it had accepted");
-    if (fork) {
-      hipStream_t ax = aux->stream;
-      GNX_HIP(hipEventRecord(aux->fork, s));
-      GNX_HIP(hipStreamWaitEvent(ax, aux->fork, 0));
-      rc = block_wide_ln_run(wide.on(ax, GNX_PHASE_GRAPH), p->ln1, p->eps, p->eps_mode, stats, WideLnEdges{}, took);
-      if (rc == GNX_OK) {  // the G-row FeedForward: out = gf' + gf + FF(gn2(gf)); the hidden buffer is its alone (the wide FeedForwards are the fused kernel)
-        float* hidden2 = reinterpret_cast<float*>(base + off[6]);
-        rc = launch_ffn_fused(h, 2, l2[2], d[2], p->ff[2], out[2], x[2], out[2], R, ax);
-        if (rc == 1) {
-          if (ffn_on_mfma(d[2])) {
-            rc = launch_dense_rows(h, 2, l2[2], d[2], p->ff[2].fc1, 4 * d[2], nullptr, nullptr, hidden2, R, ax, "k_rows_gemm_ff1");
-            if (rc == GNX_OK) rc = launch_dense_rows(h, 2, hidden2, 4 * d[2], p->ff[2].fc2, d[2], out[2], x[2], out[2], R, ax, "k_rows_gemm_ff2");
-          } else if (core_narrow_width(d[2])) {
-            rc = launch_core_post(x[2], rows[2], d[2], p->ln2[2], p->ff[2], p->eps, p->eps_mode, out[2], ax);
-          } else {
-            rc = launch_ffn_residual(l2[2], x[2], rows[2], d[2], p->ff[2], out[2], ax);
-          }
-        }
-      }
-      // the node FeedForward rides on the side stream too: its workgroups fill the CUs that the edge FeedForward's last, partly
-      // filled round of tiles leaves idle (7813 tiles on 512 slots: 15.26 rounds)
-      static const bool node_ffn_main = getenv("GNX_NODE_FFN_MAIN") != nullptr;
-      if (rc == GNX_OK && !node_ffn_main) rc = node_ffn(ax);
-      // the join is recorded even after a failure: a capture must not end with the side stream un-joined
-      const hipError_t e1 = hipEventRecord(aux->join, ax);
-      // (the edges' gn2 buffer is unused in this form: room for the split weight planes of k_ffn_x6)
-      int32_t rc2 = fuse_e ? GNX_OK  // (the block's edge launch was the edge form of k_ffn_x6: out[0] is final)
-                           : launch_ffn_fused(h, 0, x[0], d[0], p->ff[0], out[0], x[0], out[0], R, s, inline_e ? nullptr : l1[0], &p->ln2[0], l2[0], sizeof(float) * rows[0] * d[0], inline_e,
-                                              p->eps, p->eps_mode);
-      if (rc2 == GNX_OK && node_ffn_main) rc2 = node_ffn(s);
-      const hipError_t e2 = hipStreamWaitEvent(s, aux->join, 0);
-      if (rc) return rc;
-      if (rc2) return rc2;
-      GNX_HIP(e1);
-      GNX_HIP(e2);
-      return GNX_OK;
-    }
-  } else if (!fused_ln) {
+  } else if (!narrow.took) {
     for (int t = 0; t < 3; ++t) {
-      // narrow widths: only gn1(x) is materialised (the block needs it); gn2 is recomputed inside k_core_post
-      const bool narrow = core_narrow_width(d[t]) && !(flags & GNX_FLAG_FORCE_GENERIC);
-      if (narrow) rc = launch_ln1_rows(x[t], rows[t], d[t], p->ln1[t], p->eps, p->eps_mode, l1[t], s);
-      else rc = launch_layernorm2(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, l1[t], l2[t], s);
+      // narrow widths (FeedForward by k_core_post, which recomputes gn2): only gn1(x) is materialised (the block needs it)
+      if (pl.ff[t] == FF_POST) rc = launch_ln1_rows(x[t], rows[t], d[t], p->ln1[t], p->eps, p->eps_mode, c.l1[t], s);
+      else rc = launch_layernorm2(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, c.l1[t], c.l2[t], s);
       if (rc) return rc;
     }
-    rc = block_plain(blk.with(l1[0], l1[1], l1[2]));  // everything materialised: the plain block on gn1(x)
+    rc = block_plain(blk.with(c.l1[0], c.l1[1], c.l1[2]));  // everything materialised: the plain block on gn1(x)
     if (rc) return rc;
   }
-  float* hidden = reinterpret_cast<float*>(base + off[6]);
-  if (all_narrow) {  // the three entities' FeedForward + residual in one launch when the width triple has the combined kernel
-    const int n_rows = partial_rows_of(h);
-    rc = launch_core_post3(x, rows, d, p->ln2, p->ff, p->eps, p->eps_mode, out, s, defer_gu ? &narrow.args : nullptr, n_rows, edge_ff_done);
+
+  // ---- FeedForward + residual per entity ----
+  if (pl.all_narrow) {  // the three entities' FeedForward + residual in one launch when the width triple has the combined kernel
+    const bool defer_gu = pl.post3 && narrow.took;  // ... with the graph update the block left
+    rc = launch_core_post3(x, rows, d, p->ln2, p->ff, p->eps, p->eps_mode, c.out, s, defer_gu ? &narrow.args : nullptr, partial_rows_of(h), narrow.ffe_took);
     if (rc != 1) return rc;
-    if (edge_ff_done) return fail(GNX_ERR_INVALID_ARG, "internal: the edge FeedForward ran in the block kernel but the one-launch post kernel declined");
+    if (narrow.ffe_took) return fail(GNX_ERR_INVALID_ARG, "internal: the edge FeedForward ran in the block kernel but the one-launch post kernel declined");
   }
-  for (int t = 0; t < 3; ++t) {
-    if (ffn_on_mfma(d[t]) && !(flags & (GNX_FLAG_FORCE_GENERIC | GNX_FLAG_NO_MFMA))) {
-      // out = block(LN1 x) + x + fc2(relu(fc1(LN2 x)))      (gncore.jl:56-68, gnfeedforward.jl:27-31)
-      if (wide_ln && t < 2) {
-        const bool inl = t == 0 && inline_e;
-        if (t == 0 && fuse_e) continue;  // (the block's edge launch was the edge form of k_ffn_x6: out[0] is final)
-        if (t == 1 && node_mat) {        // (materialised node LayerNorms: gn2(nf) is in l2[1])
-          if ((rc = launch_ffn_fused(h, 1, l2[1], d[1], p->ff[1], out[1], x[1], out[1], R, s))) return rc;
-          continue;
-        }
-        if ((rc = launch_ffn_fused(h, t, x[t], d[t], p->ff[t], out[t], x[t], out[t], R, s, inl ? nullptr : l1[t], &p->ln2[t], l2[t], sizeof(float) * rows[t] * d[t], inl, p->eps, p->eps_mode))) return rc;
-        continue;
-      }
-      // hidden layer never leaves the chip (d = 64, 128); the edges' launch may use the hidden buffer of the two-GEMM form as its scratch
-      rc = launch_ffn_fused(h, t, l2[t], d[t], p->ff[t], out[t], x[t], out[t], R, s, nullptr, nullptr, t < 2 ? hidden : nullptr, sizeof(float) * rows[t] * 4 * (size_t)d[t]);
-      if (rc == GNX_OK) continue;
-      if (rc != 1) return rc;
-      if ((rc = launch_dense_rows(h, t, l2[t], d[t], p->ff[t].fc1, 4 * d[t], nullptr, nullptr, hidden, R, s, "k_rows_gemm_ff1"))) return rc;
-      if ((rc = launch_dense_rows(h, t, hidden, 4 * d[t], p->ff[t].fc2, d[t], out[t], x[t], out[t], R, s, "k_rows_gemm_ff2"))) return rc;
-    } else if (core_narrow_width(d[t]) && !(flags & GNX_FLAG_FORCE_GENERIC)) {
-      if ((rc = launch_core_post(x[t], rows[t], d[t], p->ln2[t], p->ff[t], p->eps, p->eps_mode, out[t], s))) return rc;
-    } else if ((rc = launch_ffn_residual(l2[t], x[t], rows[t], d[t], p->ff[t], out[t], s))) {
-      return rc;
-    }
+  if (!aux) {
+    for (int t = 0; t < 3; ++t)
+      if ((rc = c.ffn(t, s))) return rc;
+    return GNX_OK;
   }
-  return GNX_OK;
+  // Two streams.  The graph level of the core — the block's graph update (four 5-us launches) and the G-row FeedForward — is independent of the
+  // edge / node FeedForwards that follow the block: it runs on the handle's side stream beside them (fork after the node update, join
+  // before returning; inside a capture the side stream joins the captured graph).
+  // The node FeedForward rides on the side stream too: its workgroups fill the CUs that the edge FeedForward's last, partly filled round of
+  // tiles leaves idle (7813 tiles on 512 slots: 15.26 rounds).
+  static const bool node_ffn_main = getenv("GNX_NODE_FFN_MAIN") != nullptr;
+  auto graph_side = [&](hipStream_t ax) -> int32_t {
+    bool took = false;
+    int32_t r = block_wide_ln_run(wide.on(ax, GNX_PHASE_GRAPH), p->ln1, p->eps, p->eps_mode, stats, WideLnEdges{}, took);
+    if (r == GNX_OK) r = c.ffn(2, ax);
+    return r == GNX_OK && !node_ffn_main ? c.ffn(1, ax) : r;
+  };
+  auto edge_main = [&]() -> int32_t {
+    const int32_t r = c.ffn(0, s);
+    return r == GNX_OK && node_ffn_main ? c.ffn(1, s) : r;
+  };
+  return fork_join(aux, s, graph_side, edge_main);
 }
 
 // ---- bfloat16 features (gnx_core_forward_typed) ----
@@ -916,26 +918,11 @@ static bool core_typed_native(const gnx_graphs* h, const gnx_core_params* p, uin
   return p->block.og == 3 && narrow_bf16_ln_aot(h, block_probe(h, &p->block));
 }
 
-// workspace of a bf16 core call: gnx_core_forward's, then (fallback only) fp32 copies of the six tensors, each carve 256-B aligned.  The native
-// path stages the block's three outputs in fp32 too, but in the gn1 regions of the fp32 layout (core_ws: off[0], off[2], off[4] — exactly
-// the three tensors' sizes), which the LayerNorm-on-load form never writes: no byte beyond the fp32 core's workspace.
-struct CoreTypedWs {
-  size_t base, off[6], n[6], total;
-};
-static CoreTypedWs core_typed_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool native) {
-  CoreTypedWs w{};
-  size_t o8[8];
-  core_ws(h, p, R, o8, &w.base);
-  const int64_t rows[3] = {h->E, h->N, h->G};
-  const int d[3] = {p->block.de, p->block.dn, p->block.dg};
-  size_t o = align_up(w.base, 256);
-  for (int i = 0; i < 6; ++i) {
-    w.n[i] = native ? 0 : (size_t)R * (size_t)rows[i % 3] * (size_t)d[i % 3];
-    w.off[i] = o;
-    o += align_up(sizeof(float) * w.n[i], 256);
-  }
-  w.total = native ? w.base : o;
-  return w;
+// workspace of a bf16 core call: gnx_core_forward's, then (fallback only) fp32 copies of the six tensors (gnx_staging.h).  The native path
+// stages the block's three outputs in fp32 too, but inside the fp32 layout (CoreLayout::block_out): no byte beyond the fp32 core's workspace.
+static Staging core_typed_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool native) {
+  const int d[6] = {p->block.de, p->block.dn, p->block.dg, p->block.de, p->block.dn, p->block.dg};
+  return stage_features(core_layout(h, p, R).total, h, R, d, native ? 0 : 6);
 }
 
 // The native path (validated call, core_typed_native): the fp32 narrow core's launches on bf16 rows.  The block normalises the bf16 rows as it
@@ -945,16 +932,13 @@ static CoreTypedWs core_typed_ws(const gnx_graphs* h, const gnx_core_params* p, 
 // no edge-sized staging is written — then k_core_post3 with the graph update inside; else the block whole, then k_core_post per entity.
 static int32_t core_forward_bf16_native(const gnx_graphs* h, const gnx_core_params* p, const gnx_block_params& b, const void* const x[3], int64_t R, void* const out[3],
                                         void* ws, size_t ws_bytes, uint32_t flags, hipStream_t s) {
-  size_t off[8], total;
-  core_ws(h, p, R, off, &total);
-  char* base = static_cast<char*>(ws);
-  float* st[3];
-  for (int t = 0; t < 3; ++t) st[t] = reinterpret_cast<float*>(base + off[2 * t]);
+  const CoreLayout L = core_layout(h, p, R);
+  float* const st[3] = {L.block_out(ws, 0), L.block_out(ws, 1), L.block_out(ws, 2)};
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
   const int d[3] = {b.de, b.dn, b.dg};
   const bool post3 = core_post3_applies(rows, d, p->ff, true, s);
   const int phase = post3 ? GNX_PHASE_EDGE_NODE : GNX_PHASE_ALL;
-  Prepared q(BlockCall{h, &b, GNX_ELEM_BF16, x[0], x[1], x[2], R, st[0], st[1], st[2], base + off[7], ws_bytes - off[7], flags, s, phase});
+  Prepared q(BlockCall{h, &b, GNX_ELEM_BF16, x[0], x[1], x[2], R, st[0], st[1], st[2], static_cast<char*>(ws) + L.block, ws_bytes - L.block, flags, s, phase});
   if (q.rc) return q.rc;
   BlockArgs& a = q.a;
   for (int t = 0; t < 3; ++t) { a.ln_g[t] = p->ln1[t].gamma; a.ln_b[t] = p->ln1[t].beta; }
@@ -1007,7 +991,7 @@ int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_params* p, in
   // what needs no handle comes first: every refusal below happens before any GPU work
   if (!p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
   const void* bufs[6] = {ef, nf, gf, ef_out, nf_out, gf_out};
-  int32_t rc = check_bf16_aligned(bufs);
+  int32_t rc = check_bf16_aligned(bufs, 6);
   if (rc) return rc;
   if ((rc = check_core_dims(p->block))) return rc;
   if (!h) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
@@ -1017,8 +1001,8 @@ int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_params* p, in
   b.prepared = p->prepared;
   if ((rc = check_core(h, p, b, R, ef, nf, gf, ef_out, nf_out, gf_out, flags))) return rc;
   const bool native = core_typed_native(h, p, flags);
-  const CoreTypedWs w = core_typed_ws(h, p, R, native);
-  if ((rc = check_core_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_core_typed_workspace_bytes()"))) return rc;
+  const Staging w = core_typed_ws(h, p, R, native);
+  if ((rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_core_typed_workspace_bytes()"))) return rc;
   if (native) {
     DeviceTurn turn(s, false);  // (narrow widths: no matrix instruction)
     PreparedScope prepared(p->prepared);
@@ -1027,16 +1011,11 @@ int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_params* p, in
     return core_forward_bf16_native(h, p, b, x, R, out, ws, w.base, flags, s);
   }
   // every other path: widen into the workspace, the fp32 core (its own dispatch, DeviceTurn included), round the outputs
-  float* st[6];
-  for (int i = 0; i < 6; ++i) st[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + w.off[i]);
-  for (int i = 0; i < 3; ++i)
-    if (w.n[i] > 0 && (rc = launch_bf16_widen(bufs[i], w.n[i], st[i], s)) != GNX_OK) return rc;
+  if ((rc = stage_widen(w, ws, bufs, 0, 3, s))) return rc;
   // (a batch without edges: its empty edge buffers may be NULL, for the fp32 core too)
-  rc = gnx_core_forward(h, p, w.n[0] ? st[0] : nullptr, st[1], st[2], R, w.n[3] ? st[3] : nullptr, st[4], st[5], ws, w.base, flags, stream);
-  if (rc) return rc;
-  for (int i = 3; i < 6; ++i)
-    if (w.n[i] > 0 && (rc = launch_bf16_round(st[i], w.n[i], const_cast<void*>(bufs[i]), s)) != GNX_OK) return rc;
-  return GNX_OK;
+  rc = gnx_core_forward(h, p, w.n[0] ? w.at(ws, 0) : nullptr, w.at(ws, 1), w.at(ws, 2), R, w.n[3] ? w.at(ws, 3) : nullptr, w.at(ws, 4), w.at(ws, 5), ws, w.base, flags,
+                        stream);
+  return rc ? rc : stage_round(w, ws, bufs, 3, 6, s);
 }
 
 int32_t gnx_row_stats(const float* x, int64_t rows, int32_t d, float eps, int32_t eps_mode, float* stats, void* stream) {

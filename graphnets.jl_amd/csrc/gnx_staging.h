@@ -1,0 +1,64 @@
+// Host plumbing the entry points of gnx_forward.hip and gnx_backward.hip share: the workspace and bf16-alignment checks of a call, and the
+// staging of a bf16 call that converts around an fp32 path (widen into the workspace, run fp32, round the outputs).  No kernel here.
+#pragma once
+#include <algorithm>
+
+#include "gnx_launchers.h"
+
+namespace gnx {
+
+// the workspace of a call against `total`, the size its query returns (`message`: "workspace missing or smaller than <that query>()")
+inline int32_t check_ws(const void* ws, size_t ws_bytes, size_t total, const char* message) {
+  if (!ws || ws_bytes < total) return fail(GNX_ERR_WORKSPACE, message);
+  if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+  return GNX_OK;
+}
+
+// the feature buffers of a bf16 call (NULL passes): rows of odd width are then 2-byte aligned, which is all the kernels assume
+inline int32_t check_bf16_aligned(const void* const* bufs, int n) {
+  for (int i = 0; i < n; ++i)
+    if (((uintptr_t)bufs[i] & 3) != 0) return fail(GNX_ERR_INVALID_ARG, "bf16 feature buffers must be 4-byte aligned");
+  return GNX_OK;
+}
+
+// fp32 copies of up to 12 tensors behind a base layout (the fp32 path's own workspace, bytes [0, base)), each carve 256-B aligned
+struct Staging {
+  size_t base, off[12], n[12], total;  // n: elements of copy i (0: absent)
+  float* at(void* ws, int i) const { return reinterpret_cast<float*>(static_cast<char*>(ws) + off[i]); }
+};
+// k == 0: a call that stages nothing (a native bf16 path) — its workspace is the base layout's, to the byte
+inline Staging stage_layout(size_t base_total, const size_t* counts, int k) {
+  Staging w{};
+  w.base = base_total;
+  size_t o = align_up(base_total, 256);
+  for (int i = 0; i < k; ++i) {
+    w.n[i] = counts[i];
+    w.off[i] = o;
+    o += align_up(sizeof(float) * counts[i], 256);
+  }
+  w.total = k ? o : base_total;
+  return w;
+}
+// ... of feature tensors: copy i has the rows of entity i % 3 (edges, nodes, graphs; times R) and width[i] columns
+inline Staging stage_features(size_t base_total, const gnx_graphs* h, int64_t R, const int* width, int k) {
+  const int64_t rows[3] = {h->E, h->N, h->G};
+  size_t counts[12];
+  for (int i = 0; i < k; ++i) counts[i] = (size_t)R * (size_t)rows[i % 3] * (size_t)std::max(width[i], 0);
+  return stage_layout(base_total, counts, k);
+}
+// widen bufs[first, last) into their copies / round the copies back into bufs[first, last); a NULL buffer or an empty tensor is skipped
+inline int32_t stage_widen(const Staging& st, void* ws, const void* const* bufs, int first, int last, hipStream_t s) {
+  for (int i = first; i < last; ++i)
+    if (bufs[i] && st.n[i] > 0)
+      if (const int32_t rc = launch_bf16_widen(bufs[i], st.n[i], st.at(ws, i), s)) return rc;
+  return GNX_OK;
+}
+// (the outputs stand in the caller's one list of buffers, which is const for its inputs' sake)
+inline int32_t stage_round(const Staging& st, void* ws, const void* const* bufs, int first, int last, hipStream_t s) {
+  for (int i = first; i < last; ++i)
+    if (bufs[i] && st.n[i] > 0)
+      if (const int32_t rc = launch_bf16_round(st.at(ws, i), st.n[i], const_cast<void*>(bufs[i]), s)) return rc;
+  return GNX_OK;
+}
+
+}  // namespace gnx

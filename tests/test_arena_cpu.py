@@ -302,7 +302,7 @@ ALIGNMENT_TEST = re.compile(r"\bal16\(|(?:\(uintptr_t\)|\(al\b)[^;{}]*?&\s*(?:15
 # file -> number of source lines holding a pointer-alignment test.  Each of them picks a kernel form (or refuses a call) by the address of a
 # caller's buffer; tests/test_gpu_alignment.py runs both sides of them.
 ALIGNMENT_SITES = {
-    "gnx_backward.hip": 8,       # launch_delta's `al`; the typed entry's bf16 checks; four workspace checks; the core backward's al16
+    "gnx_backward.hip": 2,       # launch_delta's `al`; the core backward's al16 (its entry points' checks: gnx_staging.h)
     "gnx_backward_wide.hip": 2,  # k_dw_gemm's and the segmented sums' v4
     "gnx_chain.cpp": 1,          # workspace
     "gnx_dropout.hip": 2,        # the quad / scalar mask kernel; workspace
@@ -310,7 +310,8 @@ ALIGNMENT_SITES = {
     "gnx_edge_x6.hip": 10,       # proj_x6_applies, node_x6_applies and the launchers' refusals
     "gnx_ffn_fused.hip": 2,      # ffn_fused_applies; the LayerNorm-on-load refusal
     "gnx_ffn_x6.hip": 5,         # ffn_x6_applies and the launchers' refusals
-    "gnx_forward.hip": 6,        # workspace and bf16 checks of the entry points; the core's wide_ln decision
+    "gnx_forward.hip": 2,        # the typed loop's bf16 check of every step; the core's wide_ln decision (the other entry checks: gnx_staging.h)
+    "gnx_staging.h": 2,          # check_ws and check_bf16_aligned: the workspace / bf16 checks of every entry point of gnx_forward.hip and gnx_backward.hip
     "gnx_generic.hip": 3,        # ln_stats_applies, launch_ln_stats, launch_layernorm2's al16
     "gnx_wide.hip": 17,          # al16 itself, out_vec, launch_gemm's g.vec and refusals, wide_plan
 }
