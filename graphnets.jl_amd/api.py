@@ -883,9 +883,13 @@ class GNBlock:
     """`GNBlock(in => out; dropout=0)` (gnblock.jl:47-61).  `block(x)` = gnblock.jl:63-69 via gnx_block_forward.
 
     `bf16_backward` (also a plain attribute): lets a differentiable call on bfloat16 features run — gnx_block_backward_typed is its pullback,
-    the input gradients come back rounded to bfloat16, the weight / bias gradients in float32.  Off (the default) such a call raises."""
+    the input gradients come back rounded to bfloat16, the weight / bias gradients in float32.  Off (the default) such a call raises.
 
-    def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False):
+    `fused_backward` (also a plain attribute): the pullback of a float32 call is gnx_block_backward_fused — at the narrow width sets it covers the
+    edge level runs in one kernel; the input gradients and the node / graph parameter gradients keep gnx_block_backward's bits, the edge
+    function's weight / bias gradient is summed in another fixed order.  Elsewhere, and on bfloat16 features, nothing changes."""
+
+    def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -898,6 +902,7 @@ class GNBlock:
         self.dropout = dropout  # stored, never applied by the forward (gnblock.jl:63-69)
         self.flags = 0
         self.bf16_backward = bool(bf16_backward)
+        self.fused_backward = bool(fused_backward)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1110,11 +1115,14 @@ class _BlockFn(torch.autograd.Function):
         grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None)
                                   for w, b in zip(gW, gb)])
         with torch.cuda.device(dev):
-            nb = lib.gnx_block_backward_workspace_bytes(g._h, C.byref(p), R)
+            fused = getattr(block, "fused_backward", False)  # (GNBlock.fused_backward: the narrow edge level in one kernel)
+            query, call = (lib.gnx_block_backward_fused_workspace_bytes, lib.gnx_block_backward_fused) if fused else \
+                          (lib.gnx_block_backward_workspace_bytes, lib.gnx_block_backward)
+            nb = query(g._h, C.byref(p), R)
             ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-            check(lib.gnx_block_backward(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_),
-                                         _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
-                                         torch.cuda.current_stream(dev).cuda_stream))
+            check(call(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_),
+                       _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
+                       torch.cuda.current_stream(dev).cuda_stream))
         gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
         return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
 

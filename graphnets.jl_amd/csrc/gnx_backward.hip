@@ -295,17 +295,20 @@ static void launch_bw_dx(dim3 grid, hipStream_t s, const float* delta, const flo
 struct BwLayout {
   size_t Xe, Xn, Xg, de_, dn_, dg_, dXe, dXn, dXg, part, wt, off2, ssrc, sdst, sg, tnf, total;
 };
-static BwLayout bw_layout(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+// fused (gnx_block_backward_fused where it applies): the edge level is k_bw_edge_wave — no Xe and no delta_e region, dXe holds the compact
+// dXe_c [R*E][2 dn + dg], and `part` also fits the kernel's partial rows
+static BwLayout bw_layout(const gnx_graphs* h, const gnx_block_params* p, int64_t R, bool fused = false) {
   const size_t E = h->E, N = h->N, G = h->G;
   const size_t Ke = p->de + 2 * p->dn + p->dg, Kn = p->oe + p->dn + p->dg, Kg = p->oe + p->on + p->dg;
   BwLayout L{};
   size_t o = 0;
   auto take = [&](size_t floats) { const size_t at = o; o += align_up(floats * sizeof(float), 256); return at; };
-  L.Xe = take(R * E * Ke); L.Xn = take(R * N * Kn); L.Xg = take(R * G * Kg);
-  L.de_ = take(R * E * p->oe); L.dn_ = take(R * N * p->on); L.dg_ = take(R * G * p->og);
-  L.dXe = take(R * E * Ke); L.dXn = take(R * N * Kn); L.dXg = take(R * G * Kg);
+  L.Xe = take(fused ? 0 : R * E * Ke); L.Xn = take(R * N * Kn); L.Xg = take(R * G * Kg);
+  L.de_ = take(fused ? 0 : R * E * p->oe); L.dn_ = take(R * N * p->on); L.dg_ = take(R * G * p->og);
+  L.dXe = take(R * E * (fused ? Ke - p->de : Ke)); L.dXn = take(R * N * Kn); L.dXg = take(R * G * Kg);
   const size_t ch_e = (R * E + BW_CH - 1) / BW_CH, ch_n = (R * N + BW_CH - 1) / BW_CH, ch_g = (R * G + BW_CH - 1) / BW_CH;
-  const size_t pmax = std::max({ch_e * p->oe * (Ke + 1), ch_n * p->on * (Kn + 1), ch_g * p->og * (Kg + 1)});
+  const size_t pe = fused ? (size_t)R * bw_edge_wave_rows(h) : ch_e;  // rows of the edge level's weight-gradient partials
+  const size_t pmax = std::max({pe * p->oe * (Ke + 1), ch_n * p->on * (Kn + 1), ch_g * p->og * (Kg + 1)});
   const size_t cs = std::max((size_t)R * G * 256, (size_t)2048) * std::max({p->oe, p->on, 1});  // column-sum slices
   const size_t pm = std::max(dw_mfma_partial_floats(R * E, p->oe, (int)Ke), dw_mfma_partial_floats(R * N, p->on, (int)Kn));
   L.part = take(std::max({pmax, cs, pm}));
@@ -591,7 +594,7 @@ template <bool BF16>
 static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
                                 const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
                                 const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
-                                void* ws, size_t ws_bytes, void* stream, float* dgf_acc) {
+                                void* ws, size_t ws_bytes, void* stream, float* dgf_acc, bool fused = false) {
   hipStream_t s = (hipStream_t)stream;
   if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
   DeviceTurn turn(s, matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
@@ -601,8 +604,9 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   const int acts[3] = {p->edgefn.act, p->nodefn.act, p->graphfn.act};
   if (BF16 && (bw_mfma_edge(h, p, R) || bw_mfma_node(h, p, R))) return fail(GNX_ERR_INVALID_ARG, "bf16 backward: matrix-core widths take the staging path");
   constexpr size_t kElem = BF16 ? 2 : sizeof(float);  // bytes of a feature element
-  const BwLayout L = bw_layout(h, p, R);
-  if ((rc = check_ws(ws, ws_bytes, L.total, "workspace missing or smaller than gnx_block_backward_workspace_bytes()"))) return rc;
+  const BwLayout L = bw_layout(h, p, R, fused);
+  if ((rc = check_ws(ws, ws_bytes, L.total, fused ? "workspace missing or smaller than gnx_block_backward_fused_workspace_bytes()"
+                                                  : "workspace missing or smaller than gnx_block_backward_workspace_bytes()"))) return rc;
   rc = gnx_ensure_wide_tables(h, stream);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
   if (rc) return rc;
   rc = gnx_ensure_csr(h);
@@ -645,7 +649,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   };
   // function inputs, exactly as the forward's building blocks define them
   { ProfScope ps("bw_fn_inputs", s);
-  if (oe && E && !mfma_e && (rc = launch_fn_input(h, 0, ef, de, nf, dn, gf, dg, R, Xe, s, BF16))) return rc;
+  if (oe && E && !mfma_e && !fused && (rc = launch_fn_input(h, 0, ef, de, nf, dn, gf, dg, R, Xe, s, BF16))) return rc;
   if (on && (rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s, BF16))) return rc; }
   if (og) {  // Xg = [sum_e ef' ; sum_n nf' ; gf] with parallel two-stage column sums (one workgroup per graph would walk 1M rows)
     colsum(ef_out, oe, oe, 0, E, h->d_edge_off, me, Xg, Kg, 0, 0, BF16);
@@ -679,7 +683,19 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   }
   // edge level
   const bool have_e = oe > 0 && E > 0;
-  if (have_e) {
+  if (have_e && fused) {  // delta, dXe and the weight-gradient partials of a wave tile in registers and LDS (gnx_backward_narrow.hip)
+    const bool want_dw = gr.edgefn.weight || gr.edgefn.bias;
+    dxe_stride = 2 * dn + dg; dxe_col0 = de;
+    BwEdgeWave a{ef, nf, gf, g_ef_out, ef_out, have_g ? dXg : nullptr, Kg, have_n ? dXn : nullptr, Kn, p->edgefn.weight, acts[0],
+                 de ? d_ef : nullptr, (d_nf && dn) || (d_gf && dg) ? dXe : nullptr, want_dw ? part : nullptr,
+                 h->d_wtiles, (int)h->n_wtiles(), h->d_rowval, h->d_edge_dst, N, E, G};
+    { ProfScope ps("bw_delta_edge", s);
+    if ((rc = launch_bw_edge_wave(p, a, R, s))) return rc; }
+    if (want_dw) {
+      ProfScope ps("bw_dw_generic", s);
+      GNX_LAUNCH(k_bw_dw_final, dim3(oe * (Ke + 1)), dim3(256), 0, s, part, (int)(R * (int64_t)bw_edge_wave_rows(h)), oe, Ke, gr.edgefn.weight, gr.edgefn.bias);
+    }
+  } else if (have_e) {
     preact(0, Xe, p->edgefn, (size_t)R * E, Ke, oe, dlt_e);
     DeltaArgs a{g_ef_out, acts[0] == GNX_ACT_GELU ? dlt_e : ef_out, dlt_e, have_g ? dXg : nullptr, Kg, 0, have_n ? dXn : nullptr, Kn, 0, h->d_edge_off, h->d_edge_dst, oe, E, G, acts[0], 2};
     { ProfScope ps("bw_delta_edge", s);
@@ -789,6 +805,31 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
                            const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
                            void* ws, size_t ws_bytes, void* stream) {
   return block_backward_t<false>(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr);
+}
+
+int32_t gnx_block_backward_fused_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  if (!h || !p || R <= 0 || (R > 1 && h->G != 1) || R > 65535) return 0;
+  if (p->de < 0 || p->dn < 0 || p->dg < 0 || p->oe <= 0 || p->on < 0 || p->og < 0) return 0;
+  if (h->E <= 0 || h->n_wtiles() <= 0 || !h->d_wtiles) return 0;
+  if (!bw_edge_wave_has(p->de, p->dn, p->dg, p->oe)) return 0;
+  if (p->edgefn.act == GNX_ACT_GELU) return 0;  // (its pre-activation would have to be recomputed bit for bit)
+  return bw_mfma_edge(h, p, R) ? 0 : 1;
+}
+
+size_t gnx_block_backward_fused_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  if (!gnx_block_backward_fused_applies(h, p, R)) return gnx_block_backward_workspace_bytes(h, p, R);
+  (void)gnx_ensure_wide_tables(h);  // (as the generic query: outside any capture)
+  (void)gnx_ensure_csr(h);
+  return bw_layout(h, p, R, true).total;
+}
+
+int32_t gnx_block_backward_fused(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
+                                 const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
+                                 const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
+                                 void* ws, size_t ws_bytes, void* stream) {
+  const bool fused = gnx_block_backward_fused_applies(h, p, R) != 0;
+  return block_backward_t<false>(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr,
+                                 fused);
 }
 
 size_t gnx_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {

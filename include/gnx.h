@@ -446,6 +446,24 @@ GNX_API int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_pa
                                          const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads,
                                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* gnx_block_backward with the edge level of narrow width sets in ONE kernel: a wavefront per wave tile of the handle keeps an edge's input row,
+ * its delta and its dXe row in registers — the edge function's input Xe and delta_e are never written, d_ef is written once, and only the
+ * 2 dn + dg columns of dXe that d_nf / d_gf sum reach the workspace; the weight / bias gradient of the edge function is summed per tile (edge
+ * order), per workgroup (wave order), then by the generic final reduction: fixed orders, no atomics, bitwise reproducible.
+ * gnx_block_backward_fused_applies: 1 where the fused edge level runs — (de, dn, dg) => oe one of (10,5,0)=>3, (3,4,5)=>3, (0,2,0)=>2, (2,2,2)=>2,
+ * (4,3,2)=>3 (any on / og), E > 0, an edge activation other than gelu, and the edge level not on the matrix cores — else 0 (also for a NULL
+ * handle or params).  Where it does not apply, the call IS gnx_block_backward (same bits in every output) and the query returns
+ * gnx_block_backward_workspace_bytes.  Where it applies: d_ef, d_nf, d_gf and every node / graph parameter gradient are bit for bit
+ * gnx_block_backward's; grads->edgefn.weight / .bias are the same sums in another fixed order.  The workspace has a layout of its own (no Xe, no
+ * delta_e, the compact dXe), smaller than the generic one on all but tiny graphs: size it with the fused query.  Arguments, NULL rules,
+ * validation and status codes are gnx_block_backward's; buffers need 4-byte alignment only.  No allocation, no synchronisation. */
+GNX_API int32_t gnx_block_backward_fused_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas);
+GNX_API size_t gnx_block_backward_fused_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas);
+GNX_API int32_t gnx_block_backward_fused(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
+                                 const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out,
+                                 const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef, float* d_nf,
+                                 float* d_gf, const gnx_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the Chain block: takes the forward's INPUTS and the upstream gradients (NULL = zero); every layer's output is recomputed
  * into the workspace.  Gradients w.r.t. the inputs (optional) and, per chain, one gnx_dense_grad per layer (host arrays of n_layers
  * entries, or NULL; entries' pointers optional), all OVERWRITTEN.  The tail layers and the node / graph chains are row-wise Dense
