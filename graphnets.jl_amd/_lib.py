@@ -160,6 +160,10 @@ SIGNATURES = {
     "gnx_block_backward_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(BlockParams), C.c_int64, C.c_int32]),
     "gnx_block_backward_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32] + [_fp] * 9 + [C.c_int64] + [_fp] * 3 +
                                  [C.POINTER(BlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnx_block_backward_fused_typed_applies": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int64, C.c_int32]),
+    "gnx_block_backward_fused_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(BlockParams), C.c_int64, C.c_int32]),
+    "gnx_block_backward_fused_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32] + [_fp] * 9 + [C.c_int64] + [_fp] * 3 +
+                                       [C.POINTER(BlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_core_backward_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int64]),
     "gnx_core_backward": (C.c_int32, [C.c_void_p, C.c_void_p] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_core_backward_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

@@ -887,7 +887,9 @@ class GNBlock:
 
     `fused_backward` (also a plain attribute): the pullback of a float32 call is gnx_block_backward_fused — at the narrow width sets it covers the
     edge level runs in one kernel; the input gradients and the node / graph parameter gradients keep gnx_block_backward's bits, the edge
-    function's weight / bias gradient is summed in another fixed order.  Elsewhere, and on bfloat16 features, nothing changes."""
+    function's weight / bias gradient is summed in another fixed order.  Elsewhere nothing changes.  With `bf16_backward` on as well, the
+    pullback of a bfloat16 call is gnx_block_backward_fused_typed: the fused edge level reading and writing bfloat16 where it applies (the
+    input gradients and the node / graph parameter gradients keep gnx_block_backward_typed's bits), gnx_block_backward_typed elsewhere."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
@@ -1128,7 +1130,8 @@ class _BlockFn(torch.autograd.Function):
 
 
 class _BlockBf16Fn(torch.autograd.Function):
-    """_BlockFn on bfloat16 features (GNBlock.bf16_backward): forward = gnx_block_forward_typed, backward = gnx_block_backward_typed.  The six
+    """_BlockFn on bfloat16 features (GNBlock.bf16_backward): forward = gnx_block_forward_typed, backward = gnx_block_backward_typed
+    (gnx_block_backward_fused_typed with GNBlock.fused_backward).  The six
     saved tensors are bf16; the input gradients come back in bf16 (rounded once from the fp32 pullback at the rounded saved outputs), the
     weight / bias gradients in fp32 in _BlockFn's layout."""
 
@@ -1184,11 +1187,14 @@ class _BlockBf16Fn(torch.autograd.Function):
         grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None)
                                   for w, b in zip(gW, gb)])
         with torch.cuda.device(dev):
-            nb = lib.gnx_block_backward_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16)
+            fused = getattr(block, "fused_backward", False)  # (GNBlock.fused_backward: the narrow edge level in one kernel)
+            query, call = (lib.gnx_block_backward_fused_typed_workspace_bytes, lib.gnx_block_backward_fused_typed) if fused else \
+                          (lib.gnx_block_backward_typed_workspace_bytes, lib.gnx_block_backward_typed)
+            nb = query(g._h, C.byref(p), R, _lib.ELEM_BF16)
             ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-            check(lib.gnx_block_backward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge),
-                                               _ptr(gn_), _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
-                                               torch.cuda.current_stream(dev).cuda_stream))
+            check(call(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge),
+                       _ptr(gn_), _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
+                       torch.cuda.current_stream(dev).cuda_stream))
         gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
         return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
 

@@ -590,6 +590,8 @@ static bool bw_mfma_node(const gnx_graphs* h, const gnx_block_params* p, int64_t
 // gnx_block_backward.  BF16 (gnx_block_backward_typed on its native path: neither level on the matrix cores): the nine feature-shaped inputs and
 // d_ef / d_nf point to bfloat16 — declared float like the feature pointers of BlockArgs, the kernels read them as the element type of the
 // launch — and d_gf, which several launches accumulate, is built in `dgf_acc` (R * G * dg floats) and rounded once at the end.
+// BF16 and fused (gnx_block_backward_fused_typed where it applies): the edge level is k_bw_edge_wave_bf16; dXe_c, the partial rows and everything
+// behind them are the fp32 fused call's.
 template <bool BF16>
 static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
                                 const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
@@ -690,7 +692,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
                  de ? d_ef : nullptr, (d_nf && dn) || (d_gf && dg) ? dXe : nullptr, want_dw ? part : nullptr,
                  h->d_wtiles, (int)h->n_wtiles(), h->d_rowval, h->d_edge_dst, N, E, G};
     { ProfScope ps("bw_delta_edge", s);
-    if ((rc = launch_bw_edge_wave(p, a, R, s))) return rc; }
+    if ((rc = launch_bw_edge_wave(p, a, R, s, BF16))) return rc; }
     if (want_dw) {
       ProfScope ps("bw_dw_generic", s);
       GNX_LAUNCH(k_bw_dw_final, dim3(oe * (Ke + 1)), dim3(256), 0, s, part, (int)(R * (int64_t)bw_edge_wave_rows(h)), oe, Ke, gr.edgefn.weight, gr.edgefn.bias);
@@ -776,9 +778,10 @@ struct TypedBwWs {
   Staging st;  // native: copy 0 is the fp32 sum of d_gf; staging: copies 0..8 the inputs, 9..11 the input gradients
   bool native;
 };
-static TypedBwWs typed_bw_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+// fused (gnx_block_backward_fused_typed where it applies, which implies native): the fused layout in front
+static TypedBwWs typed_bw_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R, bool fused = false) {
   const bool native = !bw_mfma_edge(h, p, R) && !bw_mfma_node(h, p, R);
-  const size_t base = bw_layout(h, p, R).total, dgf = (size_t)R * (size_t)h->G * (size_t)std::max(p->dg, 0);
+  const size_t base = bw_layout(h, p, R, fused).total, dgf = (size_t)R * (size_t)h->G * (size_t)std::max(p->dg, 0);
   const int d[12] = {p->de, p->dn, p->dg, p->oe, p->on, p->og, p->oe, p->on, p->og, p->de, p->dn, p->dg};
   return TypedBwWs{native ? stage_layout(base, &dgf, 1) : stage_features(base, h, R, d, 12), native};
 }
@@ -865,6 +868,40 @@ int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_params* p,
   auto st = [&](int i) -> float* { return bufs[i] && w.n[i] > 0 ? w.at(ws, i) : nullptr; };  // the copy of a tensor the caller passed
   rc = gnx_block_backward(h, p, st(0), st(1), st(2), st(3), st(4), st(5), st(6), st(7), st(8), R, st(9), st(10), st(11), grads, ws, w.base, stream);
   return rc ? rc : stage_round(w, ws, bufs, 9, 12, s);
+}
+
+int32_t gnx_block_backward_fused_typed_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
+  if (elem == GNX_ELEM_F32) return gnx_block_backward_fused_applies(h, p, R);
+  if (elem != GNX_ELEM_BF16 || !gnx_block_backward_fused_applies(h, p, R)) return 0;
+  return bw_mfma_edge(h, p, R) || bw_mfma_node(h, p, R) ? 0 : 1;  // (the typed call's native path: the kernels read and write bf16 themselves)
+}
+
+size_t gnx_block_backward_fused_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
+  if (elem == GNX_ELEM_F32) return gnx_block_backward_fused_workspace_bytes(h, p, R);
+  if (!gnx_block_backward_fused_typed_applies(h, p, R, elem)) return gnx_block_backward_typed_workspace_bytes(h, p, R, elem);
+  (void)gnx_ensure_wide_tables(h);  // (as the fp32 query: outside any capture)
+  (void)gnx_ensure_csr(h);
+  return typed_bw_ws(h, p, R, true).st.total;
+}
+
+int32_t gnx_block_backward_fused_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                       const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
+                                       const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  if (elem == GNX_ELEM_F32)
+    return gnx_block_backward_fused(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
+                                    mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream);
+  if (!gnx_block_backward_fused_typed_applies(h, p, R, elem))  // (also: a bad elem, a NULL handle or params — refused there with its statuses)
+    return gnx_block_backward_typed(h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
+                                    stream);
+  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
+  if (rc) return rc;
+  const void* const bufs[12] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
+  if ((rc = check_bf16_aligned(bufs, 12))) return rc;
+  const Staging w = typed_bw_ws(h, p, R, true).st;
+  if ((rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_block_backward_fused_typed_workspace_bytes()"))) return rc;
+  return block_backward_t<true>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
+                                mf(d_nf), mf(d_gf), grads, ws, w.base, stream, w.at(ws, 0), true);
 }
 
 

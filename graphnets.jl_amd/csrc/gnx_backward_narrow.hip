@@ -10,13 +10,25 @@
 // partial[r][workgroup][P] in the pair order of k_bw_dw_partial, which k_bw_dw_final finishes.  No atomics, every sum in a fixed order.
 //
 // delta and dXe are computed by the operations of k_bw_delta (kind 2) and k_bw_dx in their order, so d_ef and dXe_c carry the bits of the
-// generic form; only the weight / bias gradient is summed in another order.  One form for every address: dword accesses only.
+// generic form; only the weight / bias gradient is summed in another order.
+//
+// Element type (BF16: gnx_block_backward_fused_typed, GNX_ELEM_BF16): ef, nf, gf, g_ef_out, ef_out and d_ef hold bfloat16 — declared float in
+// BwEdgeWave like the feature pointers of BlockArgs.  A bf16 element is widened on load (exact) and d_ef is rounded to nearest even once on
+// store; dXg, dXn, We, dXe_c, the LDS rows, the partial rows and every instruction between load and store are the fp32 kernel's.  One form for
+// every address: fp32 tensors by dword accesses, bf16 tensors by one 16-bit access per element of the lane's own row (ld_feat / st_feat, as
+// the generic typed kernels) — a lane never touches the other half of a dword, so rows that start in the middle of one need no special case.
+// The body is one template; the fp32 kernel keeps its name and its four width parameters, the bf16 kernel is k_bw_edge_wave_bf16.
 #include "gnx_launchers.h"
+#include "gnx_wave_kernel.h"  // ld_feat / st_feat, feat
 
 namespace gnx {
 
-template <int DE, int DN, int DG, int OE>
-__global__ __launch_bounds__(256) void k_bw_edge_wave(BwEdgeWave a) {
+// one element of a typed row
+__device__ __forceinline__ float ld_row(const float* p, size_t i) { return p[i]; }
+__device__ __forceinline__ float ld_row(const bf16_t* p, size_t i) { return bf16_lo(p[i]); }
+
+template <int DE, int DN, int DG, int OE, bool BF16>
+__device__ __forceinline__ void bw_edge_wave(BwEdgeWave a) {
   constexpr int KE = DE + 2 * DN + DG, CW = 2 * DN + DG, P = OE * (KE + 1);
   constexpr int LD = (OE + KE) | 1;  // odd row length: the lanes' row writes fall on 64 different banks
   static_assert(P <= 64, "one lane per (k, j) pair");
@@ -34,9 +46,9 @@ __global__ __launch_bounds__(256) void k_bw_edge_wave(BwEdgeWave a) {
   if (wt < a.n_wtiles) {  // wave-uniform
     const Tile t = a.wtiles[wt];
     float* const rows = s_rows[wave];
-    const float* const ef = a.ef + r * (size_t)a.E * DE;
-    const float* const nf = a.nf + r * (size_t)a.N * DN;
-    const float* const gfr = a.gf + (r * (size_t)a.G + t.g) * DG;
+    const auto* const ef = feat<BF16>(a.ef) + r * (size_t)a.E * DE;  // (float or bf16_t rows)
+    const auto* const nf = feat<BF16>(a.nf) + r * (size_t)a.N * DN;
+    const auto* const gfr = feat<BF16>(a.gf) + (r * (size_t)a.G + t.g) * DG;
     const float* const dxg = a.dXg ? a.dXg + (r * (size_t)a.G + t.g) * a.Kg : nullptr;
     for (int c0 = t.e0; c0 < t.e1; c0 += 64) {
       const int cnt = min(64, t.e1 - c0);
@@ -46,26 +58,26 @@ __global__ __launch_bounds__(256) void k_bw_edge_wave(BwEdgeWave a) {
       const int src = a.rowval[e], dst = a.edge_dst[e];
       float x[KE], d[OE];
 #pragma unroll
-      for (int k = 0; k < DE; ++k) x[k] = ef[(size_t)e * DE + k];
+      for (int k = 0; k < DE; ++k) x[k] = ld_row(ef, (size_t)e * DE + k);
 #pragma unroll
-      for (int k = 0; k < DN; ++k) x[DE + k] = nf[(size_t)src * DN + k];
+      for (int k = 0; k < DN; ++k) x[DE + k] = ld_row(nf, (size_t)src * DN + k);
 #pragma unroll
-      for (int k = 0; k < DN; ++k) x[DE + DN + k] = nf[(size_t)dst * DN + k];
+      for (int k = 0; k < DN; ++k) x[DE + DN + k] = ld_row(nf, (size_t)dst * DN + k);
 #pragma unroll
-      for (int k = 0; k < DG; ++k) x[DE + 2 * DN + k] = gfr[k];
+      for (int k = 0; k < DG; ++k) x[DE + 2 * DN + k] = ld_row(gfr, k);
 #pragma unroll
       for (int j = 0; j < OE; ++j) {  // k_bw_delta, kind 2
-        float g = a.g_ef_out ? a.g_ef_out[re * OE + j] : 0.f;
+        float g = a.g_ef_out ? ld_feat<BF16>(a.g_ef_out, re * OE + j) : 0.f;
         if (dxg) g += dxg[j];
         if (a.dXn) g += a.dXn[(r * (size_t)a.N + dst) * a.Kn + j];
-        d[j] = g * act_grad_from_out(a.ef_out[re * OE + j], a.act);
+        d[j] = g * act_grad_from_out(ld_feat<BF16>(a.ef_out, re * OE + j), a.act);
       }
 #pragma unroll
       for (int k = 0; k < KE; ++k) {  // k_bw_dx
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < OE; ++j) acc = fmaf(w[k * OE + j], d[j], acc);
-        if (k < DE) { if (a.d_ef && live) a.d_ef[re * DE + k] = acc; }
+        if (k < DE) { if (a.d_ef && live) st_feat<BF16>(a.d_ef, re * DE + k, acc); }
         else if (a.dXe_c && live) a.dXe_c[re * CW + (k - DE)] = acc;
       }
       if (a.partial) {  // uniform
@@ -96,6 +108,11 @@ __global__ __launch_bounds__(256) void k_bw_edge_wave(BwEdgeWave a) {
   }
 }
 
+template <int DE, int DN, int DG, int OE>
+__global__ __launch_bounds__(256) void k_bw_edge_wave(BwEdgeWave a) { bw_edge_wave<DE, DN, DG, OE, false>(a); }
+template <int DE, int DN, int DG, int OE>
+__global__ __launch_bounds__(256) void k_bw_edge_wave_bf16(BwEdgeWave a) { bw_edge_wave<DE, DN, DG, OE, true>(a); }
+
 // the ahead-of-time narrow width sets whose edge level the generic path runs (J * K < 64): (de, dn, dg, oe)
 #define GNX_BW_EDGE_WAVE_DIMS(X) X(10, 5, 0, 3) X(3, 4, 5, 3) X(0, 2, 0, 2) X(2, 2, 2, 2) X(4, 3, 2, 3)
 
@@ -108,12 +125,13 @@ bool bw_edge_wave_has(int de, int dn, int dg, int oe) {
 
 size_t bw_edge_wave_rows(const gnx_graphs* h) { return (size_t)((h->n_wtiles() + 3) / 4); }
 
-int32_t launch_bw_edge_wave(const gnx_block_params* p, const BwEdgeWave& a, int64_t R, hipStream_t s) {
+int32_t launch_bw_edge_wave(const gnx_block_params* p, const BwEdgeWave& a, int64_t R, hipStream_t s, bool bf16) {
   if (a.n_wtiles <= 0 || a.E <= 0) return GNX_OK;
   const dim3 grid((unsigned)((a.n_wtiles + 3) / 4), (unsigned)R);
 #define GNX_X(DE, DN, DG, OE)                                                        \
   if (p->de == DE && p->dn == DN && p->dg == DG && p->oe == OE) {                    \
-    GNX_LAUNCH((k_bw_edge_wave<DE, DN, DG, OE>), grid, dim3(256), 0, s, a);          \
+    if (bf16) GNX_LAUNCH((k_bw_edge_wave_bf16<DE, DN, DG, OE>), grid, dim3(256), 0, s, a); \
+    else GNX_LAUNCH((k_bw_edge_wave<DE, DN, DG, OE>), grid, dim3(256), 0, s, a);     \
     GNX_HIP(hipGetLastError());                                                      \
     return GNX_OK;                                                                   \
   }

@@ -156,7 +156,8 @@ struct BwEdgeWave {
 };
 bool bw_edge_wave_has(int de, int dn, int dg, int oe);  // is the width set instantiated?
 size_t bw_edge_wave_rows(const gnx_graphs* h);          // partial rows per replica
-int32_t launch_bw_edge_wave(const gnx_block_params* p, const BwEdgeWave& a, int64_t R, hipStream_t s);
+// bf16: ef, nf, gf, g_ef_out, ef_out and d_ef hold bfloat16 elements (declared float, like the feature pointers of BlockArgs)
+int32_t launch_bw_edge_wave(const gnx_block_params* p, const BwEdgeWave& a, int64_t R, hipStream_t s, bool bf16 = false);
 
 // ---- gnx_dropout.hip ----
 bool dropout_active(const gnx_dropout* d);

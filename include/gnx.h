@@ -464,6 +464,25 @@ GNX_API int32_t gnx_block_backward_fused(const gnx_graphs* h, const gnx_block_pa
                                  const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef, float* d_nf,
                                  float* d_gf, const gnx_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The fused narrow edge pullback on bfloat16 feature tensors: gnx_block_backward_typed with the edge level of gnx_block_backward_fused.  `elem`
+ * is gnx_block_backward_typed's.  GNX_ELEM_F32: the three entries are gnx_block_backward_fused's.  GNX_ELEM_BF16:
+ * gnx_block_backward_fused_typed_applies is 1 where gnx_block_backward_fused_applies is and the typed call is on its native path (neither the
+ * edge nor the node level on the matrix cores), else 0; any other `elem` gives 0, and 0 from the workspace query.  Where it does not apply the
+ * call IS gnx_block_backward_typed — same validation, same workspace size, same bits.  Where it applies the fused kernel reads ef, nf[src],
+ * nf[dst], gf, g_ef_out and ef_out as bfloat16 (widened on load, exact) and writes d_ef as bfloat16 (rounded to nearest even, once); dXe_c, the
+ * weight-gradient partial rows and all arithmetic stay fp32.  Contract where it applies, for finite data: d_ef / d_nf / d_gf and the node /
+ * graph parameter gradients are bit for bit gnx_block_backward_typed's — and to_bf16 of / equal to gnx_block_backward_fused's on the exactly
+ * widened tensors; grads->edgefn.weight / .bias are bit for bit gnx_block_backward_fused's on the widened tensors (the sums of the typed call in
+ * another fixed order).  The workspace is the fused layout plus 256-B aligned room for R * G * dg floats (the fp32 sum of d_gf): size it with
+ * the query, outside any capture.  Refused before any launch, with gnx_block_backward_typed's statuses: a NULL handle or params, a bad `elem`,
+ * bf16 buffers that are not 4-byte aligned, a workspace that is missing or too small. */
+GNX_API int32_t gnx_block_backward_fused_typed_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_block_backward_fused_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API int32_t gnx_block_backward_fused_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf,
+                                               const void* gf, const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out,
+                                               const void* g_nf_out, const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
+                                               const gnx_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the Chain block: takes the forward's INPUTS and the upstream gradients (NULL = zero); every layer's output is recomputed
  * into the workspace.  Gradients w.r.t. the inputs (optional) and, per chain, one gnx_dense_grad per layer (host arrays of n_layers
  * entries, or NULL; entries' pointers optional), all OVERWRITTEN.  The tail layers and the node / graph chains are row-wise Dense
