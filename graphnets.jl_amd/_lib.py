@@ -164,6 +164,10 @@ SIGNATURES = {
     "gnx_block_backward_fused_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(BlockParams), C.c_int64, C.c_int32]),
     "gnx_block_backward_fused_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32] + [_fp] * 9 + [C.c_int64] + [_fp] * 3 +
                                        [C.POINTER(BlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnx_block_backward_narrow_applies": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int64, C.c_int32]),
+    "gnx_block_backward_narrow_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(BlockParams), C.c_int64, C.c_int32]),
+    "gnx_block_backward_narrow": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32] + [_fp] * 9 + [C.c_int64] + [_fp] * 3 +
+                                  [C.POINTER(BlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_core_backward_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int64]),
     "gnx_core_backward": (C.c_int32, [C.c_void_p, C.c_void_p] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_core_backward_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
@@ -208,6 +212,7 @@ SIGNATURES = {
     "gnx_jit_precompile": (C.c_int32, [C.POINTER(BlockParams), C.c_int32, C.POINTER(C.c_size_t)]),
     "gnx_jit_precompile_typed": (C.c_int32, [C.POINTER(BlockParams), C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "gnx_jit_precompile_core_post": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "gnx_jit_precompile_bw_edge": (C.c_int32, [C.POINTER(BlockParams), C.c_int32, C.POINTER(C.c_size_t)]),
     "gnx_jit_stats": (C.c_int32, [_i64p]),
     "gnx_profile_enable": (C.c_int32, [C.c_int32]),
     "gnx_profile_reset": (C.c_int32, []),

@@ -889,9 +889,15 @@ class GNBlock:
     edge level runs in one kernel; the input gradients and the node / graph parameter gradients keep gnx_block_backward's bits, the edge
     function's weight / bias gradient is summed in another fixed order.  Elsewhere nothing changes.  With `bf16_backward` on as well, the
     pullback of a bfloat16 call is gnx_block_backward_fused_typed: the fused edge level reading and writing bfloat16 where it applies (the
-    input gradients and the node / graph parameter gradients keep gnx_block_backward_typed's bits), gnx_block_backward_typed elsewhere."""
+    input gradients and the node / graph parameter gradients keep gnx_block_backward_typed's bits), gnx_block_backward_typed elsewhere.
 
-    def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False):
+    `narrow_backward` (also a plain attribute; wins over `fused_backward`): the pullback is gnx_block_backward_narrow, on float32 features and —
+    with `bf16_backward` — on bfloat16 ones: the fused edge level at ANY eligible narrow width set (oe * (de + 2 dn + dg) < 64), the kernel of a
+    set outside the five ahead-of-time ones specialised at run time on first use (GNX_JIT_CACHE=<dir> keeps it on disk).  On the five sets the
+    bits are `fused_backward`'s; where the set is not eligible nothing changes."""
+
+    def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
+                 narrow_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -905,6 +911,7 @@ class GNBlock:
         self.flags = 0
         self.bf16_backward = bool(bf16_backward)
         self.fused_backward = bool(fused_backward)
+        self.narrow_backward = bool(narrow_backward)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1118,20 +1125,26 @@ class _BlockFn(torch.autograd.Function):
                                   for w, b in zip(gW, gb)])
         with torch.cuda.device(dev):
             fused = getattr(block, "fused_backward", False)  # (GNBlock.fused_backward: the narrow edge level in one kernel)
-            query, call = (lib.gnx_block_backward_fused_workspace_bytes, lib.gnx_block_backward_fused) if fused else \
-                          (lib.gnx_block_backward_workspace_bytes, lib.gnx_block_backward)
-            nb = query(g._h, C.byref(p), R)
-            ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-            check(call(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_),
-                       _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
-                       torch.cuda.current_stream(dev).cuda_stream))
+            args = (_ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf),
+                    C.byref(grads))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if getattr(block, "narrow_backward", False):  # (GNBlock.narrow_backward: ... at any eligible narrow width set; wins over fused_backward)
+                nb = lib.gnx_block_backward_narrow_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_F32)
+                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
+                check(lib.gnx_block_backward_narrow(g._h, C.byref(p), _lib.ELEM_F32, *args, ws.data_ptr(), ws.numel(), stream))
+            else:
+                query, call = (lib.gnx_block_backward_fused_workspace_bytes, lib.gnx_block_backward_fused) if fused else \
+                              (lib.gnx_block_backward_workspace_bytes, lib.gnx_block_backward)
+                nb = query(g._h, C.byref(p), R)
+                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
+                check(call(g._h, C.byref(p), *args, ws.data_ptr(), ws.numel(), stream))
         gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
         return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
 
 
 class _BlockBf16Fn(torch.autograd.Function):
     """_BlockFn on bfloat16 features (GNBlock.bf16_backward): forward = gnx_block_forward_typed, backward = gnx_block_backward_typed
-    (gnx_block_backward_fused_typed with GNBlock.fused_backward).  The six
+    (gnx_block_backward_fused_typed with GNBlock.fused_backward, gnx_block_backward_narrow with GNBlock.narrow_backward).  The six
     saved tensors are bf16; the input gradients come back in bf16 (rounded once from the fp32 pullback at the rounded saved outputs), the
     weight / bias gradients in fp32 in _BlockFn's layout."""
 
@@ -1190,6 +1203,8 @@ class _BlockBf16Fn(torch.autograd.Function):
             fused = getattr(block, "fused_backward", False)  # (GNBlock.fused_backward: the narrow edge level in one kernel)
             query, call = (lib.gnx_block_backward_fused_typed_workspace_bytes, lib.gnx_block_backward_fused_typed) if fused else \
                           (lib.gnx_block_backward_typed_workspace_bytes, lib.gnx_block_backward_typed)
+            if getattr(block, "narrow_backward", False):  # (GNBlock.narrow_backward wins over fused_backward)
+                query, call = lib.gnx_block_backward_narrow_workspace_bytes, lib.gnx_block_backward_narrow
             nb = query(g._h, C.byref(p), R, _lib.ELEM_BF16)
             ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
             check(call(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge),

@@ -15,6 +15,7 @@
 
 #include "gnx_staging.h"
 #include "gnx_wave_kernel.h"  // ld_feat / st_feat: a bf16 or fp32 element of a feature buffer
+#include "gnx_bw_edge_wave_kernel.h"  // BwEdgeWave
 #include "gnx_feat4.h"        // ld_bf16x4, ld_feat4 / st_feat4: four of them
 
 namespace gnx {
@@ -591,12 +592,13 @@ static bool bw_mfma_node(const gnx_graphs* h, const gnx_block_params* p, int64_t
 // d_ef / d_nf point to bfloat16 — declared float like the feature pointers of BlockArgs, the kernels read them as the element type of the
 // launch — and d_gf, which several launches accumulate, is built in `dgf_acc` (R * G * dg floats) and rounded once at the end.
 // BF16 and fused (gnx_block_backward_fused_typed where it applies): the edge level is k_bw_edge_wave_bf16; dXe_c, the partial rows and everything
-// behind them are the fp32 fused call's.
+// behind them are the fp32 fused call's.  jit_fn (gnx_block_backward_narrow on a run-time width set; implies fused): that kernel specialised at run
+// time for the call's width set and element type, launched in place of the ahead-of-time instantiation.
 template <bool BF16>
 static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
                                 const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
                                 const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
-                                void* ws, size_t ws_bytes, void* stream, float* dgf_acc, bool fused = false) {
+                                void* ws, size_t ws_bytes, void* stream, float* dgf_acc, bool fused = false, hipFunction_t jit_fn = nullptr) {
   hipStream_t s = (hipStream_t)stream;
   if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
   DeviceTurn turn(s, matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
@@ -607,8 +609,9 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   if (BF16 && (bw_mfma_edge(h, p, R) || bw_mfma_node(h, p, R))) return fail(GNX_ERR_INVALID_ARG, "bf16 backward: matrix-core widths take the staging path");
   constexpr size_t kElem = BF16 ? 2 : sizeof(float);  // bytes of a feature element
   const BwLayout L = bw_layout(h, p, R, fused);
-  if ((rc = check_ws(ws, ws_bytes, L.total, fused ? "workspace missing or smaller than gnx_block_backward_fused_workspace_bytes()"
-                                                  : "workspace missing or smaller than gnx_block_backward_workspace_bytes()"))) return rc;
+  if ((rc = check_ws(ws, ws_bytes, L.total, jit_fn ? "workspace missing or smaller than gnx_block_backward_narrow_workspace_bytes()"
+                                            : fused ? "workspace missing or smaller than gnx_block_backward_fused_workspace_bytes()"
+                                                    : "workspace missing or smaller than gnx_block_backward_workspace_bytes()"))) return rc;
   rc = gnx_ensure_wide_tables(h, stream);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
   if (rc) return rc;
   rc = gnx_ensure_csr(h);
@@ -692,7 +695,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
                  de ? d_ef : nullptr, (d_nf && dn) || (d_gf && dg) ? dXe : nullptr, want_dw ? part : nullptr,
                  h->d_wtiles, (int)h->n_wtiles(), h->d_rowval, h->d_edge_dst, N, E, G};
     { ProfScope ps("bw_delta_edge", s);
-    if ((rc = launch_bw_edge_wave(p, a, R, s, BF16))) return rc; }
+    if ((rc = jit_fn ? launch_bw_edge_wave_jit(jit_fn, a, R, s) : launch_bw_edge_wave(p, a, R, s, BF16))) return rc; }
     if (want_dw) {
       ProfScope ps("bw_dw_generic", s);
       GNX_LAUNCH(k_bw_dw_final, dim3(oe * (Ke + 1)), dim3(256), 0, s, part, (int)(R * (int64_t)bw_edge_wave_rows(h)), oe, Ke, gr.edgefn.weight, gr.edgefn.bias);
@@ -790,6 +793,21 @@ static TypedBwWs typed_bw_ws(const gnx_graphs* h, const gnx_block_params* p, int
 static const float* cf(const void* q) { return static_cast<const float*>(q); }
 static float* mf(void* q) { return static_cast<float*>(q); }
 
+// the fused bf16 call once it applies: gnx_block_backward_fused_typed (jit_fn == nullptr: the ahead-of-time kernel) and gnx_block_backward_narrow
+static int32_t bw_fused_bf16(const gnx_graphs* h, const gnx_block_params* p, const void* ef, const void* nf, const void* gf, const void* ef_out,
+                             const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R,
+                             void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws, size_t ws_bytes, void* stream, hipFunction_t jit_fn) {
+  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
+  if (rc) return rc;
+  const void* const bufs[12] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
+  if ((rc = check_bf16_aligned(bufs, 12))) return rc;
+  const Staging w = typed_bw_ws(h, p, R, true).st;
+  if ((rc = check_ws(ws, ws_bytes, w.total, jit_fn ? "workspace missing or smaller than gnx_block_backward_narrow_workspace_bytes()"
+                                                   : "workspace missing or smaller than gnx_block_backward_fused_typed_workspace_bytes()"))) return rc;
+  return block_backward_t<true>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
+                                mf(d_nf), mf(d_gf), grads, ws, w.base, stream, w.at(ws, 0), true, jit_fn);
+}
+
 }  // namespace gnx
 
 using namespace gnx;
@@ -810,13 +828,18 @@ int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const
   return block_backward_t<false>(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr);
 }
 
+// what the fused edge level asks of a call whatever provides its kernel (the ahead-of-time list, the run-time specialiser)
+static bool bw_fused_conditions(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
+  if (!h || !p || R <= 0 || (R > 1 && h->G != 1) || R > 65535) return false;
+  if (p->de < 0 || p->dn < 0 || p->dg < 0 || p->oe <= 0 || p->on < 0 || p->og < 0) return false;
+  if (h->E <= 0 || h->n_wtiles() <= 0 || !h->d_wtiles) return false;
+  if (p->edgefn.act == GNX_ACT_GELU) return false;  // (its pre-activation would have to be recomputed bit for bit)
+  return !bw_mfma_edge(h, p, R);
+}
+
 int32_t gnx_block_backward_fused_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  if (!h || !p || R <= 0 || (R > 1 && h->G != 1) || R > 65535) return 0;
-  if (p->de < 0 || p->dn < 0 || p->dg < 0 || p->oe <= 0 || p->on < 0 || p->og < 0) return 0;
-  if (h->E <= 0 || h->n_wtiles() <= 0 || !h->d_wtiles) return 0;
-  if (!bw_edge_wave_has(p->de, p->dn, p->dg, p->oe)) return 0;
-  if (p->edgefn.act == GNX_ACT_GELU) return 0;  // (its pre-activation would have to be recomputed bit for bit)
-  return bw_mfma_edge(h, p, R) ? 0 : 1;
+  if (!bw_fused_conditions(h, p, R)) return 0;  // (first: it refuses NULL params)
+  return bw_edge_wave_has(p->de, p->dn, p->dg, p->oe) ? 1 : 0;
 }
 
 size_t gnx_block_backward_fused_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
@@ -894,14 +917,62 @@ int32_t gnx_block_backward_fused_typed(const gnx_graphs* h, const gnx_block_para
   if (!gnx_block_backward_fused_typed_applies(h, p, R, elem))  // (also: a bad elem, a NULL handle or params — refused there with its statuses)
     return gnx_block_backward_typed(h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
                                     stream);
-  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
-  if (rc) return rc;
-  const void* const bufs[12] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
-  if ((rc = check_bf16_aligned(bufs, 12))) return rc;
-  const Staging w = typed_bw_ws(h, p, R, true).st;
-  if ((rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_block_backward_fused_typed_workspace_bytes()"))) return rc;
-  return block_backward_t<true>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
-                                mf(d_nf), mf(d_gf), grads, ws, w.base, stream, w.at(ws, 0), true);
+  return bw_fused_bf16(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr);
+}
+
+// ---- gnx_block_backward_narrow: the fused edge level at any eligible narrow width set ----
+namespace {
+enum NarrowBw { NB_GENERIC, NB_AOT, NB_JIT };
+// The form a narrow call takes, decided in ONE place for the two queries and the call.  NB_AOT: gnx_block_backward_fused_typed applies (and
+// GNX_JIT_ALL does not ask for the run-time kernel there).  NB_JIT: the width set is eligible (jit_bw_edge_eligible), the other conditions of the
+// fused call hold and the kernel of this device is loaded — obtained here (disk cache or compile, then load) unless `s` is being captured.
+NarrowBw narrow_bw_form(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem, hipStream_t s, hipFunction_t* fn) {
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return NB_GENERIC;
+  static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // (diagnostic: the run-time kernel at the ahead-of-time width sets too; read once)
+  const bool aot = gnx_block_backward_fused_typed_applies(h, p, R, elem) != 0;
+  if (aot && !jit_all) return NB_AOT;
+  if (!bw_fused_conditions(h, p, R)) return NB_GENERIC;
+  if (elem == GNX_ELEM_BF16 && bw_mfma_node(h, p, R)) return NB_GENERIC;  // (the typed call's staging path)
+  if (jit_get_bw_edge(p->de, p->dn, p->dg, p->oe, elem == GNX_ELEM_BF16, s, fn) == GNX_OK) return NB_JIT;
+  return aot ? NB_AOT : NB_GENERIC;
+}
+}  // namespace
+
+int32_t gnx_block_backward_narrow_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
+  hipFunction_t fn = nullptr;
+  return narrow_bw_form(h, p, R, elem, nullptr, &fn) != NB_GENERIC ? 1 : 0;
+}
+
+size_t gnx_block_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
+  hipFunction_t fn = nullptr;
+  switch (narrow_bw_form(h, p, R, elem, nullptr, &fn)) {
+    case NB_AOT: return gnx_block_backward_fused_typed_workspace_bytes(h, p, R, elem);
+    case NB_JIT: break;
+    default: return gnx_block_backward_typed_workspace_bytes(h, p, R, elem);
+  }
+  (void)gnx_ensure_wide_tables(h);  // (as the generic query: outside any capture)
+  (void)gnx_ensure_csr(h);
+  return elem == GNX_ELEM_BF16 ? typed_bw_ws(h, p, R, true).st.total : bw_layout(h, p, R, true).total;
+}
+
+int32_t gnx_block_backward_narrow(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                  const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
+                                  const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws,
+                                  size_t ws_bytes, void* stream) {
+  hipFunction_t fn = nullptr;
+  switch (narrow_bw_form(h, p, R, elem, (hipStream_t)stream, &fn)) {
+    case NB_AOT:
+      return gnx_block_backward_fused_typed(h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws,
+                                            ws_bytes, stream);
+    case NB_JIT: break;
+    default:  // (also: a bad elem, a NULL handle or params — refused there with its statuses)
+      return gnx_block_backward_typed(h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
+                                      stream);
+  }
+  if (elem == GNX_ELEM_BF16)
+    return bw_fused_bf16(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, fn);
+  return block_backward_t<false>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
+                                 mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream, nullptr, true, fn);
 }
 
 

@@ -141,23 +141,18 @@ int32_t segsum_rows(const float* src, const int* ptr, const int* idx, int N, int
 int32_t add_cols(const float* in, int ld, int off, size_t rows, int d, float* out, int accumulate, hipStream_t s);
 
 // ---- gnx_backward_narrow.hip: the edge level of the block backward at narrow widths in one kernel (gnx_block_backward_fused) ----
-struct BwEdgeWave {
-  const float *ef, *nf, *gf;       // the forward's inputs, replica 0
-  const float *g_ef_out, *ef_out;  // upstream gradient of the edges (or nullptr) and the forward's edge output
-  const float* dXg; int Kg;        // the graph level's dX rows [R][G][Kg] (edge columns first) or nullptr
-  const float* dXn; int Kn;        // the node level's dX rows [R][N][Kn] (edge columns first) or nullptr
-  const float* We; int act;
-  float* d_ef;     // [R][E][de] or nullptr
-  float* dXe_c;    // [R][E][2 dn + dg]: the columns of dXe behind the ef segment, or nullptr
-  float* partial;  // [R][bw_edge_wave_rows][oe (Ke + 1)] or nullptr (neither dWe nor dbe wanted)
-  const Tile* wtiles; int n_wtiles;
-  const int *rowval, *edge_dst;
-  int N, E, G;
-};
+struct BwEdgeWave;  // the kernel's argument record: gnx_bw_edge_wave_kernel.h
 bool bw_edge_wave_has(int de, int dn, int dg, int oe);  // is the width set instantiated?
 size_t bw_edge_wave_rows(const gnx_graphs* h);          // partial rows per replica
 // bf16: ef, nf, gf, g_ef_out, ef_out and d_ef hold bfloat16 elements (declared float, like the feature pointers of BlockArgs)
 int32_t launch_bw_edge_wave(const gnx_block_params* p, const BwEdgeWave& a, int64_t R, hipStream_t s, bool bf16 = false);
+// gnx_jit.cpp: the same kernel specialised at run time (gnx_block_backward_narrow).  Eligible: oe >= 1, Ke >= 1, oe Ke < 64 (at most two
+// (k, j) pairs per lane), the kernel's static LDS within a workgroup's 64 KB, run-time specialisation enabled.
+bool jit_bw_edge_eligible(int de, int dn, int dg, int oe);
+// 0: *fn is ready; 1: not available (the caller runs the generic edge level).  Never compiles or loads while `s` is being captured.
+int32_t jit_get_bw_edge(int de, int dn, int dg, int oe, bool bf16, hipStream_t s, hipFunction_t* fn);
+// the launch of launch_bw_edge_wave with that function
+int32_t launch_bw_edge_wave_jit(hipFunction_t fn, const BwEdgeWave& a, int64_t R, hipStream_t s);
 
 // ---- gnx_dropout.hip ----
 bool dropout_active(const gnx_dropout* d);

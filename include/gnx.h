@@ -483,6 +483,42 @@ GNX_API int32_t gnx_block_backward_fused_typed(const gnx_graphs* h, const gnx_bl
                                                const void* g_nf_out, const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
                                                const gnx_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The fused narrow edge pullback at ANY narrow width set: gnx_block_backward_fused_typed where its five ahead-of-time width sets apply, and the
+ * same kernel specialised at run time (hiprtc, as the forward's run-time kernels: gnx_jit_precompile below) for every other eligible set.
+ * `elem`, the arguments, NULL rules, status codes and the 4-byte alignment of bf16 buffers are gnx_block_backward_fused_typed's; an unknown
+ * `elem` gives 0 from both queries and GNX_ERR_INVALID_ARG from the call.  The call takes one of three forms:
+ *  - Ahead-of-time sets: where gnx_block_backward_fused_typed_applies is 1 the call IS gnx_block_backward_fused_typed — same workspace size, same
+ *    bits in all nine outputs, grads->edgefn.weight / .bias included.
+ *  - Run-time sets: elsewhere the run-time kernel runs when (a) the width set is eligible: oe >= 1, Ke = de + 2 dn + dg >= 1, oe Ke < 64 (the
+ *    weight gradient's oe (Ke + 1) pairs fit two per lane) and the kernel's static LDS, 16 (64 ((oe + Ke) | 1) + 64 ceil(oe (Ke + 1) / 64)) bytes,
+ *    is within 64 KB (this excludes oe + Ke = 64, e.g. (23,15,10)=>1), with run-time specialisation enabled (not GNX_JIT=0); (b) the other
+ *    conditions of the fused call hold: E > 0, wave tiles exist, n_replicas <= 65535 and > 1 only with one graph, an edge activation other than
+ *    gelu, the edge level not on the matrix cores, and for GNX_ELEM_BF16 the typed call on its native path; (c) the kernel of this device is
+ *    loaded.  Then the workspace is the fused layout (plus the fp32 sum of d_gf for bf16); d_ef, d_nf, d_gf and the node / graph parameter
+ *    gradients are bit for bit gnx_block_backward_typed's (gnx_block_backward's for GNX_ELEM_F32); grads->edgefn.weight / .bias are the same
+ *    sums in the kernel's fixed order, bitwise reproducible from run to run; and the bf16 call's edge gradients are bit for bit the fp32
+ *    narrow call's on the exactly widened tensors.
+ *  - Generic: otherwise the call IS gnx_block_backward_typed, with its workspace size and its bits.
+ * gnx_block_backward_narrow_applies / _workspace_bytes OBTAIN the kernel of a run-time set — from GNX_JIT_CACHE=<dir> or by compiling it, then
+ * loading it on the current device — so they belong outside any capture, like every other query of this header; the first use of a width set
+ * costs one hiprtc compilation (a fraction of a second) unless the disk cache holds it.  They answer 1 / the fused size only if the kernel is
+ * loaded; loading is sticky per process and device (a failure too), so a call that follows a query takes the form the query announced.
+ * A call is never the first to compile inside a capture: a call on a capturing stream for a width set that no query (and no earlier call)
+ * loaded finds no kernel, takes the GENERIC form — and refuses a workspace smaller than gnx_block_backward_typed_workspace_bytes with the
+ * usual status and message.  Query first, outside the capture.
+ * Every class of eligible width sets was measured against the generic call on a 1M-edge graph (profiles/bw_narrow_c2.json: 0.47 - 0.70 of its
+ * time, oe = 1 with Ke = 44 and 62 included), so the eligibility rule cuts none out.
+ * GNX_JIT_ALL (diagnostic, read once) makes these entries run the run-time kernel at the five ahead-of-time sets too; nothing else changes.
+ * gnx_jit_precompile_bw_edge: compile only (no GPU needed; honours GNX_JIT_CACHE) — *code_bytes = size of the code object; GNX_ERR_DIMS for a
+ * width set that is not eligible, GNX_ERR_INVALID_ARG for NULL params or a bad `elem`.  Only p->de, dn, dg, oe are read. */
+GNX_API int32_t gnx_block_backward_narrow_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_block_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API int32_t gnx_block_backward_narrow(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf,
+                                          const void* gf, const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out,
+                                          const void* g_nf_out, const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
+                                          const gnx_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+GNX_API int32_t gnx_jit_precompile_bw_edge(const gnx_block_params* p, int32_t elem, size_t* code_bytes);
+
 /* Backward of the Chain block: takes the forward's INPUTS and the upstream gradients (NULL = zero); every layer's output is recomputed
  * into the workspace.  Gradients w.r.t. the inputs (optional) and, per chain, one gnx_dense_grad per layer (host arrays of n_layers
  * entries, or NULL; entries' pointers optional), all OVERWRITTEN.  The tail layers and the node / graph chains are row-wise Dense

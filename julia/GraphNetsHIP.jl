@@ -711,8 +711,12 @@ cpu(m::GNCoreList) = GNCoreList(map(cpu, m.list))
 #      examples/sort/sort.jl:122-132).  `block_pullback(m, x, y, ȳ)` returns (∂ef, ∂nf, ∂gf, (∂W, ∂b) for the three Dense layers);
 #      with ChainRulesCore loaded it is the body of the rrule below.  (gnx_core_backward is bound the same way; the tested
 #      binding of both is graphnets.jl_amd/api.py: _BlockFn / _CoreFn.) ----
+#      `narrow=true`: gnx_block_backward_narrow — the edge level of any eligible narrow width set (oe * (de + 2dn + dg) < 64) in one kernel,
+#      specialised at run time on first use (GNX_JIT_CACHE keeps it on disk); its workspace query obtains the kernel, so the first call of a
+#      width set belongs outside any capture.  Input gradients and node / graph parameter gradients keep gnx_block_backward's bits.
 likeof(a) = isnothing(a) ? nothing : similar(a)
-function block_pullback_device(m::GNBlock, x, y, ȳ)
+const GNX_ELEM_F32 = Int32(3)
+function block_pullback_device(m::GNBlock, x, y, ȳ; narrow::Bool=false)
     g::GNGraphBatch = x.graphs
     R = replicas(x.ef, x.nf, x.gf)
     p = Ref(block_c(m))
@@ -720,6 +724,17 @@ function block_pullback_device(m::GNBlock, x, y, ȳ)
     layers = (m.edgefn, m.nodefn, m.graphfn)
     gW = [similar(l.weight) for l in layers]; gB = [similar(l.bias) for l in layers]
     grads = Ref(GnxBlockGrads(GnxDenseGrad(devptr(gW[1]), devptr(gB[1])), GnxDenseGrad(devptr(gW[2]), devptr(gB[2])), GnxDenseGrad(devptr(gW[3]), devptr(gB[3]))))
+    if narrow
+        ws = workspace!(g, (:block_backward_narrow, m.in, m.out, R)) do
+            ccall((:gnx_block_backward_narrow_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxBlockParams}, Int64, Int32), g.handle, p, R, GNX_ELEM_F32)
+        end
+        GC.@preserve m x y ȳ dins gW gB ws check(ccall((:gnx_block_backward_narrow, libgnx), Int32,
+            (Ptr{Cvoid}, Ptr{GnxBlockParams}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+             Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{GnxBlockGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+            g.handle, p, GNX_ELEM_F32, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(y.ef), devptr(y.nf), devptr(y.gf),
+            devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R, devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]))
+        return (ef=dins[1], nf=dins[2], gf=dins[3], params=[(weight=gW[i], bias=gB[i]) for i in 1:3])
+    end
     ws = workspace!(g, (:block_backward, m.in, m.out, R)) do
         ccall((:gnx_block_backward_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxBlockParams}, Int64), g.handle, p, R)
     end
@@ -730,8 +745,13 @@ function block_pullback_device(m::GNBlock, x, y, ȳ)
         devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R, devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]))
     (ef=dins[1], nf=dins[2], gf=dins[3], params=[(weight=gW[i], bias=gB[i]) for i in 1:3])
 end
-function block_pullback(m::GNBlock, x, y, ȳ)
-    r = block_pullback_device(gpu(m), gpu(x), gpu(y), gpu(ȳ))
+# does the fused edge level run for this block on this batch (the run-time kernel is obtained here: outside any capture)?
+function narrow_backward_applies(m::GNBlock, g::GNGraphBatch, R::Integer=1)
+    p = Ref(block_c(gpu(m)))
+    ccall((:gnx_block_backward_narrow_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxBlockParams}, Int64, Int32), g.handle, p, R, GNX_ELEM_F32) == 1
+end
+function block_pullback(m::GNBlock, x, y, ȳ; narrow::Bool=false)
+    r = block_pullback_device(gpu(m), gpu(x), gpu(y), gpu(ȳ); narrow=narrow)
     ondevice(x) ? r : (ef=cpu(r.ef), nf=cpu(r.nf), gf=cpu(r.gf), params=[map(cpu, q) for q in r.params])
 end
 
