@@ -57,7 +57,8 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="bfloat16 features through every layer, forward and backward (weights and the loss stay float32)")
     ap.add_argument("--narrow-backward", action="store_true",
                     help="the encoder / decoder blocks' pullback through gnx_block_backward_narrow: the fused edge level where the width set is eligible "
-                         "(oe * (de + 2 dn + dg) < 64; e.g. the encoder at --width 16 without --vocab), its kernel specialised at run time on first use")
+                         "(oe * (de + 2 dn + dg) < 64; e.g. the encoder at --width 16 without --vocab), its kernel specialised at run time on first use; "
+                         "and the cores' pullback through gnx_core_backward_narrow: each FeedForward's pullback in one kernel at --width <= 16")
     args = ap.parse_args()
     if args.bf16 and args.dropout > 0:
         sys.exit("--bf16 with --dropout > 0: Dropout in training mode on bfloat16 features is not implemented (the training-mode core is fp32 only)")
@@ -68,7 +69,7 @@ def main():
     w = args.width
     b16 = bool(args.bf16)
     enc = gn.GNBlock((0, args.vocab or 1, 0), (w, w, w), device=dev, act=("relu", "relu", "relu"), bf16_backward=b16, narrow_backward=args.narrow_backward)
-    cores = gn.GNCoreList([gn.GNCore((w, w, w), dropout=args.dropout, device=dev, bf16=b16, bf16_backward=b16) for _ in range(2)])
+    cores = gn.GNCoreList([gn.GNCore((w, w, w), dropout=args.dropout, device=dev, bf16=b16, bf16_backward=b16, narrow_backward=args.narrow_backward) for _ in range(2)])
     dec = gn.GNBlock((w, w, w), (2, 2, 0), device=dev, bf16_backward=b16, narrow_backward=args.narrow_backward)
     params = []
     for blk in (enc, dec):

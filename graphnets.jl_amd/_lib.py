@@ -173,6 +173,10 @@ SIGNATURES = {
     "gnx_core_backward_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "gnx_core_backward_typed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
                                 [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnx_core_backward_narrow_applies": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "gnx_core_backward_narrow_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "gnx_core_backward_narrow": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Dropout)] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
+                                 [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_core_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(CoreParams), C.c_int64]),
     "gnx_core_forward": (C.c_int32, [C.c_void_p, C.POINTER(CoreParams)] + _FWD[2:]),
     "gnx_core_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(CoreParams), C.c_int64, C.c_int32, C.c_uint32]),

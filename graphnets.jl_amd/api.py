@@ -1300,9 +1300,12 @@ class GNCore:
     `bf16_backward` (also a plain attribute, as GNBlock's): lets a differentiable call on bfloat16 features run — gnx_core_backward_typed is its
     pullback, the three saved inputs stay bf16, input gradients come back in bf16 and parameter gradients in fp32.  Off (the default) such a
     call raises NotImplementedError.  Dropout active on bfloat16 features (forced by `trainmode`, or p > 0 inside a gradient call) raises
-    NotImplementedError either way: the training-mode pair is fp32 only."""
+    NotImplementedError either way: the training-mode pair is fp32 only.
+    `narrow_backward` (also a plain attribute, as GNBlock's): the pullback is gnx_core_backward_narrow, on float32 features (with the call's
+    Dropout value when one is active) and — with `bf16_backward` — on bfloat16 ones: the pullback of each FeedForward in one kernel where all
+    three widths are at most 16 and the hidden activations identity / relu, exactly the other pullbacks everywhere else.  Off by default."""
 
-    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False, bf16_backward=False):
+    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False, bf16_backward=False, narrow_backward=False):
         dims = tuple(int(d) for d in dims)
         assert any(d > 0 for d in dims)  # gncore.jl:47
         self.dims = dims
@@ -1314,6 +1317,7 @@ class GNCore:
         self.flags = 0
         self.bf16 = bool(bf16)
         self.bf16_backward = bool(bf16_backward)
+        self.narrow_backward = bool(narrow_backward)
 
     def _c(self, keep):
         p = _lib.CoreParams()
@@ -1483,7 +1487,8 @@ def trainmode(m, mode=True):
 
 
 class _CoreFn(torch.autograd.Function):
-    """torch autograd node of one GNCore call: forward = gnx_core_forward, backward = gnx_core_backward."""
+    """torch autograd node of one GNCore call: forward = gnx_core_forward, backward = gnx_core_backward (gnx_core_backward_narrow with
+    GNCore.narrow_backward)."""
 
     @staticmethod
     def forward(ctx, core, g, R, flags, drop, ef, nf, gf, *params):
@@ -1507,6 +1512,13 @@ class _CoreFn(torch.autograd.Function):
         gr = _core_grads(core, out)
         d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
         with torch.cuda.device(dev):
+            if getattr(core, "narrow_backward", False):  # (GNCore.narrow_backward: the FeedForward pullbacks in one kernel each where the core is narrow)
+                nb = lib.gnx_core_backward_narrow_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_F32)
+                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
+                check(lib.gnx_core_backward_narrow(g._h, C.byref(p), _lib.ELEM_F32, None if ctx.drop is None else C.byref(ctx.drop), ef.data_ptr(),
+                                                   nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(),
+                                                   d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+                return (None, None, None, None, None, d_ef, d_nf, d_gf, *out)
             nb = lib.gnx_core_backward_workspace_bytes(g._h, C.byref(p), R)
             ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
             if ctx.drop is None:
@@ -1572,6 +1584,13 @@ class _CoreBf16Fn(torch.autograd.Function):
         gr = _core_grads(core, out)
         d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
         with torch.cuda.device(dev):
+            if getattr(core, "narrow_backward", False):  # (GNCore.narrow_backward)
+                nb = lib.gnx_core_backward_narrow_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16)
+                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
+                check(lib.gnx_core_backward_narrow(g._h, C.byref(p), _lib.ELEM_BF16, None, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_),
+                                                   _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(), d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(),
+                                                   torch.cuda.current_stream(dev).cuda_stream))
+                return (None, None, None, None, d_ef, d_nf, d_gf, *out)
             nb = lib.gnx_core_backward_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16)
             ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
             check(lib.gnx_core_backward_typed(g._h, C.byref(p), _lib.ELEM_BF16, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg),

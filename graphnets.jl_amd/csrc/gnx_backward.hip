@@ -981,7 +981,9 @@ namespace {
 struct CoreBwLayout {
   size_t l1[3], l2[3], bout[3], dl1[3], dz2[3], h, dh, t1, t2, off2, blk_fw, blk_bw, part, wt, tcs, lnpart, total;
 };
-CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
+// narrow (gnx_core_backward_narrow where it applies): step 2 is k_core_bw_narrow — no h, dh, wt or tcs region, and `part` fits the kernel's
+// partial rows (both Denses of an entity side by side) next to the column-sum slices of step 4
+CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool narrow = false) {
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
   const int d[3] = {p->block.de, p->block.dn, p->block.dg};
   CoreBwLayout L{};
@@ -994,21 +996,26 @@ CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64
     hmax = std::max(hmax, sizeof(float) * rows[t] * 4 * (size_t)d[t]);
     tmax = std::max(tmax, b);
   }
+  if (narrow) hmax = 0;
   L.h = take(hmax); L.dh = take(hmax); L.t1 = take(tmax); L.t2 = take(tmax); L.off2 = take(64);
   L.blk_fw = take(gnx_block_workspace_bytes(h, &p->block, R));
   L.blk_bw = take(gnx_block_backward_workspace_bytes(h, &p->block, R));
   size_t pmax = sizeof(float) * 2048 * 4 * (size_t)std::max(d[0], std::max(d[1], d[2]));
   for (int t = 0; t < 3; ++t) {
+    if (narrow) {
+      pmax = std::max(pmax, sizeof(float) * core_bw_narrow_rows(rows[t], d[t]) * ((size_t)(4 * d[t]) * (d[t] + 1) + (size_t)d[t] * (4 * d[t] + 1)));
+      continue;
+    }
     const size_t ch = (rows[t] + BW_CH - 1) / BW_CH;
     pmax = std::max(pmax, sizeof(float) * ch * (size_t)(4 * d[t]) * (d[t] + 1));
     pmax = std::max(pmax, sizeof(float) * ch * (size_t)d[t] * (4 * d[t] + 1));
     pmax = std::max(pmax, sizeof(float) * dw_mfma_partial_floats(rows[t], 4 * d[t], d[t]));
   }
   L.part = take(pmax);
-  L.wt = take(sizeof(float) * 4 * (size_t)std::max(d[0], std::max(d[1], d[2])) * std::max(d[0], std::max(d[1], d[2])));
+  L.wt = take(narrow ? 0 : sizeof(float) * 4 * (size_t)std::max(d[0], std::max(d[1], d[2])) * std::max(d[0], std::max(d[1], d[2])));
   size_t tcs = 0;  // per-tile column sums of delta1 (tiles of the matrix-core path: 128-row chunks per graph)
   const size_t nt[3] = {(size_t)h->n_etiles, (size_t)h->n_ntiles, (size_t)h->n_gtiles};
-  for (int t = 0; t < 3; ++t) tcs = std::max(tcs, sizeof(float) * (size_t)R * nt[t] * 4 * d[t]);
+  for (int t = 0; t < 3 && !narrow; ++t) tcs = std::max(tcs, sizeof(float) * (size_t)R * nt[t] * 4 * d[t]);
   L.tcs = take(tcs);
   size_t lnp = 0;  // k_ln_backward_v4: [blocks][4][D] column partial sums
   for (int t = 0; t < 3; ++t) lnp = std::max(lnp, sizeof(float) * ((rows[t] + 127) / 128) * 4 * (size_t)d[t]);
@@ -1018,9 +1025,9 @@ CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64
 }
 // gnx_core_backward_typed, GNX_ELEM_BF16: the fp32 layout, then an fp32 copy of each upstream gradient, every carve 256-B aligned.  (x and d_x
 // need none: the LayerNorm kernels read and write bf16 themselves.)
-Staging typed_core_bw_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
+Staging typed_core_bw_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool narrow = false) {
   const int d[3] = {p->block.de, p->block.dn, p->block.dg};
-  return stage_features(core_bw_layout(h, p, R).total, h, R, d, 3);
+  return stage_features(core_bw_layout(h, p, R, narrow).total, h, R, d, 3);
 }
 }  // namespace
 
@@ -1039,10 +1046,12 @@ size_t gnx_core_backward_workspace_bytes(const gnx_graphs* h, const gnx_core_par
 // BF16 (gnx_core_backward_typed): the nine feature-shaped tensors hold bfloat16 elements (declared float, like the feature pointers of BlockArgs).
 // Only the LayerNorm kernels touch x and d_x — steps 1 and 4 — and they take the element type; the upstream gradients are widened once into
 // fp32 copies behind the fp32 layout, which every consumer below reads; the kernel forms are chosen from the CALLER's addresses as before.
+// narrow (gnx_core_backward_narrow where it applies): step 2 of an entity is one k_core_bw_narrow launch and the two finishers of its partial rows,
+// on the narrow layout; steps 1, 3 and 4 are the same launches.
 template <bool BF16>
 static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p, const gnx_dropout* dr, const float* ef, const float* nf, const float* gf,
                                   const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
-                                  float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+                                  float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream, bool narrow = false) {
   hipStream_t s = (hipStream_t)stream;
   if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
   const gnx_block_params& b = p->block;
@@ -1062,10 +1071,11 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
     const void* const bufs[9] = {ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
     if ((rc = check_bf16_aligned(bufs, 9))) return rc;
   }
-  const CoreBwLayout L = core_bw_layout(h, p, R);
-  const Staging tw = BF16 ? typed_core_bw_ws(h, p, R) : Staging{};
-  if ((rc = check_ws(ws, ws_bytes, BF16 ? tw.total : L.total, BF16 ? "workspace missing or smaller than gnx_core_backward_typed_workspace_bytes()"
-                                                                   : "workspace missing or smaller than gnx_core_backward_workspace_bytes()"))) return rc;
+  const CoreBwLayout L = core_bw_layout(h, p, R, narrow);
+  const Staging tw = BF16 ? typed_core_bw_ws(h, p, R, narrow) : Staging{};
+  if ((rc = check_ws(ws, ws_bytes, BF16 ? tw.total : L.total, narrow ? "workspace missing or smaller than gnx_core_backward_narrow_workspace_bytes()"
+                                                              : BF16 ? "workspace missing or smaller than gnx_core_backward_typed_workspace_bytes()"
+                                                                     : "workspace missing or smaller than gnx_core_backward_workspace_bytes()"))) return rc;
   if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
   char* base = static_cast<char*>(ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -1107,6 +1117,19 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
     if (dropout_active(dr)) {
       if ((rc = launch_dropout(*dr, t, rows[t] * (size_t)D, gout[t], F(L.t1), 1, s))) return rc;  // (t1 is free until step 4)
       gff = F(L.t1);
+    }
+    if (narrow) {  // the whole pullback of this FeedForward in one kernel (gnx_core_bw_narrow.hip), then one finisher per Dense
+      const size_t nwg = core_bw_narrow_rows(rows[t], D);
+      const gnx_ffn_grad& gf_ = gr.ff[t];
+      float* part1 = gf_.fc1.weight || gf_.fc1.bias ? part : nullptr;
+      float* part2 = gf_.fc2.weight || gf_.fc2.bias ? part + nwg * (size_t)H * (D + 1) : nullptr;
+      { ProfScope ps("bw_delta", s);
+        if ((rc = launch_core_bw_narrow(F(L.l2[t]), gff, p->ff[t], rows[t], D, dz2, part1, part2, s))) return rc; }
+      ProfScope ps("bw_dw_generic", s);
+      if (part1) GNX_LAUNCH(k_bw_dw_final, dim3((unsigned)(H * (D + 1))), dim3(256), 0, s, part1, (int)nwg, H, D, gf_.fc1.weight, gf_.fc1.bias);
+      if (part2) GNX_LAUNCH(k_bw_dw_final, dim3((unsigned)(D * (H + 1))), dim3(256), 0, s, part2, (int)nwg, D, H, gf_.fc2.weight, gf_.fc2.bias);
+      GNX_HIP(hipGetLastError());
+      continue;
     }
     // gelu is not a function of its output: hbuf first holds the PRE-activation z1 = W1 z + b1, delta1 = dh .* gelu'(z1) is formed from
     // it (act code 4 of the delta kernel = "out holds z"), then hbuf becomes h = gelu(z1) in place for dW2
@@ -1232,6 +1255,43 @@ int32_t gnx_core_backward_typed(const gnx_graphs* h, const gnx_core_params* p, i
   if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
   return core_backward_impl<true>(h, p, nullptr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws,
                                   ws_bytes, stream);
+}
+
+// gnx_core_backward_narrow: where k_core_bw_narrow takes the FeedForward pullbacks.  A rule of the parameters alone (not of the row counts): a
+// valid core, all three widths narrow, hidden activations the kernel knows (identity / relu — the forward's combined kernel takes the same).
+int32_t gnx_core_backward_narrow_applies(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) {
+  if (!h || !p || (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16)) return 0;
+  if (R <= 0 || (R > 1 && h->G != 1) || R > 65535) return 0;
+  const gnx_block_params& b = p->block;
+  if (b.de <= 0 || b.dn <= 0 || b.dg <= 0 || b.oe != b.de || b.on != b.dn || b.og != b.dg) return 0;
+  const int d[3] = {b.de, b.dn, b.dg};
+  for (int t = 0; t < 3; ++t)
+    if (!core_narrow_width(d[t]) || p->ff[t].fc2.act != GNX_ACT_IDENTITY || p->ff[t].fc1.act < GNX_ACT_IDENTITY || p->ff[t].fc1.act > GNX_ACT_RELU) return 0;
+  return 1;
+}
+size_t gnx_core_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) {
+  if (!gnx_core_backward_narrow_applies(h, p, R, elem)) return gnx_core_backward_typed_workspace_bytes(h, p, R, elem);
+  (void)gnx_ensure_wide_tables(h);  // (as the generic query: outside any capture)
+  (void)gnx_ensure_csr(h);
+  return elem == GNX_ELEM_BF16 ? typed_core_bw_ws(h, p, R, true).total : core_bw_layout(h, p, R, true).total;
+}
+int32_t gnx_core_backward_narrow(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const gnx_dropout* dropout, const void* ef, const void* nf,
+                                 const void* gf, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf,
+                                 void* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (int32_t rc = check_dropout(dropout)) return rc;
+  const gnx_dropout* dr = dropout_active(dropout) ? dropout : nullptr;
+  if (dr && elem == GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "bf16 core backward with an active Dropout: no typed training-mode forward exists");
+  if (!gnx_core_backward_narrow_applies(h, p, R, elem)) {
+    if (dr) return gnx_core_backward_train(h, p, dr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream);
+    return gnx_core_backward_typed(h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
+  }
+  if (elem == GNX_ELEM_BF16)
+    return core_backward_impl<true>(h, p, nullptr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws,
+                                    ws_bytes, stream, true);
+  return core_backward_impl<false>(h, p, dr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws, ws_bytes,
+                                   stream, true);
 }
 }  // extern "C"
 

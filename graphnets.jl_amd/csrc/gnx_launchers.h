@@ -154,6 +154,12 @@ int32_t jit_get_bw_edge(int de, int dn, int dg, int oe, bool bf16, hipStream_t s
 // the launch of launch_bw_edge_wave with that function
 int32_t launch_bw_edge_wave_jit(hipFunction_t fn, const BwEdgeWave& a, int64_t R, hipStream_t s);
 
+// ---- gnx_core_bw_narrow.hip: the FeedForward pullback of the core backward at narrow widths in one kernel (gnx_core_backward_narrow) ----
+size_t core_bw_narrow_rows(size_t rows, int d);  // partial rows (= workgroups) of the launch over `rows` rows at width d
+// dz2 = the pullback of ff through z = gn2(x) with upstream g; part1 / part2: [core_bw_narrow_rows][4d (d + 1)] / [..][d (4d + 1)] partial rows of
+// fc1's / fc2's weight and bias gradient in k_bw_dw_final's pair order, or nullptr (not wanted).  d: a core_narrow_width; fc1 identity or relu
+int32_t launch_core_bw_narrow(const float* z, const float* g, const gnx_ffn& ff, size_t rows, int d, float* dz2, float* part1, float* part2, hipStream_t s);
+
 // ---- gnx_dropout.hip ----
 bool dropout_active(const gnx_dropout* d);
 int32_t check_dropout(const gnx_dropout* d);

@@ -668,6 +668,34 @@ GNX_API int32_t gnx_core_backward_train(const gnx_graphs* h, const gnx_core_para
                                 float* d_ef, float* d_nf, float* d_gf, const gnx_core_grads* grads, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
+/* The same backward — (m::GNCore)(x) = x + block(gn1(x)) + ffwd(gn2(x)) (src/gncore.jl:56-59), ffwd = Chain(Dense(d => 4d, relu), Dense(4d => d),
+ * Dropout(p)) (src/gnfeedforward.jl:27-31) — with the pullback of each FeedForward in ONE kernel where the core is narrow: a row of gn2(x), its
+ * 4d hidden units, their deltas, the upstream gradient and the gradient w.r.t. gn2(x) live in one lane's registers, the weights are scalar
+ * operands, and the four weight / bias gradients are summed in the kernel in a fixed order (rows of a 64-row chunk in row order, a wave's chunks in
+ * chunk order, a workgroup's waves in wave order, workgroups by the generic finisher) — no atomics, the same bits on every call.  The hidden
+ * activations and deltas ([rows][4d], twice) never reach memory, and the workspace carries neither region.
+ * gnx_core_backward_narrow_applies = 1: a valid core (dims => dims, all > 0, fc2 identity, valid n_replicas) whose three widths are all within
+ * 1..16 and whose three fc1 activations are identity or relu, `elem` GNX_ELEM_F32 or GNX_ELEM_BF16; it does not depend on the row counts.  (No
+ * width is cut from the rule: see profiles/core_bw_narrow.json.)  Then every entity with rows and an upstream gradient runs that kernel plus one
+ * finisher per Dense; everything else — both LayerNorm passes, the block's forward and pullback, the LayerNorm pullback, the zero fills of an
+ * entity without rows or without upstream gradient, the Dropout mask as a pass over the upstream gradient, the bf16 widening — is the launches of
+ * gnx_core_backward / _train / _typed.  Results: d_ef, d_nf, d_gf, the block's gradients and the LayerNorm gradients carry the bits of those calls
+ * wherever they run their generic kernels (the gradient w.r.t. gn2(x) is computed by the same operations in the same order); the twelve
+ * FeedForward gradients are the same sums in another fixed order (a few fp32 roundings apart).
+ * `dropout`: NULL or p = 0 — test mode; 0 < p <= 1 with GNX_ELEM_F32 — the pullback of gnx_core_forward_train under the same value; with
+ * GNX_ELEM_BF16 an active dropout is GNX_ERR_INVALID_ARG before anything is written (no typed training-mode forward exists).
+ * Where it does not apply, the call IS gnx_core_backward_typed (no active dropout) or gnx_core_backward_train (fp32, active dropout), bit for
+ * bit, and the workspace query returns theirs.  The query builds the CSR view and the wide tables: call it outside any capture.  The call
+ * itself compiles nothing at run time (sixteen ahead-of-time instantiations cover every core), allocates nothing, does not synchronise and is
+ * safe inside a capture.  NULL rules, optional outputs and status codes are gnx_core_backward_typed's; both queries return 0 on a NULL handle or
+ * params. */
+GNX_API int32_t gnx_core_backward_narrow_applies(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_core_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem);
+GNX_API int32_t gnx_core_backward_narrow(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const gnx_dropout* dropout /* NULL: none */,
+                                         const void* ef, const void* nf, const void* gf, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out,
+                                         int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf, const gnx_core_grads* grads, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+
 /* ---- row statistics of a packed [rows][d] tensor: stats[row] = (mean, 1 / (sigma + eps)) (eps_mode 0, Flux 0.14 `normalise`) or
  * (mean, 1 / sqrt(sigma^2 + eps)) (eps_mode 1), uncorrected sigma — the one pass over x from which the wide kernels apply GNGraphNorm's
  * LayerNorms (src/gngraphnorm.jl:19-26) as they load their rows; exported as the building block it is (and so that it can be exercised

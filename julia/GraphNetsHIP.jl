@@ -665,7 +665,9 @@ struct GnxCoreGrads
     block::GnxBlockGrads
     ln1::NTuple{3,GnxLayerNormGrad}; ln2::NTuple{3,GnxLayerNormGrad}; ff::NTuple{3,GnxFfnGrad}
 end
-function core_pullback_device(m::GNCore, x, ȳ, drop=nothing)
+# `narrow=true`: gnx_core_backward_narrow — the pullback of each FeedForward in one kernel where all three widths are at most 16 and the hidden
+# activations identity / relu (gncore.jl:56-59, gnfeedforward.jl:27-31), `drop` passed on as its Dropout value; everywhere else the very calls below.
+function core_pullback_device(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false)
     g::GNGraphBatch = x.graphs
     R = size(x.ef, 3)
     p = Ref(core_c(m))
@@ -677,6 +679,18 @@ function core_pullback_device(m::GNCore, x, ȳ, drop=nothing)
     grads = Ref(GnxCoreGrads(GnxBlockGrads(gd(b.edgefn), gd(b.nodefn), gd(b.graphfn)), map(gl, m.gn1), map(gl, m.gn2),
                              map(t -> GnxFfnGrad(gd(t[1]), gd(t[2])), m.ffwd)))
     dins = (similar(x.ef), similar(x.nf), similar(x.gf))
+    if narrow
+        ws = workspace!(g, (:core_backward_narrow, m.dims, R)) do
+            ccall((:gnx_core_backward_narrow_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64, Int32), g.handle, p, R, GNX_ELEM_F32)
+        end
+        d = drop === nothing ? Ptr{GnxDropout}(C_NULL) : Ref(drop::GnxDropout)
+        GC.@preserve m x ȳ gbuf dins ws d check(ccall((:gnx_core_backward_narrow, libgnx), Int32,
+            (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int32, Ptr{GnxDropout}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+             Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{GnxCoreGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+            g.handle, p, GNX_ELEM_F32, d, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
+            devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]))
+        return (ef=dins[1], nf=dins[2], gf=dins[3], params=gbuf)
+    end
     ws = workspace!(g, (:core_backward, m.dims, R)) do
         ccall((:gnx_core_backward_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64), g.handle, p, R)
     end
@@ -696,9 +710,14 @@ function core_pullback_device(m::GNCore, x, ȳ, drop=nothing)
     end
     (ef=dins[1], nf=dins[2], gf=dins[3], params=gbuf)                  # block (W, b) x 3, gn1 (γ, β) x 3, gn2 (γ, β) x 3, ffwd (W1, b1, W2, b2) x 3
 end
-function core_pullback(m::GNCore, x, ȳ, drop=nothing)
-    r = core_pullback_device(gpu(m), gpu(x), gpu(ȳ), drop)
+function core_pullback(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false)
+    r = core_pullback_device(gpu(m), gpu(x), gpu(ȳ), drop; narrow=narrow)
     ondevice(x) ? r : (ef=cpu(r.ef), nf=cpu(r.nf), gf=cpu(r.gf), params=map(cpu, r.params))
+end
+# does the fused FeedForward pullback run for this core (a rule of its widths and activations, not of the batch's row counts)?
+function narrow_backward_applies(m::GNCore, g::GNGraphBatch, R::Integer=1)
+    p = Ref(core_c(gpu(m)))
+    ccall((:gnx_core_backward_narrow_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64, Int32), g.handle, p, R, GNX_ELEM_F32) == 1
 end
 
 # GNCoreList is `foldl((x, f) -> f(x), list; init=x)` exactly as src/gncorelist.jl:43-45.
