@@ -1103,43 +1103,7 @@ class _BlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        lib = _lib.load()
-        block, g, R = ctx.block, ctx.g, ctx.R
-        sv = iter(ctx.saved_tensors)
-        ef, nf, gf, eo, no, go = (next(sv) if present else None for present in ctx.slots)
-        it = iter(gouts)
-        ge, gn_, gg = (next(it) if pr else None for pr in ctx.present)
-        cont = lambda t: None if t is None else t.contiguous()
-        ge, gn_, gg = cont(ge), cont(gn_), cont(gg)
-        keep = []
-        p = block._c(keep)
-        dev = g.device
-        need = ctx.needs_input_grad[1:]  # (g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg) -> ef is need[3]
-        d_ef = torch.empty_like(ef) if ef is not None and need[3] else None
-        d_nf = torch.empty_like(nf) if nf is not None and need[4] else None
-        d_gf = torch.empty_like(gf) if gf is not None and need[5] else None
-        layers = (block.edgefn, block.nodefn, block.graphfn)
-        gW = [torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev) if need[6 + 2 * i] else None for i, l in enumerate(layers)]
-        gb = [torch.empty_like(l.bias) if (l.bias is not None and need[7 + 2 * i]) else None for i, l in enumerate(layers)]
-        grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None)
-                                  for w, b in zip(gW, gb)])
-        with torch.cuda.device(dev):
-            fused = getattr(block, "fused_backward", False)  # (GNBlock.fused_backward: the narrow edge level in one kernel)
-            args = (_ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf),
-                    C.byref(grads))
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if getattr(block, "narrow_backward", False):  # (GNBlock.narrow_backward: ... at any eligible narrow width set; wins over fused_backward)
-                nb = lib.gnx_block_backward_narrow_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_F32)
-                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-                check(lib.gnx_block_backward_narrow(g._h, C.byref(p), _lib.ELEM_F32, *args, ws.data_ptr(), ws.numel(), stream))
-            else:
-                query, call = (lib.gnx_block_backward_fused_workspace_bytes, lib.gnx_block_backward_fused) if fused else \
-                              (lib.gnx_block_backward_workspace_bytes, lib.gnx_block_backward)
-                nb = query(g._h, C.byref(p), R)
-                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-                check(call(g._h, C.byref(p), *args, ws.data_ptr(), ws.numel(), stream))
-        gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
-        return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
+        return _block_pullback(ctx, gouts, _lib.ELEM_F32)
 
 
 class _BlockBf16Fn(torch.autograd.Function):
@@ -1173,45 +1137,59 @@ class _BlockBf16Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        lib = _lib.load()
-        block, g, R = ctx.block, ctx.g, ctx.R
-        sv = iter(ctx.saved_tensors)
-        ef, nf, gf, eo, no, go = (next(sv) if present else None for present in ctx.slots)
-        it = iter(gouts)
-        ge, gn_, gg = (next(it) if pr else None for pr in ctx.present)
+        return _block_pullback(ctx, gouts, _lib.ELEM_BF16)
 
-        def cot(t):  # contiguous and 4-byte aligned (a cotangent has the bf16 dtype of its output)
-            if t is None:
-                return None
-            t = t.contiguous()
-            return t if t.data_ptr() % 4 == 0 else t.clone()
 
-        ge, gn_, gg = cot(ge), cot(gn_), cot(gg)
-        keep = []
-        p = block._c(keep)
-        dev = g.device
-        need = ctx.needs_input_grad[1:]  # (g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg) -> ef is need[3]
-        d_ef = torch.empty_like(ef) if ef is not None and need[3] else None
-        d_nf = torch.empty_like(nf) if nf is not None and need[4] else None
-        d_gf = torch.empty_like(gf) if gf is not None and need[5] else None
-        layers = (block.edgefn, block.nodefn, block.graphfn)
-        gW = [torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev) if need[6 + 2 * i] else None for i, l in enumerate(layers)]
-        gb = [torch.empty_like(l.bias) if (l.bias is not None and need[7 + 2 * i]) else None for i, l in enumerate(layers)]
-        grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None)
-                                  for w, b in zip(gW, gb)])
-        with torch.cuda.device(dev):
-            fused = getattr(block, "fused_backward", False)  # (GNBlock.fused_backward: the narrow edge level in one kernel)
-            query, call = (lib.gnx_block_backward_fused_typed_workspace_bytes, lib.gnx_block_backward_fused_typed) if fused else \
-                          (lib.gnx_block_backward_typed_workspace_bytes, lib.gnx_block_backward_typed)
-            if getattr(block, "narrow_backward", False):  # (GNBlock.narrow_backward wins over fused_backward)
-                query, call = lib.gnx_block_backward_narrow_workspace_bytes, lib.gnx_block_backward_narrow
-            nb = query(g._h, C.byref(p), R, _lib.ELEM_BF16)
-            ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-            check(call(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge),
-                       _ptr(gn_), _ptr(gg), R, _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
-                       torch.cuda.current_stream(dev).cuda_stream))
-        gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
-        return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
+def _cotangent(t, elem):
+    """a cotangent as the C entries read it: contiguous, and for the bf16 entries 4-byte aligned (a view may start at an odd element: copy it);
+    a missing one stays None (passed as NULL)"""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t.clone() if elem == _lib.ELEM_BF16 and t.data_ptr() % 4 else t
+
+
+def _block_pullback(ctx, gouts, elem):
+    """backward of _BlockFn (elem = ELEM_F32) and _BlockBf16Fn (ELEM_BF16).  The C entry by element type and the block's switches —
+    GNBlock.narrow_backward wins over GNBlock.fused_backward:
+                  plain                      fused_backward                    narrow_backward
+      fp32        gnx_block_backward         gnx_block_backward_fused          gnx_block_backward_narrow
+      bf16        gnx_block_backward_typed   gnx_block_backward_fused_typed    gnx_block_backward_narrow"""
+    lib = _lib.load()
+    block, g, R = ctx.block, ctx.g, ctx.R
+    bf16 = elem == _lib.ELEM_BF16
+    sv = iter(ctx.saved_tensors)
+    ef, nf, gf, eo, no, go = (next(sv) if present else None for present in ctx.slots)
+    it = iter(gouts)
+    ge, gn_, gg = (_cotangent(next(it), elem) if pr else None for pr in ctx.present)
+    keep = []
+    p = block._c(keep)
+    dev = g.device
+    need = ctx.needs_input_grad[1:]  # (g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg) -> ef is need[3]
+    d_ef = torch.empty_like(ef) if ef is not None and need[3] else None
+    d_nf = torch.empty_like(nf) if nf is not None and need[4] else None
+    d_gf = torch.empty_like(gf) if gf is not None and need[5] else None
+    layers = (block.edgefn, block.nodefn, block.graphfn)
+    gW = [torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev) if need[6 + 2 * i] else None for i, l in enumerate(layers)]
+    gb = [torch.empty_like(l.bias) if (l.bias is not None and need[7 + 2 * i]) else None for i, l in enumerate(layers)]
+    grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None)
+                              for w, b in zip(gW, gb)])
+    narrow = getattr(block, "narrow_backward", False)
+    e = (elem,) if bf16 or narrow else ()  # (gnx_block_backward and gnx_block_backward_fused are fp32 only: no element code)
+    if narrow:  # (the fused edge level at any eligible narrow width set)
+        query, call = lib.gnx_block_backward_narrow_workspace_bytes, lib.gnx_block_backward_narrow
+    elif getattr(block, "fused_backward", False):  # (the narrow edge level in one kernel)
+        query, call = (lib.gnx_block_backward_fused_typed_workspace_bytes, lib.gnx_block_backward_fused_typed) if bf16 else \
+                      (lib.gnx_block_backward_fused_workspace_bytes, lib.gnx_block_backward_fused)
+    else:
+        query, call = (lib.gnx_block_backward_typed_workspace_bytes, lib.gnx_block_backward_typed) if bf16 else \
+                      (lib.gnx_block_backward_workspace_bytes, lib.gnx_block_backward)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(int(query(g._h, C.byref(p), R, *e)), 256), dtype=torch.uint8, device=dev)
+        check(call(g._h, C.byref(p), *e, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
+                   _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
+    return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
 
 
 class _ChainBlockFn(torch.autograd.Function):
@@ -1499,37 +1477,7 @@ class _CoreFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ge, gn_, gg):
-        lib = _lib.load()
-        core, g, R = ctx.core, ctx.g, ctx.R
-        ef, nf, gf = ctx.saved_tensors
-        dev = g.device
-        cont = lambda t: None if t is None else t.contiguous()
-        ge, gn_, gg = cont(ge), cont(gn_), cont(gg)
-        keep = []
-        p = core._c(keep)
-        plist = core._param_list()
-        out = [torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=dev).t() if q.dim() == 2 else torch.empty_like(q) for q in plist]
-        gr = _core_grads(core, out)
-        d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
-        with torch.cuda.device(dev):
-            if getattr(core, "narrow_backward", False):  # (GNCore.narrow_backward: the FeedForward pullbacks in one kernel each where the core is narrow)
-                nb = lib.gnx_core_backward_narrow_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_F32)
-                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-                check(lib.gnx_core_backward_narrow(g._h, C.byref(p), _lib.ELEM_F32, None if ctx.drop is None else C.byref(ctx.drop), ef.data_ptr(),
-                                                   nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(),
-                                                   d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-                return (None, None, None, None, None, d_ef, d_nf, d_gf, *out)
-            nb = lib.gnx_core_backward_workspace_bytes(g._h, C.byref(p), R)
-            ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-            if ctx.drop is None:
-                check(lib.gnx_core_backward(g._h, C.byref(p), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg), R,
-                                            d_ef.data_ptr(), d_nf.data_ptr(), d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(),
-                                            torch.cuda.current_stream(dev).cuda_stream))
-            else:  # the forward's masks, regenerated from the call's seed
-                check(lib.gnx_core_backward_train(g._h, C.byref(p), C.byref(ctx.drop), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_),
-                                                  _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(), d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(),
-                                                  torch.cuda.current_stream(dev).cuda_stream))
-        return (None, None, None, None, None, d_ef, d_nf, d_gf, *out)
+        return (None,) * 5 + _core_pullback(ctx, (ge, gn_, gg), _lib.ELEM_F32, ctx.drop)
 
 
 def _core_grads(core, out):
@@ -1565,38 +1513,37 @@ class _CoreBf16Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ge, gn_, gg):
-        lib = _lib.load()
-        core, g, R = ctx.core, ctx.g, ctx.R
-        ef, nf, gf = ctx.saved_tensors
-        dev = g.device
+        return (None,) * 4 + _core_pullback(ctx, (ge, gn_, gg), _lib.ELEM_BF16, None)
 
-        def cot(t):  # contiguous and 4-byte aligned (a cotangent has the bf16 dtype of its output); a missing one is passed as NULL
-            if t is None:
-                return None
-            t = t.contiguous()
-            return t if t.data_ptr() % 4 == 0 else t.clone()
 
-        ge, gn_, gg = cot(ge), cot(gn_), cot(gg)
-        keep = []
-        p = core._c(keep)
-        plist = core._param_list()
-        out = [torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=dev).t() if q.dim() == 2 else torch.empty_like(q) for q in plist]
-        gr = _core_grads(core, out)
-        d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
-        with torch.cuda.device(dev):
-            if getattr(core, "narrow_backward", False):  # (GNCore.narrow_backward)
-                nb = lib.gnx_core_backward_narrow_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16)
-                ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-                check(lib.gnx_core_backward_narrow(g._h, C.byref(p), _lib.ELEM_BF16, None, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_),
-                                                   _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(), d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(),
-                                                   torch.cuda.current_stream(dev).cuda_stream))
-                return (None, None, None, None, d_ef, d_nf, d_gf, *out)
-            nb = lib.gnx_core_backward_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16)
-            ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-            check(lib.gnx_core_backward_typed(g._h, C.byref(p), _lib.ELEM_BF16, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg),
-                                              R, d_ef.data_ptr(), d_nf.data_ptr(), d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(),
-                                              torch.cuda.current_stream(dev).cuda_stream))
-        return (None, None, None, None, d_ef, d_nf, d_gf, *out)
+def _core_pullback(ctx, cots, elem, drop):
+    """backward of _CoreFn (elem = ELEM_F32; drop: the forward's gnx_dropout or None) and _CoreBf16Fn (ELEM_BF16, no Dropout): (d_ef, d_nf, d_gf,
+    *parameter gradients).  The C entry: gnx_core_backward_narrow with GNCore.narrow_backward (the FeedForward pullbacks in one kernel each where
+    the core is narrow); otherwise gnx_core_backward_typed in bf16, gnx_core_backward in fp32 — gnx_core_backward_train with a Dropout (the
+    forward's masks, regenerated from the call's seed)."""
+    lib = _lib.load()
+    core, g, R = ctx.core, ctx.g, ctx.R
+    ef, nf, gf = ctx.saved_tensors
+    dev = g.device
+    ge, gn_, gg = (_cotangent(t, elem) for t in cots)
+    keep = []
+    p = core._c(keep)
+    out = [torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=dev).t() if q.dim() == 2 else torch.empty_like(q) for q in core._param_list()]
+    gr = _core_grads(core, out)
+    d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
+    dr = None if drop is None else C.byref(drop)
+    with torch.cuda.device(dev):
+        if getattr(core, "narrow_backward", False):
+            nb, call, head = lib.gnx_core_backward_narrow_workspace_bytes(g._h, C.byref(p), R, elem), lib.gnx_core_backward_narrow, (elem, dr)
+        elif elem == _lib.ELEM_BF16:
+            nb, call, head = lib.gnx_core_backward_typed_workspace_bytes(g._h, C.byref(p), R, elem), lib.gnx_core_backward_typed, (elem,)
+        else:
+            nb = lib.gnx_core_backward_workspace_bytes(g._h, C.byref(p), R)
+            call, head = (lib.gnx_core_backward, ()) if drop is None else (lib.gnx_core_backward_train, (dr,))
+        ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
+        check(call(g._h, C.byref(p), *head, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(),
+                   d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return (d_ef, d_nf, d_gf, *out)
 
 
 class GNCoreList:

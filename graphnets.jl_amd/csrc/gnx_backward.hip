@@ -293,12 +293,19 @@ static void launch_bw_dx(dim3 grid, hipStream_t s, const float* delta, const flo
   else GNX_LAUNCH(k_bw_dx<false>, grid, dim3(256), 0, s, delta, W, rows, J, K, dX, k0, k1, direct, direct_w);
 }
 
+// The form of a block backward's edge level.  BE_NONE: no edge function output or no edges.  BE_GENERIC: Xe materialised, k_bw_delta, k_bw_dx and the
+// chunked weight-gradient reduction.  BE_MFMA: the regrouped matrix-core form.  BE_WAVE_AOT / BE_WAVE_JIT: k_bw_edge_wave (gnx_backward_narrow.hip),
+// an ahead-of-time instantiation / the kernel specialised at run time for the call's width set and element type (gnx_jit.cpp).
+enum BwEdge { BE_NONE, BE_GENERIC, BE_MFMA, BE_WAVE_AOT, BE_WAVE_JIT };
+static bool bw_wave(BwEdge e) { return e == BE_WAVE_AOT || e == BE_WAVE_JIT; }
+
 struct BwLayout {
   size_t Xe, Xn, Xg, de_, dn_, dg_, dXe, dXn, dXg, part, wt, off2, ssrc, sdst, sg, tnf, total;
 };
-// fused (gnx_block_backward_fused where it applies): the edge level is k_bw_edge_wave — no Xe and no delta_e region, dXe holds the compact
-// dXe_c [R*E][2 dn + dg], and `part` also fits the kernel's partial rows
-static BwLayout bw_layout(const gnx_graphs* h, const gnx_block_params* p, int64_t R, bool fused = false) {
+// With the edge level in k_bw_edge_wave (`fused` below) there is no Xe and no delta_e region, dXe holds the compact dXe_c [R*E][2 dn + dg], and
+// `part` also fits the kernel's partial rows
+static BwLayout bw_layout(const gnx_graphs* h, const gnx_block_params* p, int64_t R, BwEdge edge) {
+  const bool fused = bw_wave(edge);
   const size_t E = h->E, N = h->N, G = h->G;
   const size_t Ke = p->de + 2 * p->dn + p->dg, Kn = p->oe + p->dn + p->dg, Kg = p->oe + p->on + p->dg;
   BwLayout L{};
@@ -560,20 +567,62 @@ static int32_t colsum_all(const float* in, size_t rows, int d, float* out, float
 
 __global__ void k_set_off2(int* off2, int rows) { off2[0] = 0; off2[1] = rows; }
 
+// per-graph column sums of the column block [coff, coff + d) of a row tensor (rows of length ld, graph g = rows [off[g], off[g+1]), R replicas)
+// into out[(r*G + g)*out_stride + out_off ..], two stages in a fixed order: one slice per 2048 rows of the largest graph (max_rows), at most 256
+static void colsum_graphs(const float* in, bool in_bf16, int d, int ld, int coff, int rows_total, const int* off, int64_t max_rows, int G, unsigned Ru,
+                          float* part, float* out, int out_stride, int out_off, int accumulate, hipStream_t s) {
+  if (d == 0) return;
+  const int S = (int)std::min<int64_t>(std::max<int64_t>(max_rows / 2048, 1), 256);
+  if (in_bf16) GNX_LAUNCH(k_bw_colsum1<true>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, in, d, rows_total, off, S, G, part, ld, coff);
+  else GNX_LAUNCH(k_bw_colsum1<false>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, in, d, rows_total, off, S, G, part, ld, coff);
+  GNX_LAUNCH(k_bw_colsum2, dim3((unsigned)G, Ru), dim3(64), 0, s, part, d, S, G, out, out_stride, out_off, accumulate);
+}
+
 // x <- act(x) in place (a gelu FeedForward keeps its pre-activation until delta1 is formed, then becomes the hidden layer)
 __global__ void k_act_inplace(float* __restrict__ x, size_t n, int act) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < n) x[idx] = act_apply(x[idx], act);
 }
 
-// what gnx_block_backward checks of its arguments before anything else (h, p non-NULL)
-static int32_t bw_check(const gnx_graphs* h, const gnx_block_params* p, const void* ef, const void* nf, const void* gf, const void* ef_out, const void* nf_out,
-                        const void* gf_out, int64_t R) {
-  if (R <= 0 || (R > 1 && h->G != 1) || R > 65535) return fail(GNX_ERR_INVALID_ARG, "bad n_replicas");
+static bool replicas_ok(const gnx_graphs* h, int64_t R) { return R > 0 && (R == 1 || h->G == 1) && R <= 65535; }
+
+// ---- one block backward: the call record, the plan, the driver ----
+// What every block-backward entry receives.  The twelve feature-shaped tensors hold `elem` elements.
+struct BwCall {
+  const gnx_graphs* h;
+  const gnx_block_params* p;
+  int32_t elem;  // GNX_ELEM_F32 / GNX_ELEM_BF16
+  const void *ef, *nf, *gf, *ef_out, *nf_out, *gf_out, *g_ef_out, *g_nf_out, *g_gf_out;
+  int64_t R;
+  void *d_ef, *d_nf, *d_gf;
+  const gnx_block_grads* grads;
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t s;
+  // the twelve in one list: 0..8 the inputs, 9..11 the input gradients
+  void bufs(const void* b[12]) const {
+    const void* const all[12] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
+    std::copy(all, all + 12, b);
+  }
+  // the same call in fp32 on the copies of a staging (a tensor the caller did not pass, or an empty one, stays NULL)
+  BwCall staged(const Staging& st) const {
+    const void* b[12];
+    bufs(b);
+    float* a[12];
+    for (int i = 0; i < 12; ++i) a[i] = b[i] && st.n[i] > 0 ? st.at(ws, i) : nullptr;
+    return BwCall{h, p, GNX_ELEM_F32, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], R, a[9], a[10], a[11], grads, ws, ws_bytes, s};
+  }
+};
+
+// what a block backward checks of its arguments before anything else (h, p non-NULL)
+static int32_t bw_check(const BwCall& c) {
+  const gnx_graphs* h = c.h;
+  const gnx_block_params* p = c.p;
+  if (!replicas_ok(h, c.R)) return fail(GNX_ERR_INVALID_ARG, "bad n_replicas");
   const int de = p->de, dn = p->dn, dg = p->dg, oe = p->oe, on = p->on, og = p->og;
   if (de < 0 || dn < 0 || dg < 0 || oe < 0 || on < 0 || og < 0 || de + dn + dg == 0 || oe + on + og == 0) return fail(GNX_ERR_DIMS, "bad widths");
-  if ((de && !ef && h->E > 0) || (dn && !nf) || (dg && !gf)) return fail(GNX_ERR_INVALID_ARG, "a forward input with non-zero width is NULL");
-  if ((oe && !ef_out && h->E > 0) || (on && !nf_out) || (og && !gf_out)) return fail(GNX_ERR_INVALID_ARG, "a forward output with non-zero width is NULL");
+  if ((de && !c.ef && h->E > 0) || (dn && !c.nf) || (dg && !c.gf)) return fail(GNX_ERR_INVALID_ARG, "a forward input with non-zero width is NULL");
+  if ((oe && !c.ef_out && h->E > 0) || (on && !c.nf_out) || (og && !c.gf_out)) return fail(GNX_ERR_INVALID_ARG, "a forward output with non-zero width is NULL");
   const int acts[3] = {p->edgefn.act, p->nodefn.act, p->graphfn.act};
   for (int a : acts)
     if (a < 0 || a > GNX_ACT_GELU) return fail(GNX_ERR_INVALID_ARG, "unknown activation code");
@@ -588,35 +637,79 @@ static bool bw_mfma_node(const gnx_graphs* h, const gnx_block_params* p, int64_t
   return p->on > 0 && bw_use_mfma((size_t)R * h->N, p->on, p->oe + p->dn + p->dg);
 }
 
-// gnx_block_backward.  BF16 (gnx_block_backward_typed on its native path: neither level on the matrix cores): the nine feature-shaped inputs and
-// d_ef / d_nf point to bfloat16 — declared float like the feature pointers of BlockArgs, the kernels read them as the element type of the
-// launch — and d_gf, which several launches accumulate, is built in `dgf_acc` (R * G * dg floats) and rounded once at the end.
-// BF16 and fused (gnx_block_backward_fused_typed where it applies): the edge level is k_bw_edge_wave_bf16; dXe_c, the partial rows and everything
-// behind them are the fp32 fused call's.  jit_fn (gnx_block_backward_narrow on a run-time width set; implies fused): that kernel specialised at run
-// time for the call's width set and element type, launched in place of the ahead-of-time instantiation.
+// Everything that is decided about a block backward, decided once: by a query (stream NULL) and by a call, from the same arguments.
+// `want`: the entry that was called.  BW_PLAIN (gnx_block_backward, _typed) never takes the wave kernel; BW_FUSED (_fused, _fused_typed) takes an
+// ahead-of-time instantiation where there is one; BW_NARROW (_narrow) also the run-time kernel at every other eligible width set.
+// A bf16 call is native — the kernels read and write bf16 themselves, d_gf, which several launches accumulate, is built in fp32 (copy 0 of `st`) and
+// rounded once — unless a level is on the matrix cores: then it is staged (copies 0..8 of `st` the inputs widened, 9..11 the input gradients, the
+// fp32 driver on the copies, the gradients rounded back).  The workspace: the fp32 layout L in front, then `st`; every carve 256-B aligned.
+enum BwWant { BW_PLAIN, BW_FUSED, BW_NARROW };
+struct BwPlan {
+  bool bf16, staging, mfma_node;  // mfma_node: the node level is on the matrix cores
+  BwEdge edge;
+  hipFunction_t jit_fn;  // BE_WAVE_JIT: the kernel
+  BwLayout L;
+  Staging st;
+  size_t total;       // what the entry's _workspace_bytes returns; 0: h, p, R or elem rule out every call
+  const char* query;  // "workspace missing or smaller than <the query of the entry whose form this is>()"
+};
+static BwPlan bw_plan(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem, BwWant want, hipStream_t s) {
+  BwPlan pl{};
+  if (!h || !p || R <= 0 || (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16)) return pl;
+  pl.bf16 = elem == GNX_ELEM_BF16;
+  const bool mfma_e = bw_mfma_edge(h, p, R);
+  pl.mfma_node = bw_mfma_node(h, p, R);
+  pl.staging = pl.bf16 && (mfma_e || pl.mfma_node);
+  pl.edge = !(p->oe > 0 && h->E > 0) ? BE_NONE : mfma_e ? BE_MFMA : BE_GENERIC;
+  // the wave kernel, whatever provides it, takes a generic edge level of a valid call other than gelu (its pre-activation would have to be
+  // recomputed bit for bit) on a handle with wave tiles; not a staged call
+  if (want != BW_PLAIN && pl.edge == BE_GENERIC && !pl.staging && replicas_ok(h, R) && p->de >= 0 && p->dn >= 0 && p->dg >= 0 && p->on >= 0 && p->og >= 0 &&
+      h->n_wtiles() > 0 && h->d_wtiles && p->edgefn.act != GNX_ACT_GELU) {
+    static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // (diagnostic: the run-time kernel at the ahead-of-time width sets too; read once)
+    const bool aot = bw_edge_wave_has(p->de, p->dn, p->dg, p->oe);
+    // the run-time kernel of this device is obtained here (disk cache or compile, then load) unless `s` is being captured
+    if (want == BW_NARROW && (!aot || jit_all) && jit_get_bw_edge(p->de, p->dn, p->dg, p->oe, pl.bf16, s, &pl.jit_fn) == GNX_OK) pl.edge = BE_WAVE_JIT;
+    else if (aot) pl.edge = BE_WAVE_AOT;
+  }
+  pl.L = bw_layout(h, p, R, pl.edge);
+  const size_t dgf = (size_t)R * (size_t)h->G * (size_t)std::max(p->dg, 0);
+  const int d[12] = {p->de, p->dn, p->dg, p->oe, p->on, p->og, p->oe, p->on, p->og, p->de, p->dn, p->dg};
+  pl.st = !pl.bf16 ? Staging{} : pl.staging ? stage_features(pl.L.total, h, R, d, 12) : stage_layout(pl.L.total, &dgf, 1);
+  pl.total = pl.bf16 ? pl.st.total : pl.L.total;
+  pl.query = pl.edge == BE_WAVE_JIT ? "workspace missing or smaller than gnx_block_backward_narrow_workspace_bytes()"
+           : pl.edge == BE_WAVE_AOT ? (pl.bf16 ? "workspace missing or smaller than gnx_block_backward_fused_typed_workspace_bytes()"
+                                               : "workspace missing or smaller than gnx_block_backward_fused_workspace_bytes()")
+           : pl.bf16 ? "workspace missing or smaller than gnx_block_backward_typed_workspace_bytes()"
+                     : "workspace missing or smaller than gnx_block_backward_workspace_bytes()";
+  return pl;
+}
+
+// the feature pointers of a record as the float* the kernels' arguments are declared with (like the feature pointers of BlockArgs: the kernels
+// read them as the element type of the launch)
+static const float* cf(const void* q) { return static_cast<const float*>(q); }
+static float* mf(void* q) { return static_cast<float*>(q); }
+
+// The launches of a checked call on its plan's layout (bw_run below).  BF16: the twelve feature-shaped tensors are bfloat16 (a native bf16 call);
+// a staged call comes here as the fp32 call on its copies.
 template <bool BF16>
-static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
-                                const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
-                                const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
-                                void* ws, size_t ws_bytes, void* stream, float* dgf_acc, bool fused = false, hipFunction_t jit_fn = nullptr) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  DeviceTurn turn(s, matrix_core_widths(*p));  // (one matrix-core call at a time per device: gnx_internal.h)
-  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
-  if (rc) return rc;
+static int32_t block_backward_t(const BwCall& c, const BwPlan& pl) {
+  const gnx_graphs* h = c.h;
+  const gnx_block_params* p = c.p;
+  const hipStream_t s = c.s;
+  const int64_t R = c.R;
+  const float *ef = cf(c.ef), *nf = cf(c.nf), *gf = cf(c.gf), *ef_out = cf(c.ef_out), *nf_out = cf(c.nf_out), *gf_out = cf(c.gf_out);
+  const float *g_ef_out = cf(c.g_ef_out), *g_nf_out = cf(c.g_nf_out), *g_gf_out = cf(c.g_gf_out);
+  float *d_ef = mf(c.d_ef), *d_nf = mf(c.d_nf), *d_gf = mf(c.d_gf);
+  const BwLayout& L = pl.L;
+  const bool fused = bw_wave(pl.edge), mfma_e = pl.edge == BE_MFMA, have_e = pl.edge != BE_NONE;
   const int de = p->de, dn = p->dn, dg = p->dg, oe = p->oe, on = p->on, og = p->og;
   const int acts[3] = {p->edgefn.act, p->nodefn.act, p->graphfn.act};
-  if (BF16 && (bw_mfma_edge(h, p, R) || bw_mfma_node(h, p, R))) return fail(GNX_ERR_INVALID_ARG, "bf16 backward: matrix-core widths take the staging path");
   constexpr size_t kElem = BF16 ? 2 : sizeof(float);  // bytes of a feature element
-  const BwLayout L = bw_layout(h, p, R, fused);
-  if ((rc = check_ws(ws, ws_bytes, L.total, jit_fn ? "workspace missing or smaller than gnx_block_backward_narrow_workspace_bytes()"
-                                            : fused ? "workspace missing or smaller than gnx_block_backward_fused_workspace_bytes()"
-                                                    : "workspace missing or smaller than gnx_block_backward_workspace_bytes()"))) return rc;
-  rc = gnx_ensure_wide_tables(h, stream);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
+  int32_t rc = gnx_ensure_wide_tables(h, s);  // (the delta kernels read the destination of every edge; the matrix-core pullbacks the 128-row tiles)
   if (rc) return rc;
   rc = gnx_ensure_csr(h);
   if (rc) return rc;
-  char* base = static_cast<char*>(ws);
+  char* base = static_cast<char*>(c.ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   float *Xe = F(L.Xe), *Xn = F(L.Xn), *Xg = F(L.Xg), *dlt_e = F(L.de_), *dlt_n = F(L.dn_), *dlt_g = F(L.dg_);
   float *dXe = F(L.dXe), *dXn = F(L.dXn), *dXg = F(L.dXg), *part = F(L.part), *wt = F(L.wt);
@@ -626,7 +719,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   const int Ke = de + 2 * dn + dg, Kn = oe + dn + dg, Kg = oe + on + dg;
   dxe_stride = Ke;
   const gnx_block_grads none{};
-  const gnx_block_grads& gr = grads ? *grads : none;
+  const gnx_block_grads& gr = c.grads ? *c.grads : none;
   auto blocks = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
   const unsigned Ru = (unsigned)R;
 
@@ -635,15 +728,10 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   for (int64_t g = 0; g < h->G; ++g) { me = std::max(me, h->h_edge_off[g + 1] - h->h_edge_off[g]); mn = std::max(mn, h->h_node_off[g + 1] - h->h_node_off[g]); }
   auto colsum = [&](const float* in, int d, int ld, int coff, int rows_total, const int* off, int64_t max_rows, float* out, int out_stride, int out_off,
                     int accumulate, bool in_bf16 = false) {
-    if (d == 0) return;
-    const int S = (int)std::min<int64_t>(std::max<int64_t>(max_rows / 2048, 1), 256);
-    if (in_bf16) GNX_LAUNCH(k_bw_colsum1<true>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, in, d, rows_total, off, S, G, part, ld, coff);
-    else GNX_LAUNCH(k_bw_colsum1<false>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, in, d, rows_total, off, S, G, part, ld, coff);
-    GNX_LAUNCH(k_bw_colsum2, dim3((unsigned)G, Ru), dim3(64), 0, s, part, d, S, G, out, out_stride, out_off, accumulate);
+    colsum_graphs(in, in_bf16, d, ld, coff, rows_total, off, max_rows, G, Ru, part, out, out_stride, out_off, accumulate, s);
   };
-  // Edge level on the matrix cores: regrouped (see below) — the edge function's input Xe is never materialised.
+  // Edge level on the matrix cores (mfma_e): regrouped (see below) — the edge function's input Xe is never materialised.
   // (a gelu edge function needs its pre-activation, hence the materialised Xe of the generic form)
-  const bool mfma_e = bw_mfma_edge(h, p, R);
   // gelu: the level's pre-activation z = W x + b, recomputed into its delta buffer; the delta kernel then reads it in place
   // the element types the delta kernels of a level read (their EL): a bf16 call has bf16 G, and bf16 `out` unless the level is gelu
   auto el = [&](int level) { return !BF16 ? 0 : acts[level] == GNX_ACT_GELU ? 1 : 3; };
@@ -654,7 +742,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   };
   // function inputs, exactly as the forward's building blocks define them
   { ProfScope ps("bw_fn_inputs", s);
-  if (oe && E && !mfma_e && !fused && (rc = launch_fn_input(h, 0, ef, de, nf, dn, gf, dg, R, Xe, s, BF16))) return rc;
+  if (pl.edge == BE_GENERIC && (rc = launch_fn_input(h, 0, ef, de, nf, dn, gf, dg, R, Xe, s, BF16))) return rc;
   if (on && (rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s, BF16))) return rc; }
   if (og) {  // Xg = [sum_e ef' ; sum_n nf' ; gf] with parallel two-stage column sums (one workgroup per graph would walk 1M rows)
     colsum(ef_out, oe, oe, 0, E, h->d_edge_off, me, Xg, Kg, 0, 0, BF16);
@@ -678,7 +766,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
     preact(1, Xn, p->nodefn, (size_t)R * N, Kn, on, dlt_n);
     DeltaArgs a{g_nf_out, acts[1] == GNX_ACT_GELU ? dlt_n : nf_out, dlt_n, have_g ? dXg : nullptr, Kg, oe, nullptr, 0, 0, h->d_node_off, nullptr, on, N, G, acts[1], 1};
     launch_delta(a, (size_t)G * Kg, (size_t)0, Ru, s, el(1));
-    if (bw_mfma_node(h, p, R)) {  // matrix cores: dXn = dn Wn^T, dWn = Xn^T dn, dbn = column sums
+    if (pl.mfma_node) {  // matrix cores: dXn = dn Wn^T, dWn = Xn^T dn, dbn = column sums
       if ((rc = dx_mfma(h, 1, dlt_n, p->nodefn.weight, on, Kn, 0, Kn, dXn, R, wt, true, s, "bw_dx_node"))) return rc;
       if ((rc = dw_auto(dlt_n, Xn, (size_t)R * N, on, Kn, gr.nodefn, part, off2, s))) return rc;
     } else {
@@ -687,7 +775,6 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
     }
   }
   // edge level
-  const bool have_e = oe > 0 && E > 0;
   if (have_e && fused) {  // delta, dXe and the weight-gradient partials of a wave tile in registers and LDS (gnx_backward_narrow.hip)
     const bool want_dw = gr.edgefn.weight || gr.edgefn.bias;
     dxe_stride = 2 * dn + dg; dxe_col0 = de;
@@ -695,7 +782,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
                  de ? d_ef : nullptr, (d_nf && dn) || (d_gf && dg) ? dXe : nullptr, want_dw ? part : nullptr,
                  h->d_wtiles, (int)h->n_wtiles(), h->d_rowval, h->d_edge_dst, N, E, G};
     { ProfScope ps("bw_delta_edge", s);
-    if ((rc = jit_fn ? launch_bw_edge_wave_jit(jit_fn, a, R, s) : launch_bw_edge_wave(p, a, R, s, BF16))) return rc; }
+    if ((rc = pl.jit_fn ? launch_bw_edge_wave_jit(pl.jit_fn, a, R, s) : launch_bw_edge_wave(p, a, R, s, BF16))) return rc; }
     if (want_dw) {
       ProfScope ps("bw_dw_generic", s);
       GNX_LAUNCH(k_bw_dw_final, dim3(oe * (Ke + 1)), dim3(256), 0, s, part, (int)(R * (int64_t)bw_edge_wave_rows(h)), oe, Ke, gr.edgefn.weight, gr.edgefn.bias);
@@ -763,7 +850,7 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
                        de - dxe_col0, de + dn - dxe_col0, h->d_colptr, h->d_csr_ptr, h->d_csr_eid, N, E, dn, d_nf);
   }
   if (d_gf && dg) {  // d_gf[g] = dXg[g][gf cols] + sum_{n in g} dXn[n][gf cols] + sum_{e in g} dXe[e][gf cols]
-    float* const acc = BF16 ? dgf_acc : d_gf;  // (bf16: the fp32 sum, rounded once below)
+    float* const acc = BF16 ? pl.st.at(c.ws, 0) : d_gf;  // (bf16: the fp32 sum, rounded once below)
     { ProfScope ps("bw_dgf", s);
     GNX_LAUNCH(k_bw_dgf_init, blocks((size_t)R * G * dg), dim3(256), 0, s, have_g ? dXg : nullptr, Kg, oe + on, (int)(R * G), dg, acc);
     if (have_n) colsum(dXn, dg, Kn, oe + dn, N, h->d_node_off, mn, acc, dg, 0, 1);
@@ -775,37 +862,37 @@ static int32_t block_backward_t(const gnx_graphs* h, const gnx_block_params* p, 
   return GNX_OK;
 }
 
-// workspace of a bf16 backward: gnx_block_backward's, then — native path — the fp32 sum of d_gf, or — staging path — fp32 copies of the nine
-// feature-shaped inputs and the three input gradients (gnx_staging.h); every carve 256-B aligned
-struct TypedBwWs {
-  Staging st;  // native: copy 0 is the fp32 sum of d_gf; staging: copies 0..8 the inputs, 9..11 the input gradients
-  bool native;
-};
-// fused (gnx_block_backward_fused_typed where it applies, which implies native): the fused layout in front
-static TypedBwWs typed_bw_ws(const gnx_graphs* h, const gnx_block_params* p, int64_t R, bool fused = false) {
-  const bool native = !bw_mfma_edge(h, p, R) && !bw_mfma_node(h, p, R);
-  const size_t base = bw_layout(h, p, R, fused).total, dgf = (size_t)R * (size_t)h->G * (size_t)std::max(p->dg, 0);
-  const int d[12] = {p->de, p->dn, p->dg, p->oe, p->on, p->og, p->oe, p->on, p->og, p->de, p->dn, p->dg};
-  return TypedBwWs{native ? stage_layout(base, &dgf, 1) : stage_features(base, h, R, d, 12), native};
+// One block-backward call: the refusals in their order — unknown elem, NULL handle or params, the arguments, bf16 alignment, the workspace; all
+// before any launch — then the plan's form.  A staged call widens into the workspace, runs the fp32 driver on the copies and rounds the input
+// gradients back.
+static int32_t bw_run(const BwCall& c, BwWant want) {
+  if (c.elem != GNX_ELEM_F32 && c.elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (!c.h || !c.p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  const BwPlan pl = bw_plan(c.h, c.p, c.R, c.elem, want, c.s);
+  DeviceTurn turn(c.s, matrix_core_widths(*c.p));  // (one matrix-core call at a time per device: gnx_internal.h)
+  int32_t rc = bw_check(c);
+  if (rc) return rc;
+  const void* bufs[12];
+  c.bufs(bufs);
+  if (pl.bf16 && (rc = check_bf16_aligned(bufs, 12))) return rc;
+  if ((rc = check_ws(c.ws, c.ws_bytes, pl.total, pl.query))) return rc;
+  if (pl.bf16 && !pl.staging) return block_backward_t<true>(c, pl);
+  if (!pl.bf16) return block_backward_t<false>(c, pl);
+  if ((rc = stage_widen(pl.st, c.ws, bufs, 0, 9, c.s))) return rc;
+  rc = block_backward_t<false>(c.staged(pl.st), pl);
+  return rc ? rc : stage_round(pl.st, c.ws, bufs, 9, 12, c.s);
 }
 
-// the typed entry points' feature pointers as the float* the kernels' arguments are declared with
-static const float* cf(const void* q) { return static_cast<const float*>(q); }
-static float* mf(void* q) { return static_cast<float*>(q); }
-
-// the fused bf16 call once it applies: gnx_block_backward_fused_typed (jit_fn == nullptr: the ahead-of-time kernel) and gnx_block_backward_narrow
-static int32_t bw_fused_bf16(const gnx_graphs* h, const gnx_block_params* p, const void* ef, const void* nf, const void* gf, const void* ef_out,
-                             const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R,
-                             void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws, size_t ws_bytes, void* stream, hipFunction_t jit_fn) {
-  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
-  if (rc) return rc;
-  const void* const bufs[12] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
-  if ((rc = check_bf16_aligned(bufs, 12))) return rc;
-  const Staging w = typed_bw_ws(h, p, R, true).st;
-  if ((rc = check_ws(ws, ws_bytes, w.total, jit_fn ? "workspace missing or smaller than gnx_block_backward_narrow_workspace_bytes()"
-                                                   : "workspace missing or smaller than gnx_block_backward_fused_typed_workspace_bytes()"))) return rc;
-  return block_backward_t<true>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
-                                mf(d_nf), mf(d_gf), grads, ws, w.base, stream, w.at(ws, 0), true, jit_fn);
+// a _workspace_bytes entry of either family: its plan's total, and what the backward reads of the handle built here, outside any capture (a
+// failure resurfaces in the backward)
+static size_t query_total(const gnx_graphs* h, size_t total) {
+  if (total == 0) return 0;
+  (void)gnx_ensure_wide_tables(h);
+  (void)gnx_ensure_csr(h);
+  return total;
+}
+static size_t bw_query(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem, BwWant want) {
+  return query_total(h, bw_plan(h, p, R, elem, want, nullptr).total);
 }
 
 }  // namespace gnx
@@ -814,167 +901,78 @@ using namespace gnx;
 
 extern "C" {
 
-size_t gnx_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  if (!h || !p || R <= 0) return 0;
-  (void)gnx_ensure_wide_tables(h);  // what the backward reads is built here, outside any capture (a failure resurfaces in the backward)
-  (void)gnx_ensure_csr(h);
-  return bw_layout(h, p, R).total;
-}
+// Every call entry: the record, then bw_run with what the entry wants.  Every _applies: "the plan's edge form is the wave kernel".  Every
+// _workspace_bytes: the plan's total.  (gnx_block_backward_narrow's queries may obtain the run-time kernel; its call never does so inside a capture.)
+size_t gnx_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) { return bw_query(h, p, R, GNX_ELEM_F32, BW_PLAIN); }
 
 int32_t gnx_block_backward(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
                            const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
                            const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
                            void* ws, size_t ws_bytes, void* stream) {
-  return block_backward_t<false>(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr);
-}
-
-// what the fused edge level asks of a call whatever provides its kernel (the ahead-of-time list, the run-time specialiser)
-static bool bw_fused_conditions(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  if (!h || !p || R <= 0 || (R > 1 && h->G != 1) || R > 65535) return false;
-  if (p->de < 0 || p->dn < 0 || p->dg < 0 || p->oe <= 0 || p->on < 0 || p->og < 0) return false;
-  if (h->E <= 0 || h->n_wtiles() <= 0 || !h->d_wtiles) return false;
-  if (p->edgefn.act == GNX_ACT_GELU) return false;  // (its pre-activation would have to be recomputed bit for bit)
-  return !bw_mfma_edge(h, p, R);
+  return bw_run(BwCall{h, p, GNX_ELEM_F32, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
+                       (hipStream_t)stream}, BW_PLAIN);
 }
 
 int32_t gnx_block_backward_fused_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  if (!bw_fused_conditions(h, p, R)) return 0;  // (first: it refuses NULL params)
-  return bw_edge_wave_has(p->de, p->dn, p->dg, p->oe) ? 1 : 0;
+  return bw_wave(bw_plan(h, p, R, GNX_ELEM_F32, BW_FUSED, nullptr).edge) ? 1 : 0;
 }
 
-size_t gnx_block_backward_fused_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) {
-  if (!gnx_block_backward_fused_applies(h, p, R)) return gnx_block_backward_workspace_bytes(h, p, R);
-  (void)gnx_ensure_wide_tables(h);  // (as the generic query: outside any capture)
-  (void)gnx_ensure_csr(h);
-  return bw_layout(h, p, R, true).total;
-}
+size_t gnx_block_backward_fused_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R) { return bw_query(h, p, R, GNX_ELEM_F32, BW_FUSED); }
 
 int32_t gnx_block_backward_fused(const gnx_graphs* h, const gnx_block_params* p, const float* ef, const float* nf, const float* gf,
                                  const float* ef_out, const float* nf_out, const float* gf_out, const float* g_ef_out, const float* g_nf_out,
                                  const float* g_gf_out, int64_t R, float* d_ef, float* d_nf, float* d_gf, const gnx_block_grads* grads,
                                  void* ws, size_t ws_bytes, void* stream) {
-  const bool fused = gnx_block_backward_fused_applies(h, p, R) != 0;
-  return block_backward_t<false>(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr,
-                                 fused);
+  return bw_run(BwCall{h, p, GNX_ELEM_F32, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
+                       (hipStream_t)stream}, BW_FUSED);
 }
 
 size_t gnx_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
-  if (elem == GNX_ELEM_F32) return gnx_block_backward_workspace_bytes(h, p, R);
-  if (elem != GNX_ELEM_BF16 || !h || !p || R <= 0) return 0;
-  (void)gnx_ensure_wide_tables(h);  // (as the fp32 query: outside any capture)
-  (void)gnx_ensure_csr(h);
-  return typed_bw_ws(h, p, R).st.total;
+  return bw_query(h, p, R, elem, BW_PLAIN);
 }
 
 int32_t gnx_block_backward_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                  const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
                                  const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (elem == GNX_ELEM_F32)
-    return gnx_block_backward(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf),
-                              mf(d_gf), grads, ws, ws_bytes, stream);
-  if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
-  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  int32_t rc = bw_check(h, p, ef, nf, gf, ef_out, nf_out, gf_out, R);
-  if (rc) return rc;
-  const void* const bufs[12] = {ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
-  if ((rc = check_bf16_aligned(bufs, 12))) return rc;
-  const TypedBwWs tw = typed_bw_ws(h, p, R);
-  const Staging& w = tw.st;
-  if ((rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_block_backward_typed_workspace_bytes()"))) return rc;
-  if (tw.native)  // the kernels read and write bf16 themselves (declared float, like the feature pointers of BlockArgs)
-    return block_backward_t<true>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
-                                  mf(d_nf), mf(d_gf), grads, ws, w.base, stream, w.at(ws, 0));
-  // matrix-core widths: widen into the workspace, the fp32 backward (its own DeviceTurn), round the input gradients
-  const hipStream_t s = (hipStream_t)stream;
-  if ((rc = stage_widen(w, ws, bufs, 0, 9, s))) return rc;
-  auto st = [&](int i) -> float* { return bufs[i] && w.n[i] > 0 ? w.at(ws, i) : nullptr; };  // the copy of a tensor the caller passed
-  rc = gnx_block_backward(h, p, st(0), st(1), st(2), st(3), st(4), st(5), st(6), st(7), st(8), R, st(9), st(10), st(11), grads, ws, w.base, stream);
-  return rc ? rc : stage_round(w, ws, bufs, 9, 12, s);
+  return bw_run(BwCall{h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
+                       (hipStream_t)stream}, BW_PLAIN);
 }
 
 int32_t gnx_block_backward_fused_typed_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
-  if (elem == GNX_ELEM_F32) return gnx_block_backward_fused_applies(h, p, R);
-  if (elem != GNX_ELEM_BF16 || !gnx_block_backward_fused_applies(h, p, R)) return 0;
-  return bw_mfma_edge(h, p, R) || bw_mfma_node(h, p, R) ? 0 : 1;  // (the typed call's native path: the kernels read and write bf16 themselves)
+  return bw_wave(bw_plan(h, p, R, elem, BW_FUSED, nullptr).edge) ? 1 : 0;
 }
 
 size_t gnx_block_backward_fused_typed_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
-  if (elem == GNX_ELEM_F32) return gnx_block_backward_fused_workspace_bytes(h, p, R);
-  if (!gnx_block_backward_fused_typed_applies(h, p, R, elem)) return gnx_block_backward_typed_workspace_bytes(h, p, R, elem);
-  (void)gnx_ensure_wide_tables(h);  // (as the fp32 query: outside any capture)
-  (void)gnx_ensure_csr(h);
-  return typed_bw_ws(h, p, R, true).st.total;
+  return bw_query(h, p, R, elem, BW_FUSED);
 }
 
 int32_t gnx_block_backward_fused_typed(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                        const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
                                        const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws,
                                        size_t ws_bytes, void* stream) {
-  if (elem == GNX_ELEM_F32)
-    return gnx_block_backward_fused(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
-                                    mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream);
-  if (!gnx_block_backward_fused_typed_applies(h, p, R, elem))  // (also: a bad elem, a NULL handle or params — refused there with its statuses)
-    return gnx_block_backward_typed(h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
-                                    stream);
-  return bw_fused_bf16(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, nullptr);
+  return bw_run(BwCall{h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
+                       (hipStream_t)stream}, BW_FUSED);
 }
 
 // ---- gnx_block_backward_narrow: the fused edge level at any eligible narrow width set ----
-namespace {
-enum NarrowBw { NB_GENERIC, NB_AOT, NB_JIT };
-// The form a narrow call takes, decided in ONE place for the two queries and the call.  NB_AOT: gnx_block_backward_fused_typed applies (and
-// GNX_JIT_ALL does not ask for the run-time kernel there).  NB_JIT: the width set is eligible (jit_bw_edge_eligible), the other conditions of the
-// fused call hold and the kernel of this device is loaded — obtained here (disk cache or compile, then load) unless `s` is being captured.
-NarrowBw narrow_bw_form(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem, hipStream_t s, hipFunction_t* fn) {
-  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return NB_GENERIC;
-  static const bool jit_all = getenv("GNX_JIT_ALL") != nullptr;  // (diagnostic: the run-time kernel at the ahead-of-time width sets too; read once)
-  const bool aot = gnx_block_backward_fused_typed_applies(h, p, R, elem) != 0;
-  if (aot && !jit_all) return NB_AOT;
-  if (!bw_fused_conditions(h, p, R)) return NB_GENERIC;
-  if (elem == GNX_ELEM_BF16 && bw_mfma_node(h, p, R)) return NB_GENERIC;  // (the typed call's staging path)
-  if (jit_get_bw_edge(p->de, p->dn, p->dg, p->oe, elem == GNX_ELEM_BF16, s, fn) == GNX_OK) return NB_JIT;
-  return aot ? NB_AOT : NB_GENERIC;
-}
-}  // namespace
-
 int32_t gnx_block_backward_narrow_applies(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
-  hipFunction_t fn = nullptr;
-  return narrow_bw_form(h, p, R, elem, nullptr, &fn) != NB_GENERIC ? 1 : 0;
+  return bw_wave(bw_plan(h, p, R, elem, BW_NARROW, nullptr).edge) ? 1 : 0;
 }
 
 size_t gnx_block_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_block_params* p, int64_t R, int32_t elem) {
-  hipFunction_t fn = nullptr;
-  switch (narrow_bw_form(h, p, R, elem, nullptr, &fn)) {
-    case NB_AOT: return gnx_block_backward_fused_typed_workspace_bytes(h, p, R, elem);
-    case NB_JIT: break;
-    default: return gnx_block_backward_typed_workspace_bytes(h, p, R, elem);
-  }
-  (void)gnx_ensure_wide_tables(h);  // (as the generic query: outside any capture)
-  (void)gnx_ensure_csr(h);
-  return elem == GNX_ELEM_BF16 ? typed_bw_ws(h, p, R, true).st.total : bw_layout(h, p, R, true).total;
+  return bw_query(h, p, R, elem, BW_NARROW);
 }
 
 int32_t gnx_block_backward_narrow(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                   const void* ef_out, const void* nf_out, const void* gf_out, const void* g_ef_out, const void* g_nf_out,
                                   const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf, const gnx_block_grads* grads, void* ws,
                                   size_t ws_bytes, void* stream) {
-  hipFunction_t fn = nullptr;
-  switch (narrow_bw_form(h, p, R, elem, (hipStream_t)stream, &fn)) {
-    case NB_AOT:
-      return gnx_block_backward_fused_typed(h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws,
-                                            ws_bytes, stream);
-    case NB_JIT: break;
-    default:  // (also: a bad elem, a NULL handle or params — refused there with its statuses)
-      return gnx_block_backward_typed(h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
-                                      stream);
-  }
-  if (elem == GNX_ELEM_BF16)
-    return bw_fused_bf16(h, p, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, fn);
-  return block_backward_t<false>(h, p, cf(ef), cf(nf), cf(gf), cf(ef_out), cf(nf_out), cf(gf_out), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef),
-                                 mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream, nullptr, true, fn);
+  return bw_run(BwCall{h, p, elem, ef, nf, gf, ef_out, nf_out, gf_out, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes,
+                       (hipStream_t)stream}, BW_NARROW);
 }
 
+}  // extern "C"
 
 // ---- GNCore backward ----
 namespace {
@@ -983,7 +981,7 @@ struct CoreBwLayout {
 };
 // narrow (gnx_core_backward_narrow where it applies): step 2 is k_core_bw_narrow — no h, dh, wt or tcs region, and `part` fits the kernel's
 // partial rows (both Denses of an entity side by side) next to the column-sum slices of step 4
-CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool narrow = false) {
+CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool narrow) {
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
   const int d[3] = {p->block.de, p->block.dn, p->block.dg};
   CoreBwLayout L{};
@@ -1023,66 +1021,108 @@ CoreBwLayout core_bw_layout(const gnx_graphs* h, const gnx_core_params* p, int64
   L.total = o + 256;
   return L;
 }
-// gnx_core_backward_typed, GNX_ELEM_BF16: the fp32 layout, then an fp32 copy of each upstream gradient, every carve 256-B aligned.  (x and d_x
-// need none: the LayerNorm kernels read and write bf16 themselves.)
-Staging typed_core_bw_ws(const gnx_graphs* h, const gnx_core_params* p, int64_t R, bool narrow = false) {
+
+// What every core-backward entry receives.  The nine feature-shaped tensors hold `elem` elements.
+struct CoreBwCall {
+  const gnx_graphs* h;
+  const gnx_core_params* p;
+  int32_t elem;  // GNX_ELEM_F32 / GNX_ELEM_BF16
+  const gnx_dropout* dropout;  // gnx_core_backward_train, gnx_core_backward_narrow: the forward's Dropout, or NULL
+  const void *ef, *nf, *gf, *g_ef_out, *g_nf_out, *g_gf_out;
+  int64_t R;
+  void *d_ef, *d_nf, *d_gf;
+  const gnx_core_grads* grads;
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t s;
+};
+
+// What is wrong with a GNCore backward's (h, p, R), in the order the call reports it, or nullptr.  (h, p non-NULL)
+const char kCoreBwDims[] = "GNCore needs dims => dims with all(dims .> 0)";  // (GNX_ERR_DIMS; the others GNX_ERR_INVALID_ARG)
+const char* core_bw_valid(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
+  const gnx_block_params& b = p->block;
+  if (b.de <= 0 || b.dn <= 0 || b.dg <= 0 || b.oe != b.de || b.on != b.dn || b.og != b.dg) return kCoreBwDims;
+  if (!replicas_ok(h, R)) return "bad n_replicas";
+  for (int t = 0; t < 3; ++t)
+    if (p->ff[t].fc2.act != GNX_ACT_IDENTITY) return "core backward: fc2 must be identity";
+  return nullptr;
+}
+
+// Everything that is decided about a core backward, decided once per query and once per call.  `want_narrow`: gnx_core_backward_narrow was called.
+// narrow: k_core_bw_narrow takes the FeedForward pullbacks — a rule of the parameters alone (not of the row counts): a valid core, all three widths
+// narrow, hidden activations the kernel knows (identity / relu — the forward's combined kernel takes the same).
+// bf16: behind the fp32 layout L, `st` holds an fp32 copy of each upstream gradient, every carve 256-B aligned.  (x and d_x need none: the
+// LayerNorm kernels read and write bf16 themselves.)
+struct CoreBwPlan {
+  bool bf16, narrow;
+  const gnx_dropout* dr;  // the active Dropout, or nullptr
+  CoreBwLayout L;
+  Staging st;
+  size_t total;       // what the entry's _workspace_bytes returns; 0: h, p, R or elem rule out every call
+  const char* query;  // "workspace missing or smaller than <the query of the entry whose form this is>()"
+};
+CoreBwPlan core_bw_plan(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem, const gnx_dropout* dropout, bool want_narrow) {
+  CoreBwPlan pl{};
+  if (!h || !p || R <= 0 || (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16)) return pl;
+  pl.bf16 = elem == GNX_ELEM_BF16;
+  pl.dr = dropout_active(dropout) ? dropout : nullptr;
   const int d[3] = {p->block.de, p->block.dn, p->block.dg};
-  return stage_features(core_bw_layout(h, p, R, narrow).total, h, R, d, 3);
+  pl.narrow = want_narrow && !core_bw_valid(h, p, R);
+  for (int t = 0; t < 3; ++t)
+    pl.narrow = pl.narrow && core_narrow_width(d[t]) && p->ff[t].fc1.act >= GNX_ACT_IDENTITY && p->ff[t].fc1.act <= GNX_ACT_RELU;
+  pl.L = core_bw_layout(h, p, R, pl.narrow);
+  pl.st = pl.bf16 ? stage_features(pl.L.total, h, R, d, 3) : Staging{};
+  pl.total = pl.bf16 ? pl.st.total : pl.L.total;
+  pl.query = pl.narrow ? "workspace missing or smaller than gnx_core_backward_narrow_workspace_bytes()"
+           : pl.bf16   ? "workspace missing or smaller than gnx_core_backward_typed_workspace_bytes()"
+                       : "workspace missing or smaller than gnx_core_backward_workspace_bytes()";
+  return pl;
+}
+size_t core_bw_query(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem, bool want_narrow) {
+  return query_total(h, core_bw_plan(h, p, R, elem, nullptr, want_narrow).total);
 }
 }  // namespace
 
-size_t gnx_core_backward_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R) {
-  if (!h || !p || R <= 0) return 0;
-  (void)gnx_ensure_wide_tables(h);
-  (void)gnx_ensure_csr(h);
-  return core_bw_layout(h, p, R).total;
-}
-
-}  // extern "C"
-
-// `dr` (gnx_core_backward_train): the FeedForwards' outputs were multiplied by the Dropout masks of *dr in the forward
-// (gnx_core_forward_train, csrc/gnx_dropout.hip), so the upstream gradient of every FeedForward branch is g_out .* mask — the mask
-// regenerated from (seed, entity, element); the block branch and the residual see g_out as it is.
-// BF16 (gnx_core_backward_typed): the nine feature-shaped tensors hold bfloat16 elements (declared float, like the feature pointers of BlockArgs).
+// The forward's Dropout (pl.dr: gnx_core_forward_train, csrc/gnx_dropout.hip) multiplied the FeedForwards' outputs by its masks, so the upstream
+// gradient of every FeedForward branch is g_out .* mask — the mask regenerated from (seed, entity, element); the block branch and the residual
+// see g_out as it is.
+// BF16 (gnx_core_backward_typed): the nine feature-shaped tensors hold bfloat16 elements (read as float*, like the feature pointers of BlockArgs).
 // Only the LayerNorm kernels touch x and d_x — steps 1 and 4 — and they take the element type; the upstream gradients are widened once into
 // fp32 copies behind the fp32 layout, which every consumer below reads; the kernel forms are chosen from the CALLER's addresses as before.
-// narrow (gnx_core_backward_narrow where it applies): step 2 of an entity is one k_core_bw_narrow launch and the two finishers of its partial rows,
-// on the narrow layout; steps 1, 3 and 4 are the same launches.
+// pl.narrow (gnx_core_backward_narrow where it applies): step 2 of an entity is one k_core_bw_narrow launch and the two finishers of its partial
+// rows, on the narrow layout; steps 1, 3 and 4 are the same launches.
 template <bool BF16>
-static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p, const gnx_dropout* dr, const float* ef, const float* nf, const float* gf,
-                                  const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
-                                  float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream, bool narrow = false) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+static int32_t core_backward_impl(const CoreBwCall& c, const CoreBwPlan& pl) {
+  const gnx_graphs* h = c.h;
+  const gnx_core_params* p = c.p;
+  const hipStream_t s = c.s;
+  const int64_t R = c.R;
+  const float *ef = cf(c.ef), *nf = cf(c.nf), *gf = cf(c.gf), *g_ef_out = cf(c.g_ef_out), *g_nf_out = cf(c.g_nf_out), *g_gf_out = cf(c.g_gf_out);
   const gnx_block_params& b = p->block;
   DeviceTurn turn(s, matrix_core_widths(b));
-  if (b.de <= 0 || b.dn <= 0 || b.dg <= 0 || b.oe != b.de || b.on != b.dn || b.og != b.dg) return fail(GNX_ERR_DIMS, "GNCore needs dims => dims with all(dims .> 0)");
+  const char* const bad = core_bw_valid(h, p, R);
+  if (bad == kCoreBwDims) return fail(GNX_ERR_DIMS, bad);
   if ((!ef && h->E > 0) || !nf || !gf) return fail(GNX_ERR_INVALID_ARG, "GNCore needs ef, nf and gf");
-  if (R <= 0 || (R > 1 && h->G != 1) || R > 65535) return fail(GNX_ERR_INVALID_ARG, "bad n_replicas");
-  for (int t = 0; t < 3; ++t) {
-    if (p->ff[t].fc2.act != GNX_ACT_IDENTITY) return fail(GNX_ERR_INVALID_ARG, "core backward: fc2 must be identity");
-  }
+  if (bad) return fail(GNX_ERR_INVALID_ARG, bad);
   const float* x[3] = {ef, nf, gf};
   const float* gout[3] = {g_ef_out, g_nf_out, g_gf_out};  // what the consumers read (BF16: the fp32 copies, set below)
   const float* const gcaller[3] = {g_ef_out, g_nf_out, g_gf_out};
-  float* dxo[3] = {d_ef, d_nf, d_gf};
+  float* dxo[3] = {mf(c.d_ef), mf(c.d_nf), mf(c.d_gf)};
   int32_t rc;
   if constexpr (BF16) {
-    const void* const bufs[9] = {ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
+    const void* const bufs[9] = {c.ef, c.nf, c.gf, c.g_ef_out, c.g_nf_out, c.g_gf_out, c.d_ef, c.d_nf, c.d_gf};
     if ((rc = check_bf16_aligned(bufs, 9))) return rc;
   }
-  const CoreBwLayout L = core_bw_layout(h, p, R, narrow);
-  const Staging tw = BF16 ? typed_core_bw_ws(h, p, R, narrow) : Staging{};
-  if ((rc = check_ws(ws, ws_bytes, BF16 ? tw.total : L.total, narrow ? "workspace missing or smaller than gnx_core_backward_narrow_workspace_bytes()"
-                                                              : BF16 ? "workspace missing or smaller than gnx_core_backward_typed_workspace_bytes()"
-                                                                     : "workspace missing or smaller than gnx_core_backward_workspace_bytes()"))) return rc;
-  if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
-  char* base = static_cast<char*>(ws);
+  const CoreBwLayout& L = pl.L;
+  const Staging& tw = pl.st;
+  if ((rc = check_ws(c.ws, c.ws_bytes, pl.total, pl.query))) return rc;
+  if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw;
+  char* base = static_cast<char*>(c.ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
   const int d[3] = {b.de, b.dn, b.dg};
   const gnx_core_grads none{};
-  const gnx_core_grads& gr = grads ? *grads : none;
+  const gnx_core_grads& gr = c.grads ? *c.grads : none;
   if constexpr (BF16) {  // a NULL upstream gradient stays NULL; one without rows is never read
     for (int t = 0; t < 3; ++t) {
       if (!gcaller[t] || tw.n[t] == 0) continue;
@@ -1099,7 +1139,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
     if ((rc = BF16 ? launch_layernorm2_bf16(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, F(L.l1[t]), F(L.l2[t]), s)
                    : launch_layernorm2(x[t], rows[t], d[t], p->ln1[t], p->ln2[t], p->eps, p->eps_mode, F(L.l1[t]), F(L.l2[t]), s))) return rc;
   if ((rc = gnx_block_forward(h, &b, F(L.l1[0]), F(L.l1[1]), F(L.l1[2]), R, F(L.bout[0]), F(L.bout[1]), F(L.bout[2]), base + L.blk_fw,
-                              gnx_block_workspace_bytes(h, &b, R), 0, stream))) return rc;
+                              gnx_block_workspace_bytes(h, &b, R), 0, s))) return rc;
   // 2. FeedForward pullback per entity: f = W2 h + b2, h = act1(W1 z + b1), z = gn2(x); upstream of f is g_out
   for (int t = 0; t < 3; ++t) {
     float* dz2 = F(L.dz2[t]);
@@ -1114,11 +1154,11 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
     }
     float* hbuf = F(L.h); float* dh = F(L.dh);
     const float* gff = gout[t];  // upstream of the FeedForward branch
-    if (dropout_active(dr)) {
-      if ((rc = launch_dropout(*dr, t, rows[t] * (size_t)D, gout[t], F(L.t1), 1, s))) return rc;  // (t1 is free until step 4)
+    if (pl.dr) {
+      if ((rc = launch_dropout(*pl.dr, t, rows[t] * (size_t)D, gout[t], F(L.t1), 1, s))) return rc;  // (t1 is free until step 4)
       gff = F(L.t1);
     }
-    if (narrow) {  // the whole pullback of this FeedForward in one kernel (gnx_core_bw_narrow.hip), then one finisher per Dense
+    if (pl.narrow) {  // the whole pullback of this FeedForward in one kernel (gnx_core_bw_narrow.hip), then one finisher per Dense
       const size_t nwg = core_bw_narrow_rows(rows[t], D);
       const gnx_ffn_grad& gf_ = gr.ff[t];
       float* part1 = gf_.fc1.weight || gf_.fc1.bias ? part : nullptr;
@@ -1187,7 +1227,7 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
   }
   // 3. block pullback: inputs gn1(x), outputs recomputed above, upstream g_out -> gradients w.r.t. gn1(x)
   if ((rc = gnx_block_backward(h, &b, F(L.l1[0]), F(L.l1[1]), F(L.l1[2]), F(L.bout[0]), F(L.bout[1]), F(L.bout[2]), gout[0], gout[1], gout[2], R,
-                               F(L.dl1[0]), F(L.dl1[1]), F(L.dl1[2]), &gr.block, base + L.blk_bw, gnx_block_backward_workspace_bytes(h, &b, R), stream))) return rc;
+                               F(L.dl1[0]), F(L.dl1[1]), F(L.dl1[2]), &gr.block, base + L.blk_bw, gnx_block_backward_workspace_bytes(h, &b, R), s))) return rc;
   // 4. LayerNorm pullbacks (both norms at once) + residual; gamma/beta gradients as column sums over all rows
   for (int t = 0; t < 3; ++t) {
     if (rows[t] == 0) {  // (sums over nothing: zeros, not what the buffers held)
@@ -1230,68 +1270,51 @@ static int32_t core_backward_impl(const gnx_graphs* h, const gnx_core_params* p,
   return GNX_OK;
 }
 
+// one core-backward call on its plan (h, p non-NULL)
+static int32_t core_bw_run(const CoreBwCall& c, bool want_narrow) {
+  const CoreBwPlan pl = core_bw_plan(c.h, c.p, c.R, c.elem, c.dropout, want_narrow);
+  return !pl.bf16 ? core_backward_impl<false>(c, pl) : core_backward_impl<true>(c, pl);
+}
+static const char kBadElem[] = "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16", kNullCore[] = "NULL handle or params";
+
 extern "C" {
+size_t gnx_core_backward_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R) { return core_bw_query(h, p, R, GNX_ELEM_F32, false); }
 int32_t gnx_core_backward(const gnx_graphs* h, const gnx_core_params* p, const float* ef, const float* nf, const float* gf,
                           const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                           float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  return core_backward_impl<false>(h, p, nullptr, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, kNullCore);
+  return core_bw_run(CoreBwCall{h, p, GNX_ELEM_F32, nullptr, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, (hipStream_t)stream}, false);
 }
 int32_t gnx_core_backward_train(const gnx_graphs* h, const gnx_core_params* p, const gnx_dropout* dropout, const float* ef, const float* nf,
                                 const float* gf, const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef,
                                 float* d_nf, float* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   if (int32_t rc = check_dropout(dropout)) return rc;
-  return core_backward_impl<false>(h, p, dropout, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, kNullCore);
+  return core_bw_run(CoreBwCall{h, p, GNX_ELEM_F32, dropout, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, (hipStream_t)stream}, false);
 }
-size_t gnx_core_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) {
-  if (elem == GNX_ELEM_F32) return gnx_core_backward_workspace_bytes(h, p, R);
-  if (elem != GNX_ELEM_BF16 || gnx_core_backward_workspace_bytes(h, p, R) == 0) return 0;  // (the fp32 query builds the tables, outside any capture)
-  return typed_core_bw_ws(h, p, R).total;
-}
+size_t gnx_core_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) { return core_bw_query(h, p, R, elem, false); }
 int32_t gnx_core_backward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                 const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf,
                                 const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  if (elem == GNX_ELEM_F32)
-    return gnx_core_backward(h, p, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream);
-  if (elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
-  return core_backward_impl<true>(h, p, nullptr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws,
-                                  ws_bytes, stream);
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, kNullCore);
+  return core_bw_run(CoreBwCall{h, p, elem, nullptr, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, (hipStream_t)stream}, false);
 }
 
-// gnx_core_backward_narrow: where k_core_bw_narrow takes the FeedForward pullbacks.  A rule of the parameters alone (not of the row counts): a
-// valid core, all three widths narrow, hidden activations the kernel knows (identity / relu — the forward's combined kernel takes the same).
+// gnx_core_backward_narrow: where k_core_bw_narrow takes the FeedForward pullbacks (CoreBwPlan::narrow)
 int32_t gnx_core_backward_narrow_applies(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) {
-  if (!h || !p || (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16)) return 0;
-  if (R <= 0 || (R > 1 && h->G != 1) || R > 65535) return 0;
-  const gnx_block_params& b = p->block;
-  if (b.de <= 0 || b.dn <= 0 || b.dg <= 0 || b.oe != b.de || b.on != b.dn || b.og != b.dg) return 0;
-  const int d[3] = {b.de, b.dn, b.dg};
-  for (int t = 0; t < 3; ++t)
-    if (!core_narrow_width(d[t]) || p->ff[t].fc2.act != GNX_ACT_IDENTITY || p->ff[t].fc1.act < GNX_ACT_IDENTITY || p->ff[t].fc1.act > GNX_ACT_RELU) return 0;
-  return 1;
+  return core_bw_plan(h, p, R, elem, nullptr, true).narrow ? 1 : 0;
 }
-size_t gnx_core_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) {
-  if (!gnx_core_backward_narrow_applies(h, p, R, elem)) return gnx_core_backward_typed_workspace_bytes(h, p, R, elem);
-  (void)gnx_ensure_wide_tables(h);  // (as the generic query: outside any capture)
-  (void)gnx_ensure_csr(h);
-  return elem == GNX_ELEM_BF16 ? typed_core_bw_ws(h, p, R, true).total : core_bw_layout(h, p, R, true).total;
-}
+size_t gnx_core_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem) { return core_bw_query(h, p, R, elem, true); }
 int32_t gnx_core_backward_narrow(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const gnx_dropout* dropout, const void* ef, const void* nf,
                                  const void* gf, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf,
                                  void* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, kNullCore);
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
   if (int32_t rc = check_dropout(dropout)) return rc;
-  const gnx_dropout* dr = dropout_active(dropout) ? dropout : nullptr;
-  if (dr && elem == GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "bf16 core backward with an active Dropout: no typed training-mode forward exists");
-  if (!gnx_core_backward_narrow_applies(h, p, R, elem)) {
-    if (dr) return gnx_core_backward_train(h, p, dr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws, ws_bytes, stream);
-    return gnx_core_backward_typed(h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream);
-  }
-  if (elem == GNX_ELEM_BF16)
-    return core_backward_impl<true>(h, p, nullptr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws,
-                                    ws_bytes, stream, true);
-  return core_backward_impl<false>(h, p, dr, cf(ef), cf(nf), cf(gf), cf(g_ef_out), cf(g_nf_out), cf(g_gf_out), R, mf(d_ef), mf(d_nf), mf(d_gf), grads, ws, ws_bytes,
-                                   stream, true);
+  if (dropout_active(dropout) && elem == GNX_ELEM_BF16)
+    return fail(GNX_ERR_INVALID_ARG, "bf16 core backward with an active Dropout: no typed training-mode forward exists");
+  return core_bw_run(CoreBwCall{h, p, elem, dropout, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, (hipStream_t)stream}, true);
 }
 }  // extern "C"
 
@@ -1533,9 +1556,7 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
     if (on > 0) {
       int64_t mn = 1;
       for (int64_t g = 0; g < h->G; ++g) mn = std::max(mn, h->h_node_off[g + 1] - h->h_node_off[g]);
-      const int S = (int)std::min<int64_t>(std::max<int64_t>(mn / 2048, 1), 256);
-      GNX_LAUNCH(k_bw_colsum1<false>, dim3((unsigned)S * (unsigned)G, 1, Ru), dim3(256), 0, s, dXn, dg, N, h->d_node_off, S, G, part, Kn, oe + dn);
-      GNX_LAUNCH(k_bw_colsum2, dim3((unsigned)G, Ru), dim3(64), 0, s, part, dg, S, G, d_gf, dg, 0, 1);
+      colsum_graphs(dXn, false, dg, Kn, oe + dn, N, h->d_node_off, mn, G, Ru, part, d_gf, dg, 0, 1, s);
     }
     if (og > 0 && (rc = add_cols(dXg, Kg, oe + on, rows[2], dg, d_gf, 1, s))) return rc;
   }
