@@ -3,9 +3,12 @@
 (/root/reference/examples/sort/sort.jl:31-81,116-134): every graph is a fully connected set of N random numbers, the
 model (GNBlock -> GNCoreList -> GNBlock) learns, per node, whether the node holds the minimum, and per edge i->j whether
 x_j is the successor of x_i in sorted order; loss = logitcrossentropy on flatunpaddednf + flatunpaddedef.
-    python examples/train_sort.py [--iters 300] [--graphs 64] [--n 8] [--width 16] [--bf16]
+    python examples/train_sort.py [--iters 300] [--graphs 64] [--n 8] [--width 16] [--bf16] [--dropout P --typed-dropout]
 --bf16: the features are batched as bfloat16 and stay bfloat16 from layer to layer — forward and backward of every block and core run on them
 (gnx_block_backward_typed, gnx_core_backward_typed); weights, their gradients and the loss stay float32.
+--typed-dropout: every core's `typed_dropout` switch — a training call with --dropout > 0 goes through gnx_core_forward_train_typed /
+gnx_core_backward_train_typed (the mask inside one FeedForward kernel per entity at --width <= 16); it is what lets --bf16 and --dropout go
+together.
 """
 import argparse
 import os
@@ -59,9 +62,11 @@ def main():
                     help="the encoder / decoder blocks' pullback through gnx_block_backward_narrow: the fused edge level where the width set is eligible "
                          "(oe * (de + 2 dn + dg) < 64; e.g. the encoder at --width 16 without --vocab), its kernel specialised at run time on first use; "
                          "and the cores' pullback through gnx_core_backward_narrow: each FeedForward's pullback in one kernel at --width <= 16")
+    ap.add_argument("--typed-dropout", action="store_true",
+                    help="the cores' training calls (--dropout > 0) through gnx_core_forward_train_typed / gnx_core_backward_train_typed, on float32 or --bf16 features")
     args = ap.parse_args()
-    if args.bf16 and args.dropout > 0:
-        sys.exit("--bf16 with --dropout > 0: Dropout in training mode on bfloat16 features is not implemented (the training-mode core is fp32 only)")
+    if args.bf16 and args.dropout > 0 and not args.typed_dropout:
+        sys.exit("--bf16 with --dropout > 0 needs --typed-dropout: without the cores' typed_dropout switch the training-mode core takes float32 features only")
     if args.reference_config:
         args.vocab, args.n, args.width, args.graphs = 100, 10, 384, 4
     dev = torch.device("cuda", 0)
@@ -70,6 +75,8 @@ def main():
     b16 = bool(args.bf16)
     enc = gn.GNBlock((0, args.vocab or 1, 0), (w, w, w), device=dev, act=("relu", "relu", "relu"), bf16_backward=b16, narrow_backward=args.narrow_backward)
     cores = gn.GNCoreList([gn.GNCore((w, w, w), dropout=args.dropout, device=dev, bf16=b16, bf16_backward=b16, narrow_backward=args.narrow_backward) for _ in range(2)])
+    for core in cores.list:
+        core.typed_dropout = bool(args.typed_dropout)
     dec = gn.GNBlock((w, w, w), (2, 2, 0), device=dev, bf16_backward=b16, narrow_backward=args.narrow_backward)
     params = []
     for blk in (enc, dec):

@@ -186,6 +186,12 @@ SIGNATURES = {
     "gnx_core_forward_train": (C.c_int32, [C.c_void_p, C.POINTER(CoreParams), C.POINTER(Dropout)] + _FWD[2:]),
     "gnx_core_backward_train": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(Dropout)] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
                                 [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnx_core_train_fused_applies": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "gnx_core_train_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(CoreParams), C.c_int64, C.c_int32, C.c_uint32]),
+    "gnx_core_forward_train_typed": (C.c_int32, [C.c_void_p, C.POINTER(CoreParams), C.c_int32, C.POINTER(Dropout)] + _FWD[2:]),
+    "gnx_core_backward_train_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "gnx_core_backward_train_typed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Dropout), C.c_int32] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
+                                      [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_fn_input": (C.c_int32, [C.c_void_p, C.c_int32, _fp, C.c_int32, _fp, C.c_int32, _fp, C.c_int32, C.c_int64, _fp, C.c_void_p]),
     "gnx_collapse_offsets": (C.c_int32, [C.c_void_p, _i64p]),
     "gnx_collapse_edges": (C.c_int32, [C.c_void_p, _fp, C.c_int32, C.c_int64, _fp, C.c_void_p]),

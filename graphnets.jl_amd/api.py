@@ -1278,12 +1278,17 @@ class GNCore:
     `bf16_backward` (also a plain attribute, as GNBlock's): lets a differentiable call on bfloat16 features run — gnx_core_backward_typed is its
     pullback, the three saved inputs stay bf16, input gradients come back in bf16 and parameter gradients in fp32.  Off (the default) such a
     call raises NotImplementedError.  Dropout active on bfloat16 features (forced by `trainmode`, or p > 0 inside a gradient call) raises
-    NotImplementedError either way: the training-mode pair is fp32 only.
+    NotImplementedError either way unless `typed_dropout` is on.
+    `typed_dropout` (also a plain attribute; off by default): a call with an active Dropout goes through gnx_core_forward_train_typed — on float32
+    features, and on bfloat16 ones where `bf16` / `bf16_backward` allow them — and its autograd node calls gnx_core_backward_train_typed with
+    narrow = `narrow_backward`.  Where all three widths are at most 16 (hidden activations identity / relu) the forward applies the mask inside
+    one FeedForward kernel per entity: a dropped element is x + block exactly.  The seed rule (`last_dropout`, `testmode` / `trainmode`) is unchanged.
     `narrow_backward` (also a plain attribute, as GNBlock's): the pullback is gnx_core_backward_narrow, on float32 features (with the call's
     Dropout value when one is active) and — with `bf16_backward` — on bfloat16 ones: the pullback of each FeedForward in one kernel where all
     three widths are at most 16 and the hidden activations identity / relu, exactly the other pullbacks everywhere else.  Off by default."""
 
-    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False, bf16_backward=False, narrow_backward=False):
+    def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False, bf16_backward=False, narrow_backward=False,
+                 typed_dropout=False):
         dims = tuple(int(d) for d in dims)
         assert any(d > 0 for d in dims)  # gncore.jl:47
         self.dims = dims
@@ -1296,6 +1301,7 @@ class GNCore:
         self.bf16 = bool(bf16)
         self.bf16_backward = bool(bf16_backward)
         self.narrow_backward = bool(narrow_backward)
+        self.typed_dropout = bool(typed_dropout)
 
     def _c(self, keep):
         p = _lib.CoreParams()
@@ -1384,7 +1390,18 @@ class GNCore:
                                       "core.bf16_backward = True) to differentiate through gnx_core_backward_typed, call it under torch.no_grad() "
                                       "with parameters that need no gradient, or use float32 features")
         forced = getattr(self, "_dropout_mode", None)
-        if float(self.ffwd.dropout or 0) > 0 and (grad_call if forced is None else forced):
+        if getattr(self, "typed_dropout", False):
+            drop = self._dropout_now(grad_call)
+            if drop is not None:  # gnx_core_forward_train_typed / gnx_core_backward_train_typed on bf16 features
+                g, ef, nf, gf, R = _forward_common(x, self.dims, None)
+                flags = self.flags if flags is None else flags
+                if grad_call:
+                    eo, no, go = _CoreBf16TrainFn.apply(self, g, R, flags, drop, ef, nf, gf, *self._param_list())
+                else:
+                    ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+                    eo, no, go = _core_forward_train_typed(self, g, R, flags, drop, ef, nf, gf, _lib.ELEM_BF16)
+                return NT(g, _jl(eo), _jl(no), _jl(go))
+        elif float(self.ffwd.dropout or 0) > 0 and (grad_call if forced is None else forced):
             raise NotImplementedError("GNCore: Dropout in training mode on bfloat16 features (a typed gnx_core_forward_train / "
                                       "gnx_core_backward_train) is not implemented; use testmode(core), dropout=0 or float32 features")
         if grad_call:
@@ -1426,6 +1443,8 @@ def _core_forward(core, g, R, flags, drop, ef, nf, gf):
             ws = g.workspace(lib.gnx_core_workspace_bytes(g._h, C.byref(p), R), ("core", core.dims, R))
             check(lib.gnx_core_forward(g._h, C.byref(p), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(), no.data_ptr(),
                                        go.data_ptr(), ws.data_ptr(), ws.numel(), flags, stream))
+        elif getattr(core, "typed_dropout", False):
+            return _core_forward_train_typed(core, g, R, flags, drop, ef, nf, gf, _lib.ELEM_F32)
         else:
             nb = lib.gnx_core_train_workspace_bytes(g._h, C.byref(p), R)
             if nb == 0:
@@ -1433,6 +1452,21 @@ def _core_forward(core, g, R, flags, drop, ef, nf, gf):
             ws = g.workspace(nb, ("core_train", core.dims, R))
             check(lib.gnx_core_forward_train(g._h, C.byref(p), C.byref(drop), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(),
                                              no.data_ptr(), go.data_ptr(), ws.data_ptr(), ws.numel(), flags, stream))
+    return eo, no, go
+
+
+def _core_forward_train_typed(core, g, R, flags, drop, ef, nf, gf, elem):
+    """gnx_core_forward_train_typed (GNCore.typed_dropout, an active Dropout) on packed fp32 or 4-byte aligned bf16 tensors."""
+    lib = _lib.load()
+    keep = []
+    p = core._c(keep)
+    dev = g.device
+    eo, no, go = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
+    with torch.cuda.device(dev):
+        nb = lib.gnx_core_train_typed_workspace_bytes(g._h, C.byref(p), R, elem, flags)
+        ws = g.workspace(max(int(nb), 256), ("core_train_typed", core.dims, R, elem, flags))
+        check(lib.gnx_core_forward_train_typed(g._h, C.byref(p), elem, C.byref(drop), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(),
+                                               no.data_ptr(), go.data_ptr(), ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
     return eo, no, go
 
 
@@ -1516,9 +1550,27 @@ class _CoreBf16Fn(torch.autograd.Function):
         return (None,) * 4 + _core_pullback(ctx, (ge, gn_, gg), _lib.ELEM_BF16, None)
 
 
+class _CoreBf16TrainFn(torch.autograd.Function):
+    """_CoreBf16Fn with an active Dropout (GNCore.typed_dropout): forward = gnx_core_forward_train_typed, backward =
+    gnx_core_backward_train_typed under the same gnx_dropout value."""
+
+    @staticmethod
+    def forward(ctx, core, g, R, flags, drop, ef, nf, gf, *params):
+        ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+        eo, no, go = _core_forward_train_typed(core, g, R, flags, drop, ef, nf, gf, _lib.ELEM_BF16)
+        ctx.core, ctx.g, ctx.R, ctx.drop = core, g, R, drop
+        ctx.save_for_backward(ef, nf, gf)
+        return eo, no, go
+
+    @staticmethod
+    def backward(ctx, ge, gn_, gg):
+        return (None,) * 5 + _core_pullback(ctx, (ge, gn_, gg), _lib.ELEM_BF16, ctx.drop)
+
+
 def _core_pullback(ctx, cots, elem, drop):
-    """backward of _CoreFn (elem = ELEM_F32; drop: the forward's gnx_dropout or None) and _CoreBf16Fn (ELEM_BF16, no Dropout): (d_ef, d_nf, d_gf,
-    *parameter gradients).  The C entry: gnx_core_backward_narrow with GNCore.narrow_backward (the FeedForward pullbacks in one kernel each where
+    """backward of _CoreFn (elem = ELEM_F32; drop: the forward's gnx_dropout or None), _CoreBf16Fn (ELEM_BF16, no Dropout) and _CoreBf16TrainFn
+    (ELEM_BF16 with the forward's gnx_dropout): (d_ef, d_nf, d_gf, *parameter gradients).  The C entry: gnx_core_backward_train_typed for an active
+    Dropout with GNCore.typed_dropout (narrow = GNCore.narrow_backward); else gnx_core_backward_narrow with GNCore.narrow_backward (the FeedForward pullbacks in one kernel each where
     the core is narrow); otherwise gnx_core_backward_typed in bf16, gnx_core_backward in fp32 — gnx_core_backward_train with a Dropout (the
     forward's masks, regenerated from the call's seed)."""
     lib = _lib.load()
@@ -1533,7 +1585,11 @@ def _core_pullback(ctx, cots, elem, drop):
     d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
     dr = None if drop is None else C.byref(drop)
     with torch.cuda.device(dev):
-        if getattr(core, "narrow_backward", False):
+        if drop is not None and getattr(core, "typed_dropout", False):
+            narrow = 1 if getattr(core, "narrow_backward", False) else 0
+            nb = lib.gnx_core_backward_train_typed_workspace_bytes(g._h, C.byref(p), R, elem, narrow)
+            call, head = lib.gnx_core_backward_train_typed, (elem, dr, narrow)
+        elif getattr(core, "narrow_backward", False):
             nb, call, head = lib.gnx_core_backward_narrow_workspace_bytes(g._h, C.byref(p), R, elem), lib.gnx_core_backward_narrow, (elem, dr)
         elif elem == _lib.ELEM_BF16:
             nb, call, head = lib.gnx_core_backward_typed_workspace_bytes(g._h, C.byref(p), R, elem), lib.gnx_core_backward_typed, (elem,)

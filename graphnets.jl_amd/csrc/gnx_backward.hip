@@ -1316,6 +1316,22 @@ int32_t gnx_core_backward_narrow(const gnx_graphs* h, const gnx_core_params* p, 
     return fail(GNX_ERR_INVALID_ARG, "bf16 core backward with an active Dropout: no typed training-mode forward exists");
   return core_bw_run(CoreBwCall{h, p, elem, dropout, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, (hipStream_t)stream}, true);
 }
+
+// gnx_core_backward_train_typed: the pullback of gnx_core_forward_train_typed (either of its paths computes x + b + m .* f) — the same plan
+// and run as the entries above, with the forward's Dropout on either element type; narrow = 1 asks for k_core_bw_narrow as gnx_core_backward_narrow does
+size_t gnx_core_backward_train_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t R, int32_t elem, int32_t narrow) {
+  if (narrow != 0 && narrow != 1) return 0;
+  return core_bw_query(h, p, R, elem, narrow != 0);
+}
+int32_t gnx_core_backward_train_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const gnx_dropout* dropout, int32_t narrow, const void* ef,
+                                      const void* nf, const void* gf, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef,
+                                      void* d_nf, void* d_gf, const gnx_core_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
+  if (int32_t rc = check_dropout(dropout)) return rc;
+  if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, kNullCore);
+  return core_bw_run(CoreBwCall{h, p, elem, dropout, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, (hipStream_t)stream}, narrow != 0);
+}
 }  // extern "C"
 
 // ---- GNBlock with Chain update functions: backward ----

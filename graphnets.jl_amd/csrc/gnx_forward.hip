@@ -683,6 +683,19 @@ static int32_t check_core(const gnx_graphs* h, const gnx_core_params* p, const g
   return GNX_OK;
 }
 
+}  // extern "C"
+namespace gnx {
+// (gnx_launchers.h: what gnx_core_forward_train_typed checks before its own launches)
+int32_t core_forward_check_dims(const gnx_core_params* p) { return check_core_dims(p->block); }
+int32_t core_forward_check(const gnx_graphs* h, const gnx_core_params* p, int64_t R, const void* ef, const void* nf, const void* gf, const void* ef_out,
+                           const void* nf_out, const void* gf_out, uint32_t flags) {
+  gnx_block_params b = p->block;
+  b.prepared = p->prepared;
+  return check_core(h, p, b, R, ef, nf, gf, ef_out, nf_out, gf_out, flags);
+}
+}  // namespace gnx
+extern "C" {
+
 // ---- the GNCore forward: a validated call (CoreRun), what it does (CorePlan: decided before the first launch), the FeedForward step ----
 // The form of an entity's FeedForward + residual: out = block(gn1 x) + x + fc2(act1(fc1(gn2 x)))   (gncore.jl:56-68, gnfeedforward.jl:27-31)
 enum FfForm {

@@ -165,6 +165,19 @@ bool dropout_active(const gnx_dropout* d);
 int32_t check_dropout(const gnx_dropout* d);
 int32_t launch_dropout(const gnx_dropout& d, int entity, size_t n, const float* in, float* out, int mode, hipStream_t s);
 
+// ---- gnx_core_train_narrow.hip: the training-mode FeedForward + Dropout + residuals of a narrow core in one kernel (gnx_core_forward_train_typed) ----
+// launch_ln1_rows on bfloat16 rows (y fp32)
+int32_t launch_ln1_rows_bf16(const void* x, size_t rows, int d, const gnx_layernorm& l1, float eps, int eps_mode, float* y, hipStream_t s);
+// y = fmaf(m, ffwd(gn2(x)), x + block_out), m the mask of `dr` for `entity`; x and y hold bfloat16 elements with bf16, block_out is fp32.
+// d: a core_narrow_width; fc1 identity or relu, fc2 identity
+int32_t launch_core_post_train(const void* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode, const float* block_out,
+                               const gnx_dropout& dr, int entity, void* y, bool bf16, hipStream_t s);
+
+// ---- gnx_forward.hip: the validation of a core forward, for the training-mode entries of gnx_dropout.hip (a FormScope of the call's flags open) ----
+int32_t core_forward_check_dims(const gnx_core_params* p);  // (needs no handle)
+int32_t core_forward_check(const gnx_graphs* h, const gnx_core_params* p, int64_t R, const void* ef, const void* nf, const void* gf, const void* ef_out,
+                           const void* nf_out, const void* gf_out, uint32_t flags);
+
 // ---- gnx_build_device.hip: the CSC of a dense batch built on the device ----
 int32_t build_csc_on_device(const void* const* adj, const void* packed, int packed_on_device, const int64_t* n_nodes, int64_t G, int32_t elem_kind, int32_t row_major,
                             gnx::vec_i64& h_colptr, gnx::vec_i64& h_rowval, const std::vector<int64_t>& h_node_off, DenseCscOnDevice* keep);

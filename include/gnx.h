@@ -574,7 +574,7 @@ GNX_API int32_t gnx_core_backward(const gnx_graphs* h, const gnx_core_params* p,
  * is gnx_core_backward_workspace_bytes plus the three 256-B aligned fp32 copies; the query builds the CSR view and the wide tables, so call it
  * outside any capture.  bf16 buffers must be 4-byte aligned (rows of odd width are then 2-byte aligned: the kernels never assume more), else
  * GNX_ERR_INVALID_ARG; the workspace 16-byte aligned, else GNX_ERR_WORKSPACE; both before anything is written or launched.  No allocation, no
- * synchronisation.  Not typed (fp32 only): the training-mode pair gnx_core_forward_train / gnx_core_backward_train. */
+ * synchronisation.  With the forward's Dropout active: gnx_core_backward_train_typed. */
 GNX_API size_t gnx_core_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem);
 GNX_API int32_t gnx_core_backward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                         const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf,
@@ -634,8 +634,8 @@ GNX_API int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, 
  * tables, run-time specialisations), so call it outside any capture; it returns 0 for an unknown `elem` or GNX_FLAG_DEFER_GRAPH_UPDATE with
  * bf16, both of which gnx_core_forward_typed rejects (GNX_ERR_INVALID_ARG) before any GPU work — as it does a misaligned bf16 buffer and
  * (GNX_ERR_DIMS) dims that the block does not map to themselves, each of them even on a NULL handle.  Every other rule is gnx_core_forward's:
- * NULL rules, status codes, no allocation, no synchronisation, capture-safe.  The pullback is gnx_core_backward_typed.  Not typed (fp32 only):
- * gnx_core_forward_train / gnx_core_backward_train, gnx_model. */
+ * NULL rules, status codes, no allocation, no synchronisation, capture-safe.  The pullback is gnx_core_backward_typed.  In training mode (an active
+ * Dropout): gnx_core_forward_train_typed / gnx_core_backward_train_typed.  Not typed: gnx_model. */
 GNX_API size_t gnx_core_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem, uint32_t flags);
 GNX_API int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
                                        int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace, size_t workspace_bytes,
@@ -651,7 +651,8 @@ GNX_API int32_t gnx_core_forward_typed(const gnx_graphs* h, const gnx_core_param
  * scale apart — not x + block exactly as in Flux; the backward treats its FeedForward gradient as exactly zero.)
  * The host draws a fresh `seed` per forward call (one per core of a GNCoreList).  dropout = NULL or p = 0: exactly gnx_core_forward /
  * gnx_core_backward.  The forward is gnx_core_forward (any flags) followed by the correction y += (m - 1) .* f, f recomputed unfused in the
- * workspace (csrc/gnx_dropout.hip). */
+ * workspace (csrc/gnx_dropout.hip).  The FUSED form of gnx_core_forward_train_typed (below) applies the mask inside the FeedForward kernel and
+ * does not carry the (f_fused - f_unfused) residual: a dropped element there is x + block exactly. */
 typedef struct gnx_dropout {
   float p;          /* drop probability, 0 <= p <= 1 */
   uint32_t reserved;
@@ -683,7 +684,8 @@ GNX_API int32_t gnx_core_backward_train(const gnx_graphs* h, const gnx_core_para
  * wherever they run their generic kernels (the gradient w.r.t. gn2(x) is computed by the same operations in the same order); the twelve
  * FeedForward gradients are the same sums in another fixed order (a few fp32 roundings apart).
  * `dropout`: NULL or p = 0 — test mode; 0 < p <= 1 with GNX_ELEM_F32 — the pullback of gnx_core_forward_train under the same value; with
- * GNX_ELEM_BF16 an active dropout is GNX_ERR_INVALID_ARG before anything is written (no typed training-mode forward exists).
+ * GNX_ELEM_BF16 an active dropout is GNX_ERR_INVALID_ARG before anything is written (this entry keeps refusing it; the pullback of the typed
+ * training-mode forward is gnx_core_backward_train_typed).
  * Where it does not apply, the call IS gnx_core_backward_typed (no active dropout) or gnx_core_backward_train (fp32, active dropout), bit for
  * bit, and the workspace query returns theirs.  The query builds the CSR view and the wide tables: call it outside any capture.  The call
  * itself compiles nothing at run time (sixteen ahead-of-time instantiations cover every core), allocates nothing, does not synchronise and is
@@ -695,6 +697,46 @@ GNX_API int32_t gnx_core_backward_narrow(const gnx_graphs* h, const gnx_core_par
                                          const void* ef, const void* nf, const void* gf, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out,
                                          int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf, const gnx_core_grads* grads, void* workspace,
                                          size_t workspace_bytes, void* stream);
+
+/* ---- GNCore in TRAINING mode on either element type (src/gncore.jl:56-59, src/gnfeedforward.jl:27-31): y = x + block(gn1(x)) + m .* ffwd(gn2(x))
+ * with the masks of gnx_dropout above, on fp32 or bfloat16 feature tensors (`elem` applies to all six), and its pullback.
+ * FORWARD.  dropout NULL or p = 0: exactly gnx_core_forward_typed (same bits, same validation, that call's workspace:
+ * gnx_core_typed_workspace_bytes).  Active dropout, by path:
+ *   FUSED, where gnx_core_train_fused_applies = 1 — the rule of gnx_core_backward_narrow_applies to the letter (the two share one predicate): a
+ *   valid core whose three widths are within 1..16, fc1 identity / relu, fc2 identity, `elem` F32 or BF16, independent of the row counts.   No
+ *   width is cut from the rule: every measured width is faster than gnx_core_forward_train (profiles/core_train_narrow.json).  Per entity with rows: one gn1 launch (k_ln1_rows, or the same kernel reading
+ *   bf16 rows) into the workspace, gnx_block_forward on those rows into fp32 carves of the workspace (the call's `flags` go to the block), then
+ *   k_core_post_train (csrc/gnx_core_train_narrow.hip): y = fmaf(m, ffwd(gn2(x)), x + b) with gn2, the 4d hidden units and the mask in one
+ *   lane's registers.  No fp32 copy of a bf16 input or output, no hidden units and no f in memory; an entity without rows launches nothing
+ *   (ef / ef_out may be NULL when E == 0).  Where m == 0 the element is x + b exactly — the bits of the same call with p = 1.  With
+ *   GNX_ELEM_BF16 the outputs are bit for bit to_bf16 of the same entry called with GNX_ELEM_F32 on the exactly widened inputs.
+ *   Elsewhere, GNX_ELEM_F32: exactly gnx_core_forward_train (same bits, gnx_core_train_workspace_bytes).  GNX_ELEM_BF16: the three inputs are
+ *   widened behind that layout, gnx_core_forward runs in fp32 into fp32 carves, f is recomputed as gnx_core_forward_train does, and one pass
+ *   stores to_bf16(fmaf(m - 1, f, y32)) into the caller's buffers: bit for bit to_bf16(gnx_core_forward_train(widened inputs)) under the same
+ *   flags and dropout, no value rounded twice.
+ * Refused before anything is written or launched, in this order: an unknown `elem` (GNX_ERR_INVALID_ARG), p outside [0, 1]
+ * (GNX_ERR_INVALID_ARG), a bf16 buffer that is not 4-byte aligned (GNX_ERR_INVALID_ARG), GNX_FLAG_DEFER_GRAPH_UPDATE with an active dropout
+ * (GNX_ERR_INVALID_ARG), dims (GNX_ERR_DIMS), then gnx_core_forward's NULL and parameter rules, a workspace too small or not 16-byte aligned
+ * (GNX_ERR_WORKSPACE).  gnx_core_train_typed_workspace_bytes sizes the path an ACTIVE dropout takes; it returns 0 where the call would refuse
+ * elem, the handle or the params (and for GNX_FLAG_DEFER_GRAPH_UPDATE), and builds whatever tables that path needs: call it outside a capture.
+ * The call allocates nothing, does not synchronise and is capture-safe.  x and y must not overlap.
+ * BACKWARD: the pullback of both forward paths under the same gnx_dropout value.  `narrow`: 0 — the launches of gnx_core_backward_train; 1 — those
+ * of gnx_core_backward_narrow (k_core_bw_narrow where gnx_core_backward_narrow_applies); anything else is GNX_ERR_INVALID_ARG (the query: 0).
+ * With GNX_ELEM_F32 the call IS that entry.  With GNX_ELEM_BF16, ref being that entry on the exactly widened tensors under the same dropout:
+ * d_ef / d_nf / d_gf are bit for bit to_bf16(ref's), all parameter gradients bit for bit ref's — the mask is applied to the widened fp32 copy of
+ * the upstream gradient.  (gnx_core_backward_narrow itself keeps refusing bf16 with an active dropout.)  Everything else — NULL rules, optional
+ * outputs, alignment, status codes, capture — is gnx_core_backward_typed's; the workspace is the size its query returns. */
+GNX_API int32_t gnx_core_train_fused_applies(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_core_train_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem, uint32_t flags);
+GNX_API int32_t gnx_core_forward_train_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const gnx_dropout* dropout, const void* ef,
+                                             const void* nf, const void* gf, int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out,
+                                             void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
+GNX_API size_t gnx_core_backward_train_typed_workspace_bytes(const gnx_graphs* h, const gnx_core_params* p, int64_t n_replicas, int32_t elem,
+                                                             int32_t narrow);
+GNX_API int32_t gnx_core_backward_train_typed(const gnx_graphs* h, const gnx_core_params* p, int32_t elem, const gnx_dropout* dropout, int32_t narrow,
+                                              const void* ef, const void* nf, const void* gf, const void* g_ef_out, const void* g_nf_out,
+                                              const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
+                                              const gnx_core_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- row statistics of a packed [rows][d] tensor: stats[row] = (mean, 1 / (sigma + eps)) (eps_mode 0, Flux 0.14 `normalise`) or
  * (mean, 1 / sqrt(sigma^2 + eps)) (eps_mode 1), uncorrected sigma — the one pass over x from which the wide kernels apply GNGraphNorm's

@@ -623,12 +623,27 @@ core_c(m::GNCore) = GnxCoreParams(block_c(m.block), map(ln_c, m.gn1), map(ln_c, 
 
 # `drop` (a GnxDropout): the call is the forward of a gradient call — Flux applies the FeedForwards' Dropout(p) there and only there
 # (gnfeedforward.jl:27-31) — gnx_core_forward_train; the pullback regenerates the masks from the same value (core_pullback_device).
-function core_device(m::GNCore, x, drop=nothing)                       # ONE asynchronous gnx_core_forward; see block_device
+# `typed=true`: gnx_core_forward_train_typed (gncore.jl:56-59, gnfeedforward.jl:27-31) — where all three widths are at most 16 and the hidden
+# activations identity / relu, the mask is applied inside one FeedForward kernel per entity; everywhere else the very call below.
+function core_device(m::GNCore, x, drop=nothing; typed::Bool=false)    # ONE asynchronous gnx_core_forward; see block_device
     (; graphs, ef, nf, gf) = x
     @assert ef !== nothing && nf !== nothing && gf !== nothing         # graphnetadd needs all three (gncore.jl:61-68)
     g::GNGraphBatch = graphs
     R = size(ef, 3)
     p = Ref(core_c(m))
+    if drop !== nothing && typed
+        d = Ref(drop::GnxDropout)
+        ws = workspace!(g, (:core_train_typed, m.dims, R)) do
+            ccall((:gnx_core_train_typed_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64, Int32, UInt32), g.handle, p, R, GNX_ELEM_F32, UInt32(0))
+        end
+        o_ef, o_nf, o_gf = similar(ef), similar(nf), similar(gf)
+        GC.@preserve m ef nf gf o_ef o_nf o_gf ws check(ccall((:gnx_core_forward_train_typed, libgnx), Int32,
+            (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int32, Ptr{GnxDropout}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+             Ptr{Cvoid}, Csize_t, UInt32, Ptr{Cvoid}),
+            g.handle, p, GNX_ELEM_F32, d, devptr(ef), devptr(nf), devptr(gf), R, devptr(o_ef), devptr(o_nf), devptr(o_gf),
+            ws.ptr, ws.cap, UInt32(0), STREAM[]))
+        return (graphs=g, ef=o_ef, nf=o_nf, gf=o_gf)
+    end
     if drop !== nothing
         d = Ref(drop::GnxDropout)
         ws = workspace!(g, (:core_train, m.dims, R)) do
@@ -654,7 +669,7 @@ function core_device(m::GNCore, x, drop=nothing)                       # ONE asy
     (graphs=g, ef=o_ef, nf=o_nf, gf=o_gf)
 end
 (m::GNCore)(x) = back(core_device(gpu(m), gpu(x)), x)                  # src/gncore.jl:56-68 (test mode: Dropout is the identity)
-core_train(m::GNCore, x, drop) = back(core_device(gpu(m), gpu(x), drop), x)   # the forward of a gradient call (the rrule of julia/ext)
+core_train(m::GNCore, x, drop; typed::Bool=false) = back(core_device(gpu(m), gpu(x), drop; typed=typed), x)   # the forward of a gradient call (the rrule of julia/ext)
 newdropout(m::GNCore) = m.dropout > 0 ? GnxDropout(m.dropout, UInt32(0), rand(UInt64)) : nothing   # a fresh mask per call, as Flux draws one
 
 # pullback of (m::GNCore)(x) → gnx_core_backward: takes the forward's INPUT x and the cotangent ȳ of its output; every intermediate is
@@ -667,7 +682,8 @@ struct GnxCoreGrads
 end
 # `narrow=true`: gnx_core_backward_narrow — the pullback of each FeedForward in one kernel where all three widths are at most 16 and the hidden
 # activations identity / relu (gncore.jl:56-59, gnfeedforward.jl:27-31), `drop` passed on as its Dropout value; everywhere else the very calls below.
-function core_pullback_device(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false)
+# `typed=true` with a `drop`: gnx_core_backward_train_typed, the pullback of core_device(...; typed=true), `narrow` passed on as its flag.
+function core_pullback_device(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false, typed::Bool=false)
     g::GNGraphBatch = x.graphs
     R = size(x.ef, 3)
     p = Ref(core_c(m))
@@ -679,6 +695,19 @@ function core_pullback_device(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false
     grads = Ref(GnxCoreGrads(GnxBlockGrads(gd(b.edgefn), gd(b.nodefn), gd(b.graphfn)), map(gl, m.gn1), map(gl, m.gn2),
                              map(t -> GnxFfnGrad(gd(t[1]), gd(t[2])), m.ffwd)))
     dins = (similar(x.ef), similar(x.nf), similar(x.gf))
+    if typed && drop !== nothing
+        nrw = Int32(narrow ? 1 : 0)
+        ws = workspace!(g, (:core_backward_train_typed, m.dims, R, narrow)) do
+            ccall((:gnx_core_backward_train_typed_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64, Int32, Int32), g.handle, p, R, GNX_ELEM_F32, nrw)
+        end
+        d = Ref(drop::GnxDropout)
+        GC.@preserve m x ȳ gbuf dins ws d check(ccall((:gnx_core_backward_train_typed, libgnx), Int32,
+            (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int32, Ptr{GnxDropout}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+             Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{GnxCoreGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+            g.handle, p, GNX_ELEM_F32, d, nrw, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
+            devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]))
+        return (ef=dins[1], nf=dins[2], gf=dins[3], params=gbuf)
+    end
     if narrow
         ws = workspace!(g, (:core_backward_narrow, m.dims, R)) do
             ccall((:gnx_core_backward_narrow_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64, Int32), g.handle, p, R, GNX_ELEM_F32)
@@ -710,14 +739,20 @@ function core_pullback_device(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false
     end
     (ef=dins[1], nf=dins[2], gf=dins[3], params=gbuf)                  # block (W, b) x 3, gn1 (γ, β) x 3, gn2 (γ, β) x 3, ffwd (W1, b1, W2, b2) x 3
 end
-function core_pullback(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false)
-    r = core_pullback_device(gpu(m), gpu(x), gpu(ȳ), drop; narrow=narrow)
+function core_pullback(m::GNCore, x, ȳ, drop=nothing; narrow::Bool=false, typed::Bool=false)
+    r = core_pullback_device(gpu(m), gpu(x), gpu(ȳ), drop; narrow=narrow, typed=typed)
     ondevice(x) ? r : (ef=cpu(r.ef), nf=cpu(r.nf), gf=cpu(r.gf), params=map(cpu, r.params))
 end
 # does the fused FeedForward pullback run for this core (a rule of its widths and activations, not of the batch's row counts)?
 function narrow_backward_applies(m::GNCore, g::GNGraphBatch, R::Integer=1)
     p = Ref(core_c(gpu(m)))
     ccall((:gnx_core_backward_narrow_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64, Int32), g.handle, p, R, GNX_ELEM_F32) == 1
+end
+
+# does the training-mode forward apply the mask inside the FeedForward kernel for this core (the same rule as narrow_backward_applies)?
+function train_fused_applies(m::GNCore, g::GNGraphBatch, R::Integer=1)
+    p = Ref(core_c(gpu(m)))
+    ccall((:gnx_core_train_fused_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxCoreParams}, Int64, Int32), g.handle, p, R, GNX_ELEM_F32) == 1
 end
 
 # GNCoreList is `foldl((x, f) -> f(x), list; init=x)` exactly as src/gncorelist.jl:43-45.
