@@ -141,6 +141,9 @@ SIGNATURES = {
     "gnx_block_forward_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32] + _FWD[2:]),
     "gnx_chain_block_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
     "gnx_chain_block_forward": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams)] + _FWD[2:]),
+    "gnx_chain_block_forward_narrow_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
+    "gnx_chain_block_forward_narrow_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
+    "gnx_chain_block_forward_narrow": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams)] + _FWD[2:]),
     "gnx_chain_block_backward_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
     "gnx_chain_block_backward": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams)] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
                                  [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -894,10 +894,14 @@ class GNBlock:
     `narrow_backward` (also a plain attribute; wins over `fused_backward`): the pullback is gnx_block_backward_narrow, on float32 features and —
     with `bf16_backward` — on bfloat16 ones: the fused edge level at ANY eligible narrow width set (oe * (de + 2 dn + dg) < 64), the kernel of a
     set outside the five ahead-of-time ones specialised at run time on first use (GNX_JIT_CACHE=<dir> keeps it on disk).  On the five sets the
-    bits are `fused_backward`'s; where the set is not eligible nothing changes."""
+    bits are `fused_backward`'s; where the set is not eligible nothing changes.
+
+    `narrow_chain` (also a plain attribute): a block whose update functions are Chains runs its forward through gnx_chain_block_forward_narrow —
+    each update function whose input and layer widths are at most 32 in one kernel (a row per lane through all layers), the others as before.
+    Off (the default): gnx_chain_block_forward.  The pullback (gnx_chain_block_backward) recomputes its activations and does not change."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
-                 narrow_backward=False):
+                 narrow_backward=False, narrow_chain=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -912,6 +916,7 @@ class GNBlock:
         self.bf16_backward = bool(bf16_backward)
         self.fused_backward = bool(fused_backward)
         self.narrow_backward = bool(narrow_backward)
+        self.narrow_chain = bool(narrow_chain)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -981,11 +986,15 @@ class GNBlock:
         mk = lambda T, d: torch.empty((R, T, d), dtype=torch.float32, device=dev) if d > 0 else None
         eo, no, go = mk(g.n_edges, outw[0]), mk(g.n_nodes, outw[1]), mk(g.n_graphs, outw[2])
         with torch.cuda.device(dev):
-            nbytes = lib.gnx_chain_block_workspace_bytes(g._h, C.byref(p), R)
+            narrow = bool(getattr(self, "narrow_chain", False))
+            query, entry = ((lib.gnx_chain_block_forward_narrow_workspace_bytes, lib.gnx_chain_block_forward_narrow) if narrow else
+                            (lib.gnx_chain_block_workspace_bytes, lib.gnx_chain_block_forward))
+            nbytes = query(g._h, C.byref(p), R)
             if nbytes == 0:
                 raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-            ws = g.workspace(nbytes, ("chain", self.in_dims, tuple(tuple(int(l.weight.shape[0]) for l in ch.layers) for ch in chains), R))
-            check(lib.gnx_chain_block_forward(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
+            ws = g.workspace(nbytes, ("chain_narrow" if narrow else "chain", self.in_dims,
+                                      tuple(tuple(int(l.weight.shape[0]) for l in ch.layers) for ch in chains), R))
+            check(entry(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
                                               ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
         return eo, no, go
 

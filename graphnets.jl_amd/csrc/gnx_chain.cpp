@@ -11,6 +11,8 @@
 //   node function : getnodefninput (gnx_fn_input kind 1: [sum_{e->n} ef' ; nf ; gf_g], N rows) then row-wise Dense layers;
 //   graph function: getgraphfninput (kind 2, G rows) then row-wise Dense layers.
 // Semantics are exactly (m::GNBlock)(x) of src/gnblock.jl:63-69 with Chain update functions; zero-width outputs -> `nothing`.
+// gnx_chain_block_forward_narrow: the same block with every update function whose input and layer widths are at most 32 in ONE kernel
+// (gnx_chain_narrow.hip: k_chain_mlp, a row per lane through all layers); a function outside that rule runs the launches above.
 #include <algorithm>
 
 #include "gnx_launchers.h"
@@ -121,23 +123,25 @@ int32_t check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64
   return GNX_OK;
 }
 
-ChainWs layout(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, size_t ident_floats) {
+// fused: the functions gnx_chain_block_forward_narrow runs in one kernel each (bit 0 edge, 1 node, 2 graph) — they need none of the block
+// workspace / e_buf, n_in / n_buf, g_buf; 0: the layout of gnx_chain_block_forward
+ChainWs layout(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, size_t ident_floats, unsigned fused = 0) {
   ChainWs w{};
   size_t o = 0;
   auto take = [&](size_t floats) { const size_t at = o; o += align_up(sizeof(float) * floats, 256); return at; };
   const int oe = out_width(p->edgefn), on = out_width(p->nodefn), og = out_width(p->graphfn);
   w.block_off = 0; w.block_bytes = 0;
-  if (oe > 0) {
+  if (oe > 0 && !(fused & 1)) {
     const gnx_block_params b = edge_block(p);
     w.block_bytes = gnx_block_workspace_bytes(h, &b, R);
     o = align_up(w.block_bytes, 256);
   }
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
-  for (int i = 0; i < 2; ++i) w.e_buf[i] = take(p->edgefn.n_layers > 1 ? rows[0] * max_width(p->edgefn) : 0);
-  w.n_in = take(on > 0 ? rows[1] * (size_t)(oe + p->dn + p->dg) : 0);
-  for (int i = 0; i < 2; ++i) w.n_buf[i] = take(p->nodefn.n_layers > 1 ? rows[1] * max_width(p->nodefn) : 0);
+  for (int i = 0; i < 2; ++i) w.e_buf[i] = take(p->edgefn.n_layers > 1 && !(fused & 1) ? rows[0] * max_width(p->edgefn) : 0);
+  w.n_in = take(on > 0 && !(fused & 2) ? rows[1] * (size_t)(oe + p->dn + p->dg) : 0);
+  for (int i = 0; i < 2; ++i) w.n_buf[i] = take(p->nodefn.n_layers > 1 && !(fused & 2) ? rows[1] * max_width(p->nodefn) : 0);
   w.g_in = take(og > 0 ? rows[2] * (size_t)(oe + on + p->dg) : 0);
-  for (int i = 0; i < 2; ++i) w.g_buf[i] = take(p->graphfn.n_layers > 1 ? rows[2] * max_width(p->graphfn) : 0);
+  for (int i = 0; i < 2; ++i) w.g_buf[i] = take(p->graphfn.n_layers > 1 && !(fused & 4) ? rows[2] * max_width(p->graphfn) : 0);
   w.ident = take(ident_floats);
   w.total = o + 256;
   return w;
@@ -159,29 +163,41 @@ int32_t run_layers(const gnx_graphs* h, int entity, const gnx_chain& c, int firs
   return GNX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t gnx_chain_block_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R) {
-  if (check_params(h, p0, R) != GNX_OK) return 0;
-  ChainLnFirst lnf;
-  const gnx_chain_block_params* p = lnf.init(p0, nullptr);
-  // further layers of a chain are row-wise Dense launches on the matrix-core kernel: its tables are built here, outside any capture
-  if (p->edgefn.n_layers > 1 || p->nodefn.n_layers > 1 || p->graphfn.n_layers > 1 || out_width(p->edgefn) == 0) (void)gnx_ensure_wide_tables(h);
-  return layout(h, p, R, lnf.ident_floats()).total;
+// the functions of a (checked) block that the fused rule takes: bit 0 edge, 1 node, 2 graph (gnx_launchers.h: chain_narrow_takes)
+unsigned narrow_mask(const gnx_graphs* h, const gnx_chain_block_params* p) {
+  const int oe = out_width(p->edgefn), on = out_width(p->nodefn);
+  unsigned m = 0;
+  if (chain_narrow_takes(p->edgefn, p->de + 2 * p->dn + p->dg, (size_t)h->E)) m |= 1;
+  if (chain_narrow_takes(p->nodefn, oe + p->dn + p->dg, (size_t)h->N)) m |= 2;
+  if (chain_narrow_takes(p->graphfn, oe + on + p->dg, (size_t)h->G)) m |= 4;
+  return m;
 }
 
-int32_t gnx_chain_block_forward(const gnx_graphs* h, const gnx_chain_block_params* p0, const float* ef, const float* nf, const float* gf, int64_t R,
-                                float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+// narrow: gnx_chain_block_forward_narrow (the fused functions of narrow_mask in one kernel each); else gnx_chain_block_forward
+size_t chain_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, bool narrow) {
+  if (check_params(h, p0, R) != GNX_OK) return 0;
+  const unsigned fused = narrow ? narrow_mask(h, p0) : 0;
+  ChainLnFirst lnf;
+  const gnx_chain_block_params* p = (fused & 1) ? p0 : lnf.init(p0, nullptr);  // (a fused edge function has its input row in registers: no identity layer)
+  // further layers of a chain are row-wise Dense launches on the matrix-core kernel: its tables are built here, outside any capture
+  // (the fused edge function reads the destination of every edge from them)
+  const bool rows_e = !(fused & 1) && (p->edgefn.n_layers > 1 || out_width(p->edgefn) == 0);
+  const bool rows_n = !(fused & 2) && p->nodefn.n_layers > 1, rows_g = !(fused & 4) && p->graphfn.n_layers > 1;
+  if (rows_e || rows_n || rows_g || (fused & 1)) (void)gnx_ensure_wide_tables(h);
+  return layout(h, p, R, lnf.ident_floats(), fused).total;
+}
+
+int32_t chain_forward(const gnx_graphs* h, const gnx_chain_block_params* p0, const float* ef, const float* nf, const float* gf, int64_t R, float* ef_out,
+                      float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream, bool narrow) {
   hipStream_t s = (hipStream_t)stream;
   gnx::FormScope forms(flags);  // the forms this call selected (gnx.h: GNX_FLAG_EDGE_FP32 ...)
   int32_t rc = check_params(h, p0, R);
   if (rc) return rc;
+  const unsigned fused = narrow ? narrow_mask(h, p0) : 0;
   ChainLnFirst lnf;
-  {  // (the identity layer's weights sit at a fixed place of the workspace: the layout does not depend on the pointer)
+  if (!(fused & 1)) {  // (the identity layer's weights sit at a fixed place of the workspace: the layout does not depend on the pointer)
     const gnx_chain_block_params* q = lnf.init(p0, nullptr);
-    if (lnf.on && ws) lnf.layers[0].weight = reinterpret_cast<const float*>(static_cast<char*>(ws) + layout(h, q, R, lnf.ident_floats()).ident);
+    if (lnf.on && ws) lnf.layers[0].weight = reinterpret_cast<const float*>(static_cast<char*>(ws) + layout(h, q, R, lnf.ident_floats(), fused).ident);
   }
   const gnx_chain_block_params* p = lnf.on ? &lnf.p : p0;
   const int de = p->de, dn = p->dn, dg = p->dg;
@@ -192,14 +208,18 @@ int32_t gnx_chain_block_forward(const gnx_graphs* h, const gnx_chain_block_param
   gnx::DeviceTurn turn(s, chain_wide);
   if ((de > 0 && !ef && h->E > 0) || (dn > 0 && !nf) || (dg > 0 && !gf)) return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL (width 0 <=> nothing)");
   if ((oe > 0 && !ef_out && h->E > 0) || (on > 0 && !nf_out) || (og > 0 && !gf_out)) return fail(GNX_ERR_INVALID_ARG, "an output with non-zero width is NULL");
-  const ChainWs w = layout(h, p, R, lnf.ident_floats());
-  if (!ws || ws_bytes < w.total) return fail(GNX_ERR_WORKSPACE, "workspace missing or smaller than gnx_chain_block_workspace_bytes()");
+  const ChainWs w = layout(h, p, R, lnf.ident_floats(), fused);
+  if (!ws || ws_bytes < w.total)
+    return fail(GNX_ERR_WORKSPACE, narrow ? "workspace missing or smaller than gnx_chain_block_forward_narrow_workspace_bytes()"
+                                          : "workspace missing or smaller than gnx_chain_block_workspace_bytes()");
   if (((uintptr_t)ws & 15) != 0) return fail(GNX_ERR_WORKSPACE, "workspace must be 16-byte aligned");
   char* base = static_cast<char*>(ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   if ((rc = lnf.fill(F(w.ident), s))) return rc;
   // ---- edge function (gnblock.jl:65): first Dense fused with getedgefninput, the rest row-wise ----
-  if (oe > 0 && h->E > 0) {
+  if (fused & 1) {
+    if ((rc = launch_chain_narrow(h, 0, p->edgefn, ef, de, nf, dn, gf, dg, ef_out, R, s, "k_rows_gemm_chain_e"))) return rc;
+  } else if (oe > 0 && h->E > 0) {
     const gnx_block_params b = edge_block(p);
     float* first_out = p->edgefn.n_layers == 1 ? ef_out : F(w.e_buf[0]);
     if ((rc = gnx_block_forward(h, &b, ef, nf, gf, R, first_out, nullptr, nullptr, base + w.block_off, w.block_bytes, flags, stream))) return rc;
@@ -209,7 +229,9 @@ int32_t gnx_chain_block_forward(const gnx_graphs* h, const gnx_chain_block_param
     }
   }
   // ---- node function (gnblock.jl:66): sees the NEW ef', the OLD nf and gf ----
-  if (on > 0) {
+  if (fused & 2) {
+    if ((rc = launch_chain_narrow(h, 1, p->nodefn, ef_out, oe, nf, dn, gf, dg, nf_out, R, s, "k_rows_gemm_chain_n"))) return rc;
+  } else if (on > 0) {
     if ((rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, F(w.n_in), s))) return rc;
     float* const bufs[2] = {F(w.n_buf[0]), F(w.n_buf[1])};
     if ((rc = run_layers(h, 1, p->nodefn, 0, F(w.n_in), oe + dn + dg, bufs, nf_out, R, s, "k_rows_gemm_chain_n"))) return rc;
@@ -217,10 +239,36 @@ int32_t gnx_chain_block_forward(const gnx_graphs* h, const gnx_chain_block_param
   // ---- graph function (gnblock.jl:67): NEW ef', NEW nf', OLD gf ----
   if (og > 0) {
     if ((rc = launch_fn_input(h, 2, ef_out, oe, nf_out, on, gf, dg, R, F(w.g_in), s))) return rc;
-    float* const bufs[2] = {F(w.g_buf[0]), F(w.g_buf[1])};
-    if ((rc = run_layers(h, 2, p->graphfn, 0, F(w.g_in), oe + on + dg, bufs, gf_out, R, s, "k_rows_gemm_chain_g"))) return rc;
+    if (fused & 4) {
+      if ((rc = launch_chain_narrow(h, 2, p->graphfn, F(w.g_in), oe + on + dg, nullptr, 0, nullptr, 0, gf_out, R, s, "k_rows_gemm_chain_g"))) return rc;
+    } else {
+      float* const bufs[2] = {F(w.g_buf[0]), F(w.g_buf[1])};
+      if ((rc = run_layers(h, 2, p->graphfn, 0, F(w.g_in), oe + on + dg, bufs, gf_out, R, s, "k_rows_gemm_chain_g"))) return rc;
+    }
   }
   return GNX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gnx_chain_block_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_workspace_bytes(h, p, R, false); }
+
+int32_t gnx_chain_block_forward(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
+                                float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  return chain_forward(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream, false);
+}
+
+int32_t gnx_chain_block_forward_narrow_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return check_params(h, p, R) == GNX_OK ? (int32_t)narrow_mask(h, p) : 0;
+}
+
+size_t gnx_chain_block_forward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_workspace_bytes(h, p, R, true); }
+
+int32_t gnx_chain_block_forward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
+                                       float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  return chain_forward(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream, true);
 }
 
 }  // extern "C"

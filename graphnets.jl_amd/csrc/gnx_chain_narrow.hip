@@ -1,0 +1,241 @@
+// GNBlock with Chain update functions at narrow widths: one update function = one kernel (gnx_chain_block_forward_narrow, gnx_chain.cpp).
+//
+//   k_chain_mlp<WMAX, SRC> : one lane = one row of the entity; the lane builds the function's input row in registers (SRC), runs it through
+//                            ALL layers of the function — Dense with any activation, LayerNorm layer values — and stores the last layer's row.
+//
+// SRC_EDGE  [ef[e] ; nf[rowval[e]] ; nf[edge_dst[e]] ; gf[graph(e)]]                 (getedgefninput, gnblock.jl:65; k_fn_input_edge)
+// SRC_NODE  [sum_{e in colptr[n] .. colptr[n+1]} ef'[e] ; nf[n] ; gf[graph(n)]]     (getnodefninput; sequential fp32 adds in CSC order: the bits
+//                                                                                      of k_fn_input_node)
+// SRC_ROWS  a materialised [rows][K] buffer                                          (the graph function behind launch_fn_input(kind 2))
+//
+// The current and the next activations are float[WMAX] arrays indexed by unrolled constants only (registers, no scratch:
+// profiles/chain_narrow_resources.json); WMAX in {8, 16, 32} is the smallest that covers the input width and every layer width.  Entries at or
+// beyond a layer's width are kept at exactly 0.f.  The function's parameters are staged in LDS once per workgroup, zero-padded to groups of
+// four — a Dense as [ceil4(k_in)][ceil4(width)] weights (element (j, k) at k * ceil4(width) + j) + ceil4(width) biases, a LayerNorm as gamma and
+// beta — and read with uniform addresses (a ds_read_b128 of one address is a broadcast, as in core_post_lds_body: gnx_core_post_kernel.h).
+// A layer's products run as groups of 4 outputs x 4 inputs behind wave-uniform tests of the group against the layer's widths: a 16 -> 3 layer
+// pays 4 x 1 groups, not the 32-wide tile of the matrix-core GEMM.  Every group is a basic block of its own, so the scheduler cannot hoist the
+// weight reads of a whole layer into registers (the hazard the sched_barriers of core_post_lds_body fence).
+// Feature and output pointers may be 4-byte aligned only: every global access is one dword.  Offsets are size_t.
+#include "gnx_launchers.h"
+#include "gnx_wave_kernel.h"  // act_row
+
+namespace gnx {
+
+enum : int { SRC_EDGE = 0, SRC_NODE = 1, SRC_ROWS = 2 };
+
+struct ChainMlpLayer {
+  const float* w;  // Dense: weight (out x in, column-major) / LayerNorm: gamma
+  const float* b;  // Dense: bias or nullptr / LayerNorm: beta
+  int width;       // output width
+  int op;          // 0..4: Dense with activation GNX_ACT_*; 5 / 6: LayerNorm with 1 / (sigma + eps) / 1 / sqrt(sigma^2 + eps)
+};
+
+struct ChainMlpArgs {
+  ChainMlpLayer layer[kChainMaxLayers];
+  int n_layers, K;       // K: width of the function's input row
+  const float *a0, *a1, *a2;  // EDGE: ef, nf, gf / NODE: ef', nf, gf / ROWS: the input rows, -, -
+  int d0, d1, d2;        // their widths (EDGE: de, dn, dg; NODE: oe, dn, dg)
+  int N, E, G;
+  const int *colptr, *rowval, *edge_dst, *seg_off;  // seg_off: edge_off (EDGE) / node_off (NODE), [G + 1]
+  float* out; int ow;    // [R][rows][ow]
+  size_t rows;           // rows of the entity per replica
+};
+
+__host__ __device__ constexpr int ceil4(int x) { return (x + 3) & ~3; }
+
+// cur[at .. at + w) = p[0 .. w): one dword load per element behind a uniform test
+template <int WMAX>
+__device__ __forceinline__ void chain_load_seg(const float* __restrict__ p, int at, int w, float (&cur)[WMAX]) {
+#pragma unroll
+  for (int k = 0; k < WMAX; ++k)
+    if (k >= at && k < at + w) cur[k] = p[k - at];
+}
+
+template <int WMAX, int SRC>
+__global__ __launch_bounds__(256) void k_chain_mlp(ChainMlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float s_par[];
+  {  // stage the parameters, zero-padded
+    int off = 0, kin = a.K;
+    for (int l = 0; l < a.n_layers; ++l) {
+      const ChainMlpLayer L = a.layer[l];
+      const int OP = ceil4(L.width);
+      if (L.op < 5) {
+        const int n = ceil4(kin) * OP;
+        for (int i = threadIdx.x; i < n; i += 256) {
+          const int k = i / OP, j = i - k * OP;
+          s_par[off + i] = (k < kin && j < L.width) ? L.w[(size_t)k * L.width + j] : 0.f;
+        }
+        for (int j = threadIdx.x; j < OP; j += 256) s_par[off + n + j] = (j < L.width && L.b) ? L.b[j] : 0.f;
+        off += n + OP;
+      } else {
+        for (int j = threadIdx.x; j < OP; j += 256) {
+          s_par[off + j] = j < L.width ? L.w[j] : 0.f;
+          s_par[off + OP + j] = j < L.width ? L.b[j] : 0.f;
+        }
+        off += 2 * OP;
+      }
+      kin = L.width;
+    }
+  }
+  __syncthreads();
+  const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= a.rows) return;
+  const size_t r = blockIdx.y;
+
+  float cur[WMAX];
+#pragma unroll
+  for (int k = 0; k < WMAX; ++k) cur[k] = 0.f;
+  if constexpr (SRC == SRC_EDGE) {
+    const int e = (int)row;
+    if (a.d0 > 0) chain_load_seg<WMAX>(a.a0 + (r * (size_t)a.E + e) * a.d0, 0, a.d0, cur);
+    if (a.d1 > 0) {
+      chain_load_seg<WMAX>(a.a1 + (r * (size_t)a.N + a.rowval[e]) * a.d1, a.d0, a.d1, cur);
+      chain_load_seg<WMAX>(a.a1 + (r * (size_t)a.N + a.edge_dst[e]) * a.d1, a.d0 + a.d1, a.d1, cur);
+    }
+    if (a.d2 > 0) chain_load_seg<WMAX>(a.a2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, e)) * a.d2, a.d0 + 2 * a.d1, a.d2, cur);
+  } else if constexpr (SRC == SRC_NODE) {
+    const int n = (int)row;
+    if (a.d0 > 0) {
+      const int e1 = a.colptr[n + 1];
+      for (int e = a.colptr[n]; e < e1; ++e) {
+        const float* __restrict__ p = a.a0 + (r * (size_t)a.E + e) * a.d0;
+#pragma unroll
+        for (int k = 0; k < WMAX; ++k)
+          if (k < a.d0) cur[k] += p[k];
+      }
+    }
+    if (a.d1 > 0) chain_load_seg<WMAX>(a.a1 + (r * (size_t)a.N + n) * a.d1, a.d0, a.d1, cur);
+    if (a.d2 > 0) chain_load_seg<WMAX>(a.a2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, n)) * a.d2, a.d0 + a.d1, a.d2, cur);
+  } else {
+    chain_load_seg<WMAX>(a.a0 + (r * a.rows + row) * (size_t)a.K, 0, a.K, cur);
+  }
+
+  int off = 0, kin = a.K;
+#pragma unroll 1
+  for (int l = 0; l < a.n_layers; ++l) {
+    const int width = a.layer[l].width, op = a.layer[l].op;
+    const int OP = ceil4(width);
+    if (op < 5) {
+      float nxt[WMAX];
+      const float* __restrict__ sw = s_par + off;
+      const float* __restrict__ sb = sw + ceil4(kin) * OP;
+#pragma unroll
+      for (int j0 = 0; j0 < WMAX; j0 += 4) {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        if (j0 < width) {
+          const float4 bb = *reinterpret_cast<const float4*>(sb + j0);
+          acc[0] = bb.x; acc[1] = bb.y; acc[2] = bb.z; acc[3] = bb.w;
+#pragma unroll
+          for (int k0 = 0; k0 < WMAX; k0 += 4) {
+            if (k0 < kin) {
+#pragma unroll
+              for (int kk = 0; kk < 4; ++kk) {
+                const float4 w = *reinterpret_cast<const float4*>(sw + (k0 + kk) * OP + j0);
+                acc[0] = fmaf(w.x, cur[k0 + kk], acc[0]); acc[1] = fmaf(w.y, cur[k0 + kk], acc[1]);
+                acc[2] = fmaf(w.z, cur[k0 + kk], acc[2]); acc[3] = fmaf(w.w, cur[k0 + kk], acc[3]);
+              }
+            }
+          }
+          act_row<4>(acc, op);
+        }
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) nxt[j0 + jj] = j0 + jj < width ? acc[jj] : 0.f;  // (sigmoid(0) != 0: the padding stays exactly 0)
+      }
+#pragma unroll
+      for (int k = 0; k < WMAX; ++k) cur[k] = nxt[k];
+      off += ceil4(kin) * OP + OP;
+    } else {
+      // k_chain_layernorm's formula (gnx_chain.cpp), the sums taken by the lane in element order
+      const float* __restrict__ sg = s_par + off;
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < WMAX; ++k) s += cur[k];  // (the padding is 0)
+      const float mu = s / (float)width;
+      float v = 0.f;
+#pragma unroll
+      for (int k = 0; k < WMAX; ++k)
+        if (k < width) { const float c = cur[k] - mu; v = fmaf(c, c, v); }
+      v /= (float)width;
+      const float inv = op == 5 ? 1.f / (sqrtf(v) + kChainLnEps) : 1.f / sqrtf(v + kChainLnEps);
+#pragma unroll
+      for (int k0 = 0; k0 < WMAX; k0 += 4) {
+        if (k0 < width) {
+          const float4 g = *reinterpret_cast<const float4*>(sg + k0);
+          const float4 b = *reinterpret_cast<const float4*>(sg + OP + k0);
+          const float gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) cur[k0 + kk] = k0 + kk < width ? fmaf(gg[kk], (cur[k0 + kk] - mu) * inv, bb[kk]) : 0.f;
+        }
+      }
+      off += 2 * OP;
+    }
+    kin = width;
+  }
+
+  float* __restrict__ o = a.out + (r * a.rows + row) * (size_t)a.ow;
+#pragma unroll
+  for (int k = 0; k < WMAX; ++k)
+    if (k < a.ow) o[k] = cur[k];
+}
+
+// floats of LDS the parameters of `c` take in the kernel's layout (input width k_in)
+size_t chain_narrow_lds_floats(const gnx_chain& c, int k_in) {
+  size_t n = 0;
+  int kin = k_in;
+  for (int i = 0; i < c.n_layers; ++i) {
+    const int OP = ceil4(c.widths[i]);
+    n += chain_layer_is_ln(c.layers[i]) ? 2 * (size_t)OP : (size_t)ceil4(kin) * OP + OP;
+    kin = c.widths[i];
+  }
+  return n;
+}
+
+bool chain_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows) {
+  if (c.n_layers < 1 || c.n_layers > kChainMaxLayers || !c.layers || !c.widths || entity_rows == 0) return false;
+  if (c.widths[c.n_layers - 1] <= 0 || k_in > kChainNarrowMaxWidth) return false;
+  for (int i = 0; i < c.n_layers; ++i)
+    if (c.widths[i] > kChainNarrowMaxWidth) return false;
+  return chain_narrow_lds_floats(c, k_in) <= kChainNarrowLdsFloats;
+}
+
+template <int SRC>
+static void chain_mlp_launch(int wmax, dim3 grid, size_t lds, hipStream_t s, const ChainMlpArgs& a) {
+  if (wmax <= 8) GNX_LAUNCH((k_chain_mlp<8, SRC>), grid, dim3(256), lds, s, a);
+  else if (wmax <= 16) GNX_LAUNCH((k_chain_mlp<16, SRC>), grid, dim3(256), lds, s, a);
+  else GNX_LAUNCH((k_chain_mlp<32, SRC>), grid, dim3(256), lds, s, a);
+}
+
+// One update function of a Chain block in one launch.  entity 0: in0 / in1 / in2 = ef, nf, gf of widths d0, d1, d2 (SRC_EDGE); 1: ef', nf, gf
+// (SRC_NODE); 2: in0 = the materialised [R G][d0] input rows (SRC_ROWS; d1 = d2 = 0).  The caller asked chain_narrow_takes.
+int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
+                            float* out, int64_t R, hipStream_t s, const char* name) {
+  ChainMlpArgs a{};
+  const int K = entity == 0 ? d0 + 2 * d1 + d2 : d0 + d1 + d2;
+  const size_t rows = entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G);
+  if (!chain_narrow_takes(c, K, rows)) return fail(GNX_ERR_INVALID_ARG, "launch_chain_narrow: the function is outside the fused rule");
+  if (entity == 0) { if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw; }  // (the destination of every edge)
+  int wmax = K, kin = K;
+  for (int i = 0; i < c.n_layers; ++i) {
+    const gnx_dense& l = c.layers[i];
+    if (!chain_layer_is_ln(l) && c.widths[i] > 0 && kin > 0 && !l.weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
+    a.layer[i] = ChainMlpLayer{l.weight, l.bias, c.widths[i], chain_layer_is_ln(l) ? 5 + chain_layer_ln_mode(l) : l.act};
+    wmax = wmax > c.widths[i] ? wmax : c.widths[i];
+    kin = c.widths[i];
+  }
+  a.n_layers = c.n_layers; a.K = K;
+  a.a0 = in0; a.a1 = in1; a.a2 = in2; a.d0 = d0; a.d1 = d1; a.d2 = d2;
+  a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G;
+  a.colptr = h->d_colptr; a.rowval = h->d_rowval; a.edge_dst = h->d_edge_dst; a.seg_off = entity == 0 ? h->d_edge_off : h->d_node_off;
+  a.out = out; a.ow = c.widths[c.n_layers - 1]; a.rows = rows;
+  const dim3 grid((unsigned)((rows + 255) / 256), (unsigned)R);
+  const size_t lds = sizeof(float) * chain_narrow_lds_floats(c, K);
+  ProfScope ps(name, s);
+  if (entity == 0) chain_mlp_launch<SRC_EDGE>(wmax, grid, lds, s, a);
+  else if (entity == 1) chain_mlp_launch<SRC_NODE>(wmax, grid, lds, s, a);
+  else chain_mlp_launch<SRC_ROWS>(wmax, grid, lds, s, a);
+  GNX_HIP(hipGetLastError());
+  return GNX_OK;
+}
+
+}  // namespace gnx

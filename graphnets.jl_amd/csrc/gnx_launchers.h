@@ -173,6 +173,16 @@ int32_t launch_ln1_rows_bf16(const void* x, size_t rows, int d, const gnx_layern
 int32_t launch_core_post_train(const void* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode, const float* block_out,
                                const gnx_dropout& dr, int entity, void* y, bool bf16, hipStream_t s);
 
+// ---- gnx_chain_narrow.hip: one update function of a Chain block in one kernel (gnx_chain_block_forward_narrow) ----
+constexpr int kChainNarrowMaxWidth = 32;         // input width and every layer width of a fused function
+constexpr size_t kChainNarrowLdsFloats = 10240;  // its zero-padded parameters in LDS: 40 KB (include/gnx.h states the rule)
+size_t chain_narrow_lds_floats(const gnx_chain& c, int k_in);
+// is the function fused: >= 1 layer, a non-zero output width, k_in and every width <= 32, parameters within the LDS budget, rows to run on
+bool chain_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows);
+// entity 0: in0 / in1 / in2 = ef, nf, gf (widths d0, d1, d2); 1: ef', nf, gf; 2: in0 = the materialised [R G][d0] input rows (d1 = d2 = 0)
+int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
+                            float* out, int64_t R, hipStream_t s, const char* name);
+
 // ---- gnx_forward.hip: the validation of a core forward, for the training-mode entries of gnx_dropout.hip (a FormScope of the call's flags open) ----
 int32_t core_forward_check_dims(const gnx_core_params* p);  // (needs no handle)
 int32_t core_forward_check(const gnx_graphs* h, const gnx_core_params* p, int64_t R, const void* ef, const void* nf, const void* gf, const void* ef_out,

@@ -400,6 +400,23 @@ GNX_API size_t gnx_chain_block_workspace_bytes(const gnx_graphs* h, const gnx_ch
 GNX_API int32_t gnx_chain_block_forward(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
                                 int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out, void* workspace, size_t workspace_bytes,
                                 uint32_t flags, void* stream);
+/* The same block with each update function in ONE kernel where its widths are narrow: a row of the entity lives in one lane's registers, is
+ * built there (edge: [ef ; nf[src] ; nf[dst] ; gf_g], node: [sum of the incoming ef' in CSC order ; nf ; gf_g], graph: the materialised
+ * getgraphfninput rows) and runs through ALL layers of the function — Dense with any activation, LayerNorm layer values, a LayerNorm as the
+ * edge function's first layer without an identity Dense in front — with the function's parameters staged in LDS.  The rule is per update
+ * function.  A function is fused when it has at least one layer and a non-zero output width, its input width and every layer width are at
+ * most 32, its zero-padded parameters (a Dense: ceil4(k_in) * ceil4(width) + ceil4(width) floats, a LayerNorm: 2 * ceil4(width), ceil4 = rounded
+ * up to a multiple of 4) fit the kernel's LDS budget of 10240 floats (40 KB), and its entity has rows.
+ * _applies: bit 0 the edge, bit 1 the node, bit 2 the graph function is fused; 0 on bad arguments.  _workspace_bytes: a fused function has
+ * none of the hidden-row / input buffers (the graph function keeps its G input rows); it builds the handle's tables the call reads, so call it
+ * outside a stream capture.  A function outside the rule runs exactly gnx_chain_block_forward's launches for it; with a mask of 0 the call IS
+ * gnx_chain_block_forward (same workspace size, same bits).  A fused function's results are plain fp32 FMA chains in layer order: within the
+ * library's 1e-5 bound of gnx_chain_block_forward's, not its bits.  Arguments and refusals as gnx_chain_block_forward. */
+GNX_API int32_t gnx_chain_block_forward_narrow_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API size_t gnx_chain_block_forward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API int32_t gnx_chain_block_forward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                       int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out, void* workspace, size_t workspace_bytes,
+                                       uint32_t flags, void* stream);
 
 /* ---- backward of the block: what a Zygote `rrule` / torch autograd function for (m::GNBlock)(x) needs.
  * Inputs: the forward's inputs (ef, nf, gf), its outputs (ef_out, nf_out, gf_out) and the upstream gradients with the

@@ -24,7 +24,7 @@ module GraphNetsHIP
 export GNGraphBatch, batch, unbatch, getedgefninput, getnodefninput, getgraphfninput, GNBlock, zerodim2nothing, GNCore, GNCoreList,
        efview, nfview, gfview, flatunpaddednf, flatunpaddedef, collapsef, unpaddedcollapsedef, flatunpaddedcollapsedef
 # ... plus what the drop-in adds: layers as plain structs, pullbacks, the library-side hipGraph model, the multi-GPU split
-export Dense, LayerNorm, ChainBlock, chain_pullback, block_pullback, core_pullback, Model, partition_graphs, DistBlock
+export Dense, LayerNorm, ChainBlock, chain_forward, chain_narrow_applies, chain_pullback, block_pullback, core_pullback, Model, partition_graphs, DistBlock
 # ... and device residency: `x |> batch |> gpu`, `model |> gpu`, `y |> cpu` (what Flux's `gpu` / `cpu` are to the reference)
 export DeviceArray, gpu, cpu, synchronize, chained, flush, steps
 
@@ -843,22 +843,35 @@ function chain_params(m::ChainBlock, keep::Vector{Any})
     end
     GnxChainBlockParams(m.in..., 0, one(m.edgefn), one(m.nodefn), one(m.graphfn))
 end
-function chain_device(m::ChainBlock, x)
+# narrow = true: gnx_chain_block_forward_narrow — every update function whose input and layer widths are at most 32 runs in one kernel (a row per
+# lane through all layers), the others as before; a workspace key of its own
+function chain_device(m::ChainBlock, x; narrow::Bool=false)
     g::GNGraphBatch = x.graphs
     R = replicas(x.ef, x.nf, x.gf)
     keep = Any[]
     p = Ref(chain_params(m, keep))
     oe, on, og = outwidth(m.edgefn), outwidth(m.nodefn), outwidth(m.graphfn)
-    ws = workspace!(g, (:chain, chainkey(m), R)) do
-        ccall((:gnx_chain_block_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R)
+    ws = workspace!(g, (narrow ? :chain_narrow : :chain, chainkey(m), R)) do
+        narrow ? ccall((:gnx_chain_block_forward_narrow_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R) :
+                 ccall((:gnx_chain_block_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R)
     end
     o = (outarray(oe, nedges(g), R), outarray(on, nnodes(g), R), outarray(og, ngraphs(g), R))
-    GC.@preserve m keep x o ws check(ccall((:gnx_chain_block_forward, libgnx), Int32,
+    GC.@preserve m keep x o ws check(narrow ? ccall((:gnx_chain_block_forward_narrow, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cvoid}, Csize_t, UInt32, Ptr{Cvoid}),
+        g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, UInt32(0), STREAM[]) :
+      ccall((:gnx_chain_block_forward, libgnx), Int32,
         (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cvoid}, Csize_t, UInt32, Ptr{Cvoid}),
         g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, UInt32(0), STREAM[]))
     (graphs=g, ef=o[1], nf=o[2], gf=o[3])
 end
+# which update functions gnx_chain_block_forward_narrow fuses on this batch: bit 0 edge, bit 1 node, bit 2 graph
+function chain_narrow_applies(m::ChainBlock, x)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    GC.@preserve m keep ccall((:gnx_chain_block_forward_narrow_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
+end
 (m::ChainBlock)(x) = back(chain_device(gpu(m), gpu(x)), x)
+chain_forward(m::ChainBlock, x; narrow::Bool=false) = back(chain_device(gpu(m), gpu(x); narrow=narrow), x)
 # pullback: gradients w.r.t. the inputs and every layer's (weight, bias); the forward is recomputed inside the library
 function chain_pullback_device(m::ChainBlock, x, ȳ)
     g::GNGraphBatch = x.graphs
