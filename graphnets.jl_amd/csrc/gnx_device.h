@@ -87,6 +87,20 @@ struct RunTable {
 };
 // the table's place in the kernel-argument segment of (BlockArgs, RunTable, ...)
 constexpr unsigned kRunTableOffset = (unsigned)((sizeof(BlockArgs) + 7) / 8 * 8);
+// A run that CARRIES the graph updates of the run before it (k_block_wave_carry: RUN with a CHAIN front): what that update needs of each of
+// the previous run's n slots, by value behind the RunTable as the third kernel argument.
+struct PrevSlot {
+  const float* gf;
+  float* gf_out;
+  const float* partials;
+};
+struct PrevTable {
+  PrevSlot slot[kRunSlots];
+  int n;
+  int per_slot;  // front workgroups per slot: 1 for one graph, (G + 3) / 4 otherwise (a wavefront per graph)
+};
+constexpr unsigned kPrevTableOffset = kRunTableOffset + (unsigned)sizeof(RunTable);
+static_assert(sizeof(RunTable) % 8 == 0, "the PrevTable follows the RunTable without padding");
 
 // relu as ONE v_max_f32.  fmaxf(x, 0.f) compiles to two under the default IEEE mode: a canonicalising v_max_f32 x, x, x in front of the
 // maximum whenever the compiler cannot see that x is the result of an arithmetic instruction (the packed FMAs of the streamed products are

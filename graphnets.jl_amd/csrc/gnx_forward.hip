@@ -439,6 +439,17 @@ static int steps_run_max() {
   return v;
 }
 
+// GNX_STEPS_DEFER=0 (read once): no run carries the graph updates of the run before it — every run of several steps is two launches, the
+// schedule before carrying runs.  For A/B measurements.
+static bool steps_defer_on() {
+  static const bool v = [] {
+    const char* e = getenv("GNX_STEPS_DEFER");
+    return !(e && *e && atoi(e) == 0);
+  }();
+  return v;
+}
+static int partial_rows_of(const gnx_graphs* h);
+
 // The loop of gnx_block_forward_steps (bf16 rows: gnx_block_forward_steps_typed on the native path), on one stream or — `overlap` — on two.  The
 // caller holds the DeviceTurn and the FormScope.
 static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_block_step* steps, int64_t n_steps, int64_t R,
@@ -448,6 +459,11 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
   // dispatch per run instead of per step.  Where the next steps are not such a window (a conflict among them, an invalid step, R > 1,
   // widths without a run kernel, the off-switch) the step is a run of its own: a chained step as before, its graph update pending until the
   // next launch on its stream.
+  // A run's graph updates wait, too, where the next run can CARRY them (fp32 rows, two streams, k_block_wave_carry for the call): if that
+  // run conflicts with this one only in ways that stream order and two partial-row areas resolve (gnx_step_hazard.h: run_defers) it goes on
+  // this run's stream, writes its partial rows to the area this run did not use, and front workgroups of its block launch finish this
+  // run's graph updates beside its tiles — a loop that rotates over as many buffer sets as a run has steps is then one launch per run.
+  // Else they are flushed (k_graph_run on this run's stream) before anything of the next run is issued: the launches of today, in today's order.
   // Two streams: even runs on the caller's, odd runs on a side stream of the handle's pool (taken as gnx_core_forward takes it), so that
   // run j + 1's launch fills the slots that run j's ramp and drain leave idle and the per-launch cost of one hides under the other.
   // Every set taken, GNX_FLAG_NO_FORK, the per-kernel profiler on, or not the fused narrow kernel: one stream, the runs in order.
@@ -496,6 +512,28 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
     GNX_HIP(hipStreamWaitEvent(str[1], aux->fork, 0));
   }
   RunSpans recent[3];  // runs j - 1, j - 2, j - 3
+  int rstream[3] = {0, 0, 0};  // ... and the streams they went to
+  // The pending graph updates of the last run of several steps (run j - 1 while run j is being issued, never older).  area: which partial-row
+  // area of its workspaces that run wrote — A, the block's own (BlockWs::part_off), or B, the head of the agg area, which no fused narrow
+  // kernel touches.  A carrying run writes the other one, so the rows its front reads are not the rows its tiles write.
+  struct RunPending {
+    bool has = false;
+    BlockArgs args;
+    RunTable tab;
+    int n = 0, area = 0, stream = 0;
+    int64_t j = 0;
+  } rpend;
+  const BlockWs bw = valid && !bf16 ? block_ws(h, p, R) : BlockWs{};
+  const bool area_b_fits = valid && !bf16 && bw.part_off - bw.agg_off >= sizeof(float) * (size_t)partial_rows_of(h) * (size_t)((p->oe + p->on + 3) / 4 * 4);
+  const bool can_defer = two && !bf16 && area_b_fits && steps_defer_on();
+  auto flush_run = [&]() -> int32_t {
+    if (!rpend.has) return GNX_OK;
+    rpend.has = false;
+    if (const int32_t frc = launch_block_narrow_run(h, rpend.args, rpend.tab, rpend.n, str[rpend.stream], false, GNX_PHASE_GRAPH)) return frc;
+    // (the run's event again, now behind its graph updates: nothing waits for the earlier record yet)
+    if (const hipError_t e = hipEventRecord(aux->step[rpend.j & 3], str[rpend.stream]); e != hipSuccess) return hip_fail(e, "gnx_block_forward_steps: step event");
+    return GNX_OK;
+  };
   int32_t rc = GNX_OK;
   int64_t i = 0;  // the run's first step
   for (int64_t j = 0; i < n_steps && rc == GNX_OK; ++j) {
@@ -517,10 +555,17 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
       for (int z = 0; ok && z < win.n; ++z) ok = slot_of(steps[i + z], tab.slot[z], z == 0 ? &run_args : nullptr);
       if (ok) cur = win;
     }
-    const int k = two ? (int)(j & 1) : 0, o = k ^ 1;
+    // does this run carry the pending graph updates of the run before it?  Else they are flushed first, as if never deferred.
+    const bool carry_kernel = can_defer && cur.n > 1 && block_narrow_carry_applies(h, run_args);
+    const bool carries = rpend.has && carry_kernel && run_defers(cur, recent[0]);
+    if (!carries && (rc = flush_run())) break;
+    const RunPlace place = two ? run_place(j, carries, rstream) : RunPlace{};
+    const int k = place.stream, o = k ^ 1;
     StepOrder ord;
     if (two) {
-      ord = run_order(cur, recent, j);
+      // (not regular — gnx_step_hazard.h: run_place: behind everything issued so far)
+      if (place.regular) ord = run_order(cur, recent, j);
+      else ord.flush_own = ord.after_other = true;
     } else {
       // one stream: a run whose buffers overlap its predecessor's (a shared workspace / gf_out, or gf' read as the next step's input) cannot
       // start before that one's graph update has run
@@ -540,7 +585,22 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
     }
     if (cur.n > 1) {
       // (validated above: a failure here is a launch failure; nothing of this run is pending afterwards)
-      rc = launch_block_narrow_run(h, run_args, tab, cur.n, str[k], bf16);
+      if (carries) {
+        PrevTable prev{};
+        prev.n = rpend.n;
+        for (int z = 0; z < rpend.n; ++z) prev.slot[z] = PrevSlot{rpend.tab.slot[z].gf, rpend.tab.slot[z].gf_out, rpend.tab.slot[z].partials};
+        const int area = rpend.area ^ 1;
+        if (area == 1)
+          for (int z = 0; z < cur.n; ++z) tab.slot[z].partials = reinterpret_cast<float*>(static_cast<char*>(steps[i + z].workspace) + bw.agg_off);
+        rpend.has = false;  // (in this launch or, if it fails, nowhere: a launch failure)
+        rc = launch_block_narrow_carry(h, run_args, tab, cur.n, prev, str[k]);
+        if (rc == GNX_OK) { rpend.has = true; rpend.args = run_args; rpend.tab = tab; rpend.n = cur.n; rpend.area = area; rpend.stream = k; rpend.j = j; }
+      } else if (carry_kernel) {
+        rc = launch_block_narrow_run(h, run_args, tab, cur.n, str[k], false, GNX_PHASE_EDGE_NODE);
+        if (rc == GNX_OK) { rpend.has = true; rpend.args = run_args; rpend.tab = tab; rpend.n = cur.n; rpend.area = 0; rpend.stream = k; rpend.j = j; }
+      } else {
+        rc = launch_block_narrow_run(h, run_args, tab, cur.n, str[k], bf16);
+      }
     } else {
       gnx_pending_update next{};
       rc = run(st, k, &next);
@@ -553,10 +613,12 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
       if (const hipError_t e = hipEventRecord(aux->step[j & 3], str[k]); e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: step event"); break; }
     }
     recent[2] = recent[1]; recent[1] = recent[0]; recent[0] = cur;
+    rstream[2] = rstream[1]; rstream[1] = rstream[0]; rstream[0] = k;
     i += cur.n;
   }
   // the last one-step runs' graph updates (one per stream), then the join — on every path, so that a capture never ends with the side stream
   // un-joined and an error leaves everything issued so far complete when the caller's stream is
+  const int32_t rfr = flush_run();
   const int32_t rf0 = flush(0), rf1 = two ? flush(1) : GNX_OK;
   hipError_t e1 = hipSuccess, e2 = hipSuccess;
   if (two) {
@@ -564,6 +626,7 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
     e2 = hipStreamWaitEvent(str[0], aux->join, 0);
   }
   if (rc) return rc;
+  if (rfr) return rfr;
   if (rf0) return rf0;
   if (rf1) return rf1;
   GNX_HIP(e1);

@@ -52,7 +52,9 @@ bool narrow_bf16_ln_aot(const gnx_graphs* h, const BlockArgs& a);
 int32_t launch_ln_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
 bool block_narrow_run_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16);
 bool narrow_bf16_run(const gnx_graphs* h, const BlockArgs& a);
-int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16);
+int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16, int phase = 3);
+bool block_narrow_carry_applies(const gnx_graphs* h, const BlockArgs& a);
+int32_t launch_block_narrow_carry(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, const PrevTable& prev, hipStream_t s);
 int32_t launch_run_bf16(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s);
 bool jit_eligible(const BlockArgs& a, int ept);
 int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph, bool bf16 = false);

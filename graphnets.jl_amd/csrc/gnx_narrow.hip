@@ -159,20 +159,54 @@ bool block_narrow_run_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16
 #undef GNX_CASE
   return false;
 }
-int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16) {
-  if (bf16) {  // ... on bf16 rows: gnx_narrow_bf16.hip
+int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16, int phase) {
+  if (bf16) {  // ... on bf16 rows: gnx_narrow_bf16.hip (always both launches)
+    if (phase != 3) return fail(GNX_ERR_INVALID_ARG, "internal: a bf16 run is issued whole");
     const int32_t rc = launch_run_bf16(h, a, t, Z, s);
     return rc == 1 ? fail(GNX_ERR_INVALID_ARG, "internal: bf16 run launch for a width set without that kernel") : rc;
   }
 #define GNX_CASE(DE, DN, DG, OE, ON)                                                                                               \
   if (a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) {                                                         \
     if constexpr (OE + ON > 0) {                                                                                                   \
-      return h->G == 1 ? launch_wave_run<DE, DN, DG, OE, ON, true>(h, a, t, Z, s) : launch_wave_run<DE, DN, DG, OE, ON, false>(h, a, t, Z, s); \
+      return h->G == 1 ? launch_wave_run<DE, DN, DG, OE, ON, true>(h, a, t, Z, s, phase) : launch_wave_run<DE, DN, DG, OE, ON, false>(h, a, t, Z, s, phase); \
     }                                                                                                                              \
   }
   GNX_NARROW_RUN_DIMS(GNX_CASE)
 #undef GNX_CASE
   return fail(GNX_ERR_INVALID_ARG, "internal: run launch for a width set without that kernel");
+}
+
+// A run whose block launch carries the graph updates of the run before it (k_block_wave_carry; fp32 rows): the run sets whose carrying
+// kernel keeps the run kernel's limits — no scratch, at most 80 scalar registers, no more vector registers than the chained kernel of the
+// set (tests/test_steps_deferred_cpu.py) — in the one-graph form (X1) and the several-graphs form (XG).  A set or form without one keeps the
+// two launches per run: of GNX_NARROW_RUN_DIMS, (2,2,2)=>(2,2) — its carrying kernel takes 55 vector registers in both forms, its chained
+// kernel 54.
+#define GNX_NARROW_CARRY_DIMS(X1, XG) \
+  X1(10, 5, 0, 3, 4) XG(10, 5, 0, 3, 4) \
+  X1(3, 4, 5, 3, 4) XG(3, 4, 5, 3, 4)   \
+  X1(10, 5, 3, 3, 4) XG(10, 5, 3, 3, 4) \
+  X1(0, 2, 0, 2, 2) XG(0, 2, 0, 2, 2)   \
+  X1(4, 3, 2, 3, 4) XG(4, 3, 2, 3, 4)
+bool block_narrow_carry_applies(const gnx_graphs* h, const BlockArgs& a) {
+  if (!block_narrow_run_applies(h, a, false)) return false;
+#define GNX_CASE1(DE, DN, DG, OE, ON) \
+  if (h->G == 1 && a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return true;
+#define GNX_CASEG(DE, DN, DG, OE, ON) \
+  if (h->G != 1 && a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return true;
+  GNX_NARROW_CARRY_DIMS(GNX_CASE1, GNX_CASEG)
+#undef GNX_CASE1
+#undef GNX_CASEG
+  return false;
+}
+int32_t launch_block_narrow_carry(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, const PrevTable& prev, hipStream_t s) {
+#define GNX_CASE1(DE, DN, DG, OE, ON) \
+  if (h->G == 1 && a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return launch_wave_carry<DE, DN, DG, OE, ON, true>(h, a, t, Z, prev, s);
+#define GNX_CASEG(DE, DN, DG, OE, ON) \
+  if (h->G != 1 && a.de == DE && a.dn == DN && a.dg == DG && a.oe == OE && a.on == ON) return launch_wave_carry<DE, DN, DG, OE, ON, false>(h, a, t, Z, prev, s);
+  GNX_NARROW_CARRY_DIMS(GNX_CASE1, GNX_CASEG)
+#undef GNX_CASE1
+#undef GNX_CASEG
+  return fail(GNX_ERR_INVALID_ARG, "internal: carrying run launch for a width set without that kernel");
 }
 
 // the edge FeedForward + residual of a narrow GNCore inside the block kernel (k_block_wave<..., FFE>): ahead-of-time widths, identity / relu

@@ -61,23 +61,45 @@ static int32_t launch_wave_g(const gnx_graphs* h, const BlockArgs& a, int64_t R,
 
 // A run of Z steps of gnx_block_forward_steps (a.ef ... a.partials unused: the slots of `t`): every slot's edge + node update in one launch
 // (k_block_wave_run, slot-major: x fastest), then every slot's graph update in a second one right behind it, with k_graph_t's thread count.
+// phase: GNX_PHASE_EDGE_NODE alone leaves the graph updates to a later launch (the next run's front, or this function with GNX_PHASE_GRAPH).
 template <int DE, int DN, int DG, int OE, int ON, bool ONEG, bool BF16 = false>
-static int32_t launch_wave_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s) {
+static int32_t launch_wave_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, int phase = 3) {
   constexpr int C = OE + ON;
   if (Z < 1 || Z > kRunSlots) return fail(GNX_ERR_INVALID_ARG, "internal: a run of more steps than the table has slots");
   const int n_rows = partial_rows(h);
-  {
+  if (phase & 1) {
     ProfScope ps("k_block_wave", s);
     GNX_LAUNCH((k_block_wave_run<DE, DN, DG, OE, ON, 2, ONEG, BF16>), dim3((unsigned)((a.n_wtiles + 3) / 4), (unsigned)Z), dim3(kThreads), 0, s, a, t, n_rows);
     GNX_HIP(hipGetLastError());
   }
-  if (a.og > 0) {
+  if ((phase & 2) && a.og > 0) {
     const int threads = graph_update_threads(h);
     const size_t lds = sizeof(float) * (size_t)graph_update_lds_floats(C, a.dg, a.og, threads);
     ProfScope ps("k_graph_t", s);
     GNX_LAUNCH((k_graph_run<C, ONEG, BF16>), dim3((unsigned)a.G, (unsigned)Z), dim3(threads), lds, s, a, t, n_rows);
     GNX_HIP(hipGetLastError());
   }
+  return GNX_OK;
+}
+
+// A run of Z steps whose launch also carries the graph updates of the run before it (k_block_wave_carry; fp32 rows) in a.prev_blocks front
+// workgroups per row.  The block launch only: this run's own graph updates are pending afterwards.
+template <int DE, int DN, int DG, int OE, int ON, bool ONEG>
+static int32_t launch_wave_carry(const gnx_graphs* h, const BlockArgs& a0, const RunTable& t, int Z, const PrevTable& prev0, hipStream_t s) {
+  if (Z < 1 || Z > kRunSlots || prev0.n < 1 || prev0.n > kRunSlots) return fail(GNX_ERR_INVALID_ARG, "internal: a run of more steps than the table has slots");
+  BlockArgs a = a0;
+  PrevTable prev = prev0;
+  prev.per_slot = h->G == 1 ? 1 : (int)((h->G + 3) / 4);
+  // The front (gnx_wave_kernel.h: CHAIN with RUN).  One graph: the previous run's slot x in the x-th workgroup behind the tiles of row 0.
+  // Several graphs: per_slot workgroups per slot in front of the tiles, slots y, y + Z, ... in row y.  Rounded up to a multiple of 8 (the
+  // workgroups beyond return at once): workgroup x + gridDim.x * y goes to XCD (x + gridDim.x * y) % 8, so a front that is no multiple of
+  // 8 would shift a tile's XCD from slot to slot; with it the slots of a tile meet in one L2, as in k_block_wave_run.
+  a.prev_blocks = ((h->G == 1 ? prev.n : prev.per_slot * ((prev.n + Z - 1) / Z)) + 7) / 8 * 8;
+  const int n_rows = partial_rows(h);
+  ProfScope ps("k_block_wave", s);
+  GNX_LAUNCH((k_block_wave_carry<DE, DN, DG, OE, ON, 2, ONEG>), dim3((unsigned)((a.n_wtiles + 3) / 4) + (unsigned)a.prev_blocks, (unsigned)Z), dim3(kThreads), 0, s, a, t,
+             prev, n_rows);
+  GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
 

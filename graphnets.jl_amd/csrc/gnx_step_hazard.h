@@ -126,4 +126,63 @@ inline StepOrder run_order(const RunSpans& cur, const RunSpans* recent, long lon
   return o;
 }
 
+// ---- a run that carries the graph updates of the run before it (k_block_wave_carry: front workgroups of ITS block launch) ----
+// Run `prev` is issued as its block launch alone and its graph updates wait; if the next run conflicts with it — so that it would be ordered
+// behind it anyway — and every conflict is of a kind that stream order plus two partial-row areas resolves, the next run goes on prev's
+// stream and its launch carries them.  What then runs at the same time is prev's graph updates (they read prev's gf and the partial rows
+// in prev's workspaces, they write prev's gf_out) and cur's edge + node updates (they read cur's inputs, they write cur's ef_out, nf_out
+// and the partial rows in cur's workspaces).  Between a step x of cur and a step y of prev these overlaps are harmless:
+//   x's ef_out / nf_out with y's ef_out / nf_out — write after write, ordered by the two block launches;
+//   x's gf_out with y's gf_out — y's update runs in cur's launch, x's in a later one;
+//   x's workspace with y's, if they are THE SAME workspace — cur writes the partial-row area that prev did not (steps_schedule).
+// Every other overlap that makes the two steps conflict (steps_conflict) keeps today's order: prev's graph updates as a launch of their
+// own, then cur.  Among them the ones that would race — cur reading what prev's update writes (dims -> dims: gf' fed back), cur's ef_out /
+// nf_out over prev's gf, gf_out or workspace, workspaces that overlap without being the same — and, conservatively, all the rest.
+inline bool spans_identical(ByteSpan a, ByteSpan b) { return a.lo == b.lo && a.hi == b.hi; }
+
+// may step x (of the later run) be in a launch whose front finishes step y's graph update?  (No overlap at all: yes.)
+inline bool step_defers(const StepSpans& x, const StepSpans& y) {
+  for (int t = 0; t < 4; ++t) {
+    for (const ByteSpan& r : y.rd) if (spans_overlap(x.wr[t], r)) return false;
+    for (int u = 0; u < 4; ++u) {
+      if (!spans_overlap(x.wr[t], y.wr[u])) continue;
+      const bool rows = t < 2 && u < 2, gf_out = t == 2 && u == 2, ws = t == 3 && u == 3 && spans_identical(x.wr[3], y.wr[3]);
+      if (!rows && !gf_out && !ws) return false;
+    }
+  }
+  for (const ByteSpan& w : y.wr)
+    for (const ByteSpan& r : x.rd) if (spans_overlap(w, r)) return false;
+  return true;
+}
+
+// does run `cur` carry the graph updates of run `prev`, the run right before it?  (The caller also asks that the kernel exists for the call
+// and that the second partial-row area fits.)
+inline bool run_defers(const RunSpans& cur, const RunSpans& prev) {
+  if (cur.n < 2 || prev.n < 2 || !runs_conflict(cur, prev)) return false;
+  for (int a = 0; a < cur.n; ++a)
+    for (int b = 0; b < prev.n; ++b)
+      if (!step_defers(cur.step[a], prev.step[b])) return false;
+  return true;
+}
+
+// The two-stream schedule with carrying runs.  A carrying run stays on the stream of the run it follows, so the runs no longer alternate
+// between the streams, which is what run_order and the wait for run j - 3 assume.  A run is REGULAR if it and the three before it all sit
+// on the stream of their parity (j & 1): then the schedule is today's, decision for decision.  Any other run (a carrying run, or one with a
+// carrying run among the three before it) is ordered behind EVERYTHING issued before it on both streams — it costs nothing where it
+// happens: a carrying run conflicts with its predecessor and waits for it anyway.  With that, when launch j starts every launch up to
+// j - 4 has ended, as before: an irregular run waits for all of them; a regular one waits for run j - 3 on the other stream and follows
+// run j - 2 on its own, and every older run is in front of one of the two in stream order.
+struct RunPlace {
+  int stream = 0;        // the stream run j is issued on
+  bool regular = true;   // run_order's decisions hold; else the run waits for everything issued so far
+};
+// recent_stream[d - 1]: the stream of run j - d, d = 1 .. min(j, 3); carries: run j carries run j - 1's graph updates
+inline RunPlace run_place(long long j, bool carries, const int* recent_stream) {
+  RunPlace p;
+  p.stream = carries ? recent_stream[0] : (int)(j & 1);
+  p.regular = p.stream == (int)(j & 1);
+  for (int d = 1; d <= 3 && d <= j; ++d) p.regular = p.regular && recent_stream[d - 1] == (int)((j - d) & 1);
+  return p;
+}
+
 }  // namespace gnx

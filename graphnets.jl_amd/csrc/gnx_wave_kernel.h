@@ -800,6 +800,15 @@ __device__ __forceinline__ cslotp run_slot() {
   return p;
 }
 
+// ... and the previous run's table of a carrying run (k_block_wave_carry)
+typedef const PrevTable __attribute__((address_space(4))) * cprevp;
+__device__ __forceinline__ cprevp run_prev() {
+  typedef const char __attribute__((address_space(4))) * ccharp;
+  cprevp p = (cprevp)((ccharp)__builtin_amdgcn_kernarg_segment_ptr() + kPrevTableOffset);
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 // OUT32 (with BF16; the block of a narrow bf16 GNCore, gnx_core_forward_typed): the INPUT rows are bf16, the block's own outputs — nf', and ef'
 // without FFE — are stored as fp32 (they are intermediates of the core: the post kernels add the residual terms to them unrounded); with FFE
 // the edge lanes store the CORE's edge row, rounded once, as bf16.
@@ -807,7 +816,8 @@ template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, b
 __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   static_assert(!OUT32 || (BF16 && LN), "OUT32: bf16 rows in, fp32 rows out — the LayerNorm-on-load block of a bf16 core");
   constexpr bool OBF16 = BF16 && !OUT32;  // element type of the ef' / nf' rows this kernel stores
-  static_assert(!RUN || (!PACK && !FFE && !LN && !CHAIN && OE + ON > 0), "RUN: the two-launch form of a plain block, one slot per step");
+  static_assert(!RUN || (!PACK && !FFE && !LN && OE + ON > 0), "RUN: the two-launch form of a plain block, one slot per step");
+  static_assert(!(RUN && CHAIN) || !BF16, "RUN with a CHAIN front (k_block_wave_carry): fp32 rows only");
   static_assert(!(PACK && ONEG), "packs are for batches of several graphs");
   static_assert(!BF16 || OUT32 || (!FFE && !LN), "bf16 features: the plain block forward and its chained form; a core's block hands on fp32");
   static_assert(!CHAIN || (!PACK && !FFE && !LN && OE + ON > 0), "CHAIN: the two-launch form of a plain block");
@@ -827,7 +837,43 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   typedef const int __attribute__((address_space(4))) * cintp;
   int bx = blockIdx.x, gx = gridDim.x;  // this call's tiles are the blocks behind the chained ones
-  if constexpr (CHAIN) {
+  if constexpr (CHAIN && RUN) {
+    // the front of a run: the graph updates of the PREVIOUS run's slots, from the PrevTable behind the RunTable — read here, afresh, so that
+    // nothing of it is held by the tiles' workgroups.  One slot per workgroup (a loop over slots here costs the whole kernel 22 vector
+    // registers); the launcher rounds a.prev_blocks up to a multiple of 8, and front workgroups without a slot return.
+    if constexpr (ONEG) {
+      // One graph: the a.prev_blocks workgroups BEHIND the tiles of every row, slot x in the x-th of them in ROW 0.  Behind: the tiles keep
+      // blockIdx.x, as in k_block_wave_run (in front of them, the kernel's tiles were 5 % slower than that kernel's).  Row 0: workgroups are
+      // dispatched row by row and a slot's update is one workgroup of ~15 us — behind row 0's tiles it starts 1 / Z into the launch and ends
+      // long before the tiles do; behind the last row's it would outlast them.
+      gx = (a.n_wtiles + 3) / 4;
+      if (bx >= gx) {
+        if (a.og > 0 && blockIdx.y == 0) {
+          const cprevp P = run_prev();
+          if (const int z = bx - gx; z < P->n) {
+            graph_update_rows<C, false, 4, BF16>(a, P->slot[z].gf, P->slot[z].gf_out, P->slot[z].partials, 0, 0, 0, gx, (int)threadIdx.x, kThreads, s_mem,
+                                                 graph_update_threads_for_rows(gx));
+          }
+        }
+        return;
+      }
+    } else {
+      // Several graphs: in FRONT of every row's tiles, P->per_slot workgroups per slot, a wavefront per graph (<= 256 partial rows each:
+      // short); the workgroups blockIdx.x / per_slot == q of row y take slot y + q Z (the previous run may have had more slots than this
+      // one has rows).
+      if (bx < a.prev_blocks) {
+        if (a.og > 0) {
+          const cprevp P = run_prev();
+          const int q = bx / P->per_slot;
+          const int g = (bx - q * P->per_slot) * WAVES + wv;
+          if (const int z = (int)blockIdx.y + q * (int)gridDim.y; z < P->n && g < a.G)
+            graph_update_rows<C, true, 4, BF16>(a, P->slot[z].gf, P->slot[z].gf_out, P->slot[z].partials, g, 0, a.wtile_off[g], a.wtile_off[g + 1], lane, 64, s_mem + wv * WSL);
+        }
+        return;
+      }
+      bx -= a.prev_blocks; gx -= a.prev_blocks;
+    }
+  } else if constexpr (CHAIN) {
     if ((int)blockIdx.x < a.prev_blocks) {
       if (a.og > 0) {
         constexpr int CPc = (C + 3) / 4 * 4;
@@ -1310,6 +1356,16 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 template <int DE, int DN, int DG, int OE, int ON, int EPT, bool ONEG, bool BF16 = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(GNX_WAVE_SGPRS))) void k_block_wave_run(BlockArgs a, RunTable t, int n_rows) {
   block_wave_body<DE, DN, DG, OE, ON, EPT, false, ONEG, false, false, false, BF16, true>(a, n_rows);
+}
+
+// A run that carries the graph updates of the run before it (RUN and CHAIN above; fp32 rows): grid ((n_wtiles + 3) / 4 + a.prev_blocks, Z).
+// The a.prev_blocks "front" workgroups of a row (behind its tiles for one graph, in front of them for several: see the body) finish the
+// previous run's slots as k_graph_run would (the CHAIN front's emulation of its thread count: the same bits), the others are
+// k_block_wave_run's.  The previous run wrote the OTHER partial-row area of its workspaces
+// (gnx_forward.hip: steps_schedule), so the rows the front reads are not the rows this launch's tiles write.
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool ONEG>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(GNX_WAVE_SGPRS))) void k_block_wave_carry(BlockArgs a, RunTable t, PrevTable pt, int n_rows) {
+  block_wave_body<DE, DN, DG, OE, ON, EPT, false, ONEG, false, false, true, false, true>(a, n_rows);
 }
 
 // Graph update for the wave path: one workgroup per graph (one wavefront when the graph has <= 256 partial rows).
