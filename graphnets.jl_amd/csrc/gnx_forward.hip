@@ -454,16 +454,9 @@ static int partial_rows_of(const gnx_graphs* h);
 // caller holds the DeviceTurn and the FormScope.
 static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, int32_t elem, const gnx_block_step* steps, int64_t n_steps, int64_t R,
                               uint32_t flags, void* stream, bool overlap) {
-  // The unit of the schedule is the RUN (gnx_step_hazard.h): steps_run_max() neighbouring steps no two of which conflict — or the last four
-  // or more of the loop — issued as ONE block launch with a slot per step and one launch for their graph updates: a ramp, a drain and a
-  // dispatch per run instead of per step.  Where the next steps are not such a window (a conflict among them, an invalid step, R > 1,
-  // widths without a run kernel, the off-switch) the step is a run of its own: a chained step as before, its graph update pending until the
-  // next launch on its stream.
-  // A run's graph updates wait, too, where the next run can CARRY them (fp32 rows, two streams, k_block_wave_carry for the call): if that
-  // run conflicts with this one only in ways that stream order and two partial-row areas resolve (gnx_step_hazard.h: run_defers) it goes on
-  // this run's stream, writes its partial rows to the area this run did not use, and front workgroups of its block launch finish this
-  // run's graph updates beside its tiles — a loop that rotates over as many buffer sets as a run has steps is then one launch per run.
-  // Else they are flushed (k_graph_run on this run's stream) before anything of the next run is issued: the launches of today, in today's order.
+  // The schedule lives in gnx_step_hazard.h (StepsPlanner): which steps share a launch, which stream a run goes to, what it waits for, where
+  // a graph update ends up.  Here: the side stream, the spans and the validation of the steps a window holds, the launch predicates, and
+  // the planner's operations issued one by one.
   // Two streams: even runs on the caller's, odd runs on a side stream of the handle's pool (taken as gnx_core_forward takes it), so that
   // run j + 1's launch fills the slots that run j's ramp and drain leave idle and the per-launch cost of one hides under the other.
   // Every set taken, GNX_FLAG_NO_FORK, the per-kernel profiler on, or not the fused narrow kernel: one stream, the runs in order.
@@ -471,32 +464,22 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
   const gnx_graphs::AuxSet* aux = hold.set;
   const bool two = aux != nullptr;
   hipStream_t str[2] = {(hipStream_t)stream, aux ? aux->stream : nullptr};
-  // the pending graph update of each stream: a one-step run's rides at the front of the next ONE-STEP launch on ITS stream (run j + 1's on
-  // one stream, run j + 2's on two); a launch of several steps has no such front and the update is flushed ahead of it
-  gnx_pending_update pend[2]{};
-  auto flush = [&](int k) -> int32_t {
-    if (!pend[k].workspace) return GNX_OK;
-    const int32_t rc = graph_update(h, p, elem, pend[k], R, flags, str[k]);
-    pend[k] = gnx_pending_update{};
-    return rc;
-  };
-  auto run = [&](const gnx_block_step& st, int k, gnx_pending_update* next) -> int32_t {
-    const gnx_pending_update* prev = pend[k].workspace ? &pend[k] : nullptr;
-    return chained_step(BlockCall{h, p, elem, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[k], GNX_PHASE_ALL},
-                        prev, next);
-  };
   const bool bf16 = elem == GNX_ELEM_BF16;
   const bool valid = h && p && check_block(h, p, R) == GNX_OK;  // (else the first step reports the error)
   // per feature: 4 or 2 bytes; the workspace extent is the workspace query's (bf16 on this path: the native kernels, no staging)
   const size_t elem_bytes = bf16 ? 2 : sizeof(float);
   const size_t ws_extent = !valid ? 0 : bf16 ? typed_ws(h, p, R, true).total : block_ws(h, p, R).total;
+  auto call_of = [&](const gnx_block_step& st, hipStream_t s) {
+    return BlockCall{h, p, elem, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, s, GNX_PHASE_ALL};
+  };
+  auto pending_of = [&](long long s) { return gnx_pending_update{steps[s].workspace, steps[s].workspace_bytes, steps[s].gf, steps[s].gf_out}; };
   // several steps per launch: replicas use blockIdx.y themselves; the widths and the batch must be ones with a run kernel (asked at the first candidate)
   // (the per-kernel profiler attributes time launch by launch, one step each: with it on every run is one step)
   bool can_fuse = valid && R == 1 && !(flags & GNX_FLAG_FORCE_GENERIC) && steps_run_max() > 1 && !profile_enabled();
   // a step joins a run only VALIDATED (the whole step's arguments and workspace): an invalid one starts a run of its own, whose chained
   // step reports the error once everything before it has been issued.  run_args: the launch's shared arguments, from the run's first step.
   auto slot_of = [&](const gnx_block_step& st, RunSlot& sl, BlockArgs* run_args) -> bool {
-    Prepared q(BlockCall{h, p, elem, st.ef, st.nf, st.gf, R, st.ef_out, st.nf_out, st.gf_out, st.workspace, st.workspace_bytes, flags, str[0], GNX_PHASE_ALL});
+    Prepared q(call_of(st, str[0]));
     if (q.rc) return false;
     if (run_args) {
       if (!block_narrow_run_applies(h, q.a, bf16)) return can_fuse = false;
@@ -505,42 +488,74 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
     sl = RunSlot{q.a.ef, q.a.nf, q.a.gf, q.a.ef_out, q.a.nf_out, q.a.gf_out, q.a.partials};
     return true;
   };
-  // The schedule and its hazard rule: gnx_step_hazard.h (run_order).  Run j waits for run j - 3's launches (the ring of events aux->step),
-  // so that only runs up to three apart can be in flight together; conflicts among those are ordered as run_order says.
+  // The two partial-row areas of a workspace: A, the block's own (BlockWs::part_off), and B, the head of the agg area, which no fused narrow
+  // kernel touches.  A carrying run writes the one its predecessor did not, so the rows its front reads are not the rows its tiles write.
+  const BlockWs bw = valid && !bf16 ? block_ws(h, p, R) : BlockWs{};
+  const bool area_b_fits = valid && !bf16 && bw.part_off - bw.agg_off >= sizeof(float) * (size_t)partial_rows_of(h) * (size_t)((p->oe + p->on + 3) / 4 * 4);
+  StepsPlanner planner(two, !bf16 && area_b_fits && steps_defer_on(), steps_run_max(), n_steps);
+  // run j's table and shared arguments in [j & 1]: a deferred run is the one before the run being issued, never older
+  RunTable tab[2];
+  BlockArgs args[2];
+  bool took = false;  // the last one-step launch left its graph update pending
+  auto hip_rc = [](hipError_t e, const char* what) { return e == hipSuccess ? GNX_OK : hip_fail(e, what); };
+  auto issue = [&](const StepsOp& op) -> int32_t {
+    const hipStream_t s = str[op.stream];
+    switch (op.kind) {
+      case kOpFlushRun:
+        if (const int32_t rc = launch_block_narrow_run(h, args[op.run & 1], tab[op.run & 1], op.n, s, false, GNX_PHASE_GRAPH)) return rc;
+        // (the run's event again, now behind its graph updates: nothing waits for the earlier record yet)
+        return hip_rc(hipEventRecord(aux->step[op.run & 3], s), "gnx_block_forward_steps: step event");
+      case kOpFlushStep: return graph_update(h, p, elem, pending_of(op.step), R, flags, s);
+      case kOpWaitRun: return hip_rc(hipStreamWaitEvent(s, aux->step[op.run & 3], 0), "gnx_block_forward_steps: ordering a step behind the step three before it");
+      case kOpBehindOther: {
+        hipEvent_t ev = op.stream == 0 ? aux->join : aux->fork;
+        hipError_t e = hipEventRecord(ev, str[op.stream ^ 1]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, ev, 0);
+        return hip_rc(e, "gnx_block_forward_steps: ordering a step behind the other stream");
+      }
+      case kOpLaunchStep: {
+        // (an argument error of this step: what is pending belongs to earlier steps, whose arguments were valid — finished at the end, then the error)
+        const gnx_pending_update prev = op.ride >= 0 ? pending_of(op.ride) : gnx_pending_update{};
+        gnx_pending_update next{};
+        const int32_t rc = chained_step(call_of(steps[op.step], s), op.ride >= 0 ? &prev : nullptr, &next);
+        took = next.workspace != nullptr;
+        return rc;
+      }
+      case kOpLaunchRun: {
+        // (validated before it was planned: a failure here is a launch failure; nothing of this run is pending afterwards)
+        const BlockArgs& a = args[op.run & 1];
+        RunTable& t = tab[op.run & 1];
+        if (op.area == 1)
+          for (int z = 0; z < op.n; ++z) t.slot[z].partials = reinterpret_cast<float*>(static_cast<char*>(steps[op.step + z].workspace) + bw.agg_off);
+        if (op.form == kRunBlock) return launch_block_narrow_run(h, a, t, op.n, s, false, GNX_PHASE_EDGE_NODE);
+        if (op.form == kRunWhole) return launch_block_narrow_run(h, a, t, op.n, s, bf16);
+        const RunTable& pt = tab[(op.run & 1) ^ 1];
+        PrevTable prev{};
+        prev.n = op.ride_n;
+        for (int z = 0; z < op.ride_n; ++z) prev.slot[z] = PrevSlot{pt.slot[z].gf, pt.slot[z].gf_out, pt.slot[z].partials};
+        return launch_block_narrow_carry(h, a, t, op.n, prev, s);
+      }
+      case kOpRecordRun: return hip_rc(hipEventRecord(aux->step[op.run & 3], s), "gnx_block_forward_steps: step event");
+      case kOpJoin: {
+        const hipError_t e1 = hipEventRecord(aux->join, str[1]), e2 = hipStreamWaitEvent(str[0], aux->join, 0);
+        GNX_HIP(e1);
+        GNX_HIP(e2);
+        return GNX_OK;
+      }
+    }
+    return GNX_OK;
+  };
   if (two) {
     GNX_HIP(hipEventRecord(aux->fork, str[0]));
     GNX_HIP(hipStreamWaitEvent(str[1], aux->fork, 0));
   }
-  RunSpans recent[3];  // runs j - 1, j - 2, j - 3
-  int rstream[3] = {0, 0, 0};  // ... and the streams they went to
-  // The pending graph updates of the last run of several steps (run j - 1 while run j is being issued, never older).  area: which partial-row
-  // area of its workspaces that run wrote — A, the block's own (BlockWs::part_off), or B, the head of the agg area, which no fused narrow
-  // kernel touches.  A carrying run writes the other one, so the rows its front reads are not the rows its tiles write.
-  struct RunPending {
-    bool has = false;
-    BlockArgs args;
-    RunTable tab;
-    int n = 0, area = 0, stream = 0;
-    int64_t j = 0;
-  } rpend;
-  const BlockWs bw = valid && !bf16 ? block_ws(h, p, R) : BlockWs{};
-  const bool area_b_fits = valid && !bf16 && bw.part_off - bw.agg_off >= sizeof(float) * (size_t)partial_rows_of(h) * (size_t)((p->oe + p->on + 3) / 4 * 4);
-  const bool can_defer = two && !bf16 && area_b_fits && steps_defer_on();
-  auto flush_run = [&]() -> int32_t {
-    if (!rpend.has) return GNX_OK;
-    rpend.has = false;
-    if (const int32_t frc = launch_block_narrow_run(h, rpend.args, rpend.tab, rpend.n, str[rpend.stream], false, GNX_PHASE_GRAPH)) return frc;
-    // (the run's event again, now behind its graph updates: nothing waits for the earlier record yet)
-    if (const hipError_t e = hipEventRecord(aux->step[rpend.j & 3], str[rpend.stream]); e != hipSuccess) return hip_fail(e, "gnx_block_forward_steps: step event");
-    return GNX_OK;
-  };
   int32_t rc = GNX_OK;
-  int64_t i = 0;  // the run's first step
-  for (int64_t j = 0; i < n_steps && rc == GNX_OK; ++j) {
+  while (planner.first < n_steps && rc == GNX_OK) {
+    const int64_t i = planner.first;
     const gnx_block_step& st = steps[i];
+    RunTable& t = tab[planner.j & 1] = RunTable{};
+    BlockArgs& a = args[planner.j & 1] = BlockArgs{};
     RunSpans cur;
-    RunTable tab{};
-    BlockArgs run_args{};
     cur.step[0] = valid ? step_spans(h, p, R, st, elem_bytes, ws_extent) : StepSpans{};
     cur.n = 1;
     if (can_fuse && n_steps - i >= 2) {
@@ -548,90 +563,29 @@ static int32_t steps_schedule(const gnx_graphs* h, const gnx_block_params* p, in
       RunSpans win = cur;
       while (i + win.n < n_steps) {
         const StepSpans sp = step_spans(h, p, R, steps[i + win.n], elem_bytes, ws_extent);
-        if (!run_takes(win, sp, steps_run_max())) break;
+        if (!planner.takes(win, sp)) break;
         win.step[win.n++] = sp;
       }
-      bool ok = window_is_run(win.n, i, n_steps, steps_run_max());
-      for (int z = 0; ok && z < win.n; ++z) ok = slot_of(steps[i + z], tab.slot[z], z == 0 ? &run_args : nullptr);
+      bool ok = planner.is_run(win.n);
+      for (int z = 0; ok && z < win.n; ++z) ok = slot_of(steps[i + z], t.slot[z], z == 0 ? &a : nullptr);
       if (ok) cur = win;
     }
-    // does this run carry the pending graph updates of the run before it?  Else they are flushed first, as if never deferred.
-    const bool carry_kernel = can_defer && cur.n > 1 && block_narrow_carry_applies(h, run_args);
-    const bool carries = rpend.has && carry_kernel && run_defers(cur, recent[0]);
-    if (!carries && (rc = flush_run())) break;
-    const RunPlace place = two ? run_place(j, carries, rstream) : RunPlace{};
-    const int k = place.stream, o = k ^ 1;
-    StepOrder ord;
-    if (two) {
-      // (not regular — gnx_step_hazard.h: run_place: behind everything issued so far)
-      if (place.regular) ord = run_order(cur, recent, j);
-      else ord.flush_own = ord.after_other = true;
-    } else {
-      // one stream: a run whose buffers overlap its predecessor's (a shared workspace / gf_out, or gf' read as the next step's input) cannot
-      // start before that one's graph update has run
-      ord.flush_own = pend[0].workspace && (pend[0].workspace == st.workspace || (p && p->og > 0 && pend[0].gf_out == st.gf_out) || runs_conflict(cur, recent[0]));
-    }
-    if ((ord.flush_own || cur.n > 1) && (rc = flush(k))) break;
-    if (two && j >= 3) {
-      const hipError_t e = hipStreamWaitEvent(str[k], aux->step[(j - 3) & 3], 0);
-      if (e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: ordering a step behind the step three before it"); break; }
-    }
-    if (ord.after_other) {
-      if ((rc = flush(o))) break;
-      hipEvent_t ev = o == 1 ? aux->join : aux->fork;
-      hipError_t e = hipEventRecord(ev, str[o]);
-      if (e == hipSuccess) e = hipStreamWaitEvent(str[k], ev, 0);
-      if (e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: ordering a step behind the other stream"); break; }
-    }
-    if (cur.n > 1) {
-      // (validated above: a failure here is a launch failure; nothing of this run is pending afterwards)
-      if (carries) {
-        PrevTable prev{};
-        prev.n = rpend.n;
-        for (int z = 0; z < rpend.n; ++z) prev.slot[z] = PrevSlot{rpend.tab.slot[z].gf, rpend.tab.slot[z].gf_out, rpend.tab.slot[z].partials};
-        const int area = rpend.area ^ 1;
-        if (area == 1)
-          for (int z = 0; z < cur.n; ++z) tab.slot[z].partials = reinterpret_cast<float*>(static_cast<char*>(steps[i + z].workspace) + bw.agg_off);
-        rpend.has = false;  // (in this launch or, if it fails, nowhere: a launch failure)
-        rc = launch_block_narrow_carry(h, run_args, tab, cur.n, prev, str[k]);
-        if (rc == GNX_OK) { rpend.has = true; rpend.args = run_args; rpend.tab = tab; rpend.n = cur.n; rpend.area = area; rpend.stream = k; rpend.j = j; }
-      } else if (carry_kernel) {
-        rc = launch_block_narrow_run(h, run_args, tab, cur.n, str[k], false, GNX_PHASE_EDGE_NODE);
-        if (rc == GNX_OK) { rpend.has = true; rpend.args = run_args; rpend.tab = tab; rpend.n = cur.n; rpend.area = 0; rpend.stream = k; rpend.j = j; }
-      } else {
-        rc = launch_block_narrow_run(h, run_args, tab, cur.n, str[k], bf16);
-      }
-    } else {
-      gnx_pending_update next{};
-      rc = run(st, k, &next);
-      // (an argument error of step i: what is pending belongs to earlier steps, whose arguments were valid — finished below, then the error)
-      if (rc == GNX_OK) pend[k] = next;
-    }
-    if (rc != GNX_OK) break;
-    if (two) {
-      // (step[j & 3] was last recorded for run j - 4, and the wait on that record — run j - 1's — is already enqueued)
-      if (const hipError_t e = hipEventRecord(aux->step[j & 3], str[k]); e != hipSuccess) { rc = hip_fail(e, "gnx_block_forward_steps: step event"); break; }
-    }
-    recent[2] = recent[1]; recent[1] = recent[0]; recent[0] = cur;
-    rstream[2] = rstream[1]; rstream[1] = rstream[0]; rstream[0] = k;
-    i += cur.n;
+    const bool carry_kernel = planner.may_defer(cur) && block_narrow_carry_applies(h, a);
+    const long long pnd = planner.pend[0];
+    const bool aliases = pnd >= 0 && (steps[pnd].workspace == st.workspace || (p && p->og > 0 && steps[pnd].gf_out == st.gf_out));
+    const StepsPlan plan = planner.next(cur, carry_kernel, aliases);
+    int issued = 0;
+    while (issued < plan.n && (rc = issue(plan.op[issued])) == GNX_OK) ++issued;
+    planner.done(plan, cur, issued, took);
   }
-  // the last one-step runs' graph updates (one per stream), then the join — on every path, so that a capture never ends with the side stream
-  // un-joined and an error leaves everything issued so far complete when the caller's stream is
-  const int32_t rfr = flush_run();
-  const int32_t rf0 = flush(0), rf1 = two ? flush(1) : GNX_OK;
-  hipError_t e1 = hipSuccess, e2 = hipSuccess;
-  if (two) {
-    e1 = hipEventRecord(aux->join, str[1]);
-    e2 = hipStreamWaitEvent(str[0], aux->join, 0);
+  // what is still deferred or pending, then the join — on every path, so that a capture never ends with the side stream un-joined and an
+  // error leaves everything issued so far complete when the caller's stream is.  The first error is the call's.
+  const StepsPlan end = planner.close();
+  for (int z = 0; z < end.n; ++z) {
+    const int32_t erc = issue(end.op[z]);
+    rc = rc ? rc : erc;
   }
-  if (rc) return rc;
-  if (rfr) return rfr;
-  if (rf0) return rf0;
-  if (rf1) return rf1;
-  GNX_HIP(e1);
-  GNX_HIP(e2);
-  return GNX_OK;
+  return rc;
 }
 
 int32_t gnx_block_forward_steps(const gnx_graphs* h, const gnx_block_params* p, const gnx_block_step* steps, int64_t n_steps, int64_t R, uint32_t flags,

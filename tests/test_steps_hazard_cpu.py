@@ -1,6 +1,7 @@
 """The host-side hazard rule of gnx_block_forward_steps' two-stream schedule (graphnets.jl_amd/csrc/gnx_step_hazard.h), compiled on its
 own with g++: two steps may be in flight together only if no byte range one writes overlaps a range the other reads or writes; and the
-two-stream schedule built on it (step_order + the wait of step i for step i - 3), checked by simulating the order it enforces."""
+two-stream schedule of single steps built on it — the library's planner (StepsPlanner) at a run maximum of 1 — checked by simulating the
+order its operations enforce (tests/c/steps_plan_sim.h)."""
 import os
 import subprocess
 
@@ -72,116 +73,43 @@ def test_step_hazard_rule(tmp_path):
 
 
 SCHEDULE = r"""
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#include "gnx_step_hazard.h"
-using namespace gnx;
-// Simulation of gnx_block_forward_steps' two-stream schedule (gnx_forward.hip) as a happens-before relation: launches are nodes on two
-// streams (stream order), plus the waits the schedule adds.  An activity is a step's edge + node update (its launch) or its graph update
-// (chained into the launch two later on its stream, or a flush launch).  Every two activities of different steps whose buffers conflict
-// must be ordered, whatever the streams' relative progress.
-struct Node { int stream; std::vector<int> steps; };
-struct Sim {
-  std::vector<Node> nodes;
-  std::vector<std::vector<int>> deps;  // explicit edges into a node
-  int last[2] = {-1, -1};
-  int add(int stream, std::vector<int> steps, std::vector<int> extra) {
-    nodes.push_back({stream, steps});
-    if (last[stream] >= 0) extra.push_back(last[stream]);
-    deps.push_back(extra);
-    return last[stream] = (int)nodes.size() - 1;
-  }
-};
-static char mem[1 << 20];
-// a buffer set: seven 64-byte ranges at base
-static StepSpans spans_of(int in_set, int out_set, int ws_set) {
-  StepSpans s;
-  for (int t = 0; t < 3; ++t) s.rd[t] = byte_span(mem + in_set * 1024 + t * 64, 64);
-  for (int t = 0; t < 3; ++t) s.wr[t] = byte_span(mem + out_set * 1024 + 512 + t * 64, 64);
-  s.wr[3] = byte_span(mem + 200 * 1024 + ws_set * 64, 64);
-  return s;
-}
-// dims -> dims: the inputs of a step are the outputs of out_set
-static StepSpans spans_chain(int src_out_set, int out_set, int ws_set) {
-  StepSpans s = spans_of(0, out_set, ws_set);
-  for (int t = 0; t < 3; ++t) s.rd[t] = byte_span(mem + src_out_set * 1024 + 512 + t * 64, 64);
-  return s;
-}
-// returns the number of unordered conflicting pairs
-static int check(const std::vector<StepSpans>& sp, bool chain, bool wait3) {
-  const long long K = (long long)sp.size();
-  Sim sim;
-  int pend[2] = {-1, -1};
-  std::vector<int> launch(K, -1);
-  StepSpans recent[3];
-  for (long long i = 0; i < K; ++i) {
-    const int k = (int)(i & 1), o = k ^ 1;
-    const StepOrder ord = step_order(sp[i], recent, i);
-    if (ord.flush_own && pend[k] >= 0) { sim.add(k, {pend[k]}, {}); pend[k] = -1; }
-    std::vector<int> extra;
-    if (wait3 && i >= 3) extra.push_back(launch[i - 3]);
-    if (ord.after_other) {
-      if (pend[o] >= 0) { sim.add(o, {pend[o]}, {}); pend[o] = -1; }
-      if (sim.last[o] >= 0) extra.push_back(sim.last[o]);
-    }
-    std::vector<int> acts = {(int)i};
-    if (pend[k] >= 0) acts.push_back(pend[k]);  // the chained graph update of step i - 2 at the front of this launch
-    launch[i] = sim.add(k, acts, extra);
-    pend[k] = chain ? (int)i : -1;  // (not chained: the step's graph update is inside its own launch)
-    recent[2] = recent[1]; recent[1] = recent[0]; recent[0] = sp[i];
-  }
-  for (int k = 0; k < 2; ++k)
-    if (pend[k] >= 0) sim.add(k, {pend[k]}, {});
-  const int n = (int)sim.nodes.size();
-  std::vector<std::vector<char>> r(n, std::vector<char>(n, 0));  // r[a][b]: a ends before b starts
-  for (int b = 0; b < n; ++b)
-    for (int a : sim.deps[b]) {
-      r[a][b] = 1;
-      for (int x = 0; x < n; ++x) if (r[x][a]) r[x][b] = 1;
-    }
-  int bad = 0;
-  for (int a = 0; a < n; ++a)
-    for (int b = a; b < n; ++b) {
-      if (a != b && (r[a][b] || r[b][a])) continue;
-      for (int s : sim.nodes[a].steps)
-        for (int t : sim.nodes[b].steps)
-          if (s != t && steps_conflict(sp[s], sp[t])) ++bad;
-    }
-  return bad;
+#include "steps_plan_sim.h"
+using namespace sim;
+// The planner at a run maximum of 1, on two streams: every run is one step.  Returns the unordered conflicting pairs (by whole steps: nothing
+// is carried here) plus every way the plan is not the schedule of single steps.
+static int check1(const Loop& sp, bool chain, bool wait3) {
+  Config cf;
+  cf.run_max = 1;
+  cf.chain = chain;
+  cf.drop_wait3 = !wait3;
+  const Result r = check(sp, cf);
+  return r.unordered + r.unordered_steps + r.differs + r.in_run + r.multi + r.carried + r.flushed;
 }
 int main() {
   int fails = 0;
   for (int chain = 0; chain < 2; ++chain) {
     // rotating buffer sets: every count, every length
     for (int nsets = 1; nsets <= 9; ++nsets)
-      for (int K = 1; K <= 24; ++K) {
-        std::vector<StepSpans> sp;
-        for (int i = 0; i < K; ++i) sp.push_back(spans_of(i % nsets, i % nsets, i % nsets));
-        if (int b = check(sp, chain, true)) { std::printf("FAIL rotating nsets=%d K=%d chain=%d: %d\n", nsets, K, chain, b); ++fails; }
-      }
+      for (int K = 1; K <= 24; ++K)
+        if (int b = check1(rotation(K, nsets), chain, true)) { std::printf("FAIL rotating nsets=%d K=%d chain=%d: %d\n", nsets, K, chain, b); ++fails; }
     // one shared workspace; dims -> dims
     for (int K = 1; K <= 12; ++K) {
-      std::vector<StepSpans> a, b;
+      Loop a, b;
       for (int i = 0; i < K; ++i) { a.push_back(spans_of(i, i, 0)); b.push_back(spans_chain(i == 0 ? 99 : i - 1, i, i)); }
-      if (check(a, chain, true) || check(b, chain, true)) { std::printf("FAIL shared / chain K=%d\n", K); ++fails; }
+      if (check1(a, chain, true) || check1(b, chain, true)) { std::printf("FAIL shared / chain K=%d\n", K); ++fails; }
     }
     // random reuse of inputs, outputs and workspaces from small pools
     unsigned x = 12345u;
     auto rnd = [&](int m) { x = x * 1664525u + 1013904223u; return (int)((x >> 8) % (unsigned)m); };
     for (int trial = 0; trial < 3000; ++trial) {
       const int K = 1 + rnd(20), m = 1 + rnd(7);
-      std::vector<StepSpans> sp;
+      Loop sp;
       for (int i = 0; i < K; ++i) sp.push_back(rnd(4) == 0 && i > 0 ? spans_chain(rnd(m), rnd(m), rnd(m)) : spans_of(rnd(m), rnd(m), rnd(m)));
-      if (int b = check(sp, chain, true)) { std::printf("FAIL random trial %d chain=%d: %d\n", trial, chain, b); ++fails; break; }
+      if (int b = check1(sp, chain, true)) { std::printf("FAIL random trial %d chain=%d: %d\n", trial, chain, b); ++fails; break; }
     }
   }
-  // the checker sees the race the wait for step i - 3 prevents: five rotating sets without it
-  {
-    std::vector<StepSpans> sp;
-    for (int i = 0; i < 12; ++i) sp.push_back(spans_of(i % 5, i % 5, i % 5));
-    if (!check(sp, true, false)) { std::printf("FAIL: five rotating sets without the step i - 3 wait were not flagged\n"); ++fails; }
-  }
+  // the checker sees the race the wait for step i - 3 prevents: five rotating sets with that wait dropped from the plan
+  if (!check1(rotation(12, 5), true, false)) { std::printf("FAIL: five rotating sets without the step i - 3 wait were not flagged\n"); ++fails; }
   if (fails) return 1;
   std::printf("schedule ok\n");
   return 0;
@@ -194,7 +122,8 @@ def test_two_stream_schedule_orders_every_conflicting_pair(tmp_path):
     src.write_text(SCHEDULE)
     exe = tmp_path / "schedule"
     cxx = os.environ.get("CXX", "g++")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "graphnets.jl_amd", "csrc"), str(src), "-o", str(exe)])
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "graphnets.jl_amd", "csrc"), "-I", os.path.join(ROOT, "tests", "c"),
+                           str(src), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "schedule ok" in out.stdout
