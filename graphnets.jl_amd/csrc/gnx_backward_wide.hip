@@ -1,7 +1,10 @@
 // Matrix-core versions of the two heavy primitives of the backward pass (gnx_backward.hip) for wide feature widths:
 //   dX = delta * W^T        rows x J times J x K       -> k_rows_gemm (gnx_wide.hip) on a transposed copy of W
 //   dW = X^T * delta        K x J, reduced over ALL rows -> k_dw_gemm below: split over row chunks, fixed-order final sum
-// Both are exact fp32 (v_mfma_f32_32x32x2_f32) with a fixed summation order, like the forward.
+// Both evaluate every fp32 product, by default, as six bf16 matrix-core terms of an exact three-way split of both operands, split on the fly and
+// accumulated in fp32, small terms first (gnx_x6_mma.h: as accurate as the fp32 instruction; tests/test_gpu_bw_x6_stress.py holds every gradient
+// element to 1e-5 of its sum of absolute terms against float64).  The fp32 matrix instruction (v_mfma_f32_32x32x2_f32) runs instead where the
+// process-wide GNX_FFN_FP32 / GNX_EDGE_FP32 select it — the backward's entry points take no flags.  Either way the summation order is fixed.
 #include <algorithm>
 
 #include "gnx_launchers.h"

@@ -23,6 +23,9 @@ Two forms are provided, both float64:
   (ii) SPARSE form — the same mathematics on packed CSC data, arrays in the C-ABI layout `[R][T][D]`
        (byte-identical to Julia's column-major `(D, T, R)`).
 `tests/test_oracle.py` proves (i) == (ii) and checks both against the reference's fixtures.
+
+The SPARSE form also has the pullbacks of the block and the core (`block_backward_sparse`, `core_backward_sparse`), each gradient with an error
+scale; `tests/test_bw_x6_stress_cpu.py` proves them equal to torch float64 autograd of the forward's restatements.
 """
 from __future__ import annotations
 
@@ -588,6 +591,219 @@ def core_forward_sparse(p, csc, ef, nf, gf, return_scale=False, in_scale=None):
     if return_scale:
         return tuple(out), tuple(scales)
     return tuple(out)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Pullbacks (float64) with an error scale
+# ----------------------------------------------------------------------------------------------------------
+# The scale S of a gradient is THE SAME PULLBACK EVALUATED IN ABSOLUTE VALUES: a product contributes S_a · S_b, a sum the sum of its terms'
+# scales; S_v = |v| for a tensor handed to the call; for a value the call recomputes (LayerNorm outputs, a core's block outputs, hidden units,
+# a gelu pre-activation) S_v is the forward oracle's `return_scale`; act' taken from an output y contributes |act'| plus its first-order
+# sensitivity to y times S_y.  The pullback is linear in the cotangents and made of products and sums only, so values and scales run through
+# the same code (`_dense_pullback`, `_ln_pullback`), once on the signed operands and once on their scales.  Like the forward scale this is a
+# worst-case bound: `|got - ref| <= 1e-5 · S` elementwise is what an fp32 evaluation in any order keeps with room to spare.
+_GELU_C, _GELU_A = np.sqrt(2.0 / np.pi), 0.044715
+
+
+def _gelu_d1_d2(x):
+    """first and second derivative of NNlib.gelu (tanh form)"""
+    u, u1, u2 = _GELU_C * (x + _GELU_A * x ** 3), _GELU_C * (1.0 + 3.0 * _GELU_A * x ** 2), 6.0 * _GELU_C * _GELU_A * x
+    t = np.tanh(u)
+    s = 1.0 - t * t
+    return 0.5 * (1.0 + t) + 0.5 * x * s * u1, s * u1 + 0.5 * x * (s * u2 - 2.0 * t * s * u1 * u1)
+
+
+def act_grad(act, y, sy, z=None, sz=None):
+    """(act', its scale) as the backward takes it: from the activation's OUTPUT y (scale sy) for identity / relu / tanh / sigmoid, from the
+    pre-activation z (scale sz) for gelu.  Scale = |act'| + |d act' / d(y or z)| · s; relu's mask y > 0 has no first-order term (the callers keep
+    their inputs away from the kink)."""
+    if act == ACT_IDENTITY:
+        one = np.ones_like(y)
+        return one, one
+    if act == ACT_RELU:
+        m = (y > 0).astype(F64)
+        return m, m
+    if act == ACT_TANH:
+        d = 1.0 - y * y
+        return d, np.abs(d) + 2.0 * np.abs(y) * sy
+    if act == ACT_SIGMOID:
+        d = y * (1.0 - y)
+        return d, np.abs(d) + np.abs(1.0 - 2.0 * y) * sy
+    if act == ACT_GELU:
+        d1, d2 = _gelu_d1_d2(z)
+        return d1, np.abs(d1) + np.abs(d2) * sz
+    raise ValueError(f"unknown activation {act}")
+
+
+def _dense_pullback(X, SX, W, b, act, y, sy, g, sg):
+    """One Dense y = act(X Wᵀ + b) on rows: (δ, dW [in][out] — the ABI's layout —, db, dX) and the four scales.  X, y, g: (T, ·) float64."""
+    W = np.asarray(W, dtype=F64)
+    aW = np.abs(W)
+    z = sz = None
+    if act == ACT_GELU:
+        z, sz = X @ W.T + np.asarray(b, dtype=F64)[None, :], SX @ aW.T + np.abs(np.asarray(b, dtype=F64))[None, :]
+    a, sa = act_grad(act, y, sy, z, sz)
+    d, sd = g * a, sg * sa
+    return (d, X.T @ d, d.sum(axis=0), d @ W), (sd, SX.T @ sd, sd.sum(axis=0), sd @ aW)
+
+
+def _w0(a, T):
+    """`nothing` / a zero-width tensor as a (T, 0) array"""
+    return np.zeros((T, 0), dtype=F64) if a is None else np.asarray(a, dtype=F64)
+
+
+BLOCK_GRAD_NAMES = tuple(f"grad.{fn}.{k}" for fn in ("edgefn", "nodefn", "graphfn") for k in ("dW", "db"))
+
+
+def _block_pullback(p, csc, x, sx, y, sy, cot, scot):
+    """One replica.  x, y, cot and their scales: triples of (T, d) float64 arrays (zero width for `nothing`).  Returns
+    ((d_ef, d_nf, d_gf), {parameter gradient}), and the same pair of scales.  The edge level runs in row chunks."""
+    colptr, rowval, node_off, edge_off = csc
+    N, E, G = len(colptr) - 1, len(rowval), len(node_off) - 1
+    dst = np.repeat(np.arange(N), np.diff(colptr))
+    ng = np.repeat(np.arange(G), np.diff(node_off))
+    eg = np.repeat(np.arange(G), np.diff(edge_off))
+    de, dn, dg = p["in_dims"]
+    oe, on, og = p["out_dims"]
+    (ef, nf, gf), (sef, snf, sgf) = x, sx
+    (he, hn, hg), (she, shn, shg) = y, sy
+    cat = lambda parts: np.concatenate(parts, axis=1)
+    # graph level
+    Xg, SXg = cat([_segsum(he, eg, G), _segsum(hn, ng, G), gf]), cat([_segsum(she, eg, G), _segsum(shn, ng, G), sgf])
+    (_, dWg, dbg, dXg), (_, sWg, sbg, sXg) = _dense_pullback(Xg, SXg, p["Wg"], p["bg"], p["act_g"], hg, shg, cot[2], scot[2])
+    # node level
+    Xn, SXn = cat([_segsum(he, dst, N), nf, gf[ng]]), cat([_segsum(she, dst, N), snf, sgf[ng]])
+    gn_, sgn = cot[1] + dXg[ng][:, oe:oe + on], scot[1] + sXg[ng][:, oe:oe + on]
+    (_, dWn, dbn, dXn), (_, sWn, sbn, sXn) = _dense_pullback(Xn, SXn, p["Wn"], p["bn"], p["act_n"], hn, shn, gn_, sgn)
+    # edge level
+    Ke = de + 2 * dn + dg
+    acc = lambda: [np.zeros((E, de)), np.zeros((N, dn)), np.zeros((G, dg)), np.zeros((Ke, oe)), np.zeros(oe)]
+    v, s = acc(), acc()
+    for c0 in range(0, E, _CHUNK):
+        c1 = min(E, c0 + _CHUNK)
+        src_c, dst_c, eg_c = rowval[c0:c1], dst[c0:c1], eg[c0:c1]
+        Xe, SXe = cat([ef[c0:c1], nf[src_c], nf[dst_c], gf[eg_c]]), cat([sef[c0:c1], snf[src_c], snf[dst_c], sgf[eg_c]])
+        ge = cot[0][c0:c1] + dXg[eg_c][:, :oe] + dXn[dst_c][:, :oe]
+        sge = scot[0][c0:c1] + sXg[eg_c][:, :oe] + sXn[dst_c][:, :oe]
+        res = _dense_pullback(Xe, SXe, p["We"], p["be"], p["act_e"], he[c0:c1], she[c0:c1], ge, sge)
+        for o, (_, dW, db, dX) in zip((v, s), res):
+            o[0][c0:c1] = dX[:, :de]
+            o[1] += _segsum(dX[:, de:de + dn], src_c, N) + _segsum(dX[:, de + dn:de + 2 * dn], dst_c, N)
+            o[2] += _segsum(dX[:, de + 2 * dn:], eg_c, G)
+            o[3] += dW
+            o[4] += db
+    outs = []
+    for o, dXn_, dXg_, pw in ((v, dXn, dXg, (dWn, dbn, dWg, dbg)), (s, sXn, sXg, (sWn, sbn, sWg, sbg))):
+        d_nf = o[1] + dXn_[:, oe:oe + dn]
+        d_gf = o[2] + _segsum(dXn_[:, oe + dn:], ng, G) + dXg_[:, oe + on:]
+        outs.append(((o[0], d_nf, d_gf), dict(zip(BLOCK_GRAD_NAMES, (o[3], o[4], *pw)))))
+    return outs[0], outs[1]
+
+
+def _pack_dx(per_replica, widths):
+    return tuple(None if d == 0 else np.stack([q[k] for q in per_replica]) for k, d in enumerate(widths))
+
+
+def block_backward_sparse(p, csc, x, y, cot, return_scale=True):
+    """Pullback of block_forward_sparse as gnx_block_backward defines it: x = (ef, nf, gf) the forward inputs, y = (ef', nf', gf') the forward
+    OUTPUTS AS GIVEN (at the ABI they are inputs: Xn and Xg are built from them and act' of tanh / sigmoid / relu is taken from them; a gelu
+    level recomputes its pre-activation), cot the three cotangents; all packed [R][T][d], `None` for `nothing` / a zero width.  Returns the nine
+    gradients {d_ef, d_nf, d_gf: [R][T][d] | None; grad.<fn>.dW: [in][out]; grad.<fn>.db} — parameter gradients summed over the replicas — and,
+    with `return_scale`, the dict of their scales (see above; every input is handed to the call, so S_v = |v| throughout)."""
+    rows = (len(csc[1]), len(csc[0]) - 1, len(csc[2]) - 1)
+    R = next(a.shape[0] for a in (*x, *y, *cot) if a is not None)
+    dxs, sdxs, grads, sgrads = [], [], None, None
+    for r in range(R):
+        tr = lambda trip: tuple(_w0(None if a is None else a[r], T) for a, T in zip(trip, rows))
+        xr, yr, cr = tr(x), tr(y), tr(cot)
+        ab = lambda trip: tuple(np.abs(a) for a in trip)
+        (dx, gr), (sdx, sgr) = _block_pullback(p, csc, xr, ab(xr), yr, ab(yr), cr, ab(cr))
+        dxs.append(dx); sdxs.append(sdx)
+        grads = gr if grads is None else {k: grads[k] + gr[k] for k in gr}
+        sgrads = sgr if sgrads is None else {k: sgrads[k] + sgr[k] for k in sgr}
+    val = dict(zip(("d_ef", "d_nf", "d_gf"), _pack_dx(dxs, p["in_dims"])), **grads)
+    if not return_scale:
+        return val
+    return val, dict(zip(("d_ef", "d_nf", "d_gf"), _pack_dx(sdxs, p["in_dims"])), **sgrads)
+
+
+def _ln_pullback(x, sx, gamma, eps, eps_mode, g, sg):
+    """Pullback of layernorm(x) = γ x̂ + β over the last axis: (dx, dγ, dβ) and their scales.  With dx̂ = g γ and r = den / σ (eps_mode 0) or 1
+    (eps_mode 1): dx = (dx̂ - mean(dx̂) - x̂ · mean(dx̂ x̂) · r) / den.  Scales: the same expression with every term's absolute value added,
+    and layernorm_scale(γ = 1, β = 0) for the recomputed x̂."""
+    gamma = np.asarray(gamma, dtype=F64)
+    mu = x.mean(axis=-1, keepdims=True)
+    xc = x - mu
+    var = (xc ** 2).mean(axis=-1, keepdims=True)
+    den = (np.sqrt(var) + eps) if eps_mode == 0 else np.sqrt(var + eps)
+    r = den / np.sqrt(var) if eps_mode == 0 else 1.0
+    xhat = xc / den
+    sxhat = layernorm_scale(x, sx, np.ones_like(gamma), np.zeros_like(gamma), eps, eps_mode).astype(F64)
+    dxh, sdxh = g * gamma, sg * np.abs(gamma)
+    dx = (dxh - dxh.mean(axis=-1, keepdims=True) - xhat * (dxh * xhat).mean(axis=-1, keepdims=True) * r) / den
+    sdx = (sdxh + sdxh.mean(axis=-1, keepdims=True) + sxhat * (sdxh * sxhat).mean(axis=-1, keepdims=True) * r) / den
+    flat = lambda a: a.reshape(-1, a.shape[-1])
+    return (dx, flat(g * xhat).sum(axis=0), flat(g).sum(axis=0)), (sdx, flat(sg * sxhat).sum(axis=0), flat(sg).sum(axis=0))
+
+
+def core_backward_sparse(p, csc, x, cot, return_scale=True, hidden_act=None):
+    """Pullback of core_forward_sparse, y = x + block(gn1(x)) + ffwd(gn2(x)), as gnx_core_backward defines it: x and cot are the three packed
+    [R][T][d] inputs and cotangents; everything else is recomputed.  `hidden_act`: the FeedForwards' hidden activation (default p["hidden_act"],
+    else relu as in the forward oracle); tanh takes act' from the recomputed hidden units, gelu from the recomputed pre-activation.  Returns the
+    33 gradients {d_ef, d_nf, d_gf, grad.<fn>.dW/db (block), grad.ln1_<t>/ln2_<t>.gamma/beta, grad.ff_<t>.fc1/fc2.dW/db} and their scales."""
+    act = p.get("hidden_act", ACT_RELU) if hidden_act is None else hidden_act
+    xs = [np.asarray(v, dtype=F64) for v in x]
+    gs = [np.asarray(v, dtype=F64) for v in cot]
+    sxs, sgs = [np.abs(v) for v in xs], [np.abs(v) for v in gs]
+    eps, em = p["eps"], p["eps_mode"]
+    R = xs[0].shape[0]
+    val, sc = {}, {}
+    dx, sdx = [g.copy() for g in gs], [s.copy() for s in sgs]  # the residual
+    # FeedForward and gn2
+    for i, t in enumerate("eng"):
+        g2, b2 = p[f"ln2_{t}_gamma"], p[f"ln2_{t}_beta"]
+        d = xs[i].shape[-1]
+        l2 = layernorm(xs[i], g2, b2, eps, em, axis=-1).reshape(-1, d)
+        sl2 = layernorm_scale(xs[i], sxs[i], g2, b2, eps, em).astype(F64).reshape(-1, d)
+        W1, b1, W2, b2_ = p[f"ff_{t}_W1"], p[f"ff_{t}_b1"], p[f"ff_{t}_W2"], p[f"ff_{t}_b2"]
+        g, sg = gs[i].reshape(-1, d), sgs[i].reshape(-1, d)
+        dl2, sdl2 = np.empty_like(l2), np.empty_like(l2)
+        tot = None
+        for c0 in range(0, l2.shape[0], _CHUNK):
+            c1 = min(l2.shape[0], c0 + _CHUNK)
+            h = _dense_rows(W1, b1, act, l2[c0:c1])
+            sh = sl2[c0:c1] @ np.abs(np.asarray(W1, dtype=F64)).T + np.abs(np.asarray(b1, dtype=F64))[None, :]
+            one = np.ones_like(g[c0:c1])
+            (dh_, dW2, db2, dh), (sdh_, sW2, sb2, sdh) = _dense_pullback(h, sh, W2, b2_, ACT_IDENTITY, one, one, g[c0:c1], sg[c0:c1])
+            (_, dW1, db1, dl2[c0:c1]), (_, sW1, sb1, sdl2[c0:c1]) = _dense_pullback(l2[c0:c1], sl2[c0:c1], W1, b1, act, h, sh, dh, sdh)
+            part = [dW1, db1, dW2, db2, sW1, sb1, sW2, sb2]
+            tot = part if tot is None else [a + b for a, b in zip(tot, part)]
+        for k, n in enumerate(("fc1.dW", "fc1.db", "fc2.dW", "fc2.db")):
+            val[f"grad.ff_{t}.{n}"], sc[f"grad.ff_{t}.{n}"] = tot[k], tot[4 + k]
+        (d2, dgam, dbet), (sd2, sgam, sbet) = _ln_pullback(xs[i], sxs[i], g2, eps, em, dl2.reshape(xs[i].shape), sdl2.reshape(xs[i].shape))
+        dx[i] += d2; sdx[i] += sd2
+        val[f"grad.ln2_{t}.gamma"], val[f"grad.ln2_{t}.beta"], sc[f"grad.ln2_{t}.gamma"], sc[f"grad.ln2_{t}.beta"] = dgam, dbet, sgam, sbet
+    # block and gn1
+    l1 = [layernorm(xs[i], p[f"ln1_{t}_gamma"], p[f"ln1_{t}_beta"], eps, em, axis=-1) for i, t in enumerate("eng")]
+    sl1 = [layernorm_scale(xs[i], sxs[i], p[f"ln1_{t}_gamma"], p[f"ln1_{t}_beta"], eps, em).astype(F64) for i, t in enumerate("eng")]
+    yb, syb = block_forward_sparse(p["block"], csc, *l1, return_scale=True, in_scale=tuple(sl1))
+    dl1, sdl1, grads, sgrads = [], [], None, None
+    for r in range(R):
+        pick = lambda trip: tuple(np.asarray(a[r], dtype=F64) for a in trip)
+        (d1, gr), (sd1, sgr) = _block_pullback(p["block"], csc, pick(l1), pick(sl1), pick(yb), pick(syb), pick(gs), pick(sgs))
+        dl1.append(d1); sdl1.append(sd1)
+        grads = gr if grads is None else {k: grads[k] + gr[k] for k in gr}
+        sgrads = sgr if sgrads is None else {k: sgrads[k] + sgr[k] for k in sgr}
+    val.update(grads); sc.update(sgrads)
+    for i, t in enumerate("eng"):
+        g1 = np.stack([q[i] for q in dl1])
+        sg1 = np.stack([q[i] for q in sdl1])
+        (d1, dgam, dbet), (sd1, sgam, sbet) = _ln_pullback(xs[i], sxs[i], p[f"ln1_{t}_gamma"], eps, em, g1, sg1)
+        dx[i] += d1; sdx[i] += sd1
+        val[f"grad.ln1_{t}.gamma"], val[f"grad.ln1_{t}.beta"], sc[f"grad.ln1_{t}.gamma"], sc[f"grad.ln1_{t}.beta"] = dgam, dbet, sgam, sbet
+    for n, d_, s_ in zip(("d_ef", "d_nf", "d_gf"), dx, sdx):
+        val[n], sc[n] = d_, s_
+    return (val, sc) if return_scale else val
 
 
 def make_chain_block_params(rng, in_dims, edge_widths, node_widths, graph_widths, acts=(ACT_RELU, ACT_TANH, ACT_IDENTITY)):
