@@ -898,10 +898,16 @@ class GNBlock:
 
     `narrow_chain` (also a plain attribute): a block whose update functions are Chains runs its forward through gnx_chain_block_forward_narrow —
     each update function whose input and layer widths are at most 32 in one kernel (a row per lane through all layers), the others as before.
-    Off (the default): gnx_chain_block_forward.  The pullback (gnx_chain_block_backward) recomputes its activations and does not change."""
+    Off (the default): gnx_chain_block_forward.  The pullback (gnx_chain_block_backward) recomputes its activations and does not change.
+
+    `narrow_chain_backward` (also a plain attribute; independent of `narrow_chain`): the pullback of such a block is
+    gnx_chain_block_backward_narrow — each update function inside its rule (include/gnx.h: the forward's rule and 64 KB of LDS for two
+    waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled back in one kernel, a row per lane forward
+    and back through all layers, with only what crosses levels recomputed into the workspace; the others as before.  The gradients are within
+    the generic pullback's error of the exact ones, not its bits.  Off (the default): gnx_chain_block_backward."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
-                 narrow_backward=False, narrow_chain=False):
+                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -917,6 +923,7 @@ class GNBlock:
         self.fused_backward = bool(fused_backward)
         self.narrow_backward = bool(narrow_backward)
         self.narrow_chain = bool(narrow_chain)
+        self.narrow_chain_backward = bool(narrow_chain_backward)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1203,7 +1210,8 @@ def _block_pullback(ctx, gouts, elem):
 
 class _ChainBlockFn(torch.autograd.Function):
     """autograd node of a GNBlock whose update functions are Chains: forward = gnx_chain_block_forward, backward =
-    gnx_chain_block_backward (which recomputes every layer's output from the inputs)."""
+    gnx_chain_block_backward (which recomputes every layer's output from the inputs), or gnx_chain_block_backward_narrow with the block's
+    `narrow_chain_backward` switch."""
 
     @staticmethod
     def forward(ctx, block, g, R, flags, ef, nf, gf, *params):
@@ -1244,13 +1252,14 @@ class _ChainBlockFn(torch.autograd.Function):
             arrays.append((_lib.DenseGrad * max(len(entries), 1))(*entries))
         grads = _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays])
         with torch.cuda.device(dev):
-            nb = lib.gnx_chain_block_backward_workspace_bytes(g._h, C.byref(p), R)
+            query, entry = ((lib.gnx_chain_block_backward_narrow_workspace_bytes, lib.gnx_chain_block_backward_narrow)
+                            if getattr(block, "narrow_chain_backward", False) else (lib.gnx_chain_block_backward_workspace_bytes, lib.gnx_chain_block_backward))
+            nb = query(g._h, C.byref(p), R)
             if nb == 0:
                 raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
             ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-            check(lib.gnx_chain_block_backward(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R,
-                                               _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
-                                               torch.cuda.current_stream(dev).cuda_stream))
+            check(entry(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R,
+                        _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
         out = [None, None, None, None, d_ef, d_nf, d_gf]
         for w, b in zip(gW, gb):
             out += [None if w is None else (w if w.dim() == 1 else w.t()), b]  # (out, in) view with column-major storage, like the weights; a LayerNorm's gamma as it is

@@ -17,6 +17,7 @@
 #include "gnx_wave_kernel.h"  // ld_feat / st_feat: a bf16 or fp32 element of a feature buffer
 #include "gnx_bw_edge_wave_kernel.h"  // BwEdgeWave
 #include "gnx_feat4.h"        // ld_bf16x4, ld_feat4 / st_feat4: four of them
+#include "gnx_chain_mlp.h"    // gelu_grad_pre / act_grad_bw: the derivative formulas k_chain_mlp_bw shares
 
 namespace gnx {
 
@@ -32,15 +33,8 @@ __device__ __forceinline__ float ld_elem(const bf16_t* p) { return bf16_lo(*p); 
 // delta[m][j] = (G[m][j] + extra1[i1(m)][o1 + j] + extra2[i2(m)][o2 + j]) * act'(out[m][j]);  one thread per element.
 // kind 0: rows = graphs (no extras); 1: rows = nodes (extra1 = dXg rows by graph); 2: rows = edges (extra1 = dXg by graph,
 // extra2 = dXn by destination node).
-// d/dz of NNlib.gelu's tanh form 0.5 z (1 + tanh(c (z + 0.044715 z^3))): unlike relu / tanh / sigmoid it is not a function of the
-// OUTPUT (gelu is not monotonic), so for a gelu level the pre-activation z = W x + b is recomputed into the delta buffer first
-// (k_fw_dense) and DeltaArgs::out points at it: act code 4 here means "out holds z".
-__device__ __forceinline__ float gelu_grad_pre(float z) {
-  const float c = 0.7978845608028654f, k = 0.044715f;
-  const float t = tanhf(c * (z + k * z * z * z));
-  return 0.5f * (1.f + t) + 0.5f * z * (1.f - t * t) * c * (1.f + 3.f * k * z * z);
-}
-__device__ __forceinline__ float act_grad_bw(float v, int act) { return act == 4 ? gelu_grad_pre(v) : act_grad_from_out(v, act); }
+// (gelu_grad_pre / act_grad_bw: gnx_chain_mlp.h; a gelu level's pre-activation z = W x + b is recomputed into the delta buffer first
+// (k_fw_dense) and DeltaArgs::out points at it: act code 4 here means "out holds z")
 
 struct DeltaArgs {
   const float* G; const float* out; float* delta;
@@ -1350,20 +1344,44 @@ gnx_block_params chain_edge_block(const gnx_chain_block_params* p) {  // the one
   return b;
 }
 struct ChainBwLayout {
-  size_t act[3][kChainMaxLayers + 1];  // stored layer outputs per chain
-  size_t Xn, Xg, dXn, dXg, gbuf[3], blk_fw, blk_fw_bytes, blk_bw, blk_bw_bytes, part, wt, off2, ident, total;
+  size_t act[3][kChainMaxLayers + 1];  // stored layer outputs per chain (a fused chain: its last layer's, where a level above reads it)
+  size_t Xn, Xg, dXn, dXg, gbuf[3], blk_fw, blk_fw_bytes, blk_bw, blk_bw_bytes, part, wt, off2, ident, dxe, total;
 };
-ChainBwLayout chain_bw_layout(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, size_t ident_floats) {
+// the functions gnx_chain_block_backward_narrow pulls back in one kernel each (bit 0 edge, 1 node, 2 graph: chain_bw_narrow_takes)
+unsigned chain_bw_narrow_mask(const gnx_graphs* h, const gnx_chain_block_params* p) {
+  const int oe = chain_out(p->edgefn), on = chain_out(p->nodefn);
+  unsigned m = 0;
+  if (chain_bw_narrow_takes(p->edgefn, p->de + 2 * p->dn + p->dg, (size_t)h->E)) m |= 1;
+  if (chain_bw_narrow_takes(p->nodefn, oe + p->dn + p->dg, (size_t)h->N)) m |= 2;
+  if (chain_bw_narrow_takes(p->graphfn, oe + on + p->dg, (size_t)h->G)) m |= 4;
+  return m;
+}
+// A generic graph function behind a fused node function: nf' is recomputed by the generic launches (Xn and every layer's output kept), so that the
+// graph function's input — and with it its parameter gradients — keeps gnx_chain_block_backward's bits.
+bool chain_bw_node_fw_generic(unsigned fused, int og) { return (fused & 2) && og > 0 && !(fused & 4); }
+// fused: the mask above — a fused function keeps no per-layer outputs, no delta buffers and (the edge function) no inner block workspaces; it
+// adds its partial rows and (the edge function) the compact [R E][2 dn + dg] input gradient.  fused = 0: the layout of gnx_chain_block_backward
+ChainBwLayout chain_bw_layout(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, size_t ident_floats, unsigned fused = 0) {
   ChainBwLayout L{};
   size_t o = 0;
   auto take = [&](size_t floats) { const size_t at = o; o += align_up(floats * sizeof(float), 256); return at; };
   const gnx_chain* ch[3] = {&p->edgefn, &p->nodefn, &p->graphfn};
   const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
+  const size_t trows[3] = {(size_t)h->E, (size_t)h->N, (size_t)h->G};
   const int oe = chain_out(p->edgefn), on = chain_out(p->nodefn), og = chain_out(p->graphfn);
   const int Kn = oe + p->dn + p->dg, Kg = oe + on + p->dg;
   const int k0[3] = {p->de + 2 * p->dn + p->dg, Kn, Kg};
   size_t gmax = 1, pmax = 2048 * 4, wmax = 1;
   for (int t = 0; t < 3; ++t) {
+    if (fused & (1u << t)) {
+      const bool crosses = t == 0 ? on > 0 || og > 0 : t == 1 && og > 0;  // ef' feeds the node / graph inputs, nf' the graph input
+      if (t == 1 && chain_bw_node_fw_generic(fused, og)) {
+        for (int i = 0; i < ch[t]->n_layers; ++i) L.act[t][i] = take(rows[t] * (size_t)ch[t]->widths[i]);
+      } else if (crosses) L.act[t][ch[t]->n_layers - 1] = take(rows[t] * (size_t)chain_out(*ch[t]));
+      const ChainBwNarrowShape sh = chain_bw_narrow_shape(*ch[t], k0[t], trows[t]);
+      pmax = std::max(pmax, (size_t)sh.P * sh.nwg * (size_t)R);
+      continue;
+    }
     for (int i = 0; i < ch[t]->n_layers; ++i) {
       L.act[t][i] = take(rows[t] * (size_t)ch[t]->widths[i]);
       const int J = ch[t]->widths[i], K = i > 0 ? ch[t]->widths[i - 1] : k0[t];
@@ -1374,39 +1392,81 @@ ChainBwLayout chain_bw_layout(const gnx_graphs* h, const gnx_chain_block_params*
     gmax = std::max(gmax, rows[t] * (size_t)chain_max(*ch[t]));
   }
   pmax = std::max(pmax, std::max((size_t)R * h->G * 256, (size_t)2048) * (size_t)std::max({p->dg, oe, 1}));  // column-sum slices
-  L.Xn = take(on > 0 ? rows[1] * Kn : 0); L.dXn = take(on > 0 ? rows[1] * Kn : 0);
+  L.Xn = take(on > 0 && (!(fused & 2) || chain_bw_node_fw_generic(fused, og)) ? rows[1] * Kn : 0); L.dXn = take(on > 0 ? rows[1] * Kn : 0);
   L.Xg = take(og > 0 ? rows[2] * Kg : 0); L.dXg = take(og > 0 ? rows[2] * Kg : 0);
-  for (int i = 0; i < 3; ++i) L.gbuf[i] = take(gmax);
-  const gnx_block_params b = chain_edge_block(p);
-  L.blk_fw_bytes = gnx_block_workspace_bytes(h, &b, R);
-  L.blk_fw = o; o += align_up(L.blk_fw_bytes, 256);
-  L.blk_bw_bytes = gnx_block_backward_workspace_bytes(h, &b, R);
-  L.blk_bw = o; o += align_up(L.blk_bw_bytes, 256);
+  const bool all_fused = (oe == 0 || (fused & 1)) && (on == 0 || (fused & 2)) && (og == 0 || (fused & 4)) && fused != 0;
+  for (int i = 0; i < 3; ++i) L.gbuf[i] = take(all_fused ? 0 : gmax);
+  if (!(fused & 1)) {
+    const gnx_block_params b = chain_edge_block(p);
+    L.blk_fw_bytes = gnx_block_workspace_bytes(h, &b, R);
+    L.blk_fw = o; o += align_up(L.blk_fw_bytes, 256);
+    L.blk_bw_bytes = gnx_block_backward_workspace_bytes(h, &b, R);
+    L.blk_bw = o; o += align_up(L.blk_bw_bytes, 256);
+  }
   L.part = take(pmax); L.wt = take(wmax); L.off2 = take(16);
   L.ident = take(ident_floats);  // the identity layer of a LayerNorm-first edge function (gnx_internal.h: ChainLnFirst)
+  L.dxe = take((fused & 1) ? rows[0] * (size_t)(2 * p->dn + p->dg) : 0);
   L.total = o + 256;
   return L;
 }
-}  // namespace
 
-extern "C" {
-
-size_t gnx_chain_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R) {
-  if (!h || !p0 || R <= 0 || gnx_chain_block_workspace_bytes(h, p0, R) == 0) return 0;  // (the forward's query validates the chains)
-  ChainLnFirst lnf;
-  const gnx_chain_block_params* p = lnf.init(p0, nullptr);
-  return chain_bw_layout(h, p, R, lnf.ident_floats()).total;
+// the parameter-gradient finish of a fused function: one k_bw_dw_final per layer over the kernel's partial rows (a LayerNorm as J = width, K = 1)
+int32_t chain_bw_narrow_finals(const gnx_chain& c, int k_in, const ChainBwNarrowShape& sh, int64_t R, const float* part, const gnx_dense_grad* grads, hipStream_t s) {
+  ProfScope ps("bw_dw_generic", s);
+  const size_t nwg = sh.nwg * (size_t)R;
+  int kin = k_in;
+  for (int i = 0; i < c.n_layers; ++i) {
+    const bool ln = chain_layer_is_ln(c.layers[i]);
+    const int J = c.widths[i], K = ln ? 1 : kin;
+    const gnx_dense_grad g = grads ? grads[i] : gnx_dense_grad{nullptr, nullptr};
+    if (g.weight || g.bias) GNX_LAUNCH(k_bw_dw_final, dim3((unsigned)(J * (K + 1))), dim3(256), 0, s, part + (size_t)sh.part_off[i] * nwg, (int)nwg, J, K, g.weight, g.bias);
+    kin = J;
+  }
+  GNX_HIP(hipGetLastError());
+  return GNX_OK;
+}
+bool chain_wants_grads(const gnx_chain& c, const gnx_dense_grad* grads) {
+  for (int i = 0; grads && i < c.n_layers; ++i)
+    if (grads[i].weight || grads[i].bias) return true;
+  return false;
 }
 
-int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_params* p0, const float* ef, const float* nf, const float* gf,
-                                 const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
-                                 float* d_gf, const gnx_chain_block_grads* grads0, void* ws, size_t ws_bytes, void* stream) {
+// validated params (check_params of gnx_chain.cpp), replicas and an edge output: what both queries and `_applies` need before a layout exists
+bool chain_bw_valid(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R) { return h && p0 && chain_check_params(h, p0, R) == GNX_OK; }
+}  // namespace
+
+namespace {
+// gnx_chain_block_backward (narrow = false) and gnx_chain_block_backward_narrow: one body.  `fused` is chain_bw_narrow_mask for the latter and 0
+// for the former — with 0 every line below is the generic call.
+size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, bool narrow) {
+  if (!narrow) {
+    if (!h || !p0 || R <= 0 || gnx_chain_block_workspace_bytes(h, p0, R) == 0) return 0;  // (the forward's query validates the chains)
+  } else if (!chain_bw_valid(h, p0, R)) return 0;
+  const unsigned fused = narrow ? chain_bw_narrow_mask(h, p0) : 0;
+  if (narrow) {  // a level that stays generic reads the tables the generic query builds through the forward's query: build them here as well
+    const bool generic_level = (chain_out(p0->edgefn) > 0 && !(fused & 1)) || (chain_out(p0->nodefn) > 0 && !(fused & 2)) || (chain_out(p0->graphfn) > 0 && !(fused & 4));
+    if (generic_level && gnx_chain_block_workspace_bytes(h, p0, R) == 0) return 0;
+  }
+  if (fused) {  // what the fused levels read of the handle, built here, outside any capture
+    (void)gnx_ensure_wide_tables(h);
+    (void)gnx_ensure_csr(h);
+  }
+  ChainLnFirst lnf;
+  const gnx_chain_block_params* p = (fused & 1) ? p0 : lnf.init(p0, nullptr);  // (a fused edge function has its input row in registers: no identity layer)
+  return chain_bw_layout(h, p, R, lnf.ident_floats(), fused).total;
+}
+
+int32_t chain_backward(const gnx_graphs* h, const gnx_chain_block_params* p0, const float* ef, const float* nf, const float* gf,
+                       const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
+                       float* d_gf, const gnx_chain_block_grads* grads0, void* ws, size_t ws_bytes, void* stream, bool narrow) {
   hipStream_t s = (hipStream_t)stream;
   if (!h || !p0) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  if (gnx_chain_block_workspace_bytes(h, p0, R) == 0) return GNX_ERR_DIMS;  // gnx_last_error() holds the reason
-  ChainLnFirst lnf;  // a LayerNorm as the edge function's first layer: behind an identity Dense (its gradient slot is empty)
-  const gnx_chain_block_params* p = lnf.init(p0, nullptr);
-  const gnx_chain_block_grads* grads = lnf.init_grads(grads0);
+  if (!narrow) { if (gnx_chain_block_workspace_bytes(h, p0, R) == 0) return GNX_ERR_DIMS; }  // gnx_last_error() holds the reason
+  else if (chain_check_params(h, p0, R) != GNX_OK) return GNX_ERR_DIMS;
+  const unsigned fused = narrow ? chain_bw_narrow_mask(h, p0) : 0;
+  ChainLnFirst lnf;  // a LayerNorm as the (generic) edge function's first layer: behind an identity Dense (its gradient slot is empty)
+  const gnx_chain_block_params* p = (fused & 1) ? p0 : lnf.init(p0, nullptr);
+  const gnx_chain_block_grads* grads = (fused & 1) ? grads0 : lnf.init_grads(grads0);
   bool chain_wide = p->de > 32 || p->dn > 32 || p->dg > 32;
   for (const gnx_chain* c : {&p->edgefn, &p->nodefn, &p->graphfn})
     for (int i = 0; i < c->n_layers; ++i) chain_wide = chain_wide || (c->widths && c->widths[i] > 32);
@@ -1416,9 +1476,11 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
   const int oe = chain_out(p->edgefn), on = chain_out(p->nodefn), og = chain_out(p->graphfn);
   if ((de > 0 && !ef && h->E > 0) || (dn > 0 && !nf) || (dg > 0 && !gf)) return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL");
   if (oe == 0) return fail(GNX_ERR_DIMS, "chain backward: not implemented for an edge function without output (the forward takes it; train such a block with one-layer update functions)");
-  const ChainBwLayout L = chain_bw_layout(h, p, R, lnf.ident_floats());
-  if (int32_t rcc = check_ws(ws, ws_bytes, L.total, "workspace missing or smaller than gnx_chain_block_backward_workspace_bytes()")) return rcc;
+  const ChainBwLayout L = chain_bw_layout(h, p, R, lnf.ident_floats(), fused);
+  if (int32_t rcc = check_ws(ws, ws_bytes, L.total, narrow ? "workspace missing or smaller than gnx_chain_block_backward_narrow_workspace_bytes()"
+                                                            : "workspace missing or smaller than gnx_chain_block_backward_workspace_bytes()")) return rcc;
   if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
+  if (fused & 1) { if (int32_t rcs = gnx_ensure_csr(h)) return rcs; }  // (k_bw_dnf's out-edge view; the query built it)
   char* base = static_cast<char*>(ws);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   if (lnf.on) {
@@ -1440,24 +1502,39 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
   };
   auto A = [&](int t, int i) { return F(L.act[t][i]); };
   const gnx_block_params b1 = chain_edge_block(p);
+  const gnx_dense_grad* gfn[3] = {grads ? grads->edgefn : nullptr, grads ? grads->nodefn : nullptr, grads ? grads->graphfn : nullptr};
+  const int k0[3] = {de + 2 * dn + dg, Kn, Kg};
+  // the pullback of a fused function: one kernel (under `name`), then one finisher per layer whose gradient is wanted
+  auto fused_level = [&](int t, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2, ChainBwNarrowIo io, const char* name) -> int32_t {
+    const bool want = chain_wants_grads(*ch[t], gfn[t]);
+    io.part = want ? part : nullptr;
+    { ProfScope ps(name, s);
+      if (int32_t r2 = launch_chain_bw_narrow(h, t, *ch[t], in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
+    return want ? chain_bw_narrow_finals(*ch[t], k0[t], chain_bw_narrow_shape(*ch[t], k0[t], (size_t)trow[t]), R, part, gfn[t], s) : GNX_OK;
+  };
   int32_t rc;
 
-  // ---- forward again, every layer's output kept (gnx_chain_block_forward's sequence) ----
-  if (E > 0) {
+  // ---- forward again: a generic function keeps every layer's output (gnx_chain_block_forward's sequence); a fused one only its last layer's,
+  //      and only where a level above reads it ----
+  if (fused & 1) {
+    if ((on > 0 || og > 0) && (rc = launch_chain_narrow(h, 0, *ch[0], ef, de, nf, dn, gf, dg, A(0, ch[0]->n_layers - 1), R, s, "bw_chain_fw_e"))) return rc;
+  } else if (E > 0) {
     if ((rc = gnx_block_forward(h, &b1, ef, nf, gf, R, A(0, 0), nullptr, nullptr, base + L.blk_fw, L.blk_fw_bytes, 0, stream))) return rc;
     for (int i = 1; i < ch[0]->n_layers; ++i)
       if ((rc = launch_chain_layer(h, 0, ch[0]->layers[i], A(0, i - 1), ch[0]->widths[i - 1], ch[0]->widths[i], A(0, i), R, s, "bw_chain_fw_e"))) return rc;
   }
   const float* ef_out = A(0, ch[0]->n_layers - 1);
   const float* nf_out = on > 0 ? A(1, ch[1]->n_layers - 1) : nullptr;
-  if (on > 0) {
+  if ((fused & 2) && !chain_bw_node_fw_generic(fused, og)) {
+    if (og > 0 && (rc = launch_chain_narrow(h, 1, *ch[1], ef_out, oe, nf, dn, gf, dg, A(1, ch[1]->n_layers - 1), R, s, "bw_chain_fw_n"))) return rc;
+  } else if (on > 0) {
     if ((rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s))) return rc;
     for (int i = 0; i < ch[1]->n_layers; ++i)
       if ((rc = launch_chain_layer(h, 1, ch[1]->layers[i], i ? A(1, i - 1) : Xn, i ? ch[1]->widths[i - 1] : Kn, ch[1]->widths[i], A(1, i), R, s, "bw_chain_fw_n"))) return rc;
   }
   if (og > 0) {
     if ((rc = launch_fn_input(h, 2, ef_out, oe, nf_out, on, gf, dg, R, Xg, s))) return rc;
-    for (int i = 0; i < ch[2]->n_layers; ++i)
+    for (int i = 0; i < ch[2]->n_layers && !(fused & 4); ++i)
       if ((rc = launch_chain_layer(h, 2, ch[2]->layers[i], i ? A(2, i - 1) : Xg, i ? ch[2]->widths[i - 1] : Kg, ch[2]->widths[i], A(2, i), R, s, "bw_chain_fw_g"))) return rc;
   }
 
@@ -1540,16 +1617,42 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
   };
 
   // ---- graph chain ----
-  if (og > 0) {
+  if (fused & 4) {
+    if ((rc = fused_level(2, Xg, Kg, nullptr, 0, nullptr, 0, ChainBwNarrowIo{g_gf_out, nullptr, 0, 0, nullptr, 0, dXg, 0, nullptr, nullptr}, "bw_delta"))) return rc;
+  } else if (og > 0) {
     last_delta(2, g_gf_out, gb[0], Xg, Kg, -1);
     if ((rc = pull_layers(2, 0, gb[0], gb[1], Xg, Kg, dXg, nullptr))) return rc;
   }
   // ---- node chain: upstream + dXg[graph of the node][oe : oe+on] ----
-  if (on > 0) {
+  if (fused & 2) {
+    if ((rc = fused_level(1, ef_out, oe, nf, dn, gf, dg, ChainBwNarrowIo{g_nf_out, og > 0 ? dXg : nullptr, Kg, oe, nullptr, 0, dXn, 0, nullptr, nullptr}, "bw_delta"))) return rc;
+  } else if (on > 0) {
     last_delta(1, g_nf_out, gb[0], Xn, Kn, -1);
     if ((rc = pull_layers(1, 0, gb[0], gb[1], Xn, Kn, dXn, nullptr))) return rc;
   }
-  // ---- edge chain: upstream + dXg[graph][0:oe] + dXn[dst][0:oe]; tail layers row-wise, the first layer through the block pullback ----
+  // ---- edge chain: upstream + dXg[graph][0:oe] + dXn[dst][0:oe] ----
+  if (fused & 1) {
+    // one kernel: d_ef directly, the node / graph columns of the input gradient into dXe_c [R E][2 dn + dg]; then k_bw_dnf and the per-graph
+    // column sums, exactly as after the fused edge level of block_backward_t
+    const bool need_cols = (d_nf && dn > 0) || (d_gf && dg > 0);
+    float* dXe = F(L.dxe);
+    const int ldc = 2 * dn + dg;
+    if ((rc = fused_level(0, ef, de, nf, dn, gf, dg, ChainBwNarrowIo{g_ef_out, og > 0 ? dXg : nullptr, Kg, 0, on > 0 ? dXn : nullptr, Kn, need_cols ? dXe : nullptr, de,
+                                                                      d_ef && de > 0 ? d_ef : nullptr, nullptr}, "bw_delta_edge"))) return rc;
+    if (d_nf && dn > 0) {
+      ProfScope ps("bw_dnf", s);
+      GNX_LAUNCH(k_bw_dnf<false>, dim3(blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr, h->d_csr_ptr,
+                 h->d_csr_eid, N, E, dn, d_nf);
+    }
+    if (d_gf && dg > 0) {
+      ProfScope ps("bw_dgf", s);
+      int64_t me = 1;
+      for (int64_t g = 0; g < h->G; ++g) me = std::max(me, h->h_edge_off[g + 1] - h->h_edge_off[g]);
+      GNX_LAUNCH(k_bw_dgf_init, blocks((size_t)R * G * dg), dim3(256), 0, s, (const float*)nullptr, Kg, oe + on, (int)(R * G), dg, d_gf);
+      colsum_graphs(dXe, false, dg, ldc, 2 * dn, E, h->d_edge_off, me, G, Ru, part, d_gf, dg, 0, 1, s);
+    }
+  } else {
+  // tail layers row-wise, the first layer through the block pullback
   float* g_first = gb[0];  // gradient w.r.t. the FIRST layer's output
   if (E > 0) {
     if (ch[0]->n_layers == 1) {
@@ -1566,6 +1669,7 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
   g1.edgefn = grad_of(0, 0);
   if ((rc = gnx_block_backward(h, &b1, ef, nf, gf, A(0, 0), nullptr, nullptr, E > 0 ? g_first : nullptr, nullptr, nullptr, R, d_ef, d_nf, d_gf, &g1,
                                base + L.blk_bw, L.blk_bw_bytes, stream))) return rc;
+  }
   // ---- the node / graph functions' own shares of d_nf, d_gf ----
   if (d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, Kn, oe, rows[1], dn, d_nf, 1, s))) return rc;
   if (d_gf && dg > 0) {
@@ -1578,6 +1682,31 @@ int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_para
   }
   GNX_HIP(hipGetLastError());
   return GNX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gnx_chain_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_bw_query(h, p, R, false); }
+
+int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                 const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
+                                 float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  return chain_backward(h, p, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, false);
+}
+
+// gnx_chain_block_backward_narrow: every update function inside the rule (chain_bw_narrow_takes) pulled back in one kernel
+int32_t gnx_chain_block_backward_narrow_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return chain_bw_valid(h, p, R) && chain_out(p->edgefn) > 0 ? (int32_t)chain_bw_narrow_mask(h, p) : 0;
+}
+
+size_t gnx_chain_block_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_bw_query(h, p, R, true); }
+
+int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                        const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
+                                        float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  return chain_backward(h, p, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, true);
 }
 
 }  // extern "C"

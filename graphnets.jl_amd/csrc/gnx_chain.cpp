@@ -251,6 +251,10 @@ int32_t chain_forward(const gnx_graphs* h, const gnx_chain_block_params* p0, con
 
 }  // namespace
 
+namespace gnx {
+int32_t chain_check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return check_params(h, p, R); }
+}  // namespace gnx
+
 extern "C" {
 
 size_t gnx_chain_block_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_workspace_bytes(h, p, R, false); }

@@ -17,99 +17,21 @@
 // pays 4 x 1 groups, not the 32-wide tile of the matrix-core GEMM.  Every group is a basic block of its own, so the scheduler cannot hoist the
 // weight reads of a whole layer into registers (the hazard the sched_barriers of core_post_lds_body fence).
 // Feature and output pointers may be 4-byte aligned only: every global access is one dword.  Offsets are size_t.
-#include "gnx_launchers.h"
-#include "gnx_wave_kernel.h"  // act_row
+#include "gnx_chain_mlp.h"  // the argument record, the parameter staging and the input row: shared with k_chain_mlp_bw (its chain_layer_fw is the loop below)
 
 namespace gnx {
-
-enum : int { SRC_EDGE = 0, SRC_NODE = 1, SRC_ROWS = 2 };
-
-struct ChainMlpLayer {
-  const float* w;  // Dense: weight (out x in, column-major) / LayerNorm: gamma
-  const float* b;  // Dense: bias or nullptr / LayerNorm: beta
-  int width;       // output width
-  int op;          // 0..4: Dense with activation GNX_ACT_*; 5 / 6: LayerNorm with 1 / (sigma + eps) / 1 / sqrt(sigma^2 + eps)
-};
-
-struct ChainMlpArgs {
-  ChainMlpLayer layer[kChainMaxLayers];
-  int n_layers, K;       // K: width of the function's input row
-  const float *a0, *a1, *a2;  // EDGE: ef, nf, gf / NODE: ef', nf, gf / ROWS: the input rows, -, -
-  int d0, d1, d2;        // their widths (EDGE: de, dn, dg; NODE: oe, dn, dg)
-  int N, E, G;
-  const int *colptr, *rowval, *edge_dst, *seg_off;  // seg_off: edge_off (EDGE) / node_off (NODE), [G + 1]
-  float* out; int ow;    // [R][rows][ow]
-  size_t rows;           // rows of the entity per replica
-};
-
-__host__ __device__ constexpr int ceil4(int x) { return (x + 3) & ~3; }
-
-// cur[at .. at + w) = p[0 .. w): one dword load per element behind a uniform test
-template <int WMAX>
-__device__ __forceinline__ void chain_load_seg(const float* __restrict__ p, int at, int w, float (&cur)[WMAX]) {
-#pragma unroll
-  for (int k = 0; k < WMAX; ++k)
-    if (k >= at && k < at + w) cur[k] = p[k - at];
-}
 
 template <int WMAX, int SRC>
 __global__ __launch_bounds__(256) void k_chain_mlp(ChainMlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s_par[];
-  {  // stage the parameters, zero-padded
-    int off = 0, kin = a.K;
-    for (int l = 0; l < a.n_layers; ++l) {
-      const ChainMlpLayer L = a.layer[l];
-      const int OP = ceil4(L.width);
-      if (L.op < 5) {
-        const int n = ceil4(kin) * OP;
-        for (int i = threadIdx.x; i < n; i += 256) {
-          const int k = i / OP, j = i - k * OP;
-          s_par[off + i] = (k < kin && j < L.width) ? L.w[(size_t)k * L.width + j] : 0.f;
-        }
-        for (int j = threadIdx.x; j < OP; j += 256) s_par[off + n + j] = (j < L.width && L.b) ? L.b[j] : 0.f;
-        off += n + OP;
-      } else {
-        for (int j = threadIdx.x; j < OP; j += 256) {
-          s_par[off + j] = j < L.width ? L.w[j] : 0.f;
-          s_par[off + OP + j] = j < L.width ? L.b[j] : 0.f;
-        }
-        off += 2 * OP;
-      }
-      kin = L.width;
-    }
-  }
+  chain_stage_params(a, s_par, 256);
   __syncthreads();
   const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= a.rows) return;
   const size_t r = blockIdx.y;
 
   float cur[WMAX];
-#pragma unroll
-  for (int k = 0; k < WMAX; ++k) cur[k] = 0.f;
-  if constexpr (SRC == SRC_EDGE) {
-    const int e = (int)row;
-    if (a.d0 > 0) chain_load_seg<WMAX>(a.a0 + (r * (size_t)a.E + e) * a.d0, 0, a.d0, cur);
-    if (a.d1 > 0) {
-      chain_load_seg<WMAX>(a.a1 + (r * (size_t)a.N + a.rowval[e]) * a.d1, a.d0, a.d1, cur);
-      chain_load_seg<WMAX>(a.a1 + (r * (size_t)a.N + a.edge_dst[e]) * a.d1, a.d0 + a.d1, a.d1, cur);
-    }
-    if (a.d2 > 0) chain_load_seg<WMAX>(a.a2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, e)) * a.d2, a.d0 + 2 * a.d1, a.d2, cur);
-  } else if constexpr (SRC == SRC_NODE) {
-    const int n = (int)row;
-    if (a.d0 > 0) {
-      const int e1 = a.colptr[n + 1];
-      for (int e = a.colptr[n]; e < e1; ++e) {
-        const float* __restrict__ p = a.a0 + (r * (size_t)a.E + e) * a.d0;
-#pragma unroll
-        for (int k = 0; k < WMAX; ++k)
-          if (k < a.d0) cur[k] += p[k];
-      }
-    }
-    if (a.d1 > 0) chain_load_seg<WMAX>(a.a1 + (r * (size_t)a.N + n) * a.d1, a.d0, a.d1, cur);
-    if (a.d2 > 0) chain_load_seg<WMAX>(a.a2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, n)) * a.d2, a.d0 + a.d1, a.d2, cur);
-  } else {
-    chain_load_seg<WMAX>(a.a0 + (r * a.rows + row) * (size_t)a.K, 0, a.K, cur);
-  }
+  chain_input_row<WMAX, SRC>(a, row, r, cur);
 
   int off = 0, kin = a.K;
 #pragma unroll 1
@@ -215,19 +137,13 @@ int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c,
   const size_t rows = entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G);
   if (!chain_narrow_takes(c, K, rows)) return fail(GNX_ERR_INVALID_ARG, "launch_chain_narrow: the function is outside the fused rule");
   if (entity == 0) { if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw; }  // (the destination of every edge)
-  int wmax = K, kin = K;
+  int kin = K;
   for (int i = 0; i < c.n_layers; ++i) {
-    const gnx_dense& l = c.layers[i];
-    if (!chain_layer_is_ln(l) && c.widths[i] > 0 && kin > 0 && !l.weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
-    a.layer[i] = ChainMlpLayer{l.weight, l.bias, c.widths[i], chain_layer_is_ln(l) ? 5 + chain_layer_ln_mode(l) : l.act};
-    wmax = wmax > c.widths[i] ? wmax : c.widths[i];
+    if (!chain_layer_is_ln(c.layers[i]) && c.widths[i] > 0 && kin > 0 && !c.layers[i].weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
     kin = c.widths[i];
   }
-  a.n_layers = c.n_layers; a.K = K;
-  a.a0 = in0; a.a1 = in1; a.a2 = in2; a.d0 = d0; a.d1 = d1; a.d2 = d2;
-  a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G;
-  a.colptr = h->d_colptr; a.rowval = h->d_rowval; a.edge_dst = h->d_edge_dst; a.seg_off = entity == 0 ? h->d_edge_off : h->d_node_off;
-  a.out = out; a.ow = c.widths[c.n_layers - 1]; a.rows = rows;
+  const int wmax = chain_mlp_fill(h, entity, c, in0, d0, in1, d1, in2, d2, a);
+  a.out = out; a.ow = c.widths[c.n_layers - 1];
   const dim3 grid((unsigned)((rows + 255) / 256), (unsigned)R);
   const size_t lds = sizeof(float) * chain_narrow_lds_floats(c, K);
   ProfScope ps(name, s);

@@ -185,6 +185,31 @@ bool chain_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows);
 int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                             float* out, int64_t R, hipStream_t s, const char* name);
 
+// ---- gnx_chain_bw_narrow.hip: the pullback of one update function of a Chain block in one kernel (gnx_chain_block_backward_narrow) ----
+// the kernel's LDS plan for a function: the staged parameters, then per wave 64 tape rows of `ld` floats (the input row, every layer's output but
+// the last, the parked deltas) and P accumulators (one per parameter)
+struct ChainBwNarrowShape {
+  int ld, P, par_floats, waves, dslot;  // waves: per workgroup, as many as fit 64 KB of LDS, at most 4 — the rule takes a function from 2 on
+  int par_off[kChainMaxLayers], part_off[kChainMaxLayers], tape_out[kChainMaxLayers];  // per layer: staged parameters / accumulators / output slot
+  size_t nwg;                           // workgroups (= partial rows per layer) per replica: a wave takes 64 rows
+};
+ChainBwNarrowShape chain_bw_narrow_shape(const gnx_chain& c, int k_in, size_t rows);
+// the rule of gnx_chain_block_backward_narrow for one function (include/gnx.h states it): chain_narrow_takes and two waves' LDS within 64 KB
+bool chain_bw_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows);
+struct ChainBwNarrowIo {
+  const float* G;                           // upstream gradient of the function's output, or nullptr
+  const float* ex1; int ex1_stride, ex1_off;  // dXg [R G][ex1_stride], columns from ex1_off (node / edge level), or nullptr
+  const float* ex2; int ex2_stride;           // dXn [R N][ex2_stride], columns from 0 (edge level), or nullptr
+  float* dx; int dx_c0;                     // columns [dx_c0, K) of the input gradient, rows of length K - dx_c0, or nullptr
+  float* direct;                            // columns [0, dx_c0), rows of length dx_c0 (d_ef), or nullptr
+  float* part;                              // [sum_l P_l][R nwg] partial rows (layer l at part + part_off[l] * R * nwg), or nullptr
+};
+// entity / in0..in2 as launch_chain_narrow.  The caller asked chain_bw_narrow_takes and opens the ProfScope.
+int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
+                               const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
+// gnx_chain.cpp: the validation of a Chain block's parameters and replicas (reads the handle's counts only)
+int32_t chain_check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R);
+
 // ---- gnx_forward.hip: the validation of a core forward, for the training-mode entries of gnx_dropout.hip (a FormScope of the call's flags open) ----
 int32_t core_forward_check_dims(const gnx_core_params* p);  // (needs no handle)
 int32_t core_forward_check(const gnx_graphs* h, const gnx_core_params* p, int64_t R, const void* ef, const void* nf, const void* gf, const void* ef_out,

@@ -550,6 +550,36 @@ GNX_API int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_bl
                                  const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
                                  float* d_nf, float* d_gf, const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes,
                                  void* stream);
+/* The same pullback with each update function in ONE kernel where its widths are narrow (k_chain_mlp_bw, csrc/gnx_chain_bw_narrow.hip): a lane
+ * builds its row's input as the fused forward does, runs it forward through all layers, forms the last layer's delta (upstream + the shares of
+ * the levels above) and walks back through the layers in registers.  The lane's input row and every layer's output but the last wait on a tape
+ * in LDS; a gelu pre-activation and a LayerNorm's statistics are recomputed from it.  Parameter gradients are summed per workgroup in a fixed
+ * order (no atomics) and finished by one small launch per layer; results are bitwise reproducible and independent of the workspace's contents.
+ * The rule is per update function.  With k_in the function's input width and w_i its layer widths (i = 0 .. n - 1), a function is fused when
+ *   - gnx_chain_block_forward_narrow's rule takes it (>= 1 layer, w_{n-1} > 0, k_in and every w_i <= 32, staged parameters
+ *     par = sum_i (Dense: ceil4(k_i) * ceil4(w_i) + ceil4(w_i); LayerNorm: 2 * ceil4(w_i)) <= 10240 floats, k_0 = k_in, k_i = w_{i-1}; rows), and
+ *   - par + 2 * (64 * ld + P) <= 16384 floats (64 KB of LDS for a workgroup of two waves), where
+ *       ld = (k_in + sum_{i < n-1} w_i + max_i (Dense: w_i; LayerNorm: 2 * w_i)) | 1     the tape row of a lane (odd),
+ *       P  = sum_i (Dense: w_i * (k_i + 1); LayerNorm: 2 * w_i)                          one accumulator per parameter.
+ * One wave's tape and accumulators fit 64 KB for every function with all widths <= 16 and <= 8 layers and with all widths <= 32 and <= 3
+ * layers, and the kernel runs them; but that one-wave class IS CUT from the rule: measured on the 1M-edge shapes its member (edge [32,32,3] at
+ * k_in 23) took 1.34 / 1.75 times the generic pullback's time (profiles/chain_bw_narrow.json).  What stays — e.g. [16,3] at k_in 20,
+ * [16,ln,16,3] at k_in 23, [32,4] at k_in 11, eight 8-wide layers — met the bar at all three register widths and source forms.
+ * A function the forward fuses and this rule does not is a legitimate mixed case.
+ * _applies: bit 0 the edge, bit 1 the node, bit 2 the graph function is fused; 0 on bad arguments (and for an edge function without output,
+ * which the call refuses).  _workspace_bytes: a fused function keeps no per-layer outputs, no delta buffers and (the edge function) no inner
+ * block workspaces — only what crosses levels (ef', nf', the graph input rows, dXn, dXg), the node / graph columns of the edge rows' input
+ * gradient [R E][2 dn + dg] and the partial rows (a fused node function in front of a graph function outside the rule keeps its per-layer
+ * outputs: nf' is then recomputed by the generic launches, so that the graph function's parameter gradients keep their bits); it builds the handle's tables the call reads, so call it outside a stream capture (the call
+ * itself works inside one).  A function outside the rule runs exactly gnx_chain_block_backward's launches for it; with a mask of 0 the call
+ * IS gnx_chain_block_backward (same workspace size, same bits).  Arguments, optional outputs and refusals (in their order) as
+ * gnx_chain_block_backward; every buffer may be 4-byte aligned only. */
+GNX_API int32_t gnx_chain_block_backward_narrow_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API size_t gnx_chain_block_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                        const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
+                                        float* d_nf, float* d_gf, const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes,
+                                        void* stream);
 
 /* Backward of (m::GNCore)(x) = x + block(gn1(x)) + ffwd(gn2(x)) (src/gncore.jl:56-68).  Takes the forward's INPUTS and the
  * upstream gradients; the intermediates (both LayerNorms, the block's outputs, the FeedForward hidden activations) are

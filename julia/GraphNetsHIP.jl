@@ -24,7 +24,7 @@ module GraphNetsHIP
 export GNGraphBatch, batch, unbatch, getedgefninput, getnodefninput, getgraphfninput, GNBlock, zerodim2nothing, GNCore, GNCoreList,
        efview, nfview, gfview, flatunpaddednf, flatunpaddedef, collapsef, unpaddedcollapsedef, flatunpaddedcollapsedef
 # ... plus what the drop-in adds: layers as plain structs, pullbacks, the library-side hipGraph model, the multi-GPU split
-export Dense, LayerNorm, ChainBlock, chain_forward, chain_narrow_applies, chain_pullback, block_pullback, core_pullback, Model, partition_graphs, DistBlock
+export Dense, LayerNorm, ChainBlock, chain_forward, chain_narrow_applies, chain_pullback, chain_backward, chain_backward_narrow_applies, block_pullback, core_pullback, Model, partition_graphs, DistBlock
 # ... and device residency: `x |> batch |> gpu`, `model |> gpu`, `y |> cpu` (what Flux's `gpu` / `cpu` are to the reference)
 export DeviceArray, gpu, cpu, synchronize, chained, flush, steps
 
@@ -873,7 +873,9 @@ end
 (m::ChainBlock)(x) = back(chain_device(gpu(m), gpu(x)), x)
 chain_forward(m::ChainBlock, x; narrow::Bool=false) = back(chain_device(gpu(m), gpu(x); narrow=narrow), x)
 # pullback: gradients w.r.t. the inputs and every layer's (weight, bias); the forward is recomputed inside the library
-function chain_pullback_device(m::ChainBlock, x, ȳ)
+# narrow = true: gnx_chain_block_backward_narrow — every update function inside its rule (include/gnx.h) is pulled back in one kernel, the others as
+# before; a workspace key of its own
+function chain_pullback_device(m::ChainBlock, x, ȳ; narrow::Bool=false)
     g::GNGraphBatch = x.graphs
     R = replicas(x.ef, x.nf, x.gf)
     keep = Any[]
@@ -885,19 +887,32 @@ function chain_pullback_device(m::ChainBlock, x, ȳ)
     arrs = [[GnxDenseGrad(devptr(gW[t][i]), devptr(gB[t][i])) for i in eachindex(chains[t])] for t in 1:3]
     gp(t) = isempty(arrs[t]) ? Ptr{GnxDenseGrad}(C_NULL) : pointer(arrs[t])
     grads = Ref(GnxChainBlockGrads(gp(1), gp(2), gp(3)))
-    ws = workspace!(g, (:chain_backward, chainkey(m), R)) do
-        ccall((:gnx_chain_block_backward_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R)
+    ws = workspace!(g, (narrow ? :chain_backward_narrow : :chain_backward, chainkey(m), R)) do
+        narrow ? ccall((:gnx_chain_block_backward_narrow_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R) :
+                 ccall((:gnx_chain_block_backward_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R)
     end
-    GC.@preserve m keep x ȳ dins gW gB arrs ws check(ccall((:gnx_chain_block_backward, libgnx), Int32,
+    GC.@preserve m keep x ȳ dins gW gB arrs ws check(narrow ? ccall((:gnx_chain_block_backward_narrow, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64,
+         Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{GnxChainBlockGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
+        devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]) :
+      ccall((:gnx_chain_block_backward, libgnx), Int32,
         (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64,
          Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{GnxChainBlockGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
         g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
         devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]))
     (ef=dins[1], nf=dins[2], gf=dins[3], params=[[(weight=gW[t][i], bias=gB[t][i]) for i in eachindex(chains[t])] for t in 1:3])
 end
-function chain_pullback(m::ChainBlock, x, ȳ)
-    r = chain_pullback_device(gpu(m), gpu(x), gpu(ȳ))
+function chain_backward(m::ChainBlock, x, ȳ; narrow::Bool=false)
+    r = chain_pullback_device(gpu(m), gpu(x), gpu(ȳ); narrow=narrow)
     ondevice(x) ? r : (ef=cpu(r.ef), nf=cpu(r.nf), gf=cpu(r.gf), params=[[map(cpu, q) for q in c] for c in r.params])
+end
+chain_pullback(m::ChainBlock, x, ȳ) = chain_backward(m, x, ȳ)
+# which update functions gnx_chain_block_backward_narrow pulls back in one kernel on this batch: bit 0 edge, bit 1 node, bit 2 graph
+function chain_backward_narrow_applies(m::ChainBlock, x)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    GC.@preserve m keep ccall((:gnx_chain_block_backward_narrow_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
 end
 
 # ---- a chain of layers as ONE hipGraph inside libgnx (gnx_model_*): decoder(core(encoder(x))) of examples/sort/sort.jl:68-75.
