@@ -24,8 +24,9 @@ Two forms are provided, both float64:
        (byte-identical to Julia's column-major `(D, T, R)`).
 `tests/test_oracle.py` proves (i) == (ii) and checks both against the reference's fixtures.
 
-The SPARSE form also has the pullbacks of the block and the core (`block_backward_sparse`, `core_backward_sparse`), each gradient with an error
-scale; `tests/test_bw_x6_stress_cpu.py` proves them equal to torch float64 autograd of the forward's restatements.
+The SPARSE form also has the pullbacks of the block, the core and the block with Chain update functions (`block_backward_sparse`,
+`core_backward_sparse`, `chain_block_backward_sparse`), each gradient with an error scale; `tests/test_bw_x6_stress_cpu.py` and
+`tests/test_chain_bw_stress_cpu.py` prove them equal to torch float64 autograd of the forward's restatements.
 """
 from __future__ import annotations
 
@@ -806,25 +807,38 @@ def core_backward_sparse(p, csc, x, cot, return_scale=True, hidden_act=None):
     return (val, sc) if return_scale else val
 
 
-def make_chain_block_params(rng, in_dims, edge_widths, node_widths, graph_widths, acts=(ACT_RELU, ACT_TANH, ACT_IDENTITY)):
+LN_TOKENS = {"ln": "layernorm", "ln_sqrt": "layernorm_sqrt_eps"}  # width token -> marker string of the layer tuple
+LN_SQRT_EPS = LN_TOKENS["ln_sqrt"]
+CHAIN_LN_EPS = 1e-5  # Flux's default, the only value the ABI has for a Chain's LayerNorm
+
+
+def ln_eps_mode(marker):
+    """eps mode of a chain's LayerNorm layer tuple (marker, gamma, beta): 0 = (x - mean) / (sigma + eps), 1 = / sqrt(sigma^2 + eps)"""
+    assert marker in LN_TOKENS.values(), marker
+    return 1 if marker == LN_SQRT_EPS else 0
+
+
+def make_chain_block_params(rng, in_dims, edge_widths, node_widths, graph_widths, acts=(ACT_RELU, ACT_TANH, ACT_IDENTITY), last_acts=None):
     """GNBlock whose update functions are Chains of Dense layers (gnblock.jl:1-6 allows any Chain; the default is one Dense):
     `*_widths` = output widths of the layers of each chain (empty = that output is `nothing`); hidden layers use `acts[i % 3]`,
-    the last layer of a chain is linear (like the reference's default).  A width entry "ln" puts a Flux `LayerNorm(d)` layer value
-    there (d = the width in front of it; random gamma / beta): the layer tuple is ("layernorm", gamma, beta)."""
+    the last layer of a chain is linear (like the reference's default) unless `last_acts` = (edge, node, graph) names its activation.
+    A width entry "ln" puts a Flux `LayerNorm(d)` layer value there (d = the width in front of it; random gamma / beta): the layer tuple is
+    ("layernorm", gamma, beta); the entry "ln_sqrt" the same in the sqrt-eps mode, / sqrt(sigma^2 + eps): ("layernorm_sqrt_eps", gamma, beta).
+    Neither `last_acts` nor the mode draws anything: every seed gives the numbers it gave without them."""
     de, dn, dg = in_dims
     # (a LayerNorm keeps the width in front of it; a chain of LayerNorms alone keeps its input's)
-    last = lambda ws, k: next((w for w in reversed(ws) if w != "ln"), k if ws else 0)
+    last = lambda ws, k: next((w for w in reversed(ws) if not isinstance(w, str)), k if ws else 0)
     oe = last(edge_widths, de + 2 * dn + dg)
     on = last(node_widths, oe + dn + dg)
     kin = dict(edge=de + 2 * dn + dg, node=oe + dn + dg, graph=oe + on + dg)
     p = dict(in_dims=tuple(in_dims))
-    for name, widths in (("edge", edge_widths), ("node", node_widths), ("graph", graph_widths)):
+    for t, (name, widths) in enumerate((("edge", edge_widths), ("node", node_widths), ("graph", graph_widths))):
         layers, k = [], kin[name]
         for i, w in enumerate(widths):
-            if w == "ln":
-                layers.append(("layernorm", rng.uniform(0.5, 1.5, size=k).astype(np.float32), rng.uniform(-0.2, 0.2, size=k).astype(np.float32)))
+            if isinstance(w, str):
+                layers.append((LN_TOKENS[w], rng.uniform(0.5, 1.5, size=k).astype(np.float32), rng.uniform(-0.2, 0.2, size=k).astype(np.float32)))
                 continue
-            act = acts[i % len(acts)] if i + 1 < len(widths) else ACT_IDENTITY
+            act = acts[i % len(acts)] if i + 1 < len(widths) else (ACT_IDENTITY if last_acts is None else last_acts[t])
             layers.append((glorot_uniform(rng, w, k), rng.uniform(-0.1, 0.1, size=w).astype(np.float32), act))
             k = w
         p[name] = layers
@@ -845,8 +859,8 @@ def chain_block_forward_sparse(p, csc, ef, nf, gf, return_scale=False):
     def run(layers, X, S):
         for W, b, act in layers:
             if isinstance(W, str):  # ("layernorm", gamma, beta): a Flux LayerNorm(d) layer value between the Dense layers (gnblock.jl:1-6 admits any Chain)
-                S = layernorm_scale(X, S, b, act)
-                X = layernorm(X, b, act, axis=-1)
+                S = layernorm_scale(X, S, b, act, CHAIN_LN_EPS, ln_eps_mode(W))
+                X = layernorm(X, b, act, CHAIN_LN_EPS, ln_eps_mode(W), axis=-1)
                 continue
             S = np.abs(S) @ np.abs(np.asarray(W, dtype=F64)).T + np.abs(np.asarray(b, dtype=F64))[None, :]
             X = _dense_rows(W, b, act, X)
@@ -889,6 +903,186 @@ def chain_block_forward_sparse(p, csc, ef, nf, gf, return_scale=False):
             lst.append(v)
     pack = lambda ls: tuple(None if (lst[0] is None or lst[0].shape[1] == 0) else np.stack(lst) for lst in ls)
     return (pack(outs), pack(scales)) if return_scale else pack(outs)
+
+
+def _act_prime_z(act, z):
+    """|d act / dz| at the pre-activation z"""
+    if act == ACT_IDENTITY:
+        return np.ones_like(z)
+    if act == ACT_RELU:
+        return (z > 0).astype(F64)
+    if act == ACT_TANH:
+        return 1.0 - np.tanh(z) ** 2
+    if act == ACT_SIGMOID:
+        y = apply_act(z, act)
+        return y * (1.0 - y)
+    return np.abs(_gelu_d1_d2(z)[0])
+
+
+def _chain_tape(layers, X, S, first_order=False):
+    """chain_block_forward_sparse's `run`, keeping every layer's input and output with their scales: [(X, SX, y, Sy, Sn)], and the chain's output.
+    Sy is the forward's own scale (a Dense: SX |W|^T + |b|, the scale of its pre-activation z, for any activation).  `first_order`: the scale
+    handed to the NEXT layer is |y| + |act'(z)| (Sz - |z|) instead — the output's own rounding plus the first-order share of its
+    pre-activation's error —, which is what Sz is for the identity and never more than Sz + |y| - |act' z|."""
+    tape = []
+    for W, b, act in layers:
+        if isinstance(W, str):
+            Sy = layernorm_scale(X, S, b, act, CHAIN_LN_EPS, ln_eps_mode(W)).astype(F64)
+            y = layernorm(X, b, act, CHAIN_LN_EPS, ln_eps_mode(W), axis=-1)
+            Sn = Sy
+        else:
+            Sy = np.abs(S) @ np.abs(np.asarray(W, dtype=F64)).T + np.abs(np.asarray(b, dtype=F64))[None, :]
+            y = _dense_rows(W, b, act, X)
+            Sn = Sy
+            if first_order and act != ACT_IDENTITY:
+                z = X @ np.asarray(W, dtype=F64).T + np.asarray(b, dtype=F64)[None, :]
+                Sn = np.abs(y) + _act_prime_z(act, z) * (Sy - np.abs(z))
+        tape.append((X, S, y, Sy, Sn))
+        X, S = y, Sn
+    return tape, X, S
+
+
+def _prod1(a, sa, b, sb):
+    """first-order scale of a product: |a b| (its own rounding) + |a| (Sb - |b|) + (Sa - |a|) |b|"""
+    return np.abs(a) * sb + (sa - np.abs(a)) * np.abs(b)
+
+
+def _dense_pullback1(X, SX, W, b, act, y, sy, sz, g, sg):
+    """`_dense_pullback` with FIRST-ORDER scales: every product a . b contributes |a| Sb + Sa |b| - |a b| instead of Sa . Sb (the term dropped,
+    (Sa - |a|)(Sb - |b|), is second order: 1e-5 of it is below 1e-5 . 1e-5 . Sa . Sb).  In a pullback through L layers and three levels the
+    product rule multiplies the factors S / |value| of every recomputed operand — each about the number of terms of the sum behind it — and on
+    a batch with sums over thousands of edges reaches 1e27 times the value; the first-order rule adds them.  sy: the scale of the layer's
+    OUTPUT (first-order: |y| + |act'| (Sz - |z|)), sz: of its pre-activation."""
+    W = np.asarray(W, dtype=F64)
+    aW = np.abs(W)
+    z = X @ W.T + np.asarray(b, dtype=F64)[None, :] if act == ACT_GELU else None
+    a, sa = act_grad(act, y, sy, z, sz)
+    d, sd = g * a, _prod1(g, sg, a, sa)
+    sdW = np.abs(X).T @ sd + (SX - np.abs(X)).T @ np.abs(d)
+    return (d, X.T @ d, d.sum(axis=0), d @ W), (sd, sdW, sd.sum(axis=0), sd @ aW)
+
+
+def _ln_pullback1(x, sx, gamma, eps, eps_mode, g, sg):
+    """`_ln_pullback` with first-order scales (see `_dense_pullback1`): with u = dxh - mean(dxh) - xhat c r, c = mean(dxh xhat), dx = u / den;
+    the deviation's error is layernorm_scale's q (relative q / den on 1 / den)."""
+    gamma = np.asarray(gamma, dtype=F64)
+    mu = x.mean(axis=-1, keepdims=True)
+    xc = x - mu
+    var = (xc ** 2).mean(axis=-1, keepdims=True)
+    den = (np.sqrt(var) + eps) if eps_mode == 0 else np.sqrt(var + eps)
+    r = den / np.sqrt(var) if eps_mode == 0 else 1.0
+    xhat = xc / den
+    sxhat = layernorm_scale(x, sx, np.ones_like(gamma), np.zeros_like(gamma), eps, eps_mode).astype(F64)
+    sc = sx + sx.mean(axis=-1, keepdims=True)
+    q = np.sqrt((sc ** 2).mean(axis=-1, keepdims=True))
+    m = lambda v: v.mean(axis=-1, keepdims=True)
+    dxh, sdxh = g * gamma, sg * np.abs(gamma)
+    c, s_c = m(dxh * xhat), m(_prod1(dxh, sdxh, xhat, sxhat))
+    u = dxh - m(dxh) - xhat * c * r
+    su = sdxh + m(sdxh) + r * _prod1(xhat, sxhat, c, s_c)
+    dx, sdx = u / den, (su + np.abs(u) * (q / den)) / den
+    flat = lambda a: a.reshape(-1, a.shape[-1])
+    return (dx, flat(g * xhat).sum(axis=0), flat(g).sum(axis=0)), (sdx, flat(_prod1(g, sg, xhat, sxhat)).sum(axis=0), flat(sg).sum(axis=0))
+
+
+def _chain_pullback(layers, tape, g, sg, first_order=False):
+    """The pullback of one Chain on rows from the cotangent g of its output: (dX of the chain's input, [(dW | dgamma, db | dbeta)] per layer), and
+    the same pair of scales — `_dense_pullback` / `_ln_pullback` layer by layer (`first_order`: their first-order forms), every recomputed
+    layer input and output at its forward scale."""
+    grads, sgrads = [None] * len(layers), [None] * len(layers)
+    for i in range(len(layers) - 1, -1, -1):
+        W, b, act = layers[i]
+        X, SX, y, Sy, Sn = tape[i]
+        if isinstance(W, str):
+            (g, dgam, dbet), (sg, sgam, sbet) = (_ln_pullback1 if first_order else _ln_pullback)(X, SX, b, CHAIN_LN_EPS, ln_eps_mode(W), g, sg)
+            grads[i], sgrads[i] = (dgam, dbet), (sgam, sbet)
+        else:
+            if first_order:
+                (_, dW, db, g), (_, sW, sb, sg) = _dense_pullback1(X, SX, W, b, act, y, Sn, Sy, g, sg)
+            else:
+                (_, dW, db, g), (_, sW, sb, sg) = _dense_pullback(X, SX, W, b, act, y, Sy, g, sg)
+            grads[i], sgrads[i] = (dW, db), (sW, sb)
+    return (g, grads), (sg, sgrads)
+
+
+def chain_block_tapes(p, csc, ef, nf, gf, first_order=False):
+    """One replica of chain_block_forward_sparse with every layer kept: ef, nf, gf (T, d) float64 arrays (zero width for `nothing`).  Returns
+    ((edge, node, graph) tapes — per layer (X, SX, y, Sy, Sn), for a Dense Sy = SX |W|^T + |b| is the scale of its pre-activation, Sn the scale the next layer is handed
+    (`_chain_tape`) —, (he, hn, hg))."""
+    colptr, rowval, node_off, edge_off = csc
+    N, E, G = len(colptr) - 1, len(rowval), len(node_off) - 1
+    dst = np.repeat(np.arange(N), np.diff(colptr))
+    ng = np.repeat(np.arange(G), np.diff(node_off))
+    eg = np.repeat(np.arange(G), np.diff(edge_off))
+    cat = lambda parts: np.concatenate(parts, axis=1)
+    Xe = cat([ef, nf[rowval], nf[dst], gf[eg]])
+    te, he, she = _chain_tape(p["edge"], Xe, np.abs(Xe), first_order)
+    if not p["edge"]:  # (a chain without layers = a zero-width output)
+        he, she = np.zeros((E, 0)), np.zeros((E, 0))
+    Xn = cat([_segsum(he, dst, N), nf, gf[ng]])
+    tn, hn, shn = _chain_tape(p["node"], Xn, cat([_segsum(she, dst, N), np.abs(nf), np.abs(gf[ng])]), first_order)
+    if not p["node"]:
+        hn, shn = np.zeros((N, 0)), np.zeros((N, 0))
+    Xg = cat([_segsum(he, eg, G), _segsum(hn, ng, G), gf])
+    tg, hg, _ = _chain_tape(p["graph"], Xg, cat([_segsum(she, eg, G), _segsum(shn, ng, G), np.abs(gf)]), first_order)
+    return (te, tn, tg), (he, hn, hg)
+
+
+def chain_block_backward_sparse(p, csc, x, cot, return_scale=True, first_order=True):
+    """Pullback of chain_block_forward_sparse as gnx_chain_block_backward defines it: x = (ef, nf, gf) the forward inputs and cot the three
+    cotangents, packed [R][T][d] with `None` for `nothing`; everything between the inputs and the outputs is recomputed.  Returns {d_ef, d_nf, d_gf:
+    [R][T][d] | None; "<fn><i>.dW": [in][out] of a Dense, gamma's gradient of a LayerNorm; "<fn><i>.db": the bias's, beta's} for fn in edge, node,
+    graph — parameter gradients summed over the replicas — and, with `return_scale`, the dict of their scales (see `Pullbacks` above: a tensor
+    handed to the call has S = |v|, a recomputed one the forward's scale).  The routing between the levels is `_block_pullback`'s.
+    `first_order` (the default): the scales of `_dense_pullback1` / `_ln_pullback1` — never above those of the product rule (`first_order=False`:
+    `_dense_pullback` / `_ln_pullback` as the block and the core use them), which on a chain is vacuous; tests/test_chain_bw_stress_cpu.py
+    asserts both S >= |value| and first-order S <= product S on every case."""
+    colptr, rowval, node_off, edge_off = csc
+    N, E, G = len(colptr) - 1, len(rowval), len(node_off) - 1
+    dst = np.repeat(np.arange(N), np.diff(colptr))
+    ng = np.repeat(np.arange(G), np.diff(node_off))
+    eg = np.repeat(np.arange(G), np.diff(edge_off))
+    de, dn, dg = p["in_dims"]
+    rows = (E, N, G)
+    R = next(a.shape[0] for a in (*x, *cot) if a is not None)
+    dxs, sdxs, val, sc = [], [], {}, {}
+    for r in range(R):
+        ef, nf, gf = (_w0(None if a is None else a[r], T) for a, T in zip(x, rows))
+        (te, tn, tg), (he, hn, hg) = chain_block_tapes(p, csc, ef, nf, gf, first_order)
+        oe, on = he.shape[1], hn.shape[1]
+        ce, cn, cg = (_w0(None if a is None else a[r], T) for a, T in zip(cot, rows))
+        # graph level
+        dXg, sXg = np.zeros((G, oe + on + dg)), np.zeros((G, oe + on + dg))
+        gr = {}
+        if p["graph"]:
+            cg = cg if cg.shape[1] else np.zeros((G, hg.shape[1]))  # (no cotangent for an output: zeros)
+            (dXg, gr["graph"]), (sXg, sgg) = _chain_pullback(p["graph"], tg, cg, np.abs(cg), first_order)
+        # node level
+        dXn, sXn = np.zeros((N, oe + dn + dg)), np.zeros((N, oe + dn + dg))
+        if p["node"]:
+            cn = cn if cn.shape[1] else np.zeros((N, on))
+            (dXn, gr["node"]), (sXn, sgn) = _chain_pullback(p["node"], tn, cn + dXg[ng][:, oe:oe + on], np.abs(cn) + sXg[ng][:, oe:oe + on], first_order)
+        # edge level
+        dXe, sXe = np.zeros((E, de + 2 * dn + dg)), np.zeros((E, de + 2 * dn + dg))
+        if p["edge"]:
+            ce = ce if ce.shape[1] else np.zeros((E, oe))
+            (dXe, gr["edge"]), (sXe, sge) = _chain_pullback(p["edge"], te, ce + dXg[eg][:, :oe] + dXn[dst][:, :oe], np.abs(ce) + sXg[eg][:, :oe] + sXn[dst][:, :oe], first_order)
+        sgr = dict(graph=sgg if p["graph"] else None, node=sgn if p["node"] else None, edge=sge if p["edge"] else None)
+        outs = []
+        for dXe_, dXn_, dXg_ in ((dXe, dXn, dXg), (sXe, sXn, sXg)):
+            d_nf = _segsum(dXe_[:, de:de + dn], rowval, N) + _segsum(dXe_[:, de + dn:de + 2 * dn], dst, N) + dXn_[:, oe:oe + dn]
+            d_gf = _segsum(dXe_[:, de + 2 * dn:], eg, G) + _segsum(dXn_[:, oe + dn:], ng, G) + dXg_[:, oe + on:]
+            outs.append((dXe_[:, :de], d_nf, d_gf))
+        dxs.append(outs[0]); sdxs.append(outs[1])
+        for name in ("edge", "node", "graph"):
+            for i in range(len(p[name])):
+                for k, which in enumerate(("dW", "db")):
+                    n = f"{name}{i}.{which}"
+                    val[n] = gr[name][i][k] + (val[n] if n in val else 0.0)
+                    sc[n] = sgr[name][i][k] + (sc[n] if n in sc else 0.0)
+    val.update(zip(("d_ef", "d_nf", "d_gf"), _pack_dx(dxs, p["in_dims"])))
+    sc.update(zip(("d_ef", "d_nf", "d_gf"), _pack_dx(sdxs, p["in_dims"])))
+    return (val, sc) if return_scale else val
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@ import pytest
 
 from oracle import gn_oracle as O
 from tests import util as U
+from tests.chain_torch import _torch_chain_block  # noqa: F401  (other test modules take it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -78,42 +79,6 @@ def test_chain_block_shared_graph_replicas_and_errors(gn):
             if r is not None:
                 U.assert_close(np.transpose(got.cpu().numpy(), (2, 1, 0)), r, sc)
         U.assert_close(yz.gf.cpu().numpy().T[:, None, :], rz[2], sz[2])
-
-
-def _torch_chain_block(csc, ef, nf, gf, W):
-    """float64 torch restatement of the block with Chain update functions (one replica); W[name] = list of (weight, bias, act)."""
-    import torch
-    ACT = {0: lambda x: x, 1: torch.relu, 2: torch.tanh, 3: torch.sigmoid, 4: lambda x: torch.nn.functional.gelu(x, approximate="tanh")}
-    colptr, rowval, node_off, edge_off = (torch.from_numpy(np.asarray(a)) for a in csc)
-    N, G = len(colptr) - 1, len(node_off) - 1
-    dst = torch.repeat_interleave(torch.arange(N), colptr[1:] - colptr[:-1])
-    ng = torch.repeat_interleave(torch.arange(G), node_off[1:] - node_off[:-1])
-    eg = torch.repeat_interleave(torch.arange(G), edge_off[1:] - edge_off[:-1])
-    cat = lambda parts: torch.cat([q for q in parts if q is not None], dim=1)
-
-    def chain(x, layers, pre):
-        for w, b, a in layers:
-            if isinstance(w, str):  # ("layernorm", gamma, beta): Flux 0.14 normalise (x - mean) / (sigma + eps), then gamma . xhat + beta
-                mu = x.mean(dim=1, keepdim=True)
-                sd = ((x - mu) ** 2).mean(dim=1, keepdim=True).sqrt()
-                x = b * ((x - mu) / (sd + 1e-5)) + a
-                continue
-            z = x @ w.T + b
-            pre.append((z, a))
-            x = ACT[a](z)
-        return x
-
-    pre = []
-    he = chain(cat([ef, None if nf is None else nf[rowval], None if nf is None else nf[dst], None if gf is None else gf[eg]]), W["edge"], pre)
-    hn = hg = None
-    if W["node"]:
-        agg = torch.zeros((N, he.shape[1]), dtype=he.dtype).index_add(0, dst, he)
-        hn = chain(cat([agg, nf, None if gf is None else gf[ng]]), W["node"], pre)
-    if W["graph"]:  # (a block without a node function: its zero-width nf' is an empty segment of the graph function's input, gnblock.jl:63-69)
-        se = torch.zeros((G, he.shape[1]), dtype=he.dtype).index_add(0, eg, he)
-        sn = None if hn is None else torch.zeros((G, hn.shape[1]), dtype=he.dtype).index_add(0, ng, hn)
-        hg = chain(cat([se, sn, gf]), W["graph"], pre)
-    return (he, hn, hg), pre
 
 
 BW_CASES = [

@@ -1,7 +1,9 @@
 """gnx_chain_block_backward_narrow: the pullback of a GNBlock whose update functions are Chains with every update function inside the rule in ONE
 kernel (csrc/gnx_chain_bw_narrow.hip) — against float64 torch autograd through the Python switch, against the generic entry through the ABI
-(max|narrow - ref| <= max(4 max|generic - ref|, 1e-5 max(1, max|ref|)) per gradient tensor: the factor 4 is the margin tests/test_gpu_bw_x6_stress.py
-gives another summation order, 1e-5 the project's plain bound), structural batches, what happens outside the rule, the launch structure, the
+(max|narrow - ref| <= max(4 max|generic - ref|, 1e-5 max(1, max|ref|)) per gradient tensor: a NORMWISE bound whose yardstick is the generic
+entry's own error — it does not have the margin of tests/test_gpu_bw_x6_stress.py, whose factor 4 is on a mean error against a float32 evaluation;
+the elementwise bar |got - ref| <= 1e-5 . S against the float64 pullback oracle, for both entries, is tests/test_gpu_chain_bw_stress.py's),
+structural batches, what happens outside the rule, the launch structure, the
 memory contract on exactly sized 4-byte-aligned buffers, stream capture, the Python switch and a seeded sweep.  Small batches throughout: five
 graphs of 3..40 nodes."""
 import ctypes as C

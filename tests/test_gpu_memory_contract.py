@@ -550,7 +550,8 @@ def _chain_params(gn, a, p, keep):
         wid = (C.c_int32 * max(len(layers), 1))()
         for i, (w, b, c) in enumerate(layers):
             ln = isinstance(w, str)
-            arr[i] = _dense(gn, a, f"chain.{name}{i}", 0 if ln else c, L.LAYER_LAYERNORM if ln else 0)
+            kind = 0 if not ln else (L.LAYER_LAYERNORM | L.LAYER_LN_SQRT_EPS if O.ln_eps_mode(w) == 1 else L.LAYER_LAYERNORM)
+            arr[i] = _dense(gn, a, f"chain.{name}{i}", 0 if ln else c, kind)
             wid[i] = len(b) if ln else w.shape[0]
         keep += [arr, wid]
         ch = getattr(q, field)
