@@ -904,10 +904,17 @@ class GNBlock:
     gnx_chain_block_backward_narrow — each update function inside its rule (include/gnx.h: the forward's rule and 64 KB of LDS for two
     waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled back in one kernel, a row per lane forward
     and back through all layers, with only what crosses levels recomputed into the workspace; the others as before.  The gradients are within
-    the generic pullback's error of the exact ones, not its bits.  Off (the default): gnx_chain_block_backward."""
+    the generic pullback's error of the exact ones, not its bits.  Off (the default): gnx_chain_block_backward.
+
+    `bf16_chain` (also a plain attribute): lets a block whose update functions are Chains run on bfloat16 features through
+    gnx_chain_block_forward_typed, mirroring gnx_chain_block_forward_narrow with `narrow_chain` and gnx_chain_block_forward without: bf16 outputs,
+    bit for bit the fp32 entry on the widened inputs rounded once.  With `narrow_chain` and every update function inside the narrow rule the
+    fused kernels read and write the bf16 rows themselves; elsewhere fp32 copies go around the fp32 entry.  A differentiable call also needs
+    `bf16_backward`: its pullback is gnx_chain_block_backward_typed (`narrow_chain_backward` selects the mirrored fp32 pullback), input
+    gradients rounded to bfloat16, parameter gradients in float32.  Off (the default) such a block on bfloat16 features raises."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
-                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False):
+                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -924,6 +931,7 @@ class GNBlock:
         self.narrow_backward = bool(narrow_backward)
         self.narrow_chain = bool(narrow_chain)
         self.narrow_chain_backward = bool(narrow_chain_backward)
+        self.bf16_chain = bool(bf16_chain)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -985,15 +993,23 @@ class GNBlock:
             outw.append(widths[-1] if widths else 0)
         return p, chains, outw
 
-    def _chain_forward(self, g, R, flags, ef, nf, gf):
+    def _chain_forward(self, g, R, flags, ef, nf, gf, bf16=False):
         lib = _lib.load()
         keep = []
         p, chains, outw = self._chain_params(keep)
         dev = g.device
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.float32, device=dev) if d > 0 else None
+        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.bfloat16 if bf16 else torch.float32, device=dev) if d > 0 else None
         eo, no, go = mk(g.n_edges, outw[0]), mk(g.n_nodes, outw[1]), mk(g.n_graphs, outw[2])
         with torch.cuda.device(dev):
             narrow = bool(getattr(self, "narrow_chain", False))
+            if bf16:  # gnx_chain_block_forward_typed mirrors the entry `narrow_chain` selects
+                nbytes = lib.gnx_chain_block_forward_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, int(narrow))
+                if nbytes == 0:
+                    raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
+                ws = g.workspace(nbytes, ("chain_bf16", narrow, self.in_dims, tuple(tuple(int(l.weight.shape[0]) for l in ch.layers) for ch in chains), R))
+                check(lib.gnx_chain_block_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
+                                                        ws.data_ptr(), ws.numel(), int(narrow), flags, torch.cuda.current_stream(dev).cuda_stream))
+                return eo, no, go
             query, entry = ((lib.gnx_chain_block_forward_narrow_workspace_bytes, lib.gnx_chain_block_forward_narrow) if narrow else
                             (lib.gnx_chain_block_workspace_bytes, lib.gnx_chain_block_forward))
             nbytes = query(g._h, C.byref(p), R)
@@ -1021,13 +1037,43 @@ class GNBlock:
             eo, no, go = self._chain_forward(g, R, flags, ef, nf, gf)
         return NT(g, _jl(eo), _jl(no), _jl(go))
 
+    def _call_chains_bf16(self, x, flags):
+        """Chain update functions on bfloat16 features (`bf16_chain`): gnx_chain_block_forward_typed, bf16 outputs; a differentiable call needs
+        `bf16_backward` (gnx_chain_block_backward_typed is then the pullback) and raises without it."""
+        xt = _as_nt(x)
+        chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
+        params = [t for ch in chains for l in ch.layers for t in (l.weight, l.bias)]
+        feats = [a for a in (xt.ef, xt.nf, xt.gf) if isinstance(a, torch.Tensor)]
+        trainable = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in feats + params)
+        if trainable:
+            if not getattr(self, "bf16_backward", False):
+                raise NotImplementedError("GNBlock: the backward of a Chain block on bfloat16 features is not implemented unless the block's bf16_backward "
+                                          "switch is on (GNBlock(..., bf16_backward=True) or blk.bf16_backward = True): its input gradients are rounded "
+                                          "to bfloat16; or call it under torch.no_grad() or with float32 features")
+            if any(ch.dropout_p > 0 for ch in chains):
+                raise NotImplementedError("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
+                                          "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
+        g, ef, nf, gf, R = _forward_common(x, self.in_dims, None)
+        flags = self.flags if flags is None else flags
+        if trainable:
+            outs = iter(_ChainBlockBf16Fn.apply(self, g, R, flags, ef, nf, gf, *params))
+            eo, no, go = (next(outs) if ch.out_width > 0 else None for ch in chains)
+        else:
+            # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
+            ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+            eo, no, go = self._chain_forward(g, R, flags, ef, nf, gf, bf16=True)
+        return NT(g, _jl(eo), _jl(no), _jl(go))
+
     def __call__(self, x, flags=None):
         fns = (self.edgefn, self.nodefn, self.graphfn)
         chained = any(isinstance(f, Chain) and (len(f) != 1 or isinstance(f.layers[0], LayerNorm) or f.dropout_p > 0) for f in fns)
         xt = _as_nt(x)
         if _feature_dtype(xt.ef, xt.nf, xt.gf) == torch.bfloat16:  # (mixed bf16 / other features: TypeError, before any library call)
             if chained:
-                raise NotImplementedError("GNBlock: Chain update functions on bfloat16 features are not supported; convert the features with .float()")
+                if not getattr(self, "bf16_chain", False):
+                    raise NotImplementedError("GNBlock: Chain update functions on bfloat16 features are not supported unless the block's bf16_chain switch "
+                                              "is on (GNBlock(..., bf16_chain=True) or blk.bf16_chain = True); or convert the features with .float()")
+                return self._call_chains_bf16(x, flags)
             return self._call_bf16(x, flags)
         if chained:
             return self._call_chains(x, flags)
@@ -1224,46 +1270,83 @@ class _ChainBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        lib = _lib.load()
-        block, g, R = ctx.block, ctx.g, ctx.R
-        sv = iter(ctx.saved_tensors)
-        ef, nf, gf = (next(sv) if present else None for present in ctx.slots)
-        it = iter(gouts)
-        ge, gn_, gg = (next(it) if pr else None for pr in ctx.present)
-        cont = lambda t: None if t is None else t.contiguous()
-        ge, gn_, gg = cont(ge), cont(gn_), cont(gg)
-        keep = []
-        p, chains, _ = block._chain_params(keep)
-        dev = g.device
-        need = ctx.needs_input_grad  # (block, g, R, flags, ef, nf, gf, W, b, W, b, ...)
-        d_ef = torch.empty_like(ef) if ef is not None and need[4] else None
-        d_nf = torch.empty_like(nf) if nf is not None and need[5] else None
-        d_gf = torch.empty_like(gf) if gf is not None and need[6] else None
-        gW, gb, arrays, k = [], [], [], 7
-        for ch in chains:
-            entries = []
-            for l in ch.layers:
-                ln = isinstance(l, LayerNorm)  # (its "weight" slot is gamma [d])
-                w = (torch.empty_like(l.gamma) if ln else torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev)) if need[k] else None
-                b = torch.empty_like(l.bias) if (l.bias is not None and need[k + 1]) else None
-                k += 2
-                gW.append(w); gb.append(b)
-                entries.append(_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None))
-            arrays.append((_lib.DenseGrad * max(len(entries), 1))(*entries))
-        grads = _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays])
-        with torch.cuda.device(dev):
+        return _chain_block_pullback(ctx, gouts, _lib.ELEM_F32)
+
+
+def _chain_block_pullback(ctx, gouts, elem):
+    """backward of _ChainBlockFn (elem F32) and _ChainBlockBf16Fn (BF16: gnx_chain_block_backward_typed on bf16 feature-shaped tensors)"""
+    lib = _lib.load()
+    block, g, R = ctx.block, ctx.g, ctx.R
+    bf16 = elem == _lib.ELEM_BF16
+    sv = iter(ctx.saved_tensors)
+    ef, nf, gf = (next(sv) if present else None for present in ctx.slots)
+    it = iter(gouts)
+    ge, gn_, gg = (next(it) if pr else None for pr in ctx.present)
+    cont = lambda t: None if t is None else t.contiguous()
+    ge, gn_, gg = cont(ge), cont(gn_), cont(gg)
+    if bf16:  # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
+        ge, gn_, gg = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ge, gn_, gg))
+    keep = []
+    p, chains, _ = block._chain_params(keep)
+    dev = g.device
+    need = ctx.needs_input_grad  # (block, g, R, flags, ef, nf, gf, W, b, W, b, ...)
+    d_ef = torch.empty_like(ef) if ef is not None and need[4] else None
+    d_nf = torch.empty_like(nf) if nf is not None and need[5] else None
+    d_gf = torch.empty_like(gf) if gf is not None and need[6] else None
+    gW, gb, arrays, k = [], [], [], 7
+    for ch in chains:
+        entries = []
+        for l in ch.layers:
+            ln = isinstance(l, LayerNorm)  # (its "weight" slot is gamma [d])
+            w = (torch.empty_like(l.gamma) if ln else torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev)) if need[k] else None
+            b = torch.empty_like(l.bias) if (l.bias is not None and need[k + 1]) else None
+            k += 2
+            gW.append(w); gb.append(b)
+            entries.append(_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None))
+        arrays.append((_lib.DenseGrad * max(len(entries), 1))(*entries))
+    grads = _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays])
+    with torch.cuda.device(dev):
+        narrow = bool(getattr(block, "narrow_chain_backward", False))
+        if bf16:
+            nb = lib.gnx_chain_block_backward_typed_workspace_bytes(g._h, C.byref(p), R, elem, int(narrow))
+        else:
             query, entry = ((lib.gnx_chain_block_backward_narrow_workspace_bytes, lib.gnx_chain_block_backward_narrow)
-                            if getattr(block, "narrow_chain_backward", False) else (lib.gnx_chain_block_backward_workspace_bytes, lib.gnx_chain_block_backward))
+                            if narrow else (lib.gnx_chain_block_backward_workspace_bytes, lib.gnx_chain_block_backward))
             nb = query(g._h, C.byref(p), R)
-            if nb == 0:
-                raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-            ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+        if nb == 0:
+            raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
+        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+        if bf16:
+            check(lib.gnx_chain_block_backward_typed(g._h, C.byref(p), elem, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
+                                                     _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), int(narrow),
+                                                     torch.cuda.current_stream(dev).cuda_stream))
+        else:
             check(entry(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R,
                         _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-        out = [None, None, None, None, d_ef, d_nf, d_gf]
-        for w, b in zip(gW, gb):
-            out += [None if w is None else (w if w.dim() == 1 else w.t()), b]  # (out, in) view with column-major storage, like the weights; a LayerNorm's gamma as it is
-        return tuple(out)
+    out = [None, None, None, None, d_ef, d_nf, d_gf]
+    for w, b in zip(gW, gb):
+        out += [None if w is None else (w if w.dim() == 1 else w.t()), b]  # (out, in) view with column-major storage, like the weights; a LayerNorm's gamma as it is
+    return tuple(out)
+
+
+class _ChainBlockBf16Fn(torch.autograd.Function):
+    """_ChainBlockFn on bfloat16 features (GNBlock.bf16_chain with bf16_backward): forward = gnx_chain_block_forward_typed, backward =
+    gnx_chain_block_backward_typed mirroring the pullback `narrow_chain_backward` selects.  The saved inputs are bf16; the input gradients come
+    back in bf16 (rounded once from the fp32 pullback of the widened tensors), the parameter gradients in fp32 in _ChainBlockFn's layout."""
+
+    @staticmethod
+    def forward(ctx, block, g, R, flags, ef, nf, gf, *params):
+        ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
+        eo, no, go = block._chain_forward(g, R, flags, ef, nf, gf, bf16=True)
+        ctx.block, ctx.g, ctx.R = block, g, R
+        ctx.slots = tuple(t is not None for t in (ef, nf, gf))
+        ctx.save_for_backward(*[t for t in (ef, nf, gf) if t is not None])
+        ctx.present = tuple(o is not None for o in (eo, no, go))
+        return tuple(o for o in (eo, no, go) if o is not None)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        return _chain_block_pullback(ctx, gouts, _lib.ELEM_BF16)
 
 
 class GNFeedForward:

@@ -1684,6 +1684,12 @@ int32_t chain_backward(const gnx_graphs* h, const gnx_chain_block_params* p0, co
   return GNX_OK;
 }
 
+// the workspace of gnx_chain_block_backward_typed on bf16 features: the fp32 pullback's (`base`), then fp32 copies of the nine feature-shaped tensors
+Staging chain_bw_typed_ws(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, size_t base) {
+  const int d[9] = {p->de, p->dn, p->dg, chain_out(p->edgefn), chain_out(p->nodefn), chain_out(p->graphfn), p->de, p->dn, p->dg};
+  return stage_features(base, h, R, d, 9);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1707,6 +1713,40 @@ int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_chain_blo
                                         const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                                         float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   return chain_backward(h, p, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, true);
+}
+
+// gnx_chain_block_backward_typed: either pullback above (narrow selects which) on fp32 or bf16 features.  bf16 is staged: the six feature
+// inputs and upstream gradients are widened into fp32 copies behind the fp32 pullback's workspace, the three input gradients rounded back
+// (gnx_staging.h); the parameter gradients are the fp32 pullback's own.
+size_t gnx_chain_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, int32_t narrow) {
+  if ((elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) || (narrow != 0 && narrow != 1)) return 0;
+  const size_t base = chain_bw_query(h, p, R, narrow != 0);
+  return elem == GNX_ELEM_F32 || base == 0 ? base : chain_bw_typed_ws(h, p, R, base).total;
+}
+
+int32_t gnx_chain_block_backward_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                       const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf,
+                                       const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, int32_t narrow, void* stream) {
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
+  if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
+  if (elem == GNX_ELEM_F32)
+    return chain_backward(h, p, static_cast<const float*>(ef), static_cast<const float*>(nf), static_cast<const float*>(gf), static_cast<const float*>(g_ef_out),
+                          static_cast<const float*>(g_nf_out), static_cast<const float*>(g_gf_out), R, static_cast<float*>(d_ef), static_cast<float*>(d_nf),
+                          static_cast<float*>(d_gf), grads, ws, ws_bytes, stream, narrow != 0);
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  if (int32_t rc = chain_check_params(h, p, R)) return rc;
+  const void* bufs[9] = {ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
+  if (int32_t rc = check_bf16_aligned(bufs, 9)) return rc;
+  if ((p->de > 0 && !ef && h->E > 0) || (p->dn > 0 && !nf) || (p->dg > 0 && !gf)) return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL");
+  const size_t base = chain_bw_query(h, p, R, narrow != 0);  // (what the fp32 pullback asks of the handle exists since the caller's query)
+  if (base == 0) return GNX_ERR_DIMS;  // gnx_last_error() holds the reason
+  const Staging w = chain_bw_typed_ws(h, p, R, base);
+  if (int32_t rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_chain_block_backward_typed_workspace_bytes()")) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  if (int32_t rc = stage_widen(w, ws, bufs, 0, 6, s)) return rc;
+  auto at = [&](int i) { return bufs[i] && w.n[i] > 0 ? w.at(ws, i) : nullptr; };
+  if (int32_t rc = chain_backward(h, p, at(0), at(1), at(2), at(3), at(4), at(5), R, at(6), at(7), at(8), grads, ws, w.base, stream, narrow != 0)) return rc;
+  return stage_round(w, ws, bufs, 6, 9, s);
 }
 
 }  // extern "C"

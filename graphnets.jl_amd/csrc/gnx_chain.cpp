@@ -13,9 +13,12 @@
 // Semantics are exactly (m::GNBlock)(x) of src/gnblock.jl:63-69 with Chain update functions; zero-width outputs -> `nothing`.
 // gnx_chain_block_forward_narrow: the same block with every update function whose input and layer widths are at most 32 in ONE kernel
 // (gnx_chain_narrow.hip: k_chain_mlp, a row per lane through all layers); a function outside that rule runs the launches above.
+// gnx_chain_block_forward_typed: either entry on bfloat16 features — where every function that runs is inside the rule, the same kernels reading
+// and writing bf16 rows (gnx_chain_narrow_bf16.hip); elsewhere fp32 copies around the fp32 entry (gnx_staging.h).
 #include <algorithm>
 
 #include "gnx_launchers.h"
+#include "gnx_staging.h"
 
 using namespace gnx;
 
@@ -249,6 +252,81 @@ int32_t chain_forward(const gnx_graphs* h, const gnx_chain_block_params* p0, con
   return GNX_OK;
 }
 
+// ---- bfloat16 features (gnx_chain_block_forward_typed) ----
+// The native path: narrow = 1 and every update function with an output and rows to run on is inside the fused rule — then each runs as one
+// k_chain_mlp_bf16 launch on the bf16 rows (gnx_chain_narrow_bf16.hip) and nothing of the block is widened or rounded by a pass of its own.
+bool typed_native(const gnx_graphs* h, const gnx_chain_block_params* p, bool narrow) {
+  if (!narrow) return false;
+  const unsigned m = narrow_mask(h, p);
+  const int ow[3] = {out_width(p->edgefn), out_width(p->nodefn), out_width(p->graphfn)};
+  const int64_t rows[3] = {h->E, h->N, h->G};
+  for (int t = 0; t < 3; ++t)
+    if (ow[t] > 0 && rows[t] > 0 && !(m & (1u << t))) return false;
+  return true;
+}
+// the workspace of the mirrored fp32 entry (validated parameters); the query has built what the layout asks of the handle
+size_t base_total(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, bool narrow) {
+  const unsigned fused = narrow ? narrow_mask(h, p0) : 0;
+  ChainLnFirst lnf;
+  const gnx_chain_block_params* p = (fused & 1) ? p0 : lnf.init(p0, nullptr);
+  return layout(h, p, R, lnf.ident_floats(), fused).total;
+}
+// workspace of a bf16 call: the mirrored entry's, then (native) the fp32 rows a later function of the call reads — 0: ef' for the node / graph
+// function, 1: nf' and 2: the widened gf for the graph function — or (staged) fp32 copies of the three inputs and the three outputs
+Staging typed_ws(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, bool narrow, bool native) {
+  const int oe = out_width(p->edgefn), on = out_width(p->nodefn), og = out_width(p->graphfn);
+  const size_t base = base_total(h, p, R, narrow);
+  if (!native) {
+    const int d[6] = {p->de, p->dn, p->dg, oe, on, og};
+    return stage_features(base, h, R, d, 6);
+  }
+  const size_t counts[3] = {on > 0 || og > 0 ? (size_t)R * h->E * oe : 0, og > 0 ? (size_t)R * h->N * on : 0, og > 0 ? (size_t)R * h->G * p->dg : 0};
+  return stage_layout(base, counts, 3);
+}
+
+int32_t chain_forward_bf16(const gnx_graphs* h, const gnx_chain_block_params* p, const void* ef, const void* nf, const void* gf, int64_t R, void* ef_out,
+                           void* nf_out, void* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream, bool narrow) {
+  hipStream_t s = (hipStream_t)stream;
+  int32_t rc = check_params(h, p, R);
+  if (rc) return rc;
+  const int de = p->de, dn = p->dn, dg = p->dg;
+  const int oe = out_width(p->edgefn), on = out_width(p->nodefn), og = out_width(p->graphfn);
+  if ((de > 0 && !ef && h->E > 0) || (dn > 0 && !nf) || (dg > 0 && !gf)) return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL (width 0 <=> nothing)");
+  if ((oe > 0 && !ef_out && h->E > 0) || (on > 0 && !nf_out) || (og > 0 && !gf_out)) return fail(GNX_ERR_INVALID_ARG, "an output with non-zero width is NULL");
+  const void* bufs[6] = {ef, nf, gf, ef_out, nf_out, gf_out};
+  if ((rc = check_bf16_aligned(bufs, 6))) return rc;
+  const bool native = typed_native(h, p, narrow);
+  const Staging w = typed_ws(h, p, R, narrow, native);
+  if ((rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_chain_block_forward_typed_workspace_bytes()"))) return rc;
+  if (!native) {  // widen into the workspace, the mirrored fp32 entry (its own dispatch), round the outputs
+    if ((rc = stage_widen(w, ws, bufs, 0, 3, s))) return rc;
+    auto at = [&](int i) { return w.n[i] > 0 ? w.at(ws, i) : nullptr; };
+    if ((rc = chain_forward(h, p, at(0), at(1), at(2), R, at(3), at(4), at(5), ws, w.base, flags, stream, narrow))) return rc;
+    return stage_round(w, ws, bufs, 3, 6, s);
+  }
+  gnx::FormScope forms(flags);
+  gnx::DeviceTurn turn(s, false);  // (narrow widths: no matrix instruction)
+  const unsigned fused = narrow_mask(h, p);
+  float* ef32 = w.n[0] > 0 ? w.at(ws, 0) : nullptr;  // ef' / nf' unrounded, for the functions of this call that read them
+  float* nf32 = w.n[1] > 0 ? w.at(ws, 1) : nullptr;
+  if (fused & 1) {
+    if ((rc = launch_chain_narrow_bf16(h, 0, p->edgefn, ef, de, nf, dn, gf, dg, ef_out, ef32, R, s, "k_rows_gemm_chain_e"))) return rc;
+  }
+  if (fused & 2) {
+    if ((rc = launch_chain_narrow_bf16(h, 1, p->nodefn, ef32, oe, nf, dn, gf, dg, nf_out, nf32, R, s, "k_rows_gemm_chain_n"))) return rc;
+  }
+  if (og > 0) {  // (typed_native: inside the rule)
+    float* gf32 = w.n[2] > 0 ? w.at(ws, 2) : nullptr;
+    if (gf32 && (rc = launch_bf16_widen(gf, w.n[2], gf32, s))) return rc;
+    ChainLnFirst lnf;
+    const gnx_chain_block_params* q = (fused & 1) ? p : lnf.init(p, nullptr);  // (the layout of base_total)
+    float* g_in = reinterpret_cast<float*>(static_cast<char*>(ws) + layout(h, q, R, lnf.ident_floats(), fused).g_in);
+    if ((rc = launch_fn_input(h, 2, ef32, oe, nf32, on, gf32, dg, R, g_in, s))) return rc;
+    if ((rc = launch_chain_narrow_bf16(h, 2, p->graphfn, g_in, oe + on + dg, nullptr, 0, nullptr, 0, gf_out, nullptr, R, s, "k_rows_gemm_chain_g"))) return rc;
+  }
+  return GNX_OK;
+}
+
 }  // namespace
 
 namespace gnx {
@@ -273,6 +351,28 @@ size_t gnx_chain_block_forward_narrow_workspace_bytes(const gnx_graphs* h, const
 int32_t gnx_chain_block_forward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
                                        float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
   return chain_forward(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream, true);
+}
+
+// gnx_chain_block_forward_typed: either entry above on fp32 or bf16 features (narrow selects which one the call mirrors)
+int32_t gnx_chain_block_forward_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, int32_t narrow) {
+  return elem == GNX_ELEM_BF16 && narrow == 1 && check_params(h, p, R) == GNX_OK && typed_native(h, p, true) ? 1 : 0;
+}
+
+size_t gnx_chain_block_forward_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, int32_t narrow) {
+  if ((elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) || (narrow != 0 && narrow != 1)) return 0;
+  const size_t base = chain_workspace_bytes(h, p, R, narrow != 0);  // validates; builds the tables either path reads, outside any capture
+  if (elem == GNX_ELEM_F32 || base == 0) return base;
+  return typed_ws(h, p, R, narrow != 0, typed_native(h, p, narrow != 0)).total;
+}
+
+int32_t gnx_chain_block_forward_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf, int64_t R,
+                                      void* ef_out, void* nf_out, void* gf_out, void* ws, size_t ws_bytes, int32_t narrow, uint32_t flags, void* stream) {
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
+  if (elem == GNX_ELEM_F32)
+    return chain_forward(h, p, static_cast<const float*>(ef), static_cast<const float*>(nf), static_cast<const float*>(gf), R, static_cast<float*>(ef_out),
+                         static_cast<float*>(nf_out), static_cast<float*>(gf_out), ws, ws_bytes, flags, stream, narrow != 0);
+  return chain_forward_bf16(h, p, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream, narrow != 0);
 }
 
 }  // extern "C"

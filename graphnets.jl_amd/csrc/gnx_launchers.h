@@ -184,6 +184,11 @@ bool chain_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows);
 // entity 0: in0 / in1 / in2 = ef, nf, gf (widths d0, d1, d2); 1: ef', nf, gf; 2: in0 = the materialised [R G][d0] input rows (d1 = d2 = 0)
 int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                             float* out, int64_t R, hipStream_t s, const char* name);
+// ---- gnx_chain_narrow_bf16.hip: the same on bf16 features (gnx_chain_block_forward_typed's native path) ----
+// entity 0: in0 / in1 / in2 are bf16; 1: in0 is the fp32 ef' of this call, in1 / in2 are bf16; 2: in0 is fp32.  out: bf16 rows; out32: the same rows
+// unrounded in fp32, or nullptr.  The caller asked chain_narrow_takes.
+int32_t launch_chain_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
+                                 void* out, float* out32, int64_t R, hipStream_t s, const char* name);
 
 // ---- gnx_chain_bw_narrow.hip: the pullback of one update function of a Chain block in one kernel (gnx_chain_block_backward_narrow) ----
 // the kernel's LDS plan for a function: the staged parameters, then per wave 64 tape rows of `ld` floats (the input row, every layer's output but

@@ -417,6 +417,31 @@ GNX_API size_t gnx_chain_block_forward_narrow_workspace_bytes(const gnx_graphs* 
 GNX_API int32_t gnx_chain_block_forward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
                                        int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out, void* workspace, size_t workspace_bytes,
                                        uint32_t flags, void* stream);
+/* Either Chain forward on float32 or bfloat16 features.  `elem` (GNX_ELEM_*) applies to the three feature inputs and the three outputs; weights
+ * stay float32.  `narrow` (0 or 1) selects the entry the call mirrors: gnx_chain_block_forward (0) or gnx_chain_block_forward_narrow (1).
+ * GNX_ELEM_F32 IS the mirrored entry: same validation, same workspace size, same bits.  Any other elem than F32 / BF16: the call returns
+ * GNX_ERR_INVALID_ARG before any GPU work, the queries return 0 (so does a narrow other than 0 / 1).
+ * GNX_ELEM_BF16, finite data: the three outputs are bit for bit to_bf16(ref), ref the mirrored fp32 entry on the exactly widened inputs under
+ * the same flags, rounded to nearest even once; every intermediate stays fp32.  A bf16 buffer must be 4-byte aligned (else GNX_ERR_INVALID_ARG
+ * before any GPU work); rows of odd width and replicas of an odd rows * width then start 2-byte aligned, which is all the kernels assume.
+ * Native path — narrow = 1 and every update function that has a non-zero output width AND whose entity has rows is in
+ * gnx_chain_block_forward_narrow_applies' mask: each function runs as ONE launch of the fused kernel reading bf16 rows and storing its last
+ * layer's row as bf16 (k_chain_mlp_bf16, csrc/gnx_chain_narrow_bf16.hip), under the fp32 entry's profiler names; a function a later one of the
+ * call reads also leaves its unrounded fp32 row in the workspace.  Beside those launches only the graph function's helpers run: the widening of
+ * gf (G rows) and the materialisation of its input rows.  No edge- or node-sized tensor is widened or rounded by a pass of its own.
+ * Workspace: the narrow entry's plus fp32 carves of ef' (if the node or graph function consumes it), nf' (if the graph function does) and
+ * the widened gf (if the graph function exists and dg > 0).  _typed_applies: 1 for this path, 0 otherwise (bad arguments and F32 included).
+ * Staged path — every other case (narrow = 0, a function outside the rule, a mixed mask): fp32 copies of the three inputs and the three
+ * outputs around the mirrored entry; the workspace is that entry's plus the six copies.
+ * No class of instantiations is cut from the native rule: see README.md ("Chain blocks on bfloat16 features") for the measured figures.
+ * The queries build the handle's tables (call them outside a stream capture); the call allocates nothing, does not synchronise and uses one
+ * stream.  Refusals as the mirrored entry's, the workspace one naming gnx_chain_block_forward_typed_workspace_bytes(). */
+GNX_API int32_t gnx_chain_block_forward_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem, int32_t narrow);
+GNX_API size_t gnx_chain_block_forward_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem,
+                                                             int32_t narrow);
+GNX_API int32_t gnx_chain_block_forward_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf,
+                                              const void* gf, int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace,
+                                              size_t workspace_bytes, int32_t narrow, uint32_t flags, void* stream);
 
 /* ---- backward of the block: what a Zygote `rrule` / torch autograd function for (m::GNBlock)(x) needs.
  * Inputs: the forward's inputs (ef, nf, gf), its outputs (ef_out, nf_out, gf_out) and the upstream gradients with the
@@ -580,6 +605,22 @@ GNX_API int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_c
                                         const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
                                         float* d_nf, float* d_gf, const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes,
                                         void* stream);
+/* Either Chain pullback on float32 or bfloat16 features.  `elem` applies to the nine feature-shaped tensors (the inputs, the upstream gradients,
+ * the input gradients); parameter gradients stay float32.  `narrow` (0 or 1): gnx_chain_block_backward (0) or gnx_chain_block_backward_narrow
+ * (1).  GNX_ELEM_F32 IS the mirrored entry (same validation, workspace size, bits); another elem than F32 / BF16 or a narrow other than 0 / 1:
+ * GNX_ERR_INVALID_ARG before any GPU work, 0 from the query.  A bf16 buffer must be 4-byte aligned (GNX_ERR_INVALID_ARG before any GPU work).
+ * GNX_ELEM_BF16 is staged, there is no bf16 pullback kernel: the six inputs and upstream gradients are widened into fp32 copies (256-byte
+ * aligned carves behind the fp32 pullback's workspace), the fp32 pullback runs on them, the three input gradients are rounded back.  d_ef, d_nf,
+ * d_gf are bit for bit to_bf16(ref) and every parameter gradient is bit for bit ref's, ref the mirrored fp32 pullback on the exactly widened
+ * tensors in 16-byte-aligned buffers.  Optional outputs and NULL upstream gradients as in the fp32 entries.  The workspace is the mirrored
+ * entry's plus the nine copies; its refusal names gnx_chain_block_backward_typed_workspace_bytes().  The query builds the handle's tables (call
+ * it outside a stream capture); the call allocates nothing, does not synchronise and uses one stream. */
+GNX_API size_t gnx_chain_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem,
+                                                              int32_t narrow);
+GNX_API int32_t gnx_chain_block_backward_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf,
+                                               const void* gf, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t n_replicas,
+                                               void* d_ef, void* d_nf, void* d_gf, const gnx_chain_block_grads* grads, void* workspace,
+                                               size_t workspace_bytes, int32_t narrow, void* stream);
 
 /* Backward of (m::GNCore)(x) = x + block(gn1(x)) + ffwd(gn2(x)) (src/gncore.jl:56-68).  Takes the forward's INPUTS and the
  * upstream gradients; the intermediates (both LayerNorms, the block's outputs, the FeedForward hidden activations) are

@@ -914,6 +914,58 @@ function chain_backward_narrow_applies(m::ChainBlock, x)
     p = Ref(chain_params(m, keep))
     GC.@preserve m keep ccall((:gnx_chain_block_backward_narrow_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
 end
+# ---- the typed Chain entries (gnx_chain_block_forward_typed / _backward_typed): `narrow` selects the fp32 entry the call mirrors.  The shim's
+#      arrays are Float32, so it passes GNX_ELEM_F32 — then the call IS the mirrored entry (same workspace size, same bits); with bfloat16
+#      device buffers the same argument lists take GNX_ELEM_BF16 (include/gnx.h states the bf16 contracts). ----
+function chain_typed_device(m::ChainBlock, x; narrow::Bool=false)
+    g::GNGraphBatch = x.graphs
+    R = replicas(x.ef, x.nf, x.gf)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    nrw = Int32(narrow)
+    elem = GNX_ELEM_F32
+    oe, on, og = outwidth(m.edgefn), outwidth(m.nodefn), outwidth(m.graphfn)
+    ws = workspace!(g, (:chain_typed, chainkey(m), R, narrow)) do
+        ccall((:gnx_chain_block_forward_typed_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64, Int32, Int32), g.handle, p, R, elem, nrw)
+    end
+    o = (outarray(oe, nedges(g), R), outarray(on, nnodes(g), R), outarray(og, ngraphs(g), R))
+    GC.@preserve m keep x o ws check(ccall((:gnx_chain_block_forward_typed, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Int32, UInt32, Ptr{Cvoid}),
+        g.handle, p, elem, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, nrw, UInt32(0), STREAM[]))
+    (graphs=g, ef=o[1], nf=o[2], gf=o[3])
+end
+# would gnx_chain_block_forward_typed run its native bf16 path on this batch (narrow = true and every function that runs inside the narrow rule)
+const GNX_ELEM_BF16 = Int32(5)
+function chain_typed_applies(m::ChainBlock, x; narrow::Bool=true, elem::Int32=GNX_ELEM_BF16)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    GC.@preserve m keep ccall((:gnx_chain_block_forward_typed_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64, Int32, Int32),
+                              x.graphs.handle, p, replicas(x.ef, x.nf, x.gf), elem, Int32(narrow)) == 1
+end
+function chain_typed_pullback_device(m::ChainBlock, x, ȳ; narrow::Bool=false)
+    g::GNGraphBatch = x.graphs
+    R = replicas(x.ef, x.nf, x.gf)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    nrw = Int32(narrow)
+    elem = GNX_ELEM_F32
+    dins = (likeof(x.ef), likeof(x.nf), likeof(x.gf))
+    chains = (m.edgefn, m.nodefn, m.graphfn)
+    gs = [[gradslots(l) for l in c] for c in chains]
+    gW = [[q[1] for q in c] for c in gs]; gB = [[q[2] for q in c] for c in gs]
+    arrs = [[GnxDenseGrad(devptr(gW[t][i]), devptr(gB[t][i])) for i in eachindex(chains[t])] for t in 1:3]
+    gp(t) = isempty(arrs[t]) ? Ptr{GnxDenseGrad}(C_NULL) : pointer(arrs[t])
+    grads = Ref(GnxChainBlockGrads(gp(1), gp(2), gp(3)))
+    ws = workspace!(g, (:chain_backward_typed, chainkey(m), R, narrow)) do
+        ccall((:gnx_chain_block_backward_typed_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64, Int32, Int32), g.handle, p, R, elem, nrw)
+    end
+    GC.@preserve m keep x ȳ dins gW gB arrs ws check(ccall((:gnx_chain_block_backward_typed, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{GnxChainBlockGrads}, Ptr{Cvoid}, Csize_t, Int32, Ptr{Cvoid}),
+        g.handle, p, elem, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
+        devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, nrw, STREAM[]))
+    (ef=dins[1], nf=dins[2], gf=dins[3], params=[[(weight=gW[t][i], bias=gB[t][i]) for i in eachindex(chains[t])] for t in 1:3])
+end
 
 # ---- a chain of layers as ONE hipGraph inside libgnx (gnx_model_*): decoder(core(encoder(x))) of examples/sort/sort.jl:68-75.
 #      The model keeps its (device-resident) layers, its output arrays and — inside the library — every intermediate and workspace:
