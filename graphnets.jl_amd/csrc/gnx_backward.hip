@@ -1329,86 +1329,60 @@ int32_t gnx_core_backward_train_typed(const gnx_graphs* h, const gnx_core_params
 }  // extern "C"
 
 // ---- GNBlock with Chain update functions: backward ----
+// gnx_chain_block_backward and gnx_chain_block_backward_narrow are one body on one plan (ChainBwPlan; the layout and the fused mask:
+// gnx_chain_plan.h).  The mask is 0 for the former — with 0 every line below is the generic call.
 namespace {
-int chain_out(const gnx_chain& c) { return c.n_layers > 0 ? c.widths[c.n_layers - 1] : 0; }
-int chain_max(const gnx_chain& c) {
-  int m = 0;
-  for (int i = 0; i < c.n_layers; ++i) m = std::max(m, c.widths[i]);
-  return m;
-}
-gnx_block_params chain_edge_block(const gnx_chain_block_params* p) {  // the one-layer block that is the edge chain's first Dense
-  gnx_block_params b{};
-  b.de = p->de; b.dn = p->dn; b.dg = p->dg;
-  b.oe = p->edgefn.widths[0]; b.on = 0; b.og = 0;
-  b.edgefn = p->edgefn.layers[0];
-  return b;
-}
-struct ChainBwLayout {
-  size_t act[3][kChainMaxLayers + 1];  // stored layer outputs per chain (a fused chain: its last layer's, where a level above reads it)
-  size_t Xn, Xg, dXn, dXg, gbuf[3], blk_fw, blk_fw_bytes, blk_bw, blk_bw_bytes, part, wt, off2, ident, dxe, total;
+// What every Chain pullback entry receives.  The nine feature-shaped tensors hold `elem` elements.
+struct ChainBwCall {
+  const gnx_graphs* h; const gnx_chain_block_params* p; int32_t elem;
+  const void *ef, *nf, *gf, *g_ef_out, *g_nf_out, *g_gf_out; int64_t R; void *d_ef, *d_nf, *d_gf;
+  const gnx_chain_block_grads* grads; void* ws; size_t ws_bytes; void* stream;
 };
-// the functions gnx_chain_block_backward_narrow pulls back in one kernel each (bit 0 edge, 1 node, 2 graph: chain_bw_narrow_takes)
-unsigned chain_bw_narrow_mask(const gnx_graphs* h, const gnx_chain_block_params* p) {
-  const int oe = chain_out(p->edgefn), on = chain_out(p->nodefn);
-  unsigned m = 0;
-  if (chain_bw_narrow_takes(p->edgefn, p->de + 2 * p->dn + p->dg, (size_t)h->E)) m |= 1;
-  if (chain_bw_narrow_takes(p->nodefn, oe + p->dn + p->dg, (size_t)h->N)) m |= 2;
-  if (chain_bw_narrow_takes(p->graphfn, oe + on + p->dg, (size_t)h->G)) m |= 4;
-  return m;
-}
-// A generic graph function behind a fused node function: nf' is recomputed by the generic launches (Xn and every layer's output kept), so that the
-// graph function's input — and with it its parameter gradients — keeps gnx_chain_block_backward's bits.
-bool chain_bw_node_fw_generic(unsigned fused, int og) { return (fused & 2) && og > 0 && !(fused & 4); }
-// fused: the mask above — a fused function keeps no per-layer outputs, no delta buffers and (the edge function) no inner block workspaces; it
-// adds its partial rows and (the edge function) the compact [R E][2 dn + dg] input gradient.  fused = 0: the layout of gnx_chain_block_backward
-ChainBwLayout chain_bw_layout(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, size_t ident_floats, unsigned fused = 0) {
+
+// The pullback's plan: the common part and the layout.  A bf16 call is staged: fp32 copies of the six feature inputs and upstream gradients and of
+// the three input gradients behind the fp32 layout.  lay_out() runs once, behind the refusals that read the handle's counts alone.
+const char* const kBwQuery[3] = {"workspace missing or smaller than gnx_chain_block_backward_workspace_bytes()", "workspace missing or smaller than gnx_chain_block_backward_narrow_workspace_bytes()",
+                                 "workspace missing or smaller than gnx_chain_block_backward_typed_workspace_bytes()"};
+struct ChainBwPlan : ChainPlan {
   ChainBwLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t floats) { const size_t at = o; o += align_up(floats * sizeof(float), 256); return at; };
-  const gnx_chain* ch[3] = {&p->edgefn, &p->nodefn, &p->graphfn};
-  const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
-  const size_t trows[3] = {(size_t)h->E, (size_t)h->N, (size_t)h->G};
-  const int oe = chain_out(p->edgefn), on = chain_out(p->nodefn), og = chain_out(p->graphfn);
-  const int Kn = oe + p->dn + p->dg, Kg = oe + on + p->dg;
-  const int k0[3] = {p->de + 2 * p->dn + p->dg, Kn, Kg};
-  size_t gmax = 1, pmax = 2048 * 4, wmax = 1;
-  for (int t = 0; t < 3; ++t) {
-    if (fused & (1u << t)) {
-      const bool crosses = t == 0 ? on > 0 || og > 0 : t == 1 && og > 0;  // ef' feeds the node / graph inputs, nf' the graph input
-      if (t == 1 && chain_bw_node_fw_generic(fused, og)) {
-        for (int i = 0; i < ch[t]->n_layers; ++i) L.act[t][i] = take(rows[t] * (size_t)ch[t]->widths[i]);
-      } else if (crosses) L.act[t][ch[t]->n_layers - 1] = take(rows[t] * (size_t)chain_out(*ch[t]));
-      const ChainBwNarrowShape sh = chain_bw_narrow_shape(*ch[t], k0[t], trows[t]);
-      pmax = std::max(pmax, (size_t)sh.P * sh.nwg * (size_t)R);
-      continue;
-    }
-    for (int i = 0; i < ch[t]->n_layers; ++i) {
-      L.act[t][i] = take(rows[t] * (size_t)ch[t]->widths[i]);
-      const int J = ch[t]->widths[i], K = i > 0 ? ch[t]->widths[i - 1] : k0[t];
-      const size_t chunks = (rows[t] + BW_CH - 1) / BW_CH;
-      pmax = std::max({pmax, chunks * (size_t)J * (K + 1), (size_t)2048 * J, dw_mfma_partial_floats(rows[t], J, K)});
-      wmax = std::max(wmax, (size_t)J * K);
-    }
-    gmax = std::max(gmax, rows[t] * (size_t)chain_max(*ch[t]));
+  ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow) : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery) {}
+  void lay_out(const gnx_graphs* h) {
+    if (rc || total) return;
+    const bool blk = !(fused & 1) && sh.ch[0]->n_layers > 0;  // the first Dense of a generic edge function: the one-layer block, forward and pullback
+    L = chain_bw_layout(sh, fused, lnf.ident_floats(), blk ? gnx_block_workspace_bytes(h, &sh.edge_block, sh.R) : 0,
+                        blk ? gnx_block_backward_workspace_bytes(h, &sh.edge_block, sh.R) : 0, BW_CH, dw_mfma_partial_floats);
+    const int d[9] = {sh.de, sh.dn, sh.dg, sh.ow[0], sh.ow[1], sh.ow[2], sh.de, sh.dn, sh.dg};
+    sized(L.total, stage_features(L.total, h, sh.R, d, 9));
   }
-  pmax = std::max(pmax, std::max((size_t)R * h->G * 256, (size_t)2048) * (size_t)std::max({p->dg, oe, 1}));  // column-sum slices
-  L.Xn = take(on > 0 && (!(fused & 2) || chain_bw_node_fw_generic(fused, og)) ? rows[1] * Kn : 0); L.dXn = take(on > 0 ? rows[1] * Kn : 0);
-  L.Xg = take(og > 0 ? rows[2] * Kg : 0); L.dXg = take(og > 0 ? rows[2] * Kg : 0);
-  const bool all_fused = (oe == 0 || (fused & 1)) && (on == 0 || (fused & 2)) && (og == 0 || (fused & 4)) && fused != 0;
-  for (int i = 0; i < 3; ++i) L.gbuf[i] = take(all_fused ? 0 : gmax);
-  if (!(fused & 1)) {
-    const gnx_block_params b = chain_edge_block(p);
-    L.blk_fw_bytes = gnx_block_workspace_bytes(h, &b, R);
-    L.blk_fw = o; o += align_up(L.blk_fw_bytes, 256);
-    L.blk_bw_bytes = gnx_block_backward_workspace_bytes(h, &b, R);
-    L.blk_bw = o; o += align_up(L.blk_bw_bytes, 256);
-  }
-  L.part = take(pmax); L.wt = take(wmax); L.off2 = take(16);
-  L.ident = take(ident_floats);  // the identity layer of a LayerNorm-first edge function (gnx_internal.h: ChainLnFirst)
-  L.dxe = take((fused & 1) ? rows[0] * (size_t)(2 * p->dn + p->dg) : 0);
-  L.total = o + 256;
-  return L;
-}
+};
+
+// What the pieces of the fp32 pullback share, and the pieces: the call's fp32 tensors, the plan and its widths, the plan's carves as pointers.
+struct ChainBwCtx {
+  const gnx_graphs* h; const ChainBwPlan& pl; const gnx_chain_block_params* p;  // p: pl.p
+  const gnx_chain_block_grads* grads;  // behind the LayerNorm-first rewrite
+  const float *ef, *nf, *gf, *g_ef_out, *g_nf_out, *g_gf_out;
+  float *d_ef, *d_nf, *d_gf;
+  int64_t R; void* stream; hipStream_t s; char* base;
+  int de, dn, dg, oe, on, og, Kn, Kg, E, N, G;
+  unsigned Ru, fused;
+  float *Xn, *Xg, *dXn, *dXg, *part, *wt, *gb[3];
+  int* off2;
+  const float *ef_out, *nf_out;  // the recomputed ef', nf' (nullptr without output)
+  float* F(const ChainCarve& c) const { return reinterpret_cast<float*>(base + c.off); }
+  float* A(int t, int i) const { return F(pl.L.act[t][i]); }  // the stored output of layer i of chain t
+  const gnx_chain& ch(int t) const { return *pl.sh.ch[t]; }
+  const gnx_dense_grad* gfn(int t) const { return !grads ? nullptr : (t == 0 ? grads->edgefn : t == 1 ? grads->nodefn : grads->graphfn); }
+  gnx_dense_grad grad_of(int t, int i) const { return gfn(t) ? gfn(t)[i] : gnx_dense_grad{nullptr, nullptr}; }
+  int32_t recompute();
+  void delta_rows(int t, int i, float* buf, const float* Ain, int K);
+  int32_t zero_layer_grads(int t, int i, int K);
+  int32_t pull_layers(int t, int first, float* cur, float* other, const float* X0, int K0, float* g_first, float** result);
+  void last_delta(int t, const float* upstream, float* out, const float* X0, int K0, int act_override);
+  int32_t fused_level(int t, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2, ChainBwNarrowIo io, const char* name);
+  int32_t edge_fused(), edge_generic(), shares();
+};
+
+dim3 chain_blocks(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // the parameter-gradient finish of a fused function: one k_bw_dw_final per layer over the kernel's partial rows (a LayerNorm as J = width, K = 1)
 int32_t chain_bw_narrow_finals(const gnx_chain& c, int k_in, const ChainBwNarrowShape& sh, int64_t R, const float* part, const gnx_dense_grad* grads, hipStream_t s) {
@@ -1431,297 +1405,293 @@ bool chain_wants_grads(const gnx_chain& c, const gnx_dense_grad* grads) {
   return false;
 }
 
-// validated params (check_params of gnx_chain.cpp), replicas and an edge output: what both queries and `_applies` need before a layout exists
-bool chain_bw_valid(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R) { return h && p0 && chain_check_params(h, p0, R) == GNX_OK; }
-}  // namespace
-
-namespace {
-// gnx_chain_block_backward (narrow = false) and gnx_chain_block_backward_narrow: one body.  `fused` is chain_bw_narrow_mask for the latter and 0
-// for the former — with 0 every line below is the generic call.
-size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, bool narrow) {
-  if (!narrow) {
-    if (!h || !p0 || R <= 0 || gnx_chain_block_workspace_bytes(h, p0, R) == 0) return 0;  // (the forward's query validates the chains)
-  } else if (!chain_bw_valid(h, p0, R)) return 0;
-  const unsigned fused = narrow ? chain_bw_narrow_mask(h, p0) : 0;
-  if (narrow) {  // a level that stays generic reads the tables the generic query builds through the forward's query: build them here as well
-    const bool generic_level = (chain_out(p0->edgefn) > 0 && !(fused & 1)) || (chain_out(p0->nodefn) > 0 && !(fused & 2)) || (chain_out(p0->graphfn) > 0 && !(fused & 4));
-    if (generic_level && gnx_chain_block_workspace_bytes(h, p0, R) == 0) return 0;
-  }
-  if (fused) {  // what the fused levels read of the handle, built here, outside any capture
-    (void)gnx_ensure_wide_tables(h);
-    (void)gnx_ensure_csr(h);
-  }
-  ChainLnFirst lnf;
-  const gnx_chain_block_params* p = (fused & 1) ? p0 : lnf.init(p0, nullptr);  // (a fused edge function has its input row in registers: no identity layer)
-  return chain_bw_layout(h, p, R, lnf.ident_floats(), fused).total;
-}
-
-int32_t chain_backward(const gnx_graphs* h, const gnx_chain_block_params* p0, const float* ef, const float* nf, const float* gf,
-                       const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
-                       float* d_gf, const gnx_chain_block_grads* grads0, void* ws, size_t ws_bytes, void* stream, bool narrow) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h || !p0) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  if (!narrow) { if (gnx_chain_block_workspace_bytes(h, p0, R) == 0) return GNX_ERR_DIMS; }  // gnx_last_error() holds the reason
-  else if (chain_check_params(h, p0, R) != GNX_OK) return GNX_ERR_DIMS;
-  const unsigned fused = narrow ? chain_bw_narrow_mask(h, p0) : 0;
-  ChainLnFirst lnf;  // a LayerNorm as the (generic) edge function's first layer: behind an identity Dense (its gradient slot is empty)
-  const gnx_chain_block_params* p = (fused & 1) ? p0 : lnf.init(p0, nullptr);
-  const gnx_chain_block_grads* grads = (fused & 1) ? grads0 : lnf.init_grads(grads0);
-  bool chain_wide = p->de > 32 || p->dn > 32 || p->dg > 32;
-  for (const gnx_chain* c : {&p->edgefn, &p->nodefn, &p->graphfn})
-    for (int i = 0; i < c->n_layers; ++i) chain_wide = chain_wide || (c->widths && c->widths[i] > 32);
-  DeviceTurn turn(s, chain_wide);
-  const gnx_chain* ch[3] = {&p->edgefn, &p->nodefn, &p->graphfn};
-  const int de = p->de, dn = p->dn, dg = p->dg;
-  const int oe = chain_out(p->edgefn), on = chain_out(p->nodefn), og = chain_out(p->graphfn);
-  if ((de > 0 && !ef && h->E > 0) || (dn > 0 && !nf) || (dg > 0 && !gf)) return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL");
-  if (oe == 0) return fail(GNX_ERR_DIMS, "chain backward: not implemented for an edge function without output (the forward takes it; train such a block with one-layer update functions)");
-  const ChainBwLayout L = chain_bw_layout(h, p, R, lnf.ident_floats(), fused);
-  if (int32_t rcc = check_ws(ws, ws_bytes, L.total, narrow ? "workspace missing or smaller than gnx_chain_block_backward_narrow_workspace_bytes()"
-                                                            : "workspace missing or smaller than gnx_chain_block_backward_workspace_bytes()")) return rcc;
-  if (int32_t rcw = gnx_ensure_wide_tables(h, stream)) return rcw;
-  if (fused & 1) { if (int32_t rcs = gnx_ensure_csr(h)) return rcs; }  // (k_bw_dnf's out-edge view; the query built it)
-  char* base = static_cast<char*>(ws);
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
-  if (lnf.on) {
-    lnf.layers[0].weight = F(L.ident);
-    if (int32_t rci = lnf.fill(F(L.ident), s)) return rci;
-  }
-  const int E = (int)h->E, N = (int)h->N, G = (int)h->G;
-  const size_t rows[3] = {(size_t)R * h->E, (size_t)R * h->N, (size_t)R * h->G};
-  const int trow[3] = {E, N, G};
-  const int Kn = oe + dn + dg, Kg = oe + on + dg;
-  const unsigned Ru = (unsigned)R;
-  auto blocks = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
-  float *Xn = F(L.Xn), *Xg = F(L.Xg), *dXn = F(L.dXn), *dXg = F(L.dXg), *part = F(L.part), *wt = F(L.wt);
-  int* off2 = reinterpret_cast<int*>(base + L.off2);
-  const gnx_dense_grad no_grad{nullptr, nullptr};
-  auto grad_of = [&](int t, int i) -> const gnx_dense_grad& {
-    const gnx_dense_grad* a = !grads ? nullptr : (t == 0 ? grads->edgefn : t == 1 ? grads->nodefn : grads->graphfn);
-    return a ? a[i] : no_grad;
-  };
-  auto A = [&](int t, int i) { return F(L.act[t][i]); };
-  const gnx_block_params b1 = chain_edge_block(p);
-  const gnx_dense_grad* gfn[3] = {grads ? grads->edgefn : nullptr, grads ? grads->nodefn : nullptr, grads ? grads->graphfn : nullptr};
-  const int k0[3] = {de + 2 * dn + dg, Kn, Kg};
-  // the pullback of a fused function: one kernel (under `name`), then one finisher per layer whose gradient is wanted
-  auto fused_level = [&](int t, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2, ChainBwNarrowIo io, const char* name) -> int32_t {
-    const bool want = chain_wants_grads(*ch[t], gfn[t]);
-    io.part = want ? part : nullptr;
-    { ProfScope ps(name, s);
-      if (int32_t r2 = launch_chain_bw_narrow(h, t, *ch[t], in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
-    return want ? chain_bw_narrow_finals(*ch[t], k0[t], chain_bw_narrow_shape(*ch[t], k0[t], (size_t)trow[t]), R, part, gfn[t], s) : GNX_OK;
-  };
+// ---- forward again: a generic function keeps every layer's output (gnx_chain_block_forward's sequence); a fused one only its last layer's,
+//      and only where a level above reads it ----
+int32_t ChainBwCtx::recompute() {
+  const gnx_chain &ce = ch(0), &cn = ch(1), &cg = ch(2);
   int32_t rc;
-
-  // ---- forward again: a generic function keeps every layer's output (gnx_chain_block_forward's sequence); a fused one only its last layer's,
-  //      and only where a level above reads it ----
   if (fused & 1) {
-    if ((on > 0 || og > 0) && (rc = launch_chain_narrow(h, 0, *ch[0], ef, de, nf, dn, gf, dg, A(0, ch[0]->n_layers - 1), R, s, "bw_chain_fw_e"))) return rc;
-  } else if (E > 0) {
-    if ((rc = gnx_block_forward(h, &b1, ef, nf, gf, R, A(0, 0), nullptr, nullptr, base + L.blk_fw, L.blk_fw_bytes, 0, stream))) return rc;
-    for (int i = 1; i < ch[0]->n_layers; ++i)
-      if ((rc = launch_chain_layer(h, 0, ch[0]->layers[i], A(0, i - 1), ch[0]->widths[i - 1], ch[0]->widths[i], A(0, i), R, s, "bw_chain_fw_e"))) return rc;
+    if ((on > 0 || og > 0) && (rc = launch_chain_narrow(h, 0, ce, ef, de, nf, dn, gf, dg, A(0, ce.n_layers - 1), R, s, "bw_chain_fw_e"))) return rc;
+  } else if (h->E > 0) {
+    if ((rc = gnx_block_forward(h, &pl.sh.edge_block, ef, nf, gf, R, A(0, 0), nullptr, nullptr, base + pl.L.blk_fw.off, pl.L.blk_fw.bytes, 0, stream))) return rc;
+    for (int i = 1; i < ce.n_layers; ++i)
+      if ((rc = launch_chain_layer(h, 0, ce.layers[i], A(0, i - 1), ce.widths[i - 1], ce.widths[i], A(0, i), R, s, "bw_chain_fw_e"))) return rc;
   }
-  const float* ef_out = A(0, ch[0]->n_layers - 1);
-  const float* nf_out = on > 0 ? A(1, ch[1]->n_layers - 1) : nullptr;
+  ef_out = A(0, ce.n_layers - 1);
+  nf_out = on > 0 ? A(1, cn.n_layers - 1) : nullptr;
   if ((fused & 2) && !chain_bw_node_fw_generic(fused, og)) {
-    if (og > 0 && (rc = launch_chain_narrow(h, 1, *ch[1], ef_out, oe, nf, dn, gf, dg, A(1, ch[1]->n_layers - 1), R, s, "bw_chain_fw_n"))) return rc;
+    if (og > 0 && (rc = launch_chain_narrow(h, 1, cn, ef_out, oe, nf, dn, gf, dg, A(1, cn.n_layers - 1), R, s, "bw_chain_fw_n"))) return rc;
   } else if (on > 0) {
     if ((rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s))) return rc;
-    for (int i = 0; i < ch[1]->n_layers; ++i)
-      if ((rc = launch_chain_layer(h, 1, ch[1]->layers[i], i ? A(1, i - 1) : Xn, i ? ch[1]->widths[i - 1] : Kn, ch[1]->widths[i], A(1, i), R, s, "bw_chain_fw_n"))) return rc;
+    for (int i = 0; i < cn.n_layers; ++i)
+      if ((rc = launch_chain_layer(h, 1, cn.layers[i], i ? A(1, i - 1) : Xn, i ? cn.widths[i - 1] : Kn, cn.widths[i], A(1, i), R, s, "bw_chain_fw_n"))) return rc;
   }
   if (og > 0) {
     if ((rc = launch_fn_input(h, 2, ef_out, oe, nf_out, on, gf, dg, R, Xg, s))) return rc;
-    for (int i = 0; i < ch[2]->n_layers && !(fused & 4); ++i)
-      if ((rc = launch_chain_layer(h, 2, ch[2]->layers[i], i ? A(2, i - 1) : Xg, i ? ch[2]->widths[i - 1] : Kg, ch[2]->widths[i], A(2, i), R, s, "bw_chain_fw_g"))) return rc;
+    for (int i = 0; i < cg.n_layers && !(fused & 4); ++i)
+      if ((rc = launch_chain_layer(h, 2, cg.layers[i], i ? A(2, i - 1) : Xg, i ? cg.widths[i - 1] : Kg, cg.widths[i], A(2, i), R, s, "bw_chain_fw_g"))) return rc;
   }
+  return GNX_OK;
+}
 
-  // ---- row-wise pullback of layers [first, n) of chain t.  `cur` holds delta of the LAST layer on entry; on exit `*g_first` (rows x K_first)
-  //      holds the gradient w.r.t. the input of layer `first` ----
-  float* gb[3] = {F(L.gbuf[0]), F(L.gbuf[1]), F(L.gbuf[2])};
-  auto delta_rows = [&](int t, int i, float* buf, const float* Ain, int K) {  // buf <- buf .* act'(layer i), all R*T rows, no extras
-    const gnx_dense& d = ch[t]->layers[i];
-    const int J = ch[t]->widths[i];
-    const float* outp = A(t, i);
-    if (d.act == GNX_ACT_GELU) {
-      ProfScope ps("bw_gelu_preact", s);
-      GNX_LAUNCH(k_fw_dense, blocks(rows[t] * J), dim3(256), 0, s, Ain, d.weight, d.bias, rows[t], K, J, GNX_ACT_IDENTITY, gb[2]);
-      outp = gb[2];
-    }
-    DeltaArgs a{buf, outp, buf, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, J, (int)rows[t], 1, d.act, 0};
-    ProfScope ps("bw_delta", s);
-    launch_delta(a, 0, 0, 1, s);
-  };
-  // an entity without rows (a batch without edges): its layers' parameter gradients are sums over nothing — zeros, not what the buffers held
-  auto zero_layer_grads = [&](int t, int i, int K) -> int32_t {
-    const gnx_dense_grad& gz = grad_of(t, i);
-    const int J = ch[t]->widths[i];
-    if (gz.weight && J > 0) GNX_HIP(hipMemsetAsync(gz.weight, 0, sizeof(float) * (chain_layer_is_ln(ch[t]->layers[i]) ? (size_t)J : (size_t)J * K), s));
-    if (gz.bias && J > 0) GNX_HIP(hipMemsetAsync(gz.bias, 0, sizeof(float) * (size_t)J, s));
-    return GNX_OK;
-  };
-  auto pull_layers = [&](int t, int first, float* cur, float* other, const float* X0, int K0, float* g_first, float** result) -> int32_t {
-    for (int i = ch[t]->n_layers - 1; i >= first; --i) {
-      const int J = ch[t]->widths[i], K = i > 0 ? ch[t]->widths[i - 1] : K0;
-      const float* Ain = i > 0 ? A(t, i - 1) : X0;
-      float* gin = i == first && g_first ? g_first : other;
-      if (i == first && result) *result = gin;
-      const gnx_dense& d = ch[t]->layers[i];
-      if (rows[t] == 0 && J > 0) { if (int32_t rz = zero_layer_grads(t, i, K)) return rz; }
-      if (rows[t] == 0 || J == 0) continue;
-      int32_t r2;
-      if (chain_layer_is_ln(d)) {
-        // a LayerNorm layer value: dx through the normalisation (k_ln_backward with one norm), dgamma = column sums of dy . xhat, dbeta = of dy
-        float* t1 = gb[2];  // (free here: the gelu pre-activation buffer of delta_rows / last_delta is consumed inside those calls)
-        { ProfScope ps("bw_layernorm", s);
-          GNX_LAUNCH(k_ln_backward<false>, dim3((unsigned)((rows[t] + 3) / 4)), dim3(256), 0, s, Ain, rows[t], J, d.weight, d.weight, cur, (const float*)nullptr, (const float*)nullptr,
-                     kChainLnEps, chain_layer_ln_mode(d), gin, t1, (float*)nullptr); }
-        GNX_LAUNCH(k_set_off2, dim3(1), dim3(1), 0, s, off2, (int)rows[t]);
-        if ((r2 = colsum_all(t1, rows[t], J, grad_of(t, i).weight, part, off2, s))) return r2;
-        if ((r2 = colsum_all(cur, rows[t], J, grad_of(t, i).bias, part, off2, s))) return r2;
-      } else
-      if (bw_use_mfma(rows[t], J, K)) {
-        if (gin && K > 0 && (r2 = dx_mfma(h, t, cur, d.weight, J, K, 0, K, gin, R, wt, true, s, "bw_dx_chain"))) return r2;
-        if ((r2 = dw_auto(cur, Ain, rows[t], J, K, grad_of(t, i), part, off2, s))) return r2;
-      } else {
-        if (gin && K > 0) launch_bw_dx(dim3(blocks(rows[t] * K).x, 1), s, cur, d.weight, (int)rows[t], J, K, gin, 0, 0, (float*)nullptr, 0);
-        if ((r2 = dw_reduce(cur, Ain, rows[t], J, K, grad_of(t, i), part, s))) return r2;
-      }
-      if (i > first) {  // delta of layer i-1 from the gradient w.r.t. its output
-        delta_rows(t, i - 1, gin, i - 1 > 0 ? A(t, i - 2) : X0, i - 1 > 0 ? ch[t]->widths[i - 2] : K0);
-        std::swap(cur, other);
-      }
-    }
-    return GNX_OK;
-  };
-  // delta of a chain's LAST layer: (upstream + the shares of the levels above) .* act'   [kind 0 graphs / 1 nodes / 2 edges]
-  auto last_delta = [&](int t, const float* upstream, float* out, const float* X0, int K0, int act_override) {
-    const int li = ch[t]->n_layers - 1, J = ch[t]->widths[li];
-    const gnx_dense& d = ch[t]->layers[li];
-    const int act = act_override >= 0 ? act_override : d.act;
-    const float* outp = A(t, li);
-    if (act == GNX_ACT_GELU) {
-      const float* Ain = li > 0 ? A(t, li - 1) : X0;
-      const int K = li > 0 ? ch[t]->widths[li - 1] : K0;
-      ProfScope ps("bw_gelu_preact", s);
-      GNX_LAUNCH(k_fw_dense, blocks(rows[t] * J), dim3(256), 0, s, Ain, d.weight, d.bias, rows[t], K, J, GNX_ACT_IDENTITY, gb[2]);
-      outp = gb[2];
-    }
-    DeltaArgs a{upstream, outp, out, t >= 1 && og > 0 ? dXg : nullptr, Kg, t == 1 ? oe : 0, t == 0 && on > 0 ? dXn : nullptr, Kn, 0,
-                t == 1 ? h->d_node_off : h->d_edge_off, h->d_edge_dst, J, trow[t], G, act, t == 2 ? 0 : (t == 1 ? 1 : 2)};
-    if (t == 0) { a.ex1 = og > 0 ? dXg : nullptr; a.ex1_off = 0; }
-    ProfScope ps("bw_delta", s);
-    launch_delta(a, (size_t)G * Kg, (size_t)N * Kn, Ru, s);
-  };
+// buf <- buf .* act'(layer i of chain t), all R*T rows, no extras.  Ain [rows][K]: the layer's input (a gelu level differentiates from its
+// pre-activation, recomputed into gb[2])
+void ChainBwCtx::delta_rows(int t, int i, float* buf, const float* Ain, int K) {
+  const gnx_dense& d = ch(t).layers[i];
+  const int J = ch(t).widths[i];
+  const float* outp = A(t, i);
+  if (d.act == GNX_ACT_GELU) {
+    ProfScope ps("bw_gelu_preact", s);
+    GNX_LAUNCH(k_fw_dense, chain_blocks(pl.sh.rows[t] * J), dim3(256), 0, s, Ain, d.weight, d.bias, pl.sh.rows[t], K, J, GNX_ACT_IDENTITY, gb[2]);
+    outp = gb[2];
+  }
+  DeltaArgs a{buf, outp, buf, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, J, (int)pl.sh.rows[t], 1, d.act, 0};
+  ProfScope ps("bw_delta", s);
+  launch_delta(a, 0, 0, 1, s);
+}
 
-  // ---- graph chain ----
-  if (fused & 4) {
-    if ((rc = fused_level(2, Xg, Kg, nullptr, 0, nullptr, 0, ChainBwNarrowIo{g_gf_out, nullptr, 0, 0, nullptr, 0, dXg, 0, nullptr, nullptr}, "bw_delta"))) return rc;
-  } else if (og > 0) {
-    last_delta(2, g_gf_out, gb[0], Xg, Kg, -1);
-    if ((rc = pull_layers(2, 0, gb[0], gb[1], Xg, Kg, dXg, nullptr))) return rc;
-  }
-  // ---- node chain: upstream + dXg[graph of the node][oe : oe+on] ----
-  if (fused & 2) {
-    if ((rc = fused_level(1, ef_out, oe, nf, dn, gf, dg, ChainBwNarrowIo{g_nf_out, og > 0 ? dXg : nullptr, Kg, oe, nullptr, 0, dXn, 0, nullptr, nullptr}, "bw_delta"))) return rc;
-  } else if (on > 0) {
-    last_delta(1, g_nf_out, gb[0], Xn, Kn, -1);
-    if ((rc = pull_layers(1, 0, gb[0], gb[1], Xn, Kn, dXn, nullptr))) return rc;
-  }
-  // ---- edge chain: upstream + dXg[graph][0:oe] + dXn[dst][0:oe] ----
-  if (fused & 1) {
-    // one kernel: d_ef directly, the node / graph columns of the input gradient into dXe_c [R E][2 dn + dg]; then k_bw_dnf and the per-graph
-    // column sums, exactly as after the fused edge level of block_backward_t
-    const bool need_cols = (d_nf && dn > 0) || (d_gf && dg > 0);
-    float* dXe = F(L.dxe);
-    const int ldc = 2 * dn + dg;
-    if ((rc = fused_level(0, ef, de, nf, dn, gf, dg, ChainBwNarrowIo{g_ef_out, og > 0 ? dXg : nullptr, Kg, 0, on > 0 ? dXn : nullptr, Kn, need_cols ? dXe : nullptr, de,
-                                                                      d_ef && de > 0 ? d_ef : nullptr, nullptr}, "bw_delta_edge"))) return rc;
-    if (d_nf && dn > 0) {
-      ProfScope ps("bw_dnf", s);
-      GNX_LAUNCH(k_bw_dnf<false>, dim3(blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr, h->d_csr_ptr,
-                 h->d_csr_eid, N, E, dn, d_nf);
+// an entity without rows (a batch without edges): its layers' parameter gradients are sums over nothing — zeros, not what the buffers held
+int32_t ChainBwCtx::zero_layer_grads(int t, int i, int K) {
+  const gnx_dense_grad gz = grad_of(t, i);
+  const int J = ch(t).widths[i];
+  if (gz.weight && J > 0) GNX_HIP(hipMemsetAsync(gz.weight, 0, sizeof(float) * (chain_layer_is_ln(ch(t).layers[i]) ? (size_t)J : (size_t)J * K), s));
+  if (gz.bias && J > 0) GNX_HIP(hipMemsetAsync(gz.bias, 0, sizeof(float) * (size_t)J, s));
+  return GNX_OK;
+}
+
+// ---- row-wise pullback of layers [first, n) of chain t.  `cur` holds delta of the LAST layer on entry; on exit `*g_first` (rows x K_first)
+//      holds the gradient w.r.t. the input of layer `first` ----
+int32_t ChainBwCtx::pull_layers(int t, int first, float* cur, float* other, const float* X0, int K0, float* g_first, float** result) {
+  const gnx_chain& c = ch(t);
+  const size_t rows = pl.sh.rows[t];
+  for (int i = c.n_layers - 1; i >= first; --i) {
+    const int J = c.widths[i], K = i > 0 ? c.widths[i - 1] : K0;
+    const float* Ain = i > 0 ? A(t, i - 1) : X0;
+    float* gin = i == first && g_first ? g_first : other;
+    if (i == first && result) *result = gin;
+    const gnx_dense& d = c.layers[i];
+    if (rows == 0 && J > 0) { if (int32_t rz = zero_layer_grads(t, i, K)) return rz; }
+    if (rows == 0 || J == 0) continue;
+    int32_t r2;
+    if (chain_layer_is_ln(d)) {
+      // a LayerNorm layer value: dx through the normalisation (k_ln_backward with one norm), dgamma = column sums of dy . xhat, dbeta = of dy
+      float* t1 = gb[2];  // (free here: the gelu pre-activation buffer of delta_rows / last_delta is consumed inside those calls)
+      { ProfScope ps("bw_layernorm", s);
+        GNX_LAUNCH(k_ln_backward<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, Ain, rows, J, d.weight, d.weight, cur, (const float*)nullptr, (const float*)nullptr,
+                   kChainLnEps, chain_layer_ln_mode(d), gin, t1, (float*)nullptr); }
+      GNX_LAUNCH(k_set_off2, dim3(1), dim3(1), 0, s, off2, (int)rows);
+      if ((r2 = colsum_all(t1, rows, J, grad_of(t, i).weight, part, off2, s))) return r2;
+      if ((r2 = colsum_all(cur, rows, J, grad_of(t, i).bias, part, off2, s))) return r2;
+    } else if (bw_use_mfma(rows, J, K)) {
+      if (gin && K > 0 && (r2 = dx_mfma(h, t, cur, d.weight, J, K, 0, K, gin, R, wt, true, s, "bw_dx_chain"))) return r2;
+      if ((r2 = dw_auto(cur, Ain, rows, J, K, grad_of(t, i), part, off2, s))) return r2;
+    } else {
+      if (gin && K > 0) launch_bw_dx(dim3(chain_blocks(rows * K).x, 1), s, cur, d.weight, (int)rows, J, K, gin, 0, 0, (float*)nullptr, 0);
+      if ((r2 = dw_reduce(cur, Ain, rows, J, K, grad_of(t, i), part, s))) return r2;
     }
-    if (d_gf && dg > 0) {
-      ProfScope ps("bw_dgf", s);
-      int64_t me = 1;
-      for (int64_t g = 0; g < h->G; ++g) me = std::max(me, h->h_edge_off[g + 1] - h->h_edge_off[g]);
-      GNX_LAUNCH(k_bw_dgf_init, blocks((size_t)R * G * dg), dim3(256), 0, s, (const float*)nullptr, Kg, oe + on, (int)(R * G), dg, d_gf);
-      colsum_graphs(dXe, false, dg, ldc, 2 * dn, E, h->d_edge_off, me, G, Ru, part, d_gf, dg, 0, 1, s);
+    if (i > first) {  // delta of layer i-1 from the gradient w.r.t. its output
+      delta_rows(t, i - 1, gin, i - 1 > 0 ? A(t, i - 2) : X0, i - 1 > 0 ? c.widths[i - 2] : K0);
+      std::swap(cur, other);
     }
-  } else {
-  // tail layers row-wise, the first layer through the block pullback
+  }
+  return GNX_OK;
+}
+
+// delta of a chain's LAST layer: (upstream + the shares of the levels above) .* act'   [kind 0 graphs / 1 nodes / 2 edges]
+void ChainBwCtx::last_delta(int t, const float* upstream, float* out, const float* X0, int K0, int act_override) {
+  const gnx_chain& c = ch(t);
+  const int li = c.n_layers - 1, J = c.widths[li];
+  const gnx_dense& d = c.layers[li];
+  const int act = act_override >= 0 ? act_override : d.act;
+  const float* outp = A(t, li);
+  if (act == GNX_ACT_GELU) {
+    const float* Ain = li > 0 ? A(t, li - 1) : X0;
+    const int K = li > 0 ? c.widths[li - 1] : K0;
+    ProfScope ps("bw_gelu_preact", s);
+    GNX_LAUNCH(k_fw_dense, chain_blocks(pl.sh.rows[t] * J), dim3(256), 0, s, Ain, d.weight, d.bias, pl.sh.rows[t], K, J, GNX_ACT_IDENTITY, gb[2]);
+    outp = gb[2];
+  }
+  DeltaArgs a{upstream, outp, out, t >= 1 && og > 0 ? dXg : nullptr, Kg, t == 1 ? oe : 0, t == 0 && on > 0 ? dXn : nullptr, Kn, 0,
+              t == 1 ? h->d_node_off : h->d_edge_off, h->d_edge_dst, J, (int)pl.sh.trows[t], G, act, t == 2 ? 0 : (t == 1 ? 1 : 2)};
+  if (t == 0) { a.ex1 = og > 0 ? dXg : nullptr; a.ex1_off = 0; }
+  ProfScope ps("bw_delta", s);
+  launch_delta(a, (size_t)G * Kg, (size_t)h->N * Kn, (unsigned)R, s);
+}
+
+// the pullback of a fused function: one kernel (under `name`), then one finisher per layer whose gradient is wanted
+int32_t ChainBwCtx::fused_level(int t, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2, ChainBwNarrowIo io, const char* name) {
+  const gnx_chain& c = ch(t);
+  const bool want = chain_wants_grads(c, gfn(t));
+  io.part = want ? part : nullptr;
+  { ProfScope ps(name, s);
+    if (int32_t r2 = launch_chain_bw_narrow(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
+  return want ? chain_bw_narrow_finals(c, pl.sh.k0[t], chain_bw_narrow_shape(c, pl.sh.k0[t], pl.sh.trows[t]), R, part, gfn(t), s) : GNX_OK;
+}
+
+// ---- edge chain, fused: upstream + dXg[graph][0:oe] + dXn[dst][0:oe] in one kernel — d_ef directly, the node / graph columns of the input
+//      gradient into dXe_c [R E][2 dn + dg]; then k_bw_dnf and the per-graph column sums, exactly as after the fused edge level of block_backward_t ----
+int32_t ChainBwCtx::edge_fused() {
+  const bool need_cols = (d_nf && dn > 0) || (d_gf && dg > 0);
+  float* dXe = F(pl.L.dxe);
+  const int ldc = 2 * dn + dg;
+  if (int32_t rc = fused_level(0, ef, de, nf, dn, gf, dg, ChainBwNarrowIo{g_ef_out, og > 0 ? dXg : nullptr, Kg, 0, on > 0 ? dXn : nullptr, Kn,
+                                                                                           need_cols ? dXe : nullptr, de, d_ef && de > 0 ? d_ef : nullptr, nullptr}, "bw_delta_edge")) return rc;
+  if (d_nf && dn > 0) {
+    ProfScope ps("bw_dnf", s);
+    GNX_LAUNCH(k_bw_dnf<false>, dim3(chain_blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr, h->d_csr_ptr,
+               h->d_csr_eid, N, E, dn, d_nf);
+  }
+  if (d_gf && dg > 0) {
+    ProfScope ps("bw_dgf", s);
+    int64_t me = 1;
+    for (int64_t g = 0; g < h->G; ++g) me = std::max(me, h->h_edge_off[g + 1] - h->h_edge_off[g]);
+    GNX_LAUNCH(k_bw_dgf_init, chain_blocks((size_t)R * G * dg), dim3(256), 0, s, (const float*)nullptr, Kg, oe + on, (int)(R * G), dg, d_gf);
+    colsum_graphs(dXe, false, dg, ldc, 2 * dn, E, h->d_edge_off, me, G, Ru, part, d_gf, dg, 0, 1, s);
+  }
+  return GNX_OK;
+}
+
+// ---- edge chain, generic: tail layers row-wise, the first layer through the block pullback ----
+int32_t ChainBwCtx::edge_generic() {
+  const gnx_chain& c = ch(0);
+  int32_t rc;
   float* g_first = gb[0];  // gradient w.r.t. the FIRST layer's output
-  if (E > 0) {
-    if (ch[0]->n_layers == 1) {
+  if (h->E > 0) {
+    if (c.n_layers == 1) {
       last_delta(0, g_ef_out, gb[0], nullptr, 0, GNX_ACT_IDENTITY);  // the sum only: the block pullback applies the layer's own act'
     } else {
       last_delta(0, g_ef_out, gb[0], nullptr, 0, -1);
       if ((rc = pull_layers(0, 1, gb[0], gb[1], nullptr, 0, nullptr, &g_first))) return rc;  // g_first: where the last dX went
     }
   } else {
-    for (int i = 1; i < ch[0]->n_layers; ++i)
-      if ((rc = zero_layer_grads(0, i, ch[0]->widths[i - 1]))) return rc;  // (layer 0: the block pullback below zeroes its own)
+    for (int i = 1; i < c.n_layers; ++i)
+      if ((rc = zero_layer_grads(0, i, c.widths[i - 1]))) return rc;  // (layer 0: the block pullback below zeroes its own)
   }
   gnx_block_grads g1{};
   g1.edgefn = grad_of(0, 0);
-  if ((rc = gnx_block_backward(h, &b1, ef, nf, gf, A(0, 0), nullptr, nullptr, E > 0 ? g_first : nullptr, nullptr, nullptr, R, d_ef, d_nf, d_gf, &g1,
-                               base + L.blk_bw, L.blk_bw_bytes, stream))) return rc;
-  }
-  // ---- the node / graph functions' own shares of d_nf, d_gf ----
-  if (d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, Kn, oe, rows[1], dn, d_nf, 1, s))) return rc;
+  return gnx_block_backward(h, &pl.sh.edge_block, ef, nf, gf, A(0, 0), nullptr, nullptr, h->E > 0 ? g_first : nullptr, nullptr, nullptr, R, d_ef, d_nf, d_gf, &g1,
+                            base + pl.L.blk_bw.off, pl.L.blk_bw.bytes, stream);
+}
+
+// ---- the node / graph functions' own shares of d_nf, d_gf ----
+int32_t ChainBwCtx::shares() {
+  int32_t rc;
+  if (d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, Kn, oe, pl.sh.rows[1], dn, d_nf, 1, s))) return rc;
   if (d_gf && dg > 0) {
     if (on > 0) {
       int64_t mn = 1;
       for (int64_t g = 0; g < h->G; ++g) mn = std::max(mn, h->h_node_off[g + 1] - h->h_node_off[g]);
-      colsum_graphs(dXn, false, dg, Kn, oe + dn, N, h->d_node_off, mn, G, Ru, part, d_gf, dg, 0, 1, s);
+      colsum_graphs(dXn, false, dg, Kn, oe + dn, (int)h->N, h->d_node_off, mn, (int)h->G, (unsigned)R, part, d_gf, dg, 0, 1, s);
     }
-    if (og > 0 && (rc = add_cols(dXg, Kg, oe + on, rows[2], dg, d_gf, 1, s))) return rc;
+    if (og > 0 && (rc = add_cols(dXg, Kg, oe + on, pl.sh.rows[2], dg, d_gf, 1, s))) return rc;
   }
+  return GNX_OK;
+}
+
+// The fp32 launches of a pullback on its plan's layout, behind the two refusals that need the plan.  `c`: the call in fp32 — the caller's own
+// tensors, or a staged bf16 call's copies with ws_bytes = the fp32 layout's total.
+int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
+  const gnx_graphs* h = c.h;
+  const hipStream_t s = (hipStream_t)c.stream;
+  DeviceTurn turn(s, pl.sh.wide);
+  if (pl.sh.ow[0] == 0) return fail(GNX_ERR_DIMS, "chain backward: not implemented for an edge function without output (the forward takes it; train such a block with one-layer update functions)");
+  pl.lay_out(h);  // (a staged call has laid out, and comes here behind its own workspace check)
+  int32_t rc;
+  if ((rc = check_ws(c.ws, c.ws_bytes, pl.base, pl.query))) return rc;
+  if ((rc = gnx_ensure_wide_tables(h, c.stream))) return rc;
+  if ((pl.fused & 1) && (rc = gnx_ensure_csr(h))) return rc;  // (k_bw_dnf's out-edge view; the query built it)
+  ChainBwCtx x{h, pl, pl.p, pl.lnf.init_grads(c.grads), cf(c.ef), cf(c.nf), cf(c.gf), cf(c.g_ef_out), cf(c.g_nf_out), cf(c.g_gf_out), mf(c.d_ef), mf(c.d_nf), mf(c.d_gf),
+               c.R, c.stream, s, static_cast<char*>(c.ws), pl.p->de, pl.p->dn, pl.p->dg, pl.sh.ow[0], pl.sh.ow[1], pl.sh.ow[2], pl.sh.k0[1], pl.sh.k0[2],
+               (int)h->E, (int)h->N, (int)h->G, (unsigned)c.R, pl.fused};
+  x.Xn = x.F(pl.L.Xn); x.Xg = x.F(pl.L.Xg); x.dXn = x.F(pl.L.dXn); x.dXg = x.F(pl.L.dXg); x.part = x.F(pl.L.part); x.wt = x.F(pl.L.wt);
+  for (int i = 0; i < 3; ++i) x.gb[i] = x.F(pl.L.gbuf[i]);
+  x.off2 = reinterpret_cast<int*>(x.base + pl.L.off2.off);
+  pl.bind_ident(x.F(pl.L.ident));
+  if ((rc = pl.lnf.fill(x.F(pl.L.ident), s))) return rc;
+  if ((rc = x.recompute())) return rc;
+  const unsigned fused = pl.fused;
+  const int dn = x.dn, dg = x.dg, oe = x.oe, on = x.on, og = x.og, Kn = x.Kn, Kg = x.Kg;
+  // ---- graph chain ----
+  if (fused & 4) {
+    if ((rc = x.fused_level(2, x.Xg, Kg, nullptr, 0, nullptr, 0, ChainBwNarrowIo{x.g_gf_out, nullptr, 0, 0, nullptr, 0, x.dXg, 0, nullptr, nullptr}, "bw_delta"))) return rc;
+  } else if (og > 0) {
+    x.last_delta(2, x.g_gf_out, x.gb[0], x.Xg, Kg, -1);
+    if ((rc = x.pull_layers(2, 0, x.gb[0], x.gb[1], x.Xg, Kg, x.dXg, nullptr))) return rc;
+  }
+  // ---- node chain: upstream + dXg[graph of the node][oe : oe+on] ----
+  if (fused & 2) {
+    if ((rc = x.fused_level(1, x.ef_out, oe, x.nf, dn, x.gf, dg, ChainBwNarrowIo{x.g_nf_out, og > 0 ? x.dXg : nullptr, Kg, oe, nullptr, 0, x.dXn, 0, nullptr, nullptr}, "bw_delta"))) return rc;
+  } else if (on > 0) {
+    x.last_delta(1, x.g_nf_out, x.gb[0], x.Xn, Kn, -1);
+    if ((rc = x.pull_layers(1, 0, x.gb[0], x.gb[1], x.Xn, Kn, x.dXn, nullptr))) return rc;
+  }
+  if ((rc = (fused & 1) ? x.edge_fused() : x.edge_generic())) return rc;
+  if ((rc = x.shares())) return rc;
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
 
-// the workspace of gnx_chain_block_backward_typed on bf16 features: the fp32 pullback's (`base`), then fp32 copies of the nine feature-shaped tensors
-Staging chain_bw_typed_ws(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, size_t base) {
-  const int d[9] = {p->de, p->dn, p->dg, chain_out(p->edgefn), chain_out(p->nodefn), chain_out(p->graphfn), p->de, p->dn, p->dg};
-  return stage_features(base, h, R, d, 9);
+// One Chain pullback call: the refusals in their order — NULL handle or params, the parameters, (bf16) alignment, NULL features; nothing of the
+// handle but its counts is read before them.  An fp32 call then goes to the fp32 launches; a bf16 call lays out, checks its workspace, widens its
+// six inputs, runs the fp32 launches on the copies and rounds the three input gradients (gnx_staging.h); the parameter gradients are the fp32
+// pullback's own.
+int32_t chain_bw_run(const ChainBwCall& c, bool narrow) {
+  if (!c.h || !c.p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow);
+  if (pl.rc) return c.elem == GNX_ELEM_BF16 ? pl.rc : GNX_ERR_DIMS;  // (fp32: one code for every refused parameter set; gnx_last_error() holds the reason)
+  const void* bufs[9] = {c.ef, c.nf, c.gf, c.g_ef_out, c.g_nf_out, c.g_gf_out, c.d_ef, c.d_nf, c.d_gf};
+  int32_t rc;
+  if (pl.bf16 && (rc = check_bf16_aligned(bufs, 9))) return rc;
+  if ((rc = chain_check_features(pl.sh, c.ef, c.nf, c.gf, "an input with non-zero width is NULL"))) return rc;
+  if (!pl.bf16) return chain_backward_fp32(c, pl);
+  pl.lay_out(c.h);
+  if ((rc = check_ws(c.ws, c.ws_bytes, pl.total, pl.query))) return rc;
+  const hipStream_t s = (hipStream_t)c.stream;
+  if ((rc = stage_widen(pl.st, c.ws, bufs, 0, 6, s))) return rc;
+  auto at = [&](int i) { return bufs[i] && pl.st.n[i] > 0 ? pl.st.at(c.ws, i) : nullptr; };
+  const ChainBwCall c32{c.h, c.p, GNX_ELEM_F32, at(0), at(1), at(2), at(3), at(4), at(5), c.R, at(6), at(7), at(8), c.grads, c.ws, pl.base, c.stream};
+  if ((rc = chain_backward_fp32(c32, pl))) return rc;
+  return stage_round(pl.st, c.ws, bufs, 6, 9, s);
+}
+
+// a _workspace_bytes entry: the plan's total; query_total builds what the pullback reads of the handle, outside any capture
+size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow) {
+  ChainBwPlan pl(h, p, R, elem, narrow);
+  pl.lay_out(h);  // (nothing for refused parameters: the total stays 0)
+  return query_total(h, pl.total);
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t gnx_chain_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_bw_query(h, p, R, false); }
+// Every _workspace_bytes: the plan's total (and the plan's tables built).  _applies: the mask of the pullback's rule.  Every call entry: the
+// record, then chain_bw_run.
+size_t gnx_chain_block_backward_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_bw_query(h, p, R, GNX_ELEM_F32, false); }
 
 int32_t gnx_chain_block_backward(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
                                  const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                                  float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  return chain_backward(h, p, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, false);
+  return chain_bw_run(ChainBwCall{h, p, GNX_ELEM_F32, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, false);
 }
 
 // gnx_chain_block_backward_narrow: every update function inside the rule (chain_bw_narrow_takes) pulled back in one kernel
 int32_t gnx_chain_block_backward_narrow_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
-  return chain_bw_valid(h, p, R) && chain_out(p->edgefn) > 0 ? (int32_t)chain_bw_narrow_mask(h, p) : 0;
+  const ChainBwPlan pl(h, p, R, GNX_ELEM_F32, true);  // (the constructor reads the handle's counts alone)
+  return !pl.rc && pl.sh.ow[0] > 0 ? (int32_t)pl.fused : 0;  // (no pullback without an edge output)
 }
 
-size_t gnx_chain_block_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_bw_query(h, p, R, true); }
+size_t gnx_chain_block_backward_narrow_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) { return chain_bw_query(h, p, R, GNX_ELEM_F32, true); }
 
 int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
                                         const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                                         float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
-  return chain_backward(h, p, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream, true);
+  return chain_bw_run(ChainBwCall{h, p, GNX_ELEM_F32, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true);
 }
 
-// gnx_chain_block_backward_typed: either pullback above (narrow selects which) on fp32 or bf16 features.  bf16 is staged: the six feature
-// inputs and upstream gradients are widened into fp32 copies behind the fp32 pullback's workspace, the three input gradients rounded back
-// (gnx_staging.h); the parameter gradients are the fp32 pullback's own.
+// gnx_chain_block_backward_typed: either pullback above (narrow selects which) on fp32 or bf16 features; bf16 is staged
 size_t gnx_chain_block_backward_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, int32_t narrow) {
-  if ((elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) || (narrow != 0 && narrow != 1)) return 0;
-  const size_t base = chain_bw_query(h, p, R, narrow != 0);
-  return elem == GNX_ELEM_F32 || base == 0 ? base : chain_bw_typed_ws(h, p, R, base).total;
+  return (elem == GNX_ELEM_F32 || elem == GNX_ELEM_BF16) && (narrow == 0 || narrow == 1) ? chain_bw_query(h, p, R, elem, narrow != 0) : 0;
 }
 
 int32_t gnx_chain_block_backward_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
@@ -1729,24 +1699,7 @@ int32_t gnx_chain_block_backward_typed(const gnx_graphs* h, const gnx_chain_bloc
                                        const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, int32_t narrow, void* stream) {
   if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
   if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
-  if (elem == GNX_ELEM_F32)
-    return chain_backward(h, p, static_cast<const float*>(ef), static_cast<const float*>(nf), static_cast<const float*>(gf), static_cast<const float*>(g_ef_out),
-                          static_cast<const float*>(g_nf_out), static_cast<const float*>(g_gf_out), R, static_cast<float*>(d_ef), static_cast<float*>(d_nf),
-                          static_cast<float*>(d_gf), grads, ws, ws_bytes, stream, narrow != 0);
-  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  if (int32_t rc = chain_check_params(h, p, R)) return rc;
-  const void* bufs[9] = {ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, d_ef, d_nf, d_gf};
-  if (int32_t rc = check_bf16_aligned(bufs, 9)) return rc;
-  if ((p->de > 0 && !ef && h->E > 0) || (p->dn > 0 && !nf) || (p->dg > 0 && !gf)) return fail(GNX_ERR_INVALID_ARG, "an input with non-zero width is NULL");
-  const size_t base = chain_bw_query(h, p, R, narrow != 0);  // (what the fp32 pullback asks of the handle exists since the caller's query)
-  if (base == 0) return GNX_ERR_DIMS;  // gnx_last_error() holds the reason
-  const Staging w = chain_bw_typed_ws(h, p, R, base);
-  if (int32_t rc = check_ws(ws, ws_bytes, w.total, "workspace missing or smaller than gnx_chain_block_backward_typed_workspace_bytes()")) return rc;
-  const hipStream_t s = (hipStream_t)stream;
-  if (int32_t rc = stage_widen(w, ws, bufs, 0, 6, s)) return rc;
-  auto at = [&](int i) { return bufs[i] && w.n[i] > 0 ? w.at(ws, i) : nullptr; };
-  if (int32_t rc = chain_backward(h, p, at(0), at(1), at(2), at(3), at(4), at(5), R, at(6), at(7), at(8), grads, ws, w.base, stream, narrow != 0)) return rc;
-  return stage_round(w, ws, bufs, 6, 9, s);
+  return chain_bw_run(ChainBwCall{h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, narrow != 0);
 }
 
 }  // extern "C"

@@ -37,7 +37,6 @@ struct ChainMlpBwArgs {
   float* part;                  // the partial rows, layer l at part + sh.part_off[l] * (R * nwg); or nullptr (no parameter gradient wanted)
 };
 
-constexpr int kChainBwLdsFloats = 16384;     // parameters + every wave's tape and accumulators: 64 KB
 constexpr int chain_bw_smax(int WMAX) { return (WMAX + 1 + 64 / WMAX - 1) / (64 / WMAX); }  // pairs per lane of a WMAX x (WMAX + 1) layer
 
 // One layer's parameter-gradient phase over the cnt rows the wave parked: inputs at slots [xs, xs + K), deltas at [ds, ds + J).
@@ -273,64 +272,21 @@ __global__ __launch_bounds__(256) void k_chain_mlp_bw(ChainMlpBwArgs a) {
   }
 }
 
-ChainBwNarrowShape chain_bw_narrow_shape(const gnx_chain& c, int k_in, size_t rows) {
-  ChainBwNarrowShape sh{};
-  int kin = k_in, slots = k_in, dmax = 0;
-  for (int i = 0; i < c.n_layers; ++i) {
-    const bool ln = chain_layer_is_ln(c.layers[i]);
-    const int J = c.widths[i];
-    sh.par_off[i] = sh.par_floats;
-    sh.par_floats += chain_layer_par_floats(kin, J, ln);
-    sh.part_off[i] = sh.P;
-    sh.P += ln ? 2 * J : J * (kin + 1);
-    sh.tape_out[i] = slots;
-    if (i + 1 < c.n_layers) slots += J;
-    dmax = std::max(dmax, ln ? 2 * J : J);
-    kin = J;
-  }
-  sh.dslot = slots;
-  sh.ld = (slots + dmax) | 1;
-  const int per_wave = 64 * sh.ld + sh.P;
-  sh.waves = std::min(4, std::max(0, (kChainBwLdsFloats - sh.par_floats) / per_wave));
-  if (sh.waves > 0) sh.nwg = (rows + 64 * (size_t)sh.waves - 1) / (64 * (size_t)sh.waves);
-  return sh;
-}
-
-bool chain_bw_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows) {
-  // two waves per workgroup at least: the one-wave class (a tape and accumulators beyond 28 KB) is cut — measured, it re-stages its parameters for
-  // every 64 rows, writes a partial row per 64 rows and misses the generic pullback's time (profiles/chain_bw_narrow.json)
-  return chain_narrow_takes(c, k_in, entity_rows) && chain_bw_narrow_shape(c, k_in, entity_rows).waves >= 2;
-}
-
-template <int SRC>
-static void chain_mlp_bw_launch(int wmax, dim3 grid, dim3 block, size_t lds, hipStream_t s, const ChainMlpBwArgs& a) {
-  if (wmax <= 8) GNX_LAUNCH((k_chain_mlp_bw<8, SRC>), grid, block, lds, s, a);
-  else if (wmax <= 16) GNX_LAUNCH((k_chain_mlp_bw<16, SRC>), grid, block, lds, s, a);
-  else GNX_LAUNCH((k_chain_mlp_bw<32, SRC>), grid, block, lds, s, a);
-}
-
+// The caller asked chain_bw_narrow_takes (gnx_chain_plan.h: the rule and the LDS plan, chain_bw_narrow_shape) and opens the ProfScope.
 int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                                const ChainBwNarrowIo& io, int64_t R, hipStream_t s) {
   ChainMlpBwArgs a{};
-  const int K = entity == 0 ? d0 + 2 * d1 + d2 : d0 + d1 + d2;
-  const size_t rows = entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G);
-  if (!chain_bw_narrow_takes(c, K, rows)) return fail(GNX_ERR_INVALID_ARG, "launch_chain_bw_narrow: the function is outside the fused rule");
-  int kin = K;
-  for (int i = 0; i < c.n_layers; ++i) {
-    if (!chain_layer_is_ln(c.layers[i]) && kin > 0 && !c.layers[i].weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
-    kin = c.widths[i];
-  }
-  const int wmax = chain_mlp_fill(h, entity, c, in0, d0, in1, d1, in2, d2, a.f);
-  a.sh = chain_bw_narrow_shape(c, K, rows);
+  int wmax;
+  size_t rows;
+  if (int32_t rc = chain_mlp_prologue(h, entity, c, in0, d0, in1, d1, in2, d2, CHAIN_RULE_BW, "launch_chain_bw_narrow", s, a.f, &wmax, &rows)) return rc;
+  a.sh = chain_bw_narrow_shape(c, a.f.K, rows);
   a.G = io.G;
   a.ex1 = io.ex1; a.ex1_stride = io.ex1_stride; a.ex1_off = io.ex1_off; a.ex1_rep = (size_t)h->G * io.ex1_stride;
   a.ex2 = io.ex2; a.ex2_stride = io.ex2_stride; a.ex2_rep = (size_t)h->N * io.ex2_stride;
   a.dx = io.dx; a.dx_c0 = io.dx_c0; a.direct = io.direct; a.part = io.part;
   const dim3 grid((unsigned)a.sh.nwg, (unsigned)R), block(64 * a.sh.waves);
   const size_t lds = sizeof(float) * ((size_t)a.sh.par_floats + (size_t)a.sh.waves * (64 * a.sh.ld + a.sh.P));
-  if (entity == 0) chain_mlp_bw_launch<SRC_EDGE>(wmax, grid, block, lds, s, a);
-  else if (entity == 1) chain_mlp_bw_launch<SRC_NODE>(wmax, grid, block, lds, s, a);
-  else chain_mlp_bw_launch<SRC_ROWS>(wmax, grid, block, lds, s, a);
+  chain_mlp_dispatch(wmax, entity, [&](auto W, auto S) { GNX_LAUNCH((k_chain_mlp_bw<decltype(W)::value, decltype(S)::value>), grid, block, lds, s, a); });
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }

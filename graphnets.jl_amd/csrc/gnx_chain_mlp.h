@@ -3,6 +3,9 @@
 // the forward kernel's layer, operation for operation, as a function: the pullback's forward half runs it (and so carries the forward's bits);
 // k_chain_mlp keeps its loop in place, because as a function call the same text costs its 32-wide instantiation 16 more registers.
 #pragma once
+#include <algorithm>
+#include <type_traits>
+
 #include "gnx_launchers.h"
 #include "gnx_wave_kernel.h"  // act_row
 
@@ -27,8 +30,6 @@ struct ChainMlpArgs {
   float* out; int ow;    // [R][rows][ow]
   size_t rows;           // rows of the entity per replica
 };
-
-__host__ __device__ constexpr int ceil4(int x) { return (x + 3) & ~3; }
 
 // cur[at .. at + w) = p[0 .. w): one dword load per element behind a uniform test
 template <int WMAX>
@@ -63,8 +64,7 @@ __device__ __forceinline__ void chain_stage_params(const ChainMlpArgs& a, float*
     kin = L.width;
   }
 }
-// floats a layer takes in that layout
-__host__ __device__ constexpr int chain_layer_par_floats(int kin, int width, bool ln) { return ln ? 2 * ceil4(width) : ceil4(kin) * ceil4(width) + ceil4(width); }
+// (floats a layer takes in that layout: chain_layer_par_floats, gnx_chain_plan.h — ceil4 is defined there)
 
 // the input row of `row` (replica r) of the function, entries at or beyond K exactly 0.f
 template <int WMAX, int SRC>
@@ -167,22 +167,39 @@ __device__ __forceinline__ float gelu_grad_pre(float z) {
 }
 __device__ __forceinline__ float act_grad_bw(float v, int act) { return act == 4 ? gelu_grad_pre(v) : act_grad_from_out(v, act); }
 
-// the argument record's function part from a (checked) chain; returns the register width's lower bound (the largest of K and the layer widths)
-inline int chain_mlp_fill(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
-                          ChainMlpArgs& a) {
+// What the three fused launchers (launch_chain_narrow, _bf16, launch_chain_bw_narrow: `who`) do first: ask the rule, refuse a Dense without weights
+// (the forward's launchers pass a layer of width 0, the pullback's does not: each keeps the set it took), fill the argument record's function
+// part from the chain.  *wmax: the register width's lower bound (the largest of K and the layer widths); *rows: rows of the entity per replica.
+inline int32_t chain_mlp_prologue(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
+                                  ChainRule rule, const char* who, hipStream_t s, ChainMlpArgs& a, int* wmax, size_t* rows) {
   const int K = entity == 0 ? d0 + 2 * d1 + d2 : d0 + d1 + d2;
-  int wmax = K;
+  *rows = entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G);
+  if (!chain_rule_takes(rule, c, K, *rows)) return fail(GNX_ERR_INVALID_ARG, std::string(who) + ": the function is outside the fused rule");
+  // the destination of every edge: a forward launch makes sure of the table itself, the pullback (chain_bw_run) has
+  if (rule == CHAIN_RULE_FW && entity == 0) { if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw; }
+  *wmax = K;
+  int kin = K;
   for (int i = 0; i < c.n_layers; ++i) {
     const gnx_dense& l = c.layers[i];
+    if (!chain_layer_is_ln(l) && (rule == CHAIN_RULE_BW || c.widths[i] > 0) && kin > 0 && !l.weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
     a.layer[i] = ChainMlpLayer{l.weight, l.bias, c.widths[i], chain_layer_is_ln(l) ? 5 + chain_layer_ln_mode(l) : l.act};
-    wmax = wmax > c.widths[i] ? wmax : c.widths[i];
+    *wmax = std::max(*wmax, (int)c.widths[i]);
+    kin = c.widths[i];
   }
   a.n_layers = c.n_layers; a.K = K;
   a.a0 = in0; a.a1 = in1; a.a2 = in2; a.d0 = d0; a.d1 = d1; a.d2 = d2;
   a.N = (int)h->N; a.E = (int)h->E; a.G = (int)h->G;
   a.colptr = h->d_colptr; a.rowval = h->d_rowval; a.edge_dst = h->d_edge_dst; a.seg_off = entity == 0 ? h->d_edge_off : h->d_node_off;
-  a.rows = entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G);
-  return wmax;
+  a.rows = *rows;
+  return GNX_OK;
+}
+
+// the WMAX x SRC switch of the three launchers: launch(WMAX, SRC) as integral constants, WMAX in {8, 16, 32} the smallest that covers wmax
+template <int V> using ChainInt = std::integral_constant<int, V>;
+template <class Launch>
+inline void chain_mlp_dispatch(int wmax, int entity, Launch&& launch) {
+  auto width = [&](auto src) { wmax <= 8 ? launch(ChainInt<8>{}, src) : wmax <= 16 ? launch(ChainInt<16>{}, src) : launch(ChainInt<32>{}, src); };
+  entity == 0 ? width(ChainInt<SRC_EDGE>{}) : entity == 1 ? width(ChainInt<SRC_NODE>{}) : width(ChainInt<SRC_ROWS>{});
 }
 
 }  // namespace gnx

@@ -101,55 +101,19 @@ __global__ __launch_bounds__(256) void k_chain_mlp(ChainMlpArgs a) {
     if (k < a.ow) o[k] = cur[k];
 }
 
-// floats of LDS the parameters of `c` take in the kernel's layout (input width k_in)
-size_t chain_narrow_lds_floats(const gnx_chain& c, int k_in) {
-  size_t n = 0;
-  int kin = k_in;
-  for (int i = 0; i < c.n_layers; ++i) {
-    const int OP = ceil4(c.widths[i]);
-    n += chain_layer_is_ln(c.layers[i]) ? 2 * (size_t)OP : (size_t)ceil4(kin) * OP + OP;
-    kin = c.widths[i];
-  }
-  return n;
-}
-
-bool chain_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows) {
-  if (c.n_layers < 1 || c.n_layers > kChainMaxLayers || !c.layers || !c.widths || entity_rows == 0) return false;
-  if (c.widths[c.n_layers - 1] <= 0 || k_in > kChainNarrowMaxWidth) return false;
-  for (int i = 0; i < c.n_layers; ++i)
-    if (c.widths[i] > kChainNarrowMaxWidth) return false;
-  return chain_narrow_lds_floats(c, k_in) <= kChainNarrowLdsFloats;
-}
-
-template <int SRC>
-static void chain_mlp_launch(int wmax, dim3 grid, size_t lds, hipStream_t s, const ChainMlpArgs& a) {
-  if (wmax <= 8) GNX_LAUNCH((k_chain_mlp<8, SRC>), grid, dim3(256), lds, s, a);
-  else if (wmax <= 16) GNX_LAUNCH((k_chain_mlp<16, SRC>), grid, dim3(256), lds, s, a);
-  else GNX_LAUNCH((k_chain_mlp<32, SRC>), grid, dim3(256), lds, s, a);
-}
-
 // One update function of a Chain block in one launch.  entity 0: in0 / in1 / in2 = ef, nf, gf of widths d0, d1, d2 (SRC_EDGE); 1: ef', nf, gf
-// (SRC_NODE); 2: in0 = the materialised [R G][d0] input rows (SRC_ROWS; d1 = d2 = 0).  The caller asked chain_narrow_takes.
+// (SRC_NODE); 2: in0 = the materialised [R G][d0] input rows (SRC_ROWS; d1 = d2 = 0).  The caller asked chain_narrow_takes (gnx_chain_plan.h).
 int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                             float* out, int64_t R, hipStream_t s, const char* name) {
   ChainMlpArgs a{};
-  const int K = entity == 0 ? d0 + 2 * d1 + d2 : d0 + d1 + d2;
-  const size_t rows = entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G);
-  if (!chain_narrow_takes(c, K, rows)) return fail(GNX_ERR_INVALID_ARG, "launch_chain_narrow: the function is outside the fused rule");
-  if (entity == 0) { if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw; }  // (the destination of every edge)
-  int kin = K;
-  for (int i = 0; i < c.n_layers; ++i) {
-    if (!chain_layer_is_ln(c.layers[i]) && c.widths[i] > 0 && kin > 0 && !c.layers[i].weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
-    kin = c.widths[i];
-  }
-  const int wmax = chain_mlp_fill(h, entity, c, in0, d0, in1, d1, in2, d2, a);
+  int wmax;
+  size_t rows;
+  if (int32_t rc = chain_mlp_prologue(h, entity, c, in0, d0, in1, d1, in2, d2, CHAIN_RULE_FW, "launch_chain_narrow", s, a, &wmax, &rows)) return rc;
   a.out = out; a.ow = c.widths[c.n_layers - 1];
   const dim3 grid((unsigned)((rows + 255) / 256), (unsigned)R);
-  const size_t lds = sizeof(float) * chain_narrow_lds_floats(c, K);
+  const size_t lds = sizeof(float) * chain_narrow_lds_floats(c, a.K);
   ProfScope ps(name, s);
-  if (entity == 0) chain_mlp_launch<SRC_EDGE>(wmax, grid, lds, s, a);
-  else if (entity == 1) chain_mlp_launch<SRC_NODE>(wmax, grid, lds, s, a);
-  else chain_mlp_launch<SRC_ROWS>(wmax, grid, lds, s, a);
+  chain_mlp_dispatch(wmax, entity, [&](auto W, auto S) { GNX_LAUNCH((k_chain_mlp<decltype(W)::value, decltype(S)::value>), grid, dim3(256), lds, s, a); });
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }

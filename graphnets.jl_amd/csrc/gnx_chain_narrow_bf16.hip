@@ -103,36 +103,21 @@ __global__ __launch_bounds__(256) void k_chain_mlp_bf16(ChainMlpBf16Args t) {
   }
 }
 
-template <int SRC>
-static void chain_mlp_bf16_launch(int wmax, dim3 grid, size_t lds, hipStream_t s, const ChainMlpBf16Args& t) {
-  if (wmax <= 8) GNX_LAUNCH((k_chain_mlp_bf16<8, SRC>), grid, dim3(256), lds, s, t);
-  else if (wmax <= 16) GNX_LAUNCH((k_chain_mlp_bf16<16, SRC>), grid, dim3(256), lds, s, t);
-  else GNX_LAUNCH((k_chain_mlp_bf16<32, SRC>), grid, dim3(256), lds, s, t);
-}
-
 // launch_chain_narrow on bf16 features (which of in0 .. in2 are bf16: the head of this file); out: bf16 rows, out32: the same rows in fp32 or
 // nullptr.  The caller asked chain_narrow_takes.
 int32_t launch_chain_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
                                  void* out, float* out32, int64_t R, hipStream_t s, const char* name) {
   ChainMlpBf16Args t{};
-  const int K = entity == 0 ? d0 + 2 * d1 + d2 : d0 + d1 + d2;
-  const size_t rows = entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G);
-  if (!chain_narrow_takes(c, K, rows)) return fail(GNX_ERR_INVALID_ARG, "launch_chain_narrow_bf16: the function is outside the fused rule");
-  if (entity == 0) { if (int32_t rcw = gnx_ensure_wide_tables(h, s)) return rcw; }  // (the destination of every edge)
-  int kin = K;
-  for (int i = 0; i < c.n_layers; ++i) {
-    if (!chain_layer_is_ln(c.layers[i]) && c.widths[i] > 0 && kin > 0 && !c.layers[i].weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
-    kin = c.widths[i];
-  }
-  const int wmax = chain_mlp_fill(h, entity, c, static_cast<const float*>(in0), d0, static_cast<const float*>(in1), d1, static_cast<const float*>(in2), d2, t.f);
+  int wmax;
+  size_t rows;
+  if (int32_t rc = chain_mlp_prologue(h, entity, c, static_cast<const float*>(in0), d0, static_cast<const float*>(in1), d1, static_cast<const float*>(in2), d2,
+                                      CHAIN_RULE_FW, "launch_chain_narrow_bf16", s, t.f, &wmax, &rows)) return rc;
   t.f.ow = c.widths[c.n_layers - 1];
   t.out = static_cast<bf16_t*>(out); t.out32 = out32;
   const dim3 grid((unsigned)((rows + 255) / 256), (unsigned)R);
-  const size_t lds = sizeof(float) * chain_narrow_lds_floats(c, K);
+  const size_t lds = sizeof(float) * chain_narrow_lds_floats(c, t.f.K);
   ProfScope ps(name, s);
-  if (entity == 0) chain_mlp_bf16_launch<SRC_EDGE>(wmax, grid, lds, s, t);
-  else if (entity == 1) chain_mlp_bf16_launch<SRC_NODE>(wmax, grid, lds, s, t);
-  else chain_mlp_bf16_launch<SRC_ROWS>(wmax, grid, lds, s, t);
+  chain_mlp_dispatch(wmax, entity, [&](auto W, auto S) { GNX_LAUNCH((k_chain_mlp_bf16<decltype(W)::value, decltype(S)::value>), grid, dim3(256), lds, s, t); });
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }

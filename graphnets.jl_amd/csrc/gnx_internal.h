@@ -16,6 +16,7 @@
 #include "gnx.h"
 
 #include "gnx_device.h"  // gnx::Tile, gnx::BlockArgs
+#include "gnx_chain_plan.h"  // kChainMaxLayers, chain_layer_is_ln: the host arithmetic of a Chain block call
 
 namespace gnx {
 // std::vector whose resize() leaves trivially constructible elements uninitialised: the O(N + E) arrays of a handle are written in full by the
@@ -140,10 +141,7 @@ struct FormScope {  // an exported forward opens one: the functions below it rea
   FormScope& operator=(const FormScope&) = delete;
   uint32_t prev;
 };
-// a Chain's layer entries (include/gnx.h: gnx_dense.kind): Dense or a LayerNorm(d) layer value (gamma, beta in weight, bias; eps = Flux's default)
-constexpr float kChainLnEps = 1e-5f;
-inline bool chain_layer_is_ln(const gnx_dense& l) { return (l.kind & 0xff) == GNX_LAYER_LAYERNORM; }
-inline int chain_layer_ln_mode(const gnx_dense& l) { return (l.kind & GNX_LAYER_LN_SQRT_EPS) ? 1 : 0; }
+// one layer of a Chain (gnx_chain_plan.h: chain_layer_is_ln), row-wise over all rows of the entity
 int32_t launch_chain_layer(const gnx_graphs* h, int entity, const gnx_dense& layer, const float* x, int k_in, int width, float* out, int64_t R, hipStream_t s,
                            const char* name);  // gnx_chain.cpp
 // An edge function whose FIRST layer is a LayerNorm, `Chain(LayerNorm(K_e), Dense ...)`: the chain entry points fuse a chain's first layer with
@@ -151,7 +149,6 @@ int32_t launch_chain_layer(const gnx_graphs* h, int entity, const gnx_dense& lay
 // the identity layer's output IS the function input, bit for bit (x . 1 + 0 in fp32 and in the six-term split: h + m + l = x exactly), and both
 // the forward and the pullback (the scatter of the input gradient into d_ef / d_nf[src] / d_nf[dst] / d_gf included) stay those of a Dense-first
 // chain.  `ident` = K_e x K_e floats in the call's workspace, written by fill() on the call's stream.  Not copyable: p.edgefn points into it.
-constexpr int kChainMaxLayers = 16;
 struct ChainLnFirst {
   bool on = false;
   int ke = 0;

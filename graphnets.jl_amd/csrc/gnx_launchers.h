@@ -175,12 +175,7 @@ int32_t launch_ln1_rows_bf16(const void* x, size_t rows, int d, const gnx_layern
 int32_t launch_core_post_train(const void* x, size_t rows, int d, const gnx_layernorm& l2, const gnx_ffn& ff, float eps, int eps_mode, const float* block_out,
                                const gnx_dropout& dr, int entity, void* y, bool bf16, hipStream_t s);
 
-// ---- gnx_chain_narrow.hip: one update function of a Chain block in one kernel (gnx_chain_block_forward_narrow) ----
-constexpr int kChainNarrowMaxWidth = 32;         // input width and every layer width of a fused function
-constexpr size_t kChainNarrowLdsFloats = 10240;  // its zero-padded parameters in LDS: 40 KB (include/gnx.h states the rule)
-size_t chain_narrow_lds_floats(const gnx_chain& c, int k_in);
-// is the function fused: >= 1 layer, a non-zero output width, k_in and every width <= 32, parameters within the LDS budget, rows to run on
-bool chain_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows);
+// ---- gnx_chain_narrow.hip: one update function of a Chain block in one kernel (gnx_chain_block_forward_narrow; the rule: gnx_chain_plan.h) ----
 // entity 0: in0 / in1 / in2 = ef, nf, gf (widths d0, d1, d2); 1: ef', nf, gf; 2: in0 = the materialised [R G][d0] input rows (d1 = d2 = 0)
 int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                             float* out, int64_t R, hipStream_t s, const char* name);
@@ -191,16 +186,6 @@ int32_t launch_chain_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chai
                                  void* out, float* out32, int64_t R, hipStream_t s, const char* name);
 
 // ---- gnx_chain_bw_narrow.hip: the pullback of one update function of a Chain block in one kernel (gnx_chain_block_backward_narrow) ----
-// the kernel's LDS plan for a function: the staged parameters, then per wave 64 tape rows of `ld` floats (the input row, every layer's output but
-// the last, the parked deltas) and P accumulators (one per parameter)
-struct ChainBwNarrowShape {
-  int ld, P, par_floats, waves, dslot;  // waves: per workgroup, as many as fit 64 KB of LDS, at most 4 — the rule takes a function from 2 on
-  int par_off[kChainMaxLayers], part_off[kChainMaxLayers], tape_out[kChainMaxLayers];  // per layer: staged parameters / accumulators / output slot
-  size_t nwg;                           // workgroups (= partial rows per layer) per replica: a wave takes 64 rows
-};
-ChainBwNarrowShape chain_bw_narrow_shape(const gnx_chain& c, int k_in, size_t rows);
-// the rule of gnx_chain_block_backward_narrow for one function (include/gnx.h states it): chain_narrow_takes and two waves' LDS within 64 KB
-bool chain_bw_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows);
 struct ChainBwNarrowIo {
   const float* G;                           // upstream gradient of the function's output, or nullptr
   const float* ex1; int ex1_stride, ex1_off;  // dXg [R G][ex1_stride], columns from ex1_off (node / edge level), or nullptr
@@ -212,8 +197,6 @@ struct ChainBwNarrowIo {
 // entity / in0..in2 as launch_chain_narrow.  The caller asked chain_bw_narrow_takes and opens the ProfScope.
 int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                                const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
-// gnx_chain.cpp: the validation of a Chain block's parameters and replicas (reads the handle's counts only)
-int32_t chain_check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R);
 
 // ---- gnx_forward.hip: the validation of a core forward, for the training-mode entries of gnx_dropout.hip (a FormScope of the call's flags open) ----
 int32_t core_forward_check_dims(const gnx_core_params* p);  // (needs no handle)

@@ -1,5 +1,6 @@
-// Host plumbing the entry points of gnx_forward.hip and gnx_backward.hip share: the workspace and bf16-alignment checks of a call, and the
-// staging of a bf16 call that converts around an fp32 path (widen into the workspace, run fp32, round the outputs).  No kernel here.
+// Host plumbing the entry points of gnx_forward.hip, gnx_backward.hip and gnx_chain.cpp share: the workspace and bf16-alignment checks of a call, the
+// staging of a bf16 call that converts around an fp32 path (widen into the workspace, run fp32, round the outputs), and what the Chain block's
+// forward and pullback decide in common about a call (ChainPlan; defined in gnx_chain.cpp).  No kernel here.
 #pragma once
 #include <algorithm>
 
@@ -60,5 +61,29 @@ inline int32_t stage_round(const Staging& st, void* ws, const void* const* bufs,
       if (const int32_t rc = launch_bf16_round(st.at(ws, i), st.n[i], const_cast<void*>(bufs[i]), s)) return rc;
   return GNX_OK;
 }
+
+// ---- a call of a GNBlock with Chain update functions (gnx_chain.cpp: the forward entries; gnx_backward.hip: the pullbacks) ----
+// What is decided about such a call from the handle's counts alone, decided once, by a query and by a call from the same arguments: the validation,
+// the fused mask of `rule` (0 unless `narrow`), the LayerNorm-first rewrite (ChainLnFirst: a generic edge function that opens with a LayerNorm runs
+// behind an identity Dense, a fused one as it stands; p: the parameters every launch works on, sh: their shape) and the query whose name the
+// workspace refusal cites (query_of: the plain, the narrow, the typed entry's).  The forward and the pullback derive their plan from it
+// (ChainFwPlan, ChainBwPlan) and add their layout, which sized() completes.  Not copyable (ChainLnFirst is not): `p` may point into `lnf`.
+struct ChainPlan {
+  ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3]);
+  int32_t rc;  // the validation's; not GNX_OK: nothing below is set
+  ChainLnFirst lnf;
+  const gnx_chain_block_params* p = nullptr;
+  ChainShape sh{};
+  unsigned fused = 0;
+  bool bf16 = false;
+  Staging st{};                // a bf16 call: the fp32 carves behind the fp32 layout
+  size_t base = 0, total = 0;  // the fp32 layout's total; what the entry's _workspace_bytes returns
+  const char* query = nullptr;
+  // a call binds the identity layer of the rewrite to its carve of the workspace: in the chain and in the one-layer block that is its copy
+  void bind_ident(const float* ident) { if (lnf.on) { lnf.layers[0].weight = ident; sh.edge_block.edgefn.weight = ident; } }
+  void sized(size_t fp32_total, const Staging& staging) { base = fp32_total; st = staging; total = bf16 ? st.total : base; }
+};
+// "an input with non-zero width is NULL": one check behind every Chain entry, each with its own message
+int32_t chain_check_features(const ChainShape& sh, const void* ef, const void* nf, const void* gf, const char* message);
 
 }  // namespace gnx

@@ -16,7 +16,7 @@ CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 WMAX = (8, 16, 32)
 SRC = ("edge", "node", "rows")
-LDS_BUDGET_BYTES = 4 * 16384  # kChainBwLdsFloats (gnx_chain_bw_narrow.hip)
+LDS_BUDGET_BYTES = 4 * 16384  # kChainBwLdsFloats (gnx_chain_plan.h)
 
 
 def resources(hipcc=HIPCC):
