@@ -157,6 +157,10 @@ SIGNATURES = {
     "gnx_chain_block_backward_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32, C.c_int32]),
     "gnx_chain_block_backward_typed": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int32] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
                                        [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    "gnx_chain_block_backward_narrow_typed_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
+    "gnx_chain_block_backward_narrow_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
+    "gnx_chain_block_backward_narrow_typed": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int32] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
+                                              [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_block_forward_chained": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams)] + _FWD[2:] + [C.POINTER(PendingUpdate), C.POINTER(PendingUpdate)]),
     "gnx_block_forward_steps": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.POINTER(BlockStep), C.c_int64, C.c_int64, C.c_uint32, C.c_void_p]),
     "gnx_block_forward_steps_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32, C.POINTER(BlockStep), C.c_int64, C.c_int64, C.c_uint32,

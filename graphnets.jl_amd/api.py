@@ -911,10 +911,16 @@ class GNBlock:
     bit for bit the fp32 entry on the widened inputs rounded once.  With `narrow_chain` and every update function inside the narrow rule the
     fused kernels read and write the bf16 rows themselves; elsewhere fp32 copies go around the fp32 entry.  A differentiable call also needs
     `bf16_backward`: its pullback is gnx_chain_block_backward_typed (`narrow_chain_backward` selects the mirrored fp32 pullback), input
-    gradients rounded to bfloat16, parameter gradients in float32.  Off (the default) such a block on bfloat16 features raises."""
+    gradients rounded to bfloat16, parameter gradients in float32.  Off (the default) such a block on bfloat16 features raises.
+
+    `native_chain_backward` (also a plain attribute): the pullback of a differentiable call of such a block on bfloat16 features (which still
+    needs `bf16_chain` and `bf16_backward`) is gnx_chain_block_backward_narrow_typed.  Where the whole block is inside the narrow pullback's
+    rule, each update function is pulled back in one kernel that reads the bf16 rows and upstream gradients and writes the bf16 edge gradient
+    itself: no edge- or node-sized fp32 copy is made, and the gradients are bit for bit those of gnx_chain_block_backward_typed with
+    `narrow_chain_backward`.  Elsewhere the call is that staged pullback.  Off (the default), and on float32 features, nothing changes."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
-                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False):
+                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -932,6 +938,7 @@ class GNBlock:
         self.narrow_chain = bool(narrow_chain)
         self.narrow_chain_backward = bool(narrow_chain_backward)
         self.bf16_chain = bool(bf16_chain)
+        self.native_chain_backward = bool(native_chain_backward)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1274,7 +1281,8 @@ class _ChainBlockFn(torch.autograd.Function):
 
 
 def _chain_block_pullback(ctx, gouts, elem):
-    """backward of _ChainBlockFn (elem F32) and _ChainBlockBf16Fn (BF16: gnx_chain_block_backward_typed on bf16 feature-shaped tensors)"""
+    """backward of _ChainBlockFn (elem F32) and _ChainBlockBf16Fn (BF16: gnx_chain_block_backward_typed on bf16 feature-shaped tensors, or
+    gnx_chain_block_backward_narrow_typed with the block's `native_chain_backward` switch)"""
     lib = _lib.load()
     block, g, R = ctx.block, ctx.g, ctx.R
     bf16 = elem == _lib.ELEM_BF16
@@ -1307,7 +1315,10 @@ def _chain_block_pullback(ctx, gouts, elem):
     grads = _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays])
     with torch.cuda.device(dev):
         narrow = bool(getattr(block, "narrow_chain_backward", False))
-        if bf16:
+        native = bf16 and bool(getattr(block, "native_chain_backward", False))
+        if native:
+            nb = lib.gnx_chain_block_backward_narrow_typed_workspace_bytes(g._h, C.byref(p), R, elem)
+        elif bf16:
             nb = lib.gnx_chain_block_backward_typed_workspace_bytes(g._h, C.byref(p), R, elem, int(narrow))
         else:
             query, entry = ((lib.gnx_chain_block_backward_narrow_workspace_bytes, lib.gnx_chain_block_backward_narrow)
@@ -1316,7 +1327,11 @@ def _chain_block_pullback(ctx, gouts, elem):
         if nb == 0:
             raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
         ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-        if bf16:
+        if native:
+            check(lib.gnx_chain_block_backward_narrow_typed(g._h, C.byref(p), elem, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
+                                                            _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
+                                                            torch.cuda.current_stream(dev).cuda_stream))
+        elif bf16:
             check(lib.gnx_chain_block_backward_typed(g._h, C.byref(p), elem, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
                                                      _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), int(narrow),
                                                      torch.cuda.current_stream(dev).cuda_stream))
@@ -1331,7 +1346,8 @@ def _chain_block_pullback(ctx, gouts, elem):
 
 class _ChainBlockBf16Fn(torch.autograd.Function):
     """_ChainBlockFn on bfloat16 features (GNBlock.bf16_chain with bf16_backward): forward = gnx_chain_block_forward_typed, backward =
-    gnx_chain_block_backward_typed mirroring the pullback `narrow_chain_backward` selects.  The saved inputs are bf16; the input gradients come
+    gnx_chain_block_backward_typed mirroring the pullback `narrow_chain_backward` selects (gnx_chain_block_backward_narrow_typed with
+    `native_chain_backward`).  The saved inputs are bf16; the input gradients come
     back in bf16 (rounded once from the fp32 pullback of the widened tensors), the parameter gradients in fp32 in _ChainBlockFn's layout."""
 
     @staticmethod

@@ -135,6 +135,22 @@ __global__ void k_bw_dnf(const float* dXn, int Kn, int n_off, const float* dXe, 
   st_feat<BF16>(d_nf, r * (size_t)N * dn + idx, acc);
 }
 
+// k_bw_dnf for the native bf16 Chain pullback: d_nf is bfloat16 and the sum keeps the fp32 Chain pullback's order — 0, the in-edges, the out-edges,
+// then the node function's own share dXn[n][n_off + k] (the fp32 call adds it last, by add_cols) — before it is rounded once
+__global__ void k_bw_dnf_share_last(const float* dXn, int Kn, int n_off, const float* dXe, int Ke, int src_off, int dst_off, const int* colptr,
+                                    const int* csr_ptr, const int* csr_eid, int N, int E, int dn, bf16_t* d_nf) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t r = blockIdx.y;
+  if (idx >= (size_t)N * dn) return;
+  const int n = (int)(idx / dn), k = (int)(idx % dn);
+  float acc = 0.f;
+  const float* base = dXe + r * (size_t)E * Ke;
+  for (int e = colptr[n]; e < colptr[n + 1]; ++e) acc += base[(size_t)e * Ke + dst_off + k];
+  for (int i = csr_ptr[n]; i < csr_ptr[n + 1]; ++i) acc += base[(size_t)csr_eid[i] * Ke + src_off + k];
+  if (dXn) acc += dXn[(r * N + n) * (size_t)Kn + n_off + k];
+  d_nf[r * (size_t)N * dn + idx] = to_bf16(acc);
+}
+
 // per-graph column sums of a row tensor (sum_e ef', sum_n nf' for Xg), two stages, fixed order:
 // stage 1: workgroup (slice s of graph g): thread (grp, c) strides over the slice's rows for column c -> partial[g][s][c].  BF16: `in` is bfloat16
 template <bool BF16>
@@ -1341,22 +1357,40 @@ struct ChainBwCall {
 
 // The pullback's plan: the common part and the layout.  A bf16 call is staged: fp32 copies of the six feature inputs and upstream gradients and of
 // the three input gradients behind the fp32 layout.  lay_out() runs once, behind the refusals that read the handle's counts alone.
+// native (gnx_chain_block_backward_narrow_typed alone asks for it, chain_bw_typed_native decides): every function is one k_chain_mlp_bw_bf16 launch on
+// the caller's bf16 tensors; behind the fp32 layout stand two graph-sized fp32 carves (chain_bw_native_layout) and nothing E- or N-sized.
+const char kBwNarrowTypedQuery[] = "workspace missing or smaller than gnx_chain_block_backward_narrow_typed_workspace_bytes()";
 const char* const kBwQuery[3] = {"workspace missing or smaller than gnx_chain_block_backward_workspace_bytes()", "workspace missing or smaller than gnx_chain_block_backward_narrow_workspace_bytes()",
                                  "workspace missing or smaller than gnx_chain_block_backward_typed_workspace_bytes()"};
 struct ChainBwPlan : ChainPlan {
   ChainBwLayout L{};
-  ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow) : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery) {}
+  bool native = false;
+  ChainBwNativeWs nw{};
+  ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false)
+      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery) {
+    if (rc || !narrow_typed) return;
+    native = chain_bw_typed_native(sh, fused, bf16);
+    if (bf16) query = kBwNarrowTypedQuery;
+  }
   void lay_out(const gnx_graphs* h) {
     if (rc || total) return;
     const bool blk = !(fused & 1) && sh.ch[0]->n_layers > 0;  // the first Dense of a generic edge function: the one-layer block, forward and pullback
     L = chain_bw_layout(sh, fused, lnf.ident_floats(), blk ? gnx_block_workspace_bytes(h, &sh.edge_block, sh.R) : 0,
                         blk ? gnx_block_backward_workspace_bytes(h, &sh.edge_block, sh.R) : 0, BW_CH, dw_mfma_partial_floats);
+    if (native) {
+      nw = chain_bw_native_layout(sh, L.total);
+      base = L.total; total = nw.total;
+      return;
+    }
     const int d[9] = {sh.de, sh.dn, sh.dg, sh.ow[0], sh.ow[1], sh.ow[2], sh.de, sh.dn, sh.dg};
     sized(L.total, stage_features(L.total, h, sh.R, d, 9));
   }
 };
 
 // What the pieces of the fp32 pullback share, and the pieces: the call's fp32 tensors, the plan and its widths, the plan's carves as pointers.
+// A native bf16 call (pl.native) runs the same pieces in the same order: ef, nf, gf, the three upstream gradients, d_ef and d_nf are then the
+// caller's bf16 tensors (declared float), which only the bf16 kernels touch; gf_rows is the widened gf and d_gf the fp32 accumulator of the plan's
+// two carves, rounded into the caller's d_gf at the end.
 struct ChainBwCtx {
   const gnx_graphs* h; const ChainBwPlan& pl; const gnx_chain_block_params* p;  // p: pl.p
   const gnx_chain_block_grads* grads;  // behind the LayerNorm-first rewrite
@@ -1368,6 +1402,7 @@ struct ChainBwCtx {
   float *Xn, *Xg, *dXn, *dXg, *part, *wt, *gb[3];
   int* off2;
   const float *ef_out, *nf_out;  // the recomputed ef', nf' (nullptr without output)
+  const float* gf_rows;          // gf in fp32, for the graph function's input rows: gf itself, or a native call's widened copy
   float* F(const ChainCarve& c) const { return reinterpret_cast<float*>(base + c.off); }
   float* A(int t, int i) const { return F(pl.L.act[t][i]); }  // the stored output of layer i of chain t
   const gnx_chain& ch(int t) const { return *pl.sh.ch[t]; }
@@ -1411,7 +1446,8 @@ int32_t ChainBwCtx::recompute() {
   const gnx_chain &ce = ch(0), &cn = ch(1), &cg = ch(2);
   int32_t rc;
   if (fused & 1) {
-    if ((on > 0 || og > 0) && (rc = launch_chain_narrow(h, 0, ce, ef, de, nf, dn, gf, dg, A(0, ce.n_layers - 1), R, s, "bw_chain_fw_e"))) return rc;
+    if ((on > 0 || og > 0) && (rc = pl.native ? launch_chain_narrow_bf16(h, 0, ce, ef, de, nf, dn, gf, dg, nullptr, A(0, ce.n_layers - 1), R, s, "bw_chain_fw_e")
+                                              : launch_chain_narrow(h, 0, ce, ef, de, nf, dn, gf, dg, A(0, ce.n_layers - 1), R, s, "bw_chain_fw_e"))) return rc;
   } else if (h->E > 0) {
     if ((rc = gnx_block_forward(h, &pl.sh.edge_block, ef, nf, gf, R, A(0, 0), nullptr, nullptr, base + pl.L.blk_fw.off, pl.L.blk_fw.bytes, 0, stream))) return rc;
     for (int i = 1; i < ce.n_layers; ++i)
@@ -1420,14 +1456,15 @@ int32_t ChainBwCtx::recompute() {
   ef_out = A(0, ce.n_layers - 1);
   nf_out = on > 0 ? A(1, cn.n_layers - 1) : nullptr;
   if ((fused & 2) && !chain_bw_node_fw_generic(fused, og)) {
-    if (og > 0 && (rc = launch_chain_narrow(h, 1, cn, ef_out, oe, nf, dn, gf, dg, A(1, cn.n_layers - 1), R, s, "bw_chain_fw_n"))) return rc;
+    if (og > 0 && (rc = pl.native ? launch_chain_narrow_bf16(h, 1, cn, ef_out, oe, nf, dn, gf, dg, nullptr, A(1, cn.n_layers - 1), R, s, "bw_chain_fw_n")
+                                  : launch_chain_narrow(h, 1, cn, ef_out, oe, nf, dn, gf, dg, A(1, cn.n_layers - 1), R, s, "bw_chain_fw_n"))) return rc;
   } else if (on > 0) {
     if ((rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s))) return rc;
     for (int i = 0; i < cn.n_layers; ++i)
       if ((rc = launch_chain_layer(h, 1, cn.layers[i], i ? A(1, i - 1) : Xn, i ? cn.widths[i - 1] : Kn, cn.widths[i], A(1, i), R, s, "bw_chain_fw_n"))) return rc;
   }
   if (og > 0) {
-    if ((rc = launch_fn_input(h, 2, ef_out, oe, nf_out, on, gf, dg, R, Xg, s))) return rc;
+    if ((rc = launch_fn_input(h, 2, ef_out, oe, nf_out, on, gf_rows, dg, R, Xg, s))) return rc;
     for (int i = 0; i < cg.n_layers && !(fused & 4); ++i)
       if ((rc = launch_chain_layer(h, 2, cg.layers[i], i ? A(2, i - 1) : Xg, i ? cg.widths[i - 1] : Kg, cg.widths[i], A(2, i), R, s, "bw_chain_fw_g"))) return rc;
   }
@@ -1524,7 +1561,7 @@ int32_t ChainBwCtx::fused_level(int t, const float* in0, int d0, const float* in
   const bool want = chain_wants_grads(c, gfn(t));
   io.part = want ? part : nullptr;
   { ProfScope ps(name, s);
-    if (int32_t r2 = launch_chain_bw_narrow(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
+    if (int32_t r2 = pl.native ? launch_chain_bw_narrow_bf16(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s) : launch_chain_bw_narrow(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
   return want ? chain_bw_narrow_finals(c, pl.sh.k0[t], chain_bw_narrow_shape(c, pl.sh.k0[t], pl.sh.trows[t]), R, part, gfn(t), s) : GNX_OK;
 }
 
@@ -1538,8 +1575,12 @@ int32_t ChainBwCtx::edge_fused() {
                                                                                            need_cols ? dXe : nullptr, de, d_ef && de > 0 ? d_ef : nullptr, nullptr}, "bw_delta_edge")) return rc;
   if (d_nf && dn > 0) {
     ProfScope ps("bw_dnf", s);
-    GNX_LAUNCH(k_bw_dnf<false>, dim3(chain_blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr, h->d_csr_ptr,
-               h->d_csr_eid, N, E, dn, d_nf);
+    if (pl.native)  // (with the node function's share, which shares() then leaves out)
+      GNX_LAUNCH(k_bw_dnf_share_last, dim3(chain_blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, on > 0 ? dXn : (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr,
+                 h->d_csr_ptr, h->d_csr_eid, N, E, dn, reinterpret_cast<bf16_t*>(d_nf));
+    else
+      GNX_LAUNCH(k_bw_dnf<false>, dim3(chain_blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr, h->d_csr_ptr,
+                 h->d_csr_eid, N, E, dn, d_nf);
   }
   if (d_gf && dg > 0) {
     ProfScope ps("bw_dgf", s);
@@ -1576,7 +1617,7 @@ int32_t ChainBwCtx::edge_generic() {
 // ---- the node / graph functions' own shares of d_nf, d_gf ----
 int32_t ChainBwCtx::shares() {
   int32_t rc;
-  if (d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, Kn, oe, pl.sh.rows[1], dn, d_nf, 1, s))) return rc;
+  if (!pl.native && d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, Kn, oe, pl.sh.rows[1], dn, d_nf, 1, s))) return rc;
   if (d_gf && dg > 0) {
     if (on > 0) {
       int64_t mn = 1;
@@ -1589,7 +1630,9 @@ int32_t ChainBwCtx::shares() {
 }
 
 // The fp32 launches of a pullback on its plan's layout, behind the two refusals that need the plan.  `c`: the call in fp32 — the caller's own
-// tensors, or a staged bf16 call's copies with ws_bytes = the fp32 layout's total.
+// tensors, or a staged bf16 call's copies with ws_bytes = the fp32 layout's total — or a native bf16 call as it came: the same launches in the
+// same order under the same names, the three fused levels and the recompute by the bf16 kernels, d_nf by k_bw_dnf_share_last (no add_cols into
+// it), d_gf accumulated in fp32 behind the layout and rounded once.  One k_bf16_widen (gf) and one k_bf16_round (d_gf) at the most, both graph-sized.
 int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   const gnx_graphs* h = c.h;
   const hipStream_t s = (hipStream_t)c.stream;
@@ -1597,7 +1640,7 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   if (pl.sh.ow[0] == 0) return fail(GNX_ERR_DIMS, "chain backward: not implemented for an edge function without output (the forward takes it; train such a block with one-layer update functions)");
   pl.lay_out(h);  // (a staged call has laid out, and comes here behind its own workspace check)
   int32_t rc;
-  if ((rc = check_ws(c.ws, c.ws_bytes, pl.base, pl.query))) return rc;
+  if ((rc = check_ws(c.ws, c.ws_bytes, pl.native ? pl.total : pl.base, pl.query))) return rc;
   if ((rc = gnx_ensure_wide_tables(h, c.stream))) return rc;
   if ((pl.fused & 1) && (rc = gnx_ensure_csr(h))) return rc;  // (k_bw_dnf's out-edge view; the query built it)
   ChainBwCtx x{h, pl, pl.p, pl.lnf.init_grads(c.grads), cf(c.ef), cf(c.nf), cf(c.gf), cf(c.g_ef_out), cf(c.g_nf_out), cf(c.g_gf_out), mf(c.d_ef), mf(c.d_nf), mf(c.d_gf),
@@ -1606,6 +1649,13 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   x.Xn = x.F(pl.L.Xn); x.Xg = x.F(pl.L.Xg); x.dXn = x.F(pl.L.dXn); x.dXg = x.F(pl.L.dXg); x.part = x.F(pl.L.part); x.wt = x.F(pl.L.wt);
   for (int i = 0; i < 3; ++i) x.gb[i] = x.F(pl.L.gbuf[i]);
   x.off2 = reinterpret_cast<int*>(x.base + pl.L.off2.off);
+  x.gf_rows = x.gf;
+  float* const d_gf_caller = x.d_gf;
+  if (pl.native) {
+    x.gf_rows = pl.nw.gf32.bytes ? x.F(pl.nw.gf32) : nullptr;
+    if (x.gf_rows && (rc = launch_bf16_widen(c.gf, pl.nw.gf32.bytes / sizeof(float), x.F(pl.nw.gf32), s))) return rc;
+    if (x.d_gf) x.d_gf = x.F(pl.nw.dgf32);
+  }
   pl.bind_ident(x.F(pl.L.ident));
   if ((rc = pl.lnf.fill(x.F(pl.L.ident), s))) return rc;
   if ((rc = x.recompute())) return rc;
@@ -1627,23 +1677,25 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   }
   if ((rc = (fused & 1) ? x.edge_fused() : x.edge_generic())) return rc;
   if ((rc = x.shares())) return rc;
+  if (pl.native && d_gf_caller && x.dg > 0 && (rc = launch_bf16_round(x.d_gf, pl.sh.rows[2] * (size_t)x.dg, d_gf_caller, s))) return rc;
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
 
 // One Chain pullback call: the refusals in their order — NULL handle or params, the parameters, (bf16) alignment, NULL features; nothing of the
-// handle but its counts is read before them.  An fp32 call then goes to the fp32 launches; a bf16 call lays out, checks its workspace, widens its
+// handle but its counts is read before them.  An fp32 call then goes to the fp32 launches, and so does a native bf16 call (narrow_typed: the call
+// came through gnx_chain_block_backward_narrow_typed, which alone may be native) on its own tensors; any other bf16 call lays out, checks its workspace, widens its
 // six inputs, runs the fp32 launches on the copies and rounds the three input gradients (gnx_staging.h); the parameter gradients are the fp32
 // pullback's own.
-int32_t chain_bw_run(const ChainBwCall& c, bool narrow) {
+int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = false) {
   if (!c.h || !c.p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow);
+  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow, narrow_typed);
   if (pl.rc) return c.elem == GNX_ELEM_BF16 ? pl.rc : GNX_ERR_DIMS;  // (fp32: one code for every refused parameter set; gnx_last_error() holds the reason)
   const void* bufs[9] = {c.ef, c.nf, c.gf, c.g_ef_out, c.g_nf_out, c.g_gf_out, c.d_ef, c.d_nf, c.d_gf};
   int32_t rc;
   if (pl.bf16 && (rc = check_bf16_aligned(bufs, 9))) return rc;
   if ((rc = chain_check_features(pl.sh, c.ef, c.nf, c.gf, "an input with non-zero width is NULL"))) return rc;
-  if (!pl.bf16) return chain_backward_fp32(c, pl);
+  if (!pl.bf16 || pl.native) return chain_backward_fp32(c, pl);
   pl.lay_out(c.h);
   if ((rc = check_ws(c.ws, c.ws_bytes, pl.total, pl.query))) return rc;
   const hipStream_t s = (hipStream_t)c.stream;
@@ -1655,8 +1707,8 @@ int32_t chain_bw_run(const ChainBwCall& c, bool narrow) {
 }
 
 // a _workspace_bytes entry: the plan's total; query_total builds what the pullback reads of the handle, outside any capture
-size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow) {
-  ChainBwPlan pl(h, p, R, elem, narrow);
+size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false) {
+  ChainBwPlan pl(h, p, R, elem, narrow, narrow_typed);
   pl.lay_out(h);  // (nothing for refused parameters: the total stays 0)
   return query_total(h, pl.total);
 }
@@ -1700,6 +1752,23 @@ int32_t gnx_chain_block_backward_typed(const gnx_graphs* h, const gnx_chain_bloc
   if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
   if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
   return chain_bw_run(ChainBwCall{h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, narrow != 0);
+}
+
+// gnx_chain_block_backward_narrow_typed: the narrow pullback on fp32 or bf16 features; bf16 inside chain_bw_typed_native runs on the bf16 tensors
+// themselves (ChainBwPlan::native), any other bf16 call is the typed entry's staged call with narrow = 1
+int32_t gnx_chain_block_backward_narrow_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  return elem == GNX_ELEM_BF16 && ChainBwPlan(h, p, R, elem, true, true).native ? 1 : 0;  // (the constructor reads the handle's counts alone)
+}
+
+size_t gnx_chain_block_backward_narrow_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  return elem == GNX_ELEM_F32 || elem == GNX_ELEM_BF16 ? chain_bw_query(h, p, R, elem, true, true) : 0;
+}
+
+int32_t gnx_chain_block_backward_narrow_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                              const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf,
+                                              const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
+  return chain_bw_run(ChainBwCall{h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true, true);
 }
 
 }  // extern "C"

@@ -97,6 +97,51 @@ __device__ __forceinline__ void chain_input_row(const ChainMlpArgs& a, size_t ro
   }
 }
 
+// ---- the same on bfloat16 feature rows (k_chain_mlp_bf16, k_chain_mlp_bw_bf16): which sources are bf16 stands at the head of their files ----
+// cur[at .. at + w) = widened p[0 .. w): one 16-bit load per element behind a uniform test
+template <int WMAX>
+__device__ __forceinline__ void chain_load_seg_bf16(const bf16_t* __restrict__ p, int at, int w, float (&cur)[WMAX]) {
+#pragma unroll
+  for (int k = 0; k < WMAX; ++k)
+    if (k >= at && k < at + w) cur[k] = bf16_lo(p[k - at]);
+}
+
+// chain_input_row on bf16 features; entries at or beyond K exactly 0.f
+template <int WMAX, int SRC>
+__device__ __forceinline__ void chain_input_row_bf16(const ChainMlpArgs& a, size_t row, size_t r, float (&cur)[WMAX]) {
+  if constexpr (SRC == SRC_ROWS) {
+    chain_input_row<WMAX, SRC_ROWS>(a, row, r, cur);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < WMAX; ++k) cur[k] = 0.f;
+  const bf16_t* __restrict__ b0 = reinterpret_cast<const bf16_t*>(a.a0);
+  const bf16_t* __restrict__ b1 = reinterpret_cast<const bf16_t*>(a.a1);
+  const bf16_t* __restrict__ b2 = reinterpret_cast<const bf16_t*>(a.a2);
+  if constexpr (SRC == SRC_EDGE) {
+    const int e = (int)row;
+    if (a.d0 > 0) chain_load_seg_bf16<WMAX>(b0 + (r * (size_t)a.E + e) * a.d0, 0, a.d0, cur);
+    if (a.d1 > 0) {
+      chain_load_seg_bf16<WMAX>(b1 + (r * (size_t)a.N + a.rowval[e]) * a.d1, a.d0, a.d1, cur);
+      chain_load_seg_bf16<WMAX>(b1 + (r * (size_t)a.N + a.edge_dst[e]) * a.d1, a.d0 + a.d1, a.d1, cur);
+    }
+    if (a.d2 > 0) chain_load_seg_bf16<WMAX>(b2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, e)) * a.d2, a.d0 + 2 * a.d1, a.d2, cur);
+  } else {
+    const int n = (int)row;
+    if (a.d0 > 0) {  // the fp32 ef' of this call: chain_input_row's sequential adds in CSC order
+      const int e1 = a.colptr[n + 1];
+      for (int e = a.colptr[n]; e < e1; ++e) {
+        const float* __restrict__ p = a.a0 + (r * (size_t)a.E + e) * a.d0;
+#pragma unroll
+        for (int k = 0; k < WMAX; ++k)
+          if (k < a.d0) cur[k] += p[k];
+      }
+    }
+    if (a.d1 > 0) chain_load_seg_bf16<WMAX>(b1 + (r * (size_t)a.N + n) * a.d1, a.d0, a.d1, cur);
+    if (a.d2 > 0) chain_load_seg_bf16<WMAX>(b2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, n)) * a.d2, a.d0 + a.d1, a.d2, cur);
+  }
+}
+
 // cur <- layer(cur): a Dense (op 0..4, its activation) or a LayerNorm (op 5 / 6) of k_in inputs and `width` outputs whose staged parameters
 // start at s_par + off; returns the next layer's offset.  Products run as groups of 4 outputs x 4 inputs behind wave-uniform tests; entries at or beyond `width` end exactly 0.f.
 template <int WMAX>

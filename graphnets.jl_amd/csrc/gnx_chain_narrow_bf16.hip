@@ -22,53 +22,11 @@ namespace gnx {
 
 struct ChainMlpBf16Args {
   ChainMlpArgs f;  // f.a0 .. f.a2: bf16 where the head of this file says so (declared float, like the feature pointers of BlockArgs); f.out unused
-  bf16_t* out;     // [R][rows][ow] bf16
+  bf16_t* out;     // [R][rows][ow] bf16, or nullptr
   float* out32;    // [R][rows][ow] fp32, or nullptr
 };
 
-// cur[at .. at + w) = widened p[0 .. w): one 16-bit load per element behind a uniform test
-template <int WMAX>
-__device__ __forceinline__ void chain_load_seg_bf16(const bf16_t* __restrict__ p, int at, int w, float (&cur)[WMAX]) {
-#pragma unroll
-  for (int k = 0; k < WMAX; ++k)
-    if (k >= at && k < at + w) cur[k] = bf16_lo(p[k - at]);
-}
-
-// chain_input_row on bf16 features; entries at or beyond K exactly 0.f
-template <int WMAX, int SRC>
-__device__ __forceinline__ void chain_input_row_bf16(const ChainMlpArgs& a, size_t row, size_t r, float (&cur)[WMAX]) {
-  if constexpr (SRC == SRC_ROWS) {
-    chain_input_row<WMAX, SRC_ROWS>(a, row, r, cur);
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < WMAX; ++k) cur[k] = 0.f;
-  const bf16_t* __restrict__ b0 = reinterpret_cast<const bf16_t*>(a.a0);
-  const bf16_t* __restrict__ b1 = reinterpret_cast<const bf16_t*>(a.a1);
-  const bf16_t* __restrict__ b2 = reinterpret_cast<const bf16_t*>(a.a2);
-  if constexpr (SRC == SRC_EDGE) {
-    const int e = (int)row;
-    if (a.d0 > 0) chain_load_seg_bf16<WMAX>(b0 + (r * (size_t)a.E + e) * a.d0, 0, a.d0, cur);
-    if (a.d1 > 0) {
-      chain_load_seg_bf16<WMAX>(b1 + (r * (size_t)a.N + a.rowval[e]) * a.d1, a.d0, a.d1, cur);
-      chain_load_seg_bf16<WMAX>(b1 + (r * (size_t)a.N + a.edge_dst[e]) * a.d1, a.d0 + a.d1, a.d1, cur);
-    }
-    if (a.d2 > 0) chain_load_seg_bf16<WMAX>(b2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, e)) * a.d2, a.d0 + 2 * a.d1, a.d2, cur);
-  } else {
-    const int n = (int)row;
-    if (a.d0 > 0) {  // the fp32 ef' of this call: chain_input_row's sequential adds in CSC order
-      const int e1 = a.colptr[n + 1];
-      for (int e = a.colptr[n]; e < e1; ++e) {
-        const float* __restrict__ p = a.a0 + (r * (size_t)a.E + e) * a.d0;
-#pragma unroll
-        for (int k = 0; k < WMAX; ++k)
-          if (k < a.d0) cur[k] += p[k];
-      }
-    }
-    if (a.d1 > 0) chain_load_seg_bf16<WMAX>(b1 + (r * (size_t)a.N + n) * a.d1, a.d0, a.d1, cur);
-    if (a.d2 > 0) chain_load_seg_bf16<WMAX>(b2 + (r * (size_t)a.G + segment_of(a.seg_off, a.G, n)) * a.d2, a.d0 + a.d1, a.d2, cur);
-  }
-}
+// (chain_input_row_bf16, the gather of a bf16 input row: gnx_chain_mlp.h — the pullback kernel of gnx_chain_bw_narrow_bf16.hip builds its row with it too)
 
 template <int WMAX, int SRC>
 __global__ __launch_bounds__(256) void k_chain_mlp_bf16(ChainMlpBf16Args t) {
@@ -91,10 +49,12 @@ __global__ __launch_bounds__(256) void k_chain_mlp_bf16(ChainMlpBf16Args t) {
   }
 
   const size_t at = (r * a.rows + row) * (size_t)a.ow;
-  bf16_t* __restrict__ o = t.out + at;
+  if (t.out) {  // (uniform; the pullback's recompute wants the fp32 rows alone)
+    bf16_t* __restrict__ o = t.out + at;
 #pragma unroll
-  for (int k = 0; k < WMAX; ++k)
-    if (k < a.ow) o[k] = to_bf16(cur[k]);
+    for (int k = 0; k < WMAX; ++k)
+      if (k < a.ow) o[k] = to_bf16(cur[k]);
+  }
   if (t.out32) {
     float* __restrict__ o32 = t.out32 + at;
 #pragma unroll
@@ -103,8 +63,8 @@ __global__ __launch_bounds__(256) void k_chain_mlp_bf16(ChainMlpBf16Args t) {
   }
 }
 
-// launch_chain_narrow on bf16 features (which of in0 .. in2 are bf16: the head of this file); out: bf16 rows, out32: the same rows in fp32 or
-// nullptr.  The caller asked chain_narrow_takes.
+// launch_chain_narrow on bf16 features (which of in0 .. in2 are bf16: the head of this file); out: bf16 rows or nullptr, out32: the same rows in
+// fp32 or nullptr.  The caller asked chain_narrow_takes.
 int32_t launch_chain_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
                                  void* out, float* out32, int64_t R, hipStream_t s, const char* name) {
   ChainMlpBf16Args t{};

@@ -1,5 +1,5 @@
 // Everything about a call of a GNBlock with Chain update functions that is arithmetic on counts and widths: the shape of the call, the two fused
-// rules with the LDS plans behind them, the fused mask, and the two workspace layouts.  Plain C++17 host code — no HIP, nothing of a handle but
+// rules with the LDS plans behind them, the fused mask, the two native bf16 rules, and the workspace layouts.  Plain C++17 host code — no HIP, nothing of a handle but
 // its three counts — so that tests/test_chain_plan_cpu.py compiles it alone.  The plans of a call (ChainPlan, gnx_staging.h) are built from these.
 #pragma once
 #include <stddef.h>
@@ -234,6 +234,27 @@ inline ChainBwLayout chain_bw_layout(const ChainShape& s, unsigned fused, size_t
   L.dxe = c.floats((fused & 1) ? s.rows[0] * (size_t)(2 * s.dn + s.dg) : 0);
   L.total = c.o + 256;
   return L;
+}
+
+// bfloat16 features, the pullback's native path (gnx_chain_block_backward_narrow_typed): the edge function has an output and edges to run on
+// (there is no pullback without), and every update function with an output and rows to run on is inside the pullback's fused rule (`fused`: the
+// mask of CHAIN_RULE_BW).  Then every function is one k_chain_mlp_bw_bf16 launch on the bf16 rows, chain_bw_node_fw_generic cannot occur, and no
+// E- or N-sized tensor is widened or rounded by a pass of its own.  A mixed mask stays staged.
+inline bool chain_bw_typed_native(const ChainShape& s, unsigned fused, bool bf16) {
+  return bf16 && s.ow[0] > 0 && s.trows[0] > 0 && chain_typed_native(s, fused);
+}
+// ... and its workspace: the fp32 narrow layout (chain_bw_layout with the same mask, fp32_total bytes) and behind it two graph-sized fp32 carves
+// of R G dg floats — the widened gf, which the graph function's input rows (Xg) are assembled from, and the fp32 d_gf the per-graph column sums
+// accumulate into before it is rounded once.  (The upstream gradients are read as bf16 by the kernels: none is widened.)
+struct ChainBwNativeWs { ChainCarve gf32, dgf32; size_t total; };
+inline ChainBwNativeWs chain_bw_native_layout(const ChainShape& s, size_t fp32_total) {
+  ChainBwNativeWs w{};
+  ChainCarver c;
+  c.o = ChainCarver::up(fp32_total);
+  w.gf32 = c.floats(s.ow[2] > 0 ? s.rows[2] * (size_t)s.dg : 0);
+  w.dgf32 = c.floats(s.rows[2] * (size_t)s.dg);
+  w.total = c.o;
+  return w;
 }
 
 }  // namespace gnx

@@ -180,8 +180,8 @@ int32_t launch_core_post_train(const void* x, size_t rows, int d, const gnx_laye
 int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                             float* out, int64_t R, hipStream_t s, const char* name);
 // ---- gnx_chain_narrow_bf16.hip: the same on bf16 features (gnx_chain_block_forward_typed's native path) ----
-// entity 0: in0 / in1 / in2 are bf16; 1: in0 is the fp32 ef' of this call, in1 / in2 are bf16; 2: in0 is fp32.  out: bf16 rows; out32: the same rows
-// unrounded in fp32, or nullptr.  The caller asked chain_narrow_takes.
+// entity 0: in0 / in1 / in2 are bf16; 1: in0 is the fp32 ef' of this call, in1 / in2 are bf16; 2: in0 is fp32.  out: bf16 rows, or nullptr
+// (the pullback's recompute); out32: the same rows unrounded in fp32, or nullptr.  The caller asked chain_narrow_takes.
 int32_t launch_chain_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
                                  void* out, float* out32, int64_t R, hipStream_t s, const char* name);
 
@@ -197,6 +197,10 @@ struct ChainBwNarrowIo {
 // entity / in0..in2 as launch_chain_narrow.  The caller asked chain_bw_narrow_takes and opens the ProfScope.
 int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                                const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
+// ---- gnx_chain_bw_narrow_bf16.hip: the same on bf16 features (gnx_chain_block_backward_narrow_typed's native path) ----
+// in0 .. in2 as launch_chain_narrow_bf16; io.G and io.direct hold bfloat16 elements (declared float), io.ex1, io.ex2, io.dx and io.part are fp32
+int32_t launch_chain_bw_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
+                                    const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
 
 // ---- gnx_forward.hip: the validation of a core forward, for the training-mode entries of gnx_dropout.hip (a FormScope of the call's flags open) ----
 int32_t core_forward_check_dims(const gnx_core_params* p);  // (needs no handle)

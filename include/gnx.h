@@ -609,7 +609,7 @@ GNX_API int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_c
  * the input gradients); parameter gradients stay float32.  `narrow` (0 or 1): gnx_chain_block_backward (0) or gnx_chain_block_backward_narrow
  * (1).  GNX_ELEM_F32 IS the mirrored entry (same validation, workspace size, bits); another elem than F32 / BF16 or a narrow other than 0 / 1:
  * GNX_ERR_INVALID_ARG before any GPU work, 0 from the query.  A bf16 buffer must be 4-byte aligned (GNX_ERR_INVALID_ARG before any GPU work).
- * GNX_ELEM_BF16 is staged, there is no bf16 pullback kernel: the six inputs and upstream gradients are widened into fp32 copies (256-byte
+ * GNX_ELEM_BF16 is staged here (the bf16 pullback kernel runs behind gnx_chain_block_backward_narrow_typed, below): the six inputs and upstream gradients are widened into fp32 copies (256-byte
  * aligned carves behind the fp32 pullback's workspace), the fp32 pullback runs on them, the three input gradients are rounded back.  d_ef, d_nf,
  * d_gf are bit for bit to_bf16(ref) and every parameter gradient is bit for bit ref's, ref the mirrored fp32 pullback on the exactly widened
  * tensors in 16-byte-aligned buffers.  Optional outputs and NULL upstream gradients as in the fp32 entries.  The workspace is the mirrored
@@ -621,6 +621,33 @@ GNX_API int32_t gnx_chain_block_backward_typed(const gnx_graphs* h, const gnx_ch
                                                const void* gf, const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t n_replicas,
                                                void* d_ef, void* d_nf, void* d_gf, const gnx_chain_block_grads* grads, void* workspace,
                                                size_t workspace_bytes, int32_t narrow, void* stream);
+/* gnx_chain_block_backward_narrow on float32 or bfloat16 features, bfloat16 NATIVELY where the whole block is narrow (k_chain_mlp_bw_bf16,
+ * csrc/gnx_chain_bw_narrow_bf16.hip: k_chain_mlp_bw's body with bf16 feature-shaped operands — the rows gathered and the upstream gradient read
+ * with one 16-bit load per element and widened exactly, d_ef rounded to nearest even once and written with one 16-bit store per element; the
+ * tape, the accumulators and every arithmetic operation are the fp32 kernel's).  `elem` applies to the nine feature-shaped tensors; parameter
+ * gradients stay float32.  The argument list is gnx_chain_block_backward_typed's without `narrow`.
+ * The native rule: elem = GNX_ELEM_BF16, the edge function has an output and E > 0, and every update function with a non-zero output width and
+ * rows to run on is in gnx_chain_block_backward_narrow_applies' mask.  Then every function is one launch of that kernel on the bf16 rows; ef' and
+ * nf' are recomputed by k_chain_mlp_bf16 into the fp32 layout alone; d_nf is summed in the fp32 pullback's order (0, the in-edges, the out-edges,
+ * the node function's own share) and rounded once; d_gf accumulates in fp32 and is rounded once.  No E- or N-sized tensor is widened or rounded
+ * by a pass of its own: the workspace is gnx_chain_block_backward_narrow's plus two 256-byte-aligned carves of R G dg floats (the widened gf, the
+ * fp32 d_gf), and the call launches one k_bf16_widen and one k_bf16_round at the most, both graph-sized (the staged call: six and three).
+ * d_ef, d_nf, d_gf and every parameter gradient are bit for bit gnx_chain_block_backward_typed(narrow = 1)'s on the same nine tensors.
+ * No class is cut from the native rule (whole calls on the eight shapes of profiles/chain_bw_native.json against the staged call).
+ * GNX_ELEM_F32 IS gnx_chain_block_backward_narrow (same validation, workspace size, bits).  GNX_ELEM_BF16 outside the native rule — a mixed
+ * mask, no edges — IS gnx_chain_block_backward_typed(narrow = 1) (same workspace size, same bits); a bf16 call's workspace refusal names
+ * gnx_chain_block_backward_narrow_typed_workspace_bytes() either way.  _applies: 1 exactly on the native path, 0 otherwise (GNX_ELEM_F32 and bad
+ * arguments included).  Another elem than F32 / BF16: GNX_ERR_INVALID_ARG before any GPU work, 0 from the queries.  A bf16 buffer must be
+ * 4-byte aligned; optional outputs, NULL upstream gradients and the order of refusals as in gnx_chain_block_backward_typed.  The query builds
+ * the handle's tables, the out-edge (CSR) view included — call it outside a stream capture; the call allocates nothing, does not synchronise,
+ * uses one stream and works inside a capture. */
+GNX_API int32_t gnx_chain_block_backward_narrow_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_chain_block_backward_narrow_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas,
+                                                                     int32_t elem);
+GNX_API int32_t gnx_chain_block_backward_narrow_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef,
+                                                      const void* nf, const void* gf, const void* g_ef_out, const void* g_nf_out,
+                                                      const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
+                                                      const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Backward of (m::GNCore)(x) = x + block(gn1(x)) + ffwd(gn2(x)) (src/gncore.jl:56-68).  Takes the forward's INPUTS and the
  * upstream gradients; the intermediates (both LayerNorms, the block's outputs, the FeedForward hidden activations) are
