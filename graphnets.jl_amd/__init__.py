@@ -5,7 +5,7 @@ The directory name follows the project naming contract and is not a valid Python
 """
 from . import _lib
 from ._lib import GnxError, LIB_PATH, profile_calibrate, profile_enable, profile_read, profile_reset
-from .api import (NT, BlockPlan, Chain, Dense, Dropout, Graphed, Model, GNBlock, GNCore, GNCoreList, GNFeedForward, GNGraphBatch, GNGraphNorm, LayerNorm, batch,
+from .api import (NT, BlockPlan, Chain, ChainDropout, chain_dropout_mask, Dense, Dropout, Graphed, Model, GNBlock, GNCore, GNCoreList, GNFeedForward, GNGraphBatch, GNGraphNorm, LayerNorm, batch,
                   efview, flatunpaddedef, flatunpaddednf, getedgefninput, getgraphfninput, getnodefninput, gfview, nfview,
                   collapsef, dropout_mask, flatunpaddedcollapsedef, logitcrossentropy, padded, testmode, trainmode, unbatch, unpadded, unpaddedcollapsedef, zerodim2nothing)
 

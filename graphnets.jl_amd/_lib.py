@@ -39,6 +39,7 @@ class Dense(C.Structure):
 
 
 LAYER_DENSE, LAYER_LAYERNORM, LAYER_LN_SQRT_EPS = 0, 1, 0x100
+LAYER_DROPOUT = 2  # a Dropout(p) entry of a Chain: the *_train entries alone take it
 
 
 class BlockParams(C.Structure):
@@ -93,6 +94,10 @@ class CoreParams(C.Structure):
 
 class Dropout(C.Structure):  # gnx_dropout
     _fields_ = [("p", C.c_float), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class ChainDropout(C.Structure):  # gnx_chain_dropout: the per-call record of the Dropout entries inside a block's Chains
+    _fields_ = [("seed", C.c_uint64), ("p", C.POINTER(C.c_float) * 3)]
 
 
 class Layer(C.Structure):
@@ -161,6 +166,13 @@ SIGNATURES = {
     "gnx_chain_block_backward_narrow_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
     "gnx_chain_block_backward_narrow_typed": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int32] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
                                               [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnx_chain_dropout_mask": (C.c_int32, [C.POINTER(ChainDropout), C.c_int32, C.c_int32, C.c_float, C.c_int64, _fp, C.c_void_p]),
+    "gnx_chain_block_train_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
+    "gnx_chain_block_forward_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
+    "gnx_chain_block_forward_train": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.POINTER(ChainDropout)] + _FWD[2:11] + [C.c_int32, C.c_uint32, C.c_void_p]),
+    "gnx_chain_block_backward_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
+    "gnx_chain_block_backward_train": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.POINTER(ChainDropout)] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
+                                       [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     "gnx_block_forward_chained": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams)] + _FWD[2:] + [C.POINTER(PendingUpdate), C.POINTER(PendingUpdate)]),
     "gnx_block_forward_steps": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.POINTER(BlockStep), C.c_int64, C.c_int64, C.c_uint32, C.c_void_p]),
     "gnx_block_forward_steps_typed": (C.c_int32, [C.c_void_p, C.POINTER(BlockParams), C.c_int32, C.POINTER(BlockStep), C.c_int64, C.c_int64, C.c_uint32,

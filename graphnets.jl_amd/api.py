@@ -747,8 +747,9 @@ class Chain:
       * an activation function as a layer (`"relu"`, `torch.tanh`, ... — Flux: `Chain(Dense(a => b), relu)`) becomes the activation of the `Dense`
         in front of it when that one has none — `relu.(W x .+ b)` either way;
       * `"identity"` / `None` is dropped;
-      * `Dropout(p)` is the identity in test mode and dropped; a differentiable call of a block whose chains hold a Dropout with p > 0 is refused
-        (the training-mode Dropout of this library is the FeedForward's: GNCore(dims; dropout)).
+      * `Dropout(p)` is the identity in test mode and dropped from `layers`; where it stood is kept in `dropouts` — (number of layers in front
+        of it, p) per Dropout.  A differentiable call of a block whose chains hold a Dropout with p > 0 is refused unless the block's
+        `chain_dropout` switch is on: then the Dropouts are applied in training mode (gnx_chain_block_forward_train / _backward_train).
       * a `LayerNorm(d)` layer value normalises the rows of the layer in front of it (`Chain(Dense(a => d, relu), LayerNorm(d), Dense(d => b))`):
         a row-wise launch of its own, differentiable (gamma / beta gradients); as the EDGE function's first layer it runs behind an identity Dense
         that the library puts in front (the fused first launch then writes getedgefninput itself).
@@ -756,7 +757,7 @@ class Chain:
 
     def __init__(self, *layers):
         given = list(layers[0]) if len(layers) == 1 and isinstance(layers[0], (list, tuple)) else list(layers)
-        self.layers, self.dropout_p = [], 0.0
+        self.layers, self.dropout_p, self.dropouts = [], 0.0, []
         for l in given:
             if isinstance(l, (Dense, LayerNorm)):
                 self.layers.append(l)
@@ -764,6 +765,7 @@ class Chain:
                 continue
             elif isinstance(l, Dropout):
                 self.dropout_p = max(self.dropout_p, l.p)
+                self.dropouts.append((len(self.layers), l.p))
             elif (isinstance(l, str) and l in _lib.ACT) or (callable(l) and l in _ACT_CALLABLES):
                 name = l if isinstance(l, str) else _ACT_CALLABLES[l]
                 if not self.layers or not isinstance(self.layers[-1], Dense) or self.layers[-1].act != "identity":
@@ -779,9 +781,36 @@ class Chain:
     def __len__(self):
         return len(self.layers)
 
+    def _entries(self):
+        """the entries of a training call's gnx_chain in the order the user wrote them: ("layer", Dense | LayerNorm) and ("dropout", p)"""
+        out = []
+        for i in range(len(self.layers) + 1):
+            out += [("dropout", p) for after, p in getattr(self, "dropouts", ()) if after == i]
+            if i < len(self.layers):
+                out.append(("layer", self.layers[i]))
+        return out
+
     @property
     def out_width(self):
         return int(self.layers[-1].weight.shape[0]) if self.layers else 0
+
+
+class ChainDropout:
+    """The gnx_chain_dropout record of one call of a GNBlock whose Chains hold Dropouts (`blk.last_chain_dropout`): the call's seed and, per
+    update function (0 edge, 1 node, 2 graph), one p per entry of the call's chain — the user's layers with the Dropouts where they stood; 0
+    where the entry is no Dropout.  The masks are never stored: `chain_dropout_mask` regenerates them from this record."""
+
+    def __init__(self, seed, p):
+        self.seed, self.p = int(seed), [[float(v) for v in q] for q in p]
+
+    def _c(self, keep):
+        d = _lib.ChainDropout()
+        d.seed = self.seed
+        for t, q in enumerate(self.p):
+            arr = (C.c_float * max(len(q), 1))(*q)
+            keep.append(arr)
+            d.p[t] = C.cast(arr, C.POINTER(C.c_float))
+        return d
 
 
 class LayerNorm:
@@ -917,10 +946,18 @@ class GNBlock:
     needs `bf16_chain` and `bf16_backward`) is gnx_chain_block_backward_narrow_typed.  Where the whole block is inside the narrow pullback's
     rule, each update function is pulled back in one kernel that reads the bf16 rows and upstream gradients and writes the bf16 edge gradient
     itself: no edge- or node-sized fp32 copy is made, and the gradients are bit for bit those of gnx_chain_block_backward_typed with
-    `narrow_chain_backward`.  Elsewhere the call is that staged pullback.  Off (the default), and on float32 features, nothing changes."""
+    `narrow_chain_backward`.  Elsewhere the call is that staged pullback.  Off (the default), and on float32 features, nothing changes.
+
+    `chain_dropout` (also a plain attribute): `Dropout(p)` layers inside the update-function Chains are applied in training mode.  A call with an
+    active Dropout — some p > 0, and inside a gradient call or forced by `trainmode` / `testmode` — runs gnx_chain_block_forward_train and, where
+    differentiable, gnx_chain_block_backward_train (`narrow` = `narrow_chain` / `narrow_chain_backward`: each function inside the training rule
+    in one kernel that regenerates its masks in registers).  Every call draws a fresh seed (from `rng` if set; torch.manual_seed reproduces it) and
+    keeps the record in `last_chain_dropout` (`chain_dropout_mask` turns it into masks).  A call without an active Dropout runs what it ran before.
+    float32 features only: bfloat16 features with an active chain Dropout raise NotImplementedError.  Off (the default): a differentiable call of a
+    block whose chains hold a Dropout(p > 0) raises NotImplementedError, as before."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
-                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False):
+                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False, chain_dropout=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -939,6 +976,7 @@ class GNBlock:
         self.narrow_chain_backward = bool(narrow_chain_backward)
         self.bf16_chain = bool(bf16_chain)
         self.native_chain_backward = bool(native_chain_backward)
+        self.chain_dropout = bool(chain_dropout)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1000,6 +1038,63 @@ class GNBlock:
             outw.append(widths[-1] if widths else 0)
         return p, chains, outw
 
+    def _chain_dropout_now(self, chains, grad_call):
+        """The record of the Dropouts inside this block's Chains for THIS call: None (identity: the call runs what it ran before) or a ChainDropout
+        with a fresh seed.  Flux's rule: active inside a gradient call, identity otherwise, unless `testmode` / `trainmode` forced it."""
+        if not getattr(self, "chain_dropout", False) or not any(p > 0 for ch in chains for _, p in getattr(ch, "dropouts", ())):
+            return None
+        forced = getattr(self, "_dropout_mode", None)
+        if not (grad_call if forced is None else forced):
+            return None
+        for ch in chains:
+            kinds = [k for k, _ in ch._entries()]
+            if kinds[:1] == ["dropout"] or any(a == b == "dropout" for a, b in zip(kinds, kinds[1:])):
+                raise NotImplementedError("GNBlock: a Dropout as the first layer of an update-function Chain or right behind another Dropout is not "
+                                          "supported in training mode (gnx_chain_block_forward_train: a Dropout entry follows a Dense or LayerNorm)")
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=getattr(self, "rng", None)).item())  # torch.manual_seed reproduces it
+        self.last_chain_dropout = ChainDropout(seed, [[v if k == "dropout" else 0.0 for k, v in ch._entries()] for ch in chains])
+        return self.last_chain_dropout
+
+    def _chain_train_params(self, keep):
+        """_chain_params for a training call: the chains with their Dropout entries where the user wrote them (GNX_LAYER_DROPOUT: no weight, no
+        bias, the width of the entry in front)"""
+        chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
+        p = _lib.ChainBlockParams()
+        p.de, p.dn, p.dg = self.in_dims
+        outw = []
+        for name, ch in zip(("edgefn", "nodefn", "graphfn"), chains):
+            entries, widths = [], []
+            for kind, l in ch._entries():
+                widths.append(widths[-1] if kind == "dropout" else int(l.weight.shape[0]))
+                entries.append(_lib.Dense(None, None, _lib.ACT["identity"], _lib.LAYER_DROPOUT) if kind == "dropout" else l._c_layer(keep))
+            arr = (_lib.Dense * max(len(entries), 1))(*entries)
+            wid = (C.c_int32 * max(len(entries), 1))(*widths)
+            keep += [arr, wid]
+            c = getattr(p, name)
+            c.layers, c.widths, c.n_layers = arr, wid, len(entries)
+            outw.append(widths[-1] if widths else 0)
+        return p, chains, outw
+
+    def _chain_train_forward(self, g, R, flags, rec, ef, nf, gf):
+        """gnx_chain_block_forward_train under the record `rec` (narrow = `narrow_chain`)"""
+        lib = _lib.load()
+        keep = []
+        p, chains, outw = self._chain_train_params(keep)
+        dev = g.device
+        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.float32, device=dev) if d > 0 else None
+        eo, no, go = mk(g.n_edges, outw[0]), mk(g.n_nodes, outw[1]), mk(g.n_graphs, outw[2])
+        narrow = int(bool(getattr(self, "narrow_chain", False)))
+        with torch.cuda.device(dev):
+            nbytes = lib.gnx_chain_block_forward_train_workspace_bytes(g._h, C.byref(p), R, narrow)
+            if nbytes == 0:
+                raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
+            ws = g.workspace(nbytes, ("chain_train", narrow, self.in_dims, tuple(tuple(k if k == "dropout" else int(l.weight.shape[0]) for k, l in ch._entries())
+                                                                                 for ch in chains), R))
+            drop = rec._c(keep)
+            check(lib.gnx_chain_block_forward_train(g._h, C.byref(p), C.byref(drop), _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
+                                                    ws.data_ptr(), ws.numel(), narrow, flags, torch.cuda.current_stream(dev).cuda_stream))
+        return eo, no, go
+
     def _chain_forward(self, g, R, flags, ef, nf, gf, bf16=False):
         lib = _lib.load()
         keep = []
@@ -1034,8 +1129,16 @@ class GNBlock:
         flags = self.flags if flags is None else flags
         chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
         params = [t for ch in chains for l in ch.layers for t in (l.weight, l.bias)]
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [ef, nf, gf] + params):
-            if any(ch.dropout_p > 0 for ch in chains):
+        grad_call = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [ef, nf, gf] + params)
+        rec = self._chain_dropout_now(chains, grad_call)
+        if rec is not None:  # `chain_dropout` and an active Dropout: the training entries
+            if grad_call:
+                outs = iter(_ChainBlockTrainFn.apply(self, g, R, flags, rec, ef, nf, gf, *params))
+                eo, no, go = (next(outs) if ch.out_width > 0 else None for ch in chains)
+            else:
+                eo, no, go = self._chain_train_forward(g, R, flags, rec, ef, nf, gf)
+        elif grad_call:
+            if any(ch.dropout_p > 0 for ch in chains) and not (getattr(self, "chain_dropout", False) and getattr(self, "_dropout_mode", None) is False):
                 raise NotImplementedError("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
                                           "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
             outs = iter(_ChainBlockFn.apply(self, g, R, flags, ef, nf, gf, *params))
@@ -1052,6 +1155,9 @@ class GNBlock:
         params = [t for ch in chains for l in ch.layers for t in (l.weight, l.bias)]
         feats = [a for a in (xt.ef, xt.nf, xt.gf) if isinstance(a, torch.Tensor)]
         trainable = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in feats + params)
+        if getattr(self, "chain_dropout", False) and getattr(self, "_dropout_mode", None) is True and any(ch.dropout_p > 0 for ch in chains):
+            raise NotImplementedError("GNBlock: an active Dropout inside an update-function Chain on bfloat16 features is not implemented "
+                                      "(gnx_chain_block_forward_train is float32); use testmode(blk) or float32 features")
         if trainable:
             if not getattr(self, "bf16_backward", False):
                 raise NotImplementedError("GNBlock: the backward of a Chain block on bfloat16 features is not implemented unless the block's bf16_backward "
@@ -1278,6 +1384,81 @@ class _ChainBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gouts):
         return _chain_block_pullback(ctx, gouts, _lib.ELEM_F32)
+
+
+class _ChainBlockTrainFn(torch.autograd.Function):
+    """_ChainBlockFn with active Dropouts inside the Chains (GNBlock.chain_dropout): forward = gnx_chain_block_forward_train, backward =
+    gnx_chain_block_backward_train under the same record — the masks are regenerated, never stored (narrow = the block's `narrow_chain` /
+    `narrow_chain_backward`)."""
+
+    @staticmethod
+    def forward(ctx, block, g, R, flags, rec, ef, nf, gf, *params):
+        eo, no, go = block._chain_train_forward(g, R, flags, rec, ef, nf, gf)
+        ctx.block, ctx.g, ctx.R, ctx.rec = block, g, R, rec
+        ctx.slots = tuple(t is not None for t in (ef, nf, gf))
+        ctx.save_for_backward(*[t for t in (ef, nf, gf) if t is not None])
+        ctx.present = tuple(o is not None for o in (eo, no, go))
+        return tuple(o for o in (eo, no, go) if o is not None)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        lib = _lib.load()
+        block, g, R = ctx.block, ctx.g, ctx.R
+        sv = iter(ctx.saved_tensors)
+        ef, nf, gf = (next(sv) if present else None for present in ctx.slots)
+        it = iter(gouts)
+        ge, gn_, gg = (None if t is None else t.contiguous() for t in (next(it) if pr else None for pr in ctx.present))
+        keep = []
+        p, chains, _ = block._chain_train_params(keep)
+        dev = g.device
+        need = ctx.needs_input_grad  # (block, g, R, flags, rec, ef, nf, gf, W, b, W, b, ...)
+        d_ef = torch.empty_like(ef) if ef is not None and need[5] else None
+        d_nf = torch.empty_like(nf) if nf is not None and need[6] else None
+        d_gf = torch.empty_like(gf) if gf is not None and need[7] else None
+        gW, gb, arrays, k = [], [], [], 8
+        for ch in chains:
+            entries = []  # one gnx_dense_grad per entry of the call's chain; a Dropout entry's slot is ignored
+            for kind, l in ch._entries():
+                if kind == "dropout":
+                    entries.append(_lib.DenseGrad(None, None))
+                    continue
+                ln = isinstance(l, LayerNorm)  # (its "weight" slot is gamma [d])
+                w = (torch.empty_like(l.gamma) if ln else torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev)) if need[k] else None
+                b = torch.empty_like(l.bias) if (l.bias is not None and need[k + 1]) else None
+                k += 2
+                gW.append(w); gb.append(b)
+                entries.append(_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None))
+            arrays.append((_lib.DenseGrad * max(len(entries), 1))(*entries))
+        grads = _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays])
+        narrow = int(bool(getattr(block, "narrow_chain_backward", False)))
+        with torch.cuda.device(dev):
+            nb = lib.gnx_chain_block_backward_train_workspace_bytes(g._h, C.byref(p), R, narrow)
+            if nb == 0:
+                raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
+            ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+            drop = ctx.rec._c(keep)
+            check(lib.gnx_chain_block_backward_train(g._h, C.byref(p), C.byref(drop), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
+                                                     _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), narrow,
+                                                     torch.cuda.current_stream(dev).cuda_stream))
+        out = [None, None, None, None, None, d_ef, d_nf, d_gf]
+        for w, b in zip(gW, gb):
+            out += [None if w is None else (w if w.dim() == 1 else w.t()), b]
+        return tuple(out)
+
+
+def chain_dropout_mask(record, function, layer, shape, device=None):
+    """The mask a training call of a Chain block applied at entry `layer` of update function `function` (0 edge, 1 node, 2 graph) — `layer`
+    counts the entries of the call's chain, the Dropouts where the user wrote them — under `record` (`blk.last_chain_dropout`): a (w, T, R)
+    array of 0 and 1 / (1 - p), the layout of the features (gnx_chain_dropout_mask)."""
+    dev = _device(device)
+    d, T, R = (int(v) for v in shape)
+    out = torch.empty((R, T, d), dtype=torch.float32, device=dev)
+    keep = []
+    rec = record._c(keep)
+    with torch.cuda.device(dev):
+        check(_lib.load().gnx_chain_dropout_mask(C.byref(rec), int(function), int(layer), float(record.p[int(function)][int(layer)]), out.numel(), out.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+    return _jl(out)
 
 
 def _chain_block_pullback(ctx, gouts, elem):
@@ -1600,10 +1781,10 @@ def dropout_mask(drop, entity, shape, device=None):
 
 def testmode(m, mode=True):
     """`Flux.testmode!(m, mode)`: True = Dropout is the identity whatever the call; False = always active; None = automatic (active inside a
-    gradient call).  Applies to a GNCore, a GNCoreList or any iterable of layers; returns m."""
+    gradient call).  Applies to a GNCore, a GNBlock (the Dropouts inside its Chains: `chain_dropout`), a GNCoreList or any iterable of layers; returns m."""
     forced = None if mode is None else (not mode)
     for l in (m.list if isinstance(m, GNCoreList) else (m if isinstance(m, (list, tuple)) else [m])):
-        if isinstance(l, GNCore):
+        if isinstance(l, (GNCore, GNBlock)):
             l._dropout_mode = forced
         elif isinstance(l, (GNCoreList, list, tuple)):
             testmode(l, mode)

@@ -1366,8 +1366,9 @@ struct ChainBwPlan : ChainPlan {
   ChainBwLayout L{};
   bool native = false;
   ChainBwNativeWs nw{};
-  ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false)
-      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery) {
+  ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false)
+      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery, train) {
+    if (!rc && train) query = "workspace missing or smaller than gnx_chain_block_backward_train_workspace_bytes()";
     if (rc || !narrow_typed) return;
     native = chain_bw_typed_native(sh, fused, bf16);
     if (bf16) query = kBwNarrowTypedQuery;
@@ -1510,7 +1511,13 @@ int32_t ChainBwCtx::pull_layers(int t, int first, float* cur, float* other, cons
     if (rows == 0 && J > 0) { if (int32_t rz = zero_layer_grads(t, i, K)) return rz; }
     if (rows == 0 || J == 0) continue;
     int32_t r2;
-    if (chain_layer_is_ln(d)) {
+    if (chain_layer_is_dropout(d)) {
+      // a Dropout entry of a training call: the gradient w.r.t. its input is the gradient w.r.t. its output times the forward's mask (the launch
+      // of the forward again); no parameters.  The delta of the layer in front then reads that layer's stored, undropped output (delta_rows below)
+      const ChainDropSite* st = chain_drop_site(d);
+      if (!st) return fail(GNX_ERR_INVALID_ARG, "Chain: a Dropout entry outside a training call");
+      if ((r2 = launch_dropout(gnx_dropout{st->p, 0, st->seed}, (int)st->stream, rows * (size_t)J, cur, gin, 1, s))) return r2;
+    } else if (chain_layer_is_ln(d)) {
       // a LayerNorm layer value: dx through the normalisation (k_ln_backward with one norm), dgamma = column sums of dy . xhat, dbeta = of dy
       float* t1 = gb[2];  // (free here: the gelu pre-activation buffer of delta_rows / last_delta is consumed inside those calls)
       { ProfScope ps("bw_layernorm", s);
@@ -1687,9 +1694,9 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
 // came through gnx_chain_block_backward_narrow_typed, which alone may be native) on its own tensors; any other bf16 call lays out, checks its workspace, widens its
 // six inputs, runs the fp32 launches on the copies and rounds the three input gradients (gnx_staging.h); the parameter gradients are the fp32
 // pullback's own.
-int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = false) {
+int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = false, bool train = false) {
   if (!c.h || !c.p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow, narrow_typed);
+  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow, narrow_typed, train);
   if (pl.rc) return c.elem == GNX_ELEM_BF16 ? pl.rc : GNX_ERR_DIMS;  // (fp32: one code for every refused parameter set; gnx_last_error() holds the reason)
   const void* bufs[9] = {c.ef, c.nf, c.gf, c.g_ef_out, c.g_nf_out, c.g_gf_out, c.d_ef, c.d_nf, c.d_gf};
   int32_t rc;
@@ -1707,8 +1714,8 @@ int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = fals
 }
 
 // a _workspace_bytes entry: the plan's total; query_total builds what the pullback reads of the handle, outside any capture
-size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false) {
-  ChainBwPlan pl(h, p, R, elem, narrow, narrow_typed);
+size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false) {
+  ChainBwPlan pl(h, p, R, elem, narrow, narrow_typed, train);
   pl.lay_out(h);  // (nothing for refused parameters: the total stays 0)
   return query_total(h, pl.total);
 }
@@ -1769,6 +1776,27 @@ int32_t gnx_chain_block_backward_narrow_typed(const gnx_graphs* h, const gnx_cha
                                               const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
   return chain_bw_run(ChainBwCall{h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true, true);
+}
+
+// gnx_chain_block_backward_train: the pullback of gnx_chain_block_forward_train under the same record (ChainTrain: the refusals, the library's copy of
+// the chains, the caller's gradient slots in its order).  Without an active entry the call IS the mirrored entry on the stripped chains.
+size_t gnx_chain_block_backward_train_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t narrow) {
+  if (!h || (narrow != 0 && narrow != 1)) return 0;
+  ChainTrain all(p, nullptr, true), none(p, nullptr);
+  if (all.rc || none.rc) return 0;
+  const size_t a = chain_bw_query(h, &all.p, R, GNX_ELEM_F32, narrow != 0, false, all.active), b = chain_bw_query(h, &none.p, R, GNX_ELEM_F32, narrow != 0);
+  return a && b ? std::max(a, b) : 0;
+}
+
+int32_t gnx_chain_block_backward_train(const gnx_graphs* h, const gnx_chain_block_params* p, const gnx_chain_dropout* dropout, const float* ef, const float* nf,
+                                       const float* gf, const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
+                                       float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, int32_t narrow, void* stream) {
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  ChainTrain tr(p, dropout);
+  if (tr.rc) return tr.rc;
+  if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
+  return chain_bw_run(ChainBwCall{h, &tr.p, GNX_ELEM_F32, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, tr.map_grads(grads), ws, ws_bytes, stream},
+                      narrow != 0, false, tr.active);
 }
 
 }  // extern "C"

@@ -57,6 +57,12 @@ int32_t ChainLnFirst::fill(float* ident, hipStream_t s) const {
 // one layer of a Chain, row-wise over all rows of the entity: Dense (launch_dense_rows) or LayerNorm; shared with the backward's recompute
 int32_t launch_chain_layer(const gnx_graphs* h, int entity, const gnx_dense& layer, const float* x, int k_in, int width, float* out, int64_t R, hipStream_t s,
                            const char* name) {
+  if (chain_layer_is_dropout(layer)) {  // a training call's entry (ChainTrain): out = x .* mask, the mask of the entry's site
+    const ChainDropSite* st = chain_drop_site(layer);
+    if (!st) return fail(GNX_ERR_INVALID_ARG, "Chain: a Dropout entry outside a training call");
+    const size_t n = (size_t)R * (entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G)) * (size_t)width;
+    return launch_dropout(gnx_dropout{st->p, 0, st->seed}, (int)st->stream, n, x, out, 1, s);
+  }
   if (!chain_layer_is_ln(layer)) return launch_dense_rows(h, entity, x, k_in, layer, width, nullptr, nullptr, out, R, s, name);
   const size_t rows = (size_t)R * (entity == 0 ? (size_t)h->E : (entity == 1 ? (size_t)h->N : (size_t)h->G));
   if (rows == 0 || width == 0) return GNX_OK;
@@ -69,7 +75,7 @@ int32_t launch_chain_layer(const gnx_graphs* h, int entity, const gnx_dense& lay
 
 namespace {
 
-int32_t check_chain(const gnx_chain& c, const char* what, int k_in) {
+int32_t check_chain(const gnx_chain& c, const char* what, int k_in, bool train) {
   if (c.n_layers < 0 || c.n_layers > kChainMaxLayers) return fail(GNX_ERR_INVALID_ARG, std::string(what) + ": n_layers must be 0..16");
   if (c.n_layers > 0 && (!c.layers || !c.widths)) return fail(GNX_ERR_INVALID_ARG, std::string(what) + ": layers / widths is NULL");
   for (int i = 0; i < c.n_layers; ++i) {
@@ -77,6 +83,7 @@ int32_t check_chain(const gnx_chain& c, const char* what, int k_in) {
     if (i + 1 < c.n_layers && c.widths[i] == 0) return fail(GNX_ERR_DIMS, std::string(what) + ": only the last layer of a Chain may have width 0");
     if (c.layers[i].act < GNX_ACT_IDENTITY || c.layers[i].act > GNX_ACT_GELU) return fail(GNX_ERR_INVALID_ARG, std::string(what) + ": unknown activation");
     const int kind = c.layers[i].kind & 0xff;
+    if (train && kind == GNX_LAYER_DROPOUT) continue;  // (placed, shaped and bound to its site by ChainTrain)
     if (kind != GNX_LAYER_DENSE && kind != GNX_LAYER_LAYERNORM) return fail(GNX_ERR_INVALID_ARG, std::string(what) + ": unknown layer kind");
     if (kind == GNX_LAYER_LAYERNORM) {  // a LayerNorm(d) layer value: gamma, beta of its input's width, no activation of its own
       if (c.widths[i] != (i > 0 ? c.widths[i - 1] : k_in)) return fail(GNX_ERR_DIMS, std::string(what) + ": a LayerNorm layer keeps the width of its input");
@@ -87,18 +94,18 @@ int32_t check_chain(const gnx_chain& c, const char* what, int k_in) {
   return GNX_OK;
 }
 
-int32_t check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+int32_t check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, bool train = false) {
   if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
   if (R <= 0 || (R > 1 && h->G != 1) || R > 65535) return fail(GNX_ERR_INVALID_ARG, "bad n_replicas");
   if (p->de < 0 || p->dn < 0 || p->dg < 0) return fail(GNX_ERR_DIMS, "negative feature width");
   if (p->de + p->dn + p->dg == 0) return fail(GNX_ERR_DIMS, "all input widths are 0 (gnblock.jl:48, batch.jl:56)");
   auto out_width = [](const gnx_chain& c) { return c.n_layers > 0 ? c.widths[c.n_layers - 1] : 0; };
   int32_t rc;
-  if ((rc = check_chain(p->edgefn, "edgefn", p->de + 2 * p->dn + p->dg))) return rc;
+  if ((rc = check_chain(p->edgefn, "edgefn", p->de + 2 * p->dn + p->dg, train))) return rc;
   const int oe = out_width(p->edgefn);
-  if ((rc = check_chain(p->nodefn, "nodefn", oe + p->dn + p->dg))) return rc;
+  if ((rc = check_chain(p->nodefn, "nodefn", oe + p->dn + p->dg, train))) return rc;
   const int on = out_width(p->nodefn);
-  if ((rc = check_chain(p->graphfn, "graphfn", oe + on + p->dg))) return rc;
+  if ((rc = check_chain(p->graphfn, "graphfn", oe + on + p->dg, train))) return rc;
   if (oe + on + out_width(p->graphfn) == 0) return fail(GNX_ERR_DIMS, "all output widths are 0 (gnblock.jl:49)");
   // A zero-width ef' / nf' is an empty segment of the next function's input, exactly as for one-layer update functions
   // (gnblock.jl:63-69 computes getnodefninput / getgraphfninput over the 0-row h_ef; width 0 <=> nothing in launch_fn_input).
@@ -109,8 +116,8 @@ int32_t check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64
 
 namespace gnx {
 
-ChainPlan::ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3])
-    : rc(check_params(h, p0, R)) {
+ChainPlan::ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3], bool train)
+    : rc(check_params(h, p0, R, train)) {
   if (rc) return;
   bf16 = elem == GNX_ELEM_BF16;
   query = query_of[bf16 ? 2 : narrow];
@@ -119,6 +126,62 @@ ChainPlan::ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int6
   p = (fused & 1) ? p0 : lnf.init(p0, nullptr);  // (the identity layer's weights sit at a fixed place of the workspace: bind_ident)
   if (lnf.on) sh = chain_shape(h->E, h->N, h->G, *p, R);
 }
+// The refusals in include/gnx.h's order — the chains' arrays, every p_l, a missing p[t], the entries' places and shapes — then the copy.
+ChainTrain::ChainTrain(const gnx_chain_block_params* p0, const gnx_chain_dropout* d, bool every_entry) {
+  if (!p0) { rc = fail(GNX_ERR_INVALID_ARG, "NULL handle or params"); return; }
+  const gnx_chain* in[3] = {&p0->edgefn, &p0->nodefn, &p0->graphfn};
+  const char* const what[3] = {"edgefn", "nodefn", "graphfn"};
+  for (int t = 0; t < 3; ++t) {
+    if (in[t]->n_layers < 0 || in[t]->n_layers > kChainMaxLayers) { rc = fail(GNX_ERR_INVALID_ARG, std::string(what[t]) + ": n_layers must be 0..16"); return; }
+    if (in[t]->n_layers > 0 && (!in[t]->layers || !in[t]->widths)) { rc = fail(GNX_ERR_INVALID_ARG, std::string(what[t]) + ": layers / widths is NULL"); return; }
+  }
+  auto is_drop = [&](int t, int i) { return chain_layer_is_dropout(in[t]->layers[i]); };
+  for (int t = 0; t < 3 && d; ++t)
+    for (int i = 0; i < in[t]->n_layers && d->p[t]; ++i)
+      if (is_drop(t, i) && !(d->p[t][i] >= 0.f && d->p[t][i] <= 1.f)) { rc = fail(GNX_ERR_INVALID_ARG, std::string(what[t]) + ": Dropout: p must lie in [0, 1] (Flux.Dropout asserts 0 <= p <= 1)"); return; }
+  for (int t = 0; t < 3 && d; ++t)
+    for (int i = 0; i < in[t]->n_layers && !d->p[t]; ++i)
+      if (is_drop(t, i)) { rc = fail(GNX_ERR_INVALID_ARG, std::string(what[t]) + ": the chain has a Dropout entry and gnx_chain_dropout.p of the function is NULL"); return; }
+  for (int t = 0; t < 3; ++t)
+    for (int i = 0; i < in[t]->n_layers; ++i) {
+      if (!is_drop(t, i)) continue;
+      const gnx_dense& l = in[t]->layers[i];
+      if (i == 0 || is_drop(t, i - 1)) { rc = fail(GNX_ERR_INVALID_ARG, std::string(what[t]) + ": a Dropout entry follows a Dense or LayerNorm entry (never first, never behind another Dropout)"); return; }
+      if (in[t]->widths[i] != in[t]->widths[i - 1]) { rc = fail(GNX_ERR_INVALID_ARG, std::string(what[t]) + ": a Dropout entry keeps the width of the entry in front of it"); return; }
+      if (l.weight || l.bias || l.act != GNX_ACT_IDENTITY || l.kind != GNX_LAYER_DROPOUT) { rc = fail(GNX_ERR_INVALID_ARG, std::string(what[t]) + ": a Dropout entry has no weight, no bias and no activation"); return; }
+    }
+  p = *p0;
+  gnx_chain* out[3] = {&p.edgefn, &p.nodefn, &p.graphfn};
+  for (int t = 0; t < 3; ++t) {
+    int n = 0;
+    for (int i = 0; i < in[t]->n_layers; ++i) {
+      gnx_dense l = in[t]->layers[i];
+      if (is_drop(t, i)) {
+        const float pl = every_entry ? 0.5f : (d ? d->p[t][i] : 0.f);
+        if (!(pl > 0.f)) continue;  // the identity: removed
+        sites[t][n] = ChainDropSite{d ? d->seed : 0, pl, (uint32_t)(16 + 16 * t + i)};
+        l.bias = reinterpret_cast<const float*>(&sites[t][n]);  // (never read as floats: chain_drop_site)
+        active = true;
+      }
+      layers[t][n] = l; widths[t][n] = in[t]->widths[i]; src[t][n] = i;
+      ++n;
+    }
+    out[t]->layers = layers[t]; out[t]->widths = widths[t]; out[t]->n_layers = n;
+  }
+}
+const gnx_chain_block_grads* ChainTrain::map_grads(const gnx_chain_block_grads* g0) {
+  if (!g0) return nullptr;
+  grads = *g0;
+  const gnx_dense_grad* in[3] = {g0->edgefn, g0->nodefn, g0->graphfn};
+  const gnx_chain* ch[3] = {&p.edgefn, &p.nodefn, &p.graphfn};
+  for (int t = 0; t < 3; ++t)
+    for (int i = 0; in[t] && i < ch[t]->n_layers; ++i) g[t][i] = chain_layer_is_dropout(layers[t][i]) ? gnx_dense_grad{nullptr, nullptr} : in[t][src[t][i]];
+  if (g0->edgefn) grads.edgefn = g[0];
+  if (g0->nodefn) grads.nodefn = g[1];
+  if (g0->graphfn) grads.graphfn = g[2];
+  return &grads;
+}
+
 int32_t chain_check_features(const ChainShape& sh, const void* ef, const void* nf, const void* gf, const char* message) {
   return (sh.de > 0 && !ef && sh.trows[0] > 0) || (sh.dn > 0 && !nf) || (sh.dg > 0 && !gf) ? fail(GNX_ERR_INVALID_ARG, message) : GNX_OK;
 }
@@ -134,7 +197,7 @@ int32_t run_layers(const gnx_graphs* h, int entity, const gnx_chain& c, int firs
   int k = k_in;
   for (int i = first; i < c.n_layers; ++i) {
     float* dst = i + 1 == c.n_layers ? out : buf[(i - first) & 1];
-    if (c.widths[i] > 0 && k > 0 && !c.layers[i].weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
+    if (c.widths[i] > 0 && k > 0 && !c.layers[i].weight && !chain_layer_is_dropout(c.layers[i])) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
     const int32_t rc = launch_chain_layer(h, entity, c.layers[i], cur, k, c.widths[i], dst, R, s, name);
     if (rc) return rc;
     cur = dst;
@@ -157,7 +220,8 @@ const char* const kFwQuery[3] = {"workspace missing or smaller than gnx_chain_bl
 struct ChainFwPlan : ChainPlan {
   bool native = false;
   ChainWs w{};
-  ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow) : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_FW, kFwQuery) {
+  ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool train = false)
+      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_FW, kFwQuery, train) {
     native = !rc && bf16 && narrow && chain_typed_native(sh, fused);
   }
   bool wide_tables() const { return chain_fw_reads_wide_tables(sh, fused); }
@@ -244,9 +308,10 @@ int32_t chain_forward_native(const ChainFwCall& c, const ChainFwPlan& pl) {
 // One Chain forward call: validate and plan, the refusals that read nothing of the handle but its counts — NULL features, bf16 alignment — the
 // layout, the workspace refusal, the plan's tables; then the plan's form.  A staged bf16 call widens into the workspace, runs the fp32 launches on
 // the copies and rounds the outputs.
-int32_t chain_fw_run(const ChainFwCall& c, bool narrow) {
-  ChainFwPlan pl(c.h, c.p, c.R, c.elem, narrow);
+int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false) {
+  ChainFwPlan pl(c.h, c.p, c.R, c.elem, narrow, train);
   if (pl.rc) return pl.rc;
+  if (train) pl.query = "workspace missing or smaller than gnx_chain_block_forward_train_workspace_bytes()";
   const hipStream_t s = (hipStream_t)c.stream;
   gnx::FormScope forms(c.flags);  // the forms this call selected (gnx.h: GNX_FLAG_EDGE_FP32 ...)
   gnx::DeviceTurn turn(s, !pl.native && pl.sh.wide);  // (any layer of any chain at matrix-core widths; the native path has none)
@@ -269,8 +334,8 @@ int32_t chain_fw_run(const ChainFwCall& c, bool narrow) {
 }
 
 // a _workspace_bytes entry: the plan's total, and the plan's tables built here, outside any capture (a failure resurfaces in the call)
-size_t chain_fw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow) {
-  ChainFwPlan pl(h, p, R, elem, narrow);
+size_t chain_fw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool train = false) {
+  ChainFwPlan pl(h, p, R, elem, narrow, train);
   if (pl.rc) return 0;
   pl.lay_out(h);
   if (pl.wide_tables()) (void)gnx_ensure_wide_tables(h);
@@ -317,6 +382,44 @@ int32_t gnx_chain_block_forward_typed(const gnx_graphs* h, const gnx_chain_block
   if (!elem_ok(elem)) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
   if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
   return chain_fw_run(ChainFwCall{h, p, elem, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, narrow != 0);
+}
+
+// ---- training mode: Dropout entries inside the chains (include/gnx.h; ChainTrain, gnx_staging.h) ----
+int32_t gnx_chain_dropout_mask(const gnx_chain_dropout* d, int32_t function, int32_t layer, float p, int64_t n, float* out, void* stream) {
+  if (!d || (!out && n > 0) || n < 0) return fail(GNX_ERR_INVALID_ARG, "gnx_chain_dropout_mask: NULL argument or negative length");
+  if (function < 0 || function > 2 || layer < 0 || layer >= kChainMaxLayers) return fail(GNX_ERR_INVALID_ARG, "gnx_chain_dropout_mask: function outside 0..2 or layer outside 0..15");
+  if (!(p >= 0.f && p <= 1.f)) return fail(GNX_ERR_INVALID_ARG, "Dropout: p must lie in [0, 1] (Flux.Dropout asserts 0 <= p <= 1)");
+  if (n == 0) return GNX_OK;
+  return launch_dropout(gnx_dropout{p, 0, d->seed}, 16 + 16 * function + layer, (size_t)n, nullptr, out, 0, (hipStream_t)stream);
+}
+
+// the mask of the training rule with every Dropout entry active (the plan header's two rules read the entries)
+int32_t gnx_chain_block_train_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t backward) {
+  if (!h || (backward != 0 && backward != 1)) return 0;
+  ChainTrain tr(p, nullptr, true);
+  if (tr.rc || check_params(h, &tr.p, R, true) != GNX_OK) return 0;
+  const ChainShape sh = chain_shape(h->E, h->N, h->G, tr.p, R);
+  if (backward && sh.ow[0] == 0) return 0;  // (no pullback without an edge output)
+  return (int32_t)chain_fused_mask(sh, backward ? CHAIN_RULE_BW : CHAIN_RULE_FW);
+}
+
+// The query sees no record: what a call with every entry active needs, and no less than the mirrored entry on the stripped chains.
+size_t gnx_chain_block_forward_train_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t narrow) {
+  if (!h || (narrow != 0 && narrow != 1)) return 0;
+  ChainTrain all(p, nullptr, true), none(p, nullptr);
+  if (all.rc || none.rc) return 0;
+  const size_t a = chain_fw_query(h, &all.p, R, GNX_ELEM_F32, narrow != 0, all.active), b = chain_fw_query(h, &none.p, R, GNX_ELEM_F32, narrow != 0);
+  return a && b ? std::max(a, b) : 0;
+}
+
+int32_t gnx_chain_block_forward_train(const gnx_graphs* h, const gnx_chain_block_params* p, const gnx_chain_dropout* dropout, const float* ef, const float* nf,
+                                      const float* gf, int64_t R, float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, int32_t narrow,
+                                      uint32_t flags, void* stream) {
+  if (!h || !p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
+  ChainTrain tr(p, dropout);
+  if (tr.rc) return tr.rc;
+  if (narrow != 0 && narrow != 1) return fail(GNX_ERR_INVALID_ARG, "narrow must be 0 or 1");
+  return chain_fw_run(ChainFwCall{h, &tr.p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, narrow != 0, tr.active);
 }
 
 }  // extern "C"

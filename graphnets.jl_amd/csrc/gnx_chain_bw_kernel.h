@@ -14,8 +14,22 @@
 // ex1 / ex2 (dXg, dXn), dx and the partial rows are fp32 in both.  A bf16 buffer is 4-byte aligned (the entry checks); rows of odd width and
 // replicas of an odd rows * d start 2-byte aligned: every bf16 access is one 16-bit load or store of an element of the tensor — no
 // read-modify-write of a dword, no byte outside the tensor.
+//
+// GNX_CHAIN_BW_TRAIN (optional, 0 / 1; gnx_chain_bw_train_narrow.hip defines it 1): the training pullback k_chain_mlp_bw_train — the same text
+// with the Dropout op of a training call's chains (op 7, gnx_chain_drop.h) behind `#if`, and the entries' record as a second kernel argument.
+// In the forward half the dropped row goes on the tape like any layer's output; on the way back gin = d .* m with the mask regenerated; the
+// entry has no accumulators, no parameter-gradient phase and no partial row.  With 0 the preprocessor leaves the two kernels above their text.
 #pragma once
 #include "gnx_chain_mlp.h"
+#ifndef GNX_CHAIN_BW_TRAIN
+#define GNX_CHAIN_BW_TRAIN 0
+#endif
+#if GNX_CHAIN_BW_TRAIN
+#include "gnx_chain_drop.h"
+#define GNX_CHAIN_BW_DROP_ARG , ChainDropArgs dr
+#else
+#define GNX_CHAIN_BW_DROP_ARG
+#endif
 
 namespace gnx {
 
@@ -60,7 +74,7 @@ __device__ __forceinline__ void chain_bw_dw_phase(const float* tape, int ld, int
 #error "define GNX_CHAIN_BW_KERNEL and GNX_CHAIN_BW_BF16 before including gnx_chain_bw_kernel.h"
 #endif
 template <int WMAX, int SRC>
-__global__ __launch_bounds__(256) void GNX_CHAIN_BW_KERNEL(ChainMlpBwArgs a) {
+__global__ __launch_bounds__(256) void GNX_CHAIN_BW_KERNEL(ChainMlpBwArgs a GNX_CHAIN_BW_DROP_ARG) {
   constexpr bool BF16 = GNX_CHAIN_BW_BF16;
   extern __shared__ __attribute__((aligned(16))) float s_par[];
   constexpr int SMAX = chain_bw_smax(WMAX);
@@ -70,7 +84,7 @@ __global__ __launch_bounds__(256) void GNX_CHAIN_BW_KERNEL(ChainMlpBwArgs a) {
   float* const tape = s_par + a.sh.par_floats + wave * (64 * ld + P);  // this wave's rows, then its accumulators
   float* const accs = tape + 64 * ld;
   float* const my = tape + lane * ld;
-  chain_stage_params(f, s_par, NT);
+  chain_stage_params<GNX_CHAIN_BW_TRAIN != 0>(f, s_par, NT);
   for (int p = lane; p < P; p += 64) accs[p] = 0.f;
   __syncthreads();
   const size_t r = blockIdx.y;
@@ -93,6 +107,10 @@ __global__ __launch_bounds__(256) void GNX_CHAIN_BW_KERNEL(ChainMlpBwArgs a) {
 #pragma unroll 1
       for (int l = 0; l < nl; ++l) {
         const int width = f.layer[l].width, op = f.layer[l].op;
+#if GNX_CHAIN_BW_TRAIN
+        if (op == kChainOpDropout) chain_drop_row<WMAX>(dr.seed, dr.stream[l], dr.p[l], dr.scale[l], (r * f.rows + row) * (size_t)width, width, cur);
+        else
+#endif
         if (l == nl - 1 && op == GNX_ACT_GELU) (void)chain_layer_fw<WMAX>(s_par, a.sh.par_off[l], kin, width, GNX_ACT_IDENTITY, cur);  // its pre-activation is all the way back reads
         else (void)chain_layer_fw<WMAX>(s_par, a.sh.par_off[l], kin, width, op, cur);
         if (l < nl - 1) {
@@ -141,6 +159,13 @@ __global__ __launch_bounds__(256) void GNX_CHAIN_BW_KERNEL(ChainMlpBwArgs a) {
       float gin[WMAX];
 #pragma unroll
       for (int k = 0; k < WMAX; ++k) gin[k] = 0.f;
+#if GNX_CHAIN_BW_TRAIN
+      if (op == kChainOpDropout) {  // gin = d .* m, the forward's mask again
+#pragma unroll
+        for (int k = 0; k < WMAX; ++k) gin[k] = d[k];
+        chain_drop_row<WMAX>(dr.seed, dr.stream[l], dr.p[l], dr.scale[l], (r * f.rows + row) * (size_t)width, width, gin);
+      } else
+#endif
       if (op < 5) {
         if (a.part) {
 #pragma unroll
@@ -267,6 +292,9 @@ __global__ __launch_bounds__(256) void GNX_CHAIN_BW_KERNEL(ChainMlpBwArgs a) {
   int kin = f.K;
   for (int l = 0; l < nl; ++l) {
     const int width = f.layer[l].width;
+#if GNX_CHAIN_BW_TRAIN
+    if (f.layer[l].op == kChainOpDropout) continue;  // (no parameters; its width is kin)
+#endif
     const int Pl = f.layer[l].op < 5 ? width * (kin + 1) : 2 * width, at = a.sh.part_off[l];
     float* __restrict__ out = a.part + (size_t)at * nwg + wg * (size_t)Pl;
     for (int p = threadIdx.x; p < Pl; p += NT) {

@@ -32,6 +32,7 @@ namespace gnx {
 // The caller asked chain_bw_narrow_takes (gnx_chain_plan.h: the rule and the LDS plan, chain_bw_narrow_shape) and opens the ProfScope.
 int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                                const ChainBwNarrowIo& io, int64_t R, hipStream_t s) {
+  if (chain_has_dropout(c)) return launch_chain_bw_narrow_train(h, entity, c, in0, d0, in1, d1, in2, d2, io, R, s);  // (a training call: gnx_chain_bw_train_narrow.hip)
   ChainMlpBwArgs a{};
   int wmax;
   size_t lds;

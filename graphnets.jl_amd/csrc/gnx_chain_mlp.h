@@ -17,7 +17,8 @@ struct ChainMlpLayer {
   const float* w;  // Dense: weight (out x in, column-major) / LayerNorm: gamma
   const float* b;  // Dense: bias or nullptr / LayerNorm: beta
   int width;       // output width
-  int op;          // 0..4: Dense with activation GNX_ACT_*; 5 / 6: LayerNorm with 1 / (sigma + eps) / 1 / sqrt(sigma^2 + eps)
+  int op;          // 0..4: Dense with activation GNX_ACT_*; 5 / 6: LayerNorm with 1 / (sigma + eps) / 1 / sqrt(sigma^2 + eps);
+                   // 7: a Dropout entry of a training call (w = b = nullptr; the training kernels alone see it: gnx_chain_drop.h)
 };
 
 struct ChainMlpArgs {
@@ -41,10 +42,13 @@ __device__ __forceinline__ void chain_load_seg(const float* __restrict__ p, int 
 
 // the function's parameters into s_par, zero-padded to groups of four: a Dense as [ceil4(k_in)][ceil4(width)] weights (element (j, k) at
 // k * ceil4(width) + j) + ceil4(width) biases, a LayerNorm as gamma and beta.  All NT threads of the workgroup call it; the caller synchronises.
+// TRAIN (the training kernels): a Dropout entry (op 7) stages nothing.
+template <bool TRAIN = false>
 __device__ __forceinline__ void chain_stage_params(const ChainMlpArgs& a, float* s_par, int NT) {
   int off = 0, kin = a.K;
   for (int l = 0; l < a.n_layers; ++l) {
     const ChainMlpLayer L = a.layer[l];
+    if constexpr (TRAIN) { if (L.op == 7) continue; }  // (its width is kin)
     const int OP = ceil4(L.width);
     if (L.op < 5) {
       const int n = ceil4(kin) * OP;
@@ -226,8 +230,9 @@ inline int32_t chain_mlp_prologue(const gnx_graphs* h, int entity, const gnx_cha
   int kin = K;
   for (int i = 0; i < c.n_layers; ++i) {
     const gnx_dense& l = c.layers[i];
-    if (!chain_layer_is_ln(l) && (rule == CHAIN_RULE_BW || c.widths[i] > 0) && kin > 0 && !l.weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
-    a.layer[i] = ChainMlpLayer{l.weight, l.bias, c.widths[i], chain_layer_is_ln(l) ? 5 + chain_layer_ln_mode(l) : l.act};
+    const bool drop = chain_layer_is_dropout(l);  // (a training launcher's chain: no parameters, op 7)
+    if (!chain_layer_is_ln(l) && !drop && (rule == CHAIN_RULE_BW || c.widths[i] > 0) && kin > 0 && !l.weight) return fail(GNX_ERR_INVALID_ARG, "Chain: Dense weight is NULL");
+    a.layer[i] = drop ? ChainMlpLayer{nullptr, nullptr, c.widths[i], 7} : ChainMlpLayer{l.weight, l.bias, c.widths[i], chain_layer_is_ln(l) ? 5 + chain_layer_ln_mode(l) : l.act};
     *wmax = std::max(*wmax, (int)c.widths[i]);
     kin = c.widths[i];
   }

@@ -105,6 +105,7 @@ __global__ __launch_bounds__(256) void k_chain_mlp(ChainMlpArgs a) {
 // (SRC_NODE); 2: in0 = the materialised [R G][d0] input rows (SRC_ROWS; d1 = d2 = 0).  The caller asked chain_narrow_takes (gnx_chain_plan.h).
 int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                             float* out, int64_t R, hipStream_t s, const char* name) {
+  if (chain_has_dropout(c)) return launch_chain_narrow_train(h, entity, c, in0, d0, in1, d1, in2, d2, out, R, s, name);  // (a training call: gnx_chain_train_narrow.hip)
   ChainMlpArgs a{};
   int wmax;
   size_t rows;

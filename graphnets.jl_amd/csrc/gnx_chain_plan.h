@@ -16,6 +16,16 @@ constexpr float kChainLnEps = 1e-5f;
 constexpr int kChainMaxLayers = 16;
 inline bool chain_layer_is_ln(const gnx_dense& l) { return (l.kind & 0xff) == GNX_LAYER_LAYERNORM; }
 inline int chain_layer_ln_mode(const gnx_dense& l) { return (l.kind & GNX_LAYER_LN_SQRT_EPS) ? 1 : 0; }
+// a `Dropout(p)` layer value (GNX_LAYER_DROPOUT): only the training entries admit it (include/gnx.h), with p > 0 — it has no parameters, its
+// width is its input's.  In a training call's own copy of a chain the entry's `bias` points at its ChainDropSite.
+inline bool chain_layer_is_dropout(const gnx_dense& l) { return (l.kind & 0xff) == GNX_LAYER_DROPOUT; }
+struct ChainDropSite { uint64_t seed; float p; uint32_t stream; };  // stream: 16 + 16 * function + layer, indices of the CALLER's chain
+inline const ChainDropSite* chain_drop_site(const gnx_dense& l) { return reinterpret_cast<const ChainDropSite*>(l.bias); }
+inline bool chain_has_dropout(const gnx_chain& c) {
+  for (int i = 0; c.layers && i < c.n_layers; ++i)
+    if (chain_layer_is_dropout(c.layers[i])) return true;
+  return false;
+}
 
 // ---- the shape of a call: built once from the counts, the (checked) parameters and the replicas ----
 struct ChainShape {
@@ -68,13 +78,13 @@ inline size_t chain_narrow_lds_floats(const gnx_chain& c, int k_in) {
   int kin = k_in;
   for (int i = 0; i < c.n_layers; ++i) {
     const int OP = ceil4(c.widths[i]);
-    n += chain_layer_is_ln(c.layers[i]) ? 2 * (size_t)OP : (size_t)ceil4(kin) * OP + OP;
+    if (!chain_layer_is_dropout(c.layers[i])) n += chain_layer_is_ln(c.layers[i]) ? 2 * (size_t)OP : (size_t)ceil4(kin) * OP + OP;  // (a Dropout entry stages nothing)
     kin = c.widths[i];
   }
   return n;
 }
 // is the function fused by gnx_chain_block_forward_narrow: >= 1 layer, a non-zero output width, k_in and every width <= 32, parameters within
-// the LDS budget, rows to run on
+// the LDS budget, rows to run on.  With Dropout entries (a training call): the training forward's rule — the same, an entry staging 0 floats
 inline bool chain_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows) {
   if (c.n_layers < 1 || c.n_layers > kChainMaxLayers || !c.layers || !c.widths || entity_rows == 0) return false;
   if (c.widths[c.n_layers - 1] <= 0 || k_in > kChainNarrowMaxWidth) return false;
@@ -94,15 +104,17 @@ inline ChainBwNarrowShape chain_bw_narrow_shape(const gnx_chain& c, int k_in, si
   ChainBwNarrowShape sh{};
   int kin = k_in, slots = k_in, dmax = 0;
   for (int i = 0; i < c.n_layers; ++i) {
-    const bool ln = chain_layer_is_ln(c.layers[i]);
+    const bool ln = chain_layer_is_ln(c.layers[i]), drop = chain_layer_is_dropout(c.layers[i]);
     const int J = c.widths[i];
     sh.par_off[i] = sh.par_floats;
-    sh.par_floats += chain_layer_par_floats(kin, J, ln);
     sh.part_off[i] = sh.P;
-    sh.P += ln ? 2 * J : J * (kin + 1);
+    if (!drop) {  // (a Dropout entry: no parameters, no accumulators, nothing parked in the delta slot — only its tape slot)
+      sh.par_floats += chain_layer_par_floats(kin, J, ln);
+      sh.P += ln ? 2 * J : J * (kin + 1);
+      dmax = std::max(dmax, ln ? 2 * J : J);
+    }
     sh.tape_out[i] = slots;
     if (i + 1 < c.n_layers) slots += J;
-    dmax = std::max(dmax, ln ? 2 * J : J);
     kin = J;
   }
   sh.dslot = slots;
@@ -112,11 +124,23 @@ inline ChainBwNarrowShape chain_bw_narrow_shape(const gnx_chain& c, int k_in, si
   if (sh.waves > 0) sh.nwg = (rows + 64 * (size_t)sh.waves - 1) / (64 * (size_t)sh.waves);
   return sh;
 }
+// (with Dropout entries: the training pullback's rule, include/gnx.h)
 // the rule of gnx_chain_block_backward_narrow for one function: the forward's rule and two waves per workgroup at least.  The one-wave class (a
 // tape and accumulators beyond 28 KB) is cut — measured, it re-stages its parameters for every 64 rows, writes a partial row per 64 rows and
 // misses the generic pullback's time (profiles/chain_bw_narrow.json)
 inline bool chain_bw_narrow_takes(const gnx_chain& c, int k_in, size_t entity_rows) {
   return chain_narrow_takes(c, k_in, entity_rows) && chain_bw_narrow_shape(c, k_in, entity_rows).waves >= 2;
+}
+
+// The class CUT from the training pullback's rule: an EDGE function with Dropout entries at register width 32 (k_in or a layer width beyond
+// 16).  Measured (profiles/chain_train_narrow.json): k_chain_mlp_bw_train<32, SRC_EDGE> takes 256 VGPRs and both of its measured cases —
+// [16,do,3] at k_in 20 on the 1M-edge batch and on C2 — were slower than the generic test-mode pullback beyond its spread (2.02 against 1.02 ms,
+// 5.18 against 4.16 ms).  Such a function runs the generic training launches.
+inline bool chain_train_bw_cut(const gnx_chain& c, int k_in, int function) {
+  if (function != 0 || !chain_has_dropout(c)) return false;
+  int w = k_in;
+  for (int i = 0; i < c.n_layers; ++i) w = std::max(w, (int)c.widths[i]);
+  return w > 16;
 }
 
 enum ChainRule { CHAIN_RULE_FW, CHAIN_RULE_BW };
@@ -126,7 +150,7 @@ inline bool chain_rule_takes(ChainRule rule, const gnx_chain& c, int k_in, size_
 inline unsigned chain_fused_mask(const ChainShape& s, ChainRule rule) {
   unsigned m = 0;
   for (int t = 0; t < 3; ++t)
-    if (chain_rule_takes(rule, *s.ch[t], s.k0[t], s.trows[t])) m |= 1u << t;
+    if (chain_rule_takes(rule, *s.ch[t], s.k0[t], s.trows[t]) && !(rule == CHAIN_RULE_BW && chain_train_bw_cut(*s.ch[t], s.k0[t], t))) m |= 1u << t;
   return m;
 }
 

@@ -201,6 +201,12 @@ int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain&
 // in0 .. in2 as launch_chain_narrow_bf16; io.G and io.direct hold bfloat16 elements (declared float), io.ex1, io.ex2, io.dx and io.part are fp32
 int32_t launch_chain_bw_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
                                     const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
+// ---- gnx_chain_train_narrow.hip / gnx_chain_bw_train_narrow.hip: the two launchers above for a function with Dropout entries (a training call:
+//      every entry bound to its ChainDropSite).  launch_chain_narrow / launch_chain_bw_narrow hand such a chain over themselves ----
+int32_t launch_chain_narrow_train(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
+                                  float* out, int64_t R, hipStream_t s, const char* name);
+int32_t launch_chain_bw_narrow_train(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2,
+                                     int d2, const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
 
 // ---- gnx_forward.hip: the validation of a core forward, for the training-mode entries of gnx_dropout.hip (a FormScope of the call's flags open) ----
 int32_t core_forward_check_dims(const gnx_core_params* p);  // (needs no handle)

@@ -68,8 +68,10 @@ inline int32_t stage_round(const Staging& st, void* ws, const void* const* bufs,
 // behind an identity Dense, a fused one as it stands; p: the parameters every launch works on, sh: their shape) and the query whose name the
 // workspace refusal cites (query_of: the plain, the narrow, the typed entry's).  The forward and the pullback derive their plan from it
 // (ChainFwPlan, ChainBwPlan) and add their layout, which sized() completes.  Not copyable (ChainLnFirst is not): `p` may point into `lnf`.
+// `train`: the call came through a training entry (ChainTrain below) — its chains may hold Dropout entries.
 struct ChainPlan {
-  ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3]);
+  ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3],
+            bool train = false);
   int32_t rc;  // the validation's; not GNX_OK: nothing below is set
   ChainLnFirst lnf;
   const gnx_chain_block_params* p = nullptr;
@@ -85,5 +87,28 @@ struct ChainPlan {
 };
 // "an input with non-zero width is NULL": one check behind every Chain entry, each with its own message
 int32_t chain_check_features(const ChainShape& sh, const void* ef, const void* nf, const void* gf, const char* message);
+
+// What a training entry (gnx_chain_block_forward_train / _backward_train and their queries; include/gnx.h) makes of the caller's chains before it
+// plans: the refusals of the record and of the Dropout entries in their documented order, then the library's own copy of the three chains — the
+// entries with p = 0 (all of them without a record) removed, each entry that stays bound to its ChainDropSite (the seed, p and the stream id of
+// the CALLER's indices) through its `bias` field.  active: an entry stayed — the call runs the training launches on `p`; otherwise `p` is the
+// stripped chain and the call IS the mirrored test-mode entry on it.  every_entry: keep every Dropout entry whatever its p (the rule's query,
+// gnx_chain_block_train_applies).  Not copyable: `p` points into it.  Defined in gnx_chain.cpp.
+struct ChainTrain {
+  ChainTrain(const gnx_chain_block_params* p0, const gnx_chain_dropout* d, bool every_entry = false);
+  ChainTrain(const ChainTrain&) = delete;
+  ChainTrain& operator=(const ChainTrain&) = delete;
+  int32_t rc = GNX_OK;
+  bool active = false;
+  gnx_chain_block_params p{};
+  gnx_dense layers[3][kChainMaxLayers];
+  int32_t widths[3][kChainMaxLayers];
+  int src[3][kChainMaxLayers];  // the caller's index of layer i of `p`
+  ChainDropSite sites[3][kChainMaxLayers];
+  gnx_dense_grad g[3][kChainMaxLayers];
+  gnx_chain_block_grads grads{};
+  // the caller's gradient slots in the order of `p` (a Dropout entry's: none)
+  const gnx_chain_block_grads* map_grads(const gnx_chain_block_grads* g0);
+};
 
 }  // namespace gnx

@@ -853,6 +853,74 @@ GNX_API int32_t gnx_core_backward_train_typed(const gnx_graphs* h, const gnx_cor
                                               const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
                                               const gnx_core_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- GNBlock with Chain update functions in TRAINING mode: `Dropout(p)` layer values inside the chains, e.g.
+ * Chain(Dense(a => h, relu), Dropout(p), Dense(h => b)).  GNX_LAYER_DROPOUT is a gnx_chain layer entry: weight = bias = NULL, act = identity, its
+ * width = the width of the entry in front of it; it follows a Dense or LayerNorm entry (never first, never behind another Dropout) and may be
+ * the last entry.  Only the four *_train entries below take it: gnx_chain_block_forward / _narrow / _typed and the four backward entries refuse
+ * it as an unknown layer kind.  fp32 features only.
+ * THE MASK is never stored.  Element k of row `row` of replica r of the output of Dropout entry l of function t (0 edge, 1 node, 2 graph; rows
+ * = E, N, G; w the entry's width) has the flat index i = (r * rows + row) * w + k and the mask value
+ *     m = mask_of(component i % 4 of philox4(i / 4, 16 + 16 t + l, seed), p_l, scale_l),   scale_l = p_l < 1 ? 1 / (1 - p_l) : 0
+ * — gnx_dropout_mask's generator on the stream id 16 + 16 t + l (ids 0..2 are GNCore's entities) — and y = x * m is one fp32 multiply.  t and l
+ * are indices of the CALLER's chain: where the library puts an identity Dense in front of a LayerNorm-first edge function, and where it drops
+ * entries with p = 0, `p` and the stream ids keep the caller's indices.  The backward regenerates the masks from the same record.
+ * gnx_chain_dropout_mask writes that mask (for hosts and tests): function 0..2, layer 0..15, p in [0, 1], else GNX_ERR_INVALID_ARG.
+ * SEMANTICS.  dropout == NULL, every p_l == 0, or chains without Dropout entries: the call IS the mirrored test-mode entry on the chains with
+ * the Dropout entries removed (narrow 0: gnx_chain_block_forward / _backward; 1: _narrow) — same bits, same _applies mask, same workspace
+ * size.  An entry with p_l == 0 is removed in any call.  `grads` arrays are indexed by the caller's layers; a Dropout entry's slot is ignored.
+ * The two _workspace_bytes queries take no record: they return what a call with EVERY Dropout entry active needs — never less than the mirrored
+ * query on the stripped chains, and exactly that for chains without Dropout entries; a call needs what its own record makes of the chains (an
+ * identity call: the mirrored entry's size); the workspace refusal of a call with an active entry names the training query.
+ * REFUSALS, before any GPU work, in this order: NULL handle or params; a malformed chain (n_layers outside 0..16, NULL layers / widths); a
+ * p_l outside [0, 1] (GNX_ERR_INVALID_ARG); a NULL p[t] for a function that has a Dropout entry while dropout != NULL (INVALID_ARG); a
+ * misplaced or malformed Dropout entry — first, behind another Dropout, a width other than its input's, an activation, a weight or a bias
+ * (INVALID_ARG); narrow other than 0 / 1 (INVALID_ARG); then the mirrored entry's refusals.  The queries return 0 for all of these.
+ * GENERIC PATH (narrow = 0, and any function outside the fused rule): a Dropout entry is one k_dropout launch from the layer's input buffer to
+ * its output buffer; in the pullback the same launch turns the gradient w.r.t. its output into the gradient w.r.t. its input (no parameter
+ * gradient), the delta of the layer in front using that layer's stored, undropped output; a Dropout as last entry multiplies the summed last
+ * delta (upstream + the shares of the levels above).
+ * FUSED PATH (narrow = 1), per function, with an active Dropout entry counted as a layer of its input's width:
+ *   forward rule  : gnx_chain_block_forward_narrow's rule, a Dropout entry counting 0 staged parameter floats (its width <= 32 as any layer's);
+ *                   k_chain_mlp_train (csrc/gnx_chain_train_narrow.hip): the lane regenerates the mask of its row in registers, one Philox
+ *                   block at a time (a row lies in at most (3 + w + 3) / 4 consecutive blocks; the quad index is 64-bit).
+ *   pullback rule : gnx_chain_block_backward_narrow's formula, where a Dropout entry that is not last takes a tape slot of its width like any
+ *                   layer output, contributes 0 to par, 0 to P and nothing to the delta slot (the max_i term); two waves per workgroup at
+ *                   least, as there.  k_chain_mlp_bw_train (csrc/gnx_chain_bw_train_narrow.hip): k_chain_mlp_bw's text with the Dropout op —
+ *                   the dropped row goes on the tape, the way back multiplies the gradient by the regenerated mask; no accumulators, no
+ *                   parameter-gradient phase for the entry.
+ *                   ONE CLASS IS CUT from the pullback's rule: an EDGE function with Dropout entries at register width 32 (k_in or a layer
+ *                   width beyond 16) — its kernel takes 256 VGPRs, and both measured cases ([16,do,3] at k_in 20: 2.02 against 1.02 ms on the
+ *                   1M-edge batch, 5.18 against 4.16 ms on one 1M-edge graph) were slower than the generic test-mode pullback beyond its spread
+ *                   (profiles/chain_train_narrow.json).  Such a function runs the generic training launches.  No class is cut from the
+ *                   forward's rule (0.42 - 1.00 of the generic test-mode forward on the eight measured cases).
+ * No new instantiation uses scratch (profiles/chain_train_narrow_resources.json).  A function without an active Dropout entry runs the
+ * test-mode kernels under the test-mode rules.  ef' / nf' that cross levels are recomputed in the pullback by the training forward kernel under
+ * the same record; mixed masks and a fused node function in front of a generic graph function behave as in the test-mode entries; the
+ * workspace of a fused function is what it is there.  Results of a fused function: the forward's bits are those of the generic launches' operations in
+ * layer order as for gnx_chain_block_forward_narrow (within 1e-5 of the generic path, not its bits); the masks are the same bits on both paths.
+ * gnx_chain_block_train_applies(h, p, R, backward): the fused mask of the training rule (bit 0 edge, 1 node, 2 graph) of the forward
+ * (backward = 0) or the pullback (1) for chains whose Dropout entries are all active; 0 on bad arguments.  Without Dropout entries it equals
+ * gnx_chain_block_forward_narrow_applies / gnx_chain_block_backward_narrow_applies.
+ * The calls allocate nothing, do not synchronise, use one stream and work inside a capture (the seed travels by value); the queries build the
+ * handle's tables: call them outside a capture. */
+#define GNX_LAYER_DROPOUT 2
+typedef struct gnx_chain_dropout {
+  uint64_t seed;     /* fresh per forward call; the backward gets the same value */
+  const float* p[3]; /* edge / node / graph function: host array [n_layers] or NULL; entry i is read only where layer i is GNX_LAYER_DROPOUT */
+} gnx_chain_dropout;
+GNX_API int32_t gnx_chain_dropout_mask(const gnx_chain_dropout* dropout, int32_t function, int32_t layer, float p, int64_t n_elements, float* out,
+                                       void* stream);
+GNX_API int32_t gnx_chain_block_train_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t backward);
+GNX_API size_t gnx_chain_block_forward_train_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t narrow);
+GNX_API int32_t gnx_chain_block_forward_train(const gnx_graphs* h, const gnx_chain_block_params* p, const gnx_chain_dropout* dropout, const float* ef,
+                                              const float* nf, const float* gf, int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out,
+                                              void* workspace, size_t workspace_bytes, int32_t narrow, uint32_t flags, void* stream);
+GNX_API size_t gnx_chain_block_backward_train_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t narrow);
+GNX_API int32_t gnx_chain_block_backward_train(const gnx_graphs* h, const gnx_chain_block_params* p, const gnx_chain_dropout* dropout, const float* ef,
+                                               const float* nf, const float* gf, const float* g_ef_out, const float* g_nf_out, const float* g_gf_out,
+                                               int64_t n_replicas, float* d_ef, float* d_nf, float* d_gf, const gnx_chain_block_grads* grads,
+                                               void* workspace, size_t workspace_bytes, int32_t narrow, void* stream);
+
 /* ---- row statistics of a packed [rows][d] tensor: stats[row] = (mean, 1 / (sigma + eps)) (eps_mode 0, Flux 0.14 `normalise`) or
  * (mean, 1 / sqrt(sigma^2 + eps)) (eps_mode 1), uncorrected sigma — the one pass over x from which the wide kernels apply GNGraphNorm's
  * LayerNorms (src/gngraphnorm.jl:19-26) as they load their rows; exported as the building block it is (and so that it can be exercised
