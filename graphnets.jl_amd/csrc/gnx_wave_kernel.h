@@ -745,6 +745,22 @@ __host__ __device__ constexpr int wave_slice_floats(int OE, int EPT) {
 #ifndef GNX_WAVE_SGPRS
 #define GNX_WAVE_SGPRS 80
 #endif
+// s_waitcnt vmcnt(0) and nothing else (gfx9 encoding: vmcnt in bits 15:14 and 3:0, expcnt 6:4 and lgkmcnt 11:8 at their maxima = not awaited)
+constexpr int kWaitVmcnt0 = 0x0F70;
+#ifndef GNX_WAVE_SEG_BATCH
+#define GNX_WAVE_SEG_BATCH 4  // rows of a node's segment read per LDS round trip in the edge->node sum (1: one row per trip)
+#endif
+// ... per form: the batch lives in registers the edge phase has left, and must not add one to the kernel (the compiler's resource remarks for
+// the ahead-of-time sets decide: four rows added registers at EPT = 1, two do not; a batch cost a register or scratch where the edge phase
+// holds fewer than a dozen values per lane — (0,2,0) and (2,2,2) => (2,2), EPT = 1 at (3,4,5) and (4,3,2) — and in the bf16 kernel of four
+// edges per lane).  One row per trip also where ef' is wider than 4 columns (four rows: up to 21 registers; those kernels are bound by
+// vector issue, and a batch's selects are instructions) and in the FFE form (122-126 registers).
+template <int DE, int DN, int OE, int EPT, bool FFE, bool BF16>
+constexpr int seg_batch() {
+  if (FFE || GNX_WAVE_SEG_BATCH < 2 || OE > 4 || EPT * (DE + DN) < 12 || (BF16 && EPT > 2)) return 1;
+  if (EPT == 1) return 2;
+  return GNX_WAVE_SEG_BATCH;
+}
 #ifdef GNX_WAVE_STAMPS_BUILD  // diagnostic build only (tools/build_variant.sh ... -DGNX_WAVE_STAMPS_BUILD): per-wave shader-clock stamps
 static __device__ unsigned long long* g_wave_dbg = nullptr;  // [n_wtiles][8], set by the launcher
 #define GNX_WSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); wst_[i] = clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -1022,6 +1038,14 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
   float psum[OE1];  // single-node tiles only: this lane's share of the node's edge sum
 #pragma unroll
   for (int j = 0; j < OE1; ++j) psum[j] = 0.f;
+  // Every load is awaited HERE, on every path to the node phase.  The rows of an edge slot are used under `el < cn` only and a tile may have no
+  // edge at all: a wave that branches around the products passes none of their waits, so the compiler had to assume loads in flight at the
+  // end of the edge phase and put s_waitcnt vmcnt(0) in front of the segmented sum — where on the usual path the only vector-memory
+  // operations still outstanding are the ef' stores (counted by vmcnt on this target), and every wave sat out their acknowledgement before
+  // a node phase that reads nothing of them.  The gathered rows were requested last and every slot needs its own, so nothing is lost by
+  // waiting for all loads at once.  (The builtin, not inline assembly: the compiler's wait insertion takes it into account.  Not with LayerNorm
+  // on load: there the first rows are normalised while the gathered ones are still on their way, and the FFE form stores no row here.)
+  if constexpr (!LN) __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
   for (int c0 = 0; c0 < ne; c0 += TEW) {
     const int cn = (ne - c0) < TEW ? (ne - c0) : TEW;
     if (c0 > 0) {  // further chunks of a single-node tile with a huge in-degree: loaded in place
@@ -1044,6 +1068,7 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
           ln_row<DN>(xs[i], A1->ln_g[1], A1->ln_b[1], A1->ln_eps, A1->ln_mode);
         }
       }
+      if constexpr (!LN) __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);  // (as in front of the loop: this chunk's loads, on every path)
     }
     if constexpr (LN) {
       if (c0 == 0) {
@@ -1192,9 +1217,32 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
         v[j] = lane == 0 ? tot : 0.f;
       }
     } else if (is_node) {  // contiguous segmented sum (edges are dst-sorted, src/pad.jl:30), fixed order
-      for (int e = cp0 - e0; e < cp1 - e0; ++e) {
+      constexpr int SB = seg_batch<DE, DN, OE, EPT, FFE, BF16>();
+      if constexpr (SB > 1) {
+        // SB rows per LDS round trip (one row per trip is one s_waitcnt lgkmcnt(0) per in-edge: ~16 dependent trips for the largest node of a
+        // C2 tile): the next SB rows of the lane's segment are read at once — row indices clamped into the segment, so a short tail reads
+        // its last row again — and added IN EDGE ORDER under the lane's own bound: v = ((v + x_e) + x_e+1) + ..., the bits of the plain loop.
+        const int ee = cp1 - e0;
+        for (int e = cp0 - e0; e < ee; e += SB) {
+          float row[SB][OE1];
 #pragma unroll
-        for (int j = 0; j < OE; ++j) v[j] += s_out[e * OE + j];
+          for (int k = 0; k < SB; ++k) {
+            const int ek = e + k < ee ? e + k : ee - 1;
+#pragma unroll
+            for (int j = 0; j < OE; ++j) row[k][j] = s_out[ek * OE + j];
+          }
+#pragma unroll
+          for (int k = 0; k < SB; ++k) {
+            const bool in = k == 0 || e + k < ee;  // (a select, not a branch: the reads above stay one batch)
+#pragma unroll
+            for (int j = 0; j < OE; ++j) v[j] = in ? v[j] + row[k][j] : v[j];
+          }
+        }
+      } else {
+        for (int e = cp0 - e0; e < cp1 - e0; ++e) {
+#pragma unroll
+          for (int j = 0; j < OE; ++j) v[j] += s_out[e * OE + j];
+        }
       }
     }
   }
@@ -1224,11 +1272,20 @@ __device__ __forceinline__ void block_wave_body(BlockArgs& a, int n_rows) {
       float sel[(C + 15) / 16];
 #pragma unroll
       for (int g = 0; g < (C + 15) / 16; ++g) sel[g] = 0.f;
+      // (row16_sum of every column, stage by stage over the columns: a column's four DPP adds depend on one another, and column after
+      // column the compiler put an s_nop between them; unconditionally — a DPP reduction inside the select's branch would run with a
+      // partial EXEC mask)
+      float s16[C];
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float s16 = row16_sum(v[c]);  // (unconditionally: a DPP reduction inside the select's branch would run with a partial EXEC mask)
-        sel[c >> 4] = (lane & 15) == (c & 15) ? s16 : sel[c >> 4];
-      }
+      for (int c = 0; c < C; ++c) s16[c] = dpp_add<0xB1>(v[c]);  // quad_perm [1,0,3,2]
+#pragma unroll
+      for (int c = 0; c < C; ++c) s16[c] = dpp_add<0x4E>(s16[c]);  // quad_perm [2,3,0,1]
+#pragma unroll
+      for (int c = 0; c < C; ++c) s16[c] = dpp_add<0x141>(s16[c]);  // row_half_mirror
+#pragma unroll
+      for (int c = 0; c < C; ++c) s16[c] = dpp_add<0x140>(s16[c]);  // row_mirror
+#pragma unroll
+      for (int c = 0; c < C; ++c) sel[c >> 4] = (lane & 15) == (c & 15) ? s16[c] : sel[c >> 4];
       // Lane l of every DPP row now holds its ROW's sum of columns l%16 (+16, +32, +48); the four rows are added as (r0 + r1) + (r2 + r3)
       // — the association wave_sum() uses, so the bits are the ones the per-column form (4 readlanes + 3 adds + a select per column)
       // produced — by two lane exchanges per 16 columns instead.
