@@ -14,6 +14,7 @@ Conventions that make it read like the reference:
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -781,11 +782,12 @@ class Chain:
     def __len__(self):
         return len(self.layers)
 
-    def _entries(self):
-        """the entries of a training call's gnx_chain in the order the user wrote them: ("layer", Dense | LayerNorm) and ("dropout", p)"""
+    def _entries(self, train=True):
+        """the entries of a training call's gnx_chain in the order the user wrote them: ("layer", Dense | LayerNorm) and ("dropout", p); train =
+        False: the layers alone, in the same form"""
         out = []
         for i in range(len(self.layers) + 1):
-            out += [("dropout", p) for after, p in getattr(self, "dropouts", ()) if after == i]
+            out += [("dropout", p) for after, p in (getattr(self, "dropouts", ()) if train else ()) if after == i]
             if i < len(self.layers):
                 out.append(("layer", self.layers[i]))
         return out
@@ -908,53 +910,236 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _ptr0(t):
+    """_ptr of a gradient slot: NULL for a gradient that is not wanted or has no elements"""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+# ------------------------------------------------------------------------------------------------------------
+# which C entry a call of a GNBlock / GNCore reaches: one table, plain data
+# ------------------------------------------------------------------------------------------------------------
+_SWITCHES = ("bf16", "bf16_backward", "fused_backward", "narrow_backward", "narrow_chain", "narrow_chain_backward", "bf16_chain", "native_chain_backward",
+             "chain_dropout", "typed_dropout")
+_Entry = collections.namedtuple("_Entry", "query query_tail call head tail key")
+_CHAIN_DROPOUT_IS_TEST_MODE = ("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
+                               "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
+
+
+def _switches(owner):
+    """the names of the owner's switches that are on (an object may predate a switch: that one is off)"""
+    return frozenset(s for s in _SWITCHES if getattr(owner, s, False))
+
+
+def _entry(family, direction, elem, switches=(), record=False):
+    """The C entry of ONE call, from Python values alone (the library is not loaded).  family: "block" (a GNBlock with Dense update functions),
+    "chain" (a GNBlock with Chain update functions) or "core" (a GNCore); direction: "forward" or "backward"; elem: _lib.ELEM_F32 / ELEM_BF16 of the
+    feature tensors; switches: the names of the owner's switches that are on (_switches); record: a Dropout record is active for the call.
+
+    Returns _Entry(query, query_tail, call, head, tail, key) — names of include/gnx.h and the values around what every entry of the family takes:
+        nbytes = query(handle, params, R, *query_tail)
+        call(handle, params, *head, <the family's feature, cotangent and gradient pointers>, workspace, nbytes, *tail, stream)
+    A str among these values names a value of the call at hand: "flags", and "drop" = byref of the Dropout record (NULL without one).  `key` is the
+    layout key of GNGraphBatch.workspace, a tag and the call's values behind it; None for a pullback, which allocates a workspace of its own.
+    Raises the NotImplementedError of a combination that is switched off or does not exist.
+
+      block     forward    gnx_block_forward; bf16: gnx_block_forward_typed
+                backward   gnx_block_backward [_fused with `fused_backward`] [_typed on bf16]; gnx_block_backward_narrow with `narrow_backward`
+                           (which wins over `fused_backward`; either element type); bf16 needs `bf16_backward`
+      chain     forward    an active record: gnx_chain_block_forward_train (narrow = `narrow_chain`; fp32 only); bf16: gnx_chain_block_forward_typed
+                           (narrow = `narrow_chain`; needs `bf16_chain`); else gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
+                backward   (narrow = `narrow_chain_backward`) an active record: gnx_chain_block_backward_train; bf16 (needs `bf16_backward`):
+                           gnx_chain_block_backward_narrow_typed with `native_chain_backward`, else gnx_chain_block_backward_typed; fp32:
+                           gnx_chain_block_backward_narrow or gnx_chain_block_backward
+      core      forward    an active record: gnx_core_forward_train_typed with `typed_dropout`, else gnx_core_forward_train (fp32 only); no record:
+                           gnx_core_forward, bf16: gnx_core_forward_typed
+                backward   in this order: an active record with `typed_dropout`: gnx_core_backward_train_typed (narrow = `narrow_backward`);
+                           `narrow_backward`: gnx_core_backward_narrow; bf16: gnx_core_backward_typed; gnx_core_backward, or gnx_core_backward_train
+                           under a record (both sized by gnx_core_backward_workspace_bytes); bf16 needs `bf16_backward`"""
+    assert family in ("block", "chain", "core") and direction in ("forward", "backward") and elem in (_lib.ELEM_F32, _lib.ELEM_BF16)
+    on = lambda s: s in switches
+    bf16, fw, fl = elem == _lib.ELEM_BF16, direction == "forward", ("flags",)
+    E = lambda call, query_tail=(), head=(), tail=(), key=None, query=None: _Entry(query or call + "_workspace_bytes", query_tail, call, head, tail, key)
+    if family == "block":
+        if fw:
+            if bf16:
+                return E("gnx_block_forward_typed", (elem, "flags"), (elem,), fl, ("block_bf16", "in_dims", "out_dims", "R", "flags"), "gnx_block_typed_workspace_bytes")
+            return E("gnx_block_forward", (), (), fl, ("block", "in_dims", "out_dims", "R"), "gnx_block_workspace_bytes")
+        if bf16 and not on("bf16_backward"):
+            raise NotImplementedError("GNBlock: the backward of a bfloat16 forward is not implemented unless the block's bf16_backward switch is on "
+                                      "(GNBlock(..., bf16_backward=True) or blk.bf16_backward = True): its input gradients are rounded to bfloat16; "
+                                      "or call it under torch.no_grad() or with float32 features")
+        e = (elem,) if bf16 or on("narrow_backward") else ()  # (gnx_block_backward and gnx_block_backward_fused are fp32 only: no element code)
+        return E("gnx_block_backward" + ("_narrow" if on("narrow_backward") else ("_fused" if on("fused_backward") else "") + ("_typed" if bf16 else "")), e, e)
+    if family == "chain":
+        if bf16 and not on("bf16_chain"):
+            raise NotImplementedError("GNBlock: Chain update functions on bfloat16 features are not supported unless the block's bf16_chain switch "
+                                      "is on (GNBlock(..., bf16_chain=True) or blk.bf16_chain = True); or convert the features with .float()")
+        if bf16 and record:
+            raise NotImplementedError("GNBlock: an active Dropout inside an update-function Chain on bfloat16 features is not implemented "
+                                      "(gnx_chain_block_forward_train is float32); use testmode(blk) or float32 features")
+        if fw:
+            n = int(on("narrow_chain"))
+            if record:
+                return E("gnx_chain_block_forward_train", (n,), ("drop",), (n, "flags"), ("chain_train", n, "in_dims", "widths", "R"))
+            if bf16:  # (mirrors the entry `narrow_chain` selects)
+                return E("gnx_chain_block_forward_typed", (elem, n), (elem,), (n, "flags"), ("chain_bf16", bool(n), "in_dims", "widths", "R"))
+            if n:
+                return E("gnx_chain_block_forward_narrow", (), (), fl, ("chain_narrow", "in_dims", "widths", "R"))
+            return E("gnx_chain_block_forward", (), (), fl, ("chain", "in_dims", "widths", "R"), "gnx_chain_block_workspace_bytes")
+        if bf16 and not on("bf16_backward"):
+            raise NotImplementedError("GNBlock: the backward of a Chain block on bfloat16 features is not implemented unless the block's bf16_backward "
+                                      "switch is on (GNBlock(..., bf16_backward=True) or blk.bf16_backward = True): its input gradients are rounded "
+                                      "to bfloat16; or call it under torch.no_grad() or with float32 features")
+        n = int(on("narrow_chain_backward"))
+        if record:
+            return E("gnx_chain_block_backward_train", (n,), ("drop",), (n,))
+        if bf16 and on("native_chain_backward"):
+            return E("gnx_chain_block_backward_narrow_typed", (elem,), (elem,))
+        if bf16:  # (mirrors the pullback `narrow_chain_backward` selects)
+            return E("gnx_chain_block_backward_typed", (elem, n), (elem,), (n,))
+        return E("gnx_chain_block_backward_narrow" if n else "gnx_chain_block_backward")
+    if fw:
+        if record and on("typed_dropout"):
+            return E("gnx_core_forward_train_typed", (elem, "flags"), (elem, "drop"), fl, ("core_train_typed", "dims", "R", elem, "flags"), "gnx_core_train_typed_workspace_bytes")
+        if bf16 and record:
+            raise NotImplementedError("GNCore: Dropout in training mode on bfloat16 features (a typed gnx_core_forward_train / "
+                                      "gnx_core_backward_train) is not implemented; use testmode(core), dropout=0 or float32 features")
+        if bf16:
+            return E("gnx_core_forward_typed", (elem, "flags"), (elem,), fl, ("core_bf16", "dims", "R", "flags"), "gnx_core_typed_workspace_bytes")
+        if record:
+            return E("gnx_core_forward_train", (), ("drop",), fl, ("core_train", "dims", "R"), "gnx_core_train_workspace_bytes")
+        return E("gnx_core_forward", (), (), fl, ("core", "dims", "R"), "gnx_core_workspace_bytes")
+    if bf16 and not on("bf16_backward"):
+        raise NotImplementedError("GNCore: the backward of a bfloat16 core is off; construct the core with bf16_backward=True (or set "
+                                  "core.bf16_backward = True) to differentiate through gnx_core_backward_typed, call it under torch.no_grad() "
+                                  "with parameters that need no gradient, or use float32 features")
+    n = int(on("narrow_backward"))
+    if record and on("typed_dropout"):
+        return E("gnx_core_backward_train_typed", (elem, n), (elem, "drop", n))
+    if n:  # (with the call's Dropout value when one is active)
+        return E("gnx_core_backward_narrow", (elem,), (elem, "drop"))
+    if bf16:
+        return E("gnx_core_backward_typed", (elem,), (elem,))
+    return E("gnx_core_backward_train", (), ("drop",), query="gnx_core_backward_workspace_bytes") if record else E("gnx_core_backward")
+
+
+def _values(tokens, env):
+    """the values of an entry's tuple: a str is looked up among the values of the call at hand, anything else stands for itself"""
+    return tuple(env[t] if isinstance(t, str) else t for t in tokens)
+
+
+def _query(lib, e, g, p, R, env, strict=False):
+    """the workspace bytes entry `e` asks for; `strict` (where a query's 0 means that it refused the parameters): GnxError with its message"""
+    nbytes = int(getattr(lib, e.query)(g._h, C.byref(p), R, *_values(e.query_tail, env)))
+    if strict and nbytes == 0:
+        raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
+    return nbytes
+
+
+def _launch(lib, e, g, p, body, ws, env):
+    check(getattr(lib, e.call)(g._h, C.byref(p), *_values(e.head, env), *body, ws.data_ptr(), ws.numel(), *_values(e.tail, env),
+                               torch.cuda.current_stream(g.device).cuda_stream))
+
+
+def _forward(e, g, p, R, widths, elem, feats, env, strict=False):
+    """One forward call of entry `e` on packed [R][T][D] tensors: the three outputs (None where the width is 0), the handle's workspace under the
+    entry's layout key, the launch."""
+    lib = _lib.load()
+    dtype = torch.bfloat16 if elem == _lib.ELEM_BF16 else torch.float32
+    outs = tuple(torch.empty((R, T, d), dtype=dtype, device=g.device) if d > 0 else None for T, d in zip((g.n_edges, g.n_nodes, g.n_graphs), widths))
+    with torch.cuda.device(g.device):
+        ws = g.workspace(_query(lib, e, g, p, R, env, strict), (e.key[0], *_values(e.key[1:], env)))
+        _launch(lib, e, g, p, (*map(_ptr, feats), R, *map(_ptr, outs)), ws, env)
+    return outs
+
+
+def _pullback(e, g, p, R, body, env, strict=False):
+    """One backward call of entry `e` on a fresh workspace of its own (a strict query never returns 0: exactly its size)."""
+    lib = _lib.load()
+    with torch.cuda.device(g.device):
+        nbytes = _query(lib, e, g, p, R, env, strict)
+        ws = torch.empty(nbytes if strict else max(nbytes, 256), dtype=torch.uint8, device=g.device)
+        _launch(lib, e, g, p, body, ws, env)
+
+
+def _aligned(t):
+    """a feature-shaped tensor as the typed entries read it: bf16 buffers must be 4-byte aligned (a view may start at an odd element: copy it)"""
+    return t if t is None or t.data_ptr() % 4 == 0 else t.clone()
+
+
+def _cotangent(t):
+    """a cotangent as the C entries read it: contiguous and aligned; a missing one stays None (passed as NULL)"""
+    return None if t is None else _aligned(t.contiguous())
+
+
+def _remember(ctx, owner, g, R, elem, rec, saved, outs):
+    """what the three autograd nodes keep of a forward call; returns the outputs that exist"""
+    ctx.owner, ctx.g, ctx.R, ctx.elem, ctx.rec = owner, g, R, elem, rec
+    # tensors go through save_for_backward (no ctx -> output -> grad_fn -> ctx cycle; in-place modification is detected); ctx keeps only which were there
+    ctx.slots = tuple(t is not None for t in saved)
+    ctx.save_for_backward(*[t for t in saved if t is not None])
+    ctx.present = tuple(o is not None for o in outs)
+    return tuple(o for o in outs if o is not None)
+
+
+def _recall(ctx, gouts):
+    """(the saved tensors, the cotangents of the three outputs), None where there was none"""
+    sv, it = iter(ctx.saved_tensors), iter(gouts)
+    return [next(sv) if s else None for s in ctx.slots], [_cotangent(next(it)) if pr else None for pr in ctx.present]
+
+
+_NO_GRAD = (None,) * 6  # the nodes' leading arguments (owner, g, R, flags, elem, rec)
+
+
+def _apply(node, widths, *args):
+    """node.apply(*args) -> (eo, no, go), None where the width is 0 (a node returns the outputs that exist)"""
+    outs = iter(node.apply(*args))
+    return tuple(next(outs) if d > 0 else None for d in widths)
+
+
 class GNBlock:
-    """`GNBlock(in => out; dropout=0)` (gnblock.jl:47-61).  `block(x)` = gnblock.jl:63-69 via gnx_block_forward.
+    """`GNBlock(in => out; dropout=0)` (gnblock.jl:47-61).  `block(x)` = gnblock.jl:63-69 via gnx_block_forward; with update functions that are
+    Chains via gnx_chain_block_forward.  Which C entry a call reaches under the switches below (each also a plain attribute, off by default) is
+    the table of `_entry`; what each switch promises:
 
-    `bf16_backward` (also a plain attribute): lets a differentiable call on bfloat16 features run — gnx_block_backward_typed is its pullback,
-    the input gradients come back rounded to bfloat16, the weight / bias gradients in float32.  Off (the default) such a call raises.
+    `bf16_backward` (gnx_block_backward_typed): lets a differentiable call on bfloat16 features run — the input gradients come back rounded to
+    bfloat16, the weight / bias gradients in float32.  Off, such a call raises.
 
-    `fused_backward` (also a plain attribute): the pullback of a float32 call is gnx_block_backward_fused — at the narrow width sets it covers the
-    edge level runs in one kernel; the input gradients and the node / graph parameter gradients keep gnx_block_backward's bits, the edge
-    function's weight / bias gradient is summed in another fixed order.  Elsewhere nothing changes.  With `bf16_backward` on as well, the
-    pullback of a bfloat16 call is gnx_block_backward_fused_typed: the fused edge level reading and writing bfloat16 where it applies (the
-    input gradients and the node / graph parameter gradients keep gnx_block_backward_typed's bits), gnx_block_backward_typed elsewhere.
+    `fused_backward` (gnx_block_backward_fused, gnx_block_backward_fused_typed): at the narrow width sets it covers the edge level of the pullback
+    runs in one kernel; the input gradients and the node / graph parameter gradients keep gnx_block_backward's bits (gnx_block_backward_typed's on
+    bfloat16 features), the edge function's weight / bias gradient is summed in another fixed order.  Elsewhere nothing changes.
 
-    `narrow_backward` (also a plain attribute; wins over `fused_backward`): the pullback is gnx_block_backward_narrow, on float32 features and —
-    with `bf16_backward` — on bfloat16 ones: the fused edge level at ANY eligible narrow width set (oe * (de + 2 dn + dg) < 64), the kernel of a
-    set outside the five ahead-of-time ones specialised at run time on first use (GNX_JIT_CACHE=<dir> keeps it on disk).  On the five sets the
-    bits are `fused_backward`'s; where the set is not eligible nothing changes.
+    `narrow_backward` (gnx_block_backward_narrow; wins over `fused_backward`): the fused edge level at ANY eligible narrow width set
+    (oe * (de + 2 dn + dg) < 64), the kernel of a set outside the five ahead-of-time ones specialised at run time on first use
+    (GNX_JIT_CACHE=<dir> keeps it on disk).  On the five sets the bits are `fused_backward`'s; where the set is not eligible nothing changes.
 
-    `narrow_chain` (also a plain attribute): a block whose update functions are Chains runs its forward through gnx_chain_block_forward_narrow —
-    each update function whose input and layer widths are at most 32 in one kernel (a row per lane through all layers), the others as before.
-    Off (the default): gnx_chain_block_forward.  The pullback (gnx_chain_block_backward) recomputes its activations and does not change.
+    `narrow_chain` (gnx_chain_block_forward_narrow): each update-function Chain whose input and layer widths are at most 32 runs its forward in
+    one kernel (a row per lane through all layers), the others as before.  The pullback recomputes its activations and does not change.
 
-    `narrow_chain_backward` (also a plain attribute; independent of `narrow_chain`): the pullback of such a block is
-    gnx_chain_block_backward_narrow — each update function inside its rule (include/gnx.h: the forward's rule and 64 KB of LDS for two
-    waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled back in one kernel, a row per lane forward
-    and back through all layers, with only what crosses levels recomputed into the workspace; the others as before.  The gradients are within
-    the generic pullback's error of the exact ones, not its bits.  Off (the default): gnx_chain_block_backward.
+    `narrow_chain_backward` (gnx_chain_block_backward_narrow; independent of `narrow_chain`): each update function inside its rule (include/gnx.h:
+    the forward's rule and 64 KB of LDS for two waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled
+    back in one kernel, a row per lane forward and back through all layers, with only what crosses levels recomputed into the workspace; the
+    others as before.  The gradients are within the generic pullback's error of the exact ones, not its bits.
 
-    `bf16_chain` (also a plain attribute): lets a block whose update functions are Chains run on bfloat16 features through
-    gnx_chain_block_forward_typed, mirroring gnx_chain_block_forward_narrow with `narrow_chain` and gnx_chain_block_forward without: bf16 outputs,
-    bit for bit the fp32 entry on the widened inputs rounded once.  With `narrow_chain` and every update function inside the narrow rule the
-    fused kernels read and write the bf16 rows themselves; elsewhere fp32 copies go around the fp32 entry.  A differentiable call also needs
-    `bf16_backward`: its pullback is gnx_chain_block_backward_typed (`narrow_chain_backward` selects the mirrored fp32 pullback), input
-    gradients rounded to bfloat16, parameter gradients in float32.  Off (the default) such a block on bfloat16 features raises.
+    `bf16_chain` (gnx_chain_block_forward_typed, gnx_chain_block_backward_typed): lets a block whose update functions are Chains run on bfloat16
+    features: bf16 outputs, bit for bit the fp32 entry that `narrow_chain` selects on the widened inputs, rounded once.  With `narrow_chain` and
+    every update function inside the narrow rule the fused kernels read and write the bf16 rows themselves; elsewhere fp32 copies go around the
+    fp32 entry.  A differentiable call also needs `bf16_backward`: input gradients rounded to bfloat16, parameter gradients in float32.  Off, such
+    a block on bfloat16 features raises.
 
-    `native_chain_backward` (also a plain attribute): the pullback of a differentiable call of such a block on bfloat16 features (which still
-    needs `bf16_chain` and `bf16_backward`) is gnx_chain_block_backward_narrow_typed.  Where the whole block is inside the narrow pullback's
-    rule, each update function is pulled back in one kernel that reads the bf16 rows and upstream gradients and writes the bf16 edge gradient
-    itself: no edge- or node-sized fp32 copy is made, and the gradients are bit for bit those of gnx_chain_block_backward_typed with
-    `narrow_chain_backward`.  Elsewhere the call is that staged pullback.  Off (the default), and on float32 features, nothing changes.
+    `native_chain_backward` (gnx_chain_block_backward_narrow_typed): where the whole block is inside the narrow pullback's rule, each update
+    function of a differentiable bfloat16 call (which still needs `bf16_chain` and `bf16_backward`) is pulled back in one kernel that reads the
+    bf16 rows and upstream gradients and writes the bf16 edge gradient itself: no edge- or node-sized fp32 copy is made, and the gradients are bit
+    for bit those of gnx_chain_block_backward_typed with `narrow_chain_backward`.  Elsewhere the call is that staged pullback.  On float32
+    features nothing changes.
 
-    `chain_dropout` (also a plain attribute): `Dropout(p)` layers inside the update-function Chains are applied in training mode.  A call with an
-    active Dropout — some p > 0, and inside a gradient call or forced by `trainmode` / `testmode` — runs gnx_chain_block_forward_train and, where
-    differentiable, gnx_chain_block_backward_train (`narrow` = `narrow_chain` / `narrow_chain_backward`: each function inside the training rule
-    in one kernel that regenerates its masks in registers).  Every call draws a fresh seed (from `rng` if set; torch.manual_seed reproduces it) and
-    keeps the record in `last_chain_dropout` (`chain_dropout_mask` turns it into masks).  A call without an active Dropout runs what it ran before.
-    float32 features only: bfloat16 features with an active chain Dropout raise NotImplementedError.  Off (the default): a differentiable call of a
-    block whose chains hold a Dropout(p > 0) raises NotImplementedError, as before."""
+    `chain_dropout` (gnx_chain_block_forward_train, gnx_chain_block_backward_train): `Dropout(p)` layers inside the update-function Chains are
+    applied in training mode.  A call with an active Dropout — some p > 0, and inside a gradient call or forced by `trainmode` / `testmode` — runs
+    the training entries (narrow = `narrow_chain` /
+    `narrow_chain_backward`: each function inside the training rule in one kernel that regenerates its masks in registers).  Every call draws a
+    fresh seed (from `rng` if set; torch.manual_seed reproduces it) and keeps the record in `last_chain_dropout` (`chain_dropout_mask` turns it into
+    masks).  A call without an active Dropout runs what it ran before.  float32 features only: bfloat16 features with an active chain Dropout raise
+    NotImplementedError.  Off: a differentiable call of a block whose chains hold a Dropout(p > 0) raises NotImplementedError."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
                  narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False, chain_dropout=False):
@@ -1022,21 +1207,29 @@ class GNBlock:
     def _as_chain(self, fn):
         return fn if isinstance(fn, Chain) else Chain(fn)
 
-    def _chain_params(self, keep):
-        """gnx_chain_block_params of this block's update functions (each a Chain of Dense layers) + the chains themselves."""
+    def _chain_params(self, keep, train=False):
+        """(gnx_chain_block_params of this block's update functions (each a Chain), the chains themselves, their output widths).  train: the form
+        of a training call — the chains with their Dropout entries where the user wrote them (GNX_LAYER_DROPOUT: no weight, no bias, the width of
+        the entry in front)"""
         chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
         p = _lib.ChainBlockParams()
         p.de, p.dn, p.dg = self.in_dims
         outw = []
         for name, ch in zip(("edgefn", "nodefn", "graphfn"), chains):
-            widths = [int(l.weight.shape[0]) for l in ch.layers]
-            arr = (_lib.Dense * max(len(ch.layers), 1))(*[l._c_layer(keep) for l in ch.layers])
-            wid = (C.c_int32 * max(len(ch.layers), 1))(*widths)
+            entries, widths = [], []
+            for kind, l in ch._entries(train):
+                widths.append(widths[-1] if kind == "dropout" else int(l.weight.shape[0]))
+                entries.append(_lib.Dense(None, None, _lib.ACT["identity"], _lib.LAYER_DROPOUT) if kind == "dropout" else l._c_layer(keep))
+            arr = (_lib.Dense * max(len(entries), 1))(*entries)
+            wid = (C.c_int32 * max(len(entries), 1))(*widths)
             keep += [arr, wid]
             c = getattr(p, name)
-            c.layers, c.widths, c.n_layers = arr, wid, len(ch.layers)
+            c.layers, c.widths, c.n_layers = arr, wid, len(entries)
             outw.append(widths[-1] if widths else 0)
         return p, chains, outw
+
+    def _chain_train_params(self, keep):
+        return self._chain_params(keep, train=True)
 
     def _chain_dropout_now(self, chains, grad_call):
         """The record of the Dropouts inside this block's Chains for THIS call: None (identity: the call runs what it ran before) or a ChainDropout
@@ -1055,127 +1248,44 @@ class GNBlock:
         self.last_chain_dropout = ChainDropout(seed, [[v if k == "dropout" else 0.0 for k, v in ch._entries()] for ch in chains])
         return self.last_chain_dropout
 
-    def _chain_train_params(self, keep):
-        """_chain_params for a training call: the chains with their Dropout entries where the user wrote them (GNX_LAYER_DROPOUT: no weight, no
-        bias, the width of the entry in front)"""
+    def _chain_call(self, *feats):
+        """(the update functions as Chains, their parameter tensors, whether this call is differentiable)"""
         chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
-        p = _lib.ChainBlockParams()
-        p.de, p.dn, p.dg = self.in_dims
-        outw = []
-        for name, ch in zip(("edgefn", "nodefn", "graphfn"), chains):
-            entries, widths = [], []
-            for kind, l in ch._entries():
-                widths.append(widths[-1] if kind == "dropout" else int(l.weight.shape[0]))
-                entries.append(_lib.Dense(None, None, _lib.ACT["identity"], _lib.LAYER_DROPOUT) if kind == "dropout" else l._c_layer(keep))
-            arr = (_lib.Dense * max(len(entries), 1))(*entries)
-            wid = (C.c_int32 * max(len(entries), 1))(*widths)
-            keep += [arr, wid]
-            c = getattr(p, name)
-            c.layers, c.widths, c.n_layers = arr, wid, len(entries)
-            outw.append(widths[-1] if widths else 0)
-        return p, chains, outw
+        params = [t for ch in chains for l in ch.layers for t in (l.weight, l.bias)]
+        return chains, params, torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in [*feats, *params])
 
-    def _chain_train_forward(self, g, R, flags, rec, ef, nf, gf):
-        """gnx_chain_block_forward_train under the record `rec` (narrow = `narrow_chain`)"""
-        lib = _lib.load()
-        keep = []
-        p, chains, outw = self._chain_train_params(keep)
-        dev = g.device
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.float32, device=dev) if d > 0 else None
-        eo, no, go = mk(g.n_edges, outw[0]), mk(g.n_nodes, outw[1]), mk(g.n_graphs, outw[2])
-        narrow = int(bool(getattr(self, "narrow_chain", False)))
-        with torch.cuda.device(dev):
-            nbytes = lib.gnx_chain_block_forward_train_workspace_bytes(g._h, C.byref(p), R, narrow)
-            if nbytes == 0:
-                raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-            ws = g.workspace(nbytes, ("chain_train", narrow, self.in_dims, tuple(tuple(k if k == "dropout" else int(l.weight.shape[0]) for k, l in ch._entries())
-                                                                                 for ch in chains), R))
-            drop = rec._c(keep)
-            check(lib.gnx_chain_block_forward_train(g._h, C.byref(p), C.byref(drop), _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
-                                                    ws.data_ptr(), ws.numel(), narrow, flags, torch.cuda.current_stream(dev).cuda_stream))
-        return eo, no, go
-
-    def _chain_forward(self, g, R, flags, ef, nf, gf, bf16=False):
-        lib = _lib.load()
-        keep = []
-        p, chains, outw = self._chain_params(keep)
-        dev = g.device
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.bfloat16 if bf16 else torch.float32, device=dev) if d > 0 else None
-        eo, no, go = mk(g.n_edges, outw[0]), mk(g.n_nodes, outw[1]), mk(g.n_graphs, outw[2])
-        with torch.cuda.device(dev):
-            narrow = bool(getattr(self, "narrow_chain", False))
-            if bf16:  # gnx_chain_block_forward_typed mirrors the entry `narrow_chain` selects
-                nbytes = lib.gnx_chain_block_forward_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, int(narrow))
-                if nbytes == 0:
-                    raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-                ws = g.workspace(nbytes, ("chain_bf16", narrow, self.in_dims, tuple(tuple(int(l.weight.shape[0]) for l in ch.layers) for ch in chains), R))
-                check(lib.gnx_chain_block_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
-                                                        ws.data_ptr(), ws.numel(), int(narrow), flags, torch.cuda.current_stream(dev).cuda_stream))
-                return eo, no, go
-            query, entry = ((lib.gnx_chain_block_forward_narrow_workspace_bytes, lib.gnx_chain_block_forward_narrow) if narrow else
-                            (lib.gnx_chain_block_workspace_bytes, lib.gnx_chain_block_forward))
-            nbytes = query(g._h, C.byref(p), R)
-            if nbytes == 0:
-                raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-            ws = g.workspace(nbytes, ("chain_narrow" if narrow else "chain", self.in_dims,
-                                      tuple(tuple(int(l.weight.shape[0]) for l in ch.layers) for ch in chains), R))
-            check(entry(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
-                                              ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
-        return eo, no, go
+    def _run_chains(self, g, R, flags, elem, rec, ef, nf, gf, chains, params, grad_call):
+        flags = self.flags if flags is None else flags
+        if grad_call:
+            eo, no, go = _apply(_ChainBlockFn, [ch.out_width for ch in chains], self, g, R, flags, elem, rec, ef, nf, gf, *params)
+        else:
+            eo, no, go = _chain_forward(self, g, R, flags, elem, rec, *map(_aligned, (ef, nf, gf)))
+        return NT(g, _jl(eo), _jl(no), _jl(go))
 
     def _call_chains(self, x, flags):
-        """Update functions that are multi-layer Chains: gnx_chain_block_forward; differentiable through gnx_chain_block_backward."""
+        """Update functions that are multi-layer Chains, float32 features; with `chain_dropout` and an active Dropout: the training entries."""
         g, ef, nf, gf, R = _forward_common(x, self.in_dims, "GNBlock")
-        flags = self.flags if flags is None else flags
-        chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
-        params = [t for ch in chains for l in ch.layers for t in (l.weight, l.bias)]
-        grad_call = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [ef, nf, gf] + params)
+        chains, params, grad_call = self._chain_call(ef, nf, gf)
         rec = self._chain_dropout_now(chains, grad_call)
-        if rec is not None:  # `chain_dropout` and an active Dropout: the training entries
-            if grad_call:
-                outs = iter(_ChainBlockTrainFn.apply(self, g, R, flags, rec, ef, nf, gf, *params))
-                eo, no, go = (next(outs) if ch.out_width > 0 else None for ch in chains)
-            else:
-                eo, no, go = self._chain_train_forward(g, R, flags, rec, ef, nf, gf)
-        elif grad_call:
-            if any(ch.dropout_p > 0 for ch in chains) and not (getattr(self, "chain_dropout", False) and getattr(self, "_dropout_mode", None) is False):
-                raise NotImplementedError("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
-                                          "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
-            outs = iter(_ChainBlockFn.apply(self, g, R, flags, ef, nf, gf, *params))
-            eo, no, go = (next(outs) if ch.out_width > 0 else None for ch in chains)
-        else:
-            eo, no, go = self._chain_forward(g, R, flags, ef, nf, gf)
-        return NT(g, _jl(eo), _jl(no), _jl(go))
+        if rec is None and grad_call and any(ch.dropout_p > 0 for ch in chains) and \
+                not (getattr(self, "chain_dropout", False) and getattr(self, "_dropout_mode", None) is False):
+            raise NotImplementedError(_CHAIN_DROPOUT_IS_TEST_MODE)
+        return self._run_chains(g, R, flags, _lib.ELEM_F32, rec, ef, nf, gf, chains, params, grad_call)
 
     def _call_chains_bf16(self, x, flags):
-        """Chain update functions on bfloat16 features (`bf16_chain`): gnx_chain_block_forward_typed, bf16 outputs; a differentiable call needs
-        `bf16_backward` (gnx_chain_block_backward_typed is then the pullback) and raises without it."""
+        """Chain update functions on bfloat16 features (`bf16_chain`): bf16 outputs; a differentiable call needs `bf16_backward`.  Everything else is
+        refused before any library call."""
         xt = _as_nt(x)
-        chains = [self._as_chain(f) for f in (self.edgefn, self.nodefn, self.graphfn)]
-        params = [t for ch in chains for l in ch.layers for t in (l.weight, l.bias)]
-        feats = [a for a in (xt.ef, xt.nf, xt.gf) if isinstance(a, torch.Tensor)]
-        trainable = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in feats + params)
-        if getattr(self, "chain_dropout", False) and getattr(self, "_dropout_mode", None) is True and any(ch.dropout_p > 0 for ch in chains):
-            raise NotImplementedError("GNBlock: an active Dropout inside an update-function Chain on bfloat16 features is not implemented "
-                                      "(gnx_chain_block_forward_train is float32); use testmode(blk) or float32 features")
-        if trainable:
-            if not getattr(self, "bf16_backward", False):
-                raise NotImplementedError("GNBlock: the backward of a Chain block on bfloat16 features is not implemented unless the block's bf16_backward "
-                                          "switch is on (GNBlock(..., bf16_backward=True) or blk.bf16_backward = True): its input gradients are rounded "
-                                          "to bfloat16; or call it under torch.no_grad() or with float32 features")
-            if any(ch.dropout_p > 0 for ch in chains):
-                raise NotImplementedError("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
-                                          "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
+        chains, params, grad_call = self._chain_call(xt.ef, xt.nf, xt.gf)
+        sw, dropouts = _switches(self), any(ch.dropout_p > 0 for ch in chains)
+        if dropouts and "chain_dropout" in sw and getattr(self, "_dropout_mode", None) is True:
+            _entry("chain", "forward", _lib.ELEM_BF16, sw, record=True)  # refused: the training entries are float32
+        if grad_call:
+            _entry("chain", "backward", _lib.ELEM_BF16, sw)  # refused without bf16_backward
+            if dropouts:
+                raise NotImplementedError(_CHAIN_DROPOUT_IS_TEST_MODE)
         g, ef, nf, gf, R = _forward_common(x, self.in_dims, None)
-        flags = self.flags if flags is None else flags
-        if trainable:
-            outs = iter(_ChainBlockBf16Fn.apply(self, g, R, flags, ef, nf, gf, *params))
-            eo, no, go = (next(outs) if ch.out_width > 0 else None for ch in chains)
-        else:
-            # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
-            ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-            eo, no, go = self._chain_forward(g, R, flags, ef, nf, gf, bf16=True)
-        return NT(g, _jl(eo), _jl(no), _jl(go))
+        return self._run_chains(g, R, flags, _lib.ELEM_BF16, None, ef, nf, gf, chains, params, grad_call)
 
     def __call__(self, x, flags=None):
         fns = (self.edgefn, self.nodefn, self.graphfn)
@@ -1183,267 +1293,99 @@ class GNBlock:
         xt = _as_nt(x)
         if _feature_dtype(xt.ef, xt.nf, xt.gf) == torch.bfloat16:  # (mixed bf16 / other features: TypeError, before any library call)
             if chained:
-                if not getattr(self, "bf16_chain", False):
-                    raise NotImplementedError("GNBlock: Chain update functions on bfloat16 features are not supported unless the block's bf16_chain switch "
-                                              "is on (GNBlock(..., bf16_chain=True) or blk.bf16_chain = True); or convert the features with .float()")
+                _entry("chain", "forward", _lib.ELEM_BF16, _switches(self))  # refused without bf16_chain
                 return self._call_chains_bf16(x, flags)
             return self._call_bf16(x, flags)
         if chained:
             return self._call_chains(x, flags)
+        return self._call_dense(x, flags, _lib.ELEM_F32)
+
+    def _call_bf16(self, x, flags):
+        """bfloat16 features (batch(..., dtype=torch.bfloat16)): bf16 outputs — bit for bit the fp32 forward of the widened inputs, rounded once to
+        bf16.  A differentiable call needs `bf16_backward`; without it it raises NotImplementedError."""
+        return self._call_dense(x, flags, _lib.ELEM_BF16)
+
+    def _call_dense(self, x, flags, elem):
         if any(isinstance(f, Chain) for f in (self.edgefn, self.nodefn, self.graphfn)):  # one-layer chains are plain Dense layers
             self.edgefn, self.nodefn, self.graphfn = (f.layers[0] if isinstance(f, Chain) else f for f in (self.edgefn, self.nodefn, self.graphfn))
         self._sync_dims()
-        g, ef, nf, gf, R = _forward_common(x, self.in_dims, "GNBlock")
-        if self._trainable((ef, nf, gf)):  # differentiable call: gnx_block_backward is the pullback
-            outs = iter(_BlockFn.apply(self, g, R, self.flags if flags is None else flags, ef, nf, gf, self.edgefn.weight, self.edgefn.bias,
-                                       self.nodefn.weight, self.nodefn.bias, self.graphfn.weight, self.graphfn.bias))
-            eo, no, go = (next(outs) if d > 0 else None for d in self.out_dims)
-            return NT(g, _jl(eo), _jl(no), _jl(go))
-        lib = _lib.load()
-        keep = []
-        p = self._c(keep)
-        oe, on, og = self.out_dims
-        dev = g.device
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.float32, device=dev) if d > 0 else None
-        eo, no, go = mk(g.n_edges, oe), mk(g.n_nodes, on), mk(g.n_graphs, og)
-        with torch.cuda.device(dev):
-            ws = g.workspace(lib.gnx_block_workspace_bytes(g._h, C.byref(p), R), ("block", self.in_dims, self.out_dims, R))
-            check(lib.gnx_block_forward(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
-                                        ws.data_ptr(), ws.numel(), (self.flags if flags is None else flags),
-                                        torch.cuda.current_stream(dev).cuda_stream))
+        g, ef, nf, gf, R = _forward_common(x, self.in_dims, "GNBlock" if elem == _lib.ELEM_F32 else None)
+        flags = self.flags if flags is None else flags
+        if self._trainable((ef, nf, gf)):  # differentiable call: through the autograd node
+            _entry("block", "backward", elem, _switches(self))  # (bfloat16 features: refused without bf16_backward)
+            eo, no, go = _apply(_BlockFn, self.out_dims, self, g, R, flags, elem, None, ef, nf, gf,
+                                *(t for l in (self.edgefn, self.nodefn, self.graphfn) for t in (l.weight, l.bias)))
+        else:
+            eo, no, go = _block_forward(self, g, R, flags, elem, *map(_aligned, (ef, nf, gf)))
         return NT(g, _jl(eo), _jl(no), _jl(go))  # zero-width outputs are None (gnblock.jl:71-78)
 
 
-    def _call_bf16(self, x, flags):
-        """bfloat16 features (batch(..., dtype=torch.bfloat16)): gnx_block_forward_typed, bf16 outputs — bit for bit the fp32 forward of the
-        widened inputs, rounded once to bf16.  A differentiable call needs `bf16_backward` (gnx_block_backward_typed is then the pullback);
-        without it it raises NotImplementedError."""
-        if any(isinstance(f, Chain) for f in (self.edgefn, self.nodefn, self.graphfn)):  # one-layer chains are plain Dense layers
-            self.edgefn, self.nodefn, self.graphfn = (f.layers[0] if isinstance(f, Chain) else f for f in (self.edgefn, self.nodefn, self.graphfn))
-        self._sync_dims()
-        g, ef, nf, gf, R = _forward_common(x, self.in_dims, None)
-        if self._trainable((ef, nf, gf)):
-            if not getattr(self, "bf16_backward", False):
-                raise NotImplementedError("GNBlock: the backward of a bfloat16 forward is not implemented unless the block's bf16_backward switch is on "
-                                          "(GNBlock(..., bf16_backward=True) or blk.bf16_backward = True): its input gradients are rounded to bfloat16; "
-                                          "or call it under torch.no_grad() or with float32 features")
-            outs = iter(_BlockBf16Fn.apply(self, g, R, self.flags if flags is None else flags, ef, nf, gf, self.edgefn.weight, self.edgefn.bias,
-                                           self.nodefn.weight, self.nodefn.bias, self.graphfn.weight, self.graphfn.bias))
-            eo, no, go = (next(outs) if d > 0 else None for d in self.out_dims)
-            return NT(g, _jl(eo), _jl(no), _jl(go))
-        # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
-        ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-        lib = _lib.load()
-        keep = []
-        p = self._c(keep)
-        oe, on, og = self.out_dims
-        dev = g.device
-        flags = self.flags if flags is None else flags
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.bfloat16, device=dev) if d > 0 else None
-        eo, no, go = mk(g.n_edges, oe), mk(g.n_nodes, on), mk(g.n_graphs, og)
-        with torch.cuda.device(dev):
-            nbytes = lib.gnx_block_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, flags)
-            ws = g.workspace(nbytes, ("block_bf16", self.in_dims, self.out_dims, R, flags))
-            check(lib.gnx_block_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
-                                              ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
-        return NT(g, _jl(eo), _jl(no), _jl(go))
+def _block_forward(block, g, R, flags, elem, ef, nf, gf):
+    """the forward of a GNBlock with Dense update functions on packed (bf16: aligned) tensors"""
+    keep = []
+    p = block._c(keep)
+    env = dict(flags=flags, R=R, in_dims=block.in_dims, out_dims=block.out_dims)
+    return _forward(_entry("block", "forward", elem), g, p, R, block.out_dims, elem, (ef, nf, gf), env)
+
+
+def _chain_forward(block, g, R, flags, elem, rec, ef, nf, gf):
+    """the forward of a GNBlock with Chain update functions on packed (bf16: aligned) tensors; rec: the call's ChainDropout record or None"""
+    keep, train = [], rec is not None
+    p, chains, outw = block._chain_params(keep, train)
+    drop = rec._c(keep) if train else None
+    widths = tuple(tuple(k if k == "dropout" else int(l.weight.shape[0]) for k, l in ch._entries(train)) for ch in chains)
+    env = dict(flags=flags, R=R, in_dims=block.in_dims, widths=widths, drop=C.byref(drop) if train else None)
+    return _forward(_entry("chain", "forward", elem, _switches(block), train), g, p, R, outw, elem, (ef, nf, gf), env, strict=True)
 
 
 class _BlockFn(torch.autograd.Function):
-    """torch autograd node of one GNBlock call: forward = gnx_block_forward, backward = gnx_block_backward (the analogue of
-    the Zygote `rrule` the Julia shim would define).  Tensors are packed [R][T][D]; weights (out, in) column-major."""
+    """torch autograd node of one call of a GNBlock with Dense update functions, on float32 or bfloat16 features (the analogue of the Zygote `rrule`
+    the Julia shim would define).  Tensors are packed [R][T][D]; weights (out, in) column-major.  On bfloat16 features the six
+    saved tensors are bf16 and the input gradients come back in bf16 (rounded once from the fp32 pullback at the rounded saved outputs), the
+    weight / bias gradients in fp32 either way."""
 
     @staticmethod
-    def forward(ctx, block, g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg):
-        lib = _lib.load()
-        keep = []
-        p = block._c(keep)
-        oe, on, og = block.out_dims
-        dev = g.device
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.float32, device=dev) if d > 0 else None
-        eo, no, go = mk(g.n_edges, oe), mk(g.n_nodes, on), mk(g.n_graphs, og)
-        with torch.cuda.device(dev):
-            ws = g.workspace(lib.gnx_block_workspace_bytes(g._h, C.byref(p), R), ("block", block.in_dims, block.out_dims, R))
-            check(lib.gnx_block_forward(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go), ws.data_ptr(),
-                                        ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
-        ctx.block, ctx.g, ctx.R = block, g, R
-        # tensors go through save_for_backward (no ctx -> output -> grad_fn -> ctx cycle; in-place modification is detected);
-        # ctx keeps only which of the six slots were present
-        six = (ef, nf, gf, eo, no, go)
-        ctx.slots = tuple(t is not None for t in six)
-        ctx.save_for_backward(*[t for t in six if t is not None])
-        outs = tuple(o for o in (eo, no, go) if o is not None)
-        ctx.present = tuple(o is not None for o in (eo, no, go))
-        return outs
+    def forward(ctx, block, g, R, flags, elem, rec, ef, nf, gf, *params):
+        ef, nf, gf = map(_aligned, (ef, nf, gf))
+        outs = _block_forward(block, g, R, flags, elem, ef, nf, gf)
+        return _remember(ctx, block, g, R, elem, rec, (ef, nf, gf, *outs), outs)
 
     @staticmethod
     def backward(ctx, *gouts):
-        return _block_pullback(ctx, gouts, _lib.ELEM_F32)
+        return _block_pullback(ctx, gouts)
 
 
-class _BlockBf16Fn(torch.autograd.Function):
-    """_BlockFn on bfloat16 features (GNBlock.bf16_backward): forward = gnx_block_forward_typed, backward = gnx_block_backward_typed
-    (gnx_block_backward_fused_typed with GNBlock.fused_backward, gnx_block_backward_narrow with GNBlock.narrow_backward).  The six
-    saved tensors are bf16; the input gradients come back in bf16 (rounded once from the fp32 pullback at the rounded saved outputs), the
-    weight / bias gradients in fp32 in _BlockFn's layout."""
-
-    @staticmethod
-    def forward(ctx, block, g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg):
-        lib = _lib.load()
-        keep = []
-        p = block._c(keep)
-        oe, on, og = block.out_dims
-        dev = g.device
-        # the typed entries need 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
-        ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-        mk = lambda T, d: torch.empty((R, T, d), dtype=torch.bfloat16, device=dev) if d > 0 else None
-        eo, no, go = mk(g.n_edges, oe), mk(g.n_nodes, on), mk(g.n_graphs, og)
-        with torch.cuda.device(dev):
-            nbytes = lib.gnx_block_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, flags)
-            ws = g.workspace(nbytes, ("block_bf16", block.in_dims, block.out_dims, R, flags))
-            check(lib.gnx_block_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, _ptr(ef), _ptr(nf), _ptr(gf), R, _ptr(eo), _ptr(no), _ptr(go),
-                                              ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
-        ctx.block, ctx.g, ctx.R = block, g, R
-        six = (ef, nf, gf, eo, no, go)
-        ctx.slots = tuple(t is not None for t in six)
-        ctx.save_for_backward(*[t for t in six if t is not None])
-        ctx.present = tuple(o is not None for o in (eo, no, go))
-        return tuple(o for o in (eo, no, go) if o is not None)
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        return _block_pullback(ctx, gouts, _lib.ELEM_BF16)
-
-
-def _cotangent(t, elem):
-    """a cotangent as the C entries read it: contiguous, and for the bf16 entries 4-byte aligned (a view may start at an odd element: copy it);
-    a missing one stays None (passed as NULL)"""
-    if t is None:
-        return None
-    t = t.contiguous()
-    return t.clone() if elem == _lib.ELEM_BF16 and t.data_ptr() % 4 else t
-
-
-def _block_pullback(ctx, gouts, elem):
-    """backward of _BlockFn (elem = ELEM_F32) and _BlockBf16Fn (ELEM_BF16).  The C entry by element type and the block's switches —
-    GNBlock.narrow_backward wins over GNBlock.fused_backward:
-                  plain                      fused_backward                    narrow_backward
-      fp32        gnx_block_backward         gnx_block_backward_fused          gnx_block_backward_narrow
-      bf16        gnx_block_backward_typed   gnx_block_backward_fused_typed    gnx_block_backward_narrow"""
-    lib = _lib.load()
-    block, g, R = ctx.block, ctx.g, ctx.R
-    bf16 = elem == _lib.ELEM_BF16
-    sv = iter(ctx.saved_tensors)
-    ef, nf, gf, eo, no, go = (next(sv) if present else None for present in ctx.slots)
-    it = iter(gouts)
-    ge, gn_, gg = (_cotangent(next(it), elem) if pr else None for pr in ctx.present)
+def _block_pullback(ctx, gouts):
+    block, g, R = ctx.owner, ctx.g, ctx.R
+    (ef, nf, gf, eo, no, go), cots = _recall(ctx, gouts)
     keep = []
     p = block._c(keep)
-    dev = g.device
-    need = ctx.needs_input_grad[1:]  # (g, R, flags, ef, nf, gf, We, be, Wn, bn, Wg, bg) -> ef is need[3]
-    d_ef = torch.empty_like(ef) if ef is not None and need[3] else None
-    d_nf = torch.empty_like(nf) if nf is not None and need[4] else None
-    d_gf = torch.empty_like(gf) if gf is not None and need[5] else None
+    need = ctx.needs_input_grad[len(_NO_GRAD):]  # (ef, nf, gf, We, be, Wn, bn, Wg, bg)
+    d = [torch.empty_like(a) if a is not None and n else None for a, n in zip((ef, nf, gf), need)]
     layers = (block.edgefn, block.nodefn, block.graphfn)
-    gW = [torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev) if need[6 + 2 * i] else None for i, l in enumerate(layers)]
-    gb = [torch.empty_like(l.bias) if (l.bias is not None and need[7 + 2 * i]) else None for i, l in enumerate(layers)]
-    grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None)
-                              for w, b in zip(gW, gb)])
-    narrow = getattr(block, "narrow_backward", False)
-    e = (elem,) if bf16 or narrow else ()  # (gnx_block_backward and gnx_block_backward_fused are fp32 only: no element code)
-    if narrow:  # (the fused edge level at any eligible narrow width set)
-        query, call = lib.gnx_block_backward_narrow_workspace_bytes, lib.gnx_block_backward_narrow
-    elif getattr(block, "fused_backward", False):  # (the narrow edge level in one kernel)
-        query, call = (lib.gnx_block_backward_fused_typed_workspace_bytes, lib.gnx_block_backward_fused_typed) if bf16 else \
-                      (lib.gnx_block_backward_fused_workspace_bytes, lib.gnx_block_backward_fused)
-    else:
-        query, call = (lib.gnx_block_backward_typed_workspace_bytes, lib.gnx_block_backward_typed) if bf16 else \
-                      (lib.gnx_block_backward_workspace_bytes, lib.gnx_block_backward)
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(int(query(g._h, C.byref(p), R, *e)), 256), dtype=torch.uint8, device=dev)
-        check(call(g._h, C.byref(p), *e, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(eo), _ptr(no), _ptr(go), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
-                   _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    gWt = [None if w is None else w.t() for w in gW]  # (out, in) view with column-major storage, like the weights
-    return (None, None, None, None, d_ef, d_nf, d_gf, gWt[0], gb[0], gWt[1], gb[1], gWt[2], gb[2])
+    gW = [torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=g.device) if need[3 + 2 * i] else None for i, l in enumerate(layers)]
+    gb = [torch.empty_like(l.bias) if (l.bias is not None and need[4 + 2 * i]) else None for i, l in enumerate(layers)]
+    grads = _lib.BlockGrads(*[_lib.DenseGrad(_ptr0(w), _ptr0(b)) for w, b in zip(gW, gb)])
+    _pullback(_entry("block", "backward", ctx.elem, _switches(block)), g, p, R,
+              (*map(_ptr, (ef, nf, gf, eo, no, go)), *map(_ptr, cots), R, *map(_ptr, d), C.byref(grads)), {})
+    # (out, in) views with column-major storage, like the weights
+    return (*_NO_GRAD, *d, *(t for w, b in zip(gW, gb) for t in (None if w is None else w.t(), b)))
 
 
 class _ChainBlockFn(torch.autograd.Function):
-    """autograd node of a GNBlock whose update functions are Chains: forward = gnx_chain_block_forward, backward =
-    gnx_chain_block_backward (which recomputes every layer's output from the inputs), or gnx_chain_block_backward_narrow with the block's
-    `narrow_chain_backward` switch."""
+    """autograd node of one call of a GNBlock whose update functions are Chains (the pullback recomputes every layer's output from the three saved
+    inputs).  rec: the call's ChainDropout record — the masks are regenerated from it in the pullback, never stored — or None.  On bfloat16
+    features the saved inputs are bf16 and the input gradients come back in bf16 (rounded once from the fp32 pullback of the widened tensors),
+    the parameter gradients in fp32 either way."""
 
     @staticmethod
-    def forward(ctx, block, g, R, flags, ef, nf, gf, *params):
-        eo, no, go = block._chain_forward(g, R, flags, ef, nf, gf)
-        ctx.block, ctx.g, ctx.R = block, g, R
-        ctx.slots = tuple(t is not None for t in (ef, nf, gf))
-        ctx.save_for_backward(*[t for t in (ef, nf, gf) if t is not None])
-        ctx.present = tuple(o is not None for o in (eo, no, go))
-        return tuple(o for o in (eo, no, go) if o is not None)
+    def forward(ctx, block, g, R, flags, elem, rec, ef, nf, gf, *params):
+        ef, nf, gf = map(_aligned, (ef, nf, gf))
+        return _remember(ctx, block, g, R, elem, rec, (ef, nf, gf), _chain_forward(block, g, R, flags, elem, rec, ef, nf, gf))
 
     @staticmethod
     def backward(ctx, *gouts):
-        return _chain_block_pullback(ctx, gouts, _lib.ELEM_F32)
-
-
-class _ChainBlockTrainFn(torch.autograd.Function):
-    """_ChainBlockFn with active Dropouts inside the Chains (GNBlock.chain_dropout): forward = gnx_chain_block_forward_train, backward =
-    gnx_chain_block_backward_train under the same record — the masks are regenerated, never stored (narrow = the block's `narrow_chain` /
-    `narrow_chain_backward`)."""
-
-    @staticmethod
-    def forward(ctx, block, g, R, flags, rec, ef, nf, gf, *params):
-        eo, no, go = block._chain_train_forward(g, R, flags, rec, ef, nf, gf)
-        ctx.block, ctx.g, ctx.R, ctx.rec = block, g, R, rec
-        ctx.slots = tuple(t is not None for t in (ef, nf, gf))
-        ctx.save_for_backward(*[t for t in (ef, nf, gf) if t is not None])
-        ctx.present = tuple(o is not None for o in (eo, no, go))
-        return tuple(o for o in (eo, no, go) if o is not None)
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        lib = _lib.load()
-        block, g, R = ctx.block, ctx.g, ctx.R
-        sv = iter(ctx.saved_tensors)
-        ef, nf, gf = (next(sv) if present else None for present in ctx.slots)
-        it = iter(gouts)
-        ge, gn_, gg = (None if t is None else t.contiguous() for t in (next(it) if pr else None for pr in ctx.present))
-        keep = []
-        p, chains, _ = block._chain_train_params(keep)
-        dev = g.device
-        need = ctx.needs_input_grad  # (block, g, R, flags, rec, ef, nf, gf, W, b, W, b, ...)
-        d_ef = torch.empty_like(ef) if ef is not None and need[5] else None
-        d_nf = torch.empty_like(nf) if nf is not None and need[6] else None
-        d_gf = torch.empty_like(gf) if gf is not None and need[7] else None
-        gW, gb, arrays, k = [], [], [], 8
-        for ch in chains:
-            entries = []  # one gnx_dense_grad per entry of the call's chain; a Dropout entry's slot is ignored
-            for kind, l in ch._entries():
-                if kind == "dropout":
-                    entries.append(_lib.DenseGrad(None, None))
-                    continue
-                ln = isinstance(l, LayerNorm)  # (its "weight" slot is gamma [d])
-                w = (torch.empty_like(l.gamma) if ln else torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev)) if need[k] else None
-                b = torch.empty_like(l.bias) if (l.bias is not None and need[k + 1]) else None
-                k += 2
-                gW.append(w); gb.append(b)
-                entries.append(_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None))
-            arrays.append((_lib.DenseGrad * max(len(entries), 1))(*entries))
-        grads = _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays])
-        narrow = int(bool(getattr(block, "narrow_chain_backward", False)))
-        with torch.cuda.device(dev):
-            nb = lib.gnx_chain_block_backward_train_workspace_bytes(g._h, C.byref(p), R, narrow)
-            if nb == 0:
-                raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-            ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-            drop = ctx.rec._c(keep)
-            check(lib.gnx_chain_block_backward_train(g._h, C.byref(p), C.byref(drop), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
-                                                     _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), narrow,
-                                                     torch.cuda.current_stream(dev).cuda_stream))
-        out = [None, None, None, None, None, d_ef, d_nf, d_gf]
-        for w, b in zip(gW, gb):
-            out += [None if w is None else (w if w.dim() == 1 else w.t()), b]
-        return tuple(out)
+        return _chain_block_pullback(ctx, gouts)
 
 
 def chain_dropout_mask(record, function, layer, shape, device=None):
@@ -1461,89 +1403,40 @@ def chain_dropout_mask(record, function, layer, shape, device=None):
     return _jl(out)
 
 
-def _chain_block_pullback(ctx, gouts, elem):
-    """backward of _ChainBlockFn (elem F32) and _ChainBlockBf16Fn (BF16: gnx_chain_block_backward_typed on bf16 feature-shaped tensors, or
-    gnx_chain_block_backward_narrow_typed with the block's `native_chain_backward` switch)"""
-    lib = _lib.load()
-    block, g, R = ctx.block, ctx.g, ctx.R
-    bf16 = elem == _lib.ELEM_BF16
-    sv = iter(ctx.saved_tensors)
-    ef, nf, gf = (next(sv) if present else None for present in ctx.slots)
-    it = iter(gouts)
-    ge, gn_, gg = (next(it) if pr else None for pr in ctx.present)
-    cont = lambda t: None if t is None else t.contiguous()
-    ge, gn_, gg = cont(ge), cont(gn_), cont(gg)
-    if bf16:  # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
-        ge, gn_, gg = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ge, gn_, gg))
-    keep = []
-    p, chains, _ = block._chain_params(keep)
-    dev = g.device
-    need = ctx.needs_input_grad  # (block, g, R, flags, ef, nf, gf, W, b, W, b, ...)
-    d_ef = torch.empty_like(ef) if ef is not None and need[4] else None
-    d_nf = torch.empty_like(nf) if nf is not None and need[5] else None
-    d_gf = torch.empty_like(gf) if gf is not None and need[6] else None
-    gW, gb, arrays, k = [], [], [], 7
+def _chain_grad_slots(chains, need, train, device):
+    """The parameter-gradient slots of a Chain block's pullback: (gW, gb, gnx_chain_block_grads, keepalive).  One gnx_dense_grad per entry of the
+    call's chains — with the Dropout entries of a training call (train), whose slots are ignored; `need`: which of the parameters (W, b, W, b, ...
+    in the layers' order) want a gradient.  gW / gb are what autograd gets: a Dense's weight gradient as the (out, in) view of (in, out) storage,
+    like the weights; a LayerNorm's gamma [d] in the weight's place."""
+    gW, gb, arrays, need = [], [], [], iter(need)
     for ch in chains:
-        entries = []
-        for l in ch.layers:
-            ln = isinstance(l, LayerNorm)  # (its "weight" slot is gamma [d])
-            w = (torch.empty_like(l.gamma) if ln else torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=dev)) if need[k] else None
-            b = torch.empty_like(l.bias) if (l.bias is not None and need[k + 1]) else None
-            k += 2
-            gW.append(w); gb.append(b)
-            entries.append(_lib.DenseGrad(_ptr(w) if (w is not None and w.numel()) else None, _ptr(b) if (b is not None and b.numel()) else None))
-        arrays.append((_lib.DenseGrad * max(len(entries), 1))(*entries))
-    grads = _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays])
-    with torch.cuda.device(dev):
-        narrow = bool(getattr(block, "narrow_chain_backward", False))
-        native = bf16 and bool(getattr(block, "native_chain_backward", False))
-        if native:
-            nb = lib.gnx_chain_block_backward_narrow_typed_workspace_bytes(g._h, C.byref(p), R, elem)
-        elif bf16:
-            nb = lib.gnx_chain_block_backward_typed_workspace_bytes(g._h, C.byref(p), R, elem, int(narrow))
-        else:
-            query, entry = ((lib.gnx_chain_block_backward_narrow_workspace_bytes, lib.gnx_chain_block_backward_narrow)
-                            if narrow else (lib.gnx_chain_block_backward_workspace_bytes, lib.gnx_chain_block_backward))
-            nb = query(g._h, C.byref(p), R)
-        if nb == 0:
-            raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-        if native:
-            check(lib.gnx_chain_block_backward_narrow_typed(g._h, C.byref(p), elem, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
-                                                            _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(),
-                                                            torch.cuda.current_stream(dev).cuda_stream))
-        elif bf16:
-            check(lib.gnx_chain_block_backward_typed(g._h, C.byref(p), elem, _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R, _ptr(d_ef),
-                                                     _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), int(narrow),
-                                                     torch.cuda.current_stream(dev).cuda_stream))
-        else:
-            check(entry(g._h, C.byref(p), _ptr(ef), _ptr(nf), _ptr(gf), _ptr(ge), _ptr(gn_), _ptr(gg), R,
-                        _ptr(d_ef), _ptr(d_nf), _ptr(d_gf), C.byref(grads), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    out = [None, None, None, None, d_ef, d_nf, d_gf]
-    for w, b in zip(gW, gb):
-        out += [None if w is None else (w if w.dim() == 1 else w.t()), b]  # (out, in) view with column-major storage, like the weights; a LayerNorm's gamma as it is
-    return tuple(out)
+        slots = []
+        for kind, l in ch._entries(train):
+            if kind == "dropout":
+                slots.append(_lib.DenseGrad(None, None))
+                continue
+            w = (torch.empty_like(l.gamma) if isinstance(l, LayerNorm) else
+                 torch.empty((l.weight.shape[1], l.weight.shape[0]), dtype=torch.float32, device=device)) if next(need) else None
+            b = torch.empty_like(l.bias) if (next(need) and l.bias is not None) else None
+            slots.append(_lib.DenseGrad(_ptr0(w), _ptr0(b)))
+            gW.append(w if w is None or w.dim() == 1 else w.t())
+            gb.append(b)
+        arrays.append((_lib.DenseGrad * max(len(slots), 1))(*slots))
+    return gW, gb, _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays]), arrays
 
 
-class _ChainBlockBf16Fn(torch.autograd.Function):
-    """_ChainBlockFn on bfloat16 features (GNBlock.bf16_chain with bf16_backward): forward = gnx_chain_block_forward_typed, backward =
-    gnx_chain_block_backward_typed mirroring the pullback `narrow_chain_backward` selects (gnx_chain_block_backward_narrow_typed with
-    `native_chain_backward`).  The saved inputs are bf16; the input gradients come
-    back in bf16 (rounded once from the fp32 pullback of the widened tensors), the parameter gradients in fp32 in _ChainBlockFn's layout."""
-
-    @staticmethod
-    def forward(ctx, block, g, R, flags, ef, nf, gf, *params):
-        ef, nf, gf = (a if a is None or a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-        eo, no, go = block._chain_forward(g, R, flags, ef, nf, gf, bf16=True)
-        ctx.block, ctx.g, ctx.R = block, g, R
-        ctx.slots = tuple(t is not None for t in (ef, nf, gf))
-        ctx.save_for_backward(*[t for t in (ef, nf, gf) if t is not None])
-        ctx.present = tuple(o is not None for o in (eo, no, go))
-        return tuple(o for o in (eo, no, go) if o is not None)
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        return _chain_block_pullback(ctx, gouts, _lib.ELEM_BF16)
+def _chain_block_pullback(ctx, gouts):
+    block, g, R, train = ctx.owner, ctx.g, ctx.R, ctx.rec is not None
+    (ef, nf, gf), cots = _recall(ctx, gouts)
+    keep = []
+    p, chains, _ = block._chain_params(keep, train)
+    need = ctx.needs_input_grad[len(_NO_GRAD):]  # (ef, nf, gf, W, b, W, b, ...)
+    d = [torch.empty_like(a) if a is not None and n else None for a, n in zip((ef, nf, gf), need)]
+    gW, gb, grads, slots = _chain_grad_slots(chains, need[3:], train, g.device)
+    drop = ctx.rec._c(keep) if train else None
+    _pullback(_entry("chain", "backward", ctx.elem, _switches(block), train), g, p, R,
+              (*map(_ptr, (ef, nf, gf)), *map(_ptr, cots), R, *map(_ptr, d), C.byref(grads)), {"drop": C.byref(drop) if train else None}, strict=True)
+    return (*_NO_GRAD, *d, *(t for wb in zip(gW, gb) for t in wb))
 
 
 class GNFeedForward:
@@ -1567,23 +1460,22 @@ class GNGraphNorm:
 class GNCore:
     """`GNCore(dims; dropout=0)` (gncore.jl:46-54): `core(x) = x + block(gn1(x)) + ffwd(gn2(x))` (gncore.jl:56-59)
     via gnx_core_forward.  `dropout = p`: the Dropout(p) ending each FeedForward (gnfeedforward.jl:27-31) is active inside a gradient call
-    (gnx_core_forward_train / gnx_core_backward_train, a fresh seed per call) and the identity otherwise — Flux's automatic mode;
+    (the training entries under a fresh seed per call, kept in `last_dropout`) and the identity otherwise — Flux's automatic mode;
     `testmode(core)` / `trainmode(core)` force it as `Flux.testmode!` / `trainmode!` do.
     `eps_mode` 0 = Flux 0.14 `normalise` (x-μ)/(σ+ε); 1 = (x-μ)/sqrt(σ²+ε).
-    `bf16` (also a plain attribute): lets a call on bfloat16 features (batch(..., dtype=torch.bfloat16)) run through gnx_core_forward_typed —
-    bf16 outputs, bit for bit the fp32 core on the widened inputs rounded once.  Off (the default) a bfloat16 tensor raises TypeError; float32
-    features never notice it.
-    `bf16_backward` (also a plain attribute, as GNBlock's): lets a differentiable call on bfloat16 features run — gnx_core_backward_typed is its
-    pullback, the three saved inputs stay bf16, input gradients come back in bf16 and parameter gradients in fp32.  Off (the default) such a
-    call raises NotImplementedError.  Dropout active on bfloat16 features (forced by `trainmode`, or p > 0 inside a gradient call) raises
-    NotImplementedError either way unless `typed_dropout` is on.
-    `typed_dropout` (also a plain attribute; off by default): a call with an active Dropout goes through gnx_core_forward_train_typed — on float32
-    features, and on bfloat16 ones where `bf16` / `bf16_backward` allow them — and its autograd node calls gnx_core_backward_train_typed with
-    narrow = `narrow_backward`.  Where all three widths are at most 16 (hidden activations identity / relu) the forward applies the mask inside
-    one FeedForward kernel per entity: a dropped element is x + block exactly.  The seed rule (`last_dropout`, `testmode` / `trainmode`) is unchanged.
-    `narrow_backward` (also a plain attribute, as GNBlock's): the pullback is gnx_core_backward_narrow, on float32 features (with the call's
-    Dropout value when one is active) and — with `bf16_backward` — on bfloat16 ones: the pullback of each FeedForward in one kernel where all
-    three widths are at most 16 and the hidden activations identity / relu, exactly the other pullbacks everywhere else.  Off by default."""
+    Which C entry a call reaches under the switches below (each also a plain attribute, off by default) is the table of `_entry`; what each promises:
+    `bf16` (gnx_core_forward_typed): lets a call on bfloat16 features (batch(..., dtype=torch.bfloat16)) run — bf16 outputs, bit for bit the fp32
+    core on the widened inputs rounded once.  Off, a bfloat16 tensor raises TypeError; float32 features never notice it.
+    `bf16_backward` (gnx_core_backward_typed; as GNBlock's): lets a differentiable call on bfloat16 features run — the three saved inputs stay
+    bf16, input gradients come back in bf16 and parameter gradients in fp32.  Off, such a call raises NotImplementedError.  Dropout active on
+    bfloat16 features (forced by `trainmode`, or p > 0 inside a gradient call) raises NotImplementedError either way unless `typed_dropout` is on.
+    `typed_dropout` (gnx_core_forward_train_typed, gnx_core_backward_train_typed): a call with an active Dropout goes through the typed training
+    entries — on float32 features, and on bfloat16 ones where `bf16` / `bf16_backward` allow them (narrow = `narrow_backward` in the pullback).
+    Where all three widths are at most 16 (hidden activations identity / relu) the forward applies the mask inside one FeedForward kernel per
+    entity: a dropped element is x + block exactly.  The seed rule (`last_dropout`, `testmode` / `trainmode`) is unchanged.
+    `narrow_backward` (gnx_core_backward_narrow; as GNBlock's): on float32 features (with the call's Dropout value when one is active) and — with
+    `bf16_backward` — on bfloat16 ones, the pullback of each FeedForward runs in one kernel where all three widths are at most 16 and the hidden
+    activations identity / relu; exactly the other pullbacks everywhere else."""
 
     def __init__(self, dims, dropout=0, device=None, generator=None, eps=1e-5, eps_mode=0, bf16=False, bf16_backward=False, narrow_backward=False,
                  typed_dropout=False):
@@ -1662,110 +1554,44 @@ class GNCore:
         return self.last_dropout
 
     def __call__(self, x, flags=None):
-        # gnfeedforward.jl:27-31: the FeedForward ends in Dropout(p), which Flux applies in training mode (inside a gradient call)
-        # and skips in test mode: gnx_core_forward_train / gnx_core_backward_train with a per-call seed, gnx_core_forward otherwise.
         x = _as_nt(x)
         assert x.ef is not None and x.nf is not None and x.gf is not None, "GNCore needs ef, nf and gf (gncore.jl:61-68)"
         if getattr(self, "bf16", False) and _feature_dtype(x.ef, x.nf, x.gf, "GNCore") == torch.bfloat16:  # (mixed bf16 / other: TypeError)
             return self._call_bf16(x, flags)
         g, ef, nf, gf, R = _forward_common(x, self.dims)
-        plist = self._param_list()
-        grad_call = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [ef, nf, gf] + plist)
-        drop = self._dropout_now(grad_call)
-        if grad_call:
-            eo, no, go = _CoreFn.apply(self, g, R, self.flags if flags is None else flags, drop, ef, nf, gf, *plist)
-            return NT(g, _jl(eo), _jl(no), _jl(go))
-        eo, no, go = _core_forward(self, g, R, self.flags if flags is None else flags, drop, ef, nf, gf)
-        return NT(g, _jl(eo), _jl(no), _jl(go))
-
+        grad_call = self._training((ef, nf, gf))
+        return self._run(g, R, flags, _lib.ELEM_F32, self._dropout_now(grad_call), ef, nf, gf, grad_call)
 
     def _call_bf16(self, x, flags):
-        """bfloat16 features with the `bf16` switch on: gnx_core_forward_typed, bf16 outputs; a differentiable call needs `bf16_backward`
-        (gnx_core_backward_typed is then the pullback).  Everything else is refused before any library call."""
-        grad_call = self._training((x.ef, x.nf, x.gf))
-        if grad_call and not getattr(self, "bf16_backward", False):
-            raise NotImplementedError("GNCore: the backward of a bfloat16 core is off; construct the core with bf16_backward=True (or set "
-                                      "core.bf16_backward = True) to differentiate through gnx_core_backward_typed, call it under torch.no_grad() "
-                                      "with parameters that need no gradient, or use float32 features")
-        forced = getattr(self, "_dropout_mode", None)
-        if getattr(self, "typed_dropout", False):
-            drop = self._dropout_now(grad_call)
-            if drop is not None:  # gnx_core_forward_train_typed / gnx_core_backward_train_typed on bf16 features
-                g, ef, nf, gf, R = _forward_common(x, self.dims, None)
-                flags = self.flags if flags is None else flags
-                if grad_call:
-                    eo, no, go = _CoreBf16TrainFn.apply(self, g, R, flags, drop, ef, nf, gf, *self._param_list())
-                else:
-                    ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-                    eo, no, go = _core_forward_train_typed(self, g, R, flags, drop, ef, nf, gf, _lib.ELEM_BF16)
-                return NT(g, _jl(eo), _jl(no), _jl(go))
-        elif float(self.ffwd.dropout or 0) > 0 and (grad_call if forced is None else forced):
-            raise NotImplementedError("GNCore: Dropout in training mode on bfloat16 features (a typed gnx_core_forward_train / "
-                                      "gnx_core_backward_train) is not implemented; use testmode(core), dropout=0 or float32 features")
+        """bfloat16 features with the `bf16` switch on: bf16 outputs; a differentiable call needs `bf16_backward`, an active Dropout
+        `typed_dropout`.  Everything else is refused before any library call."""
+        grad_call, sw, drop = self._training((x.ef, x.nf, x.gf)), _switches(self), None
         if grad_call:
-            g, ef, nf, gf, R = _forward_common(x, self.dims, None)
-            eo, no, go = _CoreBf16Fn.apply(self, g, R, self.flags if flags is None else flags, ef, nf, gf, *self._param_list())
-            return NT(g, _jl(eo), _jl(no), _jl(go))
-        eo, no, go, g = self._forward_bf16(x, flags)
+            _entry("core", "backward", _lib.ELEM_BF16, sw)  # refused without bf16_backward
+        forced = getattr(self, "_dropout_mode", None)
+        if "typed_dropout" in sw:
+            drop = self._dropout_now(grad_call)
+        elif float(self.ffwd.dropout or 0) > 0 and (grad_call if forced is None else forced):
+            _entry("core", "forward", _lib.ELEM_BF16, sw, record=True)  # refused: the plain training entries are float32
+        g, ef, nf, gf, R = _forward_common(x, self.dims, None)
+        return self._run(g, R, flags, _lib.ELEM_BF16, drop, ef, nf, gf, grad_call)
+
+    def _run(self, g, R, flags, elem, drop, ef, nf, gf, grad_call):
+        flags = self.flags if flags is None else flags
+        if grad_call:
+            eo, no, go = _CoreFn.apply(self, g, R, flags, elem, drop, ef, nf, gf, *self._param_list())
+        else:
+            eo, no, go = _core_forward(self, g, R, flags, elem, drop, *map(_aligned, (ef, nf, gf)))
         return NT(g, _jl(eo), _jl(no), _jl(go))
 
-    def _forward_bf16(self, x, flags):
-        """gnx_core_forward_typed on the features of x (or on packed tensors with their handle: x = (g, ef, nf, gf, R))."""
-        g, ef, nf, gf, R = x if isinstance(x, tuple) and len(x) == 5 else _forward_common(x, self.dims, None)
-        # the typed entry needs 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
-        ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-        lib = _lib.load()
-        keep = []
-        p = self._c(keep)
-        dev = g.device
-        flags = self.flags if flags is None else flags
-        eo, no, go = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
-        with torch.cuda.device(dev):
-            nbytes = lib.gnx_core_typed_workspace_bytes(g._h, C.byref(p), R, _lib.ELEM_BF16, flags)
-            ws = g.workspace(nbytes, ("core_bf16", self.dims, R, flags))
-            check(lib.gnx_core_forward_typed(g._h, C.byref(p), _lib.ELEM_BF16, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(), no.data_ptr(),
-                                             go.data_ptr(), ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
-        return eo, no, go, g
 
-
-def _core_forward(core, g, R, flags, drop, ef, nf, gf):
-    """gnx_core_forward, or gnx_core_forward_train when a Dropout is active for the call."""
-    lib = _lib.load()
+def _core_forward(core, g, R, flags, elem, drop, ef, nf, gf):
+    """the forward of a GNCore on packed (bf16: aligned) tensors; drop: the call's gnx_dropout (gnfeedforward.jl:27-31: applied in training mode) or None"""
     keep = []
     p = core._c(keep)
-    dev = g.device
-    eo, no, go = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if drop is None:
-            ws = g.workspace(lib.gnx_core_workspace_bytes(g._h, C.byref(p), R), ("core", core.dims, R))
-            check(lib.gnx_core_forward(g._h, C.byref(p), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(), no.data_ptr(),
-                                       go.data_ptr(), ws.data_ptr(), ws.numel(), flags, stream))
-        elif getattr(core, "typed_dropout", False):
-            return _core_forward_train_typed(core, g, R, flags, drop, ef, nf, gf, _lib.ELEM_F32)
-        else:
-            nb = lib.gnx_core_train_workspace_bytes(g._h, C.byref(p), R)
-            if nb == 0:
-                raise GnxError(_lib.ERR_DIMS, lib.gnx_last_error().decode("utf-8", "replace"))
-            ws = g.workspace(nb, ("core_train", core.dims, R))
-            check(lib.gnx_core_forward_train(g._h, C.byref(p), C.byref(drop), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(),
-                                             no.data_ptr(), go.data_ptr(), ws.data_ptr(), ws.numel(), flags, stream))
-    return eo, no, go
-
-
-def _core_forward_train_typed(core, g, R, flags, drop, ef, nf, gf, elem):
-    """gnx_core_forward_train_typed (GNCore.typed_dropout, an active Dropout) on packed fp32 or 4-byte aligned bf16 tensors."""
-    lib = _lib.load()
-    keep = []
-    p = core._c(keep)
-    dev = g.device
-    eo, no, go = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
-    with torch.cuda.device(dev):
-        nb = lib.gnx_core_train_typed_workspace_bytes(g._h, C.byref(p), R, elem, flags)
-        ws = g.workspace(max(int(nb), 256), ("core_train_typed", core.dims, R, elem, flags))
-        check(lib.gnx_core_forward_train_typed(g._h, C.byref(p), elem, C.byref(drop), ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), R, eo.data_ptr(),
-                                               no.data_ptr(), go.data_ptr(), ws.data_ptr(), ws.numel(), flags, torch.cuda.current_stream(dev).cuda_stream))
-    return eo, no, go
+    e = _entry("core", "forward", elem, _switches(core), drop is not None)
+    env = dict(flags=flags, R=R, dims=core.dims, drop=None if drop is None else C.byref(drop))
+    return _forward(e, g, p, R, core.dims, elem, (ef, nf, gf), env, strict=e.key[0] == "core_train")  # (the one core query whose 0 is reported here)
 
 
 def dropout_mask(drop, entity, shape, device=None):
@@ -1796,22 +1622,6 @@ def trainmode(m, mode=True):
     return testmode(m, None if mode is None else (not mode))
 
 
-class _CoreFn(torch.autograd.Function):
-    """torch autograd node of one GNCore call: forward = gnx_core_forward, backward = gnx_core_backward (gnx_core_backward_narrow with
-    GNCore.narrow_backward)."""
-
-    @staticmethod
-    def forward(ctx, core, g, R, flags, drop, ef, nf, gf, *params):
-        eo, no, go = _core_forward(core, g, R, flags, drop, ef, nf, gf)
-        ctx.core, ctx.g, ctx.R, ctx.drop = core, g, R, drop
-        ctx.save_for_backward(ef, nf, gf)
-        return eo, no, go
-
-    @staticmethod
-    def backward(ctx, ge, gn_, gg):
-        return (None,) * 5 + _core_pullback(ctx, (ge, gn_, gg), _lib.ELEM_F32, ctx.drop)
-
-
 def _core_grads(core, out):
     """gnx_core_grads over `out`, one fp32 tensor per entry of core._param_list() in its order (weights as (out, in) views of (in, out)-contiguous
     storage, like the parameters)."""
@@ -1829,75 +1639,32 @@ def _core_grads(core, out):
     return gr
 
 
-class _CoreBf16Fn(torch.autograd.Function):
-    """_CoreFn on bfloat16 features (GNCore.bf16 with GNCore.bf16_backward, test mode): forward = gnx_core_forward_typed, backward =
-    gnx_core_backward_typed.  The three saved inputs are bf16 — the backward recomputes every intermediate from them in fp32; the input
-    gradients come back in bf16 (rounded once from the fp32 pullback), the parameter gradients in fp32 in _CoreFn's layout."""
+class _CoreFn(torch.autograd.Function):
+    """torch autograd node of one GNCore call, on float32 or bfloat16 features; drop: the call's gnx_dropout (the pullback regenerates the forward's
+    masks from its seed) or None.  The three inputs are saved — the backward recomputes every intermediate from them in fp32; on bfloat16
+    features they are bf16 and the input gradients come back in bf16 (rounded once from the fp32 pullback), the parameter gradients in fp32."""
 
     @staticmethod
-    def forward(ctx, core, g, R, flags, ef, nf, gf, *params):
-        # the typed entries need 4-byte aligned bf16 buffers (a view may start at an odd element: copy it)
-        ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-        eo, no, go, _ = core._forward_bf16((g, ef, nf, gf, R), flags)
-        ctx.core, ctx.g, ctx.R = core, g, R
-        ctx.save_for_backward(ef, nf, gf)
-        return eo, no, go
+    def forward(ctx, core, g, R, flags, elem, drop, ef, nf, gf, *params):
+        ef, nf, gf = map(_aligned, (ef, nf, gf))
+        return _remember(ctx, core, g, R, elem, drop, (ef, nf, gf), _core_forward(core, g, R, flags, elem, drop, ef, nf, gf))
 
     @staticmethod
-    def backward(ctx, ge, gn_, gg):
-        return (None,) * 4 + _core_pullback(ctx, (ge, gn_, gg), _lib.ELEM_BF16, None)
+    def backward(ctx, *gouts):
+        return _core_pullback(ctx, gouts)
 
 
-class _CoreBf16TrainFn(torch.autograd.Function):
-    """_CoreBf16Fn with an active Dropout (GNCore.typed_dropout): forward = gnx_core_forward_train_typed, backward =
-    gnx_core_backward_train_typed under the same gnx_dropout value."""
-
-    @staticmethod
-    def forward(ctx, core, g, R, flags, drop, ef, nf, gf, *params):
-        ef, nf, gf = (a if a.data_ptr() % 4 == 0 else a.clone() for a in (ef, nf, gf))
-        eo, no, go = _core_forward_train_typed(core, g, R, flags, drop, ef, nf, gf, _lib.ELEM_BF16)
-        ctx.core, ctx.g, ctx.R, ctx.drop = core, g, R, drop
-        ctx.save_for_backward(ef, nf, gf)
-        return eo, no, go
-
-    @staticmethod
-    def backward(ctx, ge, gn_, gg):
-        return (None,) * 5 + _core_pullback(ctx, (ge, gn_, gg), _lib.ELEM_BF16, ctx.drop)
-
-
-def _core_pullback(ctx, cots, elem, drop):
-    """backward of _CoreFn (elem = ELEM_F32; drop: the forward's gnx_dropout or None), _CoreBf16Fn (ELEM_BF16, no Dropout) and _CoreBf16TrainFn
-    (ELEM_BF16 with the forward's gnx_dropout): (d_ef, d_nf, d_gf, *parameter gradients).  The C entry: gnx_core_backward_train_typed for an active
-    Dropout with GNCore.typed_dropout (narrow = GNCore.narrow_backward); else gnx_core_backward_narrow with GNCore.narrow_backward (the FeedForward pullbacks in one kernel each where
-    the core is narrow); otherwise gnx_core_backward_typed in bf16, gnx_core_backward in fp32 — gnx_core_backward_train with a Dropout (the
-    forward's masks, regenerated from the call's seed)."""
-    lib = _lib.load()
-    core, g, R = ctx.core, ctx.g, ctx.R
-    ef, nf, gf = ctx.saved_tensors
-    dev = g.device
-    ge, gn_, gg = (_cotangent(t, elem) for t in cots)
+def _core_pullback(ctx, gouts):
+    core, g, R, drop = ctx.owner, ctx.g, ctx.R, ctx.rec
+    (ef, nf, gf), cots = _recall(ctx, gouts)
     keep = []
     p = core._c(keep)
-    out = [torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=dev).t() if q.dim() == 2 else torch.empty_like(q) for q in core._param_list()]
+    out = [torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=g.device).t() if q.dim() == 2 else torch.empty_like(q) for q in core._param_list()]
     gr = _core_grads(core, out)
-    d_ef, d_nf, d_gf = torch.empty_like(ef), torch.empty_like(nf), torch.empty_like(gf)
-    dr = None if drop is None else C.byref(drop)
-    with torch.cuda.device(dev):
-        if drop is not None and getattr(core, "typed_dropout", False):
-            narrow = 1 if getattr(core, "narrow_backward", False) else 0
-            nb = lib.gnx_core_backward_train_typed_workspace_bytes(g._h, C.byref(p), R, elem, narrow)
-            call, head = lib.gnx_core_backward_train_typed, (elem, dr, narrow)
-        elif getattr(core, "narrow_backward", False):
-            nb, call, head = lib.gnx_core_backward_narrow_workspace_bytes(g._h, C.byref(p), R, elem), lib.gnx_core_backward_narrow, (elem, dr)
-        elif elem == _lib.ELEM_BF16:
-            nb, call, head = lib.gnx_core_backward_typed_workspace_bytes(g._h, C.byref(p), R, elem), lib.gnx_core_backward_typed, (elem,)
-        else:
-            nb = lib.gnx_core_backward_workspace_bytes(g._h, C.byref(p), R)
-            call, head = (lib.gnx_core_backward, ()) if drop is None else (lib.gnx_core_backward_train, (dr,))
-        ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=dev)
-        check(call(g._h, C.byref(p), *head, ef.data_ptr(), nf.data_ptr(), gf.data_ptr(), _ptr(ge), _ptr(gn_), _ptr(gg), R, d_ef.data_ptr(), d_nf.data_ptr(),
-                   d_gf.data_ptr(), C.byref(gr), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    return (d_ef, d_nf, d_gf, *out)
+    d = [torch.empty_like(a) for a in (ef, nf, gf)]
+    _pullback(_entry("core", "backward", ctx.elem, _switches(core), drop is not None), g, p, R,
+              (*map(_ptr, (ef, nf, gf)), *map(_ptr, cots), R, *map(_ptr, d), C.byref(gr)), {"drop": None if drop is None else C.byref(drop)})
+    return (*_NO_GRAD, *d, *out)
 
 
 class GNCoreList:
