@@ -12,7 +12,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 NAME = "gnx_block_forward_steps_typed"
 
 
@@ -149,30 +148,13 @@ def test_bf16_step_spans_compiled_with_gxx(tmp_path):
     assert "bf16 spans ok" in r.stdout
 
 
-def _resources(stderr):
-    """kernel -> {sgpr, vgpr, scratch} from -Rpass-analysis=kernel-resource-usage remarks"""
-    out = {}
-    for blk in re.split(r"remark: Function Name: ", stderr)[1:]:
-        name = blk.split()[0]
-        g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
-        out[name] = dict(sgpr=g("TotalSGPRs"), vgpr=g("VGPRs"), scratch=g(r"ScratchSize \[bytes/lane\]"))
-    return out
-
-
 def test_chained_bf16_kernels_resource_audit():
     """k_block_wave<..., CHAIN, BF16> of every bf16 ahead-of-time width set (one graph and several graphs), compiled as build.py compiles
     gnx_narrow_bf16.hip: no scratch, at most the kernel's 80 scalar registers, no more vector registers than the fp32 chained kernel"""
+    from tools.kernel_resources import HIPCC, remarks_many
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    base = [HIPCC, "-x", "hip", "-c", "--cuda-device-only", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-            "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull]
-    procs = {k: subprocess.Popen(base + extra + [os.path.join(CSRC, f)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-             for k, f, extra in (("bf16", "gnx_narrow_bf16.hip", ["-fno-slp-vectorize"]), ("f32", "gnx_narrow.hip", []))}
-    res = {}
-    for k, p in procs.items():
-        _, err = p.communicate(timeout=1200)
-        assert p.returncode == 0, err[-3000:]
-        res[k] = _resources(err)
+    res = dict(zip(("bf16", "f32"), remarks_many(["gnx_narrow_bf16.hip", "gnx_narrow.hip"])))  # (both compiles at once, as build.py compiles the files)
     chained = {n: v for n, v in res["bf16"].items() if re.match(r"_ZN3gnx12k_block_waveI(Li\d+E){6}(Lb[01]E){4}Lb1ELb1EEEv", n)}
     # two per width set of GNX_NARROW_DIMS_BF16 (one graph, several graphs); (10,5,0) => (3,4,5) and (3,4,5) => (3,4,5) at least
     assert len(chained) >= 4 and any("ILi3ELi4ELi5ELi3ELi4E" in n for n in chained), sorted(chained)

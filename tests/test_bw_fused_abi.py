@@ -4,14 +4,11 @@ instantiations of k_bw_edge_wave compile for gfx950 without scratch memory (read
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 NEW = ("gnx_block_backward_fused_applies", "gnx_block_backward_fused_workspace_bytes", "gnx_block_backward_fused")
 SETS = ((10, 5, 0, 3), (3, 4, 5, 3), (0, 2, 0, 2), (2, 2, 2, 2), (4, 3, 2, 3))  # (de, dn, dg, oe)
 
@@ -71,28 +68,16 @@ def test_gnblock_has_the_switch():
     assert gn.GNCore((10, 5, 3), device="cpu").block.fused_backward is False  # (GNCore's inner block is not touched)
 
 
-def resources(hipcc=HIPCC):
-    """{(de, dn, dg, oe): {sgpr, vgpr, scratch, lds, occupancy}} of the k_bw_edge_wave instantiations, from -Rpass-analysis=kernel-resource-usage
-    on gnx_backward_narrow.hip compiled as build.py compiles it (also what tools/time_bw_fused.py records)"""
-    cmd = [hipcc, "-x", "hip", "-c", "--cuda-device-only", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-           "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, os.path.join(CSRC, "gnx_backward_narrow.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = {}
-    for blk in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN3gnx14k_bw_edge_waveILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEEv", blk.split()[0])
-        if not m:
-            continue
-        g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
-        out[tuple(int(v) for v in m.groups())] = dict(sgpr=g("TotalSGPRs"), vgpr=g("VGPRs"), scratch=g(r"ScratchSize \[bytes/lane\]"),
-                                                      lds=g(r"LDS Size \[bytes/block\]"), occupancy=g(r"Occupancy \[waves/SIMD\]"))
-    return out
-
-
 def test_the_five_instantiations_compile_without_scratch():
+    from tools.kernel_resources import HIPCC, remarks
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    res = resources()
+    # {(de, dn, dg, oe): {sgpr, vgpr, scratch, lds, occupancy}} of the k_bw_edge_wave instantiations of gnx_backward_narrow.hip
+    res = {}
+    for name, r in remarks("gnx_backward_narrow.hip").items():
+        m = re.match(r"_ZN3gnx14k_bw_edge_waveILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEEv", name)
+        if m:
+            res[tuple(int(v) for v in m.groups())] = dict(sgpr=r["sgpr"], vgpr=r["vgpr"], scratch=r["scratch"], lds=r["lds"], occupancy=r["waves_per_simd"])
     assert set(res) == set(SETS), sorted(res)
     for dims, r in res.items():
         assert r["scratch"] == 0, (dims, r)

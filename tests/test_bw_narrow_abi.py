@@ -120,12 +120,12 @@ def test_the_kernel_compiles_at_run_time_for_eligible_width_sets_only(lib, monke
 
 
 def test_no_scratch_and_the_lds_of_the_eligibility_rule():
-    from tools.bw_narrow_resources import HIPCC, eligible, resources, static_lds
+    from tools.kernel_resources import HIPCC, eligible, resources, static_lds
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
     sets = RUN_TIME + AOT
     assert all(eligible(*s) for s in sets) and not any(eligible(*s) for s in REFUSED)
-    res = resources(sets)
+    res = resources("bw_narrow", sets)
     assert set(res) == {str(s) for s in sets}, sorted(res)
     for s in sets:
         r = res[str(s)]

@@ -180,7 +180,8 @@ def test_gnblock_has_the_switch_and_off_still_raises(monkeypatch):
 
 
 def test_every_instantiation_compiles_without_scratch():
-    from tools.chain_narrow_bf16_resources import HIPCC, LDS_BUDGET_BYTES, SRC, WMAX, resources
+    from tools.kernel_resources import FAMILIES, HIPCC, resources
+    LDS_BUDGET_BYTES, SRC, WMAX = (FAMILIES["chain_narrow_bf16"][k] for k in ("LDS_BUDGET_BYTES", "SRC", "WMAX"))
     with open(os.path.join(ROOT, "profiles", "chain_narrow_bf16_resources.json")) as f:
         rec = json.load(f)
     assert sorted(rec["srcs"]) == sorted(SRC) == ["edge", "node", "rows"] and rec["lds_budget_bytes"] == LDS_BUDGET_BYTES == 40960
@@ -189,7 +190,7 @@ def test_every_instantiation_compiles_without_scratch():
         assert all(v["scratch"] == 0 and v["lds_static"] == 0 for v in rec["srcs"][s].values()), rec["srcs"][s]
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    res = resources()
+    res = resources("chain_narrow_bf16")
     assert sum(len(res[s]) for s in SRC) == 9
     for s in SRC:
         assert sorted(res[s]) == list(WMAX), (s, sorted(res[s]))

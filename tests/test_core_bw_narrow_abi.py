@@ -107,10 +107,11 @@ def test_bad_elem_and_bad_dropout_are_refused_before_gpu_work(lib):
 
 
 def test_every_instantiation_compiles_without_scratch():
-    from tools.core_bw_narrow_resources import HIPCC, WIDTHS, resources
+    from tools.kernel_resources import FAMILIES, HIPCC, resources
+    WIDTHS = FAMILIES["core_bw_narrow"]["WIDTHS"]
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    res = resources()
+    res = resources("core_bw_narrow")
     assert sorted(res) == list(WIDTHS) == list(range(1, 17)), sorted(res)
     for d in WIDTHS:
         assert res[d]["scratch"] == 0, (d, res[d])

@@ -142,10 +142,11 @@ def test_gncore_has_the_switch_and_off_still_raises():
 
 
 def test_every_instantiation_compiles_without_scratch():
-    from tools.core_train_narrow_resources import ELEMS, HIPCC, WIDTHS, resources
+    from tools.kernel_resources import FAMILIES, HIPCC, resources
+    ELEMS, WIDTHS = (FAMILIES["core_train_narrow"][k] for k in ("ELEMS", "WIDTHS"))
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    res = resources()
+    res = resources("core_train_narrow")
     assert sorted(res) == sorted(ELEMS) == ["bf16", "f32"]
     for e in ELEMS:
         assert sorted(res[e]) == list(WIDTHS) == list(range(1, 17)), (e, sorted(res[e]))

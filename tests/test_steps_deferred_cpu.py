@@ -13,7 +13,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SCHEDULE = r"""
 #include "steps_plan_sim.h"
@@ -134,16 +133,6 @@ def test_carrying_runs_order_every_conflicting_pair(tmp_path):
     assert "deferred ok" in out.stdout
 
 
-def _resources(stderr):
-    """kernel -> {sgpr, vgpr, scratch} from -Rpass-analysis=kernel-resource-usage remarks"""
-    out = {}
-    for blk in re.split(r"remark: Function Name: ", stderr)[1:]:
-        name = blk.split()[0]
-        g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
-        out[name] = dict(sgpr=g("TotalSGPRs"), vgpr=g("VGPRs"), scratch=g(r"ScratchSize \[bytes/lane\]"))
-    return out
-
-
 def _key(de, dn, dg, oe, on):
     return "".join(f"Li{v}E" for v in (de, dn, dg, oe, on, 2))
 
@@ -156,13 +145,10 @@ def test_carrying_kernels_resource_audit():
     """Every k_block_wave_carry instantiation, compiled as build.py compiles gnx_narrow.hip: no scratch, at most 80 scalar registers (the
     eighth workgroup per CU), no more vector registers than the chained kernel of the same set and form; exactly the listed instantiations,
     fp32 rows only."""
+    from tools.kernel_resources import HIPCC, remarks
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    cmd = [HIPCC, "-x", "hip", "-c", "--cuda-device-only", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-           "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, os.path.join(CSRC, "gnx_narrow.hip")]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-    assert p.returncode == 0, p.stderr[-3000:]
-    res = _resources(p.stderr)
+    res = remarks("gnx_narrow.hip")
     pat = re.compile(r"_ZN3gnx18k_block_wave_carryI((?:Li\d+E){6})Lb([01])EEEv")
     carry = {n: v for n, v in res.items() if "k_block_wave_carry" in n}
     assert all(pat.match(n) for n in carry), sorted(carry)

@@ -11,7 +11,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SCHEDULE = r"""
 #include "steps_plan_sim.h"
@@ -116,16 +115,6 @@ def test_runs_grouping_and_schedule_order_every_conflicting_pair(tmp_path):
     assert "runs ok" in out.stdout
 
 
-def _resources(stderr):
-    """kernel -> {sgpr, vgpr, scratch} from -Rpass-analysis=kernel-resource-usage remarks"""
-    out = {}
-    for blk in re.split(r"remark: Function Name: ", stderr)[1:]:
-        name = blk.split()[0]
-        g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
-        out[name] = dict(sgpr=g("TotalSGPRs"), vgpr=g("VGPRs"), scratch=g(r"ScratchSize \[bytes/lane\]"))
-    return out
-
-
 # the width sets with a run kernel (gnx_narrow.hip: GNX_NARROW_RUN_DIMS; gnx_narrow_bf16.hip: GNX_NARROW_RUN_DIMS_BF16), as the mangled names spell them
 def _key(de, dn, dg, oe, on):
     return "".join(f"Li{v}E" for v in (de, dn, dg, oe, on, 2))
@@ -141,17 +130,10 @@ def test_run_kernels_resource_audit():
     scratch, at most 80 scalar registers (the eighth workgroup per CU), no more vector registers than the chained kernel of the same set.
     The instantiations are exactly the listed ones; the fp32 sets that chain but have no run kernel are the ones whose kernels are beyond the
     80 scalar registers in every form."""
+    from tools.kernel_resources import HIPCC, remarks_many
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    base = [HIPCC, "-x", "hip", "-c", "--cuda-device-only", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-            "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull]
-    procs = {k: subprocess.Popen(base + extra + [os.path.join(CSRC, f)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-             for k, f, extra in (("bf16", "gnx_narrow_bf16.hip", ["-fno-slp-vectorize"]), ("f32", "gnx_narrow.hip", []))}
-    res = {}
-    for k, p in procs.items():
-        _, err = p.communicate(timeout=1200)
-        assert p.returncode == 0, err[-3000:]
-        res[k] = _resources(err)
+    res = dict(zip(("bf16", "f32"), remarks_many(["gnx_narrow_bf16.hip", "gnx_narrow.hip"])))  # (both compiles at once, as build.py compiles the files)
     pat = re.compile(r"_ZN3gnx16k_block_wave_runI((?:Li\d+E){6})Lb([01])ELb([01])EEEv")
 
     def chained(key, dims, oneg, bf16):  # k_block_wave<dims, LN = 0, ONEG, PACK = 0, FFE = 0, CHAIN = 1, BF16>

@@ -28,30 +28,21 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 DIMS = (10, 5, 3)
-CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
 
 
 def kernel_resources():
-    """{file: {kernel: {vgpr, sgpr, scratch, waves_per_simd, lds}}} of the core's kernels at (10,5,3), from -Rpass-analysis=kernel-resource-usage"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    base = [hipcc, "-x", "hip", "-c", "--cuda-device-only", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-            "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull]
-    files = (("gnx_narrow_bf16.hip", ["-fno-slp-vectorize"]), ("gnx_narrow.hip", []), ("gnx_core_narrow.hip", []))
-    procs = [(f, subprocess.Popen(base + extra + [os.path.join(CSRC, f)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)) for f, extra in files]
+    """{file: {kernel: {vgpr, sgpr, scratch, waves_per_simd, lds}}} of the core's kernels at (10,5,3), from tools/kernel_resources.py's remarks"""
+    from tools.kernel_resources import remarks_many
+    files = ("gnx_narrow_bf16.hip", "gnx_narrow.hip", "gnx_core_narrow.hip")
     want = re.compile(r"k_block_wave(_ffe)?ILi10ELi5ELi3ELi10ELi5ELi2ELb1|k_core_post3ILi10ELi5ELi3E|k_graph_tILi15E")  # (LN = 1: the core's block)
     out = {}
-    for f, p in procs:
-        _, err = p.communicate(timeout=1800)
-        assert p.returncode == 0, err[-3000:]
-        for blk in re.split(r"remark: Function Name: ", err)[1:]:
-            name = blk.split()[0]
+    for f, res in zip(files, remarks_many(files)):
+        for name, r in res.items():
             if not want.search(name):
                 continue
-            g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
             demangled = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip() or name
             out.setdefault(f, {})[re.sub(r"\(.*$", "", demangled).replace("void gnx::", "")] = dict(
-                vgpr=g("VGPRs"), sgpr=g("TotalSGPRs"), scratch_bytes_per_lane=g(r"ScratchSize \[bytes/lane\]"), waves_per_simd=g(r"Occupancy \[waves/SIMD\]"),
-                lds_bytes=g(r"LDS Size \[bytes/block\]"))
+                vgpr=r["vgpr"], sgpr=r["sgpr"], scratch_bytes_per_lane=r["scratch"], waves_per_simd=r["waves_per_simd"], lds_bytes=r["lds"])
     return out
 
 

@@ -32,29 +32,19 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 WIDTHS = ((10, 5, 3), (128, 64, 32))
-CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
 
 
 def kernel_resources():
     """{kernel<...>: {vgpr, sgpr, scratch, lds, waves_per_simd}} of k_layernorm2, k_layernorm2_v4, k_ln_backward, k_ln_backward_v4"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    base = [hipcc, "-x", "hip", "-c", "--cuda-device-only", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-            "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull]
-    procs = [subprocess.Popen(base + [os.path.join(CSRC, f)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-             for f in ("gnx_generic.hip", "gnx_backward.hip")]
+    from tools.kernel_resources import remarks_many
     out = {}
-    for p in procs:
-        _, err = p.communicate(timeout=1800)
-        assert p.returncode == 0, err[-3000:]
-        for blk in re.split(r"remark: Function Name: ", err)[1:]:
-            name = blk.split()[0]
+    for res in remarks_many(("gnx_generic.hip", "gnx_backward.hip")):
+        for name, r in res.items():
             if not re.search(r"k_layernorm2|k_ln_backward", name):
                 continue
-            g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
             demangled = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip() or name
             out[re.sub(r"\(.*$", "", demangled).replace("void gnx::", "").replace("gnx::", "")] = dict(
-                vgpr=g("VGPRs"), sgpr=g("TotalSGPRs"), scratch_bytes_per_lane=g(r"ScratchSize \[bytes/lane\]"), lds_bytes=g(r"LDS Size \[bytes/block\]"),
-                waves_per_simd=g(r"Occupancy \[waves/SIMD\]"))
+                vgpr=r["vgpr"], sgpr=r["sgpr"], scratch_bytes_per_lane=r["scratch"], lds_bytes=r["lds"], waves_per_simd=r["waves_per_simd"])
     assert out and all(v["scratch_bytes_per_lane"] == 0 for v in out.values()), "an instantiation uses scratch"
     return dict(sorted(out.items()))
 

@@ -9,7 +9,7 @@ The two forms alternate window by window in one process; each window is timed wi
 warm-up; the medians and every window are recorded, and whether the fused call is faster by more than the spread (max - min over the windows) of
 the generic call.  Per case: the per-kernel profiler breakdown of both forms (gnx_profile_*, one profiled call each after the timing), the two
 workspace sizes, and a check that the fused input gradients and node / graph parameter gradients are the generic call's bits.  The compiler's
-resource remarks of the five instantiations (registers, LDS, scratch) are read when hipcc is present, as tests/test_bw_fused_abi.py reads them.
+resource remarks of the five instantiations (registers, LDS, scratch) are read when hipcc is present (tools/kernel_resources.py).
 
   python tools/time_bw_fused.py [--windows 7] [--window 0.2] [--out profiles/bw_fused_c2.json]
 """
@@ -17,6 +17,7 @@ import argparse
 import ctypes as C
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -54,6 +55,17 @@ def timed_windows(torch, forms, windows, window_s):
 def summary(ms):
     return dict(median_ms=float(np.median(ms)), min_ms=float(min(ms)), max_ms=float(max(ms)), spread_ms=float(max(ms) - min(ms)),
                 window_ms=[round(x, 5) for x in ms])
+
+
+def kernel_resources():
+    """{"(de, dn, dg, oe)": {sgpr, vgpr, scratch, lds, occupancy}} of the five k_bw_edge_wave instantiations of gnx_backward_narrow.hip"""
+    from tools.kernel_resources import remarks
+    res = {}
+    for name, r in remarks("gnx_backward_narrow.hip").items():
+        m = re.match(r"_ZN3gnx14k_bw_edge_waveILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEEv", name)
+        if m:
+            res[tuple(int(v) for v in m.groups())] = dict(sgpr=r["sgpr"], vgpr=r["vgpr"], scratch=r["scratch"], lds=r["lds"], occupancy=r["waves_per_simd"])
+    return {str(k): v for k, v in sorted(res.items())}
 
 
 def one_case(a, gn, g, dims, label):
@@ -127,8 +139,8 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     try:  # (the compiler runs before this process opens the GPU)
-        from tests.test_bw_fused_abi import HIPCC, resources
-        kres = {str(k): v for k, v in sorted(resources().items())} if os.path.exists(HIPCC) else "not measured (no hipcc)"
+        from tools.kernel_resources import HIPCC
+        kres = kernel_resources() if os.path.exists(HIPCC) else "not measured (no hipcc)"
     except Exception as e:  # the timing stands without it
         kres = f"not measured ({type(e).__name__})"
     import torch

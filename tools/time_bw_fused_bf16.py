@@ -29,39 +29,23 @@ import argparse
 import ctypes as C
 import json
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.kernel_resources import HIPCC  # noqa: E402
 from tools.time_bw_fused import summary, timed_windows  # noqa: E402
 
 OUT = (3, 4, 5)
-CSRC = os.path.join(ROOT, "graphnets.jl_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-def resources(hipcc=HIPCC):
-    """{"(de, dn, dg, oe)": {"fp32": {...}, "bf16": {...}}} of k_bw_edge_wave / k_bw_edge_wave_bf16, from -Rpass-analysis=kernel-resource-usage
-    on gnx_backward_narrow.hip compiled as build.py compiles it"""
-    cmd = [hipcc, "-x", "hip", "-c", "--cuda-device-only", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-           "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, os.path.join(CSRC, "gnx_backward_narrow.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = {}
-    for blk in re.split(r"remark: Function Name: ", r.stderr)[1:]:
-        m = re.match(r"_ZN3gnx\d+k_bw_edge_wave(_bf16)?ILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEEv", blk.split()[0])
-        if not m:
-            continue
-        g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
-        key = str(tuple(int(v) for v in m.groups()[1:]))
-        out.setdefault(key, {})["bf16" if m.group(1) else "fp32"] = dict(
-            sgpr=g("TotalSGPRs"), vgpr=g("VGPRs"), scratch=g(r"ScratchSize \[bytes/lane\]"), lds=g(r"LDS Size \[bytes/block\]"),
-            waves_per_simd=g(r"Occupancy \[waves/SIMD\]"))
-    return out
+def resources():
+    """{"(de, dn, dg, oe)": {"fp32": {...}, "bf16": {...}}} of k_bw_edge_wave / k_bw_edge_wave_bf16 in gnx_backward_narrow.hip, compiled as build.py
+    compiles it (tools/kernel_resources.py)"""
+    from tools.kernel_resources import pick, remarks
+    return pick("bw_narrow", remarks("gnx_backward_narrow.hip"))
 
 
 def profiled(gn, torch, f):
