@@ -945,7 +945,8 @@ int32_t gnx_core_forward(const gnx_graphs* h, const gnx_core_params* p, const fl
 // gnx_core_forward.
 static bool core_typed_native(const gnx_graphs* h, const gnx_core_params* p, uint32_t flags) {
   if ((flags & GNX_FLAG_FORCE_GENERIC) || form(GNX_FLAG_NO_JIT)) return false;
-  return p->block.og == 3 && narrow_bf16_ln_aot(h, block_probe(h, &p->block));
+  const BlockArgs a = block_probe(h, &p->block);
+  return p->block.og == 3 && a.n_wtiles > 0 && a.E > 0 && narrow_ln_aot(h, a, true);
 }
 
 // workspace of a bf16 core call: gnx_core_forward's, then (fallback only) fp32 copies of the six tensors (gnx_staging.h).  The native path

@@ -283,7 +283,7 @@ enum : int {
 };
 
 // The widths and counts of a block on a handle, nothing else set: what the "which kernel takes these widths" predicates read (jit_eligible,
-// narrow_route / block_narrow_takes, narrow_bf16_aot, wide_plan) and the start of every full BlockArgs.  h == NULL (a width set asked
+// narrow_route / block_narrow_takes, wide_plan) and the start of every full BlockArgs.  h == NULL (a width set asked
 // about without a batch: gnx_jit_precompile) leaves the counts 0.
 inline BlockArgs block_probe(const gnx_graphs* h, const gnx_block_params* p) {
   BlockArgs a{};

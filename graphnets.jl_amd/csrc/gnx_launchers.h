@@ -3,6 +3,7 @@
 // a compile error, not a link error), and the one place their default arguments are written.  Not part of the ABI.
 #pragma once
 #include "gnx_internal.h"
+#include "gnx_narrow_sets.h"
 
 namespace gnx {
 
@@ -38,6 +39,10 @@ int32_t launch_fn_input(const gnx_graphs* h, int kind, const float* ef, int de, 
 
 // ---- gnx_narrow.hip / gnx_narrow_bf16.hip / gnx_jit.cpp: the fused narrow block ----
 // launch_*: 1 when the path does not apply to these dims (the caller falls through to the next path); phase: GNX_PHASE_* (gnx_internal.h)
+// Which ahead-of-time forms a width set has is read from the table of gnx_narrow_sets.h, in any translation unit:
+inline unsigned narrow_forms(const BlockArgs& a, bool bf16) { return narrow_forms(a.de, a.dn, a.dg, a.oe, a.on, bf16); }
+// LayerNorm on load ahead of time (with bf16: the block of a bf16 core): the sets with NF_LN, at the default wave-tile size
+inline bool narrow_ln_aot(const gnx_graphs* h, const BlockArgs& a, bool bf16) { return (narrow_forms(a, bf16) & NF_LN) && h->wtile_e_cap == 128; }
 int32_t launch_block_narrow(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase, bool bf16 = false);
 void warm_block_narrow(const gnx_graphs* h, const gnx_block_params* p, bool bf16 = false);
 bool block_narrow_ready(const gnx_graphs* h, const BlockArgs& a, hipStream_t s);
@@ -45,16 +50,14 @@ bool block_narrow_ffe_applies(const gnx_graphs* h, const BlockArgs& a, int act1,
 bool block_narrow_chain_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16 = false);
 bool block_narrow_takes(const gnx_graphs* h, const BlockArgs& a, hipStream_t s, bool bf16 = false);
 int32_t launch_block_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, bool bf16);
-bool narrow_bf16_aot(const gnx_graphs* h, const BlockArgs& a);
-int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
-int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
-bool narrow_bf16_ln_aot(const gnx_graphs* h, const BlockArgs& a);
-int32_t launch_ln_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
 bool block_narrow_run_applies(const gnx_graphs* h, const BlockArgs& a, bool bf16);
-bool narrow_bf16_run(const gnx_graphs* h, const BlockArgs& a);
 int32_t launch_block_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, bool bf16, int phase = 3);
 bool block_narrow_carry_applies(const gnx_graphs* h, const BlockArgs& a);
 int32_t launch_block_narrow_carry(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, const PrevTable& prev, hipStream_t s);
+// gnx_narrow_bf16.hip: the same launchers on bf16 rows (a.ffe_w1 / LayerNorm on load: launch_ln_bf16); 1: the table has no such kernel
+int32_t launch_fused_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
+int32_t launch_chained_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s);
+int32_t launch_ln_bf16(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase);
 int32_t launch_run_bf16(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s);
 bool jit_eligible(const BlockArgs& a, int ept);
 int32_t jit_get(const BlockArgs& a, int ept, hipStream_t s, hipFunction_t* block, hipFunction_t* graph, bool bf16 = false);

@@ -1,9 +1,11 @@
-// Launchers of the fused narrow kernels (gnx_wave_kernel.h) for a width set known at compile time: shared by gnx_narrow.hip (fp32 features)
-// and gnx_narrow_bf16.hip (bfloat16 features, a translation unit of its own: see there).
+// Launchers of the fused narrow kernels (gnx_wave_kernel.h) for a width set known at compile time, and — at the end — the ONE place the
+// table of gnx_narrow_sets.h is expanded: narrow_set_dispatch and the four launchers by form on top of it.  Shared by gnx_narrow.hip (fp32
+// features: BF16 = false) and gnx_narrow_bf16.hip (bfloat16 features, a translation unit of its own: see there).
 #pragma once
 #include <cstdlib>
 
 #include "gnx_device.h"
+#include "gnx_narrow_sets.h"
 #include "gnx_wave_kernel.h"
 
 namespace gnx {
@@ -137,9 +139,77 @@ static int32_t launch_fused(const gnx_graphs* h, const BlockArgs& a, int64_t R, 
   if (h->wtile_e_cap == 64) return launch_wave_t<DE, DN, DG, OE, ON, 1, false, BF16>(h, a, R, s, phase);
   if (h->wtile_e_cap == 128) return launch_wave_t<DE, DN, DG, OE, ON, 2, false, BF16>(h, a, R, s, phase);
   if (h->wtile_e_cap == 256) {
-    if constexpr ((DE + DN) * 4 <= 64) return launch_wave_t<DE, DN, DG, OE, ON, 4, false, BF16>(h, a, R, s, phase);
+    if constexpr (narrow_cap_ok(DE, DN, 256)) return launch_wave_t<DE, DN, DG, OE, ON, 4, false, BF16>(h, a, R, s, phase);
   }
   return 1;
+}
+
+// ---- the table's one expansion site ----
+// f(S{}) for the row S of the element type's list (gnx_narrow_sets.h) with a's widths: S::DE .. S::ON and S::forms are constants, so f picks
+// its instantiation with `if constexpr (S::forms & NF_...)` and a form a row lacks is never compiled.  1: no row (or f had no kernel).
+template <class F, class... S>
+static int32_t narrow_set_dispatch_in(NarrowSetList<S...>, const BlockArgs& a, F&& f) {
+  int32_t rc = 1;
+  (void)((S::is(a.de, a.dn, a.dg, a.oe, a.on) && ((rc = f(S{})), true)) || ...);
+  return rc;
+}
+template <bool BF16, class F>
+static int32_t narrow_set_dispatch(const BlockArgs& a, F&& f) {
+  if constexpr (BF16) return narrow_set_dispatch_in(NarrowSetsBF16{}, a, f);
+  else return narrow_set_dispatch_in(NarrowSetsF32{}, a, f);
+}
+
+// The launchers by form; each returns 1 where the set, or the set at this batch or wave-tile size, has no such kernel.
+// NF_PLAIN: the block — whole (phase 3), one launch of the two, or only the graph update from partial rows a chained launch left.
+template <bool BF16>
+static int32_t launch_narrow_plain(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+  return narrow_set_dispatch<BF16>(a, [&](auto set) -> int32_t {
+    using S = decltype(set);
+    if constexpr (S::forms & NF_PLAIN) return launch_fused<S::DE, S::DN, S::DG, S::OE, S::ON, BF16>(h, a, R, s, phase);
+    return 1;
+  });
+}
+// NF_PLAIN, chained: this call's edge + node update with a.prev_* (the previous call's pending graph update) at the front of the launch.
+template <bool BF16>
+static int32_t launch_narrow_chained(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s) {
+  return narrow_set_dispatch<BF16>(a, [&](auto set) -> int32_t {
+    using S = decltype(set);
+    if constexpr (S::forms & NF_PLAIN)
+      return h->G == 1 ? launch_wave_g<S::DE, S::DN, S::DG, S::OE, S::ON, 2, false, true, false, true, BF16>(h, a, R, s, 1)
+                       : launch_wave_g<S::DE, S::DN, S::DG, S::OE, S::ON, 2, false, false, false, true, BF16>(h, a, R, s, 1);
+    return 1;
+  });
+}
+// NF_RUN1 / NF_RUNG: a run of Z steps in one launch plus one for their graph updates.
+template <bool BF16>
+static int32_t launch_narrow_run(const gnx_graphs* h, const BlockArgs& a, const RunTable& t, int Z, hipStream_t s, int phase) {
+  return narrow_set_dispatch<BF16>(a, [&](auto set) -> int32_t {
+    using S = decltype(set);
+    if (h->G == 1) {
+      if constexpr (S::forms & NF_RUN1) return launch_wave_run<S::DE, S::DN, S::DG, S::OE, S::ON, true, BF16>(h, a, t, Z, s, phase);
+    } else {
+      if constexpr (S::forms & NF_RUNG) return launch_wave_run<S::DE, S::DN, S::DG, S::OE, S::ON, false, BF16>(h, a, t, Z, s, phase);
+    }
+    return 1;
+  });
+}
+// NF_LN / NF_FFE (a.ffe_w1 set): LayerNorm on load — with BF16 the block of a bf16 core: gn1 applied to the bf16 rows as they are loaded, the
+// block's outputs leave as fp32 (a.nf_out, a.gf_out and, without the FeedForward in the edge lanes, a.ef_out are fp32 staging); with
+// a.ffe_w1 the edge lanes finish the core's edge rows and store them, rounded once, as bf16 (a.ef_out is then the caller's).
+template <bool BF16>
+static int32_t launch_narrow_ln(const gnx_graphs* h, const BlockArgs& a, int64_t R, hipStream_t s, int phase) {
+  if (h->wtile_e_cap != 128) return 1;
+  return narrow_set_dispatch<BF16>(a, [&](auto set) -> int32_t {
+    using S = decltype(set);
+    if (a.ffe_w1) {
+      if constexpr (S::forms & NF_FFE)
+        return h->G == 1 ? launch_wave_g<S::DE, S::DN, S::DG, S::OE, S::ON, 2, true, true, true, false, BF16>(h, a, R, s, phase)
+                         : launch_wave_g<S::DE, S::DN, S::DG, S::OE, S::ON, 2, true, false, true, false, BF16>(h, a, R, s, phase);
+    } else {
+      if constexpr (S::forms & NF_LN) return launch_wave_t<S::DE, S::DN, S::DG, S::OE, S::ON, 2, true, BF16>(h, a, R, s, phase);
+    }
+    return 1;
+  });
 }
 
 }  // namespace gnx

@@ -4,7 +4,11 @@
 // answer on a box without a GPU.  What runs under ASan: adjacency / CSC validation and conversion, tile-table construction,
 // every error path that must free a half-built handle, model-descriptor validation, the run-time kernel specialiser's
 // source handling (hiprtc compiles gfx950 code without a GPU) and the profiling registry.
+#include <dirent.h>
+#include <unistd.h>
+
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <random>
 #include <string>
@@ -13,9 +17,13 @@
 #include "gnx_internal.h"
 
 extern "C" const char gnx_jit_source[] = R"(
-namespace gnx { struct BlockArgs { int x; };
-template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG> __global__ void k_block_wave(BlockArgs a, int n) {}
-template <int C, bool ONEG> __global__ void k_graph_t(BlockArgs a, int n) {} }
+namespace gnx { struct BlockArgs { int x; }; struct BwEdgeWave { int x; };
+template <int DE, int DN, int DG, int OE, int ON, int EPT, bool LN, bool ONEG, bool PACK = false, bool RUN = false, bool CHAIN = false, bool BF16 = false>
+__global__ void k_block_wave(BlockArgs a, int n) {}
+template <int C, bool ONEG, bool BF16 = false, bool OUT16 = false> __global__ void k_graph_t(BlockArgs a, int n) {}
+template <int DE, int DN, int DG, bool GRAPH> __global__ void k_core_post3(BlockArgs a, int n) {}
+template <int DE, int DN, int DG, int OE> __global__ void k_bw_edge_wave(BwEdgeWave a) {}
+template <int DE, int DN, int DG, int OE> __global__ void k_bw_edge_wave_bf16(BwEdgeWave a) {} }
 )";
 
 namespace gnx {
@@ -255,6 +263,62 @@ int main() {
     EXPECT(gnx_jit_precompile(&p, 128, &bytes) == GNX_ERR_DIMS);
     int64_t st[4];
     EXPECT(gnx_jit_stats(st) == GNX_OK);
+  }
+  // ---- the specialiser's disk cache and statistics, every kind twice: compiled and written the first time, read back the second; the
+  //      compile-only entry of k_core_post3 moves no counter and writes no file ----
+  {
+    char dir[] = "/tmp/gnx_jit_cache_XXXXXX";
+    EXPECT(mkdtemp(dir) != nullptr);
+    setenv("GNX_JIT_CACHE", dir, 1);
+    auto files = [&] {
+      std::vector<std::string> names;
+      if (DIR* d = opendir(dir)) {
+        while (dirent* e = readdir(d))
+          if (e->d_name[0] != '.') names.push_back(e->d_name);
+        closedir(d);
+      }
+      return names;
+    };
+    gnx_block_params p{};
+    p.de = 7; p.dn = 3; p.dg = 2; p.oe = 5; p.on = 6; p.og = 1;
+    gnx_block_params q{};
+    q.de = 3; q.dn = 2; q.dg = 4; q.oe = 3; q.on = 2; q.og = 1;
+    size_t bytes = 0;
+    struct Kind { const char* prefix; int32_t (*call)(const gnx_block_params*, size_t*); const gnx_block_params* p; };
+    const Kind kinds[] = {
+        {"gnx_wave_7_3_2_5_6_e2_", [](const gnx_block_params* p, size_t* b) { return gnx_jit_precompile(p, 128, b); }, &p},
+        {"gnx_wave_7_3_2_5_6_e1_bf16_", [](const gnx_block_params* p, size_t* b) { return gnx_jit_precompile_typed(p, 64, GNX_ELEM_BF16, b); }, &p},
+        {"gnx_bw_edge_3_2_4_3_f32_", [](const gnx_block_params* p, size_t* b) { return gnx_jit_precompile_bw_edge(p, GNX_ELEM_F32, b); }, &q},
+        {"gnx_bw_edge_3_2_4_3_bf16_", [](const gnx_block_params* p, size_t* b) { return gnx_jit_precompile_bw_edge(p, GNX_ELEM_BF16, b); }, &q},
+    };
+    size_t n_files = 0;
+    for (const Kind& k : kinds) {
+      int64_t s0[4], s1[4], s2[4];
+      EXPECT(gnx_jit_stats(s0) == GNX_OK);
+      bytes = 0;
+      if (k.call(k.p, &bytes) != GNX_OK) { EXPECT(gnx_last_error()[0] != 0); continue; }  // hiprtc absent: a message
+      const size_t first = bytes;
+      EXPECT(gnx_jit_stats(s1) == GNX_OK && s1[0] == s0[0] + 1 && s1[1] == s0[1] && s1[2] == s0[2] && s1[3] == s0[3]);
+      const std::vector<std::string> names = files();
+      EXPECT(names.size() == ++n_files);
+      size_t hits = 0;
+      for (const std::string& n : names) hits += n.compare(0, strlen(k.prefix), k.prefix) == 0 && n.size() == strlen(k.prefix) + 16 + 4 && n.substr(n.size() - 4) == ".bin";
+      EXPECT(hits == 1);
+      EXPECT(k.call(k.p, &bytes) == GNX_OK && bytes == first && first > 0);
+      EXPECT(gnx_jit_stats(s2) == GNX_OK && s2[0] == s1[0] && s2[1] == s1[1] + 1 && s2[2] == s1[2] && s2[3] == s1[3]);
+      EXPECT(files().size() == n_files);
+    }
+    for (int twice = 0; twice < 2; ++twice) {
+      int64_t s0[4], s1[4];
+      EXPECT(gnx_jit_stats(s0) == GNX_OK);
+      const int32_t rc = gnx_jit_precompile_core_post(5, 4, 3, &bytes);
+      EXPECT(rc == GNX_OK ? bytes > 0 : gnx_last_error()[0] != 0);
+      EXPECT(gnx_jit_stats(s1) == GNX_OK && memcmp(s0, s1, sizeof s0) == 0 && files().size() == n_files);
+    }
+    EXPECT(gnx_jit_precompile_core_post(17, 4, 3, &bytes) == GNX_ERR_DIMS);
+    for (const std::string& n : files()) remove((std::string(dir) + "/" + n).c_str());
+    rmdir(dir);
+    unsetenv("GNX_JIT_CACHE");
   }
   // ---- profiling registry ----
   {

@@ -156,7 +156,7 @@ def test_chained_bf16_kernels_resource_audit():
         pytest.skip("hipcc not available")
     res = dict(zip(("bf16", "f32"), remarks_many(["gnx_narrow_bf16.hip", "gnx_narrow.hip"])))  # (both compiles at once, as build.py compiles the files)
     chained = {n: v for n, v in res["bf16"].items() if re.match(r"_ZN3gnx12k_block_waveI(Li\d+E){6}(Lb[01]E){4}Lb1ELb1EEEv", n)}
-    # two per width set of GNX_NARROW_DIMS_BF16 (one graph, several graphs); (10,5,0) => (3,4,5) and (3,4,5) => (3,4,5) at least
+    # two per NF_PLAIN set of the bf16 list in gnx_narrow_sets.h (one graph, several graphs); (10,5,0) => (3,4,5) and (3,4,5) => (3,4,5) at least
     assert len(chained) >= 4 and any("ILi3ELi4ELi5ELi3ELi4E" in n for n in chained), sorted(chained)
     for n, v in chained.items():
         f32 = res["f32"].get(n.replace("ELb1ELb1EEEv", "ELb1ELb0EEEv"))

@@ -137,7 +137,7 @@ def _key(de, dn, dg, oe, on):
     return "".join(f"Li{v}E" for v in (de, dn, dg, oe, on, 2))
 
 
-# the width sets and graph-count forms with a carrying kernel (gnx_narrow.hip: GNX_NARROW_CARRY_DIMS), as the mangled names spell them
+# the width sets and graph-count forms with a carrying kernel (gnx_narrow_sets.h: NF_CARRY1 / NF_CARRYG), as the mangled names spell them
 CARRY = {(_key(*d), g) for d in ((10, 5, 0, 3, 4), (3, 4, 5, 3, 4), (10, 5, 3, 3, 4), (0, 2, 0, 2, 2), (4, 3, 2, 3, 4)) for g in "01"}
 
 

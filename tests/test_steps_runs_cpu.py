@@ -115,7 +115,7 @@ def test_runs_grouping_and_schedule_order_every_conflicting_pair(tmp_path):
     assert "runs ok" in out.stdout
 
 
-# the width sets with a run kernel (gnx_narrow.hip: GNX_NARROW_RUN_DIMS; gnx_narrow_bf16.hip: GNX_NARROW_RUN_DIMS_BF16), as the mangled names spell them
+# the width sets with a run kernel (gnx_narrow_sets.h: NF_RUN1 / NF_RUNG of either list), as the mangled names spell them
 def _key(de, dn, dg, oe, on):
     return "".join(f"Li{v}E" for v in (de, dn, dg, oe, on, 2))
 
