@@ -16,59 +16,23 @@ Backward: the generic pullback, the all-fused one, the fused node pullback behin
 graph output), a hidden gelu, a gelu last layer, a wide case, grads = NULL, bf16 staged.
 """
 import argparse
-import ctypes as C
 import hashlib
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import calls, timing  # noqa: E402
+from tools.calls import FN  # noqa: E402
+from tools.timing import sha  # noqa: E402
 
-FN = (("edge", "edgefn"), ("node", "nodefn"), ("graph", "graphfn"))
 # (label, graph, in_dims, edge / node / graph widths): the cases tests/chain_bw_cases.py does not have
 EXTRA = (("X-edgeless", "edgeless", (10, 5, 3), [16, 3], [8, 4], [6, 5]),
          ("X-forward-only-oe0", "batch", (10, 5, 3), [], [8, 4], [6, 5]),
          ("X-partial-forward", "batch", (10, 5, 3), [33, 3], [8, 4], [6, 5]))  # the edge function outside the forward's rule, the other two inside
-
-
-def sha(t):
-    import torch
-    return None if t is None else hashlib.sha256(t.detach().contiguous().view(-1).view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
-
-
-def ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
-def chain_params(gn, p, keep):
-    """(gnx_chain_block_params, [[(dW shape, db shape)]]) of an oracle parameter dict; the weights go to the device"""
-    import torch
-    from oracle import gn_oracle as O
-    L = gn._lib
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-    q = L.ChainBlockParams()
-    q.de, q.dn, q.dg = p["in_dims"]
-    shapes = []
-    for name, field in FN:
-        layers = p[name]
-        arr, wid = (L.Dense * max(len(layers), 1))(), (C.c_int32 * max(len(layers), 1))()
-        shapes.append([])
-        for i, (w, b, c) in enumerate(layers):
-            ln = isinstance(w, str)
-            W, B = (dev(b), dev(c)) if ln else (dev(np.asarray(w).T), dev(b))
-            kind = 0 if not ln else (L.LAYER_LAYERNORM | L.LAYER_LN_SQRT_EPS if O.ln_eps_mode(w) == 1 else L.LAYER_LAYERNORM)
-            arr[i] = L.Dense(ptr(W), ptr(B), 0 if ln else int(c), kind)
-            wid[i] = len(b) if ln else w.shape[0]
-            shapes[-1].append((tuple(W.shape), tuple(B.shape)))
-            keep += [W, B]
-        keep += [arr, wid]
-        ch = getattr(q, field)
-        ch.layers, ch.widths, ch.n_layers = arr, wid, len(layers)
-    return q, shapes
 
 
 def out_widths(p):
@@ -79,67 +43,42 @@ def out_widths(p):
 def run_case(gn, g, d, grads_null=False):
     """{entry label: record} of one case on handle g; d = dict(p, x, cot, R)"""
     import torch
-    lib, L = gn._lib.load(), gn._lib
+    L = gn._lib
     keep = []
-    q, gshapes = chain_params(gn, d["p"], keep)
-    p, R = C.byref(q), d["R"]
-    s = torch.cuda.current_stream().cuda_stream
-    rows = (g.n_edges, g.n_nodes, g.n_graphs)
+    q = calls.chain_params(gn, d["p"], keep)
     ow = out_widths(d["p"])
-    nan = lambda shape, dt: torch.full(shape, float("nan"), dtype=dt, device="cuda")
     to = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda().to(dt)
     rec = {}
     # (label, elem or None for the fp32-only entries, narrow)
     forms = [("fp32", None, 0), ("fp32 narrow", None, 1)] + [(f"typed {en} narrow={n}", e, n) for en, e in (("fp32", L.ELEM_F32), ("bf16", L.ELEM_BF16)) for n in (0, 1)]
     for label, elem, narrow in forms:
-        dt = torch.bfloat16 if elem == L.ELEM_BF16 else torch.float32
-        x = [to(v, dt) for v in d["x"]]
-        cot = [to(v, dt) for v in d["cot"]]
         typed = elem is not None
-        # ---- forward ----
-        if typed:
-            query, entry, ap = lib.gnx_chain_block_forward_typed_workspace_bytes, lib.gnx_chain_block_forward_typed, lib.gnx_chain_block_forward_typed_applies
-            qa, head, tail = (elem, narrow), (elem,), (narrow, 0, s)
-        else:
-            query = lib.gnx_chain_block_forward_narrow_workspace_bytes if narrow else lib.gnx_chain_block_workspace_bytes
-            entry, ap = (lib.gnx_chain_block_forward_narrow if narrow else lib.gnx_chain_block_forward), lib.gnx_chain_block_forward_narrow_applies
-            qa, head, tail = (), (), (0, s)
-        nb = int(query(g._h, p, R, *qa))
-        ws = torch.full((max(nb, 256),), 0xA5, dtype=torch.uint8, device="cuda")
-        outs = [nan((R, T, w), dt) if w else None for T, w in zip(rows, ow)]
-        rc = int(entry(g._h, p, *head, *map(ptr, x), R, *map(ptr, outs), ws.data_ptr(), nb, *tail))
-        torch.cuda.synchronize()
-        assert rc == 0, (label, lib.gnx_last_error())
-        rec["forward " + label] = dict(applies=int(ap(g._h, p, R, *qa)), workspace_bytes=nb, rc=rc, sha256={n: sha(t) for n, t in zip(("ef_out", "nf_out", "gf_out"), outs)})
-        if ow[0] == 0:  # no pullback without an edge output: a forward-only block
-            continue
-        # ---- backward ----
-        if typed:
-            query, entry, qa, head, tail = lib.gnx_chain_block_backward_typed_workspace_bytes, lib.gnx_chain_block_backward_typed, (elem, narrow), (elem,), (narrow, s)
-        else:
-            query = lib.gnx_chain_block_backward_narrow_workspace_bytes if narrow else lib.gnx_chain_block_backward_workspace_bytes
-            entry, qa, head, tail = (lib.gnx_chain_block_backward_narrow if narrow else lib.gnx_chain_block_backward), (), (), (s,)
-        nb = int(query(g._h, p, R, *qa))
-        ws = torch.full((max(nb, 256),), 0xA5, dtype=torch.uint8, device="cuda")
-        dx = [nan(tuple(v.shape), dt) if v is not None else None for v in x]
-        gts = [[(nan(a, torch.float32), nan(b, torch.float32)) for a, b in fn] for fn in gshapes]
-        arrays = []
-        for fn in gts:
-            arr = (L.DenseGrad * max(len(fn), 1))()
-            for i, (a, b) in enumerate(fn):
-                arr[i] = L.DenseGrad(ptr(a), ptr(b))
-            arrays.append(arr)
-        gr = L.ChainBlockGrads(*[C.cast(a, C.POINTER(L.DenseGrad)) for a in arrays])
-        rc = int(entry(g._h, p, *head, *map(ptr, x), *map(ptr, cot), R, *map(ptr, dx), None if grads_null else C.byref(gr), ws.data_ptr(), nb, *tail))
-        torch.cuda.synchronize()
-        assert rc == 0, (label, lib.gnx_last_error())
-        hashes = {n: sha(t) for n, t in zip(("d_ef", "d_nf", "d_gf"), dx)}
-        hashes.update({f"{name}{i}.{k}": sha(t) for (name, _), fn in zip(FN, gts) for i, ab in enumerate(fn) for k, t in zip(("dW", "db"), ab)})
-        rec["backward " + label] = dict(applies=int(lib.gnx_chain_block_backward_narrow_applies(g._h, p, R)), workspace_bytes=nb, rc=rc, sha256=hashes)
+        elem = L.ELEM_F32 if elem is None else elem
+        dt = calls.elem_dtype(gn, elem)
+        case = calls.given_case(g, q, keep, [to(v, dt) for v in d["x"]], [to(v, dt) for v in d["cot"]], ow, R=d["R"], oracle=d["p"])
+        for direction in ("forward", "backward"):
+            if direction == "backward" and ow[0] == 0:  # no pullback without an edge output: a forward-only block
+                continue
+            if typed:  # (the typed entries take `narrow` as a value, the fp32-only ones are two names)
+                c = calls.build(gn, case, "chain", direction, elem, f"gnx_chain_block_{direction}_typed", narrow=narrow, poison=True, grads=not grads_null)
+            else:
+                c = calls.build(gn, case, "chain", direction, elem, f"gnx_chain_block_{direction}" + ("_narrow" if narrow else ""), poison=True, grads=not grads_null)
+            c.f()
+            torch.cuda.synchronize()
+            if direction == "forward":
+                ap = calls.applies(gn, case, "gnx_chain_block_forward_typed_applies", elem, narrow) if typed else calls.applies(gn, case, "gnx_chain_block_forward_narrow_applies")
+                hashes = {n: sha(t) for n, t in zip(("ef_out", "nf_out", "gf_out"), c.outs)}
+            else:
+                ap = calls.applies(gn, case, "gnx_chain_block_backward_narrow_applies")
+                hashes = {n: sha(t) for n, t in zip(("d_ef", "d_nf", "d_gf"), c.outs)}
+                slots = iter(c.grads if c.grads else calls.grad_slots(gn, case, "chain", poison=True)[0])  # (grads = NULL: slots nobody wrote, still NaN)
+                hashes.update({f"{name}{i}.{k}": sha(next(slots)) for name, _ in FN for i in range(len(d["p"][name])) for k in ("dW", "db")})
+            rec[f"{direction} {label}"] = dict(applies=ap, workspace_bytes=c.nbytes, rc=0, sha256=hashes)
     return rec
 
 
-def run():
+def run(limit=None):
+    """the child's record; limit: the first cases of tests/chain_bw_cases.py only, without the assertion over all of them (tests/test_gpu_timing_tools.py)"""
     import torch
     import graphnets_jl_amd as gn
     from oracle import gn_oracle as O
@@ -151,9 +90,11 @@ def run():
     edgeless = [(np.zeros(n + 1, dtype=np.int64), np.zeros(0, dtype=np.int64)) for n in (5, 3, 7)]
     handles = {k: MC._from_csc(gn, parts)[0] for k, parts in (("batch", list(CC.batch_parts())), ("one", [BC.graph_parts()]), ("edgeless", edgeless))}
     rec = {}
-    for cid in CC.CASE_IDS:
+    for cid in CC.CASE_IDS[:limit]:
         d = CC.data(cid)
         rec[cid] = run_case(gn, handles["one" if d["R"] > 1 else "batch"], d)
+    if limit is not None:
+        return rec
     rec["N-w16-32 grads NULL"] = run_case(gn, handles["batch"], CC.data("N-w16-32"), grads_null=True)
     for k, (label, graph, in_dims, ew, nw, gw) in enumerate(EXTRA):
         g = handles[graph]
@@ -173,7 +114,7 @@ def run():
             "gelu last fused": bw("N-last-act") == 7, "fused node behind a generic graph function": bw("N-mixed") == 2 and CC.out_widths("N-mixed")[2] > 0,
             "forward only": "backward fp32" not in rec["X-forward-only-oe0"], "edgeless backward": rec["X-edgeless"]["backward fp32 narrow"]["rc"] == 0}
     assert all(want.values()), [k for k, v in want.items() if not v]
-    print(json.dumps(rec))
+    return rec
 
 
 def main():
@@ -184,30 +125,19 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.run:
-        return run()
-    recs = []
-    for lib in a.libs:  # one after the other, parent first; a failure ends the run
-        try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--run"], env=dict(os.environ, GNX_LIB_PATH=os.path.abspath(lib)), capture_output=True,
-                               text=True, timeout=a.timeout, cwd=ROOT)
-        except subprocess.TimeoutExpired:
-            print(f"{lib}: no end within {a.timeout} s", file=sys.stderr)
-            sys.exit(2)
-        if r.returncode != 0:
-            print(f"{lib}: exit status {r.returncode}\n{r.stderr[-4000:]}", file=sys.stderr)
-            sys.exit(2)  # (a child that failed: nothing further is started)
-        recs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        return timing.print_record(run())
+    recs = [rec for _, rec in timing.library_rounds(__file__, a.libs, 1, ["--run"], a.timeout, cwd=ROOT)]  # one after the other, parent first; a failure ends the run
     same = recs[0] == recs[1]
     differing = [] if same else sorted(f"{k} / {e}" for k in set(recs[0]) | set(recs[1]) for e in set(recs[0].get(k, {})) | set(recs[1].get(k, {}))
                                        if recs[0].get(k, {}).get(e) != recs[1].get(k, {}).get(e))
     if a.out:  # one line per call: the tensors' hashes (compared one by one above) folded into one SHA-256 over "name:hash" lines in name order
         fold = lambda e: dict(applies=e["applies"], workspace_bytes=e["workspace_bytes"], rc=e["rc"], tensors=sum(h is not None for h in e["sha256"].values()),
                               sha256=hashlib.sha256("\n".join(f"{n}:{h}" for n, h in sorted(e["sha256"].items())).encode()).hexdigest())
-        calls = lambda rec: {f"{k} / {e}": fold(v) for k, c in rec.items() for e, v in c.items()}
+        folded = lambda rec: {f"{k} / {e}": fold(v) for k, c in rec.items() for e, v in c.items()}
         with open(a.out, "w") as fh:
             fh.write('{"identical": %s, "differing": %s' % (json.dumps(same), json.dumps(differing)))
             for key, rec in (("calls", recs[1]),) + (() if same else (("parent_calls", recs[0]),)):
-                fh.write(',\n"%s": {\n' % key + ",\n".join(f"{json.dumps(call)}: {json.dumps(v)}" for call, v in calls(rec).items()) + "\n}")
+                fh.write(',\n"%s": {\n' % key + ",\n".join(f"{json.dumps(call)}: {json.dumps(v)}" for call, v in folded(rec).items()) + "\n}")
             fh.write("}\n")
     n = sum(len(v) for v in recs[1].values())
     print(f"{len(recs[1])} cases, {n} calls: " + ("the two libraries agree on every applies result, workspace size, return code and output bit" if same else f"DIFFERENT: {differing}"))

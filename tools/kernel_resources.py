@@ -56,6 +56,11 @@ def parse_remarks(stderr):
     return out
 
 
+def demangle(name):
+    """c++filt's reading of a mangled kernel name (the name itself where c++filt gives none)"""
+    return subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip() or name
+
+
 def remarks(source, like=None):
     """parse_remarks of one device-only compile for gfx950.  source: a file of csrc, or program text, which gets the per-file options of the
     csrc file `like`.  Cached in the process by source and options: a pytest session compiles each file once."""

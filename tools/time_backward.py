@@ -5,18 +5,11 @@ import os
 import sys
 import time
 
-import torch
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench  # noqa: E402
-import graphnets_jl_amd as gn  # noqa: E402
-
-cp, rv, nn = bench.make_c2()
-g = gn.GNGraphBatch.from_csc(cp, rv, nn)
-dev = g.device
 
 
-def run(din, dout, core=False):
+def run(gn, torch, g, din, dout, core=False):
+    dev = g.device
     layer = gn.GNCore(din) if core else gn.GNBlock(din, dout)
     ps = layer.parameters() if core else [t for l in (layer.edgefn, layer.nodefn, layer.graphfn) for t in (l.weight, l.bias)]
     for p in ps:
@@ -46,8 +39,16 @@ def run(din, dout, core=False):
     print(f"{'GNCore' if core else 'GNBlock'} {din}=>{dout}: forward+backward {dt * 1e3:.3f} ms / iteration; kernels (us): {prof}")
 
 
-specs = sys.argv[1:] or ["10,5,0:3,4,5", "128,64,32:128,64,32"]
-for sp in specs:
-    core = sp.startswith("core:")
-    a, b = sp.replace("core:", "").split(":")
-    run(tuple(int(v) for v in a.split(",")), tuple(int(v) for v in b.split(",")), core)
+def main():
+    import torch
+    import bench
+    import graphnets_jl_amd as gn
+    g = gn.GNGraphBatch.from_csc(*bench.make_c2())
+    for sp in sys.argv[1:] or ["10,5,0:3,4,5", "128,64,32:128,64,32"]:
+        core = sp.startswith("core:")
+        a, b = sp.replace("core:", "").split(":")
+        run(gn, torch, g, tuple(int(v) for v in a.split(",")), tuple(int(v) for v in b.split(",")), core)
+
+
+if __name__ == "__main__":
+    main()

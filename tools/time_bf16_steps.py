@@ -1,14 +1,14 @@
 """Times the loop over batches at README dims (10,5,0) => (3,4,5) in three forms, alternating window by window in one process:
 fp32 gnx_block_forward_steps, bf16 gnx_block_forward_steps_typed, and K separate gnx_block_forward_typed calls (what a bf16 caller ran
 before the typed loop existed).  K steps per call (--steps, >= 20) over 8 rotating buffer sets; each window is timed with device events
-over >= --window seconds after warm-up; the median ms/step of the windows is printed.  Configs: the 1M-edge batch (BASELINE configs[1])
-and a batch of 512 small graphs that takes the one-launch pack form.  The bf16 loop's outputs are checked bit for bit against the
-separate calls on the timed buffers.  --graph: each form is captured once into a hipGraph and the windows replay it (no host cost per step).
+over >= --window seconds after warm-up (tools/timing.py: timed_windows); the median ms/step of the windows is printed.  Configs: the
+1M-edge batch (BASELINE configs[1]) and a batch of 512 small graphs that takes the one-launch pack form.  The bf16 loop's outputs are
+checked bit for bit against the separate calls on the timed buffers.  --graph: each form is captured once into a hipGraph and the windows
+replay it (no host cost per step).
 
   python tools/time_bf16_steps.py [--steps 20] [--windows 7] [--window 0.2] [--graph] [--only c2|all] [--out result.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -16,11 +16,14 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import calls, timing  # noqa: E402
 
 NSETS = 8
+TIMING = dict(warmup=5, probe=10, min_calls=10)
+CONFIGS = (("C2 (1M edges, one graph)", timing.er_1m), ("512 small graphs (pack form)", timing.pack512))
 
 
-def run_config(gn, torch, name, g, K, windows, window_s, graph=False):
+def run_config(gn, torch, name, g, K, a):
     from oracle import gn_oracle as O
     from tests import util as U
     dims, out = (10, 5, 0), (3, 4, 5)
@@ -28,8 +31,7 @@ def run_config(gn, torch, name, g, K, windows, window_s, graph=False):
     blk = U.block_from_params(gn, O.make_block_params(rng, dims, out))
     plan32 = gn.BlockPlan(blk, g)
     plan16 = gn.BlockPlan(blk, g, dtype=torch.bfloat16)
-    ins = [(torch.from_numpy(rng.random((1, g.n_edges, 10), dtype=np.float32)).cuda(),
-            torch.from_numpy(rng.random((1, g.n_nodes, 5), dtype=np.float32)).cuda()) for _ in range(NSETS)]
+    ins = [(calls.draw(rng, "unit", (1, g.n_edges, 10)), calls.draw(rng, "unit", (1, g.n_nodes, 5))) for _ in range(NSETS)]
     sets32 = [dict(ef=e, nf=n, gf=None, out=plan32.outputs(), ws=plan32.new_workspace()) for e, n in ins]
     sets16 = [dict(ef=e.to(torch.bfloat16), nf=n.to(torch.bfloat16), gf=None, out=plan16.outputs(), ws=plan16.new_workspace()) for e, n in ins]
     sep16 = [dict(b, out=plan16.outputs()) for b in sets16]  # the separate calls write buffers of their own (compared below)
@@ -43,7 +45,7 @@ def run_config(gn, torch, name, g, K, windows, window_s, graph=False):
 
     forms = {"fp32_steps": lambda: plan32.steps(seq32), "bf16_steps": lambda: plan16.steps(seq16), "bf16_separate_typed": separate}
     graphs = []
-    if graph:
+    if a.graph:
         for key, f in list(forms.items()):
             f()
             torch.cuda.synchronize()
@@ -52,35 +54,28 @@ def run_config(gn, torch, name, g, K, windows, window_s, graph=False):
                 f()
             graphs.append(cg)
             forms[key] = cg.replay
-    calls, ms = {}, {k: [] for k in forms}
-    for key, f in forms.items():  # warm-up, then the calls per window (>= window_s of device time)
-        for _ in range(5):
-            f()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            f()
-        e1.record()
-        torch.cuda.synchronize()
-        calls[key] = max(10, int(window_s * 1e3 / (e0.elapsed_time(e1) / 10)) + 1)
-    for _ in range(windows):
-        for key, f in forms.items():  # alternate the forms window by window
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(calls[key]):
-                f()
-            e1.record()
-            torch.cuda.synchronize()
-            ms[key].append(e0.elapsed_time(e1) / (calls[key] * K))
-    differ = {k: sum(int((a[t].view(torch.int16) != b[t].view(torch.int16)).sum()) for a, b in zip([s["out"] for s in sets16], [s["out"] for s in sep16]))
+    ms, per_window = timing.timed_windows(torch, forms, a.windows, a.window, **TIMING)
+    differ = {k: sum(int((u[t].view(torch.int16) != v[t].view(torch.int16)).sum()) for u, v in zip([s["out"] for s in sets16], [s["out"] for s in sep16]))
               for t, k in enumerate(("ef", "nf", "gf"))}
-    res = dict(config=name, replayed_from_captured_graph=graph, E=g.n_edges, N=g.n_nodes, G=g.n_graphs, dims="(10,5,0)=>(3,4,5)", steps_per_call=K,
-               buffer_sets=NSETS, windows=windows, calls_per_window=calls, bf16_steps_bit_identical_to_separate_calls=not any(differ.values()), values_differing=differ)
-    for key in forms:
-        res[key] = dict(median_ms_per_step=float(np.median(ms[key])), window_ms_per_step=[round(x, 6) for x in ms[key]])
+    res = dict(config=name, replayed_from_captured_graph=a.graph, E=g.n_edges, N=g.n_nodes, G=g.n_graphs, dims="(10,5,0)=>(3,4,5)", steps_per_call=K,
+               buffer_sets=NSETS, windows=a.windows, calls_per_window=per_window, bf16_steps_bit_identical_to_separate_calls=not any(differ.values()),
+               values_differing=differ)
+    for key in forms:  # (a call is K steps)
+        res[key] = dict(median_ms_per_step=float(np.median(ms[key])) / K, window_ms_per_step=[round(x / K, 6) for x in ms[key]])
     res["bf16_steps_over_separate"] = res["bf16_steps"]["median_ms_per_step"] / res["bf16_separate_typed"]["median_ms_per_step"]
     res["bf16_steps_over_fp32_steps"] = res["bf16_steps"]["median_ms_per_step"] / res["fp32_steps"]["median_ms_per_step"]
     return res
+
+
+def run(a, graphs=None):
+    """the record; graphs: one GNGraphBatch per config in place of the full-size ones (tests/test_gpu_timing_tools.py)"""
+    import torch
+    import graphnets_jl_amd as gn
+    torch.cuda.set_device(0)
+    out = timing.RecordWriter(a.out, device=torch.cuda.get_device_name(0), replayed_from_captured_graph=a.graph, timing=timing.windows_timing(a, **TIMING), results=[])
+    for i, (name, make) in enumerate(CONFIGS[:1 if a.only == "c2" else None]):
+        out.add("results", run_config(gn, torch, name, make(gn) if graphs is None else graphs[i], a.steps, a))
+    return out.res
 
 
 def main():
@@ -94,32 +89,13 @@ def main():
     a = ap.parse_args()
     if a.steps < 20:
         ap.error("--steps must be >= 20")
-    import torch
-    import graphnets_jl_amd as gn
-    from tests import util as U
-    torch.cuda.set_device(0)
-    colptr, rowval = U.er_csc(np.random.default_rng(0), 100_000, 1_000_000)
-    results = [run_config(gn, torch, "C2 (1M edges, one graph)", gn.GNGraphBatch.from_csc([colptr], [rowval], [100_000]), a.steps, a.windows, a.window,
-                          a.graph)]
-    if a.only == "all":
-        # 512 graphs of 32..256 nodes with ~3 in-edges per node: every graph <= 8 wave tiles, so the batch takes the pack form
-        rng = np.random.default_rng(1)
-        cps, rvs, ns = [], [], []
-        for n in rng.integers(32, 257, 512):
-            cp, rv = U.er_csc(rng, int(n), int(3 * n))
-            cps.append(cp); rvs.append(rv); ns.append(int(n))
-        results.append(run_config(gn, torch, "512 small graphs (pack form)", gn.GNGraphBatch.from_csc(cps, rvs, ns), a.steps, a.windows, a.window,
-                                   a.graph))
-    out = dict(device=torch.cuda.get_device_name(0), replayed_from_captured_graph=a.graph, results=results)
-    for r in results:
+    res = run(a)
+    for r in res["results"]:
         print(f"{r['config']}: fp32 steps {r['fp32_steps']['median_ms_per_step'] * 1e3:.2f} us/step, bf16 steps "
               f"{r['bf16_steps']['median_ms_per_step'] * 1e3:.2f} us/step, {r['steps_per_call']} separate typed calls "
               f"{r['bf16_separate_typed']['median_ms_per_step'] * 1e3:.2f} us/step; bf16 loop bit-identical to the separate calls: "
               f"{r['bf16_steps_bit_identical_to_separate_calls']}")
-    print(json.dumps(out))
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(out, f, indent=1)
+    timing.print_record(res)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ call it stands in for: gnx_chain_block_forward of the PARENT commit's library.  
 
 Every sample is ONE whole call between two device events, cache-cold: a 512 MiB buffer is overwritten in front of it (outside the events).
 30 warm-up calls (settled clocks, loaded code objects); medians, min / max and the spread (max - min) of the samples are recorded, with the
-workspace bytes of both calls.
+workspace bytes of both calls (tools/timing.py: cold_samples).
 `--parent-root DIR`: a checkout of the parent commit with its library built; it is timed there first, in a process of its own (this script
 with --root DIR --baseline-only: one library per process), in the same session on the same device.  This build's own time for the untouched
 gnx_chain_block_forward stands next to the parent's to show the two sessions overlap.  `not_slower_beyond_spread`: narrow median <= parent
@@ -14,45 +14,18 @@ of the parent stay empty.
   python tools/time_chain_narrow.py [--samples 41] [--parent-root DIR] [--out profiles/chain_narrow.json]
 """
 import argparse
-import ctypes as C
-import json
 import os
-import subprocess
 import sys
 
-import numpy as np
-
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, HERE)
+from tools import calls, timing  # noqa: E402
+
 CONFIGS = (((10, 5, 0), [16, 3], [8, 4], [6, 5]),
            ((10, 5, 3), [32, 32, 3], [32, 4], [16, 5]),
            ((3, 2, 1), [8, 8, 2], [8, 3], [8, 2]),
            ((10, 5, 3), [16, "ln", 16, 3], [16, 4], [5]))
-FLUSH_BYTES = 512 << 20
-
-
-def cold_samples(torch, forms, samples, warmup=30):
-    """forms: {key: callable}; {key: [ms of each cache-cold call]}, the forms alternating sample by sample"""
-    flush = torch.empty(FLUSH_BYTES, dtype=torch.uint8, device="cuda")
-    for f in forms.values():
-        for _ in range(warmup):
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in forms}
-    for i in range(samples):
-        for key, f in forms.items():
-            flush.fill_(i & 0xFF)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            torch.cuda.synchronize()
-            ms[key].append(e0.elapsed_time(e1))
-    return ms
-
-
-def summary(ms):
-    return dict(median_ms=float(np.median(ms)), min_ms=float(min(ms)), max_ms=float(max(ms)), spread_ms=float(max(ms) - min(ms)),
-                p10_ms=float(np.percentile(ms, 10)), p90_ms=float(np.percentile(ms, 90)), samples=len(ms))
+WARMUP = 30
 
 
 def buckets(cfg):
@@ -69,44 +42,49 @@ def buckets(cfg):
 
 def one_case(a, gn, g, cfg, baseline_only):
     import torch
-    from oracle import gn_oracle as O
-    from tests.test_gpu_chain import _block
-    lib = gn._lib.load()
-    rng = np.random.default_rng(0)
-    p = O.make_chain_block_params(rng, *cfg)
-    blk = _block(gn, p)
-    keep = []
-    cp, _, outw = blk._chain_params(keep)
-    s = torch.cuda.current_stream().cuda_stream
-    rows = (g.n_edges, g.n_nodes, g.n_graphs)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    x = [torch.from_numpy(rng.random((1, T, d), dtype=np.float32)).cuda() if d else None for T, d in zip(rows, cfg[0])]
-
-    def form(query, entry):
-        nb = int(query(g._h, C.byref(cp), 1))
-        assert nb > 0, lib.gnx_last_error()
-        ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
-        y = [torch.empty((1, T, d), dtype=torch.float32, device="cuda") if d else None for T, d in zip(rows, outw)]
-
-        def call():
-            assert entry(g._h, C.byref(cp), *map(ptr, x), 1, *map(ptr, y), ws.data_ptr(), nb, 0, s) == 0, lib.gnx_last_error()
-
-        return call, nb, y
-
-    forms, wsb, outs = {}, {}, {}
-    forms["chain"], wsb["chain"], outs["chain"] = form(lib.gnx_chain_block_workspace_bytes, lib.gnx_chain_block_forward)
+    F32 = gn._lib.ELEM_F32
+    case = calls.chain_case(gn, g, cfg, cot=False)
+    built = {"chain": calls.build(gn, case, "chain", "forward", F32, "gnx_chain_block_forward")}
     rec = dict(in_dims=list(cfg[0]), edge=cfg[1], node=cfg[2], graph=cfg[3], E=g.n_edges, N=g.n_nodes, G=g.n_graphs)
     if not baseline_only:
-        rec["applies"] = int(lib.gnx_chain_block_forward_narrow_applies(g._h, C.byref(cp), 1))
+        rec["applies"] = calls.applies(gn, case, "gnx_chain_block_forward_narrow_applies")
         rec["register_width"] = buckets(cfg)
-        forms["narrow"], wsb["narrow"], outs["narrow"] = form(lib.gnx_chain_block_forward_narrow_workspace_bytes, lib.gnx_chain_block_forward_narrow)
-    ms = cold_samples(torch, forms, a.samples)
-    rec.update(forms={k: summary(v) for k, v in ms.items()}, workspace_bytes=wsb)
+        built["narrow"] = calls.build(gn, case, "chain", "forward", F32, "gnx_chain_block_forward_narrow")
+    ms = timing.cold_samples(torch, {k: c.f for k, c in built.items()}, a.samples, WARMUP)
+    rec.update(forms={k: timing.summary_samples(v) for k, v in ms.items()}, workspace_bytes={k: c.nbytes for k, c in built.items()})
     if not baseline_only:  # the two calls of this build on the same inputs: how far apart the outputs are
         torch.cuda.synchronize()
         rec["max_diff_narrow_vs_chain_over_scale"] = max(float((u.double() - v.double()).abs().max() / max(1.0, float(v.double().abs().max())))
-                                                         for u, v in zip(outs["narrow"], outs["chain"]) if u is not None)
+                                                         for u, v in zip(built["narrow"].outs, built["chain"].outs) if u is not None)
     return rec
+
+
+def run(a, parent=None, graphs=None, limit=None):
+    """the record; parent: the parent's cases; graphs: {key: GNGraphBatch} in place of the full-size ones, limit: the first cases only
+    (tests/test_gpu_timing_tools.py)"""
+    import torch
+    import graphnets_jl_amd as gn
+    torch.cuda.set_device(0)
+    out = timing.RecordWriter(None if a.baseline_only else a.out, device=torch.cuda.get_device_name(0),
+                              box="one MI355X; parent and this build timed in one session, one process each", samples=a.samples,
+                              method="one call per sample between device events, 512 MiB overwritten in front of every sample (cache-cold), forms alternating, 30 warm-up calls each",
+                              timing=timing.cold_timing(a.samples, WARMUP), measured=bool(parent), cases=[])
+    get = timing.OneGraph(gn, graphs)
+    cut = []
+    for i, (key, cfg) in enumerate([(key, cfg) for key in ("C2", "hetero512") for cfg in CONFIGS][:limit]):
+        gname = timing.GRAPHS[key][0]
+        c = one_case(a, gn, get(key), cfg, a.baseline_only)
+        c["graph_name"] = gname
+        if not a.baseline_only:
+            f = c["forms"]
+            line = f"{gname} {cfg}: chain {f['chain']['median_ms']:.4f}   narrow {f['narrow']['median_ms']:.4f} ms   ws {c['workspace_bytes']['narrow'] >> 20} / " \
+                   f"{c['workspace_bytes']['chain'] >> 20} MiB   applies {c['applies']}"
+            if parent:
+                line += timing.against_parent(c, parent[i], i, cut)
+                out.res["slower_than_parent_beyond_spread"] = cut
+            print(line, flush=True)
+        out.add("cases", c)  # (after every case: a run cut short leaves what it measured)
+    return out.res
 
 
 def main():
@@ -119,54 +97,11 @@ def main():
     a = ap.parse_args()
     parent = None
     if a.parent_root:  # first, and in a process of its own: one library per process
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--root", os.path.abspath(a.parent_root), "--baseline-only", "--samples", str(a.samples)],
-                           capture_output=True, text=True, timeout=500)
-        assert r.returncode == 0, r.stderr[-3000:]
-        parent = json.loads(r.stdout.strip().splitlines()[-1])["cases"]
-    sys.path.insert(0, a.root)
-    os.chdir(a.root)
-    import torch
-    import bench
-    import graphnets_jl_amd as gn
-    torch.cuda.set_device(0)
-    res = dict(device=torch.cuda.get_device_name(0), box="one MI355X; parent and this build timed in one session, one process each", samples=a.samples,
-               method="one call per sample between device events, 512 MiB overwritten in front of every sample (cache-cold), forms alternating, 30 warm-up calls each",
-               measured=bool(parent), cases=[])
-    graphs = (("C2: one graph, 100k nodes, 1M edges", lambda: gn.GNGraphBatch.from_csc(*bench.make_c2())),
-              ("512 graphs of 32..256 nodes, 1M edges", lambda: gn.GNGraphBatch.from_csc(*bench.make_hetero(3))))
-    cut = []
-    for gname, make in graphs:
-        g = make()
-        for cfg in CONFIGS:
-            c = one_case(a, gn, g, cfg, a.baseline_only)
-            c["graph_name"] = gname
-            i = len(res["cases"])
-            res["cases"].append(c)
-            if a.baseline_only:
-                continue
-            f = c["forms"]
-            line = f"{gname} {cfg}: chain {f['chain']['median_ms']:.4f}   narrow {f['narrow']['median_ms']:.4f} ms   ws {c['workspace_bytes']['narrow'] >> 20} / " \
-                   f"{c['workspace_bytes']['chain'] >> 20} MiB   applies {c['applies']}"
-            if parent:
-                pc = parent[i]
-                assert pc["graph_name"] == gname and pc["in_dims"] == c["in_dims"] and pc["edge"] == c["edge"]
-                base = pc["forms"]["chain"]
-                c["parent"] = dict(forms=pc["forms"], workspace_bytes=pc["workspace_bytes"])
-                c["narrow_over_parent"] = f["narrow"]["median_ms"] / base["median_ms"]
-                c["not_slower_beyond_spread"] = bool(f["narrow"]["median_ms"] <= base["median_ms"] + base["spread_ms"])
-                if not c["not_slower_beyond_spread"]:
-                    cut.append(i)
-                line += f"   parent {base['median_ms']:.4f} (spread {base['spread_ms']:.4f})   narrow / parent {c['narrow_over_parent']:.3f}"
-            print(line, flush=True)
-            if parent:
-                res["slower_than_parent_beyond_spread"] = cut
-            if a.out:  # (after every case: a run cut short leaves what it measured)
-                with open(a.out, "w") as fh:
-                    json.dump(res, fh, indent=1)
-                    fh.write("\n")
-        del g
+        parent = timing.parent_baseline(__file__, a.parent_root, ["--samples", a.samples], 500)["cases"]
+    timing.child_root(a.root)
+    res = run(a, parent)
     if a.baseline_only:
-        print(json.dumps(res))
+        timing.print_record(res)
 
 
 if __name__ == "__main__":
