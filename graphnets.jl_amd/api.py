@@ -919,7 +919,7 @@ def _ptr0(t):
 # which C entry a call of a GNBlock / GNCore reaches: one table, plain data
 # ------------------------------------------------------------------------------------------------------------
 _SWITCHES = ("bf16", "bf16_backward", "fused_backward", "narrow_backward", "narrow_chain", "narrow_chain_backward", "bf16_chain", "native_chain_backward",
-             "chain_dropout", "typed_dropout")
+             "chain_dropout", "typed_dropout", "wave_chain")
 _Entry = collections.namedtuple("_Entry", "query query_tail call head tail key")
 _CHAIN_DROPOUT_IS_TEST_MODE = ("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
                                "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
@@ -946,7 +946,8 @@ def _entry(family, direction, elem, switches=(), record=False):
                 backward   gnx_block_backward [_fused with `fused_backward`] [_typed on bf16]; gnx_block_backward_narrow with `narrow_backward`
                            (which wins over `fused_backward`; either element type); bf16 needs `bf16_backward`
       chain     forward    an active record: gnx_chain_block_forward_train (narrow = `narrow_chain`; fp32 only); bf16: gnx_chain_block_forward_typed
-                           (narrow = `narrow_chain`; needs `bf16_chain`); else gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
+                           (narrow = `narrow_chain`; needs `bf16_chain`); else gnx_chain_block_forward_wave with `wave_chain` (which wins over
+                           `narrow_chain`), gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
                 backward   (narrow = `narrow_chain_backward`) an active record: gnx_chain_block_backward_train; bf16 (needs `bf16_backward`):
                            gnx_chain_block_backward_narrow_typed with `native_chain_backward`, else gnx_chain_block_backward_typed; fp32:
                            gnx_chain_block_backward_narrow or gnx_chain_block_backward
@@ -983,6 +984,8 @@ def _entry(family, direction, elem, switches=(), record=False):
                 return E("gnx_chain_block_forward_train", (n,), ("drop",), (n, "flags"), ("chain_train", n, "in_dims", "widths", "R"))
             if bf16:  # (mirrors the entry `narrow_chain` selects)
                 return E("gnx_chain_block_forward_typed", (elem, n), (elem,), (n, "flags"), ("chain_bf16", bool(n), "in_dims", "widths", "R"))
+            if on("wave_chain"):
+                return E("gnx_chain_block_forward_wave", (), (), fl, ("chain_wave", "in_dims", "widths", "R"))
             if n:
                 return E("gnx_chain_block_forward_narrow", (), (), fl, ("chain_narrow", "in_dims", "widths", "R"))
             return E("gnx_chain_block_forward", (), (), fl, ("chain", "in_dims", "widths", "R"), "gnx_chain_block_workspace_bytes")
@@ -1116,6 +1119,11 @@ class GNBlock:
     `narrow_chain` (gnx_chain_block_forward_narrow): each update-function Chain whose input and layer widths are at most 32 runs its forward in
     one kernel (a row per lane through all layers), the others as before.  The pullback recomputes its activations and does not change.
 
+    `wave_chain` (gnx_chain_block_forward_wave; wins over `narrow_chain` on float32 features in test mode, changes nothing on bfloat16 features
+    or under an active chain Dropout): where the whole block is inside the wave rule (include/gnx.h: narrow edge and node functions, no node with
+    more in-edges than a wave tile holds) the edge and the node function run in one wave-per-tile kernel and the graph function from its partial
+    rows — ef' and nf' bit for bit `narrow_chain`'s; elsewhere the call is `narrow_chain`'s.  The pullback is the one the other switches select.
+
     `narrow_chain_backward` (gnx_chain_block_backward_narrow; independent of `narrow_chain`): each update function inside its rule (include/gnx.h:
     the forward's rule and 64 KB of LDS for two waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled
     back in one kernel, a row per lane forward and back through all layers, with only what crosses levels recomputed into the workspace; the
@@ -1142,7 +1150,8 @@ class GNBlock:
     NotImplementedError.  Off: a differentiable call of a block whose chains hold a Dropout(p > 0) raises NotImplementedError."""
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
-                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False, chain_dropout=False):
+                 narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False, chain_dropout=False,
+                 wave_chain=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -1162,6 +1171,7 @@ class GNBlock:
         self.bf16_chain = bool(bf16_chain)
         self.native_chain_backward = bool(native_chain_backward)
         self.chain_dropout = bool(chain_dropout)
+        self.wave_chain = bool(wave_chain)
 
     def _c(self, keep):
         p = _lib.BlockParams()

@@ -15,6 +15,8 @@
 // (gnx_chain_narrow.hip: k_chain_mlp, a row per lane through all layers); a function outside that rule runs the launches above.
 // gnx_chain_block_forward_typed: either entry on bfloat16 features — where every function that runs is inside the rule, the same kernels reading
 // and writing bf16 rows (gnx_chain_narrow_bf16.hip); elsewhere fp32 copies around the fp32 entry (gnx_staging.h).
+// gnx_chain_block_forward_wave: the narrow entry with the edge and the node function in ONE wave-per-tile kernel and the graph function from that
+// kernel's partial rows (gnx_chain_wave.hip) where chain_wave_takes (gnx_chain_plan.h) holds; elsewhere the narrow entry's launches.
 #include <algorithm>
 
 #include "gnx_launchers.h"
@@ -215,14 +217,18 @@ struct ChainFwCall {
 // The forward's plan.  native: a bf16 call whose every running function is fused — one k_chain_mlp_bf16 launch each, three fp32 carves behind the
 // layout (chain_native_counts); any other bf16 call is staged: fp32 copies of its six tensors around the fp32 launches.  wide_tables: the
 // row-wise layers and a fused edge function read the matrix-core tables; the query builds them outside any capture.
+const char* const kFwWaveQuery = "workspace missing or smaller than gnx_chain_block_forward_wave_workspace_bytes()";
 const char* const kFwQuery[3] = {"workspace missing or smaller than gnx_chain_block_workspace_bytes()", "workspace missing or smaller than gnx_chain_block_forward_narrow_workspace_bytes()",
                                  "workspace missing or smaller than gnx_chain_block_forward_typed_workspace_bytes()"};
 struct ChainFwPlan : ChainPlan {
   bool native = false;
+  bool wave = false;  // the wave form runs (asked for through gnx_chain_block_forward_wave, and chain_wave_takes): partial rows at the workspace's head
   ChainWs w{};
-  ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool train = false)
+  ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool train = false, bool ask_wave = false)
       : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_FW, kFwQuery, train) {
     native = !rc && bf16 && narrow && chain_typed_native(sh, fused);
+    wave = !rc && ask_wave && narrow && !train && chain_wave_takes(sh, bf16, h->max_in_degree, h->wtile_e_cap);
+    if (ask_wave) query = kFwWaveQuery;
   }
   bool wide_tables() const { return chain_fw_reads_wide_tables(sh, fused); }
   void lay_out(const gnx_graphs* h) {  // (the inner block's query builds what its edge update reads of the handle)
@@ -230,7 +236,8 @@ struct ChainFwPlan : ChainPlan {
     size_t counts[3];
     chain_native_counts(sh, counts);
     const int d[6] = {sh.de, sh.dn, sh.dg, sh.ow[0], sh.ow[1], sh.ow[2]};
-    sized(w.total, native ? stage_layout(w.total, counts, 3) : stage_features(w.total, h, sh.R, d, 6));
+    const size_t fp32_total = wave ? std::max(w.total, sizeof(float) * chain_wave_partial_floats(sh, h->n_wtiles())) : w.total;
+    sized(fp32_total, native ? stage_layout(fp32_total, counts, 3) : stage_features(fp32_total, h, sh.R, d, 6));
   }
 };
 
@@ -246,6 +253,7 @@ int32_t chain_forward_fp32(const ChainFwCall& c, ChainFwPlan& pl, const float* e
   if ((rc = pl.lnf.fill(F(w.ident), s))) return rc;
   const gnx_chain_block_params* p = pl.p;
   const unsigned fused = pl.fused;
+  if (pl.wave) return launch_chain_wave(h, *p, pl.sh, ef, nf, gf, ef_out, nf_out, gf_out, reinterpret_cast<float*>(base), c.R, s);
   const int de = p->de, dn = p->dn, dg = p->dg, oe = pl.sh.ow[0], on = pl.sh.ow[1], og = pl.sh.ow[2], Kn = pl.sh.k0[1], Kg = pl.sh.k0[2];
   // ---- edge function (gnblock.jl:65): first Dense fused with getedgefninput, the rest row-wise ----
   if (fused & 1) {
@@ -308,8 +316,8 @@ int32_t chain_forward_native(const ChainFwCall& c, const ChainFwPlan& pl) {
 // One Chain forward call: validate and plan, the refusals that read nothing of the handle but its counts — NULL features, bf16 alignment — the
 // layout, the workspace refusal, the plan's tables; then the plan's form.  A staged bf16 call widens into the workspace, runs the fp32 launches on
 // the copies and rounds the outputs.
-int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false) {
-  ChainFwPlan pl(c.h, c.p, c.R, c.elem, narrow, train);
+int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false, bool wave = false) {
+  ChainFwPlan pl(c.h, c.p, c.R, c.elem, narrow, train, wave);
   if (pl.rc) return pl.rc;
   if (train) pl.query = "workspace missing or smaller than gnx_chain_block_forward_train_workspace_bytes()";
   const hipStream_t s = (hipStream_t)c.stream;
@@ -334,8 +342,8 @@ int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false) {
 }
 
 // a _workspace_bytes entry: the plan's total, and the plan's tables built here, outside any capture (a failure resurfaces in the call)
-size_t chain_fw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool train = false) {
-  ChainFwPlan pl(h, p, R, elem, narrow, train);
+size_t chain_fw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool train = false, bool wave = false) {
+  ChainFwPlan pl(h, p, R, elem, narrow, train, wave);
   if (pl.rc) return 0;
   pl.lay_out(h);
   if (pl.wide_tables()) (void)gnx_ensure_wide_tables(h);
@@ -366,6 +374,20 @@ size_t gnx_chain_block_forward_narrow_workspace_bytes(const gnx_graphs* h, const
 int32_t gnx_chain_block_forward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
                                        float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
   return chain_fw_run(ChainFwCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true);
+}
+
+// gnx_chain_block_forward_wave: the narrow entry, its plan asked for the wave form
+int32_t gnx_chain_block_forward_wave_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return ChainFwPlan(h, p, R, GNX_ELEM_F32, true, false, true).wave ? 1 : 0;  // (the constructor reads the handle's counts alone)
+}
+
+size_t gnx_chain_block_forward_wave_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return chain_fw_query(h, p, R, GNX_ELEM_F32, true, false, true);
+}
+
+int32_t gnx_chain_block_forward_wave(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
+                                     float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  return chain_fw_run(ChainFwCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true, false, true);
 }
 
 // gnx_chain_block_forward_typed: either entry above on fp32 or bf16 features (narrow selects which one the call mirrors)

@@ -154,6 +154,42 @@ inline unsigned chain_fused_mask(const ChainShape& s, ChainRule rule) {
   return m;
 }
 
+// ---- the wave form (gnx_chain_block_forward_wave; gnx_chain_wave.hip): the edge and the node function in one wave-per-tile kernel ----
+constexpr int kChainWaveLdsFloats = 16384;  // both functions' parameters + every wave's ef' rows: 64 KB
+// floats between two ef' rows of a wave's LDS slice: odd, so that 64 lanes on 64 different rows of one column meet in no bank
+constexpr int chain_wave_stride(int oe) { return oe | 1; }
+// waves per workgroup: 4 where the parameters of both functions and four slices of [cap][stride(oe)] floats fit the LDS, else 2; 0: not even 2
+inline int chain_wave_waves(const ChainShape& s, int cap) {
+  const size_t par = chain_narrow_lds_floats(*s.ch[0], s.k0[0]) + chain_narrow_lds_floats(*s.ch[1], s.k0[1]);
+  const size_t slice = (size_t)cap * chain_wave_stride(s.ow[0]);
+  if (slice == 0 || par > kChainWaveLdsFloats) return 0;
+  const size_t fit = (kChainWaveLdsFloats - par) / slice;
+  return fit >= 4 ? 4 : (fit >= 2 ? 2 : 0);
+}
+// The class CUT from the wave rule: register width 32 (an input or layer width of the edge or the node function beyond 16) on a batch of SEVERAL
+// graphs.  Measured (profiles/chain_wave.json, whole calls, cache-cold, against the parent's narrow entry): k_chain_wave<32> takes 179 VGPRs
+// (two waves per SIMD) and on the 512-graph 1M-edge batch its three cases were slower than the parent beyond its spread — 0.207 against 0.107 ms
+// (spread 0.004), 0.388 against 0.199 (0.005), 0.265 against 0.141 (0.006).  On the one-graph 1M-edge batch the same cases took 0.188 against
+// 3.278 ms, 0.352 against 3.354, 0.241 against 3.294: there the class stays.  Register width 8 passed on both batches (0.066 against 0.077 ms,
+// 0.075 against 2.106); register width 16 and the two-wave classes were not measured.
+inline bool chain_wave_cut(const ChainShape& s) {
+  return std::max({s.k0[0], s.k0[1], s.maxw[0], s.maxw[1]}) > 16 && s.trows[2] > 1;
+}
+// The rule (include/gnx.h states it).  `s`: the shape of the caller's own parameters; bf16: the call's features; max_in_degree / cap: the handle's
+// largest in-degree and wave-tile edge cap — every wave tile is ONE chunk of at most `cap` edges exactly when no node has more in-edges.
+inline bool chain_wave_takes(const ChainShape& s, bool bf16, int64_t max_in_degree, int cap) {
+  if (bf16 || cap <= 0 || s.trows[0] == 0 || s.ow[0] <= 0 || s.ow[1] <= 0) return false;
+  for (int t = 0; t < 3; ++t)
+    if (chain_has_dropout(*s.ch[t])) return false;
+  if (!chain_narrow_takes(*s.ch[0], s.k0[0], s.trows[0]) || !chain_narrow_takes(*s.ch[1], s.k0[1], s.trows[1])) return false;
+  if (s.ch[2]->n_layers > 0 && !chain_narrow_takes(*s.ch[2], s.k0[2], s.trows[2])) return false;
+  return max_in_degree <= cap && chain_wave_waves(s, cap) >= 2 && !chain_wave_cut(s);
+}
+// its partial rows: R x wave tiles x (oe + on) floats at the head of the workspace (a block without a graph function writes none)
+inline size_t chain_wave_partial_floats(const ChainShape& s, int64_t n_wtiles) {
+  return s.ow[2] > 0 ? (size_t)s.R * (size_t)n_wtiles * (size_t)(s.ow[0] + s.ow[1]) : 0;
+}
+
 // bfloat16 features, the forward's native path: every update function with an output and rows to run on is inside the fused rule — then each
 // runs as one k_chain_mlp_bf16 launch on the bf16 rows and nothing of the block is widened or rounded by a pass of its own
 inline bool chain_typed_native(const ChainShape& s, unsigned fused) {

@@ -417,6 +417,28 @@ GNX_API size_t gnx_chain_block_forward_narrow_workspace_bytes(const gnx_graphs* 
 GNX_API int32_t gnx_chain_block_forward_narrow(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
                                        int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out, void* workspace, size_t workspace_bytes,
                                        uint32_t flags, void* stream);
+/* The narrow entry with the edge and the node function in ONE kernel, one wavefront per wave tile (a contiguous node range of one graph, at most
+ * 64 nodes, and its contiguous in-edges, at most the handle's wave-tile edge cap, 128 by default): ef' goes to memory once and stays in the wave's
+ * LDS, the node lanes sum it from there in CSC order, and each tile leaves one row [sum ef' ; sum nf'] from which a finishing launch (one workgroup
+ * per graph) runs the graph function — no per-graph reduction over the E and N rows, no input rows of the node or graph function in memory.
+ * The rule, for the whole block (_applies returns 1; 0 elsewhere and on bad arguments): float32 features, test mode (no Dropout entry in any
+ * chain); E > 0 and non-zero output widths of the edge and the node function; the edge and the node function inside
+ * gnx_chain_block_forward_narrow's rule (a LayerNorm as the edge function's first layer included), the graph function absent (no layers) or
+ * inside it; no node with more in-edges than the wave-tile edge cap; and LDS: par + 2 * cap * (oe | 1) <= 16384 floats (64 KB), par the
+ * zero-padded parameter floats of the edge and the node function together — four waves per workgroup where four such slices fit, else two.
+ * One class is cut, measured slower than the narrow entry: an input or layer width of the edge or the node function beyond 16 (the kernel's
+ * 32-wide instantiation) on a batch of more than one graph.
+ * A block outside the rule runs gnx_chain_block_forward_narrow's launches unchanged, bit for bit.
+ * Bits inside the rule: ef' and nf' are those of gnx_chain_block_forward_narrow (the same per-row arithmetic, the same CSC-order sums); gf' sums
+ * the tiles' rows in another (fixed) order: within the library's 1e-5 bound of it, the same bits from call to call whatever the workspace held.
+ * _workspace_bytes: max(gnx_chain_block_forward_narrow_workspace_bytes, 4 * R * wave tiles * (oe + on)) inside the rule with a graph function,
+ * else the narrow entry's; it builds the handle's tables the call reads, so call it outside a stream capture.  Under the profiler the block
+ * launch reports as k_rows_gemm_chain_e, the finishing launch as k_rows_gemm_chain_g.  Arguments and refusals as gnx_chain_block_forward. */
+GNX_API int32_t gnx_chain_block_forward_wave_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API size_t gnx_chain_block_forward_wave_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API int32_t gnx_chain_block_forward_wave(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                     int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out, void* workspace, size_t workspace_bytes,
+                                     uint32_t flags, void* stream);
 /* Either Chain forward on float32 or bfloat16 features.  `elem` (GNX_ELEM_*) applies to the three feature inputs and the three outputs; weights
  * stay float32.  `narrow` (0 or 1) selects the entry the call mirrors: gnx_chain_block_forward (0) or gnx_chain_block_forward_narrow (1).
  * GNX_ELEM_F32 IS the mirrored entry: same validation, same workspace size, same bits.  Any other elem than F32 / BF16: the call returns

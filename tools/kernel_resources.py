@@ -193,6 +193,18 @@ def _rec_chain_train_narrow(f, res, twin):
     return rec
 
 
+def _rec_chain_wave(f, res, twin):
+    r, narrow = res(), twin("chain_narrow")["srcs"]
+    rec = dict(what="k_chain_wave<W> / k_chain_graph_wave<W> per register width" + REMARKS, box=BOX, file_flags=file_flags(f["file"]),
+               lds_budget_bytes=f["LDS_BUDGET_BYTES"], kernels={k: {str(w): r[k][w] for w in WMAX} for k in f["KERNEL_NAMES"]},
+               k_chain_mlp_edge_vgpr={str(w): narrow["edge"][str(w)]["vgpr"] for w in WMAX})
+    bad = [f"{k}/{w}" for k in f["KERNEL_NAMES"] for w in WMAX if r[k][w]["scratch"] or r[k][w]["lds_static"]]
+    rec["instantiations_with_scratch_or_static_lds"] = bad
+    rec["note"] = "one register width per launch (three instantiations per kernel): the edge and the node phase follow each other in one wave, so a " \
+                  "width per function would not lower the registers of the wider phase"
+    return rec
+
+
 def _chain(kernel, file, lds_budget, **more):
     """a Chain kernel k<WMAX, SRC> of one file: resources() is {src: {WMAX: {...}}}; the LDS is dynamic (at most LDS_BUDGET_BYTES)"""
     return dict(file=file, kernel=kernel, name=r"_ZN3gnx\d+" + kernel + r"ILi(\d+)ELi(\d+)EEEv", key=lambda m: (SRC[int(m.group(2))], int(m.group(1))),
@@ -223,6 +235,9 @@ FAMILIES = {
     "chain_narrow_bf16": _chain("k_chain_mlp_bf16", "gnx_chain_narrow_bf16.hip", 4 * 10240),
     # the same text as the fp32 pullback (csrc/gnx_chain_bw_kernel.h), whose 32-wide kernel takes 235 VGPRs at 2 waves per SIMD
     "chain_bw_narrow_bf16": _chain("k_chain_mlp_bw_bf16", "gnx_chain_bw_narrow_bf16.hip", 4 * 16384, twin="chain_bw_narrow"),
+    # the wave form of the Chain forward: both functions' parameters and every wave's ef' rows in LDS (kChainWaveLdsFloats: gnx_chain_plan.h)
+    "chain_wave": dict(file="gnx_chain_wave.hip", name=r"_ZN3gnx\d+(k_chain_wave|k_chain_graph_wave)ILi(\d+)EEEv", key=lambda m: (m.group(1), int(m.group(2))),
+                       fields=STATIC, record=_rec_chain_wave, KERNEL_NAMES=("k_chain_wave", "k_chain_graph_wave"), LDS_BUDGET_BYTES=4 * 16384),
     # the two Chain training kernels (the layer code of chain_narrow / chain_bw_narrow with the Dropout op), 18 instantiations: none may use scratch
     # (include/gnx.h: a class that does is cut from the training rule); the record carries the test-mode twins' VGPRs next to each.
     # resources("chain_train_narrow", direction)
