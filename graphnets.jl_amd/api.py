@@ -945,9 +945,10 @@ def _entry(family, direction, elem, switches=(), record=False):
       block     forward    gnx_block_forward; bf16: gnx_block_forward_typed
                 backward   gnx_block_backward [_fused with `fused_backward`] [_typed on bf16]; gnx_block_backward_narrow with `narrow_backward`
                            (which wins over `fused_backward`; either element type); bf16 needs `bf16_backward`
-      chain     forward    an active record: gnx_chain_block_forward_train (narrow = `narrow_chain`; fp32 only); bf16: gnx_chain_block_forward_typed
-                           (narrow = `narrow_chain`; needs `bf16_chain`); else gnx_chain_block_forward_wave with `wave_chain` (which wins over
-                           `narrow_chain`), gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
+      chain     forward    an active record: gnx_chain_block_forward_train (narrow = `narrow_chain`; fp32 only); bf16 (needs `bf16_chain`):
+                           gnx_chain_block_forward_wave_typed with `wave_chain`, else gnx_chain_block_forward_typed (narrow = `narrow_chain`);
+                           fp32: gnx_chain_block_forward_wave with `wave_chain` (which wins over `narrow_chain`),
+                           gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
                 backward   (narrow = `narrow_chain_backward`) an active record: gnx_chain_block_backward_train; bf16 (needs `bf16_backward`):
                            gnx_chain_block_backward_narrow_typed with `native_chain_backward`, else gnx_chain_block_backward_typed; fp32:
                            gnx_chain_block_backward_narrow or gnx_chain_block_backward
@@ -982,6 +983,8 @@ def _entry(family, direction, elem, switches=(), record=False):
             n = int(on("narrow_chain"))
             if record:
                 return E("gnx_chain_block_forward_train", (n,), ("drop",), (n, "flags"), ("chain_train", n, "in_dims", "widths", "R"))
+            if bf16 and on("wave_chain"):
+                return E("gnx_chain_block_forward_wave_typed", (elem,), (elem,), fl, ("chain_wave_bf16", "in_dims", "widths", "R"))
             if bf16:  # (mirrors the entry `narrow_chain` selects)
                 return E("gnx_chain_block_forward_typed", (elem, n), (elem,), (n, "flags"), ("chain_bf16", bool(n), "in_dims", "widths", "R"))
             if on("wave_chain"):
@@ -1119,10 +1122,13 @@ class GNBlock:
     `narrow_chain` (gnx_chain_block_forward_narrow): each update-function Chain whose input and layer widths are at most 32 runs its forward in
     one kernel (a row per lane through all layers), the others as before.  The pullback recomputes its activations and does not change.
 
-    `wave_chain` (gnx_chain_block_forward_wave; wins over `narrow_chain` on float32 features in test mode, changes nothing on bfloat16 features
-    or under an active chain Dropout): where the whole block is inside the wave rule (include/gnx.h: narrow edge and node functions, no node with
-    more in-edges than a wave tile holds) the edge and the node function run in one wave-per-tile kernel and the graph function from its partial
-    rows — ef' and nf' bit for bit `narrow_chain`'s; elsewhere the call is `narrow_chain`'s.  The pullback is the one the other switches select.
+    `wave_chain` (gnx_chain_block_forward_wave; wins over `narrow_chain` in test mode, changes nothing under an active chain Dropout): where the
+    whole block is inside the wave rule (include/gnx.h: narrow edge and node functions, no node with more in-edges than a wave tile holds) the
+    edge and the node function run in one wave-per-tile kernel and the graph function from its partial rows — ef' and nf' bit for bit
+    `narrow_chain`'s; elsewhere the call is `narrow_chain`'s.  On bfloat16 features (with `bf16_chain`: gnx_chain_block_forward_wave_typed) the
+    same kernel reads the bf16 rows and writes each bf16 output once, bit for bit to_bf16 of the float32 call on the widened inputs, with no
+    float32 copy of anything edge- or node-sized; outside that entry's rule the call is `bf16_chain` with `narrow_chain`.  The pullback is the
+    one the other switches select.
 
     `narrow_chain_backward` (gnx_chain_block_backward_narrow; independent of `narrow_chain`): each update function inside its rule (include/gnx.h:
     the forward's rule and 64 KB of LDS for two waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled

@@ -17,6 +17,8 @@
 // and writing bf16 rows (gnx_chain_narrow_bf16.hip); elsewhere fp32 copies around the fp32 entry (gnx_staging.h).
 // gnx_chain_block_forward_wave: the narrow entry with the edge and the node function in ONE wave-per-tile kernel and the graph function from that
 // kernel's partial rows (gnx_chain_wave.hip) where chain_wave_takes (gnx_chain_plan.h) holds; elsewhere the narrow entry's launches.
+// gnx_chain_block_forward_wave_typed: that entry on fp32 or bf16 features — bf16 inside chain_wave_typed_takes: the same two launches reading and
+// writing bf16 rows (gnx_chain_wave_bf16.hip), the partial rows the whole workspace; bf16 elsewhere: gnx_chain_block_forward_typed(narrow = 1).
 #include <algorithm>
 
 #include "gnx_launchers.h"
@@ -217,18 +219,22 @@ struct ChainFwCall {
 // The forward's plan.  native: a bf16 call whose every running function is fused — one k_chain_mlp_bf16 launch each, three fp32 carves behind the
 // layout (chain_native_counts); any other bf16 call is staged: fp32 copies of its six tensors around the fp32 launches.  wide_tables: the
 // row-wise layers and a fused edge function read the matrix-core tables; the query builds them outside any capture.
-const char* const kFwWaveQuery = "workspace missing or smaller than gnx_chain_block_forward_wave_workspace_bytes()";
+const char* const kFwWaveQuery[2] = {"workspace missing or smaller than gnx_chain_block_forward_wave_workspace_bytes()",
+                                     "workspace missing or smaller than gnx_chain_block_forward_wave_typed_workspace_bytes()"};
 const char* const kFwQuery[3] = {"workspace missing or smaller than gnx_chain_block_workspace_bytes()", "workspace missing or smaller than gnx_chain_block_forward_narrow_workspace_bytes()",
                                  "workspace missing or smaller than gnx_chain_block_forward_typed_workspace_bytes()"};
 struct ChainFwPlan : ChainPlan {
   bool native = false;
-  bool wave = false;  // the wave form runs (asked for through gnx_chain_block_forward_wave, and chain_wave_takes): partial rows at the workspace's head
+  // the wave form runs (asked for through gnx_chain_block_forward_wave / _wave_typed, and chain_wave_takes / chain_wave_typed_takes): partial rows
+  // at the workspace's head — on bf16 features nothing else
+  bool wave = false;
   ChainWs w{};
   ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool train = false, bool ask_wave = false)
       : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_FW, kFwQuery, train) {
     native = !rc && bf16 && narrow && chain_typed_native(sh, fused);
-    wave = !rc && ask_wave && narrow && !train && chain_wave_takes(sh, bf16, h->max_in_degree, h->wtile_e_cap);
-    if (ask_wave) query = kFwWaveQuery;
+    wave = !rc && ask_wave && narrow && !train &&
+           (bf16 ? chain_wave_typed_takes(sh, h->max_in_degree, h->wtile_e_cap) : chain_wave_takes(sh, false, h->max_in_degree, h->wtile_e_cap));
+    if (ask_wave) query = kFwWaveQuery[bf16];
   }
   bool wide_tables() const { return chain_fw_reads_wide_tables(sh, fused); }
   void lay_out(const gnx_graphs* h) {  // (the inner block's query builds what its edge update reads of the handle)
@@ -236,6 +242,11 @@ struct ChainFwPlan : ChainPlan {
     size_t counts[3];
     chain_native_counts(sh, counts);
     const int d[6] = {sh.de, sh.dn, sh.dg, sh.ow[0], sh.ow[1], sh.ow[2]};
+    if (wave && bf16) {  // the partial rows alone: no fp32 layout, no carve behind it
+      const size_t partial_bytes = chain_wave_typed_bytes(sh, h->n_wtiles());
+      sized(partial_bytes, stage_layout(partial_bytes, counts, 0));
+      return;
+    }
     const size_t fp32_total = wave ? std::max(w.total, sizeof(float) * chain_wave_partial_floats(sh, h->n_wtiles())) : w.total;
     sized(fp32_total, native ? stage_layout(fp32_total, counts, 3) : stage_features(fp32_total, h, sh.R, d, 6));
   }
@@ -334,6 +345,7 @@ int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false, bool
   if (pl.wide_tables() && (rc = gnx_ensure_wide_tables(c.h, s))) return rc;
   auto cf = [](const void* q) { return static_cast<const float*>(q); };
   if (!pl.bf16) return chain_forward_fp32(c, pl, cf(c.ef), cf(c.nf), cf(c.gf), static_cast<float*>(c.ef_out), static_cast<float*>(c.nf_out), static_cast<float*>(c.gf_out));
+  if (pl.wave) return launch_chain_wave_bf16(c.h, *pl.p, pl.sh, c.ef, c.nf, c.gf, c.ef_out, c.nf_out, c.gf_out, static_cast<float*>(c.ws), c.R, s);
   if (pl.native) return chain_forward_native(c, pl);
   if ((rc = stage_widen(pl.st, c.ws, bufs, 0, 3, s))) return rc;
   auto at = [&](int i) { return pl.st.n[i] > 0 ? pl.st.at(c.ws, i) : nullptr; };
@@ -388,6 +400,21 @@ size_t gnx_chain_block_forward_wave_workspace_bytes(const gnx_graphs* h, const g
 int32_t gnx_chain_block_forward_wave(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
                                      float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
   return chain_fw_run(ChainFwCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true, false, true);
+}
+
+// gnx_chain_block_forward_wave_typed: the wave entry on fp32 or bf16 features; bf16 outside chain_wave_typed_takes: the typed entry with narrow = 1
+int32_t gnx_chain_block_forward_wave_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  return elem_ok(elem) && ChainFwPlan(h, p, R, elem, true, false, true).wave ? 1 : 0;
+}
+
+size_t gnx_chain_block_forward_wave_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  return elem_ok(elem) ? chain_fw_query(h, p, R, elem, true, false, true) : 0;
+}
+
+int32_t gnx_chain_block_forward_wave_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                           int64_t R, void* ef_out, void* nf_out, void* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  if (!elem_ok(elem)) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  return chain_fw_run(ChainFwCall{h, p, elem, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true, false, true);
 }
 
 // gnx_chain_block_forward_typed: either entry above on fp32 or bf16 features (narrow selects which one the call mirrors)

@@ -190,6 +190,32 @@ inline size_t chain_wave_partial_floats(const ChainShape& s, int64_t n_wtiles) {
   return s.ow[2] > 0 ? (size_t)s.R * (size_t)n_wtiles * (size_t)(s.ow[0] + s.ow[1]) : 0;
 }
 
+// ---- the wave form on bfloat16 features (gnx_chain_block_forward_wave_typed; gnx_chain_wave_bf16.hip) ----
+// A wave's LDS slice holds its ef' rows [cap][stride(oe)] and then, written over them, its nf' rows [64][stride(on)] on their way to the flat store
+inline size_t chain_wave_typed_slice(const ChainShape& s, int cap) {
+  return std::max((size_t)cap * chain_wave_stride(s.ow[0]), (size_t)64 * chain_wave_stride(s.ow[1]));
+}
+// waves per workgroup: chain_wave_waves with that slice
+inline int chain_wave_typed_waves(const ChainShape& s, int cap) {
+  const size_t par = chain_narrow_lds_floats(*s.ch[0], s.k0[0]) + chain_narrow_lds_floats(*s.ch[1], s.k0[1]);
+  if (cap <= 0 || s.ow[0] <= 0 || par > kChainWaveLdsFloats) return 0;
+  const size_t fit = (kChainWaveLdsFloats - par) / chain_wave_typed_slice(s, cap);
+  return fit >= 4 ? 4 : (fit >= 2 ? 2 : 0);
+}
+// The rule: the fp32 form's conditions with the larger slice in the LDS term.  Measured (profiles/chain_wave_bf16.json, whole calls, cache-cold,
+// against the parent's gnx_chain_block_forward_typed(narrow = 1)): register width 8 at four waves on the 512-graph 1M-edge batch 0.071 against
+// 0.081 ms (spread 0.005) and on the one-graph batch 0.081 against 2.125; register width 32 at four waves on the one-graph batch 0.201 against
+// 3.304 ms, 0.364 against 3.397, 0.255 against 3.326 — every measured class meets the bar, none is cut for its own figures.  chain_wave_cut
+// (register width 32 on several graphs) applies as it stands, inherited from the fp32 form's measurement and NOT measured on bf16 features;
+// register width 16 and the two-wave classes were not measured either.
+inline bool chain_wave_typed_takes(const ChainShape& s, int64_t max_in_degree, int cap) {
+  return chain_wave_takes(s, false, max_in_degree, cap) && chain_wave_typed_waves(s, cap) >= 2;
+}
+// its workspace: the partial rows alone (256 bytes where there are none: a query's 0 is a refusal)
+inline size_t chain_wave_typed_bytes(const ChainShape& s, int64_t n_wtiles) {
+  return std::max((size_t)256, sizeof(float) * chain_wave_partial_floats(s, n_wtiles));
+}
+
 // bfloat16 features, the forward's native path: every update function with an output and rows to run on is inside the fused rule — then each
 // runs as one k_chain_mlp_bf16 launch on the bf16 rows and nothing of the block is widened or rounded by a pass of its own
 inline bool chain_typed_native(const ChainShape& s, unsigned fused) {

@@ -191,6 +191,10 @@ int32_t launch_chain_wave(const gnx_graphs* h, const gnx_chain_block_params& p, 
 // (the pullback's recompute); out32: the same rows unrounded in fp32, or nullptr.  The caller asked chain_narrow_takes.
 int32_t launch_chain_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
                                  void* out, float* out32, int64_t R, hipStream_t s, const char* name);
+// ---- gnx_chain_wave_bf16.hip: launch_chain_wave with bf16 features and outputs (gnx_chain_block_forward_wave_typed).  The caller asked
+//      chain_wave_typed_takes; each bf16 output is written once, the partial rows are the call's whole workspace ----
+int32_t launch_chain_wave_bf16(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const void* ef, const void* nf, const void* gf, void* ef_out,
+                               void* nf_out, void* gf_out, float* partials, int64_t R, hipStream_t s);
 
 // ---- gnx_chain_bw_narrow.hip: the pullback of one update function of a Chain block in one kernel (gnx_chain_block_backward_narrow) ----
 struct ChainBwNarrowIo {

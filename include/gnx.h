@@ -464,6 +464,31 @@ GNX_API size_t gnx_chain_block_forward_typed_workspace_bytes(const gnx_graphs* h
 GNX_API int32_t gnx_chain_block_forward_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf,
                                               const void* gf, int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace,
                                               size_t workspace_bytes, int32_t narrow, uint32_t flags, void* stream);
+/* gnx_chain_block_forward_wave on float32 or bfloat16 features.  `elem` (GNX_ELEM_*) applies to the three feature inputs and the three outputs.
+ * GNX_ELEM_F32 IS gnx_chain_block_forward_wave: same validation, same workspace size, same bits; _applies returns that entry's answer.  Any
+ * other elem than F32 / BF16: the call returns GNX_ERR_INVALID_ARG before any GPU work, the queries return 0.  A bf16 buffer must be 4-byte
+ * aligned (else GNX_ERR_INVALID_ARG before any GPU work); rows and tile runs may start 2-byte aligned, which is all the kernels assume.
+ * GNX_ELEM_BF16 inside the rule (_applies returns 1): the wave form's two launches read the bf16 rows themselves (one 16-bit load per element,
+ * widened exactly) and write each bf16 output exactly once — a tile's ef' and nf' are contiguous runs of the outputs, stored from the wave's LDS
+ * slice as packed dwords across the lanes with the run's odd first / last element as a 16-bit store, each element rounded to nearest even once;
+ * the finishing launch reads gf as bf16 and rounds gf' once (csrc/gnx_chain_wave_bf16.hip).  No pass of its own widens or rounds anything and no
+ * fp32 copy of anything edge- or node-sized exists.  Finite data: the three outputs are bit for bit to_bf16(gnx_chain_block_forward_wave on the
+ * exactly widened inputs).  The rule: gnx_chain_block_forward_wave's, the float32 condition dropped, with a larger LDS slice per wave — the nf'
+ * rows pass through it on their way out: par + 2 * max(cap * (oe | 1), 64 * (on | 1)) <= 16384 floats, four waves per workgroup where four
+ * such slices fit, else two.  The class that entry cuts (an input or layer width of the edge or the node function beyond 16 on a batch of more
+ * than one graph) is cut here too, inherited from its measurement, not measured on bf16 features; see README.md ("Wave-per-tile Chain block on
+ * bfloat16 features") for what was measured.  _workspace_bytes inside the rule: the partial rows alone, max(256, 4 * R * wave tiles * (oe + on))
+ * with a graph function, else 256 — never more than gnx_chain_block_forward_wave_workspace_bytes for the same block.
+ * GNX_ELEM_BF16 outside the rule (_applies returns 0): the call runs gnx_chain_block_forward_typed(narrow = 1)'s launches on that entry's
+ * workspace size and returns its bits.
+ * The queries build the handle's tables (call them outside a stream capture); the call allocates nothing, does not synchronise and uses one
+ * stream.  Under the profiler the launches report as k_rows_gemm_chain_e and k_rows_gemm_chain_g.  Refusals as gnx_chain_block_forward's, the
+ * workspace one naming gnx_chain_block_forward_wave_typed_workspace_bytes() on bf16 features. */
+GNX_API int32_t gnx_chain_block_forward_wave_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_chain_block_forward_wave_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API int32_t gnx_chain_block_forward_wave_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf,
+                                                   const void* gf, int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace,
+                                                   size_t workspace_bytes, uint32_t flags, void* stream);
 
 /* ---- backward of the block: what a Zygote `rrule` / torch autograd function for (m::GNBlock)(x) needs.
  * Inputs: the forward's inputs (ef, nf, gf), its outputs (ef_out, nf_out, gf_out) and the upstream gradients with the
