@@ -919,7 +919,7 @@ def _ptr0(t):
 # which C entry a call of a GNBlock / GNCore reaches: one table, plain data
 # ------------------------------------------------------------------------------------------------------------
 _SWITCHES = ("bf16", "bf16_backward", "fused_backward", "narrow_backward", "narrow_chain", "narrow_chain_backward", "bf16_chain", "native_chain_backward",
-             "chain_dropout", "typed_dropout", "wave_chain")
+             "chain_dropout", "typed_dropout", "wave_chain", "wave_chain_backward")
 _Entry = collections.namedtuple("_Entry", "query query_tail call head tail key")
 _CHAIN_DROPOUT_IS_TEST_MODE = ("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
                                "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
@@ -951,6 +951,7 @@ def _entry(family, direction, elem, switches=(), record=False):
                            gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
                 backward   (narrow = `narrow_chain_backward`) an active record: gnx_chain_block_backward_train; bf16 (needs `bf16_backward`):
                            gnx_chain_block_backward_narrow_typed with `native_chain_backward`, else gnx_chain_block_backward_typed; fp32:
+                           gnx_chain_block_backward_wave with `wave_chain_backward` (which wins over `narrow_chain_backward`), else
                            gnx_chain_block_backward_narrow or gnx_chain_block_backward
       core      forward    an active record: gnx_core_forward_train_typed with `typed_dropout`, else gnx_core_forward_train (fp32 only); no record:
                            gnx_core_forward, bf16: gnx_core_forward_typed
@@ -1003,6 +1004,8 @@ def _entry(family, direction, elem, switches=(), record=False):
             return E("gnx_chain_block_backward_narrow_typed", (elem,), (elem,))
         if bf16:  # (mirrors the pullback `narrow_chain_backward` selects)
             return E("gnx_chain_block_backward_typed", (elem, n), (elem,), (n,))
+        if on("wave_chain_backward"):
+            return E("gnx_chain_block_backward_wave")
         return E("gnx_chain_block_backward_narrow" if n else "gnx_chain_block_backward")
     if fw:
         if record and on("typed_dropout"):
@@ -1135,6 +1138,10 @@ class GNBlock:
     back in one kernel, a row per lane forward and back through all layers, with only what crosses levels recomputed into the workspace; the
     others as before.  The gradients are within the generic pullback's error of the exact ones, not its bits.
 
+    `wave_chain_backward` (gnx_chain_block_backward_wave; wins over `narrow_chain_backward`, requires no other switch; float32 features in test
+    mode): where the whole block is inside the pullback's wave rule (include/gnx.h) one wavefront per wave tile pulls back the node and the
+    edge function in one kernel, with ef', nf' and the node-to-edge gradient columns in LDS; elsewhere the call is `narrow_chain_backward`'s.
+
     `bf16_chain` (gnx_chain_block_forward_typed, gnx_chain_block_backward_typed): lets a block whose update functions are Chains run on bfloat16
     features: bf16 outputs, bit for bit the fp32 entry that `narrow_chain` selects on the widened inputs, rounded once.  With `narrow_chain` and
     every update function inside the narrow rule the fused kernels read and write the bf16 rows themselves; elsewhere fp32 copies go around the
@@ -1157,7 +1164,7 @@ class GNBlock:
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
                  narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False, chain_dropout=False,
-                 wave_chain=False):
+                 wave_chain=False, wave_chain_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -1178,6 +1185,7 @@ class GNBlock:
         self.native_chain_backward = bool(native_chain_backward)
         self.chain_dropout = bool(chain_dropout)
         self.wave_chain = bool(wave_chain)
+        self.wave_chain_backward = bool(wave_chain_backward)
 
     def _c(self, keep):
         p = _lib.BlockParams()

@@ -1366,15 +1366,28 @@ struct ChainBwPlan : ChainPlan {
   ChainBwLayout L{};
   bool native = false;
   ChainBwNativeWs nw{};
-  ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false)
+  // the wave form runs (asked for through gnx_chain_block_backward_wave, and chain_bw_wave_takes): its own layout, nothing of L
+  bool wave = false;
+  ChainBwWaveLayout WL{};
+  ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false,
+              bool ask_wave = false)
       : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery, train) {
     if (!rc && train) query = "workspace missing or smaller than gnx_chain_block_backward_train_workspace_bytes()";
+    if (!rc && ask_wave) {
+      wave = narrow && !train && !bf16 && chain_bw_wave_takes(sh, false, h->max_in_degree, h->wtile_e_cap, h->n_wtiles());
+      if (wave) query = "workspace missing or smaller than gnx_chain_block_backward_wave_workspace_bytes()";
+    }
     if (rc || !narrow_typed) return;
     native = chain_bw_typed_native(sh, fused, bf16);
     if (bf16) query = kBwNarrowTypedQuery;
   }
   void lay_out(const gnx_graphs* h) {
     if (rc || total) return;
+    if (wave) {
+      WL = chain_bw_wave_layout(sh, h->wtile_e_cap, h->n_wtiles());
+      base = total = WL.total;
+      return;
+    }
     const bool blk = !(fused & 1) && sh.ch[0]->n_layers > 0;  // the first Dense of a generic edge function: the one-layer block, forward and pullback
     L = chain_bw_layout(sh, fused, lnf.ident_floats(), blk ? gnx_block_workspace_bytes(h, &sh.edge_block, sh.R) : 0,
                         blk ? gnx_block_backward_workspace_bytes(h, &sh.edge_block, sh.R) : 0, BW_CH, dw_mfma_partial_floats);
@@ -1415,7 +1428,10 @@ struct ChainBwCtx {
   int32_t pull_layers(int t, int first, float* cur, float* other, const float* X0, int K0, float* g_first, float** result);
   void last_delta(int t, const float* upstream, float* out, const float* X0, int K0, int act_override);
   int32_t fused_level(int t, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2, ChainBwNarrowIo io, const char* name);
-  int32_t edge_fused(), edge_generic(), shares();
+  int32_t edge_fused(), edge_generic();
+  int32_t edge_cols(const float* dXe);              // d_nf and d_gf from the compact node / graph columns of the edge rows' input gradient
+  int32_t shares(int ld_n, int c0_n);               // dXn: rows of ld_n floats whose column c0_n is column oe of the node rows' input gradient
+  int32_t shares() { return shares(Kn, oe); }
 };
 
 dim3 chain_blocks(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
@@ -1577,9 +1593,12 @@ int32_t ChainBwCtx::fused_level(int t, const float* in0, int d0, const float* in
 int32_t ChainBwCtx::edge_fused() {
   const bool need_cols = (d_nf && dn > 0) || (d_gf && dg > 0);
   float* dXe = F(pl.L.dxe);
-  const int ldc = 2 * dn + dg;
   if (int32_t rc = fused_level(0, ef, de, nf, dn, gf, dg, ChainBwNarrowIo{g_ef_out, og > 0 ? dXg : nullptr, Kg, 0, on > 0 ? dXn : nullptr, Kn,
                                                                                            need_cols ? dXe : nullptr, de, d_ef && de > 0 ? d_ef : nullptr, nullptr}, "bw_delta_edge")) return rc;
+  return edge_cols(dXe);
+}
+int32_t ChainBwCtx::edge_cols(const float* dXe) {
+  const int ldc = 2 * dn + dg;
   if (d_nf && dn > 0) {
     ProfScope ps("bw_dnf", s);
     if (pl.native)  // (with the node function's share, which shares() then leaves out)
@@ -1622,17 +1641,57 @@ int32_t ChainBwCtx::edge_generic() {
 }
 
 // ---- the node / graph functions' own shares of d_nf, d_gf ----
-int32_t ChainBwCtx::shares() {
+int32_t ChainBwCtx::shares(int ld_n, int c0_n) {
   int32_t rc;
-  if (!pl.native && d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, Kn, oe, pl.sh.rows[1], dn, d_nf, 1, s))) return rc;
+  if (!pl.native && d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, ld_n, c0_n, pl.sh.rows[1], dn, d_nf, 1, s))) return rc;
   if (d_gf && dg > 0) {
     if (on > 0) {
       int64_t mn = 1;
       for (int64_t g = 0; g < h->G; ++g) mn = std::max(mn, h->h_node_off[g + 1] - h->h_node_off[g]);
-      colsum_graphs(dXn, false, dg, Kn, oe + dn, (int)h->N, h->d_node_off, mn, (int)h->G, (unsigned)R, part, d_gf, dg, 0, 1, s);
+      colsum_graphs(dXn, false, dg, ld_n, c0_n + dn, (int)h->N, h->d_node_off, mn, (int)h->G, (unsigned)R, part, d_gf, dg, 0, 1, s);
     }
     if (og > 0 && (rc = add_cols(dXg, Kg, oe + on, pl.sh.rows[2], dg, d_gf, 1, s))) return rc;
   }
+  return GNX_OK;
+}
+
+// The wave form (pl.wave): with a graph function the tiles' partial rows, the graph function's input rows from them and the graph level as in
+// the narrow pullback; then the node and the edge function's pullbacks in one wave-per-tile kernel, its finals, and the share launches as they
+// run after the narrow pullback's fused edge level — on the wave layout's carves (dXn compact: [R N][dn + dg]).
+int32_t chain_backward_wave(ChainBwCtx& x) {
+  const ChainBwPlan& pl = x.pl;
+  const ChainBwWaveLayout& W = pl.WL;
+  const gnx_graphs* h = x.h;
+  const hipStream_t s = x.s;
+  const int dn = x.dn, dg = x.dg, de = x.de, og = x.og;
+  float* const partials = x.F(W.partials);
+  float* const dXe = x.F(W.dxe);
+  x.Xg = x.F(W.Xg); x.dXg = x.F(W.dXg); x.dXn = x.F(W.dXn); x.part = x.F(W.part);
+  int32_t rc;
+  if (og > 0) {
+    { ProfScope ps("bw_chain_fw_e", s);
+      if ((rc = launch_chain_wave_partials(h, *pl.p, pl.sh, x.ef, x.nf, x.gf, partials, x.R, s))) return rc; }
+    { ProfScope ps("bw_chain_fw_g", s);
+      if ((rc = launch_chain_graph_rows_wave(h, pl.sh, partials, x.gf, x.Xg, x.R, s))) return rc; }
+    if ((rc = x.fused_level(2, x.Xg, x.Kg, nullptr, 0, nullptr, 0, ChainBwNarrowIo{x.g_gf_out, nullptr, 0, 0, nullptr, 0, x.dXg, 0, nullptr, nullptr}, "bw_delta"))) return rc;
+  }
+  const ChainBwWaveShape ws = chain_bw_wave_shape(pl.sh, h->wtile_e_cap, h->n_wtiles());
+  const bool want_e = chain_wants_grads(x.ch(0), x.gfn(0)), want_n = chain_wants_grads(x.ch(1), x.gfn(1));
+  const bool cols_e = (x.d_nf && dn > 0) || (x.d_gf && dg > 0);
+  float* const part_e = x.part;
+  float* const part_n = x.part + (size_t)ws.e.P * ws.nwg * (size_t)x.R;
+  { ProfScope ps("bw_delta_edge", s);
+    if ((rc = launch_chain_wave_bw(h, *pl.p, pl.sh, x.ef, x.nf, x.gf,
+                                   ChainWaveBwIo{x.g_ef_out, x.g_nf_out, og > 0 ? x.dXg : nullptr, x.Kg, x.d_ef && de > 0 ? x.d_ef : nullptr, cols_e ? dXe : nullptr,
+                                                 cols_e && dn + dg > 0 ? x.dXn : nullptr, want_e ? part_e : nullptr, want_n ? part_n : nullptr},
+                                   x.R, s))) return rc; }
+  ChainBwNarrowShape fe = ws.e, fn = ws.n;  // (the finals read nwg and part_off alone)
+  fe.nwg = fn.nwg = ws.nwg;
+  if (want_e && (rc = chain_bw_narrow_finals(x.ch(0), pl.sh.k0[0], fe, x.R, part_e, x.gfn(0), s))) return rc;
+  if (want_n && (rc = chain_bw_narrow_finals(x.ch(1), pl.sh.k0[1], fn, x.R, part_n, x.gfn(1), s))) return rc;
+  if ((rc = x.edge_cols(dXe))) return rc;
+  if ((rc = x.shares(dn + dg, 0))) return rc;
+  GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
 
@@ -1653,6 +1712,7 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   ChainBwCtx x{h, pl, pl.p, pl.lnf.init_grads(c.grads), cf(c.ef), cf(c.nf), cf(c.gf), cf(c.g_ef_out), cf(c.g_nf_out), cf(c.g_gf_out), mf(c.d_ef), mf(c.d_nf), mf(c.d_gf),
                c.R, c.stream, s, static_cast<char*>(c.ws), pl.p->de, pl.p->dn, pl.p->dg, pl.sh.ow[0], pl.sh.ow[1], pl.sh.ow[2], pl.sh.k0[1], pl.sh.k0[2],
                (int)h->E, (int)h->N, (int)h->G, (unsigned)c.R, pl.fused};
+  if (pl.wave) return chain_backward_wave(x);
   x.Xn = x.F(pl.L.Xn); x.Xg = x.F(pl.L.Xg); x.dXn = x.F(pl.L.dXn); x.dXg = x.F(pl.L.dXg); x.part = x.F(pl.L.part); x.wt = x.F(pl.L.wt);
   for (int i = 0; i < 3; ++i) x.gb[i] = x.F(pl.L.gbuf[i]);
   x.off2 = reinterpret_cast<int*>(x.base + pl.L.off2.off);
@@ -1694,9 +1754,9 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
 // came through gnx_chain_block_backward_narrow_typed, which alone may be native) on its own tensors; any other bf16 call lays out, checks its workspace, widens its
 // six inputs, runs the fp32 launches on the copies and rounds the three input gradients (gnx_staging.h); the parameter gradients are the fp32
 // pullback's own.
-int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = false, bool train = false) {
+int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = false, bool train = false, bool ask_wave = false) {
   if (!c.h || !c.p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow, narrow_typed, train);
+  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow, narrow_typed, train, ask_wave);
   if (pl.rc) return c.elem == GNX_ELEM_BF16 ? pl.rc : GNX_ERR_DIMS;  // (fp32: one code for every refused parameter set; gnx_last_error() holds the reason)
   const void* bufs[9] = {c.ef, c.nf, c.gf, c.g_ef_out, c.g_nf_out, c.g_gf_out, c.d_ef, c.d_nf, c.d_gf};
   int32_t rc;
@@ -1714,8 +1774,9 @@ int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = fals
 }
 
 // a _workspace_bytes entry: the plan's total; query_total builds what the pullback reads of the handle, outside any capture
-size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false) {
-  ChainBwPlan pl(h, p, R, elem, narrow, narrow_typed, train);
+size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false,
+                      bool ask_wave = false) {
+  ChainBwPlan pl(h, p, R, elem, narrow, narrow_typed, train, ask_wave);
   pl.lay_out(h);  // (nothing for refused parameters: the total stays 0)
   return query_total(h, pl.total);
 }
@@ -1746,6 +1807,21 @@ int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_chain_blo
                                         const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                                         float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   return chain_bw_run(ChainBwCall{h, p, GNX_ELEM_F32, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true);
+}
+
+// gnx_chain_block_backward_wave: the narrow pullback, its plan asked for the wave form (chain_bw_wave_takes); elsewhere the narrow entry's launches
+int32_t gnx_chain_block_backward_wave_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return ChainBwPlan(h, p, R, GNX_ELEM_F32, true, false, false, true).wave ? 1 : 0;  // (the constructor reads the handle's counts alone)
+}
+
+size_t gnx_chain_block_backward_wave_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return chain_bw_query(h, p, R, GNX_ELEM_F32, true, false, false, true);
+}
+
+int32_t gnx_chain_block_backward_wave(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                      const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
+                                      float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  return chain_bw_run(ChainBwCall{h, p, GNX_ELEM_F32, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true, false, false, true);
 }
 
 // gnx_chain_block_backward_typed: either pullback above (narrow selects which) on fp32 or bf16 features; bf16 is staged

@@ -44,31 +44,7 @@ struct ChainMlpBwArgs {
   float* part;                  // the partial rows, layer l at part + sh.part_off[l] * (R * nwg); or nullptr (no parameter gradient wanted)
 };
 
-constexpr int chain_bw_smax(int WMAX) { return (WMAX + 1 + 64 / WMAX - 1) / (64 / WMAX); }  // pairs per lane of a WMAX x (WMAX + 1) layer
-
-// One layer's parameter-gradient phase over the cnt rows the wave parked: inputs at slots [xs, xs + K), deltas at [ds, ds + J).
-template <int SMAX>
-__device__ __forceinline__ void chain_bw_dw_phase(const float* tape, int ld, int cnt, int xs, int ds, int J, int K, float* acc_l, int lane) {
-  const int NG = 64 / J, j = lane % J, kg = lane / J;
-  float acc[SMAX]; int kk[SMAX];
-#pragma unroll
-  for (int q = 0; q < SMAX; ++q) {
-    const int k = kg + NG * q;
-    kk[q] = min(k, K);  // clamped: slots past the bias are summed and never written
-    acc[q] = (kg < NG && k <= K) ? acc_l[k * J + j] : 0.f;
-  }
-  for (int i = 0; i < cnt; ++i) {
-    const float dv = tape[i * ld + ds + j];
-#pragma unroll
-    for (int q = 0; q < SMAX; ++q)
-      if (NG * q <= K) acc[q] = fmaf(dv, kk[q] < K ? tape[i * ld + xs + kk[q]] : 1.f, acc[q]);  // (uniform test)
-  }
-#pragma unroll
-  for (int q = 0; q < SMAX; ++q) {
-    const int k = kg + NG * q;
-    if (kg < NG && k <= K) acc_l[k * J + j] = acc[q];
-  }
-}
+// (chain_bw_smax and chain_bw_dw_phase, the parameter-gradient phase of a layer: gnx_chain_mlp.h — k_chain_wave_bw runs them too)
 
 #if !defined(GNX_CHAIN_BW_KERNEL) || !defined(GNX_CHAIN_BW_BF16)
 #error "define GNX_CHAIN_BW_KERNEL and GNX_CHAIN_BW_BF16 before including gnx_chain_bw_kernel.h"

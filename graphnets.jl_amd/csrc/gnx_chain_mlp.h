@@ -216,6 +216,33 @@ __device__ __forceinline__ float gelu_grad_pre(float z) {
 }
 __device__ __forceinline__ float act_grad_bw(float v, int act) { return act == 4 ? gelu_grad_pre(v) : act_grad_from_out(v, act); }
 
+// ---- the pullback kernels' parameter-gradient phase (k_chain_mlp_bw and its twins: gnx_chain_bw_kernel.h; k_chain_wave_bw: gnx_chain_bw_wave.hip) ----
+constexpr int chain_bw_smax(int WMAX) { return (WMAX + 1 + 64 / WMAX - 1) / (64 / WMAX); }  // pairs per lane of a WMAX x (WMAX + 1) layer
+
+// One layer's parameter-gradient phase over the cnt rows the wave parked: inputs at slots [xs, xs + K), deltas at [ds, ds + J).
+template <int SMAX>
+__device__ __forceinline__ void chain_bw_dw_phase(const float* tape, int ld, int cnt, int xs, int ds, int J, int K, float* acc_l, int lane) {
+  const int NG = 64 / J, j = lane % J, kg = lane / J;
+  float acc[SMAX]; int kk[SMAX];
+#pragma unroll
+  for (int q = 0; q < SMAX; ++q) {
+    const int k = kg + NG * q;
+    kk[q] = min(k, K);  // clamped: slots past the bias are summed and never written
+    acc[q] = (kg < NG && k <= K) ? acc_l[k * J + j] : 0.f;
+  }
+  for (int i = 0; i < cnt; ++i) {
+    const float dv = tape[i * ld + ds + j];
+#pragma unroll
+    for (int q = 0; q < SMAX; ++q)
+      if (NG * q <= K) acc[q] = fmaf(dv, kk[q] < K ? tape[i * ld + xs + kk[q]] : 1.f, acc[q]);  // (uniform test)
+  }
+#pragma unroll
+  for (int q = 0; q < SMAX; ++q) {
+    const int k = kg + NG * q;
+    if (kg < NG && k <= K) acc_l[k * J + j] = acc[q];
+  }
+}
+
 // What the three fused launchers (launch_chain_narrow, _bf16, launch_chain_bw_narrow: `who`) do first: ask the rule, refuse a Dense without weights
 // (the forward's launchers pass a layer of width 0, the pullback's does not: each keeps the set it took), fill the argument record's function
 // part from the chain.  *wmax: the register width's lower bound (the largest of K and the layer widths); *rows: rows of the entity per replica.

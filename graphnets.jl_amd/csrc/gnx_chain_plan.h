@@ -322,6 +322,69 @@ inline ChainBwLayout chain_bw_layout(const ChainShape& s, unsigned fused, size_t
   return L;
 }
 
+// ---- the wave form of the pullback (gnx_chain_block_backward_wave; gnx_chain_bw_wave.hip): the node and the edge function's pullbacks in one
+//      wave-per-tile kernel ----
+// The LDS plan of k_chain_wave_bw: both functions' staged parameters (the edge function's first), then per wave a tape of 64 rows at
+// ld = max(ld_e, ld_n) (each function under its own ChainBwNarrowShape), P_e + P_n accumulators and a slice [cap][oe | 1] — the tile's ef' rows,
+// later the node rows' input-gradient columns [0, oe).  waves: per workgroup, as many as fit 64 KB, at most 4 — the rule takes a block from 2 on.
+struct ChainBwWaveShape {
+  ChainBwNarrowShape e, n;
+  int ld, stride, par_e, par_all, per_wave, waves;
+  size_t nwg;  // workgroups (= partial rows per layer) per replica
+};
+inline ChainBwWaveShape chain_bw_wave_shape(const ChainShape& s, int cap, int64_t n_wtiles) {
+  ChainBwWaveShape w{};
+  w.e = chain_bw_narrow_shape(*s.ch[0], s.k0[0], s.trows[0]);
+  w.n = chain_bw_narrow_shape(*s.ch[1], s.k0[1], s.trows[1]);
+  w.ld = std::max(w.e.ld, w.n.ld);
+  w.stride = chain_wave_stride(s.ow[0]);
+  w.par_e = w.e.par_floats; w.par_all = w.e.par_floats + w.n.par_floats;
+  w.per_wave = 64 * w.ld + w.e.P + w.n.P + cap * w.stride;
+  w.waves = std::min(4, std::max(0, (kChainBwLdsFloats - w.par_all) / w.per_wave));
+  if (w.waves > 0) w.nwg = ((size_t)n_wtiles + w.waves - 1) / w.waves;
+  return w;
+}
+// The class CUT from the pullback's wave rule: register width 8 (every input and layer width of the edge and the node function at most 8) on a
+// batch of SEVERAL graphs.  Measured (profiles/chain_bw_wave.json, whole calls, cache-cold, all gradients wanted, against the parent's
+// gnx_chain_block_backward_narrow): on the 512-graph 1M-edge batch its case (3,2,1) [8,8,2]/[8,3]/[8,2] took 0.443 against 0.396 ms (spread
+// 0.006).  On the one-graph 1M-edge batch the same case took 0.458 against 2.424 ms and the register-width-32 case (10,5,0) [16,3]/[8,4]/[6,5]
+// 2.726 against 3.992 (spread 0.088): there both classes stay.  Register width 32 on several graphs is the forward's cut (chain_wave_cut);
+// register width 16 was not measured on either batch; the other two measured blocks are outside the rule by its LDS term.
+inline bool chain_bw_wave_cut(const ChainShape& s) {
+  return std::max({s.k0[0], s.k0[1], s.maxw[0], s.maxw[1]}) <= 8 && s.trows[2] > 1;
+}
+// The rule (include/gnx.h states it): the forward's wave rule (fp32, no Dropout entry, E > 0, oe > 0, on > 0, no node with more in-edges than
+// the wave-tile edge cap, the forward's cut class), every function that runs inside the narrow pullback's rule, the LDS plan above at two waves.
+inline bool chain_bw_wave_takes(const ChainShape& s, bool bf16, int64_t max_in_degree, int cap, int64_t n_wtiles) {
+  if (!chain_wave_takes(s, bf16, max_in_degree, cap)) return false;
+  for (int t = 0; t < 3; ++t)
+    if ((t < 2 || s.ch[t]->n_layers > 0) && !chain_bw_narrow_takes(*s.ch[t], s.k0[t], s.trows[t])) return false;
+  return chain_bw_wave_shape(s, cap, n_wtiles).waves >= 2 && !chain_bw_wave_cut(s);
+}
+// Its workspace: the tiles' partial rows and the graph level's rows (a block with a graph function), the node rows' input-gradient columns
+// [oe, Kn) as [R N][dn + dg], the edge rows' node / graph columns [R E][2 dn + dg], the partial rows of the parameter gradients (shared with
+// the column-sum slices, as in chain_bw_layout).  No ef', no nf', no columns [0, oe) of dXn.
+struct ChainBwWaveLayout { ChainCarve partials, Xg, dXg, dXn, dxe, part; size_t total; };
+inline ChainBwWaveLayout chain_bw_wave_layout(const ChainShape& s, int cap, int64_t n_wtiles) {
+  ChainBwWaveLayout L{};
+  ChainCarver c;
+  const int oe = s.ow[0], og = s.ow[2], Kg = s.k0[2];
+  const ChainBwWaveShape w = chain_bw_wave_shape(s, cap, n_wtiles);
+  size_t pmax = std::max((size_t)2048 * 4, (size_t)(w.e.P + w.n.P) * w.nwg * (size_t)s.R);
+  if (og > 0) {
+    const ChainBwNarrowShape g = chain_bw_narrow_shape(*s.ch[2], Kg, s.trows[2]);
+    pmax = std::max(pmax, (size_t)g.P * g.nwg * (size_t)s.R);
+  }
+  pmax = std::max(pmax, std::max(s.rows[2] * 256, (size_t)2048) * (size_t)std::max({s.dg, oe, 1}));  // column-sum slices
+  L.partials = c.floats(chain_wave_partial_floats(s, n_wtiles));
+  L.Xg = c.floats(og > 0 ? s.rows[2] * Kg : 0); L.dXg = c.floats(og > 0 ? s.rows[2] * Kg : 0);
+  L.dXn = c.floats(s.rows[1] * (size_t)(s.dn + s.dg));
+  L.dxe = c.floats(s.rows[0] * (size_t)(2 * s.dn + s.dg));
+  L.part = c.floats(pmax);
+  L.total = c.o + 256;
+  return L;
+}
+
 // bfloat16 features, the pullback's native path (gnx_chain_block_backward_narrow_typed): the edge function has an output and edges to run on
 // (there is no pullback without), and every update function with an output and rows to run on is inside the pullback's fused rule (`fused`: the
 // mask of CHAIN_RULE_BW).  Then every function is one k_chain_mlp_bw_bf16 launch on the bf16 rows, chain_bw_node_fw_generic cannot occur, and no

@@ -208,6 +208,23 @@ struct ChainBwNarrowIo {
 // entity / in0..in2 as launch_chain_narrow.  The caller asked chain_bw_narrow_takes and opens the ProfScope.
 int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                                const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
+// ---- gnx_chain_bw_wave.hip: the pullback of a Chain block in the wave form (gnx_chain_block_backward_wave).  The caller asked chain_bw_wave_takes
+//      and opens the ProfScopes ----
+// the tiles' partial rows [R][wave tiles][oe + on] alone: the wave forward without its ef' / nf' stores
+int32_t launch_chain_wave_partials(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const float* ef, const float* nf, const float* gf,
+                                   float* partials, int64_t R, hipStream_t s);
+// the graph function's input rows xg [R][G][oe + on + dg] from the partial rows
+int32_t launch_chain_graph_rows_wave(const gnx_graphs* h, const ChainShape& sh, const float* partials, const float* gf, float* xg, int64_t R, hipStream_t s);
+struct ChainWaveBwIo {
+  const float *g_ef, *g_nf;  // upstream gradients of ef' / nf', or nullptr
+  const float* dxg; int kg;  // dXg [R G][kg], or nullptr (no graph function)
+  float* d_ef;               // [R E][de], or nullptr
+  float* dxe;                // [R E][2 dn + dg]: the node / graph columns of the edge rows' input gradient, or nullptr
+  float* dxn;                // [R N][dn + dg]: columns [oe, Kn) of the node rows' input gradient, or nullptr
+  float *part_e, *part_n;    // the edge / node function's partial rows ([P][R nwg], nwg of chain_bw_wave_shape), or nullptr
+};
+int32_t launch_chain_wave_bw(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const float* ef, const float* nf, const float* gf,
+                             const ChainWaveBwIo& io, int64_t R, hipStream_t s);
 // ---- gnx_chain_bw_narrow_bf16.hip: the same on bf16 features (gnx_chain_block_backward_narrow_typed's native path) ----
 // in0 .. in2 as launch_chain_narrow_bf16; io.G and io.direct hold bfloat16 elements (declared float), io.ex1, io.ex2, io.dx and io.part are fp32
 int32_t launch_chain_bw_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,

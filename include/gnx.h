@@ -652,6 +652,31 @@ GNX_API int32_t gnx_chain_block_backward_narrow(const gnx_graphs* h, const gnx_c
                                         const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
                                         float* d_nf, float* d_gf, const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes,
                                         void* stream);
+/* The narrow pullback in the wave form: one wavefront per wave tile (a contiguous node range of one graph, at most 64 nodes, with every in-edge of
+ * those nodes) pulls back the node AND the edge function in one kernel (k_chain_wave_bw, csrc/gnx_chain_bw_wave.hip).  The tile's ef' rows, the
+ * per-node sums over them and columns [0, oe) of the node rows' input gradient live in the wave's LDS: neither ef' nor nf' nor those columns
+ * reach memory.  With a graph function a first launch leaves each tile's column sums [sum ef' ; sum nf'], a second (one workgroup per graph)
+ * sums them into the graph function's input rows — no per-graph walk over the E and N rows — and the graph level runs as in the narrow pullback.
+ * The rule, for the whole block (_applies returns 1; 0 elsewhere and on bad arguments):
+ *   - gnx_chain_block_forward_wave's rule holds: float32, no Dropout entry, E > 0, oe > 0, on > 0, no node with more in-edges than the wave-tile
+ *     edge cap, and not the forward's cut class (register width 32 on a batch of several graphs);
+ *   - the edge and the node function are inside gnx_chain_block_backward_narrow's rule, the graph function is absent (no layers) or inside it;
+ *   - LDS: par_e + par_n + 2 * (64 * max(ld_e, ld_n) + P_e + P_n + cap * (oe | 1)) <= 16384 floats (par, ld, P as in the narrow pullback's rule,
+ *     per function) — as many waves per workgroup as fit, four at the most.
+ * One class is cut for its own figures, measured slower than the narrow pullback beyond its spread (profiles/chain_bw_wave.json): every input
+ * and layer width of the edge and the node function at most 8 (the kernel's 8-wide instantiation) on a batch of more than one graph.
+ * A block outside the rule runs gnx_chain_block_backward_narrow's launches unchanged, on that entry's workspace size, bit for bit.
+ * Inside the rule every gradient is the same mathematical pullback in other fixed summation orders: within the library's bar against float64,
+ * the same bits from call to call whatever the workspace held; no atomics.  _workspace_bytes inside the rule: the tiles' partial rows
+ * R * wave tiles * (oe + on) and the graph rows Xg, dXg (a block with a graph function), [R N][dn + dg] and [R E][2 dn + dg] floats of input
+ * gradient columns and the parameter gradients' partial rows, each carve 256-byte aligned; it builds the handle's tables the call reads, so
+ * call it outside a stream capture.  Arguments, optional outputs and refusals as gnx_chain_block_backward_narrow. */
+GNX_API int32_t gnx_chain_block_backward_wave_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API size_t gnx_chain_block_backward_wave_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API int32_t gnx_chain_block_backward_wave(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                      const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
+                                      float* d_nf, float* d_gf, const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes,
+                                      void* stream);
 /* Either Chain pullback on float32 or bfloat16 features.  `elem` applies to the nine feature-shaped tensors (the inputs, the upstream gradients,
  * the input gradients); parameter gradients stay float32.  `narrow` (0 or 1): gnx_chain_block_backward (0) or gnx_chain_block_backward_narrow
  * (1).  GNX_ELEM_F32 IS the mirrored entry (same validation, workspace size, bits); another elem than F32 / BF16 or a narrow other than 0 / 1:

@@ -217,6 +217,17 @@ def _rec_chain_wave_bf16(f, res, twin):
     return rec
 
 
+def _rec_chain_bw_wave(f, res, twin):
+    r, narrow = res(), twin("chain_bw_narrow")["srcs"]
+    rec = dict(what="k_chain_wave_bw<W> / k_chain_wave_partials<W> per register width, k_chain_graph_rows_wave" + REMARKS, box=BOX,
+               file_flags=file_flags(f["file"]), lds_budget_bytes=f["LDS_BUDGET_BYTES"],
+               kernels={k: {str(w): r[k][w] for w in WMAX} for k in f["KERNEL_NAMES"]}, k_chain_graph_rows_wave=r["k_chain_graph_rows_wave"][0],
+               k_chain_mlp_bw_edge_vgpr={str(w): narrow["edge"][str(w)]["vgpr"] for w in WMAX})
+    every = [(f"{k}/{w}", r[k][w]) for k in f["KERNEL_NAMES"] for w in WMAX] + [("k_chain_graph_rows_wave", r["k_chain_graph_rows_wave"][0])]
+    rec["instantiations_with_scratch_or_static_lds"] = [n for n, v in every if v["scratch"] or v["lds_static"]]
+    return rec
+
+
 def _chain(kernel, file, lds_budget, **more):
     """a Chain kernel k<WMAX, SRC> of one file: resources() is {src: {WMAX: {...}}}; the LDS is dynamic (at most LDS_BUDGET_BYTES)"""
     return dict(file=file, kernel=kernel, name=r"_ZN3gnx\d+" + kernel + r"ILi(\d+)ELi(\d+)EEEv", key=lambda m: (SRC[int(m.group(2))], int(m.group(1))),
@@ -254,6 +265,10 @@ FAMILIES = {
     "chain_wave_bf16": dict(file="gnx_chain_wave_bf16.hip", name=r"_ZN3gnx\d+(k_chain_wave_bf16|k_chain_graph_wave_bf16)ILi(\d+)EEEv",
                             key=lambda m: (m.group(1), int(m.group(2))), fields=STATIC, record=_rec_chain_wave_bf16,
                             KERNEL_NAMES=("k_chain_wave_bf16", "k_chain_graph_wave_bf16"), LDS_BUDGET_BYTES=4 * 16384),
+    # the wave form of the Chain pullback: both functions' parameters and every wave's tape, accumulators and slice in LDS (kChainBwLdsFloats)
+    "chain_bw_wave": dict(file="gnx_chain_bw_wave.hip", name=r"_ZN3gnx\d+(k_chain_wave_bw|k_chain_wave_partials|k_chain_graph_rows_wave)(?:ILi(\d+)EEEv|E)",
+                          key=lambda m: (m.group(1), int(m.group(2) or 0)), fields=STATIC, record=_rec_chain_bw_wave,
+                          KERNEL_NAMES=("k_chain_wave_bw", "k_chain_wave_partials"), LDS_BUDGET_BYTES=4 * 16384),
     # the two Chain training kernels (the layer code of chain_narrow / chain_bw_narrow with the Dropout op), 18 instantiations: none may use scratch
     # (include/gnx.h: a class that does is cut from the training rule); the record carries the test-mode twins' VGPRs next to each.
     # resources("chain_train_narrow", direction)
