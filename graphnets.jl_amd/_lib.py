@@ -176,6 +176,10 @@ SIGNATURES = {
     "gnx_chain_block_backward_narrow_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
     "gnx_chain_block_backward_narrow_typed": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int32] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
                                               [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnx_chain_block_backward_wave_typed_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
+    "gnx_chain_block_backward_wave_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
+    "gnx_chain_block_backward_wave_typed": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int32] + [_fp] * 6 + [C.c_int64] + [_fp] * 3 +
+                                            [C.POINTER(ChainBlockGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnx_chain_dropout_mask": (C.c_int32, [C.POINTER(ChainDropout), C.c_int32, C.c_int32, C.c_float, C.c_int64, _fp, C.c_void_p]),
     "gnx_chain_block_train_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
     "gnx_chain_block_forward_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),

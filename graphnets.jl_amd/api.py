@@ -950,6 +950,7 @@ def _entry(family, direction, elem, switches=(), record=False):
                            fp32: gnx_chain_block_forward_wave with `wave_chain` (which wins over `narrow_chain`),
                            gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
                 backward   (narrow = `narrow_chain_backward`) an active record: gnx_chain_block_backward_train; bf16 (needs `bf16_backward`):
+                           gnx_chain_block_backward_wave_typed with `wave_chain_backward` (which wins over the two below),
                            gnx_chain_block_backward_narrow_typed with `native_chain_backward`, else gnx_chain_block_backward_typed; fp32:
                            gnx_chain_block_backward_wave with `wave_chain_backward` (which wins over `narrow_chain_backward`), else
                            gnx_chain_block_backward_narrow or gnx_chain_block_backward
@@ -1000,6 +1001,8 @@ def _entry(family, direction, elem, switches=(), record=False):
         n = int(on("narrow_chain_backward"))
         if record:
             return E("gnx_chain_block_backward_train", (n,), ("drop",), (n,))
+        if bf16 and on("wave_chain_backward"):  # (outside its rule the entry is gnx_chain_block_backward_narrow_typed)
+            return E("gnx_chain_block_backward_wave_typed", (elem,), (elem,))
         if bf16 and on("native_chain_backward"):
             return E("gnx_chain_block_backward_narrow_typed", (elem,), (elem,))
         if bf16:  # (mirrors the pullback `narrow_chain_backward` selects)
@@ -1141,6 +1144,10 @@ class GNBlock:
     `wave_chain_backward` (gnx_chain_block_backward_wave; wins over `narrow_chain_backward`, requires no other switch; float32 features in test
     mode): where the whole block is inside the pullback's wave rule (include/gnx.h) one wavefront per wave tile pulls back the node and the
     edge function in one kernel, with ef', nf' and the node-to-edge gradient columns in LDS; elsewhere the call is `narrow_chain_backward`'s.
+    On bfloat16 features (with `bf16_chain` and `bf16_backward`) it selects gnx_chain_block_backward_wave_typed and wins over
+    `native_chain_backward` as well: inside the same rule the wave kernels read the bf16 rows and upstream gradients and write the bf16 edge
+    gradient themselves — input gradients bit for bit the float32 wave pullback's on the widened tensors, rounded once, parameter gradients its
+    float32 bits; elsewhere the call is `native_chain_backward`'s.
 
     `bf16_chain` (gnx_chain_block_forward_typed, gnx_chain_block_backward_typed): lets a block whose update functions are Chains run on bfloat16
     features: bf16 outputs, bit for bit the fp32 entry that `narrow_chain` selects on the widened inputs, rounded once.  With `narrow_chain` and

@@ -1366,26 +1366,32 @@ struct ChainBwPlan : ChainPlan {
   ChainBwLayout L{};
   bool native = false;
   ChainBwNativeWs nw{};
-  // the wave form runs (asked for through gnx_chain_block_backward_wave, and chain_bw_wave_takes): its own layout, nothing of L
-  bool wave = false;
+  // the wave form runs (asked for through gnx_chain_block_backward_wave or _wave_typed, and chain_bw_wave_takes): its own layout, nothing of L.
+  // wave_bf16 (gnx_chain_block_backward_wave_typed alone: narrow_typed with ask_wave): the wave form on the caller's bf16 tensors — the wave
+  // layout and behind it the two graph-sized carves of `nw` (chain_bw_wave_typed_layout)
+  bool wave = false, wave_bf16 = false;
   ChainBwWaveLayout WL{};
+  bool on_bf16() const { return native || wave_bf16; }  // the launches read and write the caller's bf16 tensors themselves
   ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false,
               bool ask_wave = false)
       : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery, train) {
     if (!rc && train) query = "workspace missing or smaller than gnx_chain_block_backward_train_workspace_bytes()";
     if (!rc && ask_wave) {
-      wave = narrow && !train && !bf16 && chain_bw_wave_takes(sh, false, h->max_in_degree, h->wtile_e_cap, h->n_wtiles());
-      if (wave) query = "workspace missing or smaller than gnx_chain_block_backward_wave_workspace_bytes()";
+      wave = narrow && !train && (!bf16 || narrow_typed) && chain_bw_wave_takes(sh, bf16, h->max_in_degree, h->wtile_e_cap, h->n_wtiles());
+      wave_bf16 = wave && bf16;
+      if (wave) query = wave_bf16 ? "workspace missing or smaller than gnx_chain_block_backward_wave_typed_workspace_bytes()"
+                                  : "workspace missing or smaller than gnx_chain_block_backward_wave_workspace_bytes()";
     }
-    if (rc || !narrow_typed) return;
+    if (rc || !narrow_typed || wave) return;
     native = chain_bw_typed_native(sh, fused, bf16);
     if (bf16) query = kBwNarrowTypedQuery;
   }
   void lay_out(const gnx_graphs* h) {
     if (rc || total) return;
     if (wave) {
-      WL = chain_bw_wave_layout(sh, h->wtile_e_cap, h->n_wtiles());
-      base = total = WL.total;
+      const ChainBwWaveTypedLayout T = chain_bw_wave_typed_layout(sh, h->wtile_e_cap, h->n_wtiles());
+      WL = T.W; nw = T.nw;
+      base = WL.total; total = wave_bf16 ? T.total : WL.total;
       return;
     }
     const bool blk = !(fused & 1) && sh.ch[0]->n_layers > 0;  // the first Dense of a generic edge function: the one-layer block, forward and pullback
@@ -1429,7 +1435,9 @@ struct ChainBwCtx {
   void last_delta(int t, const float* upstream, float* out, const float* X0, int K0, int act_override);
   int32_t fused_level(int t, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2, ChainBwNarrowIo io, const char* name);
   int32_t edge_fused(), edge_generic();
-  int32_t edge_cols(const float* dXe);              // d_nf and d_gf from the compact node / graph columns of the edge rows' input gradient
+  // d_nf and d_gf from the compact node / graph columns of the edge rows' input gradient; dXn (ld_n, c0_n as for shares): read by a bf16 call alone
+  int32_t edge_cols(const float* dXe, int ld_n, int c0_n);
+  int32_t edge_cols(const float* dXe) { return edge_cols(dXe, Kn, oe); }
   int32_t shares(int ld_n, int c0_n);               // dXn: rows of ld_n floats whose column c0_n is column oe of the node rows' input gradient
   int32_t shares() { return shares(Kn, oe); }
 };
@@ -1584,7 +1592,7 @@ int32_t ChainBwCtx::fused_level(int t, const float* in0, int d0, const float* in
   const bool want = chain_wants_grads(c, gfn(t));
   io.part = want ? part : nullptr;
   { ProfScope ps(name, s);
-    if (int32_t r2 = pl.native ? launch_chain_bw_narrow_bf16(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s) : launch_chain_bw_narrow(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
+    if (int32_t r2 = pl.on_bf16() ? launch_chain_bw_narrow_bf16(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s) : launch_chain_bw_narrow(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
   return want ? chain_bw_narrow_finals(c, pl.sh.k0[t], chain_bw_narrow_shape(c, pl.sh.k0[t], pl.sh.trows[t]), R, part, gfn(t), s) : GNX_OK;
 }
 
@@ -1597,12 +1605,12 @@ int32_t ChainBwCtx::edge_fused() {
                                                                                            need_cols ? dXe : nullptr, de, d_ef && de > 0 ? d_ef : nullptr, nullptr}, "bw_delta_edge")) return rc;
   return edge_cols(dXe);
 }
-int32_t ChainBwCtx::edge_cols(const float* dXe) {
+int32_t ChainBwCtx::edge_cols(const float* dXe, int ld_n, int c0_n) {
   const int ldc = 2 * dn + dg;
   if (d_nf && dn > 0) {
     ProfScope ps("bw_dnf", s);
-    if (pl.native)  // (with the node function's share, which shares() then leaves out)
-      GNX_LAUNCH(k_bw_dnf_share_last, dim3(chain_blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, on > 0 ? dXn : (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr,
+    if (pl.on_bf16())  // (with the node function's share, which shares() then leaves out)
+      GNX_LAUNCH(k_bw_dnf_share_last, dim3(chain_blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, on > 0 ? dXn : (const float*)nullptr, ld_n, c0_n, dXe, ldc, 0, dn, h->d_colptr,
                  h->d_csr_ptr, h->d_csr_eid, N, E, dn, reinterpret_cast<bf16_t*>(d_nf));
     else
       GNX_LAUNCH(k_bw_dnf<false>, dim3(chain_blocks((size_t)N * dn).x, Ru), dim3(256), 0, s, (const float*)nullptr, Kn, oe, dXe, ldc, 0, dn, h->d_colptr, h->d_csr_ptr,
@@ -1643,7 +1651,7 @@ int32_t ChainBwCtx::edge_generic() {
 // ---- the node / graph functions' own shares of d_nf, d_gf ----
 int32_t ChainBwCtx::shares(int ld_n, int c0_n) {
   int32_t rc;
-  if (!pl.native && d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, ld_n, c0_n, pl.sh.rows[1], dn, d_nf, 1, s))) return rc;
+  if (!pl.on_bf16() && d_nf && dn > 0 && on > 0 && (rc = add_cols(dXn, ld_n, c0_n, pl.sh.rows[1], dn, d_nf, 1, s))) return rc;
   if (d_gf && dg > 0) {
     if (on > 0) {
       int64_t mn = 1;
@@ -1658,6 +1666,10 @@ int32_t ChainBwCtx::shares(int ld_n, int c0_n) {
 // The wave form (pl.wave): with a graph function the tiles' partial rows, the graph function's input rows from them and the graph level as in
 // the narrow pullback; then the node and the edge function's pullbacks in one wave-per-tile kernel, its finals, and the share launches as they
 // run after the narrow pullback's fused edge level — on the wave layout's carves (dXn compact: [R N][dn + dg]).
+// A bf16 call (pl.wave_bf16) runs the same launches in the same order under the same names on the caller's bf16 tensors: gf is widened once
+// (G rows) for k_chain_graph_rows_wave, the graph level reads g_gf_out as bf16 (k_chain_mlp_bw_bf16), the two wave kernels are the bf16 twins,
+// d_nf is written once by k_bw_dnf_share_last from the compact dXn (the fp32 order: 0, in-edges, out-edges, the node function's share last),
+// d_gf accumulates in the fp32 carve and is rounded once.  No E- or N-sized tensor is widened or rounded by a pass of its own.
 int32_t chain_backward_wave(ChainBwCtx& x) {
   const ChainBwPlan& pl = x.pl;
   const ChainBwWaveLayout& W = pl.WL;
@@ -1668,11 +1680,19 @@ int32_t chain_backward_wave(ChainBwCtx& x) {
   float* const dXe = x.F(W.dxe);
   x.Xg = x.F(W.Xg); x.dXg = x.F(W.dXg); x.dXn = x.F(W.dXn); x.part = x.F(W.part);
   int32_t rc;
+  const bool bf = pl.wave_bf16;
+  x.gf_rows = x.gf;
+  float* const d_gf_caller = x.d_gf;
+  if (bf) {
+    x.gf_rows = pl.nw.gf32.bytes ? x.F(pl.nw.gf32) : nullptr;
+    if (x.gf_rows && (rc = launch_bf16_widen(x.gf, pl.nw.gf32.bytes / sizeof(float), x.F(pl.nw.gf32), s))) return rc;
+    if (x.d_gf) x.d_gf = x.F(pl.nw.dgf32);
+  }
   if (og > 0) {
     { ProfScope ps("bw_chain_fw_e", s);
-      if ((rc = launch_chain_wave_partials(h, *pl.p, pl.sh, x.ef, x.nf, x.gf, partials, x.R, s))) return rc; }
+      if ((rc = (bf ? launch_chain_wave_partials_bf16 : launch_chain_wave_partials)(h, *pl.p, pl.sh, x.ef, x.nf, x.gf, partials, x.R, s))) return rc; }
     { ProfScope ps("bw_chain_fw_g", s);
-      if ((rc = launch_chain_graph_rows_wave(h, pl.sh, partials, x.gf, x.Xg, x.R, s))) return rc; }
+      if ((rc = launch_chain_graph_rows_wave(h, pl.sh, partials, x.gf_rows, x.Xg, x.R, s))) return rc; }
     if ((rc = x.fused_level(2, x.Xg, x.Kg, nullptr, 0, nullptr, 0, ChainBwNarrowIo{x.g_gf_out, nullptr, 0, 0, nullptr, 0, x.dXg, 0, nullptr, nullptr}, "bw_delta"))) return rc;
   }
   const ChainBwWaveShape ws = chain_bw_wave_shape(pl.sh, h->wtile_e_cap, h->n_wtiles());
@@ -1681,7 +1701,7 @@ int32_t chain_backward_wave(ChainBwCtx& x) {
   float* const part_e = x.part;
   float* const part_n = x.part + (size_t)ws.e.P * ws.nwg * (size_t)x.R;
   { ProfScope ps("bw_delta_edge", s);
-    if ((rc = launch_chain_wave_bw(h, *pl.p, pl.sh, x.ef, x.nf, x.gf,
+    if ((rc = (bf ? launch_chain_wave_bw_bf16 : launch_chain_wave_bw)(h, *pl.p, pl.sh, x.ef, x.nf, x.gf,
                                    ChainWaveBwIo{x.g_ef_out, x.g_nf_out, og > 0 ? x.dXg : nullptr, x.Kg, x.d_ef && de > 0 ? x.d_ef : nullptr, cols_e ? dXe : nullptr,
                                                  cols_e && dn + dg > 0 ? x.dXn : nullptr, want_e ? part_e : nullptr, want_n ? part_n : nullptr},
                                    x.R, s))) return rc; }
@@ -1689,8 +1709,9 @@ int32_t chain_backward_wave(ChainBwCtx& x) {
   fe.nwg = fn.nwg = ws.nwg;
   if (want_e && (rc = chain_bw_narrow_finals(x.ch(0), pl.sh.k0[0], fe, x.R, part_e, x.gfn(0), s))) return rc;
   if (want_n && (rc = chain_bw_narrow_finals(x.ch(1), pl.sh.k0[1], fn, x.R, part_n, x.gfn(1), s))) return rc;
-  if ((rc = x.edge_cols(dXe))) return rc;
+  if ((rc = x.edge_cols(dXe, dn + dg, 0))) return rc;
   if ((rc = x.shares(dn + dg, 0))) return rc;
+  if (bf && d_gf_caller && dg > 0 && (rc = launch_bf16_round(x.d_gf, pl.sh.rows[2] * (size_t)dg, d_gf_caller, s))) return rc;
   GNX_HIP(hipGetLastError());
   return GNX_OK;
 }
@@ -1706,7 +1727,7 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   if (pl.sh.ow[0] == 0) return fail(GNX_ERR_DIMS, "chain backward: not implemented for an edge function without output (the forward takes it; train such a block with one-layer update functions)");
   pl.lay_out(h);  // (a staged call has laid out, and comes here behind its own workspace check)
   int32_t rc;
-  if ((rc = check_ws(c.ws, c.ws_bytes, pl.native ? pl.total : pl.base, pl.query))) return rc;
+  if ((rc = check_ws(c.ws, c.ws_bytes, pl.on_bf16() ? pl.total : pl.base, pl.query))) return rc;
   if ((rc = gnx_ensure_wide_tables(h, c.stream))) return rc;
   if ((pl.fused & 1) && (rc = gnx_ensure_csr(h))) return rc;  // (k_bw_dnf's out-edge view; the query built it)
   ChainBwCtx x{h, pl, pl.p, pl.lnf.init_grads(c.grads), cf(c.ef), cf(c.nf), cf(c.gf), cf(c.g_ef_out), cf(c.g_nf_out), cf(c.g_gf_out), mf(c.d_ef), mf(c.d_nf), mf(c.d_gf),
@@ -1762,7 +1783,7 @@ int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = fals
   int32_t rc;
   if (pl.bf16 && (rc = check_bf16_aligned(bufs, 9))) return rc;
   if ((rc = chain_check_features(pl.sh, c.ef, c.nf, c.gf, "an input with non-zero width is NULL"))) return rc;
-  if (!pl.bf16 || pl.native) return chain_backward_fp32(c, pl);
+  if (!pl.bf16 || pl.on_bf16()) return chain_backward_fp32(c, pl);
   pl.lay_out(c.h);
   if ((rc = check_ws(c.ws, c.ws_bytes, pl.total, pl.query))) return rc;
   const hipStream_t s = (hipStream_t)c.stream;
@@ -1852,6 +1873,25 @@ int32_t gnx_chain_block_backward_narrow_typed(const gnx_graphs* h, const gnx_cha
                                               const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
   return chain_bw_run(ChainBwCall{h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true, true);
+}
+
+// gnx_chain_block_backward_wave_typed: the wave pullback on fp32 or bf16 features.  GNX_ELEM_F32 is gnx_chain_block_backward_wave; bf16 inside
+// chain_bw_wave_takes runs the wave form on the bf16 tensors themselves (ChainBwPlan::wave_bf16), any other bf16 call is
+// gnx_chain_block_backward_narrow_typed on the same arguments
+int32_t gnx_chain_block_backward_wave_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return 0;
+  return ChainBwPlan(h, p, R, elem, true, true, false, true).wave ? 1 : 0;  // (the constructor reads the handle's counts alone)
+}
+
+size_t gnx_chain_block_backward_wave_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  return elem == GNX_ELEM_F32 || elem == GNX_ELEM_BF16 ? chain_bw_query(h, p, R, elem, true, true, false, true) : 0;
+}
+
+int32_t gnx_chain_block_backward_wave_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                            const void* g_ef_out, const void* g_nf_out, const void* g_gf_out, int64_t R, void* d_ef, void* d_nf, void* d_gf,
+                                            const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  if (elem != GNX_ELEM_F32 && elem != GNX_ELEM_BF16) return fail(GNX_ERR_INVALID_ARG, kBadElem);
+  return chain_bw_run(ChainBwCall{h, p, elem, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true, true, false, true);
 }
 
 // gnx_chain_block_backward_train: the pullback of gnx_chain_block_forward_train under the same record (ChainTrain: the refusals, the library's copy of

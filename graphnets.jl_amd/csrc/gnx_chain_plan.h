@@ -355,11 +355,21 @@ inline bool chain_bw_wave_cut(const ChainShape& s) {
 }
 // The rule (include/gnx.h states it): the forward's wave rule (fp32, no Dropout entry, E > 0, oe > 0, on > 0, no node with more in-edges than
 // the wave-tile edge cap, the forward's cut class), every function that runs inside the narrow pullback's rule, the LDS plan above at two waves.
+// bf16 (gnx_chain_block_backward_wave_typed; gnx_chain_bw_wave_bf16.hip): the fp32 rule with nothing added — the tape, the accumulators and the
+// slice stay fp32, so the LDS plan is chain_bw_wave_shape as it stands.  chain_wave_cut and chain_bw_wave_cut apply by inheritance from the fp32
+// measurements; they were NOT measured on bf16 features.
 inline bool chain_bw_wave_takes(const ChainShape& s, bool bf16, int64_t max_in_degree, int cap, int64_t n_wtiles) {
-  if (!chain_wave_takes(s, bf16, max_in_degree, cap)) return false;
+  if (!chain_wave_takes(s, false, max_in_degree, cap)) return false;
   for (int t = 0; t < 3; ++t)
     if ((t < 2 || s.ch[t]->n_layers > 0) && !chain_bw_narrow_takes(*s.ch[t], s.k0[t], s.trows[t])) return false;
-  return chain_bw_wave_shape(s, cap, n_wtiles).waves >= 2 && !chain_bw_wave_cut(s);
+  if (chain_bw_wave_shape(s, cap, n_wtiles).waves < 2 || chain_bw_wave_cut(s)) return false;
+  // bf16: no class is cut for its own figures.  Measured (profiles/chain_bw_wave_bf16.json, whole calls, cache-cold, all gradients wanted, against
+  // the parent's gnx_chain_block_backward_narrow_typed on the same bf16 tensors), on the one-graph 1M-edge batch: register width 8, (3,2,1)
+  // [8,8,2]/[8,3]/[8,2], 0.489 against 2.431 ms (spread 0.061; the fp32 wave pullback on fp32 tensors 0.458); register width 32, (10,5,0)
+  // [16,3]/[8,4]/[6,5], 2.767 against 3.972 ms (spread 0.081; fp32 2.719).  Not measured on bf16 features: register width 16 on either batch, and
+  // any class on several graphs (there the two measured classes are cut by inheritance, the other measured blocks are outside the LDS term).
+  (void)bf16;
+  return true;
 }
 // Its workspace: the tiles' partial rows and the graph level's rows (a block with a graph function), the node rows' input-gradient columns
 // [oe, Kn) as [R N][dn + dg], the edge rows' node / graph columns [R E][2 dn + dg], the partial rows of the parameter gradients (shared with
@@ -404,6 +414,16 @@ inline ChainBwNativeWs chain_bw_native_layout(const ChainShape& s, size_t fp32_t
   w.dgf32 = c.floats(s.rows[2] * (size_t)s.dg);
   w.total = c.o;
   return w;
+}
+// The wave pullback on bf16 features: chain_bw_wave_layout and behind it the same two graph-sized carves (R G dg floats each: the widened gf,
+// which k_chain_graph_rows_wave assembles Xg from, and the fp32 d_gf accumulator).  Nothing E- or N-sized is added.
+struct ChainBwWaveTypedLayout { ChainBwWaveLayout W; ChainBwNativeWs nw; size_t total; };
+inline ChainBwWaveTypedLayout chain_bw_wave_typed_layout(const ChainShape& s, int cap, int64_t n_wtiles) {
+  ChainBwWaveTypedLayout L{};
+  L.W = chain_bw_wave_layout(s, cap, n_wtiles);
+  L.nw = chain_bw_native_layout(s, L.W.total);
+  L.total = L.nw.total;
+  return L;
 }
 
 }  // namespace gnx

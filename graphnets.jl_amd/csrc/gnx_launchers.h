@@ -225,6 +225,12 @@ struct ChainWaveBwIo {
 };
 int32_t launch_chain_wave_bw(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const float* ef, const float* nf, const float* gf,
                              const ChainWaveBwIo& io, int64_t R, hipStream_t s);
+// ---- gnx_chain_bw_wave_bf16.hip: the two launchers above on bf16 features (gnx_chain_block_backward_wave_typed) ----
+// ef, nf, gf, io.g_ef, io.g_nf and io.d_ef hold bfloat16 elements (declared float); partials, io.dxg, io.dxe, io.dxn and the partial rows are fp32
+int32_t launch_chain_wave_partials_bf16(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const float* ef, const float* nf, const float* gf,
+                                        float* partials, int64_t R, hipStream_t s);
+int32_t launch_chain_wave_bw_bf16(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const float* ef, const float* nf, const float* gf,
+                                  const ChainWaveBwIo& io, int64_t R, hipStream_t s);
 // ---- gnx_chain_bw_narrow_bf16.hip: the same on bf16 features (gnx_chain_block_backward_narrow_typed's native path) ----
 // in0 .. in2 as launch_chain_narrow_bf16; io.G and io.direct hold bfloat16 elements (declared float), io.ex1, io.ex2, io.dx and io.part are fp32
 int32_t launch_chain_bw_narrow_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,

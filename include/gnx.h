@@ -720,6 +720,37 @@ GNX_API int32_t gnx_chain_block_backward_narrow_typed(const gnx_graphs* h, const
                                                       const void* nf, const void* gf, const void* g_ef_out, const void* g_nf_out,
                                                       const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
                                                       const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+/* gnx_chain_block_backward_wave on float32 or bfloat16 features, bfloat16 in the wave form itself (k_chain_wave_partials_bf16 and
+ * k_chain_wave_bw_bf16, csrc/gnx_chain_bw_wave_bf16.hip: the fp32 wave kernels' text with bf16 feature-shaped operands — ef, nf[src], nf[dst],
+ * nf[n], gf[g] and the upstream gradients of ef' and nf' read with one 16-bit load per element and widened exactly, d_ef rounded to nearest even
+ * once and written with one 16-bit store per element; the slice, the tape, the accumulators and every arithmetic operation are the fp32
+ * kernels').  `elem` applies to the nine feature-shaped tensors; parameter gradients are always float32.  The argument list is
+ * gnx_chain_block_backward_narrow_typed's.
+ *   - GNX_ELEM_F32: the call IS gnx_chain_block_backward_wave (same validation, workspace size, bits, inside and outside its rule).
+ *   - GNX_ELEM_BF16 inside the rule: gnx_chain_block_backward_wave's rule with nothing added (the LDS term unchanged: everything in LDS stays
+ *     float32), its two cut classes included — register width 32 on several graphs (the forward's) and register width 8 on several graphs;
+ *     both are inherited from the float32 measurements and were not measured on bfloat16 features (profiles/chain_bw_wave_bf16.json names
+ *     what was).  d_ef, d_nf, d_gf are bit for bit to_bf16 of what gnx_chain_block_backward_wave returns on the exactly widened tensors, every
+ *     parameter gradient is bit for bit that call's float32.  gf is widened once (G rows) for the graph function's input rows, the graph level
+ *     reads the upstream gradient of gf' as bf16; d_nf is summed in the float32 order (0, the in-edges, the out-edges, the node function's own
+ *     share) and rounded once; d_gf accumulates in float32 and is rounded once.  No E- or N-sized tensor is widened or rounded by a pass of its
+ *     own: the workspace is gnx_chain_block_backward_wave's plus two 256-byte-aligned carves of R G dg floats, and the call launches one
+ *     k_bf16_widen and one k_bf16_round at the most, both graph-sized.
+ *   - GNX_ELEM_BF16 outside the rule: the call IS gnx_chain_block_backward_narrow_typed on the same arguments (same workspace size, same bits,
+ *     its workspace refusal's name).
+ * _applies: 1 exactly where the wave form runs (either elem), 0 otherwise and on bad arguments.  Inside the rule a bf16 call's workspace refusal
+ * names gnx_chain_block_backward_wave_typed_workspace_bytes().  Refusals in the order of the other typed Chain pullbacks: another elem than
+ * F32 / BF16 (GNX_ERR_INVALID_ARG before any GPU work, 0 from the queries), NULL handle or params, the parameters, a bf16 buffer that is not
+ * 4-byte aligned (the nine buffers), a NULL feature of non-zero width.  Optional outputs and NULL upstream gradients as in
+ * gnx_chain_block_backward_typed.  The query builds the handle's tables, the out-edge (CSR) view included — call it outside a stream capture;
+ * the call allocates nothing, does not synchronise, uses one stream and works inside a capture. */
+GNX_API int32_t gnx_chain_block_backward_wave_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_chain_block_backward_wave_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas,
+                                                                   int32_t elem);
+GNX_API int32_t gnx_chain_block_backward_wave_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef,
+                                                    const void* nf, const void* gf, const void* g_ef_out, const void* g_nf_out,
+                                                    const void* g_gf_out, int64_t n_replicas, void* d_ef, void* d_nf, void* d_gf,
+                                                    const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Backward of (m::GNCore)(x) = x + block(gn1(x)) + ffwd(gn2(x)) (src/gncore.jl:56-68).  Takes the forward's INPUTS and the
  * upstream gradients; the intermediates (both LayerNorms, the block's outputs, the FeedForward hidden activations) are

@@ -955,6 +955,37 @@ function chain_backward_wave_applies(m::ChainBlock, x)
     p = Ref(chain_params(m, keep))
     GC.@preserve m keep ccall((:gnx_chain_block_backward_wave_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
 end
+# Through gnx_chain_block_backward_wave_typed: the shim's arrays are Float32, so it passes GNX_ELEM_F32 — then the call IS
+# gnx_chain_block_backward_wave (same workspace size, same bits); with bfloat16 device buffers the same argument list takes GNX_ELEM_BF16 and
+# the wave kernels read the bf16 rows and upstream gradients and write the bf16 edge gradient themselves (include/gnx.h states the contract).
+function chain_pullback_device_wave(m::ChainBlock, x, ȳ; elem::Int32=GNX_ELEM_F32)
+    g::GNGraphBatch = x.graphs
+    R = replicas(x.ef, x.nf, x.gf)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    dins = (likeof(x.ef), likeof(x.nf), likeof(x.gf))
+    chains = (m.edgefn, m.nodefn, m.graphfn)
+    gs = [[gradslots(l) for l in c] for c in chains]
+    gW = [[q[1] for q in c] for c in gs]; gB = [[q[2] for q in c] for c in gs]
+    arrs = [[GnxDenseGrad(devptr(gW[t][i]), devptr(gB[t][i])) for i in eachindex(chains[t])] for t in 1:3]
+    gp(t) = isempty(arrs[t]) ? Ptr{GnxDenseGrad}(C_NULL) : pointer(arrs[t])
+    grads = Ref(GnxChainBlockGrads(gp(1), gp(2), gp(3)))
+    ws = workspace!(g, (:chain_backward_wave_typed, chainkey(m), R, elem)) do
+        ccall((:gnx_chain_block_backward_wave_typed_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64, Int32), g.handle, p, R, elem)
+    end
+    GC.@preserve m keep x ȳ dins gW gB arrs ws check(ccall((:gnx_chain_block_backward_wave_typed, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{GnxChainBlockGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        g.handle, p, elem, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
+        devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]))
+    (ef=dins[1], nf=dins[2], gf=dins[3], params=[[(weight=gW[t][i], bias=gB[t][i]) for i in eachindex(chains[t])] for t in 1:3])
+end
+# 1 where gnx_chain_block_backward_wave_typed runs its wave form on this batch with features of `elem` (GNX_ELEM_F32: gnx_chain_block_backward_wave's answer)
+function chain_backward_wave_typed_applies(m::ChainBlock, x; elem::Int32=GNX_ELEM_F32)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    GC.@preserve m keep ccall((:gnx_chain_block_backward_wave_typed_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64, Int32), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf), elem)
+end
 # ---- the typed Chain entries (gnx_chain_block_forward_typed / _backward_typed): `narrow` selects the fp32 entry the call mirrors.  The shim's
 #      arrays are Float32, so it passes GNX_ELEM_F32 — then the call IS the mirrored entry (same workspace size, same bits); with bfloat16
 #      device buffers the same argument lists take GNX_ELEM_BF16 (include/gnx.h states the bf16 contracts). ----

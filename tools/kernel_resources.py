@@ -228,6 +228,18 @@ def _rec_chain_bw_wave(f, res, twin):
     return rec
 
 
+def _rec_chain_bw_wave_bf16(f, res, twin):
+    r, fp32 = res(), twin("chain_bw_wave")["kernels"]
+    names = f["KERNEL_NAMES"]
+    rec = dict(what="k_chain_wave_bw_bf16<W> / k_chain_wave_partials_bf16<W> per register width, each next to its fp32 twin's VGPRs" + REMARKS, box=BOX,
+               file_flags=file_flags(f["file"]), lds_budget_bytes=f["LDS_BUDGET_BYTES"],
+               kernels={k: {str(w): dict(r[k][w], fp32_vgpr=fp32[k[:-5]][str(w)]["vgpr"]) for w in WMAX} for k in names})
+    rec["instantiations_with_scratch_or_static_lds"] = [f"{k}/{w}" for k in names for w in WMAX if r[k][w]["scratch"] or r[k][w]["lds_static"]]
+    rec["instantiations_with_fewer_waves_per_simd_than_fp32"] = [f"{k}/{w}" for k in names for w in WMAX
+                                                                 if r[k][w]["waves_per_simd"] < fp32[k[:-5]][str(w)]["waves_per_simd"]]
+    return rec
+
+
 def _chain(kernel, file, lds_budget, **more):
     """a Chain kernel k<WMAX, SRC> of one file: resources() is {src: {WMAX: {...}}}; the LDS is dynamic (at most LDS_BUDGET_BYTES)"""
     return dict(file=file, kernel=kernel, name=r"_ZN3gnx\d+" + kernel + r"ILi(\d+)ELi(\d+)EEEv", key=lambda m: (SRC[int(m.group(2))], int(m.group(1))),
@@ -269,6 +281,10 @@ FAMILIES = {
     "chain_bw_wave": dict(file="gnx_chain_bw_wave.hip", name=r"_ZN3gnx\d+(k_chain_wave_bw|k_chain_wave_partials|k_chain_graph_rows_wave)(?:ILi(\d+)EEEv|E)",
                           key=lambda m: (m.group(1), int(m.group(2) or 0)), fields=STATIC, record=_rec_chain_bw_wave,
                           KERNEL_NAMES=("k_chain_wave_bw", "k_chain_wave_partials"), LDS_BUDGET_BYTES=4 * 16384),
+    # its bf16 twin: the same text (csrc/gnx_chain_bw_wave_kernel.h) and the same LDS plan — everything in LDS stays fp32
+    "chain_bw_wave_bf16": dict(file="gnx_chain_bw_wave_bf16.hip", name=r"_ZN3gnx\d+(k_chain_wave_bw_bf16|k_chain_wave_partials_bf16)ILi(\d+)EEEv",
+                               key=lambda m: (m.group(1), int(m.group(2))), fields=STATIC, record=_rec_chain_bw_wave_bf16,
+                               KERNEL_NAMES=("k_chain_wave_bw_bf16", "k_chain_wave_partials_bf16"), LDS_BUDGET_BYTES=4 * 16384),
     # the two Chain training kernels (the layer code of chain_narrow / chain_bw_narrow with the Dropout op), 18 instantiations: none may use scratch
     # (include/gnx.h: a class that does is cut from the training rule); the record carries the test-mode twins' VGPRs next to each.
     # resources("chain_train_narrow", direction)
