@@ -152,6 +152,9 @@ SIGNATURES = {
     "gnx_chain_block_forward_wave_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
     "gnx_chain_block_forward_wave_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
     "gnx_chain_block_forward_wave": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams)] + _FWD[2:]),
+    "gnx_chain_block_forward_wide_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
+    "gnx_chain_block_forward_wide_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64]),
+    "gnx_chain_block_forward_wide": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams)] + _FWD[2:]),
     "gnx_chain_block_forward_wave_typed_applies": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
     "gnx_chain_block_forward_wave_typed_workspace_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int64, C.c_int32]),
     "gnx_chain_block_forward_wave_typed": (C.c_int32, [C.c_void_p, C.POINTER(ChainBlockParams), C.c_int32] + _FWD[2:]),

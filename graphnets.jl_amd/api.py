@@ -919,7 +919,7 @@ def _ptr0(t):
 # which C entry a call of a GNBlock / GNCore reaches: one table, plain data
 # ------------------------------------------------------------------------------------------------------------
 _SWITCHES = ("bf16", "bf16_backward", "fused_backward", "narrow_backward", "narrow_chain", "narrow_chain_backward", "bf16_chain", "native_chain_backward",
-             "chain_dropout", "typed_dropout", "wave_chain", "wave_chain_backward")
+             "chain_dropout", "typed_dropout", "wave_chain", "wave_chain_backward", "wide_chain")
 _Entry = collections.namedtuple("_Entry", "query query_tail call head tail key")
 _CHAIN_DROPOUT_IS_TEST_MODE = ("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
                                "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
@@ -947,7 +947,8 @@ def _entry(family, direction, elem, switches=(), record=False):
                            (which wins over `fused_backward`; either element type); bf16 needs `bf16_backward`
       chain     forward    an active record: gnx_chain_block_forward_train (narrow = `narrow_chain`; fp32 only); bf16 (needs `bf16_chain`):
                            gnx_chain_block_forward_wave_typed with `wave_chain`, else gnx_chain_block_forward_typed (narrow = `narrow_chain`);
-                           fp32: gnx_chain_block_forward_wave with `wave_chain` (which wins over `narrow_chain`),
+                           fp32: gnx_chain_block_forward_wide with `wide_chain` (_chain_forward hands it over only where that entry's
+                           _applies mask is non-zero), gnx_chain_block_forward_wave with `wave_chain` (which wins over `narrow_chain`),
                            gnx_chain_block_forward_narrow with `narrow_chain`, gnx_chain_block_forward
                 backward   (narrow = `narrow_chain_backward`) an active record: gnx_chain_block_backward_train; bf16 (needs `bf16_backward`):
                            gnx_chain_block_backward_wave_typed with `wave_chain_backward` (which wins over the two below),
@@ -989,6 +990,8 @@ def _entry(family, direction, elem, switches=(), record=False):
                 return E("gnx_chain_block_forward_wave_typed", (elem,), (elem,), fl, ("chain_wave_bf16", "in_dims", "widths", "R"))
             if bf16:  # (mirrors the entry `narrow_chain` selects)
                 return E("gnx_chain_block_forward_typed", (elem, n), (elem,), (n, "flags"), ("chain_bf16", bool(n), "in_dims", "widths", "R"))
+            if on("wide_chain"):
+                return E("gnx_chain_block_forward_wide", (), (), fl, ("chain_wide", "in_dims", "widths", "R"))
             if on("wave_chain"):
                 return E("gnx_chain_block_forward_wave", (), (), fl, ("chain_wave", "in_dims", "widths", "R"))
             if n:
@@ -1136,6 +1139,12 @@ class GNBlock:
     float32 copy of anything edge- or node-sized; outside that entry's rule the call is `bf16_chain` with `narrow_chain`.  The pullback is the
     one the other switches select.
 
+    `wide_chain` (gnx_chain_block_forward_wide): a float32 test-mode forward in which some update function is at matrix-core widths inside that
+    entry's rule (include/gnx.h: outside the narrow rule, at least two layers, input and layer widths up to 128) runs each such function in one
+    kernel that keeps the gathered input, every hidden row and every LayerNorm in LDS, each function inside the narrow rule as `narrow_chain`
+    does, the others as before.  Where the entry's mask is 0 — every block the wave rule takes included — on bfloat16 features and under an
+    active chain Dropout the call goes where it goes without the switch.  The pullback recomputes from the inputs and does not change.
+
     `narrow_chain_backward` (gnx_chain_block_backward_narrow; independent of `narrow_chain`): each update function inside its rule (include/gnx.h:
     the forward's rule and 64 KB of LDS for two waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled
     back in one kernel, a row per lane forward and back through all layers, with only what crosses levels recomputed into the workspace; the
@@ -1171,7 +1180,7 @@ class GNBlock:
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
                  narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False, chain_dropout=False,
-                 wave_chain=False, wave_chain_backward=False):
+                 wave_chain=False, wave_chain_backward=False, wide_chain=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -1193,6 +1202,7 @@ class GNBlock:
         self.chain_dropout = bool(chain_dropout)
         self.wave_chain = bool(wave_chain)
         self.wave_chain_backward = bool(wave_chain_backward)
+        self.wide_chain = bool(wide_chain)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1366,7 +1376,10 @@ def _chain_forward(block, g, R, flags, elem, rec, ef, nf, gf):
     drop = rec._c(keep) if train else None
     widths = tuple(tuple(k if k == "dropout" else int(l.weight.shape[0]) for k, l in ch._entries(train)) for ch in chains)
     env = dict(flags=flags, R=R, in_dims=block.in_dims, widths=widths, drop=C.byref(drop) if train else None)
-    return _forward(_entry("chain", "forward", elem, _switches(block), train), g, p, R, outw, elem, (ef, nf, gf), env, strict=True)
+    sw = _switches(block)
+    if "wide_chain" in sw and (train or elem != _lib.ELEM_F32 or _lib.load().gnx_chain_block_forward_wide_applies(g._h, C.byref(p), R) == 0):
+        sw = sw - {"wide_chain"}  # (no function inside the wide rule: the call goes where it goes without the switch)
+    return _forward(_entry("chain", "forward", elem, sw, train), g, p, R, outw, elem, (ef, nf, gf), env, strict=True)
 
 
 class _BlockFn(torch.autograd.Function):

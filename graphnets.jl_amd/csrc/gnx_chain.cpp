@@ -120,14 +120,16 @@ int32_t check_params(const gnx_graphs* h, const gnx_chain_block_params* p, int64
 
 namespace gnx {
 
-ChainPlan::ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3], bool train)
+ChainPlan::ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3], bool train,
+                     bool ask_wide)
     : rc(check_params(h, p0, R, train)) {
   if (rc) return;
   bf16 = elem == GNX_ELEM_BF16;
   query = query_of[bf16 ? 2 : narrow];
   sh = chain_shape(h->E, h->N, h->G, *p0, R);
   fused = narrow ? chain_fused_mask(sh, rule) : 0;
-  p = (fused & 1) ? p0 : lnf.init(p0, nullptr);  // (the identity layer's weights sit at a fixed place of the workspace: bind_ident)
+  wide = ask_wide && narrow && !train && !bf16 ? chain_wide_mask(sh) : 0;
+  p = ((fused | wide) & 1) ? p0 : lnf.init(p0, nullptr);  // (the identity layer's weights sit at a fixed place of the workspace: bind_ident)
   if (lnf.on) sh = chain_shape(h->E, h->N, h->G, *p, R);
 }
 // The refusals in include/gnx.h's order — the chains' arrays, every p_l, a missing p[t], the entries' places and shapes — then the copy.
@@ -229,16 +231,17 @@ struct ChainFwPlan : ChainPlan {
   // at the workspace's head — on bf16 features nothing else
   bool wave = false;
   ChainWs w{};
-  ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool train = false, bool ask_wave = false)
-      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_FW, kFwQuery, train) {
+  ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool train = false, bool ask_wave = false, bool ask_wide = false)
+      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_FW, kFwQuery, train, ask_wide) {
     native = !rc && bf16 && narrow && chain_typed_native(sh, fused);
     wave = !rc && ask_wave && narrow && !train &&
            (bf16 ? chain_wave_typed_takes(sh, h->max_in_degree, h->wtile_e_cap) : chain_wave_takes(sh, false, h->max_in_degree, h->wtile_e_cap));
     if (ask_wave) query = kFwWaveQuery[bf16];
+    if (ask_wide) query = "workspace missing or smaller than gnx_chain_block_forward_wide_workspace_bytes()";
   }
-  bool wide_tables() const { return chain_fw_reads_wide_tables(sh, fused); }
+  bool wide_tables() const { return chain_fw_reads_wide_tables(sh, fused | wide); }
   void lay_out(const gnx_graphs* h) {  // (the inner block's query builds what its edge update reads of the handle)
-    w = chain_fw_layout(sh, fused, lnf.ident_floats(), sh.ow[0] > 0 && !(fused & 1) ? gnx_block_workspace_bytes(h, &sh.edge_block, sh.R) : 0);
+    w = chain_fw_layout(sh, fused, lnf.ident_floats(), sh.ow[0] > 0 && !((fused | wide) & 1) ? gnx_block_workspace_bytes(h, &sh.edge_block, sh.R) : 0, wide);
     size_t counts[3];
     chain_native_counts(sh, counts);
     const int d[6] = {sh.de, sh.dn, sh.dg, sh.ow[0], sh.ow[1], sh.ow[2]};
@@ -263,12 +266,14 @@ int32_t chain_forward_fp32(const ChainFwCall& c, ChainFwPlan& pl, const float* e
   pl.bind_ident(F(w.ident));
   if ((rc = pl.lnf.fill(F(w.ident), s))) return rc;
   const gnx_chain_block_params* p = pl.p;
-  const unsigned fused = pl.fused;
+  const unsigned fused = pl.fused, wide = pl.wide;
   if (pl.wave) return launch_chain_wave(h, *p, pl.sh, ef, nf, gf, ef_out, nf_out, gf_out, reinterpret_cast<float*>(base), c.R, s);
   const int de = p->de, dn = p->dn, dg = p->dg, oe = pl.sh.ow[0], on = pl.sh.ow[1], og = pl.sh.ow[2], Kn = pl.sh.k0[1], Kg = pl.sh.k0[2];
   // ---- edge function (gnblock.jl:65): first Dense fused with getedgefninput, the rest row-wise ----
   if (fused & 1) {
     if ((rc = launch_chain_narrow(h, 0, p->edgefn, ef, de, nf, dn, gf, dg, ef_out, c.R, s, "k_rows_gemm_chain_e"))) return rc;
+  } else if (wide & 1) {
+    if ((rc = launch_chain_wide(h, 0, p->edgefn, ef, de, nf, dn, gf, dg, ef_out, c.R, s, "k_rows_gemm_chain_e"))) return rc;
   } else if (oe > 0 && h->E > 0) {
     float* first_out = p->edgefn.n_layers == 1 ? ef_out : F(w.e_buf[0]);
     if ((rc = gnx_block_forward(h, &pl.sh.edge_block, ef, nf, gf, c.R, first_out, nullptr, nullptr, base + w.block.off, w.block.bytes, c.flags, c.stream))) return rc;
@@ -283,13 +288,17 @@ int32_t chain_forward_fp32(const ChainFwCall& c, ChainFwPlan& pl, const float* e
   } else if (on > 0) {
     if ((rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, c.R, F(w.n_in), s))) return rc;
     float* const bufs[2] = {F(w.n_buf[0]), F(w.n_buf[1])};
-    if ((rc = run_layers(h, 1, p->nodefn, 0, F(w.n_in), Kn, bufs, nf_out, c.R, s, "k_rows_gemm_chain_n"))) return rc;
+    if (wide & 2) rc = launch_chain_wide(h, 1, p->nodefn, F(w.n_in), Kn, nullptr, 0, nullptr, 0, nf_out, c.R, s, "k_rows_gemm_chain_n");
+    else rc = run_layers(h, 1, p->nodefn, 0, F(w.n_in), Kn, bufs, nf_out, c.R, s, "k_rows_gemm_chain_n");
+    if (rc) return rc;
   }
   // ---- graph function (gnblock.jl:67): NEW ef', NEW nf', OLD gf ----
   if (og > 0) {
     if ((rc = launch_fn_input(h, 2, ef_out, oe, nf_out, on, gf, dg, c.R, F(w.g_in), s))) return rc;
     if (fused & 4) {
       if ((rc = launch_chain_narrow(h, 2, p->graphfn, F(w.g_in), Kg, nullptr, 0, nullptr, 0, gf_out, c.R, s, "k_rows_gemm_chain_g"))) return rc;
+    } else if (wide & 4) {
+      if ((rc = launch_chain_wide(h, 2, p->graphfn, F(w.g_in), Kg, nullptr, 0, nullptr, 0, gf_out, c.R, s, "k_rows_gemm_chain_g"))) return rc;
     } else {
       float* const bufs[2] = {F(w.g_buf[0]), F(w.g_buf[1])};
       if ((rc = run_layers(h, 2, p->graphfn, 0, F(w.g_in), Kg, bufs, gf_out, c.R, s, "k_rows_gemm_chain_g"))) return rc;
@@ -327,8 +336,8 @@ int32_t chain_forward_native(const ChainFwCall& c, const ChainFwPlan& pl) {
 // One Chain forward call: validate and plan, the refusals that read nothing of the handle but its counts — NULL features, bf16 alignment — the
 // layout, the workspace refusal, the plan's tables; then the plan's form.  A staged bf16 call widens into the workspace, runs the fp32 launches on
 // the copies and rounds the outputs.
-int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false, bool wave = false) {
-  ChainFwPlan pl(c.h, c.p, c.R, c.elem, narrow, train, wave);
+int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false, bool wave = false, bool wide = false) {
+  ChainFwPlan pl(c.h, c.p, c.R, c.elem, narrow, train, wave, wide);
   if (pl.rc) return pl.rc;
   if (train) pl.query = "workspace missing or smaller than gnx_chain_block_forward_train_workspace_bytes()";
   const hipStream_t s = (hipStream_t)c.stream;
@@ -354,8 +363,8 @@ int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false, bool
 }
 
 // a _workspace_bytes entry: the plan's total, and the plan's tables built here, outside any capture (a failure resurfaces in the call)
-size_t chain_fw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool train = false, bool wave = false) {
-  ChainFwPlan pl(h, p, R, elem, narrow, train, wave);
+size_t chain_fw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool train = false, bool wave = false, bool wide = false) {
+  ChainFwPlan pl(h, p, R, elem, narrow, train, wave, wide);
   if (pl.rc) return 0;
   pl.lay_out(h);
   if (pl.wide_tables()) (void)gnx_ensure_wide_tables(h);
@@ -400,6 +409,20 @@ size_t gnx_chain_block_forward_wave_workspace_bytes(const gnx_graphs* h, const g
 int32_t gnx_chain_block_forward_wave(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
                                      float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
   return chain_fw_run(ChainFwCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true, false, true);
+}
+
+// gnx_chain_block_forward_wide: the narrow entry, its plan asked for the wide mask — each function inside chain_wide_takes in one k_chain_wide launch
+int32_t gnx_chain_block_forward_wide_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return (int32_t)ChainFwPlan(h, p, R, GNX_ELEM_F32, true, false, false, true).wide;  // (the constructor reads the handle's counts alone; refused: 0)
+}
+
+size_t gnx_chain_block_forward_wide_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return chain_fw_query(h, p, R, GNX_ELEM_F32, true, false, false, true);
+}
+
+int32_t gnx_chain_block_forward_wide(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
+                                     float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  return chain_fw_run(ChainFwCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true, false, false, true);
 }
 
 // gnx_chain_block_forward_wave_typed: the wave entry on fp32 or bf16 features; bf16 outside chain_wave_typed_takes: the typed entry with narrow = 1

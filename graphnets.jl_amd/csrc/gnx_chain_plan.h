@@ -154,6 +154,66 @@ inline unsigned chain_fused_mask(const ChainShape& s, ChainRule rule) {
   return m;
 }
 
+// ---- the wide form (gnx_chain_block_forward_wide; gnx_chain_wide.hip): one update function at matrix-core widths in one kernel ----
+constexpr int kChainWideMaxWidth = 128;    // input width and every layer width of a function the kernel takes
+constexpr int kChainWideLdsFloats = 16384; // the weight chunk, the bias row and every wave's slice: 64 KB
+constexpr int kChainWideRows = 32;         // rows a wave owns through all layers
+constexpr int ceil16(int x) { return (x + 15) & ~15; }
+constexpr int ceil32(int x) { return (x + 31) & ~31; }
+// The LDS plan of k_chain_wide, in floats: the weight chunk — 16 reduction steps of the widest Dense as three bf16 planes [3][np][16] — then the
+// bias row [np], then per wave a slice [32][ld] fp32 that holds the wave's rows through all layers.  ld: odd, from the largest 16-padded width.
+// waves: per workgroup, as many slices as fit 64 KB, at most 4 — the rule takes a function from 2 on.  nb: 32-column accumulator blocks of the
+// widest Dense (the kernel's template class: 1 or 2 inside the rule; 3 and 4 count as 4, the class chain_wide_cut cuts).
+struct ChainWideShape {
+  int ld, waves, nb, np, chunk_floats, bias_off, slice_off, floats;
+  size_t nwg;  // workgroups per replica: a wave takes 32 rows
+};
+inline ChainWideShape chain_wide_shape(const gnx_chain& c, int k_in, size_t rows) {
+  ChainWideShape w{};
+  int maxw = k_in, maxd = 1;
+  for (int i = 0; i < c.n_layers; ++i) {
+    maxw = std::max(maxw, (int)c.widths[i]);
+    if (!chain_layer_is_ln(c.layers[i]) && !chain_layer_is_dropout(c.layers[i])) maxd = std::max(maxd, (int)c.widths[i]);
+  }
+  w.ld = ceil16(maxw) | 1;
+  w.np = ceil32(maxd);
+  w.nb = w.np / 32 == 3 ? 4 : w.np / 32;
+  w.chunk_floats = 3 * w.np * 8;  // (16 bf16 = 8 floats per column and plane)
+  w.bias_off = w.chunk_floats;
+  w.slice_off = w.bias_off + w.np;
+  w.waves = std::min(4, std::max(0, (kChainWideLdsFloats - w.slice_off) / (kChainWideRows * w.ld)));
+  w.floats = w.slice_off + w.waves * kChainWideRows * w.ld;
+  if (w.waves > 0) w.nwg = (rows + (size_t)kChainWideRows * w.waves - 1) / ((size_t)kChainWideRows * w.waves);
+  return w;
+}
+// The class CUT from the wide rule: a widest Dense beyond 64 columns (three or four accumulator blocks), in either source form, on one graph and
+// on several.  Measured (profiles/chain_wide.json, whole calls, cache-cold, medians of 15, against the parent's gnx_chain_block_forward; the
+// record was taken before the cut): its instantiation took 200 VGPRs + 64 AGPRs — one workgroup of three waves per CU — and on the 512-graph
+// 1M-edge batch (10,5,3) [128,ln,128,3]/[128,4]/[5] took 2.152 against 1.135 ms (spread 0.024), (32,32,8) [128,128,32]/[128,32]/[64,8] 3.563
+// against 1.619 (0.035); on the one-graph 1M-edge batch 5.344 against 4.395 (0.131) and 49.94 against 48.04 (0.93).  The two-block class stays:
+// (10,5,0) [64,3]/[64,4]/[32,5] 0.251 against 0.263 ms (0.027) and 3.457 against 3.453 (0.102), (10,5,3) [64,64,3]/[64,4]/[16,5] 0.371 against
+// 0.416 (0.030) and 3.560 against 3.615 (0.090).  Not measured: the one-block class (every Dense at most 32 columns behind a wider input or
+// LayerNorm), and the graph function's rows form on its own (its only case sat in a block whose edge and node function are of the cut class).
+inline bool chain_wide_cut(const gnx_chain& c, int k_in) { return chain_wide_shape(c, k_in, 1).np > 64; }
+// is the function run by k_chain_wide (gnx_chain_block_forward_wide; include/gnx.h states the rule): outside chain_narrow_takes; at least two
+// Dense / LayerNorm entries and no Dropout entry; a non-zero output width and rows to run on; 1 <= k_in <= 128 and every layer width <= 128; the
+// LDS plan above at two waves at least; not of the class chain_wide_cut names.
+inline bool chain_wide_takes(const gnx_chain& c, int k_in, size_t entity_rows) {
+  if (c.n_layers < 2 || c.n_layers > kChainMaxLayers || !c.layers || !c.widths || entity_rows == 0) return false;
+  if (chain_narrow_takes(c, k_in, entity_rows) || chain_has_dropout(c)) return false;
+  if (c.widths[c.n_layers - 1] <= 0 || k_in < 1 || k_in > kChainWideMaxWidth) return false;
+  for (int i = 0; i < c.n_layers; ++i)
+    if (c.widths[i] < 1 || c.widths[i] > kChainWideMaxWidth) return false;
+  return chain_wide_shape(c, k_in, entity_rows).waves >= 2 && !chain_wide_cut(c, k_in);
+}
+// the functions of a block the wide kernel runs: bit 0 edge, 1 node, 2 graph.  `s`: the shape of the caller's own parameters
+inline unsigned chain_wide_mask(const ChainShape& s) {
+  unsigned m = 0;
+  for (int t = 0; t < 3; ++t)
+    if (chain_wide_takes(*s.ch[t], s.k0[t], s.trows[t])) m |= 1u << t;
+  return m;
+}
+
 // ---- the wave form (gnx_chain_block_forward_wave; gnx_chain_wave.hip): the edge and the node function in one wave-per-tile kernel ----
 constexpr int kChainWaveLdsFloats = 16384;  // both functions' parameters + every wave's ef' rows: 64 KB
 // floats between two ef' rows of a wave's LDS slice: odd, so that 64 lanes on 64 different rows of one column meet in no bank
@@ -252,13 +312,17 @@ struct ChainWs {
   ChainCarve ident;  // the identity layer of a LayerNorm-first edge function (ChainLnFirst)
   size_t total;
 };
-inline ChainWs chain_fw_layout(const ChainShape& s, unsigned fused, size_t ident_floats, size_t block_bytes) {
+// wide: the mask of chain_wide_mask (gnx_chain_block_forward_wide) — such a function has its rows in LDS: none of those buffers either; the
+// node function keeps its materialised input rows n_in.
+inline ChainWs chain_fw_layout(const ChainShape& s, unsigned fused, size_t ident_floats, size_t block_bytes, unsigned wide = 0) {
   ChainWs w{};
   ChainCarver c;
   const int on = s.ow[1], og = s.ow[2];
+  const unsigned narrow = fused;
+  fused |= wide;
   w.block = c.bytes(block_bytes);
   for (int i = 0; i < 2; ++i) w.e_buf[i] = c.floats(s.ch[0]->n_layers > 1 && !(fused & 1) ? s.rows[0] * s.maxw[0] : 0);
-  w.n_in = c.floats(on > 0 && !(fused & 2) ? s.rows[1] * (size_t)s.k0[1] : 0);
+  w.n_in = c.floats(on > 0 && !(narrow & 2) ? s.rows[1] * (size_t)s.k0[1] : 0);
   for (int i = 0; i < 2; ++i) w.n_buf[i] = c.floats(s.ch[1]->n_layers > 1 && !(fused & 2) ? s.rows[1] * s.maxw[1] : 0);
   w.g_in = c.floats(og > 0 ? s.rows[2] * (size_t)s.k0[2] : 0);
   for (int i = 0; i < 2; ++i) w.g_buf[i] = c.floats(s.ch[2]->n_layers > 1 && !(fused & 4) ? s.rows[2] * s.maxw[2] : 0);

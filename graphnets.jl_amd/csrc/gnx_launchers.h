@@ -182,6 +182,11 @@ int32_t launch_core_post_train(const void* x, size_t rows, int d, const gnx_laye
 // entity 0: in0 / in1 / in2 = ef, nf, gf (widths d0, d1, d2); 1: ef', nf, gf; 2: in0 = the materialised [R G][d0] input rows (d1 = d2 = 0)
 int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                             float* out, int64_t R, hipStream_t s, const char* name);
+// ---- gnx_chain_wide.hip: one update function of a Chain block at matrix-core widths in one kernel (gnx_chain_block_forward_wide) ----
+// entity 0: in0 / in1 / in2 = ef, nf, gf (widths d0, d1, d2); 1, 2: in0 = the materialised [R rows][d0] input rows (d1 = d2 = 0).  The caller
+// asked chain_wide_takes (gnx_chain_plan.h)
+int32_t launch_chain_wide(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
+                          float* out, int64_t R, hipStream_t s, const char* name);
 // ---- gnx_chain_wave.hip: the edge and the node function of a Chain block in one wave-per-tile kernel, the graph function from its partial rows
 //      (gnx_chain_block_forward_wave).  The caller asked chain_wave_takes; sh: the shape of p; partials: chain_wave_partial_floats(sh, ...) floats ----
 int32_t launch_chain_wave(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const float* ef, const float* nf, const float* gf, float* ef_out,

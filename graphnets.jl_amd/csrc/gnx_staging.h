@@ -71,12 +71,13 @@ inline int32_t stage_round(const Staging& st, void* ws, const void* const* bufs,
 // `train`: the call came through a training entry (ChainTrain below) — its chains may hold Dropout entries.
 struct ChainPlan {
   ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, ChainRule rule, const char* const query_of[3],
-            bool train = false);
+            bool train = false, bool ask_wide = false);
   int32_t rc;  // the validation's; not GNX_OK: nothing below is set
   ChainLnFirst lnf;
   const gnx_chain_block_params* p = nullptr;
   ChainShape sh{};
   unsigned fused = 0;
+  unsigned wide = 0;  // the functions k_chain_wide runs (gnx_chain_block_forward_wide: fp32, test mode), disjoint from `fused`
   bool bf16 = false;
   Staging st{};                // a bf16 call: the fp32 carves behind the fp32 layout
   size_t base = 0, total = 0;  // the fp32 layout's total; what the entry's _workspace_bytes returns

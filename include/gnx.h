@@ -439,6 +439,29 @@ GNX_API size_t gnx_chain_block_forward_wave_workspace_bytes(const gnx_graphs* h,
 GNX_API int32_t gnx_chain_block_forward_wave(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
                                      int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out, void* workspace, size_t workspace_bytes,
                                      uint32_t flags, void* stream);
+/* The narrow entry with a second mask: each update function at MATRIX-CORE widths in ONE kernel (csrc/gnx_chain_wide.hip).  A workgroup of 2-4
+ * wavefronts takes 32 rows per wavefront; a wavefront owns its rows through all layers in an LDS slice [32][ld] fp32 — the gathered edge input
+ * [ef ; nf[src] ; nf[dst] ; gf_g] (the node and the graph function: their materialised input rows), every hidden row and every LayerNorm stay
+ * on chip, memory sees the function's input once and its output once.  Dense layers run on v_mfma_f32_32x32x16_bf16 as six terms of the exact
+ * three-way bf16 split (the library's default arithmetic: within its 1e-5 bound of the float64 result, not gnx_chain_block_forward's bits), the
+ * weights staged through LDS in chunks of 16 reduction steps; a LayerNorm as the edge function's first layer runs in the kernel, no identity
+ * Dense in front.  GNX_FLAG_FP32_MFMA and the other per-call form flags select nothing inside a function this kernel takes: it ignores them.
+ * The rule is per update function (_applies: bit 0 the edge, bit 1 the node, bit 2 the graph function; 0 on bad arguments).  A function is
+ * taken when it is NOT inside gnx_chain_block_forward_narrow's rule, has at least two entries (Dense or LayerNorm) and no Dropout entry, a
+ * non-zero output width and rows to run on, 1 <= input width <= 128 and every layer width in 1..128, and its LDS plan fits 64 KB at two
+ * wavefronts at least: 24 * np floats of weight chunk (np = the widest Dense rounded up to 32 columns) + np of bias + waves * 32 * ld of
+ * slices, ld = (the largest of the input and layer widths rounded up to 16) | 1; waves = as many as fit, at most 4.  One class is cut,
+ * measured slower than gnx_chain_block_forward on one graph and on several: a function with a Dense layer wider than 64 (np > 64).
+ * A function inside the narrow rule runs k_chain_mlp as in the narrow entry, anything else gnx_chain_block_forward's launches, bit for bit.
+ * _workspace_bytes: a function of either mask has none of the block workspace / hidden-row buffers (a wide node function keeps its N input
+ * rows, the graph function its G input rows); it builds the handle's tables the call reads, so call it outside a stream capture.  Under the
+ * profiler the launches report as k_rows_gemm_chain_e / _n / _g.  Arguments and refusals as gnx_chain_block_forward, a short workspace naming
+ * gnx_chain_block_forward_wide_workspace_bytes(). */
+GNX_API int32_t gnx_chain_block_forward_wide_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API size_t gnx_chain_block_forward_wide_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API int32_t gnx_chain_block_forward_wide(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                     int64_t n_replicas, float* ef_out, float* nf_out, float* gf_out, void* workspace, size_t workspace_bytes,
+                                     uint32_t flags, void* stream);
 /* Either Chain forward on float32 or bfloat16 features.  `elem` (GNX_ELEM_*) applies to the three feature inputs and the three outputs; weights
  * stay float32.  `narrow` (0 or 1) selects the entry the call mirrors: gnx_chain_block_forward (0) or gnx_chain_block_forward_narrow (1).
  * GNX_ELEM_F32 IS the mirrored entry: same validation, same workspace size, same bits.  Any other elem than F32 / BF16: the call returns

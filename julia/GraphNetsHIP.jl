@@ -24,7 +24,7 @@ module GraphNetsHIP
 export GNGraphBatch, batch, unbatch, getedgefninput, getnodefninput, getgraphfninput, GNBlock, zerodim2nothing, GNCore, GNCoreList,
        efview, nfview, gfview, flatunpaddednf, flatunpaddedef, collapsef, unpaddedcollapsedef, flatunpaddedcollapsedef
 # ... plus what the drop-in adds: layers as plain structs, pullbacks, the library-side hipGraph model, the multi-GPU split
-export Dense, LayerNorm, ChainBlock, chain_forward, chain_narrow_applies, chain_wave_applies, chain_pullback, chain_backward, chain_backward_narrow_applies, chain_backward_wave_applies, block_pullback, core_pullback, Model, partition_graphs, DistBlock
+export Dense, LayerNorm, ChainBlock, chain_forward, chain_narrow_applies, chain_wave_applies, chain_wide_applies, chain_pullback, chain_backward, chain_backward_narrow_applies, chain_backward_wave_applies, block_pullback, core_pullback, Model, partition_graphs, DistBlock
 # ... and device residency: `x |> batch |> gpu`, `model |> gpu`, `y |> cpu` (what Flux's `gpu` / `cpu` are to the reference)
 export DeviceArray, gpu, cpu, synchronize, chained, flush, steps
 
@@ -847,7 +847,10 @@ end
 # lane through all layers), the others as before; a workspace key of its own
 # wave = true (wins over narrow): gnx_chain_block_forward_wave — where the whole block is inside the wave rule (include/gnx.h) the edge and the node
 # function run in one wave-per-tile kernel and the graph function from its partial rows; elsewhere the narrow entry's launches
-function chain_device(m::ChainBlock, x; narrow::Bool=false, wave::Bool=false)
+# wide = true (wins over both): gnx_chain_block_forward_wide — the narrow entry with each update function at matrix-core widths inside its rule
+# (include/gnx.h) in one kernel that keeps the function's input, hidden rows and LayerNorms in LDS
+function chain_device(m::ChainBlock, x; narrow::Bool=false, wave::Bool=false, wide::Bool=false)
+    wide && return chain_device_wide(m, x)
     wave && return chain_device_wave(m, x)
     g::GNGraphBatch = x.graphs
     R = replicas(x.ef, x.nf, x.gf)
@@ -866,6 +869,27 @@ function chain_device(m::ChainBlock, x; narrow::Bool=false, wave::Bool=false)
         (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cvoid}, Csize_t, UInt32, Ptr{Cvoid}),
         g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, UInt32(0), STREAM[]))
     (graphs=g, ef=o[1], nf=o[2], gf=o[3])
+end
+function chain_device_wide(m::ChainBlock, x)
+    g::GNGraphBatch = x.graphs
+    R = replicas(x.ef, x.nf, x.gf)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    oe, on, og = outwidth(m.edgefn), outwidth(m.nodefn), outwidth(m.graphfn)
+    ws = workspace!(g, (:chain_wide, chainkey(m), R)) do
+        ccall((:gnx_chain_block_forward_wide_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R)
+    end
+    o = (outarray(oe, nedges(g), R), outarray(on, nnodes(g), R), outarray(og, ngraphs(g), R))
+    GC.@preserve m keep x o ws check(ccall((:gnx_chain_block_forward_wide, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cvoid}, Csize_t, UInt32, Ptr{Cvoid}),
+        g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, UInt32(0), STREAM[]))
+    (graphs=g, ef=o[1], nf=o[2], gf=o[3])
+end
+# which update functions gnx_chain_block_forward_wide runs in its matrix-core kernel on this batch: bit 0 edge, bit 1 node, bit 2 graph
+function chain_wide_applies(m::ChainBlock, x)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    GC.@preserve m keep ccall((:gnx_chain_block_forward_wide_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
 end
 # Through gnx_chain_block_forward_wave_typed: the shim's arrays are Float32, so it passes GNX_ELEM_F32 — then the call IS
 # gnx_chain_block_forward_wave (same workspace size, same bits); with bfloat16 device buffers the same argument list takes GNX_ELEM_BF16 and
@@ -898,7 +922,7 @@ function chain_narrow_applies(m::ChainBlock, x)
     GC.@preserve m keep ccall((:gnx_chain_block_forward_narrow_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
 end
 (m::ChainBlock)(x) = back(chain_device(gpu(m), gpu(x)), x)
-chain_forward(m::ChainBlock, x; narrow::Bool=false, wave::Bool=false) = back(chain_device(gpu(m), gpu(x); narrow=narrow, wave=wave), x)
+chain_forward(m::ChainBlock, x; narrow::Bool=false, wave::Bool=false, wide::Bool=false) = back(chain_device(gpu(m), gpu(x); narrow=narrow, wave=wave, wide=wide), x)
 # pullback: gradients w.r.t. the inputs and every layer's (weight, bias); the forward is recomputed inside the library
 # narrow = true: gnx_chain_block_backward_narrow — every update function inside its rule (include/gnx.h) is pulled back in one kernel, the others as
 # before; a workspace key of its own
