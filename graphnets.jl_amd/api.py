@@ -919,7 +919,7 @@ def _ptr0(t):
 # which C entry a call of a GNBlock / GNCore reaches: one table, plain data
 # ------------------------------------------------------------------------------------------------------------
 _SWITCHES = ("bf16", "bf16_backward", "fused_backward", "narrow_backward", "narrow_chain", "narrow_chain_backward", "bf16_chain", "native_chain_backward",
-             "chain_dropout", "typed_dropout", "wave_chain", "wave_chain_backward", "wide_chain")
+             "chain_dropout", "typed_dropout", "wave_chain", "wave_chain_backward", "wide_chain", "wide_chain_backward")
 _Entry = collections.namedtuple("_Entry", "query query_tail call head tail key")
 _CHAIN_DROPOUT_IS_TEST_MODE = ("GNBlock: a Dropout(p > 0) inside an update-function Chain is the identity in test mode only; a differentiable "
                                "call would train another model — use GNCore(dims; dropout = p) for the FeedForward's Dropout")
@@ -953,8 +953,9 @@ def _entry(family, direction, elem, switches=(), record=False):
                 backward   (narrow = `narrow_chain_backward`) an active record: gnx_chain_block_backward_train; bf16 (needs `bf16_backward`):
                            gnx_chain_block_backward_wave_typed with `wave_chain_backward` (which wins over the two below),
                            gnx_chain_block_backward_narrow_typed with `native_chain_backward`, else gnx_chain_block_backward_typed; fp32:
-                           gnx_chain_block_backward_wave with `wave_chain_backward` (which wins over `narrow_chain_backward`), else
-                           gnx_chain_block_backward_narrow or gnx_chain_block_backward
+                           gnx_chain_block_backward_wide with `wide_chain_backward` (which wins over the two below; _chain_backward hands it
+                           over only where that entry's _applies mask is non-zero), gnx_chain_block_backward_wave with `wave_chain_backward`
+                           (which wins over `narrow_chain_backward`), else gnx_chain_block_backward_narrow or gnx_chain_block_backward
       core      forward    an active record: gnx_core_forward_train_typed with `typed_dropout`, else gnx_core_forward_train (fp32 only); no record:
                            gnx_core_forward, bf16: gnx_core_forward_typed
                 backward   in this order: an active record with `typed_dropout`: gnx_core_backward_train_typed (narrow = `narrow_backward`);
@@ -1010,6 +1011,8 @@ def _entry(family, direction, elem, switches=(), record=False):
             return E("gnx_chain_block_backward_narrow_typed", (elem,), (elem,))
         if bf16:  # (mirrors the pullback `narrow_chain_backward` selects)
             return E("gnx_chain_block_backward_typed", (elem, n), (elem,), (n,))
+        if on("wide_chain_backward"):
+            return E("gnx_chain_block_backward_wide")
         if on("wave_chain_backward"):
             return E("gnx_chain_block_backward_wave")
         return E("gnx_chain_block_backward_narrow" if n else "gnx_chain_block_backward")
@@ -1145,6 +1148,14 @@ class GNBlock:
     does, the others as before.  Where the entry's mask is 0 — every block the wave rule takes included — on bfloat16 features and under an
     active chain Dropout the call goes where it goes without the switch.  The pullback recomputes from the inputs and does not change.
 
+    `wide_chain_backward` (gnx_chain_block_backward_wide; independent of `wide_chain`, wins over `wave_chain_backward` and
+    `narrow_chain_backward`): in a float32 test-mode pullback each update function at matrix-core widths inside that entry's rule (include/gnx.h:
+    the wide forward's rule, at most 8 entries, two LDS tapes of 32 rows within 64 KB, e.g. [64, 64, 3] behind a 20-wide input) is pulled back
+    in one persistent kernel that keeps the recomputed rows, the deltas and the LayerNorm statistics in LDS and the parameter-gradient
+    accumulators in registers; each function inside the narrow rule as `narrow_chain_backward` does, the others as before.  Where the entry's
+    mask is 0, on bfloat16 features and under an active chain Dropout the call goes where it goes without the switch.  The gradients are within
+    the generic pullback's error of the exact ones, not its bits.
+
     `narrow_chain_backward` (gnx_chain_block_backward_narrow; independent of `narrow_chain`): each update function inside its rule (include/gnx.h:
     the forward's rule and 64 KB of LDS for two waves' row tapes and accumulators, e.g. [16, 3] or [16, ln, 16, 3] behind a 23-wide input) is pulled
     back in one kernel, a row per lane forward and back through all layers, with only what crosses levels recomputed into the workspace; the
@@ -1180,7 +1191,7 @@ class GNBlock:
 
     def __init__(self, in_dims, out_dims=None, dropout=0, device=None, generator=None, act=("identity",) * 3, bf16_backward=False, fused_backward=False,
                  narrow_backward=False, narrow_chain=False, narrow_chain_backward=False, bf16_chain=False, native_chain_backward=False, chain_dropout=False,
-                 wave_chain=False, wave_chain_backward=False, wide_chain=False):
+                 wave_chain=False, wave_chain_backward=False, wide_chain=False, wide_chain_backward=False):
         in_dims, out_dims = _pair(in_dims, out_dims)
         assert any(d > 0 for d in in_dims)  # gnblock.jl:48
         assert any(d > 0 for d in out_dims)  # gnblock.jl:49
@@ -1203,6 +1214,7 @@ class GNBlock:
         self.wave_chain = bool(wave_chain)
         self.wave_chain_backward = bool(wave_chain_backward)
         self.wide_chain = bool(wide_chain)
+        self.wide_chain_backward = bool(wide_chain_backward)
 
     def _c(self, keep):
         p = _lib.BlockParams()
@@ -1469,6 +1481,14 @@ def _chain_grad_slots(chains, need, train, device):
     return gW, gb, _lib.ChainBlockGrads(*[C.cast(a, C.POINTER(_lib.DenseGrad)) for a in arrays]), arrays
 
 
+def _chain_backward(block, g, p, R, elem, train):
+    """the switches a Chain pullback is entered with: `wide_chain_backward` only where gnx_chain_block_backward_wide takes a function"""
+    sw = _switches(block)
+    if "wide_chain_backward" in sw and (train or elem != _lib.ELEM_F32 or _lib.load().gnx_chain_block_backward_wide_applies(g._h, C.byref(p), R) == 0):
+        sw = sw - {"wide_chain_backward"}  # (no function inside the wide rule: the call goes where it goes without the switch)
+    return sw
+
+
 def _chain_block_pullback(ctx, gouts):
     block, g, R, train = ctx.owner, ctx.g, ctx.R, ctx.rec is not None
     (ef, nf, gf), cots = _recall(ctx, gouts)
@@ -1478,7 +1498,7 @@ def _chain_block_pullback(ctx, gouts):
     d = [torch.empty_like(a) if a is not None and n else None for a, n in zip((ef, nf, gf), need)]
     gW, gb, grads, slots = _chain_grad_slots(chains, need[3:], train, g.device)
     drop = ctx.rec._c(keep) if train else None
-    _pullback(_entry("chain", "backward", ctx.elem, _switches(block), train), g, p, R,
+    _pullback(_entry("chain", "backward", ctx.elem, _chain_backward(block, g, p, R, ctx.elem, train), train), g, p, R,
               (*map(_ptr, (ef, nf, gf)), *map(_ptr, cots), R, *map(_ptr, d), C.byref(grads)), {"drop": C.byref(drop) if train else None}, strict=True)
     return (*_NO_GRAD, *d, *(t for wb in zip(gW, gb) for t in wb))
 

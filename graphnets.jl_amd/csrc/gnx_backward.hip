@@ -1373,8 +1373,9 @@ struct ChainBwPlan : ChainPlan {
   ChainBwWaveLayout WL{};
   bool on_bf16() const { return native || wave_bf16; }  // the launches read and write the caller's bf16 tensors themselves
   ChainBwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false,
-              bool ask_wave = false)
-      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery, train) {
+              bool ask_wave = false, bool ask_wide = false)
+      : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_BW, kBwQuery, train, ask_wide) {
+    if (!rc && wide) query = "workspace missing or smaller than gnx_chain_block_backward_wide_workspace_bytes()";  // (mask 0: the narrow entry's call, its query)
     if (!rc && train) query = "workspace missing or smaller than gnx_chain_block_backward_train_workspace_bytes()";
     if (!rc && ask_wave) {
       wave = narrow && !train && (!bf16 || narrow_typed) && chain_bw_wave_takes(sh, bf16, h->max_in_degree, h->wtile_e_cap, h->n_wtiles());
@@ -1394,9 +1395,9 @@ struct ChainBwPlan : ChainPlan {
       base = WL.total; total = wave_bf16 ? T.total : WL.total;
       return;
     }
-    const bool blk = !(fused & 1) && sh.ch[0]->n_layers > 0;  // the first Dense of a generic edge function: the one-layer block, forward and pullback
+    const bool blk = !((fused | wide) & 1) && sh.ch[0]->n_layers > 0;  // the first Dense of a generic edge function: the one-layer block, forward and pullback
     L = chain_bw_layout(sh, fused, lnf.ident_floats(), blk ? gnx_block_workspace_bytes(h, &sh.edge_block, sh.R) : 0,
-                        blk ? gnx_block_backward_workspace_bytes(h, &sh.edge_block, sh.R) : 0, BW_CH, dw_mfma_partial_floats);
+                        blk ? gnx_block_backward_workspace_bytes(h, &sh.edge_block, sh.R) : 0, BW_CH, dw_mfma_partial_floats, wide);
     if (native) {
       nw = chain_bw_native_layout(sh, L.total);
       base = L.total; total = nw.total;
@@ -1470,7 +1471,9 @@ bool chain_wants_grads(const gnx_chain& c, const gnx_dense_grad* grads) {
 int32_t ChainBwCtx::recompute() {
   const gnx_chain &ce = ch(0), &cn = ch(1), &cg = ch(2);
   int32_t rc;
-  if (fused & 1) {
+  if (pl.wide & 1) {
+    if ((on > 0 || og > 0) && (rc = launch_chain_wide(h, 0, ce, ef, de, nf, dn, gf, dg, A(0, ce.n_layers - 1), R, s, "bw_chain_fw_e"))) return rc;
+  } else if (fused & 1) {
     if ((on > 0 || og > 0) && (rc = pl.native ? launch_chain_narrow_bf16(h, 0, ce, ef, de, nf, dn, gf, dg, nullptr, A(0, ce.n_layers - 1), R, s, "bw_chain_fw_e")
                                               : launch_chain_narrow(h, 0, ce, ef, de, nf, dn, gf, dg, A(0, ce.n_layers - 1), R, s, "bw_chain_fw_e"))) return rc;
   } else if (h->E > 0) {
@@ -1480,7 +1483,10 @@ int32_t ChainBwCtx::recompute() {
   }
   ef_out = A(0, ce.n_layers - 1);
   nf_out = on > 0 ? A(1, cn.n_layers - 1) : nullptr;
-  if ((fused & 2) && !chain_bw_node_fw_generic(fused, og)) {
+  if (pl.wide & 2) {  // its input rows stay (the kernel's SRC_ROWS form reads them); nf' only for the graph function's input
+    if ((rc = launch_fn_input(h, 1, ef_out, oe, nf, dn, gf, dg, R, Xn, s))) return rc;
+    if (og > 0 && (rc = launch_chain_wide(h, 1, cn, Xn, Kn, nullptr, 0, nullptr, 0, A(1, cn.n_layers - 1), R, s, "bw_chain_fw_n"))) return rc;
+  } else if ((fused & 2) && !chain_bw_node_fw_generic(fused, og)) {
     if (og > 0 && (rc = pl.native ? launch_chain_narrow_bf16(h, 1, cn, ef_out, oe, nf, dn, gf, dg, nullptr, A(1, cn.n_layers - 1), R, s, "bw_chain_fw_n")
                                   : launch_chain_narrow(h, 1, cn, ef_out, oe, nf, dn, gf, dg, A(1, cn.n_layers - 1), R, s, "bw_chain_fw_n"))) return rc;
   } else if (on > 0) {
@@ -1490,7 +1496,7 @@ int32_t ChainBwCtx::recompute() {
   }
   if (og > 0) {
     if ((rc = launch_fn_input(h, 2, ef_out, oe, nf_out, on, gf_rows, dg, R, Xg, s))) return rc;
-    for (int i = 0; i < cg.n_layers && !(fused & 4); ++i)
+    for (int i = 0; i < cg.n_layers && !((fused | pl.wide) & 4); ++i)
       if ((rc = launch_chain_layer(h, 2, cg.layers[i], i ? A(2, i - 1) : Xg, i ? cg.widths[i - 1] : Kg, cg.widths[i], A(2, i), R, s, "bw_chain_fw_g"))) return rc;
   }
   return GNX_OK;
@@ -1591,6 +1597,15 @@ int32_t ChainBwCtx::fused_level(int t, const float* in0, int d0, const float* in
   const gnx_chain& c = ch(t);
   const bool want = chain_wants_grads(c, gfn(t));
   io.part = want ? part : nullptr;
+  if (pl.wide & (1u << t)) {  // one persistent kernel at matrix-core widths; its partial rows in the finishers' layout
+    { ProfScope ps(name, s);
+      if (int32_t r2 = launch_chain_bw_wide(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
+    const ChainBwWideShape ws = chain_bw_wide_shape(c, pl.sh.k0[t], pl.sh.trows[t]);
+    ChainBwNarrowShape fs{};  // (the finals read nwg and part_off alone)
+    fs.nwg = ws.nwg;
+    for (int i = 0; i < c.n_layers; ++i) fs.part_off[i] = ws.part_off[i];
+    return want ? chain_bw_narrow_finals(c, pl.sh.k0[t], fs, R, part, gfn(t), s) : GNX_OK;
+  }
   { ProfScope ps(name, s);
     if (int32_t r2 = pl.on_bf16() ? launch_chain_bw_narrow_bf16(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s) : launch_chain_bw_narrow(h, t, c, in0, d0, in1, d1, in2, d2, io, R, s)) return r2; }
   return want ? chain_bw_narrow_finals(c, pl.sh.k0[t], chain_bw_narrow_shape(c, pl.sh.k0[t], pl.sh.trows[t]), R, part, gfn(t), s) : GNX_OK;
@@ -1729,7 +1744,7 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   int32_t rc;
   if ((rc = check_ws(c.ws, c.ws_bytes, pl.on_bf16() ? pl.total : pl.base, pl.query))) return rc;
   if ((rc = gnx_ensure_wide_tables(h, c.stream))) return rc;
-  if ((pl.fused & 1) && (rc = gnx_ensure_csr(h))) return rc;  // (k_bw_dnf's out-edge view; the query built it)
+  if (((pl.fused | pl.wide) & 1) && (rc = gnx_ensure_csr(h))) return rc;  // (k_bw_dnf's out-edge view; the query built it)
   ChainBwCtx x{h, pl, pl.p, pl.lnf.init_grads(c.grads), cf(c.ef), cf(c.nf), cf(c.gf), cf(c.g_ef_out), cf(c.g_nf_out), cf(c.g_gf_out), mf(c.d_ef), mf(c.d_nf), mf(c.d_gf),
                c.R, c.stream, s, static_cast<char*>(c.ws), pl.p->de, pl.p->dn, pl.p->dg, pl.sh.ow[0], pl.sh.ow[1], pl.sh.ow[2], pl.sh.k0[1], pl.sh.k0[2],
                (int)h->E, (int)h->N, (int)h->G, (unsigned)c.R, pl.fused};
@@ -1747,23 +1762,25 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
   pl.bind_ident(x.F(pl.L.ident));
   if ((rc = pl.lnf.fill(x.F(pl.L.ident), s))) return rc;
   if ((rc = x.recompute())) return rc;
-  const unsigned fused = pl.fused;
+  const unsigned fused = pl.fused, wide = pl.wide;
   const int dn = x.dn, dg = x.dg, oe = x.oe, on = x.on, og = x.og, Kn = x.Kn, Kg = x.Kg;
   // ---- graph chain ----
-  if (fused & 4) {
+  if ((fused | wide) & 4) {
     if ((rc = x.fused_level(2, x.Xg, Kg, nullptr, 0, nullptr, 0, ChainBwNarrowIo{x.g_gf_out, nullptr, 0, 0, nullptr, 0, x.dXg, 0, nullptr, nullptr}, "bw_delta"))) return rc;
   } else if (og > 0) {
     x.last_delta(2, x.g_gf_out, x.gb[0], x.Xg, Kg, -1);
     if ((rc = x.pull_layers(2, 0, x.gb[0], x.gb[1], x.Xg, Kg, x.dXg, nullptr))) return rc;
   }
   // ---- node chain: upstream + dXg[graph of the node][oe : oe+on] ----
-  if (fused & 2) {
+  if (wide & 2) {  // the rows form: the whole input gradient of the materialised row into dXn
+    if ((rc = x.fused_level(1, x.Xn, Kn, nullptr, 0, nullptr, 0, ChainBwNarrowIo{x.g_nf_out, og > 0 ? x.dXg : nullptr, Kg, oe, nullptr, 0, x.dXn, 0, nullptr, nullptr}, "bw_delta"))) return rc;
+  } else if (fused & 2) {
     if ((rc = x.fused_level(1, x.ef_out, oe, x.nf, dn, x.gf, dg, ChainBwNarrowIo{x.g_nf_out, og > 0 ? x.dXg : nullptr, Kg, oe, nullptr, 0, x.dXn, 0, nullptr, nullptr}, "bw_delta"))) return rc;
   } else if (on > 0) {
     x.last_delta(1, x.g_nf_out, x.gb[0], x.Xn, Kn, -1);
     if ((rc = x.pull_layers(1, 0, x.gb[0], x.gb[1], x.Xn, Kn, x.dXn, nullptr))) return rc;
   }
-  if ((rc = (fused & 1) ? x.edge_fused() : x.edge_generic())) return rc;
+  if ((rc = ((fused | wide) & 1) ? x.edge_fused() : x.edge_generic())) return rc;
   if ((rc = x.shares())) return rc;
   if (pl.native && d_gf_caller && x.dg > 0 && (rc = launch_bf16_round(x.d_gf, pl.sh.rows[2] * (size_t)x.dg, d_gf_caller, s))) return rc;
   GNX_HIP(hipGetLastError());
@@ -1775,9 +1792,9 @@ int32_t chain_backward_fp32(const ChainBwCall& c, ChainBwPlan& pl) {
 // came through gnx_chain_block_backward_narrow_typed, which alone may be native) on its own tensors; any other bf16 call lays out, checks its workspace, widens its
 // six inputs, runs the fp32 launches on the copies and rounds the three input gradients (gnx_staging.h); the parameter gradients are the fp32
 // pullback's own.
-int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = false, bool train = false, bool ask_wave = false) {
+int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = false, bool train = false, bool ask_wave = false, bool ask_wide = false) {
   if (!c.h || !c.p) return fail(GNX_ERR_INVALID_ARG, "NULL handle or params");
-  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow, narrow_typed, train, ask_wave);
+  ChainBwPlan pl(c.h, c.p, c.R, c.elem, narrow, narrow_typed, train, ask_wave, ask_wide);
   if (pl.rc) return c.elem == GNX_ELEM_BF16 ? pl.rc : GNX_ERR_DIMS;  // (fp32: one code for every refused parameter set; gnx_last_error() holds the reason)
   const void* bufs[9] = {c.ef, c.nf, c.gf, c.g_ef_out, c.g_nf_out, c.g_gf_out, c.d_ef, c.d_nf, c.d_gf};
   int32_t rc;
@@ -1796,8 +1813,8 @@ int32_t chain_bw_run(const ChainBwCall& c, bool narrow, bool narrow_typed = fals
 
 // a _workspace_bytes entry: the plan's total; query_total builds what the pullback reads of the handle, outside any capture
 size_t chain_bw_query(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem, bool narrow, bool narrow_typed = false, bool train = false,
-                      bool ask_wave = false) {
-  ChainBwPlan pl(h, p, R, elem, narrow, narrow_typed, train, ask_wave);
+                      bool ask_wave = false, bool ask_wide = false) {
+  ChainBwPlan pl(h, p, R, elem, narrow, narrow_typed, train, ask_wave, ask_wide);
   pl.lay_out(h);  // (nothing for refused parameters: the total stays 0)
   return query_total(h, pl.total);
 }
@@ -1843,6 +1860,23 @@ int32_t gnx_chain_block_backward_wave(const gnx_graphs* h, const gnx_chain_block
                                       const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
                                       float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   return chain_bw_run(ChainBwCall{h, p, GNX_ELEM_F32, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true, false, false, true);
+}
+
+// gnx_chain_block_backward_wide: the narrow pullback, its plan asked for the wide mask (chain_bw_wide_mask) — a function inside it is one
+// k_chain_bw_wide launch and its finishers; with mask 0 the narrow entry's launches
+int32_t gnx_chain_block_backward_wide_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  const ChainBwPlan pl(h, p, R, GNX_ELEM_F32, true, false, false, false, true);  // (the constructor reads the handle's counts alone)
+  return !pl.rc ? (int32_t)pl.wide : 0;
+}
+
+size_t gnx_chain_block_backward_wide_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R) {
+  return chain_bw_query(h, p, R, GNX_ELEM_F32, true, false, false, false, true);
+}
+
+int32_t gnx_chain_block_backward_wide(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                      const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t R, float* d_ef, float* d_nf,
+                                      float* d_gf, const gnx_chain_block_grads* grads, void* ws, size_t ws_bytes, void* stream) {
+  return chain_bw_run(ChainBwCall{h, p, GNX_ELEM_F32, ef, nf, gf, g_ef_out, g_nf_out, g_gf_out, R, d_ef, d_nf, d_gf, grads, ws, ws_bytes, stream}, true, false, false, false, true);
 }
 
 // gnx_chain_block_backward_typed: either pullback above (narrow selects which) on fp32 or bf16 features; bf16 is staged

@@ -128,7 +128,7 @@ ChainPlan::ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int6
   query = query_of[bf16 ? 2 : narrow];
   sh = chain_shape(h->E, h->N, h->G, *p0, R);
   fused = narrow ? chain_fused_mask(sh, rule) : 0;
-  wide = ask_wide && narrow && !train && !bf16 ? chain_wide_mask(sh) : 0;
+  wide = ask_wide && narrow && !train && !bf16 ? (rule == CHAIN_RULE_FW ? chain_wide_mask(sh) : chain_bw_wide_mask(sh)) : 0;
   p = ((fused | wide) & 1) ? p0 : lnf.init(p0, nullptr);  // (the identity layer's weights sit at a fixed place of the workspace: bind_ident)
   if (lnf.on) sh = chain_shape(h->E, h->N, h->G, *p, R);
 }

@@ -214,6 +214,89 @@ inline unsigned chain_wide_mask(const ChainShape& s) {
   return m;
 }
 
+// ---- the wide form of the pullback (gnx_chain_block_backward_wide; gnx_chain_bw_wide.hip): one update function at matrix-core widths pulled
+//      back in one kernel ----
+constexpr int kChainBwWideLdsFloats = 16384;  // the weight chunk, the bias row and every wave's tape: 64 KB, the project's budget — two such
+                                              // workgroups share a CU's 160 KB, and no launch raises the dynamic-LDS attribute
+constexpr int kChainBwWideGrid = 512;         // the persistent grid: workgroups per replica at the most, two per CU of an MI355X — the partial
+                                              // rows of the parameter gradients are bounded by it, whatever the entity's rows
+constexpr int kChainBwWideMaxLayers = 8;      // entries of a function (the kernel keeps four vector accumulators per entry in registers)
+constexpr int kChainBwWideAcc = 4;            // 32 x 32 dW blocks a wave keeps in registers across tiles
+constexpr int kChainBwWideMaxItems = 24;
+// The plan of k_chain_bw_wide.  The tape of a row, in floats: the input row zero-padded to 16, then per entry its output padded to 16 (the
+// entry's delta is later written over it), a gelu Dense's pre-activation padded to 16 or a LayerNorm's (mu, sigma + eps, q, -); 16 floats of
+// slack (a 32-column fragment read of the last slot stays on the tape); ld odd.  LDS: the staged chunk [3][np][16] bf16, the bias row [np], then
+// `waves` tapes of [32][ld].  block[]: the dW blocks (entry, 32 rows k, 32 columns j), block b kept by wave b % waves in register slot b / waves.
+// item[]: the runs of staged chunks in the order the kernel consumes them — forward: a Dense's [kin][width] in chunks of 16 k; way back: its
+// transpose in chunks of 16 j, one run per pass of np input columns (entry 0 only where the caller wants the input gradient: `with_dx0`).
+struct ChainBwWideShape {
+  int ld, P, waves, nb, np, chunk_floats, bias_off, tape_off, floats, n_blocks, n_items, n_items_dx0;
+  int in_off[kChainBwWideMaxLayers], out_off[kChainBwWideMaxLayers], aux_off[kChainBwWideMaxLayers], part_off[kChainBwWideMaxLayers];
+  unsigned char block[4 * kChainBwWideAcc][3];  // entry, kb, jb
+  unsigned char item[kChainBwWideMaxItems][4];  // entry, transposed, pass, chunks; the first n_items without entry 0's way back, n_items_dx0 with it
+  size_t ntiles, nwg;  // tiles of 32 * waves rows; workgroups (= partial rows per entry) per replica: min(ntiles, kChainBwWideGrid)
+};
+inline ChainBwWideShape chain_bw_wide_shape(const gnx_chain& c, int k_in, size_t rows) {
+  ChainBwWideShape w{};
+  if (c.n_layers > kChainBwWideMaxLayers) return w;  // (waves 0: outside)
+  const ChainWideShape f = chain_wide_shape(c, k_in, rows);
+  w.nb = f.nb; w.np = f.np;
+  int slots = ceil16(k_in), kin = k_in, nblocks = 0;
+  for (int i = 0; i < c.n_layers; ++i) {
+    const bool ln = chain_layer_is_ln(c.layers[i]);
+    const int J = c.widths[i];
+    w.in_off[i] = i ? w.out_off[i - 1] : 0;
+    w.out_off[i] = slots; slots += ceil16(J);
+    w.aux_off[i] = slots;
+    if (ln) slots += 4; else if (c.layers[i].act == GNX_ACT_GELU) slots += ceil16(J);
+    w.part_off[i] = w.P;
+    w.P += ln ? 2 * J : J * (kin + 1);
+    if (!ln)
+      for (int kb = 0; kb < ceil32(kin) / 32; ++kb)
+        for (int jb = 0; jb < ceil32(J) / 32; ++jb, ++nblocks)
+          if (nblocks < 4 * kChainBwWideAcc) { w.block[nblocks][0] = (unsigned char)i; w.block[nblocks][1] = (unsigned char)kb; w.block[nblocks][2] = (unsigned char)jb; }
+    kin = J;
+  }
+  w.ld = (slots + 16) | 1;
+  w.chunk_floats = 3 * w.np * 8;
+  w.bias_off = w.chunk_floats;
+  w.tape_off = w.bias_off + w.np;
+  w.waves = std::min(4, std::max(0, (kChainBwWideLdsFloats - w.tape_off) / (kChainWideRows * w.ld)));
+  if (w.waves < 2 || nblocks > w.waves * kChainBwWideAcc) { w.waves = 0; return w; }
+  w.n_blocks = nblocks;
+  w.floats = w.tape_off + w.waves * kChainWideRows * w.ld;
+  auto item = [&](int i, int t, int pass, int chunks) {
+    if (w.n_items_dx0 < kChainBwWideMaxItems) { unsigned char* it = w.item[w.n_items_dx0]; it[0] = (unsigned char)i; it[1] = (unsigned char)t; it[2] = (unsigned char)pass; it[3] = (unsigned char)chunks; }
+    ++w.n_items_dx0;
+  };
+  kin = k_in;
+  for (int i = 0; i < c.n_layers; kin = c.widths[i++])
+    if (!chain_layer_is_ln(c.layers[i])) item(i, 0, 0, ceil16(kin) / 16);
+  for (int i = c.n_layers - 1; i >= 0; --i) {
+    if (i == 0) w.n_items = w.n_items_dx0;
+    if (chain_layer_is_ln(c.layers[i])) continue;
+    const int K = i ? c.widths[i - 1] : k_in;
+    for (int pass = 0; pass * w.np < K; ++pass) item(i, 1, pass, ceil16(c.widths[i]) / 16);
+  }
+  if (w.n_items_dx0 > kChainBwWideMaxItems) { w.waves = 0; return w; }
+  w.ntiles = (rows + (size_t)kChainWideRows * w.waves - 1) / ((size_t)kChainWideRows * w.waves);
+  w.nwg = std::min(w.ntiles, (size_t)kChainBwWideGrid);
+  return w;
+}
+// The rule of gnx_chain_block_backward_wide for one function (include/gnx.h states it): the forward's wide rule (chain_wide_takes, the class of
+// chain_wide_cut outside), at most eight entries, and the plan above — two tapes at least within 64 KB, every dW block in a register slot.
+// Measured classes and what was not measured: DESIGN.md, profiles/chain_bw_wide.json.
+inline bool chain_bw_wide_takes(const gnx_chain& c, int k_in, size_t entity_rows) {
+  return chain_wide_takes(c, k_in, entity_rows) && chain_bw_wide_shape(c, k_in, entity_rows).waves >= 2;
+}
+// the functions of a block the wide pullback kernel runs: bit 0 edge, 1 node, 2 graph (no pullback without an edge output)
+inline unsigned chain_bw_wide_mask(const ChainShape& s) {
+  unsigned m = 0;
+  for (int t = 0; t < 3 && s.ow[0] > 0; ++t)
+    if (chain_bw_wide_takes(*s.ch[t], s.k0[t], s.trows[t])) m |= 1u << t;
+  return m;
+}
+
 // ---- the wave form (gnx_chain_block_forward_wave; gnx_chain_wave.hip): the edge and the node function in one wave-per-tile kernel ----
 constexpr int kChainWaveLdsFloats = 16384;  // both functions' parameters + every wave's ef' rows: 64 KB
 // floats between two ef' rows of a wave's LDS slice: odd, so that 64 lanes on 64 different rows of one column meet in no bank
@@ -341,13 +424,16 @@ inline bool chain_fw_reads_wide_tables(const ChainShape& s, unsigned fused) {
 // buffers and (the edge function) no inner block workspaces; it adds its partial rows and (the edge function) the compact [R E][2 dn + dg] input
 // gradient.  blk_fw_bytes / blk_bw_bytes: gnx_block_workspace_bytes / gnx_block_backward_workspace_bytes of s.edge_block unless the edge
 // function is fused; chunk: BW_CH, the rows per partial of the generic weight-gradient reduction; dw_partial(rows, J, K): dw_mfma_partial_floats.
+// wide: the mask of chain_bw_wide_mask (gnx_chain_block_backward_wide), disjoint from `fused` — such a function has its rows on the kernel's LDS tape: no
+// per-layer outputs, no delta buffers and no transposed weights are sized for it; the node and the graph function keep their input rows Xn / Xg.
 struct ChainBwLayout {
   ChainCarve act[3][kChainMaxLayers + 1];  // stored layer outputs per chain (a fused chain: its last layer's, where a level above reads it)
   ChainCarve Xn, dXn, Xg, dXg, gbuf[3], blk_fw, blk_bw, part, wt, off2, ident, dxe;
   size_t total;
 };
 template <class DwPartial>
-inline ChainBwLayout chain_bw_layout(const ChainShape& s, unsigned fused, size_t ident_floats, size_t blk_fw_bytes, size_t blk_bw_bytes, size_t chunk, DwPartial dw_partial) {
+inline ChainBwLayout chain_bw_layout(const ChainShape& s, unsigned fused, size_t ident_floats, size_t blk_fw_bytes, size_t blk_bw_bytes, size_t chunk, DwPartial dw_partial,
+                                     unsigned wide = 0) {
   ChainBwLayout L{};
   ChainCarver c;
   const int oe = s.ow[0], on = s.ow[1], og = s.ow[2];
@@ -355,6 +441,12 @@ inline ChainBwLayout chain_bw_layout(const ChainShape& s, unsigned fused, size_t
   size_t gmax = 1, pmax = 2048 * 4, wmax = 1;
   for (int t = 0; t < 3; ++t) {
     const gnx_chain& ch = *s.ch[t];
+    if (wide & (1u << t)) {  // its last layer's output where a level above reads it (launch_chain_wide), and its partial rows: nothing else
+      if (t == 0 ? on > 0 || og > 0 : t == 1 && og > 0) L.act[t][ch.n_layers - 1] = c.floats(s.rows[t] * (size_t)s.ow[t]);
+      const ChainBwWideShape sh = chain_bw_wide_shape(ch, s.k0[t], s.trows[t]);
+      pmax = std::max(pmax, (size_t)sh.P * sh.nwg * (size_t)s.R);
+      continue;
+    }
     if (fused & (1u << t)) {
       const bool crosses = t == 0 ? on > 0 || og > 0 : t == 1 && og > 0;  // ef' feeds the node / graph inputs, nf' the graph input
       if (t == 1 && chain_bw_node_fw_generic(fused, og)) {
@@ -376,12 +468,13 @@ inline ChainBwLayout chain_bw_layout(const ChainShape& s, unsigned fused, size_t
   pmax = std::max(pmax, std::max(s.rows[2] * 256, (size_t)2048) * (size_t)std::max({s.dg, oe, 1}));  // column-sum slices
   L.Xn = c.floats(on > 0 && (!(fused & 2) || chain_bw_node_fw_generic(fused, og)) ? s.rows[1] * Kn : 0); L.dXn = c.floats(on > 0 ? s.rows[1] * Kn : 0);
   L.Xg = c.floats(og > 0 ? s.rows[2] * Kg : 0); L.dXg = c.floats(og > 0 ? s.rows[2] * Kg : 0);
-  const bool all_fused = (oe == 0 || (fused & 1)) && (on == 0 || (fused & 2)) && (og == 0 || (fused & 4)) && fused != 0;
+  const unsigned one = fused | wide;  // the functions that run in one kernel
+  const bool all_fused = (oe == 0 || (one & 1)) && (on == 0 || (one & 2)) && (og == 0 || (one & 4)) && one != 0;
   for (int i = 0; i < 3; ++i) L.gbuf[i] = c.floats(all_fused ? 0 : gmax);
   L.blk_fw = c.bytes(blk_fw_bytes); L.blk_bw = c.bytes(blk_bw_bytes);
   L.part = c.floats(pmax); L.wt = c.floats(wmax); L.off2 = c.floats(16);
   L.ident = c.floats(ident_floats);
-  L.dxe = c.floats((fused & 1) ? s.rows[0] * (size_t)(2 * s.dn + s.dg) : 0);
+  L.dxe = c.floats((one & 1) ? s.rows[0] * (size_t)(2 * s.dn + s.dg) : 0);
   L.total = c.o + 256;
   return L;
 }

@@ -213,6 +213,11 @@ struct ChainBwNarrowIo {
 // entity / in0..in2 as launch_chain_narrow.  The caller asked chain_bw_narrow_takes and opens the ProfScope.
 int32_t launch_chain_bw_narrow(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                                const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
+// ---- gnx_chain_bw_wide.hip: the pullback of one update function at matrix-core widths in one persistent kernel (gnx_chain_block_backward_wide) ----
+// entity / in0..in2 as launch_chain_wide, io as launch_chain_bw_narrow (the partial rows: P and nwg of chain_bw_wide_shape).  The caller asked
+// chain_bw_wide_takes, made sure of the handle's matrix-core tables and opens the ProfScope.
+int32_t launch_chain_bw_wide(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
+                             const ChainBwNarrowIo& io, int64_t R, hipStream_t s);
 // ---- gnx_chain_bw_wave.hip: the pullback of a Chain block in the wave form (gnx_chain_block_backward_wave).  The caller asked chain_bw_wave_takes
 //      and opens the ProfScopes ----
 // the tiles' partial rows [R][wave tiles][oe + on] alone: the wave forward without its ef' / nf' stores

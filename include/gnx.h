@@ -700,6 +700,27 @@ GNX_API int32_t gnx_chain_block_backward_wave(const gnx_graphs* h, const gnx_cha
                                       const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
                                       float* d_nf, float* d_gf, const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes,
                                       void* stream);
+/* gnx_chain_block_backward_narrow with every update function at matrix-core widths pulled back in ONE kernel (k_chain_bw_wide; float32
+ * features, test mode) — the pullback of gnx_chain_block_forward_wide.  _applies: the mask of those functions (bit 0 edge, 1 node, 2 graph).
+ * Rule, per function: inside gnx_chain_block_forward_wide's rule (outside the narrow rule; at least two Dense / LayerNorm entries, no
+ * Dropout entry; 1 <= k_in <= 128 and every width <= 128; no Dense beyond 64 columns), at most 8 entries, and the kernel's LDS plan within
+ * 64 KB at two waves at least: 24 * np + np floats of staged weights (np: the widest Dense padded to 32 columns) and per wave a tape of
+ * 32 rows x ld floats — ld odd: the input row and every entry's output padded to 16, a gelu Dense's pre-activation padded to 16, 4 floats
+ * per LayerNorm, 16 of slack — with every 32 x 32 block of the weight gradients in one of 4 register slots of a wave.  The block needs an
+ * edge output.  The kernel runs on a persistent grid of at most 512 workgroups per replica and writes one partial row of the parameter
+ * gradients per workgroup, so the workspace holds nothing per layer that grows with E or N for such a function: its last output where a
+ * level above reads it, the node / graph function's input rows and their gradients, [R E][2 dn + dg] input-gradient columns behind a wide
+ * edge function, the partial rows.  A function outside the mask runs as gnx_chain_block_backward_narrow runs it; with mask 0 the call IS
+ * that entry (same workspace size, same bits).  Inside the mask every gradient is the same mathematical pullback in other fixed summation
+ * orders: within the library's bar against float64, the same bits from call to call whatever the workspace held; no atomics.
+ * _workspace_bytes builds the handle's tables the call reads: call it outside a stream capture.  Arguments, optional outputs and refusals as
+ * gnx_chain_block_backward_narrow.  bfloat16 features and training calls have no such entry. */
+GNX_API int32_t gnx_chain_block_backward_wide_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API size_t gnx_chain_block_backward_wide_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas);
+GNX_API int32_t gnx_chain_block_backward_wide(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf,
+                                      const float* g_ef_out, const float* g_nf_out, const float* g_gf_out, int64_t n_replicas, float* d_ef,
+                                      float* d_nf, float* d_gf, const gnx_chain_block_grads* grads, void* workspace, size_t workspace_bytes,
+                                      void* stream);
 /* Either Chain pullback on float32 or bfloat16 features.  `elem` applies to the nine feature-shaped tensors (the inputs, the upstream gradients,
  * the input gradients); parameter gradients stay float32.  `narrow` (0 or 1): gnx_chain_block_backward (0) or gnx_chain_block_backward_narrow
  * (1).  GNX_ELEM_F32 IS the mirrored entry (same validation, workspace size, bits); another elem than F32 / BF16 or a narrow other than 0 / 1:

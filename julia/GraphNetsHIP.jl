@@ -24,7 +24,7 @@ module GraphNetsHIP
 export GNGraphBatch, batch, unbatch, getedgefninput, getnodefninput, getgraphfninput, GNBlock, zerodim2nothing, GNCore, GNCoreList,
        efview, nfview, gfview, flatunpaddednf, flatunpaddedef, collapsef, unpaddedcollapsedef, flatunpaddedcollapsedef
 # ... plus what the drop-in adds: layers as plain structs, pullbacks, the library-side hipGraph model, the multi-GPU split
-export Dense, LayerNorm, ChainBlock, chain_forward, chain_narrow_applies, chain_wave_applies, chain_wide_applies, chain_pullback, chain_backward, chain_backward_narrow_applies, chain_backward_wave_applies, block_pullback, core_pullback, Model, partition_graphs, DistBlock
+export Dense, LayerNorm, ChainBlock, chain_forward, chain_narrow_applies, chain_wave_applies, chain_wide_applies, chain_pullback, chain_backward, chain_backward_narrow_applies, chain_backward_wave_applies, chain_backward_wide_applies, block_pullback, core_pullback, Model, partition_graphs, DistBlock
 # ... and device residency: `x |> batch |> gpu`, `model |> gpu`, `y |> cpu` (what Flux's `gpu` / `cpu` are to the reference)
 export DeviceArray, gpu, cpu, synchronize, chained, flush, steps
 
@@ -928,7 +928,9 @@ chain_forward(m::ChainBlock, x; narrow::Bool=false, wave::Bool=false, wide::Bool
 # before; a workspace key of its own
 # wave = true (wins over narrow): gnx_chain_block_backward_wave — where the whole block is inside the pullback's wave rule (include/gnx.h) the node
 # and the edge function are pulled back in one wave-per-tile kernel; elsewhere the narrow entry's launches
-function chain_pullback_device(m::ChainBlock, x, ȳ; narrow::Bool=false, wave::Bool=false)
+# wide = true (wins over wave and narrow): gnx_chain_block_backward_wide — every update function at matrix-core widths inside its rule (include/gnx.h)
+# is pulled back in one persistent kernel; the others as the narrow entry runs them
+function chain_pullback_device(m::ChainBlock, x, ȳ; narrow::Bool=false, wave::Bool=false, wide::Bool=false)
     g::GNGraphBatch = x.graphs
     R = replicas(x.ef, x.nf, x.gf)
     keep = Any[]
@@ -940,12 +942,18 @@ function chain_pullback_device(m::ChainBlock, x, ȳ; narrow::Bool=false, wave::B
     arrs = [[GnxDenseGrad(devptr(gW[t][i]), devptr(gB[t][i])) for i in eachindex(chains[t])] for t in 1:3]
     gp(t) = isempty(arrs[t]) ? Ptr{GnxDenseGrad}(C_NULL) : pointer(arrs[t])
     grads = Ref(GnxChainBlockGrads(gp(1), gp(2), gp(3)))
-    ws = workspace!(g, (wave ? :chain_backward_wave : narrow ? :chain_backward_narrow : :chain_backward, chainkey(m), R)) do
+    ws = workspace!(g, (wide ? :chain_backward_wide : wave ? :chain_backward_wave : narrow ? :chain_backward_narrow : :chain_backward, chainkey(m), R)) do
+        wide ? ccall((:gnx_chain_block_backward_wide_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R) :
         wave ? ccall((:gnx_chain_block_backward_wave_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R) :
         narrow ? ccall((:gnx_chain_block_backward_narrow_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R) :
                  ccall((:gnx_chain_block_backward_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R)
     end
-    GC.@preserve m keep x ȳ dins gW gB arrs ws check(wave ? ccall((:gnx_chain_block_backward_wave, libgnx), Int32,
+    GC.@preserve m keep x ȳ dins gW gB arrs ws check(wide ? ccall((:gnx_chain_block_backward_wide, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64,
+         Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{GnxChainBlockGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
+        devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]) :
+      wave ? ccall((:gnx_chain_block_backward_wave, libgnx), Int32,
         (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64,
          Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{GnxChainBlockGrads}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
         g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), devptr(ȳ.ef), devptr(ȳ.nf), devptr(ȳ.gf), R,
@@ -962,11 +970,17 @@ function chain_pullback_device(m::ChainBlock, x, ȳ; narrow::Bool=false, wave::B
         devptr(dins[1]), devptr(dins[2]), devptr(dins[3]), grads, ws.ptr, ws.cap, STREAM[]))
     (ef=dins[1], nf=dins[2], gf=dins[3], params=[[(weight=gW[t][i], bias=gB[t][i]) for i in eachindex(chains[t])] for t in 1:3])
 end
-function chain_backward(m::ChainBlock, x, ȳ; narrow::Bool=false, wave::Bool=false)
-    r = chain_pullback_device(gpu(m), gpu(x), gpu(ȳ); narrow=narrow, wave=wave)
+function chain_backward(m::ChainBlock, x, ȳ; narrow::Bool=false, wave::Bool=false, wide::Bool=false)
+    r = chain_pullback_device(gpu(m), gpu(x), gpu(ȳ); narrow=narrow, wave=wave, wide=wide)
     ondevice(x) ? r : (ef=cpu(r.ef), nf=cpu(r.nf), gf=cpu(r.gf), params=[[map(cpu, q) for q in c] for c in r.params])
 end
-chain_pullback(m::ChainBlock, x, ȳ) = chain_backward(m, x, ȳ)
+chain_pullback(m::ChainBlock, x, ȳ; wide::Bool=false) = chain_backward(m, x, ȳ; wide=wide)
+# which update functions gnx_chain_block_backward_wide pulls back in one matrix-core kernel on this batch: bit 0 edge, bit 1 node, bit 2 graph
+function chain_backward_wide_applies(m::ChainBlock, x)
+    keep = Any[]
+    p = Ref(chain_params(m, keep))
+    GC.@preserve m keep ccall((:gnx_chain_block_backward_wide_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
+end
 # which update functions gnx_chain_block_backward_narrow pulls back in one kernel on this batch: bit 0 edge, bit 1 node, bit 2 graph
 function chain_backward_narrow_applies(m::ChainBlock, x)
     keep = Any[]

@@ -11,7 +11,12 @@ whose time stands next to the parent's to show the two sessions overlap.
 source form x one graph or several) has to meet on every case that reaches it to stay in chain_wide_takes.
 (The name stays outside tools/time_*.py: tests/test_timing_tools_cpu.py counts those files.  Built from tools/timing.py and tools/calls.py alone.)
 
+`--backward`: the same comparison for the pullback — gnx_chain_block_backward_wide (csrc/gnx_chain_bw_wide.hip; the switch `wide_chain_backward`)
+against gnx_chain_block_backward of the parent's library, all gradients wanted, on the same configs and batches; the class of a case is then
+what chain_bw_wide_takes has to keep.
+
   python tools/chain_wide_timing.py [--samples 15] [--parent-root DIR] [--out profiles/chain_wide.json]
+  python tools/chain_wide_timing.py --backward [--samples 15] [--parent-root DIR] [--out profiles/chain_bw_wide.json]
 """
 import argparse
 import os
@@ -37,21 +42,22 @@ def blocks(widths):
 def one_case(a, gn, g, cfg, baseline_only):
     import torch
     F32 = gn._lib.ELEM_F32
-    case = calls.chain_case(gn, g, cfg, cot=False)
-    built = {"generic": calls.build(gn, case, "chain", "forward", F32, "gnx_chain_block_forward")}
+    way = "backward" if a.backward else "forward"
+    case = calls.chain_case(gn, g, cfg, cot=a.backward)
+    built = {"generic": calls.build(gn, case, "chain", way, F32, "gnx_chain_block_" + way)}
     rec = dict(in_dims=list(cfg[0]), edge=cfg[1], node=cfg[2], graph=cfg[3], E=g.n_edges, N=g.n_nodes, G=g.n_graphs)
     if not baseline_only:
-        rec["applies"] = calls.applies(gn, case, "gnx_chain_block_forward_wide_applies")
-        rec["narrow_applies"] = calls.applies(gn, case, "gnx_chain_block_forward_narrow_applies")
+        rec["applies"] = calls.applies(gn, case, f"gnx_chain_block_{way}_wide_applies")
+        rec["narrow_applies"] = calls.applies(gn, case, f"gnx_chain_block_{way}_narrow_applies")
         rec["class"] = dict(blocks={n: blocks(w) for n, w, bit in (("edge", cfg[1], 1), ("node", cfg[2], 2), ("graph", cfg[3], 4)) if rec["applies"] & bit},
                             graphs="one" if g.n_graphs == 1 else "several")
-        built["wide"] = calls.build(gn, case, "chain", "forward", F32, ("wide_chain",))
+        built["wide"] = calls.build(gn, case, "chain", way, F32, ("wide_chain_backward",) if a.backward else ("wide_chain",))
     ms = timing.cold_samples(torch, {k: c.f for k, c in built.items()}, a.samples, WARMUP)
     rec.update(forms={k: timing.summary_samples(v) for k, v in ms.items()}, workspace_bytes={k: c.nbytes for k, c in built.items()})
     if not baseline_only:  # the two calls of this build on the same inputs: how far apart the outputs are
         torch.cuda.synchronize()
         rec["max_diff_wide_vs_generic_over_scale"] = max(float((u.double() - v.double()).abs().max() / max(1.0, float(v.double().abs().max())))
-                                                         for u, v in zip(built["wide"].outs, built["generic"].outs) if u is not None)
+                                                         for u, v in zip(built["wide"].outs + built["wide"].grads, built["generic"].outs + built["generic"].grads) if u is not None)
         rec["profiler_one_call"] = {k: timing.profiled_once(gn, torch, c.f) for k, c in built.items()}
     return rec
 
@@ -95,13 +101,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=15)
     ap.add_argument("--root", default=HERE, help="the checkout whose package and library are timed")
-    ap.add_argument("--baseline-only", action="store_true", help="time gnx_chain_block_forward only and print one JSON line")
+    ap.add_argument("--baseline-only", action="store_true", help="time gnx_chain_block_forward (--backward: gnx_chain_block_backward) only and print one JSON line")
+    ap.add_argument("--backward", action="store_true", help="time the pullbacks: gnx_chain_block_backward_wide against gnx_chain_block_backward")
     ap.add_argument("--parent-root", default=None, help="a checkout of the parent commit, its library built")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     parent = None
     if a.parent_root:  # first, and in a process of its own: one library per process
-        parent = timing.parent_baseline(__file__, a.parent_root, ["--samples", a.samples], 500)["cases"]
+        parent = timing.parent_baseline(__file__, a.parent_root, ["--samples", a.samples] + (["--backward"] if a.backward else []), 500)["cases"]
     timing.child_root(a.root)
     res = run(a, parent)
     if a.baseline_only:

@@ -205,6 +205,15 @@ def _rec_chain_wave(f, res, twin):
     return rec
 
 
+def _rec_chain_bw_wide(f, res, twin):
+    r = res()
+    rec = dict(what="k_chain_bw_wide<NB, SRC> per accumulator-block class and source form: NB forward / dX accumulators, four dW blocks and four "
+                    "vector accumulators per entry stay in registers across a workgroup's tiles" + REMARKS, box=BOX, lds_budget_bytes=f["LDS_BUDGET_BYTES"],
+               srcs={s: {str(nb): r[s][nb] for nb in f["NB"]} for s in f["SRCS"]})
+    rec["instantiations_with_scratch_or_static_lds"] = [f"{s}/{nb}" for s in f["SRCS"] for nb in f["NB"] if r[s][nb]["scratch"] or r[s][nb]["lds_static"]]
+    return rec
+
+
 def _rec_chain_wide(f, res, twin):
     r = res()
     rec = dict(what="k_chain_wide<NB, SRC> per accumulator-block class and source form" + REMARKS, box=BOX, lds_budget_bytes=f["LDS_BUDGET_BYTES"],
@@ -284,6 +293,9 @@ FAMILIES = {
     # the Chain forward at matrix-core widths: the weight chunk, the bias row and every wave's slice in LDS (kChainWideLdsFloats: gnx_chain_plan.h)
     "chain_wide": dict(file="gnx_chain_wide.hip", name=r"_ZN3gnx\d+k_chain_wideILi(\d+)ELi(\d+)EEEv", key=lambda m: (SRC[int(m.group(2))], int(m.group(1))),
                        fields=STATIC, record=_rec_chain_wide, NB=(1, 2), SRCS=("edge", "rows"), LDS_BUDGET_BYTES=4 * 16384),
+    # its pullback: the weight chunk, the bias row and every wave's tape in LDS (kChainBwWideLdsFloats: gnx_chain_plan.h)
+    "chain_bw_wide": dict(file="gnx_chain_bw_wide.hip", name=r"_ZN3gnx\d+k_chain_bw_wideILi(\d+)ELi(\d+)EEEv", key=lambda m: (SRC[int(m.group(2))], int(m.group(1))),
+                          fields=STATIC, record=_rec_chain_bw_wide, NB=(1, 2), SRCS=("edge", "rows"), LDS_BUDGET_BYTES=4 * 16384),
     # its bf16 twin: the same LDS budget, a wave's slice also stages its nf' rows for the flat store
     "chain_wave_bf16": dict(file="gnx_chain_wave_bf16.hip", name=r"_ZN3gnx\d+(k_chain_wave_bf16|k_chain_graph_wave_bf16)ILi(\d+)EEEv",
                             key=lambda m: (m.group(1), int(m.group(2))), fields=STATIC, record=_rec_chain_wave_bf16,
