@@ -946,6 +946,7 @@ def _entry(family, direction, elem, switches=(), record=False):
                 backward   gnx_block_backward [_fused with `fused_backward`] [_typed on bf16]; gnx_block_backward_narrow with `narrow_backward`
                            (which wins over `fused_backward`; either element type); bf16 needs `bf16_backward`
       chain     forward    an active record: gnx_chain_block_forward_train (narrow = `narrow_chain`; fp32 only); bf16 (needs `bf16_chain`):
+                           gnx_chain_block_forward_wide_typed with `wide_chain` (handed over as for fp32, below),
                            gnx_chain_block_forward_wave_typed with `wave_chain`, else gnx_chain_block_forward_typed (narrow = `narrow_chain`);
                            fp32: gnx_chain_block_forward_wide with `wide_chain` (_chain_forward hands it over only where that entry's
                            _applies mask is non-zero), gnx_chain_block_forward_wave with `wave_chain` (which wins over `narrow_chain`),
@@ -987,6 +988,8 @@ def _entry(family, direction, elem, switches=(), record=False):
             n = int(on("narrow_chain"))
             if record:
                 return E("gnx_chain_block_forward_train", (n,), ("drop",), (n, "flags"), ("chain_train", n, "in_dims", "widths", "R"))
+            if bf16 and on("wide_chain"):  # (_chain_forward hands the switch over only where the entry's _applies mask is non-zero)
+                return E("gnx_chain_block_forward_wide_typed", (elem,), (elem,), fl, ("chain_wide_bf16", "in_dims", "widths", "R"))
             if bf16 and on("wave_chain"):
                 return E("gnx_chain_block_forward_wave_typed", (elem,), (elem,), fl, ("chain_wave_bf16", "in_dims", "widths", "R"))
             if bf16:  # (mirrors the entry `narrow_chain` selects)
@@ -1145,8 +1148,13 @@ class GNBlock:
     `wide_chain` (gnx_chain_block_forward_wide): a float32 test-mode forward in which some update function is at matrix-core widths inside that
     entry's rule (include/gnx.h: outside the narrow rule, at least two layers, input and layer widths up to 128) runs each such function in one
     kernel that keeps the gathered input, every hidden row and every LayerNorm in LDS, each function inside the narrow rule as `narrow_chain`
-    does, the others as before.  Where the entry's mask is 0 — every block the wave rule takes included — on bfloat16 features and under an
-    active chain Dropout the call goes where it goes without the switch.  The pullback recomputes from the inputs and does not change.
+    does, the others as before.  Where the entry's mask is 0 — every block the wave rule takes included — and under an active chain Dropout
+    the call goes where it goes without the switch.  The pullback recomputes from the inputs and does not change.
+    On bfloat16 features (with `bf16_chain`: gnx_chain_block_forward_wide_typed) — a combination that was a no-op while `wide_chain` was float32
+    only — the test-mode forward runs that entry where its native form applies (its mask non-zero and every update function that runs inside
+    the wide or the narrow rule): the wide functions in one kernel each that gathers the bf16 rows, keeps them as bf16 in LDS, runs the first
+    Dense as three matrix instructions per step instead of six and stores each bf16 output once — bit for bit to_bf16 of the float32 call on
+    the widened inputs, with no float32 copy of anything edge-sized.  Elsewhere the bfloat16 call goes where it goes without the switch.
 
     `wide_chain_backward` (gnx_chain_block_backward_wide; independent of `wide_chain`, wins over `wave_chain_backward` and
     `narrow_chain_backward`): in a float32 test-mode pullback each update function at matrix-core widths inside that entry's rule (include/gnx.h:
@@ -1389,7 +1397,8 @@ def _chain_forward(block, g, R, flags, elem, rec, ef, nf, gf):
     widths = tuple(tuple(k if k == "dropout" else int(l.weight.shape[0]) for k, l in ch._entries(train)) for ch in chains)
     env = dict(flags=flags, R=R, in_dims=block.in_dims, widths=widths, drop=C.byref(drop) if train else None)
     sw = _switches(block)
-    if "wide_chain" in sw and (train or elem != _lib.ELEM_F32 or _lib.load().gnx_chain_block_forward_wide_applies(g._h, C.byref(p), R) == 0):
+    # (float32: gnx_chain_block_forward_wide's mask; bfloat16: gnx_chain_block_forward_wide_typed's, non-zero where its native form runs)
+    if "wide_chain" in sw and (train or _lib.load().gnx_chain_block_forward_wide_typed_applies(g._h, C.byref(p), R, elem) == 0):
         sw = sw - {"wide_chain"}  # (no function inside the wide rule: the call goes where it goes without the switch)
     return _forward(_entry("chain", "forward", elem, sw, train), g, p, R, outw, elem, (ef, nf, gf), env, strict=True)
 

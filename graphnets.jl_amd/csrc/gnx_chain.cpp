@@ -19,6 +19,9 @@
 // kernel's partial rows (gnx_chain_wave.hip) where chain_wave_takes (gnx_chain_plan.h) holds; elsewhere the narrow entry's launches.
 // gnx_chain_block_forward_wave_typed: that entry on fp32 or bf16 features — bf16 inside chain_wave_typed_takes: the same two launches reading and
 // writing bf16 rows (gnx_chain_wave_bf16.hip), the partial rows the whole workspace; bf16 elsewhere: gnx_chain_block_forward_typed(narrow = 1).
+// gnx_chain_block_forward_wide_typed: the wide entry on fp32 or bf16 features — bf16 inside chain_wide_typed_native: each wide function one
+// k_chain_wide_bf16 launch on the bf16 rows (gnx_chain_wide_bf16.hip), each narrow one a k_chain_mlp_bf16 launch; bf16 with a wide mask and a
+// generic function: staged around the fp32 wide launches; bf16 without a wide function: gnx_chain_block_forward_typed(narrow = 1).
 #include <algorithm>
 
 #include "gnx_launchers.h"
@@ -128,7 +131,8 @@ ChainPlan::ChainPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int6
   query = query_of[bf16 ? 2 : narrow];
   sh = chain_shape(h->E, h->N, h->G, *p0, R);
   fused = narrow ? chain_fused_mask(sh, rule) : 0;
-  wide = ask_wide && narrow && !train && !bf16 ? (rule == CHAIN_RULE_FW ? chain_wide_mask(sh) : chain_bw_wide_mask(sh)) : 0;
+  // (bf16: the forward alone has a wide form — gnx_chain_block_forward_wide_typed; the pullback of wide functions on bf16 features is staged)
+  wide = ask_wide && narrow && !train && (!bf16 || rule == CHAIN_RULE_FW) ? (rule == CHAIN_RULE_FW ? chain_wide_mask(sh) : chain_bw_wide_mask(sh)) : 0;
   p = ((fused | wide) & 1) ? p0 : lnf.init(p0, nullptr);  // (the identity layer's weights sit at a fixed place of the workspace: bind_ident)
   if (lnf.on) sh = chain_shape(h->E, h->N, h->G, *p, R);
 }
@@ -230,6 +234,9 @@ struct ChainFwPlan : ChainPlan {
   // the wave form runs (asked for through gnx_chain_block_forward_wave / _wave_typed, and chain_wave_takes / chain_wave_typed_takes): partial rows
   // at the workspace's head — on bf16 features nothing else
   bool wave = false;
+  // a bf16 call asked for the wide mask, and chain_wide_typed_native: every function that runs is one launch on the bf16 rows, the wide ones
+  // k_chain_wide_bf16; the workspace is the fp32 wide layout and the three carves of chain_native_counts behind it
+  bool wide_native = false;
   ChainWs w{};
   ChainFwPlan(const gnx_graphs* h, const gnx_chain_block_params* p0, int64_t R, int32_t elem, bool narrow, bool train = false, bool ask_wave = false, bool ask_wide = false)
       : ChainPlan(h, p0, R, elem, narrow, CHAIN_RULE_FW, kFwQuery, train, ask_wide) {
@@ -237,7 +244,9 @@ struct ChainFwPlan : ChainPlan {
     wave = !rc && ask_wave && narrow && !train &&
            (bf16 ? chain_wave_typed_takes(sh, h->max_in_degree, h->wtile_e_cap) : chain_wave_takes(sh, false, h->max_in_degree, h->wtile_e_cap));
     if (ask_wave) query = kFwWaveQuery[bf16];
-    if (ask_wide) query = "workspace missing or smaller than gnx_chain_block_forward_wide_workspace_bytes()";
+    wide_native = !rc && bf16 && chain_wide_typed_native(sh, fused, wide);
+    if (ask_wide) query = bf16 ? "workspace missing or smaller than gnx_chain_block_forward_wide_typed_workspace_bytes()"
+                               : "workspace missing or smaller than gnx_chain_block_forward_wide_workspace_bytes()";
   }
   bool wide_tables() const { return chain_fw_reads_wide_tables(sh, fused | wide); }
   void lay_out(const gnx_graphs* h) {  // (the inner block's query builds what its edge update reads of the handle)
@@ -251,7 +260,7 @@ struct ChainFwPlan : ChainPlan {
       return;
     }
     const size_t fp32_total = wave ? std::max(w.total, sizeof(float) * chain_wave_partial_floats(sh, h->n_wtiles())) : w.total;
-    sized(fp32_total, native ? stage_layout(fp32_total, counts, 3) : stage_features(fp32_total, h, sh.R, d, 6));
+    sized(fp32_total, native || wide_native ? stage_layout(fp32_total, counts, 3) : stage_features(fp32_total, h, sh.R, d, 6));
   }
 };
 
@@ -333,6 +342,39 @@ int32_t chain_forward_native(const ChainFwCall& c, const ChainFwPlan& pl) {
   return GNX_OK;
 }
 
+// the native bf16 launches with wide functions (ChainFwPlan::wide_native): chain_forward_fp32's order of functions, each one launch on the bf16
+// rows — k_chain_wide_bf16 for a function of the wide mask, k_chain_mlp_bf16 for one of the narrow mask.  A wide node function's input rows come
+// from the unrounded ef' and the bf16 nf / gf (launch_chain_node_rows_bf16), the graph function's from the three carves as in chain_forward_native.
+int32_t chain_forward_wide_native(const ChainFwCall& c, const ChainFwPlan& pl) {
+  const gnx_graphs* h = c.h;
+  const gnx_chain_block_params* p = pl.p;
+  const hipStream_t s = (hipStream_t)c.stream;
+  const int de = p->de, dn = p->dn, dg = p->dg, oe = pl.sh.ow[0], on = pl.sh.ow[1], og = pl.sh.ow[2];
+  const unsigned fused = pl.fused, wide = pl.wide;
+  auto at = [&](int i) { return pl.st.n[i] > 0 ? pl.st.at(c.ws, i) : nullptr; };
+  auto F = [&](const ChainCarve& v) { return reinterpret_cast<float*>(static_cast<char*>(c.ws) + v.off); };
+  float *ef32 = at(0), *nf32 = at(1);
+  int32_t rc;
+  if (fused & 1) rc = launch_chain_narrow_bf16(h, 0, p->edgefn, c.ef, de, c.nf, dn, c.gf, dg, c.ef_out, ef32, c.R, s, "k_rows_gemm_chain_e");
+  else rc = (wide & 1) ? launch_chain_wide_bf16(h, 0, p->edgefn, c.ef, de, c.nf, dn, c.gf, dg, c.ef_out, ef32, c.R, s, "k_rows_gemm_chain_e") : GNX_OK;
+  if (rc) return rc;
+  if (fused & 2) {
+    if ((rc = launch_chain_narrow_bf16(h, 1, p->nodefn, ef32, oe, c.nf, dn, c.gf, dg, c.nf_out, nf32, c.R, s, "k_rows_gemm_chain_n"))) return rc;
+  } else if (wide & 2) {
+    if ((rc = launch_chain_node_rows_bf16(h, ef32, oe, c.nf, dn, c.gf, dg, c.R, F(pl.w.n_in), s))) return rc;
+    if ((rc = launch_chain_wide_bf16(h, 1, p->nodefn, F(pl.w.n_in), pl.sh.k0[1], nullptr, 0, nullptr, 0, c.nf_out, nf32, c.R, s, "k_rows_gemm_chain_n"))) return rc;
+  }
+  if (og > 0 && ((fused | wide) & 4)) {
+    float* gf32 = at(2);
+    if (gf32 && (rc = launch_bf16_widen(c.gf, pl.st.n[2], gf32, s))) return rc;
+    if ((rc = launch_fn_input(h, 2, ef32, oe, nf32, on, gf32, dg, c.R, F(pl.w.g_in), s))) return rc;
+    if (fused & 4) rc = launch_chain_narrow_bf16(h, 2, p->graphfn, F(pl.w.g_in), pl.sh.k0[2], nullptr, 0, nullptr, 0, c.gf_out, nullptr, c.R, s, "k_rows_gemm_chain_g");
+    else rc = launch_chain_wide_bf16(h, 2, p->graphfn, F(pl.w.g_in), pl.sh.k0[2], nullptr, 0, nullptr, 0, c.gf_out, nullptr, c.R, s, "k_rows_gemm_chain_g");
+    if (rc) return rc;
+  }
+  return GNX_OK;
+}
+
 // One Chain forward call: validate and plan, the refusals that read nothing of the handle but its counts — NULL features, bf16 alignment — the
 // layout, the workspace refusal, the plan's tables; then the plan's form.  A staged bf16 call widens into the workspace, runs the fp32 launches on
 // the copies and rounds the outputs.
@@ -356,6 +398,7 @@ int32_t chain_fw_run(const ChainFwCall& c, bool narrow, bool train = false, bool
   if (!pl.bf16) return chain_forward_fp32(c, pl, cf(c.ef), cf(c.nf), cf(c.gf), static_cast<float*>(c.ef_out), static_cast<float*>(c.nf_out), static_cast<float*>(c.gf_out));
   if (pl.wave) return launch_chain_wave_bf16(c.h, *pl.p, pl.sh, c.ef, c.nf, c.gf, c.ef_out, c.nf_out, c.gf_out, static_cast<float*>(c.ws), c.R, s);
   if (pl.native) return chain_forward_native(c, pl);
+  if (pl.wide_native) return chain_forward_wide_native(c, pl);
   if ((rc = stage_widen(pl.st, c.ws, bufs, 0, 3, s))) return rc;
   auto at = [&](int i) { return pl.st.n[i] > 0 ? pl.st.at(c.ws, i) : nullptr; };
   if ((rc = chain_forward_fp32(c, pl, at(0), at(1), at(2), at(3), at(4), at(5)))) return rc;
@@ -423,6 +466,24 @@ size_t gnx_chain_block_forward_wide_workspace_bytes(const gnx_graphs* h, const g
 int32_t gnx_chain_block_forward_wide(const gnx_graphs* h, const gnx_chain_block_params* p, const float* ef, const float* nf, const float* gf, int64_t R,
                                      float* ef_out, float* nf_out, float* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
   return chain_fw_run(ChainFwCall{h, p, GNX_ELEM_F32, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true, false, false, true);
+}
+
+// gnx_chain_block_forward_wide_typed: the wide entry on fp32 or bf16 features.  _applies: F32 the wide mask; BF16 the wide mask where the native
+// form runs, 0 where the call is staged (a generic function) or is gnx_chain_block_forward_typed(narrow = 1) (no wide function)
+int32_t gnx_chain_block_forward_wide_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  if (!elem_ok(elem)) return 0;
+  const ChainFwPlan pl(h, p, R, elem, true, false, false, true);  // (the constructor reads the handle's counts alone; refused: 0)
+  return elem == GNX_ELEM_F32 || pl.wide_native ? (int32_t)pl.wide : 0;
+}
+
+size_t gnx_chain_block_forward_wide_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t R, int32_t elem) {
+  return elem_ok(elem) ? chain_fw_query(h, p, R, elem, true, false, false, true) : 0;
+}
+
+int32_t gnx_chain_block_forward_wide_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf, const void* gf,
+                                           int64_t R, void* ef_out, void* nf_out, void* gf_out, void* ws, size_t ws_bytes, uint32_t flags, void* stream) {
+  if (!elem_ok(elem)) return fail(GNX_ERR_INVALID_ARG, "elem must be GNX_ELEM_F32 or GNX_ELEM_BF16");
+  return chain_fw_run(ChainFwCall{h, p, elem, ef, nf, gf, R, ef_out, nf_out, gf_out, ws, ws_bytes, flags, stream}, true, false, false, true);
 }
 
 // gnx_chain_block_forward_wave_typed: the wave entry on fp32 or bf16 features; bf16 outside chain_wave_typed_takes: the typed entry with narrow = 1

@@ -214,6 +214,16 @@ inline unsigned chain_wide_mask(const ChainShape& s) {
   return m;
 }
 
+// ---- the wide form on bfloat16 features (gnx_chain_block_forward_wide_typed; gnx_chain_wide_bf16.hip) ----
+// The LDS plan is ChainWideShape as it stands: the gathered bf16 row of an edge function that opens with a Dense lives in the memory of the wave's
+// fp32 slice, which the first Dense overwrites only after its last chunk is read.  Its row stride, in bf16 elements: the 16-padded input width
+// plus 8.  Why: a lane's A fragment is 8 consecutive reduction steps of row c31 at element 16 c + 8 hi, i.e. 16 bytes — the stride must be a
+// multiple of 8 elements for that to be ONE aligned 16-byte read; and KP + 8 = 8 (2 j + 1) elements = 16 (2 j + 1) bytes is an ODD number of 16-byte
+// columns, so the sixteen consecutive lanes (one hi, sixteen rows) that a 16-byte LDS read serves per pass fall on sixteen different 16-byte
+// columns of the 64 four-byte banks (256 bytes): no conflict.  It fits: 32 (KP + 8) 2 bytes <= 32 (KP | 1) 4 bytes from KP = 6 on, and KP >= 16.
+// (The pass model — 16 consecutive lanes per pass — is the assumption; the stride was not measured against another.)
+constexpr int chain_wide_bf16_stride(int k_in) { return ceil16(k_in) + 8; }
+
 // ---- the wide form of the pullback (gnx_chain_block_backward_wide; gnx_chain_bw_wide.hip): one update function at matrix-core widths pulled
 //      back in one kernel ----
 constexpr int kChainBwWideLdsFloats = 16384;  // the weight chunk, the bias row and every wave's tape: 64 KB, the project's budget — two such
@@ -418,6 +428,33 @@ inline bool chain_fw_reads_wide_tables(const ChainShape& s, unsigned fused) {
   const bool rows_e = !(fused & 1) && (s.ch[0]->n_layers > 1 || s.ow[0] == 0);
   const bool rows_n = !(fused & 2) && s.ch[1]->n_layers > 1, rows_g = !(fused & 4) && s.ch[2]->n_layers > 1;
   return rows_e || rows_n || rows_g || (fused & 1);
+}
+
+// ---- the wide form on bfloat16 features (gnx_chain_block_forward_wide_typed), its native rule and workspace ----
+// The native rule of a bf16 call: some function is inside the wide rule, and every update function with an output and rows to run on is inside
+// the wide mask or the narrow fused mask.  Then each wide function is one k_chain_wide_bf16 launch and each narrow one a k_chain_mlp_bf16 launch
+// on the bf16 rows; nothing E-sized is widened or rounded by a pass of its own.  No class is cut from it for its own figures.  Measured
+// (profiles/chain_wide_bf16.json, whole calls, cache-cold, medians of 15, against the parent's gnx_chain_block_forward_typed(narrow = 1) on the
+// same bf16 tensors): the two-block class on the 512-graph 1M-edge batch, (10,5,3) [64,64,3]/[64,4]/[16,5] 0.372 against 0.429 ms (spreads 0.004 /
+// 0.023; the fp32 wide entry on fp32 tensors 0.371), (10,5,0) [64,3]/[64,4]/[32,5] 0.244 against 0.281 (0.003 / 0.006; fp32 0.252) — both beat the
+// parent by more than the larger spread; workspace 15.7 against 657 MiB.  On the one-graph 1M-edge batch 3.566 against 3.631 (0.077 / 0.079) and
+// 3.448 against 3.481 (0.071 / 0.085): inside the spread, not slower.  Before k_chain_wide_bf16 was held to three waves per SIMD (168 registers)
+// the same cases took 0.500 and 0.323 ms on the 512-graph batch: slower than the parent.  Not measured: the one-block class, a LayerNorm-first edge
+// function (the widening path), a narrow edge function in front of a wide node function, and the graph function's rows form on its own.
+inline bool chain_wide_typed_native(const ChainShape& s, unsigned fused, unsigned wide) {
+  return wide != 0 && chain_typed_native(s, fused | wide);
+}
+// ... and its workspace: chain_fw_layout with both masks (n_in for a wide node function, g_in; no block workspace, no e_buf / n_buf / g_buf of a
+// function that runs) and behind it the three carves of chain_native_counts (the unrounded ef' and nf' for the later functions of the call, the
+// widened gf for the graph function's input rows).  No copy of ef, nf or of an output: a wide node function's input rows are assembled from the
+// fp32 ef' and the bf16 nf / gf directly (k_chain_node_rows_bf16).
+inline size_t chain_wide_typed_native_bytes(const ChainShape& s, unsigned fused, unsigned wide, size_t ident_floats) {
+  ChainCarver c;
+  c.o = ChainCarver::up(chain_fw_layout(s, fused, ident_floats, 0, wide).total);
+  size_t counts[3];
+  chain_native_counts(s, counts);
+  for (int i = 0; i < 3; ++i) c.floats(counts[i]);
+  return c.o;
 }
 
 // The pullback (gnx_chain_block_backward: fused = 0; _narrow: the mask of CHAIN_RULE_BW).  A fused function keeps no per-layer outputs, no delta

@@ -187,6 +187,13 @@ int32_t launch_chain_narrow(const gnx_graphs* h, int entity, const gnx_chain& c,
 // asked chain_wide_takes (gnx_chain_plan.h)
 int32_t launch_chain_wide(const gnx_graphs* h, int entity, const gnx_chain& c, const float* in0, int d0, const float* in1, int d1, const float* in2, int d2,
                           float* out, int64_t R, hipStream_t s, const char* name);
+// ---- gnx_chain_wide_bf16.hip: the same on bf16 features (gnx_chain_block_forward_wide_typed's native form) ----
+// entity 0: in0 / in1 / in2 are bf16; 1, 2: in0 = the materialised fp32 input rows.  out: bf16 rows; out32: the same rows unrounded in fp32, or
+// nullptr.  The caller asked chain_wide_takes.
+int32_t launch_chain_wide_bf16(const gnx_graphs* h, int entity, const gnx_chain& c, const void* in0, int d0, const void* in1, int d1, const void* in2, int d2,
+                               void* out, float* out32, int64_t R, hipStream_t s, const char* name);
+// the input rows [R][N][de + dn + dg] of a wide node function of such a call: launch_fn_input's kind 1 from the fp32 ef' and the bf16 nf, gf
+int32_t launch_chain_node_rows_bf16(const gnx_graphs* h, const float* ef32, int de, const void* nf, int dn, const void* gf, int dg, int64_t R, float* out, hipStream_t s);
 // ---- gnx_chain_wave.hip: the edge and the node function of a Chain block in one wave-per-tile kernel, the graph function from its partial rows
 //      (gnx_chain_block_forward_wave).  The caller asked chain_wave_takes; sh: the shape of p; partials: chain_wave_partial_floats(sh, ...) floats ----
 int32_t launch_chain_wave(const gnx_graphs* h, const gnx_chain_block_params& p, const ChainShape& sh, const float* ef, const float* nf, const float* gf, float* ef_out,

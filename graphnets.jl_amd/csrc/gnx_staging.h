@@ -77,7 +77,7 @@ struct ChainPlan {
   const gnx_chain_block_params* p = nullptr;
   ChainShape sh{};
   unsigned fused = 0;
-  unsigned wide = 0;  // the functions k_chain_wide (gnx_chain_block_forward_wide) / k_chain_bw_wide (gnx_chain_block_backward_wide) runs: fp32, test mode, disjoint from `fused`
+  unsigned wide = 0;  // the functions k_chain_wide (gnx_chain_block_forward_wide) / k_chain_bw_wide (gnx_chain_block_backward_wide) runs: test mode, disjoint from `fused`; fp32 — and, the forward alone, bf16 (gnx_chain_block_forward_wide_typed)
   bool bf16 = false;
   Staging st{};                // a bf16 call: the fp32 carves behind the fp32 layout
   size_t base = 0, total = 0;  // the fp32 layout's total; what the entry's _workspace_bytes returns

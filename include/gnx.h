@@ -512,6 +512,34 @@ GNX_API size_t gnx_chain_block_forward_wave_typed_workspace_bytes(const gnx_grap
 GNX_API int32_t gnx_chain_block_forward_wave_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf,
                                                    const void* gf, int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace,
                                                    size_t workspace_bytes, uint32_t flags, void* stream);
+/* gnx_chain_block_forward_wide on float32 or bfloat16 features.  `elem` (GNX_ELEM_*) applies to the three feature inputs and the three outputs.
+ * GNX_ELEM_F32 IS gnx_chain_block_forward_wide: same validation, same workspace size, same bits, _applies its mask.  Any other elem than F32 /
+ * BF16: the call returns GNX_ERR_INVALID_ARG before any GPU work, the queries return 0.  A bf16 buffer must be 4-byte aligned (else
+ * GNX_ERR_INVALID_ARG before any GPU work); segments, rows and runs may start 2-byte aligned, which is all the kernels assume.
+ * GNX_ELEM_BF16, finite data, in every form: the three outputs are bit for bit to_bf16(gnx_chain_block_forward_wide on the exactly widened
+ * inputs), each element rounded to nearest even once; later functions of the call read the unrounded fp32 rows.
+ * Native form (_applies returns the wide mask, non-zero) — the wide mask is non-zero and every update function with a non-zero output width whose
+ * entity has rows is inside the wide mask or gnx_chain_block_forward_narrow_applies' mask.  A wide function is ONE launch of
+ * k_chain_wide_bf16 (csrc/gnx_chain_wide_bf16.hip): the fp32 kernel's work split, LDS plan and rule, unchanged; the edge form gathers ef, nf[src],
+ * nf[dst] and gf as bf16 (packed dwords where a pair is aligned, 16-bit loads at odd ends, no dword across a tensor's end), keeps the row in LDS
+ * as bf16 inside the wavefront's slice and runs the first Dense as three matrix instructions per 16 reduction steps instead of six (the row is
+ * its own high plane); the rows form reads fp32 input rows assembled from the unrounded ef' / nf' of the call; the output is stored once as bf16
+ * (dwords, 16-bit odd ends) and, where a later function reads it, unrounded as fp32 into the workspace.  A narrow function is one k_chain_mlp_bf16
+ * launch as in gnx_chain_block_forward_typed.  Workspace: gnx_chain_block_forward_wide_workspace_bytes' layout (a wide node function's N input
+ * rows, the graph function's G input rows) plus fp32 carves of ef' (if the node or graph function consumes it), nf' (if the graph function
+ * does) and the widened gf (graph function, dg > 0) — no copy of ef, of nf or of an output, no hidden-row buffer.
+ * Staged form (_applies returns 0) — the wide mask is non-zero and some function that runs is in neither mask: fp32 copies of the six tensors
+ * around gnx_chain_block_forward_wide's launches.
+ * No wide function (_applies returns 0): the call, its workspace size and its bits are gnx_chain_block_forward_typed(narrow = 1)'s.
+ * No class is cut from the native rule; see README.md ("Wide Chain blocks on bfloat16 features") for what was measured.
+ * The queries build the handle's tables (call them outside a stream capture); the call allocates nothing, does not synchronise and uses one
+ * stream.  Under the profiler the launches report as k_rows_gemm_chain_e / _n / _g.  Refusals as gnx_chain_block_forward's, the workspace one
+ * naming gnx_chain_block_forward_wide_typed_workspace_bytes() on bf16 features. */
+GNX_API int32_t gnx_chain_block_forward_wide_typed_applies(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API size_t gnx_chain_block_forward_wide_typed_workspace_bytes(const gnx_graphs* h, const gnx_chain_block_params* p, int64_t n_replicas, int32_t elem);
+GNX_API int32_t gnx_chain_block_forward_wide_typed(const gnx_graphs* h, const gnx_chain_block_params* p, int32_t elem, const void* ef, const void* nf,
+                                                   const void* gf, int64_t n_replicas, void* ef_out, void* nf_out, void* gf_out, void* workspace,
+                                                   size_t workspace_bytes, uint32_t flags, void* stream);
 
 /* ---- backward of the block: what a Zygote `rrule` / torch autograd function for (m::GNBlock)(x) needs.
  * Inputs: the forward's inputs (ef, nf, gf), its outputs (ef_out, nf_out, gf_out) and the upstream gradients with the

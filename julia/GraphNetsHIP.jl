@@ -870,26 +870,30 @@ function chain_device(m::ChainBlock, x; narrow::Bool=false, wave::Bool=false, wi
         g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, UInt32(0), STREAM[]))
     (graphs=g, ef=o[1], nf=o[2], gf=o[3])
 end
-function chain_device_wide(m::ChainBlock, x)
+# Through gnx_chain_block_forward_wide_typed: the shim's arrays are Float32, so it passes GNX_ELEM_F32 — then the call IS
+# gnx_chain_block_forward_wide (same workspace size, same bits); with bfloat16 device buffers the same argument list takes GNX_ELEM_BF16 and
+# each wide function gathers, keeps and stores the bf16 rows itself (include/gnx.h states the contract).
+function chain_device_wide(m::ChainBlock, x; elem::Int32=GNX_ELEM_F32)
     g::GNGraphBatch = x.graphs
     R = replicas(x.ef, x.nf, x.gf)
     keep = Any[]
     p = Ref(chain_params(m, keep))
     oe, on, og = outwidth(m.edgefn), outwidth(m.nodefn), outwidth(m.graphfn)
-    ws = workspace!(g, (:chain_wide, chainkey(m), R)) do
-        ccall((:gnx_chain_block_forward_wide_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), g.handle, p, R)
+    ws = workspace!(g, (:chain_wide, chainkey(m), R, elem)) do
+        ccall((:gnx_chain_block_forward_wide_typed_workspace_bytes, libgnx), Csize_t, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64, Int32), g.handle, p, R, elem)
     end
     o = (outarray(oe, nedges(g), R), outarray(on, nnodes(g), R), outarray(og, ngraphs(g), R))
-    GC.@preserve m keep x o ws check(ccall((:gnx_chain_block_forward_wide, libgnx), Int32,
-        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cvoid}, Csize_t, UInt32, Ptr{Cvoid}),
-        g.handle, p, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, UInt32(0), STREAM[]))
+    GC.@preserve m keep x o ws check(ccall((:gnx_chain_block_forward_wide_typed, libgnx), Int32,
+        (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, UInt32, Ptr{Cvoid}),
+        g.handle, p, elem, devptr(x.ef), devptr(x.nf), devptr(x.gf), R, devptr(o[1]), devptr(o[2]), devptr(o[3]), ws.ptr, ws.cap, UInt32(0), STREAM[]))
     (graphs=g, ef=o[1], nf=o[2], gf=o[3])
 end
-# which update functions gnx_chain_block_forward_wide runs in its matrix-core kernel on this batch: bit 0 edge, bit 1 node, bit 2 graph
-function chain_wide_applies(m::ChainBlock, x)
+# which update functions gnx_chain_block_forward_wide_typed runs in its matrix-core kernel on this batch with features of `elem`: bit 0 edge,
+# bit 1 node, bit 2 graph (GNX_ELEM_F32: gnx_chain_block_forward_wide's mask; GNX_ELEM_BF16: 0 unless the native form runs)
+function chain_wide_applies(m::ChainBlock, x; elem::Int32=GNX_ELEM_F32)
     keep = Any[]
     p = Ref(chain_params(m, keep))
-    GC.@preserve m keep ccall((:gnx_chain_block_forward_wide_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf))
+    GC.@preserve m keep ccall((:gnx_chain_block_forward_wide_typed_applies, libgnx), Int32, (Ptr{Cvoid}, Ptr{GnxChainBlockParams}, Int64, Int32), x.graphs.handle, p, replicas(x.ef, x.nf, x.gf), elem)
 end
 # Through gnx_chain_block_forward_wave_typed: the shim's arrays are Float32, so it passes GNX_ELEM_F32 — then the call IS
 # gnx_chain_block_forward_wave (same workspace size, same bits); with bfloat16 device buffers the same argument list takes GNX_ELEM_BF16 and

@@ -15,7 +15,14 @@ source form x one graph or several) has to meet on every case that reaches it to
 against gnx_chain_block_backward of the parent's library, all gradients wanted, on the same configs and batches; the class of a case is then
 what chain_bw_wide_takes has to keep.
 
+`--bf16`: the forward on bfloat16 features — gnx_chain_block_forward_wide_typed (csrc/gnx_chain_wide_bf16.hip; the switches `bf16_chain` +
+`wide_chain`) against the parent's route for the same call, gnx_chain_block_forward_typed(narrow = 1) of the parent's library, on the two blocks of
+BF16_CONFIGS and both batches; gnx_chain_block_forward_wide on the widened tensors is timed beside them for information.
+`beats_parent_beyond_spread`: wide median < parent median - max(the parent's spread, the wide entry's spread) — what the native rule
+(chain_wide_typed_native) has to meet on the 512-graph batch.
+
   python tools/chain_wide_timing.py [--samples 15] [--parent-root DIR] [--out profiles/chain_wide.json]
+  python tools/chain_wide_timing.py --bf16 [--samples 15] [--parent-root DIR] [--out profiles/chain_wide_bf16.json]
   python tools/chain_wide_timing.py --backward [--samples 15] [--parent-root DIR] [--out profiles/chain_bw_wide.json]
 """
 import argparse
@@ -31,6 +38,7 @@ CONFIGS = [((10, 5, 0), [64, 3], [64, 4], [32, 5]),
            ((10, 5, 3), [64, 64, 3], [64, 4], [16, 5]),
            ((10, 5, 3), [128, "ln", 128, 3], [128, 4], [5]),
            ((32, 32, 8), [128, 128, 32], [128, 32], [64, 8])]
+BF16_CONFIGS = [CONFIGS[1], CONFIGS[0]]
 
 
 def blocks(widths):
@@ -39,7 +47,33 @@ def blocks(widths):
     return 4 if nb == 3 else nb
 
 
+def one_case_bf16(a, gn, g, cfg, baseline_only):
+    """forms: "narrow" = gnx_chain_block_forward_typed(narrow = 1) on the bf16 tensors (the call the new entry stands in for), "wide" = the new
+    entry on them, "wide_fp32" = gnx_chain_block_forward_wide on their widening"""
+    import torch
+    F32, BF16 = gn._lib.ELEM_F32, gn._lib.ELEM_BF16
+    case = calls.chain_case(gn, g, cfg, dtype=torch.bfloat16, cot=False)
+    built = {"narrow": calls.build(gn, case, "chain", "forward", BF16, "gnx_chain_block_forward_typed", narrow=1)}
+    rec = dict(in_dims=list(cfg[0]), edge=cfg[1], node=cfg[2], graph=cfg[3], E=g.n_edges, N=g.n_nodes, G=g.n_graphs)
+    if not baseline_only:
+        rec["applies"] = calls.applies(gn, case, "gnx_chain_block_forward_wide_typed_applies", BF16)
+        rec["class"] = dict(blocks={n: blocks(w) for n, w, bit in (("edge", cfg[1], 1), ("node", cfg[2], 2), ("graph", cfg[3], 4)) if rec["applies"] & bit},
+                            graphs="one" if g.n_graphs == 1 else "several")
+        built["wide"] = calls.build(gn, case, "chain", "forward", BF16, ("wide_chain", "bf16_chain"))
+        built["wide_fp32"] = calls.build(gn, case, "chain", "forward", F32, ("wide_chain",), x=[None if t is None else t.float() for t in case.x])
+    ms = timing.cold_samples(torch, {k: c.f for k, c in built.items()}, a.samples, WARMUP)
+    rec.update(forms={k: timing.summary_samples(v) for k, v in ms.items()}, workspace_bytes={k: c.nbytes for k, c in built.items()})
+    if not baseline_only:
+        torch.cuda.synchronize()
+        rec["bits_equal_to_bf16_of_fp32_wide"] = all(u is None or torch.equal(u.view(torch.int16), v.to(torch.bfloat16).view(torch.int16))
+                                                     for u, v in zip(built["wide"].outs, built["wide_fp32"].outs))
+        rec["profiler_one_call"] = {k: timing.profiled_once(gn, torch, c.f) for k, c in built.items()}
+    return rec
+
+
 def one_case(a, gn, g, cfg, baseline_only):
+    if a.bf16:
+        return one_case_bf16(a, gn, g, cfg, baseline_only)
     import torch
     F32 = gn._lib.ELEM_F32
     way = "backward" if a.backward else "forward"
@@ -74,20 +108,23 @@ def run(a, parent=None, graphs=None, limit=None):
                               timing=timing.cold_timing(a.samples, WARMUP), measured=bool(parent), cases=[])
     get = timing.OneGraph(gn, graphs)
     cut = []
-    for i, (key, cfg) in enumerate([(key, cfg) for key in ("hetero512", "C2") for cfg in CONFIGS][:limit]):
+    stood_in = "narrow" if a.bf16 else "generic"  # the form of the parent's library the new entry stands in for
+    for i, (key, cfg) in enumerate([(key, cfg) for key in ("hetero512", "C2") for cfg in (BF16_CONFIGS if a.bf16 else CONFIGS)][:limit]):
         c = one_case(a, gn, get(key), cfg, a.baseline_only)
         c["graph_name"] = timing.GRAPHS[key][0]
         if not a.baseline_only:
             f = c["forms"]
-            line = f"{c['graph_name']} {cfg}: generic {f['generic']['median_ms']:.4f}   wide {f['wide']['median_ms']:.4f} ms   ws {c['workspace_bytes']['wide'] >> 20} / " \
-                   f"{c['workspace_bytes']['generic'] >> 20} MiB   applies {c['applies']}   class {c['class']}"
+            line = f"{c['graph_name']} {cfg}: {stood_in} {f[stood_in]['median_ms']:.4f}   wide {f['wide']['median_ms']:.4f} ms   ws {c['workspace_bytes']['wide'] >> 20} / " \
+                   f"{c['workspace_bytes'][stood_in] >> 20} MiB   applies {c['applies']}   class {c['class']}"
             if parent:
                 pc = parent[i]
                 assert pc["graph_name"] == c["graph_name"] and pc["in_dims"] == c["in_dims"] and pc["edge"] == c["edge"]
-                base = pc["forms"]["generic"]
+                base = pc["forms"][stood_in]
                 c["parent"] = dict(forms=pc["forms"], workspace_bytes=pc["workspace_bytes"])
                 c["wide_over_parent"] = f["wide"]["median_ms"] / base["median_ms"]
                 c["not_slower_beyond_spread"] = bool(f["wide"]["median_ms"] <= base["median_ms"] + base["spread_ms"])
+                if a.bf16:
+                    c["beats_parent_beyond_spread"] = bool(f["wide"]["median_ms"] < base["median_ms"] - max(base["spread_ms"], f["wide"]["spread_ms"]))
                 if not c["not_slower_beyond_spread"]:
                     cut.append(i)
                 out.res["slower_than_parent_beyond_spread"] = cut
@@ -103,12 +140,13 @@ def main():
     ap.add_argument("--root", default=HERE, help="the checkout whose package and library are timed")
     ap.add_argument("--baseline-only", action="store_true", help="time gnx_chain_block_forward (--backward: gnx_chain_block_backward) only and print one JSON line")
     ap.add_argument("--backward", action="store_true", help="time the pullbacks: gnx_chain_block_backward_wide against gnx_chain_block_backward")
+    ap.add_argument("--bf16", action="store_true", help="bfloat16 features: gnx_chain_block_forward_wide_typed against the parent's gnx_chain_block_forward_typed(narrow = 1)")
     ap.add_argument("--parent-root", default=None, help="a checkout of the parent commit, its library built")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     parent = None
     if a.parent_root:  # first, and in a process of its own: one library per process
-        parent = timing.parent_baseline(__file__, a.parent_root, ["--samples", a.samples] + (["--backward"] if a.backward else []), 500)["cases"]
+        parent = timing.parent_baseline(__file__, a.parent_root, ["--samples", a.samples] + (["--backward"] if a.backward else []) + (["--bf16"] if a.bf16 else []), 500)["cases"]
     timing.child_root(a.root)
     res = run(a, parent)
     if a.baseline_only:

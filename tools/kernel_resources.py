@@ -222,6 +222,17 @@ def _rec_chain_wide(f, res, twin):
     return rec
 
 
+def _rec_chain_wide_bf16(f, res, twin):
+    r, fp32 = res(), twin("chain_wide")["srcs"]
+    rec = dict(what="k_chain_wide_bf16<NB, SRC> per accumulator-block class and source form, each next to its fp32 twin's VGPRs (one text: "
+                    "csrc/gnx_chain_wide_kernel.h)" + REMARKS, box=BOX, lds_budget_bytes=f["LDS_BUDGET_BYTES"],
+               srcs={s: {str(nb): dict(r[s][nb], fp32_vgpr=fp32[s][str(nb)]["vgpr"]) for nb in f["NB"]} for s in f["SRCS"]})
+    rec["instantiations_with_scratch_or_static_lds"] = [f"{s}/{nb}" for s in f["SRCS"] for nb in f["NB"] if r[s][nb]["scratch"] or r[s][nb]["lds_static"]]
+    rec["instantiations_with_fewer_waves_per_simd_than_fp32"] = [f"{s}/{nb}" for s in f["SRCS"] for nb in f["NB"]
+                                                                 if r[s][nb]["waves_per_simd"] < fp32[s][str(nb)]["waves_per_simd"]]
+    return rec
+
+
 def _rec_chain_wave_bf16(f, res, twin):
     r, fp32 = res(), twin("chain_wave")["kernels"]
     names = f["KERNEL_NAMES"]
@@ -293,6 +304,10 @@ FAMILIES = {
     # the Chain forward at matrix-core widths: the weight chunk, the bias row and every wave's slice in LDS (kChainWideLdsFloats: gnx_chain_plan.h)
     "chain_wide": dict(file="gnx_chain_wide.hip", name=r"_ZN3gnx\d+k_chain_wideILi(\d+)ELi(\d+)EEEv", key=lambda m: (SRC[int(m.group(2))], int(m.group(1))),
                        fields=STATIC, record=_rec_chain_wide, NB=(1, 2), SRCS=("edge", "rows"), LDS_BUDGET_BYTES=4 * 16384),
+    # its bf16 twin: the same LDS plan — the gathered bf16 row of the edge form lives inside the wave's slice
+    "chain_wide_bf16": dict(file="gnx_chain_wide_bf16.hip", name=r"_ZN3gnx\d+k_chain_wide_bf16ILi(\d+)ELi(\d+)EEEv",
+                            key=lambda m: (SRC[int(m.group(2))], int(m.group(1))), fields=STATIC, record=_rec_chain_wide_bf16, NB=(1, 2),
+                            SRCS=("edge", "rows"), LDS_BUDGET_BYTES=4 * 16384),
     # its pullback: the weight chunk, the bias row and every wave's tape in LDS (kChainBwWideLdsFloats: gnx_chain_plan.h)
     "chain_bw_wide": dict(file="gnx_chain_bw_wide.hip", name=r"_ZN3gnx\d+k_chain_bw_wideILi(\d+)ELi(\d+)EEEv", key=lambda m: (SRC[int(m.group(2))], int(m.group(1))),
                           fields=STATIC, record=_rec_chain_bw_wide, NB=(1, 2), SRCS=("edge", "rows"), LDS_BUDGET_BYTES=4 * 16384),
